@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: HMC leapfrog steps/s + achieved HBM GB/s of the G sweep.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--extra]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+Prints one JSON line: `value` (steps/s), `ms_per_step` (milliseconds per timed leapfrog step; K of them are
+timed, after W untimed warm-up steps).  --dump-outputs DIR writes what the timed steps computed as .npy files
+(same arguments, same inputs: two builds compare output for output); --extra adds the other BASELINE
+configurations to the line.
 
 A "step" is one leapfrog step of the hot path (hmc.py:117-152): momentum update with the
 gradient 2 Aw^T r + alpha grad R, position update with clamp-and-reflect, and the forward
@@ -251,12 +256,41 @@ def cpu_baseline(mesh, xp, yp, zp, dobs, target_s=16.0, max_cells=10000):
 #: (e.g. sharded and unsharded) be compared through their JSON lines
 LAST_STATE = {"U": None}
 
+#: --dump-outputs: all files of one run together stay below this (npy headers included)
+DUMP_BYTES = 64_000_000
 
-def run_single_chain(eng, M, Sigma, dt, L, steps, warmup, seed, barrier=lambda: None):
+
+def dump_outputs(folder, arrays, budget=DUMP_BYTES):
+    """Write every array as float64 `folder/<name>.npy`.  When the whole set would exceed `budget` bytes,
+    each array of more than 1 MB keeps a fixed sample of its last axis instead (indices drawn once from
+    default_rng(0), sorted, written as `<name>_index.npy`), sized so that the set fits.  Returns
+    {name: shape written}."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    header = 128 * 2 * len(arrays)                      # an npy header per file (and per index file)
+    large = {k: a for k, a in arrays.items() if a.nbytes > (1 << 20) and a.ndim >= 1}
+    total = sum(a.nbytes for a in arrays.values())
+    if total + header > budget and large:
+        room = budget - header - sum(a.nbytes for k, a in arrays.items() if k not in large)
+        share = room / sum(a.nbytes for a in large.values())
+        for k, a in large.items():
+            n = a.shape[-1]
+            rows = a.size // n
+            keep = max(1, min(n, int(share * a.nbytes) // (8 * (rows + 1))))
+            idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+            arrays[k] = np.ascontiguousarray(a[..., idx])
+            arrays[k + "_index"] = idx.astype(np.float64)
+    os.makedirs(folder, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(folder, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
+def run_single_chain(eng, M, Sigma, dt, L, steps, warmup, seed, barrier=lambda: None, record=None):
     """One chain through the sampler's own path (Engine.run_chain), momenta drawn in the reference's
     RNG order (legacy global generator, hmc.py:95,164).  Returns (elapsed_s, accepted, trajectories,
     profile).  Every draw happens inside the timed region, overlapped with the GPU where the pipeline
-    manages to."""
+    manages to.  `record` (a dict, or None): receives the timed trajectories' "accepted" flags and "out5"
+    rows, as on_result hands them over."""
     np.random.seed(seed)
     from gravinv3dhmc_amd.inversion.rng import LegacyDraws
 
@@ -269,7 +303,7 @@ def run_single_chain(eng, M, Sigma, dt, L, steps, warmup, seed, barrier=lambda: 
             return plan, draws()
         return plan, LegacyDraws(M, (L, L), Sigma, fixed_L=plan)   # the same stream, drawn by the library
 
-    def run(prepared):
+    def run(prepared, rec=None):
         plan, gen = prepared
         stat = {"acc": 0, "traj": 0}
 
@@ -277,6 +311,9 @@ def run_single_chain(eng, M, Sigma, dt, L, steps, warmup, seed, barrier=lambda: 
             stat["acc"] += int(acc)
             stat["traj"] += 1
             LAST_STATE["U"] = [float(v) for v in out5[:3]]
+            if rec is not None:
+                rec["accepted"].append(bool(acc))
+                rec["out5"].append(np.array(out5, dtype=np.float64))
 
         try:
             eng.run_chain(gen, dt, on_result, overlap=True)   # as the sampler calls it (inversion/hmc.py)
@@ -288,11 +325,13 @@ def run_single_chain(eng, M, Sigma, dt, L, steps, warmup, seed, barrier=lambda: 
     if warmup > 0:
         run(prepare(warmup))
     prepared = prepare(steps)
+    if record is not None:
+        record.update(accepted=[], out5=[])
     eng.synchronize()
     barrier()
     eng.profile_enable(True)
     t0 = time.perf_counter()
-    naccept, ntraj = run(prepared)
+    naccept, ntraj = run(prepared, record)
     eng.synchronize()
     elapsed = time.perf_counter() - t0
     barrier()
@@ -695,8 +734,17 @@ def main():
     ap.add_argument("--seed", type=int, default=100,
                     help="np.random.seed of the chain of rank 0; rank r takes seed + r (hmc.py:369)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true",
-                    help="skip the extra block (C1, north_star's target configuration) of the default line")
+    ap.add_argument("--extra", action="store_true",
+                    help="default workload only: add the `extra` block -- C1 (north_star's target configuration) in "
+                         "this process and every EXTRA_RUNS configuration in a child process, each with its own "
+                         "step counts -- and `config_values` to the line (minutes of GPU time, a line of ~10 KB)")
+    ap.add_argument("--no-extra", action="store_true", help=argparse.SUPPRESS)   # (the default; kept for old commands)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float64): x, the chain "
+                         "state after the last timed trajectory (one row per chain with --chains-per-gpu > 1), dsyn, "
+                         "its synthetic data (one chain only), out5 (U, U_data, U_model, ... of every timed "
+                         "trajectory) and accepted (1.0 / 0.0 per timed trajectory); at most 64 MB in all (larger "
+                         "arrays: a fixed sample of the last axis, indices in <name>_index.npy); written by rank 0")
     ap.add_argument("--shard", action="store_true",
                     help="ONE chain whose cells (columns of G) are split over the ranks' GPUs, "
                          "all-reduce of the forward partial per step (strong scaling); default "
@@ -709,6 +757,8 @@ def main():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="all ranks share GPU 0 (rehearsal of the N>1 launch path on a 1-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.batch_team != "auto":
         os.environ["GRAVHMC_BATCH_TEAM"] = "1" if args.batch_team == "on" else "0"
 
@@ -788,6 +838,7 @@ def main():
     Sigma, dt, L = 0.001, extra["dt"], args.traj_len
     CPG = args.chains_per_gpu
     barrier = ranks.barrier
+    record = {} if args.dump_outputs else None        # the timed trajectories' results, for --dump-outputs
     if CPG > 1:
         # ---- several chains per GPU: one RandomState per chain (seed 100 + global chain index,
         # the stream np.random.seed gives the reference's rank), lock-step rounds of L steps
@@ -827,15 +878,18 @@ def main():
                         self.queue[k].extend(self.draws[k].take_ring(n))   # (L, row address, u, ring index)
                 list(draw_pool.map(one, range(CPG)))
 
-            def run(self):
+            def run(self, record=None):
+                """record (dict or None): per chain, the "accepted" flags and "out5" rows of its trajectories."""
                 queue, nacc, done = self.queue, 0, [0] * CPG
+                if record is not None:
+                    record.update(accepted=[[] for _ in range(CPG)], out5=[[] for _ in range(CPG)])
                 clk = HOST_LOOP
                 while min(done) < len(self.plan):
                     t_a = time.perf_counter()
                     T = min(Tmax, min(len(q) for q in queue))
                     if T == 0:                             # nothing left to offer: finish what is in flight
-                        acc, _, _, ns, nd = eng.batch_run([[] for _ in range(CPG)], dt, np.zeros((CPG, 0)),
-                                                          np.zeros((CPG, 0)), carry=True)
+                        acc, out5, _, ns, nd = eng.batch_run([[] for _ in range(CPG)], dt, np.zeros((CPG, 0)),
+                                                             np.zeros((CPG, 0)), carry=True)
                     else:
                         entered = threading.Event()
                         fut = pool.submit(eng.batch_run, [[tr[1] for tr in q[:T]] for q in queue], dt,
@@ -847,7 +901,7 @@ def main():
                                 break
                         self.top_up()                      # (the offers after this one, while the GPU runs)
                         t_b = time.perf_counter()
-                        acc, _, _, ns, nd = fut.result()
+                        acc, out5, _, ns, nd = fut.result()
                         clk["draw_s"] += t_b - t_a
                         clk["wait_for_gpu_call_s"] += time.perf_counter() - t_b
                         clk["calls"] += 1
@@ -855,6 +909,9 @@ def main():
                         del queue[k][:int(ns[k])]
                         done[k] += int(nd[k])
                         nacc += int(acc[k, :int(nd[k])].sum())
+                        if record is not None:
+                            record["accepted"][k].extend(acc[k, :int(nd[k])])
+                            record["out5"][k].extend(out5[k, :int(nd[k])])
                 return nacc, len(self.plan)
 
             def release(self):
@@ -873,7 +930,7 @@ def main():
         barrier()
         eng.profile_enable(True)
         t0 = time.perf_counter()
-        naccept, ntraj = rounds.run()
+        naccept, ntraj = rounds.run(record)
         eng.synchronize()
         elapsed = time.perf_counter() - t0
         rounds.release()
@@ -882,10 +939,22 @@ def main():
         # the reference's RNG stream (legacy global generator), one chain per rank (a sharded chain
         # shares one stream)
         elapsed, naccept, ntraj, prof = run_single_chain(eng, M, Sigma, dt, L, args.steps, args.warmup,
-                                                         args.seed if args.shard else args.seed + rank, barrier)
+                                                         args.seed if args.shard else args.seed + rank, barrier,
+                                                         record)
     if CPG > 1:
         prof = eng.profile_read()
         eng.profile_enable(False)
+    dumped = None
+    if record is not None:
+        # (every rank fetches: a sharded engine gathers the chain state with a collective)
+        if CPG > 1:
+            outputs = {"x": np.stack([eng.batch_get_x(c) for c in range(CPG)]),
+                       "out5": np.array(record["out5"]), "accepted": np.array(record["accepted"])}
+        else:
+            outputs = {"x": eng.chain_get_x(), "dsyn": eng.chain_get_dsyn(),
+                       "out5": np.array(record["out5"]).reshape(-1, 5), "accepted": np.array(record["accepted"])}
+        if rank == 0:
+            dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, outputs)}
     # what a pure read of the same matrix reaches on this device (outside the timed region)
     stream_gbps = None
     if not args.matrix_free and not args.shift_invariant and int(N) * int(M) * 8 >= (1 << 30):
@@ -1106,8 +1175,10 @@ def main():
                 line["cpu_baseline"] = {"error": "%s: %s" % (type(e).__name__, e)}
     eng.close()
     if rank == 0:
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if world == 1 and args.workload == "c2_uniform_100x100x50" and CPG == 1 and not args.shard \
-                and not args.matrix_free and not args.no_extra:
+                and not args.matrix_free and args.extra:
             # north_star's target configuration next to the headline workload, same process
             try:
                 line["extra"] = {"c1_uniform_20x30x10": c1_block(dev, not args.no_cpu_baseline)}

@@ -60,6 +60,45 @@ def prism_cases(R):
     print("prism_cases", K.shape, "finite:", np.isfinite(K).all())
 
 
+def _ref_prism_columns(R, xp, yp, zp, cells):
+    """Columns of the reference's _prism.gz for the given cells, scaled as prism.py does."""
+    K = np.zeros((xp.size, len(cells)))
+    for c, b in enumerate(cells):
+        res, k1 = np.zeros(xp.size), np.zeros(xp.size)
+        R._prism.gz(xp, yp, zp, *[float(v) for v in b], 1.0, res, k1)
+        K[:, c] = k1
+    K *= R.constants.G * R.constants.SI2MGAL
+    return K
+
+
+def prism_random(R):
+    """_prism.gz on random observations around three cells (corners and a face included)."""
+    rng = np.random.default_rng(9)
+    n = 200
+    xp, yp, zp = rng.uniform(-500, 2500, n), rng.uniform(-500, 3500, n), -rng.uniform(0, 50, n)
+    xp[:5], yp[:5], zp[:5] = [0.0, 100.0, 50.0, 0.0, 100.0], [0.0, 0.0, 50.0, 100.0, 100.0], 0.0   # corners / face
+    cells = np.array([[0, 100, 0, 100, 0, 100], [300, 400, 500, 700, 50, 250], [-50, 50, -30, 70, 10, 60.5]], float)
+    K = _ref_prism_columns(R, xp, yp, zp, cells)
+    assert np.array_equal(oracle.prism_gz_kernel(xp, yp, zp, cells), K), "oracle prism kernel differs from reference"
+    np.savez_compressed(os.path.join(GOLD, "prism_random.npz"), xp=xp, yp=yp, zp=zp, cells=cells, K=K)
+    print("prism_random", K.shape)
+
+
+def c1_prism_columns(R):
+    """300 random columns of C1's 600 x 6000 kernel through _prism.gz: the column indices and the digest of
+    the block (600 x 300 doubles are too large to store for a bit-for-bit comparison)."""
+    from gravinv3dhmc_amd import mesher
+    yp, xp = [a.ravel() for a in np.meshgrid(np.linspace(0, 3000, 30), np.linspace(0, 2000, 20))]
+    zp = np.zeros_like(xp)
+    bounds = mesher.PrismMesh((0, 2000, 0, 3000, 0, 1000), (100, 100, 100)).cell_bounds()
+    cols = np.random.default_rng(3).choice(bounds.shape[0], 300, replace=False)
+    K = _ref_prism_columns(R, xp, yp, zp, bounds[cols])
+    assert np.array_equal(oracle.prism_gz_kernel(xp, yp, zp, bounds[cols]), K), "oracle prism kernel differs from reference"
+    np.savez_compressed(os.path.join(GOLD, "c1_prism_columns.npz"), cols=cols, digest=np.array(oracle.kernel_digest(K)),
+                        absmax=np.abs(K).max())
+    print("c1_prism_columns", K.shape, oracle.kernel_digest(K))
+
+
 def c1_spot(R):
     """Config C1 (uniformgrid singlecube) kernel spot values + noise-free forward."""
     mesh = _quiet(R.mesher.PrismMesh, (0, 2000, 0, 3000, 0, 1000), (100, 100, 100))
@@ -446,6 +485,8 @@ def main():
         return 0
     mesher_cases(R)
     prism_cases(R)
+    prism_random(R)
+    c1_prism_columns(R)
     xp, yp, zp, _ = c1_spot(R)
     tess_cases(R)
     potential_small(R)

@@ -1,11 +1,8 @@
 """CPU suite: the oracle against the golden vectors generated from the reference
 (oracle/make_golden.py) and against the reference's committed run logs."""
 import numpy as np
-import pytest
 
-import os
-
-from conftest import ROOT, gold
+from conftest import gold
 from helpers import relmax
 from oracle import oracle
 
@@ -336,35 +333,10 @@ def test_bootstrap_port_with_wavelet_forward_is_the_reference_formulation():
 
 
 def test_oracle_prism_kernel_is_the_reference_kernel_bit_for_bit():
-    """Where oracle/_ref/_prism*.so exists (the reference's gravmag/_prism.pyx compiled unmodified by
-    oracle/build_ref.py): the C restatement against `_prism.gz` itself on random and singular geometries."""
-    import glob
-    import importlib.machinery
-    import importlib.util
+    """The C restatement against the reference's own `_prism.gz` (gravmag/_prism.pyx compiled unmodified by
+    oracle/build_ref.py) on random and singular geometries: prism_random.npz holds its output
+    (oracle/make_golden.py)."""
     from oracle import oracle as orc
-    sos = glob.glob(os.path.join(ROOT, "oracle", "_ref", "_prism*.so"))
-    if not sos:
-        pytest.skip("oracle/_ref/_prism*.so not built (no /root/reference at build time)")
-    had = hasattr(np, "float")
-    if not had:
-        np.float = float
-    try:
-        loader = importlib.machinery.ExtensionFileLoader("_prism", sos[0])
-        spec = importlib.util.spec_from_file_location("_prism", sos[0], loader=loader)
-        ref = importlib.util.module_from_spec(spec)
-        loader.exec_module(ref)
-        rng = np.random.default_rng(9)
-        n = 200
-        xp, yp, zp = rng.uniform(-500, 2500, n), rng.uniform(-500, 3500, n), -rng.uniform(0, 50, n)
-        xp[:5], yp[:5], zp[:5] = [0.0, 100.0, 50.0, 0.0, 100.0], [0.0, 0.0, 50.0, 100.0, 100.0], 0.0   # corners / face
-        cells = np.array([[0, 100, 0, 100, 0, 100], [300, 400, 500, 700, 50, 250], [-50, 50, -30, 70, 10, 60.5]], float)
-        K = np.zeros((n, len(cells)))
-        for c, b in enumerate(cells):
-            res, k1 = np.zeros(n), np.zeros(n)
-            ref.gz(xp, yp, zp, *[float(v) for v in b], 1.0, res, k1)
-            K[:, c] = k1
-        K *= 0.00000006673 * 100000.0
-        assert np.array_equal(orc.prism_gz_kernel(xp, yp, zp, cells), K)
-    finally:
-        if not had:
-            del np.float
+    g = gold("prism_random.npz")
+    assert g["K"].shape == (200, 3)
+    assert np.array_equal(orc.prism_gz_kernel(g["xp"], g["yp"], g["zp"], g["cells"]), g["K"])
