@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("GRAVHMC_LIB") or os.path.join(_HERE, "libgravhmc.so")
 
 GH_OK, GH_ERR_ARG, GH_ERR_HIP, GH_ERR_NOMEM, GH_ERR_OVERFLOW, GH_ERR_UNSUPPORTED, GH_ERR_COMM = \
     0, -1, -2, -3, -4, -5, -6
-CELL_PRISM, CELL_TESSEROID = 0, 1
+CELL_PRISM, CELL_TESSEROID, CELL_PRISM_TF = 0, 1, 2
 REG_KINDS = {"Damping": 0, "Smoothness": 1, "MS": 2, "TV": 3}
 
 _dp = C.POINTER(C.c_double)
@@ -30,6 +30,8 @@ PROTOTYPES = {
     "gh_synchronize": (C.c_int, [_ctx]),
     "gh_set_obs": (C.c_int, [_ctx, _dp, _dp, _dp]),
     "gh_set_cells": (C.c_int, [_ctx, _dp, C.c_int, C.c_double]),
+    "gh_set_cells_tf": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
+    "gh_tf_result": (C.c_int, [_ctx, _dp, _dp]),
     "gh_set_matrix_free": (C.c_int, [_ctx, C.c_int]),
     "gh_set_matrix_free_exact": (C.c_int, [_ctx, C.c_int]),
     "gh_batch_fused_stats": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64),

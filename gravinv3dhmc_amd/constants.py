@@ -1,7 +1,7 @@
 """Physical constants and unit conversions used on the hot path.
 
-Values are the reference's (constants.py:29,32,34,44) and must stay bit-identical:
-lengths in m, density in g/cm^3, gz in mGal.
+Values are the reference's (constants.py:29,32,34,37,41,44) and must stay bit-identical:
+lengths in m, density in g/cm^3, gz in mGal, magnetization in A/m, total field in uT.
 """
 #: gravitational constant for density in g/cm^3 (constants.py:34) -- used by prism AND tesseroid gz
 G = 0.00000006673
@@ -11,3 +11,8 @@ Gs = 0.00000000006673
 SI2MGAL = 100000.0
 #: mean Earth radius in m (constants.py:44)
 MEAN_EARTH_RADIUS = 6378137.0
+#: mu_0 / (4 pi) in H/m (constants.py:37)
+CM = 10. ** (-7)
+#: the reference's tesla conversion (constants.py:41): 10**6, i.e. T -> uT, not the 10**9 (T -> nT) its
+#: docstring names.  CM * T2NT == 0.09999999999999999 scales the total-field kernel (gravmag.prism.tf).
+T2NT = 10. ** (6)

@@ -174,6 +174,56 @@ int gh_set_cells(gh_ctx *c, const double *bounds6, int kind, double ratio)
     return GH_OK;
 }
 
+int gh_set_cells_tf(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
+{
+    if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_tf: null pointer");
+    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(fz))
+        return fail(c, GH_ERR_ARG, "gh_set_cells_tf: the field direction must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
+    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
+    c->cell_kind = GH_CELL_PRISM_TF;
+    c->tf_dir[0] = fx;
+    c->tf_dir[1] = fy;
+    c->tf_dir[2] = fz;
+    TRY(dalloc(c, &c->tf_dir_d, 3));
+    TRY(h2d(c, c->tf_dir_d, c->tf_dir, 3));
+    c->have_cells = true;
+    return GH_OK;
+}
+
+int gh_tf_result(gh_ctx *c, const double *mag3, double *result)
+{
+    if (!c || !mag3 || !result) return fail(c, GH_ERR_ARG, "gh_tf_result: null pointer");
+    TRY(need(c, c->have_obs && c->have_cells, "gh_tf_result: call gh_set_obs and gh_set_cells_tf first"));
+    if (c->cell_kind != GH_CELL_PRISM_TF)
+        return fail(c, GH_ERR_ARG, "gh_tf_result: the cells are not a total-field magnetic model (gh_set_cells_tf)");
+    if (c->sh.kind != 0)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_tf_result: the magnetic field's result runs on an unsharded context");
+    HIPCHK(c, hipSetDevice(c->device));
+    double *dmag = nullptr, *dres = nullptr;
+    HIPCHK(c, hipMalloc((void **)&dmag, sizeof(double) * 3 * (size_t)std::max<int64_t>(c->M, 1)));
+    if (hipMalloc((void **)&dres, sizeof(double) * (size_t)std::max<int64_t>(c->N, 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        hipFree(dmag);
+        return fail(c, GH_ERR_NOMEM, "gh_tf_result: device allocation of %lld doubles failed", (long long)c->N);
+    }
+    hipError_t e = hipMemcpyAsync(dmag, mag3, sizeof(double) * 3 * (size_t)c->M, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        prism_tf_result_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(
+            c->obs[0], c->obs[1], c->obs[2], c->bounds, dmag, c->N, c->M, c->tf_dir[0], c->tf_dir[1], c->tf_dir[2],
+            dres);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(result, dres, sizeof(double) * (size_t)c->N, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipFree(dmag);
+    hipFree(dres);
+    HIPCHK(c, e);
+    return GH_OK;
+}
+
 int gh_set_matrix_free(gh_ctx *c, int enable)
 {
     if (!c) return GH_ERR_ARG;
@@ -295,7 +345,14 @@ int gh_build_G(gh_ctx *c)
             c->obs[0], c->obs[1], c->obs[2], c->bounds, c->N, c->M, c->ld, c->G);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else {
+    } else if (c->cell_kind == GH_CELL_PRISM_TF) {
+        const int64_t blocks = std::min<int64_t>((total + 255) / 256, 1 << 22);
+        prism_tf_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(
+            c->obs[0], c->obs[1], c->obs[2], c->bounds, c->N, c->M, c->ld, c->tf_dir[0], c->tf_dir[1],
+            c->tf_dir[2], c->G);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else if (c->cell_kind == GH_CELL_TESSEROID) {
         double *conv = nullptr;
         int *err_cell = nullptr;
         TessStats *stats = nullptr;
@@ -325,6 +382,8 @@ int gh_build_G(gh_ctx *c)
             if (v != 0) c->warn_cells += 1;
         c->leaves = (int64_t)hs.leaves;
         if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
+    } else {
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: unknown cell kind %d", c->cell_kind);
     }
     c->have_G = true;
     c->weighted = false;
@@ -401,8 +460,8 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
         lonsym_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
             lonsym_geom(c), c->ls->a_of, c->ls->m_of, weightfactor, c->wm);
     } else if (c->mf) {
-        mf_colnorm_kernel<<<dim3((unsigned)((c->M + 3) / 4)), dim3(256), 0, c->stream>>>(mf_geom(c), weightfactor,
-                                                                                        c->wm);
+        hipLaunchKernelGGL(c->cell_kind == GH_CELL_PRISM_TF ? mf_colnorm_kernel<true> : mf_colnorm_kernel<false>,
+                           dim3((unsigned)((c->M + 3) / 4)), dim3(256), 0, c->stream, mf_geom(c), weightfactor, c->wm);
     } else if (shard_rows(c)) {
         // row blocks: a column's norm spans the ranks -- local sums of squares, all-reduce, then the power and
         // the scaling of the local rows
@@ -729,8 +788,9 @@ int gh_compress_wavelet(gh_ctx *c, int dims, const int shape3[3], double thr, in
                 // no stored kernel: the rows are evaluated (twice over the two passes: setup path)
                 for (int64_t r0 = 0; r0 < nr; r0 += 32768) {
                     const int64_t rn = std::min<int64_t>(32768, nr - r0);
-                    mf_rows_kernel<<<dim3((unsigned)((M + 255) / 256), (unsigned)rn), dim3(256), 0, c->stream>>>(
-                        mf_geom(c), c->wm, i0 + r0, rn, X + r0 * M);
+                    hipLaunchKernelGGL(c->cell_kind == GH_CELL_PRISM_TF ? mf_rows_kernel<true> : mf_rows_kernel<false>,
+                                       dim3((unsigned)((M + 255) / 256), (unsigned)rn), dim3(256), 0, c->stream,
+                                       mf_geom(c), (const double *)c->wm, i0 + r0, rn, X + r0 * M);
                 }
             } else {
                 gather_rows_kernel<<<dim3((unsigned)((M + 31) / 32), (unsigned)((nr + 31) / 32)), dim3(256), 0,
@@ -1249,6 +1309,8 @@ static int kids_make(gh_ctx *c, int C, const double *x0s, const double *low, con
         c->kids.push_back(k);
         k->cell_kind = c->cell_kind;
         k->ratio = c->ratio;
+        for (int q = 0; q < 3; ++q) k->tf_dir[q] = c->tf_dir[q];
+        k->tf_dir_d = c->tf_dir_d;
         k->have_obs = k->have_cells = k->have_G = true;
         k->mf = true;
         k->weighted = c->weighted;
@@ -1366,6 +1428,9 @@ int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const 
              "gh_batch_init: needs the kernel (gh_build_G / gh_upload_G), gh_set_data and gh_set_reg"));
     if (c->sh.kind != 0)
         return fail(c, GH_ERR_UNSUPPORTED, "batched chains run on the unsharded kernel only");
+    if (c->mf && c->cell_kind == GH_CELL_PRISM_TF)
+        return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of the magnetic field (total field, "
+                                           "GH_CELL_PRISM_TF) are not supported: store the kernel or run single chains");
     HIPCHK(c, hipSetDevice(c->device));
     if (lonsym_on(c)) {
         // (the light contexts of the chains share the tables, not a compressed forward operator)

@@ -6,9 +6,11 @@
 
 // ------------------------------------------------ batched chains on the matrix-free kernel (mfbatch.hip.h)
 
+// (GH_CELL_PRISM_TF has no batch kernels: gh_batch_init and mfb_plan refuse a matrix-free magnetic context
+// before any of these is asked for)
 static int mfb_kind(const gh_ctx *c)
 {
-    if (c->cell_kind != GH_CELL_TESSEROID) return 0;
+    if (c->cell_kind == GH_CELL_PRISM) return 0;
     if (!c->mf_near_on) return 1;
     if (c->mf_exact) return 2;
     return (c->obs_h_uniform && env_int("GRAVHMC_MFB_RU", 1) != 0) ? 4 : 3;  // 4: one observation height
@@ -227,6 +229,8 @@ static int mft_failed(gh_ctx *c, bool *failed)
 static int mfb_plan(gh_ctx *c)
 {
     gh_ctx::Batch &b = c->bt;
+    if (c->cell_kind == GH_CELL_PRISM_TF)
+        return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of the magnetic field are not supported");
     const int64_t ntiles = (c->M + 15) / 16;
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(mfb_adj_for(c)), MFB_LDS_ADJ));
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(mfb_fwd_for(c)), MFB_LDS_FWD));

@@ -188,6 +188,7 @@ static MfGeom mf_geom(const gh_ctx *c)
     }
     g.bounds6 = c->bounds;
     g.ratio = c->ratio;
+    if (c->cell_kind == GH_CELL_PRISM_TF) g.o3 = c->tf_dir_d;
     return g;
 }
 
@@ -205,7 +206,8 @@ static mf_fused_fn mf_fused_for_kind(int T, int ept)
 
 static mf_fused_fn mf_fused_for(const gh_ctx *c)
 {
-    if (c->cell_kind != GH_CELL_TESSEROID) return mf_fused_for_kind<0>(c->mf_T, c->mf_EPT);
+    if (c->cell_kind == GH_CELL_PRISM) return mf_fused_for_kind<0>(c->mf_T, c->mf_EPT);
+    if (c->cell_kind == GH_CELL_PRISM_TF) return mf_fused_for_kind<5>(c->mf_T, c->mf_EPT);
     if (!c->mf_near_on) return mf_fused_for_kind<1>(c->mf_T, c->mf_EPT);
     if (c->mf_exact) return mf_fused_for_kind<2>(c->mf_T, c->mf_EPT);
     if (!c->mf_pipe) return mf_fused_for_kind<3>(c->mf_T, c->mf_EPT);
@@ -346,12 +348,15 @@ static int launch_mf(gh_ctx *c, SweepArgs &a)
                            wm, c->cell_kind == GH_CELL_TESSEROID ? c->mf_cellc : nullptr, near,
                            c->prof ? c->mf_stats : nullptr);
     } else {
+        const bool tf = c->cell_kind == GH_CELL_PRISM_TF;
         if (a.mode & SW_ADJ)
-            mf_adjoint_kernel<<<dim3((unsigned)((c->M + 3) / 4)), dim3(256), 0, c->stream>>>(g, a, wm);
+            hipLaunchKernelGGL(tf ? mf_adjoint_kernel<true> : mf_adjoint_kernel<false>, dim3((unsigned)((c->M + 3) / 4)),
+                               dim3(256), 0, c->stream, g, a, wm);
         if (a.mode & SW_FWD) {
             const double *x = (a.mode & SW_UPD) ? a.x_out : a.x_in;
-            mf_forward_kernel<<<dim3((unsigned)((c->ld + 255) / 256), (unsigned)c->grid), dim3(256), 0,
-                                c->stream>>>(g, x, wm, c->mf_cells_per_chunk, c->ld, a.slab);
+            hipLaunchKernelGGL(tf ? mf_forward_kernel<true> : mf_forward_kernel<false>,
+                               dim3((unsigned)((c->ld + 255) / 256), (unsigned)c->grid), dim3(256), 0, c->stream, g, x,
+                               wm, c->mf_cells_per_chunk, c->ld, a.slab);
         }
     }
     if (timed) {

@@ -1093,6 +1093,113 @@ prism_gz_kernel(const double *__restrict__ xp, const double *__restrict__ yp,
     }
 }
 
+// CM * T2NT of the reference (constants.py:37,41): 10**-7 * 10**6 rounds to 0.09999999999999999; entries in
+// uT per A/m of magnetization along the field (T2NT is 10**6 there, not the 10**9 of an nT scale)
+#define TF_SCALE (1e-7 * 1e6)
+
+// The six second derivatives of 1/r at one corner (_prism.pyx:52-78: kernelxx, xy, xz, yy, yz, zz)
+__device__ __forceinline__ void prism_tf_corner(double dx, double dy, double dz, double r, double &v1, double &v2,
+                                                double &v3, double &v4, double &v5, double &v6)
+{
+#pragma clang fp contract(off)
+    v1 = -safe_atan2_d(dz * dy, dx * r);
+    v2 = safe_log_d(dz + r);
+    v3 = safe_log_d(dy + r);
+    v4 = -safe_atan2_d(dz * dx, dy * r);
+    v5 = safe_log_d(dx + r);
+    v6 = -safe_atan2_d(dx * dy, dz * r);
+}
+
+// One (observation, prism) entry of the total-field anomaly for a unit magnetization along the field
+// direction (fx, fy, fz) = dircos(inc, dec): CM*T2NT * sum over the 8 corners of (-1)^(i+j+k) f.(V f) in the
+// reference's order -- bk = V f first, then f.bk (_prism.pyx:80-113, prism.py:665-733), not the shorter
+// quadratic form, which rounds differently.
+__device__ __forceinline__ double prism_tf_entry(double px, double py, double pz, const double *b, double fx,
+                                                 double fy, double fz)
+{
+#pragma clang fp contract(off)
+    const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double dz = Z[k] - pz;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const double dy = Y[j] - py;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const double dx = X[i] - px;
+                const double r = sqrt(dx * dx + dy * dy + dz * dz);
+                double v1, v2, v3, v4, v5, v6;
+                prism_tf_corner(dx, dy, dz, r, v1, v2, v3, v4, v5, v6);
+                const double bxk = v1 * fx + v2 * fy + v3 * fz;
+                const double byk = v2 * fx + v4 * fy + v5 * fz;
+                const double bzk = v3 * fx + v5 * fy + v6 * fz;
+                const double kern = fx * bxk + fy * byk + fz * bzk;
+                const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
+                acc += sign * kern;
+            }
+        }
+    }
+    return acc * TF_SCALE;
+}
+
+// Dense assembly of the total-field kernel: the layout of prism_gz_kernel (obs fastest, zero padding rows)
+__global__ void __launch_bounds__(256)
+prism_tf_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
+                const double *__restrict__ bounds6, int64_t N, int64_t M, int64_t ld, double fx, double fy,
+                double fz, double *__restrict__ G)
+{
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ld * M;
+         idx += (int64_t)gridDim.x * 256) {
+        const int64_t c = idx / ld, l = idx - c * ld;
+        G[idx] = (l < N) ? prism_tf_entry(xp[l], yp[l], zp[l], bounds6 + 6 * c, fx, fy, fz) : 0.0;
+    }
+}
+
+// prism.tf's `result` (prism.py:665-733): one thread per observation, the cells in mesh order, ONE sum per
+// observation over every corner of every cell of (-1)^(i+j+k) f.(V m_c) with the cell's magnetization m_c =
+// mag3[3c .. 3c+2], scaled once at the end -- the reference's accumulation order.
+__global__ void __launch_bounds__(256)
+prism_tf_result_kernel(const double *__restrict__ xp, const double *__restrict__ yp,
+                       const double *__restrict__ zp, const double *__restrict__ bounds6,
+                       const double *__restrict__ mag3, int64_t N, int64_t M, double fx, double fy, double fz,
+                       double *__restrict__ res)
+{
+#pragma clang fp contract(off)
+    const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= N) return;
+    const double px = xp[l], py = yp[l], pz = zp[l];
+    double acc = 0.0;
+    for (int64_t c = 0; c < M; ++c) {
+        const double *b = bounds6 + 6 * c;
+        const double mx = mag3[3 * c], my = mag3[3 * c + 1], mz = mag3[3 * c + 2];
+        const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const double dz = Z[k] - pz;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const double dy = Y[j] - py;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const double dx = X[i] - px;
+                    const double r = sqrt(dx * dx + dy * dy + dz * dz);
+                    double v1, v2, v3, v4, v5, v6;
+                prism_tf_corner(dx, dy, dz, r, v1, v2, v3, v4, v5, v6);
+                    const double bx = v1 * mx + v2 * my + v3 * mz;
+                    const double by = v2 * mx + v4 * my + v5 * mz;
+                    const double bz = v3 * mx + v5 * my + v6 * mz;
+                    const double kern = fx * bx + fy * by + fz * bz;
+                    const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
+                    acc += sign * kern;
+                }
+            }
+        }
+    }
+    res[l] = acc * TF_SCALE;
+}
+
 constexpr int TESS_STACK = 100;  // tesseroid.py:79
 
 struct TessStats {
@@ -1611,17 +1718,22 @@ ring_stats_kernel(const double *ring, int64_t M, int nvalid, double *mean, doubl
 // wm computed by mf_colnorm_kernel.
 
 struct MfGeom {
-    int kind;  // 0 prism, 1 tesseroid
+    int kind;  // 0 prism, 1 tesseroid, 2 prism total field (GH_CELL_*)
     double radius_u;  // tesseroids, every observation at one height: its radius R + h (else 0)
     int64_t N, M;
-    const double *o0, *o1, *o2, *o3;  // prism: x,y,z,-  tesseroid: lon_r, sinlat, coslat, radius
+    const double *o0, *o1, *o2, *o3;  // prism: x,y,z,- (total field: x,y,z,(fx,fy,fz))  tesseroid: lon_r, sinlat, coslat, radius
     const double *o4, *o5;            // tesseroid: sin lon, cos lon (fast leaf)
     const double *bounds6;
     double ratio;
 };
 
+// TF: the prisms' total-field entry (GH_CELL_PRISM_TF; the field direction is the three doubles at g.o3),
+// else g.kind 0 prism gz / 1 tesseroid.  The generic passes below are templated on it so that the gz and
+// tesseroid instantiations keep their register budget.
+template <bool TF>
 __device__ __forceinline__ double mf_entry(const MfGeom &g, int64_t i, const double *b)
 {
+    if (TF) return prism_tf_entry(g.o0[i], g.o1[i], g.o2[i], b, g.o3[0], g.o3[1], g.o3[2]);
     if (g.kind == 0) return prism_entry(g.o0[i], g.o1[i], g.o2[i], b);
     int err = 0;
     unsigned long long nl = 0;
@@ -1630,6 +1742,7 @@ __device__ __forceinline__ double mf_entry(const MfGeom &g, int64_t i, const dou
 }
 
 // wm_j = (sum_i K_ij^2)^wf: one wave per cell, lanes over observations
+template <bool TF>
 __global__ void __launch_bounds__(256) mf_colnorm_kernel(MfGeom g, double wf, double *wm)
 {
     const int lane = threadIdx.x & 63;
@@ -1638,7 +1751,7 @@ __global__ void __launch_bounds__(256) mf_colnorm_kernel(MfGeom g, double wf, do
     const double *b = g.bounds6 + 6 * j;
     double s = 0.0;
     for (int64_t i = lane; i < g.N; i += 64) {
-        const double k = mf_entry(g, i, b);
+        const double k = mf_entry<TF>(g, i, b);
         s += k * k;
     }
     s = wave_allreduce_sum(s);
@@ -1647,6 +1760,7 @@ __global__ void __launch_bounds__(256) mf_colnorm_kernel(MfGeom g, double wf, do
 
 // Adjoint + leapfrog update for one cell per wave: the matrix-free counterpart of the ADJ /
 // UPD / PFIN / GOUT / SPEC part of sweep_kernel (same arithmetic per column).
+template <bool TF>
 __global__ void __launch_bounds__(256) mf_adjoint_kernel(MfGeom g, SweepArgs a, const double *wm)
 {
     __shared__ double red[4];
@@ -1657,7 +1771,7 @@ __global__ void __launch_bounds__(256) mf_adjoint_kernel(MfGeom g, SweepArgs a, 
     if (j < g.M) {
         const double *b = g.bounds6 + 6 * j;
         double s = 0.0;
-        for (int64_t i = lane; i < g.N; i += 64) s += mf_entry(g, i, b) * a.r[i];
+        for (int64_t i = lane; i < g.N; i += 64) s += mf_entry<TF>(g, i, b) * a.r[i];
         s = wave_allreduce_sum(s);
         const double w = wm[j];
         s = (w != 0.0) ? s * (1.0 / w) : s;
@@ -1695,6 +1809,7 @@ __global__ void __launch_bounds__(256) mf_adjoint_kernel(MfGeom g, SweepArgs a, 
 }
 
 // Forward partials: thread = observation, blockIdx.y = chunk of cells; slab[chunk][i]
+template <bool TF>
 __global__ void __launch_bounds__(256)
 mf_forward_kernel(MfGeom g, const double *x, const double *wm, int64_t cells_per_chunk, int64_t ld,
                   double *slab)
@@ -1709,7 +1824,7 @@ mf_forward_kernel(MfGeom g, const double *x, const double *wm, int64_t cells_per
         for (int64_t j = j0; j < j1; ++j) {
             const double w = wm ? wm[j] : 1.0;
             const double xs = (w != 0.0) ? x[j] * (1.0 / w) : x[j];
-            acc += mf_entry(g, i, g.bounds6 + 6 * j) * xs;
+            acc += mf_entry<TF>(g, i, g.bounds6 + 6 * j) * xs;
         }
     }
     slab[(int64_t)blockIdx.y * ld + i] = acc;
@@ -1720,13 +1835,14 @@ mf_forward_kernel(MfGeom g, const double *x, const double *wm, int64_t cells_per
 // out[nrows][M] (what gather_rows_kernel copies out of a stored G): the wavelet compressor's input
 // (compressor3D.kernelcompressor transforms whole rows).  Entries by the generic engines (mf_entry: the
 // values the dense assembly stores), divided by the column's weight as the in-place weighting does.
+template <bool TF>
 __global__ void __launch_bounds__(256)
 mf_rows_kernel(MfGeom g, const double *__restrict__ wm, int64_t i0, int64_t nrows, double *__restrict__ out)
 {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t i = blockIdx.y;
     if (j >= g.M || i >= nrows) return;
-    const double k = mf_entry(g, i0 + i, g.bounds6 + 6 * j);
+    const double k = mf_entry<TF>(g, i0 + i, g.bounds6 + 6 * j);
     const double w = wm ? wm[j] : 1.0;
     out[i * g.M + j] = (w != 0.0) ? k * (1.0 / w) : k;
 }
@@ -2048,8 +2164,8 @@ struct MfStats {
 
 // T threads per workgroup, EPT rows per thread (row of slot k: t + k*T): T*EPT >= ld; KIND: 0 prisms,
 // 1 tesseroids with the subdivision inside the pass, 2 / 3 tesseroids with the near-field table and the
-// exact-order / the fast root leaf (separate kernels: the prism entry's log/atan2 and the tesseroid entry's trigonometry would
-// otherwise share one register budget).
+// exact-order / the fast root leaf, 5 prisms' total field (separate kernels: the prism entry's log/atan2 and the
+// tesseroid entry's trigonometry would otherwise share one register budget; 4 is taken by mfbatch.hip.h's kinds).
 // LDS: T*EPT doubles (the column) + 2 x (T/64 + 8) doubles (ping-pong slots of the dot).
 template <int T, int EPT, int KIND>
 __global__ void __launch_bounds__(T)
@@ -2064,15 +2180,18 @@ mf_fused_kernel(MfGeom g, SweepArgs a, const double *__restrict__ wm, const doub
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int mode = a.mode;
     const int64_t N = g.N;
+    constexpr bool TABLE = KIND == 2 || KIND == 3;  // tesseroids with the near-field table
     const int ept = (int)((a.ld + T - 1) / T);  // slots in use (<= EPT)
+    // (KIND 5: the field direction, the same for every entry)
+    const double fx = KIND == 5 ? g.o3[0] : 0.0, fy = KIND == 5 ? g.o3[1] : 0.0, fz = KIND == 5 ? g.o3[2] : 0.0;
     double dacc[EPT];
 #pragma unroll
     for (int k = 0; k < EPT; ++k) dacc[k] = 0.0;
     double pp = 0.0;
     unsigned nleaf = 0, nent = 0;
     // (table forms: a thread's rows of r are the same for every column -- kept in registers)
-    double rr[KIND >= 2 ? EPT : 1];
-    if (KIND >= 2) {
+    double rr[TABLE ? EPT : 1];
+    if (TABLE) {
 #pragma unroll
         for (int k = 0; k < EPT; ++k) {
             const int64_t i = tid + (int64_t)k * T;
@@ -2136,7 +2255,7 @@ mf_fused_kernel(MfGeom g, SweepArgs a, const double *__restrict__ wm, const doub
                 Ks[(size_t)k * T + tid] = v;
             }
         }
-        if (KIND >= 2) {
+        if (TABLE) {
             const int64_t q0 = near.ptr[j], q1 = near.ptr[j + 1];
             if (q1 > q0) {
                 __syncthreads();
@@ -2156,6 +2275,9 @@ mf_fused_kernel(MfGeom g, SweepArgs a, const double *__restrict__ wm, const doub
                 if (i < N) {
                     if (KIND == 0) {
                         v = prism_entry(g.o0[i], g.o1[i], g.o2[i], b);
+                        nleaf += 1;
+                    } else if (KIND == 5) {
+                        v = prism_tf_entry(g.o0[i], g.o1[i], g.o2[i], b, fx, fy, fz);
                         nleaf += 1;
                     } else {
                         v = tess_entry_cc(g.o0[i], g.o1[i], g.o2[i], g.o3[i], cc, b, g.ratio, nleaf);
@@ -2224,7 +2346,7 @@ mf_fused_kernel(MfGeom g, SweepArgs a, const double *__restrict__ wm, const doub
         }
     }
     if (stats) {
-        unsigned long long e = nent, l = (KIND >= 2) ? nent : nleaf;  // (KIND 2, 3: one root leaf per entry)
+        unsigned long long e = nent, l = TABLE ? nent : nleaf;  // (KIND 2, 3: one root leaf per entry)
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
             e += __shfl_xor(e, off, WAVE);

@@ -91,11 +91,29 @@ class Engine(object):
             raise ValueError("Input arrays xp, yp, and zp must have same length!")
         self._chk(self._lib.gh_set_obs(self._h, ptr(a), ptr(b), ptr(c)))
 
-    def set_cells(self, bounds6, kind, ratio=1.6):
+    def set_cells(self, bounds6, kind, ratio=1.6, direction=None):
+        """kind CELL_PRISM / CELL_TESSEROID (ratio: the tesseroid distance-size ratio), or CELL_PRISM_TF with
+        direction = (fx, fy, fz), the unit vector of the regional field (utils.dircos(inc, dec))."""
         b = f64(bounds6)
         if b.shape != (self.M, 6):
             raise ValueError("bounds table must be (M, 6)")
+        if int(kind) == _lib.CELL_PRISM_TF:
+            if direction is None or len(direction) != 3:
+                raise ValueError("the magnetic (total-field) kernel needs direction = (fx, fy, fz)")
+            fx, fy, fz = (float(v) for v in direction)
+            self._chk(self._lib.gh_set_cells_tf(self._h, ptr(b), fx, fy, fz))
+            return
         self._chk(self._lib.gh_set_cells(self._h, ptr(b), int(kind), float(ratio)))
+
+    def tf_result(self, mag3):
+        """Total-field anomaly (uT) of the CELL_PRISM_TF cells magnetized with mag3[M, 3] (A/m), in the
+        reference's accumulation order (gh_tf_result); needs no G."""
+        m = f64(mag3)
+        if m.shape != (self.M, 3):
+            raise ValueError("magnetization must be (M, 3)")
+        out = np.empty(self.N)
+        self._chk(self._lib.gh_tf_result(self._h, ptr(m), ptr(out)))
+        return out
 
     def set_matrix_free(self, on=True, exact=None):
         """Never store G.  exact (tesseroids): True = a far pair's GLQ leaf in the reference's operation

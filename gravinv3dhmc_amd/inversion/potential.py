@@ -14,7 +14,7 @@ import time
 import numpy as np
 from scipy.sparse import coo_matrix
 
-from .. import _lib, mesher
+from .. import _lib, mesher, utils
 from ..engine import DeviceMatrix, Engine
 
 
@@ -36,7 +36,7 @@ def _diag(values):
 
 
 class GravMagModule(object):
-    """Gravity inversion model: mesh + sensitivity matrix + potential, on one MI355X.
+    """Gravity / magnetic inversion model: mesh + sensitivity matrix + potential, on one MI355X.
 
     Parameters are the reference's (potential.py:35-58):
 
@@ -48,6 +48,9 @@ class GravMagModule(object):
     * mratio: geometric growth of dz; mseg / mdivisionsection: piecewise dz.
     * weightfactor: exponent of the column-norm sensitivity weighting (0.5 = 2-norm).
     * wavelet: False, '1D' or '3D' (compressed forward operator).
+    * field: "gravity" (gz, mGal per g/cm^3) or "magnetic" (cartesian only: the total-field anomaly in uT
+      per A/m of magnetization along the regional field of mangle = (inclination, declination) in degrees,
+      gravmag.prism.tf).
     * mtopo=(x, y, topography) keyword: carve the mesh with a topography surface.
     * device: GPU ordinal (extension; the reference has no such argument).
     * shard: a `dist.Ranks` object: the cells of ONE model are split in column blocks over the
@@ -89,12 +92,13 @@ class GravMagModule(object):
         self.device = device
         self._say = print if verbose else (lambda *a, **k: None)
 
-        if field != "gravity" or coordinate not in ("cartesian", "spherical"):
-            if field == "magnetic" and coordinate in ("cartesian", "spherical"):
-                raise NotImplementedError(
-                    "magnetic kernels are outside the accelerated hot path (gravity gz only)")
+        if field not in ("gravity", "magnetic") or coordinate not in ("cartesian", "spherical"):
             raise ValueError("Please choose coordinate from(cartesian, spherical) and field "
                              "from(gravity, magnetic)!")
+        if field == "magnetic" and coordinate == "spherical":
+            # (the reference's branch is `pass`, then a NameError on the undefined mesh: potential.py:106-108)
+            raise NotImplementedError("the magnetic field on tesseroids (coordinate='spherical') is not supported")
+        magnetic = field == "magnetic"
         if wavelet not in (False, None, '1D', '3D'):
             raise ValueError("wavelet must be False, '1D' or '3D'")
         self._say("Calculating {} field in {} coordinate.".format(field, coordinate))
@@ -108,7 +112,12 @@ class GravMagModule(object):
         for _key, value in kwargs.items():  # mtopo=(x, y, topography)  (potential.py:92-96)
             self.topocarve = True
             self.mask = mesh.carvetopo(value[0], value[1], value[2])
-        mesh.addprop('density', np.zeros(mesh.size))
+        if magnetic:
+            # (potential.py:139: zero magnetization along the field; the reference's magnetic branch always
+            # builds PrismMesh and ignores mseg (potential.py:131) -- mseg is honoured here as for gravity)
+            mesh.addprop('magnetization', utils.ang2vec(np.zeros(mesh.size), self.inc, self.dec))
+        else:
+            mesh.addprop('density', np.zeros(mesh.size))
         self.mesh = mesh
 
         bounds = mesh.cell_bounds(active_only=True)
@@ -141,6 +150,8 @@ class GravMagModule(object):
         if spherical:
             self._say("Number of effective tesseroids", bounds.shape[0])
             eng.set_cells(bounds, _lib.CELL_TESSEROID, 1.6)
+        elif magnetic:
+            eng.set_cells(bounds, _lib.CELL_PRISM_TF, direction=utils.dircos(self.inc, self.dec))
         else:
             eng.set_cells(bounds, _lib.CELL_PRISM)
         eng.build_G()
@@ -148,9 +159,12 @@ class GravMagModule(object):
             import warnings
             from ..gravmag.tesseroid import _WARN_DIVIDE
             warnings.warn(_WARN_DIVIDE, RuntimeWarning)
-        if not spherical:
-            self._say("kernel.shape", (N, bounds.shape[0]))
-        self._say("End of calculate kernel:%.6f s" % (time.time() - start))
+        if magnetic:
+            self._say("End of calculate kernel:", time.time() - start)   # (potential.py:149)
+        else:
+            if not spherical:
+                self._say("kernel.shape", (N, bounds.shape[0]))
+            self._say("End of calculate kernel:%.6f s" % (time.time() - start))
         self._engine = eng
 
         self.mshape = mesh.shape

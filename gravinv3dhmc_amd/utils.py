@@ -2,7 +2,7 @@
 
 `rho2carve` / `carve2rho` (utils.py:714-749): move between the full-mesh cell order and the
 vector of active (uncarved) cells; `regular` (utils.py:114-151): observation grid with x slow,
-y fast.  Vectorised restatements (the reference's `regular` no longer runs under numpy >= 2,
+y fast; `dircos` / `ang2vec`: the regional field's direction and magnetization vectors.  Vectorised restatements (the reference's `regular` no longer runs under numpy >= 2,
 SURVEY section 2 #11)."""
 import numpy as np
 
@@ -37,6 +37,21 @@ def regular(area, shape, z=None):
     if z is not None:
         out.append(z * np.ones(nx * ny, dtype=np.float64))
     return out
+
+
+def dircos(inc, dec):
+    """Unit vector [x, y, z] (x North, y East, z Down) of inclination `inc` (positive down) and
+    declination `dec` (from North), both in degrees (utils.py:448-474; the same expressions, so the
+    same bits)."""
+    rad = np.pi / 180.
+    cinc = np.cos(rad * inc)
+    return [cinc * np.cos(rad * dec), cinc * np.sin(rad * dec), np.sin(rad * inc)]
+
+
+def ang2vec(intensity, inc, dec):
+    """Vectors of magnitude `intensity` along (inc, dec): shape (3,) for a scalar intensity,
+    (n, 3) for n intensities (utils.py:420-446)."""
+    return np.transpose([intensity * c for c in dircos(inc, dec)])
 
 
 _FMT_BUF = [None, 0]

@@ -71,7 +71,8 @@ typedef enum {
     GH_ERR_COMM = -6      /* collective layer error */
 } gh_status;
 
-enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1 };
+/* GH_CELL_PRISM_TF: prisms, total-field magnetic anomaly (set with gh_set_cells_tf, not gh_set_cells) */
+enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2 };
 /* potential.py:827-836 `regulization` strings */
 enum { GH_REG_DAMPING = 0, GH_REG_SMOOTHNESS = 1, GH_REG_MS = 2, GH_REG_TV = 3 };
 
@@ -94,6 +95,19 @@ int gh_set_obs(gh_ctx *ctx, const double *a, const double *b, const double *c);
  * w,e,s,n,top,bottom (tesseroid); `ratio` is the tesseroid distance-size ratio
  * (tesseroid.py:77, 1.6 for gz), ignored for prisms. */
 int gh_set_cells(gh_ctx *ctx, const double *bounds6, int kind, double ratio);
+/* Prisms of a total-field magnetic model (GH_CELL_PRISM_TF), M x 6 row-major x1,x2,y1,y2,z1,z2 in mesh
+ * order, with the unit vector (fx, fy, fz) = dircos(inc, dec) of the regional field (utils.py:448-474).
+ * Entry (i, j) is the total-field anomaly at observation i of prism j magnetized with 1 A/m along the
+ * field, in uT (prism.py:665-733 with pmag = 1: CM * T2NT = 10**-7 * 10**6, constants.py:37,41).  The dense
+ * assembly, the weighting, every stored-kernel path and the matrix-free passes (fused and two-pass, the
+ * wavelet rows) run on it; the matrix-free batch of chains and the shift-invariant store refuse it with
+ * GH_ERR_UNSUPPORTED. */
+int gh_set_cells_tf(gh_ctx *ctx, const double *bounds6, double fx, double fy, double fz);
+/* prism.tf's `result` on a GH_CELL_PRISM_TF context (needs gh_set_obs / gh_set_cells_tf, not G):
+ * mag3 is the magnetization (mx, my, mz) in A/m of each of the M cells, M x 3 row-major; result[N]
+ * in uT, accumulated corner by corner, cell by cell in mesh order into one sum per observation and
+ * scaled once, as the reference does. */
+int gh_tf_result(gh_ctx *ctx, const double *mag3, double *result);
 /* Matrix-free mode (call before gh_build_G): the kernel matrix is never stored; the prism /
  * tesseroid entries are re-evaluated where they are needed.  With N <= 16384 observations a
  * leapfrog step evaluates every entry ONCE (a workgroup keeps a cell's column on the chip between
