@@ -14,7 +14,12 @@ LIB_PATH = os.environ.get("GRAVHMC_LIB") or os.path.join(_HERE, "libgravhmc.so")
 
 GH_OK, GH_ERR_ARG, GH_ERR_HIP, GH_ERR_NOMEM, GH_ERR_OVERFLOW, GH_ERR_UNSUPPORTED, GH_ERR_COMM = \
     0, -1, -2, -3, -4, -5, -6
-CELL_PRISM, CELL_TESSEROID, CELL_PRISM_TF = 0, 1, 2
+CELL_PRISM, CELL_TESSEROID, CELL_PRISM_TF, CELL_PRISM_COMP = 0, 1, 2, 3
+#: the gravity fields of prisms (GH_COMP_*, gh_set_cells_prism)
+COMP_POTENTIAL, COMP_GEOID, COMP_GX, COMP_GY, COMP_GZ, COMP_GXX, COMP_GXY, COMP_GXZ, COMP_GYY, COMP_GYZ, COMP_GZZ = \
+    range(11)
+COMPONENTS = {"potential": COMP_POTENTIAL, "geoid": COMP_GEOID, "gx": COMP_GX, "gy": COMP_GY, "gz": COMP_GZ,
+              "gxx": COMP_GXX, "gxy": COMP_GXY, "gxz": COMP_GXZ, "gyy": COMP_GYY, "gyz": COMP_GYZ, "gzz": COMP_GZZ}
 REG_KINDS = {"Damping": 0, "Smoothness": 1, "MS": 2, "TV": 3}
 
 _dp = C.POINTER(C.c_double)
@@ -32,6 +37,8 @@ PROTOTYPES = {
     "gh_set_cells": (C.c_int, [_ctx, _dp, C.c_int, C.c_double]),
     "gh_set_cells_tf": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
     "gh_tf_result": (C.c_int, [_ctx, _dp, _dp]),
+    "gh_set_cells_prism": (C.c_int, [_ctx, _dp, C.c_int]),
+    "gh_prism_result": (C.c_int, [_ctx, _dp, _dp]),
     "gh_set_matrix_free": (C.c_int, [_ctx, C.c_int]),
     "gh_set_matrix_free_exact": (C.c_int, [_ctx, C.c_int]),
     "gh_batch_fused_stats": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64),

@@ -31,6 +31,11 @@
 #include <vector>
 
 using namespace ghk;
+static_assert(COMP_POTENTIAL == GH_COMP_POTENTIAL && COMP_GEOID == GH_COMP_GEOID && COMP_GX == GH_COMP_GX &&
+                  COMP_GY == GH_COMP_GY && COMP_GZ == GH_COMP_GZ && COMP_GXX == GH_COMP_GXX && COMP_GXY == GH_COMP_GXY &&
+                  COMP_GXZ == GH_COMP_GXZ && COMP_GYY == GH_COMP_GYY && COMP_GYZ == GH_COMP_GYZ &&
+                  COMP_GZZ == GH_COMP_GZZ,
+              "the kernels' component numbers are the C ABI's GH_COMP_*");
 
 #include "host_ctx.h"
 #include "host_sweep.h"
@@ -224,6 +229,55 @@ int gh_tf_result(gh_ctx *c, const double *mag3, double *result)
     return GH_OK;
 }
 
+int gh_set_cells_prism(gh_ctx *c, const double *bounds6, int component)
+{
+    if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_prism: null pointer");
+    if (component < GH_COMP_POTENTIAL || component > GH_COMP_GZZ)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_prism: component %d is not one of GH_COMP_POTENTIAL (0) .. GH_COMP_GZZ (10)",
+                    component);
+    // gz is the prism kind of gh_set_cells: the same context, the same kernels, the same bits
+    if (component == GH_COMP_GZ) return gh_set_cells(c, bounds6, GH_CELL_PRISM, 1.6);
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
+    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
+    c->cell_kind = GH_CELL_PRISM_COMP;
+    c->comp = component;
+    c->have_cells = true;
+    return GH_OK;
+}
+
+int gh_prism_result(gh_ctx *c, const double *dens, double *result)
+{
+    if (!c || !dens || !result) return fail(c, GH_ERR_ARG, "gh_prism_result: null pointer");
+    TRY(need(c, c->have_obs && c->have_cells, "gh_prism_result: call gh_set_obs and gh_set_cells_prism first"));
+    if (c->cell_kind != GH_CELL_PRISM && c->cell_kind != GH_CELL_PRISM_COMP)
+        return fail(c, GH_ERR_ARG, "gh_prism_result: the cells are not a prism density model (gh_set_cells_prism)");
+    if (c->sh.kind != 0)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_prism_result: the prism result runs on an unsharded context");
+    const int comp = c->cell_kind == GH_CELL_PRISM_COMP ? c->comp : GH_COMP_GZ;
+    HIPCHK(c, hipSetDevice(c->device));
+    double *ddens = nullptr, *dres = nullptr;
+    HIPCHK(c, hipMalloc((void **)&ddens, sizeof(double) * (size_t)std::max<int64_t>(c->M, 1)));
+    if (hipMalloc((void **)&dres, sizeof(double) * (size_t)std::max<int64_t>(c->N, 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        hipFree(ddens);
+        return fail(c, GH_ERR_NOMEM, "gh_prism_result: device allocation of %lld doubles failed", (long long)c->N);
+    }
+    hipError_t e = hipMemcpyAsync(ddens, dens, sizeof(double) * (size_t)c->M, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        prism_comp_result_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(
+            c->obs[0], c->obs[1], c->obs[2], c->bounds, ddens, c->N, c->M, comp, dres);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(result, dres, sizeof(double) * (size_t)c->N, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipFree(ddens);
+    hipFree(dres);
+    HIPCHK(c, e);
+    return GH_OK;
+}
+
 int gh_set_matrix_free(gh_ctx *c, int enable)
 {
     if (!c) return GH_ERR_ARG;
@@ -352,6 +406,23 @@ int gh_build_G(gh_ctx *c)
             c->tf_dir[2], c->G);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else if (c->cell_kind == GH_CELL_PRISM_COMP) {
+        typedef void (*comp_fn)(const double *, const double *, const double *, const double *, int64_t, int64_t,
+                                int64_t, double *);
+        // (indexed by GH_COMP_*; gz is a GH_CELL_PRISM context)
+        static const comp_fn fns[] = {prism_comp_kernel<GH_COMP_POTENTIAL>, prism_comp_kernel<GH_COMP_GEOID>,
+                                      prism_comp_kernel<GH_COMP_GX>,        prism_comp_kernel<GH_COMP_GY>,
+                                      nullptr,                              prism_comp_kernel<GH_COMP_GXX>,
+                                      prism_comp_kernel<GH_COMP_GXY>,       prism_comp_kernel<GH_COMP_GXZ>,
+                                      prism_comp_kernel<GH_COMP_GYY>,       prism_comp_kernel<GH_COMP_GYZ>,
+                                      prism_comp_kernel<GH_COMP_GZZ>};
+        if (c->comp < 0 || c->comp > GH_COMP_GZZ || !fns[c->comp])
+            return fail(c, GH_ERR_ARG, "gh_build_G: component %d has no GH_CELL_PRISM_COMP kernel", c->comp);
+        const int64_t blocks = std::min<int64_t>((total + 255) / 256, 1 << 22);
+        hipLaunchKernelGGL(fns[c->comp], dim3((unsigned)blocks), dim3(256), 0, c->stream, c->obs[0], c->obs[1],
+                           c->obs[2], (const double *)c->bounds, c->N, c->M, c->ld, c->G);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
     } else if (c->cell_kind == GH_CELL_TESSEROID) {
         double *conv = nullptr;
         int *err_cell = nullptr;
@@ -460,7 +531,7 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
         lonsym_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
             lonsym_geom(c), c->ls->a_of, c->ls->m_of, weightfactor, c->wm);
     } else if (c->mf) {
-        hipLaunchKernelGGL(c->cell_kind == GH_CELL_PRISM_TF ? mf_colnorm_kernel<true> : mf_colnorm_kernel<false>,
+        hipLaunchKernelGGL(mf_pick(c, mf_colnorm_kernel<MF_E_GEN>, mf_colnorm_kernel<MF_E_TF>, mf_colnorm_kernel<MF_E_COMP>),
                            dim3((unsigned)((c->M + 3) / 4)), dim3(256), 0, c->stream, mf_geom(c), weightfactor, c->wm);
     } else if (shard_rows(c)) {
         // row blocks: a column's norm spans the ranks -- local sums of squares, all-reduce, then the power and
@@ -788,7 +859,8 @@ int gh_compress_wavelet(gh_ctx *c, int dims, const int shape3[3], double thr, in
                 // no stored kernel: the rows are evaluated (twice over the two passes: setup path)
                 for (int64_t r0 = 0; r0 < nr; r0 += 32768) {
                     const int64_t rn = std::min<int64_t>(32768, nr - r0);
-                    hipLaunchKernelGGL(c->cell_kind == GH_CELL_PRISM_TF ? mf_rows_kernel<true> : mf_rows_kernel<false>,
+                    hipLaunchKernelGGL(mf_pick(c, mf_rows_kernel<MF_E_GEN>, mf_rows_kernel<MF_E_TF>,
+                                               mf_rows_kernel<MF_E_COMP>),
                                        dim3((unsigned)((M + 255) / 256), (unsigned)rn), dim3(256), 0, c->stream,
                                        mf_geom(c), (const double *)c->wm, i0 + r0, rn, X + r0 * M);
                 }
@@ -1311,6 +1383,7 @@ static int kids_make(gh_ctx *c, int C, const double *x0s, const double *low, con
         k->ratio = c->ratio;
         for (int q = 0; q < 3; ++q) k->tf_dir[q] = c->tf_dir[q];
         k->tf_dir_d = c->tf_dir_d;
+        k->comp = c->comp;
         k->have_obs = k->have_cells = k->have_G = true;
         k->mf = true;
         k->weighted = c->weighted;
@@ -1431,6 +1504,10 @@ int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const 
     if (c->mf && c->cell_kind == GH_CELL_PRISM_TF)
         return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of the magnetic field (total field, "
                                            "GH_CELL_PRISM_TF) are not supported: store the kernel or run single chains");
+    if (c->mf && c->cell_kind == GH_CELL_PRISM_COMP)
+        return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of a prism gravity component other "
+                                           "than gz (GH_CELL_PRISM_COMP) are not supported: store the kernel or run "
+                                           "single chains");
     HIPCHK(c, hipSetDevice(c->device));
     if (lonsym_on(c)) {
         // (the light contexts of the chains share the tables, not a compressed forward operator)

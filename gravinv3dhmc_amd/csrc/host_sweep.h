@@ -169,6 +169,7 @@ static MfGeom mf_geom(const gh_ctx *c)
 {
     MfGeom g;
     g.kind = c->cell_kind;
+    g.comp = c->cell_kind == GH_CELL_PRISM_COMP ? c->comp : 0;
     g.radius_u = (c->cell_kind == GH_CELL_TESSEROID && c->obs_h_uniform) ? 6378137.0 + c->obs_h0 : 0.0;
     g.N = c->N;
     g.M = c->M;
@@ -192,6 +193,22 @@ static MfGeom mf_geom(const gh_ctx *c)
     return g;
 }
 
+// The entry form of the generic matrix-free passes (mf_colnorm / mf_adjoint / mf_forward / mf_rows_kernel<E>)
+static int mf_entry_form(const gh_ctx *c)
+{
+    if (c->cell_kind == GH_CELL_PRISM_TF) return MF_E_TF;
+    if (c->cell_kind == GH_CELL_PRISM_COMP) return MF_E_COMP;
+    return MF_E_GEN;  // GH_CELL_PRISM / GH_CELL_TESSEROID: by MfGeom::kind
+}
+
+// kernel<E> of a generic pass for the context's entry form
+template <typename F>
+static F mf_pick(const gh_ctx *c, F gen, F tf, F comp)
+{
+    const int e = mf_entry_form(c);
+    return e == MF_E_TF ? tf : e == MF_E_COMP ? comp : gen;
+}
+
 typedef void (*mf_fused_fn)(MfGeom, SweepArgs, const double *, const double *, MfNear, MfStats *);
 
 template <int KIND>
@@ -208,6 +225,8 @@ static mf_fused_fn mf_fused_for(const gh_ctx *c)
 {
     if (c->cell_kind == GH_CELL_PRISM) return mf_fused_for_kind<0>(c->mf_T, c->mf_EPT);
     if (c->cell_kind == GH_CELL_PRISM_TF) return mf_fused_for_kind<5>(c->mf_T, c->mf_EPT);
+    if (c->cell_kind == GH_CELL_PRISM_COMP)  // (6: the gradient tensor, 7: potential, geoid, gx, gy)
+        return c->comp >= GH_COMP_GXX ? mf_fused_for_kind<6>(c->mf_T, c->mf_EPT) : mf_fused_for_kind<7>(c->mf_T, c->mf_EPT);
     if (!c->mf_near_on) return mf_fused_for_kind<1>(c->mf_T, c->mf_EPT);
     if (c->mf_exact) return mf_fused_for_kind<2>(c->mf_T, c->mf_EPT);
     if (!c->mf_pipe) return mf_fused_for_kind<3>(c->mf_T, c->mf_EPT);
@@ -348,13 +367,14 @@ static int launch_mf(gh_ctx *c, SweepArgs &a)
                            wm, c->cell_kind == GH_CELL_TESSEROID ? c->mf_cellc : nullptr, near,
                            c->prof ? c->mf_stats : nullptr);
     } else {
-        const bool tf = c->cell_kind == GH_CELL_PRISM_TF;
         if (a.mode & SW_ADJ)
-            hipLaunchKernelGGL(tf ? mf_adjoint_kernel<true> : mf_adjoint_kernel<false>, dim3((unsigned)((c->M + 3) / 4)),
-                               dim3(256), 0, c->stream, g, a, wm);
+            hipLaunchKernelGGL(mf_pick(c, mf_adjoint_kernel<MF_E_GEN>, mf_adjoint_kernel<MF_E_TF>,
+                                       mf_adjoint_kernel<MF_E_COMP>),
+                               dim3((unsigned)((c->M + 3) / 4)), dim3(256), 0, c->stream, g, a, wm);
         if (a.mode & SW_FWD) {
             const double *x = (a.mode & SW_UPD) ? a.x_out : a.x_in;
-            hipLaunchKernelGGL(tf ? mf_forward_kernel<true> : mf_forward_kernel<false>,
+            hipLaunchKernelGGL(mf_pick(c, mf_forward_kernel<MF_E_GEN>, mf_forward_kernel<MF_E_TF>,
+                                       mf_forward_kernel<MF_E_COMP>),
                                dim3((unsigned)((c->ld + 255) / 256), (unsigned)c->grid), dim3(256), 0, c->stream, g, x,
                                wm, c->mf_cells_per_chunk, c->ld, a.slab);
         }

@@ -1200,6 +1200,192 @@ prism_tf_result_kernel(const double *__restrict__ xp, const double *__restrict__
     res[l] = acc * TF_SCALE;
 }
 
+// ---- the other gravity fields of prisms (GH_CELL_PRISM_COMP)
+
+// The components: the values of GH_COMP_* (include/gravhmc.h; gravhmc.hip checks that they agree -- this header
+// also compiles on its own, for the build's code check)
+enum { COMP_POTENTIAL = 0, COMP_GEOID, COMP_GX, COMP_GY, COMP_GZ, COMP_GXX, COMP_GXY, COMP_GXZ, COMP_GYY, COMP_GYZ,
+       COMP_GZZ };
+
+// The scale prism.py applies to kernel2d and result once, at the end (prism.py:151,178-179,231,314,367,...):
+// products of the reference constants G, SI2MGAL, SI2EOTVOS, g0 (constants.py:26,29,34,50), rounded once
+// as Python rounds them.
+template <int COMP>
+__device__ __forceinline__ constexpr double prism_comp_scale()
+{
+    return COMP == COMP_POTENTIAL ? 0.00000006673
+           : COMP == COMP_GEOID   ? 0.00000006673 / 9.80
+           : COMP <= COMP_GZ      ? 0.00000006673 * 100000.0
+                                     : 0.00000006673 * 1000000000.0;
+}
+
+// The kernel of one component at one corner (dx, dy, dz) = corner - observation of the prism b: the distance
+// and then kernelpot / x / y / z / xx ... zz (_prism.pyx:36-68) in the reference's operation order.  gxy, gxz
+// and gyz take the reference's perturbed distance when the point lies on the line of an edge in front of
+// the corner (_prism.pyx:346-351, 380-385, 443-448): the entry there is large but finite.
+template <int COMP>
+__device__ __forceinline__ double prism_comp_corner(double dx, double dy, double dz, const double *b)
+{
+#pragma clang fp contract(off)
+    double r;
+    if (COMP == COMP_GXY && dx == 0 && dy == 0 && dz < 0) {
+        const double t1 = 0.00001 * (b[1] - b[0]), t2 = 0.00001 * (b[3] - b[2]);
+        r = sqrt(t1 * t1 + t2 * t2 + dz * dz);
+    } else if (COMP == COMP_GXZ && dx == 0 && dz == 0 && dy < 0) {
+        const double t1 = 0.00001 * (b[1] - b[0]), t2 = 0.00001 * (b[5] - b[4]);
+        r = sqrt(t1 * t1 + t2 * t2 + dy * dy);
+    } else if (COMP == COMP_GYZ && dy == 0 && dz == 0 && dx < 0) {
+        const double t1 = 0.00001 * (b[3] - b[2]), t2 = 0.00001 * (b[5] - b[4]);
+        r = sqrt(t1 * t1 + t2 * t2 + dx * dx);
+    } else {
+        r = sqrt(dx * dx + dy * dy + dz * dz);
+    }
+    if (COMP == COMP_POTENTIAL || COMP == COMP_GEOID)
+        return dx * dy * safe_log_d(dz + r) + dy * dz * safe_log_d(dx + r) + dx * dz * safe_log_d(dy + r) -
+               0.5 * (dx * dx) * safe_atan2_d(dz * dy, dx * r) - 0.5 * (dy * dy) * safe_atan2_d(dz * dx, dy * r) -
+               0.5 * (dz * dz) * safe_atan2_d(dx * dy, dz * r);
+    if (COMP == COMP_GX)
+        return -(dy * safe_log_d(dz + r) + dz * safe_log_d(dy + r) - dx * safe_atan2_d(dz * dy, dx * r));
+    if (COMP == COMP_GY)
+        return -(dz * safe_log_d(dx + r) + dx * safe_log_d(dz + r) - dy * safe_atan2_d(dx * dz, dy * r));
+    if (COMP == COMP_GZ)
+        return -(dx * safe_log_d(dy + r) + dy * safe_log_d(dx + r) - dz * safe_atan2_d(dx * dy, dz * r));
+    if (COMP == COMP_GXX) return -safe_atan2_d(dz * dy, dx * r);
+    if (COMP == COMP_GXY) return safe_log_d(dz + r);
+    if (COMP == COMP_GXZ) return safe_log_d(dy + r);
+    if (COMP == COMP_GYY) return -safe_atan2_d(dz * dx, dy * r);
+    if (COMP == COMP_GYZ) return safe_log_d(dx + r);
+    return -safe_atan2_d(dx * dy, dz * r);  // COMP_GZZ
+}
+
+// One (observation, prism) entry of a component for a density of 1: scale * the sum over the 8 corners
+// (k: z2, z1; then j; then i) of (-1)^(i+j+k) kernel, one accumulator (prism.py:102-662 with _prism.pyx's
+// loops).  prism_comp_entry<COMP_GZ> is prism_entry's arithmetic.
+template <int COMP>
+__device__ __forceinline__ double prism_comp_entry(double px, double py, double pz, const double *b)
+{
+#pragma clang fp contract(off)
+    const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double dz = Z[k] - pz;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const double dy = Y[j] - py;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const double dx = X[i] - px;
+                const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
+                acc += sign * prism_comp_corner<COMP>(dx, dy, dz, b);
+            }
+        }
+    }
+    return acc * prism_comp_scale<COMP>();
+}
+
+// The entry of a component chosen at run time (the matrix-free passes: one component per context, so the
+// branch is uniform).  gz is not among them: a gz context is GH_CELL_PRISM and runs prism_entry.  Two
+// families, so that a pass can hold the one it runs: the tensor (one log or atan2 per corner) and the
+// potential / geoid / gx / gy (six or three per corner).
+__device__ __forceinline__ double prism_field_entry_rt(int comp, double px, double py, double pz, const double *b)
+{
+    switch (comp) {
+    case COMP_POTENTIAL: return prism_comp_entry<COMP_POTENTIAL>(px, py, pz, b);
+    case COMP_GEOID: return prism_comp_entry<COMP_GEOID>(px, py, pz, b);
+    case COMP_GX: return prism_comp_entry<COMP_GX>(px, py, pz, b);
+    default: return prism_comp_entry<COMP_GY>(px, py, pz, b);
+    }
+}
+
+__device__ __forceinline__ double prism_tensor_entry_rt(int comp, double px, double py, double pz, const double *b)
+{
+    switch (comp) {
+    case COMP_GXX: return prism_comp_entry<COMP_GXX>(px, py, pz, b);
+    case COMP_GXY: return prism_comp_entry<COMP_GXY>(px, py, pz, b);
+    case COMP_GXZ: return prism_comp_entry<COMP_GXZ>(px, py, pz, b);
+    case COMP_GYY: return prism_comp_entry<COMP_GYY>(px, py, pz, b);
+    case COMP_GYZ: return prism_comp_entry<COMP_GYZ>(px, py, pz, b);
+    default: return prism_comp_entry<COMP_GZZ>(px, py, pz, b);
+    }
+}
+
+__device__ __forceinline__ double prism_comp_entry_rt(int comp, double px, double py, double pz, const double *b)
+{
+    return comp >= COMP_GXX ? prism_tensor_entry_rt(comp, px, py, pz, b) : prism_field_entry_rt(comp, px, py, pz, b);
+}
+
+// Dense assembly of one component: the layout of prism_gz_kernel (obs fastest, zero padding rows to ld,
+// grid-stride).  One instantiation per component, so that each keeps its own register budget.
+template <int COMP>
+__global__ void __launch_bounds__(256)
+prism_comp_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
+                  const double *__restrict__ bounds6, int64_t N, int64_t M, int64_t ld, double *__restrict__ G)
+{
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ld * M;
+         idx += (int64_t)gridDim.x * 256) {
+        const int64_t c = idx / ld, l = idx - c * ld;
+        G[idx] = (l < N) ? prism_comp_entry<COMP>(xp[l], yp[l], zp[l], bounds6 + 6 * c) : 0.0;
+    }
+}
+
+template <int COMP>
+__device__ __forceinline__ double prism_comp_result_one(double px, double py, double pz,
+                                                        const double *__restrict__ bounds6,
+                                                        const double *__restrict__ dens, int64_t M)
+{
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int64_t c = 0; c < M; ++c) {
+        const double *b = bounds6 + 6 * c;
+        const double d = dens[c];
+        const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const double dz = Z[k] - pz;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const double dy = Y[j] - py;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const double dx = X[i] - px;
+                    const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
+                    acc += sign * prism_comp_corner<COMP>(dx, dy, dz, b) * d;
+                }
+            }
+        }
+    }
+    return acc * prism_comp_scale<COMP>();
+}
+
+// prism.<component>'s `result` (prism.py:102-662): one thread per observation, ONE sum per observation of
+// ((-1)^(i+j+k) kernel) * density over every corner of every cell in mesh order, scaled once at the end --
+// the reference's accumulation order.  The component is uniform over the launch.
+__global__ void __launch_bounds__(256)
+prism_comp_result_kernel(const double *__restrict__ xp, const double *__restrict__ yp,
+                         const double *__restrict__ zp, const double *__restrict__ bounds6,
+                         const double *__restrict__ dens, int64_t N, int64_t M, int comp, double *__restrict__ res)
+{
+    const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= N) return;
+    const double px = xp[l], py = yp[l], pz = zp[l];
+    double v;
+    switch (comp) {
+    case COMP_POTENTIAL: v = prism_comp_result_one<COMP_POTENTIAL>(px, py, pz, bounds6, dens, M); break;
+    case COMP_GEOID: v = prism_comp_result_one<COMP_GEOID>(px, py, pz, bounds6, dens, M); break;
+    case COMP_GX: v = prism_comp_result_one<COMP_GX>(px, py, pz, bounds6, dens, M); break;
+    case COMP_GY: v = prism_comp_result_one<COMP_GY>(px, py, pz, bounds6, dens, M); break;
+    case COMP_GZ: v = prism_comp_result_one<COMP_GZ>(px, py, pz, bounds6, dens, M); break;
+    case COMP_GXX: v = prism_comp_result_one<COMP_GXX>(px, py, pz, bounds6, dens, M); break;
+    case COMP_GXY: v = prism_comp_result_one<COMP_GXY>(px, py, pz, bounds6, dens, M); break;
+    case COMP_GXZ: v = prism_comp_result_one<COMP_GXZ>(px, py, pz, bounds6, dens, M); break;
+    case COMP_GYY: v = prism_comp_result_one<COMP_GYY>(px, py, pz, bounds6, dens, M); break;
+    case COMP_GYZ: v = prism_comp_result_one<COMP_GYZ>(px, py, pz, bounds6, dens, M); break;
+    default: v = prism_comp_result_one<COMP_GZZ>(px, py, pz, bounds6, dens, M); break;
+    }
+    res[l] = v;
+}
+
 constexpr int TESS_STACK = 100;  // tesseroid.py:79
 
 struct TessStats {
@@ -1718,7 +1904,8 @@ ring_stats_kernel(const double *ring, int64_t M, int nvalid, double *mean, doubl
 // wm computed by mf_colnorm_kernel.
 
 struct MfGeom {
-    int kind;  // 0 prism, 1 tesseroid, 2 prism total field (GH_CELL_*)
+    int kind;  // 0 prism, 1 tesseroid, 2 prism total field, 3 prism gravity component (GH_CELL_*)
+    int comp;  // kind 3: the component (COMP_*; in what was kind's padding, the struct keeps its size)
     double radius_u;  // tesseroids, every observation at one height: its radius R + h (else 0)
     int64_t N, M;
     const double *o0, *o1, *o2, *o3;  // prism: x,y,z,- (total field: x,y,z,(fx,fy,fz))  tesseroid: lon_r, sinlat, coslat, radius
@@ -1726,14 +1913,18 @@ struct MfGeom {
     const double *bounds6;
     double ratio;
 };
+static_assert(sizeof(MfGeom) == 96, "MfGeom is a kernel argument of every matrix-free pass: keep its size");
 
-// TF: the prisms' total-field entry (GH_CELL_PRISM_TF; the field direction is the three doubles at g.o3),
-// else g.kind 0 prism gz / 1 tesseroid.  The generic passes below are templated on it so that the gz and
+// The entry form of the generic passes below: MF_E_GEN = g.kind 0 prism gz / 1 tesseroid, MF_E_TF = the
+// prisms' total-field entry (GH_CELL_PRISM_TF; the field direction is the three doubles at g.o3), MF_E_COMP =
+// a prism gravity component (GH_CELL_PRISM_COMP; g.comp).  The passes are templated on it so that the gz and
 // tesseroid instantiations keep their register budget.
-template <bool TF>
+enum { MF_E_GEN = 0, MF_E_TF = 1, MF_E_COMP = 2 };
+template <int E>
 __device__ __forceinline__ double mf_entry(const MfGeom &g, int64_t i, const double *b)
 {
-    if (TF) return prism_tf_entry(g.o0[i], g.o1[i], g.o2[i], b, g.o3[0], g.o3[1], g.o3[2]);
+    if (E == MF_E_TF) return prism_tf_entry(g.o0[i], g.o1[i], g.o2[i], b, g.o3[0], g.o3[1], g.o3[2]);
+    if (E == MF_E_COMP) return prism_comp_entry_rt(g.comp, g.o0[i], g.o1[i], g.o2[i], b);
     if (g.kind == 0) return prism_entry(g.o0[i], g.o1[i], g.o2[i], b);
     int err = 0;
     unsigned long long nl = 0;
@@ -1742,7 +1933,7 @@ __device__ __forceinline__ double mf_entry(const MfGeom &g, int64_t i, const dou
 }
 
 // wm_j = (sum_i K_ij^2)^wf: one wave per cell, lanes over observations
-template <bool TF>
+template <int E>
 __global__ void __launch_bounds__(256) mf_colnorm_kernel(MfGeom g, double wf, double *wm)
 {
     const int lane = threadIdx.x & 63;
@@ -1751,7 +1942,7 @@ __global__ void __launch_bounds__(256) mf_colnorm_kernel(MfGeom g, double wf, do
     const double *b = g.bounds6 + 6 * j;
     double s = 0.0;
     for (int64_t i = lane; i < g.N; i += 64) {
-        const double k = mf_entry<TF>(g, i, b);
+        const double k = mf_entry<E>(g, i, b);
         s += k * k;
     }
     s = wave_allreduce_sum(s);
@@ -1760,7 +1951,7 @@ __global__ void __launch_bounds__(256) mf_colnorm_kernel(MfGeom g, double wf, do
 
 // Adjoint + leapfrog update for one cell per wave: the matrix-free counterpart of the ADJ /
 // UPD / PFIN / GOUT / SPEC part of sweep_kernel (same arithmetic per column).
-template <bool TF>
+template <int E>
 __global__ void __launch_bounds__(256) mf_adjoint_kernel(MfGeom g, SweepArgs a, const double *wm)
 {
     __shared__ double red[4];
@@ -1771,7 +1962,7 @@ __global__ void __launch_bounds__(256) mf_adjoint_kernel(MfGeom g, SweepArgs a, 
     if (j < g.M) {
         const double *b = g.bounds6 + 6 * j;
         double s = 0.0;
-        for (int64_t i = lane; i < g.N; i += 64) s += mf_entry<TF>(g, i, b) * a.r[i];
+        for (int64_t i = lane; i < g.N; i += 64) s += mf_entry<E>(g, i, b) * a.r[i];
         s = wave_allreduce_sum(s);
         const double w = wm[j];
         s = (w != 0.0) ? s * (1.0 / w) : s;
@@ -1809,7 +2000,7 @@ __global__ void __launch_bounds__(256) mf_adjoint_kernel(MfGeom g, SweepArgs a, 
 }
 
 // Forward partials: thread = observation, blockIdx.y = chunk of cells; slab[chunk][i]
-template <bool TF>
+template <int E>
 __global__ void __launch_bounds__(256)
 mf_forward_kernel(MfGeom g, const double *x, const double *wm, int64_t cells_per_chunk, int64_t ld,
                   double *slab)
@@ -1824,7 +2015,7 @@ mf_forward_kernel(MfGeom g, const double *x, const double *wm, int64_t cells_per
         for (int64_t j = j0; j < j1; ++j) {
             const double w = wm ? wm[j] : 1.0;
             const double xs = (w != 0.0) ? x[j] * (1.0 / w) : x[j];
-            acc += mf_entry<TF>(g, i, g.bounds6 + 6 * j) * xs;
+            acc += mf_entry<E>(g, i, g.bounds6 + 6 * j) * xs;
         }
     }
     slab[(int64_t)blockIdx.y * ld + i] = acc;
@@ -1835,14 +2026,14 @@ mf_forward_kernel(MfGeom g, const double *x, const double *wm, int64_t cells_per
 // out[nrows][M] (what gather_rows_kernel copies out of a stored G): the wavelet compressor's input
 // (compressor3D.kernelcompressor transforms whole rows).  Entries by the generic engines (mf_entry: the
 // values the dense assembly stores), divided by the column's weight as the in-place weighting does.
-template <bool TF>
+template <int E>
 __global__ void __launch_bounds__(256)
 mf_rows_kernel(MfGeom g, const double *__restrict__ wm, int64_t i0, int64_t nrows, double *__restrict__ out)
 {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t i = blockIdx.y;
     if (j >= g.M || i >= nrows) return;
-    const double k = mf_entry<TF>(g, i0 + i, g.bounds6 + 6 * j);
+    const double k = mf_entry<E>(g, i0 + i, g.bounds6 + 6 * j);
     const double w = wm ? wm[j] : 1.0;
     out[i * g.M + j] = (w != 0.0) ? k * (1.0 / w) : k;
 }
@@ -2164,7 +2355,9 @@ struct MfStats {
 
 // T threads per workgroup, EPT rows per thread (row of slot k: t + k*T): T*EPT >= ld; KIND: 0 prisms,
 // 1 tesseroids with the subdivision inside the pass, 2 / 3 tesseroids with the near-field table and the
-// exact-order / the fast root leaf, 5 prisms' total field (separate kernels: the prism entry's log/atan2 and the
+// exact-order / the fast root leaf, 5 prisms' total field, 6 / 7 prisms' gradient tensor / potential, geoid, gx,
+// gy (the component g.comp is a uniform branch inside the family; one kernel for all ten components held 272
+// registers at <256, 4>, one wave per SIMD instead of two) (separate kernels: the prism entry's log/atan2 and the
 // tesseroid entry's trigonometry would otherwise share one register budget; 4 is taken by mfbatch.hip.h's kinds).
 // LDS: T*EPT doubles (the column) + 2 x (T/64 + 8) doubles (ping-pong slots of the dot).
 template <int T, int EPT, int KIND>
@@ -2184,6 +2377,7 @@ mf_fused_kernel(MfGeom g, SweepArgs a, const double *__restrict__ wm, const doub
     const int ept = (int)((a.ld + T - 1) / T);  // slots in use (<= EPT)
     // (KIND 5: the field direction, the same for every entry)
     const double fx = KIND == 5 ? g.o3[0] : 0.0, fy = KIND == 5 ? g.o3[1] : 0.0, fz = KIND == 5 ? g.o3[2] : 0.0;
+    const int comp = (KIND == 6 || KIND == 7) ? g.comp : 0;  // (KIND 6, 7: the component)
     double dacc[EPT];
 #pragma unroll
     for (int k = 0; k < EPT; ++k) dacc[k] = 0.0;
@@ -2278,6 +2472,12 @@ mf_fused_kernel(MfGeom g, SweepArgs a, const double *__restrict__ wm, const doub
                         nleaf += 1;
                     } else if (KIND == 5) {
                         v = prism_tf_entry(g.o0[i], g.o1[i], g.o2[i], b, fx, fy, fz);
+                        nleaf += 1;
+                    } else if (KIND == 6) {
+                        v = prism_tensor_entry_rt(comp, g.o0[i], g.o1[i], g.o2[i], b);
+                        nleaf += 1;
+                    } else if (KIND == 7) {
+                        v = prism_field_entry_rt(comp, g.o0[i], g.o1[i], g.o2[i], b);
                         nleaf += 1;
                     } else {
                         v = tess_entry_cc(g.o0[i], g.o1[i], g.o2[i], g.o3[i], cc, b, g.ratio, nleaf);

@@ -213,11 +213,11 @@ def make_sharded_engine(N, M, ranks, device=None, backend="rccl", align=1, axis=
             return allgather_slices(self.ranks, local, self.parts)
 
         # -- overrides: full vectors in, full vectors out -----------------------------------
-        def set_cells(self, bounds6, kind, ratio=1.6, direction=None):
+        def set_cells(self, bounds6, kind, ratio=1.6, direction=None, component=None):
             b = np.asarray(bounds6, dtype=np.float64)
             if b.shape[0] == self.M_global:
                 b = b[self.m0:self.m1]
-            Engine.set_cells(self, b, kind, ratio, direction)
+            Engine.set_cells(self, b, kind, ratio, direction, component)
 
         def weight(self, weightfactor=0.5):
             return self._full(Engine.weight(self, weightfactor))

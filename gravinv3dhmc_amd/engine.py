@@ -91,12 +91,22 @@ class Engine(object):
             raise ValueError("Input arrays xp, yp, and zp must have same length!")
         self._chk(self._lib.gh_set_obs(self._h, ptr(a), ptr(b), ptr(c)))
 
-    def set_cells(self, bounds6, kind, ratio=1.6, direction=None):
+    def set_cells(self, bounds6, kind, ratio=1.6, direction=None, component=None):
         """kind CELL_PRISM / CELL_TESSEROID (ratio: the tesseroid distance-size ratio), or CELL_PRISM_TF with
-        direction = (fx, fy, fz), the unit vector of the regional field (utils.dircos(inc, dec))."""
+        direction = (fx, fy, fz), the unit vector of the regional field (utils.dircos(inc, dec)).
+        component (prisms, kind CELL_PRISM or CELL_PRISM_COMP): the gravity field, a name of
+        _lib.COMPONENTS or a COMP_* value; "gz" is kind CELL_PRISM itself (gh_set_cells_prism)."""
         b = f64(bounds6)
         if b.shape != (self.M, 6):
             raise ValueError("bounds table must be (M, 6)")
+        if component is not None or int(kind) == _lib.CELL_PRISM_COMP:
+            if int(kind) not in (_lib.CELL_PRISM, _lib.CELL_PRISM_COMP):
+                raise ValueError("a gravity component is a field of prisms (kind CELL_PRISM / CELL_PRISM_COMP)")
+            comp = _lib.COMPONENTS.get(component, -1) if isinstance(component, str) else component
+            if comp not in _lib.COMPONENTS.values():
+                raise ValueError("component must be one of %s" % ", ".join(_lib.COMPONENTS))
+            self._chk(self._lib.gh_set_cells_prism(self._h, ptr(b), int(comp)))
+            return
         if int(kind) == _lib.CELL_PRISM_TF:
             if direction is None or len(direction) != 3:
                 raise ValueError("the magnetic (total-field) kernel needs direction = (fx, fy, fz)")
@@ -113,6 +123,16 @@ class Engine(object):
             raise ValueError("magnetization must be (M, 3)")
         out = np.empty(self.N)
         self._chk(self._lib.gh_tf_result(self._h, ptr(m), ptr(out)))
+        return out
+
+    def prism_result(self, dens):
+        """The field of the prism cells (CELL_PRISM or CELL_PRISM_COMP) with densities dens[M] (g/cm^3), in
+        the reference's accumulation order (gh_prism_result); needs no G."""
+        d = f64(dens)
+        if d.shape != (self.M,):
+            raise ValueError("density must be (M,)")
+        out = np.empty(self.N)
+        self._chk(self._lib.gh_prism_result(self._h, ptr(d), ptr(out)))
         return out
 
     def set_matrix_free(self, on=True, exact=None):

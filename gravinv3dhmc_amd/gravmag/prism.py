@@ -1,8 +1,11 @@
-"""gz and the total-field magnetic anomaly of right rectangular prisms on the GPU.
+"""The gravity fields and the total-field magnetic anomaly of right rectangular prisms on the GPU.
 
 Mirror of the reference's `gravmag.prism.gz` (gravmag/prism.py:911-918 -> _dispatcher_gravity
 :998-1038 -> _gz :291-316 -> _prism.gz, _prism.pyx:265-290): same arguments, same return
-`(result, kernel2d)` in mGal for densities in g/cm^3.  And of `gravmag.prism.tf` (prism.py:975 ->
+`(result, kernel2d)` in mGal for densities in g/cm^3.  Likewise its other gravity fields
+(prism.py:875-972 -> _potential, _geoid, _gx, ... _gzz :102-662 -> _prism.pyx:36-68, 206-509):
+`potential` (G, SI units per g/cm^3), `geoid` (m), `gx`, `gy` (mGal) and the gradient tensor `gxx`,
+`gxy`, `gxz`, `gyy`, `gyz`, `gzz` (Eotvos).  And of `gravmag.prism.tf` (prism.py:975 ->
 _dispatcher_magnetic :1140-1180 -> _tf :665-733 -> _prism.tf, _prism.pyx:80-113): `(result, kernel2d)`
 in uT for magnetizations in A/m (CM * T2NT, constants.py).  `njobs`/`pool` are accepted and
 ignored (the reference uses them for host multiprocessing; the assembly here is one HIP
@@ -83,3 +86,89 @@ def tf(xp, yp, zp, prisms, inc, dec, pmag=None, njobs=1, pool=None, return_kerne
     finally:
         eng.close()
     return result, kernel2d
+
+
+def build_engine_component(xp, yp, zp, prisms, component, dens=None, device=0):
+    """Cells of one gravity component's kernel on the device (G not built yet); returns (engine, densities)."""
+    xp, yp, zp = (np.asarray(a, dtype=np.float64) for a in (xp, yp, zp))
+    if xp.shape != yp.shape or xp.shape != zp.shape:
+        raise ValueError("Input arrays xp, yp, and zp must have same length!")
+    bounds, rho, _ = active_cells(prisms, dens)
+    if bounds.shape[0] == 0:
+        raise ValueError("mesh has no cell with a 'density' property (and no dens given)")
+    eng = Engine(xp.size, bounds.shape[0], device=device)
+    try:
+        eng.set_obs(xp, yp, zp)
+        eng.set_cells(bounds, _lib.CELL_PRISM_COMP, component=component)
+    except Exception:
+        eng.close()
+        raise
+    return eng, rho
+
+
+def _field(component, xp, yp, zp, prisms, dens, return_kernel, device):
+    """(result, kernel2d) of one component: the result in the reference's accumulation order
+    (gh_prism_result), the kernel from the dense assembly, Fortran-ordered (None without return_kernel)."""
+    eng, rho = build_engine_component(xp, yp, zp, prisms, component, dens, device)
+    try:
+        result = eng.prism_result(rho)
+        kernel2d = None
+        if return_kernel:
+            eng.build_G()
+            kernel2d = eng.download_G()
+    finally:
+        eng.close()
+    return result, kernel2d
+
+
+def potential(xp, yp, zp, prisms, dens=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """Gravitational potential of the prism model and its kernel (G times the reference's kernelpot sum)."""
+    return _field("potential", xp, yp, zp, prisms, dens, return_kernel, device)
+
+
+def geoid(xp, yp, zp, prisms, dens=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """Geoid height of the prism model and its kernel: the potential times 1/g0 (G/g0)."""
+    return _field("geoid", xp, yp, zp, prisms, dens, return_kernel, device)
+
+
+def gx(xp, yp, zp, prisms, dens=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """North gravity component in mGal and its kernel."""
+    return _field("gx", xp, yp, zp, prisms, dens, return_kernel, device)
+
+
+def gy(xp, yp, zp, prisms, dens=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """East gravity component in mGal and its kernel."""
+    return _field("gy", xp, yp, zp, prisms, dens, return_kernel, device)
+
+
+def gxx(xp, yp, zp, prisms, dens=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """gxx gravity gradient in Eotvos and its kernel."""
+    return _field("gxx", xp, yp, zp, prisms, dens, return_kernel, device)
+
+
+def gxy(xp, yp, zp, prisms, dens=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """gxy gravity gradient in Eotvos and its kernel.  As in the reference, a point on the line of a
+    vertical edge above the prism takes a perturbed distance there: large but finite values."""
+    return _field("gxy", xp, yp, zp, prisms, dens, return_kernel, device)
+
+
+def gxz(xp, yp, zp, prisms, dens=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """gxz gravity gradient in Eotvos and its kernel (the reference's perturbed distance on the line of
+    an edge along y)."""
+    return _field("gxz", xp, yp, zp, prisms, dens, return_kernel, device)
+
+
+def gyy(xp, yp, zp, prisms, dens=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """gyy gravity gradient in Eotvos and its kernel."""
+    return _field("gyy", xp, yp, zp, prisms, dens, return_kernel, device)
+
+
+def gyz(xp, yp, zp, prisms, dens=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """gyz gravity gradient in Eotvos and its kernel (the reference's perturbed distance on the line of
+    an edge along x)."""
+    return _field("gyz", xp, yp, zp, prisms, dens, return_kernel, device)
+
+
+def gzz(xp, yp, zp, prisms, dens=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """gzz gravity gradient in Eotvos and its kernel."""
+    return _field("gzz", xp, yp, zp, prisms, dens, return_kernel, device)

@@ -51,6 +51,10 @@ class GravMagModule(object):
     * field: "gravity" (gz, mGal per g/cm^3) or "magnetic" (cartesian only: the total-field anomaly in uT
       per A/m of magnetization along the regional field of mangle = (inclination, declination) in degrees,
       gravmag.prism.tf).
+    * component: the gravity field of a cartesian gravity model (extension; the reference's module inverts gz
+      only): "gz" (default), "potential", "geoid", "gx", "gy" or a gradient-tensor component "gxx", "gxy",
+      "gxz", "gyy", "gyz", "gzz" -- the kernel of gravmag.prism.<component>, in its units.  Spherical models
+      take gz only (NotImplementedError), the magnetic field none (ValueError).
     * mtopo=(x, y, topography) keyword: carve the mesh with a topography surface.
     * device: GPU ordinal (extension; the reference has no such argument).
     * shard: a `dist.Ranks` object: the cells of ONE model are split in column blocks over the
@@ -72,7 +76,7 @@ class GravMagModule(object):
                  coordinate="cartesian", njobs=1, field="gravity",
                  mangle=(90, 0), wavelet=False, device=0, verbose=True, shard=None,
                  shard_backend="rccl", matrix_free=False, shard_planes=False, shift_invariant=False, shard_axis="cells",
-                 **kwargs):
+                 component="gz", **kwargs):
         self.dobs = dobs
         self.fixed = fixed
         self.grav_fix = grav_fix
@@ -99,9 +103,22 @@ class GravMagModule(object):
             # (the reference's branch is `pass`, then a NameError on the undefined mesh: potential.py:106-108)
             raise NotImplementedError("the magnetic field on tesseroids (coordinate='spherical') is not supported")
         magnetic = field == "magnetic"
+        if component not in _lib.COMPONENTS:
+            raise ValueError("component must be one of %s" % ", ".join(_lib.COMPONENTS))
+        if component != "gz":
+            if magnetic:
+                raise ValueError("component=%r is a gravity field: the magnetic field is the total-field anomaly"
+                                 % component)
+            if coordinate == "spherical":
+                raise NotImplementedError("component=%r on tesseroids (coordinate='spherical') is not supported: "
+                                          "spherical models take gz only" % component)
+        self.component = component
         if wavelet not in (False, None, '1D', '3D'):
             raise ValueError("wavelet must be False, '1D' or '3D'")
-        self._say("Calculating {} field in {} coordinate.".format(field, coordinate))
+        if component != "gz":
+            self._say("Calculating {} field ({}) in {} coordinate.".format(field, component, coordinate))
+        else:
+            self._say("Calculating {} field in {} coordinate.".format(field, coordinate))
         spherical = coordinate == "spherical"
         if spherical:
             mesh = (mesher.TesseroidMeshSegment(mrange, mspacing, mdivisionsection) if mseg
@@ -152,6 +169,8 @@ class GravMagModule(object):
             eng.set_cells(bounds, _lib.CELL_TESSEROID, 1.6)
         elif magnetic:
             eng.set_cells(bounds, _lib.CELL_PRISM_TF, direction=utils.dircos(self.inc, self.dec))
+        elif component != "gz":
+            eng.set_cells(bounds, _lib.CELL_PRISM_COMP, component=component)
         else:
             eng.set_cells(bounds, _lib.CELL_PRISM)
         eng.build_G()

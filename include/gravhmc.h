@@ -5,7 +5,10 @@
  * its sampler uses is the duck-typed model object of inversion/hmc.py:30-32,71-83 (calls
  * `model.kernelw()` and `model.misfit_and_grad(...)`) and, one level down, the native kernels
  * `gravmag/_prism.pyx:265-290` (`_prism.gz`) and `gravmag/_tesseroid_numba.py:32-71,335`
- * (`_tesseroid_numba.gz`).  Every entry point below names the reference interface it replaces.
+ * (`_tesseroid_numba.gz`).  Prisms also carry the reference's other fields: the total-field magnetic
+ * anomaly (`_prism.tf`, gh_set_cells_tf) and the ten other gravity fields -- potential, geoid, gx, gy and
+ * the gradient tensor gxx ... gzz (`_prism.pyx:36-68, 206-509`, gh_set_cells_prism).  Every entry point
+ * below names the reference interface it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer of the reference would add.
  *
  * Conventions
@@ -71,8 +74,23 @@ typedef enum {
     GH_ERR_COMM = -6      /* collective layer error */
 } gh_status;
 
-/* GH_CELL_PRISM_TF: prisms, total-field magnetic anomaly (set with gh_set_cells_tf, not gh_set_cells) */
-enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2 };
+/* GH_CELL_PRISM_TF: prisms, total-field magnetic anomaly (set with gh_set_cells_tf, not gh_set_cells);
+ * GH_CELL_PRISM_COMP: prisms, one gravity field other than gz (set with gh_set_cells_prism) */
+enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2, GH_CELL_PRISM_COMP = 3 };
+/* The gravity fields of prisms (gravmag/prism.py:875-972), for gh_set_cells_prism */
+enum {
+    GH_COMP_POTENTIAL = 0, /* G, per g/cm^3 (SI otherwise) */
+    GH_COMP_GEOID = 1,     /* G / g0: the potential over 9.80 m/s^2, in m */
+    GH_COMP_GX = 2,        /* G * SI2MGAL: mGal */
+    GH_COMP_GY = 3,
+    GH_COMP_GZ = 4,
+    GH_COMP_GXX = 5,       /* G * SI2EOTVOS: Eotvos */
+    GH_COMP_GXY = 6,
+    GH_COMP_GXZ = 7,
+    GH_COMP_GYY = 8,
+    GH_COMP_GYZ = 9,
+    GH_COMP_GZZ = 10
+};
 /* potential.py:827-836 `regulization` strings */
 enum { GH_REG_DAMPING = 0, GH_REG_SMOOTHNESS = 1, GH_REG_MS = 2, GH_REG_TV = 3 };
 
@@ -108,6 +126,22 @@ int gh_set_cells_tf(gh_ctx *ctx, const double *bounds6, double fx, double fy, do
  * in uT, accumulated corner by corner, cell by cell in mesh order into one sum per observation and
  * scaled once, as the reference does. */
 int gh_tf_result(gh_ctx *ctx, const double *mag3, double *result);
+/* Prisms of a density model for one gravity field `component` (GH_COMP_*), M x 6 row-major
+ * x1,x2,y1,y2,z1,z2 in mesh order.  Entry (i, j) is the field at observation i of prism j with a density
+ * of 1 g/cm^3, scaled as prism.py scales kernel2d: G for the potential, G/g0 for the geoid, G*SI2MGAL for
+ * gx / gy / gz, G*SI2EOTVOS for the tensor (constants.py).  GH_COMP_GZ makes a GH_CELL_PRISM context, the
+ * same bits as gh_set_cells(kind 0); every other component a GH_CELL_PRISM_COMP one.  gxy, gxz and gyz
+ * keep the reference's perturbed distance on the line of a vertical / horizontal edge
+ * (_prism.pyx:346-351, 380-385, 443-448), so their entries there are large but finite.  The dense
+ * assembly, the weighting, every stored-kernel path and the matrix-free passes (fused and two-pass, the
+ * wavelet rows) run on it; the matrix-free batch of chains and the shift-invariant store refuse it with
+ * GH_ERR_UNSUPPORTED. */
+int gh_set_cells_prism(gh_ctx *ctx, const double *bounds6, int component);
+/* prism.<component>'s `result` on a GH_CELL_PRISM or GH_CELL_PRISM_COMP context (needs gh_set_obs /
+ * gh_set_cells_prism, not G): dens[M] in g/cm^3; result[N] accumulated corner by corner, cell by cell in
+ * mesh order into one sum per observation and scaled once, as the reference does.  Unsharded contexts
+ * only (GH_ERR_UNSUPPORTED otherwise). */
+int gh_prism_result(gh_ctx *ctx, const double *dens, double *result);
 /* Matrix-free mode (call before gh_build_G): the kernel matrix is never stored; the prism /
  * tesseroid entries are re-evaluated where they are needed.  With N <= 16384 observations a
  * leapfrog step evaluates every entry ONCE (a workgroup keeps a cell's column on the chip between
