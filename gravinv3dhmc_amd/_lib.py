@@ -14,8 +14,8 @@ LIB_PATH = os.environ.get("GRAVHMC_LIB") or os.path.join(_HERE, "libgravhmc.so")
 
 GH_OK, GH_ERR_ARG, GH_ERR_HIP, GH_ERR_NOMEM, GH_ERR_OVERFLOW, GH_ERR_UNSUPPORTED, GH_ERR_COMM = \
     0, -1, -2, -3, -4, -5, -6
-CELL_PRISM, CELL_TESSEROID, CELL_PRISM_TF, CELL_PRISM_COMP = 0, 1, 2, 3
-#: the gravity fields of prisms (GH_COMP_*, gh_set_cells_prism)
+CELL_PRISM, CELL_TESSEROID, CELL_PRISM_TF, CELL_PRISM_COMP, CELL_TESSEROID_COMP = 0, 1, 2, 3, 4
+#: the gravity fields of prisms and tesseroids (GH_COMP_*, gh_set_cells_prism / gh_set_cells_tess)
 COMP_POTENTIAL, COMP_GEOID, COMP_GX, COMP_GY, COMP_GZ, COMP_GXX, COMP_GXY, COMP_GXZ, COMP_GYY, COMP_GYZ, COMP_GZZ = \
     range(11)
 COMPONENTS = {"potential": COMP_POTENTIAL, "geoid": COMP_GEOID, "gx": COMP_GX, "gy": COMP_GY, "gz": COMP_GZ,
@@ -38,6 +38,7 @@ PROTOTYPES = {
     "gh_set_cells_tf": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
     "gh_tf_result": (C.c_int, [_ctx, _dp, _dp]),
     "gh_set_cells_prism": (C.c_int, [_ctx, _dp, C.c_int]),
+    "gh_set_cells_tess": (C.c_int, [_ctx, _dp, C.c_int, C.c_double]),
     "gh_prism_result": (C.c_int, [_ctx, _dp, _dp]),
     "gh_set_matrix_free": (C.c_int, [_ctx, C.c_int]),
     "gh_set_matrix_free_exact": (C.c_int, [_ctx, C.c_int]),

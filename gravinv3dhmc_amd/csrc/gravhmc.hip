@@ -246,10 +246,39 @@ int gh_set_cells_prism(gh_ctx *c, const double *bounds6, int component)
     return GH_OK;
 }
 
+int gh_set_cells_tess(gh_ctx *c, const double *bounds6, int component, double ratio)
+{
+    if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_tess: null pointer");
+    if (component < GH_COMP_POTENTIAL || component > GH_COMP_GZZ)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_tess: component %d is not one of GH_COMP_POTENTIAL (0) .. GH_COMP_GZZ (10)",
+                    component);
+    // w <= e, s <= n, top >= bottom: the reference's assertion (tesseroid.py:137-138)
+    for (int64_t j = 0; j < c->M; ++j) {
+        const double *b = bounds6 + 6 * j;
+        if (!(b[0] <= b[1] && b[2] <= b[3] && b[4] >= b[5]))
+            return fail(c, GH_ERR_ARG, "gh_set_cells_tess: invalid tesseroid dimensions (cell %lld: %g %g %g %g %g %g)",
+                        (long long)j, b[0], b[1], b[2], b[3], b[4], b[5]);
+    }
+    // gz is the tesseroid kind of gh_set_cells: the same context, the same kernels, the same bits
+    if (component == GH_COMP_GZ) return gh_set_cells(c, bounds6, GH_CELL_TESSEROID, ratio);
+    if (!(ratio > 0)) return fail(c, GH_ERR_ARG, "Invalid ratio %g. Must be > 0.", ratio);
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
+    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
+    c->cell_kind = GH_CELL_TESSEROID_COMP;
+    c->comp = component;
+    c->ratio = ratio;
+    c->have_cells = true;
+    return GH_OK;
+}
+
 int gh_prism_result(gh_ctx *c, const double *dens, double *result)
 {
     if (!c || !dens || !result) return fail(c, GH_ERR_ARG, "gh_prism_result: null pointer");
     TRY(need(c, c->have_obs && c->have_cells, "gh_prism_result: call gh_set_obs and gh_set_cells_prism first"));
+    if (c->cell_kind == GH_CELL_TESSEROID_COMP)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_prism_result: a tesseroid gravity component (GH_CELL_TESSEROID_COMP) has "
+                                           "no result pass of its own: gh_forward on its kernel");
     if (c->cell_kind != GH_CELL_PRISM && c->cell_kind != GH_CELL_PRISM_COMP)
         return fail(c, GH_ERR_ARG, "gh_prism_result: the cells are not a prism density model (gh_set_cells_prism)");
     if (c->sh.kind != 0)
@@ -351,6 +380,57 @@ int gh_set_matrix_free_exact(gh_ctx *c, int exact)
     return GH_OK;
 }
 
+// tess_comp_kernel of the context's component over all (observation, cell) pairs: G (ld x M) when G is given,
+// else the statistics alone; warn_cells, leaves, and GH_ERR_OVERFLOW as the gz build reports them.  conv: the
+// converted observations (lon rad, sin lat, cos lat, radius; N each).
+static int tess_comp_assemble(gh_ctx *c, const double *conv, double *G)
+{
+    typedef void (*tc_fn)(const double *, const double *, const double *, const double *, const double *, int64_t,
+                          int64_t, int64_t, double, int, double *, int *, TessStats *);
+    // (indexed by GH_COMP_*: one instantiation per leaf, the geoid runs the potential's; gz is a GH_CELL_TESSEROID
+    // context)
+    static const tc_fn fns[] = {tess_comp_kernel<GH_COMP_POTENTIAL>, tess_comp_kernel<GH_COMP_POTENTIAL>,
+                                tess_comp_kernel<GH_COMP_GX>,        tess_comp_kernel<GH_COMP_GY>,
+                                nullptr,                             tess_comp_kernel<GH_COMP_GXX>,
+                                tess_comp_kernel<GH_COMP_GXY>,       tess_comp_kernel<GH_COMP_GXZ>,
+                                tess_comp_kernel<GH_COMP_GYY>,       tess_comp_kernel<GH_COMP_GYZ>,
+                                tess_comp_kernel<GH_COMP_GZZ>};
+    if (c->comp < 0 || c->comp > GH_COMP_GZZ || !fns[c->comp])
+        return fail(c, GH_ERR_ARG, "gh_build_G: component %d has no GH_CELL_TESSEROID_COMP kernel", c->comp);
+    int *err_cell = nullptr;
+    TessStats *stats = nullptr;
+    HIPCHK(c, hipMalloc((void **)&err_cell, sizeof(int) * (size_t)std::max<int64_t>(c->M, 1)));
+    if (hipMalloc((void **)&stats, sizeof(TessStats)) != hipSuccess) {
+        (void)hipGetLastError();
+        hipFree(err_cell);
+        return fail(c, GH_ERR_NOMEM, "gh_build_G: device allocation of the tesseroid statistics failed");
+    }
+    const int64_t N = c->N;
+    std::vector<int> herr((size_t)c->M);
+    TessStats hs{};
+    hipError_t e = hipMemsetAsync(err_cell, 0, sizeof(int) * (size_t)c->M, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(stats, 0, sizeof(TessStats), c->stream);
+    if (e == hipSuccess) {
+        const int64_t blocks = std::min<int64_t>((c->ld * c->M + 63) / 64, 1 << 24);
+        hipLaunchKernelGGL(fns[c->comp], dim3((unsigned)blocks), dim3(64), 0, c->stream, conv, conv + N, conv + 2 * N,
+                           conv + 3 * N, (const double *)c->bounds, N, c->M, c->ld, c->ratio, c->comp, G, err_cell,
+                           stats);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(herr.data(), err_cell, sizeof(int) * (size_t)c->M, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&hs, stats, sizeof hs, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipFree(err_cell);
+    hipFree(stats);
+    HIPCHK(c, e);
+    for (int v : herr)
+        if (v != 0) c->warn_cells += 1;
+    c->leaves = (int64_t)hs.leaves;
+    if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
+    return GH_OK;
+}
+
 int gh_build_G(gh_ctx *c)
 {
     if (!c) return GH_ERR_ARG;
@@ -361,6 +441,17 @@ int gh_build_G(gh_ctx *c)
     if (c->mf) {
         if (c->slab) return fail(c, GH_ERR_ARG, "gh_build_G: a matrix-free context is built once");
         c->mf_fused = c->ld <= 16384 && env_int("GRAVHMC_MF_FUSED", 1) != 0;
+        // (tesseroid components: the two-pass form, with the entry evaluated inside each pass -- no fused KIND;
+        // the near-field table and the cell-constant fast leaf are gz's)
+        if (c->cell_kind == GH_CELL_TESSEROID_COMP) c->mf_fused = false;
+        if (c->cell_kind == GH_CELL_TESSEROID_COMP) {
+            const int64_t N = c->N;
+            TRY(dalloc(c, &c->tconv, (size_t)(6 * N)));
+            tess_convert_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream>>>(
+                c->obs[0], c->obs[1], c->obs[2], N, c->tconv, c->tconv + N, c->tconv + 2 * N,
+                c->tconv + 3 * N, c->tconv + 4 * N, c->tconv + 5 * N);
+            HIPCHK(c, hipGetLastError());
+        }
         if (c->cell_kind == GH_CELL_TESSEROID) {
             const int64_t N = c->N;
             TRY(dalloc(c, &c->tconv, (size_t)(6 * N)));
@@ -379,6 +470,9 @@ int gh_build_G(gh_ctx *c)
             }
         }
         if (c->ls) TRY(lonsym_build(c));
+        // (tesseroid components: the error codes, leaves and overflow of the subdivision, as the dense build
+        // reports them, from one pass that stores nothing)
+        if (c->cell_kind == GH_CELL_TESSEROID_COMP) TRY(tess_comp_assemble(c, c->tconv, nullptr));
         TRY(configure_mf(c));
         TRY(dalloc(c, &c->mf_stats, 1));
         c->have_G = true;
@@ -423,6 +517,15 @@ int gh_build_G(gh_ctx *c)
                            c->obs[2], (const double *)c->bounds, c->N, c->M, c->ld, c->G);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else if (c->cell_kind == GH_CELL_TESSEROID_COMP) {
+        double *conv = nullptr;
+        HIPCHK(c, hipMalloc((void **)&conv, sizeof(double) * 4 * (size_t)c->N));
+        const int64_t N = c->N;
+        tess_convert_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream>>>(
+            c->obs[0], c->obs[1], c->obs[2], N, conv, conv + N, conv + 2 * N, conv + 3 * N);
+        const int rc = tess_comp_assemble(c, conv, c->G);
+        hipFree(conv);
+        TRY(rc);
     } else if (c->cell_kind == GH_CELL_TESSEROID) {
         double *conv = nullptr;
         int *err_cell = nullptr;
@@ -531,7 +634,8 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
         lonsym_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
             lonsym_geom(c), c->ls->a_of, c->ls->m_of, weightfactor, c->wm);
     } else if (c->mf) {
-        hipLaunchKernelGGL(mf_pick(c, mf_colnorm_kernel<MF_E_GEN>, mf_colnorm_kernel<MF_E_TF>, mf_colnorm_kernel<MF_E_COMP>),
+        hipLaunchKernelGGL(mf_pick(c, mf_colnorm_kernel<MF_E_GEN>, mf_colnorm_kernel<MF_E_TF>, mf_colnorm_kernel<MF_E_COMP>,
+                                   mf_colnorm_kernel<MF_E_TESS>),
                            dim3((unsigned)((c->M + 3) / 4)), dim3(256), 0, c->stream, mf_geom(c), weightfactor, c->wm);
     } else if (shard_rows(c)) {
         // row blocks: a column's norm spans the ranks -- local sums of squares, all-reduce, then the power and
@@ -860,7 +964,7 @@ int gh_compress_wavelet(gh_ctx *c, int dims, const int shape3[3], double thr, in
                 for (int64_t r0 = 0; r0 < nr; r0 += 32768) {
                     const int64_t rn = std::min<int64_t>(32768, nr - r0);
                     hipLaunchKernelGGL(mf_pick(c, mf_rows_kernel<MF_E_GEN>, mf_rows_kernel<MF_E_TF>,
-                                               mf_rows_kernel<MF_E_COMP>),
+                                               mf_rows_kernel<MF_E_COMP>, mf_rows_kernel<MF_E_TESS>),
                                        dim3((unsigned)((M + 255) / 256), (unsigned)rn), dim3(256), 0, c->stream,
                                        mf_geom(c), (const double *)c->wm, i0 + r0, rn, X + r0 * M);
                 }
@@ -1383,7 +1487,7 @@ static int kids_make(gh_ctx *c, int C, const double *x0s, const double *low, con
         k->ratio = c->ratio;
         for (int q = 0; q < 3; ++q) k->tf_dir[q] = c->tf_dir[q];
         k->tf_dir_d = c->tf_dir_d;
-        k->comp = c->comp;
+        k->comp = c->comp;  // (GH_CELL_TESSEROID_COMP never gets here: the shift-invariant store refuses it)
         k->have_obs = k->have_cells = k->have_G = true;
         k->mf = true;
         k->weighted = c->weighted;
@@ -1508,6 +1612,10 @@ int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const 
         return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of a prism gravity component other "
                                            "than gz (GH_CELL_PRISM_COMP) are not supported: store the kernel or run "
                                            "single chains");
+    if (c->mf && c->cell_kind == GH_CELL_TESSEROID_COMP)
+        return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of a tesseroid gravity component "
+                                           "other than gz (GH_CELL_TESSEROID_COMP) are not supported: store the kernel "
+                                           "or run single chains");
     HIPCHK(c, hipSetDevice(c->device));
     if (lonsym_on(c)) {
         // (the light contexts of the chains share the tables, not a compressed forward operator)

@@ -30,7 +30,7 @@ struct gh_ctx {
     double ratio = 1.6;
     double tf_dir[3] = {0.0, 0.0, 0.0};  // GH_CELL_PRISM_TF: the field direction (fx, fy, fz)
     double *tf_dir_d = nullptr;            // ... and its device copy (MfGeom::o3 of the matrix-free passes)
-    int comp = GH_COMP_GZ;                 // GH_CELL_PRISM_COMP: the gravity component (MfGeom::comp)
+    int comp = GH_COMP_GZ;                 // GH_CELL_PRISM_COMP / GH_CELL_TESSEROID_COMP: the gravity component (MfGeom::comp)
     bool have_obs = false, have_cells = false, have_G = false, weighted = false;
     double *G = nullptr;
     int64_t warn_cells = 0, leaves = 0;

@@ -112,6 +112,11 @@ static int lonsym_build(gh_ctx *c)
         h.why = why;
         return fail(c, GH_ERR_UNSUPPORTED, "shift-invariant store: %s", why);
     };
+    // (a table of a component other than gz would need the sign of the north-south mirror: gx, gxy and gxz
+    // change sign under it)
+    if (c->cell_kind == GH_CELL_TESSEROID_COMP)
+        return no("tesseroid gravity components other than gz (GH_CELL_TESSEROID_COMP) are not supported: the "
+                  "north-south mirror of the table carries no sign; store the kernel or use the matrix-free mode");
     if (c->cell_kind != GH_CELL_TESSEROID) return no("tesseroid cells only");
     const int64_t M = c->M, N = c->N;
     std::vector<double> b((size_t)M * 6), lon((size_t)N), lat((size_t)N), hh((size_t)N);

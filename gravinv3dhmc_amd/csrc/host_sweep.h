@@ -169,11 +169,12 @@ static MfGeom mf_geom(const gh_ctx *c)
 {
     MfGeom g;
     g.kind = c->cell_kind;
-    g.comp = c->cell_kind == GH_CELL_PRISM_COMP ? c->comp : 0;
+    g.comp = (c->cell_kind == GH_CELL_PRISM_COMP || c->cell_kind == GH_CELL_TESSEROID_COMP) ? c->comp : 0;
+    // (radius_u feeds gz's fast leaves only: GH_CELL_TESSEROID_COMP leaves it 0)
     g.radius_u = (c->cell_kind == GH_CELL_TESSEROID && c->obs_h_uniform) ? 6378137.0 + c->obs_h0 : 0.0;
     g.N = c->N;
     g.M = c->M;
-    if (c->cell_kind == GH_CELL_TESSEROID) {
+    if (c->cell_kind == GH_CELL_TESSEROID || c->cell_kind == GH_CELL_TESSEROID_COMP) {
         g.o0 = c->tconv;
         g.o1 = c->tconv + c->N;
         g.o2 = c->tconv + 2 * c->N;
@@ -198,15 +199,16 @@ static int mf_entry_form(const gh_ctx *c)
 {
     if (c->cell_kind == GH_CELL_PRISM_TF) return MF_E_TF;
     if (c->cell_kind == GH_CELL_PRISM_COMP) return MF_E_COMP;
+    if (c->cell_kind == GH_CELL_TESSEROID_COMP) return MF_E_TESS;
     return MF_E_GEN;  // GH_CELL_PRISM / GH_CELL_TESSEROID: by MfGeom::kind
 }
 
 // kernel<E> of a generic pass for the context's entry form
 template <typename F>
-static F mf_pick(const gh_ctx *c, F gen, F tf, F comp)
+static F mf_pick(const gh_ctx *c, F gen, F tf, F comp, F tess)
 {
     const int e = mf_entry_form(c);
-    return e == MF_E_TF ? tf : e == MF_E_COMP ? comp : gen;
+    return e == MF_E_TF ? tf : e == MF_E_COMP ? comp : e == MF_E_TESS ? tess : gen;
 }
 
 typedef void (*mf_fused_fn)(MfGeom, SweepArgs, const double *, const double *, MfNear, MfStats *);
@@ -221,6 +223,7 @@ static mf_fused_fn mf_fused_for_kind(int T, int ept)
     return mf_fused_kernel<1024, 16, KIND>;
 }
 
+// (GH_CELL_TESSEROID_COMP has no fused KIND: gh_build_G gives it the two-pass form, mf_fused = false)
 static mf_fused_fn mf_fused_for(const gh_ctx *c)
 {
     if (c->cell_kind == GH_CELL_PRISM) return mf_fused_for_kind<0>(c->mf_T, c->mf_EPT);
@@ -369,12 +372,12 @@ static int launch_mf(gh_ctx *c, SweepArgs &a)
     } else {
         if (a.mode & SW_ADJ)
             hipLaunchKernelGGL(mf_pick(c, mf_adjoint_kernel<MF_E_GEN>, mf_adjoint_kernel<MF_E_TF>,
-                                       mf_adjoint_kernel<MF_E_COMP>),
+                                       mf_adjoint_kernel<MF_E_COMP>, mf_adjoint_kernel<MF_E_TESS>),
                                dim3((unsigned)((c->M + 3) / 4)), dim3(256), 0, c->stream, g, a, wm);
         if (a.mode & SW_FWD) {
             const double *x = (a.mode & SW_UPD) ? a.x_out : a.x_in;
             hipLaunchKernelGGL(mf_pick(c, mf_forward_kernel<MF_E_GEN>, mf_forward_kernel<MF_E_TF>,
-                                       mf_forward_kernel<MF_E_COMP>),
+                                       mf_forward_kernel<MF_E_COMP>, mf_forward_kernel<MF_E_TESS>),
                                dim3((unsigned)((c->ld + 255) / 256), (unsigned)c->grid), dim3(256), 0, c->stream, g, x,
                                wm, c->mf_cells_per_chunk, c->ld, a.slab);
         }

@@ -1540,6 +1540,220 @@ __global__ void tess_convert_kernel(const double *lon, const double *lat, const 
     }
 }
 
+// ---- the other gravity fields of tesseroids (GH_CELL_TESSEROID_COMP)
+
+// The GLQ leaf of one field at one sub-tesseroid (_tesseroid_numba.py:161-332: kernelV, kernelx, kernely,
+// kernelxx ... kernelzz), unscaled, in the reference's operation order.  The potential's leaf serves the
+// geoid as well.  l_sqr**1.5 is l*sqrt(l), as tess_entry's gz leaf takes it, and l_sqr**2.5 is (l*l)*sqrt(l):
+// neither is bitwise Python's pow(), both are within a few ulp of it per node.  kernelxy,
+// kernelyy and kernelyz take cos / sin(lonc - lon), the others cos(lon - lonc), as the reference does.
+template <int LEAF>
+__device__ __forceinline__ double tess_comp_leaf(double lon, double sinlat, double coslat, double radius,
+                                                 const double (&lonc)[2], const double (&sinlatc)[2],
+                                                 const double (&coslatc)[2], const double (&rc)[2])
+{
+#pragma clang fp contract(off)
+    const double r_sqr = radius * radius;
+    double result = 0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        constexpr bool flip = LEAF == COMP_GXY || LEAF == COMP_GYY || LEAF == COMP_GYZ;
+        const double coslon = flip ? cos(lonc[i] - lon) : cos(lon - lonc[i]);
+        const double sinlon = (LEAF == COMP_GY || flip) ? sin(lonc[i] - lon) : 0.0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const double kphi = coslat * sinlatc[j] - sinlat * coslatc[j] * coslon;
+            const double cospsi = sinlat * sinlatc[j] + coslat * coslatc[j] * coslon;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const double rc_sqr = rc[k] * rc[k];
+                const double l_sqr = r_sqr + rc_sqr - 2 * radius * rc[k] * cospsi;
+                const double kappa = rc_sqr * coslatc[j];
+                const double sl = sqrt(l_sqr);
+                if (LEAF == COMP_POTENTIAL) {
+                    result += kappa / sl;
+                } else if (LEAF == COMP_GX) {
+                    result += kappa * rc[k] * kphi / (l_sqr * sl);
+                } else if (LEAF == COMP_GY) {
+                    result += kappa * (rc[k] * coslatc[j] * sinlon / (l_sqr * sl));
+                } else if (LEAF == COMP_GXX) {
+                    const double t = rc[k] * kphi;
+                    result += kappa * (3 * (t * t) - l_sqr) / ((l_sqr * l_sqr) * sl);
+                } else if (LEAF == COMP_GXY) {
+                    result += kappa * 3 * rc_sqr * kphi * coslatc[j] * sinlon / ((l_sqr * l_sqr) * sl);
+                } else if (LEAF == COMP_GXZ) {
+                    result += kappa * 3 * rc[k] * kphi * (rc[k] * cospsi - radius) / ((l_sqr * l_sqr) * sl);
+                } else if (LEAF == COMP_GYY) {
+                    const double deltay = rc[k] * coslatc[j] * sinlon;
+                    result += kappa * (3 * (deltay * deltay) - l_sqr) / ((l_sqr * l_sqr) * sl);
+                } else if (LEAF == COMP_GYZ) {
+                    const double deltay = rc[k] * coslatc[j] * sinlon;
+                    const double deltaz = rc[k] * cospsi - radius;
+                    result += kappa * 3. * deltay * deltaz / ((l_sqr * l_sqr) * sl);
+                } else {  // COMP_GZZ
+                    const double deltaz = rc[k] * cospsi - radius;
+                    result += kappa * (3 * (deltaz * deltaz) - l_sqr) / ((l_sqr * l_sqr) * sl);
+                }
+            }
+        }
+    }
+    return result;
+}
+
+// The leaf of a field chosen at run time (the matrix-free passes: one field per context, a uniform branch)
+__device__ __forceinline__ double tess_comp_leaf_rt(int comp, double lon, double sinlat, double coslat, double radius,
+                                                    const double (&lonc)[2], const double (&sinlatc)[2],
+                                                    const double (&coslatc)[2], const double (&rc)[2])
+{
+    switch (comp) {
+    case COMP_POTENTIAL:
+    case COMP_GEOID: return tess_comp_leaf<COMP_POTENTIAL>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
+    case COMP_GX: return tess_comp_leaf<COMP_GX>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
+    case COMP_GY: return tess_comp_leaf<COMP_GY>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
+    case COMP_GXX: return tess_comp_leaf<COMP_GXX>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
+    case COMP_GXY: return tess_comp_leaf<COMP_GXY>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
+    case COMP_GXZ: return tess_comp_leaf<COMP_GXZ>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
+    case COMP_GYY: return tess_comp_leaf<COMP_GYY>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
+    case COMP_GYZ: return tess_comp_leaf<COMP_GYZ>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
+    default: return tess_comp_leaf<COMP_GZZ>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
+    }
+}
+
+// The scale tesseroid.py applies to kernel2d and result once, after the sum (tesseroid.py:324-508): G for
+// the potential, G/g0 (the product formed first) for the geoid, SI2MGAL then G for gx, SI2MGAL then Gs for
+// gy -- the reference's spherical constant, 1000 times smaller than G (constants.py:32) -- and SI2EOTVOS then
+// G for the tensor.
+__device__ __forceinline__ double tess_comp_scale(int comp, double acc)
+{
+#pragma clang fp contract(off)
+    switch (comp) {
+    case COMP_POTENTIAL: return acc * 0.00000006673;
+    case COMP_GEOID: return acc * (0.00000006673 / 9.80);
+    case COMP_GX: return acc * 100000.0 * 0.00000006673;
+    case COMP_GY: return acc * 100000.0 * 0.00000000006673;
+    default: return acc * 1000000000.0 * 0.00000006673;
+    }
+}
+
+// One (observation, tesseroid) entry of a field, unscaled: tess_entry's adaptive engine (the same
+// distance_size, divisions, split and 100-entry LIFO stack; the same error-code sum, leaf count and
+// overflow flag) with the field's leaf.  LEAF < 0: the leaf of `comp`, chosen at run time.
+template <int LEAF>
+__device__ double tess_comp_entry(int comp, double lon, double sinlat, double coslat, double radius,
+                                  const double *bounds, double ratio, int &error_code, unsigned long long &nleaf,
+                                  bool &overflow)
+{
+#pragma clang fp contract(off)
+    const double MEAN_R = 6378137.0;
+    const double d2r = 3.14159265358979323846 / 180;
+    const double node[2] = {-0.577350269189625731058868041146, 0.577350269189625731058868041146};
+    double stack[TESS_STACK][6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) stack[0][q] = bounds[q];
+    int stktop = 0;
+    double acc = 0.0;
+    while (stktop >= 0) {
+        const double w = stack[stktop][0], e = stack[stktop][1], s = stack[stktop][2],
+                     n = stack[stktop][3], top = stack[stktop][4], bottom = stack[stktop][5];
+        stktop -= 1;
+        // distance_size
+        const double rt = 0.5 * (top + bottom) + MEAN_R;
+        const double lont = d2r * 0.5 * (w + e);
+        const double latt = d2r * 0.5 * (s + n);
+        const double sinlatt = sin(latt), coslatt = cos(latt);
+        const double cospsi0 = sinlat * sinlatt + coslat * coslatt * cos(lon - lont);
+        const double distance = sqrt(radius * radius + rt * rt - 2 * radius * rt * cospsi0);
+        const double rtop = top + MEAN_R;
+        const double Llon = rtop * acos(sinlatt * sinlatt + (coslatt * coslatt) * cos(d2r * (e - w)));
+        const double Llat =
+            rtop * acos(sin(d2r * n) * sin(d2r * s) + cos(d2r * n) * cos(d2r * s));
+        const double Lr = top - bottom;
+        // divisions
+        int nlon = 1, nlat = 1, nr = 1, err = 0;
+        if (distance <= ratio * Llon) {
+            if (Llon <= 0.1) err = -1; else nlon = 2;
+        }
+        if (distance <= ratio * Llat) {
+            if (Llat <= 0.1) err = -1; else nlat = 2;
+        }
+        if (distance <= ratio * Lr) {
+            if (Lr <= 1e3) err = -1; else nr = 2;
+        }
+        error_code += err;
+        const int new_cells = nlon * nlat * nr;
+        if (new_cells > 1) {
+            if (new_cells + (stktop + 1) > TESS_STACK) {
+                overflow = true;
+                break;
+            }
+            const double dlon = (e - w) / nlon, dlat = (n - s) / nlat, dr = (top - bottom) / nr;
+            for (int i = 0; i < nlon; ++i)
+                for (int j = 0; j < nlat; ++j)
+                    for (int k = 0; k < nr; ++k) {
+                        stktop += 1;
+                        stack[stktop][0] = w + i * dlon;
+                        stack[stktop][1] = w + (i + 1) * dlon;
+                        stack[stktop][2] = s + j * dlat;
+                        stack[stktop][3] = s + (j + 1) * dlat;
+                        stack[stktop][4] = bottom + (k + 1) * dr;
+                        stack[stktop][5] = bottom + k * dr;
+                    }
+        } else {
+            // scale_nodes
+            double lonc[2], sinlatc[2], coslatc[2], rc[2];
+            const double dlon = d2r * (e - w), dlat = d2r * (n - s), dr = top - bottom;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                lonc[i] = 0.5 * dlon * node[i] + d2r * 0.5 * (e + w);
+                const double latc = 0.5 * dlat * node[i] + d2r * 0.5 * (n + s);
+                sinlatc[i] = sin(latc);
+                coslatc[i] = cos(latc);
+                rc[i] = (0.5 * dr * node[i] + 0.5 * (top + bottom) + MEAN_R);
+            }
+            const double scale = dlon * dlat * dr * 0.125;
+            const double k = LEAF >= 0 ? tess_comp_leaf<(LEAF >= 0 ? LEAF : 0)>(lon, sinlat, coslat, radius, lonc,
+                                                                                 sinlatc, coslatc, rc)
+                                       : tess_comp_leaf_rt(comp, lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
+            acc += scale * k;
+            nleaf += 1;
+        }
+    }
+    return acc;
+}
+
+// Dense assembly of one field: tess_gz_kernel's layout, error codes and statistics, one thread per (obs, cell)
+// pair.  One instantiation per leaf (the geoid runs the potential's, `comp` picks the scale).  G == nullptr:
+// the error codes, leaf count and overflow flag only (the matrix-free build, which stores no entry).
+template <int LEAF>
+__global__ void __launch_bounds__(64)
+tess_comp_kernel(const double *__restrict__ lon_r, const double *__restrict__ sinlat_a,
+                 const double *__restrict__ coslat_a, const double *__restrict__ radius_a,
+                 const double *__restrict__ bounds6, int64_t N, int64_t M, int64_t ld, double ratio, int comp,
+                 double *__restrict__ G, int *__restrict__ err_cell, TessStats *stats)
+{
+    unsigned long long nleaf = 0;
+    bool overflow = false;
+    for (int64_t idx = (int64_t)blockIdx.x * 64 + threadIdx.x; idx < ld * M;
+         idx += (int64_t)gridDim.x * 64) {
+        const int64_t c = idx / ld, l = idx - c * ld;
+        if (l >= N) {
+            if (G) G[idx] = 0.0;
+            continue;
+        }
+        int error_code = 0;
+        const double v = tess_comp_entry<LEAF>(comp, lon_r[l], sinlat_a[l], coslat_a[l], radius_a[l], bounds6 + 6 * c,
+                                               ratio, error_code, nleaf, overflow);
+        if (G) G[idx] = tess_comp_scale(comp, v);
+        if (error_code != 0) atomicAdd(&err_cell[c], error_code);
+    }
+    if (overflow) atomicExch(&stats->overflow, 1);
+    // one atomic per wave for the leaf count
+    unsigned long long tot = nleaf;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) tot += __shfl_xor(tot, off, WAVE);
+    if ((threadIdx.x & 63) == 0) atomicAdd(&stats->leaves, tot);
+}
+
 // ------------------------------------------------------------- wavelet-compressed forward
 // db4 / 'periodization' analysis step along one axis of a batch of 3-D tensors, the transform
 // PyWavelets applies for gravmag/compressor3D.py:34,60 and compressor1D.py:32,54 (wavedecn /
@@ -1904,8 +2118,8 @@ ring_stats_kernel(const double *ring, int64_t M, int nvalid, double *mean, doubl
 // wm computed by mf_colnorm_kernel.
 
 struct MfGeom {
-    int kind;  // 0 prism, 1 tesseroid, 2 prism total field, 3 prism gravity component (GH_CELL_*)
-    int comp;  // kind 3: the component (COMP_*; in what was kind's padding, the struct keeps its size)
+    int kind;  // 0 prism, 1 tesseroid, 2 prism total field, 3 / 4 prism / tesseroid gravity component (GH_CELL_*)
+    int comp;  // kinds 3, 4: the component (COMP_*; in what was kind's padding, the struct keeps its size)
     double radius_u;  // tesseroids, every observation at one height: its radius R + h (else 0)
     int64_t N, M;
     const double *o0, *o1, *o2, *o3;  // prism: x,y,z,- (total field: x,y,z,(fx,fy,fz))  tesseroid: lon_r, sinlat, coslat, radius
@@ -1917,18 +2131,23 @@ static_assert(sizeof(MfGeom) == 96, "MfGeom is a kernel argument of every matrix
 
 // The entry form of the generic passes below: MF_E_GEN = g.kind 0 prism gz / 1 tesseroid, MF_E_TF = the
 // prisms' total-field entry (GH_CELL_PRISM_TF; the field direction is the three doubles at g.o3), MF_E_COMP =
-// a prism gravity component (GH_CELL_PRISM_COMP; g.comp).  The passes are templated on it so that the gz and
-// tesseroid instantiations keep their register budget.
-enum { MF_E_GEN = 0, MF_E_TF = 1, MF_E_COMP = 2 };
+// a prism gravity component (GH_CELL_PRISM_COMP; g.comp), MF_E_TESS = a tesseroid gravity component
+// (GH_CELL_TESSEROID_COMP; g.comp: tess_comp_entry with the leaf chosen at run time, scaled as the dense
+// assembly scales it).  The passes are templated on it so that the gz and tesseroid instantiations keep their
+// register budget.
+enum { MF_E_GEN = 0, MF_E_TF = 1, MF_E_COMP = 2, MF_E_TESS = 3 };
 template <int E>
 __device__ __forceinline__ double mf_entry(const MfGeom &g, int64_t i, const double *b)
 {
     if (E == MF_E_TF) return prism_tf_entry(g.o0[i], g.o1[i], g.o2[i], b, g.o3[0], g.o3[1], g.o3[2]);
     if (E == MF_E_COMP) return prism_comp_entry_rt(g.comp, g.o0[i], g.o1[i], g.o2[i], b);
-    if (g.kind == 0) return prism_entry(g.o0[i], g.o1[i], g.o2[i], b);
+    if (E != MF_E_TESS && g.kind == 0) return prism_entry(g.o0[i], g.o1[i], g.o2[i], b);
     int err = 0;
     unsigned long long nl = 0;
     bool ov = false;
+    if (E == MF_E_TESS)
+        return tess_comp_scale(g.comp, tess_comp_entry<-1>(g.comp, g.o0[i], g.o1[i], g.o2[i], g.o3[i], b, g.ratio,
+                                                           err, nl, ov));
     return tess_entry(g.o0[i], g.o1[i], g.o2[i], g.o3[i], b, g.ratio, err, nl, ov);
 }
 

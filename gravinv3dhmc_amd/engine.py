@@ -94,14 +94,26 @@ class Engine(object):
     def set_cells(self, bounds6, kind, ratio=1.6, direction=None, component=None):
         """kind CELL_PRISM / CELL_TESSEROID (ratio: the tesseroid distance-size ratio), or CELL_PRISM_TF with
         direction = (fx, fy, fz), the unit vector of the regional field (utils.dircos(inc, dec)).
-        component (prisms, kind CELL_PRISM or CELL_PRISM_COMP): the gravity field, a name of
-        _lib.COMPONENTS or a COMP_* value; "gz" is kind CELL_PRISM itself (gh_set_cells_prism)."""
+        component (kind CELL_PRISM or CELL_PRISM_COMP for prisms, CELL_TESSEROID or CELL_TESSEROID_COMP for
+        tesseroids): the gravity field, a name of _lib.COMPONENTS or a COMP_* value; "gz" is kind CELL_PRISM /
+        CELL_TESSEROID itself (gh_set_cells_prism / gh_set_cells_tess)."""
         b = f64(bounds6)
         if b.shape != (self.M, 6):
             raise ValueError("bounds table must be (M, 6)")
+        if int(kind) in (_lib.CELL_TESSEROID, _lib.CELL_TESSEROID_COMP) and \
+                (component is not None or int(kind) == _lib.CELL_TESSEROID_COMP):
+            comp = _lib.COMPONENTS.get(component, -1) if isinstance(component, str) else component
+            if comp not in _lib.COMPONENTS.values():
+                raise ValueError("component must be one of %s" % ", ".join(_lib.COMPONENTS))
+            if comp == _lib.COMP_GZ:   # (today's call: the same context)
+                self._chk(self._lib.gh_set_cells(self._h, ptr(b), _lib.CELL_TESSEROID, float(ratio)))
+            else:
+                self._chk(self._lib.gh_set_cells_tess(self._h, ptr(b), int(comp), float(ratio)))
+            return
         if component is not None or int(kind) == _lib.CELL_PRISM_COMP:
             if int(kind) not in (_lib.CELL_PRISM, _lib.CELL_PRISM_COMP):
-                raise ValueError("a gravity component is a field of prisms (kind CELL_PRISM / CELL_PRISM_COMP)")
+                raise ValueError("a gravity component is a field of prisms or tesseroids (kind CELL_PRISM / "
+                                 "CELL_PRISM_COMP / CELL_TESSEROID / CELL_TESSEROID_COMP)")
             comp = _lib.COMPONENTS.get(component, -1) if isinstance(component, str) else component
             if comp not in _lib.COMPONENTS.values():
                 raise ValueError("component must be one of %s" % ", ".join(_lib.COMPONENTS))

@@ -7,8 +7,9 @@
  * `gravmag/_prism.pyx:265-290` (`_prism.gz`) and `gravmag/_tesseroid_numba.py:32-71,335`
  * (`_tesseroid_numba.gz`).  Prisms also carry the reference's other fields: the total-field magnetic
  * anomaly (`_prism.tf`, gh_set_cells_tf) and the ten other gravity fields -- potential, geoid, gx, gy and
- * the gradient tensor gxx ... gzz (`_prism.pyx:36-68, 206-509`, gh_set_cells_prism).  Every entry point
- * below names the reference interface it replaces.
+ * the gradient tensor gxx ... gzz (`_prism.pyx:36-68, 206-509`, gh_set_cells_prism).  Tesseroids carry
+ * the same ten other gravity fields (`_tesseroid_numba.py:161-341`, gh_set_cells_tess).  Every entry
+ * point below names the reference interface it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer of the reference would add.
  *
  * Conventions
@@ -75,9 +76,12 @@ typedef enum {
 } gh_status;
 
 /* GH_CELL_PRISM_TF: prisms, total-field magnetic anomaly (set with gh_set_cells_tf, not gh_set_cells);
- * GH_CELL_PRISM_COMP: prisms, one gravity field other than gz (set with gh_set_cells_prism) */
-enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2, GH_CELL_PRISM_COMP = 3 };
-/* The gravity fields of prisms (gravmag/prism.py:875-972), for gh_set_cells_prism */
+ * GH_CELL_PRISM_COMP: prisms, one gravity field other than gz (set with gh_set_cells_prism);
+ * GH_CELL_TESSEROID_COMP: tesseroids, one gravity field other than gz (set with gh_set_cells_tess) */
+enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2, GH_CELL_PRISM_COMP = 3, GH_CELL_TESSEROID_COMP = 4 };
+/* The gravity fields of prisms (gravmag/prism.py:875-972), for gh_set_cells_prism, and of tesseroids
+ * (gravmag/tesseroid.py:324-508), for gh_set_cells_tess (gy of tesseroids: G * SI2MGAL with the
+ * reference's spherical G, Gs = 6.673e-11, 1000 times smaller than the G of every other field) */
 enum {
     GH_COMP_POTENTIAL = 0, /* G, per g/cm^3 (SI otherwise) */
     GH_COMP_GEOID = 1,     /* G / g0: the potential over 9.80 m/s^2, in m */
@@ -142,6 +146,19 @@ int gh_set_cells_prism(gh_ctx *ctx, const double *bounds6, int component);
  * mesh order into one sum per observation and scaled once, as the reference does.  Unsharded contexts
  * only (GH_ERR_UNSUPPORTED otherwise). */
 int gh_prism_result(gh_ctx *ctx, const double *dens, double *result);
+/* Tesseroids of a density model for one gravity field `component` (GH_COMP_*), M x 6 row-major
+ * w,e,s,n,top,bottom in mesh order, ratio > 0 the distance-size ratio of the adaptive subdivision
+ * (tesseroid.py: RATIO_V = 1 for the potential and geoid, RATIO_G = 1.6 for gx / gy / gz, RATIO_GG = 8
+ * for the tensor).  Every cell must have w <= e, s <= n, top >= bottom (GH_ERR_ARG otherwise).  Entry (i, j) is _tesseroid_numba.<field>'s kernel2d entry scaled as tesseroid.py
+ * scales it: G for the potential, G/g0 for the geoid, G*SI2MGAL for gx, Gs*SI2MGAL for gy (the
+ * reference's spherical constant), G*SI2EOTVOS for the tensor.  GH_COMP_GZ makes a GH_CELL_TESSEROID
+ * context, the same bits as gh_set_cells(kind 1); every other component a GH_CELL_TESSEROID_COMP one.
+ * gh_build_G reports the error-code cells and leaves as for kind 1 and GH_ERR_OVERFLOW when the
+ * 100-entry subdivision stack overflows, on a matrix-free context too (one extra pass over the pairs
+ * that stores nothing).  Every stored-kernel path and the matrix-free two-pass form run on it; the
+ * shift-invariant store, the matrix-free batch of chains and gh_prism_result refuse it with
+ * GH_ERR_UNSUPPORTED. */
+int gh_set_cells_tess(gh_ctx *ctx, const double *bounds6, int component, double ratio);
 /* Matrix-free mode (call before gh_build_G): the kernel matrix is never stored; the prism /
  * tesseroid entries are re-evaluated where they are needed.  With N <= 16384 observations a
  * leapfrog step evaluates every entry ONCE (a workgroup keeps a cell's column on the chip between
