@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -163,6 +164,25 @@ int gh_set_obs(gh_ctx *c, const double *a, const double *b, const double *cc)
     return GH_OK;
 }
 
+// The cells and how the kernels read them: the bounds, the kind, the component (GH_COMP_GZ for kinds 0 to 2),
+// the tesseroids' ratio and, for the total field, its direction.
+static int set_cells(gh_ctx *c, const double *bounds6, int kind, int comp, double ratio, const double *dir = nullptr)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
+    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
+    if (dir) {
+        std::copy(dir, dir + 3, c->tf_dir);
+        TRY(dalloc(c, &c->tf_dir_d, 3));
+        TRY(h2d(c, c->tf_dir_d, c->tf_dir, 3));
+    }
+    c->cell_kind = kind;
+    c->comp = comp;
+    c->ratio = ratio;
+    c->have_cells = true;
+    return GH_OK;
+}
+
 int gh_set_cells(gh_ctx *c, const double *bounds6, int kind, double ratio)
 {
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells: null pointer");
@@ -170,13 +190,7 @@ int gh_set_cells(gh_ctx *c, const double *bounds6, int kind, double ratio)
         return fail(c, GH_ERR_ARG, "gh_set_cells: kind must be 0 (prism) or 1 (tesseroid)");
     if (kind == GH_CELL_TESSEROID && !(ratio > 0))
         return fail(c, GH_ERR_ARG, "Invalid ratio %g. Must be > 0.", ratio);
-    HIPCHK(c, hipSetDevice(c->device));
-    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
-    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
-    c->cell_kind = kind;
-    c->ratio = ratio;
-    c->have_cells = true;
-    return GH_OK;
+    return set_cells(c, bounds6, kind, GH_COMP_GZ, ratio);
 }
 
 int gh_set_cells_tf(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
@@ -184,16 +198,34 @@ int gh_set_cells_tf(gh_ctx *c, const double *bounds6, double fx, double fy, doub
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_tf: null pointer");
     if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(fz))
         return fail(c, GH_ERR_ARG, "gh_set_cells_tf: the field direction must be finite");
+    const double dir[3] = {fx, fy, fz};
+    return set_cells(c, bounds6, GH_CELL_PRISM_TF, GH_COMP_GZ, c->ratio, dir);
+}
+
+// The result passes' scaffolding: upload n_in doubles, enqueue launch(device input, device result of N doubles)
+// on the context's stream, download the result.
+static int run_result(gh_ctx *c, const char *who, const double *in, size_t n_in, double *result,
+                      const std::function<void(const double *, double *)> &launch)
+{
     HIPCHK(c, hipSetDevice(c->device));
-    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
-    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
-    c->cell_kind = GH_CELL_PRISM_TF;
-    c->tf_dir[0] = fx;
-    c->tf_dir[1] = fy;
-    c->tf_dir[2] = fz;
-    TRY(dalloc(c, &c->tf_dir_d, 3));
-    TRY(h2d(c, c->tf_dir_d, c->tf_dir, 3));
-    c->have_cells = true;
+    double *din = nullptr, *dres = nullptr;
+    HIPCHK(c, hipMalloc((void **)&din, sizeof(double) * std::max<size_t>(n_in, 1)));
+    if (hipMalloc((void **)&dres, sizeof(double) * (size_t)std::max<int64_t>(c->N, 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        hipFree(din);
+        return fail(c, GH_ERR_NOMEM, "%s: device allocation of %lld doubles failed", who, (long long)c->N);
+    }
+    hipError_t e = hipMemcpyAsync(din, in, sizeof(double) * n_in, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch(din, dres);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(result, dres, sizeof(double) * (size_t)c->N, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipFree(din);
+    hipFree(dres);
+    HIPCHK(c, e);
     return GH_OK;
 }
 
@@ -205,28 +237,11 @@ int gh_tf_result(gh_ctx *c, const double *mag3, double *result)
         return fail(c, GH_ERR_ARG, "gh_tf_result: the cells are not a total-field magnetic model (gh_set_cells_tf)");
     if (c->sh.kind != 0)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_tf_result: the magnetic field's result runs on an unsharded context");
-    HIPCHK(c, hipSetDevice(c->device));
-    double *dmag = nullptr, *dres = nullptr;
-    HIPCHK(c, hipMalloc((void **)&dmag, sizeof(double) * 3 * (size_t)std::max<int64_t>(c->M, 1)));
-    if (hipMalloc((void **)&dres, sizeof(double) * (size_t)std::max<int64_t>(c->N, 1)) != hipSuccess) {
-        (void)hipGetLastError();
-        hipFree(dmag);
-        return fail(c, GH_ERR_NOMEM, "gh_tf_result: device allocation of %lld doubles failed", (long long)c->N);
-    }
-    hipError_t e = hipMemcpyAsync(dmag, mag3, sizeof(double) * 3 * (size_t)c->M, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
+    return run_result(c, "gh_tf_result", mag3, 3 * (size_t)c->M, result, [c](const double *dmag, double *dres) {
         prism_tf_result_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(
             c->obs[0], c->obs[1], c->obs[2], c->bounds, dmag, c->N, c->M, c->tf_dir[0], c->tf_dir[1], c->tf_dir[2],
             dres);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(result, dres, sizeof(double) * (size_t)c->N, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(dmag);
-    hipFree(dres);
-    HIPCHK(c, e);
-    return GH_OK;
+    });
 }
 
 int gh_set_cells_prism(gh_ctx *c, const double *bounds6, int component)
@@ -237,13 +252,7 @@ int gh_set_cells_prism(gh_ctx *c, const double *bounds6, int component)
                     component);
     // gz is the prism kind of gh_set_cells: the same context, the same kernels, the same bits
     if (component == GH_COMP_GZ) return gh_set_cells(c, bounds6, GH_CELL_PRISM, 1.6);
-    HIPCHK(c, hipSetDevice(c->device));
-    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
-    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
-    c->cell_kind = GH_CELL_PRISM_COMP;
-    c->comp = component;
-    c->have_cells = true;
-    return GH_OK;
+    return set_cells(c, bounds6, GH_CELL_PRISM_COMP, component, c->ratio);
 }
 
 int gh_set_cells_tess(gh_ctx *c, const double *bounds6, int component, double ratio)
@@ -262,14 +271,7 @@ int gh_set_cells_tess(gh_ctx *c, const double *bounds6, int component, double ra
     // gz is the tesseroid kind of gh_set_cells: the same context, the same kernels, the same bits
     if (component == GH_COMP_GZ) return gh_set_cells(c, bounds6, GH_CELL_TESSEROID, ratio);
     if (!(ratio > 0)) return fail(c, GH_ERR_ARG, "Invalid ratio %g. Must be > 0.", ratio);
-    HIPCHK(c, hipSetDevice(c->device));
-    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
-    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
-    c->cell_kind = GH_CELL_TESSEROID_COMP;
-    c->comp = component;
-    c->ratio = ratio;
-    c->have_cells = true;
-    return GH_OK;
+    return set_cells(c, bounds6, GH_CELL_TESSEROID_COMP, component, ratio);
 }
 
 int gh_prism_result(gh_ctx *c, const double *dens, double *result)
@@ -283,28 +285,10 @@ int gh_prism_result(gh_ctx *c, const double *dens, double *result)
         return fail(c, GH_ERR_ARG, "gh_prism_result: the cells are not a prism density model (gh_set_cells_prism)");
     if (c->sh.kind != 0)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_prism_result: the prism result runs on an unsharded context");
-    const int comp = c->cell_kind == GH_CELL_PRISM_COMP ? c->comp : GH_COMP_GZ;
-    HIPCHK(c, hipSetDevice(c->device));
-    double *ddens = nullptr, *dres = nullptr;
-    HIPCHK(c, hipMalloc((void **)&ddens, sizeof(double) * (size_t)std::max<int64_t>(c->M, 1)));
-    if (hipMalloc((void **)&dres, sizeof(double) * (size_t)std::max<int64_t>(c->N, 1)) != hipSuccess) {
-        (void)hipGetLastError();
-        hipFree(ddens);
-        return fail(c, GH_ERR_NOMEM, "gh_prism_result: device allocation of %lld doubles failed", (long long)c->N);
-    }
-    hipError_t e = hipMemcpyAsync(ddens, dens, sizeof(double) * (size_t)c->M, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
+    return run_result(c, "gh_prism_result", dens, (size_t)c->M, result, [c](const double *ddens, double *dres) {
         prism_comp_result_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], c->bounds, ddens, c->N, c->M, comp, dres);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(result, dres, sizeof(double) * (size_t)c->N, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(ddens);
-    hipFree(dres);
-    HIPCHK(c, e);
-    return GH_OK;
+            c->obs[0], c->obs[1], c->obs[2], c->bounds, ddens, c->N, c->M, c->comp, dres);
+    });
 }
 
 int gh_set_matrix_free(gh_ctx *c, int enable)
@@ -381,22 +365,19 @@ int gh_set_matrix_free_exact(gh_ctx *c, int exact)
 }
 
 // tess_comp_kernel of the context's component over all (observation, cell) pairs: G (ld x M) when G is given,
-// else the statistics alone; warn_cells, leaves, and GH_ERR_OVERFLOW as the gz build reports them.  conv: the
-// converted observations (lon rad, sin lat, cos lat, radius; N each).
+// else the statistics alone; warn_cells, leaves, and GH_ERR_OVERFLOW.  conv: the converted observations (lon
+// rad, sin lat, cos lat, radius; N each).
 static int tess_comp_assemble(gh_ctx *c, const double *conv, double *G)
 {
     typedef void (*tc_fn)(const double *, const double *, const double *, const double *, const double *, int64_t,
                           int64_t, int64_t, double, int, double *, int *, TessStats *);
-    // (indexed by GH_COMP_*: one instantiation per leaf, the geoid runs the potential's; gz is a GH_CELL_TESSEROID
-    // context)
+    // (indexed by GH_COMP_*: one instantiation per leaf, the geoid runs the potential's)
     static const tc_fn fns[] = {tess_comp_kernel<GH_COMP_POTENTIAL>, tess_comp_kernel<GH_COMP_POTENTIAL>,
                                 tess_comp_kernel<GH_COMP_GX>,        tess_comp_kernel<GH_COMP_GY>,
-                                nullptr,                             tess_comp_kernel<GH_COMP_GXX>,
+                                tess_comp_kernel<GH_COMP_GZ>,        tess_comp_kernel<GH_COMP_GXX>,
                                 tess_comp_kernel<GH_COMP_GXY>,       tess_comp_kernel<GH_COMP_GXZ>,
                                 tess_comp_kernel<GH_COMP_GYY>,       tess_comp_kernel<GH_COMP_GYZ>,
                                 tess_comp_kernel<GH_COMP_GZZ>};
-    if (c->comp < 0 || c->comp > GH_COMP_GZZ || !fns[c->comp])
-        return fail(c, GH_ERR_ARG, "gh_build_G: component %d has no GH_CELL_TESSEROID_COMP kernel", c->comp);
     int *err_cell = nullptr;
     TessStats *stats = nullptr;
     HIPCHK(c, hipMalloc((void **)&err_cell, sizeof(int) * (size_t)std::max<int64_t>(c->M, 1)));
@@ -444,7 +425,7 @@ int gh_build_G(gh_ctx *c)
         // (tesseroid components: the two-pass form, with the entry evaluated inside each pass -- no fused KIND;
         // the near-field table and the cell-constant fast leaf are gz's)
         if (c->cell_kind == GH_CELL_TESSEROID_COMP) c->mf_fused = false;
-        if (c->cell_kind == GH_CELL_TESSEROID_COMP) {
+        if (c->cell_kind == GH_CELL_TESSEROID || c->cell_kind == GH_CELL_TESSEROID_COMP) {
             const int64_t N = c->N;
             TRY(dalloc(c, &c->tconv, (size_t)(6 * N)));
             tess_convert_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream>>>(
@@ -453,12 +434,6 @@ int gh_build_G(gh_ctx *c)
             HIPCHK(c, hipGetLastError());
         }
         if (c->cell_kind == GH_CELL_TESSEROID) {
-            const int64_t N = c->N;
-            TRY(dalloc(c, &c->tconv, (size_t)(6 * N)));
-            tess_convert_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream>>>(
-                c->obs[0], c->obs[1], c->obs[2], N, c->tconv, c->tconv + N, c->tconv + 2 * N,
-                c->tconv + 3 * N, c->tconv + 4 * N, c->tconv + 5 * N);
-            HIPCHK(c, hipGetLastError());
             c->mf_exact = c->mf_exact_req >= 0 ? c->mf_exact_req != 0 : env_int("GRAVHMC_MF_EXACT", 0) != 0;
             {
                 // what depends on the cell alone, once per cell instead of once per (obs, cell) pair
@@ -486,38 +461,23 @@ int gh_build_G(gh_ctx *c)
                     "N = %lld: more than 16384 observations per device: shard the observations or use "
                     "the matrix-free mode (gh_set_matrix_free)", (long long)c->N);
     TRY(dalloc(c, &c->G, (size_t)c->ld * (size_t)c->M, false));
-    const int64_t total = c->ld * c->M;
-    if (c->cell_kind == GH_CELL_PRISM) {
-        const int64_t blocks = std::min<int64_t>((total + 255) / 256, 1 << 22);
-        prism_gz_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], c->bounds, c->N, c->M, c->ld, c->G);
+    if (c->cell_kind == GH_CELL_PRISM || c->cell_kind == GH_CELL_PRISM_TF || c->cell_kind == GH_CELL_PRISM_COMP) {
+        typedef void (*prism_fn)(const double *, const double *, const double *, const double *, int64_t, int64_t,
+                                 int64_t, double3, double *);
+        // (indexed by GH_COMP_*, then the total field)
+        static const prism_fn fns[] = {prism_kernel<GH_COMP_POTENTIAL>, prism_kernel<GH_COMP_GEOID>,
+                                       prism_kernel<GH_COMP_GX>,        prism_kernel<GH_COMP_GY>,
+                                       prism_kernel<GH_COMP_GZ>,        prism_kernel<GH_COMP_GXX>,
+                                       prism_kernel<GH_COMP_GXY>,       prism_kernel<GH_COMP_GXZ>,
+                                       prism_kernel<GH_COMP_GYY>,       prism_kernel<GH_COMP_GYZ>,
+                                       prism_kernel<GH_COMP_GZZ>,       prism_kernel<PRISM_TF>};
+        const int64_t blocks = std::min<int64_t>((c->ld * c->M + 255) / 256, 1 << 22);
+        hipLaunchKernelGGL(fns[c->cell_kind == GH_CELL_PRISM_TF ? PRISM_TF : c->comp], dim3((unsigned)blocks), dim3(256),
+                           0, c->stream, c->obs[0], c->obs[1], c->obs[2], (const double *)c->bounds, c->N, c->M, c->ld,
+                           make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), c->G);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else if (c->cell_kind == GH_CELL_PRISM_TF) {
-        const int64_t blocks = std::min<int64_t>((total + 255) / 256, 1 << 22);
-        prism_tf_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], c->bounds, c->N, c->M, c->ld, c->tf_dir[0], c->tf_dir[1],
-            c->tf_dir[2], c->G);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else if (c->cell_kind == GH_CELL_PRISM_COMP) {
-        typedef void (*comp_fn)(const double *, const double *, const double *, const double *, int64_t, int64_t,
-                                int64_t, double *);
-        // (indexed by GH_COMP_*; gz is a GH_CELL_PRISM context)
-        static const comp_fn fns[] = {prism_comp_kernel<GH_COMP_POTENTIAL>, prism_comp_kernel<GH_COMP_GEOID>,
-                                      prism_comp_kernel<GH_COMP_GX>,        prism_comp_kernel<GH_COMP_GY>,
-                                      nullptr,                              prism_comp_kernel<GH_COMP_GXX>,
-                                      prism_comp_kernel<GH_COMP_GXY>,       prism_comp_kernel<GH_COMP_GXZ>,
-                                      prism_comp_kernel<GH_COMP_GYY>,       prism_comp_kernel<GH_COMP_GYZ>,
-                                      prism_comp_kernel<GH_COMP_GZZ>};
-        if (c->comp < 0 || c->comp > GH_COMP_GZZ || !fns[c->comp])
-            return fail(c, GH_ERR_ARG, "gh_build_G: component %d has no GH_CELL_PRISM_COMP kernel", c->comp);
-        const int64_t blocks = std::min<int64_t>((total + 255) / 256, 1 << 22);
-        hipLaunchKernelGGL(fns[c->comp], dim3((unsigned)blocks), dim3(256), 0, c->stream, c->obs[0], c->obs[1],
-                           c->obs[2], (const double *)c->bounds, c->N, c->M, c->ld, c->G);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else if (c->cell_kind == GH_CELL_TESSEROID_COMP) {
+    } else if (c->cell_kind == GH_CELL_TESSEROID || c->cell_kind == GH_CELL_TESSEROID_COMP) {
         double *conv = nullptr;
         HIPCHK(c, hipMalloc((void **)&conv, sizeof(double) * 4 * (size_t)c->N));
         const int64_t N = c->N;
@@ -526,36 +486,6 @@ int gh_build_G(gh_ctx *c)
         const int rc = tess_comp_assemble(c, conv, c->G);
         hipFree(conv);
         TRY(rc);
-    } else if (c->cell_kind == GH_CELL_TESSEROID) {
-        double *conv = nullptr;
-        int *err_cell = nullptr;
-        TessStats *stats = nullptr;
-        HIPCHK(c, hipMalloc((void **)&conv, sizeof(double) * 4 * (size_t)c->N));
-        HIPCHK(c, hipMalloc((void **)&err_cell, sizeof(int) * (size_t)c->M));
-        HIPCHK(c, hipMalloc((void **)&stats, sizeof(TessStats)));
-        HIPCHK(c, hipMemsetAsync(err_cell, 0, sizeof(int) * (size_t)c->M, c->stream));
-        HIPCHK(c, hipMemsetAsync(stats, 0, sizeof(TessStats), c->stream));
-        const int64_t N = c->N;
-        tess_convert_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], N, conv, conv + N, conv + 2 * N, conv + 3 * N);
-        const int64_t blocks = std::min<int64_t>((total + 63) / 64, 1 << 24);
-        tess_gz_kernel<<<dim3((unsigned)blocks), dim3(64), 0, c->stream>>>(
-            conv, conv + N, conv + 2 * N, conv + 3 * N, c->bounds, N, c->M, c->ld, c->ratio, c->G,
-            err_cell, stats);
-        HIPCHK(c, hipGetLastError());
-        std::vector<int> herr((size_t)c->M);
-        TessStats hs;
-        HIPCHK(c, hipMemcpyAsync(herr.data(), err_cell, sizeof(int) * (size_t)c->M,
-                                 hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(&hs, stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(conv);
-        hipFree(err_cell);
-        hipFree(stats);
-        for (int v : herr)
-            if (v != 0) c->warn_cells += 1;
-        c->leaves = (int64_t)hs.leaves;
-        if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
     } else {
         return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: unknown cell kind %d", c->cell_kind);
     }

@@ -6,8 +6,8 @@
 
 // ------------------------------------------------ batched chains on the matrix-free kernel (mfbatch.hip.h)
 
-// (GH_CELL_PRISM_TF, GH_CELL_PRISM_COMP and GH_CELL_TESSEROID_COMP have no batch kernels: gh_batch_init and
-// mfb_plan refuse a matrix-free magnetic or gravity-component context before any of these is asked for)
+// (GH_CELL_PRISM_TF, GH_CELL_PRISM_COMP and GH_CELL_TESSEROID_COMP have no batch kernels: gh_batch_init refuses
+// a matrix-free magnetic or gravity-component context before any of these is asked for)
 static int mfb_kind(const gh_ctx *c)
 {
     if (c->cell_kind == GH_CELL_PRISM) return 0;
@@ -229,14 +229,6 @@ static int mft_failed(gh_ctx *c, bool *failed)
 static int mfb_plan(gh_ctx *c)
 {
     gh_ctx::Batch &b = c->bt;
-    if (c->cell_kind == GH_CELL_PRISM_TF)
-        return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of the magnetic field are not supported");
-    if (c->cell_kind == GH_CELL_PRISM_COMP)
-        return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of a prism gravity component other "
-                                           "than gz are not supported");
-    if (c->cell_kind == GH_CELL_TESSEROID_COMP)
-        return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of a tesseroid gravity component "
-                                           "other than gz are not supported");
     const int64_t ntiles = (c->M + 15) / 16;
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(mfb_adj_for(c)), MFB_LDS_ADJ));
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(mfb_fwd_for(c)), MFB_LDS_FWD));

@@ -226,8 +226,8 @@ static int lonsym_build(gh_ctx *c)
     tess_convert_kernel<<<dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, c->stream>>>(
         d_so, d_so + Np, d_so + 2 * Np, Np, conv, conv + Np, conv + 2 * Np, conv + 3 * Np);
     const int64_t total = h.ldT * nc;
-    tess_gz_kernel<<<dim3((unsigned)std::min<int64_t>((total + 63) / 64, 1 << 24)), dim3(64), 0, c->stream>>>(
-        conv, conv + Np, conv + 2 * Np, conv + 3 * Np, d_sb, Np, nc, h.ldT, c->ratio, h.T, err_cell, stats);
+    tess_comp_kernel<COMP_GZ><<<dim3((unsigned)std::min<int64_t>((total + 63) / 64, 1 << 24)), dim3(64), 0, c->stream>>>(
+        conv, conv + Np, conv + 2 * Np, conv + 3 * Np, d_sb, Np, nc, h.ldT, c->ratio, COMP_GZ, h.T, err_cell, stats);
     HIPCHK(c, hipGetLastError());
     TessStats hs;
     std::vector<int> herr((size_t)nc);

@@ -169,7 +169,7 @@ static MfGeom mf_geom(const gh_ctx *c)
 {
     MfGeom g;
     g.kind = c->cell_kind;
-    g.comp = (c->cell_kind == GH_CELL_PRISM_COMP || c->cell_kind == GH_CELL_TESSEROID_COMP) ? c->comp : 0;
+    g.comp = c->comp;
     // (radius_u feeds gz's fast leaves only: GH_CELL_TESSEROID_COMP leaves it 0)
     g.radius_u = (c->cell_kind == GH_CELL_TESSEROID && c->obs_h_uniform) ? 6378137.0 + c->obs_h0 : 0.0;
     g.N = c->N;

@@ -1052,13 +1052,16 @@ __device__ __forceinline__ double safe_log_d(double x)
     return log(x);
 }
 
-// One (observation, prism) entry in mGal per g/cm^3: G*SI2MGAL * sum over the 8 corners of
-// (-1)^(i+j+k) kernelz (prism.py:291-316, _prism.pyx:49-50,265-290).
-__device__ __forceinline__ double prism_entry(double px, double py, double pz, const double *b)
+// The 8-corner sum of every prism field (_prism.pyx's loops): acc plus, over the corners of the prism b
+// (k: z2, z1; then j: y2, y1; then i: x2, x1), (-1)^(i+j+k) corner(dx, dy, dz) with (dx, dy, dz) = corner -
+// observation, into the one accumulator in this order.  The result forms fold the density or the
+// magnetization into corner(): multiplying by the sign +-1 is exact, so where it happens changes no bit.
+template <class F>
+__device__ __forceinline__ double prism_corners(double acc, double px, double py, double pz, const double *b,
+                                                F corner)
 {
 #pragma clang fp contract(off)
     const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
-    double acc = 0.0;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const double dz = Z[k] - pz;
@@ -1068,93 +1071,48 @@ __device__ __forceinline__ double prism_entry(double px, double py, double pz, c
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const double dx = X[i] - px;
-                const double r = sqrt(dx * dx + dy * dy + dz * dz);
-                const double kern = -(dx * safe_log_d(dy + r) + dy * safe_log_d(dx + r) -
-                                      dz * safe_atan2_d(dx * dy, dz * r));
                 const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
-                acc += sign * kern;
+                acc += sign * corner(dx, dy, dz);
             }
         }
     }
-    return acc * (0.00000006673 * 100000.0);
-}
-
-// Dense assembly: one thread per (obs, cell) entry, obs fastest (coalesced store).
-__global__ void __launch_bounds__(256)
-prism_gz_kernel(const double *__restrict__ xp, const double *__restrict__ yp,
-                const double *__restrict__ zp, const double *__restrict__ bounds6, int64_t N,
-                int64_t M, int64_t ld, double *__restrict__ G)
-{
-    // grid-stride: a launch is limited to 2^32 work-items, ld*M reaches 5*10^9 at C2
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ld * M;
-         idx += (int64_t)gridDim.x * 256) {
-        const int64_t c = idx / ld, l = idx - c * ld;
-        G[idx] = (l < N) ? prism_entry(xp[l], yp[l], zp[l], bounds6 + 6 * c) : 0.0;
-    }
+    return acc;
 }
 
 // CM * T2NT of the reference (constants.py:37,41): 10**-7 * 10**6 rounds to 0.09999999999999999; entries in
 // uT per A/m of magnetization along the field (T2NT is 10**6 there, not the 10**9 of an nT scale)
 #define TF_SCALE (1e-7 * 1e6)
 
-// The six second derivatives of 1/r at one corner (_prism.pyx:52-78: kernelxx, xy, xz, yy, yz, zz)
-__device__ __forceinline__ void prism_tf_corner(double dx, double dy, double dz, double r, double &v1, double &v2,
-                                                double &v3, double &v4, double &v5, double &v6)
+// f.(V m) at one corner, V the six second derivatives of 1/r there (_prism.pyx:52-78: kernelxx, xy, xz, yy,
+// yz, zz), in the reference's order -- b = V m first, then f.b (_prism.pyx:80-113, prism.py:665-733), not the
+// shorter quadratic form, which rounds differently.
+__device__ __forceinline__ double prism_tf_corner(double dx, double dy, double dz, double mx, double my, double mz,
+                                                  double fx, double fy, double fz)
 {
 #pragma clang fp contract(off)
-    v1 = -safe_atan2_d(dz * dy, dx * r);
-    v2 = safe_log_d(dz + r);
-    v3 = safe_log_d(dy + r);
-    v4 = -safe_atan2_d(dz * dx, dy * r);
-    v5 = safe_log_d(dx + r);
-    v6 = -safe_atan2_d(dx * dy, dz * r);
+    const double r = sqrt(dx * dx + dy * dy + dz * dz);
+    const double v1 = -safe_atan2_d(dz * dy, dx * r);
+    const double v2 = safe_log_d(dz + r);
+    const double v3 = safe_log_d(dy + r);
+    const double v4 = -safe_atan2_d(dz * dx, dy * r);
+    const double v5 = safe_log_d(dx + r);
+    const double v6 = -safe_atan2_d(dx * dy, dz * r);
+    const double bx = v1 * mx + v2 * my + v3 * mz;
+    const double by = v2 * mx + v4 * my + v5 * mz;
+    const double bz = v3 * mx + v5 * my + v6 * mz;
+    return fx * bx + fy * by + fz * bz;
 }
 
 // One (observation, prism) entry of the total-field anomaly for a unit magnetization along the field
-// direction (fx, fy, fz) = dircos(inc, dec): CM*T2NT * sum over the 8 corners of (-1)^(i+j+k) f.(V f) in the
-// reference's order -- bk = V f first, then f.bk (_prism.pyx:80-113, prism.py:665-733), not the shorter
-// quadratic form, which rounds differently.
+// direction (fx, fy, fz) = dircos(inc, dec): CM*T2NT * the corner sum of f.(V f).
 __device__ __forceinline__ double prism_tf_entry(double px, double py, double pz, const double *b, double fx,
                                                  double fy, double fz)
 {
 #pragma clang fp contract(off)
-    const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const double dz = Z[k] - pz;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const double dy = Y[j] - py;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const double dx = X[i] - px;
-                const double r = sqrt(dx * dx + dy * dy + dz * dz);
-                double v1, v2, v3, v4, v5, v6;
-                prism_tf_corner(dx, dy, dz, r, v1, v2, v3, v4, v5, v6);
-                const double bxk = v1 * fx + v2 * fy + v3 * fz;
-                const double byk = v2 * fx + v4 * fy + v5 * fz;
-                const double bzk = v3 * fx + v5 * fy + v6 * fz;
-                const double kern = fx * bxk + fy * byk + fz * bzk;
-                const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
-                acc += sign * kern;
-            }
-        }
-    }
+    const double acc = prism_corners(0.0, px, py, pz, b, [&](double dx, double dy, double dz) {
+        return prism_tf_corner(dx, dy, dz, fx, fy, fz, fx, fy, fz);
+    });
     return acc * TF_SCALE;
-}
-
-// Dense assembly of the total-field kernel: the layout of prism_gz_kernel (obs fastest, zero padding rows)
-__global__ void __launch_bounds__(256)
-prism_tf_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
-                const double *__restrict__ bounds6, int64_t N, int64_t M, int64_t ld, double fx, double fy,
-                double fz, double *__restrict__ G)
-{
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ld * M;
-         idx += (int64_t)gridDim.x * 256) {
-        const int64_t c = idx / ld, l = idx - c * ld;
-        G[idx] = (l < N) ? prism_tf_entry(xp[l], yp[l], zp[l], bounds6 + 6 * c, fx, fy, fz) : 0.0;
-    }
 }
 
 // prism.tf's `result` (prism.py:665-733): one thread per observation, the cells in mesh order, ONE sum per
@@ -1172,30 +1130,10 @@ prism_tf_result_kernel(const double *__restrict__ xp, const double *__restrict__
     const double px = xp[l], py = yp[l], pz = zp[l];
     double acc = 0.0;
     for (int64_t c = 0; c < M; ++c) {
-        const double *b = bounds6 + 6 * c;
         const double mx = mag3[3 * c], my = mag3[3 * c + 1], mz = mag3[3 * c + 2];
-        const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const double dz = Z[k] - pz;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const double dy = Y[j] - py;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const double dx = X[i] - px;
-                    const double r = sqrt(dx * dx + dy * dy + dz * dz);
-                    double v1, v2, v3, v4, v5, v6;
-                prism_tf_corner(dx, dy, dz, r, v1, v2, v3, v4, v5, v6);
-                    const double bx = v1 * mx + v2 * my + v3 * mz;
-                    const double by = v2 * mx + v4 * my + v5 * mz;
-                    const double bz = v3 * mx + v5 * my + v6 * mz;
-                    const double kern = fx * bx + fy * by + fz * bz;
-                    const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
-                    acc += sign * kern;
-                }
-            }
-        }
+        acc = prism_corners(acc, px, py, pz, bounds6 + 6 * c, [&](double dx, double dy, double dz) {
+            return prism_tf_corner(dx, dy, dz, mx, my, mz, fx, fy, fz);
+        });
     }
     res[l] = acc * TF_SCALE;
 }
@@ -1258,35 +1196,21 @@ __device__ __forceinline__ double prism_comp_corner(double dx, double dy, double
     return -safe_atan2_d(dx * dy, dz * r);  // COMP_GZZ
 }
 
-// One (observation, prism) entry of a component for a density of 1: scale * the sum over the 8 corners
-// (k: z2, z1; then j; then i) of (-1)^(i+j+k) kernel, one accumulator (prism.py:102-662 with _prism.pyx's
-// loops).  prism_comp_entry<COMP_GZ> is prism_entry's arithmetic.
+// One (observation, prism) entry of a component for a density of 1: scale * the corner sum of its kernel
+// (prism.py:102-662 with _prism.pyx's loops).
 template <int COMP>
 __device__ __forceinline__ double prism_comp_entry(double px, double py, double pz, const double *b)
 {
 #pragma clang fp contract(off)
-    const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const double dz = Z[k] - pz;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const double dy = Y[j] - py;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const double dx = X[i] - px;
-                const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
-                acc += sign * prism_comp_corner<COMP>(dx, dy, dz, b);
-            }
-        }
-    }
+    const double acc = prism_corners(0.0, px, py, pz, b, [&](double dx, double dy, double dz) {
+        return prism_comp_corner<COMP>(dx, dy, dz, b);
+    });
     return acc * prism_comp_scale<COMP>();
 }
 
 // The entry of a component chosen at run time (the matrix-free passes: one component per context, so the
-// branch is uniform).  gz is not among them: a gz context is GH_CELL_PRISM and runs prism_entry.  Two
-// families, so that a pass can hold the one it runs: the tensor (one log or atan2 per corner) and the
+// branch is uniform).  gz is not among them: a gz context is GH_CELL_PRISM and runs prism_comp_entry<COMP_GZ>.
+// Two families, so that a pass can hold the one it runs: the tensor (one log or atan2 per corner) and the
 // potential / geoid / gx / gy (six or three per corner).
 __device__ __forceinline__ double prism_field_entry_rt(int comp, double px, double py, double pz, const double *b)
 {
@@ -1315,17 +1239,28 @@ __device__ __forceinline__ double prism_comp_entry_rt(int comp, double px, doubl
     return comp >= COMP_GXX ? prism_tensor_entry_rt(comp, px, py, pz, b) : prism_field_entry_rt(comp, px, py, pz, b);
 }
 
-// Dense assembly of one component: the layout of prism_gz_kernel (obs fastest, zero padding rows to ld,
-// grid-stride).  One instantiation per component, so that each keeps its own register budget.
-template <int COMP>
+// Dense assembly of one prism field F (COMP_* or PRISM_TF, whose direction is dir): one thread per (obs, cell)
+// entry, obs fastest (coalesced store), zero padding rows to ld.  One instantiation per field, so that each
+// keeps its own register budget.
+constexpr int PRISM_TF = COMP_GZZ + 1;
+template <int F>
 __global__ void __launch_bounds__(256)
-prism_comp_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
-                  const double *__restrict__ bounds6, int64_t N, int64_t M, int64_t ld, double *__restrict__ G)
+prism_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
+             const double *__restrict__ bounds6, int64_t N, int64_t M, int64_t ld, double3 dir,
+             double *__restrict__ G)
 {
+    // grid-stride: a launch is limited to 2^32 work-items, ld*M reaches 5*10^9 at C2
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ld * M;
          idx += (int64_t)gridDim.x * 256) {
         const int64_t c = idx / ld, l = idx - c * ld;
-        G[idx] = (l < N) ? prism_comp_entry<COMP>(xp[l], yp[l], zp[l], bounds6 + 6 * c) : 0.0;
+        double v = 0.0;
+        if (l < N) {
+            if constexpr (F == PRISM_TF)
+                v = prism_tf_entry(xp[l], yp[l], zp[l], bounds6 + 6 * c, dir.x, dir.y, dir.z);
+            else
+                v = prism_comp_entry<F>(xp[l], yp[l], zp[l], bounds6 + 6 * c);
+        }
+        G[idx] = v;
     }
 }
 
@@ -1339,21 +1274,9 @@ __device__ __forceinline__ double prism_comp_result_one(double px, double py, do
     for (int64_t c = 0; c < M; ++c) {
         const double *b = bounds6 + 6 * c;
         const double d = dens[c];
-        const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const double dz = Z[k] - pz;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const double dy = Y[j] - py;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const double dx = X[i] - px;
-                    const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
-                    acc += sign * prism_comp_corner<COMP>(dx, dy, dz, b) * d;
-                }
-            }
-        }
+        acc = prism_corners(acc, px, py, pz, b, [&](double dx, double dy, double dz) {
+            return prism_comp_corner<COMP>(dx, dy, dz, b) * d;
+        });
     }
     return acc * prism_comp_scale<COMP>();
 }
@@ -1393,133 +1316,6 @@ struct TessStats {
     int overflow;
 };
 
-// Adaptive 2x2x2 Gauss-Legendre tesseroid gz entry (_tesseroid_numba.py:32-71, 75-157,
-// 207-222) with a private LIFO stack of sub-tesseroids; mGal per g/cm^3.  err accumulates the
-// engine's error codes (non-zero => the reference warns), nleaf counts GLQ leaves.
-__device__ double tess_entry(double lon, double sinlat, double coslat, double radius,
-                             const double *bounds, double ratio, int &error_code,
-                             unsigned long long &nleaf, bool &overflow)
-{
-#pragma clang fp contract(off)
-    const double MEAN_R = 6378137.0;
-    const double d2r = 3.14159265358979323846 / 180;
-    const double node[2] = {-0.577350269189625731058868041146, 0.577350269189625731058868041146};
-    double stack[TESS_STACK][6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) stack[0][q] = bounds[q];
-    int stktop = 0;
-    double acc = 0.0;
-    while (stktop >= 0) {
-        const double w = stack[stktop][0], e = stack[stktop][1], s = stack[stktop][2],
-                     n = stack[stktop][3], top = stack[stktop][4], bottom = stack[stktop][5];
-        stktop -= 1;
-        // distance_size
-        const double rt = 0.5 * (top + bottom) + MEAN_R;
-        const double lont = d2r * 0.5 * (w + e);
-        const double latt = d2r * 0.5 * (s + n);
-        const double sinlatt = sin(latt), coslatt = cos(latt);
-        const double cospsi0 = sinlat * sinlatt + coslat * coslatt * cos(lon - lont);
-        const double distance = sqrt(radius * radius + rt * rt - 2 * radius * rt * cospsi0);
-        const double rtop = top + MEAN_R;
-        const double Llon = rtop * acos(sinlatt * sinlatt + (coslatt * coslatt) * cos(d2r * (e - w)));
-        const double Llat =
-            rtop * acos(sin(d2r * n) * sin(d2r * s) + cos(d2r * n) * cos(d2r * s));
-        const double Lr = top - bottom;
-        // divisions
-        int nlon = 1, nlat = 1, nr = 1, err = 0;
-        if (distance <= ratio * Llon) {
-            if (Llon <= 0.1) err = -1; else nlon = 2;
-        }
-        if (distance <= ratio * Llat) {
-            if (Llat <= 0.1) err = -1; else nlat = 2;
-        }
-        if (distance <= ratio * Lr) {
-            if (Lr <= 1e3) err = -1; else nr = 2;
-        }
-        error_code += err;
-        const int new_cells = nlon * nlat * nr;
-        if (new_cells > 1) {
-            if (new_cells + (stktop + 1) > TESS_STACK) {
-                overflow = true;
-                break;
-            }
-            const double dlon = (e - w) / nlon, dlat = (n - s) / nlat, dr = (top - bottom) / nr;
-            for (int i = 0; i < nlon; ++i)
-                for (int j = 0; j < nlat; ++j)
-                    for (int k = 0; k < nr; ++k) {
-                        stktop += 1;
-                        stack[stktop][0] = w + i * dlon;
-                        stack[stktop][1] = w + (i + 1) * dlon;
-                        stack[stktop][2] = s + j * dlat;
-                        stack[stktop][3] = s + (j + 1) * dlat;
-                        stack[stktop][4] = bottom + (k + 1) * dr;
-                        stack[stktop][5] = bottom + k * dr;
-                    }
-        } else {
-            double lonc[2], sinlatc[2], coslatc[2], rc[2];
-            const double dlon = d2r * (e - w), dlat = d2r * (n - s), dr = top - bottom;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                lonc[i] = 0.5 * dlon * node[i] + d2r * 0.5 * (e + w);
-                const double latc = 0.5 * dlat * node[i] + d2r * 0.5 * (n + s);
-                sinlatc[i] = sin(latc);
-                coslatc[i] = cos(latc);
-                rc[i] = (0.5 * dr * node[i] + 0.5 * (top + bottom) + MEAN_R);
-            }
-            const double scale = dlon * dlat * dr * 0.125;
-            const double r_sqr = radius * radius;
-            double result = 0;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const double coslon = cos(lon - lonc[i]);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const double cospsi = sinlat * sinlatc[j] + coslat * coslatc[j] * coslon;
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const double l_sqr = r_sqr + rc[k] * rc[k] - 2 * radius * rc[k] * cospsi;
-                        const double kappa = (rc[k] * rc[k]) * coslatc[j];
-                        result += kappa * (rc[k] * cospsi - radius) / (l_sqr * sqrt(l_sqr));
-                    }
-                }
-            }
-            result *= -1;
-            acc += scale * result;
-            nleaf += 1;
-        }
-    }
-    return acc * 100000.0 * 0.00000006673;
-}
-
-// Dense assembly, one thread per (obs, cell) pair.
-__global__ void __launch_bounds__(64)
-tess_gz_kernel(const double *__restrict__ lon_r, const double *__restrict__ sinlat_a,
-               const double *__restrict__ coslat_a, const double *__restrict__ radius_a,
-               const double *__restrict__ bounds6, int64_t N, int64_t M, int64_t ld, double ratio,
-               double *__restrict__ G, int *__restrict__ err_cell, TessStats *stats)
-{
-    unsigned long long nleaf = 0;
-    bool overflow = false;
-    for (int64_t idx = (int64_t)blockIdx.x * 64 + threadIdx.x; idx < ld * M;
-         idx += (int64_t)gridDim.x * 64) {
-        const int64_t c = idx / ld, l = idx - c * ld;
-        if (l >= N) {
-            G[idx] = 0.0;
-            continue;
-        }
-        int error_code = 0;
-        G[idx] = tess_entry(lon_r[l], sinlat_a[l], coslat_a[l], radius_a[l], bounds6 + 6 * c, ratio,
-                            error_code, nleaf, overflow);
-        if (error_code != 0) atomicAdd(&err_cell[c], error_code);
-    }
-    if (overflow) atomicExch(&stats->overflow, 1);
-    // one atomic per wave for the leaf count
-    unsigned long long tot = nleaf;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) tot += __shfl_xor(tot, off, WAVE);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&stats->leaves, tot);
-}
-
 // obs (lon, lat, height) -> (lon rad, sin lat, cos lat, R + h)   (tesseroid.py:109-123)
 __global__ void tess_convert_kernel(const double *lon, const double *lat, const double *h,
                                     int64_t N, double *lon_r, double *sinlat, double *coslat,
@@ -1543,8 +1339,8 @@ __global__ void tess_convert_kernel(const double *lon, const double *lat, const 
 // ---- the other gravity fields of tesseroids (GH_CELL_TESSEROID_COMP)
 
 // The GLQ leaf of one field at one sub-tesseroid (_tesseroid_numba.py:161-332: kernelV, kernelx, kernely,
-// kernelxx ... kernelzz), unscaled, in the reference's operation order.  The potential's leaf serves the
-// geoid as well.  l_sqr**1.5 is l*sqrt(l), as tess_entry's gz leaf takes it, and l_sqr**2.5 is (l*l)*sqrt(l):
+// kernelz, kernelxx ... kernelzz), unscaled, in the reference's operation order.  The potential's leaf serves the
+// geoid as well.  l_sqr**1.5 is l*sqrt(l), and l_sqr**2.5 is (l*l)*sqrt(l):
 // neither is bitwise Python's pow(), both are within a few ulp of it per node.  kernelxy,
 // kernelyy and kernelyz take cos / sin(lonc - lon), the others cos(lon - lonc), as the reference does.
 template <int LEAF>
@@ -1576,6 +1372,8 @@ __device__ __forceinline__ double tess_comp_leaf(double lon, double sinlat, doub
                     result += kappa * rc[k] * kphi / (l_sqr * sl);
                 } else if (LEAF == COMP_GY) {
                     result += kappa * (rc[k] * coslatc[j] * sinlon / (l_sqr * sl));
+                } else if (LEAF == COMP_GZ) {
+                    result += kappa * (rc[k] * cospsi - radius) / (l_sqr * sl);
                 } else if (LEAF == COMP_GXX) {
                     const double t = rc[k] * kphi;
                     result += kappa * (3 * (t * t) - l_sqr) / ((l_sqr * l_sqr) * sl);
@@ -1597,6 +1395,7 @@ __device__ __forceinline__ double tess_comp_leaf(double lon, double sinlat, doub
             }
         }
     }
+    if (LEAF == COMP_GZ) result *= -1;
     return result;
 }
 
@@ -1621,23 +1420,26 @@ __device__ __forceinline__ double tess_comp_leaf_rt(int comp, double lon, double
 
 // The scale tesseroid.py applies to kernel2d and result once, after the sum (tesseroid.py:324-508): G for
 // the potential, G/g0 (the product formed first) for the geoid, SI2MGAL then G for gx, SI2MGAL then Gs for
-// gy -- the reference's spherical constant, 1000 times smaller than G (constants.py:32) -- and SI2EOTVOS then
-// G for the tensor.
+// gy -- the reference's spherical constant, 1000 times smaller than G (constants.py:32) -- SI2MGAL then G for
+// gz, and SI2EOTVOS then G for the tensor.
 __device__ __forceinline__ double tess_comp_scale(int comp, double acc)
 {
 #pragma clang fp contract(off)
     switch (comp) {
     case COMP_POTENTIAL: return acc * 0.00000006673;
     case COMP_GEOID: return acc * (0.00000006673 / 9.80);
-    case COMP_GX: return acc * 100000.0 * 0.00000006673;
+    case COMP_GX:
+    case COMP_GZ: return acc * 100000.0 * 0.00000006673;
     case COMP_GY: return acc * 100000.0 * 0.00000000006673;
     default: return acc * 1000000000.0 * 0.00000006673;
     }
 }
 
-// One (observation, tesseroid) entry of a field, unscaled: tess_entry's adaptive engine (the same
-// distance_size, divisions, split and 100-entry LIFO stack; the same error-code sum, leaf count and
-// overflow flag) with the field's leaf.  LEAF < 0: the leaf of `comp`, chosen at run time.
+// One (observation, tesseroid) entry of a field, unscaled: the reference's adaptive 2x2x2 Gauss-Legendre
+// engine (_tesseroid_numba.py:32-71, 75-157, 207-222: distance_size, divisions, split) with a private
+// 100-entry LIFO stack of sub-tesseroids and the field's leaf.  error_code accumulates the engine's error
+// codes (non-zero => the reference warns), nleaf counts GLQ leaves, overflow flags a full stack.  LEAF < 0:
+// the leaf of `comp`, chosen at run time.
 template <int LEAF>
 __device__ double tess_comp_entry(int comp, double lon, double sinlat, double coslat, double radius,
                                   const double *bounds, double ratio, int &error_code, unsigned long long &nleaf,
@@ -1721,9 +1523,10 @@ __device__ double tess_comp_entry(int comp, double lon, double sinlat, double co
     return acc;
 }
 
-// Dense assembly of one field: tess_gz_kernel's layout, error codes and statistics, one thread per (obs, cell)
-// pair.  One instantiation per leaf (the geoid runs the potential's, `comp` picks the scale).  G == nullptr:
-// the error codes, leaf count and overflow flag only (the matrix-free build, which stores no entry).
+// Dense assembly of one field, one thread per (obs, cell) pair, obs fastest, zero padding rows to ld; the error
+// codes summed per cell into err_cell, the leaf count and the overflow flag into stats.  One instantiation
+// per leaf: the leaf fixes the scale, except the potential's, which serves the geoid too (`comp` picks its
+// scale).  G == nullptr: the statistics only (the matrix-free build, which stores no entry).
 template <int LEAF>
 __global__ void __launch_bounds__(64)
 tess_comp_kernel(const double *__restrict__ lon_r, const double *__restrict__ sinlat_a,
@@ -1743,7 +1546,7 @@ tess_comp_kernel(const double *__restrict__ lon_r, const double *__restrict__ si
         int error_code = 0;
         const double v = tess_comp_entry<LEAF>(comp, lon_r[l], sinlat_a[l], coslat_a[l], radius_a[l], bounds6 + 6 * c,
                                                ratio, error_code, nleaf, overflow);
-        if (G) G[idx] = tess_comp_scale(comp, v);
+        if (G) G[idx] = tess_comp_scale(LEAF == COMP_POTENTIAL ? comp : LEAF, v);
         if (error_code != 0) atomicAdd(&err_cell[c], error_code);
     }
     if (overflow) atomicExch(&stats->overflow, 1);
@@ -2141,14 +1944,15 @@ __device__ __forceinline__ double mf_entry(const MfGeom &g, int64_t i, const dou
 {
     if (E == MF_E_TF) return prism_tf_entry(g.o0[i], g.o1[i], g.o2[i], b, g.o3[0], g.o3[1], g.o3[2]);
     if (E == MF_E_COMP) return prism_comp_entry_rt(g.comp, g.o0[i], g.o1[i], g.o2[i], b);
-    if (E != MF_E_TESS && g.kind == 0) return prism_entry(g.o0[i], g.o1[i], g.o2[i], b);
+    if (E != MF_E_TESS && g.kind == 0) return prism_comp_entry<COMP_GZ>(g.o0[i], g.o1[i], g.o2[i], b);
     int err = 0;
     unsigned long long nl = 0;
     bool ov = false;
     if (E == MF_E_TESS)
         return tess_comp_scale(g.comp, tess_comp_entry<-1>(g.comp, g.o0[i], g.o1[i], g.o2[i], g.o3[i], b, g.ratio,
                                                            err, nl, ov));
-    return tess_entry(g.o0[i], g.o1[i], g.o2[i], g.o3[i], b, g.ratio, err, nl, ov);
+    return tess_comp_scale(COMP_GZ, tess_comp_entry<COMP_GZ>(COMP_GZ, g.o0[i], g.o1[i], g.o2[i], g.o3[i], b, g.ratio,
+                                                             err, nl, ov));
 }
 
 // wm_j = (sum_i K_ij^2)^wf: one wave per cell, lanes over observations
@@ -2270,7 +2074,7 @@ mf_rows_kernel(MfGeom g, const double *__restrict__ wm, int64_t i0, int64_t nrow
 // the two acos, the 2x2x2 GLQ nodes with their sin/cos -- is evaluated once per cell by
 // tess_cellconst_kernel (11 of the 14 trigonometric calls of a pair that needs no subdivision, and
 // that is 99.9 % of the pairs of the global model) with the same expressions, hence the same bits,
-// as tess_entry; a pair whose root must be subdivided (or flags an error) takes tess_entry itself.
+// as tess_comp_entry<COMP_GZ>; a pair whose root must be subdivided (or flags an error) takes the engine itself.
 
 constexpr int TESS_NC = 32;  // doubles per cell in the table of cell constants
 
@@ -2345,13 +2149,14 @@ __device__ __noinline__ double tess_entry_slow(double lon, double sinlat, double
     int err = 0;
     unsigned long long nl = 0;
     bool ov = false;
-    const double v = tess_entry(lon, sinlat, coslat, radius, bounds, ratio, err, nl, ov);
+    const double v =
+        tess_comp_scale(COMP_GZ, tess_comp_entry<COMP_GZ>(COMP_GZ, lon, sinlat, coslat, radius, bounds, ratio, err, nl, ov));
     nleaf += (unsigned)nl;
     return v;
 }
 
 // The root taken as ONE 2x2x2 GLQ leaf (a pair that needs no subdivision), from the cell's constants:
-// the bits tess_entry produces for such a pair.
+// the bits tess_comp_entry<COMP_GZ> produces for such a pair.
 __device__ __forceinline__ double tess_leaf_cc(double lon, double sinlat, double coslat, double radius,
                                                const double *__restrict__ cc)
 {
@@ -2482,7 +2287,7 @@ __device__ __forceinline__ double tess_leaf_fast_ru(double sinlon, double coslon
 }
 
 // Does the pair need more than the root leaf (subdivision, or an error flag)?  The root's
-// distance / size test of tess_entry (_tesseroid_numba.py:94-111,135-157) with the same bits.
+// distance / size test of tess_comp_entry (_tesseroid_numba.py:94-111,135-157) with the same bits.
 __device__ __forceinline__ bool tess_is_near_cc(double lon, double sinlat, double coslat, double radius,
                                                 const double *__restrict__ cc)
 {
@@ -2492,7 +2297,7 @@ __device__ __forceinline__ bool tess_is_near_cc(double lon, double sinlat, doubl
     return (distance <= cc[5]) || (distance <= cc[6]) || (distance <= cc[7]);
 }
 
-// One (observation, tesseroid) entry from the cell's constants; same bits as tess_entry.
+// One (observation, tesseroid) entry from the cell's constants; same bits as tess_comp_entry<COMP_GZ>.
 __device__ __forceinline__ double tess_entry_cc(double lon, double sinlat, double coslat, double radius,
                                                 const double *__restrict__ cc, const double *bounds, double ratio,
                                                 unsigned &nleaf)
@@ -2507,13 +2312,13 @@ __device__ __forceinline__ double tess_entry_cc(double lon, double sinlat, doubl
 // and those pairs (0.02 % of the global model's 5.3*10^8, but 50 .. 2000 times the work of a far
 // pair each, and concentrated in the columns of the top layer and of the poles) are what unbalances
 // the matrix-free pass.  They are found once (count + ordered fill, one workgroup per column),
-// their entries evaluated once by tess_entry and kept as a sparse per-column list (row index,
+// their entries evaluated once by the adaptive engine and kept as a sparse per-column list (row index,
 // value); the per-step pass evaluates the root leaf for every pair and then overwrites the listed
 // rows.  Everything else of G is still never stored.
 struct MfNear {
     const int64_t *ptr;  // M + 1
     const int *row;      // ptr[M]
-    const double *val;   // ptr[M], entries in mGal per g/cm^3 (unweighted, like tess_entry)
+    const double *val;   // ptr[M], entries in mGal per g/cm^3 (unweighted, like the dense G)
 };
 
 __global__ void __launch_bounds__(256)
@@ -2687,7 +2492,7 @@ mf_fused_kernel(MfGeom g, SweepArgs a, const double *__restrict__ wm, const doub
                 double v = 0.0;
                 if (i < N) {
                     if (KIND == 0) {
-                        v = prism_entry(g.o0[i], g.o1[i], g.o2[i], b);
+                        v = prism_comp_entry<COMP_GZ>(g.o0[i], g.o1[i], g.o2[i], b);
                         nleaf += 1;
                     } else if (KIND == 5) {
                         v = prism_tf_entry(g.o0[i], g.o1[i], g.o2[i], b, fx, fy, fz);

@@ -10,7 +10,7 @@
 //     observations i -> (a_i, m_i)     a = class of equal (latitude, height), lon_i = lon_ref + m_i * dlon
 // the whole matrix is  K[i, (c, k)] = T[c][a_i][(m_i - k) mod n]:  n_c x n_a x n numbers (C4: 600 x 61 x
 // 120 doubles = 35 MB, L2 / Infinity-Cache resident) instead of N x M (4.25 GB) or 5.3e8 evaluations
-// per step.  The table is built once with the reference's own adaptive engine (tess_gz_kernel on the
+// per step.  The table is built once with the reference's own adaptive engine (tess_comp_kernel<COMP_GZ> on the
 // synthetic problem "every class at every shift against the cells of longitude index 0": near-field
 // pairs included, same subdivision decisions).  Forward and adjoint become circular correlations
 // along the longitude, per (class, cell row):

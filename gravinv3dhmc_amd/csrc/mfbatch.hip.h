@@ -18,7 +18,7 @@
 // Both passes share the evaluation phase: a workgroup of 16 waves stages a tile of 16 columns x 512
 // rows in LDS, wave w evaluating column w of the tile with the lane = row layout and the column's
 // constants in scalar registers (the single-chain pass's arithmetic: tess_leaf_fast / tess_leaf_cc
-// / tess_entry_cc / prism_entry, unchanged).  Two staging buffers: the next chunk is evaluated
+// / tess_entry_cc / prism_comp_entry<COMP_GZ>, unchanged).  Two staging buffers: the next chunk is evaluated
 // while the MFMAs consume this one, one barrier per chunk.  The rows' observation constants come
 // from LDS as well (fetched by the whole workgroup one chunk ahead): as per-lane global loads in
 // front of every evaluation -- 16 waves x the same rows -- the compiler's software pipeline ended up
@@ -132,7 +132,7 @@ __device__ __forceinline__ double mfb_eval(const MfbCol<KIND> &c, const MfGeom &
 {
     if constexpr (KIND == 0) {
         nleaf += 1;
-        return prism_entry(o[0], o[1], o[2], c.b);
+        return prism_comp_entry<COMP_GZ>(o[0], o[1], o[2], c.b);
     } else if constexpr (KIND == 1) {
         return tess_entry_cc(o[0], o[1], o[2], o[3], c.ccp, c.bp, g.ratio, nleaf);
     } else if constexpr (KIND == 2) {
