@@ -151,14 +151,15 @@ int gh_set_obs(gh_ctx *c, const double *a, const double *b, const double *cc)
     if (!c || !a || !b || !cc) return fail(c, GH_ERR_ARG, "gh_set_obs: null pointer");
     HIPCHK(c, hipSetDevice(c->device));
     const double *src[3] = {a, b, cc};
+    const int64_t n = c->joint ? c->N / 2 : c->N;  // (joint store: both blocks share the N/2 points)
     for (int i = 0; i < 3; ++i) {
-        TRY(dalloc(c, &c->obs[i], (size_t)c->N));
-        TRY(h2d(c, c->obs[i], src[i], (size_t)c->N));
+        TRY(dalloc(c, &c->obs[i], (size_t)n));
+        TRY(h2d(c, c->obs[i], src[i], (size_t)n));
     }
     // (tesseroids: one height for all observations lets the matrix-free batch hoist what depends on
     // the radius alone out of the entries, mfbatch.hip.h)
     c->obs_h_uniform = true;
-    for (int64_t i = 1; i < c->N && c->obs_h_uniform; ++i) c->obs_h_uniform = cc[i] == cc[0];
+    for (int64_t i = 1; i < n && c->obs_h_uniform; ++i) c->obs_h_uniform = cc[i] == cc[0];
     c->obs_h0 = cc[0];
     c->have_obs = true;
     return GH_OK;
@@ -168,6 +169,7 @@ int gh_set_obs(gh_ctx *c, const double *a, const double *b, const double *cc)
 // the tesseroids' ratio and, for the total field, its direction.
 static int set_cells(gh_ctx *c, const double *bounds6, int kind, int comp, double ratio, const double *dir = nullptr)
 {
+    if (c->joint) return fail(c, GH_ERR_UNSUPPORTED, "a joint gravity-magnetic context takes its cells from gh_set_cells_joint");
     HIPCHK(c, hipSetDevice(c->device));
     TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
     TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
@@ -200,6 +202,97 @@ int gh_set_cells_tf(gh_ctx *c, const double *bounds6, double fx, double fy, doub
         return fail(c, GH_ERR_ARG, "gh_set_cells_tf: the field direction must be finite");
     const double dir[3] = {fx, fy, fz};
     return set_cells(c, bounds6, GH_CELL_PRISM_TF, GH_COMP_GZ, c->ratio, dir);
+}
+
+int gh_set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
+{
+    if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_joint: null pointer");
+    if (c->N % 2 != 0 || c->M % 2 != 0)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_joint: N and M must be even (the stacked gz + tf lengths)");
+    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(fz))
+        return fail(c, GH_ERR_ARG, "gh_set_cells_joint: the field direction must be finite");
+    if (c->have_obs || c->have_cells || c->have_G || c->slab)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_joint: call it first on a fresh context (before gh_set_obs)");
+    if (c->mf || c->ls)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_joint: the joint kernel is dense only (no matrix-free mode, "
+                                           "no shift-invariant store)");
+    if (c->sh.kind != 0) return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_joint: the joint kernel is not sharded");
+    if (c->N / 2 > 16384)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_joint: N/2 = %lld observations: the joint kernel takes at "
+                                           "most 16384 (no row panels or team sweep)", (long long)(c->N / 2));
+    HIPCHK(c, hipSetDevice(c->device));
+    // the store has N/2 rows: its ld and the sweep's partition (each block on its own) follow from that
+    const int64_t ld0 = c->ld;
+    const bool ok0 = c->dense_ok;
+    c->joint = true;
+    c->ld = (c->N / 2 + 15) / 16 * 16;
+    c->dense_ok = true;
+    const int rc = configure_sweep(c);
+    if (rc != GH_OK) {
+        c->joint = false;
+        c->ld = ld0;
+        c->dense_ok = ok0;
+        (void)configure_sweep(c);
+        return rc;
+    }
+    const double dir[3] = {fx, fy, fz};
+    // (bounds: M/2 cells; the kind's data lives with the first half of the context's M)
+    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
+    TRY(h2d(c, c->bounds, bounds6, (size_t)(c->M / 2) * 6));
+    std::copy(dir, dir + 3, c->tf_dir);
+    TRY(dalloc(c, &c->tf_dir_d, 3));
+    TRY(h2d(c, c->tf_dir_d, c->tf_dir, 3));
+    c->cell_kind = GH_CELL_PRISM_JOINT;
+    c->comp = GH_COMP_GZ;
+    c->have_cells = true;
+    return GH_OK;
+}
+
+int gh_joint_std(const gh_ctx *c, double std2[2])
+{
+    if (!c || !std2) return GH_ERR_ARG;
+    if (!c->joint || !c->weighted) return GH_ERR_ARG;
+    std2[0] = c->joint_std[0];
+    std2[1] = c->joint_std[1];
+    return GH_OK;
+}
+
+int gh_joint_layout(const gh_ctx *c, int *workgroups_per_block, int *epilogue_stages)
+{
+    if (!c || !c->joint) return GH_ERR_ARG;
+    if (workgroups_per_block) *workgroups_per_block = c->grid / 2;
+    if (epilogue_stages) *epilogue_stages = joint_two_stage(c) ? 2 : 1;
+    return GH_OK;
+}
+
+// An observation-space vector of N doubles between the host and the device: as it is, or -- joint store --
+// its two halves to / from [gz: ld | tf: ld]
+static int h2d_obsvec(gh_ctx *c, double *dst, const double *src)
+{
+    if (!c->joint) return h2d(c, dst, src, (size_t)c->N);
+    const size_t n = (size_t)(c->N / 2);
+    HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)c->ld * sizeof(double), src, n * sizeof(double), n * sizeof(double), 2,
+                               hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GH_OK;
+}
+
+static int d2h_obsvec(gh_ctx *c, double *dst, const double *src)
+{
+    if (!c->joint) return d2h(c, dst, src, (size_t)c->N);
+    const size_t n = (size_t)(c->N / 2);
+    HIPCHK(c, hipMemcpy2DAsync(dst, n * sizeof(double), src, (size_t)c->ld * sizeof(double), n * sizeof(double), 2,
+                               hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GH_OK;
+}
+
+static int joint_refuse(gh_ctx *c, const char *who)
+{
+    if (c && c->joint)
+        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the joint gravity-magnetic kernel (dense, single chain)",
+                    who);
+    return GH_OK;
 }
 
 // The result passes' scaffolding: upload n_in doubles, enqueue launch(device input, device result of N doubles)
@@ -294,6 +387,7 @@ int gh_prism_result(gh_ctx *c, const double *dens, double *result)
 int gh_set_matrix_free(gh_ctx *c, int enable)
 {
     if (!c) return GH_ERR_ARG;
+    if (enable) TRY(joint_refuse(c, "gh_set_matrix_free"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_matrix_free: call before gh_build_G");
     if (c->ls) {
         c->mf_before_ls = enable != 0;  // (takes effect when the shift-invariant store is switched off)
@@ -306,6 +400,7 @@ int gh_set_matrix_free(gh_ctx *c, int enable)
 int gh_set_shift_invariant(gh_ctx *c, int enable)
 {
     if (!c) return GH_ERR_ARG;
+    if (enable) TRY(joint_refuse(c, "gh_set_shift_invariant"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_shift_invariant: call before gh_build_G");
     // (the store is a flavour of the matrix-free mode -- G is never stored -- so enabling it sets c->mf;
     // disabling it puts c->mf back to what gh_set_matrix_free last asked for)
@@ -461,7 +556,16 @@ int gh_build_G(gh_ctx *c)
                     "N = %lld: more than 16384 observations per device: shard the observations or use "
                     "the matrix-free mode (gh_set_matrix_free)", (long long)c->N);
     TRY(dalloc(c, &c->G, (size_t)c->ld * (size_t)c->M, false));
-    if (c->cell_kind == GH_CELL_PRISM || c->cell_kind == GH_CELL_PRISM_TF || c->cell_kind == GH_CELL_PRISM_COMP) {
+    if (c->cell_kind == GH_CELL_PRISM_JOINT) {
+        // both blocks of H = [A_gz | A_tf] in one launch (ld rows of N/2 observations, m = M/2 cells each)
+        const int64_t m = c->M / 2;
+        const int64_t blocks = std::min<int64_t>((c->ld * m + 255) / 256, 1 << 22);
+        prism_joint_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(
+            c->obs[0], c->obs[1], c->obs[2], c->bounds, c->N / 2, m, c->ld,
+            make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), c->G);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else if (c->cell_kind == GH_CELL_PRISM || c->cell_kind == GH_CELL_PRISM_TF || c->cell_kind == GH_CELL_PRISM_COMP) {
         typedef void (*prism_fn)(const double *, const double *, const double *, const double *, int64_t, int64_t,
                                  int64_t, double3, double *);
         // (indexed by GH_COMP_*, then the total field)
@@ -507,6 +611,7 @@ int gh_kernel_stats(const gh_ctx *c, int64_t *warn_cells, int64_t *leaves)
 int gh_upload_G(gh_ctx *c, const double *A, int64_t ld, int fortran_order)
 {
     if (!c || !A) return fail(c, GH_ERR_ARG, "gh_upload_G: null pointer");
+    TRY(joint_refuse(c, "gh_upload_G"));
     if (ld < (fortran_order ? c->N : c->M)) return fail(c, GH_ERR_ARG, "gh_upload_G: ld too small");
     if (c->mf) return fail(c, GH_ERR_ARG, "gh_upload_G: context is matrix-free");
     if (!c->dense_ok) return fail(c, GH_ERR_UNSUPPORTED, "N = %lld: more than 16384 observations per device", (long long)c->N);
@@ -543,10 +648,12 @@ int gh_download_G(gh_ctx *c, double *A, int64_t ld)
 {
     if (!c || !A) return fail(c, GH_ERR_ARG, "gh_download_G: null pointer");
     TRY(need(c, c->have_G && !c->mf, "gh_download_G: no kernel matrix resident"));
-    if (ld < c->N) return fail(c, GH_ERR_ARG, "gh_download_G: ld too small");
+    // (joint store: H = [Aw_gz | Aw_tf], N/2 rows -- the zero blocks of the stacked A are not stored)
+    const int64_t rows = c->joint ? c->N / 2 : c->N;
+    if (ld < rows) return fail(c, GH_ERR_ARG, "gh_download_G: ld too small");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpy2DAsync(A, (size_t)ld * sizeof(double), c->G, (size_t)c->ld * sizeof(double),
-                               (size_t)c->N * sizeof(double), (size_t)c->M, hipMemcpyDeviceToHost,
+                               (size_t)rows * sizeof(double), (size_t)c->M, hipMemcpyDeviceToHost,
                                c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return GH_OK;
@@ -560,6 +667,31 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
     HIPCHK(c, hipSetDevice(c->device));
     TRY(dalloc(c, &c->wm, (size_t)c->M));
     TRY(dalloc(c, &c->wm2, (size_t)c->M));
+    if (c->joint) {
+        if (weightfactor != 0.5)
+            return fail(c, GH_ERR_ARG, "gh_weight: the joint kernel is weighted by the column 2-norms (weightfactor 0.5)");
+        // population std of each unweighted block, two passes (weightKDM, potential.py:1050-1051)
+        const int64_t m = c->M / 2, n = c->N / 2;
+        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((c->ld * m + 255) / 256, (int64_t)c->cus * 8));
+        double *part = nullptr, *mean = nullptr;
+        TRY(dalloc(c, &part, 2 * (size_t)gx));
+        TRY(dalloc(c, &mean, 2));
+        std::vector<double> hp(2 * (size_t)gx);
+        double mu[2], var[2];
+        for (int pass = 0; pass < 2; ++pass) {
+            joint_std_kernel<<<dim3(gx, 2), dim3(256), 0, c->stream>>>(c->G, n, m, c->ld, pass, mean, part);
+            HIPCHK(c, hipGetLastError());
+            TRY(d2h(c, hp.data(), part, hp.size()));
+            for (int h = 0; h < 2; ++h) {
+                long double t = 0.0L;
+                for (unsigned b = 0; b < gx; ++b) t += hp[(size_t)h * gx + b];
+                (pass ? var : mu)[h] = (double)(t / (long double)((double)n * (double)m));
+            }
+            if (pass == 0) TRY(h2d(c, mean, mu, 2));
+        }
+        c->joint_std[0] = std::sqrt(var[0]);
+        c->joint_std[1] = std::sqrt(var[1]);
+    }
     if (lonsym_on(c)) {
         lonsym_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
             lonsym_geom(c), c->ls->a_of, c->ls->m_of, weightfactor, c->wm);
@@ -590,6 +722,14 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
                            c->cols_per_team, c->n_teams_sweep, weightfactor, c->wm);
     }
     HIPCHK(c, hipGetLastError());
+    if (c->joint) {
+        // Wb: the tf block times s = std_gz / std_tf, folded into the stored kernel (Aw = Wb A Wm^-1)
+        const int64_t m = c->M / 2;
+        const double sb = c->joint_std[0] / c->joint_std[1];
+        scale_cols_kernel<<<dim3((unsigned)std::min<int64_t>((c->ld * m + 255) / 256, 1 << 20)), dim3(256), 0, c->stream>>>(
+            c->G, c->ld, m, m, sb);
+        HIPCHK(c, hipGetLastError());
+    }
     std::vector<double> w((size_t)c->M);
     TRY(d2h(c, w.data(), c->wm, (size_t)c->M));
     if (wm_out) memcpy(wm_out, w.data(), sizeof(double) * (size_t)c->M);
@@ -605,6 +745,18 @@ int gh_set_data(gh_ctx *c, const double *dobs, const double *grav_fix)
 {
     if (!c || !dobs) return fail(c, GH_ERR_ARG, "gh_set_data: null pointer");
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->joint) {
+        // dobsw as it is: [gz: ld | tf: ld], no mean removal, no fixed cells (potential.py:1665-1680)
+        if (grav_fix) return fail(c, GH_ERR_ARG, "gh_set_data: the joint kernel takes no grav_fix");
+        TRY(dalloc(c, &c->dobs_c, 2 * (size_t)c->ld));
+        TRY(h2d_obsvec(c, c->dobs_c, dobs));
+        c->have_fix = false;
+        c->gfix_sum = 0.0;
+        c->have_data = true;
+        c->chain_ready = false;
+        c->bt.ready = false;
+        return GH_OK;
+    }
     const size_t N = (size_t)c->N;
     TRY(dalloc(c, &c->dobs_c, (size_t)c->ld));
     TRY(dalloc(c, &c->gfix, (size_t)c->ld));
@@ -666,6 +818,9 @@ int gh_set_reg(gh_ctx *c, int kind, double alpha, double beta, const int shape3[
         if (c->M < P || c->M % P != 0 || c->sh.m0 % P != 0)
             return fail(c, GH_ERR_UNSUPPORTED, "Smoothness/TV on a sharded model need shards of whole z-planes "
                                                "(%lld cells each): partition the cells with that alignment", (long long)P);
+    } else if (stencil && c->joint) {
+        if (!shape3 || 2 * (int64_t)shape3[0] * shape3[1] * shape3[2] != c->M)
+            return fail(c, GH_ERR_ARG, "gh_set_reg: Smoothness/TV on the joint kernel need shape nz*ny*nx == M/2 (one property's mesh)");
     } else if (stencil) {
         if (!shape3 || (int64_t)shape3[0] * shape3[1] * shape3[2] != c->M)
             return fail(c, GH_ERR_ARG, "gh_set_reg: Smoothness/TV need shape nz*ny*nx == M (carved meshes are not supported by the finite-difference operator)");
@@ -739,7 +894,7 @@ int gh_forward(gh_ctx *c, const double *mw, double *dpre)
     reduce_slab(c, nullptr, c->tmpN);
     HIPCHK(c, hipGetLastError());
     if (!shard_rows(c)) TRY(comm_allreduce(c, c->tmpN, c->ld));  // (row blocks: the local rows are complete)
-    return d2h(c, dpre, c->tmpN, (size_t)c->N);  // (forward-only sweeps never run on teams)
+    return d2h_obsvec(c, dpre, c->tmpN);  // (forward-only sweeps never run on teams)
 }
 
 int gh_adjoint(gh_ctx *c, const double *r, double *g)
@@ -748,8 +903,8 @@ int gh_adjoint(gh_ctx *c, const double *r, double *g)
     TRY(need(c, c->have_G, "gh_adjoint: no kernel matrix resident"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(ensure_work(c));
-    HIPCHK(c, hipMemsetAsync(c->tmpN, 0, sizeof(double) * (size_t)c->ld, c->stream));
-    TRY(h2d(c, c->tmpN, r, (size_t)c->N));
+    HIPCHK(c, hipMemsetAsync(c->tmpN, 0, sizeof(double) * (size_t)c->ld * (c->joint ? 2 : 1), c->stream));
+    TRY(h2d_obsvec(c, c->tmpN, r));
     SweepArgs a{};
     a.mode = SW_ADJ | SW_GOUT;
     a.r = c->tmpN;
@@ -779,7 +934,7 @@ int gh_misfit_and_grad(gh_ctx *c, const double *x, double out3[3], double *grad,
     TRY(scal_ready(c, o));
     HIPCHK(c, hipMemcpyAsync(c->h_scal, o.scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     TRY(d2h(c, grad, c->tmpM, (size_t)c->M));
-    if (dpre) TRY(d2h(c, dpre, o.d, (size_t)c->N));
+    if (dpre) TRY(d2h_obsvec(c, dpre, o.d));
     TRY(lonsym_epilogue_check(c));
     out3[0] = c->h_scal[2];
     out3[1] = c->h_scal[0];
@@ -794,8 +949,9 @@ int gh_reg_eval(gh_ctx *c, int kind, double beta, const int shape3[3], int ms_gr
     if (kind < 0 || kind > 3)
         return fail(c, GH_ERR_ARG, "Please choose regularization from 'MS','Damping', 'Smoothness', 'TV'.");
     if (kind == GH_REG_SMOOTHNESS || kind == GH_REG_TV)
-        if (!shape3 || (int64_t)shape3[0] * shape3[1] * shape3[2] != c->M)
-            return fail(c, GH_ERR_ARG, "gh_reg_eval: Smoothness/TV need shape nz*ny*nx == M");
+        if (!shape3 || (int64_t)shape3[0] * shape3[1] * shape3[2] * (c->joint ? 2 : 1) != c->M)
+            return fail(c, GH_ERR_ARG, c->joint ? "gh_reg_eval: Smoothness/TV on the joint kernel need shape nz*ny*nx == M/2"
+                                                : "gh_reg_eval: Smoothness/TV need shape nz*ny*nx == M");
     if (kind == GH_REG_MS) TRY(need(c, c->weighted, "gh_reg_eval: MS needs gh_weight first (uses Wm^2)"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(ensure_work(c));
@@ -816,8 +972,26 @@ int gh_reg_eval(gh_ctx *c, int kind, double beta, const int shape3[3], int ms_gr
     ra.wm2 = c->wm2;
     ra.greg = dg;
     ra.regpart = c->regpart;
-    reg_kernel<<<dim3(c->n_regpart), dim3(256), 0, c->stream>>>(ra);
-    sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->regpart, c->n_regpart, c->st[3].scal);
+    if (c->joint) {
+        // one property at a time (fd3djoint: the stencil never crosses into the other block)
+        const int64_t m = c->M / 2;
+        const int nrb = (int)((m + 255) / 256);
+        for (int h = 0; h < 2; ++h) {
+            RegArgs rh = ra;
+            rh.M = m;
+            if (!shape3) rh.nx = (int)m;
+            rh.x = dx + h * m;
+            rh.mwapr = dapr + h * m;
+            rh.wm2 = c->wm2 + h * m;
+            rh.greg = dg + h * m;
+            rh.regpart = c->regpart + h * nrb;
+            reg_kernel<<<dim3(nrb), dim3(256), 0, c->stream>>>(rh);
+        }
+        sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->regpart, 2 * nrb, c->st[3].scal);
+    } else {
+        reg_kernel<<<dim3(c->n_regpart), dim3(256), 0, c->stream>>>(ra);
+        sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->regpart, c->n_regpart, c->st[3].scal);
+    }
     HIPCHK(c, hipGetLastError());
     TRY(d2h(c, c->h_scal, c->st[3].scal, 2));
     *value = c->h_scal[0];
@@ -829,6 +1003,7 @@ int gh_compress_wavelet(gh_ctx *c, int dims, const int shape3[3], double thr, in
                         int64_t *nnz_out, int64_t *ncols_out)
 {
     if (!c) return GH_ERR_ARG;
+    TRY(joint_refuse(c, "gh_compress_wavelet"));
     TRY(need(c, c->have_G && c->weighted, "gh_compress_wavelet: needs the weighted kernel (gh_weight) first"));
     if (dims != 1 && dims != 3) return fail(c, GH_ERR_ARG, "gh_compress_wavelet: dims must be 1 or 3");
     if (levels < 1 || levels > 4) return fail(c, GH_ERR_ARG, "gh_compress_wavelet: levels must be 1..4");
@@ -1326,7 +1501,7 @@ int gh_chain_get_dsyn(gh_ctx *c, double *dsyn)
     TRY(need(c, c->chain_ready, "gh_chain_get_dsyn: call gh_chain_init first"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(chain_state_fresh(c));
-    return d2h(c, dsyn, c->st[c->cur].d, (size_t)c->N);
+    return d2h_obsvec(c, dsyn, c->st[c->cur].d);
 }
 
 int gh_chain_stats(gh_ctx *c, int64_t *spec_hits, int64_t *spec_misses)
@@ -1530,6 +1705,7 @@ static int kids_run(gh_ctx *c, int T, const int *L, const double *const *p0rows,
 int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const double *high)
 {
     if (!c || !x0s || !low || !high) return fail(c, GH_ERR_ARG, "gh_batch_init: null pointer");
+    TRY(joint_refuse(c, "gh_batch_init"));
     if (C < 1 || C > CB) return fail(c, GH_ERR_ARG, "gh_batch_init: 1..16 chains per batch");
     TRY(need(c, c->have_G && c->have_data && c->have_reg,
              "gh_batch_init: needs the kernel (gh_build_G / gh_upload_G), gh_set_data and gh_set_reg"));
@@ -1589,6 +1765,7 @@ int gh_batch_trajectory(gh_ctx *c, const double *p0s, double dt, const int *L, c
                         double *out5s)
 {
     if (!c || !p0s || !L || !us || !accepted || !out5s) return fail(c, GH_ERR_ARG, "gh_batch_trajectory: null pointer");
+    TRY(joint_refuse(c, "gh_batch_trajectory"));
     gh_ctx::Batch &b = c->bt;
     TRY(need(c, b.ready, "gh_batch_trajectory: call gh_batch_init first"));
     for (int k = 0; k < b.C; ++k)
@@ -1743,6 +1920,7 @@ int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const
 {
     if (!c || T < 0 || (T > 0 && (!L || !p0s || !us)) || !accepted || !out5s || ((n_started == nullptr) != (n_done == nullptr)))
         return fail(c, GH_ERR_ARG, "gh_batch_run: bad arguments");
+    TRY(joint_refuse(c, "gh_batch_run"));
     if (T == 0 && !n_done) return fail(c, GH_ERR_ARG, "gh_batch_run: T = 0 (drain) needs n_started / n_done");
     gh_ctx::Batch &b = c->bt;
     TRY(need(c, b.ready, "gh_batch_run: call gh_batch_init first"));
@@ -2352,6 +2530,7 @@ int gh_shard_init(gh_ctx *c, const void *id128, int rank, int world, int64_t M_g
 {
     if (!c || !id128) return fail(c, GH_ERR_ARG, "gh_shard_init: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init: already initialised");
+    TRY(joint_refuse(c, "gh_shard_init"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_common_init(c, rank, world, M_global, m0));
     std::string err;
@@ -2371,6 +2550,7 @@ int gh_shard_init_callback(gh_ctx *c, gh_allreduce_fn fn, void *user, int rank, 
 {
     if (!c || !fn) return fail(c, GH_ERR_ARG, "gh_shard_init_callback: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init: already initialised");
+    TRY(joint_refuse(c, "gh_shard_init"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_common_init(c, rank, world, M_global, m0));
     c->sh.cb = fn;
@@ -2383,6 +2563,7 @@ int gh_shard_init_rows(gh_ctx *c, const void *id128, int rank, int world, int64_
 {
     if (!c || !id128) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: already initialised");
+    TRY(joint_refuse(c, "gh_shard_init_rows"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_rows_init(c, rank, world, N_global, n0));
     std::string err;
@@ -2402,6 +2583,7 @@ int gh_shard_init_rows_callback(gh_ctx *c, gh_allreduce_fn fn, void *user, int r
 {
     if (!c || !fn) return fail(c, GH_ERR_ARG, "gh_shard_init_rows_callback: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: already initialised");
+    TRY(joint_refuse(c, "gh_shard_init_rows"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_rows_init(c, rank, world, N_global, n0));
     c->sh.cb = fn;

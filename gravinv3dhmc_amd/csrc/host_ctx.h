@@ -31,6 +31,10 @@ struct gh_ctx {
     double tf_dir[3] = {0.0, 0.0, 0.0};  // GH_CELL_PRISM_TF: the field direction (fx, fy, fz)
     double *tf_dir_d = nullptr;            // ... and its device copy (MfGeom::o3 of the matrix-free passes)
     int comp = GH_COMP_GZ;                 // GH_CELL_PRISM_COMP / GH_CELL_TESSEROID_COMP: the gravity component (MfGeom::comp)
+    // GH_CELL_PRISM_JOINT: H = [Aw_gz | Aw_tf] of ld rows (ld of N/2) and M = 2m columns; observation-space
+    // vectors live as [gz: ld | tf: ld] (2 ld doubles), model-space vectors as M
+    bool joint = false;
+    double joint_std[2] = {0.0, 0.0};      // population std of the unweighted gz / tf blocks (gh_weight)
     bool have_obs = false, have_cells = false, have_G = false, weighted = false;
     double *G = nullptr;
     int64_t warn_cells = 0, leaves = 0;

@@ -8,6 +8,14 @@
 // hundreds of rows serially.
 static void reduce_slab(gh_ctx *c, const double *gfix, double *d_out)
 {
+    if (c->joint) {
+        // the joint store: the first half of the slab rows sums to d_gz, the second to d_tf ([gz: ld | tf: ld])
+        const int half = c->grid / 2;
+        for (int h = 0; h < 2; ++h)
+            reduce_slab_kernel<<<dim3(c->n_dpart, 1), dim3(32, 8), 0, c->stream>>>(
+                c->slab + (int64_t)h * half * c->ld, half, c->ld, c->N / 2, nullptr, d_out + h * c->ld, c->dpart);
+        return;
+    }
     (void)lonsym_post_now(c);  // (harmonic shift-invariant store: the sweep left D^ partials, not a slab row)
     const int rows = c->slab_live > 0 ? c->slab_live : c->grid;
     if (rows > 64 && c->slab2) {
@@ -22,8 +30,78 @@ static void reduce_slab(gh_ctx *c, const double *gfix, double *d_out)
     }
 }
 
+// The joint store's epilogue: the existing epilogue kernels run once per block, on that block's half of the
+// slab rows, of d, r, dobsw and of the model, with no mean (reduce_finish_kernel with no slab-row sums and no
+// grav_fix removes a mean of exactly 0.0: r = d - dobsw) and the regulariser of that block alone (the
+// stencil of fd3djoint: nothing couples the blocks).  Partials: |r|^2 of gz, of tf, then R of gz, of tf --
+// scal_kernel sums them.  Below 2048 rows (few 32-row blocks for many slab rows) reduce_reg_kernel first
+// folds the block's slab rows into slab2 segments, as the single-property path does.
+// (two stages: fewer than 2048 rows and more than 64 slab rows per block; ensure_work then has slab2, as it
+// allocates it whenever the grid has more than 64 rows)
+static bool joint_two_stage(const gh_ctx *c)
+{
+    return c->joint && c->ld < 2048 && c->grid / 2 > 64;
+}
+
+static int finalize_joint(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
+{
+    const int half = c->grid / 2;
+    const int64_t m = c->M / 2, ld = c->ld;
+    const int nrb = (int)((m + 255) / 256);  // regulariser blocks per property
+    const bool two_stage = joint_two_stage(c);
+    if (two_stage && !c->slab2) return fail(c, GH_ERR_ARG, "joint epilogue: no slab2 (ensure_work not run)");
+    for (int h = 0; h < 2; ++h) {
+        RegArgs ra{};
+        ra.ms_grad_den_mw = 0;
+        ra.kind = c->reg_kind;
+        ra.M = m;
+        ra.nz = c->shape[0];
+        ra.ny = c->shape[1];
+        ra.nx = c->shape[2];
+        ra.alpha = c->alpha;
+        ra.beta = c->beta;
+        ra.x = x + h * m;
+        ra.mwapr = c->mwapr + h * m;
+        ra.wm2 = c->wm2 + h * m;
+        ra.greg = o.greg + h * m;
+        ra.regpart = o.part + 2 * c->n_dpart + h * nrb;
+        ReduceFinishArgs fa{};
+        fa.slab = c->slab + (int64_t)h * half * ld;
+        fa.n_rows_slab = half;
+        int n_reg = nrb;
+        if (two_stage) {
+            const int nseg = c->slab2_rows;
+            double *seg = c->slab2 + (int64_t)h * nseg * ld;
+            reduce_reg_kernel<<<dim3((unsigned)(c->n_dpart * nseg + nrb)), dim3(256), 0, c->stream>>>(
+                fa.slab, half, ld, nseg, c->n_dpart, seg, ra);
+            fa.slab = seg;
+            fa.n_rows_slab = nseg;
+            n_reg = 0;  // (done)
+        }
+        fa.n_dpart = c->n_dpart;
+        fa.n_regpart = n_reg;
+        fa.ld = ld;
+        fa.N = c->N / 2;
+        fa.dsum = nullptr;
+        fa.n_dsum = 0;
+        fa.gfix_sum = 0.0;
+        fa.gfix = nullptr;
+        fa.dobs_c = c->dobs_c + h * ld;
+        fa.d = o.d + h * ld;
+        fa.r = o.r + h * ld;
+        fa.scal = o.scal;
+        fa.r2part = o.part + h * c->n_dpart;
+        fa.ra = ra;
+        reduce_finish_kernel<<<dim3((unsigned)(c->n_dpart + n_reg)), dim3(256), 0, c->stream>>>(fa);
+    }
+    HIPCHK(c, hipGetLastError());
+    o.pending = true;
+    return GH_OK;
+}
+
 static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
 {
+    if (c->joint) return finalize_joint(c, x, o);
     double *d_out = o.d, *r_out = o.r, *greg_out = o.greg, *scal_out = o.scal;
     RegArgs ra{};
     ra.ms_grad_den_mw = 0;
@@ -210,7 +288,10 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
 static int scal_ready(gh_ctx *c, const gh_ctx::StateSet &o)
 {
     if (!o.pending) return GH_OK;
-    scal_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(o.part, c->n_dpart, c->n_regpart, c->alpha, o.scal);
+    // (joint store: |r|^2 partials of both blocks, then R partials of both blocks)
+    const int nd = c->joint ? 2 * c->n_dpart : c->n_dpart;
+    const int nr = c->joint ? 2 * (int)((c->M / 2 + 255) / 256) : c->n_regpart;
+    scal_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(o.part, nd, nr, c->alpha, o.scal);
     HIPCHK(c, hipGetLastError());
     o.pending = false;
     return GH_OK;
@@ -231,7 +312,8 @@ static int eval_forward(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
 
 static int ensure_work(gh_ctx *c)
 {
-    const size_t M = (size_t)c->M, ld = (size_t)c->ld;
+    // (joint store: observation-space vectors [gz: ld | tf: ld])
+    const size_t M = (size_t)c->M, ld = (size_t)c->ld * (c->joint ? 2 : 1);
     TRY(dalloc(c, &c->scal_all, 16));
     for (int i = 0; i < 4; ++i) {
         TRY(dalloc(c, &c->st[i].r, ld));
@@ -246,19 +328,25 @@ static int ensure_work(gh_ctx *c)
     if (c->n_panels > 1 || shard_rows(c)) TRY(dalloc(c, &c->gbuf, M));
     // (N > 16384: the team sweep writes one slab row per team, up to 128, whatever the panel grid)
     // (the harmonic forms of the shift-invariant store deliver ONE finished slab row)
-    TRY(dalloc(c, &c->slab, (size_t)(lonsym_one_row(c) ? 1 : c->n_panels > 1 ? std::max(c->grid, 128) : c->grid) * ld));
+    // (slab rows are c->ld long, also on the joint store: a workgroup's partial forward product covers its own block)
+    TRY(dalloc(c, &c->slab, (size_t)(lonsym_one_row(c) ? 1 : c->n_panels > 1 ? std::max(c->grid, 128) : c->grid) * (size_t)c->ld));
     if (c->grid > 64) {
         // segments left for the single-block finish_kernel: as many as keep its read at ~128 KB
         // (C1: 16 x 608 rows; C2: 1 x 10^4 -- sixteen there made that one block read 1.3 MB, 57 us)
-        c->slab2_rows = (int)std::max<int64_t>(1, std::min<int64_t>(16, 16384 / (int64_t)ld));
+        c->slab2_rows = (int)std::max<int64_t>(1, std::min<int64_t>(16, 16384 / (int64_t)c->ld));
         TRY(dalloc(c, &c->slab2, (size_t)c->slab2_rows * ld));
     }
     c->n_dpart = (int)((c->ld + 31) / 32);
-    if (c->ld >= 2048 && ((c->TW > 1 && c->n_panels == 1 && !c->mf) || lonsym_on(c)) && env_int("GRAVHMC_EPILOGUE1", 1) != 0) {
+    if (c->joint) {
+        // (the joint epilogue always leaves its partials: |r|^2 of both blocks, R of both blocks)
+        for (int i = 0; i < 4; ++i)
+            TRY(dalloc(c, &c->st[i].part, 2 * (size_t)c->n_dpart + 2 * (size_t)((c->M / 2 + 255) / 256)));
+    } else if (c->ld >= 2048 && ((c->TW > 1 && c->n_panels == 1 && !c->mf) || lonsym_on(c)) && env_int("GRAVHMC_EPILOGUE1", 1) != 0) {
         TRY(dalloc(c, &c->dsum, (size_t)std::max(std::max(c->grid, 128), lonsym_on(c) ? lonsym_classes(c) : 0)));
         for (int i = 0; i < 4; ++i) TRY(dalloc(c, &c->st[i].part, (size_t)c->n_dpart + (size_t)((c->M + 255) / 256)));
     }
-    c->n_regpart = (int)((c->M + 255) / 256);
+    // (joint store: the regulariser runs per property, ceil(m / 256) blocks each)
+    c->n_regpart = c->joint ? 2 * (int)((c->M / 2 + 255) / 256) : (int)((c->M + 255) / 256);
     c->n_pp0 = (int)std::min<int64_t>(1024, (c->M + 255) / 256);
     TRY(dalloc(c, &c->dpart, (size_t)c->n_dpart));
     TRY(dalloc(c, &c->regpart, (size_t)c->n_regpart));

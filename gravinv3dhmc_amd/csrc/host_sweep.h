@@ -7,26 +7,32 @@
 typedef void (*sweep_fn)(SweepArgs);
 typedef void (*weight_fn)(double *, int64_t, int64_t, int64_t, int, double, double *);
 
-template <int TW, int PF, bool NT>
+template <int TW, int PF, bool NT, bool JOINT>
 static sweep_fn pick_sweep_e(int ept2)
 {
     switch (ept2) {
-    case 1: return sweep_kernel<TW, 1, PF, NT>;
-    case 2: return sweep_kernel<TW, 2, PF, NT>;
-    case 3: return sweep_kernel<TW, 3, PF, NT>;
-    case 4: return sweep_kernel<TW, 4, PF, NT>;
-    case 5: return sweep_kernel<TW, 5, PF, NT>;
-    case 6: return sweep_kernel<TW, 6, PF, NT>;
-    case 8: return sweep_kernel<TW, 8, PF, NT>;
+    case 1: return sweep_kernel<TW, 1, PF, NT, JOINT>;
+    case 2: return sweep_kernel<TW, 2, PF, NT, JOINT>;
+    case 3: return sweep_kernel<TW, 3, PF, NT, JOINT>;
+    case 4: return sweep_kernel<TW, 4, PF, NT, JOINT>;
+    case 5: return sweep_kernel<TW, 5, PF, NT, JOINT>;
+    case 6: return sweep_kernel<TW, 6, PF, NT, JOINT>;
+    case 8: return sweep_kernel<TW, 8, PF, NT, JOINT>;
     }
     return nullptr;
 }
 
-template <int TW>
-static sweep_fn pick_sweep(int ept2, int pf, bool nt)
+template <int TW, bool JOINT>
+static sweep_fn pick_sweep_j(int ept2, int pf, bool nt)
 {
-    if (pf == 2) return nt ? pick_sweep_e<TW, 2, true>(ept2) : pick_sweep_e<TW, 2, false>(ept2);
-    return nt ? pick_sweep_e<TW, 1, true>(ept2) : pick_sweep_e<TW, 1, false>(ept2);
+    if (pf == 2) return nt ? pick_sweep_e<TW, 2, true, JOINT>(ept2) : pick_sweep_e<TW, 2, false, JOINT>(ept2);
+    return nt ? pick_sweep_e<TW, 1, true, JOINT>(ept2) : pick_sweep_e<TW, 1, false, JOINT>(ept2);
+}
+
+template <int TW>
+static sweep_fn pick_sweep(int ept2, int pf, bool nt, bool joint)
+{
+    return joint ? pick_sweep_j<TW, true>(ept2, pf, nt) : pick_sweep_j<TW, false>(ept2, pf, nt);
 }
 
 template <int TW>
@@ -46,10 +52,10 @@ static weight_fn pick_weight(int ept2)
 
 static sweep_fn sweep_for(const gh_ctx *c)
 {
-    if (c->TW == 1) return pick_sweep<1>(c->EPT2, c->PF, c->NT);
-    if (c->TW == 4) return pick_sweep<4>(c->EPT2, c->PF, c->NT);
-    if (c->TW == 8) return pick_sweep<8>(c->EPT2, c->PF, c->NT);
-    return pick_sweep<16>(c->EPT2, c->PF, c->NT);
+    if (c->TW == 1) return pick_sweep<1>(c->EPT2, c->PF, c->NT, c->joint);
+    if (c->TW == 4) return pick_sweep<4>(c->EPT2, c->PF, c->NT, c->joint);
+    if (c->TW == 8) return pick_sweep<8>(c->EPT2, c->PF, c->NT, c->joint);
+    return pick_sweep<16>(c->EPT2, c->PF, c->NT, c->joint);
 }
 
 static weight_fn weight_for(const gh_ctx *c)
@@ -152,14 +158,23 @@ static int configure_sweep(gh_ctx *c)
     wg_per_cu = env_int("GRAVHMC_WG_PER_CU", wg_per_cu);
     int64_t max_teams = (int64_t)c->cus * wg_per_cu * wg_teams;
     int64_t min_cols = env_int("GRAVHMC_MIN_COLS", tw == 1 ? 2 : 1);
-    int64_t cpt = (c->M + max_teams - 1) / max_teams;
+    // (joint store: each block of m = M/2 columns is partitioned on its own, over half the teams, and
+    // the second half of the grid repeats the first's partition on the tf block)
+    const int64_t Mp = c->joint ? c->M / 2 : c->M;
+    if (c->joint) max_teams = std::max<int64_t>(1, max_teams / 2);
+    int64_t cpt = (Mp + max_teams - 1) / max_teams;
     if (cpt < min_cols) cpt = min_cols;
     c->cols_per_team = cpt;
-    c->n_teams = (int)((c->M + cpt - 1) / cpt);
+    c->n_teams = (int)((Mp + cpt - 1) / cpt);
     c->n_teams_sweep = c->n_teams;
     c->grid = (c->n_teams + wg_teams - 1) / wg_teams;
     // (one-wave teams interleave inside their block's column range: every wave of the grid is a team)
     if (tw == 1) c->n_teams = c->n_teams_sweep = c->grid * wg_teams;
+    if (c->joint) {
+        c->grid *= 2;
+        c->n_teams *= 2;
+        c->n_teams_sweep *= 2;
+    }
     // (row panels: partials of vec_update; the team sweep: one per team, at most 128 teams)
     if (c->n_panels > 1) c->n_teams = std::max(std::max(c->n_teams, 128), (int)((c->M + 255) / 256));
     return GH_OK;
@@ -408,7 +423,7 @@ static int launch_sweep_one(gh_ctx *c, SweepArgs &a)
     if (timed) {
         HIPCHK(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
         c->ev_bytes[c->ev_used / 2] = a.rows < c->ld ? a.rows * c->M * (int64_t)sizeof(double)
-                                                      : c->N * c->M * (int64_t)sizeof(double);
+                                                      : (c->joint ? c->N / 2 : c->N) * c->M * (int64_t)sizeof(double);
         c->ev_used += 2;
     }
     if (c->prof) c->prof_launches += 1;
@@ -438,7 +453,7 @@ static bool team_plan(gh_ctx *c)
     if (t.state != 0) return t.state > 0;
     t.state = -1;
     if (env_int("GRAVHMC_TEAM", 1) == 0) return false;
-    if (c->mf || c->n_panels < 2 || !c->G) return false;
+    if (c->mf || c->joint || c->n_panels < 2 || !c->G) return false;
     // instantiation: threads x double2 per thread x column buffers
     t.threads = 1024;
     t.ept2 = 5;

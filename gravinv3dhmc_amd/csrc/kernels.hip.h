@@ -138,7 +138,12 @@ struct ColRegs {
 // TW = waves per team (1, 4, 8, 16).  TW == 1: four independent wave-teams per 256-thread block.
 // EPT2 = double2 elements held per thread: capacity = TW*64*EPT2*2 rows >= ld.
 // PF = columns prefetched ahead (1 or 2).  NT = non-temporal loads of G (streamed once).
-template <int TW, int EPT2, int PF, bool NT>
+// JOINT: the joint gravity-magnetic store H = [Aw_gz | Aw_tf] (GH_CELL_PRISM_JOINT; a.M = 2m columns of
+// a.ld rows).  The first half of the grid owns the gz columns [0, m), the second half the tf columns
+// [m, 2m), so no team straddles the boundary; a team's residual in LDS is its own block's r, at
+// a.r + blk * ld (r = [r_gz | r_tf], ld each), and its slab row holds its own block's partial forward
+// product.
+template <int TW, int EPT2, int PF, bool NT, bool JOINT = false>
 __global__ void __launch_bounds__((TW == 1 ? 4 : TW) * 64) sweep_kernel(SweepArgs a)
 {
     constexpr int TEAM_THREADS = TW * 64;
@@ -158,9 +163,16 @@ __global__ void __launch_bounds__((TW == 1 ? 4 : TW) * 64) sweep_kernel(SweepArg
     const int64_t ld = a.ld;
     const int ld2 = (int)(a.rows >> 1);  // rows of this panel in double2 units
     const int mode = a.mode;
+    // (JOINT: blk = the block this workgroup's columns belong to, lb = the workgroup's index inside it)
+    int blk = 0, lb = blockIdx.x;
+    if constexpr (JOINT) {
+        const int half = (int)(gridDim.x >> 1);
+        blk = (int)blockIdx.x >= half;
+        lb = (int)blockIdx.x - blk * half;
+    }
 
     if (mode & SW_ADJ) {
-        const d2 *r2 = reinterpret_cast<const d2 *>(a.r + a.row0);
+        const d2 *r2 = reinterpret_cast<const d2 *>(a.r + (JOINT ? blk * ld : 0) + a.row0);
         d2 *rs2 = reinterpret_cast<d2 *>(r_s);
         for (int e = tid; e < ld2; e += blockDim.x) rs2[e] = r2[e];
     }
@@ -172,7 +184,18 @@ __global__ void __launch_bounds__((TW == 1 ? 4 : TW) * 64) sweep_kernel(SweepArg
     // bandwidth at 600 x 4*10^5).  Column of iteration i: jb + i * CS, i < cnt.
     constexpr int CS = (TW == 1) ? 4 : 1;
     int64_t jb, jend;
-    if (TW == 1) {
+    if constexpr (JOINT) {
+        const int64_t m = a.M >> 1, c0 = blk * m;
+        if (TW == 1) {
+            const int64_t b0c = c0 + (int64_t)lb * (4 * a.cols_per_team);
+            jend = b0c + 4 * a.cols_per_team;
+            jb = b0c + wave;
+        } else {
+            jb = c0 + (int64_t)lb * a.cols_per_team;
+            jend = jb + a.cols_per_team;
+        }
+        if (jend > c0 + m) jend = c0 + m;
+    } else if (TW == 1) {
         const int64_t b0c = (int64_t)blockIdx.x * (4 * a.cols_per_team);
         jend = b0c + 4 * a.cols_per_team;
         jb = b0c + wave;
@@ -1262,6 +1285,101 @@ prism_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const
         }
         G[idx] = v;
     }
+}
+
+// Joint gravity-magnetic store (GH_CELL_PRISM_JOINT): one thread per (obs, cell) pair writes both blocks of
+// H = [A_gz | A_tf], the gz entry to column c and the tf entry to column m + c.  One corner loop serves both
+// fields: the distance r, log(dx + r), log(dy + r) and atan2(dx dy, dz r) of a corner are the same function
+// of the same operands in gz's and tf's corner (prism_comp_corner<COMP_GZ>, prism_tf_corner), so computing
+// them once changes no bit; each field keeps its own accumulator, in prism_corners' order, and its own
+// scale.  Every entry equals prism_kernel<COMP_GZ> / prism_kernel<PRISM_TF>'s bit for bit.
+__global__ void __launch_bounds__(256)
+prism_joint_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
+                   const double *__restrict__ bounds6, int64_t N, int64_t m, int64_t ld, double3 dir,
+                   double *__restrict__ H)
+{
+#pragma clang fp contract(off)
+    const double fx = dir.x, fy = dir.y, fz = dir.z;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ld * m;
+         idx += (int64_t)gridDim.x * 256) {
+        const int64_t c = idx / ld, l = idx - c * ld;
+        double vg = 0.0, vt = 0.0;
+        if (l < N) {
+            const double px = xp[l], py = yp[l], pz = zp[l];
+            const double *b = bounds6 + 6 * c;
+            const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
+            double ag = 0.0, at = 0.0;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const double dz = Z[k] - pz;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const double dy = Y[j] - py;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const double dx = X[i] - px;
+                        const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
+                        const double r = sqrt(dx * dx + dy * dy + dz * dz);
+                        const double lyr = safe_log_d(dy + r), lxr = safe_log_d(dx + r);
+                        const double azz = safe_atan2_d(dx * dy, dz * r);
+                        ag += sign * -(dx * lyr + dy * lxr - dz * azz);
+                        const double v1 = -safe_atan2_d(dz * dy, dx * r);
+                        const double v2 = safe_log_d(dz + r);
+                        const double v4 = -safe_atan2_d(dz * dx, dy * r);
+                        const double v6 = -azz;
+                        const double bx = v1 * fx + v2 * fy + lyr * fz;
+                        const double by = v2 * fx + v4 * fy + lxr * fz;
+                        const double bz = lyr * fx + lxr * fy + v6 * fz;
+                        at += sign * (fx * bx + fy * by + fz * bz);
+                    }
+                }
+            }
+            vg = ag * prism_comp_scale<COMP_GZ>();
+            vt = at * TF_SCALE;
+        }
+        H[idx] = vg;
+        H[idx + ld * m] = vt;
+    }
+}
+
+// Two-pass population standard deviation of the two unweighted blocks of a joint store (numpy.std, ddof 0):
+// pass 0 sums the entries, pass 1 the squares of their distances to mean[blk].  blockIdx.y = block; every
+// thread keeps a compensated (Kahan) sum over its grid-stride share, the workgroup sums its 256 threads and
+// writes part[blk * gridDim.x + blockIdx.x] (the host sums the partials).  Padding rows (l >= N) are skipped.
+__global__ void __launch_bounds__(256)
+joint_std_kernel(const double *__restrict__ H, int64_t N, int64_t m, int64_t ld, int pass,
+                 const double *__restrict__ mean, double *__restrict__ part)
+{
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    const int blk = blockIdx.y;
+    const double *B = H + (int64_t)blk * ld * m;
+    const double mu = pass ? mean[blk] : 0.0;
+    double s = 0.0, comp = 0.0;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ld * m; idx += (int64_t)gridDim.x * 256) {
+        const int64_t c = idx / ld, l = idx - c * ld;
+        if (l >= N) continue;
+        double v = B[idx];
+        if (pass) {
+            v -= mu;
+            v = v * v;
+        }
+        const double y = v - comp;
+        const double t = s + y;
+        comp = (t - s) - y;
+        s = t;
+    }
+    const double tot = block_allreduce_sum(s, red, 4);
+    if (threadIdx.x == 0) part[(int64_t)blk * gridDim.x + blockIdx.x] = tot;
+}
+
+// Columns [j0, j0 + n) of a column-major ld-row matrix times s (the balance of the joint store's tf block)
+__global__ void __launch_bounds__(256)
+scale_cols_kernel(double *__restrict__ H, int64_t ld, int64_t j0, int64_t n, double s)
+{
+    double *B = H + j0 * ld;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ld * n; idx += (int64_t)gridDim.x * 256)
+        B[idx] *= s;
 }
 
 template <int COMP>

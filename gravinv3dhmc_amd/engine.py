@@ -21,7 +21,16 @@ class DeviceMatrix(object):
         self.ndim = 2
 
     def to_numpy(self):
-        return self._engine.download_G()
+        eng = self._engine
+        if getattr(eng, "joint", False):
+            # the joint store holds H = [Aw_gz | Aw_tf] (N/2 rows): the stacked layout, zero blocks included
+            H = eng.download_G()
+            n, m = eng.N // 2, eng.M // 2
+            A = np.zeros((eng.N, eng.M), order="F")
+            A[:n, :m] = H[:, :m]
+            A[n:, m:] = H[:, m:]
+            return A
+        return eng.download_G()
 
     def __array__(self, dtype=None, copy=None):
         a = self.to_numpy()
@@ -87,7 +96,9 @@ class Engine(object):
     # -- kernel matrix ------------------------------------------------------------
     def set_obs(self, a, b, c):
         a, b, c = f64(a), f64(b), f64(c)
-        if not (a.shape == b.shape == c.shape == (self.N,)):
+        # (joint gravity-magnetic context: both blocks share the N/2 observation points)
+        n = self.N // 2 if getattr(self, "joint", False) else self.N
+        if not (a.shape == b.shape == c.shape == (n,)):
             raise ValueError("Input arrays xp, yp, and zp must have same length!")
         self._chk(self._lib.gh_set_obs(self._h, ptr(a), ptr(b), ptr(c)))
 
@@ -96,8 +107,19 @@ class Engine(object):
         direction = (fx, fy, fz), the unit vector of the regional field (utils.dircos(inc, dec)).
         component (kind CELL_PRISM or CELL_PRISM_COMP for prisms, CELL_TESSEROID or CELL_TESSEROID_COMP for
         tesseroids): the gravity field, a name of _lib.COMPONENTS or a COMP_* value; "gz" is kind CELL_PRISM /
-        CELL_TESSEROID itself (gh_set_cells_prism / gh_set_cells_tess)."""
+        CELL_TESSEROID itself (gh_set_cells_prism / gh_set_cells_tess).
+        CELL_PRISM_JOINT: the M/2 prisms (bounds (M/2, 6)) of a joint gravity-magnetic model -- gz and the total
+        field along direction, inverted together (gh_set_cells_joint); call it before set_obs."""
         b = f64(bounds6)
+        if int(kind) == _lib.CELL_PRISM_JOINT:
+            if b.shape != (self.M // 2, 6):
+                raise ValueError("bounds table of a joint model must be (M/2, 6)")
+            if direction is None or len(direction) != 3:
+                raise ValueError("the joint kernel's total field needs direction = (fx, fy, fz)")
+            fx, fy, fz = (float(v) for v in direction)
+            self._chk(self._lib.gh_set_cells_joint(self._h, ptr(b), fx, fy, fz))
+            self.joint = True
+            return
         if b.shape != (self.M, 6):
             raise ValueError("bounds table must be (M, 6)")
         if int(kind) in (_lib.CELL_TESSEROID, _lib.CELL_TESSEROID_COMP) and \
@@ -203,9 +225,23 @@ class Engine(object):
             self._chk(self._lib.gh_upload_G(self._h, ptr(A), self.M, 0))
 
     def download_G(self):
-        A = np.empty((self.M, self.N))
-        self._chk(self._lib.gh_download_G(self._h, ptr(A), self.N))
-        return A.T  # N x M, Fortran-ordered view
+        """The stored kernel, N x M, Fortran-ordered; a joint context's store H = [Aw_gz | Aw_tf] is N/2 x M."""
+        rows = self.N // 2 if getattr(self, "joint", False) else self.N
+        A = np.empty((self.M, rows))
+        self._chk(self._lib.gh_download_G(self._h, ptr(A), rows))
+        return A.T  # rows x M, Fortran-ordered view
+
+    def joint_layout(self):
+        """Sweep workgroups per block and epilogue stages of a joint context (gh_joint_layout)."""
+        wg, st = C.c_int(0), C.c_int(0)
+        self._chk(self._lib.gh_joint_layout(self._h, C.byref(wg), C.byref(st)))
+        return {"workgroups_per_block": wg.value, "epilogue_stages": st.value}
+
+    def joint_std(self):
+        """(std_gz, std_tf): population std of the unweighted blocks of a weighted joint context (gh_joint_std)."""
+        out = np.empty(2)
+        self._chk(self._lib.gh_joint_std(self._h, ptr(out)))
+        return float(out[0]), float(out[1])
 
     def weight(self, weightfactor=0.5):
         wm = np.empty(self.M)

@@ -338,6 +338,9 @@ def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
     done.  'mandatory' constraint only."""
     if constraint != 'mandatory':
         raise ValueError("HMCSampleBatch supports the 'mandatory' boundary constraint only")
+    if getattr(model._engine, "joint", False):
+        raise NotImplementedError("HMCSampleBatch does not run the joint gravity-magnetic kernel (JointModule): "
+                                  "sample its chains one at a time with HMCSample")
     eng = model._engine
     _, WmInv, Wm = model.kernelw()
     low, high = Wm @ boundaries[:, 0], Wm @ boundaries[:, 1]

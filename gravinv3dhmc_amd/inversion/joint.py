@@ -1,0 +1,166 @@
+"""Joint gravity-magnetic inversion on prism meshes, evaluated on the GPU.
+
+Host-side mirror of the reference's `inversion.potential.JointModule` (inversion/potential.py:847-1812): the
+density and the magnetization of the same prisms under the same observation points, with the block-diagonal
+kernel A = [[A_gz, 0], [0, A_tf]], the data balance Wb = diag(1 ... 1, s ... s), s = std(A_gz) / std(A_tf),
+the column-norm weights Wm of A, and the potential |Aw mw - dobsw|^2 + alpha R(mw) with no mean removal.
+
+The device keeps H = [Aw_gz | Aw_tf] (N rows, 2M columns): the zero blocks are never stored or read
+(libgravhmc's GH_CELL_PRISM_JOINT).  `Aw` is a device handle whose array is the reference's 2N x 2M layout.
+"""
+import time
+
+import numpy as np
+from scipy.sparse import block_diag, coo_matrix
+
+from .. import _lib, mesher, utils
+from ..engine import DeviceMatrix, Engine
+from .potential import _diag, _Potential
+
+
+def fd3d(shape):
+    """The reference's 3D finite-difference matrix (potential.py:266-361), CSR: for every z-layer its x then its y
+    differences, then the differences between consecutive layers; each row is cell - next cell."""
+    nz, ny, nx = (int(v) for v in shape)
+    idx = np.arange(nz * ny * nx).reshape(nz, ny, nx)
+    per_layer = (nx - 1) * ny + (ny - 1) * nx
+    rows, a, b = [], [], []
+    for k in range(nz):
+        ax = idx[k, :, :-1].ravel()
+        ay = idx[k, :-1, :].ravel()
+        a += [ax, ay]
+        b += [ax + 1, ay + nx]
+        rows.append(per_layer * k + np.arange(ax.size + ay.size))
+    if nz > 1:
+        az = idx[:-1].ravel()
+        a.append(az)
+        b.append(az + nx * ny)
+        rows.append(per_layer * nz + np.arange(az.size))
+    a, b, rows = np.concatenate(a), np.concatenate(b), np.concatenate(rows)
+    nderivs = per_layer * nz + nx * ny * (nz - 1)
+    I = np.repeat(rows, 2)
+    J = np.column_stack([a, b]).ravel()
+    V = np.tile([1, -1], rows.size)
+    return coo_matrix((V, (I, J)), (nderivs, nx * ny * nz)).tocsr()
+
+
+class JointModule(_Potential):
+    """Joint gravity (gz) and total-field magnetic inversion model on one MI355X.
+
+    Parameters are the reference's (potential.py:848-851): dobs_gz, dobs_tf (the same N observation points),
+    mrange = (xmin, xmax, ymin, ymax, zmin, zmax), mspacing = (dz, dy, dx), obsurface = [xobs, yobs, height],
+    mratio, mangle = (inclination, declination) of the regional field; `mtopo=(x, y, topography)` carves the
+    mesh (active cells only, as GravMagModule).  device: GPU ordinal (extension).
+
+    Attributes as the reference: meshrho, meshmag, mshape, mxs/mys/mzs, dobs, dobsw, Wb, Wm, WmInv, WmSquare,
+    Aw (a device handle; np.asarray(Aw) is the 2N x 2M stacked layout).  A, kernel_gz and kernel_tf are formed
+    on request from the device copy: Aw's blocks times Wm and over Wb, equal to the reference's to rounding,
+    not bit for bit.
+
+    Divergences: coordinate="spherical" and wavelet compression raise NotImplementedError (the reference's
+    branches are broken); Smoothness and TV work, with the block-diagonal operator fd3djoint (the reference
+    raises AttributeError there: it calls a missing fd3d).  CrossGradient is absent (the reference's is `pass`).
+    """
+    _props = 2  # (density and magnetization of the same mesh)
+
+    def __init__(self, dobs_gz, dobs_tf, mrange, mspacing, obsurface, mratio=1, coordinate="cartesian", njobs=1,
+                 mangle=(90, 0), wavelet=False, device=0, verbose=True, **kwargs):
+        self._say = print if verbose else (lambda *a, **k: None)
+        if coordinate == "spherical":
+            # (the reference's spherical branch never defines kernel_tf: potential.py:885-895)
+            raise NotImplementedError("joint inversion on tesseroids (coordinate='spherical') is not supported")
+        if coordinate != "cartesian":
+            raise ValueError("Please choose coordinate from(cartesian, spherical)!")
+        if wavelet not in (False, None):
+            raise NotImplementedError("wavelet compression of the joint kernel is not supported")
+        dobs_gz = np.asarray(dobs_gz, dtype=np.float64).ravel()
+        dobs_tf = np.asarray(dobs_tf, dtype=np.float64).ravel()
+        n = int(np.asarray(obsurface[0]).size)
+        if dobs_gz.size != dobs_tf.size or dobs_gz.size != n:
+            raise ValueError("dobs_gz (%d), dobs_tf (%d) and the observation points (%d) must have the same length"
+                             % (dobs_gz.size, dobs_tf.size, n))
+        self.dobs_gz, self.dobs_tf = dobs_gz, dobs_tf
+        self.mrange = mrange
+        self.mspacing = mspacing
+        self.mratio = mratio
+        self.lonobs, self.latobs, self.heightobs = obsurface[0], obsurface[1], obsurface[2]
+        self.inc, self.dec = mangle[0], mangle[1]
+        self.njobs = njobs
+        self.topocarve = False
+        self.wavelet = wavelet
+        self.device = device
+
+        self._say("Joint inversion in {} coordinate.".format(coordinate))
+        mesh = mesher.PrismMesh(mrange, mspacing, mratio)
+        for _key, value in kwargs.items():  # mtopo=(x, y, topography)  (potential.py:899-903)
+            self.topocarve = True
+            self.mask = mesh.carvetopo(value[0], value[1], value[2])
+        meshrho, meshmag = mesh.copy(), mesh.copy()
+        meshrho.addprop('density', np.zeros(mesh.size))
+        meshmag.addprop('magnetization', utils.ang2vec(np.zeros(mesh.size), self.inc, self.dec))
+        self.meshrho, self.meshmag = meshrho, meshmag
+
+        bounds = mesh.cell_bounds(active_only=True)
+        m = bounds.shape[0]
+        eng = Engine(2 * n, 2 * m, device=device)
+        eng.set_cells(bounds, _lib.CELL_PRISM_JOINT, direction=utils.dircos(self.inc, self.dec))
+        eng.set_obs(self.lonobs, self.latobs, self.heightobs)
+        eng.build_G()
+        self._engine = eng
+
+        self.mshape = mesh.shape
+        self.mxs, self.mys, self.mzs = mesh.get_xs(), mesh.get_ys(), mesh.get_zs()
+        self.weightKDM()
+        eng.set_data(self.dobsw)
+
+    # ------------------------------------------------------------------ weighting
+    def weightKDM(self):
+        """Wm (column 2-norms of A), Wb (std_gz / std_tf on the tf rows), Aw = Wb A Wm^-1 and dobsw = Wb dobs
+        (potential.py:1003-1065), on the device."""
+        wm = self._engine.weight(0.5)
+        std_gz, std_tf = self._engine.joint_std()
+        self.std_gz, self.std_tf = std_gz, std_tf
+        n = self.dobs_gz.size
+        wb = np.append(np.ones(n), np.ones(n) * (std_gz / std_tf))
+        with np.errstate(divide='ignore'):
+            inv = np.where(wm == 0, 0.0, 1.0 / wm)
+        self.Wm = _diag(wm)
+        self.WmInv = _diag(inv)
+        self.WmSquare = _diag(wm * wm)
+        self.Wb = _diag(wb)
+        self.dobs = np.append(self.dobs_gz, self.dobs_tf)
+        self.dobsw = self.Wb @ self.dobs
+        self.Aw = DeviceMatrix(self._engine)
+
+    @property
+    def A(self):
+        """The unweighted stacked kernel, 2N x 2M, from the device copy (Wb^-1 Aw Wm; rounding differs)."""
+        A = np.asarray(self.Aw)
+        wb = self.Wb.diagonal()
+        return (A / wb[:, None]) * self.Wm.diagonal()[None, :]
+
+    @property
+    def kernel_gz(self):
+        n, m = self.dobs_gz.size, self.Wm.shape[0] // 2
+        return np.ascontiguousarray(self.A[:n, :m])
+
+    @property
+    def kernel_tf(self):
+        n, m = self.dobs_gz.size, self.Wm.shape[0] // 2
+        return np.ascontiguousarray(self.A[n:, m:])
+
+    def kernelw(self):
+        """(Aw, WmInv, Wm) as the sampler expects (potential.py:1561-1566); Aw is a device handle."""
+        return self.Aw, self.WmInv, self.Wm
+
+    def forward(self, model):
+        """Unweighted forward A @ model (potential.py:1067-1073): 2N values, gz first."""
+        model = np.asarray(model, dtype=np.float64)
+        wm = self.Wm.diagonal()
+        wb = self.Wb.diagonal()
+        return self._engine.forward(model * wm) / wb
+
+    def fd3djoint(self, shape):
+        """The reference's block-diagonal finite-difference matrix of the two properties (potential.py:1075-1220)."""
+        R = fd3d(shape)
+        return block_diag([R, R], format="csr")

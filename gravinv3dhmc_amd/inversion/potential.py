@@ -35,7 +35,73 @@ def _diag(values):
     return coo_matrix((values, (row, row))).tocsr()
 
 
-class GravMagModule(object):
+class _Potential(object):
+    """The potential methods GravMagModule and JointModule share: the model transform, the regulariser sent to the
+    engine, misfit_and_grad and the reference's wrappers.  `_props`: properties that share the mesh `mshape`
+    (the stencil regularisers act on each of them on its own)."""
+    _props = 1
+
+    def _to_mw(self, x, low, high, constraint, log_fator):
+        if constraint == 'logarithmic':
+            return (low + high * np.e ** (log_fator * x)) / (1 + np.e ** (log_fator * x))
+        elif constraint == 'mandatory':
+            return x
+        raise ValueError("Please choose right boundary constraint(mandatory, logarithmic)!")
+
+    def _use_reg(self, regulization, alpha, beta, mwapr):
+        if regulization not in _lib.REG_KINDS:
+            raise ValueError("Please choose regularization from 'MS','Damping', 'Smoothness', 'TV'.")
+        mwapr = np.asarray(mwapr, dtype=np.float64)
+        # The decision to (re)send the regulariser must be the same on every rank of a sharded
+        # model (gh_set_reg is collective there) and must notice in-place edits: it depends only
+        # on the VALUES -- kind, alpha, beta and the content of the full mwapr vector -- never on
+        # addresses.  The content is compared through a 64-bit digest of its bytes (xxh3: ~10 GB/s,
+        # one pass, no second copy of the vector kept; zlib.crc32 pair where xxhash is missing).
+        key = (regulization, float(alpha), float(beta))
+        digest = (mwapr.shape, _digest(mwapr))
+        last = self._engine._reg_key
+        if last is None or last[0] != key or last[1] != digest:
+            m_model = getattr(self._engine, "M_global", self._engine.M)
+            cells = self._props * int(np.prod(self.mshape))
+            if regulization in ("Smoothness", "TV") and cells != m_model:
+                raise ValueError("Smoothness/TV need the full (uncarved) mesh: %sshape %r has %d "
+                                 "cells, model has %d" % ("" if self._props == 1 else "%d x " % self._props,
+                                                          self.mshape, cells, m_model))
+            self._engine.set_reg(regulization, alpha, beta, self.mshape, mwapr)
+            self._engine._reg_key = (key, digest)
+
+    def misfit_and_grad(self, x, mwapr, low, high, constraint, log_fator, alpha,
+                        regulization='Damping', beta=0.01):
+        """(misfit, grad, dpre, data_value, model_value) -- potential.py:812-845 (JointModule: 1780-1812)."""
+        mw = self._to_mw(x, low, high, constraint, log_fator)
+        self._use_reg(regulization, alpha, beta, mwapr)
+        return self._engine.misfit_and_grad(mw)
+
+    # wrappers the reference keeps for an (unused) adaptive regularisation factor
+    def data(self, x, low, high, constraint, log_fator):
+        mw = self._to_mw(x, low, high, constraint, log_fator)
+        self._use_reg("Damping", 0.0, 0.01, np.zeros(self._engine.M))
+        return self._engine.misfit_and_grad(mw)[3]
+
+    def _model(self, kind, x, mwapr, low, high, constraint, log_fator, beta=0.01):
+        mw = self._to_mw(x, low, high, constraint, log_fator)
+        self._use_reg(kind, 1.0, beta, mwapr)
+        return self._engine.misfit_and_grad(mw)[4]
+
+    def model_MS(self, x, mwapr, low, high, constraint, log_fator, beta):
+        return self._model("MS", x, mwapr, low, high, constraint, log_fator, beta)
+
+    def model_Damping(self, x, mwapr, low, high, constraint, log_fator):
+        return self._model("Damping", x, mwapr, low, high, constraint, log_fator)
+
+    def model_Smoothness(self, x, mwapr, low, high, constraint, log_fator):
+        return self._model("Smoothness", x, mwapr, low, high, constraint, log_fator)
+
+    def model_TV(self, x, mwapr, low, high, constraint, log_fator, beta):
+        return self._model("TV", x, mwapr, low, high, constraint, log_fator, beta)
+
+
+class GravMagModule(_Potential):
     """Gravity / magnetic inversion model: mesh + sensitivity matrix + potential, on one MI355X.
 
     Parameters are the reference's (potential.py:35-58):
@@ -220,62 +286,3 @@ class GravMagModule(object):
     def kernelw(self):
         """(Aw, WmInv, Wm) as the sampler expects (potential.py:584-589); Aw is a device handle."""
         return self.Aw, self.WmInv, self.Wm
-
-    # ------------------------------------------------------------------ potential
-    def _to_mw(self, x, low, high, constraint, log_fator):
-        if constraint == 'logarithmic':
-            return (low + high * np.e ** (log_fator * x)) / (1 + np.e ** (log_fator * x))
-        elif constraint == 'mandatory':
-            return x
-        raise ValueError("Please choose right boundary constraint(mandatory, logarithmic)!")
-
-    def _use_reg(self, regulization, alpha, beta, mwapr):
-        if regulization not in _lib.REG_KINDS:
-            raise ValueError("Please choose regularization from 'MS','Damping', 'Smoothness', 'TV'.")
-        mwapr = np.asarray(mwapr, dtype=np.float64)
-        # The decision to (re)send the regulariser must be the same on every rank of a sharded
-        # model (gh_set_reg is collective there) and must notice in-place edits: it depends only
-        # on the VALUES -- kind, alpha, beta and the content of the full mwapr vector -- never on
-        # addresses.  The content is compared through a 64-bit digest of its bytes (xxh3: ~10 GB/s,
-        # one pass, no second copy of the vector kept; zlib.crc32 pair where xxhash is missing).
-        key = (regulization, float(alpha), float(beta))
-        digest = (mwapr.shape, _digest(mwapr))
-        last = self._engine._reg_key
-        if last is None or last[0] != key or last[1] != digest:
-            m_model = getattr(self._engine, "M_global", self._engine.M)
-            if regulization in ("Smoothness", "TV") and int(np.prod(self.mshape)) != m_model:
-                raise ValueError("Smoothness/TV need the full (uncarved) mesh: shape %r has %d "
-                                 "cells, model has %d" % (self.mshape, int(np.prod(self.mshape)),
-                                                          m_model))
-            self._engine.set_reg(regulization, alpha, beta, self.mshape, mwapr)
-            self._engine._reg_key = (key, digest)
-
-    def misfit_and_grad(self, x, mwapr, low, high, constraint, log_fator, alpha,
-                        regulization='Damping', beta=0.01):
-        """(misfit, grad, dpre, data_value, model_value) -- potential.py:812-845."""
-        mw = self._to_mw(x, low, high, constraint, log_fator)
-        self._use_reg(regulization, alpha, beta, mwapr)
-        return self._engine.misfit_and_grad(mw)
-
-    # wrappers the reference keeps for an (unused) adaptive regularisation factor
-    def data(self, x, low, high, constraint, log_fator):
-        mw = self._to_mw(x, low, high, constraint, log_fator)
-        self._use_reg("Damping", 0.0, 0.01, np.zeros(self._engine.M))
-        return self._engine.misfit_and_grad(mw)[3]
-
-    def _model(self, kind, x, mwapr, low, high, constraint, log_fator, beta=0.01):
-        mw = self._to_mw(x, low, high, constraint, log_fator)
-        self._use_reg(kind, 1.0, beta, mwapr)
-        return self._engine.misfit_and_grad(mw)[4]
-
-    def model_MS(self, x, mwapr, low, high, constraint, log_fator, beta):
-        return self._model("MS", x, mwapr, low, high, constraint, log_fator, beta)
-
-    def model_Damping(self, x, mwapr, low, high, constraint, log_fator):
-        return self._model("Damping", x, mwapr, low, high, constraint, log_fator)
-
-    def model_Smoothness(self, x, mwapr, low, high, constraint, log_fator):
-        return self._model("Smoothness", x, mwapr, low, high, constraint, log_fator)
-
-    def model_TV(self, x, mwapr, low, high, constraint, log_fator, beta):
-        return self._model("TV", x, mwapr, low, high, constraint, log_fator, beta)

@@ -77,8 +77,10 @@ typedef enum {
 
 /* GH_CELL_PRISM_TF: prisms, total-field magnetic anomaly (set with gh_set_cells_tf, not gh_set_cells);
  * GH_CELL_PRISM_COMP: prisms, one gravity field other than gz (set with gh_set_cells_prism);
- * GH_CELL_TESSEROID_COMP: tesseroids, one gravity field other than gz (set with gh_set_cells_tess) */
-enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2, GH_CELL_PRISM_COMP = 3, GH_CELL_TESSEROID_COMP = 4 };
+ * GH_CELL_TESSEROID_COMP: tesseroids, one gravity field other than gz (set with gh_set_cells_tess);
+ * GH_CELL_PRISM_JOINT: prisms, gz and the total field inverted together (set with gh_set_cells_joint) */
+enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2, GH_CELL_PRISM_COMP = 3, GH_CELL_TESSEROID_COMP = 4,
+       GH_CELL_PRISM_JOINT = 5 };
 /* The gravity fields of prisms (gravmag/prism.py:875-972), for gh_set_cells_prism, and of tesseroids
  * (gravmag/tesseroid.py:324-508), for gh_set_cells_tess (gy of tesseroids: G * SI2MGAL with the
  * reference's spherical G, Gs = 6.673e-11, 1000 times smaller than the G of every other field) */
@@ -130,6 +132,35 @@ int gh_set_cells_tf(gh_ctx *ctx, const double *bounds6, double fx, double fy, do
  * in uT, accumulated corner by corner, cell by cell in mesh order into one sum per observation and
  * scaled once, as the reference does. */
 int gh_tf_result(gh_ctx *ctx, const double *mag3, double *result);
+/* Joint gravity-magnetic inversion (GH_CELL_PRISM_JOINT, inversion/potential.py:847-1812): the density and
+ * the magnetization of the same M/2 prisms (bounds6: M/2 x 6 row-major x1,x2,y1,y2,z1,z2 in mesh order)
+ * under the same N/2 observation points.  The kernel is block-diagonal, A = [[A_gz, 0], [0, A_tf]] (N x M;
+ * the tf block along (fx, fy, fz) as gh_set_cells_tf), but the device stores H = [A_gz | A_tf] only: N/2
+ * rows (padded as G) by M columns, the gz block in columns [0, M/2).  Every vector of the interface keeps
+ * the stacked shape: observation-space vectors have N entries (gz first), model-space vectors M.
+ * N and M must be even.  Call it on a fresh context, BEFORE gh_set_obs, which then takes the N/2 points.
+ *   gh_build_G   assembles both blocks in one launch, entry for entry the bits of a gz and a tf context.
+ *   gh_weight    (weightfactor 0.5 only) takes the column norms Wm of the unbalanced A, the population
+ *                standard deviations std_gz, std_tf of the two unweighted blocks (gh_joint_std), and
+ *                leaves Aw = Wb A Wm^-1 with Wb = diag(1 (N/2 times), s (N/2 times)), s = std_gz / std_tf,
+ *                folded into the stored tf block.
+ *   gh_set_data  takes dobs = dobsw = Wb [dobs_gz; dobs_tf] (N entries) and NO mean is removed; grav_fix
+ *                must be null.  The data term is |Aw mw - dobsw|^2 (potential.py:1665-1680).
+ *   gh_set_reg / gh_reg_eval: Smoothness and TV take shape3 with nz*ny*nx == M/2 and apply the stencil to
+ *                each property on its own (the block-diagonal fd3djoint, potential.py:1075): no term
+ *                couples the two blocks.
+ * Dense, single chain only: matrix-free, the shift-invariant store, the wavelet compressor, gh_batch_*,
+ * gh_shard_init*, gh_upload_G and N/2 > 16384 return GH_ERR_UNSUPPORTED; the resident chain kernel is
+ * never chosen (chains run on the fused sweep). */
+int gh_set_cells_joint(gh_ctx *ctx, const double *bounds6, double fx, double fy, double fz);
+/* std_gz, std_tf of the unweighted blocks of a weighted GH_CELL_PRISM_JOINT context (numpy.std, ddof 0,
+ * over the (N/2) (M/2) entries of each block; two passes on the device) */
+int gh_joint_std(const gh_ctx *ctx, double std2[2]);
+/* How a GH_CELL_PRISM_JOINT context runs a potential evaluation: the sweep's workgroups per block (each writes
+ * one slab row of its block's partial forward product) and the epilogue's stages per block (1: reduce_finish_kernel
+ * over the slab rows; 2: below 2048 rows with more than 64 slab rows per block, reduce_reg_kernel folds them into
+ * segments first) */
+int gh_joint_layout(const gh_ctx *ctx, int *workgroups_per_block, int *epilogue_stages);
 /* Prisms of a density model for one gravity field `component` (GH_COMP_*), M x 6 row-major
  * x1,x2,y1,y2,z1,z2 in mesh order.  Entry (i, j) is the field at observation i of prism j with a density
  * of 1 g/cm^3, scaled as prism.py scales kernel2d: G for the potential, G/g0 for the geoid, G*SI2MGAL for
@@ -252,7 +283,8 @@ int gh_weight(gh_ctx *ctx, double weightfactor, double *wm_out);
 /* ---- potential (inversion/potential.py:688-845) ---------------------------------------- */
 
 /* Observed data and, optionally, the field of fixed cells (`fixed=True, grav_fix=...`,
- * potential.py:700-703); pass NULL when unused. */
+ * potential.py:700-703); pass NULL when unused.  The mean of dobs is removed.  On a GH_CELL_PRISM_JOINT
+ * context dobs is the balanced dobsw (N entries, gz first), taken as it is: no mean removal, no grav_fix. */
 int gh_set_data(gh_ctx *ctx, const double *dobs, const double *grav_fix_or_null);
 /* Regulariser: kind (GH_REG_*), alpha (hmc RegulFactor), beta (MS/TV), mesh shape
  * (nz,ny,nx) for Smoothness/TV (must satisfy nz*ny*nx == M), weighted prior
