@@ -10,7 +10,7 @@
 // the updated positions.  Both products of all chains from one read of G (hmc.py:114-152 for every
 // chain; potential.py:698,708 are the two products).
 //
-// Exchange (the data is the flag, resident.hip.h: a double travels as two tagged 8-byte granules,
+// Exchange (the data is the flag, exchange.hip.h: a double travels as two tagged 8-byte granules,
 // written through, read with agent-scope loads, no fences, correct under any placement), a
 // reduce-scatter and an all-gather of one hop each:
 //   iteration it      every member publishes its 256 partial dots of tile it
@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(BT_NW * 64) batch_team_kernel(BatchAdjArgs a, 
     const int64_t ntiles = (a.M + 15) / 16;
     const int64_t t0 = (int64_t)cr * f.tiles_per_range;
     const int ntl = (int)((ntiles - t0 < f.tiles_per_range) ? ntiles - t0 : f.tiles_per_range);
-    if (tid == 0) abort_s = (__hip_atomic_load(f.abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) ? 1 : 0;
+    if (tid == 0) abort_s = gave_up_before(f.abort_w) ? 1 : 0;
     if (tid < 16) {
         chs[0][tid] = (double)a.phase[tid];
         chs[1][tid] = a.cu[tid];
@@ -244,18 +244,8 @@ __global__ void __launch_bounds__(BT_NW * 64) batch_team_kernel(BatchAdjArgs a, 
         if (gran_value(ga, gb, tag, val)) return true;
         unsigned spins = 0;
         long long tstart = 0;
-        while (!ld_gran(g, tag, val)) {
-            __builtin_amdgcn_s_sleep(1);
-            if ((++spins & 63u) == 0) {
-                const long long now = wall_clock64();
-                if (tstart == 0) tstart = now;
-                if (__hip_atomic_load(f.abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-                    now - tstart > RES_TIMEOUT_TICKS) {
-                    __hip_atomic_store(f.abort_w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    return false;
-                }
-            }
-        }
+        while (!ld_gran(g, tag, val))
+            if (spin_gave_up(spins, tstart, f.abort_w)) return false;
         return true;
     };
     if (ntl > 0) tile_load(ts[0], t0);

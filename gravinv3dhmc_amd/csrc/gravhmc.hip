@@ -3,6 +3,7 @@
 #include "../../include/gravhmc.h"
 #include "kernels.hip.h"
 #include "batch.hip.h"
+#include "exchange.hip.h"
 #include "resident.hip.h"
 #include "resbatch.hip.h"
 #include "teamsweep.hip.h"
@@ -424,7 +425,7 @@ int gh_shift_invariant_resident_stats(gh_ctx *c, int *workgroups, int64_t *launc
     if (launches) *launches = c->ls ? c->ls->res.launches : 0;
     if (evaluations) *evaluations = c->ls ? c->ls->res.evals : 0;
     if (trajectories) *trajectories = c->ls ? c->ls->res.trajectories : 0;
-    if (timeouts) *timeouts = c->ls ? c->ls->res.aborts : 0;
+    if (timeouts) *timeouts = c->ls ? c->ls->res.xg.aborts : 0;
     return GH_OK;
 }
 
@@ -1518,7 +1519,7 @@ int gh_team_sweep_stats(gh_ctx *c, int *members, int64_t *launches, int *timeout
     if (late_parts) *late_parts = c->tm.late_polls;
     if (members) *members = c->tm.state != 0 ? c->tm.Q : 0;
     if (launches) *launches = c->tm.launches;
-    if (timeouts) *timeouts = c->tm.aborts;
+    if (timeouts) *timeouts = c->tm.xg.aborts;
     return GH_OK;
 }
 
@@ -1615,15 +1616,15 @@ static int kids_make(gh_ctx *c, int C, const double *x0s, const double *low, con
         k->ls->res.state = -1;  // (the persistent pass takes every CU: not for chains that share the GPU)
         k->ls->dbg = nullptr;
         k->ls->csum = nullptr;
-        k->ls->epi_abort = nullptr;
+        k->ls->epi = ExchangeGuard();
         k->ls->rhat_of = nullptr;
         k->ls->post_pending = false;
-        k->ls->epi_tag = 0;
         if (k->ls->harm) {
             int rc = dalloc(k, &k->ls->Rhat, (size_t)k->ls->na * (size_t)k->ls->nf);
             if (rc == GH_OK) rc = dalloc(k, &k->ls->Dpart, (size_t)k->ls->hgrid * (size_t)k->ls->na * (size_t)k->ls->nf);
             if (rc == GH_OK && k->ls->fused) rc = dalloc(k, &k->ls->csum, 2 * (size_t)k->ls->na);
-            if (rc == GH_OK && k->ls->fused) rc = dalloc(k, &k->ls->epi_abort, 4);
+            if (rc == GH_OK && k->ls->fused)
+                rc = xg_alloc(k, k->ls->epi, {{k->ls->csum, sizeof(unsigned long long) * 2 * (size_t)k->ls->na}});
             if (rc != GH_OK) return fail(c, rc, "gh_batch_init: %s", gh_last_error(k));
         }
         if (k->ls->wide) {
@@ -2361,7 +2362,7 @@ int gh_batch_fused_stats(gh_ctx *c, int *members, int *ranges, int64_t *launches
     if (members) *members = b.fus_on ? b.fus_members : 0;
     if (ranges) *ranges = b.fus_on ? b.fus_ranges : 0;
     if (launches) *launches = b.fus_launches;
-    if (timeouts) *timeouts = b.fus_aborts;
+    if (timeouts) *timeouts = b.fus.aborts;
     return GH_OK;
 }
 
@@ -2372,7 +2373,7 @@ int gh_matrix_free_team_stats(gh_ctx *c, int *members, int *ranges, int64_t *lau
     if (members) *members = t.state == 1 ? t.members : 0;
     if (ranges) *ranges = t.state == 1 ? t.ranges : 0;
     if (launches) *launches = t.launches;
-    if (timeouts) *timeouts = t.aborts;
+    if (timeouts) *timeouts = t.xg.aborts;
     return GH_OK;
 }
 
@@ -2385,7 +2386,7 @@ int gh_batch_resident_stats(gh_ctx *c, int64_t *launches, int64_t *lock_steps, i
     if (lock_steps) *lock_steps = b.lock_steps;
     if (chain_steps) *chain_steps = b.chain_steps;
     if (lost_steps) *lost_steps = b.lost;
-    if (timeouts) *timeouts = b.aborts;
+    if (timeouts) *timeouts = b.xg.aborts;
     return GH_OK;
 }
 

@@ -151,10 +151,11 @@ static bool mft_plan(gh_ctx *c)
         return false;
     }
     if (mf_near_deltas(c) != GH_OK) return false;
-    if (dalloc(c, &t.gran, (size_t)t.ranges * MFB_FUS_RING * MFT_MAXMEM * 32) != GH_OK || dalloc(c, &t.abort_w, 4) != GH_OK ||
+    const size_t ng = (size_t)t.ranges * MFB_FUS_RING * MFT_MAXMEM * 32;
+    if (dalloc(c, &t.gran, ng) != GH_OK || xg_alloc(c, t.xg, {{t.gran, ng * sizeof(u64)}}) != GH_OK ||
         dalloc(c, &t.snear, (size_t)c->M) != GH_OK)
         return false;
-    t.tag = 0;
+    t.xg.tag = 0;
     t.state = 1;
     return true;
 }
@@ -166,10 +167,7 @@ static int mft_launch(gh_ctx *c, SweepArgs &a)
     gh_ctx::Batch &b = c->bt;
     a.ld = c->ld;
     a.M = c->M;
-    if ((uint64_t)t.tag + (uint64_t)t.tpr + 2 > 0xf0000000ull) {
-        HIPCHK(c, hipMemsetAsync(t.gran, 0, sizeof(u64) * (size_t)t.ranges * MFB_FUS_RING * MFT_MAXMEM * 32, c->stream));
-        t.tag = 0;
-    }
+    TRY(xg_prepare(c, t.xg, false, (uint64_t)t.tpr + 2));
     const double *wm = c->weighted ? c->wm : nullptr;
     if (b.mfb_near)
         mf1_near_adjoint_kernel<<<dim3((unsigned)c->M), dim3(64), 0, c->stream>>>(c->mf_near_ptr, c->mf_near_row, b.ndelta,
@@ -177,15 +175,15 @@ static int mft_launch(gh_ctx *c, SweepArgs &a)
     MftArgs f;
     f.tiles_per_range = t.tpr;
     f.gran = t.gran;
-    f.tag0 = t.tag;
-    f.abort_w = t.abort_w;
+    f.tag0 = t.xg.tag;
+    f.abort_w = t.xg.abort_w;
     f.poll_members = t.members + ((env_int("GRAVHMC_MF_TEAM_TEST_ABORT", 0) && t.members < MFT_MAXMEM) ? 1 : 0);
     f.n_pp = c->n_teams;
     f.snear = b.mfb_near ? t.snear : nullptr;
     hipLaunchKernelGGL(mft_for(c), dim3((unsigned)t.members, (unsigned)t.ranges), dim3(1024), MFT_LDS, c->stream, mf_geom(c),
                        a, f, wm, c->mf_cellc, c->prof ? c->mf_stats : nullptr);
-    t.tag += (unsigned)t.tpr + 1u;
-    t.inflight = true;
+    t.xg.tag += (unsigned)t.tpr + 1u;
+    t.xg.inflight = true;
     t.launches += 1;
     if (a.mode & SW_FWD) {
         int rows = t.ranges;
@@ -208,17 +206,15 @@ static int mft_failed(gh_ctx *c, bool *failed)
 {
     gh_ctx::MfTeam &t = c->mft;
     *failed = false;
-    if (!t.inflight) return GH_OK;
-    t.inflight = false;
-    unsigned w[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(w, t.abort_w, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    if (!t.xg.inflight) return GH_OK;
+    t.xg.inflight = false;
+    TRY(xg_read(c, t.xg));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (w[0] == 0u) return GH_OK;
+    if (t.xg.seen[0] == 0u) return GH_OK;
     fprintf(stderr, "libgravhmc: the matrix-free team pass timed out waiting for its workgroups; repeating the "
                     "trajectory on the column-per-workgroup pass\n");
-    HIPCHK(c, hipMemsetAsync(t.abort_w, 0, 4 * sizeof(unsigned), c->stream));
+    xg_give_up(t.xg, 1);
     t.state = -1;
-    t.aborts += 1;
     *failed = true;
     return GH_OK;
 }
@@ -256,9 +252,10 @@ static int mfb_plan(gh_ctx *c)
             hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(ff), 1024, MFB_LDS_FUS) ==
                 hipSuccess &&
             per_cu >= 1 && (int64_t)per_cu * c->cus >= (int64_t)b.fus_members * b.fus_ranges) {
-            TRY(dalloc(c, &b.fus_gran, (size_t)b.fus_ranges * MFB_FUS_RING * MFB_FUS_MAXMEM * 512));
-            TRY(dalloc(c, &b.fus_abort, 4));
-            b.fus_tag = 0;
+            const size_t ng = (size_t)b.fus_ranges * MFB_FUS_RING * MFB_FUS_MAXMEM * 512;
+            TRY(dalloc(c, &b.fus_gran, ng));
+            TRY(xg_alloc(c, b.fus, {{b.fus_gran, ng * sizeof(u64)}}));
+            b.fus.tag = 0;
             b.fus_on = true;
         } else {
             (void)hipGetLastError();
@@ -317,10 +314,11 @@ static int bteam_plan(gh_ctx *c)
         (void)hipGetLastError();
         return GH_OK;
     }
-    TRY(dalloc(c, &b.fus_gran, (size_t)b.fus_ranges * BT_RING * BT_MAXMEM * 512));
-    TRY(dalloc(c, &b.fus_granx, (size_t)b.fus_ranges * BT_RING * 512));
-    TRY(dalloc(c, &b.fus_abort, 4));
-    b.fus_tag = 0;
+    const size_t ng = (size_t)b.fus_ranges * BT_RING * BT_MAXMEM * 512, ngx = (size_t)b.fus_ranges * BT_RING * 512;
+    TRY(dalloc(c, &b.fus_gran, ng));
+    TRY(dalloc(c, &b.fus_granx, ngx));
+    TRY(xg_alloc(c, b.fus, {{b.fus_gran, ng * sizeof(u64)}, {b.fus_granx, ngx * sizeof(u64)}}));
+    b.fus.tag = 0;
     b.fus_on = true;
     return GH_OK;
 }
@@ -377,17 +375,13 @@ static int batch_launch_adjoint(gh_ctx *c, BatchAdjArgs &a, bool fwd_follows)
             mfb_near_adjoint_kernel<<<dim3((unsigned)c->M), dim3(256), 0, c->stream>>>(
                 c->mf_near_ptr, c->mf_near_row, b.ndelta, c->M, a.Rt, b.Snear);
         }
-        if ((uint64_t)b.fus_tag + (uint64_t)b.fus_tpr + 2 > 0xf0000000ull) {
-            HIPCHK(c, hipMemsetAsync(b.fus_gran, 0, sizeof(u64) * (size_t)b.fus_ranges * MFB_FUS_RING * MFB_FUS_MAXMEM * 512,
-                                     c->stream));
-            b.fus_tag = 0;
-        }
+        TRY(xg_prepare(c, b.fus, false, (uint64_t)b.fus_tpr + 2));
         MfbFusArgs f;
         f.tiles_per_range = b.fus_tpr;
         f.slab = b.slab;
         f.gran = b.fus_gran;
-        f.tag0 = b.fus_tag;
-        f.abort_w = b.fus_abort;
+        f.tag0 = b.fus.tag;
+        f.abort_w = b.fus.abort_w;
         // test hook: the members wait for a part that never comes, time out and give up
         f.poll_members = b.fus_members + ((env_int("GRAVHMC_MFB_TEST_ABORT", 0) && b.fus_members < MFB_FUS_MAXMEM) ? 1 : 0);
         f.n_pp = b.n_waves;
@@ -402,8 +396,8 @@ static int batch_launch_adjoint(gh_ctx *c, BatchAdjArgs &a, bool fwd_follows)
                            b.mfb_near ? b.Snear : nullptr, c->prof ? c->mf_stats : nullptr);
         TRY(batch_time_end(c, timed));
         if (c->prof) c->mf_launches += 1;
-        b.fus_tag += (unsigned)b.fus_tpr + 1u;
-        b.fus_inflight = true;
+        b.fus.tag += (unsigned)b.fus_tpr + 1u;
+        b.fus.inflight = true;
         b.fus_launches += 1;
         b.fus_fwd_of = a.X_out;
     } else if (c->mf) {
@@ -420,19 +414,15 @@ static int batch_launch_adjoint(gh_ctx *c, BatchAdjArgs &a, bool fwd_follows)
     } else if (b.fus_on) {
         // stored kernel on teams: adjoint of all chains, update and the forward at the new positions from ONE
         // read of G (an adjoint nothing follows costs the same read: the forward rides along unused)
-        if ((uint64_t)b.fus_tag + (uint64_t)b.fus_tpr + 2 > 0xf0000000ull) {
-            HIPCHK(c, hipMemsetAsync(b.fus_gran, 0, sizeof(u64) * (size_t)b.fus_ranges * BT_RING * BT_MAXMEM * 512, c->stream));
-            HIPCHK(c, hipMemsetAsync(b.fus_granx, 0, sizeof(u64) * (size_t)b.fus_ranges * BT_RING * 512, c->stream));
-            b.fus_tag = 0;
-        }
+        TRY(xg_prepare(c, b.fus, false, (uint64_t)b.fus_tpr + 2));
         BtArgs f;
         f.tiles_per_range = b.fus_tpr;
         f.nval = b.fus_nval;
         f.slab = b.slab;
         f.gran_p = b.fus_gran;
         f.gran_x = b.fus_granx;
-        f.tag0 = b.fus_tag;
-        f.abort_w = b.fus_abort;
+        f.tag0 = b.fus.tag;
+        f.abort_w = b.fus.abort_w;
         // test hook: the members wait for a part that never comes, time out and give up
         f.poll_members = b.fus_members + ((env_int("GRAVHMC_BATCH_TEAM_TEST_ABORT", 0) && b.fus_members < BT_MAXMEM) ? 1 : 0);
         f.n_pp = b.n_waves;
@@ -448,8 +438,8 @@ static int batch_launch_adjoint(gh_ctx *c, BatchAdjArgs &a, bool fwd_follows)
         hipLaunchKernelGGL(batch_team_kernel, dim3((unsigned)b.fus_members, (unsigned)b.fus_ranges), dim3(BT_NW * 64), BT_LDS,
                            c->stream, a, f);
         TRY(batch_time_end(c, timed));
-        b.fus_tag += (unsigned)b.fus_tpr + 1u;
-        b.fus_inflight = true;
+        b.fus.tag += (unsigned)b.fus_tpr + 1u;
+        b.fus.inflight = true;
         b.fus_launches += 1;
         if (fwd_follows) b.fus_fwd_of = a.X_out;
     } else {
@@ -545,17 +535,15 @@ static int mfb_fused_failed(gh_ctx *c, bool *failed)
 {
     gh_ctx::Batch &b = c->bt;
     *failed = false;
-    if (!b.fus_inflight) return GH_OK;
-    b.fus_inflight = false;
-    unsigned w[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(w, b.fus_abort, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    if (!b.fus.inflight) return GH_OK;
+    b.fus.inflight = false;
+    TRY(xg_read(c, b.fus));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (w[0] == 0u) return GH_OK;
+    if (b.fus.seen[0] == 0u) return GH_OK;
     fprintf(stderr, "libgravhmc: the %s timed out waiting for its workgroups; continuing with the two-pass kernels\n",
             c->mf ? "fused matrix-free batch pass" : "batch's team pass");
-    HIPCHK(c, hipMemsetAsync(b.fus_abort, 0, 4 * sizeof(unsigned), c->stream));
+    xg_give_up(b.fus, 1);
     b.fus_on = false;
-    b.fus_aborts += 1;
     b.fus_fwd_of = nullptr;
     *failed = true;
     TRY(batch_relayout(c));  // (stored kernel: the two-pass adjoint's copy of G, not made while the teams ran)

@@ -11,6 +11,19 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// The host half of a persistent launch's exchange (exchange.hip.h): the abort word its workgroups raise
+// when a wait gives up, the 32-bit tags its granules carry across launches, and what a give-up leaves to
+// clear.  Every path whose workgroups wait for each other embeds one (xg_* below).
+struct ExchangeGuard {
+    unsigned *abort_w = nullptr;           // 4 words: [0] raised by a give-up, [1] late polls of the team sweep
+    unsigned seen[4] = {0, 0, 0, 0};       // the abort word as last read back (xg_read)
+    unsigned tag = 0, tagE = 0, ltag = 0;  // tags used so far (a path uses one, two or three of them)
+    std::vector<DevBuf> grans;             // granule buffers zeroed when the tags start again
+    bool dirty = false;                    // a launch gave up: its granules carry tags a later launch would use
+    bool inflight = false;                 // launched since the abort word was last read back (team family)
+    int aborts = 0;                        // launches that gave up
+};
+
 struct gh_ctx {
     int device = 0;
     int64_t N = 0, M = 0, ld = 0;
@@ -64,11 +77,8 @@ struct gh_ctx {
         int state = 0;  // 0 not planned, 1 usable, -1 not applicable / given up
         int members = 0, ranges = 0, tpr = 0;
         ghk::u64 *gran = nullptr;
-        unsigned *abort_w = nullptr;
-        unsigned tag = 0;
+        ExchangeGuard xg;  // off at the first give-up
         double *snear = nullptr;
-        bool inflight = false;
-        int aborts = 0;
         int64_t launches = 0;
     } mft;
     bool chain_teams_ok = false;  // set by the trajectory code around its sweeps (it handles a time-out)
@@ -95,10 +105,7 @@ struct gh_ctx {
         int64_t cols_per_team = 0;
         size_t lds = 0;
         ghk::u64 *gran = nullptr;
-        unsigned *abort_w = nullptr;
-        unsigned tag = 0;
-        bool inflight = false;  // launched since the abort word was last looked at
-        int aborts = 0;
+        ExchangeGuard xg;  // off for good after three give-ups
         int64_t launches = 0;
         unsigned late_polls = 0;
     } tm;
@@ -219,15 +226,14 @@ struct gh_ctx {
         int mfb_grid_adj = 0, mfb_rchunks = 0, mfb_ranges = 0, mfb_tpr = 0;
         int slab_live = 0;        // blocks of the slab the last matrix-free forward wrote
         // team pass: one evaluation (mfb_fused_kernel) / one read (batch_team_kernel, stored G) per entry and step
-        bool fus_on = false, fus_inflight = false;
-        int fus_members = 0, fus_ranges = 0, fus_tpr = 0, fus_aborts = 0;
+        bool fus_on = false;
+        int fus_members = 0, fus_ranges = 0, fus_tpr = 0;
         ghk::u64 *fus_gran = nullptr;
         ghk::u64 *fus_granx = nullptr;  // stored kernel on teams (batch_team_kernel): the new positions' granules
         int fus_nval = 0;               // ... and the (cell, chain) pairs of a tile a member updates
-        unsigned *fus_abort = nullptr;
+        ExchangeGuard fus;             // either team pass (off at the first give-up)
         long long *fus_dbg = nullptr;  // GRAVHMC_MFB_TIMING: per-phase clocks of one workgroup
         double *Pstart = nullptr;      // M x 16: the momentum each trajectory in flight started with (gh_batch_run)
-        unsigned fus_tag = 0;
         int64_t fus_launches = 0;
         const double *fus_fwd_of = nullptr;  // the X whose forward partials the last fused launch left in the slab
         double *h = nullptr;      // pinned
@@ -257,8 +263,7 @@ struct gh_ctx {
         size_t lds = 0;
         ghk::u64 *slabg = nullptr, *xslabg = nullptr, *dclg = nullptr, *scalg = nullptr, *xscalg = nullptr, *xccg = nullptr;
         double *xpub = nullptr;
-        unsigned *abort_w = nullptr;
-        unsigned tag = 0, tagE = 0;  // granule tags used so far (the buffers keep them across launches)
+        ExchangeGuard xg;  // after three give-ups the context stays on the sweep path
         int Kcap = 0;
         int *L = nullptr, *accepted = nullptr, *n_run = nullptr, *chain = nullptr;
         int lds_max = 0;
@@ -267,8 +272,6 @@ struct gh_ctx {
         bool b_on = false, b_state = false;
         double *p0s = nullptr, *us = nullptr, *out5s = nullptr, *xacc = nullptr;
         int64_t launches = 0, evals = 0;
-        int aborts = 0;               // launches that timed out (3: the context stays on the sweep path)
-        bool granules_dirty = false;  // an aborted launch left tags behind: clear before the next launch
         long long *dbg = nullptr;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         // the chains in LOCK-STEP (resbatch.hip.h): planned per gh_batch_init
@@ -289,11 +292,9 @@ struct gh_ctx {
             const double **p0tab = nullptr;  // device: where each list element's momentum row lies (chain-major)
             int64_t rows_direct = 0, rows_staged = 0;  // rows sent straight from the caller's pinned memory / gathered first
             int cap = 0;                 // list elements the device lists hold
-            unsigned tag = 0, ltag = 0;
-            bool dirty = false;          // an aborted launch left tags behind
+            ExchangeGuard xg;            // off at the first give-up
             bool active[16] = {};        // chain has a trajectory in flight (carry-over mode)
             int64_t launches = 0, lock_steps = 0, lost = 0, chain_steps = 0;
-            int aborts = 0;
             long long *dbg = nullptr;
         } ls;
     } rs;
@@ -362,6 +363,48 @@ static int dalloc(gh_ctx *c, T **out, size_t count, bool zero = true)
         int rc_ = (x);         \
         if (rc_ != GH_OK) return rc_; \
     } while (0)
+
+// tags start again on zeroed granules before any of them would pass this
+constexpr uint64_t XG_TAG_LIMIT = 0xf0000000ull;
+
+// The abort word (zeroed), and the granule buffers a restart of the tags zeroes, known at plan time.
+static int xg_alloc(gh_ctx *c, ExchangeGuard &g, std::vector<DevBuf> grans)
+{
+    TRY(dalloc(c, &g.abort_w, 4));
+    g.grans = std::move(grans);
+    return GH_OK;
+}
+
+// Before a launch that may advance tag / tagE by up to ahead / aheadE (ltag: by one): after a give-up, or
+// where a tag would pass the limit, zero the granules and start the tags again.  rearm: zero the abort word
+// before every launch (the resident family); otherwise only after a give-up (the team family, whose kernels
+// look at the word at entry and leave while it is raised).
+static int xg_prepare(gh_ctx *c, ExchangeGuard &g, bool rearm, uint64_t ahead, uint64_t aheadE = 0)
+{
+    if (g.dirty || g.tag + ahead > XG_TAG_LIMIT || g.tagE + aheadE > XG_TAG_LIMIT || g.ltag > XG_TAG_LIMIT) {
+        for (const DevBuf &b : g.grans) HIPCHK(c, hipMemsetAsync(b.p, 0, b.bytes, c->stream));
+        g.tag = g.tagE = g.ltag = 0;
+        rearm = rearm || g.dirty;
+        g.dirty = false;
+    }
+    if (rearm) HIPCHK(c, hipMemsetAsync(g.abort_w, 0, sizeof g.seen, c->stream));
+    return GH_OK;
+}
+
+// Enqueue the copy of the abort word into g.seen; the path's own synchronisation point delivers it.
+static int xg_read(gh_ctx *c, ExchangeGuard &g)
+{
+    HIPCHK(c, hipMemcpyAsync(g.seen, g.abort_w, sizeof g.seen, hipMemcpyDeviceToHost, c->stream));
+    return GH_OK;
+}
+
+// A launch gave up (g.seen[0] raised): count it; its granules and the abort word are cleared before the next
+// launch.  true: the path's strikes are used up.
+static bool xg_give_up(ExchangeGuard &g, int strikes)
+{
+    g.dirty = true;
+    return ++g.aborts >= strikes;
+}
 
 static int h2d(gh_ctx *c, double *dst, const double *src, size_t n)
 {

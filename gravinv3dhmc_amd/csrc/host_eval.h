@@ -214,13 +214,9 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
         e.scal = scal_out;
         e.r2part = o.part;
         e.csum = h.csum;
-        h.epi_tag += 1u;
-        if (h.epi_tag > 0xf0000000u) {
-            HIPCHK(c, hipMemsetAsync(h.csum, 0, sizeof(unsigned long long) * 2 * (size_t)h.na, c->stream));
-            h.epi_tag = 1u;
-        }
-        e.tag = h.epi_tag;
-        e.abort_w = h.epi_abort;
+        TRY(xg_prepare(c, h.epi, false, 1));
+        e.tag = ++h.epi.tag;
+        e.abort_w = h.epi.abort_w;
         e.ra = ra;
         e.ra.regpart = o.part + c->n_dpart;
         lonsymh_epilogue_kernel<<<dim3((unsigned)(h.na + c->n_regpart)), dim3(256), 0, c->stream>>>(lonsymh_geom(c), e);

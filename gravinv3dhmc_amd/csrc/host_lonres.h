@@ -72,7 +72,12 @@ static int chain_run_lonres(gh_ctx *c, gh_ctx *st, int K, const int *L, const do
         TRY(dalloc(c, &r.scalg, 2 * (size_t)LR_MAXWG * 2));
         TRY(dalloc(c, &r.ppg, 2 * (size_t)LR_MAXWG * 2));
         TRY(dalloc(c, &r.xpub, 2 * (size_t)c->M));
-        TRY(dalloc(c, &r.abort_w, 4));
+        TRY(xg_alloc(c, r.xg, {{r.flagg, ((size_t)nwg + 8) * sizeof(ghk::u64)},
+                               {r.xccg, ((size_t)nwg + 8) * sizeof(ghk::u64)},
+                               {r.xslabg, 2 * (size_t)RES_CLUSTERS * E * 2 * sizeof(ghk::u32x4)},
+                               {r.clsg, 2 * 64 * 4 * sizeof(ghk::u32x4)},
+                               {r.scalg, 2 * (size_t)LR_MAXWG * 2 * sizeof(ghk::u32x4)},
+                               {r.ppg, 2 * (size_t)LR_MAXWG * 2 * sizeof(ghk::u32x4)}}));
         TRY(dalloc(c, &r.n_run, 4));
         TRY(dalloc(c, &r.ucur, 4));
         // M^ = the transform of the slots' observation counts: R^ of a residual of ones
@@ -107,18 +112,7 @@ static int chain_run_lonres(gh_ctx *c, gh_ctx *st, int K, const int *L, const do
     }
     int64_t steps = 1;
     for (int k = 0; k < K; ++k) steps += L[k];
-    if (r.dirty || (uint64_t)r.tag + (uint64_t)steps + 2 > 0xf0000000ull || (uint64_t)r.tagE + (uint64_t)K + 2 > 0xf0000000ull ||
-        r.ltag > 0xf0000000u) {
-        HIPCHK(c, hipMemsetAsync(r.flagg, 0, ((size_t)nwg + 8) * sizeof(ghk::u64), c->stream));
-        HIPCHK(c, hipMemsetAsync(r.xccg, 0, ((size_t)nwg + 8) * sizeof(ghk::u64), c->stream));
-        HIPCHK(c, hipMemsetAsync(r.xslabg, 0, 2 * (size_t)RES_CLUSTERS * E * 2 * sizeof(ghk::u32x4), c->stream));
-        HIPCHK(c, hipMemsetAsync(r.clsg, 0, 2 * 64 * 4 * sizeof(ghk::u32x4), c->stream));
-        HIPCHK(c, hipMemsetAsync(r.scalg, 0, 2 * (size_t)LR_MAXWG * 2 * sizeof(ghk::u32x4), c->stream));
-        HIPCHK(c, hipMemsetAsync(r.ppg, 0, 2 * (size_t)LR_MAXWG * 2 * sizeof(ghk::u32x4), c->stream));
-        r.tag = r.tagE = r.ltag = 0;
-        r.dirty = false;
-    }
-    HIPCHK(c, hipMemsetAsync(r.abort_w, 0, 4 * sizeof(unsigned), c->stream));
+    TRY(xg_prepare(c, r.xg, true, (uint64_t)steps + 2, (uint64_t)K + 2));
     // the momenta: one pinned staging buffer, one copy (the caller's array is pageable)
     if ((size_t)K * M > r.h_stage_n) {
         if (r.h_stage) HIPCHK(c, hipHostFree(r.h_stage));
@@ -210,10 +204,10 @@ static int chain_run_lonres(gh_ctx *c, gh_ctx *st, int K, const int *L, const do
     a.scalg = r.scalg;
     a.ppg = r.ppg;
     a.xccg = r.xccg;
-    a.tag0 = r.tag;
-    a.tagE0 = r.tagE;
-    a.ltag = r.ltag + 1u;
-    a.abort_w = r.abort_w;
+    a.tag0 = r.xg.tag;
+    a.tagE0 = r.xg.tagE;
+    a.ltag = r.xg.ltag + 1u;
+    a.abort_w = r.xg.abort_w;
     a.dbg = r.dbg;
     lonres_fn_t f = lonres_fn(h.rw);
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(f), r.lds));
@@ -222,27 +216,24 @@ static int chain_run_lonres(gh_ctx *c, gh_ctx *st, int K, const int *L, const do
     hipLaunchKernelGGL(f, dim3((unsigned)nwg), dim3(LR_THREADS), r.lds, c->stream, a);
     HIPCHK(c, hipGetLastError());
     if (c->prof) HIPCHK(c, hipEventRecord(r.ev1, c->stream));
-    unsigned h_sync[4] = {0, 0, 0, 0};
     int h_run[4] = {0, 0, 0, 0};
     double h_u[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(h_sync, r.abort_w, sizeof h_sync, hipMemcpyDeviceToHost, c->stream));
+    TRY(xg_read(c, r.xg));
     HIPCHK(c, hipMemcpyAsync(h_run, r.n_run, sizeof h_run, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_u, r.ucur, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(accepted, r.accepted, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(out5s, r.out5s, (size_t)K * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    r.ltag += 1u;
-    if (h_sync[0] != 0u) {
-        r.aborts += 1;
-        r.dirty = true;
-        const bool for_good = r.aborts >= 3;
+    r.xg.ltag += 1u;
+    if (r.xg.seen[0] != 0u) {
+        const bool for_good = xg_give_up(r.xg, 3);
         if (for_good) r.state = -1;
         fprintf(stderr, "libgravhmc: the persistent harmonic pass timed out waiting for its workgroups (%d of 3); %s with one "
-                        "launch per phase\n", r.aborts, for_good ? "continuing for good" : "running this batch");
+                        "launch per phase\n", r.xg.aborts, for_good ? "continuing for good" : "running this batch");
         return GH_RESIDENT_ABORTED;
     }
-    r.tag += (unsigned)h_run[1];
-    r.tagE += (unsigned)h_run[2];
+    r.xg.tag += (unsigned)h_run[1];
+    r.xg.tagE += (unsigned)h_run[2];
     r.launches += 1;
     r.evals += h_run[1];
     r.trajectories += h_run[0];

@@ -33,8 +33,7 @@ struct LonSymHost {
     const double *rhat_of = nullptr; // the residual vector R^ was last computed from (by the fused epilogue)
     double *post_slab = nullptr, *post_dsum = nullptr;
     unsigned long long *csum = nullptr;
-    unsigned *epi_abort = nullptr;
-    unsigned epi_tag = 0;
+    ExchangeGuard epi;  // the one-launch epilogue (off at the first give-up)
     // the harmonic pass as one persistent launch per batch of trajectories (lonres.hip.h, host_lonres.h)
     struct Res {
         int state = 0;  // 0 not planned yet, 1 usable, -1 not applicable
@@ -42,16 +41,13 @@ struct LonSymHost {
         ghk::d2 *slab = nullptr, *mhat = nullptr, *rhatg = nullptr;
         ghk::u64 *flagg = nullptr, *xccg = nullptr;
         ghk::u32x4 *xslabg = nullptr, *clsg = nullptr, *scalg = nullptr, *ppg = nullptr;
-        unsigned *abort_w = nullptr;
-        unsigned tag = 0, tagE = 0, ltag = 0;
-        bool dirty = false;
+        ExchangeGuard xg;  // off for good after three give-ups
         int Kcap = 0;
         int *L = nullptr, *accepted = nullptr, *n_run = nullptr;
         double *p0s = nullptr, *us = nullptr, *out5s = nullptr, *xacc = nullptr, *ucur = nullptr, *xpub = nullptr;
         double *h_stage = nullptr;
         size_t h_stage_n = 0;
         int64_t launches = 0, evals = 0, trajectories = 0;
-        int aborts = 0;
         long long *dbg = nullptr;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
     } res;
@@ -314,7 +310,7 @@ static int lonsym_build(gh_ctx *c)
         h.fused = env_int("GRAVHMC_LONSYM_FUSED", 0) != 0;
         if (h.fused) {
             TRY(dalloc(c, &h.csum, 2 * (size_t)na));
-            TRY(dalloc(c, &h.epi_abort, 4));
+            TRY(xg_alloc(c, h.epi, {{h.csum, sizeof(unsigned long long) * 2 * (size_t)na}}));
         }
     } else {
         (void)hipGetLastError();
@@ -531,12 +527,11 @@ static int lonsym_post_now(gh_ctx *c)
 // after a synchronisation point: did a fused epilogue give up waiting for its class blocks?
 static int lonsym_epilogue_check(gh_ctx *c)
 {
-    if (!lonsym_harmonic(c) || !c->ls->fused || !c->ls->epi_abort) return GH_OK;
-    unsigned w[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(w, c->ls->epi_abort, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    if (!lonsym_harmonic(c) || !c->ls->fused || !c->ls->epi.abort_w) return GH_OK;
+    TRY(xg_read(c, c->ls->epi));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (w[0] == 0u) return GH_OK;
-    HIPCHK(c, hipMemsetAsync(c->ls->epi_abort, 0, sizeof w, c->stream));
+    if (c->ls->epi.seen[0] == 0u) return GH_OK;
+    xg_give_up(c->ls->epi, 1);
     c->ls->fused = false;  // (the three-launch epilogue from here on)
     c->ls->rhat_of = nullptr;
     return fail(c, GH_ERR_HIP, "shift-invariant store: the one-launch epilogue timed out waiting for its class blocks (GPU shared?); "

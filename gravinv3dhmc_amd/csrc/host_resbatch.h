@@ -53,7 +53,10 @@ static bool resbatch_plan(gh_ctx *c, int C)
         dalloc(c, &b.dclg, (size_t)RES_CLUSTERS * ldx * 16) != GH_OK || dalloc(c, &b.xccg, (size_t)r.nwg + 8) != GH_OK ||
         dalloc(c, &b.xpub, 2 * 16 * M) != GH_OK || dalloc(c, &b.xs, 16 * M) != GH_OK || dalloc(c, &b.ps, 16 * M) != GH_OK ||
         dalloc(c, &b.pst, 16 * M) != GH_OK || dalloc(c, &b.cst, 16 * RB_CST) != GH_OK || dalloc(c, &b.n_io, 128) != GH_OK ||
-        dalloc(c, &r.abort_w, 4) != GH_OK)
+        xg_alloc(c, b.xg, {{b.flagg, ((size_t)r.nwg + 8) * sizeof(ghk::u64)},
+                           {b.xslabg, 2 * (size_t)RES_CLUSTERS * ldx * 16 * sizeof(ghk::u32x4)},
+                           {b.dclg, (size_t)RES_CLUSTERS * ldx * 16 * sizeof(ghk::u32x4)},
+                           {b.xccg, ((size_t)r.nwg + 8) * sizeof(ghk::u64)}}) != GH_OK)
         return false;
     if (env_int("GRAVHMC_RESIDENT_TIMING", 0) && dalloc(c, &b.dbg, 32) != GH_OK) return false;
     if (!r.ev0 && (hipEventCreate(&r.ev0) != hipSuccess || hipEventCreate(&r.ev1) != hipSuccess)) return false;
@@ -95,7 +98,6 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
     gh_ctx::Resident::LockStep &b = r.ls;
     const size_t M = (size_t)c->M;
     const int C = b.C, Tout = carry ? T + 1 : T;
-    const size_t ldx = (size_t)c->ld + RB_XROWS;
     HIPCHK(c, hipSetDevice(c->device));
     const int K = C * T, Kout = C * std::max(Tout, 1);
     if (std::max(K, Kout) > b.cap) {
@@ -113,15 +115,7 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
     int64_t steps = 0;
     for (int k = 0; k < K; ++k) steps += L[k] + 1;
     steps += 64 * 17;  // (what is in flight; generous)
-    if (b.dirty || (uint64_t)b.tag + (uint64_t)steps + 2 > 0xf0000000ull || b.ltag > 0xf0000000u) {
-        HIPCHK(c, hipMemsetAsync(b.flagg, 0, ((size_t)r.nwg + 8) * sizeof(ghk::u64), c->stream));
-        HIPCHK(c, hipMemsetAsync(b.xslabg, 0, 2 * (size_t)RES_CLUSTERS * ldx * 16 * sizeof(ghk::u32x4), c->stream));
-        HIPCHK(c, hipMemsetAsync(b.dclg, 0, (size_t)RES_CLUSTERS * ldx * 16 * sizeof(ghk::u32x4), c->stream));
-        HIPCHK(c, hipMemsetAsync(b.xccg, 0, ((size_t)r.nwg + 8) * sizeof(ghk::u64), c->stream));
-        b.tag = b.ltag = 0;
-        b.dirty = false;
-    }
-    HIPCHK(c, hipMemsetAsync(r.abort_w, 0, 4 * sizeof(unsigned), c->stream));
+    TRY(xg_prepare(c, b.xg, true, (uint64_t)steps + 2));
     // Momenta: device rows chain-major (ch * T + t), like the lists.  Rows inside a block of gh_pinned_alloc go
     // straight from where they lie, adjacent ones in one copy (a sampler drawing into a ring of such rows: one
     // or two copies per chain); the others are gathered into ONE pinned staging buffer first (a few host threads:
@@ -225,9 +219,9 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
     a.dclg = b.dclg;
     a.xccg = b.xccg;
     a.xpub = b.xpub;
-    a.tag0 = b.tag;
-    a.ltag = b.ltag + 1u;
-    a.abort_w = r.abort_w;
+    a.tag0 = b.xg.tag;
+    a.ltag = b.xg.ltag + 1u;
+    a.abort_w = b.xg.abort_w;
     a.dbg = b.dbg;
     resbatch_fn_t f = resbatch_for(b.ks, b.nt, c->wv.on);
     // (gh_set_data may have added or removed the fixed part of the data term since the batch was planned)
@@ -239,21 +233,19 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
     hipLaunchKernelGGL(f, dim3(r.nwg), dim3(RB_THREADS), b.lds, c->stream, a);
     HIPCHK(c, hipGetLastError());
     if (c->prof) HIPCHK(c, hipEventRecord(r.ev1, c->stream));
-    unsigned h_sync[4] = {0, 0, 0, 0};
     int h_n[128];
-    HIPCHK(c, hipMemcpyAsync(h_sync, r.abort_w, sizeof h_sync, hipMemcpyDeviceToHost, c->stream));
+    TRY(xg_read(c, b.xg));
     HIPCHK(c, hipMemcpyAsync(h_n, b.n_io, sizeof h_n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.ltag += 1u;
-    if (h_sync[0] != 0u) {
-        b.aborts += 1;
-        b.dirty = true;
+    b.xg.ltag += 1u;
+    if (b.xg.seen[0] != 0u) {
+        xg_give_up(b.xg, 1);
         fprintf(stderr, "libgravhmc: resident batch kernel timed out waiting for its workgroups; the chains take turns in "
                         "the resident chain kernel from here on\n");
         return GH_RESIDENT_ABORTED;
     }
     const int lock_steps = h_n[32];
-    b.tag += (unsigned)lock_steps;
+    b.xg.tag += (unsigned)lock_steps;
     b.launches += 1;
     b.lock_steps += lock_steps;
     // results

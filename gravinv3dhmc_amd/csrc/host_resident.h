@@ -171,7 +171,12 @@ static int resident_launch(gh_ctx *c, const ResLaunch &q, int *accepted, double 
         TRY(dalloc(c, &r.xscalg, (size_t)RES_CLUSTERS * 8));
         TRY(dalloc(c, &r.xccg, (size_t)r.nwg + 8));
         TRY(dalloc(c, &r.xpub, 2 * M));
-        TRY(dalloc(c, &r.abort_w, 4));
+        TRY(xg_alloc(c, r.xg, {{r.slabg, (size_t)(r.nwg + 8) * (size_t)c->ld * 2 * sizeof(ghk::u64)},
+                               {r.xslabg, 2 * (size_t)RES_CLUSTERS * (size_t)c->ld * 2 * sizeof(ghk::u64)},
+                               {r.dclg, (size_t)RES_CLUSTERS * (size_t)c->ld * 2 * sizeof(ghk::u64)},
+                               {r.scalg, (size_t)(r.nwg + 8) * 8 * sizeof(ghk::u64)},
+                               {r.xscalg, (size_t)RES_CLUSTERS * 8 * sizeof(ghk::u64)},
+                               {r.xccg, ((size_t)r.nwg + 8) * sizeof(ghk::u64)}}));
         TRY(dalloc(c, &r.n_run, 4));
         if (env_int("GRAVHMC_RESIDENT_TIMING", 0)) TRY(dalloc(c, &r.dbg, 32));
         if (!r.ev0) {
@@ -196,20 +201,7 @@ static int resident_launch(gh_ctx *c, const ResLaunch &q, int *accepted, double 
     }
     int64_t steps = 0;
     for (int k = 0; k < K; ++k) steps += q.L[k];
-    if (r.granules_dirty || (uint64_t)r.tag + (uint64_t)steps + (uint64_t)q.C + 2 > 0xf0000000ull ||
-        (uint64_t)r.tagE + (uint64_t)K + (uint64_t)q.C + 2 > 0xf0000000ull) {
-        // 32-bit tags about to wrap, or an aborted launch left granules carrying tags this launch
-        // would use again: start the count again on zeroed granules
-        HIPCHK(c, hipMemsetAsync(r.slabg, 0, (size_t)(r.nwg + 8) * (size_t)c->ld * 2 * sizeof(ghk::u64), c->stream));
-        HIPCHK(c, hipMemsetAsync(r.xslabg, 0, 2 * (size_t)RES_CLUSTERS * (size_t)c->ld * 2 * sizeof(ghk::u64), c->stream));
-        HIPCHK(c, hipMemsetAsync(r.dclg, 0, (size_t)RES_CLUSTERS * (size_t)c->ld * 2 * sizeof(ghk::u64), c->stream));
-        HIPCHK(c, hipMemsetAsync(r.scalg, 0, (size_t)(r.nwg + 8) * 8 * sizeof(ghk::u64), c->stream));
-        HIPCHK(c, hipMemsetAsync(r.xscalg, 0, (size_t)RES_CLUSTERS * 8 * sizeof(ghk::u64), c->stream));
-        HIPCHK(c, hipMemsetAsync(r.xccg, 0, ((size_t)r.nwg + 8) * sizeof(ghk::u64), c->stream));
-        r.tag = r.tagE = 0;
-        r.granules_dirty = false;
-    }
-    HIPCHK(c, hipMemsetAsync(r.abort_w, 0, 4 * sizeof(unsigned), c->stream));
+    TRY(xg_prepare(c, r.xg, true, (uint64_t)steps + (uint64_t)q.C + 2, (uint64_t)K + (uint64_t)q.C + 2));
     // (K = 0: only the potential and gradient at the chains' current samples are evaluated)
     if (K > 0) {
         HIPCHK(c, hipMemcpyAsync(r.p0s, q.p0s, (size_t)K * M * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -268,9 +260,9 @@ static int resident_launch(gh_ctx *c, const ResLaunch &q, int *accepted, double 
     a.xscalg = r.xscalg;
     a.xccg = r.xccg;
     a.xpub = r.xpub;
-    a.tag0 = r.tag;
-    a.tagE0 = r.tagE;
-    a.abort_w = r.abort_w;
+    a.tag0 = r.xg.tag;
+    a.tagE0 = r.xg.tagE;
+    a.abort_w = r.xg.abort_w;
     a.dbg = r.dbg;
     if (c->prof) HIPCHK(c, hipEventRecord(r.ev0, c->stream));
     // A plain launch: the grid was checked against the occupancy query in resident_plan (one
@@ -279,31 +271,28 @@ static int resident_launch(gh_ctx *c, const ResLaunch &q, int *accepted, double 
     hipLaunchKernelGGL(resident_for(r.rc, r.ct), dim3(r.nwg), dim3(RES_THREADS), lds, c->stream, a);
     HIPCHK(c, hipGetLastError());
     if (c->prof) HIPCHK(c, hipEventRecord(r.ev1, c->stream));
-    unsigned h_sync[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(h_sync, r.abort_w, sizeof h_sync, hipMemcpyDeviceToHost, c->stream));
+    TRY(xg_read(c, r.xg));
     HIPCHK(c, hipMemcpyAsync(h_run, r.n_run, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (K > 0) {
         HIPCHK(c, hipMemcpyAsync(accepted, r.accepted, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(out5s, r.out5s, (size_t)K * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (h_sync[0] != 0u) {
+    if (r.xg.seen[0] != 0u) {
         // A workgroup waited 2 s for the others: they were not all resident (another process holding
         // compute units of this device).  Nothing of the chain state was written; the caller's batch
         // is run on the sweep-per-launch path.  A transient stall does not downgrade the context:
         // the next batch tries the resident kernel again (on cleared exchange buffers); after three
         // aborted launches the context stays on the sweep path.
-        r.aborts += 1;
-        r.granules_dirty = true;
-        const bool for_good = r.aborts >= 3;
+        const bool for_good = xg_give_up(r.xg, 3);
         if (for_good) r.state = -1;
         fprintf(stderr, "libgravhmc: resident chain kernel timed out waiting for its workgroups (%d of 3); "
-                        "%s on the sweep-per-launch path\n", r.aborts,
+                        "%s on the sweep-per-launch path\n", r.xg.aborts,
                 for_good ? "continuing for good" : "running this batch");
         return GH_RESIDENT_ABORTED;
     }
-    r.tag += (unsigned)h_run[1];
-    r.tagE += (unsigned)h_run[2];
+    r.xg.tag += (unsigned)h_run[1];
+    r.xg.tagE += (unsigned)h_run[2];
     r.launches += 1;
     r.evals += h_run[1];
     if (c->prof) {

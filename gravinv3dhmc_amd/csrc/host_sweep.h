@@ -486,8 +486,8 @@ static bool team_plan(gh_ctx *c)
         return false;
     }
     const size_t ng = (size_t)n_teams * TS_MAXQ * TS_RING * 2;
-    if (dalloc(c, &t.gran, ng) != GH_OK || dalloc(c, &t.abort_w, 4) != GH_OK) return false;
-    t.tag = 0;
+    if (dalloc(c, &t.gran, ng) != GH_OK || xg_alloc(c, t.xg, {{t.gran, ng * sizeof(u64)}}) != GH_OK) return false;
+    t.xg.tag = 0;
     t.state = 1;
     return true;
 }
@@ -495,11 +495,7 @@ static bool team_plan(gh_ctx *c)
 static int launch_team(gh_ctx *c, const SweepArgs &full)
 {
     gh_ctx::Team &t = c->tm;
-    if ((uint64_t)t.tag + (uint64_t)t.cols_per_team + 2 > 0xf0000000ull) {
-        // 32-bit tags about to wrap: start again on zeroed granules
-        HIPCHK(c, hipMemsetAsync(t.gran, 0, (size_t)8 * t.tpx * TS_MAXQ * TS_RING * 2 * sizeof(u64), c->stream));
-        t.tag = 0;
-    }
+    TRY(xg_prepare(c, t.xg, false, (uint64_t)t.cols_per_team + 2));
     TeamArgs a{};
     a.s = full;
     a.s.G = c->G;
@@ -513,8 +509,8 @@ static int launch_team(gh_ctx *c, const SweepArgs &full)
     a.cols_per_team = t.cols_per_team;
     a.n_pp = c->n_teams;
     a.gran = t.gran;
-    a.tag0 = t.tag;
-    a.abort_w = t.abort_w;
+    a.tag0 = t.xg.tag;
+    a.abort_w = t.xg.abort_w;
     bool timed = c->prof && c->ev_used + 2 <= c->ev.size() && (c->prof_seen++ % c->prof_stride) == 0;
     if (timed) HIPCHK(c, hipEventRecord(c->ev[c->ev_used], c->stream));
     hipLaunchKernelGGL(team_kernel_for(t.threads, t.ept2, t.depth, t.lag), dim3(t.grid), dim3(t.threads), t.lds, c->stream, a);
@@ -525,8 +521,8 @@ static int launch_team(gh_ctx *c, const SweepArgs &full)
     }
     if (c->prof) c->prof_launches += 1;
     HIPCHK(c, hipGetLastError());
-    t.tag += (unsigned)t.cols_per_team + 1u;
-    t.inflight = true;
+    t.xg.tag += (unsigned)t.cols_per_team + 1u;
+    t.xg.inflight = true;
     t.launches += 1;
     return GH_OK;
 }
@@ -539,13 +535,9 @@ static int team_mark_failed(gh_ctx *c, const char *whose)
 {
     gh_ctx::Team &t = c->tm;
     if (t.state == -1 || !t.gran) return GH_OK;  // (teams not in use on this rank)
-    t.aborts += 1;
-    const bool for_good = t.aborts >= 3;
+    const bool for_good = xg_give_up(t.xg, 3);
     fprintf(stderr, "libgravhmc: %s team sweep timed out waiting for its workgroups (%d of 3); repeating %s in row panels\n",
-            whose, t.aborts, for_good ? "this and everything after it" : "the step");
-    HIPCHK(c, hipMemsetAsync(t.abort_w, 0, 4 * sizeof(unsigned), c->stream));
-    HIPCHK(c, hipMemsetAsync(t.gran, 0, (size_t)8 * t.tpx * TS_MAXQ * TS_RING * 2 * sizeof(u64), c->stream));
-    t.tag = 0;
+            whose, t.xg.aborts, for_good ? "this and everything after it" : "the step");
     t.state = for_good ? -1 : 2;  // 2: skip the teams until the repeated work is done (team_resume)
     return GH_OK;
 }
@@ -557,13 +549,12 @@ static int team_failed(gh_ctx *c, bool *failed)
 {
     gh_ctx::Team &t = c->tm;
     *failed = false;
-    if (!t.inflight) return GH_OK;
-    t.inflight = false;
-    unsigned w[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(w, t.abort_w, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    if (!t.xg.inflight) return GH_OK;
+    t.xg.inflight = false;
+    TRY(xg_read(c, t.xg));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    t.late_polls = w[1];  // columns whose parts some member had to wait for (all launches so far)
-    if (w[0] == 0u) return GH_OK;
+    t.late_polls = t.xg.seen[1];  // columns whose parts some member had to wait for (all launches so far)
+    if (t.xg.seen[0] == 0u) return GH_OK;
     *failed = true;
     return team_mark_failed(c, "this rank's");
 }

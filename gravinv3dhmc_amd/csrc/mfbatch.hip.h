@@ -536,7 +536,7 @@ mfb_forward_kernel(MfGeom g, MfbFwdArgs a, const double *__restrict__ cellc, MfS
 // same bits; member 0 stores the results) and feeds the new positions to the forward MFMAs on the
 // tile it still holds in its other staging buffer.  One evaluation per entry and step for all chains.
 //
-// Exchange: the data is the flag (resident.hip.h): a double travels as two tagged 8-byte granules,
+// Exchange: the data is the flag (exchange.hip.h): a double travels as two tagged 8-byte granules,
 // written through, read with agent-scope loads; no counters, no fences; correct under any placement.
 // A ring of four slots per team (a member is never more than one tile ahead of another).  Every wait
 // is bounded (2 s): on a time-out the abort word is raised, every workgroup leaves, later launches
@@ -584,7 +584,7 @@ mfb_fused_kernel(MfGeom g, BatchAdjArgs a, MfbFusArgs f, const double *__restric
     const int nb = nrb - rb0 < MFB_RC_FUS ? nrb - rb0 : MFB_RC_FUS;
     const int64_t t0 = (int64_t)cr * f.tiles_per_range;
     const int ntl = (int)((ntiles - t0 < f.tiles_per_range) ? ntiles - t0 : f.tiles_per_range);
-    if (tid == 0) abort_s = (__hip_atomic_load(f.abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) ? 1 : 0;
+    if (tid == 0) abort_s = gave_up_before(f.abort_w) ? 1 : 0;
     {
         MfbObsFetch<KIND, TL::ROWS> of;
         of.fetch(g, (int64_t)rb0 * 64, tid);
@@ -703,18 +703,8 @@ mfb_fused_kernel(MfGeom g, BatchAdjArgs a, MfbFusArgs f, const double *__restric
                         // (a member lags by more than an iteration) poll until its part is there
                         unsigned spins = 0;
                         long long tstart = 0;
-                        while (ok && !ld_gran(gran_of(it - 1, m) + 2 * gv, gtag, val)) {
-                            __builtin_amdgcn_s_sleep(1);
-                            if ((++spins & 63u) == 0) {
-                                const long long now = wall_clock64();
-                                if (tstart == 0) tstart = now;
-                                if (__hip_atomic_load(f.abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-                                    now - tstart > RES_TIMEOUT_TICKS) {
-                                    __hip_atomic_store(f.abort_w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                    ok = false;
-                                }
-                            }
-                        }
+                        while (ok && !ld_gran(gran_of(it - 1, m) + 2 * gv, gtag, val))
+                            if (spin_gave_up(spins, tstart, f.abort_w)) ok = false;
                     }
                     sum += val;
                 }
@@ -845,7 +835,7 @@ mf_team_kernel(MfGeom g, SweepArgs a, MftArgs f, const double *__restrict__ wm, 
     const int nb = nrb - rb0 < MFB_RC_FUS ? nrb - rb0 : MFB_RC_FUS;
     const int64_t t0 = (int64_t)cr * f.tiles_per_range;
     const int ntl = (int)((ntiles - t0 < f.tiles_per_range) ? ntiles - t0 : f.tiles_per_range);
-    if (tid == 0) abort_s = (__hip_atomic_load(f.abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) ? 1 : 0;
+    if (tid == 0) abort_s = gave_up_before(f.abort_w) ? 1 : 0;
     {
         MfbObsFetch<KIND, TL::ROWS> of;
         of.fetch(g, (int64_t)rb0 * 64, tid);
@@ -954,18 +944,8 @@ mf_team_kernel(MfGeom g, SweepArgs a, MftArgs f, const double *__restrict__ wm, 
                     if (!gran_value(ga[q], gb[q], gtag, val)) {
                         unsigned spins = 0;
                         long long tstart = 0;
-                        while (ok && !ld_gran(gran_of(it - 1, m) + 2 * gcol, gtag, val)) {
-                            __builtin_amdgcn_s_sleep(1);
-                            if ((++spins & 63u) == 0) {
-                                const long long now = wall_clock64();
-                                if (tstart == 0) tstart = now;
-                                if (__hip_atomic_load(f.abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-                                    now - tstart > RES_TIMEOUT_TICKS) {
-                                    __hip_atomic_store(f.abort_w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                    ok = false;
-                                }
-                            }
-                        }
+                        while (ok && !ld_gran(gran_of(it - 1, m) + 2 * gcol, gtag, val))
+                            if (spin_gave_up(spins, tstart, f.abort_w)) ok = false;
                     }
                     sum += val;
                 }

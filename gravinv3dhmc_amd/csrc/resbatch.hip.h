@@ -34,7 +34,7 @@
 // chain has nothing left to start and no decision is pending; trajectories in flight are saved (position,
 // momentum, step count) and continue in the next launch.
 //
-// Every wait is bounded (resident.hip.h's res_poll); on a time-out every workgroup leaves without writing
+// Every wait is bounded (exchange.hip.h: spin_gave_up); on a time-out every workgroup leaves without writing
 // chain state and the host continues on the chains-take-turns kernel.
 #pragma once
 #include "resident.hip.h"
@@ -182,15 +182,7 @@ __device__ __forceinline__ bool rb_poll(unsigned *abort_w, __amdgpu_buffer_rsrc_
                 }
             }
         if (__all(ok)) return true;
-        __builtin_amdgcn_s_sleep(1);
-        if ((++spins & 63u) == 0) {
-            const long long now = wall_clock64();
-            if (t0 == 0) t0 = now;
-            if (__hip_atomic_load(abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || now - t0 > RES_TIMEOUT_TICKS) {
-                __hip_atomic_store(abort_w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return false;
-            }
-        }
+        if (spin_gave_up(spins, t0, abort_w)) return false;
     }
 }
 

@@ -45,7 +45,7 @@
 // every workgroup leaves and the host falls back to the sweep path.  The grid (one workgroup per
 // CU by the LDS request) is checked against the occupancy query on the host.
 #pragma once
-#include "kernels.hip.h"
+#include "exchange.hip.h"
 
 namespace ghk {
 
@@ -55,9 +55,6 @@ constexpr int RES_CLUSTERS = 8;                       // logical clusters: workg
 constexpr int RES_CHUNKS = 32;                        // at most: row chunks of d, one per owning member of a cluster
 constexpr int RES_MAX_WG = 256;                       // <= 32 members per cluster (two per reducing thread)
 constexpr int RES_REDBUF = 16 * 33;                   // LDS transpose buffer of the cluster reduction
-constexpr long long RES_TIMEOUT_TICKS = 200000000LL;  // 2 s of the 100 MHz wall clock, per wait
-
-using u64 = unsigned long long;
 
 struct ResArgs {
     const double *G;   // Aw: the dots pass (adjoint)
@@ -135,65 +132,13 @@ __device__ __forceinline__ void st_wt(double *p, double v)
                        __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// one double as two tagged granules at g[0], g[1]
-__device__ __forceinline__ void st_gran(u64 *g, unsigned tag, double v)
-{
-    const u64 b = (u64)__double_as_longlong(v);
-    __hip_atomic_store(g, ((u64)tag << 32) | (b & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(g + 1, ((u64)tag << 32) | (b >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the same with plain stores: the line stays in the XCD's L2, where sc1 loads of the same XCD's
+// st_gran (exchange.hip.h) with plain stores: the line stays in the XCD's L2, where sc1 loads of the same XCD's
 // CUs find it (NOT visible to other XCDs until it is written back)
 __device__ __forceinline__ void st_gran_l2(u64 *g, unsigned tag, double v)
 {
     const u64 b = (u64)__double_as_longlong(v);
     __hip_atomic_store(g, ((u64)tag << 32) | (b & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     __hip_atomic_store(g + 1, ((u64)tag << 32) | (b >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// the two halves of ld_gran: the loads (issue early), and what they brought (look late -- the wait
-// for the loads sits where the words are first used)
-__device__ __forceinline__ void ld_gran_issue(u64 *g, u64 &a, u64 &b)
-{
-    a = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    b = __hip_atomic_load(g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ bool gran_value(u64 a, u64 b, unsigned tag, double &v)
-{
-    v = __longlong_as_double((long long)((a & 0xffffffffull) | (b << 32)));
-    return (unsigned)(a >> 32) == tag && (unsigned)(b >> 32) == tag;
-}
-
-__device__ __forceinline__ bool ld_gran(u64 *g, unsigned tag, double &v)
-{
-    u64 a, b;
-    ld_gran_issue(g, a, b);
-    return gran_value(a, b, tag, v);
-}
-
-// Every lane of the wave re-reads its granules (try_load: true when all of them carry the tag)
-// until the whole wave has them.  false: timed out or another workgroup raised the abort word.
-template <typename F>
-__device__ __forceinline__ bool res_poll(unsigned *abort_w, F &&try_load)
-{
-    unsigned spins = 0;
-    long long t0 = 0;
-    for (;;) {
-        const bool ok = try_load();
-        if (__all(ok)) return true;
-        __builtin_amdgcn_s_sleep(1);
-        if ((++spins & 63u) == 0) {
-            const long long now = wall_clock64();
-            if (t0 == 0) t0 = now;
-            if (__hip_atomic_load(abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-                now - t0 > RES_TIMEOUT_TICKS) {
-                __hip_atomic_store(abort_w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return false;
-            }
-        }
-    }
 }
 
 // Workgroup-wide sum (RES_WAVES waves), fixed order, result valid in every thread

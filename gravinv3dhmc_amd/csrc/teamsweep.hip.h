@@ -11,7 +11,7 @@
 // adds the Q parts in the same order, applies the same update and adds its rows times the new x_j to
 // its part of the forward partial.  One read of G again.
 //
-// The exchange is the resident chain kernel's (resident.hip.h): the data is the flag -- a double
+// The exchange is the resident chain kernel's (exchange.hip.h): the data is the flag -- a double
 // travels as two 8-byte granules {tag, 32 bits}, each written by one write-through store and read
 // with sc1 loads; no counters, no fences; correct under any placement of the workgroups.  What
 // keeps the stream of G going across the hand-off of every column:
@@ -89,7 +89,7 @@ __global__ void __launch_bounds__(TS_THREADS) teamsweep_kernel(TeamArgs a)
     double *tot_s = part + 2 * TS_MAXWAVES;
     int *abort_s = reinterpret_cast<int *>(tot_s + 2);
 
-    if (tid == 0) *abort_s = (__hip_atomic_load(a.abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) ? 1 : 0;
+    if (tid == 0) *abort_s = gave_up_before(a.abort_w) ? 1 : 0;
     {
         const d2 *r2 = reinterpret_cast<const d2 *>(s.r + row0);
         d2 *rs2 = reinterpret_cast<d2 *>(r_s);

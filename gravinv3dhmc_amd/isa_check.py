@@ -28,7 +28,7 @@ import tempfile
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 STAMP = os.path.join(_HERE, "libgravhmc.isa.json")
-HEADERS = ("kernels.hip.h", "batch.hip.h", "resident.hip.h", "mfbatch.hip.h", "batchteam.hip.h")
+HEADERS = ("kernels.hip.h", "batch.hip.h", "exchange.hip.h", "resident.hip.h", "mfbatch.hip.h", "batchteam.hip.h")
 SYMBOL = "_ZN3ghk17batch_team_kernelENS_12BatchAdjArgsENS_6BtArgsE"
 _VMEM = re.compile(r"(global|buffer|flat|scratch)_(load|store|atomic)")
 
