@@ -121,6 +121,9 @@ PROTOTYPES = {
     "gh_format_row_fixed8": (C.c_int64, [_dp, _i64, C.c_char_p, _i64]),
     "gh_measure_stream_read": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "gh_profile_enable": (C.c_int, [_ctx, C.c_int]),
+    "gh_fold_info": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(C.c_double),
+                               C.POINTER(C.c_double)]),
+    "gh_fold_detect": (C.c_int, [_i64, _dp, _dp, _dp, _i64, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gh_profile_read": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(_i64),
                                   C.POINTER(_i64)]),
 }

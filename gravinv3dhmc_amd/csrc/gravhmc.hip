@@ -13,12 +13,17 @@
 #include "lonsymh.hip.h"
 #include "lonres.hip.h"
 #include "lonsymw.hip.h"
+#include "fold.hip.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
+#include <cfloat>
+#include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -41,6 +46,7 @@ static_assert(COMP_POTENTIAL == GH_COMP_POTENTIAL && COMP_GEOID == GH_COMP_GEOID
 
 #include "host_ctx.h"
 #include "host_sweep.h"
+#include "host_fold.h"
 #include "host_lonsym.h"
 #include "host_comm.h"
 #include "host_wavelet.h"
@@ -163,6 +169,9 @@ int gh_set_obs(gh_ctx *c, const double *a, const double *b, const double *cc)
     for (int64_t i = 1; i < n && c->obs_h_uniform; ++i) c->obs_h_uniform = cc[i] == cc[0];
     c->obs_h0 = cc[0];
     c->have_obs = true;
+    c->fd.detected = 0;
+    c->fd.reason = GH_FOLD_UNDECIDED;
+    c->G_gen += 1;
     return GH_OK;
 }
 
@@ -183,6 +192,9 @@ static int set_cells(gh_ctx *c, const double *bounds6, int kind, int comp, doubl
     c->comp = comp;
     c->ratio = ratio;
     c->have_cells = true;
+    c->fd.detected = 0;
+    c->fd.reason = GH_FOLD_UNDECIDED;
+    c->G_gen += 1;
     return GH_OK;
 }
 
@@ -596,9 +608,10 @@ int gh_build_G(gh_ctx *c)
     }
     c->have_G = true;
     c->weighted = false;
+    c->G_gen += 1;
     c->chain_ready = false;
     c->bt.ready = false;
-    return GH_OK;
+    return fold_detect(c);  // (gz prisms on a grid symmetric under both mirrors: host_fold.h)
 }
 
 int gh_kernel_stats(const gh_ctx *c, int64_t *warn_cells, int64_t *leaves)
@@ -640,6 +653,9 @@ int gh_upload_G(gh_ctx *c, const double *A, int64_t ld, int fortran_order)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_G = true;
     c->weighted = false;
+    c->G_gen += 1;
+    c->fd.detected = -1;  // (entries of the caller's: no pairing is assumed)
+    c->fd.reason = GH_FOLD_NOT_GZ;
     c->chain_ready = false;
     c->bt.ready = false;
     return GH_OK;
@@ -737,6 +753,7 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
     for (auto &v : w) v = v * v;  // diag(WmSquare) = ADiag * ADiag (potential.py:253)
     TRY(h2d(c, c->wm2, w.data(), (size_t)c->M));
     c->weighted = true;
+    c->G_gen += 1;
     c->chain_ready = false;
     c->bt.ready = false;
     return GH_OK;
@@ -891,7 +908,10 @@ int gh_forward(gh_ctx *c, const double *mw, double *dpre)
     a.mode = SW_FWD;
     a.x_in = c->tmpM;
     a.slab = c->slab;
-    TRY(launch_sweep(c, a));
+    {
+        FoldExact exact(c);
+        TRY(launch_sweep(c, a));
+    }
     reduce_slab(c, nullptr, c->tmpN);
     HIPCHK(c, hipGetLastError());
     if (!shard_rows(c)) TRY(comm_allreduce(c, c->tmpN, c->ld));  // (row blocks: the local rows are complete)
@@ -910,7 +930,10 @@ int gh_adjoint(gh_ctx *c, const double *r, double *g)
     a.mode = SW_ADJ | SW_GOUT;
     a.r = c->tmpN;
     a.g_out = c->tmpM;
-    TRY(launch_sweep(c, a));
+    {
+        FoldExact exact(c);
+        TRY(launch_sweep(c, a));
+    }
     TRY(d2h(c, g, c->tmpM, (size_t)c->M));
     for (int64_t j = 0; j < c->M; ++j) g[j] *= 0.5;  // the sweep writes 2*<G_j, r>
     return GH_OK;
@@ -2733,6 +2756,32 @@ int gh_matrix_free_stats(gh_ctx *c, int64_t *entries, int64_t *leaves, int64_t *
     if (leaves) *leaves = (int64_t)h.leaves;
     if (launches) *launches = c->mf_launches;
     return GH_OK;
+}
+
+int gh_fold_info(const gh_ctx *c, int *on, int *reason, int64_t *store_bytes, double *max_dev, double *build_ms)
+{
+    if (!c) return GH_ERR_ARG;
+    const gh_ctx::Fold &f = c->fd;
+    const bool live = f.valid && f.gen == c->G_gen;
+    if (on) *on = live ? 1 : 0;
+    if (reason) *reason = (f.detected == 1 && f.gen != c->G_gen && f.reason == GH_FOLD_ON) ? GH_FOLD_UNDECIDED : f.reason;
+    if (store_bytes) *store_bytes = f.S ? fold_store_bytes(c) : 0;
+    if (max_dev) *max_dev = f.max_dev;
+    if (build_ms) *build_ms = f.build_ms;
+    return GH_OK;
+}
+
+int gh_fold_detect(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
+                   int *obs_img, int *cell_orbit)
+{
+    if (N < 0 || M < 0 || !x || !y || !z || !bounds6 || !obs_img || !cell_orbit) return GH_ERR_ARG;
+    std::vector<int> oi, co;
+    const int rc = fold_detect_host(N, x, y, z, M, bounds6, oi, co);
+    if (rc == GH_FOLD_ON) {
+        std::copy(oi.begin(), oi.end(), obs_img);
+        std::copy(co.begin(), co.end(), cell_orbit);
+    }
+    return rc;
 }
 
 int gh_profile_read(gh_ctx *c, double *sweep_ms, int64_t *sweep_launches, int64_t *bytes_per_sweep)

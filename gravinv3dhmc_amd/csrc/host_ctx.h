@@ -300,6 +300,28 @@ struct gh_ctx {
     } rs;
     int64_t prof_res_evals = 0;
 
+    // the stored kernel folded over the grid's two mirrors (host_fold.h, fold.hip.h): a quarter of G per sweep
+    uint64_t G_gen = 0;  // bumped whenever the dense store (or what it is built from) changes
+    struct Fold {
+        int detected = 0;     // 1: the geometry pairs up (gh_build_G of gz prisms), -1: it does not, 0: not looked
+        int reason = GH_FOLD_UNDECIDED;
+        uint64_t gen = ~0ull; // G_gen the decision below was made for
+        bool valid = false;   // S holds the folded store of G_gen and the sweeps use it
+        int nF = 0, ldF = 0;
+        int64_t n_orb = 0;
+        std::vector<int> obs_img, cell_orbit;  // host tables (nF x 4, n_orb x 4)
+        int *obs_img_d = nullptr, *cell_orbit_d = nullptr;
+        double *S = nullptr;
+        double *zeros = nullptr;  // M zeros: what the sweep reads for an input its mode does not use
+        unsigned long long *dev_bits = nullptr;
+        int ept2 = 0, grid = 0;
+        int64_t orb_per_team = 0;
+        size_t lds = 0;
+        double max_dev = 0.0, build_ms = 0.0;
+        int64_t launches = 0;
+        bool exact = false;   // gh_forward / gh_adjoint in progress: the operator itself, on the dense store
+    } fd;
+
     // page-locked host memory handed to the caller (gh_pinned_alloc): momentum rows drawn into it go to the device
     // without a gather on the host
     struct Pinned {

@@ -1,0 +1,371 @@
+// libgravhmc host side: the stored kernel folded over the grid's two mirrors (fold.hip.h).  Detection of the
+// pairing at gh_build_G, eligibility, the lazy build of the folded store, its launches.  Included once by
+// gravhmc.hip, after host_sweep.h.
+#pragma once
+
+// ------------------------------------------------------------------------------------ detection (host)
+
+namespace fold_detail {
+
+// Sorted clusters of the values of one axis: values closer than tol to their neighbour share a cluster.
+struct Axis {
+    std::vector<double> lo, hi;
+    double tol = 0.0;
+    void build(std::vector<double> v, double t)
+    {
+        tol = t;
+        std::sort(v.begin(), v.end());
+        for (double x : v) {
+            if (lo.empty() || x - hi.back() > tol) {
+                lo.push_back(x);
+                hi.push_back(x);
+            } else {
+                hi.back() = x;
+            }
+        }
+    }
+    // cluster within tol of x, or -1
+    int find(double x) const
+    {
+        const size_t k = (size_t)(std::upper_bound(lo.begin(), lo.end(), x + tol) - lo.begin());
+        if (k == 0) return -1;
+        return (x - hi[k - 1] <= tol) ? (int)(k - 1) : -1;
+    }
+    // cluster of the mirror image 2c - x of each cluster (-1: none); false if some cluster is wider than the
+    // tolerance allows or the map is not an involution
+    bool mirror(double c, std::vector<int> &m) const
+    {
+        m.assign(lo.size(), -1);
+        for (size_t q = 0; q < lo.size(); ++q) {
+            if (hi[q] - lo[q] > 2.0 * tol) return false;
+            m[q] = find(2.0 * c - 0.5 * (lo[q] + hi[q]));
+        }
+        for (size_t q = 0; q < lo.size(); ++q)
+            if (m[q] >= 0 && m[(size_t)m[q]] != (int)q) return false;
+        return true;
+    }
+};
+
+typedef std::array<int64_t, 6> Key;
+
+struct Index {
+    std::vector<std::pair<Key, int>> v;
+    bool build()
+    {
+        std::sort(v.begin(), v.end());
+        for (size_t i = 1; i < v.size(); ++i)
+            if (v[i].first == v[i - 1].first) return false;  // two identical points or cells
+        return true;
+    }
+    int find(const Key &k) const
+    {
+        auto it = std::lower_bound(v.begin(), v.end(), std::make_pair(k, INT_MIN));
+        return (it != v.end() && it->first == k) ? it->second : -1;
+    }
+};
+
+inline int64_t bits(double x)
+{
+    int64_t b;
+    memcpy(&b, &x, sizeof b);
+    return b;
+}
+
+// orbits {i, sx i, sy i, sx sy i} of a free Z2 x Z2 action, ordered by their smallest index (the first entry)
+inline int orbits(const std::vector<int> &sx, const std::vector<int> &sy, std::vector<int> &out)
+{
+    const size_t n = sx.size();
+    std::vector<char> seen(n, 0);
+    out.clear();
+    out.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (seen[i]) continue;
+        const int a = (int)i, b = sx[i], cc = sy[i], d = sy[(size_t)b];
+        if (sx[(size_t)cc] != d) return GH_FOLD_CELLS;  // the mirrors do not commute (cannot happen for true mirrors)
+        if (a == b || a == cc || a == d || b == cc || b == d || cc == d) return GH_FOLD_FIXED;
+        for (int v : {a, b, cc, d}) {
+            if (seen[(size_t)v]) return GH_FOLD_FIXED;
+            seen[(size_t)v] = 1;
+            out.push_back(v);
+        }
+    }
+    return GH_FOLD_ON;
+}
+
+}  // namespace fold_detail
+
+// The pairing: centre from the cells' extent, images within a few ulps of the coordinates' magnitude, heights
+// (observations) and tops / bottoms (cells) bit for bit, no fixed points.  GH_FOLD_ON and the two tables, or
+// the reason.
+static int fold_detect_host(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *b6,
+                            std::vector<int> &obs_img, std::vector<int> &cell_orbit)
+{
+    using namespace fold_detail;
+    if (N < 4 || M < 4 || N % 4 || M % 4) return N % 4 ? GH_FOLD_OBS : GH_FOLD_CELLS;
+    double xmin = b6[0], xmax = b6[1], ymin = b6[2], ymax = b6[3];
+    for (int64_t j = 0; j < M; ++j) {
+        const double *b = b6 + 6 * j;
+        xmin = std::min(xmin, std::min(b[0], b[1]));
+        xmax = std::max(xmax, std::max(b[0], b[1]));
+        ymin = std::min(ymin, std::min(b[2], b[3]));
+        ymax = std::max(ymax, std::max(b[2], b[3]));
+    }
+    double mag = std::max(std::max(std::fabs(xmin), std::fabs(xmax)), std::max(std::fabs(ymin), std::fabs(ymax)));
+    for (int64_t i = 0; i < N; ++i) mag = std::max(mag, std::max(std::fabs(x[i]), std::fabs(y[i])));
+    if (!std::isfinite(mag)) return GH_FOLD_OBS;
+    // a few ulps of the coordinates' magnitude: rounding of a mirrored grid, nothing a field would notice
+    const double tol = 8.0 * DBL_EPSILON * mag;
+    const double cx = 0.5 * (xmin + xmax), cy = 0.5 * (ymin + ymax);
+
+    // observations
+    std::vector<int> osx((size_t)N), osy((size_t)N);
+    {
+        Axis ax, ay;
+        ax.build(std::vector<double>(x, x + N), tol);
+        ay.build(std::vector<double>(y, y + N), tol);
+        std::vector<int> mx, my;
+        if (!ax.mirror(cx, mx) || !ay.mirror(cy, my)) return GH_FOLD_OBS;
+        std::vector<int> qx((size_t)N), qy((size_t)N);
+        Index idx;
+        idx.v.reserve((size_t)N);
+        for (int64_t i = 0; i < N; ++i) {
+            qx[(size_t)i] = ax.find(x[i]);
+            qy[(size_t)i] = ay.find(y[i]);
+            idx.v.push_back({Key{qx[(size_t)i], qy[(size_t)i], bits(z[i]), 0, 0, 0}, (int)i});
+        }
+        if (!idx.build()) return GH_FOLD_OBS;
+        for (int64_t i = 0; i < N; ++i) {
+            const int a = qx[(size_t)i], b = qy[(size_t)i];
+            if (mx[(size_t)a] < 0 || my[(size_t)b] < 0) return GH_FOLD_OBS;
+            osx[(size_t)i] = idx.find(Key{mx[(size_t)a], b, bits(z[i]), 0, 0, 0});
+            osy[(size_t)i] = idx.find(Key{a, my[(size_t)b], bits(z[i]), 0, 0, 0});
+            if (osx[(size_t)i] < 0 || osy[(size_t)i] < 0) return GH_FOLD_OBS;
+        }
+    }
+    // cells: [x1, x2] -> [2c - x2, 2c - x1]
+    std::vector<int> csx((size_t)M), csy((size_t)M);
+    {
+        Axis ax, ay;
+        std::vector<double> vx, vy;
+        vx.reserve(2 * (size_t)M);
+        vy.reserve(2 * (size_t)M);
+        for (int64_t j = 0; j < M; ++j) {
+            vx.push_back(b6[6 * j]);
+            vx.push_back(b6[6 * j + 1]);
+            vy.push_back(b6[6 * j + 2]);
+            vy.push_back(b6[6 * j + 3]);
+        }
+        ax.build(std::move(vx), tol);
+        ay.build(std::move(vy), tol);
+        std::vector<int> mx, my;
+        if (!ax.mirror(cx, mx) || !ay.mirror(cy, my)) return GH_FOLD_CELLS;
+        std::vector<Key> keys((size_t)M);
+        Index idx;
+        idx.v.reserve((size_t)M);
+        for (int64_t j = 0; j < M; ++j) {
+            const double *b = b6 + 6 * j;
+            keys[(size_t)j] = Key{ax.find(b[0]), ax.find(b[1]), ay.find(b[2]), ay.find(b[3]), bits(b[4]), bits(b[5])};
+            idx.v.push_back({keys[(size_t)j], (int)j});
+        }
+        if (!idx.build()) return GH_FOLD_CELLS;
+        for (int64_t j = 0; j < M; ++j) {
+            const Key &k = keys[(size_t)j];
+            if (mx[(size_t)k[0]] < 0 || mx[(size_t)k[1]] < 0 || my[(size_t)k[2]] < 0 || my[(size_t)k[3]] < 0)
+                return GH_FOLD_CELLS;
+            csx[(size_t)j] = idx.find(Key{mx[(size_t)k[1]], mx[(size_t)k[0]], k[2], k[3], k[4], k[5]});
+            csy[(size_t)j] = idx.find(Key{k[0], k[1], my[(size_t)k[3]], my[(size_t)k[2]], k[4], k[5]});
+            if (csx[(size_t)j] < 0 || csy[(size_t)j] < 0) return GH_FOLD_CELLS;
+        }
+    }
+    // (the mirror maps of clusters are involutions, so are these)
+    int rc = orbits(osx, osy, obs_img);
+    if (rc != GH_FOLD_ON) return rc == GH_FOLD_CELLS ? GH_FOLD_OBS : rc;
+    return orbits(csx, csy, cell_orbit);
+}
+
+// gh_build_G of a dense store: look for the pairing (gz prisms only)
+static int fold_detect(gh_ctx *c)
+{
+    gh_ctx::Fold &f = c->fd;
+    f.detected = -1;
+    f.valid = false;
+    f.gen = ~0ull;
+    f.reason = GH_FOLD_NOT_GZ;
+    if (c->cell_kind != GH_CELL_PRISM || c->joint || c->mf || !c->G) return GH_OK;
+    std::vector<double> ox((size_t)c->N), oy((size_t)c->N), oz((size_t)c->N), b6((size_t)c->M * 6);
+    TRY(d2h(c, ox.data(), c->obs[0], ox.size()));
+    TRY(d2h(c, oy.data(), c->obs[1], oy.size()));
+    TRY(d2h(c, oz.data(), c->obs[2], oz.size()));
+    TRY(d2h(c, b6.data(), c->bounds, b6.size()));
+    f.reason = fold_detect_host(c->N, ox.data(), oy.data(), oz.data(), c->M, b6.data(), f.obs_img, f.cell_orbit);
+    if (f.reason != GH_FOLD_ON) return GH_OK;
+    f.nF = (int)(c->N / 4);
+    f.ldF = (f.nF + 15) / 16 * 16;
+    f.n_orb = c->M / 4;
+    TRY(dalloc(c, &f.obs_img_d, (size_t)c->N, false));
+    TRY(dalloc(c, &f.cell_orbit_d, (size_t)c->M, false));
+    HIPCHK(c, hipMemcpyAsync(f.obs_img_d, f.obs_img.data(), sizeof(int) * f.obs_img.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(f.cell_orbit_d, f.cell_orbit.data(), sizeof(int) * f.cell_orbit.size(), hipMemcpyHostToDevice,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (the host tables stay, but may be reassigned by a later build)
+    f.detected = 1;
+    f.reason = GH_FOLD_UNDECIDED;
+    return GH_OK;
+}
+
+// ----------------------------------------------------------------------------------- store and launches
+
+constexpr int FOLD_MAX_EPT2 = 6;        // 12288 folded rows: registers without spills (fold_sweep_kernel)
+constexpr double FOLD_MAX_DEV = 1e-7;   // sanity bound of the build: catches a wrong pairing, not rounding
+
+typedef void (*fold_fn)(SweepArgs, FoldArgs);
+
+static fold_fn fold_kernel_for(int ept2)
+{
+    switch (ept2) {
+    case 1: return fold_sweep_kernel<1>;
+    case 2: return fold_sweep_kernel<2>;
+    case 3: return fold_sweep_kernel<3>;
+    case 4: return fold_sweep_kernel<4>;
+    case 5: return fold_sweep_kernel<5>;
+    case 6: return fold_sweep_kernel<6>;
+    }
+    return nullptr;
+}
+
+static int64_t fold_store_bytes(const gh_ctx *c)
+{
+    return c->fd.n_orb * 4 * (int64_t)c->fd.ldF * (int64_t)sizeof(double);
+}
+
+static FoldArgs fold_args(const gh_ctx *c)
+{
+    const gh_ctx::Fold &f = c->fd;
+    FoldArgs a{};
+    a.S = f.S;
+    a.obs_img = f.obs_img_d;
+    a.cell_orbit = f.cell_orbit_d;
+    a.nF = f.nF;
+    a.ldF = f.ldF;
+    a.n_orb = f.n_orb;
+    a.orb_per_team = f.orb_per_team;
+    a.n_pp = c->n_teams;
+    a.N = c->N;
+    return a;
+}
+
+// Build the folded store of the current dense one (stream-ordered, synchronises once to read the deviation).
+static int fold_build(gh_ctx *c)
+{
+    gh_ctx::Fold &f = c->fd;
+    const auto t0 = std::chrono::steady_clock::now();
+    TRY(dalloc(c, &f.S, (size_t)(fold_store_bytes(c) / (int64_t)sizeof(double)), false));
+    TRY(dalloc(c, &f.dev_bits, 1, false));
+    TRY(dalloc(c, &f.zeros, (size_t)c->M));
+    HIPCHK(c, hipMemsetAsync(f.dev_bits, 0, sizeof(unsigned long long), c->stream));
+    fold_build_kernel<<<dim3((unsigned)f.n_orb), dim3(256), 0, c->stream>>>(c->G, c->ld, fold_args(c), f.S, f.dev_bits);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long bits = 0;
+    HIPCHK(c, hipMemcpyAsync(&bits, f.dev_bits, sizeof bits, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(&f.max_dev, &bits, sizeof bits);
+    f.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return GH_OK;
+}
+
+// Does this sweep (one whole panel, single chain) read the folded store?  Decides once per dense store, builds
+// the folded store when it qualifies.
+static int fold_use(gh_ctx *c, bool *use)
+{
+    gh_ctx::Fold &f = c->fd;
+    *use = false;
+    if (f.detected != 1 || f.exact) return GH_OK;
+    if (c->sh.kind != 0 || c->wv.on || c->joint || c->mf || c->n_panels != 1) {
+        f.reason = GH_FOLD_PATH;
+        return GH_OK;
+    }
+    if (f.gen == c->G_gen) {
+        *use = f.valid;
+        return GH_OK;
+    }
+    f.gen = c->G_gen;
+    f.valid = false;
+    if (env_int("GRAVHMC_FOLD", 1) == 0) {
+        f.reason = GH_FOLD_SWITCHED_OFF;
+        return GH_OK;
+    }
+    const int64_t min_mb = env_int("GRAVHMC_FOLD_MIN_MB", 512);
+    if (c->ld * c->M * (int64_t)sizeof(double) <= (min_mb << 20)) {
+        f.reason = GH_FOLD_SMALL;
+        return GH_OK;
+    }
+    // (the resident chain kernel would run the chain on the dense store: chain and stateless calls must agree)
+    f.ept2 = (2 * f.ldF + 1023) / 1024;
+    if (f.ept2 > FOLD_MAX_EPT2 || (c->ld <= 1024 && env_int("GRAVHMC_RESIDENT", 1) != 0)) {
+        f.reason = GH_FOLD_PATH;
+        return GH_OK;
+    }
+    {
+        size_t free_b = 0, total_b = 0;
+        (void)hipMemGetInfo(&free_b, &total_b);
+        if (!f.S && (int64_t)free_b < fold_store_bytes(c) + ((int64_t)256 << 20)) {
+            f.reason = GH_FOLD_NOMEM;
+            return GH_OK;
+        }
+    }
+    fold_fn fn = fold_kernel_for(f.ept2);
+    f.lds = ((size_t)4 * f.ldF + 2 * (4 * 16 + 8)) * sizeof(double);
+    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(fn), f.lds));
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(fn), 1024, f.lds) != hipSuccess ||
+        occ < 1) {
+        (void)hipGetLastError();
+        occ = 1;
+    }
+    // (never more workgroups than the dense sweep's slab rows and pp partials)
+    int grid = (int)std::min<int64_t>(std::min<int64_t>((int64_t)c->cus * occ, c->grid), f.n_orb);
+    f.orb_per_team = (f.n_orb + grid - 1) / grid;
+    f.grid = (int)((f.n_orb + f.orb_per_team - 1) / f.orb_per_team);
+    TRY(fold_build(c));
+    if (!(f.max_dev <= FOLD_MAX_DEV)) {
+        f.reason = GH_FOLD_DEVIATION;
+        return GH_OK;
+    }
+    f.valid = true;
+    f.reason = GH_FOLD_ON;
+    *use = true;
+    return GH_OK;
+}
+
+// gh_forward and gh_adjoint apply the operator itself: the dense store, entry for entry (callers probe columns
+// with unit vectors and compare them with the prism formula at 1e-11 of the largest entry; an orbit's mean differs
+// from its entries by the formula's own cancellation noise, up to a few 1e-9 of a column's largest entry)
+struct FoldExact {
+    gh_ctx *c;
+    explicit FoldExact(gh_ctx *c_) : c(c_) { c->fd.exact = true; }
+    ~FoldExact() { c->fd.exact = false; }
+};
+
+static int launch_fold(gh_ctx *c, SweepArgs &a)
+{
+    gh_ctx::Fold &f = c->fd;
+    a.ld = c->ld;
+    a.M = c->M;
+    a.row0 = 0;
+    a.rows = c->ld;
+    bool timed = c->prof && c->ev_used + 2 <= c->ev.size() && (c->prof_seen++ % c->prof_stride) == 0;
+    if (timed) HIPCHK(c, hipEventRecord(c->ev[c->ev_used], c->stream));
+    SweepArgs b = a;  // (the kernel loads every per-cell input unconditionally)
+    for (const double **v : {&b.x_in, &b.p_in, &b.low, &b.high, &b.greg, &b.pn_in})
+        if (!*v) *v = f.zeros;
+    hipLaunchKernelGGL(fold_kernel_for(f.ept2), dim3(f.grid), dim3(1024), f.lds, c->stream, b, fold_args(c));
+    if (timed) {
+        HIPCHK(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
+        c->ev_bytes[c->ev_used / 2] = fold_store_bytes(c);
+        c->ev_used += 2;
+    }
+    if (c->prof) c->prof_launches += 1;
+    f.launches += 1;
+    HIPCHK(c, hipGetLastError());
+    return GH_OK;
+}

@@ -315,6 +315,8 @@ static int lonsym_epilogue_check(gh_ctx *c);
 static int lonsym_classes(const gh_ctx *c);
 static int lonsym_grid(const gh_ctx *c);
 static int64_t lonsym_table_bytes(const gh_ctx *c);
+static int fold_use(gh_ctx *c, bool *use);  // host_fold.h
+static int launch_fold(gh_ctx *c, SweepArgs &a);
 
 // Partition of the matrix-free passes.  N <= 16384: the fused pass (one workgroup per column at a
 // time, columns dealt round-robin); else the two-pass form (one wave per cell for the adjoint,
@@ -627,6 +629,12 @@ static int launch_sweep(gh_ctx *c, SweepArgs &a)
         if ((a.mode & SW_FWD) && c->TW > 1 && c->dsum) {
             a.dsum = c->dsum;  // sums of the slab rows: the epilogue then needs one launch
             c->dsum_live = true;
+        }
+        bool fold = false;
+        TRY(fold_use(c, &fold));  // (builds the folded store at the first sweep after the store changed)
+        if (fold) {
+            if (a.mode & SW_FWD) c->slab_live = c->fd.grid;
+            return launch_fold(c, a);
         }
         return launch_sweep_one(c, a);
     }

@@ -197,6 +197,19 @@ class Engine(object):
         return {"on": bool(on.value), "form": {0: None, 1: "registers", 2: "streamed"}[on.value], "n_freq": nf.value,
                 "table_bytes": tb.value, "workgroups": wg.value}
 
+    #: reasons of fold_info (GH_FOLD_* of include/gravhmc.h)
+    FOLD_REASONS = ("on", "undecided", "switched off", "not gz prisms", "observations not mirror-symmetric",
+                    "cells not mirror-symmetric", "fixed point", "small", "path", "no memory", "deviation")
+
+    def fold_info(self):
+        """The stored kernel folded over the grid's two mirrors (csrc/fold.hip.h): on (the single-chain sweeps
+        read it), reason (FOLD_REASONS), bytes of the folded store, largest deviation of an entry from its orbit's
+        mean relative to the orbit's largest entry, milliseconds of its build."""
+        on, rs, sb, md, bm = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_double(0), C.c_double(0)
+        self._chk(self._lib.gh_fold_info(self._h, C.byref(on), C.byref(rs), C.byref(sb), C.byref(md), C.byref(bm)))
+        return {"on": bool(on.value), "reason": self.FOLD_REASONS[rs.value], "store_bytes": sb.value,
+                "max_dev": md.value, "build_ms": bm.value}
+
     def matrix_free_stats(self):
         """Entries / GLQ leaves evaluated and launches of the fused matrix-free pass since
         profile_enable(True)."""

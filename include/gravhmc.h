@@ -40,7 +40,9 @@
  *     off / also where the register form applies), GRAVHMC_LONSYM_W, GRAVHMC_LW_WAVES_PER_CU, GRAVHMC_LW_FWD, GRAVHMC_LW_MIRROR=0 (one row of T^ per cell row),
  *     GRAVHMC_DWT_LDS / _MAX (one-launch wavelet transform);
  *   arithmetic of an entry (within the path's stated 1e-10, ~1e-14 measured): GRAVHMC_MF_EXACT -- the
- *     DEFAULT of gh_set_matrix_free_exact only; that call overrides it;
+ *     DEFAULT of gh_set_matrix_free_exact only; that call overrides it; GRAVHMC_FOLD=0 / GRAVHMC_FOLD_MIN_MB (the
+ *     sampler's sweeps of a mirror-symmetric gz prism grid on the dense store / the size from which they fold,
+ *     gh_fold_info; ~1e-11 measured);
  *   diagnostics that BREAK the results (timing only): GRAVHMC_LW_BREAK (phases of lonsymw_sweep_kernel off),
  *     GRAVHMC_BT_BREAK; GRAVHMC_LW_LDS_PAD (fewer workgroups per CU, results intact);
  *   tuning without any effect on results: GRAVHMC_PF, _NT, _TW, _TW8, _WG_PER_CU, _MIN_COLS,
@@ -558,6 +560,42 @@ int gh_rng_set_threads(gh_rng *rng, int threads);
 int gh_host_cores(void);
 int gh_rng_draw_trajectories(gh_rng *rng, int K, int Lmin, int Lmax, int64_t M, double sigma, int *L,
                              double *p0s /* K x M */, double *us /* K */);
+
+/* ---- the stored kernel folded over the grid's mirrors ------------------------------------ */
+
+/* A gz prism store whose cells and observations are symmetric under x -> 2cx - x and y -> 2cy - y (c: the
+ * centre of the cells' extent) holds only a quarter of distinct entries: G(s i, s j) = G(i, j) for each
+ * mirror s.  gh_build_G looks for the pairing; the first single-chain sweep after the store changed builds the
+ * folded store (the mean of each orbit of four entries, a quarter of the bytes) beside the dense one, which
+ * stays untouched, and the sampler's single-chain sweeps (gh_chain_*, gh_leapfrog, gh_misfit_and_grad) read it from
+ * then on: results equal the dense sweep's to ~1e-11.  gh_forward and gh_adjoint (the operator itself, entry for
+ * entry) and the batches stay on the dense store.  Used when the dense store is larger
+ * than GRAVHMC_FOLD_MIN_MB (default 512) MiB, the sweep is one panel of at most 12288 folded rows, the chain
+ * is not sharded, joint, wavelet-compressed or matrix-free and would not run on the resident chain kernel, the
+ * free memory holds the store and no entry deviates from its orbit's mean by more than 1e-7 of its orbit's
+ * largest entry; GRAVHMC_FOLD=0 switches it off.  reason: one of GH_FOLD_*. */
+enum {
+    GH_FOLD_ON = 0,
+    GH_FOLD_UNDECIDED = 1,     /* no sampler sweep since the store changed, or no dense prism store */
+    GH_FOLD_SWITCHED_OFF = 2,  /* GRAVHMC_FOLD=0 */
+    GH_FOLD_NOT_GZ = 3,        /* not a gz prism store built by gh_build_G (other kind or component, gh_upload_G) */
+    GH_FOLD_OBS = 4,           /* an observation without its mirror image (position or height) */
+    GH_FOLD_CELLS = 5,         /* a cell without its mirror image */
+    GH_FOLD_FIXED = 6,         /* an observation on a mirror line, or a cell that is its own image */
+    GH_FOLD_SMALL = 7,         /* dense store not larger than the threshold */
+    GH_FOLD_PATH = 8,          /* sharded, joint, wavelet, row panels, resident chain kernel, or too many rows */
+    GH_FOLD_NOMEM = 9,         /* not enough free device memory for the folded store */
+    GH_FOLD_DEVIATION = 10     /* an orbit's entries differ beyond the sanity bound: a wrong pairing */
+};
+/* on: the sweeps read the folded store; store_bytes, max_dev (largest |entry - orbit mean| / the orbit's
+ * largest entry) and build_ms of the last build. */
+int gh_fold_info(const gh_ctx *ctx, int *on, int *reason, int64_t *store_bytes, double *max_dev, double *build_ms);
+/* The pairing gh_build_G looks for, without a device: N observations (x, y, z), M cells (bounds6 as in
+ * gh_set_cells).  Returns one of GH_FOLD_* (GH_FOLD_ON: found).  obs_img (N ints: N/4 rows of the four images
+ * s_0 f, s_x f, s_y f, s_xy f of each fundamental observation f) and cell_orbit (M ints: M/4 rows of the four
+ * images of each orbit's first cell), both ordered by their first entry, are written when found. */
+int gh_fold_detect(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
+                   int *obs_img, int *cell_orbit);
 
 /* ---- measurement ----------------------------------------------------------------------- */
 
