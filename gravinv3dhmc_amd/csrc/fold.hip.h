@@ -29,11 +29,7 @@ struct FoldArgs {
     int64_t N;               // observations: slab rows N .. ld-1 are written as zeros
 };
 
-typedef const int __attribute__((address_space(4))) *kconst_iptr;
-__device__ __forceinline__ kconst_iptr as_kconst_i(const int *p)
-{
-    return (kconst_iptr)(unsigned long long)p;
-}
+typedef const d2 __attribute__((address_space(1))) *gconst_d2ptr;
 
 // S from the weighted dense store: one workgroup per orbit, the four entries of each orbit averaged in a
 // fixed order.  dev_bits: max over the store of max_g |entry - mean| / (largest |mean| of the orbit's
@@ -94,22 +90,53 @@ __device__ __forceinline__ double readlane_d(double v, int l)
 template <int EPT2>
 struct FoldCol {
     d2 v[EPT2];
-    int j[4];  // the orbit's cells (uniform)
+    int j;        // cell h = (lane >> 3) & 3 of the orbit
+    int jn;       // the same cell of the orbit this buffer takes next, two blocks on (requested behind this block)
+    double cv;    // per-cell inputs, lane-distributed: lane 8h + q holds input q of cell h (FOLD_IN_*)
 };
 
+// the per-cell inputs of an orbit, one per lane 8h + q (h < 4): requested with the orbit's block (their cell
+// indices one block earlier, all through the vector-memory counter), gathered into lane 8h by DPP after the dots
+// are known.  No scalar load in the loop: an s_load would share lgkmcnt with the LDS reads of r and put its
+// latency into every block's chain.
+constexpr int FOLD_SLOT = 16 * 16 + 8;  // doubles (16 waves x 4 rows x 4 dots, padded)
+
+enum { FOLD_IN_X = 0, FOLD_IN_P, FOLD_IN_GREG, FOLD_IN_HI, FOLD_IN_LO, FOLD_IN_PN, FOLD_IN_GACC, FOLD_IN_N };
+
+// v of the lane DPP control CTRL selects (0 where there is none)
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov(double v)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, false);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+
+// v of lane l + Q of the same row of 16 (row_shl Q; 0 past the row's end)
+template <int Q>
+__device__ __forceinline__ double dpp_from_up(double v)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x100 | Q, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x100 | Q, 0xf, 0xf, false);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+
 // One team of 16 waves per workgroup, one orbit block at a time (EPT2 double2 per thread: 2048 EPT2 rows
-// of S), one block in flight ahead (at C2: EPT2 = 5, 128 VGPRs, no scratch).  Every mode of sweep_kernel (SW_ADJ / UPD / FWD / PFIN / GOUT / GACC /
-// SPEC, dsum) over a whole panel; M-vectors in the caller's cell order, the slab row in the caller's
-// observation order.  Thread t holds double2 e = k 1024 + t of a block, i.e. S[o][e >> 1][2m], S[o][e >> 1][2m + 1]
-// with m = t & 1: its adjoint terms u[q] = S[2m] r[s_q f] + S[2m+1] r[s_(q^1) f] belong to dot[q ^ 2m], its
-// forward terms acc[q] = S[2m] x[q] + S[2m+1] x[q^1] to the observation s_(q^2m) f.
+// of S), one block in flight ahead together with its cells' inputs (at C2: EPT2 = 5).  Every mode of sweep_kernel
+// (SW_ADJ / UPD / FWD / PFIN / GOUT / GACC / SPEC, dsum) over a whole panel; M-vectors in the caller's cell order,
+// the slab row in the caller's observation order.  Thread t holds double2 e = k 1024 + t of a block, i.e.
+// S[o][e >> 1][2m], S[o][e >> 1][2m + 1] with m = t & 1: its adjoint terms u[q] = S[2m] r[s_q f] + S[2m+1] r[s_(q^1) f]
+// belong to dot[q ^ 2m], its forward terms acc[q] = S[2m] x[q] + S[2m+1] x[q^1] to the observation s_(q^2m) f.
+// The four cells' updates run side by side in lanes 0, 8, 16, 24 (the arithmetic of sweep_kernel per cell).
 template <int EPT2>
 __global__ void __launch_bounds__(1024) fold_sweep_kernel(SweepArgs a, FoldArgs f)
 {
-    constexpr int TT = 1024, NW = 16, SLOT = 4 * NW + 8;
+    constexpr int TT = 1024, NW = 16;
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    // LDS: [0, 4 ldF) r at the four images of each fundamental observation; 2 x SLOT ping-pong slots of the
-    // four dots of an orbit
+    // LDS: [0, 4 ldF) r at the four images of each fundamental observation; 2 x FOLD_SLOT ping-pong slots of
+    // the four dots of an orbit (one per row of 16 lanes of every wave)
     double *rF = smem;
     double *scratch = smem + 4 * f.ldF;
 
@@ -135,52 +162,65 @@ __global__ void __launch_bounds__(1024) fold_sweep_kernel(SweepArgs a, FoldArgs 
     double pp = 0.0;
 
     // (as in sweep_kernel: unconditional loads at 32-bit offsets from a uniform base, threads past the end
-    // re-read the last double2; per-cell scalars through the scalar cache, the orbit's cell indices requested
-    // one block ahead of the scalars they address)
-    unsigned coff[EPT2];
-#pragma unroll
-    for (int k = 0; k < EPT2; ++k) {
-        const int e = k * TT + tid;
-        coff[k] = (unsigned)(e < n2 ? e : n2 - 1) * (unsigned)sizeof(d2);
+    // re-read the last double2.  Only the last of a thread's double2 can lie past the end, (EPT2 - 1) 1024 < 2 ldF:
+    // the others share one offset from bases k 1024 double2 apart, and one LDS address serves all of them --
+    // registers kept out of the loop, which has none to spare)
+    unsigned voff = (unsigned)tid * (unsigned)sizeof(d2);
+    unsigned coff_last;
+    {
+        const int e = (EPT2 - 1) * TT + tid;
+        coff_last = (unsigned)(e < n2 ? e : n2 - 1) * (unsigned)sizeof(d2);
     }
+    const bool last_in = (EPT2 - 1) * TT + tid < n2;
     // (no null pointers here: launch_fold points the inputs a mode does not read at zeros, so every per-cell
-    // scalar load is unconditional)
-    const kconst_ptr kx = as_kconst(a.x_in), kp = as_kconst(a.p_in), klo = as_kconst(a.low), khi = as_kconst(a.high),
-                     kgr = as_kconst(a.greg), kpn = as_kconst(a.pn_in);
-    const kconst_iptr kco = as_kconst_i(f.cell_orbit);
+    // load is unconditional; lanes 32..63 repeat lanes 0..31)
+    const int hl = (lane >> 3) & 3, ql = lane & 7;
+    const double *in_base = ql == FOLD_IN_P      ? a.p_in
+                            : ql == FOLD_IN_GREG ? a.greg
+                            : ql == FOLD_IN_HI   ? a.high
+                            : ql == FOLD_IN_LO   ? a.low
+                            : ql == FOLD_IN_PN   ? a.pn_in
+                            : (ql == FOLD_IN_GACC && (mode & SW_GACC)) ? a.g_out
+                                                                       : a.x_in;
     const int lastc = cnt - 1;
     auto orb = [&](int i) -> int64_t { return ob + (i < lastc ? i : lastc); };
-    int jn[4];
-    auto load_idx = [&](int64_t o) {
+    // (a buffer requests the cell indices of its own next orbit, two blocks ahead: handing an index from one
+    // buffer to the other made the compiler copy it at the loop's back edge, behind a wait for every request
+    // in flight)
+    auto load_col = [&](FoldCol<EPT2> &c, int64_t o, int64_t o_after) {
+        // (the index first: a wait for it then never waits for this block)
+        const int jn = f.cell_orbit[4 * o_after + hl];
+        const unsigned long long col = (unsigned long long)(f.S + o * (int64_t)(4 * f.ldF));
 #pragma unroll
-        for (int h = 0; h < 4; ++h) jn[h] = kco[4 * o + h];
-    };
-    auto load_col = [&](FoldCol<EPT2> &c, int64_t o, int64_t o_next) {
-#pragma unroll
-        for (int h = 0; h < 4; ++h) c.j[h] = jn[h];
-        const char *col = reinterpret_cast<const char *>(f.S + o * (int64_t)(4 * f.ldF));
-#pragma unroll
-        for (int k = 0; k < EPT2; ++k) {
-            asm volatile("" : "+v"(coff[k]));
-            const d2 *src = reinterpret_cast<const d2 *>(col + coff[k]);
-            c.v[k] = __builtin_nontemporal_load(src);
+        for (int k = 0; k < EPT2 - 1; ++k) {
+            unsigned long long colk = col + (unsigned long long)k * TT * sizeof(d2);
+            asm volatile("" : "+s"(colk));
+            asm volatile("" : "+v"(voff));
+            c.v[k] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(colk + voff));
         }
-        load_idx(o_next);
+        asm volatile("" : "+v"(coff_last));
+        c.v[EPT2 - 1] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(col + coff_last));
+        // (the inputs' addresses wait for this orbit's indices, requested two blocks earlier: after this block's
+        // requests, not before them)
+        asm volatile("" : "+v"(c.jn)::"memory");
+        c.j = c.jn;
+        c.cv = in_base[c.j];
+        c.jn = jn;
     };
 
     auto process = [&](const FoldCol<EPT2> &cur, int it) {
+        // lane 8h: the inputs of cell h
+        double xl = cur.cv;
+        const double pl = dpp_from_up<FOLD_IN_P>(cur.cv);
         double xh[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) xh[h] = kx[cur.j[h]];
         if (mode & SW_ADJ) {
-            const d2 *rF2 = reinterpret_cast<const d2 *>(rF);
+            // (row i = (k 1024 + t) / 2 of r at rF + 32 i = rF + 32 (t / 2) + 16384 k)
+            const d2 *rF2 = reinterpret_cast<const d2 *>(rF) + 2 * (tid >> 1);
             double u0 = 0.0, u1 = 0.0, u2 = 0.0, u3 = 0.0;
 #pragma unroll
             for (int k = 0; k < EPT2; ++k) {
-                const int e = k * TT + tid;
-                if (e < n2) {
-                    const int i = e >> 1;
-                    const d2 ra = rF2[2 * i], rb = rF2[2 * i + 1];
+                if (k < EPT2 - 1 || last_in) {
+                    const d2 ra = rF2[k * TT], rb = rF2[k * TT + 1];
                     const d2 v = cur.v[k];
                     u0 += v.x * ra.x;
                     u0 += v.y * ra.y;
@@ -192,66 +232,78 @@ __global__ void __launch_bounds__(1024) fold_sweep_kernel(SweepArgs a, FoldArgs 
                     u3 += v.y * rb.x;
                 }
             }
-            // odd threads: u[q] is a term of dot[q ^ 2]
-            const bool odd = (tid & 1) != 0;
-            const double s0 = wave_sum_dpp(odd ? u2 : u0), s1 = wave_sum_dpp(odd ? u3 : u1),
-                         s2 = wave_sum_dpp(odd ? u0 : u2), s3 = wave_sum_dpp(odd ? u1 : u3);
-            d2 *slot = reinterpret_cast<d2 *>(scratch + (it & 1) * SLOT);
-            if (lane == 0) {
-                slot[2 * wave] = d2{s0, s1};
-                slot[2 * wave + 1] = d2{s2, s3};
-            }
+            // odd threads: u[q] is a term of dot[q ^ 2].  The four dots reduced together: lane pairs (quad_perm
+            // [1,0,3,2]) leave dots 0, 1 in even lanes and 2, 3 in odd ones, pairs of pairs ([2,3,0,1]) one dot per
+            // lane, dot 2 (l & 1) + ((l >> 1) & 1) of its quad; row_shr 4, 8 sum the quads of a row of 16 into
+            // lanes 16 r + 12 .. 15.  Every sum even lane / lower half first.
+            const bool odd = (tid & 1) != 0, hi2 = (tid & 2) != 0;
+            const double w0 = odd ? u2 : u0, w1 = odd ? u3 : u1, w2 = odd ? u0 : u2, w3 = odd ? u1 : u3;
+            const double a0 = (odd ? w2 : w0) + dpp_mov<0xb1>(odd ? w0 : w2);
+            const double a1 = (odd ? w3 : w1) + dpp_mov<0xb1>(odd ? w1 : w3);
+            double sq = (hi2 ? a1 : a0) + dpp_mov<0x4e>(hi2 ? a0 : a1);
+            sq = dpp_add<0x114, 0xf>(sq);
+            sq = dpp_add<0x118, 0xf>(sq);
+            // slot[w 16 + q 4 + r]: dot q of row r of wave w
+            double *slot = scratch + (it & 1) * FOLD_SLOT;
+            if ((lane & 15) >= 12) slot[wave * 16 + (((lane & 1) << 1) | ((lane >> 1) & 1)) * 4 + (lane >> 4)] = sq;
             __syncthreads();
-            // lane l of every wave takes the dot l & 3 of wave l >> 2; sums over the waves in fixed order: the four
-            // of a row of 16 lanes (row_shr 4, 8: lane 16 r + 12 + h), then the four rows (one LDS read per lane, not
-            // 64 values per thread)
-            double sv = reinterpret_cast<const double *>(slot)[lane];
+            // lane l of every wave takes the dot l & 3 of wave l >> 2 (its four rows, one 32-byte read); sums over
+            // the waves in fixed order: the four of a row of 16 lanes (row_shr 4, 8: lane 16 r + 12 + h), then the
+            // four rows
+            const d2 *sl = reinterpret_cast<const d2 *>(slot + (lane >> 2) * 16 + (lane & 3) * 4);
+            const d2 ra = sl[0], rb = sl[1];
+            double sv = (ra.x + ra.y) + (rb.x + rb.y);
             sv = dpp_add<0x114, 0xf>(sv);
             sv = dpp_add<0x118, 0xf>(sv);
             double t[4];
 #pragma unroll
             for (int h = 0; h < 4; ++h)
                 t[h] = ((readlane_d(sv, 12 + h) + readlane_d(sv, 28 + h)) + readlane_d(sv, 44 + h)) + readlane_d(sv, 60 + h);
-            // the orbit's four cells, one after the other (same arithmetic per cell as sweep_kernel); thread h < 4
-            // stores cell h
+            // cell h in lane 8h (same arithmetic per cell as sweep_kernel); wave 0 stores
+            const double th = hl == 0 ? t[0] : hl == 1 ? t[1] : hl == 2 ? t[2] : t[3];
+            const double g = 2.0 * th + dpp_from_up<FOLD_IN_GREG>(cur.cv);
+            double pv = 0.0, pf = 0.0;
+            if (mode & SW_PFIN) {
+                pf = pl - a.c_p * g;
+                pv = pf;
+            }
+            if (mode & SW_UPD) {
+                const double chi = dpp_from_up<FOLD_IN_HI>(cur.cv), clo = dpp_from_up<FOLD_IN_LO>(cur.cv);
+                const double psrc = (mode & SW_SPEC) ? dpp_from_up<FOLD_IN_PN>(cur.cv) : pl;
+                double pj = psrc - a.c_u * g;
+                double xj = xl + a.dt * pj;
+                if (xj > chi) {
+                    xj = chi;
+                    pj = -pj;
+                } else if (xj < clo) {
+                    xj = clo;
+                    pj = -pj;
+                }
+                pv = pj;
+                xl = xj;
+            }
+            if (mode & SW_PFIN) {
+                // (in the cells' order, as the dense sweep adds them)
 #pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                const int j = cur.j[h];
-                const double cp = kp[j];
-                const double g = 2.0 * t[h] + kgr[j];
-                double pv = 0.0;
-                if (mode & SW_PFIN) {
-                    const double pf = cp - a.c_p * g;
-                    pp += pf * pf;
-                    pv = pf;
+                for (int h = 0; h < 4; ++h) {
+                    const double q = readlane_d(pf, 8 * h);
+                    pp += q * q;
                 }
+            }
+            if (tid < 32 && ql == 0) {
+                const int j = cur.j;
+                if (mode & SW_GOUT) a.g_out[j] = (mode & SW_GACC) ? dpp_from_up<FOLD_IN_GACC>(cur.cv) + g : g;
                 if (mode & SW_UPD) {
-                    const double chi = khi[j], clo = klo[j];
-                    const double psrc = (mode & SW_SPEC) ? kpn[j] : cp;
-                    double pj = psrc - a.c_u * g;
-                    double xj = xh[h] + a.dt * pj;
-                    if (xj > chi) {
-                        xj = chi;
-                        pj = -pj;
-                    } else if (xj < clo) {
-                        xj = clo;
-                        pj = -pj;
-                    }
-                    pv = pj;
-                    xh[h] = xj;
-                }
-                if (tid == h) {
-                    if (mode & SW_GOUT) a.g_out[j] = (mode & SW_GACC) ? a.g_out[j] + g : g;
-                    if (mode & SW_UPD) {
-                        a.p_out[j] = pv;
-                        a.x_out[j] = xh[h];
-                    } else if ((mode & SW_PFIN) && !(mode & SW_SPEC)) {
-                        a.p_out[j] = pv;
-                    }
+                    a.p_out[j] = pv;
+                    a.x_out[j] = xl;
+                } else if ((mode & SW_PFIN) && !(mode & SW_SPEC)) {
+                    a.p_out[j] = pv;
                 }
             }
         }
         if (mode & SW_FWD) {
+#pragma unroll
+            for (int h = 0; h < 4; ++h) xh[h] = readlane_d(xl, 8 * h);
 #pragma unroll
             for (int k = 0; k < EPT2; ++k) {
                 const d2 v = cur.v[k];
@@ -265,18 +317,23 @@ __global__ void __launch_bounds__(1024) fold_sweep_kernel(SweepArgs a, FoldArgs 
                 acc[k][1].y += v.y * xh[2];
             }
         }
+        // (the block is consumed on every path the compiler sees: otherwise it waits for the block's requests
+        // before it reuses their registers at the top of the loop, i.e. before the next block is requested)
+#pragma unroll
+        for (int k = 0; k < EPT2; ++k) asm volatile("" ::"v"(cur.v[k]));
     };
 
     if (cnt > 0) {
         FoldCol<EPT2> b0, b1;
-        load_idx(orb(0));
-        load_col(b0, orb(0), orb(1));
+        b0.jn = f.cell_orbit[4 * orb(0) + hl];
+        b1.jn = f.cell_orbit[4 * orb(1) + hl];
+        load_col(b0, orb(0), orb(2));
         int i = 0;
         for (;;) {
-            load_col(b1, orb(i + 1), orb(i + 2));
+            load_col(b1, orb(i + 1), orb(i + 3));
             process(b0, i);
             if (++i >= cnt) break;
-            load_col(b0, orb(i + 1), orb(i + 2));
+            load_col(b0, orb(i + 1), orb(i + 3));
             process(b1, i);
             if (++i >= cnt) break;
         }

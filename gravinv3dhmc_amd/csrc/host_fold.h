@@ -215,7 +215,7 @@ static int fold_detect(gh_ctx *c)
 
 // ----------------------------------------------------------------------------------- store and launches
 
-constexpr int FOLD_MAX_EPT2 = 6;        // 12288 folded rows: registers without spills (fold_sweep_kernel)
+constexpr int FOLD_MAX_EPT2 = 5;        // 10240 folded rows: registers without spills (fold_sweep_kernel)
 constexpr double FOLD_MAX_DEV = 1e-7;   // sanity bound of the build: catches a wrong pairing, not rounding
 
 typedef void (*fold_fn)(SweepArgs, FoldArgs);
@@ -228,7 +228,6 @@ static fold_fn fold_kernel_for(int ept2)
     case 3: return fold_sweep_kernel<3>;
     case 4: return fold_sweep_kernel<4>;
     case 5: return fold_sweep_kernel<5>;
-    case 6: return fold_sweep_kernel<6>;
     }
     return nullptr;
 }
@@ -314,7 +313,7 @@ static int fold_use(gh_ctx *c, bool *use)
         }
     }
     fold_fn fn = fold_kernel_for(f.ept2);
-    f.lds = ((size_t)4 * f.ldF + 2 * (4 * 16 + 8)) * sizeof(double);
+    f.lds = ((size_t)4 * f.ldF + 2 * FOLD_SLOT) * sizeof(double);
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(fn), f.lds));
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(fn), 1024, f.lds) != hipSuccess ||

@@ -570,7 +570,7 @@ int gh_rng_draw_trajectories(gh_rng *rng, int K, int Lmin, int Lmax, int64_t M, 
  * stays untouched, and the sampler's single-chain sweeps (gh_chain_*, gh_leapfrog, gh_misfit_and_grad) read it from
  * then on: results equal the dense sweep's to ~1e-11.  gh_forward and gh_adjoint (the operator itself, entry for
  * entry) and the batches stay on the dense store.  Used when the dense store is larger
- * than GRAVHMC_FOLD_MIN_MB (default 512) MiB, the sweep is one panel of at most 12288 folded rows, the chain
+ * than GRAVHMC_FOLD_MIN_MB (default 512) MiB, the sweep is one panel of at most 10240 folded rows, the chain
  * is not sharded, joint, wavelet-compressed or matrix-free and would not run on the resident chain kernel, the
  * free memory holds the store and no entry deviates from its orbit's mean by more than 1e-7 of its orbit's
  * largest entry; GRAVHMC_FOLD=0 switches it off.  reason: one of GH_FOLD_*. */
