@@ -278,6 +278,21 @@ int gh_joint_layout(const gh_ctx *c, int *workgroups_per_block, int *epilogue_st
     return GH_OK;
 }
 
+int gh_sweep_layout(const gh_ctx *c, int *tw, int *ept2, int *pf, int *nt, int *n_teams, int64_t *cols_per_team,
+                    int *grid, int *n_panels)
+{
+    if (!c) return GH_ERR_ARG;
+    if (tw) *tw = c->TW;
+    if (ept2) *ept2 = c->EPT2;
+    if (pf) *pf = c->PF;
+    if (nt) *nt = c->NT ? 1 : 0;
+    if (n_teams) *n_teams = c->n_teams_sweep;
+    if (cols_per_team) *cols_per_team = c->cols_per_team;
+    if (grid) *grid = c->grid;
+    if (n_panels) *n_panels = c->n_panels;
+    return GH_OK;
+}
+
 // An observation-space vector of N doubles between the host and the device: as it is, or -- joint store --
 // its two halves to / from [gz: ld | tf: ld]
 static int h2d_obsvec(gh_ctx *c, double *dst, const double *src)

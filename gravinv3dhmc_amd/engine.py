@@ -250,6 +250,16 @@ class Engine(object):
         self._chk(self._lib.gh_joint_layout(self._h, C.byref(wg), C.byref(st)))
         return {"workgroups_per_block": wg.value, "epilogue_stages": st.value}
 
+    def sweep_layout(self):
+        """Instantiation and column partition of the dense fused sweep (gh_sweep_layout): team width tw, ept2
+        (double2 per thread), pf, nt, n_teams, cols_per_team, grid and n_panels."""
+        i = [C.c_int(0) for _ in range(7)]
+        cpt = C.c_int64(0)
+        self._chk(self._lib.gh_sweep_layout(self._h, C.byref(i[0]), C.byref(i[1]), C.byref(i[2]), C.byref(i[3]),
+                                            C.byref(i[4]), C.byref(cpt), C.byref(i[5]), C.byref(i[6])))
+        return {"tw": i[0].value, "ept2": i[1].value, "pf": i[2].value, "nt": i[3].value, "n_teams": i[4].value,
+                "cols_per_team": cpt.value, "grid": i[5].value, "n_panels": i[6].value}
+
     def joint_std(self):
         """(std_gz, std_tf): population std of the unweighted blocks of a weighted joint context (gh_joint_std)."""
         out = np.empty(2)

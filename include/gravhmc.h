@@ -163,6 +163,14 @@ int gh_joint_std(const gh_ctx *ctx, double std2[2]);
  * over the slab rows; 2: below 2048 rows with more than 64 slab rows per block, reduce_reg_kernel folds them into
  * segments first) */
 int gh_joint_layout(const gh_ctx *ctx, int *workgroups_per_block, int *epilogue_stages);
+/* The instantiation and column partition configure_sweep chose in gh_create for the dense fused sweep (read only;
+ * the fields of a matrix-free context are not used by it): sweep_kernel's team width tw (waves per team: 1, 4,
+ * 8, 16), ept2 (double2 per thread holding a column), pf (columns in flight beyond the one being reduced), nt
+ * (non-temporal loads of G), n_teams and cols_per_team (the column partition; a joint store's n_teams counts
+ * the teams of both blocks), grid (workgroups of one launch) and n_panels (row panels; > 1 beyond 16384 rows).
+ * Any pointer may be NULL. */
+int gh_sweep_layout(const gh_ctx *ctx, int *tw, int *ept2, int *pf, int *nt, int *n_teams, int64_t *cols_per_team,
+                    int *grid, int *n_panels);
 /* Prisms of a density model for one gravity field `component` (GH_COMP_*), M x 6 row-major
  * x1,x2,y1,y2,z1,z2 in mesh order.  Entry (i, j) is the field at observation i of prism j with a density
  * of 1 g/cm^3, scaled as prism.py scales kernel2d: G for the potential, G/g0 for the geoid, G*SI2MGAL for
