@@ -39,6 +39,9 @@ PROTOTYPES = {
     "gh_set_cells_joint": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
     "gh_joint_std": (C.c_int, [_ctx, _dp]),
     "gh_joint_layout": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gh_set_cross_gradient": (C.c_int, [_ctx, C.c_double, _dp, C.POINTER(C.c_int), C.c_double, C.c_double, _dp]),
+    "gh_cross_gradient_eval": (C.c_int, [_ctx, _dp, C.POINTER(C.c_double), _dp, _dp]),
+    "gh_cross_gradient_last": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
     "gh_sweep_layout": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                   C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gh_tf_result": (C.c_int, [_ctx, _dp, _dp]),

@@ -278,6 +278,83 @@ int gh_joint_layout(const gh_ctx *c, int *workgroups_per_block, int *epilogue_st
     return GH_OK;
 }
 
+int gh_set_cross_gradient(gh_ctx *c, double lambda, const double scale2[2], const int shape3[3], double hx, double hy,
+                          const double *hz)
+{
+    if (!c) return GH_ERR_ARG;
+    if (!c->joint)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cross_gradient: the cross-gradient term couples the two blocks of the "
+                                           "joint store (a GH_CELL_PRISM_JOINT context, gh_set_cells_joint)");
+    if (!scale2 || !shape3 || !hz) return fail(c, GH_ERR_ARG, "gh_set_cross_gradient: null pointer");
+    TRY(need(c, c->weighted, "gh_set_cross_gradient: call gh_weight first (the term acts on mw / Wm)"));
+    const int64_t m = c->M / 2;
+    if (shape3[0] < 2 || shape3[1] < 2 || shape3[2] < 2)
+        return fail(c, GH_ERR_ARG, "gh_set_cross_gradient: every extent of the mesh must be at least 2, got (%d,%d,%d)",
+                    shape3[0], shape3[1], shape3[2]);
+    if ((int64_t)shape3[0] * shape3[1] * shape3[2] != m)
+        return fail(c, GH_ERR_ARG, "gh_set_cross_gradient: shape nz*ny*nx must be M/2 = %lld (one property's full mesh), got "
+                                   "(%d,%d,%d)", (long long)m, shape3[0], shape3[1], shape3[2]);
+    if (!(lambda >= 0.0) || !std::isfinite(lambda)) return fail(c, GH_ERR_ARG, "gh_set_cross_gradient: lambda must be >= 0");
+    for (int h = 0; h < 2; ++h)
+        if (!(scale2[h] > 0.0) || !std::isfinite(scale2[h]))
+            return fail(c, GH_ERR_ARG, "gh_set_cross_gradient: the normalisers must be > 0");
+    bool ok = hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy);
+    for (int k = 0; ok && k < shape3[0] - 1; ++k) ok = hz[k] > 0.0 && std::isfinite(hz[k]);
+    if (!ok) return fail(c, GH_ERR_ARG, "gh_set_cross_gradient: every spacing must be > 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    gh_ctx::CrossGrad &cg = c->cg;
+    // (sized for any later shape: a mesh of m cells has fewer than m layers)
+    TRY(dalloc(c, &cg.ihz, (size_t)m));
+    TRY(dalloc(c, &cg.sw, (size_t)c->M));
+    std::vector<double> w((size_t)c->M), iz((size_t)shape3[0] - 1);
+    TRY(d2h(c, w.data(), c->wm, (size_t)c->M));
+    for (int64_t j = 0; j < c->M; ++j) w[(size_t)j] = w[(size_t)j] == 0.0 ? 0.0 : (1.0 / w[(size_t)j]) / scale2[j / m];
+    for (size_t k = 0; k < iz.size(); ++k) iz[k] = 1.0 / hz[k];
+    TRY(h2d(c, cg.sw, w.data(), (size_t)c->M));
+    TRY(h2d(c, cg.ihz, iz.data(), iz.size()));
+    cg.ihx = 1.0 / hx;
+    cg.ihy = 1.0 / hy;
+    for (int k = 0; k < 3; ++k) cg.shape[k] = shape3[k];
+    cg.scale[0] = scale2[0];
+    cg.scale[1] = scale2[1];
+    cg.lambda = lambda;
+    cg.set = true;
+    cg.phi_cur = cg.phi_last = 0.0;
+    c->chain_ready = false;
+    return GH_OK;
+}
+
+int gh_cross_gradient_eval(gh_ctx *c, const double *mw, double *value, double *grad, double *t)
+{
+    if (!c) return GH_ERR_ARG;
+    if (!c->joint)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_cross_gradient_eval: the cross-gradient term couples the two blocks of the "
+                                           "joint store (a GH_CELL_PRISM_JOINT context, gh_set_cells_joint)");
+    if (!mw || !value) return fail(c, GH_ERR_ARG, "gh_cross_gradient_eval: null pointer");
+    TRY(need(c, c->cg.set, "gh_cross_gradient_eval: call gh_set_cross_gradient first (lambda = 0 leaves the coupling off)"));
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(ensure_work(c));
+    const int64_t m = c->M / 2;
+    if (t) TRY(dalloc(c, &c->cg.tbuf, 3 * (size_t)m));
+    TRY(h2d(c, c->xb[3], mw, (size_t)c->M));
+    launch_cross_gradient(c, c->xb[3], 1.0, grad ? c->tmpM : nullptr, false, t ? c->cg.tbuf : nullptr, c->regpart);
+    sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->regpart, (int)((m + 255) / 256), c->st[3].scal);
+    HIPCHK(c, hipGetLastError());
+    TRY(d2h(c, c->h_scal, c->st[3].scal, 1));
+    *value = c->h_scal[0];
+    if (grad) TRY(d2h(c, grad, c->tmpM, (size_t)c->M));
+    if (t) TRY(d2h(c, t, c->cg.tbuf, 3 * (size_t)m));
+    return GH_OK;
+}
+
+int gh_cross_gradient_last(const gh_ctx *c, double *phi)
+{
+    if (!c || !phi) return GH_ERR_ARG;
+    if (!c->joint) return GH_ERR_UNSUPPORTED;
+    *phi = c->cg.phi_last;
+    return GH_OK;
+}
+
 int gh_sweep_layout(const gh_ctx *c, int *tw, int *ept2, int *pf, int *nt, int *n_teams, int64_t *cols_per_team,
                     int *grid, int *n_panels)
 {
@@ -972,9 +1049,12 @@ int gh_misfit_and_grad(gh_ctx *c, const double *x, double out3[3], double *grad,
     TRY(launch_sweep(c, a));
     TRY(scal_ready(c, o));
     HIPCHK(c, hipMemcpyAsync(c->h_scal, o.scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    const bool cg_on = cross_gradient_on(c);
+    if (cg_on) HIPCHK(c, hipMemcpyAsync(c->h_scal + 8, o.phi, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     TRY(d2h(c, grad, c->tmpM, (size_t)c->M));
     if (dpre) TRY(d2h_obsvec(c, dpre, o.d));
     TRY(lonsym_epilogue_check(c));
+    c->cg.phi_last = cg_on ? c->h_scal[8] : 0.0;
     out3[0] = c->h_scal[2];
     out3[1] = c->h_scal[0];
     out3[2] = c->h_scal[1];
@@ -1209,6 +1289,12 @@ int gh_chain_init(gh_ctx *c, const double *x0, const double *low, const double *
     TRY(eval_forward(c, c->xb[0], c->st[0]));
     TRY(scal_ready(c, c->st[0]));
     TRY(d2h(c, c->h_scal, c->st[0].scal, 4));
+    c->cg.phi_cur = 0.0;
+    if (cross_gradient_on(c)) {
+        TRY(d2h(c, c->h_scal + 8, c->st[0].phi, 1));
+        c->cg.phi_cur = c->h_scal[8];
+    }
+    c->cg.phi_last = c->cg.phi_cur;
     TRY(lonsym_epilogue_check(c));
     c->U_cur[0] = c->h_scal[2];
     c->U_cur[1] = c->h_scal[0];
@@ -1376,6 +1462,8 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
     TRY(scal_ready(c, c->st[sin]));
     if (spec) TRY(scal_ready(c, c->st[ss]));
     HIPCHK(c, hipMemcpyAsync(h, c->st[sin].scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    const bool cg_on = cross_gradient_on(c);
+    if (cg_on) HIPCHK(c, hipMemcpyAsync(h + 8, c->st[sin].phi, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h + 16, c->pp_part, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost,
                              c->stream));
     if (spec) {
@@ -1440,6 +1528,7 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
         c->U_cur[0] = Unew[0];
         c->U_cur[1] = Unew[1];
         c->U_cur[2] = Unew[2];
+        if (cg_on) c->cg.phi_cur = h[8];
         if (spec) {
             c->spec_valid = true;
             c->spec_dt = dt;
@@ -1456,6 +1545,7 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
     }
     c->pn_valid = false;
     *accepted = acc ? 1 : 0;
+    c->cg.phi_last = c->cg.phi_cur;  // (Phi of the state the chain is left in, as out5[0..2])
     out5[0] = c->U_cur[0];
     out5[1] = c->U_cur[1];
     out5[2] = c->U_cur[2];

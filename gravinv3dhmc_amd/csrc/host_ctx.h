@@ -127,6 +127,14 @@ struct gh_ctx {
     bool have_data = false, have_fix = false, have_reg = false;
     int reg_kind = 0, shape[3] = {1, 1, 1};
     double alpha = 1.0, beta = 0.01;
+    // cross-gradient coupling of a joint context (gh_set_cross_gradient): lambda > 0 switches it on
+    struct CrossGrad {
+        bool set = false;  // shape, spacings and normalisers are resident
+        double lambda = 0.0, scale[2] = {1.0, 1.0}, ihx = 1.0, ihy = 1.0;
+        int shape[3] = {1, 1, 1};
+        double *ihz = nullptr, *sw = nullptr, *tbuf = nullptr, *phi_all = nullptr;
+        double phi_cur = 0.0, phi_last = 0.0;  // of the chain's current state / of the last evaluation or state
+    } cg;
 
     // chain state: three (r, greg, d, scal) sets and three x buffers rotate between "current
     // sample", "proposal" and "speculative first step of the next trajectory"; set/buffer 3 is
@@ -134,6 +142,7 @@ struct gh_ctx {
     struct StateSet {
         double *r = nullptr, *greg = nullptr, *d = nullptr, *scal = nullptr;
         double *part = nullptr;        // |r|^2 and R partials of a one-launch epilogue
+        double *phi = nullptr;         // joint store: Phi of the cross-gradient coupling (scal_cg_kernel)
         mutable bool pending = false;  // scal[0..2] still to be summed from `part` (scal_ready)
     } st[4];
     double *xb[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -33,14 +33,47 @@ static void reduce_slab(gh_ctx *c, const double *gfix, double *d_out)
 // The joint store's epilogue: the existing epilogue kernels run once per block, on that block's half of the
 // slab rows, of d, r, dobsw and of the model, with no mean (reduce_finish_kernel with no slab-row sums and no
 // grav_fix removes a mean of exactly 0.0: r = d - dobsw) and the regulariser of that block alone (the
-// stencil of fd3djoint: nothing couples the blocks).  Partials: |r|^2 of gz, of tf, then R of gz, of tf --
-// scal_kernel sums them.  Below 2048 rows (few 32-row blocks for many slab rows) reduce_reg_kernel first
+// stencil of fd3djoint: the regulariser does not couple the blocks; the cross-gradient term, when switched on,
+// follows in a launch of its own).  Partials: |r|^2 of gz, of tf, then R of gz, of tf (then Phi) -- scal_kernel
+// (scal_cg_kernel) sums them.  Below 2048 rows (few 32-row blocks for many slab rows) reduce_reg_kernel first
 // folds the block's slab rows into slab2 segments, as the single-property path does.
 // (two stages: fewer than 2048 rows and more than 64 slab rows per block; ensure_work then has slab2, as it
 // allocates it whenever the grid has more than 64 rows)
 static bool joint_two_stage(const gh_ctx *c)
 {
     return c->joint && c->ld < 2048 && c->grid / 2 > 64;
+}
+
+// The cross-gradient coupling at x (2m), both blocks in one launch: g (or null) takes lambda dPhi/dmw -- added to
+// what is there (the epilogue: behind the two blocks' regulariser) or stored --, t (or null) the vectors, part the
+// ceil(m / 256) partials of Phi.
+static void launch_cross_gradient(gh_ctx *c, const double *x, double lambda, double *g, bool add, double *t, double *part)
+{
+    const gh_ctx::CrossGrad &cg = c->cg;
+    CrossGradArgs a{};
+    a.m = c->M / 2;
+    a.nz = cg.shape[0];
+    a.ny = cg.shape[1];
+    a.nx = cg.shape[2];
+    a.lambda = lambda;
+    a.ihx = cg.ihx;
+    a.ihy = cg.ihy;
+    a.ihz = cg.ihz;
+    a.x = x;
+    a.sw = cg.sw;
+    a.g = g;
+    a.t = t;
+    a.part = part;
+    const dim3 grid((unsigned)((a.m + 255) / 256));
+    if (add)
+        cross_gradient_kernel<true><<<grid, dim3(256), 0, c->stream>>>(a);
+    else
+        cross_gradient_kernel<false><<<grid, dim3(256), 0, c->stream>>>(a);
+}
+
+static bool cross_gradient_on(const gh_ctx *c)
+{
+    return c->joint && c->cg.set && c->cg.lambda > 0.0;
 }
 
 static int finalize_joint(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
@@ -94,6 +127,9 @@ static int finalize_joint(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
         fa.ra = ra;
         reduce_finish_kernel<<<dim3((unsigned)(c->n_dpart + n_reg)), dim3(256), 0, c->stream>>>(fa);
     }
+    // the coupling: lambda grad Phi on top of both blocks' alpha grad R, its partials behind those of R
+    if (cross_gradient_on(c))
+        launch_cross_gradient(c, x, c->cg.lambda, o.greg, true, nullptr, o.part + 2 * c->n_dpart + 2 * nrb);
     HIPCHK(c, hipGetLastError());
     o.pending = true;
     return GH_OK;
@@ -287,7 +323,10 @@ static int scal_ready(gh_ctx *c, const gh_ctx::StateSet &o)
     // (joint store: |r|^2 partials of both blocks, then R partials of both blocks)
     const int nd = c->joint ? 2 * c->n_dpart : c->n_dpart;
     const int nr = c->joint ? 2 * (int)((c->M / 2 + 255) / 256) : c->n_regpart;
-    scal_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(o.part, nd, nr, c->alpha, o.scal);
+    if (cross_gradient_on(c))
+        scal_cg_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(o.part, nd, nr, nr / 2, c->alpha, c->cg.lambda, o.scal, o.phi);
+    else
+        scal_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(o.part, nd, nr, c->alpha, o.scal);
     HIPCHK(c, hipGetLastError());
     o.pending = false;
     return GH_OK;
@@ -334,9 +373,13 @@ static int ensure_work(gh_ctx *c)
     }
     c->n_dpart = (int)((c->ld + 31) / 32);
     if (c->joint) {
-        // (the joint epilogue always leaves its partials: |r|^2 of both blocks, R of both blocks)
-        for (int i = 0; i < 4; ++i)
-            TRY(dalloc(c, &c->st[i].part, 2 * (size_t)c->n_dpart + 2 * (size_t)((c->M / 2 + 255) / 256)));
+        // (the joint epilogue always leaves its partials: |r|^2 of both blocks, R of both blocks, then -- coupling
+        // on -- Phi of the cross-gradient term, one per 256 cells of a property)
+        TRY(dalloc(c, &c->cg.phi_all, 4));
+        for (int i = 0; i < 4; ++i) {
+            TRY(dalloc(c, &c->st[i].part, 2 * (size_t)c->n_dpart + 3 * (size_t)((c->M / 2 + 255) / 256)));
+            c->st[i].phi = c->cg.phi_all + i;
+        }
     } else if (c->ld >= 2048 && ((c->TW > 1 && c->n_panels == 1 && !c->mf) || lonsym_on(c)) && env_int("GRAVHMC_EPILOGUE1", 1) != 0) {
         TRY(dalloc(c, &c->dsum, (size_t)std::max(std::max(c->grid, 128), lonsym_on(c) ? lonsym_classes(c) : 0)));
         for (int i = 0; i < 4; ++i) TRY(dalloc(c, &c->st[i].part, (size_t)c->n_dpart + (size_t)((c->M + 255) / 256)));

@@ -592,6 +592,122 @@ __global__ void __launch_bounds__(256) reg_kernel(RegArgs a)
         reg_block<false>(a, blockIdx.x, red);
 }
 
+// Cross-gradient coupling of the joint store (Gallardo & Meju 2003): t = grad u x grad w of the two
+// physical, normalised models u = mw_rho winv / s_rho, w = mw_kappa winv / s_kappa, forward differences
+// over centre distances at the cells with a forward neighbour on every axis, Phi = sum |t|^2.
+struct CrossGradArgs {
+    int64_t m;          // cells per property
+    int nz, ny, nx;
+    double lambda;      // factor of the gradient (the partials of Phi are not scaled)
+    double ihx, ihy;    // 1 / spacing
+    const double *ihz;  // nz - 1: 1 / distance between the centres of layers k and k + 1
+    const double *x;    // 2m: the stacked weighted model
+    const double *sw;   // 2m: winv / s of every entry (u = x sw)
+    double *g;          // 2m or null: lambda dPhi/dmw, added (ADD) or stored
+    double *t;          // 3m or null: t of every cell (0 where it does not contribute)
+    double *part;       // one partial of Phi per block
+};
+
+// t of cell q (layer kq; a contributing cell) and the derivatives of |t|^2 with respect to its two
+// difference vectors, A = 2 (Dw x t), B = 2 (t x Du), each component already divided by its spacing
+__device__ __forceinline__ void cg_cell(const CrossGradArgs &a, int64_t q, int kq, double (&t)[3], double (&A)[3],
+                                        double (&B)[3])
+{
+    const int64_t st[3] = {1, a.nx, (int64_t)a.nx * a.ny};
+    const double ih[3] = {a.ihx, a.ihy, a.ihz[kq]};
+    const double *xw = a.x + a.m, *sww = a.sw + a.m;
+    const double u0 = a.x[q] * a.sw[q], w0 = xw[q] * sww[q];
+    double Du[3], Dw[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int64_t n = q + st[c];
+        Du[c] = (a.x[n] * a.sw[n] - u0) * ih[c];
+        Dw[c] = (xw[n] * sww[n] - w0) * ih[c];
+    }
+    t[0] = Du[1] * Dw[2] - Du[2] * Dw[1];
+    t[1] = Du[2] * Dw[0] - Du[0] * Dw[2];
+    t[2] = Du[0] * Dw[1] - Du[1] * Dw[0];
+    A[0] = 2.0 * (Dw[1] * t[2] - Dw[2] * t[1]) * ih[0];
+    A[1] = 2.0 * (Dw[2] * t[0] - Dw[0] * t[2]) * ih[1];
+    A[2] = 2.0 * (Dw[0] * t[1] - Dw[1] * t[0]) * ih[2];
+    B[0] = 2.0 * (t[1] * Du[2] - t[2] * Du[1]) * ih[0];
+    B[1] = 2.0 * (t[2] * Du[0] - t[0] * Du[2]) * ih[1];
+    B[2] = 2.0 * (t[0] * Du[1] - t[1] * Du[0]) * ih[2];
+}
+
+// Gather form, one cell per thread, both blocks in one launch: a cell's entry of the gradient collects the
+// share of its own t (minus, every component) and of the t of its three backward neighbours (plus, the
+// component along that axis) -- each t is evaluated again where it is needed (four times in all, from a
+// model that the caches hold) instead of being stored by a launch of its own.  No atomics; the block's sum
+// of |t|^2 goes to part[blockIdx.x].
+template <bool ADD>
+__global__ void __launch_bounds__(256) cross_gradient_kernel(CrossGradArgs a)
+{
+    __shared__ double red[4];
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double phi = 0.0;
+    if (p < a.m) {
+        const int64_t nx = a.nx, ny = a.ny, P = nx * ny;
+        const int i = (int)(p % nx), j = (int)((p / nx) % ny), k = (int)(p / P);
+        const bool fx = i < a.nx - 1, fy = j < a.ny - 1, fz = k < a.nz - 1;
+        double gu = 0.0, gw = 0.0, t[3] = {0.0, 0.0, 0.0}, tb[3], A[3], B[3];
+        if (fx && fy && fz) {
+            cg_cell(a, p, k, t, A, B);
+            phi = t[0] * t[0] + t[1] * t[1] + t[2] * t[2];
+            gu -= A[0] + A[1] + A[2];
+            gw -= B[0] + B[1] + B[2];
+        }
+        if (i > 0 && fy && fz) {
+            cg_cell(a, p - 1, k, tb, A, B);
+            gu += A[0];
+            gw += B[0];
+        }
+        if (j > 0 && fx && fz) {
+            cg_cell(a, p - nx, k, tb, A, B);
+            gu += A[1];
+            gw += B[1];
+        }
+        if (k > 0 && fx && fy) {
+            cg_cell(a, p - P, k - 1, tb, A, B);
+            gu += A[2];
+            gw += B[2];
+        }
+        if (a.g) {
+            const double du = a.lambda * (gu * a.sw[p]), dw = a.lambda * (gw * a.sw[a.m + p]);
+            a.g[p] = ADD ? a.g[p] + du : du;
+            a.g[a.m + p] = ADD ? a.g[a.m + p] + dw : dw;
+        }
+        if (a.t) {
+            a.t[3 * p] = t[0];
+            a.t[3 * p + 1] = t[1];
+            a.t[3 * p + 2] = t[2];
+        }
+    }
+    const double tot = block_allreduce_sum(phi, red, 4);
+    if (threadIdx.x == 0) a.part[blockIdx.x] = tot;
+}
+
+// scal_kernel of a joint evaluation with the coupling on: the same sums in the same order, U takes
+// lambda Phi, and Phi (n_cgpart partials behind those of R) goes to a slot of its own
+__global__ void __launch_bounds__(1024) scal_cg_kernel(const double *part, int n_dpart, int n_regpart, int n_cgpart,
+                                                       double alpha, double lambda, double *scal, double *phi)
+{
+    __shared__ double red[16];
+    double s2 = 0.0, sr = 0.0, sp = 0.0;
+    for (int t = threadIdx.x; t < n_dpart; t += 1024) s2 += part[t];
+    for (int t = threadIdx.x; t < n_regpart; t += 1024) sr += part[n_dpart + t];
+    for (int t = threadIdx.x; t < n_cgpart; t += 1024) sp += part[n_dpart + n_regpart + t];
+    const double ud = block_allreduce_sum(s2, red, 16);
+    const double R = block_allreduce_sum(sr, red, 16);
+    const double Phi = block_allreduce_sum(sp, red, 16);
+    if (threadIdx.x == 0) {
+        scal[0] = ud;
+        scal[1] = R;
+        scal[2] = (ud + alpha * R) + lambda * Phi;
+        phi[0] = Phi;
+    }
+}
+
 // One launch for the two independent halves of the per-step epilogue: blocks [0, n_red) sum the
 // slab rows of one segment for 32 observations each (first stage of the slab reduction, same
 // arithmetic as reduce_slab_kernel with nseg > 1), the remaining blocks evaluate the regulariser.

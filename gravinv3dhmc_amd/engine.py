@@ -250,6 +250,41 @@ class Engine(object):
         self._chk(self._lib.gh_joint_layout(self._h, C.byref(wg), C.byref(st)))
         return {"workgroups_per_block": wg.value, "epilogue_stages": st.value}
 
+    def set_cross_gradient(self, lam, shape, hx, hy, hz, scale=(1.0, 1.0)):
+        """Cross-gradient coupling lam * sum |grad u x grad w|^2 of a weighted joint context (gh_set_cross_gradient):
+        shape = (nz, ny, nx) of one property's mesh, hx, hy and hz (nz - 1 centre distances) the spacings as given,
+        scale = (s_rho, s_kappa) the normalisers of the two physical models.  lam = 0 switches the term off."""
+        shape = [int(v) for v in shape]
+        if len(shape) != 3:
+            raise ValueError("shape must be (nz, ny, nx)")
+        hz = np.atleast_1d(f64(hz))
+        if hz.shape != (max(shape[0] - 1, 0),):
+            raise ValueError("hz must have nz - 1 = %d entries, got shape %r" % (shape[0] - 1, hz.shape))
+        scale = f64(scale)
+        if scale.shape != (2,):
+            raise ValueError("scale must be (s_rho, s_kappa)")
+        if hz.size == 0:
+            hz = np.ones(1)   # (an extent of 1 is refused by the library; it still wants an address)
+        self._chk(self._lib.gh_set_cross_gradient(self._h, float(lam), ptr(scale), (C.c_int * 3)(*shape), float(hx),
+                                                  float(hy), ptr(hz)))
+        self._chain_valid = False
+
+    def cross_gradient_eval(self, mw, want_grad=True, want_t=True):
+        """(Phi, dPhi/dmw or None, t as (M/2, 3) or None) of the cross-gradient term alone, lam = 1, with the geometry
+        of the last set_cross_gradient (gh_cross_gradient_eval)."""
+        mw = self._vecM(mw, "mw")
+        val = C.c_double(0)
+        grad = np.empty(self.M) if want_grad else None
+        t = np.empty((self.M // 2, 3)) if want_t else None
+        self._chk(self._lib.gh_cross_gradient_eval(self._h, ptr(mw), C.byref(val), ptr(grad), ptr(t)))
+        return val.value, grad, t
+
+    def cross_gradient_last(self):
+        """Phi of the last misfit_and_grad, or of the state the chain is in (gh_cross_gradient_last); 0 while off."""
+        val = C.c_double(0)
+        self._chk(self._lib.gh_cross_gradient_last(self._h, C.byref(val)))
+        return val.value
+
     def sweep_layout(self):
         """Instantiation and column partition of the dense fused sweep (gh_sweep_layout): team width tw, ept2
         (double2 per thread), pf, nt, n_teams, cols_per_team, grid and n_panels."""

@@ -3,7 +3,8 @@
 Host-side mirror of the reference's `inversion.potential.JointModule` (inversion/potential.py:847-1812): the
 density and the magnetization of the same prisms under the same observation points, with the block-diagonal
 kernel A = [[A_gz, 0], [0, A_tf]], the data balance Wb = diag(1 ... 1, s ... s), s = std(A_gz) / std(A_tf),
-the column-norm weights Wm of A, and the potential |Aw mw - dobsw|^2 + alpha R(mw) with no mean removal.
+the column-norm weights Wm of A, and the potential |Aw mw - dobsw|^2 + alpha R(mw) with no mean removal --
+plus, on request, the cross-gradient term lambda |grad rho x grad kappa|^2 that ties the two models' structure.
 
 The device keeps H = [Aw_gz | Aw_tf] (N rows, 2M columns): the zero blocks are never stored or read
 (libgravhmc's GH_CELL_PRISM_JOINT).  `Aw` is a device handle whose array is the reference's 2N x 2M layout.
@@ -52,6 +53,14 @@ class JointModule(_Potential):
     mratio, mangle = (inclination, declination) of the regional field; `mtopo=(x, y, topography)` carves the
     mesh (active cells only, as GravMagModule).  device: GPU ordinal (extension).
 
+    crossgradient = lambda, cg_scale = (s_rho, s_kappa) (extension; see set_cross_gradient): with lambda > 0 every
+    potential evaluation and every chain adds lambda * Phi, Phi = sum |grad(rho / s_rho) x grad(kappa / s_kappa)|^2
+    over the cells with a forward neighbour on all three axes (Gallardo & Meju 2003), evaluated on the device.
+    The differences are taken over RELATIVE spacings: every centre distance of the mesh divided by the smallest
+    of them, so that a cubic mesh gets the unit differences of fd3d and lambda has the order of magnitude of
+    alpha (with metres Phi would be ~1e-7 for O(1) models).  The reported model value stays R; Phi is
+    `last_cross_gradient`.  Default 0: off, nothing is launched or changed.
+
     Attributes as the reference: meshrho, meshmag, mshape, mxs/mys/mzs, dobs, dobsw, Wb, Wm, WmInv, WmSquare,
     Aw (a device handle; np.asarray(Aw) is the 2N x 2M stacked layout).  A, kernel_gz and kernel_tf are formed
     on request from the device copy: Aw's blocks times Wm and over Wb, equal to the reference's to rounding,
@@ -59,12 +68,14 @@ class JointModule(_Potential):
 
     Divergences: coordinate="spherical" and wavelet compression raise NotImplementedError (the reference's
     branches are broken); Smoothness and TV work, with the block-diagonal operator fd3djoint (the reference
-    raises AttributeError there: it calls a missing fd3d).  CrossGradient is absent (the reference's is `pass`).
+    raises AttributeError there: it calls a missing fd3d).  CrossGradient is implemented (the reference's body is
+    `pass`) and can be switched into the potential.
     """
     _props = 2  # (density and magnetization of the same mesh)
 
     def __init__(self, dobs_gz, dobs_tf, mrange, mspacing, obsurface, mratio=1, coordinate="cartesian", njobs=1,
-                 mangle=(90, 0), wavelet=False, device=0, verbose=True, **kwargs):
+                 mangle=(90, 0), wavelet=False, device=0, verbose=True, crossgradient=0.0, cg_scale=(1.0, 1.0),
+                 **kwargs):
         self._say = print if verbose else (lambda *a, **k: None)
         if coordinate == "spherical":
             # (the reference's spherical branch never defines kernel_tf: potential.py:885-895)
@@ -112,6 +123,16 @@ class JointModule(_Potential):
         self.mxs, self.mys, self.mzs = mesh.get_xs(), mesh.get_ys(), mesh.get_zs()
         self.weightKDM()
         eng.set_data(self.dobsw)
+        # centre distances of the mesh relative to the smallest of them (the cross-gradient term's spacings)
+        zc = np.array([0.5 * sum(mesh._layer_z(k)) for k in range(mesh.shape[0])])
+        hz = np.diff(zc)
+        hmin = min([float(mesh.dims[0]), float(mesh.dims[1])] + [float(v) for v in hz])
+        self._cg_spacing = (mesh.dims[0] / hmin, mesh.dims[1] / hmin, hz / hmin)
+        self._cg = None  # (lambda, scale) once the engine holds the coupling's geometry
+        if crossgradient != 0:
+            self.set_cross_gradient(crossgradient, cg_scale)
+        else:
+            self._cg_scale = tuple(float(v) for v in cg_scale)
 
     # ------------------------------------------------------------------ weighting
     def weightKDM(self):
@@ -164,3 +185,43 @@ class JointModule(_Potential):
         """The reference's block-diagonal finite-difference matrix of the two properties (potential.py:1075-1220)."""
         R = fd3d(shape)
         return block_diag([R, R], format="csr")
+
+    # ------------------------------------------------------------------ cross-gradient coupling
+    def _send_cross_gradient(self, lam, scale):
+        if self.topocarve:
+            cells = self._props * int(np.prod(self.mshape))
+            raise ValueError("CrossGradient needs the full (uncarved) mesh: %d x shape %r has %d cells, model has %d"
+                             % (self._props, self.mshape, cells, self._engine.M))
+        hx, hy, hz = self._cg_spacing
+        self._engine.set_cross_gradient(lam, self.mshape, hx, hy, hz, scale)
+        self._cg = (float(lam), scale)
+
+    def set_cross_gradient(self, lam, scale=None):
+        """Switch the cross-gradient coupling lam * Phi into the potential (lam = 0: off again; results are then
+        those of a module that never had it).  scale = (s_rho, s_kappa) > 0 normalises the two physical models
+        (kept from the last call when None).  The spacings are the mesh's centre distances relative to the smallest
+        of them (see the class docstring).  A carved mesh (mtopo=) raises ValueError."""
+        scale = tuple(float(v) for v in (self._cg_scale if scale is None else scale))
+        if len(scale) != 2:
+            raise ValueError("scale must be (s_rho, s_kappa)")
+        if lam == 0 and self._cg is None and scale[0] > 0 and scale[1] > 0:
+            self._cg_scale = scale  # (never switched on: nothing to switch off)
+            return
+        self._send_cross_gradient(lam, scale)
+        self._cg_scale = scale
+
+    def CrossGradient(self, model):
+        """The cross-gradient term of the stacked PHYSICAL model (2M entries: density, then magnetization):
+        (Phi, dPhi/dmodel, t as an (M, 3) array), with the normalisers of set_cross_gradient and lambda = 1
+        (potential.py:1558, empty in the reference)."""
+        model = np.asarray(model, dtype=np.float64).ravel()
+        if self._cg is None:
+            self._send_cross_gradient(0.0, self._cg_scale)
+        wm = self.Wm.diagonal()
+        phi, grad, t = self._engine.cross_gradient_eval(model * wm)
+        return phi, grad * wm, t
+
+    @property
+    def last_cross_gradient(self):
+        """Phi of the last misfit_and_grad, or of the state the chain is in; 0 while the coupling is off."""
+        return self._engine.cross_gradient_last()

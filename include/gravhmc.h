@@ -149,8 +149,9 @@ int gh_tf_result(gh_ctx *ctx, const double *mag3, double *result);
  *   gh_set_data  takes dobs = dobsw = Wb [dobs_gz; dobs_tf] (N entries) and NO mean is removed; grav_fix
  *                must be null.  The data term is |Aw mw - dobsw|^2 (potential.py:1665-1680).
  *   gh_set_reg / gh_reg_eval: Smoothness and TV take shape3 with nz*ny*nx == M/2 and apply the stencil to
- *                each property on its own (the block-diagonal fd3djoint, potential.py:1075): no term
- *                couples the two blocks.
+ *                each property on its own (the block-diagonal fd3djoint, potential.py:1075): the regulariser
+ *                does not couple the two blocks.
+ *   gh_set_cross_gradient adds the one term that does: lambda |grad rho x grad kappa|^2 (off by default).
  * Dense, single chain only: matrix-free, the shift-invariant store, the wavelet compressor, gh_batch_*,
  * gh_shard_init*, gh_upload_G and N/2 > 16384 return GH_ERR_UNSUPPORTED; the resident chain kernel is
  * never chosen (chains run on the fused sweep). */
@@ -163,6 +164,31 @@ int gh_joint_std(const gh_ctx *ctx, double std2[2]);
  * over the slab rows; 2: below 2048 rows with more than 64 slab rows per block, reduce_reg_kernel folds them into
  * segments first) */
 int gh_joint_layout(const gh_ctx *ctx, int *workgroups_per_block, int *epilogue_stages);
+/* Cross-gradient structural coupling of a weighted GH_CELL_PRISM_JOINT context (Gallardo & Meju 2003; the
+ * reference's JointModule.CrossGradient, potential.py:1558, is an empty method).  With shape3 = (nz, ny, nx),
+ * nz*ny*nx == M/2, x fastest (p = (k ny + j) nx + i), the physical, normalised models are
+ *     u[p] = mw[p] winv[p] / scale2[0],   w[p] = mw[M/2 + p] winv[M/2 + p] / scale2[1]
+ * (winv = 1 / Wm, 0 where Wm is 0; no prior model is subtracted).  At the cells with i < nx-1, j < ny-1, k < nz-1
+ *     Du = ((u[p+1] - u[p]) / hx, (u[p+nx] - u[p]) / hy, (u[p+nx ny] - u[p]) / hz[k]),  Dw likewise,
+ *     t = Du x Dw,   Phi = sum_p |t_p|^2
+ * and every other cell contributes nothing.  hz has nz-1 entries: the distance between the centres of layers k
+ * and k+1.  The spacings are taken as given, in any unit (JointModule passes them relative to the smallest).
+ * With lambda > 0 every potential evaluation of the context -- gh_misfit_and_grad, gh_leapfrog, gh_chain_* --
+ * becomes U = U_data + alpha R + lambda Phi, grad likewise; the reported U_model stays R (out3[2], out5[2]) and
+ * Phi is read with gh_cross_gradient_last.  One more kernel launch per evaluation, behind the regulariser's;
+ * sums in a fixed order.  lambda = 0 switches the term off: the context then launches and returns exactly
+ * what it did before the call.  A running chain must be started again (gh_chain_init).
+ * Errors: GH_ERR_UNSUPPORTED on a context that is not a joint store; GH_ERR_ARG before gh_weight, for a shape whose
+ * product is not M/2 or with an extent below 2, lambda < 0, a normaliser <= 0 or a spacing <= 0. */
+int gh_set_cross_gradient(gh_ctx *ctx, double lambda, const double scale2[2], const int shape3[3], double hx,
+                          double hy, const double *hz /* nz-1 */);
+/* The term alone at mw (M entries), lambda = 1, with the shape, spacings and normalisers of the last
+ * gh_set_cross_gradient (whatever its lambda): *value = Phi, grad (M, or NULL) = dPhi/dmw, t (3 M/2, or NULL) =
+ * the vectors t_p, cell-major, zero at the cells that do not contribute. */
+int gh_cross_gradient_eval(gh_ctx *ctx, const double *mw, double *value, double *grad, double *t);
+/* Phi of the last gh_misfit_and_grad, or of the state the chain was left in by the last gh_chain_init /
+ * trajectory (as out5[0..2]); 0 while the coupling is off. */
+int gh_cross_gradient_last(const gh_ctx *ctx, double *phi);
 /* The instantiation and column partition configure_sweep chose in gh_create for the dense fused sweep (read only;
  * the fields of a matrix-free context are not used by it): sweep_kernel's team width tw (waves per team: 1, 4,
  * 8, 16), ept2 (double2 per thread holding a column), pf (columns in flight beyond the one being reduced), nt

@@ -2,6 +2,7 @@
 
     python profiles/joint_timing.py [--out FILE]          # every step, each in its own child process
     python profiles/joint_timing.py --step NAME           # one step
+    python profiles/joint_timing.py --step joint --crossgrad 1.0   # the joint chains with the cross-gradient coupling on
 
 Steps (C2's geometry: 100 x 100 observations over [0, 5000]^2 at z = -1; C2's mesh is 100 x 100 x 50 prisms):
   assembly  build_G of a joint store over 100 x 100 x 25 prisms (2.5*10^9 pairs, both fields), of a gz and of a
@@ -78,9 +79,18 @@ def step_assembly(emit):
     emit(out)
 
 
-def chain_steps(eng, label, emit, L=20, traj=6):
+CROSSGRAD = 0.0   # --crossgrad: lambda of the cross-gradient coupling on the joint stores (0: off)
+
+
+def chain_steps(eng, label, emit, L=20, traj=6, shape=None):
     M = eng.M
     wm = eng.weight(0.5)
+    if shape is not None and CROSSGRAD > 0:
+        # (unit spacings, normalisers that bring the physical models to O(1))
+        m = M // 2
+        eng.set_cross_gradient(CROSSGRAD, shape, 1.0, 1.0, np.ones(shape[0] - 1),
+                               (1e-3 / np.median(wm[:m]), 1e-3 / np.median(wm[m:])))
+        label += "_crossgrad"
     rng = np.random.default_rng(0)
     eng.set_data(rng.normal(size=eng.N))
     eng.set_reg("Damping", 1.0, 0.01, None, np.zeros(M))
@@ -107,7 +117,7 @@ def step_joint(emit):
     bounds, obs = geometry(25)
     eng = engine("joint", bounds, obs)
     eng.build_G()
-    chain_steps(eng, "joint", emit)
+    chain_steps(eng, "joint", emit, shape=(25, 100, 100))
     eng.close()
 
 
@@ -133,7 +143,7 @@ def step_small(emit):
         eng.build_G()
         if kind == "joint":
             emit({"step": "small_layout", **eng.joint_layout()})
-        chain_steps(eng, "small_" + kind, emit, L=20, traj=20)
+        chain_steps(eng, "small_" + kind, emit, L=20, traj=20, shape=(10, 30, 20) if kind == "joint" else None)
         eng.close()
 
 
@@ -141,7 +151,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", choices=sorted(STEPS))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--crossgrad", type=float, default=0.0, help="lambda of the cross-gradient coupling (joint stores)")
     args = ap.parse_args()
+    global CROSSGRAD
+    CROSSGRAD = args.crossgrad
 
     def emit(d):
         print(json.dumps(d), flush=True)
@@ -156,6 +169,8 @@ def main():
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name]
         if args.out:
             cmd += ["--out", args.out]
+        if args.crossgrad:
+            cmd += ["--crossgrad", str(args.crossgrad)]
         rc = subprocess.call(cmd)
         if rc != 0:
             print("step %s ended with status %d: stopping" % (name, rc), flush=True)
