@@ -55,6 +55,8 @@ static_assert(COMP_POTENTIAL == GH_COMP_POTENTIAL && COMP_GEOID == GH_COMP_GEOID
 #include "host_resbatch.h"
 #include "host_lonres.h"
 #include "host_batch.h"
+#include "host_batchrun.h"
+#include "host_chain.h"
 
 // ------------------------------------------------------------------------- C-ABI
 
@@ -1325,235 +1327,6 @@ int gh_chain_prefetch_momentum(gh_ctx *c, const double *p0_next)
     return GH_OK;
 }
 
-// d, r and the scalars of the current sample after launches of the resident chain kernel
-static int chain_state_fresh(gh_ctx *c)
-{
-    if (!c->st_stale) return GH_OK;
-    TRY(eval_forward(c, c->xb[c->xcur], c->st[c->cur]));
-    TRY(scal_ready(c, c->st[c->cur]));
-    TRY(d2h(c, c->h_scal, c->st[c->cur].scal, 4));
-    c->U_cur[0] = c->h_scal[2];
-    c->U_cur[1] = c->h_scal[0];
-    c->U_cur[2] = c->h_scal[1];
-    c->st_stale = false;
-    return GH_OK;
-}
-
-static inline int other_of3(int a, int b)
-{
-    for (int i = 0; i < 3; ++i)
-        if (i != a && i != b) return i;
-    return 0;
-}
-
-// p0_next (or nullptr): momentum of the NEXT trajectory, valid until this call returns.  Announced
-// this way (gh_chain_run) it is uploaded on a second stream while this trajectory's sweeps run --
-// through the public gh_chain_prefetch_momentum the upload happens before them, with the GPU idle.
-static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, double u, const double *p0_next,
-                                 int *accepted, double out5[5])
-{
-    if (!c || !p0 || !accepted || !out5) return fail(c, GH_ERR_ARG, "gh_chain_trajectory: null pointer");
-    TRY(need(c, c->chain_ready, "gh_chain_trajectory: call gh_chain_init first"));
-    if (L < 1) return fail(c, GH_ERR_ARG, "gh_chain_trajectory: L must be >= 1");
-    HIPCHK(c, hipSetDevice(c->device));
-    TRY(chain_state_fresh(c));
-    // (sweeps launched from here may run on teams of workgroups whose time-out this function handles)
-    struct TeamsOk {
-        gh_ctx *c;
-        ~TeamsOk() { c->chain_teams_ok = false; }
-    } teams_guard{c};
-    c->chain_teams_ok = true;
-    const size_t M = (size_t)c->M;
-    const int nt = c->n_teams;
-    // Was the first step of this trajectory already taken speculatively by the previous call's
-    // last sweep (same momentum, same dt, previous proposal accepted)?
-    const bool use_spec = c->spec_valid && c->spec_dt == dt && p0[0] == c->spec_probe[0] &&
-                          p0[c->M / 2] == c->spec_probe[1] && p0[c->M - 1] == c->spec_probe[2];
-    int xin, pin, sin, s0;
-    if (use_spec) {
-        xin = c->spec_x;
-        pin = c->spec_p;
-        sin = c->spec_set;
-        s0 = 1;
-        c->spec_hits += 1;
-    } else {
-        // momentum upload + kinetic energy of p0 (hmc.py:95-104)
-        HIPCHK(c, hipMemcpyAsync(c->pb[0], p0, M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        sumsq_kernel<<<dim3(c->n_pp0), dim3(256), 0, c->stream>>>(c->pb[0], c->M, c->pp0_part);
-        xin = c->xcur;
-        pin = 0;
-        sin = c->cur;
-        s0 = 0;
-        if (c->spec_valid) c->spec_misses += 1;
-    }
-    c->spec_valid = false;
-    for (int s = s0; s < L; ++s) {
-        const int xout = other_of3(c->xcur, xin);
-        const int sout = (sin != c->cur) ? sin : other_of3(c->cur, c->cur);
-        SweepArgs a{};
-        a.mode = SW_ADJ | SW_UPD | (c->wv.on ? 0 : SW_FWD);
-        a.r = c->st[sin].r;
-        a.greg = c->st[sin].greg;
-        a.x_in = c->xb[xin];
-        a.p_in = c->pb[pin];
-        a.x_out = c->xb[xout];
-        a.p_out = c->pb[pin ^ 1];
-        a.low = c->low;
-        a.high = c->high;
-        a.c_u = (s == 0) ? dt * 0.5 : dt;
-        a.dt = dt;
-        a.slab = c->slab;
-        TRY(launch_sweep(c, a));
-        TRY(finalize(c, c->xb[xout], c->st[sout]));
-        xin = xout;
-        pin ^= 1;
-        sin = sout;
-    }
-    // Last half step of the momentum + kinetic energy (hmc.py:151-157).  When the caller has
-    // announced the next trajectory's momentum, the same sweep also takes that trajectory's
-    // first leapfrog step from the proposal (valid if the proposal is accepted): the gradient
-    // at the proposal is needed by both, so the extra sweep per trajectory disappears.
-    bool spec = c->pn_valid;
-    double probe[3] = {c->pn_probe[0], c->pn_probe[1], c->pn_probe[2]};
-    double pn_pp0 = c->pn_pp0;
-    bool pn_deferred = false;
-    if (p0_next) {
-        if (!c->copy_stream) {
-            HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-            HIPCHK(c, hipEventCreateWithFlags(&c->copy_ev, hipEventDisableTiming));
-        }
-        // (c->pn was last read by the previous trajectory's final sweep, which has completed)
-        HIPCHK(c, hipMemcpyAsync(c->pn, p0_next, M * sizeof(double), hipMemcpyHostToDevice, c->copy_stream));
-        HIPCHK(c, hipEventRecord(c->copy_ev, c->copy_stream));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->copy_ev, 0));
-        // its initial kinetic energy, summed exactly like gh_chain_prefetch_momentum does
-        sumsq_kernel<<<dim3(c->n_pp0), dim3(256), 0, c->stream>>>(c->pn, c->M, c->pn0_part);
-        probe[0] = p0_next[0];
-        probe[1] = p0_next[c->M / 2];
-        probe[2] = p0_next[c->M - 1];
-        spec = true;
-        pn_deferred = true;
-    }
-    const int xs = other_of3(c->xcur, xin), ss = other_of3(c->cur, sin);
-    {
-        SweepArgs a{};
-        a.mode = SW_ADJ | SW_PFIN;
-        a.r = c->st[sin].r;
-        a.greg = c->st[sin].greg;
-        a.p_in = c->pb[pin];
-        a.p_out = c->pb[pin ^ 1];
-        a.c_p = dt * 0.5;
-        a.pp_part = c->pp_part;
-        if (spec) {
-            a.mode |= SW_SPEC | SW_UPD | (c->wv.on ? 0 : SW_FWD);
-            a.pn_in = c->pn;
-            a.x_in = c->xb[xin];
-            a.x_out = c->xb[xs];
-            a.low = c->low;
-            a.high = c->high;
-            a.c_u = dt * 0.5;
-            a.dt = dt;
-            a.slab = c->slab;
-        }
-        TRY(launch_sweep(c, a));
-        if (spec) TRY(finalize(c, c->xb[xs], c->st[ss]));
-    }
-    double *h = c->h_scal;
-    TRY(scal_ready(c, c->st[sin]));
-    if (spec) TRY(scal_ready(c, c->st[ss]));
-    HIPCHK(c, hipMemcpyAsync(h, c->st[sin].scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    const bool cg_on = cross_gradient_on(c);
-    if (cg_on) HIPCHK(c, hipMemcpyAsync(h + 8, c->st[sin].phi, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h + 16, c->pp_part, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost,
-                             c->stream));
-    if (spec) {
-        HIPCHK(c, hipMemcpyAsync(h + 4, c->st[ss].scal, 4 * sizeof(double), hipMemcpyDeviceToHost,
-                                 c->stream));
-    }
-    if (!use_spec)
-        HIPCHK(c, hipMemcpyAsync(h + 16 + 2 * nt, c->pp0_part, (size_t)c->n_pp0 * sizeof(double),
-                                 hipMemcpyDeviceToHost, c->stream));
-    if (pn_deferred)
-        HIPCHK(c, hipMemcpyAsync(h + 16 + 2 * nt + c->n_pp0, c->pn0_part, (size_t)c->n_pp0 * sizeof(double),
-                                 hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    // a team sweep of this trajectory gave up (its workgroups were not all resident): nothing of
-    // the chain's current state was touched -- run the trajectory again, in row panels.  Sharded
-    // chain: decided by all ranks together, below (the flag rides on the scalar all-reduce)
-    TRY(lonsym_epilogue_check(c));
-    bool failed = false;
-    TRY(team_failed(c, &failed));
-    if (!failed) TRY(mft_failed(c, &failed));  // (matrix-free chain on teams: same contract)
-    auto redo = [&]() -> int {
-        c->spec_valid = c->pn_valid = false;
-        const int rc = chain_trajectory_impl(c, p0, dt, L, u, p0_next, accepted, out5);
-        team_resume(c);
-        return rc;
-    };
-    if (failed && c->sh.kind == 0) return redo();
-    if (pn_deferred) {
-        double s = 0.0;
-        for (int t = 0; t < c->n_pp0; ++t) s += h[16 + 2 * nt + c->n_pp0 + t];
-        pn_pp0 = s;
-    }
-    double pp1 = 0.0, pp0 = 0.0;
-    for (int t = 0; t < nt; ++t) pp1 += h[16 + t];
-    if (use_spec)
-        pp0 = c->spec_pp0;
-    else
-        for (int t = 0; t < c->n_pp0; ++t) pp0 += h[16 + 2 * nt + t];
-    double pn_pp0_g = pn_pp0;
-    if (shard_cols(c)) {
-        // kinetic energies are sums over cells: combine the ranks' parts (same bits everywhere)
-        double v[4] = {pp1, use_spec ? 0.0 : pp0, spec ? pn_pp0 : 0.0, failed ? 1.0 : 0.0};
-        if (failed) v[0] = v[1] = v[2] = 0.0;  // (whatever the aborted sweeps left: not worth a NaN in the sum)
-        TRY(comm_allreduce_host(c, v, 4));
-        if (v[3] != 0.0) {
-            // some rank's team sweep gave up: its slab went into everybody's d and r through the
-            // all-reduces of this trajectory -- every rank repeats it, in row panels, together
-            if (!failed) TRY(team_mark_failed(c, "another rank's"));
-            return redo();
-        }
-        pp1 = v[0];
-        if (!use_spec) pp0 = v[1];
-        pn_pp0_g = v[2];
-    }
-    const double Unew[3] = {h[2], h[0], h[1]};
-    const double Hcur = 0.5 * pp0 + c->U_cur[0];
-    const double Hnew = 0.5 * pp1 + Unew[0];
-    const bool acc = (Hnew < Hcur) || (u < std::exp(-(Hnew - Hcur)));
-    if (acc) {
-        c->xcur = xin;
-        c->cur = sin;
-        c->U_cur[0] = Unew[0];
-        c->U_cur[1] = Unew[1];
-        c->U_cur[2] = Unew[2];
-        if (cg_on) c->cg.phi_cur = h[8];
-        if (spec) {
-            c->spec_valid = true;
-            c->spec_dt = dt;
-            c->spec_pp0 = pn_pp0_g;
-            c->spec_x = xs;
-            c->spec_p = pin ^ 1;
-            c->spec_set = ss;
-            c->spec_probe[0] = probe[0];
-            c->spec_probe[1] = probe[1];
-            c->spec_probe[2] = probe[2];
-        }
-    } else if (spec) {
-        c->spec_misses += 1;  // the speculative step belonged to a rejected proposal
-    }
-    c->pn_valid = false;
-    *accepted = acc ? 1 : 0;
-    c->cg.phi_last = c->cg.phi_cur;  // (Phi of the state the chain is left in, as out5[0..2])
-    out5[0] = c->U_cur[0];
-    out5[1] = c->U_cur[1];
-    out5[2] = c->U_cur[2];
-    out5[3] = Hcur;
-    out5[4] = Hnew;
-    return GH_OK;
-}
-
 int gh_chain_trajectory(gh_ctx *c, const double *p0, double dt, int L, double u, int *accepted,
                         double out5[5])
 {
@@ -1703,134 +1476,6 @@ int gh_posterior_read(gh_ctx *c, int64_t *n_in_window, int64_t *n_total, double 
     return GH_OK;
 }
 
-// ---- a batch of chains on the shift-invariant store (BASELINE configs[3]: "8 chains"; the reference runs them
-// as MPI ranks, example/global/run_main.sh:16, each with its own 4.25 GB kernel).  A step of ONE chain on the
-// table keeps a fraction of the chip busy for ~60 us, most of it latency: the chains are C light contexts
-// that share the parent's tables (T, T^: read-only) and problem vectors, each with its own stream, chain
-// state and work buffers, driven by one host thread each -- their passes overlap on the GPU.
-static int kids_make(gh_ctx *c, int C, const double *x0s, const double *low, const double *high)
-{
-    for (gh_ctx *k : c->kids) gh_destroy(k);
-    c->kids.clear();
-    for (int i = 0; i < C; ++i) {
-        gh_ctx *k = nullptr;
-        const int rc0 = gh_create(&k, c->device, c->N, c->M);
-        if (rc0 != GH_OK) return fail(c, rc0, "gh_batch_init: %s", gh_last_error(nullptr));
-        c->kids.push_back(k);
-        k->cell_kind = c->cell_kind;
-        k->ratio = c->ratio;
-        for (int q = 0; q < 3; ++q) k->tf_dir[q] = c->tf_dir[q];
-        k->tf_dir_d = c->tf_dir_d;
-        k->comp = c->comp;  // (GH_CELL_TESSEROID_COMP never gets here: the shift-invariant store refuses it)
-        k->have_obs = k->have_cells = k->have_G = true;
-        k->mf = true;
-        k->weighted = c->weighted;
-        k->wm = c->wm;
-        k->wm2 = c->wm2;
-        k->dobs_c = c->dobs_c;
-        k->gfix = c->gfix;
-        k->gfix_sum = c->gfix_sum;
-        k->mwapr = c->mwapr;
-        k->have_data = c->have_data;
-        k->have_fix = c->have_fix;
-        k->have_reg = c->have_reg;
-        k->reg_kind = c->reg_kind;
-        for (int q = 0; q < 3; ++q) k->shape[q] = c->shape[q];
-        k->alpha = c->alpha;
-        k->beta = c->beta;
-        k->ls = new LonSymHost(*c->ls);  // (the tables are the parent's; the pass's work buffers are its own)
-        k->ls->Rhat = k->ls->Dpart = nullptr;
-        k->ls->res = LonSymHost::Res();
-        k->ls->res.state = -1;  // (the persistent pass takes every CU: not for chains that share the GPU)
-        k->ls->dbg = nullptr;
-        k->ls->csum = nullptr;
-        k->ls->epi = ExchangeGuard();
-        k->ls->rhat_of = nullptr;
-        k->ls->post_pending = false;
-        if (k->ls->harm) {
-            int rc = dalloc(k, &k->ls->Rhat, (size_t)k->ls->na * (size_t)k->ls->nf);
-            if (rc == GH_OK) rc = dalloc(k, &k->ls->Dpart, (size_t)k->ls->hgrid * (size_t)k->ls->na * (size_t)k->ls->nf);
-            if (rc == GH_OK && k->ls->fused) rc = dalloc(k, &k->ls->csum, 2 * (size_t)k->ls->na);
-            if (rc == GH_OK && k->ls->fused)
-                rc = xg_alloc(k, k->ls->epi, {{k->ls->csum, sizeof(unsigned long long) * 2 * (size_t)k->ls->na}});
-            if (rc != GH_OK) return fail(c, rc, "gh_batch_init: %s", gh_last_error(k));
-        }
-        if (k->ls->wide) {
-            k->ls->Xhat = nullptr;
-            int rc = dalloc(k, &k->ls->Rhat, (size_t)k->ls->na * (size_t)k->ls->nfp);
-            if (rc == GH_OK) rc = dalloc(k, &k->ls->Xhat, (size_t)k->ls->nc * (size_t)k->ls->nf);
-            if (rc == GH_OK) rc = dalloc(k, &k->ls->Dpart, (size_t)k->ls->wparts * (k->ls->wmirror ? 2 : 1) * (size_t)k->ls->na * (size_t)k->ls->nfp);
-            if (rc != GH_OK) return fail(c, rc, "gh_batch_init: %s", gh_last_error(k));
-        }
-        int rc = configure_mf(k);
-        if (rc == GH_OK) rc = dalloc(k, &k->mf_stats, 1);
-        if (rc == GH_OK) rc = gh_chain_init(k, x0s + (size_t)i * (size_t)c->M, low, high);
-        if (rc != GH_OK) return fail(c, rc, "gh_batch_init (chain %d): %s", i, gh_last_error(k));
-    }
-    c->bt.C = C;
-    c->bt.ready = true;
-    c->bt.run = gh_ctx::Batch::Run();
-    return GH_OK;
-}
-
-// T trajectories of every chain (lists chain-major), each chain on its own thread and stream; results of
-// chain i in slots i * Tout + t.  Nothing stays in flight.
-static int kids_run(gh_ctx *c, int T, const int *L, const double *const *p0rows, const double *p0flat, const double *us,
-                    double dt, int *accepted, double *out5s, double *x_out, int Tout)
-{
-    const int C = (int)c->kids.size();
-    const size_t M = (size_t)c->M;
-    std::vector<int> rcs((size_t)C, GH_OK);
-    // On the harmonic store the chains TAKE TURNS in the persistent launch (lonres.hip.h) -- a
-    // chain's whole list in one launch with the table in the workgroups' registers: one chain alone runs faster that way
-    // (35 k steps/s at C4) than eight side by side on the launches per phase (29-32 k together).  A launch that gives up
-    // leaves its chain untouched: that chain and the ones behind it run on their own streams as below.
-    int first_threaded = 0;
-    if (T > 0 && lonres_usable(c)) {
-        for (int i = 0; i < C; ++i) {
-            gh_ctx *k = c->kids[(size_t)i];
-            int n_run = 0;
-            const size_t o = (size_t)i * (size_t)Tout;
-            const int rc = chain_run_lonres(c, k, T, L + (size_t)i * T, p0flat ? p0flat + (size_t)i * T * M : nullptr,
-                                            p0rows ? p0rows + (size_t)i * T : nullptr, us + (size_t)i * T, dt, 0, 0, accepted + o,
-                                            out5s + o * 5, x_out ? x_out + o * M : nullptr, &n_run);
-            if (rc == GH_RESIDENT_ABORTED) break;
-            if (rc != GH_OK) return rc;
-            first_threaded = i + 1;
-        }
-        if (first_threaded == C) return GH_OK;
-    }
-    auto work = [&](int i) {
-        gh_ctx *k = c->kids[(size_t)i];
-        if (hipSetDevice(k->device) != hipSuccess) {
-            rcs[(size_t)i] = GH_ERR_HIP;
-            return;
-        }
-        for (int t = 0; t < T; ++t) {
-            const size_t src = (size_t)i * T + t, dst = (size_t)i * Tout + t;
-            const double *p0 = p0flat ? p0flat + src * M : p0rows[src];
-            const double *pn = (t + 1 < T) ? (p0flat ? p0flat + (src + 1) * M : p0rows[src + 1]) : nullptr;
-            int acc = 0;
-            double o5[5];
-            int rc = chain_trajectory_impl(k, p0, dt, L[src], us[src], pn, &acc, o5);
-            if (rc == GH_OK && x_out && acc) rc = gh_chain_get_x(k, x_out + dst * M);
-            if (rc != GH_OK) {
-                rcs[(size_t)i] = rc;
-                return;
-            }
-            accepted[dst] = acc;
-            memcpy(out5s + dst * 5, o5, 5 * sizeof(double));
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int i = first_threaded + 1; i < C; ++i) pool.emplace_back(work, i);
-    work(first_threaded);
-    for (std::thread &th : pool) th.join();
-    for (int i = 0; i < C; ++i)
-        if (rcs[(size_t)i] != GH_OK) return fail(c, rcs[(size_t)i], "chain %d: %s", i, gh_last_error(c->kids[(size_t)i]));
-    return GH_OK;
-}
-
 int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const double *high)
 {
     if (!c || !x0s || !low || !high) return fail(c, GH_ERR_ARG, "gh_batch_init: null pointer");
@@ -1903,11 +1548,8 @@ int gh_batch_trajectory(gh_ctx *c, const double *p0s, double dt, const int *L, c
     b.run.live = false;
     HIPCHK(c, hipSetDevice(c->device));
     const int C = b.C;
-    int Lmax = 0;
-    for (int k = 0; k < C; ++k) {
+    for (int k = 0; k < C; ++k)
         if (L[k] < 1) return fail(c, GH_ERR_ARG, "gh_batch_trajectory: L must be >= 1");
-        Lmax = std::max(Lmax, L[k]);
-    }
     if (!c->kids.empty()) return kids_run(c, 1, L, nullptr, p0s, us, dt, accepted, out5s, nullptr, 1);
     if (c->rs.b_on && c->rs.ls.on) {
         for (int k = 0; k < C; ++k)
@@ -1920,127 +1562,16 @@ int gh_batch_trajectory(gh_ctx *c, const double *p0s, double dt, const int *L, c
         c->rs.ls.on = false;  // (nothing was in flight: the chains take turns from here on)
     }
     if (c->rs.b_on) {
-        gh_ctx::Resident &r = c->rs;
         int chain_of[CB];
         for (int k = 0; k < C; ++k) chain_of[k] = k;
-        ResLaunch q;
-        q.C = C;
-        q.K = C;
-        q.chain_of = chain_of;
-        q.L = L;
-        q.p0s = p0s;
-        q.us = us;
-        q.dt = dt;
-        q.x_dev = r.bx;
-        q.gcur_dev = r.bg;
-        q.ucur_dev = r.bu;
-        q.have_state = r.b_state ? 1 : 0;
-        int h_run[4] = {0, 0, 0, 0};
-        const int rc = resident_launch(c, q, accepted, out5s, h_run);
-        if (rc == GH_OK) {
-            r.b_state = true;
-            return GH_OK;
-        }
+        const int rc = batch_resident_turns(c, C, chain_of, L, p0s, us, dt, false, false, accepted, out5s);
         if (rc != GH_RESIDENT_ABORTED) return rc;
-        // the kernel gave up (its workgroups were not all resident): carry on with the MFMA batch
-        std::vector<double> xs((size_t)C * (size_t)c->M);
-        TRY(d2h(c, xs.data(), r.bx, xs.size()));
-        r.b_on = false;
-        TRY(batch_init_mfma(c, C, xs.data()));
     }
-    const int64_t n16 = c->M * CB;
-    TRY(batch_upload_rows(c, p0s, C, b.Pw[0]));
-    batch_sumsq_kernel<<<dim3((unsigned)b.n_pp0), dim3(256), 0, c->stream>>>(b.Pw[0], c->M, b.pp0_part);
-    const double *X_in = b.Xc, *Rt_in = b.Rtc, *GREG_in = b.GREGc;
-    int pin = 0, xo = 0;
-    for (int s = 0; s <= Lmax; ++s) {
-        BatchAdjArgs a{};
-        a.Gb = b.Gb;
-        a.G = c->G;
-        a.ld = c->ld;
-        a.M = c->M;
-        a.np = (int)(c->ld / 16);
-        a.Rt = Rt_in;
-        a.GREG = GREG_in;
-        a.X_in = X_in;
-        a.P_in = b.Pw[pin];
-        a.X_out = b.Xw[xo];
-        a.P_out = b.Pw[pin ^ 1];
-        a.low = c->low;
-        a.high = c->high;
-        a.G_out = nullptr;
-        a.pp_part = b.pp_part;
-        a.dt = dt;
-        a.n_waves = b.n_waves;
-        bool any_upd = false;
-        for (int k = 0; k < CB; ++k) {
-            a.phase[k] = PH_IDLE;
-            a.cu[k] = (s == 0) ? dt * 0.5 : dt;
-            a.cp[k] = dt * 0.5;
-            if (k < C) {
-                if (s < L[k]) {
-                    a.phase[k] = PH_UPD;
-                    any_upd = true;
-                } else if (s == L[k]) {
-                    a.phase[k] = PH_PFIN;
-                }
-            }
-        }
-        TRY(batch_launch_adjoint(c, a, any_upd));
-        if (any_upd) TRY(batch_evaluate(c, b.Xw[xo], b.Dw, b.GREGw, b.Rtw));
-        X_in = b.Xw[xo];
-        Rt_in = b.Rtw;
-        GREG_in = b.GREGw;
-        pin ^= 1;
-        xo ^= 1;
-    }
-    double *h = b.h;
-    HIPCHK(c, hipMemcpyAsync(h, b.scal, sizeof(double) * CB * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h + CB * 4, b.pp_part, sizeof(double) * (size_t)b.n_waves * CB, hipMemcpyDeviceToHost,
-                             c->stream));
-    HIPCHK(c, hipMemcpyAsync(h + CB * 4 + (size_t)b.n_waves * CB, b.pp0_part, sizeof(double) * (size_t)b.n_pp0 * CB,
-                             hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    {
-        // a fused team pass of this round gave up: nothing of the chains' current states was touched --
-        // run the round again (the fused form is off from here on)
-        bool failed = false;
-        TRY(mfb_fused_failed(c, &failed));
-        if (failed) return gh_batch_trajectory(c, p0s, dt, L, us, accepted, out5s);
-    }
-    unsigned mask = 0;
-    for (int k = 0; k < C; ++k) {
-        double pp1 = 0.0, pp0 = 0.0;
-        for (int w = 0; w < b.n_waves; ++w) pp1 += h[CB * 4 + (size_t)w * CB + k];
-        for (int w = 0; w < b.n_pp0; ++w) pp0 += h[CB * 4 + (size_t)(b.n_waves + w) * CB + k];
-        const double Unew[3] = {h[4 * k + 2], h[4 * k + 0], h[4 * k + 1]};
-        const double Hcur = 0.5 * pp0 + b.U[k][0];
-        const double Hnew = 0.5 * pp1 + Unew[0];
-        const bool acc = (Hnew < Hcur) || (us[k] < std::exp(-(Hnew - Hcur)));
-        if (acc) {
-            mask |= 1u << k;
-            b.U[k][0] = Unew[0];
-            b.U[k][1] = Unew[1];
-            b.U[k][2] = Unew[2];
-        }
-        accepted[k] = acc ? 1 : 0;
-        out5s[5 * k + 0] = b.U[k][0];
-        out5s[5 * k + 1] = b.U[k][1];
-        out5s[5 * k + 2] = b.U[k][2];
-        out5s[5 * k + 3] = Hcur;
-        out5s[5 * k + 4] = Hnew;
-    }
-    if (mask) {
-        const int64_t l16 = c->ld * CB;
-        batch_commit_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(X_in, b.Xc, n16, mask);
-        batch_commit_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(b.GREGw, b.GREGc, n16,
-                                                                                            mask);
-        batch_commit_kernel<<<dim3((unsigned)((l16 + 255) / 256)), dim3(256), 0, c->stream>>>(b.Dw, b.Dc, l16, mask);
-        batch_commit_rt_kernel<<<dim3((unsigned)((l16 + 255) / 256)), dim3(256), 0, c->stream>>>(b.Rtw, b.Rtc, l16,
-                                                                                               mask);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    // fp64-MFMA batch, a round in lock-step (host_batchrun.h).  A fused team pass of the round gave up: nothing of the
+    // chains' current states was touched -- run the round again (the fused form is off from here on)
+    bool failed = false;
+    TRY(batch_round_lockstep(c, p0s, dt, L, us, accepted, out5s, &failed));
+    if (failed) return gh_batch_trajectory(c, p0s, dt, L, us, accepted, out5s);
     return GH_OK;
 }
 
@@ -2092,7 +1623,6 @@ int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const
     if (c->rs.b_on) {
         // small problem: the chains take turns inside the resident chain kernel, trajectory t of
         // every chain before trajectory t + 1 of any (in front of them what the lock-step kernel left in flight)
-        gh_ctx::Resident &r = c->rs;
         const int P = (int)pre_ch.size(), K = P + C * T;
         std::vector<int> chain_of((size_t)K), Lk((size_t)K), acc((size_t)K), has_pre((size_t)C, 0);
         std::vector<double> pk((size_t)K * M), uk((size_t)K), o5((size_t)K * 5);
@@ -2111,23 +1641,9 @@ int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const
                 uk[k] = us[src];
                 memcpy(pk.data() + (size_t)k * M, p0s[src], M * sizeof(double));
             }
-        ResLaunch q;
-        q.C = C;
-        q.K = K;
-        q.chain_of = chain_of.data();
-        q.L = Lk.data();
-        q.p0s = pk.data();
-        q.us = uk.data();
-        q.dt = dt;
-        q.x_dev = r.bx;
-        q.gcur_dev = r.bg;
-        q.ucur_dev = r.bu;
-        q.have_state = r.b_state ? 1 : 0;
-        q.want_x = x_out != nullptr;
-        int h_run[4] = {0, 0, 0, 0};
-        const int rc = resident_launch(c, q, acc.data(), o5.data(), h_run);
+        const int rc = batch_resident_turns(c, K, chain_of.data(), Lk.data(), pk.data(), uk.data(), dt, x_out != nullptr, P > 0,
+                                            acc.data(), o5.data());
         if (rc == GH_OK) {
-            r.b_state = true;
             const int Tout = n_done ? T + 1 : T;
             for (int k = 0; k < K; ++k) {
                 const int ch = chain_of[k];
@@ -2136,7 +1652,7 @@ int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const
                 accepted[dst] = acc[k];
                 memcpy(out5s + (size_t)dst * 5, o5.data() + (size_t)k * 5, 5 * sizeof(double));
                 if (x_out && acc[k])
-                    HIPCHK(c, hipMemcpyAsync(x_out + (size_t)dst * M, r.xacc + (size_t)k * M, M * sizeof(double),
+                    HIPCHK(c, hipMemcpyAsync(x_out + (size_t)dst * M, c->rs.xacc + (size_t)k * M, M * sizeof(double),
                                              hipMemcpyDeviceToHost, c->stream));
             }
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2147,304 +1663,9 @@ int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const
             return GH_OK;
         }
         if (rc != GH_RESIDENT_ABORTED) return rc;
-        if (P > 0) return fail(c, GH_ERR_HIP, "gh_batch_run: the resident kernels timed out with trajectories in flight");
-        std::vector<double> xs((size_t)C * M);
-        TRY(d2h(c, xs.data(), r.bx, xs.size()));
-        r.b_on = false;
-        TRY(batch_init_mfma(c, C, xs.data()));
     }
-    // ---- fp64-MFMA batch, chains desynchronised: per sweep every chain is in its own phase.
-    // The scheduler's state (b.run) outlives the call when the caller asks for n_started / n_done:
-    // the call then ends as soon as a chain has nothing left to start, the others keep their
-    // trajectory in flight and carry on in the next call -- no sweep is ever spent waiting for
-    // the slowest chain.  Without them every chain's T trajectories are completed.
-    const bool carry = n_done != nullptr;
-    const bool use_spec = env_int("GRAVHMC_BATCH_SPEC", 1) != 0;
-    gh_ctx::Batch::Run &run = b.run;
-    const int64_t n16 = c->M * CB, l16 = c->ld * CB;
-    const unsigned all = (C >= 32) ? 0xffffffffu : ((1u << C) - 1u);
-    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-    double *h = b.h;
-    if (!c->copy_stream) {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-        HIPCHK(c, hipEventCreateWithFlags(&c->copy_ev, hipEventDisableTiming));
-    }
-    TRY(dalloc(c, &b.stage2, (size_t)n16));
-    TRY(dalloc(c, &b.GREGw2, (size_t)n16));
-    TRY(dalloc(c, &b.Dw2, (size_t)l16));
-    TRY(dalloc(c, &b.Rtw2, (size_t)l16));
-    TRY(dalloc(c, &b.scal2, CB * 4));
-    TRY(dalloc(c, &b.Pn, (size_t)n16));
-    TRY(dalloc(c, &b.pn0_part, (size_t)b.n_pp0 * CB));
-    // (matrix-free team pass: the momentum every trajectory in flight started with, so that the
-    // trajectories can be replayed if a pass gives up)
-    const bool keep_pstart = b.fus_on;
-    if (keep_pstart) TRY(dalloc(c, &b.Pstart, (size_t)n16));
-    // two working sets: a sweep reads set run.ws, the evaluation behind it writes the other one
-    double *GREGs[2] = {b.GREGw, b.GREGw2}, *Ds[2] = {b.Dw, b.Dw2}, *Rts[2] = {b.Rtw, b.Rtw2},
-           *scals[2] = {b.scal, b.scal2};
-    if (!run.live) {
-        // working state <- current state of every chain
-        run = gh_ctx::Batch::Run();
-        batch_commit_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.Xc, b.Xw[0], n16, all);
-        batch_commit_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.GREGc, GREGs[0], n16, all);
-        batch_commit_kernel<<<blocks(l16), dim3(256), 0, c->stream>>>(b.Dc, Ds[0], l16, all);
-        batch_commit_rt_kernel<<<blocks(l16), dim3(256), 0, c->stream>>>(b.Rtc, Rts[0], l16, all);
-        HIPCHK(c, hipGetLastError());
-        run.live = true;
-    } else if (run.dt != dt) {
-        for (int k = 0; k < C; ++k)
-            if (run.active[k]) return fail(c, GH_ERR_ARG, "gh_batch_run: dt changed while trajectories are in flight");
-    }
-    run.dt = dt;
-    std::vector<int> q_of((size_t)C, 0), done_of((size_t)C, 0);
-    // The momentum of the trajectory a chain starts next waits in one of the chain's two staging
-    // rows (b.stage / b.stage2, used alternately); it is sent on the copy stream while sweeps run.
-    std::vector<char> staged((size_t)C, 0);
-    auto stage_row = [&](int ch, int par) { return (par ? b.stage2 : b.stage) + (size_t)ch * M; };
-    auto upload = [&](int ch, hipStream_t st) -> int {  // list element q_of[ch] -> the chain's free row
-        run.par[ch] ^= 1;
-        HIPCHK(c, hipMemcpyAsync(stage_row(ch, run.par[ch]), p0s[(size_t)ch * T + q_of[ch]],
-                                 M * sizeof(double), hipMemcpyHostToDevice, st));
-        staged[ch] = 1;
-        return GH_OK;
-    };
-    // staged rows of the chains in `mask` -> their columns of the interleaved array dst
-    auto scatter_staged = [&](unsigned mask, double *dst) {
-        unsigned even = 0, odd = 0;
-        for (int ch = 0; ch < C; ++ch)
-            if (mask & (1u << ch)) (run.par[ch] ? odd : even) |= 1u << ch;
-        if (even) batch_scatter_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.stage, c->M, even, dst);
-        if (odd) batch_scatter_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.stage2, c->M, odd, dst);
-    };
-    auto wait_copies = [&]() -> int {  // (momenta sent ahead on the copy stream: wait for its last copy)
-        HIPCHK(c, hipEventRecord(c->copy_ev, c->copy_stream));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->copy_ev, 0));
-        return GH_OK;
-    };
-    std::vector<int> pending;  // chains whose next momentum is still to be sent ahead
-    for (int ch = 0; ch < C; ++ch) {
-        if (T == 0) break;
-        if (!run.active[ch])
-            TRY(upload(ch, c->stream));
-        else
-            pending.push_back(ch);
-    }
-    // a chain takes the trajectory at the head of its list: bookkeeping shared by both kinds of start
-    auto take_next = [&](int ch, double pp0_val, int s_first) {
-        const size_t slot = (size_t)ch * T + q_of[ch];
-        run.pp0[ch] = pp0_val;
-        run.L_cur[ch] = L[slot];
-        run.u_cur[ch] = us[slot];
-        run.s_of[ch] = s_first;
-        run.active[ch] = true;
-        q_of[ch] += 1;
-        staged[ch] = 0;
-        // the one after goes ahead once the next sweep has been queued (the staging copy blocks
-        // this thread, not the GPU)
-        if (q_of[ch] < T) pending.push_back(ch);
-    };
-    // working state <- current state, momenta of the chains in `mask` <- their next trajectory
-    auto start_chains = [&](unsigned mask) -> int {
-        TRY(wait_copies());
-        for (int ch = 0; ch < C; ++ch)
-            if ((mask & (1u << ch)) && !staged[ch]) TRY(upload(ch, c->stream));
-        scatter_staged(mask, b.Pw[run.pin]);
-        if (keep_pstart) batch_commit_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.Pw[run.pin], b.Pstart, n16, mask);
-        batch_commit_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.Xc, b.Xw[run.xi], n16, mask);
-        batch_commit_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.GREGc, GREGs[run.ws], n16, mask);
-        batch_commit_kernel<<<blocks(l16), dim3(256), 0, c->stream>>>(b.Dc, Ds[run.ws], l16, mask);
-        batch_commit_rt_kernel<<<blocks(l16), dim3(256), 0, c->stream>>>(b.Rtc, Rts[run.ws], l16, mask);
-        batch_sumsq_kernel<<<dim3((unsigned)b.n_pp0), dim3(256), 0, c->stream>>>(b.Pw[run.pin], c->M, b.pp0_part);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h + CB * 4 + (size_t)b.n_waves * CB, b.pp0_part,
-                                 sizeof(double) * (size_t)b.n_pp0 * CB, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int ch = 0; ch < C; ++ch)
-            if (mask & (1u << ch)) {
-                double s = 0.0;
-                for (int w = 0; w < b.n_pp0; ++w) s += h[CB * 4 + (size_t)(b.n_waves + w) * CB + ch];
-                take_next(ch, s, 0);
-            }
-        return GH_OK;
-    };
-    const size_t h_pn0 = CB * 4 + (size_t)(b.n_waves + b.n_pp0) * CB;  // (b.h is sized for it below)
-    for (;;) {
-        unsigned starters = 0;
-        bool starved = false, any_active = false;
-        for (int k = 0; k < C; ++k) {
-            if (run.active[k]) {
-                any_active = true;
-            } else if (q_of[k] < T) {
-                starters |= 1u << k;
-                any_active = true;
-            } else {
-                starved = true;
-            }
-        }
-        if (carry ? (T == 0 ? !any_active : starved) : !any_active) break;
-        if (starters) TRY(start_chains(starters));
-        const int rs = run.ws, wset = rs ^ 1;
-        BatchAdjArgs a{};
-        a.Gb = b.Gb;
-        a.G = c->G;
-        a.ld = c->ld;
-        a.M = c->M;
-        a.np = (int)(c->ld / 16);
-        a.Rt = Rts[rs];
-        a.GREG = GREGs[rs];
-        a.X_in = b.Xw[run.xi];
-        a.P_in = b.Pw[run.pin];
-        a.Pn = b.Pn;
-        a.X_out = b.Xw[run.xi ^ 1];
-        a.P_out = b.Pw[run.pin ^ 1];
-        a.low = c->low;
-        a.high = c->high;
-        a.G_out = nullptr;
-        a.pp_part = b.pp_part;
-        a.dt = dt;
-        a.n_waves = b.n_waves;
-        bool any_upd = false;
-        unsigned fin = 0, spec = 0;
-        for (int k = 0; k < CB; ++k) {
-            a.phase[k] = PH_IDLE;
-            a.cu[k] = dt;
-            a.cp[k] = dt * 0.5;
-            if (k < C && run.active[k]) {
-                if (run.s_of[k] < run.L_cur[k]) {
-                    a.phase[k] = PH_UPD;
-                    a.cu[k] = (run.s_of[k] == 0) ? dt * 0.5 : dt;
-                    any_upd = true;
-                } else {
-                    fin |= 1u << k;
-                    // the chain's next trajectory is known: its first step rides on this sweep
-                    if (use_spec && q_of[k] < T) {
-                        a.phase[k] = PH_PFIN_SPEC;
-                        a.cu[k] = dt * 0.5;
-                        spec |= 1u << k;
-                        any_upd = true;
-                    } else {
-                        a.phase[k] = PH_PFIN;
-                    }
-                }
-            }
-        }
-        if (spec) {
-            TRY(wait_copies());
-            for (int ch = 0; ch < C; ++ch)
-                if ((spec & (1u << ch)) && !staged[ch]) TRY(upload(ch, c->stream));
-            scatter_staged(spec, b.Pn);
-            batch_sumsq_kernel<<<dim3((unsigned)b.n_pp0), dim3(256), 0, c->stream>>>(b.Pn, c->M, b.pn0_part);
-        }
-        TRY(batch_launch_adjoint(c, a, any_upd));
-        if (any_upd) {
-            TRY(batch_evaluate(c, b.Xw[run.xi ^ 1], Ds[wset], GREGs[wset], Rts[wset], scals[wset]));
-            run.ws = wset;
-        }
-        for (int ch : pending) TRY(upload(ch, c->copy_stream));
-        pending.clear();
-        const int x_prop = run.xi;  // the sweep's input: the proposals of the chains that finished
-        run.xi ^= 1;
-        run.pin ^= 1;
-        for (int k = 0; k < C; ++k)
-            if (run.active[k]) run.s_of[k] += 1;
-        if (!fin) continue;
-        // the chains that took their final half step in this sweep: Metropolis test.  Their
-        // proposals' potentials, gradients and residuals are in the set the sweep READ.
-        HIPCHK(c, hipMemcpyAsync(h, scals[rs], sizeof(double) * CB * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(h + CB * 4, b.pp_part, sizeof(double) * (size_t)b.n_waves * CB,
-                                 hipMemcpyDeviceToHost, c->stream));
-        if (spec)
-            HIPCHK(c, hipMemcpyAsync(h + h_pn0, b.pn0_part, sizeof(double) * (size_t)b.n_pp0 * CB,
-                                     hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        {
-            // a team pass since the last look gave up: what the trajectories in flight accumulated since is
-            // void, the chains' current states are intact (nothing is committed before this point) -- every
-            // active chain starts its trajectory again from its current state and its own momentum, on the
-            // two-pass kernels (which need no co-residency)
-            bool failed = false;
-            TRY(mfb_fused_failed(c, &failed));
-            if (failed) {
-                if (!b.Pstart) return fail(c, GH_ERR_HIP, "gh_batch_run: the fused matrix-free batch pass timed out");
-                unsigned act = 0;
-                for (int k = 0; k < C; ++k)
-                    if (run.active[k]) {
-                        act |= 1u << k;
-                        run.s_of[k] = 0;
-                    }
-                batch_commit_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.Pstart, b.Pw[run.pin], n16, act);
-                batch_commit_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.Xc, b.Xw[run.xi], n16, act);
-                batch_commit_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.GREGc, GREGs[run.ws], n16, act);
-                batch_commit_kernel<<<blocks(l16), dim3(256), 0, c->stream>>>(b.Dc, Ds[run.ws], l16, act);
-                batch_commit_rt_kernel<<<blocks(l16), dim3(256), 0, c->stream>>>(b.Rtc, Rts[run.ws], l16, act);
-                HIPCHK(c, hipGetLastError());
-                continue;
-            }
-        }
-        unsigned mask = 0;
-        // result slots per chain: T, plus one in carry-over mode for the trajectory that came in flight
-        const int Tout = carry ? T + 1 : T;
-        for (int k = 0; k < C; ++k) {
-            if (!(fin & (1u << k))) continue;
-            const size_t slot = (size_t)k * Tout + done_of[k];
-            double pp1 = 0.0;
-            for (int w = 0; w < b.n_waves; ++w) pp1 += h[CB * 4 + (size_t)w * CB + k];
-            const double Unew[3] = {h[4 * k + 2], h[4 * k + 0], h[4 * k + 1]};
-            const double Hcur = 0.5 * run.pp0[k] + b.U[k][0];
-            const double Hnew = 0.5 * pp1 + Unew[0];
-            const bool acc = (Hnew < Hcur) || (run.u_cur[k] < std::exp(-(Hnew - Hcur)));
-            if (acc) {
-                mask |= 1u << k;
-                b.U[k][0] = Unew[0];
-                b.U[k][1] = Unew[1];
-                b.U[k][2] = Unew[2];
-            }
-            accepted[slot] = acc ? 1 : 0;
-            out5s[5 * slot + 0] = b.U[k][0];
-            out5s[5 * slot + 1] = b.U[k][1];
-            out5s[5 * slot + 2] = b.U[k][2];
-            out5s[5 * slot + 3] = Hcur;
-            out5s[5 * slot + 4] = Hnew;
-        }
-        if (mask) {
-            batch_commit_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.Xw[x_prop], b.Xc, n16, mask);
-            batch_commit_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(GREGs[rs], b.GREGc, n16, mask);
-            batch_commit_kernel<<<blocks(l16), dim3(256), 0, c->stream>>>(Ds[rs], b.Dc, l16, mask);
-            batch_commit_rt_kernel<<<blocks(l16), dim3(256), 0, c->stream>>>(Rts[rs], b.Rtc, l16, mask);
-            HIPCHK(c, hipGetLastError());
-            if (x_out)
-                for (int k = 0; k < C; ++k)
-                    if (mask & (1u << k)) {
-                        batch_extract_kernel<<<blocks(c->M), dim3(256), 0, c->stream>>>(b.Xc, k, c->M, c->tmpM);
-                        TRY(d2h(c, x_out + ((size_t)k * Tout + done_of[k]) * M, c->tmpM, M));
-                    }
-        }
-        for (int k = 0; k < C; ++k)
-            if (fin & (1u << k)) {
-                run.active[k] = false;
-                done_of[k] += 1;
-                if ((spec & mask) & (1u << k)) {
-                    // accepted, and the first step of the next trajectory has been taken: carry on
-                    double s = 0.0;
-                    for (int w = 0; w < b.n_pp0; ++w) s += h[h_pn0 + (size_t)w * CB + k];
-                    take_next(k, s, 1);
-                    if (keep_pstart) batch_commit_kernel<<<blocks(n16), dim3(256), 0, c->stream>>>(b.Pn, b.Pstart, n16, 1u << k);
-                }
-            }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-    bool any_active = false;
-    for (int k = 0; k < C; ++k) {
-        if (n_done) {
-            n_started[k] = q_of[k];
-            n_done[k] = done_of[k];
-        }
-        any_active = any_active || run.active[k];
-    }
-    if (!any_active) run.live = false;  // (the working buffers are rebuilt from the current state next time)
-    return GH_OK;
+    // fp64-MFMA batch, the chains desynchronised (host_batchrun.h)
+    return BatchRun{c, T, L, p0s, us, dt, accepted, out5s, x_out, n_done != nullptr}.go(n_started, n_done);
 }
 
 // Diagnostic (not in the public header): accumulated phase times of the shift-invariant pass

@@ -1,8 +1,6 @@
-// libgravhmc host side: buffers and evaluation of the fp64-MFMA chain batch (batch.hip.h).
-// Included once by gravhmc.hip.
+// libgravhmc host side: buffers, evaluation and the steps of the fp64-MFMA chain batch (batch.hip.h); its two
+// schedules are in host_batchrun.h.  Included once by gravhmc.hip.
 #pragma once
-
-// --------------------------------------------------------------- batched chains (MFMA)
 
 // ------------------------------------------------ batched chains on the matrix-free kernel (mfbatch.hip.h)
 
@@ -323,8 +321,23 @@ static int bteam_plan(gh_ctx *c)
     return GH_OK;
 }
 
-static int batch_time_begin(gh_ctx *c, bool &timed);
-static int batch_time_end(gh_ctx *c, bool timed);
+static int batch_time_begin(gh_ctx *c, bool &timed)
+{
+    timed = c->prof && c->ev_used + 2 <= c->ev.size();
+    if (timed) HIPCHK(c, hipEventRecord(c->ev[c->ev_used], c->stream));
+    return GH_OK;
+}
+
+static int batch_time_end(gh_ctx *c, bool timed)
+{
+    if (timed) {
+        HIPCHK(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
+        c->ev_bytes[c->ev_used / 2] = c->N * c->M * (int64_t)sizeof(double);
+        c->ev_used += 2;
+    }
+    c->bt.sweeps += 1;
+    return GH_OK;
+}
 
 // forward of all chains at X into the slab (ranges of column tiles, plus the near-field block)
 static int mfb_forward(gh_ctx *c, const double *X)
@@ -499,7 +512,7 @@ static int batch_alloc(gh_ctx *c)
     TRY(dalloc(c, &b.pp_part, (size_t)b.n_waves * CB));
     b.n_pp0 = (int)std::min<int64_t>(512, (c->M + 15) / 16);
     TRY(dalloc(c, &b.pp0_part, (size_t)b.n_pp0 * CB));
-    HIPCHK(c, hipHostMalloc((void **)&b.h, sizeof(double) * (size_t)(CB * 4 + (b.n_waves + 2 * b.n_pp0) * CB)));
+    HIPCHK(c, hipHostMalloc((void **)&b.h, sizeof(double) * b.h_size()));
     // (the two-pass batch's second copy of G: not with the team pass -- if that ever gives up, the copy is made then)
     if (!b.fus_on) TRY(batch_relayout(c));
     TRY(dalloc(c, &c->tmpM, (size_t)c->M));
@@ -507,24 +520,6 @@ static int batch_alloc(gh_ctx *c)
     TRY(dalloc(c, &c->high, (size_t)c->M));
     if (!c->mwapr) TRY(dalloc(c, &c->mwapr, (size_t)c->M));
     if (!c->wm2) TRY(dalloc(c, &c->wm2, (size_t)c->M));
-    return GH_OK;
-}
-
-static int batch_time_begin(gh_ctx *c, bool &timed)
-{
-    timed = c->prof && c->ev_used + 2 <= c->ev.size();
-    if (timed) HIPCHK(c, hipEventRecord(c->ev[c->ev_used], c->stream));
-    return GH_OK;
-}
-
-static int batch_time_end(gh_ctx *c, bool timed)
-{
-    if (timed) {
-        HIPCHK(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-        c->ev_bytes[c->ev_used / 2] = c->N * c->M * (int64_t)sizeof(double);
-        c->ev_used += 2;
-    }
-    c->bt.sweeps += 1;
     return GH_OK;
 }
 
@@ -643,4 +638,91 @@ static int batch_init_mfma(gh_ctx *c, int C, const double *x0s)
     }
     b.ready = true;
     return GH_OK;
+}
+
+static dim3 blocks256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+// columns of the chains in `mask` of an M x 16 array: src -> dst
+static void batch_copy_cols(gh_ctx *c, const double *src, double *dst, unsigned mask)
+{
+    const int64_t n16 = c->M * CB;
+    batch_commit_kernel<<<blocks256(n16), dim3(256), 0, c->stream>>>(src, dst, n16, mask);
+}
+
+// state of the chains in `mask`: set `from` -> set `to` (enqueued; the caller looks at hipGetLastError)
+static void batch_copy_state(gh_ctx *c, const BatchSet &from, const BatchSet &to, unsigned mask)
+{
+    const int64_t l16 = c->ld * CB;
+    batch_copy_cols(c, from.X, to.X, mask);
+    batch_copy_cols(c, from.GREG, to.GREG, mask);
+    batch_commit_kernel<<<blocks256(l16), dim3(256), 0, c->stream>>>(from.D, to.D, l16, mask);
+    batch_commit_rt_kernel<<<blocks256(l16), dim3(256), 0, c->stream>>>(from.Rt, to.Rt, l16, mask);
+}
+
+// The arguments of one sweep that reads the state `in` and the momenta P_in (Pn: the next trajectories', for
+// PH_PFIN_SPEC, or nullptr).  Per chain slot: its phase, and whether the step is the first of its trajectory
+// (the momentum then moves half a step; so it does on the speculative first step of PH_PFIN_SPEC).
+static BatchAdjArgs batch_sweep_args(gh_ctx *c, const BatchSet &in, const double *P_in, const double *Pn, double *X_out,
+                                     double *P_out, double dt, const int phase[CB], const bool first[CB])
+{
+    gh_ctx::Batch &b = c->bt;
+    BatchAdjArgs a{};
+    a.Gb = b.Gb;
+    a.G = c->G;
+    a.ld = c->ld;
+    a.M = c->M;
+    a.np = (int)(c->ld / 16);
+    a.Rt = in.Rt;
+    a.GREG = in.GREG;
+    a.X_in = in.X;
+    a.P_in = P_in;
+    a.Pn = Pn;
+    a.X_out = X_out;
+    a.P_out = P_out;
+    a.low = c->low;
+    a.high = c->high;
+    a.G_out = nullptr;
+    a.pp_part = b.pp_part;
+    a.dt = dt;
+    a.n_waves = b.n_waves;
+    for (int k = 0; k < CB; ++k) {
+        a.phase[k] = phase[k];
+        a.cu[k] = (first[k] || phase[k] == PH_PFIN_SPEC) ? dt * 0.5 : dt;
+        a.cp[k] = dt * 0.5;
+    }
+    return a;
+}
+
+// Small problem: the chains take turns inside the resident chain kernel (host_resident.h), K trajectories in
+// list order; results in list order, the accepted models in c->rs.xacc if want_x.  GH_RESIDENT_ABORTED: the
+// kernel gave up (its workgroups were not all resident) and the chains carry on as an MFMA batch from their
+// states -- unless trajectories a lock-step launch had in flight were in front of the list (replayed).
+static int batch_resident_turns(gh_ctx *c, int K, const int *chain_of, const int *L, const double *p0s, const double *us,
+                                double dt, bool want_x, bool replayed, int *accepted, double *out5s)
+{
+    gh_ctx::Resident &r = c->rs;
+    const int C = c->bt.C;
+    ResLaunch q;
+    q.C = C;
+    q.K = K;
+    q.chain_of = chain_of;
+    q.L = L;
+    q.p0s = p0s;
+    q.us = us;
+    q.dt = dt;
+    q.x_dev = r.bx;
+    q.gcur_dev = r.bg;
+    q.ucur_dev = r.bu;
+    q.have_state = r.b_state ? 1 : 0;
+    q.want_x = want_x;
+    int h_run[4] = {0, 0, 0, 0};
+    const int rc = resident_launch(c, q, accepted, out5s, h_run);
+    if (rc == GH_OK) r.b_state = true;
+    if (rc != GH_RESIDENT_ABORTED) return rc;
+    if (replayed) return fail(c, GH_ERR_HIP, "gh_batch_run: the resident kernels timed out with trajectories in flight");
+    std::vector<double> xs((size_t)C * (size_t)c->M);
+    TRY(d2h(c, xs.data(), r.bx, xs.size()));
+    r.b_on = false;
+    TRY(batch_init_mfma(c, C, xs.data()));
+    return GH_RESIDENT_ABORTED;
 }

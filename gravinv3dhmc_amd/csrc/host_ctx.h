@@ -24,6 +24,9 @@ struct ExchangeGuard {
     int aborts = 0;                        // launches that gave up
 };
 
+// One state set of the MFMA batch (chain-interleaved): models, alpha * grad R, synthetic data, residuals.
+struct BatchSet { double *X, *GREG, *D, *Rt; };
+
 struct gh_ctx {
     int device = 0;
     int64_t N = 0, M = 0, ld = 0;
@@ -245,7 +248,7 @@ struct gh_ctx {
         double *Pstart = nullptr;      // M x 16: the momentum each trajectory in flight started with (gh_batch_run)
         int64_t fus_launches = 0;
         const double *fus_fwd_of = nullptr;  // the X whose forward partials the last fused launch left in the slab
-        double *h = nullptr;      // pinned
+        double *h = nullptr;      // pinned read-back buffer, laid out by h_*() below
         int n_colblocks = 0, n_regblocks = 0, n_waves = 0, n_pp0 = 0;
         int64_t cols_per_block = 0;
         double U[CB][3];
@@ -260,6 +263,22 @@ struct gh_ctx {
             int xi = 0, pin = 0, ws = 0;  // ws: working set the next sweep reads
             double dt = 0.0;
         } run;
+        // the state sets: the chains' current one, and working set ws (0 / 1) with the models in Xw[xi]
+        BatchSet cur() const { return {Xc, GREGc, Dc, Rtc}; }
+        BatchSet work(int xi, int ws) const { return {Xw[xi], ws ? GREGw2 : GREGw, ws ? Dw2 : Dw, ws ? Rtw2 : Rtw}; }
+        double *scal_of(int ws) const { return ws ? scal2 : scal; }
+        // h: 4 scalars per chain slot, then rows of CB partial sums of |p|^2 -- n_waves of the final half step
+        // (pp_part), n_pp0 of the initial momenta (pp0_part), n_pp0 of the next trajectories' momenta (pn0_part)
+        size_t h_pp() const { return (size_t)CB * 4; }
+        size_t h_pp0() const { return h_pp() + (size_t)n_waves * CB; }
+        size_t h_pn0() const { return h_pp0() + (size_t)n_pp0 * CB; }
+        size_t h_size() const { return h_pn0() + (size_t)n_pp0 * CB; }
+        double h_sum(size_t region, int rows, int k) const  // chain k's sum over the rows of a region, in row order
+        {
+            double s = 0.0;
+            for (int w = 0; w < rows; ++w) s += h[region + (size_t)w * CB + k];
+            return s;
+        }
     } bt;
 
     // resident chain kernel (resident.hip.h): G held in LDS across a whole batch of trajectories
@@ -435,6 +454,23 @@ static bool xg_give_up(ExchangeGuard &g, int strikes)
 {
     g.dirty = true;
     return ++g.aborts >= strikes;
+}
+
+// The Metropolis test of a finished trajectory (hmc.py:158-177).  pp0 / pp1: |p|^2 at its start / end; scal: the
+// proposal's scalars as the finishing kernels leave them (data, regulariser, total); U: the chain's current
+// potentials (total, data, regulariser), replaced on acceptance.  out5: U of the state the chain is left in, H of
+// the current state and of the proposal.
+static bool metropolis_step(double pp0, double pp1, const double *scal, double u, double U[3], double out5[5])
+{
+    const double Unew[3] = {scal[2], scal[0], scal[1]};
+    const double Hcur = 0.5 * pp0 + U[0];
+    const double Hnew = 0.5 * pp1 + Unew[0];
+    const bool acc = (Hnew < Hcur) || (u < std::exp(-(Hnew - Hcur)));
+    if (acc) memcpy(U, Unew, sizeof Unew);
+    memcpy(out5, U, sizeof Unew);
+    out5[3] = Hcur;
+    out5[4] = Hnew;
+    return acc;
 }
 
 static int h2d(gh_ctx *c, double *dst, const double *src, size_t n)

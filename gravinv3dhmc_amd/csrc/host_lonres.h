@@ -1,5 +1,5 @@
 // libgravhmc host side: planning and launching the persistent harmonic pass of the shift-invariant store
-// (lonres.hip.h).  Included once by gravhmc.hip.
+// (lonres.hip.h), and the batch of chains on that store.  Included once by gravhmc.hip.
 #pragma once
 
 typedef void (*lonres_fn_t)(LonResArgs);
@@ -264,5 +264,135 @@ static int chain_run_lonres(gh_ctx *c, gh_ctx *st, int K, const int *L, const do
     st->U_cur[2] = h_u[2];
     st->spec_valid = st->pn_valid = false;
     st->st_stale = true;
+    return GH_OK;
+}
+
+static int chain_trajectory_impl(gh_ctx *, const double *, double, int, double, const double *, int *, double[5]);  // host_chain.h
+
+// ---- a batch of chains on the shift-invariant store (BASELINE configs[3]: "8 chains"; the reference runs them
+// as MPI ranks, example/global/run_main.sh:16, each with its own 4.25 GB kernel).  A step of ONE chain on the
+// table keeps a fraction of the chip busy for ~60 us, most of it latency: the chains are C light contexts
+// that share the parent's tables (T, T^: read-only) and problem vectors, each with its own stream, chain
+// state and work buffers, driven by one host thread each -- their passes overlap on the GPU.
+static int kids_make(gh_ctx *c, int C, const double *x0s, const double *low, const double *high)
+{
+    for (gh_ctx *k : c->kids) gh_destroy(k);
+    c->kids.clear();
+    for (int i = 0; i < C; ++i) {
+        gh_ctx *k = nullptr;
+        const int rc0 = gh_create(&k, c->device, c->N, c->M);
+        if (rc0 != GH_OK) return fail(c, rc0, "gh_batch_init: %s", gh_last_error(nullptr));
+        c->kids.push_back(k);
+        k->cell_kind = c->cell_kind;
+        k->ratio = c->ratio;
+        for (int q = 0; q < 3; ++q) k->tf_dir[q] = c->tf_dir[q];
+        k->tf_dir_d = c->tf_dir_d;
+        k->comp = c->comp;  // (GH_CELL_TESSEROID_COMP never gets here: the shift-invariant store refuses it)
+        k->have_obs = k->have_cells = k->have_G = true;
+        k->mf = true;
+        k->weighted = c->weighted;
+        k->wm = c->wm;
+        k->wm2 = c->wm2;
+        k->dobs_c = c->dobs_c;
+        k->gfix = c->gfix;
+        k->gfix_sum = c->gfix_sum;
+        k->mwapr = c->mwapr;
+        k->have_data = c->have_data;
+        k->have_fix = c->have_fix;
+        k->have_reg = c->have_reg;
+        k->reg_kind = c->reg_kind;
+        for (int q = 0; q < 3; ++q) k->shape[q] = c->shape[q];
+        k->alpha = c->alpha;
+        k->beta = c->beta;
+        k->ls = new LonSymHost(*c->ls);  // (the tables are the parent's; the pass's work buffers are its own)
+        k->ls->Rhat = k->ls->Dpart = nullptr;
+        k->ls->res = LonSymHost::Res();
+        k->ls->res.state = -1;  // (the persistent pass takes every CU: not for chains that share the GPU)
+        k->ls->dbg = nullptr;
+        k->ls->csum = nullptr;
+        k->ls->epi = ExchangeGuard();
+        k->ls->rhat_of = nullptr;
+        k->ls->post_pending = false;
+        if (k->ls->harm) {
+            int rc = dalloc(k, &k->ls->Rhat, (size_t)k->ls->na * (size_t)k->ls->nf);
+            if (rc == GH_OK) rc = dalloc(k, &k->ls->Dpart, (size_t)k->ls->hgrid * (size_t)k->ls->na * (size_t)k->ls->nf);
+            if (rc == GH_OK && k->ls->fused) rc = dalloc(k, &k->ls->csum, 2 * (size_t)k->ls->na);
+            if (rc == GH_OK && k->ls->fused)
+                rc = xg_alloc(k, k->ls->epi, {{k->ls->csum, sizeof(unsigned long long) * 2 * (size_t)k->ls->na}});
+            if (rc != GH_OK) return fail(c, rc, "gh_batch_init: %s", gh_last_error(k));
+        }
+        if (k->ls->wide) {
+            k->ls->Xhat = nullptr;
+            int rc = dalloc(k, &k->ls->Rhat, (size_t)k->ls->na * (size_t)k->ls->nfp);
+            if (rc == GH_OK) rc = dalloc(k, &k->ls->Xhat, (size_t)k->ls->nc * (size_t)k->ls->nf);
+            if (rc == GH_OK) rc = dalloc(k, &k->ls->Dpart, (size_t)k->ls->wparts * (k->ls->wmirror ? 2 : 1) * (size_t)k->ls->na * (size_t)k->ls->nfp);
+            if (rc != GH_OK) return fail(c, rc, "gh_batch_init: %s", gh_last_error(k));
+        }
+        int rc = configure_mf(k);
+        if (rc == GH_OK) rc = dalloc(k, &k->mf_stats, 1);
+        if (rc == GH_OK) rc = gh_chain_init(k, x0s + (size_t)i * (size_t)c->M, low, high);
+        if (rc != GH_OK) return fail(c, rc, "gh_batch_init (chain %d): %s", i, gh_last_error(k));
+    }
+    c->bt.C = C;
+    c->bt.ready = true;
+    c->bt.run = gh_ctx::Batch::Run();
+    return GH_OK;
+}
+
+// T trajectories of every chain (lists chain-major), each chain on its own thread and stream; results of
+// chain i in slots i * Tout + t.  Nothing stays in flight.
+static int kids_run(gh_ctx *c, int T, const int *L, const double *const *p0rows, const double *p0flat, const double *us,
+                    double dt, int *accepted, double *out5s, double *x_out, int Tout)
+{
+    const int C = (int)c->kids.size();
+    const size_t M = (size_t)c->M;
+    std::vector<int> rcs((size_t)C, GH_OK);
+    // On the harmonic store the chains TAKE TURNS in the persistent launch (lonres.hip.h) -- a
+    // chain's whole list in one launch with the table in the workgroups' registers: one chain alone runs faster that way
+    // (35 k steps/s at C4) than eight side by side on the launches per phase (29-32 k together).  A launch that gives up
+    // leaves its chain untouched: that chain and the ones behind it run on their own streams as below.
+    int first_threaded = 0;
+    if (T > 0 && lonres_usable(c)) {
+        for (int i = 0; i < C; ++i) {
+            gh_ctx *k = c->kids[(size_t)i];
+            int n_run = 0;
+            const size_t o = (size_t)i * (size_t)Tout;
+            const int rc = chain_run_lonres(c, k, T, L + (size_t)i * T, p0flat ? p0flat + (size_t)i * T * M : nullptr,
+                                            p0rows ? p0rows + (size_t)i * T : nullptr, us + (size_t)i * T, dt, 0, 0, accepted + o,
+                                            out5s + o * 5, x_out ? x_out + o * M : nullptr, &n_run);
+            if (rc == GH_RESIDENT_ABORTED) break;
+            if (rc != GH_OK) return rc;
+            first_threaded = i + 1;
+        }
+        if (first_threaded == C) return GH_OK;
+    }
+    auto work = [&](int i) {
+        gh_ctx *k = c->kids[(size_t)i];
+        if (hipSetDevice(k->device) != hipSuccess) {
+            rcs[(size_t)i] = GH_ERR_HIP;
+            return;
+        }
+        for (int t = 0; t < T; ++t) {
+            const size_t src = (size_t)i * T + t, dst = (size_t)i * Tout + t;
+            const double *p0 = p0flat ? p0flat + src * M : p0rows[src];
+            const double *pn = (t + 1 < T) ? (p0flat ? p0flat + (src + 1) * M : p0rows[src + 1]) : nullptr;
+            int acc = 0;
+            double o5[5];
+            int rc = chain_trajectory_impl(k, p0, dt, L[src], us[src], pn, &acc, o5);
+            if (rc == GH_OK && x_out && acc) rc = gh_chain_get_x(k, x_out + dst * M);
+            if (rc != GH_OK) {
+                rcs[(size_t)i] = rc;
+                return;
+            }
+            accepted[dst] = acc;
+            memcpy(out5s + dst * 5, o5, 5 * sizeof(double));
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int i = first_threaded + 1; i < C; ++i) pool.emplace_back(work, i);
+    work(first_threaded);
+    for (std::thread &th : pool) th.join();
+    for (int i = 0; i < C; ++i)
+        if (rcs[(size_t)i] != GH_OK) return fail(c, rcs[(size_t)i], "chain %d: %s", i, gh_last_error(c->kids[(size_t)i]));
     return GH_OK;
 }
