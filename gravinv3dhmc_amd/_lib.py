@@ -15,6 +15,9 @@ LIB_PATH = os.environ.get("GRAVHMC_LIB") or os.path.join(_HERE, "libgravhmc.so")
 GH_OK, GH_ERR_ARG, GH_ERR_HIP, GH_ERR_NOMEM, GH_ERR_OVERFLOW, GH_ERR_UNSUPPORTED, GH_ERR_COMM = \
     0, -1, -2, -3, -4, -5, -6
 CELL_PRISM, CELL_TESSEROID, CELL_PRISM_TF, CELL_PRISM_COMP, CELL_TESSEROID_COMP, CELL_PRISM_JOINT = 0, 1, 2, 3, 4, 5
+CELL_PRISM_MULTI = 6
+#: components a CELL_PRISM_MULTI context stacks at most (GH_MULTI_MAX)
+MULTI_MAX = 11
 #: the gravity fields of prisms and tesseroids (GH_COMP_*, gh_set_cells_prism / gh_set_cells_tess)
 COMP_POTENTIAL, COMP_GEOID, COMP_GX, COMP_GY, COMP_GZ, COMP_GXX, COMP_GXY, COMP_GXZ, COMP_GYY, COMP_GYZ, COMP_GZZ = \
     range(11)
@@ -37,6 +40,8 @@ PROTOTYPES = {
     "gh_set_cells": (C.c_int, [_ctx, _dp, C.c_int, C.c_double]),
     "gh_set_cells_tf": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
     "gh_set_cells_joint": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
+    "gh_set_cells_multi": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp]),
+    "gh_multi_info": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp, _dp]),
     "gh_joint_std": (C.c_int, [_ctx, _dp]),
     "gh_joint_layout": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gh_set_cross_gradient": (C.c_int, [_ctx, C.c_double, _dp, C.POINTER(C.c_int), C.c_double, C.c_double, _dp]),

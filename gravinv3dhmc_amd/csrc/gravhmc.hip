@@ -43,6 +43,7 @@ static_assert(COMP_POTENTIAL == GH_COMP_POTENTIAL && COMP_GEOID == GH_COMP_GEOID
                   COMP_GXZ == GH_COMP_GXZ && COMP_GYY == GH_COMP_GYY && COMP_GYZ == GH_COMP_GYZ &&
                   COMP_GZZ == GH_COMP_GZZ,
               "the kernels' component numbers are the C ABI's GH_COMP_*");
+static_assert(MULTI_MAX == GH_MULTI_MAX, "the kernels' row-block table holds the C ABI's GH_MULTI_MAX components");
 
 #include "host_ctx.h"
 #include "host_sweep.h"
@@ -160,7 +161,8 @@ int gh_set_obs(gh_ctx *c, const double *a, const double *b, const double *cc)
     if (!c || !a || !b || !cc) return fail(c, GH_ERR_ARG, "gh_set_obs: null pointer");
     HIPCHK(c, hipSetDevice(c->device));
     const double *src[3] = {a, b, cc};
-    const int64_t n = c->joint ? c->N / 2 : c->N;  // (joint store: both blocks share the N/2 points)
+    // (joint store: both blocks share the N/2 points; multi-component store: all blocks share the N/n points)
+    const int64_t n = c->joint ? c->N / 2 : c->mc.n > 0 ? c->N / c->mc.n : c->N;
     for (int i = 0; i < 3; ++i) {
         TRY(dalloc(c, &c->obs[i], (size_t)n));
         TRY(h2d(c, c->obs[i], src[i], (size_t)n));
@@ -182,6 +184,7 @@ int gh_set_obs(gh_ctx *c, const double *a, const double *b, const double *cc)
 static int set_cells(gh_ctx *c, const double *bounds6, int kind, int comp, double ratio, const double *dir = nullptr)
 {
     if (c->joint) return fail(c, GH_ERR_UNSUPPORTED, "a joint gravity-magnetic context takes its cells from gh_set_cells_joint");
+    if (c->mc.n > 0) return fail(c, GH_ERR_UNSUPPORTED, "a multi-component context takes its cells from gh_set_cells_multi");
     HIPCHK(c, hipSetDevice(c->device));
     TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
     TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
@@ -260,6 +263,68 @@ int gh_set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double fy, d
     c->cell_kind = GH_CELL_PRISM_JOINT;
     c->comp = GH_COMP_GZ;
     c->have_cells = true;
+    return GH_OK;
+}
+
+int gh_set_cells_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *weights)
+{
+    if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_multi: null pointer");
+    if (ncomp < 1 || ncomp > GH_MULTI_MAX)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_multi: %d components: the multi-component store takes 1 to %d", ncomp,
+                    GH_MULTI_MAX);
+    for (int b = 0; b < ncomp; ++b) {
+        if (comps[b] < GH_COMP_POTENTIAL || comps[b] > GH_COMP_GZZ)
+            return fail(c, GH_ERR_ARG, "gh_set_cells_multi: component %d is not one of GH_COMP_POTENTIAL (0) .. GH_COMP_GZZ (10)",
+                        comps[b]);
+        for (int a = 0; a < b; ++a)
+            if (comps[a] == comps[b])
+                return fail(c, GH_ERR_ARG, "gh_set_cells_multi: component %d is listed twice", comps[b]);
+        if (!(weights[b] > 0.0) || !std::isfinite(weights[b]))
+            return fail(c, GH_ERR_ARG, "gh_set_cells_multi: the data weights must be finite and > 0");
+    }
+    if (c->N % ncomp != 0)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_multi: N = %lld is not %d blocks of the same observation points",
+                    (long long)c->N, ncomp);
+    if (c->joint || c->have_obs || c->have_cells || c->have_G || c->slab)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_multi: call it first on a fresh context (before gh_set_obs)");
+    if (c->mf || c->ls)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_multi: the multi-component store is dense only (no matrix-free "
+                                           "mode, no shift-invariant store)");
+    if (c->sh.kind != 0) return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_multi: the multi-component store is not sharded");
+    if (c->N > 16384)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_multi: %d components x %lld observations = %lld rows: the "
+                                           "multi-component store takes at most 16384 (it runs on the fused sweep: no row "
+                                           "panels, no team sweep)", ncomp, (long long)(c->N / ncomp), (long long)c->N);
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
+    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
+    c->mc.n = ncomp;
+    for (int b = 0; b < ncomp; ++b) {
+        c->mc.comp[b] = comps[b];
+        c->mc.w[b] = weights[b];
+    }
+    c->cell_kind = GH_CELL_PRISM_MULTI;
+    c->comp = comps[0];
+    c->have_cells = true;
+    return GH_OK;
+}
+
+int gh_multi_info(gh_ctx *c, int *ncomp, int *comps, double *weights, double *pred_mean, double *obs_mean)
+{
+    if (!c) return GH_ERR_ARG;
+    if (c->mc.n == 0)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_multi_info: not a multi-component context (gh_set_cells_multi)");
+    if (ncomp) *ncomp = c->mc.n;
+    for (int b = 0; b < c->mc.n; ++b) {
+        if (comps) comps[b] = c->mc.comp[b];
+        if (weights) weights[b] = c->mc.w[b];
+        if (obs_mean) obs_mean[b] = c->mc.obs_mean[b];
+        if (pred_mean) pred_mean[b] = 0.0;
+    }
+    if (pred_mean && c->mc.bmean) {
+        HIPCHK(c, hipSetDevice(c->device));
+        TRY(d2h(c, pred_mean, c->mc.bmean, (size_t)c->mc.n));
+    }
     return GH_OK;
 }
 
@@ -394,11 +459,15 @@ static int d2h_obsvec(gh_ctx *c, double *dst, const double *src)
     return GH_OK;
 }
 
-static int joint_refuse(gh_ctx *c, const char *who)
+// The stores that are dense and run one chain -- the joint gravity-magnetic store and the multi-component store --
+// refuse `who`, each naming itself.
+static int dense_single_chain_refuse(gh_ctx *c, const char *who)
 {
     if (c && c->joint)
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the joint gravity-magnetic kernel (dense, single chain)",
                     who);
+    if (c && c->mc.n > 0)
+        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the multi-component store (dense, single chain)", who);
     return GH_OK;
 }
 
@@ -494,7 +563,7 @@ int gh_prism_result(gh_ctx *c, const double *dens, double *result)
 int gh_set_matrix_free(gh_ctx *c, int enable)
 {
     if (!c) return GH_ERR_ARG;
-    if (enable) TRY(joint_refuse(c, "gh_set_matrix_free"));
+    if (enable) TRY(dense_single_chain_refuse(c, "gh_set_matrix_free"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_matrix_free: call before gh_build_G");
     if (c->ls) {
         c->mf_before_ls = enable != 0;  // (takes effect when the shift-invariant store is switched off)
@@ -507,7 +576,7 @@ int gh_set_matrix_free(gh_ctx *c, int enable)
 int gh_set_shift_invariant(gh_ctx *c, int enable)
 {
     if (!c) return GH_ERR_ARG;
-    if (enable) TRY(joint_refuse(c, "gh_set_shift_invariant"));
+    if (enable) TRY(dense_single_chain_refuse(c, "gh_set_shift_invariant"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_shift_invariant: call before gh_build_G");
     // (the store is a flavour of the matrix-free mode -- G is never stored -- so enabling it sets c->mf;
     // disabling it puts c->mf back to what gh_set_matrix_free last asked for)
@@ -614,6 +683,27 @@ static int tess_comp_assemble(gh_ctx *c, const double *conv, double *G)
     return GH_OK;
 }
 
+// prism_kernel of one field (GH_COMP_*, or PRISM_TF) into `rows` rows of every column of the dense store, from G on:
+// the first N of them the observations' entries, the rest zero.
+static int prism_assemble(gh_ctx *c, int field, int64_t N, int64_t rows, double *G)
+{
+    typedef void (*prism_fn)(const double *, const double *, const double *, const double *, int64_t, int64_t,
+                             int64_t, double3, double *, int64_t);
+    // (indexed by GH_COMP_*, then the total field)
+    static const prism_fn fns[] = {prism_kernel<GH_COMP_POTENTIAL>, prism_kernel<GH_COMP_GEOID>,
+                                   prism_kernel<GH_COMP_GX>,        prism_kernel<GH_COMP_GY>,
+                                   prism_kernel<GH_COMP_GZ>,        prism_kernel<GH_COMP_GXX>,
+                                   prism_kernel<GH_COMP_GXY>,       prism_kernel<GH_COMP_GXZ>,
+                                   prism_kernel<GH_COMP_GYY>,       prism_kernel<GH_COMP_GYZ>,
+                                   prism_kernel<GH_COMP_GZZ>,       prism_kernel<PRISM_TF>};
+    const int64_t blocks = std::min<int64_t>((rows * c->M + 255) / 256, 1 << 22);
+    hipLaunchKernelGGL(fns[field], dim3((unsigned)blocks), dim3(256), 0, c->stream, c->obs[0], c->obs[1], c->obs[2],
+                       (const double *)c->bounds, N, c->M, rows, make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), G,
+                       c->ld);
+    HIPCHK(c, hipGetLastError());
+    return GH_OK;
+}
+
 int gh_build_G(gh_ctx *c)
 {
     if (!c) return GH_ERR_ARG;
@@ -673,20 +763,14 @@ int gh_build_G(gh_ctx *c)
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
     } else if (c->cell_kind == GH_CELL_PRISM || c->cell_kind == GH_CELL_PRISM_TF || c->cell_kind == GH_CELL_PRISM_COMP) {
-        typedef void (*prism_fn)(const double *, const double *, const double *, const double *, int64_t, int64_t,
-                                 int64_t, double3, double *);
-        // (indexed by GH_COMP_*, then the total field)
-        static const prism_fn fns[] = {prism_kernel<GH_COMP_POTENTIAL>, prism_kernel<GH_COMP_GEOID>,
-                                       prism_kernel<GH_COMP_GX>,        prism_kernel<GH_COMP_GY>,
-                                       prism_kernel<GH_COMP_GZ>,        prism_kernel<GH_COMP_GXX>,
-                                       prism_kernel<GH_COMP_GXY>,       prism_kernel<GH_COMP_GXZ>,
-                                       prism_kernel<GH_COMP_GYY>,       prism_kernel<GH_COMP_GYZ>,
-                                       prism_kernel<GH_COMP_GZZ>,       prism_kernel<PRISM_TF>};
-        const int64_t blocks = std::min<int64_t>((c->ld * c->M + 255) / 256, 1 << 22);
-        hipLaunchKernelGGL(fns[c->cell_kind == GH_CELL_PRISM_TF ? PRISM_TF : c->comp], dim3((unsigned)blocks), dim3(256),
-                           0, c->stream, c->obs[0], c->obs[1], c->obs[2], (const double *)c->bounds, c->N, c->M, c->ld,
-                           make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), c->G);
-        HIPCHK(c, hipGetLastError());
+        TRY(prism_assemble(c, c->cell_kind == GH_CELL_PRISM_TF ? PRISM_TF : c->comp, c->N, c->ld, c->G));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else if (c->cell_kind == GH_CELL_PRISM_MULTI) {
+        // one launch per component into its row block of the one store; the last block's launch also zeroes the
+        // padding rows below it
+        const int64_t Nb = c->N / c->mc.n;
+        for (int b = 0; b < c->mc.n; ++b)
+            TRY(prism_assemble(c, c->mc.comp[b], Nb, b + 1 < c->mc.n ? Nb : c->ld - b * Nb, c->G + b * Nb));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     } else if (c->cell_kind == GH_CELL_TESSEROID || c->cell_kind == GH_CELL_TESSEROID_COMP) {
         double *conv = nullptr;
@@ -719,7 +803,7 @@ int gh_kernel_stats(const gh_ctx *c, int64_t *warn_cells, int64_t *leaves)
 int gh_upload_G(gh_ctx *c, const double *A, int64_t ld, int fortran_order)
 {
     if (!c || !A) return fail(c, GH_ERR_ARG, "gh_upload_G: null pointer");
-    TRY(joint_refuse(c, "gh_upload_G"));
+    TRY(dense_single_chain_refuse(c, "gh_upload_G"));
     if (ld < (fortran_order ? c->N : c->M)) return fail(c, GH_ERR_ARG, "gh_upload_G: ld too small");
     if (c->mf) return fail(c, GH_ERR_ARG, "gh_upload_G: context is matrix-free");
     if (!c->dense_ok) return fail(c, GH_ERR_UNSUPPORTED, "N = %lld: more than 16384 observations per device", (long long)c->N);
@@ -802,6 +886,22 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
         }
         c->joint_std[0] = std::sqrt(var[0]);
         c->joint_std[1] = std::sqrt(var[1]);
+    }
+    if (c->mc.n > 0) {
+        // Wb first: the column norms are those of Wb A, or the component with the largest unit would decide them
+        RowBlocks rb{};
+        rb.n = c->mc.n;
+        rb.Nb = c->N / c->mc.n;
+        bool unit = true;
+        for (int b = 0; b < rb.n; ++b) {
+            rb.w[b] = c->mc.w[b];
+            unit = unit && rb.w[b] == 1.0;
+        }
+        if (!unit) {
+            const unsigned blocks = (unsigned)std::min<int64_t>((c->ld * c->M + 255) / 256, 1 << 20);
+            scale_rowblocks_kernel<<<dim3(blocks), dim3(256), 0, c->stream>>>(c->G, c->ld, c->M, rb);
+            HIPCHK(c, hipGetLastError());
+        }
     }
     if (lonsym_on(c)) {
         lonsym_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
@@ -898,6 +998,24 @@ int gh_set_data(gh_ctx *c, const double *dobs, const double *grav_fix)
             return sum(a, n2) + sum(a + n2, n - n2);
         }
     };
+    if (c->mc.n > 0) {
+        // Wb dobs in row blocks: every component loses its own mean
+        if (grav_fix) return fail(c, GH_ERR_ARG, "gh_set_data: the multi-component store takes no grav_fix");
+        const size_t Nb = N / (size_t)c->mc.n;
+        for (int b = 0; b < c->mc.n; ++b) {
+            double *tb = t.data() + (size_t)b * Nb;
+            const double mb = PW::sum(tb, Nb) / (double)Nb;
+            for (size_t i = 0; i < Nb; ++i) tb[i] -= mb;
+            c->mc.obs_mean[b] = mb;
+        }
+        TRY(h2d(c, c->dobs_c, t.data(), N));
+        c->have_fix = false;
+        c->gfix_sum = 0.0;
+        c->have_data = true;
+        c->chain_ready = false;
+        c->bt.ready = false;
+        return GH_OK;
+    }
     double mean = PW::sum(t.data(), N) / (double)N;
     if (shard_rows(c)) {
         // (row blocks: the mean of ALL observations -- the sum of the ranks' pairwise sums)
@@ -1124,7 +1242,7 @@ int gh_compress_wavelet(gh_ctx *c, int dims, const int shape3[3], double thr, in
                         int64_t *nnz_out, int64_t *ncols_out)
 {
     if (!c) return GH_ERR_ARG;
-    TRY(joint_refuse(c, "gh_compress_wavelet"));
+    TRY(dense_single_chain_refuse(c, "gh_compress_wavelet"));
     TRY(need(c, c->have_G && c->weighted, "gh_compress_wavelet: needs the weighted kernel (gh_weight) first"));
     if (dims != 1 && dims != 3) return fail(c, GH_ERR_ARG, "gh_compress_wavelet: dims must be 1 or 3");
     if (levels < 1 || levels > 4) return fail(c, GH_ERR_ARG, "gh_compress_wavelet: levels must be 1..4");
@@ -1479,7 +1597,7 @@ int gh_posterior_read(gh_ctx *c, int64_t *n_in_window, int64_t *n_total, double 
 int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const double *high)
 {
     if (!c || !x0s || !low || !high) return fail(c, GH_ERR_ARG, "gh_batch_init: null pointer");
-    TRY(joint_refuse(c, "gh_batch_init"));
+    TRY(dense_single_chain_refuse(c, "gh_batch_init"));
     if (C < 1 || C > CB) return fail(c, GH_ERR_ARG, "gh_batch_init: 1..16 chains per batch");
     TRY(need(c, c->have_G && c->have_data && c->have_reg,
              "gh_batch_init: needs the kernel (gh_build_G / gh_upload_G), gh_set_data and gh_set_reg"));
@@ -1539,7 +1657,7 @@ int gh_batch_trajectory(gh_ctx *c, const double *p0s, double dt, const int *L, c
                         double *out5s)
 {
     if (!c || !p0s || !L || !us || !accepted || !out5s) return fail(c, GH_ERR_ARG, "gh_batch_trajectory: null pointer");
-    TRY(joint_refuse(c, "gh_batch_trajectory"));
+    TRY(dense_single_chain_refuse(c, "gh_batch_trajectory"));
     gh_ctx::Batch &b = c->bt;
     TRY(need(c, b.ready, "gh_batch_trajectory: call gh_batch_init first"));
     for (int k = 0; k < b.C; ++k)
@@ -1580,7 +1698,7 @@ int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const
 {
     if (!c || T < 0 || (T > 0 && (!L || !p0s || !us)) || !accepted || !out5s || ((n_started == nullptr) != (n_done == nullptr)))
         return fail(c, GH_ERR_ARG, "gh_batch_run: bad arguments");
-    TRY(joint_refuse(c, "gh_batch_run"));
+    TRY(dense_single_chain_refuse(c, "gh_batch_run"));
     if (T == 0 && !n_done) return fail(c, GH_ERR_ARG, "gh_batch_run: T = 0 (drain) needs n_started / n_done");
     gh_ctx::Batch &b = c->bt;
     TRY(need(c, b.ready, "gh_batch_run: call gh_batch_init first"));
@@ -1880,7 +1998,7 @@ int gh_shard_init(gh_ctx *c, const void *id128, int rank, int world, int64_t M_g
 {
     if (!c || !id128) return fail(c, GH_ERR_ARG, "gh_shard_init: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init: already initialised");
-    TRY(joint_refuse(c, "gh_shard_init"));
+    TRY(dense_single_chain_refuse(c, "gh_shard_init"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_common_init(c, rank, world, M_global, m0));
     std::string err;
@@ -1900,7 +2018,7 @@ int gh_shard_init_callback(gh_ctx *c, gh_allreduce_fn fn, void *user, int rank, 
 {
     if (!c || !fn) return fail(c, GH_ERR_ARG, "gh_shard_init_callback: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init: already initialised");
-    TRY(joint_refuse(c, "gh_shard_init"));
+    TRY(dense_single_chain_refuse(c, "gh_shard_init"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_common_init(c, rank, world, M_global, m0));
     c->sh.cb = fn;
@@ -1913,7 +2031,7 @@ int gh_shard_init_rows(gh_ctx *c, const void *id128, int rank, int world, int64_
 {
     if (!c || !id128) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: already initialised");
-    TRY(joint_refuse(c, "gh_shard_init_rows"));
+    TRY(dense_single_chain_refuse(c, "gh_shard_init_rows"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_rows_init(c, rank, world, N_global, n0));
     std::string err;
@@ -1933,7 +2051,7 @@ int gh_shard_init_rows_callback(gh_ctx *c, gh_allreduce_fn fn, void *user, int r
 {
     if (!c || !fn) return fail(c, GH_ERR_ARG, "gh_shard_init_rows_callback: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: already initialised");
-    TRY(joint_refuse(c, "gh_shard_init_rows"));
+    TRY(dense_single_chain_refuse(c, "gh_shard_init_rows"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_rows_init(c, rank, world, N_global, n0));
     c->sh.cb = fn;

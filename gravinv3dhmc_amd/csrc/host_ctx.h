@@ -51,6 +51,16 @@ struct gh_ctx {
     // vectors live as [gz: ld | tf: ld] (2 ld doubles), model-space vectors as M
     bool joint = false;
     double joint_std[2] = {0.0, 0.0};      // population std of the unweighted gz / tf blocks (gh_weight)
+    // GH_CELL_PRISM_MULTI: n gravity components of the same cells at the same N / n points, stacked in row blocks
+    // of one dense store (block b = rows [b N/n, (b + 1) N/n), component comp[b], times w[b] once weighted)
+    struct Multi {
+        int n = 0;  // 0: not a multi-component context
+        int comp[GH_MULTI_MAX] = {};
+        double w[GH_MULTI_MAX] = {};
+        double obs_mean[GH_MULTI_MAX] = {};  // the mean gh_set_data removed from each block of Wb dobs
+        double *bsum = nullptr;              // n x (slab rows): sums of the slab rows per block (slab_block_sums_kernel)
+        double *bmean = nullptr;             // n: the blocks' means of the last evaluation's prediction
+    } mc;
     bool have_obs = false, have_cells = false, have_G = false, weighted = false;
     double *G = nullptr;
     int64_t warn_cells = 0, leaves = 0;

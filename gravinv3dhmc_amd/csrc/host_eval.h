@@ -125,7 +125,7 @@ static int finalize_joint(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
         fa.scal = o.scal;
         fa.r2part = o.part + h * c->n_dpart;
         fa.ra = ra;
-        reduce_finish_kernel<<<dim3((unsigned)(c->n_dpart + n_reg)), dim3(256), 0, c->stream>>>(fa);
+        reduce_finish_kernel<false><<<dim3((unsigned)(c->n_dpart + n_reg)), dim3(256), 0, c->stream>>>(fa);
     }
     // the coupling: lambda grad Phi on top of both blocks' alpha grad R, its partials behind those of R
     if (cross_gradient_on(c))
@@ -195,6 +195,9 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
         o.pending = false;
         return GH_OK;
     }
+    // (the multi-component store has one epilogue, the one with a mean per row block: never the single-mean forms below)
+    if (c->mc.n > 0 && !o.part)
+        return fail(c, GH_ERR_ARG, "multi-component epilogue: the state set has no partials (ensure_work not run)");
     if (c->sh.kind != 0) {
         // sharded cells: local forward partial and local regulariser sum travel in ONE
         // all-reduce, then every rank finishes the (replicated) data part identically
@@ -261,8 +264,9 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
         h.rhat_of = r_out;
         o.pending = true;
         return GH_OK;
-    } else if (c->dsum_live && o.part) {
+    } else if ((c->dsum_live || c->mc.n > 0) && o.part) {
         // the slab rows' sums at hand (and N >= 2048): the whole epilogue in one launch
+        // (multi-component store: the sums per row block come from a launch of their own, whatever N)
         ReduceFinishArgs fa{};
         fa.slab = c->slab;
         fa.n_rows_slab = c->slab_live > 0 ? c->slab_live : c->grid;
@@ -281,7 +285,19 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
         fa.r2part = o.part;
         fa.ra = ra;
         fa.ra.regpart = o.part + c->n_dpart;
-        reduce_finish_kernel<<<dim3((unsigned)(c->n_dpart + c->n_regpart)), dim3(256), 0, c->stream>>>(fa);
+        if (c->mc.n > 0) {
+            // one mean per component: r_b = (d_b - mean d_b) - (dobs_b - mean dobs_b) in every row block
+            fa.nblk = c->mc.n;
+            fa.Nb = c->N / c->mc.n;
+            fa.bmean = c->mc.bmean;
+            fa.dsum = c->mc.bsum;
+            fa.n_dsum = fa.n_rows_slab;
+            slab_block_sums_kernel<<<dim3((unsigned)fa.n_rows_slab), dim3(256), 0, c->stream>>>(c->slab, c->ld, fa.Nb, fa.nblk,
+                                                                                                c->mc.bsum);
+            reduce_finish_kernel<true><<<dim3((unsigned)(c->n_dpart + c->n_regpart)), dim3(256), 0, c->stream>>>(fa);
+        } else {
+            reduce_finish_kernel<false><<<dim3((unsigned)(c->n_dpart + c->n_regpart)), dim3(256), 0, c->stream>>>(fa);
+        }
         HIPCHK(c, hipGetLastError());
         o.pending = true;
         return GH_OK;
@@ -380,6 +396,12 @@ static int ensure_work(gh_ctx *c)
             TRY(dalloc(c, &c->st[i].part, 2 * (size_t)c->n_dpart + 3 * (size_t)((c->M / 2 + 255) / 256)));
             c->st[i].phi = c->cg.phi_all + i;
         }
+    } else if (c->mc.n > 0) {
+        // (the multi-component store's epilogue always runs as reduce_finish_kernel<BLOCKS>: its partials, the
+        // slab rows' sums per row block and the blocks' means)
+        TRY(dalloc(c, &c->mc.bsum, (size_t)c->mc.n * (size_t)std::max(c->grid, 128)));
+        TRY(dalloc(c, &c->mc.bmean, (size_t)c->mc.n));
+        for (int i = 0; i < 4; ++i) TRY(dalloc(c, &c->st[i].part, (size_t)c->n_dpart + (size_t)((c->M + 255) / 256)));
     } else if (c->ld >= 2048 && ((c->TW > 1 && c->n_panels == 1 && !c->mf) || lonsym_on(c)) && env_int("GRAVHMC_EPILOGUE1", 1) != 0) {
         TRY(dalloc(c, &c->dsum, (size_t)std::max(std::max(c->grid, 128), lonsym_on(c) ? lonsym_classes(c) : 0)));
         for (int i = 0; i < 4; ++i) TRY(dalloc(c, &c->st[i].part, (size_t)c->n_dpart + (size_t)((c->M + 255) / 256)));

@@ -764,6 +764,12 @@ reduce_reg_kernel(const double *slab, int n_rows_slab, int64_t ld, int nseg, int
 // inside this kernel was tried first: the agent-scope release fence every block needs costs more
 // than the launch it saves (30 us).  (The mean is the same number up to the association of its
 // sum; a shift delta of the mean changes |r|^2 by N delta^2 only, sum r = 0.)
+//
+// BLOCKS: the rows are nblk row blocks of Nb observations each (the multi-component store, N = nblk * Nb), every
+// one with a mean of its own: dsum then holds nblk rows of n_dsum partial sums, block b's in row b
+// (slab_block_sums_kernel), a residual subtracts the mean of the block its observation lies in, and bmean takes
+// the nblk means.  |r|^2 is the sum over all blocks, so its partials stay one per 32 observations.
+constexpr int MULTI_MAX = 11;  // row blocks at most: every gravity component once
 struct ReduceFinishArgs {
     const double *slab;
     int n_rows_slab, n_dpart, n_regpart;
@@ -775,8 +781,29 @@ struct ReduceFinishArgs {
     double *d, *r, *scal;    // as FinishArgs (scal: only [3] = mean is written here)
     double *r2part;          // n_dpart (ra.regpart: the n_regpart partials of R, kept with them)
     RegArgs ra;
+    int nblk;                // BLOCKS: row blocks, Nb observations each, and where their means go
+    int64_t Nb;
+    double *bmean;
 };
 
+// sums[b * n_rows_slab + t] = sum of slab row t over the observations of row block b: what reduce_finish_kernel
+// <BLOCKS> turns into the blocks' means.  One workgroup per slab row.  (It walks its row load by load, block after
+// block: 38 us per step at 256 rows of 72 KB, DESIGN 4.17 -- a workgroup per (slab row, block) with several loads in
+// flight is the next step.)
+__global__ void __launch_bounds__(256)
+slab_block_sums_kernel(const double *__restrict__ slab, int64_t ld, int64_t Nb, int nblk, double *__restrict__ sums)
+{
+    __shared__ double red[4];
+    const double *row = slab + (int64_t)blockIdx.x * ld;
+    for (int b = 0; b < nblk; ++b) {
+        double s = 0.0;
+        for (int64_t i = threadIdx.x; i < Nb; i += 256) s += row[b * Nb + i];
+        const double t = block_allreduce_sum(s, red, 4);
+        if (threadIdx.x == 0) sums[(int64_t)b * gridDim.x + blockIdx.x] = t;
+    }
+}
+
+template <bool BLOCKS>
 __global__ void __launch_bounds__(256) reduce_finish_kernel(ReduceFinishArgs a)
 {
     __shared__ double red8[8][33];
@@ -786,9 +813,27 @@ __global__ void __launch_bounds__(256) reduce_finish_kernel(ReduceFinishArgs a)
         reg_block(a.ra, blockIdx.x - n_red, red);
     } else {
         // mean of d + grav_fix from the slab rows' sums, identical bits in every block
-        double ds = 0.0;
-        for (int t = threadIdx.x; t < a.n_dsum; t += 256) ds += a.dsum[t];
-        const double mean = (block_allreduce_sum(ds, red, 4) + a.gfix_sum) / (double)a.N;
+        double mean = 0.0;
+        if constexpr (BLOCKS) {
+            // (one mean per row block, in LDS; this thread's observation picks its own below)
+            __shared__ double mean_s[MULTI_MAX];
+            for (int b = 0; b < a.nblk; ++b) {
+                double ds = 0.0;
+                for (int t = threadIdx.x; t < a.n_dsum; t += 256) ds += a.dsum[(int64_t)b * a.n_dsum + t];
+                const double mb = block_allreduce_sum(ds, red, 4) / (double)a.Nb;
+                if (threadIdx.x == 0) {
+                    mean_s[b] = mb;
+                    if (blockIdx.x == 0) a.bmean[b] = mb;
+                }
+            }
+            __syncthreads();
+            const int64_t i = (int64_t)blockIdx.x * 32 + (threadIdx.x & 31);
+            mean = mean_s[i < a.N ? i / a.Nb : 0];
+        } else {
+            double ds = 0.0;
+            for (int t = threadIdx.x; t < a.n_dsum; t += 256) ds += a.dsum[t];
+            mean = (block_allreduce_sum(ds, red, 4) + a.gfix_sum) / (double)a.N;
+        }
         const int rx = threadIdx.x & 31, ty = threadIdx.x >> 5;
         const int64_t i = (int64_t)blockIdx.x * 32 + rx;
         double acc = 0.0;
@@ -824,7 +869,7 @@ __global__ void __launch_bounds__(256) reduce_finish_kernel(ReduceFinishArgs a)
             for (int off = 16; off >= 1; off >>= 1) r2 += __shfl_xor(r2, off, WAVE);
             if (rx == 0) {
                 a.r2part[blockIdx.x] = r2;
-                if (blockIdx.x == 0) a.scal[3] = mean;
+                if (blockIdx.x == 0) a.scal[3] = mean;  // (BLOCKS: the first block's)
             }
         }
     }
@@ -1380,13 +1425,15 @@ __device__ __forceinline__ double prism_comp_entry_rt(int comp, double px, doubl
 
 // Dense assembly of one prism field F (COMP_* or PRISM_TF, whose direction is dir): one thread per (obs, cell)
 // entry, obs fastest (coalesced store), zero padding rows to ld.  One instantiation per field, so that each
-// keeps its own register budget.
+// keeps its own register budget.  The launch writes ld rows of every column of a store whose columns are ldg
+// rows apart: ldg == ld for a store of this field alone, ldg > ld for one row block of the multi-component
+// store (GH_CELL_PRISM_MULTI: G then points at the block's first row).
 constexpr int PRISM_TF = COMP_GZZ + 1;
 template <int F>
 __global__ void __launch_bounds__(256)
 prism_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
              const double *__restrict__ bounds6, int64_t N, int64_t M, int64_t ld, double3 dir,
-             double *__restrict__ G)
+             double *__restrict__ G, int64_t ldg)
 {
     // grid-stride: a launch is limited to 2^32 work-items, ld*M reaches 5*10^9 at C2
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ld * M;
@@ -1399,7 +1446,24 @@ prism_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const
             else
                 v = prism_comp_entry<F>(xp[l], yp[l], zp[l], bounds6 + 6 * c);
         }
-        G[idx] = v;
+        G[c * ldg + l] = v;
+    }
+}
+
+// The row blocks of a multi-component store (GH_CELL_PRISM_MULTI): block b = rows [b * Nb, (b + 1) * Nb) of every
+// column, scaled by w[b] (the data weighting Wb).
+struct RowBlocks {
+    int n;
+    int64_t Nb;
+    double w[MULTI_MAX];
+};
+
+// Wb A: every entry of row block b times w[b] (padding rows belong to no block and stay zero)
+__global__ void __launch_bounds__(256) scale_rowblocks_kernel(double *__restrict__ G, int64_t ld, int64_t M, RowBlocks rb)
+{
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ld * M; idx += (int64_t)gridDim.x * 256) {
+        const int64_t c = idx / ld, l = idx - c * ld;
+        if (l < rb.n * rb.Nb) G[idx] *= rb.w[l / rb.Nb];
     }
 }
 

@@ -97,7 +97,8 @@ class Engine(object):
     def set_obs(self, a, b, c):
         a, b, c = f64(a), f64(b), f64(c)
         # (joint gravity-magnetic context: both blocks share the N/2 observation points)
-        n = self.N // 2 if getattr(self, "joint", False) else self.N
+        # (multi-component context: all blocks share the N / ncomp points)
+        n = self.N // 2 if getattr(self, "joint", False) else self.N // getattr(self, "multi", 1)
         if not (a.shape == b.shape == c.shape == (n,)):
             raise ValueError("Input arrays xp, yp, and zp must have same length!")
         self._chk(self._lib.gh_set_obs(self._h, ptr(a), ptr(b), ptr(c)))
@@ -148,6 +149,34 @@ class Engine(object):
             self._chk(self._lib.gh_set_cells_tf(self._h, ptr(b), fx, fy, fz))
             return
         self._chk(self._lib.gh_set_cells(self._h, ptr(b), int(kind), float(ratio)))
+
+    def set_cells_multi(self, bounds6, components, weights):
+        """The M prisms of a multi-component model (gh_set_cells_multi): the gravity fields `components` (names of
+        _lib.COMPONENTS or COMP_* values, distinct) of the same cells at the same N / len(components) points, stacked
+        in row blocks of one store, block c with the data weight weights[c] > 0; call it before set_obs."""
+        b = f64(bounds6)
+        if b.shape != (self.M, 6):
+            raise ValueError("bounds table must be (M, 6)")
+        comps = [_lib.COMPONENTS.get(c, -1) if isinstance(c, str) else int(c) for c in components]
+        if any(c not in _lib.COMPONENTS.values() for c in comps):
+            raise ValueError("component must be one of %s" % ", ".join(_lib.COMPONENTS))
+        w = f64(weights)
+        if w.shape != (len(comps),):
+            raise ValueError("one data weight per component")
+        self._chk(self._lib.gh_set_cells_multi(self._h, ptr(b), len(comps), (C.c_int * max(len(comps), 1))(*comps),
+                                               ptr(w)))
+        self.multi = len(comps)
+
+    def multi_info(self):
+        """The row blocks of a multi-component context (gh_multi_info): components (COMP_* values), weights, the
+        per-block means of the last evaluation's prediction Aw mw and of the weighted observations."""
+        n = C.c_int(0)
+        comps = (C.c_int * _lib.MULTI_MAX)()
+        w, pm, om = np.zeros(_lib.MULTI_MAX), np.zeros(_lib.MULTI_MAX), np.zeros(_lib.MULTI_MAX)
+        self._chk(self._lib.gh_multi_info(self._h, C.byref(n), comps, ptr(w), ptr(pm), ptr(om)))
+        k = n.value
+        return {"components": [int(v) for v in comps[:k]], "weights": w[:k].copy(), "pred_mean": pm[:k].copy(),
+                "obs_mean": om[:k].copy()}
 
     def tf_result(self, mag3):
         """Total-field anomaly (uT) of the CELL_PRISM_TF cells magnetized with mag3[M, 3] (A/m), in the

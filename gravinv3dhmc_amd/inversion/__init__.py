@@ -1,5 +1,6 @@
-"""Potentials (GravMagModule, JointModule) and sampler (HamitonianMC, HMCSample)."""
+"""Potentials (GravMagModule, JointModule, MultiComponentModule) and sampler (HamitonianMC, HMCSample)."""
 from .hmc import HamitonianMC, HMCSample, HMCSampleBatch  # noqa: F401
 from .joint import JointModule  # noqa: F401
+from .multicomp import MultiComponentModule  # noqa: F401
 from .potential import GravMagModule  # noqa: F401
 from .reginv import BootStrap, ConjugateGradient  # noqa: F401

@@ -8,7 +8,9 @@
  * (`_tesseroid_numba.gz`).  Prisms also carry the reference's other fields: the total-field magnetic
  * anomaly (`_prism.tf`, gh_set_cells_tf) and the ten other gravity fields -- potential, geoid, gx, gy and
  * the gradient tensor gxx ... gzz (`_prism.pyx:36-68, 206-509`, gh_set_cells_prism).  Tesseroids carry
- * the same ten other gravity fields (`_tesseroid_numba.py:161-341`, gh_set_cells_tess).  Every entry
+ * the same ten other gravity fields (`_tesseroid_numba.py:161-341`, gh_set_cells_tess).  Several prism
+ * gravity fields of one density model can share one store and be inverted together (gh_set_cells_multi; an
+ * extension, the reference inverts one field at a time).  Every entry
  * point below names the reference interface it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer of the reference would add.
  *
@@ -80,9 +82,12 @@ typedef enum {
 /* GH_CELL_PRISM_TF: prisms, total-field magnetic anomaly (set with gh_set_cells_tf, not gh_set_cells);
  * GH_CELL_PRISM_COMP: prisms, one gravity field other than gz (set with gh_set_cells_prism);
  * GH_CELL_TESSEROID_COMP: tesseroids, one gravity field other than gz (set with gh_set_cells_tess);
- * GH_CELL_PRISM_JOINT: prisms, gz and the total field inverted together (set with gh_set_cells_joint) */
+ * GH_CELL_PRISM_JOINT: prisms, gz and the total field inverted together (set with gh_set_cells_joint);
+ * GH_CELL_PRISM_MULTI: prisms, several gravity fields of one density model inverted together (gh_set_cells_multi) */
 enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2, GH_CELL_PRISM_COMP = 3, GH_CELL_TESSEROID_COMP = 4,
-       GH_CELL_PRISM_JOINT = 5 };
+       GH_CELL_PRISM_JOINT = 5, GH_CELL_PRISM_MULTI = 6 };
+/* components a GH_CELL_PRISM_MULTI context stacks at most: every GH_COMP_* once */
+#define GH_MULTI_MAX 11
 /* The gravity fields of prisms (gravmag/prism.py:875-972), for gh_set_cells_prism, and of tesseroids
  * (gravmag/tesseroid.py:324-508), for gh_set_cells_tess (gy of tesseroids: G * SI2MGAL with the
  * reference's spherical G, Gs = 6.673e-11, 1000 times smaller than the G of every other field) */
@@ -164,6 +169,30 @@ int gh_joint_std(const gh_ctx *ctx, double std2[2]);
  * over the slab rows; 2: below 2048 rows with more than 64 slab rows per block, reduce_reg_kernel folds them into
  * segments first) */
 int gh_joint_layout(const gh_ctx *ctx, int *workgroups_per_block, int *epilogue_stages);
+/* Several gravity fields of ONE density model inverted together (GH_CELL_PRISM_MULTI): ncomp distinct components
+ * comps[b] (GH_COMP_*) of the same M prisms at the same N / ncomp observation points, stacked in row blocks of one
+ * dense store: rows [b N/ncomp, (b + 1) N/ncomp) of A hold component b, entry for entry the bits of a
+ * gh_set_cells_prism context of that component, in its own units.  The context's N is the stacked length;
+ * observation-space vectors are component-major.  weights[b] > 0 is the data weighting of block b.  Call it on a
+ * fresh context, BEFORE gh_set_obs, which then takes the N / ncomp points.
+ *   gh_build_G   runs the component's assembly kernel once per block into the one store.
+ *   gh_weight    scales block b by weights[b] (Wb), takes the column norms Wm of Wb A -- not of A, where the
+ *                component with the largest unit would decide them -- and leaves Aw = Wb A Wm^-1.
+ *   gh_set_data  takes dobs = Wb [dobs_0; ...; dobs_{ncomp-1}] (N entries) and removes the mean of every block
+ *                on its own; grav_fix must be null.
+ *   The data term removes the mean per block on the prediction's side too: with d = Aw mw,
+ *                r_b = (d_b - mean d_b) - (dobs_b - mean dobs_b),  U_data = sum_b |r_b|^2,  grad = 2 Aw^T r
+ *                (one mean over rows that mix units would be meaningless).  The regularisers act on the M cells.
+ *   With ncomp = 1 and weights[0] = 1 the context computes what a gh_set_cells_prism context computes.
+ * It runs on the fused sweep: N (the stacked length) > 16384 is refused with GH_ERR_UNSUPPORTED, as are
+ * matrix-free, the shift-invariant store, the wavelet compressor, gh_batch_*, gh_shard_init* and gh_upload_G; the
+ * resident chain kernel and the folded store are never chosen. */
+int gh_set_cells_multi(gh_ctx *ctx, const double *bounds6, int ncomp, const int *comps, const double *weights);
+/* The blocks of a GH_CELL_PRISM_MULTI context (every pointer may be null; arrays of GH_MULTI_MAX hold them):
+ * their number, components and weights, the mean of each block of the LAST evaluation's prediction Aw mw
+ * (gh_misfit_and_grad, or the chain's last step; zeros before the first), and the mean gh_set_data removed from
+ * each block of the weighted observations. */
+int gh_multi_info(gh_ctx *ctx, int *ncomp, int *comps, double *weights, double *pred_mean, double *obs_mean);
 /* Cross-gradient structural coupling of a weighted GH_CELL_PRISM_JOINT context (Gallardo & Meju 2003; the
  * reference's JointModule.CrossGradient, potential.py:1558, is an empty method).  With shape3 = (nz, ny, nx),
  * nz*ny*nx == M/2, x fastest (p = (k ny + j) nx + i), the physical, normalised models are
