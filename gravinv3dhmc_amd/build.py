@@ -41,8 +41,8 @@ def build(force=False, verbose=False):
     # the generated code of the kernel with hand-counted waits, checked with the compiler that built it
     bad = isa_check.stamp(hipcc())
     if bad:
-        print("gravinv3dhmc_amd.build: batch_team_kernel's generated code has findings (the team form of the "
-              "stored-kernel batch stays off):\n  " + "\n  ".join(bad[:5]))
+        print("gravinv3dhmc_amd.build: the generated-code scan has findings (those of batch_team_kernel keep the team "
+              "form of the stored-kernel batch off):\n  " + "\n  ".join(bad[:5]))
     return LIB
 
 

@@ -185,6 +185,7 @@ static int set_cells(gh_ctx *c, const double *bounds6, int kind, int comp, doubl
 {
     if (c->joint) return fail(c, GH_ERR_UNSUPPORTED, "a joint gravity-magnetic context takes its cells from gh_set_cells_joint");
     if (c->mc.n > 0) return fail(c, GH_ERR_UNSUPPORTED, "a multi-component context takes its cells from gh_set_cells_multi");
+    if (c->mvi) return fail(c, GH_ERR_UNSUPPORTED, "a magnetization-vector context takes its cells from gh_set_cells_mvi");
     HIPCHK(c, hipSetDevice(c->device));
     TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
     TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
@@ -207,7 +208,9 @@ int gh_set_cells(gh_ctx *c, const double *bounds6, int kind, double ratio)
 {
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells: null pointer");
     if (kind != GH_CELL_PRISM && kind != GH_CELL_TESSEROID)
-        return fail(c, GH_ERR_ARG, "gh_set_cells: kind must be 0 (prism) or 1 (tesseroid)");
+        return fail(c, GH_ERR_ARG, "gh_set_cells: kind must be 0 (prism) or 1 (tesseroid); the total field, the other "
+                                   "gravity fields, the joint, multi-component and magnetization-vector stores have "
+                                   "entry points of their own");
     if (kind == GH_CELL_TESSEROID && !(ratio > 0))
         return fail(c, GH_ERR_ARG, "Invalid ratio %g. Must be > 0.", ratio);
     return set_cells(c, bounds6, kind, GH_COMP_GZ, ratio);
@@ -266,6 +269,99 @@ int gh_set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double fy, d
     return GH_OK;
 }
 
+int gh_set_cells_mvi(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
+{
+    if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_mvi: null pointer");
+    if (c->M % 3 != 0 || c->M < 3)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi: M = %lld is not three components of the same prisms", (long long)c->M);
+    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(fz))
+        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi: the field direction must be finite");
+    if (c->joint || c->mc.n > 0 || c->have_obs || c->have_cells || c->have_G || c->slab)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi: call it first on a fresh context (before gh_set_obs)");
+    if (c->mf || c->ls)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi: the magnetization-vector store is dense only (no matrix-free "
+                                           "mode, no shift-invariant store)");
+    if (c->sh.kind != 0) return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi: the magnetization-vector store is not sharded");
+    if (c->N > 16384)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi: N = %lld observations: the magnetization-vector store takes at "
+                                           "most 16384 (it runs on the fused sweep: no row panels, no team sweep)",
+                    (long long)c->N);
+    HIPCHK(c, hipSetDevice(c->device));
+    const double dir[3] = {fx, fy, fz};
+    // (bounds: M/3 cells)
+    TRY(dalloc(c, &c->bounds, (size_t)(c->M / 3) * 6));
+    TRY(h2d(c, c->bounds, bounds6, (size_t)(c->M / 3) * 6));
+    std::copy(dir, dir + 3, c->tf_dir);
+    TRY(dalloc(c, &c->tf_dir_d, 3));
+    TRY(h2d(c, c->tf_dir_d, c->tf_dir, 3));
+    c->mvi = true;
+    c->cell_kind = GH_CELL_PRISM_MVI;
+    c->comp = GH_COMP_GZ;
+    c->have_cells = true;
+    return GH_OK;
+}
+
+static const char *const MVI_ONLY = "the amplitude term couples the three blocks of the magnetization-vector store (a "
+                                    "GH_CELL_PRISM_MVI context, gh_set_cells_mvi)";
+
+// amp.sw = 1 / (Wm scale), 0 where Wm is 0: from the weights the store has NOW (gh_weight builds it again)
+static int amplitude_weights(gh_ctx *c, double scale)
+{
+    TRY(dalloc(c, &c->amp.sw, (size_t)c->M));
+    std::vector<double> w((size_t)c->M);
+    TRY(d2h(c, w.data(), c->wm, (size_t)c->M));
+    for (auto &v : w) v = v == 0.0 ? 0.0 : (1.0 / v) / scale;
+    return h2d(c, c->amp.sw, w.data(), (size_t)c->M);
+}
+
+int gh_set_amplitude(gh_ctx *c, double lambda, double beta, double scale)
+{
+    if (!c) return GH_ERR_ARG;
+    if (!c->mvi) return fail(c, GH_ERR_UNSUPPORTED, "gh_set_amplitude: %s", MVI_ONLY);
+    TRY(need(c, c->weighted, "gh_set_amplitude: call gh_weight first (the term acts on mw / Wm)"));
+    if (!(lambda >= 0.0) || !std::isfinite(lambda)) return fail(c, GH_ERR_ARG, "gh_set_amplitude: lambda must be >= 0");
+    if (!(beta > 0.0) || !std::isfinite(beta)) return fail(c, GH_ERR_ARG, "gh_set_amplitude: beta must be > 0");
+    if (!(scale > 0.0) || !std::isfinite(scale)) return fail(c, GH_ERR_ARG, "gh_set_amplitude: scale must be > 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(amplitude_weights(c, scale));
+    c->amp.lambda = lambda;
+    c->amp.beta = beta;
+    c->amp.scale = scale;
+    c->amp.set = true;
+    c->cg.phi_cur = c->cg.phi_last = 0.0;
+    c->chain_ready = false;
+    return GH_OK;
+}
+
+int gh_amplitude_eval(gh_ctx *c, const double *mw, double *value, double *grad, double *amp)
+{
+    if (!c) return GH_ERR_ARG;
+    if (!c->mvi) return fail(c, GH_ERR_UNSUPPORTED, "gh_amplitude_eval: %s", MVI_ONLY);
+    if (!mw || !value) return fail(c, GH_ERR_ARG, "gh_amplitude_eval: null pointer");
+    TRY(need(c, c->amp.set, "gh_amplitude_eval: call gh_set_amplitude first (lambda = 0 leaves the coupling off)"));
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(ensure_work(c));
+    const int64_t m = c->M / 3;
+    if (amp) TRY(dalloc(c, &c->amp.abuf, (size_t)m));
+    TRY(h2d(c, c->xb[3], mw, (size_t)c->M));
+    launch_amplitude(c, c->xb[3], 1.0, grad ? c->tmpM : nullptr, false, amp ? c->amp.abuf : nullptr, c->amppart);
+    sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->amppart, (int)((m + 255) / 256), c->st[3].scal);
+    HIPCHK(c, hipGetLastError());
+    TRY(d2h(c, c->h_scal, c->st[3].scal, 1));
+    *value = c->h_scal[0];
+    if (grad) TRY(d2h(c, grad, c->tmpM, (size_t)c->M));
+    if (amp) TRY(d2h(c, amp, c->amp.abuf, (size_t)m));
+    return GH_OK;
+}
+
+int gh_amplitude_last(const gh_ctx *c, double *phi)
+{
+    if (!c || !phi) return GH_ERR_ARG;
+    if (!c->mvi) return GH_ERR_UNSUPPORTED;
+    *phi = c->cg.phi_last;
+    return GH_OK;
+}
+
 int gh_set_cells_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *weights)
 {
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_multi: null pointer");
@@ -285,7 +381,7 @@ int gh_set_cells_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *c
     if (c->N % ncomp != 0)
         return fail(c, GH_ERR_ARG, "gh_set_cells_multi: N = %lld is not %d blocks of the same observation points",
                     (long long)c->N, ncomp);
-    if (c->joint || c->have_obs || c->have_cells || c->have_G || c->slab)
+    if (c->joint || c->mvi || c->have_obs || c->have_cells || c->have_G || c->slab)
         return fail(c, GH_ERR_ARG, "gh_set_cells_multi: call it first on a fresh context (before gh_set_obs)");
     if (c->mf || c->ls)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_multi: the multi-component store is dense only (no matrix-free "
@@ -459,8 +555,8 @@ static int d2h_obsvec(gh_ctx *c, double *dst, const double *src)
     return GH_OK;
 }
 
-// The stores that are dense and run one chain -- the joint gravity-magnetic store and the multi-component store --
-// refuse `who`, each naming itself.
+// The stores that are dense and run one chain -- the joint gravity-magnetic store, the multi-component store and the
+// magnetization-vector store -- refuse `who`, each naming itself.
 static int dense_single_chain_refuse(gh_ctx *c, const char *who)
 {
     if (c && c->joint)
@@ -468,6 +564,8 @@ static int dense_single_chain_refuse(gh_ctx *c, const char *who)
                     who);
     if (c && c->mc.n > 0)
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the multi-component store (dense, single chain)", who);
+    if (c && c->mvi)
+        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the magnetization-vector store (dense, single chain)", who);
     return GH_OK;
 }
 
@@ -502,13 +600,16 @@ int gh_tf_result(gh_ctx *c, const double *mag3, double *result)
 {
     if (!c || !mag3 || !result) return fail(c, GH_ERR_ARG, "gh_tf_result: null pointer");
     TRY(need(c, c->have_obs && c->have_cells, "gh_tf_result: call gh_set_obs and gh_set_cells_tf first"));
-    if (c->cell_kind != GH_CELL_PRISM_TF)
-        return fail(c, GH_ERR_ARG, "gh_tf_result: the cells are not a total-field magnetic model (gh_set_cells_tf)");
+    if (c->cell_kind != GH_CELL_PRISM_TF && c->cell_kind != GH_CELL_PRISM_MVI)
+        return fail(c, GH_ERR_ARG, "gh_tf_result: the cells are not a total-field magnetic model (gh_set_cells_tf, "
+                                   "gh_set_cells_mvi)");
     if (c->sh.kind != 0)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_tf_result: the magnetic field's result runs on an unsharded context");
-    return run_result(c, "gh_tf_result", mag3, 3 * (size_t)c->M, result, [c](const double *dmag, double *dres) {
+    // (magnetization-vector store: M / 3 prisms)
+    const int64_t cells = c->mvi ? c->M / 3 : c->M;
+    return run_result(c, "gh_tf_result", mag3, 3 * (size_t)cells, result, [c, cells](const double *dmag, double *dres) {
         prism_tf_result_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], c->bounds, dmag, c->N, c->M, c->tf_dir[0], c->tf_dir[1], c->tf_dir[2],
+            c->obs[0], c->obs[1], c->obs[2], c->bounds, dmag, c->N, cells, c->tf_dir[0], c->tf_dir[1], c->tf_dir[2],
             dres);
     });
 }
@@ -762,6 +863,15 @@ int gh_build_G(gh_ctx *c)
             make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), c->G);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else if (c->cell_kind == GH_CELL_PRISM_MVI) {
+        // the three blocks of A = [A_x | A_y | A_z] in one launch (m = M/3 cells, each corner evaluated once)
+        const int64_t m = c->M / 3;
+        const int64_t blocks = std::min<int64_t>((c->ld * m + 255) / 256, 1 << 22);
+        prism_mvi_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(
+            c->obs[0], c->obs[1], c->obs[2], c->bounds, c->N, m, c->ld,
+            make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), c->G);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
     } else if (c->cell_kind == GH_CELL_PRISM || c->cell_kind == GH_CELL_PRISM_TF || c->cell_kind == GH_CELL_PRISM_COMP) {
         TRY(prism_assemble(c, c->cell_kind == GH_CELL_PRISM_TF ? PRISM_TF : c->comp, c->N, c->ld, c->G));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -946,6 +1056,8 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
     if (wm_out) memcpy(wm_out, w.data(), sizeof(double) * (size_t)c->M);
     for (auto &v : w) v = v * v;  // diag(WmSquare) = ADiag * ADiag (potential.py:253)
     TRY(h2d(c, c->wm2, w.data(), (size_t)c->M));
+    // (an amplitude term set on the store's earlier weights follows the new ones)
+    if (c->mvi && c->amp.set) TRY(amplitude_weights(c, c->amp.scale));
     c->weighted = true;
     c->G_gen += 1;
     c->chain_ready = false;
@@ -1051,6 +1163,10 @@ int gh_set_reg(gh_ctx *c, int kind, double alpha, double beta, const int shape3[
     } else if (stencil && c->joint) {
         if (!shape3 || 2 * (int64_t)shape3[0] * shape3[1] * shape3[2] != c->M)
             return fail(c, GH_ERR_ARG, "gh_set_reg: Smoothness/TV on the joint kernel need shape nz*ny*nx == M/2 (one property's mesh)");
+    } else if (stencil && c->mvi) {
+        if (!shape3 || 3 * (int64_t)shape3[0] * shape3[1] * shape3[2] != c->M)
+            return fail(c, GH_ERR_ARG, "gh_set_reg: Smoothness/TV on the magnetization-vector store need shape nz*ny*nx == M/3 "
+                                       "(one component's mesh)");
     } else if (stencil) {
         if (!shape3 || (int64_t)shape3[0] * shape3[1] * shape3[2] != c->M)
             return fail(c, GH_ERR_ARG, "gh_set_reg: Smoothness/TV need shape nz*ny*nx == M (carved meshes are not supported by the finite-difference operator)");
@@ -1169,7 +1285,7 @@ int gh_misfit_and_grad(gh_ctx *c, const double *x, double out3[3], double *grad,
     TRY(launch_sweep(c, a));
     TRY(scal_ready(c, o));
     HIPCHK(c, hipMemcpyAsync(c->h_scal, o.scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    const bool cg_on = cross_gradient_on(c);
+    const bool cg_on = coupling_on(c);
     if (cg_on) HIPCHK(c, hipMemcpyAsync(c->h_scal + 8, o.phi, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     TRY(d2h(c, grad, c->tmpM, (size_t)c->M));
     if (dpre) TRY(d2h_obsvec(c, dpre, o.d));
@@ -1188,8 +1304,10 @@ int gh_reg_eval(gh_ctx *c, int kind, double beta, const int shape3[3], int ms_gr
     if (kind < 0 || kind > 3)
         return fail(c, GH_ERR_ARG, "Please choose regularization from 'MS','Damping', 'Smoothness', 'TV'.");
     if (kind == GH_REG_SMOOTHNESS || kind == GH_REG_TV)
-        if (!shape3 || (int64_t)shape3[0] * shape3[1] * shape3[2] * (c->joint ? 2 : 1) != c->M)
+        if (!shape3 || (int64_t)shape3[0] * shape3[1] * shape3[2] * reg_props(c) != c->M)
             return fail(c, GH_ERR_ARG, c->joint ? "gh_reg_eval: Smoothness/TV on the joint kernel need shape nz*ny*nx == M/2"
+                                       : c->mvi ? "gh_reg_eval: Smoothness/TV on the magnetization-vector store need shape "
+                                                  "nz*ny*nx == M/3"
                                                 : "gh_reg_eval: Smoothness/TV need shape nz*ny*nx == M");
     if (kind == GH_REG_MS) TRY(need(c, c->weighted, "gh_reg_eval: MS needs gh_weight first (uses Wm^2)"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -1197,13 +1315,17 @@ int gh_reg_eval(gh_ctx *c, int kind, double beta, const int shape3[3], int ms_gr
     double *dx = c->xb[3], *dapr = c->st[3].greg, *dg = c->tmpM;
     TRY(h2d(c, dx, mw, (size_t)c->M));
     TRY(h2d(c, dapr, mwapr, (size_t)c->M));
+    // (joint and magnetization-vector stores: one property at a time, in one launch -- fd3djoint: the stencil never
+    // crosses into the next block)
+    const int props = reg_props(c);
+    const int64_t m = c->M / props;
     RegArgs ra{};
     ra.ms_grad_den_mw = ms_grad_den_mw;
     ra.kind = kind;
-    ra.M = c->M;
+    ra.M = m;
     ra.nz = shape3 ? shape3[0] : 1;
     ra.ny = shape3 ? shape3[1] : 1;
-    ra.nx = shape3 ? shape3[2] : (int)c->M;
+    ra.nx = shape3 ? shape3[2] : (int)m;
     ra.alpha = 1.0;
     ra.beta = beta;
     ra.x = dx;
@@ -1211,26 +1333,10 @@ int gh_reg_eval(gh_ctx *c, int kind, double beta, const int shape3[3], int ms_gr
     ra.wm2 = c->wm2;
     ra.greg = dg;
     ra.regpart = c->regpart;
-    if (c->joint) {
-        // one property at a time (fd3djoint: the stencil never crosses into the other block)
-        const int64_t m = c->M / 2;
-        const int nrb = (int)((m + 255) / 256);
-        for (int h = 0; h < 2; ++h) {
-            RegArgs rh = ra;
-            rh.M = m;
-            if (!shape3) rh.nx = (int)m;
-            rh.x = dx + h * m;
-            rh.mwapr = dapr + h * m;
-            rh.wm2 = c->wm2 + h * m;
-            rh.greg = dg + h * m;
-            rh.regpart = c->regpart + h * nrb;
-            reg_kernel<<<dim3(nrb), dim3(256), 0, c->stream>>>(rh);
-        }
-        sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->regpart, 2 * nrb, c->st[3].scal);
-    } else {
-        reg_kernel<<<dim3(c->n_regpart), dim3(256), 0, c->stream>>>(ra);
-        sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->regpart, c->n_regpart, c->st[3].scal);
-    }
+    ra.nprop = props;
+    ra.nrb = (int)((m + 255) / 256);
+    reg_kernel<<<dim3(c->n_regpart), dim3(256), 0, c->stream>>>(ra);
+    sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->regpart, c->n_regpart, c->st[3].scal);
     HIPCHK(c, hipGetLastError());
     TRY(d2h(c, c->h_scal, c->st[3].scal, 2));
     *value = c->h_scal[0];
@@ -1410,7 +1516,7 @@ int gh_chain_init(gh_ctx *c, const double *x0, const double *low, const double *
     TRY(scal_ready(c, c->st[0]));
     TRY(d2h(c, c->h_scal, c->st[0].scal, 4));
     c->cg.phi_cur = 0.0;
-    if (cross_gradient_on(c)) {
+    if (coupling_on(c)) {
         TRY(d2h(c, c->h_scal + 8, c->st[0].phi, 1));
         c->cg.phi_cur = c->h_scal[8];
     }

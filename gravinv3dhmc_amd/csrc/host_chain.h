@@ -139,7 +139,7 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
     TRY(scal_ready(c, c->st[sin]));
     if (spec) TRY(scal_ready(c, c->st[ss]));
     HIPCHK(c, hipMemcpyAsync(h, c->st[sin].scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    const bool cg_on = cross_gradient_on(c);
+    const bool cg_on = coupling_on(c);  // (cross-gradient or amplitude term: Phi has a slot per state set)
     if (cg_on) HIPCHK(c, hipMemcpyAsync(h + 8, c->st[sin].phi, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h + 16, c->pp_part, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost,
                              c->stream));

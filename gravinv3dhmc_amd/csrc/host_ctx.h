@@ -61,6 +61,18 @@ struct gh_ctx {
         double *bsum = nullptr;              // n x (slab rows): sums of the slab rows per block (slab_block_sums_kernel)
         double *bmean = nullptr;             // n: the blocks' means of the last evaluation's prediction
     } mc;
+    // GH_CELL_PRISM_MVI: A = [A_x | A_y | A_z] of the same M / 3 prisms at the same N points, an ordinary dense
+    // N x M store whose model vectors are property-major (mx of every cell, then my, then mz)
+    bool mvi = false;
+    // ... and its amplitude coupling (gh_set_amplitude): lambda > 0 switches it on.  (Phi of the chain's state and
+    // of the last evaluation are kept with the cross-gradient term's, cg.phi_cur / cg.phi_last: a context has
+    // at most one of the two couplings.)
+    struct Amp {
+        bool set = false;  // sw is resident
+        double lambda = 0.0, beta = 1.0, scale = 1.0;
+        double *sw = nullptr, *abuf = nullptr;  // winv / scale (M); the amplitudes of gh_amplitude_eval (M / 3)
+    } amp;
+    double *amppart = nullptr;  // partials of Phi where the epilogue keeps none (summed by finish_kernel)
     bool have_obs = false, have_cells = false, have_G = false, weighted = false;
     double *G = nullptr;
     int64_t warn_cells = 0, leaves = 0;
@@ -155,7 +167,7 @@ struct gh_ctx {
     struct StateSet {
         double *r = nullptr, *greg = nullptr, *d = nullptr, *scal = nullptr;
         double *part = nullptr;        // |r|^2 and R partials of a one-launch epilogue
-        double *phi = nullptr;         // joint store: Phi of the cross-gradient coupling (scal_cg_kernel)
+        double *phi = nullptr;         // Phi of the coupling term (joint store: cross-gradient; MVI store: amplitude)
         mutable bool pending = false;  // scal[0..2] still to be summed from `part` (scal_ready)
     } st[4];
     double *xb[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -76,6 +76,45 @@ static bool cross_gradient_on(const gh_ctx *c)
     return c->joint && c->cg.set && c->cg.lambda > 0.0;
 }
 
+// The amplitude coupling of the magnetization-vector store at x (M = 3m): g (or null) takes lambda dPhi/dmw -- added
+// to what is there (the epilogue: behind the regulariser) or stored --, amp (or null) the cells' amplitudes, part
+// the ceil(m / 256) partials of Phi.
+static void launch_amplitude(gh_ctx *c, const double *x, double lambda, double *g, bool add, double *amp, double *part)
+{
+    AmpArgs a{};
+    a.m = c->M / 3;
+    a.lambda = lambda;
+    a.beta = c->amp.beta;
+    a.scale = c->amp.scale;
+    a.x = x;
+    a.sw = c->amp.sw;
+    a.g = g;
+    a.amp = amp;
+    a.part = part;
+    const dim3 grid((unsigned)((a.m + 255) / 256));
+    if (add)
+        amplitude_kernel<true><<<grid, dim3(256), 0, c->stream>>>(a);
+    else
+        amplitude_kernel<false><<<grid, dim3(256), 0, c->stream>>>(a);
+}
+
+static bool amplitude_on(const gh_ctx *c)
+{
+    return c->mvi && c->amp.set && c->amp.lambda > 0.0;
+}
+
+// a coupling term rides on the evaluations: its Phi has a slot per state set and lambda Phi is part of U
+static bool coupling_on(const gh_ctx *c)
+{
+    return cross_gradient_on(c) || amplitude_on(c);
+}
+
+// properties stacked in the model vector, each regularised on its own (RegArgs::nprop)
+static int reg_props(const gh_ctx *c)
+{
+    return c->joint ? 2 : c->mvi ? 3 : 1;
+}
+
 static int finalize_joint(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
 {
     const int half = c->grid / 2;
@@ -153,6 +192,15 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
     ra.wm2 = c->wm2;
     ra.greg = greg_out;
     ra.regpart = c->regpart;
+    if (c->mvi) {
+        // (three properties of one mesh: the regulariser block by block on each, RegArgs::nprop)
+        ra.M = c->M / 3;
+        ra.nprop = 3;
+        ra.nrb = (int)((ra.M + 255) / 256);
+    }
+    // (magnetization-vector store, coupling on: one launch behind the regulariser's adds lambda grad Phi; its
+    // partials go behind those of R where the epilogue leaves partials, else to a buffer finish_kernel sums)
+    const bool amp_on = amplitude_on(c);
     const double *gfix = c->have_fix ? c->gfix : nullptr;
     const double *regpart = c->regpart;
     int n_regpart = c->n_regpart;
@@ -298,6 +346,7 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
         } else {
             reduce_finish_kernel<false><<<dim3((unsigned)(c->n_dpart + c->n_regpart)), dim3(256), 0, c->stream>>>(fa);
         }
+        if (amp_on) launch_amplitude(c, x, c->amp.lambda, greg_out, true, nullptr, o.part + c->n_dpart + c->n_regpart);
         HIPCHK(c, hipGetLastError());
         o.pending = true;
         return GH_OK;
@@ -314,7 +363,14 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
         nseg = c->slab_live > 0 ? c->slab_live : c->grid;
     }
     o.pending = false;
-    FinishArgs fa;
+    FinishArgs fa{};
+    if (amp_on) {
+        launch_amplitude(c, x, c->amp.lambda, greg_out, true, nullptr, c->amppart);
+        fa.cpart = c->amppart;
+        fa.n_cpart = (int)((c->M / 3 + 255) / 256);
+        fa.lambda = c->amp.lambda;
+        fa.phi = o.phi;
+    }
     fa.N = c->N;
     fa.ld = c->ld;
     fa.nseg = nseg;
@@ -341,6 +397,8 @@ static int scal_ready(gh_ctx *c, const gh_ctx::StateSet &o)
     const int nr = c->joint ? 2 * (int)((c->M / 2 + 255) / 256) : c->n_regpart;
     if (cross_gradient_on(c))
         scal_cg_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(o.part, nd, nr, nr / 2, c->alpha, c->cg.lambda, o.scal, o.phi);
+    else if (amplitude_on(c))
+        scal_cg_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(o.part, nd, nr, nr / 3, c->alpha, c->amp.lambda, o.scal, o.phi);
     else
         scal_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(o.part, nd, nr, c->alpha, o.scal);
     HIPCHK(c, hipGetLastError());
@@ -404,10 +462,20 @@ static int ensure_work(gh_ctx *c)
         for (int i = 0; i < 4; ++i) TRY(dalloc(c, &c->st[i].part, (size_t)c->n_dpart + (size_t)((c->M + 255) / 256)));
     } else if (c->ld >= 2048 && ((c->TW > 1 && c->n_panels == 1 && !c->mf) || lonsym_on(c)) && env_int("GRAVHMC_EPILOGUE1", 1) != 0) {
         TRY(dalloc(c, &c->dsum, (size_t)std::max(std::max(c->grid, 128), lonsym_on(c) ? lonsym_classes(c) : 0)));
-        for (int i = 0; i < 4; ++i) TRY(dalloc(c, &c->st[i].part, (size_t)c->n_dpart + (size_t)((c->M + 255) / 256)));
+        // (magnetization-vector store: up to three more partials of R, its blocks being counted per property, and
+        // behind them those of the amplitude term, one per 256 cells)
+        for (int i = 0; i < 4; ++i)
+            TRY(dalloc(c, &c->st[i].part, (size_t)c->n_dpart + (size_t)((c->M + 255) / 256) +
+                                              (c->mvi ? 3 + (size_t)((c->M / 3 + 255) / 256) : 0)));
     }
-    // (joint store: the regulariser runs per property, ceil(m / 256) blocks each)
-    c->n_regpart = c->joint ? 2 * (int)((c->M / 2 + 255) / 256) : (int)((c->M + 255) / 256);
+    if (c->mvi) {
+        // Phi of the amplitude term per state set, and its partials where the epilogue keeps none (finish_kernel)
+        TRY(dalloc(c, &c->cg.phi_all, 4));
+        for (int i = 0; i < 4; ++i) c->st[i].phi = c->cg.phi_all + i;
+        TRY(dalloc(c, &c->amppart, (size_t)((c->M / 3 + 255) / 256)));
+    }
+    // (joint and magnetization-vector stores: the regulariser runs per property, ceil(m / 256) blocks each)
+    c->n_regpart = reg_props(c) * (int)((c->M / reg_props(c) + 255) / 256);
     c->n_pp0 = (int)std::min<int64_t>(1024, (c->M + 255) / 256);
     TRY(dalloc(c, &c->dpart, (size_t)c->n_dpart));
     TRY(dalloc(c, &c->regpart, (size_t)c->n_regpart));

@@ -42,8 +42,9 @@ static bool resident_plan(gh_ctx *c)
     if (r.state != 0) return r.state > 0;
     r.state = -1;
     if (env_int("GRAVHMC_RESIDENT", 1) == 0) return false;
-    // (the joint gravity-magnetic store and the multi-component store run their chains on the fused sweep)
-    if (c->mf || c->joint || c->mc.n > 0 || c->sh.kind != 0 || c->n_panels != 1 || c->ld > 1024 || !c->G) return false;
+    // (the joint gravity-magnetic store, the multi-component store and the magnetization-vector store run their
+    // chains on the fused sweep)
+    if (c->mf || c->joint || c->mc.n > 0 || c->mvi || c->sh.kind != 0 || c->n_panels != 1 || c->ld > 1024 || !c->G) return false;
     int lds_max = 0;
     if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) != hipSuccess)
         return false;

@@ -455,6 +455,11 @@ struct RegArgs {
     // (model and prior model) as received from the neighbouring ranks; all zero when unsharded
     int64_t k0;
     const double *xlo, *xhi, *alo, *ahi;
+    // several properties of the same mesh stacked in one model vector, property-major (the joint store's 2, the
+    // magnetization-vector store's 3): nprop > 1 makes M, nz, ny, nx those of ONE property, gives each property
+    // nrb = ceil(M / 256) blocks and applies the regulariser to each property on its own (the block-diagonal
+    // fd3djoint: nothing crosses from one property into the next).  0 or 1: one property, as ever.
+    int nprop, nrb;
 };
 
 // Stencil regularisers (Smoothness, TV), first half: model and prior model of the six neighbours of
@@ -561,9 +566,20 @@ __device__ __forceinline__ double reg_cell(const RegArgs &a, int64_t j, double x
 template <bool HALO = false>
 __device__ __forceinline__ void reg_block(const RegArgs &a, int blk, double *red)
 {
-    const int64_t j = (int64_t)blk * 256 + threadIdx.x;
     double val = 0.0;
-    if (j < a.M) a.greg[j] = a.alpha * reg_cell<HALO>(a, j, a.x[j], val);
+    if (a.nprop > 1) {
+        // block blk is block blk % nrb of property blk / nrb: the same cell code on that property's M entries
+        const int h = blk / a.nrb;
+        RegArgs p = a;
+        p.x += h * a.M;
+        p.mwapr += h * a.M;
+        p.wm2 += h * a.M;
+        const int64_t j = (int64_t)(blk - h * a.nrb) * 256 + threadIdx.x;
+        if (j < a.M) a.greg[h * a.M + j] = a.alpha * reg_cell<HALO>(p, j, p.x[j], val);
+    } else {
+        const int64_t j = (int64_t)blk * 256 + threadIdx.x;
+        if (j < a.M) a.greg[j] = a.alpha * reg_cell<HALO>(a, j, a.x[j], val);
+    }
     const double tot = block_allreduce_sum(val, red, 4);
     if (threadIdx.x == 0) a.regpart[blk] = tot;
 }
@@ -687,8 +703,9 @@ __global__ void __launch_bounds__(256) cross_gradient_kernel(CrossGradArgs a)
     if (threadIdx.x == 0) a.part[blockIdx.x] = tot;
 }
 
-// scal_kernel of a joint evaluation with the coupling on: the same sums in the same order, U takes
-// lambda Phi, and Phi (n_cgpart partials behind those of R) goes to a slot of its own
+// scal_kernel of an evaluation with a coupling term on (the joint store's cross-gradient, the magnetization-vector
+// store's amplitude term): the same sums in the same order, U takes lambda Phi, and Phi (n_cgpart partials behind
+// those of R) goes to a slot of its own
 __global__ void __launch_bounds__(1024) scal_cg_kernel(const double *part, int n_dpart, int n_regpart, int n_cgpart,
                                                        double alpha, double lambda, double *scal, double *phi)
 {
@@ -707,6 +724,54 @@ __global__ void __launch_bounds__(1024) scal_cg_kernel(const double *part, int n
         phi[0] = Phi;
     }
 }
+
+// Amplitude coupling of the magnetization-vector store (GH_CELL_PRISM_MVI): the minimum-support functional of the
+// cells' amplitude, Phi = sum_c s_c / (s_c + beta), s_c = u_x^2 + u_y^2 + u_z^2 of the physical, normalised
+// components u_a[c] = mw[a m + c] winv[a m + c] / scale.  It is the one term that ties the three blocks together.
+struct AmpArgs {
+    int64_t m;         // cells (entries per component)
+    double lambda;     // factor of the gradient (the partials of Phi are not scaled)
+    double beta, scale;
+    const double *x;   // 3m: the stacked weighted model
+    const double *sw;  // 3m: winv / scale of every entry (u = x sw)
+    double *g;         // 3m or null: lambda dPhi/dmw, added (ADD) or stored
+    double *amp;       // m or null: the physical amplitude scale sqrt(s_c)
+    double *part;      // one partial of Phi per block
+};
+
+// One cell per thread, the three components in one launch; dPhi/du_a = 2 beta u_a / (s + beta)^2.  No atomics;
+// the block's sum of Phi goes to part[blockIdx.x].
+template <bool ADD>
+__global__ void __launch_bounds__(256) amplitude_kernel(AmpArgs a)
+{
+    __shared__ double red[4];
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double phi = 0.0;
+    if (p < a.m) {
+        double u[3], s = 0.0;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            u[q] = a.x[q * a.m + p] * a.sw[q * a.m + p];
+            s += u[q] * u[q];
+        }
+        const double den = s + a.beta;
+        phi = s / den;
+        if (a.g) {
+            const double f = (2.0 * a.beta) / (den * den);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const double dq = a.lambda * ((f * u[q]) * a.sw[q * a.m + p]);
+                a.g[q * a.m + p] = ADD ? a.g[q * a.m + p] + dq : dq;
+            }
+        }
+        if (a.amp) a.amp[p] = a.scale * sqrt(s);
+    }
+    const double tot = block_allreduce_sum(phi, red, 4);
+    if (threadIdx.x == 0) a.part[blockIdx.x] = tot;
+}
+// (both forms exist wherever this header is compiled, also on its own for the build's code check)
+template __global__ void amplitude_kernel<true>(AmpArgs);
+template __global__ void amplitude_kernel<false>(AmpArgs);
 
 // One launch for the two independent halves of the per-step epilogue: blocks [0, n_red) sum the
 // slab rows of one segment for 32 observations each (first stage of the slab reduction, same
@@ -903,7 +968,27 @@ struct FinishArgs {
     double *d;     // ld: forward product d = sum of the segments
     double *r;     // ld (zero padded)
     double *scal;  // [0]=U_data [1]=R [2]=U [3]=mean(dinv)
+    // a coupling term whose partials are at hand (the magnetization-vector store's amplitude term), or null:
+    // U takes lambda Phi, Phi goes to phi[0]
+    const double *cpart;
+    int n_cpart;
+    double lambda;
+    double *phi;
 };
+
+// U of finish_kernel: ud + alpha R, plus lambda Phi of a coupling term summed here in sum_kernel's order
+__device__ __forceinline__ double finish_total(const FinishArgs &a, double ud, double R, double *red)
+{
+    double U = ud + a.alpha * R;
+    if (a.cpart) {
+        double sp = 0.0;
+        for (int t = threadIdx.x; t < a.n_cpart; t += 1024) sp += a.cpart[t];
+        const double Phi = block_allreduce_sum(sp, red, 16);
+        U = U + a.lambda * Phi;
+        if (threadIdx.x == 0) a.phi[0] = Phi;
+    }
+    return U;
+}
 
 // Single block: last stage of the slab reduction, mean removal, residual, data misfit
 // (potential.py:700-706) and U = U_d + alpha R.  The segment sum uses the association order of
@@ -958,10 +1043,11 @@ __global__ void __launch_bounds__(1024) finish_kernel(FinishArgs a)
         double rs = 0.0;
         for (int t = threadIdx.x; t < a.n_regpart; t += 1024) rs += a.regpart[t];
         const double R = block_allreduce_sum(rs, red, 16);
+        const double U = finish_total(a, ud, R, red);
         if (threadIdx.x == 0) {
             a.scal[0] = ud;
             a.scal[1] = R;
-            a.scal[2] = ud + a.alpha * R;
+            a.scal[2] = U;
             a.scal[3] = mean;
         }
         return;
@@ -995,10 +1081,11 @@ __global__ void __launch_bounds__(1024) finish_kernel(FinishArgs a)
     double rs = 0.0;
     for (int t = threadIdx.x; t < a.n_regpart; t += 1024) rs += a.regpart[t];
     const double R = block_allreduce_sum(rs, red, 16);
+    const double U = finish_total(a, ud, R, red);
     if (threadIdx.x == 0) {
         a.scal[0] = ud;
         a.scal[1] = R;
-        a.scal[2] = ud + a.alpha * R;
+        a.scal[2] = U;
         a.scal[3] = mean;
     }
 }
@@ -1519,6 +1606,58 @@ prism_joint_kernel(const double *__restrict__ xp, const double *__restrict__ yp,
         }
         H[idx] = vg;
         H[idx + ld * m] = vt;
+    }
+}
+
+// Magnetization-vector store (GH_CELL_PRISM_MVI): one thread per (obs, cell) pair writes the pair's entry of all
+// three blocks of A = [A_x | A_y | A_z], to columns c, m + c and 2m + c.  Block a is the total-field anomaly of
+// the prisms magnetized 1 A/m along axis a: prism_tf_corner with m = e_a, where b = V e_a is column a of V
+// exactly (v * 1 + v' * 0 + v'' * 0), so the entry's corner term is f . (column a of V) in the reference's order
+// fx bx + fy by + fz bz.  The six second derivatives of a corner -- three atan2 and three log -- are evaluated
+// ONCE and serve the three accumulators; three prism_kernel<PRISM_TF> passes would evaluate them three times.
+__global__ void __launch_bounds__(256)
+prism_mvi_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
+                 const double *__restrict__ bounds6, int64_t N, int64_t m, int64_t ld, double3 dir,
+                 double *__restrict__ A)
+{
+#pragma clang fp contract(off)
+    const double fx = dir.x, fy = dir.y, fz = dir.z;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ld * m;
+         idx += (int64_t)gridDim.x * 256) {
+        const int64_t c = idx / ld, l = idx - c * ld;
+        double ax = 0.0, ay = 0.0, az = 0.0;
+        if (l < N) {
+            const double px = xp[l], py = yp[l], pz = zp[l];
+            const double *b = bounds6 + 6 * c;
+            const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const double dz = Z[k] - pz;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const double dy = Y[j] - py;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const double dx = X[i] - px;
+                        const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
+                        const double r = sqrt(dx * dx + dy * dy + dz * dz);
+                        const double v1 = -safe_atan2_d(dz * dy, dx * r);
+                        const double v2 = safe_log_d(dz + r);
+                        const double v3 = safe_log_d(dy + r);
+                        const double v4 = -safe_atan2_d(dz * dx, dy * r);
+                        const double v5 = safe_log_d(dx + r);
+                        const double v6 = -safe_atan2_d(dx * dy, dz * r);
+                        ax += sign * (fx * v1 + fy * v2 + fz * v3);
+                        ay += sign * (fx * v2 + fy * v4 + fz * v5);
+                        az += sign * (fx * v3 + fy * v5 + fz * v6);
+                    }
+                }
+            }
+        }
+        // (coalesced: consecutive threads, consecutive rows of one column, in each of the three blocks)
+        A[c * ld + l] = ax * TF_SCALE;
+        A[(m + c) * ld + l] = ay * TF_SCALE;
+        A[(2 * m + c) * ld + l] = az * TF_SCALE;
     }
 }
 

@@ -167,6 +167,42 @@ class Engine(object):
                                                ptr(w)))
         self.multi = len(comps)
 
+    def set_cells_mvi(self, bounds6, direction):
+        """The M/3 prisms (bounds (M/3, 6)) of a magnetization-vector model (gh_set_cells_mvi): three unknowns
+        (mx, my, mz) per prism, model vectors property-major, the total field along direction = (fx, fy, fz);
+        call it before set_obs."""
+        b = f64(bounds6)
+        if self.M % 3 != 0 or b.shape != (self.M // 3, 6):
+            raise ValueError("bounds table of a magnetization-vector model must be (M/3, 6)")
+        if direction is None or len(direction) != 3:
+            raise ValueError("the magnetization-vector kernel's total field needs direction = (fx, fy, fz)")
+        fx, fy, fz = (float(v) for v in direction)
+        self._chk(self._lib.gh_set_cells_mvi(self._h, ptr(b), fx, fy, fz))
+        self.mvi = True
+
+    def set_amplitude(self, lam, beta, scale=1.0):
+        """Amplitude coupling lam * sum_c s_c / (s_c + beta) of a weighted magnetization-vector context
+        (gh_set_amplitude), s_c the squared amplitude of cell c's physical vector over scale.  lam = 0 switches the
+        term off."""
+        self._chk(self._lib.gh_set_amplitude(self._h, float(lam), float(beta), float(scale)))
+        self._chain_valid = False
+
+    def amplitude_eval(self, mw, want_grad=True, want_amp=True):
+        """(Phi, dPhi/dmw or None, the cells' amplitudes (M/3) or None) of the amplitude term alone, lam = 1, with beta
+        and scale of the last set_amplitude (gh_amplitude_eval)."""
+        mw = self._vecM(mw, "mw")
+        val = C.c_double(0)
+        grad = np.empty(self.M) if want_grad else None
+        amp = np.empty(self.M // 3) if want_amp else None
+        self._chk(self._lib.gh_amplitude_eval(self._h, ptr(mw), C.byref(val), ptr(grad), ptr(amp)))
+        return val.value, grad, amp
+
+    def amplitude_last(self):
+        """Phi of the last misfit_and_grad, or of the state the chain is in (gh_amplitude_last); 0 while off."""
+        val = C.c_double(0)
+        self._chk(self._lib.gh_amplitude_last(self._h, C.byref(val)))
+        return val.value
+
     def multi_info(self):
         """The row blocks of a multi-component context (gh_multi_info): components (COMP_* values), weights, the
         per-block means of the last evaluation's prediction Aw mw and of the weighted observations."""
@@ -179,11 +215,12 @@ class Engine(object):
                 "obs_mean": om[:k].copy()}
 
     def tf_result(self, mag3):
-        """Total-field anomaly (uT) of the CELL_PRISM_TF cells magnetized with mag3[M, 3] (A/m), in the
+        """Total-field anomaly (uT) of the CELL_PRISM_TF or CELL_PRISM_MVI cells magnetized with mag3[M, 3] (A/m), in the
         reference's accumulation order (gh_tf_result); needs no G."""
         m = f64(mag3)
-        if m.shape != (self.M, 3):
-            raise ValueError("magnetization must be (M, 3)")
+        cells = self.M // 3 if getattr(self, "mvi", False) else self.M   # (magnetization-vector context: M/3 prisms)
+        if m.shape != (cells, 3):
+            raise ValueError("magnetization must be (%s, 3)" % ("M/3" if cells != self.M else "M"))
         out = np.empty(self.N)
         self._chk(self._lib.gh_tf_result(self._h, ptr(m), ptr(out)))
         return out

@@ -344,6 +344,9 @@ def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
     if getattr(model._engine, "multi", 0):
         raise NotImplementedError("HMCSampleBatch does not run the multi-component store (MultiComponentModule): "
                                   "sample its chains one at a time with HMCSample")
+    if getattr(model._engine, "mvi", False):
+        raise NotImplementedError("HMCSampleBatch does not run the magnetization-vector store (MagVectorModule): "
+                                  "sample its chains one at a time with HMCSample")
     eng = model._engine
     _, WmInv, Wm = model.kernelw()
     low, high = Wm @ boundaries[:, 0], Wm @ boundaries[:, 1]

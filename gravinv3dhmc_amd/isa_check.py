@@ -14,6 +14,10 @@ seen in the code it generated, so the build checks THAT code, with the hipcc tha
   `s_waitcnt vmcnt(n)` covers a load once at least n vector-memory instructions were issued behind it
   (gfx9 counts loads and stores in the same counter, in order).
 
+The same compile also serves `scan_plain_kernels()`: the kernels listed in PLAIN_KERNELS (the magnetization-vector
+store's assembly and amplitude term) must be in the generated code and must not spill, by the compiler's resource
+report.
+
 `check()` returns the list of findings (empty: clean).  `stamp()` records the verdict next to the
 library together with the compiler's version; `_lib.load()` switches the team form off
 (GRAVHMC_BATCH_TEAM=0: the two-pass kernels need no hand-counted waits) when the stamp is missing or
@@ -31,6 +35,8 @@ STAMP = os.path.join(_HERE, "libgravhmc.isa.json")
 HEADERS = ("kernels.hip.h", "batch.hip.h", "exchange.hip.h", "resident.hip.h", "mfbatch.hip.h", "batchteam.hip.h")
 SYMBOL = "_ZN3ghk17batch_team_kernelENS_12BatchAdjArgsENS_6BtArgsE"
 _VMEM = re.compile(r"(global|buffer|flat|scratch)_(load|store|atomic)")
+#: kernels held to "present and no spills" (every instantiation whose name contains the entry)
+PLAIN_KERNELS = ("prism_mvi_kernel", "amplitude_kernel")
 
 
 def hipcc_version(hipcc):
@@ -130,8 +136,28 @@ def scan(asm_text, report_text):
     return bad
 
 
-def check(hipcc, workdir=None):
-    """Compile the kernels' headers to gfx950 assembly with `hipcc` and scan batch_team_kernel."""
+def scan_plain_kernels(asm_text, report_text, names=PLAIN_KERNELS):
+    """Findings for the kernels in `names`: a kernel missing from the generated code, or one that spills by the
+    compiler's resource report."""
+    bad = []
+    for name in names:
+        if not re.search(r"^_Z\w*%s\w*:" % re.escape(name), asm_text, flags=re.M):
+            bad.append("%s: not in the generated code" % name)
+            continue
+        reports = list(re.finditer(r"Function Name: (\S*%s\S*)" % re.escape(name), report_text))
+        if not reports:
+            bad.append("%s: no resource report" % name)
+        for m in reports:
+            rep = report_text[m.start():]
+            rep = rep[:rep.index("LDS Size")]
+            if not (re.search(r"ScratchSize \[bytes/lane\]: 0\b", rep) and re.search(r"VGPRs Spill: 0\b", rep)):
+                bad.append("%s spills: %s" % (m.group(1), " ".join(rep.split())[:300]))
+    return bad
+
+
+def check_all(hipcc, workdir=None):
+    """Compile the kernels' headers to gfx950 assembly with `hipcc`: (findings of the batch_team_kernel scan,
+    findings of the PLAIN_KERNELS scan)."""
     own = workdir is None
     d = tempfile.mkdtemp(prefix="gravhmc_isa_") if own else str(workdir)
     try:
@@ -141,23 +167,37 @@ def check(hipcc, workdir=None):
         out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", tu,
                               "-o", asm, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
         if out.returncode != 0:
-            return ["hipcc -S failed: " + out.stderr[-1500:]]
+            return ["hipcc -S failed: " + out.stderr[-1500:]], []
+        text = open(asm).read()
         try:
-            return scan(open(asm).read(), out.stderr)
+            team = scan(text, out.stderr)
         except (ValueError, StopIteration) as e:   # the code no longer has the shape the scan knows
-            return ["scan could not find its landmarks in the generated code: %r" % (e,)]
+            team = ["scan could not find its landmarks in the generated code: %r" % (e,)]
+        try:
+            plain = scan_plain_kernels(text, out.stderr)
+        except ValueError as e:
+            plain = ["plain-kernel scan could not find its landmarks in the generated code: %r" % (e,)]
+        return team, plain
     finally:
         if own:
             import shutil
             shutil.rmtree(d, ignore_errors=True)
 
 
+def check(hipcc, workdir=None):
+    """Every finding of both scans (empty: clean)."""
+    team, plain = check_all(hipcc, workdir)
+    return team + plain
+
+
 def stamp(hipcc):
-    """Run the check and record {compiler, findings} next to the library.  Returns the findings."""
-    bad = check(hipcc)
+    """Run the checks and record {compiler, findings, plain_findings} next to the library: `findings` are
+    batch_team_kernel's (they alone decide on the team form), `plain_findings` those of PLAIN_KERNELS.  Returns
+    all of them."""
+    team, plain = check_all(hipcc)
     with open(STAMP, "w") as f:
-        json.dump({"hipcc": hipcc_version(hipcc), "findings": bad}, f, indent=1)
-    return bad
+        json.dump({"hipcc": hipcc_version(hipcc), "findings": team, "plain_findings": plain}, f, indent=1)
+    return team + plain
 
 
 def team_form_cleared():

@@ -83,9 +83,10 @@ typedef enum {
  * GH_CELL_PRISM_COMP: prisms, one gravity field other than gz (set with gh_set_cells_prism);
  * GH_CELL_TESSEROID_COMP: tesseroids, one gravity field other than gz (set with gh_set_cells_tess);
  * GH_CELL_PRISM_JOINT: prisms, gz and the total field inverted together (set with gh_set_cells_joint);
- * GH_CELL_PRISM_MULTI: prisms, several gravity fields of one density model inverted together (gh_set_cells_multi) */
+ * GH_CELL_PRISM_MULTI: prisms, several gravity fields of one density model inverted together (gh_set_cells_multi);
+ * GH_CELL_PRISM_MVI: prisms, the total field of a magnetization VECTOR per cell (gh_set_cells_mvi) */
 enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2, GH_CELL_PRISM_COMP = 3, GH_CELL_TESSEROID_COMP = 4,
-       GH_CELL_PRISM_JOINT = 5, GH_CELL_PRISM_MULTI = 6 };
+       GH_CELL_PRISM_JOINT = 5, GH_CELL_PRISM_MULTI = 6, GH_CELL_PRISM_MVI = 7 };
 /* components a GH_CELL_PRISM_MULTI context stacks at most: every GH_COMP_* once */
 #define GH_MULTI_MAX 11
 /* The gravity fields of prisms (gravmag/prism.py:875-972), for gh_set_cells_prism, and of tesseroids
@@ -139,6 +140,47 @@ int gh_set_cells_tf(gh_ctx *ctx, const double *bounds6, double fx, double fy, do
  * in uT, accumulated corner by corner, cell by cell in mesh order into one sum per observation and
  * scaled once, as the reference does. */
 int gh_tf_result(gh_ctx *ctx, const double *mag3, double *result);
+/* Magnetization vector inversion in Cartesian form (GH_CELL_PRISM_MVI; Lelievre & Oldenburg 2009): three unknowns
+ * (mx, my, mz) in A/m per prism instead of one magnetization along the field, so that remanence may turn the
+ * magnetization away from it.  Call on a fresh context whose M is THREE TIMES the number of prisms (bounds6:
+ * M/3 x 6 row-major x1,x2,y1,y2,z1,z2 in mesh order), (fx, fy, fz) = dircos(inc, dec) of the regional field.
+ * Axes: x north, y east, z down.  Model-space vectors are property-major: [mx of every cell; my; mz].
+ * The kernel is A = [A_x | A_y | A_z], an ordinary dense N x M store, column-major with ld rows per column:
+ *     A_a[i, c] = CM*T2NT * sum over the corners of prism c of (+-) f . (V e_a)            (column a M/3 + c)
+ * the total-field anomaly in uT at point i of prism c magnetized 1 A/m along axis a -- what the reference's
+ * _prism.tf accumulates into `res` for that one prism with (mx, my, mz) = e_a, in its operation order
+ * (_prism.pyx:72-111; prism.tf's kernel2d does NOT depend on pmag, it is always the column for m = f).  gh_build_G
+ * assembles the three blocks in ONE launch that evaluates the six second derivatives of a corner once.
+ * Everything the dense single-chain path offers runs on it as on any dense store: gh_weight (column norms over
+ * all M columns), gh_set_data (the mean is removed), gh_forward, gh_adjoint, gh_misfit_and_grad, gh_leapfrog,
+ * gh_chain_*, gh_download_G, the posterior window.  Damping and MS act on the M entries as they are; Smoothness
+ * and TV take shape3 with nz*ny*nx == M/3 and apply the stencil to each component on its own (a shape3 whose
+ * product is M is GH_ERR_ARG).  gh_tf_result takes mag3 of M/3 x 3.
+ * Dense, single chain only: matrix-free, the shift-invariant store, the wavelet compressor, gh_batch_*,
+ * gh_shard_init*, gh_upload_G and N > 16384 return GH_ERR_UNSUPPORTED naming the magnetization-vector store; the
+ * resident chain kernel and the folded store are never chosen (chains run on the fused sweep). */
+int gh_set_cells_mvi(gh_ctx *ctx, const double *bounds6 /* M/3 x 6 */, double fx, double fy, double fz);
+/* Amplitude coupling of a weighted GH_CELL_PRISM_MVI context: the minimum-support functional of the cells'
+ * amplitude, the one term that ties the three components of a cell together (compact bodies).  With
+ *     u_a[c] = mw[a M/3 + c] winv[a M/3 + c] / scale   (winv = 1 / Wm, 0 where Wm is 0),   s_c = sum_a u_a[c]^2,
+ *     Phi = sum_c s_c / (s_c + beta),      dPhi/dmw[a M/3 + c] = 2 beta u_a[c] / (s_c + beta)^2 * winv / scale.
+ * With lambda > 0 every potential evaluation of the context -- gh_misfit_and_grad, gh_leapfrog, gh_chain_* --
+ * becomes U = U_data + alpha R + lambda Phi, grad likewise; the reported U_model stays R (out3[2], out5[2]) and
+ * Phi is read with gh_amplitude_last.  One more kernel launch per evaluation, behind the regulariser's; sums in
+ * a fixed order.  lambda = 0 switches the term off: the context then launches and returns exactly what it did
+ * before the call.  A running chain must be started again (gh_chain_init).  The term keeps winv / scale; a
+ * gh_weight after a new gh_build_G builds it again from the new weights, lambda, beta and scale staying.
+ * Errors: GH_ERR_UNSUPPORTED on any other store; GH_ERR_ARG before gh_weight, for lambda < 0, beta <= 0 or
+ * scale <= 0. */
+int gh_set_amplitude(gh_ctx *ctx, double lambda, double beta, double scale);
+/* The term alone at mw (M entries), lambda = 1, with beta and scale of the last gh_set_amplitude (whatever its
+ * lambda): *value = Phi, grad (M, or NULL) = dPhi/dmw, amp (M/3, or NULL) = the cells' physical amplitudes
+ * scale * sqrt(s_c) = |(mx, my, mz)_c|. */
+int gh_amplitude_eval(gh_ctx *ctx, const double *mw, double *value, double *grad /* M or NULL */,
+                      double *amp /* M/3 or NULL */);
+/* Phi of the last gh_misfit_and_grad, or of the state the chain was left in by the last gh_chain_init /
+ * trajectory (as out5[0..2]); 0 while the coupling is off. */
+int gh_amplitude_last(const gh_ctx *ctx, double *phi);
 /* Joint gravity-magnetic inversion (GH_CELL_PRISM_JOINT, inversion/potential.py:847-1812): the density and
  * the magnetization of the same M/2 prisms (bounds6: M/2 x 6 row-major x1,x2,y1,y2,z1,z2 in mesh order)
  * under the same N/2 observation points.  The kernel is block-diagonal, A = [[A_gz, 0], [0, A_tf]] (N x M;
