@@ -113,6 +113,9 @@ PROTOTYPES = {
     "gh_batch_run": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_int), C.POINTER(_dp), _dp, C.c_double,
                                C.POINTER(C.c_int), _dp, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gh_batch_get_x": (C.c_int, [_ctx, C.c_int, _dp]),
+    "gh_bscg_run": (C.c_int, [_ctx, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                              _dp, _dp, _dp, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gh_bscg_stats": (C.c_int, [_ctx, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gh_posterior_window": (C.c_int, [_ctx, C.c_int]),
     "gh_posterior_add": (C.c_int, [_ctx]),
     "gh_posterior_read": (C.c_int, [_ctx, C.POINTER(_i64), C.POINTER(_i64), _dp, _dp]),

@@ -3,6 +3,7 @@
 #include "../../include/gravhmc.h"
 #include "kernels.hip.h"
 #include "batch.hip.h"
+#include "bscg.hip.h"
 #include "exchange.hip.h"
 #include "resident.hip.h"
 #include "resbatch.hip.h"
@@ -57,6 +58,7 @@ static_assert(MULTI_MAX == GH_MULTI_MAX, "the kernels' row-block table holds the
 #include "host_lonres.h"
 #include "host_batch.h"
 #include "host_batchrun.h"
+#include "host_bscg.h"
 #include "host_chain.h"
 
 // ------------------------------------------------------------------------- C-ABI
@@ -2007,6 +2009,29 @@ int gh_batch_get_x(gh_ctx *c, int chain, double *x)
                                                                                            c->tmpM);
     HIPCHK(c, hipGetLastError());
     return d2h(c, x, c->tmpM, (size_t)c->M);
+}
+
+int gh_bscg_run(gh_ctx *c, int B, const double *counts, const double *dobs, const double *mw0, double rhomin, double rhomax,
+                double beta2, double q, int maxk, double *models, double *dmis, double *mmis, double *alpha, int *n_entries,
+                int *n_alpha)
+{
+    if (!c) return GH_ERR_ARG;
+    TRY(bscg_refuse(c, B, maxk));
+    if (!counts || !dobs || !mw0 || !models || !dmis || !mmis || !alpha || !n_entries || !n_alpha)
+        return fail(c, GH_ERR_ARG, "gh_bscg_run: null pointer");
+    if (!(beta2 > 0.0) || !std::isfinite(beta2) || !std::isfinite(q) || !(rhomin <= rhomax))
+        return fail(c, GH_ERR_ARG, "gh_bscg_run: needs beta2 > 0, a finite q and rhomin <= rhomax");
+    HIPCHK(c, hipSetDevice(c->device));
+    return bscg_run(c, B, counts, dobs, mw0, rhomin, rhomax, beta2, q, maxk, models, dmis, mmis, alpha, n_entries, n_alpha);
+}
+
+int gh_bscg_stats(const gh_ctx *c, int64_t *forward_sweeps, int64_t *adjoint_sweeps, int64_t *lock_steps)
+{
+    if (!c) return GH_ERR_ARG;
+    if (forward_sweeps) *forward_sweeps = c->bs.forward_sweeps;
+    if (adjoint_sweeps) *adjoint_sweeps = c->bs.adjoint_sweeps;
+    if (lock_steps) *lock_steps = c->bs.lock_steps;
+    return GH_OK;
 }
 
 int gh_leapfrog(gh_ctx *c, double *x_inout, const double *p0, double dt, int L, const double *low,

@@ -303,6 +303,18 @@ struct gh_ctx {
         }
     } bt;
 
+    // bootstrap replicates of the CG inversion in lock-step (bscg.hip.h, host_bscg.h); the M x 16 and ld x 16
+    // vectors live in the chain batch's buffers
+    struct Bscg {
+        ghk::BscgState *st = nullptr;  // 16 slots
+        double *crow = nullptr;        // B x N counts as the host passes them
+        double *dobs = nullptr, *mw0 = nullptr, *iw = nullptr;
+        double *dirpart = nullptr, *mspart = nullptr;  // per-block partials of Iw.I, |Iw|^2 / of MS(x_new)
+        double *res = nullptr;         // result rows: data misfit, model misfit, regularisation factors
+        int res_maxk = 0, nblk = 0;
+        int64_t forward_sweeps = 0, adjoint_sweeps = 0, lock_steps = 0;  // of the last group
+    } bs;
+
     // resident chain kernel (resident.hip.h): G held in LDS across a whole batch of trajectories
     struct Resident {
         int state = 0;  // 0 not planned yet, 1 usable, -1 not applicable

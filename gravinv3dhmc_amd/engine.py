@@ -816,6 +816,35 @@ class Engine(object):
         self._chk(self._lib.gh_batch_get_x(self._h, int(chain), ptr(x)))
         return x
 
+    # -- bootstrap replicates of the CG inversion in lock-step -------------------------
+    def bscg_run(self, counts, dobs, mw0, rhomin, rhomax, beta2, q, maxk):
+        """Up to 16 replicates of BootStrap.CG on one read of G per product (csrc/bscg.hip.h).  counts: (B, N) draw
+        counts; dobs: N; mw0: the weighted start model.  Returns the unweighted models (B, M), the data and model
+        misfit rows (B, maxk - 1), the regularisation factors (B, maxk) and how many entries of each are valid."""
+        counts = np.atleast_2d(f64(counts))
+        B = int(counts.shape[0])
+        if counts.shape[1] != self.N:
+            raise ValueError("bscg_run: counts must have shape (B, N = %d)" % self.N)
+        dobs, mw0 = f64(dobs), f64(mw0)
+        if dobs.shape != (self.N,) or mw0.shape != (self.M,):
+            raise ValueError("bscg_run: dobs must have N = %d entries and mw0 M = %d" % (self.N, self.M))
+        maxk = int(maxk)
+        rows, e = max(B, 1), max(maxk - 1, 1)
+        models = np.zeros((rows, self.M))
+        dmis, mmis, alpha = np.zeros((rows, e)), np.zeros((rows, e)), np.zeros((rows, max(maxk, 1)))
+        n_entries, n_alpha = np.zeros(rows, dtype=np.int32), np.zeros(rows, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        self._chk(self._lib.gh_bscg_run(self._h, B, ptr(counts), ptr(dobs), ptr(mw0), float(rhomin), float(rhomax),
+                                        float(beta2), float(q), maxk, ptr(models), ptr(dmis), ptr(mmis), ptr(alpha),
+                                        n_entries.ctypes.data_as(ip), n_alpha.ctypes.data_as(ip)))
+        return models, dmis, mmis, alpha, n_entries, n_alpha
+
+    def bscg_stats(self):
+        """Sweeps of G and lock-steps of the last bscg_run group: 2 maxk + 1 forward, maxk adjoint, whatever B."""
+        f, a, s = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.gh_bscg_stats(self._h, C.byref(f), C.byref(a), C.byref(s)))
+        return {"forward_sweeps": f.value, "adjoint_sweeps": a.value, "lock_steps": s.value}
+
     # -- posterior window ---------------------------------------------------------
     def posterior_window(self, K=100):
         self._chk(self._lib.gh_posterior_window(self._h, int(K)))

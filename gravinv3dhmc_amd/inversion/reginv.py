@@ -310,8 +310,36 @@ class BootStrap(object):
             print("CG iteration: ", k)
         return self.WmInv @ mw_new, data_misfit, model_misfit, regul_factor
 
-    def BSCG(self, initialModel):
-        """`samples` replicates, replicate s drawn with np.random.seed(s) (reginv.py:715-755)."""
+    def CG_batch(self, counts, dobs, initialModel):
+        """Up to 16 replicates in lock-step on the device (csrc/bscg.hip.h): `counts` of shape (B, N), one row per
+        replicate.  Returns a list of B tuples (model_inv, data_misfit, model_misfit, regul_factor), each what
+        `CG(counts[b], dobs, initialModel)` returns; nothing is printed per iteration."""
+        self._batch_refuse_wavelet()
+        counts = np.atleast_2d(np.asarray(counts, dtype=np.float64))
+        mw0 = self.Wm @ np.asarray(initialModel, dtype=np.float64)
+        models, dmis, mmis, alpha, n_entries, n_alpha = self._engine.bscg_run(
+            counts, dobs, mw0, self.boundary[0], self.boundary[1], self.beta ** 2, 0.9, self.maxk)
+        out = []
+        for b in range(counts.shape[0]):
+            regul_factor = [float(a) for a in alpha[b, :n_alpha[b]]]
+            regul_factor[0] = 0  # (the sequential loop's `alpha = 0` of the first iteration)
+            out.append((models[b].copy(), [float(v) for v in dmis[b, :n_entries[b]]],
+                        [float(v) for v in mmis[b, :n_entries[b]]], regul_factor))
+        return out
+
+    def _batch_refuse_wavelet(self):
+        if self.wavelet in ('1D', '3D'):
+            raise NotImplementedError("the bootstrap batch runs on the resident kernel: with wavelet='1D'/'3D' the "
+                                      "forward is the compressed, unresampled operator (another matrix)")
+
+    def BSCG(self, initialModel, batch=None):
+        """`samples` replicates, replicate s drawn with np.random.seed(s) (reginv.py:715-755).  batch=B (1..16) runs
+        them in groups of B in lock-step on the device (`CG_batch`): one read of G per product for the whole group."""
+        if batch is not None:
+            if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or not 1 <= batch <= 16:
+                raise ValueError("batch must be an int in 1..16 (replicates per group), got {!r}".format(batch))
+            self._batch_refuse_wavelet()
+            return self._BSCG_batch(initialModel, int(batch))
         model_inv_all = np.zeros((self.samples, self.msize))
         data_misfit_all = np.zeros((self.samples, self.maxk - 1))
         model_misfit_all = np.zeros((self.samples, self.maxk - 1))
@@ -328,4 +356,26 @@ class BootStrap(object):
             data_misfit_all[sample, :] = data_misfit
             model_misfit_all[sample, :] = model_misfit
             regul_factor_all[sample, :] = regul_factor
+        return model_inv_all, data_misfit_all, model_misfit_all, regul_factor_all
+
+    def _BSCG_batch(self, initialModel, batch):
+        model_inv_all = np.zeros((self.samples, self.msize))
+        data_misfit_all = np.zeros((self.samples, self.maxk - 1))
+        model_misfit_all = np.zeros((self.samples, self.maxk - 1))
+        regul_factor_all = np.zeros((self.samples, self.maxk))
+        for first in range(0, self.samples, batch):
+            group = range(first, min(first + batch, self.samples))
+            counts = np.zeros((len(group), self.dsize))
+            for row, sample in enumerate(group):
+                np.random.seed(sample)
+                index = np.arange(0, self.dsize)
+                indexSample = np.random.choice(index, size=self.dsize, replace=True, p=None)
+                counts[row] = np.bincount(indexSample, minlength=self.dsize).astype(np.float64)
+            results = self.CG_batch(counts, self.dobs, initialModel)
+            for sample, (model_inv, data_misfit, model_misfit, regul_factor) in zip(group, results):
+                print("*********Sample {}*********".format(sample + 1))
+                model_inv_all[sample, :] = model_inv
+                data_misfit_all[sample, :] = data_misfit
+                model_misfit_all[sample, :] = model_misfit
+                regul_factor_all[sample, :] = regul_factor
         return model_inv_all, data_misfit_all, model_misfit_all, regul_factor_all

@@ -534,6 +534,35 @@ int gh_batch_trajectory(gh_ctx *ctx, const double *p0s, double dt, const int *L,
 int gh_batch_run(gh_ctx *ctx, int T, const int *L, const double *const *p0_rows, const double *us,
                  double dt, int *accepted, double *out5s, double *x_out, int *n_started, int *n_done);
 int gh_batch_get_x(gh_ctx *ctx, int chain, double *x /* M */);
+/* ---- bootstrap replicates of the CG inversion in lock-step (csrc/bscg.hip.h) ----------------- */
+
+/* Up to 16 replicates of BootStrap.CG (reginv.py:631-713) on ONE read of G per product.  The replicates share the
+ * weighted kernel Aw and differ in the draw counts c_b[i] (how often observation i was drawn, reginv.py:736-741)
+ * applied to the N-vector between forward and adjoint, so the three products of a CG step -- Aw^T R, Aw.Iw,
+ * Aw.x_new -- are the chain batch's skinny GEMMs on v_mfma_f64_16x16x4 with a CG epilogue; every product the
+ * sequential loop computes a second time is taken from the forward that ended the iteration before.  Per replicate:
+ *     D = Aw x,  data(x) = sum_i c[i] (D[i] - dobs[i])^2,  R = c o (D - dobs),  I = 2 Aw^T R + alpha g_MS(x),
+ *     MS(x) = sum wm^2 x^2 / (x^2 + beta2),  g_MS = 2 wm^2 x beta2 / (x^2 + beta2)^2      (no prior, beta2 = beta^2),
+ *     Iw = I (k = 0) or I + (|I|^2 / |I_old|^2) Iw_old,  kstep = Iw.I / (sum_i c[i] (Aw Iw)[i]^2 + alpha |Iw|^2),
+ *     x_new = wm o clamp((x - kstep Iw) o (1 / wm), rhomin, rhomax),
+ *     alpha = 0 (k = 0), data(x_1) / MS(x_1) (k = 1), q alpha where data(x_{k-1}) - data(x_k) < 0.01 data(x_{k-1}),
+ * and after the update of an iteration k >= 1, data(x_new) < 0.1 freezes the replicate before that iteration's
+ * misfit entries are recorded: its model and rows no longer change while the others go on.  The maxk lock-steps
+ * are enqueued on the context's stream without a host synchronisation; a group costs 2 maxk + 1 forward and maxk
+ * adjoint sweeps of G whatever B (gh_bscg_stats: the counts of the last group).  All sums in a fixed order; a
+ * replicate's results do not depend on the slot it runs in.
+ * counts: B rows of N; dobs: N, taken as it is (no mean removed); mw0: the start model times Wm.  Out: models, B rows
+ * of M, unweighted; dmis / mmis, B rows of maxk - 1 (data(x_new) / N and MS(x_new) / M of iterations 1 ..), of which
+ * n_entries[b] are valid; alpha, B rows of maxk, n_alpha[b] valid.
+ * Runs on the dense, weighted store of one GPU and uses the chain batch's buffers (a gh_batch_* batch must be
+ * initialised again afterwards).  GH_ERR_UNSUPPORTED, naming the bootstrap batch: a matrix-free, shift-invariant,
+ * folded, sharded, joint, multi-component or magnetization-vector context, one with the wavelet-compressed forward,
+ * an unweighted store, B outside 1..16, maxk < 2; the context stays usable. */
+int gh_bscg_run(gh_ctx *ctx, int B, const double *counts /* B x N */, const double *dobs /* N */,
+                const double *mw0 /* M, weighted */, double rhomin, double rhomax, double beta2, double q, int maxk,
+                double *models /* B x M, unweighted */, double *dmis /* B x (maxk-1) */, double *mmis /* B x (maxk-1) */,
+                double *alpha /* B x maxk */, int *n_entries /* B: valid entries of dmis/mmis */, int *n_alpha /* B */);
+int gh_bscg_stats(const gh_ctx *ctx, int64_t *forward_sweeps, int64_t *adjoint_sweeps, int64_t *lock_steps);
 /* Page-locked host memory for momentum rows (the reference draws a trajectory's momentum with
  * np.random.randn(M) * Sigma into a fresh array, inversion/hmc.py:91): rows of gh_batch_run that lie in such a
  * block go to the device straight from it, adjacent rows of a chain's list in one copy; rows anywhere else

@@ -1,0 +1,175 @@
+"""GPU suite of the bootstrap batch (`BootStrap.BSCG(batch=B)`, `BootStrap.CG_batch`, gh_bscg_run; csrc/bscg.hip.h):
+up to 16 replicates of the conjugate-gradient inversion in lock-step on one read of G per product, against the
+reference's own run, the CPU port of the oracle and the sequential path of the same object.
+
+Tolerance: relmax < 1e-7 throughout -- the bound tests/test_gpu_parity.py::test_bootstrap_matches_reference holds the
+sequential path to on the same golden run (fp64 sums in another order, through a recurrence with a clamp)."""
+import numpy as np
+import pytest
+
+from conftest import gold
+from helpers import c1_inputs, relmax
+
+pytestmark = pytest.mark.gpu
+
+NAMES = ("models", "dmis", "mmis", "alpha")
+
+
+@pytest.fixture(scope="module")
+def G(built_lib):
+    import gravinv3dhmc_amd as g
+    return g
+
+
+@pytest.fixture(scope="module")
+def small(G):
+    """The problem of test_bootstrap_matches_reference: 42 observations x 120 cells, bounds (0, 1), maxk = 5."""
+    g = gold("cg_small.npz")
+    bs = G.BootStrap(tuple(g["mrange"]), tuple(g["mspacing"]), (g["xp"], g["yp"], g["zp"]), g["dobs"],
+                     (0.0, 1.0), samples=3, beta=0.1, maxk=5, verbose=False)
+    assert (bs.dsize, bs.msize) == (42, 120)
+    return bs
+
+
+def _draw(n, seed):
+    np.random.seed(seed)
+    return np.bincount(np.random.choice(np.arange(n), size=n, replace=True, p=None), minlength=n).astype(np.float64)
+
+
+@pytest.mark.parametrize("batch", [2, 16])
+def test_batch_matches_the_reference_run_in_ragged_groups(small, capsys, batch):
+    """tests/golden/bs_small.npz (the reference's own BSCG) with groups of 2 and 1, and with one group of 3 in 16 slots.
+    42 rows: the last patch of 16 is partial; 120 columns = 7.5 tiles: the last wave's second tile is missing."""
+    b = gold("bs_small.npz")
+    res = small.BSCG(np.full(small.msize, 0.001), batch=batch)
+    out = capsys.readouterr().out
+    assert [l for l in out.splitlines() if l.startswith("*********Sample")] == \
+        ["*********Sample %d*********" % (s + 1) for s in range(3)]
+    for name, v in zip(NAMES, res):
+        err = relmax(v, b[name])
+        print("batch=%d %s: relmax %.3e" % (batch, name, err))
+        assert v.shape == b[name].shape
+        assert err < 1e-7, name
+    # the clamp is where the recurrence is non-linear: it must have acted (lower bound 0: wm * 0 / wm is exactly 0)
+    on_bound = int((res[0] == 0.0).sum() + (np.abs(res[0] - 1.0) <= 4e-16).sum())
+    print("batch=%d: %d model entries on a bound" % (batch, on_bound))
+    assert on_bound >= 1
+
+
+def test_several_row_and_column_blocks_against_the_oracle_port(G, capsys):
+    """C1's geometry, 600 x 6000: two 512-row forward blocks (the second partial), many column blocks, 375 tiles (odd).
+    dobs: the oracle's forward of a block body plus seeded noise (seed 7, the first one tried).  `samples=5, maxk=4,
+    batch=4` (groups of 4 and 1) against oracle.cg_port.bootstrap on the oracle's kernel; the sequential BSCG() of the
+    same object is held to the same bound, which shows it attainable by the existing path on this input."""
+    from oracle import cg_port, oracle
+    mesh, xp, yp, zp = c1_inputs()
+    K = oracle.prism_gz_kernel(xp, yp, zp, mesh.cell_bounds())
+    rho = np.zeros(mesh.shape)
+    rho[3:7, 10:20, 7:13] = 0.8
+    rng = np.random.default_rng(7)
+    dobs = K @ rho.ravel() + 0.05 * rng.standard_normal(xp.size)
+    m0 = np.full(mesh.size, 0.001)
+    ref = cg_port.bootstrap(K, dobs, (0.0, 1.0), m0, samples=5, beta=0.1, maxk=4)
+    bs = G.BootStrap((0, 2000, 0, 3000, 0, 1000), (100, 100, 100), (xp, yp, zp), dobs, (0.0, 1.0), samples=5,
+                     beta=0.1, maxk=4, verbose=False)
+    assert (bs.dsize, bs.msize) == (600, 6000)
+    seq = bs.BSCG(m0)
+    bat = bs.BSCG(m0, batch=4)
+    capsys.readouterr()
+    for name, r, s, v in zip(NAMES, ref, seq, bat):
+        es, eb = relmax(s, r), relmax(v, r)
+        print("%s: sequential %.3e, batch %.3e against the oracle port" % (name, es, eb))
+        assert es < 1e-7, "sequential " + name
+        assert eb < 1e-7, "batch " + name
+    st = bs._engine.bscg_stats()
+    assert st == {"forward_sweeps": 9, "adjoint_sweeps": 4, "lock_steps": 4}
+    bs._engine.close()
+
+
+def test_early_stop_freezes_a_replicate_while_the_others_go_on(small, capsys):
+    """Caller-made counts: one observation drawn N times is fitted by the first steps and passes the stop test
+    before maxk; ordinary draws run to the end.  Every replicate against BootStrap.CG on the same object, and the
+    same bits whatever slot a replicate sits in."""
+    n = small.dsize
+    one = lambda i: float(n) * (np.arange(n) == i)
+    counts = np.stack([one(5), _draw(n, 0), one(17), _draw(n, 1)])
+    m0 = np.full(small.msize, 0.001)
+    got = small.CG_batch(counts, small.dobs, m0)
+    assert capsys.readouterr().out == ""   # nothing per iteration
+    assert len(got) == 4
+    lens = [(len(g[1]), len(g[2]), len(g[3])) for g in got]
+    print("lengths (data_misfit, model_misfit, regul_factor):", lens)
+    assert any(l[2] < small.maxk for l in lens), "no replicate stopped early"
+    assert any(l == (small.maxk - 1, small.maxk - 1, small.maxk) for l in lens), "no replicate ran to the end"
+    for b in range(4):
+        want = small.CG(counts[b], small.dobs, m0)
+        assert isinstance(got[b][0], np.ndarray) and got[b][0].shape == want[0].shape
+        for name, v, w in zip(NAMES, got[b], want):
+            assert isinstance(v, type(w)) and len(v) == len(w), (b, name)
+            if len(w):
+                err = relmax(v, w)
+                print("replicate %d %s: relmax %.3e" % (b, name, err))
+                assert err < 1e-7, (b, name)
+        assert got[b][3][0] == 0
+    capsys.readouterr()
+    # other slots, other neighbours: the same bits per replicate
+    perm = [2, 0, 3, 1]
+    again = small.CG_batch(np.vstack([_draw(n, 2)[None], counts[perm]]), small.dobs, m0)[1:]
+    for slot, b in enumerate(perm):
+        for name, v, w in zip(NAMES, again[slot], got[b]):
+            assert np.array_equal(np.asarray(v), np.asarray(w)), (b, name)
+
+
+def test_one_read_of_G_per_product_whatever_the_group_size(small):
+    n, maxk = small.dsize, small.maxk
+    m0 = np.full(small.msize, 0.001)
+    eng = small._engine
+    c16 = np.stack([_draw(n, s) for s in range(16)])
+    r1 = small.CG_batch(c16[:1], small.dobs, m0)
+    s1 = eng.bscg_stats()
+    r16 = small.CG_batch(c16, small.dobs, m0)
+    s16 = eng.bscg_stats()
+    assert s1 == s16 == {"forward_sweeps": 2 * maxk + 1, "adjoint_sweeps": maxk, "lock_steps": maxk}
+    # the same group twice: identical bits; and replicate 0 alone is replicate 0 of the full group
+    r16b = small.CG_batch(c16, small.dobs, m0)
+    # ... and alone again after the full group: what the 15 slots it no longer uses held does not reach it
+    r1b = small.CG_batch(c16[:1], small.dobs, m0)
+    for a, b in zip(r16 + r1 + r1b, r16b + r16[:1] + r1):
+        for v, w in zip(a, b):
+            assert np.array_equal(np.asarray(v), np.asarray(w))
+
+
+def test_refusals_leave_the_context_usable(G, small):
+    g = gold("cg_small.npz")
+    n, m = small.dsize, small.msize
+    bounds = small.mesh.cell_bounds(active_only=True)
+    x = np.linspace(0.1, 0.4, m)
+    args = (g["dobs"], np.full(m, 0.001), 0.0, 1.0, 0.01, 0.9, 5)
+
+    def engine(matrix_free, weighted):
+        eng = G.Engine(n, m)
+        eng.set_obs(g["xp"], g["yp"], g["zp"])
+        eng.set_cells(bounds, 0)
+        if matrix_free:
+            eng.set_matrix_free(True)
+        eng.build_G()
+        if weighted:
+            eng.weight(0.5)
+        return eng
+
+    for eng, word in ((engine(True, True), "matrix-free"), (engine(False, False), "weighted")):
+        before = eng.forward(x)
+        with pytest.raises(NotImplementedError, match="bootstrap batch") as e:
+            eng.bscg_run(np.ones((2, n)), *args)
+        assert word in str(e.value)
+        assert np.array_equal(eng.forward(x), before)
+        eng.close()
+    eng = small._engine
+    before = eng.forward(x)
+    for B in (0, 17):
+        with pytest.raises(NotImplementedError, match="bootstrap batch") as e:
+            eng.bscg_run(np.ones((B, n)), *args)
+        assert "1..16" in str(e.value)
+    with pytest.raises(NotImplementedError, match="bootstrap batch"):
+        eng.bscg_run(np.ones((2, n)), *args[:-1], 1)   # maxk < 2
+    assert np.array_equal(eng.forward(x), before)
