@@ -119,6 +119,13 @@ PROTOTYPES = {
     "gh_posterior_window": (C.c_int, [_ctx, C.c_int]),
     "gh_posterior_add": (C.c_int, [_ctx]),
     "gh_posterior_read": (C.c_int, [_ctx, C.POINTER(_i64), C.POINTER(_i64), _dp, _dp]),
+    "gh_posterior_stream": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _i64, _i64, _dp, _dp]),
+    "gh_posterior_stream_slot": (C.c_int, [_ctx, C.c_int]),
+    "gh_posterior_stream_add": (C.c_int, [_ctx, C.c_int, _dp]),
+    "gh_posterior_stream_read": (C.c_int, [_ctx, C.POINTER(_i64), _dp, _dp, _dp, _dp, _dp, _dp]),
+    "gh_posterior_stream_quantiles": (C.c_int, [_ctx, C.c_int, _dp, _dp]),
+    "gh_posterior_stream_hist": (C.c_int, [_ctx, C.POINTER(C.c_uint32)]),
+    "gh_posterior_stream_free": (C.c_int, [_ctx]),
     "gh_leapfrog": (C.c_int, [_ctx, _dp, _dp, C.c_double, C.c_int, _dp, _dp, C.c_double,
                               C.POINTER(C.c_int), _dp, _dp]),
     "gh_shard_unique_id": (C.c_int, [C.c_void_p]),

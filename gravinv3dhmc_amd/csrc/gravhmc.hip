@@ -15,6 +15,7 @@
 #include "lonres.hip.h"
 #include "lonsymw.hip.h"
 #include "fold.hip.h"
+#include "poststream.hip.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -53,6 +54,7 @@ static_assert(MULTI_MAX == GH_MULTI_MAX, "the kernels' row-block table holds the
 #include "host_comm.h"
 #include "host_wavelet.h"
 #include "host_eval.h"
+#include "host_poststream.h"
 #include "host_resident.h"
 #include "host_resbatch.h"
 #include "host_lonres.h"
@@ -1559,6 +1561,8 @@ int gh_chain_trajectory(gh_ctx *c, const double *p0, double dt, int L, double u,
     return chain_trajectory_impl(c, p0, dt, L, u, nullptr, accepted, out5);
 }
 
+static int posterior_ring_store(gh_ctx *c);
+
 int gh_chain_run(gh_ctx *c, int K, const int *L, const double *p0s, const double *us, double dt,
                  const double *p0_lookahead, int64_t stop_at_accepts, int64_t record_from, int *accepted,
                  double *out5s, double *x_out, int *n_run)
@@ -1604,7 +1608,8 @@ int gh_chain_run(gh_ctx *c, int K, const int *L, const double *p0s, const double
         *n_run = k + 1;
         if (accepted[k]) {
             c->accept_count += 1;
-            if (c->ring && c->accept_count > record_from) TRY(gh_posterior_add(c));
+            if (c->ring && c->accept_count > record_from) TRY(posterior_ring_store(c));
+            TRY(post_feed_single(c, c, c->xb[c->xcur]));
             if (x_out)
                 HIPCHK(c, hipMemcpyAsync(x_out + (size_t)k * M, c->xb[c->xcur], M * sizeof(double),
                                          hipMemcpyDeviceToHost, c->stream));
@@ -1672,16 +1677,29 @@ int gh_posterior_window(gh_ctx *c, int K)
     return GH_OK;
 }
 
-int gh_posterior_add(gh_ctx *c)
+// the chain's current state into the ring's next slot
+static int posterior_ring_store(gh_ctx *c)
 {
-    if (!c) return GH_ERR_ARG;
-    TRY(need(c, c->chain_ready && c->ring, "gh_posterior_add: needs gh_chain_init and gh_posterior_window"));
     HIPCHK(c, hipSetDevice(c->device));
     ring_store_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
         c->xb[c->xcur], c->weighted ? c->wm : nullptr, c->M, c->ring + (size_t)c->ring_next * (size_t)c->M);
     HIPCHK(c, hipGetLastError());
     c->ring_next = (c->ring_next + 1) % c->ring_K;
     c->ring_count += 1;
+    return GH_OK;
+}
+
+int gh_posterior_add(gh_ctx *c)
+{
+    if (!c) return GH_ERR_ARG;
+    TRY(need(c, c->chain_ready && (c->ring || c->ps.on),
+             "gh_posterior_add: needs gh_chain_init and gh_posterior_window"));
+    if (c->ring) TRY(posterior_ring_store(c));
+    // (an explicit call: the caller decides what is recorded, the stream's window does not apply)
+    if (c->ps.on) {
+        HIPCHK(c, hipSetDevice(c->device));
+        TRY(post_feed_row(c, c->ps.slot, c->xb[c->xcur], c->weighted, c->stream));
+    }
     return GH_OK;
 }
 
@@ -1700,6 +1718,82 @@ int gh_posterior_read(gh_ctx *c, int64_t *n_in_window, int64_t *n_total, double 
     if (mean) TRY(d2h(c, mean, c->ring_mean, (size_t)c->M));
     if (sd) TRY(d2h(c, sd, c->ring_sd, (size_t)c->M));
     return GH_OK;
+}
+
+int gh_posterior_stream(gh_ctx *c, int chains, int bins, int batch_len, int64_t record_from, int64_t record_count,
+                        const double *lo, const double *hi)
+{
+    if (!c) return GH_ERR_ARG;
+    if (!lo || !hi) return fail(c, GH_ERR_ARG, "gh_posterior_stream: null pointer");
+    if (c->sh.kind != 0)
+        return fail(c, GH_ERR_UNSUPPORTED, "the posterior stream runs on an unsharded context only: with column or row "
+                                           "blocks the model or the accept decision lives on several ranks");
+    if (chains < 1 || chains > POST_MAX_CHAINS) return fail(c, GH_ERR_ARG, "gh_posterior_stream: 1..16 chain slots");
+    if (bins < 2 || bins > POST_MAX_BINS) return fail(c, GH_ERR_ARG, "gh_posterior_stream: 2..256 histogram bins");
+    if (batch_len < 1) return fail(c, GH_ERR_ARG, "gh_posterior_stream: batch_len must be >= 1");
+    if (record_from < 0 || record_count < 0)
+        return fail(c, GH_ERR_ARG, "gh_posterior_stream: record_from and record_count must be >= 0");
+    for (int64_t j = 0; j < c->M; ++j)
+        if (!(hi[j] >= lo[j])) return fail(c, GH_ERR_ARG, "gh_posterior_stream: hi < lo (or not a number) at cell %lld", (long long)j);
+    if (c->ps.on) return fail(c, GH_ERR_ARG, "gh_posterior_stream: stream already allocated (gh_posterior_stream_free first)");
+    return post_alloc(c, chains, bins, batch_len, record_from, record_count, lo, hi);
+}
+
+int gh_posterior_stream_slot(gh_ctx *c, int slot)
+{
+    if (!c) return GH_ERR_ARG;
+    TRY(need(c, c->ps.on, "gh_posterior_stream_slot: call gh_posterior_stream first"));
+    if (slot < 0 || slot >= c->ps.d.C) return fail(c, GH_ERR_ARG, "gh_posterior_stream_slot: no such chain slot");
+    c->ps.slot = slot;
+    return GH_OK;
+}
+
+int gh_posterior_stream_add(gh_ctx *c, int slot, const double *m)
+{
+    if (!c) return GH_ERR_ARG;
+    if (!m) return fail(c, GH_ERR_ARG, "gh_posterior_stream_add: null pointer");
+    TRY(need(c, c->ps.on, "gh_posterior_stream_add: call gh_posterior_stream first"));
+    if (slot < 0 || slot >= c->ps.d.C) return fail(c, GH_ERR_ARG, "gh_posterior_stream_add: no such chain slot");
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(h2d(c, c->ps.row, m, (size_t)c->M));
+    return post_feed_row(c, slot, c->ps.row, false, c->stream);
+}
+
+int gh_posterior_stream_read(gh_ctx *c, int64_t *n_per_chain, double *mean, double *sd, double *rhat, double *ess,
+                             double *chain_mean, double *chain_M2)
+{
+    if (!c) return GH_ERR_ARG;
+    TRY(need(c, c->ps.on, "gh_posterior_stream_read: call gh_posterior_stream first"));
+    return post_read(c, n_per_chain, mean, sd, rhat, ess, chain_mean, chain_M2);
+}
+
+int gh_posterior_stream_quantiles(gh_ctx *c, int nq, const double *q, double *out)
+{
+    if (!c) return GH_ERR_ARG;
+    TRY(need(c, c->ps.on, "gh_posterior_stream_quantiles: call gh_posterior_stream first"));
+    if (nq < 1 || nq > POST_MAX_Q || !q || !out) return fail(c, GH_ERR_ARG, "gh_posterior_stream_quantiles: 1..32 quantiles");
+    for (int i = 0; i < nq; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail(c, GH_ERR_ARG, "gh_posterior_stream_quantiles: q must lie in [0, 1]");
+    return post_quantiles(c, nq, q, out);
+}
+
+int gh_posterior_stream_hist(gh_ctx *c, uint32_t *out)
+{
+    if (!c) return GH_ERR_ARG;
+    if (!out) return fail(c, GH_ERR_ARG, "gh_posterior_stream_hist: null pointer");
+    TRY(need(c, c->ps.on, "gh_posterior_stream_hist: call gh_posterior_stream first"));
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, c->ps.d.H, sizeof(uint32_t) * (size_t)c->ps.d.B * (size_t)c->M, hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GH_OK;
+}
+
+int gh_posterior_stream_free(gh_ctx *c)
+{
+    if (!c) return GH_ERR_ARG;
+    if (!c->ps.on) return GH_OK;
+    return post_free(c);
 }
 
 int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const double *high)
@@ -1723,6 +1817,7 @@ int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const 
                                            "other than gz (GH_CELL_TESSEROID_COMP) are not supported: store the kernel "
                                            "or run single chains");
     HIPCHK(c, hipSetDevice(c->device));
+    for (int64_t &n : c->bt_accepts) n = 0;
     if (lonsym_on(c)) {
         // (the light contexts of the chains share the tables, not a compressed forward operator)
         if (c->wv.on) return fail(c, GH_ERR_UNSUPPORTED, "batched chains on the shift-invariant store run without the wavelet-compressed forward");

@@ -714,10 +714,12 @@ static int batch_resident_turns(gh_ctx *c, int K, const int *chain_of, const int
     q.gcur_dev = r.bg;
     q.ucur_dev = r.bu;
     q.have_state = r.b_state ? 1 : 0;
-    q.want_x = want_x;
+    q.want_x = want_x || c->ps.on;
     int h_run[4] = {0, 0, 0, 0};
     const int rc = resident_launch(c, q, accepted, out5s, h_run);
     if (rc == GH_OK) r.b_state = true;
+    for (int k = 0; rc == GH_OK && k < h_run[0]; ++k)
+        if (accepted[k]) TRY(post_feed_batch_row(c, chain_of[k], r.xacc + (size_t)k * (size_t)c->M, c->stream));
     if (rc != GH_RESIDENT_ABORTED) return rc;
     if (replayed) return fail(c, GH_ERR_HIP, "gh_batch_run: the resident kernels timed out with trajectories in flight");
     std::vector<double> xs((size_t)C * (size_t)c->M);

@@ -49,6 +49,7 @@ static int batch_round_lockstep(gh_ctx *c, const double *p0s, double dt, const i
     if (mask) {
         batch_copy_state(c, in, b.cur(), mask);  // (the last sweep's input: the proposals)
         HIPCHK(c, hipGetLastError());
+        TRY(post_feed_batch(c, b.Xc, mask));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return GH_OK;
@@ -291,6 +292,7 @@ struct BatchRun {
         if (mask) {
             batch_copy_state(c, b.work(x_prop, rs), b.cur(), mask);
             HIPCHK(c, hipGetLastError());
+            TRY(post_feed_batch(c, b.Xc, mask));
             if (x_out)
                 for (int k = 0; k < C; ++k)
                     if (mask & (1u << k)) {

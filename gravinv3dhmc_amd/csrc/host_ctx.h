@@ -397,6 +397,22 @@ struct gh_ctx {
     int ring_K = 0, ring_next = 0;
     int64_t ring_count = 0;
 
+    // streaming posterior over whole runs of up to 16 chains (poststream.hip.h, host_poststream.h)
+    struct PostStream {
+        bool on = false;
+        int slot = 0;                 // the chain slot the single-chain paths feed
+        int64_t from = 0, count = 0;  // a chain's accepted states number from + 1 ... from + count are recorded
+        ghk::PostState d = {};
+        double *lo = nullptr, *hi = nullptr, *iw = nullptr;
+        double *row = nullptr;        // M: an explicit host row on its way in (gh_posterior_stream_add)
+        double *out = nullptr;        // 4 M: pooled mean, std, R-hat, ESS of the last read
+        double *qout = nullptr;       // quantiles of the last read
+        size_t qout_n = 0;
+        int64_t n[16] = {}, K[16] = {};  // recorded samples / completed batches per chain slot
+        int64_t launches = 0;
+    } ps;
+    int64_t bt_accepts[16] = {};  // accepted trajectories per chain of the batch since gh_batch_init
+
     // profiling of the sweeps
     bool prof = false;
     int prof_stride = 1;

@@ -97,7 +97,7 @@ static int chain_run_lonres(gh_ctx *c, gh_ctx *st, int K, const int *L, const do
         HIPCHK(c, hipEventCreate(&r.ev0));
         HIPCHK(c, hipEventCreate(&r.ev1));
     }
-    const bool want_x = x_out != nullptr || st->ring != nullptr;
+    const bool want_x = x_out != nullptr || st->ring != nullptr || c->ps.on;
     if (K > r.Kcap) {
         const int cap = std::max(K, 32);
         r.L = r.accepted = nullptr;
@@ -253,6 +253,7 @@ static int chain_run_lonres(gh_ctx *c, gh_ctx *st, int K, const int *L, const do
             st->ring_next = (st->ring_next + 1) % st->ring_K;
             st->ring_count += 1;
         }
+        TRY(post_feed_single(c, st, r.xacc + (size_t)k * M));
         if (x_out)
             HIPCHK(c, hipMemcpyAsync(x_out + (size_t)k * M, r.xacc + (size_t)k * M, M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
@@ -347,6 +348,7 @@ static int kids_run(gh_ctx *c, int T, const int *L, const double *const *p0rows,
     const int C = (int)c->kids.size();
     const size_t M = (size_t)c->M;
     std::vector<int> rcs((size_t)C, GH_OK);
+    std::mutex post_mu;  // (the pooled histogram is shared: the chains' accumulate launches take turns)
     // On the harmonic store the chains TAKE TURNS in the persistent launch (lonres.hip.h) -- a
     // chain's whole list in one launch with the table in the workgroups' registers: one chain alone runs faster that way
     // (35 k steps/s at C4) than eight side by side on the launches per phase (29-32 k together).  A launch that gives up
@@ -379,6 +381,12 @@ static int kids_run(gh_ctx *c, int T, const int *L, const double *const *p0rows,
             int acc = 0;
             double o5[5];
             int rc = chain_trajectory_impl(k, p0, dt, L[src], us[src], pn, &acc, o5);
+            if (rc == GH_OK && acc) {
+                std::lock_guard<std::mutex> lock(post_mu);
+                const int64_t fed = c->ps.launches;
+                rc = post_feed_batch_row(c, i, k->xb[k->xcur], k->stream);
+                if (rc == GH_OK && c->ps.launches != fed && hipStreamSynchronize(k->stream) != hipSuccess) rc = GH_ERR_HIP;
+            }
             if (rc == GH_OK && x_out && acc) rc = gh_chain_get_x(k, x_out + dst * M);
             if (rc != GH_OK) {
                 rcs[(size_t)i] = rc;

@@ -211,7 +211,7 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
     a.Tout = std::max(Tout, 1);
     a.accepted = b.accepted;
     a.out5s = b.out5s;
-    a.xacc = x_out ? b.xacc : nullptr;
+    a.xacc = (x_out || c->ps.on) ? b.xacc : nullptr;
     a.n_io = b.n_io;
     a.slabd = b.slabd;
     a.flagg = b.flagg;
@@ -262,6 +262,9 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
         if (nd > a.Tout || h_n[ch] > T)
             return fail(c, GH_ERR_HIP, "resident batch kernel: chain %d reports %d results in %d slots (%d of %d started)", ch, nd,
                         a.Tout, h_n[ch], T);
+        // (the streaming posterior reads the accepted models where the kernel left them, in each chain's order)
+        for (int i = 0; i < nd; ++i)
+            if (acc[(size_t)ch * a.Tout + i]) TRY(post_feed_batch_row(c, ch, b.xacc + ((size_t)ch * a.Tout + i) * M, c->stream));
         if (!x_out) continue;
         int last = -1;
         for (int i = 0; i < nd; ++i)

@@ -321,7 +321,7 @@ static int chain_run_resident(gh_ctx *c, int K, const int *L, const double *p0s,
     q.stop_at_accepts = stop_at_accepts;
     q.accept_count0 = c->accept_count;
     q.x_dev = c->xb[c->xcur];
-    q.want_x = x_out != nullptr || c->ring != nullptr;
+    q.want_x = x_out != nullptr || c->ring != nullptr || c->ps.on;
     int h_run[4] = {0, 0, 0, 0};
     TRY(resident_launch(c, q, accepted, out5s, h_run));
     *n_run = h_run[0];
@@ -335,6 +335,7 @@ static int chain_run_resident(gh_ctx *c, int K, const int *L, const double *p0s,
             c->ring_next = (c->ring_next + 1) % c->ring_K;
             c->ring_count += 1;
         }
+        TRY(post_feed_single(c, c, r.xacc + (size_t)k * M));
         if (x_out)
             HIPCHK(c, hipMemcpyAsync(x_out + (size_t)k * M, r.xacc + (size_t)k * M, M * sizeof(double),
                                      hipMemcpyDeviceToHost, c->stream));

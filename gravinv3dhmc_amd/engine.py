@@ -860,6 +860,77 @@ class Engine(object):
         self._chk(self._lib.gh_posterior_read(self._h, C.byref(n), C.byref(tot), ptr(mean), ptr(sd)))
         return {"n": n.value, "total": tot.value, "mean": mean, "std": sd}
 
+    # -- streaming posterior --------------------------------------------------------
+    def posterior_stream(self, chains, bins=64, batch_len=10, record_from=0, record_count=2 ** 62, lo=None, hi=None):
+        """Running statistics of whole runs of up to 16 chains on the device (gh_posterior_stream): per chain slot
+        mean / M2 and batch means of `batch_len` samples, one pooled histogram of `bins` bins over [lo, hi] per
+        cell (unweighted model bounds: scalars or M-vectors).  Chain slot c records its accepted states number
+        record_from + 1 ... record_from + record_count.  Call it after weight()."""
+        chains, bins, batch_len = int(chains), int(bins), int(batch_len)
+        if not 1 <= chains <= 16:
+            raise ValueError("posterior_stream: chains must be 1..16")
+        if not 2 <= bins <= 256:
+            raise ValueError("posterior_stream: bins must be 2..256")
+        if batch_len < 1:
+            raise ValueError("posterior_stream: batch_len must be >= 1")
+        if int(record_from) < 0 or int(record_count) < 0:
+            raise ValueError("posterior_stream: record_from and record_count must be >= 0")
+        if lo is None or hi is None:
+            raise ValueError("posterior_stream: needs the model bounds lo and hi of the histogram")
+        lo = f64(np.broadcast_to(np.asarray(lo, dtype=np.float64), (self.M,)))
+        hi = f64(np.broadcast_to(np.asarray(hi, dtype=np.float64), (self.M,)))
+        if not np.all(hi >= lo):
+            raise ValueError("posterior_stream: hi < lo at cell %d" % int(np.argmin(hi >= lo)))
+        self._chk(self._lib.gh_posterior_stream(self._h, chains, bins, batch_len, int(record_from), int(record_count),
+                                                ptr(lo), ptr(hi)))
+        self._stream = (chains, bins)
+
+    def posterior_stream_slot(self, slot):
+        """The chain slot the single-chain paths (run_chain, posterior_add) feed from here on."""
+        self._chk(self._lib.gh_posterior_stream_slot(self._h, int(slot)))
+
+    def posterior_stream_add(self, slot, m):
+        """One explicit UNWEIGHTED model row into chain slot `slot`."""
+        self._chk(self._lib.gh_posterior_stream_add(self._h, int(slot), ptr(self._vecM(m, "m"))))
+
+    def _stream_shape(self):
+        st = getattr(self, "_stream", None)
+        if st is None:
+            raise ValueError("no posterior stream: call posterior_stream first")
+        return st
+
+    def posterior_stream_read(self):
+        """n_per_chain (chains), pooled mean / std / rhat / ess (M each), chain_mean / chain_M2 (chains, M)."""
+        chains, _ = self._stream_shape()
+        n = np.zeros(chains, dtype=np.int64)
+        out = {k: np.empty(self.M) for k in ("mean", "std", "rhat", "ess")}
+        cm, cq = np.empty((chains, self.M)), np.empty((chains, self.M))
+        self._chk(self._lib.gh_posterior_stream_read(self._h, n.ctypes.data_as(C.POINTER(C.c_int64)), ptr(out["mean"]),
+                                                     ptr(out["std"]), ptr(out["rhat"]), ptr(out["ess"]), ptr(cm), ptr(cq)))
+        out.update(n_per_chain=n, chain_mean=cm, chain_M2=cq)
+        return out
+
+    def posterior_stream_quantiles(self, q):
+        """Quantiles q (each in [0, 1]) per cell from the pooled histogram: (len(q), M)."""
+        self._stream_shape()
+        q = f64(np.atleast_1d(q))
+        if q.ndim != 1 or not 1 <= q.size <= 32 or not np.all((q >= 0) & (q <= 1)):
+            raise ValueError("posterior_stream_quantiles: 1..32 quantiles in [0, 1]")
+        out = np.empty((q.size, self.M))
+        self._chk(self._lib.gh_posterior_stream_quantiles(self._h, int(q.size), ptr(q), ptr(out)))
+        return out
+
+    def posterior_stream_hist(self):
+        """The pooled histogram counts, (bins, M) uint32."""
+        _, bins = self._stream_shape()
+        out = np.empty((bins, self.M), dtype=np.uint32)
+        self._chk(self._lib.gh_posterior_stream_hist(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def posterior_stream_free(self):
+        self._chk(self._lib.gh_posterior_stream_free(self._h))
+        self._stream = None
+
     def leapfrog(self, x, p0, dt, L, low, high, u, want_dsyn=True):
         x = self._vecM(x, "x").copy()
         p0, low, high = self._vecM(p0, "p0"), self._vecM(low, "low"), self._vecM(high, "high")

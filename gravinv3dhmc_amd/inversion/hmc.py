@@ -42,6 +42,11 @@ class HamitonianMC(object):
         #: "none" = only the device-side window of the last `posterior_last` models is kept.
         self.sample_sink = "text"
         self.posterior_last = 100
+        #: None: no streaming posterior.  True or {"bins": .., "batch_len": .., "chains": ..}: the accepted samples
+        #: ndraws + 1 ... ndraws + nsamples are folded into the engine's posterior stream (Engine.posterior_stream,
+        #: allocated here if the engine has none), chain slot `posterior_slot`.
+        self.posterior_stream = None
+        self.posterior_slot = 0
         self._chain_x = None  # identity of the host vector the device chain state mirrors
         #: work of the last sample() call: trajectories run and leapfrog steps taken (accepted or not)
         self.trajectories = 0
@@ -174,6 +179,11 @@ class HamitonianMC(object):
         if self.sample_sink == "binary" and os.path.exists(self.save_folder + "/model.bin"):
             os.remove(self.save_folder + "/model.bin")
 
+        stream = _open_stream(self.model._engine, self.posterior_stream, self.posterior_slot + 1, ndraws, nsamples,
+                              self.boundaries)
+        if stream:
+            self.model._engine.posterior_stream_slot(self.posterior_slot)
+
         fused = self.constraint == 'mandatory' and ndraws + nsamples > 0
         # (WmInv is diagonal: hmc.py:328's WmInv @ mw is an element-wise product, the same bits)
         wdiag = WmInv.diagonal() if hasattr(WmInv, "diagonal") and getattr(WmInv, "nnz", -1) == WmInv.shape[0] else None
@@ -203,6 +213,9 @@ class HamitonianMC(object):
                             f.close()
                     if window and not fused:
                         self.model._engine.posterior_add()
+                    if stream and self.constraint == 'logarithmic':
+                        # (the trajectory lives on the host: the unweighted row goes to the device as it is)
+                        self.model._engine.posterior_stream_add(self.posterior_slot, unweight(self._to_mw(state["x"])))
                 state["i"] += 1
             state["ncount"] += 1
             msg = "chain {}: {:.2%}, misfit(total, data, alpha, model)=({:.7f},{:.7f},{:.2f},{:.7f}) " \
@@ -264,6 +277,21 @@ class HamitonianMC(object):
         return x
 
 
+def _open_stream(eng, spec, chains, ndraws, nsamples, boundaries):
+    """posterior_stream=None / True / {bins, batch_len, chains}: allocate the engine's stream unless it has one.
+    True if the run feeds a stream."""
+    if spec is None or spec is False:
+        return False
+    opts = dict(spec) if isinstance(spec, dict) else {}
+    unknown = set(opts) - {"bins", "batch_len", "chains"}
+    if unknown:
+        raise ValueError("posterior_stream: unknown option(s) %s" % ", ".join(sorted(unknown)))
+    if getattr(eng, "_stream", None) is None:
+        eng.posterior_stream(opts.get("chains", chains), bins=opts.get("bins", 64), batch_len=opts.get("batch_len", 10),
+                             record_from=ndraws, record_count=nsamples, lo=boundaries[:, 0], hi=boundaries[:, 1])
+    return True
+
+
 class _LazyDsyn(object):
     """dsyn of the current chain state, fetched from the device only if somebody reads it
     (the reference's sample loop discards it, hmc.py:299)."""
@@ -285,7 +313,8 @@ def HMCSample(model, nsamples, ndraws, delta, Lrange,
               initial_model, aprior_model, boundaries, constraint, log_factor, dobs,
               adaptiveRegul, RegulRate, RegulFactor, regularization, beta,
               seed, Sigma, nbest=100, myrank=0, save_folder="mychain",
-              plotsamples=False, im=[0, 0], sample_sink="text", posterior_last=100):
+              plotsamples=False, im=[0, 0], sample_sink="text", posterior_last=100, posterior_stream=None,
+              posterior_slot=0):
     """Set up one chain and run it (hmc.py:358-403).  Chains of different ranks are
     independent: seed + myrank, folder save_folder + str(myrank)."""
     chain = HamitonianMC(model)
@@ -317,6 +346,8 @@ def HMCSample(model, nsamples, ndraws, delta, Lrange,
     chain.plotsamples = plotsamples
     chain.sample_sink = sample_sink
     chain.posterior_last = posterior_last
+    chain.posterior_stream = posterior_stream
+    chain.posterior_slot = int(posterior_slot)
     chain.sample(nsamples, ndraws)
     return chain
 
@@ -324,7 +355,8 @@ def HMCSample(model, nsamples, ndraws, delta, Lrange,
 def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
                    initial_model, aprior_model, boundaries, constraint, log_factor, dobs,
                    adaptiveRegul, RegulRate, RegulFactor, regularization, beta,
-                   seed, Sigma, nbest=100, first_rank=0, save_folder="mychain", sample_sink="text"):
+                   seed, Sigma, nbest=100, first_rank=0, save_folder="mychain", sample_sink="text",
+                   posterior_stream=None):
     """`n_chains` (<= 16) independent chains on ONE GPU against ONE copy of the kernel matrix.
 
     The reference runs K chains as K MPI ranks, each rebuilding its own G (run_main.sh:17,
@@ -335,7 +367,12 @@ def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
     running desynchronised (gh_batch_run: none waits for the longest trajectory of a round); on
     problems small enough they take turns inside the resident chain kernel instead.  Chains that
     reach ndraws + nsamples accepted samples keep running (unrecorded) until the slowest one is
-    done.  'mandatory' constraint only."""
+    done.  'mandatory' constraint only.
+
+    posterior_stream=True (or {"bins": .., "batch_len": ..}): every chain's accepted samples ndraws + 1 ... ndraws +
+    nsamples are folded into the engine's posterior stream on the device, chain c in slot c -- with
+    sample_sink="none" the run leaves mean, std, quantiles, R-hat and ESS behind without a model file
+    (Engine.posterior_stream_read, posterior.summarize_stream)."""
     if constraint != 'mandatory':
         raise ValueError("HMCSampleBatch supports the 'mandatory' boundary constraint only")
     if getattr(model._engine, "joint", False):
@@ -378,6 +415,7 @@ def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
     print("mw boundaryies:", high, low)
     print("Using mandatory boundary constraint.")
     eng.batch_init(np.stack([mw0] * n_chains), low, high)
+    _open_stream(eng, posterior_stream, n_chains, ndraws, nsamples, np.asarray(boundaries))
     alpha = RegulFactor
     acc_n = [0] * n_chains
     tot_n = [0] * n_chains

@@ -612,6 +612,34 @@ int gh_posterior_window(gh_ctx *ctx, int K);
 int gh_posterior_add(gh_ctx *ctx);
 int gh_posterior_read(gh_ctx *ctx, int64_t *n_in_window, int64_t *n_total, double *mean /* M or NULL */,
                       double *sd /* M or NULL */);
+/* Streaming posterior over WHOLE runs of up to 16 chains: every recorded accepted state is read once where it
+ * lies in HBM and folded into running statistics of fixed size -- per chain slot Welford mean / M2 and batch
+ * means of length batch_len, and one pooled histogram of `bins` equal bins over [lo, hi] per cell (unweighted
+ * model bounds, M each; values outside go to the end bins).  Memory: (5 * 8 * chains + 4 * bins) * M bytes,
+ * whatever the number of samples.  gh_posterior_stream allocates and zeroes the state (after gh_weight: the
+ * reciprocal column norms are kept); from then on chain slot c records its accepted states number
+ * record_from + 1 ... record_from + record_count, counted per chain since gh_chain_init / gh_batch_init, on every
+ * chain path (gh_chain_run, gh_batch_trajectory, gh_batch_run; chains of a batch beyond `chains` are not
+ * recorded); the ring of gh_posterior_window works unchanged beside it.  The single-chain paths feed the slot
+ * gh_posterior_stream_slot sets (default 0), so several chains run one after the other fill slots 0 .. chains - 1.
+ * gh_posterior_add, being explicit, feeds that slot whatever the window; gh_posterior_stream_add adds an
+ * explicit UNWEIGHTED host row to slot c.  gh_posterior_stream_read: samples per slot, per-cell pooled mean and
+ * population std (numpy's ddof = 0), Gelman-Rubin R-hat (NaN unless >= 2 slots recorded the same n >= 2 samples,
+ * and where the within-chain variance is 0), batch-means effective sample size summed over the recording slots
+ * (NaN while a slot has fewer than 2 complete batches), and the per-slot means and M2 (chains x M); any output
+ * may be NULL.  gh_posterior_stream_quantiles: nq <= 32 quantiles q in [0, 1] per cell from the histogram
+ * (out: nq x M), within one bin width of the empirical quantile.  GH_ERR_UNSUPPORTED on a sharded context;
+ * GH_ERR_ARG for chains outside 1..16, bins outside 2..256, batch_len < 1, hi < lo anywhere, a slot >= chains,
+ * or a second gh_posterior_stream without gh_posterior_stream_free. */
+int gh_posterior_stream(gh_ctx *ctx, int chains, int bins, int batch_len, int64_t record_from, int64_t record_count,
+                        const double *lo, const double *hi);
+int gh_posterior_stream_slot(gh_ctx *ctx, int slot);
+int gh_posterior_stream_add(gh_ctx *ctx, int slot, const double *m_host);
+int gh_posterior_stream_read(gh_ctx *ctx, int64_t *n_per_chain /* chains */, double *mean, double *sd, double *rhat,
+                             double *ess /* M each */, double *chain_mean, double *chain_M2 /* chains x M each */);
+int gh_posterior_stream_quantiles(gh_ctx *ctx, int nq, const double *q, double *out /* nq x M */);
+int gh_posterior_stream_hist(gh_ctx *ctx, uint32_t *out /* bins x M */);
+int gh_posterior_stream_free(gh_ctx *ctx);
 /* Stateless convenience with the signature SURVEY 8b lists: init + trajectory + readback. */
 int gh_leapfrog(gh_ctx *ctx, double *x_inout, const double *p0, double dt, int L,
                 const double *low, const double *high, double u, int *accepted,
