@@ -27,7 +27,7 @@ import io
 import numpy as np
 import pytest
 
-from helpers import relmax
+from helpers import metropolis_u, relmax, shape3 as _shape, stable_dt as _dt
 
 pytestmark = pytest.mark.gpu
 
@@ -67,17 +67,6 @@ def _env(monkeypatch, env):
         monkeypatch.setenv(k, str(v))
 
 
-def _shape(M):
-    """A (nz, ny, nx) with product M for the stencil regularisers."""
-    f = [d for d in range(2, int(M ** 0.5) + 1) if M % d == 0]
-    if not f:
-        return (1, 1, M)
-    nz, rest = f[0], M // f[0]
-    g = [d for d in range(2, int(rest ** 0.5) + 1) if rest % d == 0]
-    ny = g[0] if g else 1
-    return (nz, ny, rest // ny)
-
-
 def _team_columns(lay, M):
     """Columns of every team of the sweep launch, restated from sweep_kernel's partition (non-joint)."""
     cpt, n = lay["cols_per_team"], lay["n_teams"]
@@ -93,20 +82,6 @@ def _team_columns(lay, M):
 
 
 # ----------------------------------------------------------------------------- trajectories
-
-def _dt(P, x0, rng, iters=12):
-    """A step a fifth of the stability limit of the stiffest mode: power iteration on differences of the oracle's
-    gradient."""
-    g0 = P.misfit_and_grad(x0)[1]
-    v = rng.normal(size=x0.size)
-    lam = 0.0
-    for _ in range(iters):
-        v = v / np.linalg.norm(v)
-        hv = (P.misfit_and_grad(x0 + 1e-6 * v)[1] - g0) / 1e-6
-        lam = np.linalg.norm(hv)
-        v = hv
-    return 0.4 / np.sqrt(lam)
-
 
 def _trajectories(P, x0, dt, rng):
     """Five trajectories of the oracle's chain from x0 in a box of +-1.5 dt: the decisions of WANT, a rejection only
@@ -128,7 +103,7 @@ def _trajectories(P, x0, dt, rng):
                 break
         else:
             raise AssertionError("no trajectory for the decision %r" % want)
-        u = 0.5 * np.exp(-max(dH, 0.0)) if want else 0.5 * (1.0 + np.exp(-dH))
+        u = metropolis_u(dH, want)
         # the cells the first drift pushes past a bound (clamped, momentum reflected)
         xs = x + dt * (p0 - 0.5 * dt * P.misfit_and_grad(x)[1])
         n_lo += int((xs < low).sum())
