@@ -149,6 +149,10 @@ PROTOTYPES = {
     "gh_fold_info": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(C.c_double),
                                C.POINTER(C.c_double)]),
     "gh_fold_detect": (C.c_int, [_i64, _dp, _dp, _dp, _i64, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gh_fold_pair_info": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(_i64),
+                                    C.POINTER(_i64)]),
+    "gh_fold_detect_pair": (C.c_int, [_i64, _dp, _dp, _dp, _i64, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(C.c_int)]),
     "gh_profile_read": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(_i64),
                                   C.POINTER(_i64)]),
 }

@@ -371,4 +371,360 @@ __global__ void __launch_bounds__(1024) fold_sweep_kernel(SweepArgs a, FoldArgs 
     }
 }
 
+// ------------------------------------------------------------------ the diagonal reflection on top of the mirrors
+//
+// Where cells and observations are also symmetric under tau: (x, y) -> (cx + (y - cy), cy + (x - cx)) (square
+// columns, the same grid of observations along x and y; host_fold.h finds it), Aw(tau i, tau j) = Aw(i, j), so the
+// block of a cell orbit o holds the entries of its partner orbit tau o as well, row for row:
+//
+//     dotT[h]        = sum_f sum_k S[o][f][k] r[tau s_(k^h) f]        the cell tau s_h j_o
+//     dpartT[s_g f] += sum_h S[o][f][g^h] x[tau s_h j_o]              lands in slab[tau s_g f]
+//
+// i.e. the sums above with r o tau and x o tau.  One read of S[o] then serves eight cells, the store is what it
+// was (for a pair both blocks hold the mean over all eight images, fold_pair_mean_kernel), and a sweep reads the
+// leaders' blocks and those of the orbits that are their own partners (the cell columns on a diagonal) only:
+// 16 FMA per double read.
+
+struct FoldPairArgs {
+    const int *wtab;         // n_work x 16: [0, 4) cells s_h j_o of the leading orbit, [4, 8) tau s_h j_o (~ of the
+                             // entry four to the left where the orbit has no partner), [8] the orbit, then padding
+    const int *obs_img_tau;  // nF x 4: tau obs_img
+    int64_t n_work, work_per_team;
+};
+constexpr int FOLD_PAIR_W = 16;
+constexpr int FOLD_PSLOT = 64;  // doubles: 8 waves x 8 dots
+
+// Both blocks of a pair (or the two halves of a block that is its own partner) become the mean of what
+// fold_build_kernel left in them: S[o][f][k] and S[o'][f'][swap(k) ^ c_o ^ c_f] (row_tau[f] = 4 f' + c_f with
+// tau f = s_(c_f) f', orb_tau[o] = 4 o' + c_o alike, swap: bits 0 and 1 exchanged) are the same entry of Aw.
+// a + b = b + a: the bits do not depend on which orbit leads.  dev_bits: max |entry - mean| / (largest |mean| of the
+// block), as in fold_build_kernel.
+__global__ void __launch_bounds__(256) fold_pair_mean_kernel(FoldArgs f, const int *row_tau, const int *orb_tau, double *S,
+                                                             unsigned long long *dev_bits)
+{
+    __shared__ double red[2][4];
+    const int64_t o = blockIdx.x;
+    const int ot = orb_tau[o];
+    const int64_t o2 = ot >> 2;
+    const int co = ot & 3;
+    const int n = 4 * f.nF;
+    const int64_t ldb = 4 * (int64_t)f.ldF;
+    double dev = 0.0, amax = 0.0;
+    if (o <= o2) {
+        for (int e = threadIdx.x; e < n; e += blockDim.x) {
+            const int k = e & 3, rt = row_tau[e >> 2];
+            const int ks = ((k & 1) << 1) | (k >> 1);
+            const int e2 = (rt & ~3) | (ks ^ co ^ (rt & 3));
+            if (o < o2 || e < e2) {
+                const double u = S[o * ldb + e], v = S[o2 * ldb + e2];
+                const double m = (u + v) * 0.5;
+                S[o * ldb + e] = m;
+                S[o2 * ldb + e2] = m;
+                dev = fmax(dev, fabs(u - m));
+                amax = fmax(amax, fabs(m));
+            } else if (e == e2) {
+                amax = fmax(amax, fabs(S[o * ldb + e]));
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        dev = fmax(dev, __shfl_xor(dev, off, WAVE));
+        amax = fmax(amax, __shfl_xor(amax, off, WAVE));
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[0][wave] = dev;
+        red[1][wave] = amax;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
+            dev = fmax(dev, red[0][w]);
+            amax = fmax(amax, red[1][w]);
+        }
+        const double rel = amax > 0.0 ? dev / amax : 0.0;
+        atomicMax(dev_bits, (unsigned long long)__double_as_longlong(rel));
+    }
+}
+
+template <int ROWS>
+struct FoldPairCol {
+    d2 v[ROWS][2];  // S[o][f][0..1], S[o][f][2..3] of the thread's rows f = k 512 + t
+    int j;          // lane 32 s + 8 h + q: cell h of the orbit (s = 0) or of its partner (s = 1)
+    int jn, on;     // the same of the work item this buffer takes next, and that item's orbit
+    bool live;      // the cell exists (partner lanes of an orbit without a partner: false)
+    double cv;      // per-cell inputs as in FoldCol
+};
+
+// The paired form of fold_sweep_kernel: 8 waves per workgroup, a whole folded row (4 k) of ROWS rows per thread,
+// one block in flight ahead with its cells' inputs, no scalar load in the loop (the work item's orbit comes with
+// the cell indices, two blocks ahead, through a vector load).  LDS: r at the four images of each fundamental
+// observation and r o tau in the same order (4 nF doubles each, no padding: at C2 the two and the slots fill 157 of
+// the 160 KiB), 2 x FOLD_PSLOT ping-pong slots of the eight dots.  The eight cells' updates run side by side in
+// lanes 8 h (the orbit) and 32 + 8 h (its partner) with the arithmetic of fold_sweep_kernel per cell.
+template <int ROWS>
+__global__ void __launch_bounds__(512) fold_pair_sweep_kernel(SweepArgs a, FoldArgs f, FoldPairArgs p)
+{
+    constexpr int TT = 512, NW = 8;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    double *rF = smem;
+    double *rT = smem + 4 * f.nF;
+    double *scratch = smem + 8 * f.nF;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int mode = a.mode;
+
+    if (mode & SW_ADJ) {
+        for (int e = tid; e < 4 * f.nF; e += TT) {
+            rF[e] = a.r[f.obs_img[e]];
+            rT[e] = a.r[p.obs_img_tau[e]];
+        }
+    }
+    __syncthreads();
+
+    const int64_t wb = (int64_t)blockIdx.x * p.work_per_team;
+    int64_t wend = wb + p.work_per_team;
+    if (wend > p.n_work) wend = p.n_work;
+    const int cnt = wb < wend ? (int)(wend - wb) : 0;
+
+    d2 acc[ROWS][2], accT[ROWS][2];  // [k][0] = observations s_0 f, s_1 f, [k][1] = s_2 f, s_3 f (accT: their tau images)
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) acc[k][0] = acc[k][1] = accT[k][0] = accT[k][1] = d2{0.0, 0.0};
+    double pp = 0.0;
+
+    // (only the last of a thread's rows can lie past nF: (ROWS - 1) 512 <= ldF - 16 < nF.  It re-reads the last row
+    // of the block and of r and takes no part in the sums)
+    const int row_last = (ROWS - 1) * TT + tid;
+    const bool last_in = row_last < f.nF;
+    unsigned voff = (unsigned)tid * 32u;
+    unsigned coff_last = (unsigned)(row_last < f.ldF ? row_last : f.ldF - 1) * 32u;
+    const int lrow_last = last_in ? row_last : f.nF - 1;
+
+    const int hl = (lane >> 3) & 3, ql = lane & 7, sl = lane >> 5;
+    const double *in_base = ql == FOLD_IN_P      ? a.p_in
+                            : ql == FOLD_IN_GREG ? a.greg
+                            : ql == FOLD_IN_HI   ? a.high
+                            : ql == FOLD_IN_LO   ? a.low
+                            : ql == FOLD_IN_PN   ? a.pn_in
+                            : (ql == FOLD_IN_GACC && (mode & SW_GACC)) ? a.g_out
+                                                                       : a.x_in;
+    const int lastc = cnt - 1;
+    auto item = [&](int i) -> int64_t { return wb + (i < lastc ? i : lastc); };
+    auto load_col = [&](FoldPairCol<ROWS> &c, int64_t w_after) {
+        const int jn = p.wtab[FOLD_PAIR_W * w_after + (lane >> 3)];
+        const int on = p.wtab[FOLD_PAIR_W * w_after + 8];
+        const int64_t o = __builtin_amdgcn_readfirstlane(c.on);
+        const unsigned long long col = (unsigned long long)(f.S + o * (int64_t)(4 * f.ldF));
+#pragma unroll
+        for (int k = 0; k < ROWS - 1; ++k) {
+            unsigned long long colk = col + (unsigned long long)k * TT * 32u;
+            asm volatile("" : "+s"(colk));
+            asm volatile("" : "+v"(voff));
+            c.v[k][0] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(colk + voff));
+            c.v[k][1] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(colk + voff) + 1);
+        }
+        asm volatile("" : "+v"(coff_last));
+        c.v[ROWS - 1][0] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(col + coff_last));
+        c.v[ROWS - 1][1] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(col + coff_last) + 1);
+        asm volatile("" : "+v"(c.jn)::"memory");
+        c.live = c.jn >= 0;
+        c.j = c.live ? c.jn : ~c.jn;
+        c.cv = in_base[c.j];
+        c.jn = jn;
+        c.on = on;
+    };
+
+    // t[q] += sum_k S[f][k] w[k ^ q] of one row: (wa, wb) = w[0..1], w[2..3]
+    auto row_fma = [](const d2 v0, const d2 v1, const d2 wa, const d2 wb2, d2 &t01, d2 &t23) {
+        t01.x += v0.x * wa.x;
+        t01.x += v0.y * wa.y;
+        t01.x += v1.x * wb2.x;
+        t01.x += v1.y * wb2.y;
+        t01.y += v0.x * wa.y;
+        t01.y += v0.y * wa.x;
+        t01.y += v1.x * wb2.y;
+        t01.y += v1.y * wb2.x;
+        t23.x += v0.x * wb2.x;
+        t23.x += v0.y * wb2.y;
+        t23.x += v1.x * wa.x;
+        t23.x += v1.y * wa.y;
+        t23.y += v0.x * wb2.y;
+        t23.y += v0.y * wb2.x;
+        t23.y += v1.x * wa.y;
+        t23.y += v1.y * wa.x;
+    };
+
+    auto process = [&](const FoldPairCol<ROWS> &cur, int it) {
+        double xl = cur.cv;
+        const double pl = dpp_from_up<FOLD_IN_P>(cur.cv);
+        if (mode & SW_ADJ) {
+            const d2 *r2 = reinterpret_cast<const d2 *>(rF), *t2 = reinterpret_cast<const d2 *>(rT);
+            d2 ua = d2{0.0, 0.0}, ub = ua, uta = ua, utb = ua;
+#pragma unroll
+            for (int k = 0; k < ROWS; ++k) {
+                if (k < ROWS - 1 || last_in) {
+                    const int row = k < ROWS - 1 ? k * TT + tid : lrow_last;
+                    row_fma(cur.v[k][0], cur.v[k][1], r2[2 * row], r2[2 * row + 1], ua, ub);
+                    row_fma(cur.v[k][0], cur.v[k][1], t2[2 * row], t2[2 * row + 1], uta, utb);
+                }
+            }
+            // the eight dots reduced together: lane pairs leave the orbit's four in even lanes and the partner's in odd
+            // ones, pairs of pairs dots 2 b, 2 b + 1 of them in the lanes with (l >> 1) & 1 = b, row_shr 4, 8 sum the
+            // quads of a row of 16 into its lanes 12 .. 15, two exchanges the four rows.  Fixed order throughout.
+            const bool odd = (lane & 1) != 0, hi2 = (lane & 2) != 0;
+            const double u[4] = {ua.x, ua.y, ub.x, ub.y}, ut[4] = {uta.x, uta.y, utb.x, utb.y};
+            double b[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) b[q] = (odd ? ut[q] : u[q]) + dpp_mov<0xb1>(odd ? u[q] : ut[q]);
+            double s0 = (hi2 ? b[2] : b[0]) + dpp_mov<0x4e>(hi2 ? b[0] : b[2]);
+            double s1 = (hi2 ? b[3] : b[1]) + dpp_mov<0x4e>(hi2 ? b[1] : b[3]);
+            s0 = dpp_add<0x114, 0xf>(s0);
+            s0 = dpp_add<0x118, 0xf>(s0);
+            s1 = dpp_add<0x114, 0xf>(s1);
+            s1 = dpp_add<0x118, 0xf>(s1);
+            s0 += __shfl_xor(s0, 16, WAVE);
+            s1 += __shfl_xor(s1, 16, WAVE);
+            s0 += __shfl_xor(s0, 32, WAVE);
+            s1 += __shfl_xor(s1, 32, WAVE);
+            // slot[8 w + 4 s + h]: dot h of the orbit (s = 0) / its partner (s = 1), wave w
+            double *slot = scratch + (it & 1) * FOLD_PSLOT;
+            if (lane >= 12 && lane < 16) {
+                const int c = lane - 12;
+                *reinterpret_cast<d2 *>(slot + wave * 8 + 4 * (c & 1) + 2 * (c >> 1)) = d2{s0, s1};
+            }
+            __syncthreads();
+            // lane l: wave l >> 3, dot l & 7; the eight waves in fixed order
+            double sv = slot[lane];
+            sv = dpp_add<0x118, 0xf>(sv);
+            sv += __shfl_xor(sv, 16, WAVE);
+            sv += __shfl_xor(sv, 32, WAVE);
+            const double th = __shfl(sv, 8 + 4 * sl + hl, WAVE);
+            const double g = 2.0 * th + dpp_from_up<FOLD_IN_GREG>(cur.cv);
+            double pv = 0.0, pf = 0.0;
+            if (mode & SW_PFIN) {
+                pf = pl - a.c_p * g;
+                pv = pf;
+            }
+            if (mode & SW_UPD) {
+                const double chi = dpp_from_up<FOLD_IN_HI>(cur.cv), clo = dpp_from_up<FOLD_IN_LO>(cur.cv);
+                const double psrc = (mode & SW_SPEC) ? dpp_from_up<FOLD_IN_PN>(cur.cv) : pl;
+                double pj = psrc - a.c_u * g;
+                double xj = xl + a.dt * pj;
+                if (xj > chi) {
+                    xj = chi;
+                    pj = -pj;
+                } else if (xj < clo) {
+                    xj = clo;
+                    pj = -pj;
+                }
+                pv = pj;
+                xl = xj;
+            }
+            if (mode & SW_PFIN) {
+                // (the orbit's cells, then its partner's: a cell that is not there adds +0)
+                const double pz = cur.live ? pf : 0.0;
+#pragma unroll
+                for (int h = 0; h < 8; ++h) {
+                    const double q = readlane_d(pz, 8 * h);
+                    pp += q * q;
+                }
+            }
+            if (tid < 64 && ql == 0 && cur.live) {
+                const int j = cur.j;
+                if (mode & SW_GOUT) a.g_out[j] = (mode & SW_GACC) ? dpp_from_up<FOLD_IN_GACC>(cur.cv) + g : g;
+                if (mode & SW_UPD) {
+                    a.p_out[j] = pv;
+                    a.x_out[j] = xl;
+                } else if ((mode & SW_PFIN) && !(mode & SW_SPEC)) {
+                    a.p_out[j] = pv;
+                }
+            }
+        }
+        if (mode & SW_FWD) {
+            const double xz = cur.live ? xl : 0.0;
+            const d2 xa = d2{readlane_d(xz, 0), readlane_d(xz, 8)}, xb = d2{readlane_d(xz, 16), readlane_d(xz, 24)};
+            const d2 ya = d2{readlane_d(xz, 32), readlane_d(xz, 40)}, yb = d2{readlane_d(xz, 48), readlane_d(xz, 56)};
+#pragma unroll
+            for (int k = 0; k < ROWS; ++k) {
+                row_fma(cur.v[k][0], cur.v[k][1], xa, xb, acc[k][0], acc[k][1]);
+                row_fma(cur.v[k][0], cur.v[k][1], ya, yb, accT[k][0], accT[k][1]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < ROWS; ++k) {
+            asm volatile("" ::"v"(cur.v[k][0]));
+            asm volatile("" ::"v"(cur.v[k][1]));
+        }
+    };
+
+    if (cnt > 0) {
+        FoldPairCol<ROWS> b0, b1;
+        b0.jn = p.wtab[FOLD_PAIR_W * item(0) + (lane >> 3)];
+        b0.on = p.wtab[FOLD_PAIR_W * item(0) + 8];
+        b1.jn = p.wtab[FOLD_PAIR_W * item(1) + (lane >> 3)];
+        b1.on = p.wtab[FOLD_PAIR_W * item(1) + 8];
+        load_col(b0, item(2));
+        int i = 0;
+        for (;;) {
+            load_col(b1, item(i + 3));
+            process(b0, i);
+            if (++i >= cnt) break;
+            load_col(b0, item(i + 3));
+            process(b1, i);
+            if (++i >= cnt) break;
+        }
+    }
+
+    if ((mode & SW_PFIN) && tid == 0) {
+        a.pp_part[blockIdx.x] = pp;
+        for (int t = (int)(blockIdx.x + gridDim.x); t < f.n_pp; t += (int)gridDim.x) a.pp_part[t] = 0.0;
+    }
+
+    if (mode & SW_FWD) {
+        // the orbit's sums go to their observations, then, behind a barrier, the partner's are added at the tau images
+        // (another thread's observations of the same slab row); the row's sum in the same order
+        double *out = a.slab + (int64_t)blockIdx.x * a.ld;
+        double ds = 0.0;
+#pragma unroll
+        for (int k = 0; k < ROWS; ++k) {
+            const int i = k * TT + tid;
+            if (i < f.nF) {
+                const int4 oi = reinterpret_cast<const int4 *>(f.obs_img)[i];
+                out[oi.x] = acc[k][0].x;
+                out[oi.y] = acc[k][0].y;
+                out[oi.z] = acc[k][1].x;
+                out[oi.w] = acc[k][1].y;
+                ds += acc[k][0].x;
+                ds += acc[k][0].y;
+                ds += acc[k][1].x;
+                ds += acc[k][1].y;
+            }
+        }
+        for (int64_t e = f.N + tid; e < a.ld; e += TT) out[e] = 0.0;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < ROWS; ++k) {
+            const int i = k * TT + tid;
+            if (i < f.nF) {
+                const int4 oi = reinterpret_cast<const int4 *>(p.obs_img_tau)[i];
+                out[oi.x] += accT[k][0].x;
+                out[oi.y] += accT[k][0].y;
+                out[oi.z] += accT[k][1].x;
+                out[oi.w] += accT[k][1].y;
+                ds += accT[k][0].x;
+                ds += accT[k][0].y;
+                ds += accT[k][1].x;
+                ds += accT[k][1].y;
+            }
+        }
+        if (a.dsum) {
+            const double t = block_allreduce_sum(ds, scratch, NW);
+            if (tid == 0) a.dsum[blockIdx.x] = t;
+        }
+    }
+}
+
 }  // namespace ghk

@@ -2441,6 +2441,40 @@ int gh_fold_info(const gh_ctx *c, int *on, int *reason, int64_t *store_bytes, do
     return GH_OK;
 }
 
+int gh_fold_pair_info(const gh_ctx *c, int *on, int *reason, int64_t *pairs, int64_t *single_orbits, int64_t *bytes_per_sweep)
+{
+    if (!c) return GH_ERR_ARG;
+    const gh_ctx::Fold &f = c->fd;
+    const bool live = f.valid && f.gen == c->G_gen;
+    const bool pair = live && f.pair_on;
+    if (on) *on = pair ? 1 : 0;
+    if (reason) *reason = (f.pair_detected && !live && f.pair_reason == GH_FOLD_PAIR_ON) ? GH_FOLD_PAIR_UNDECIDED : f.pair_reason;
+    if (pairs) *pairs = pair ? f.n_pairs : 0;
+    if (single_orbits) *single_orbits = pair ? f.n_work - f.n_pairs : 0;
+    if (bytes_per_sweep) *bytes_per_sweep = live ? fold_sweep_bytes(c) : 0;
+    return GH_OK;
+}
+
+int gh_fold_detect_pair(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
+                        int *obs_tau, int *cell_tau, int *work, int64_t *n_work, int *pair_reason)
+{
+    if (N < 0 || M < 0 || !x || !y || !z || !bounds6 || !obs_tau || !cell_tau || !work || !n_work || !pair_reason)
+        return GH_ERR_ARG;
+    std::vector<int> oi, co, ot, ct, rt, qt, wk;
+    *n_work = 0;
+    *pair_reason = GH_FOLD_PAIR_NO_FOLD;
+    const int rc = fold_detect_host(N, x, y, z, M, bounds6, oi, co);
+    if (rc != GH_FOLD_ON) return rc;
+    *pair_reason = fold_pair_detect_host(N, x, y, z, M, bounds6, oi, co, ot, ct, rt, qt, wk);
+    if (*pair_reason == GH_FOLD_PAIR_ON) {
+        std::copy(ot.begin(), ot.end(), obs_tau);
+        std::copy(ct.begin(), ct.end(), cell_tau);
+        std::copy(wk.begin(), wk.end(), work);
+        *n_work = (int64_t)(wk.size() / 2);
+    }
+    return rc;
+}
+
 int gh_fold_detect(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
                    int *obs_img, int *cell_orbit)
 {

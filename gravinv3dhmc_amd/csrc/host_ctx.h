@@ -382,6 +382,12 @@ struct gh_ctx {
         double max_dev = 0.0, build_ms = 0.0;
         int64_t launches = 0;
         bool exact = false;   // gh_forward / gh_adjoint in progress: the operator itself, on the dense store
+        // the diagonal reflection on top of the mirrors (fold_pair_sweep_kernel): a sweep reads one block per pair
+        bool pair_detected = false, pair_on = false;
+        int pair_reason = GH_FOLD_PAIR_UNDECIDED;
+        int64_t n_work = 0, n_pairs = 0, work_per_team = 0;
+        int pair_rows = 0;
+        int *wtab_d = nullptr, *obs_img_tau_d = nullptr, *row_tau_d = nullptr, *orb_tau_d = nullptr;
     } fd;
 
     // page-locked host memory handed to the caller (gh_pinned_alloc): momentum rows drawn into it go to the device

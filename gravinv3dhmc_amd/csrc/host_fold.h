@@ -183,6 +183,163 @@ static int fold_detect_host(int64_t N, const double *x, const double *y, const d
     return orbits(csx, csy, cell_orbit);
 }
 
+// The diagonal reflection tau: (x, y) -> (cx + (y - cy), cy + (x - cx)) on top of the two mirrors (square columns,
+// the same grid of observations along x and y): clusters and tolerance as above, heights, tops and bottoms bit for
+// bit.  GH_FOLD_PAIR_ON and, with pos[i] the place 4 f + g of index i in the mirror table,
+//     obs_tau, cell_tau     the involution on the caller's indices
+//     row_tau[f] = pos[tau obs_img[f][0]] = 4 f' + c_f,  orb_tau[o] = 4 o' + c_o alike:  tau s_g f = s_(swap(g) ^ c_f) f'
+//     work                  (leading orbit, partner or -1), by leading orbit: a pair is led by its smaller index
+// or the reason.
+static int fold_pair_detect_host(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *b6,
+                                 const std::vector<int> &obs_img, const std::vector<int> &cell_orbit, std::vector<int> &obs_tau,
+                                 std::vector<int> &cell_tau, std::vector<int> &row_tau, std::vector<int> &orb_tau,
+                                 std::vector<int> &work)
+{
+    using namespace fold_detail;
+    double xmin = b6[0], xmax = b6[1], ymin = b6[2], ymax = b6[3];
+    for (int64_t j = 0; j < M; ++j) {
+        const double *b = b6 + 6 * j;
+        xmin = std::min(xmin, std::min(b[0], b[1]));
+        xmax = std::max(xmax, std::max(b[0], b[1]));
+        ymin = std::min(ymin, std::min(b[2], b[3]));
+        ymax = std::max(ymax, std::max(b[2], b[3]));
+    }
+    double mag = std::max(std::max(std::fabs(xmin), std::fabs(xmax)), std::max(std::fabs(ymin), std::fabs(ymax)));
+    for (int64_t i = 0; i < N; ++i) mag = std::max(mag, std::max(std::fabs(x[i]), std::fabs(y[i])));
+    const double tol = 8.0 * DBL_EPSILON * mag;
+    const double cx = 0.5 * (xmin + xmax), cy = 0.5 * (ymin + ymax);
+    // cluster of the other axis each cluster goes to (-1: none)
+    auto across = [](const Axis &from, double cf, const Axis &to, double ct, std::vector<int> &m) {
+        m.assign(from.lo.size(), -1);
+        for (size_t q = 0; q < from.lo.size(); ++q) m[q] = to.find(ct + (0.5 * (from.lo[q] + from.hi[q]) - cf));
+    };
+
+    obs_tau.assign((size_t)N, -1);
+    {
+        Axis ax, ay;
+        ax.build(std::vector<double>(x, x + N), tol);
+        ay.build(std::vector<double>(y, y + N), tol);
+        std::vector<int> x2y, y2x;
+        across(ax, cx, ay, cy, x2y);
+        across(ay, cy, ax, cx, y2x);
+        std::vector<int> qx((size_t)N), qy((size_t)N);
+        Index idx;
+        idx.v.reserve((size_t)N);
+        for (int64_t i = 0; i < N; ++i) {
+            qx[(size_t)i] = ax.find(x[i]);
+            qy[(size_t)i] = ay.find(y[i]);
+            idx.v.push_back({Key{qx[(size_t)i], qy[(size_t)i], bits(z[i]), 0, 0, 0}, (int)i});
+        }
+        if (!idx.build()) return GH_FOLD_PAIR_OBS;
+        for (int64_t i = 0; i < N; ++i) {
+            const int a = y2x[(size_t)qy[(size_t)i]], b = x2y[(size_t)qx[(size_t)i]];
+            if (a < 0 || b < 0) return GH_FOLD_PAIR_OBS;
+            if ((obs_tau[(size_t)i] = idx.find(Key{a, b, bits(z[i]), 0, 0, 0})) < 0) return GH_FOLD_PAIR_OBS;
+        }
+    }
+    cell_tau.assign((size_t)M, -1);
+    {
+        Axis ax, ay;
+        std::vector<double> vx, vy;
+        vx.reserve(2 * (size_t)M);
+        vy.reserve(2 * (size_t)M);
+        for (int64_t j = 0; j < M; ++j) {
+            vx.push_back(b6[6 * j]);
+            vx.push_back(b6[6 * j + 1]);
+            vy.push_back(b6[6 * j + 2]);
+            vy.push_back(b6[6 * j + 3]);
+        }
+        ax.build(std::move(vx), tol);
+        ay.build(std::move(vy), tol);
+        std::vector<int> x2y, y2x;
+        across(ax, cx, ay, cy, x2y);
+        across(ay, cy, ax, cx, y2x);
+        std::vector<Key> keys((size_t)M);
+        Index idx;
+        idx.v.reserve((size_t)M);
+        for (int64_t j = 0; j < M; ++j) {
+            const double *b = b6 + 6 * j;
+            keys[(size_t)j] = Key{ax.find(b[0]), ax.find(b[1]), ay.find(b[2]), ay.find(b[3]), bits(b[4]), bits(b[5])};
+            idx.v.push_back({keys[(size_t)j], (int)j});
+        }
+        if (!idx.build()) return GH_FOLD_PAIR_CELLS;
+        for (int64_t j = 0; j < M; ++j) {
+            const Key &k = keys[(size_t)j];
+            const int a0 = y2x[(size_t)k[2]], a1 = y2x[(size_t)k[3]], b0 = x2y[(size_t)k[0]], b1 = x2y[(size_t)k[1]];
+            if (a0 < 0 || a1 < 0 || b0 < 0 || b1 < 0) return GH_FOLD_PAIR_CELLS;
+            if ((cell_tau[(size_t)j] = idx.find(Key{a0, a1, b0, b1, k[4], k[5]})) < 0) return GH_FOLD_PAIR_CELLS;
+        }
+    }
+    // tau is an involution that turns the mirror s_g into s_swap(g): checked on the tables, then kept per row / orbit
+    auto rows = [](const std::vector<int> &img, const std::vector<int> &tau, std::vector<int> &rt) {
+        const size_t n = img.size();
+        std::vector<int> pos(n);
+        for (size_t e = 0; e < n; ++e) pos[(size_t)img[e]] = (int)e;
+        rt.assign(n / 4, -1);
+        for (size_t e = 0; e < n; ++e) {
+            const int i = img[e], g = (int)(e & 3);
+            if (tau[(size_t)tau[(size_t)i]] != i) return false;
+            const int at = pos[(size_t)tau[(size_t)i]] ^ (((g & 1) << 1) | (g >> 1));  // place of tau s_0 f
+            if (g == 0) rt[e >> 2] = at;
+            if (rt[e >> 2] != at) return false;
+        }
+        return true;
+    };
+    if (!rows(obs_img, obs_tau, row_tau)) return GH_FOLD_PAIR_OBS;
+    if (!rows(cell_orbit, cell_tau, orb_tau)) return GH_FOLD_PAIR_CELLS;
+    work.clear();
+    for (size_t o = 0; o < orb_tau.size(); ++o) {
+        const int o2 = orb_tau[o] >> 2;
+        if (o2 == (int)o) {
+            work.push_back((int)o);
+            work.push_back(-1);
+        } else if ((int)o < o2) {
+            work.push_back((int)o);
+            work.push_back(o2);
+        }
+    }
+    return GH_FOLD_PAIR_ON;
+}
+
+// the diagonal reflection of a geometry whose mirrors were found: the tables of the paired sweep on the device
+static int fold_pair_tables(gh_ctx *c, const double *ox, const double *oy, const double *oz, const double *b6)
+{
+    gh_ctx::Fold &f = c->fd;
+    std::vector<int> obs_tau, cell_tau, row_tau, orb_tau, work;
+    f.pair_on = false;
+    f.n_work = f.n_pairs = 0;
+    f.pair_reason = fold_pair_detect_host(c->N, ox, oy, oz, c->M, b6, f.obs_img, f.cell_orbit, obs_tau, cell_tau, row_tau,
+                                          orb_tau, work);
+    f.pair_detected = f.pair_reason == GH_FOLD_PAIR_ON;
+    if (!f.pair_detected) return GH_OK;
+    f.pair_reason = GH_FOLD_PAIR_UNDECIDED;
+    f.n_work = (int64_t)(work.size() / 2);
+    std::vector<int> wtab((size_t)f.n_work * ghk::FOLD_PAIR_W, 0), oit((size_t)c->N);
+    for (int64_t w = 0; w < f.n_work; ++w) {
+        const int o = work[2 * (size_t)w], o2 = work[2 * (size_t)w + 1];
+        int *t = wtab.data() + w * ghk::FOLD_PAIR_W;
+        for (int h = 0; h < 4; ++h) {
+            t[h] = f.cell_orbit[4 * (size_t)o + h];
+            t[4 + h] = o2 >= 0 ? cell_tau[(size_t)t[h]] : ~t[h];
+        }
+        t[8] = o;
+        f.n_pairs += o2 >= 0;
+    }
+    for (size_t e = 0; e < oit.size(); ++e) oit[e] = obs_tau[(size_t)f.obs_img[e]];
+    // (sized for any geometry of the context's N and M: a later build reuses them)
+    auto up = [&](int **d, const std::vector<int> &h, size_t cap) -> int {
+        TRY(dalloc(c, d, cap, false));
+        HIPCHK(c, hipMemcpyAsync(*d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, c->stream));
+        return GH_OK;
+    };
+    TRY(up(&f.wtab_d, wtab, (size_t)f.n_orb * ghk::FOLD_PAIR_W));
+    TRY(up(&f.obs_img_tau_d, oit, (size_t)c->N));
+    TRY(up(&f.row_tau_d, row_tau, (size_t)f.nF));
+    TRY(up(&f.orb_tau_d, orb_tau, (size_t)f.n_orb));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GH_OK;
+}
+
 // gh_build_G of a dense store: look for the pairing (gz prisms only)
 static int fold_detect(gh_ctx *c)
 {
@@ -191,6 +348,8 @@ static int fold_detect(gh_ctx *c)
     f.valid = false;
     f.gen = ~0ull;
     f.reason = GH_FOLD_NOT_GZ;
+    f.pair_detected = f.pair_on = false;
+    f.pair_reason = GH_FOLD_PAIR_NO_FOLD;
     if (c->cell_kind != GH_CELL_PRISM || c->joint || c->mf || !c->G) return GH_OK;
     std::vector<double> ox((size_t)c->N), oy((size_t)c->N), oz((size_t)c->N), b6((size_t)c->M * 6);
     TRY(d2h(c, ox.data(), c->obs[0], ox.size()));
@@ -208,6 +367,7 @@ static int fold_detect(gh_ctx *c)
     HIPCHK(c, hipMemcpyAsync(f.cell_orbit_d, f.cell_orbit.data(), sizeof(int) * f.cell_orbit.size(), hipMemcpyHostToDevice,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // (the host tables stay, but may be reassigned by a later build)
+    TRY(fold_pair_tables(c, ox.data(), oy.data(), oz.data(), b6.data()));
     f.detected = 1;
     f.reason = GH_FOLD_UNDECIDED;
     return GH_OK;
@@ -232,6 +392,27 @@ static fold_fn fold_kernel_for(int ept2)
     return nullptr;
 }
 
+typedef void (*fold_pair_fn)(SweepArgs, FoldArgs, FoldPairArgs);
+
+static fold_pair_fn fold_pair_kernel_for(int rows)
+{
+    switch (rows) {
+    case 1: return fold_pair_sweep_kernel<1>;
+    case 2: return fold_pair_sweep_kernel<2>;
+    case 3: return fold_pair_sweep_kernel<3>;
+    case 4: return fold_pair_sweep_kernel<4>;
+    case 5: return fold_pair_sweep_kernel<5>;
+    }
+    return nullptr;
+}
+
+constexpr size_t FOLD_PAIR_MAX_LDS = 160u << 10;  // the CU's LDS: r, r o tau and the slots of one workgroup
+
+static size_t fold_pair_lds(const gh_ctx *c)
+{
+    return ((size_t)8 * c->fd.nF + 2 * FOLD_PSLOT) * sizeof(double);
+}
+
 static int64_t fold_store_bytes(const gh_ctx *c)
 {
     return c->fd.n_orb * 4 * (int64_t)c->fd.ldF * (int64_t)sizeof(double);
@@ -253,6 +434,24 @@ static FoldArgs fold_args(const gh_ctx *c)
     return a;
 }
 
+static FoldPairArgs fold_pair_args(const gh_ctx *c)
+{
+    const gh_ctx::Fold &f = c->fd;
+    FoldPairArgs p{};
+    p.wtab = f.wtab_d;
+    p.obs_img_tau = f.obs_img_tau_d;
+    p.n_work = f.n_work;
+    p.work_per_team = f.work_per_team;
+    return p;
+}
+
+// bytes of the store one sweep reads: every block, or the blocks of the paired sweep's work items
+static int64_t fold_sweep_bytes(const gh_ctx *c)
+{
+    const gh_ctx::Fold &f = c->fd;
+    return (f.pair_on ? f.n_work : f.n_orb) * 4 * (int64_t)f.ldF * (int64_t)sizeof(double);
+}
+
 // Build the folded store of the current dense one (stream-ordered, synchronises once to read the deviation).
 static int fold_build(gh_ctx *c)
 {
@@ -268,6 +467,20 @@ static int fold_build(gh_ctx *c)
     HIPCHK(c, hipMemcpyAsync(&bits, f.dev_bits, sizeof bits, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     memcpy(&f.max_dev, &bits, sizeof bits);
+    if (f.pair_on) {
+        // the mean over all eight images: the two blocks of a pair averaged entry by entry.  An entry is within
+        // max_dev of its four-image mean and that mean within this pass's deviation of the eight-image one: their sum
+        // bounds the distance of an entry from the mean the store holds
+        HIPCHK(c, hipMemsetAsync(f.dev_bits, 0, sizeof(unsigned long long), c->stream));
+        fold_pair_mean_kernel<<<dim3((unsigned)f.n_orb), dim3(256), 0, c->stream>>>(fold_args(c), f.row_tau_d, f.orb_tau_d, f.S,
+                                                                                   f.dev_bits);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&bits, f.dev_bits, sizeof bits, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        double d8 = 0.0;
+        memcpy(&d8, &bits, sizeof bits);
+        f.max_dev += d8;
+    }
     f.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return GH_OK;
 }
@@ -289,6 +502,7 @@ static int fold_use(gh_ctx *c, bool *use)
     }
     f.gen = c->G_gen;
     f.valid = false;
+    f.pair_on = false;
     if (env_int("GRAVHMC_FOLD", 1) == 0) {
         f.reason = GH_FOLD_SWITCHED_OFF;
         return GH_OK;
@@ -312,19 +526,39 @@ static int fold_use(gh_ctx *c, bool *use)
             return GH_OK;
         }
     }
-    fold_fn fn = fold_kernel_for(f.ept2);
-    f.lds = ((size_t)4 * f.ldF + 2 * FOLD_SLOT) * sizeof(double);
-    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(fn), f.lds));
+    // the paired sweep where the diagonal reflection was found and r, r o tau fit the LDS of a CU
+    f.pair_on = false;
+    f.pair_rows = (f.ldF + 511) / 512;
+    if (!f.pair_detected) {
+        // (the reason of the detection stays)
+    } else if (env_int("GRAVHMC_FOLD_PAIR", 1) == 0) {
+        f.pair_reason = GH_FOLD_PAIR_SWITCHED_OFF;
+    } else if (fold_pair_lds(c) > FOLD_PAIR_MAX_LDS || f.pair_rows > FOLD_MAX_EPT2) {
+        f.pair_reason = GH_FOLD_PAIR_ROWS;
+    } else if (allow_dynamic_lds(reinterpret_cast<const void *>(fold_pair_kernel_for(f.pair_rows)), fold_pair_lds(c)) !=
+               hipSuccess) {
+        (void)hipGetLastError();  // (a device that does not grant one workgroup that much)
+        f.pair_reason = GH_FOLD_PAIR_ROWS;
+    } else {
+        f.pair_on = true;
+        f.pair_reason = GH_FOLD_PAIR_ON;
+    }
+    const void *fn = f.pair_on ? reinterpret_cast<const void *>(fold_pair_kernel_for(f.pair_rows))
+                               : reinterpret_cast<const void *>(fold_kernel_for(f.ept2));
+    const int threads = f.pair_on ? 512 : 1024;
+    f.lds = f.pair_on ? fold_pair_lds(c) : ((size_t)4 * f.ldF + 2 * FOLD_SLOT) * sizeof(double);
+    HIPCHK(c, allow_dynamic_lds(fn, f.lds));
     int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(fn), 1024, f.lds) != hipSuccess ||
-        occ < 1) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, f.lds) != hipSuccess || occ < 1) {
         (void)hipGetLastError();
         occ = 1;
     }
     // (never more workgroups than the dense sweep's slab rows and pp partials)
-    int grid = (int)std::min<int64_t>(std::min<int64_t>((int64_t)c->cus * occ, c->grid), f.n_orb);
-    f.orb_per_team = (f.n_orb + grid - 1) / grid;
-    f.grid = (int)((f.n_orb + f.orb_per_team - 1) / f.orb_per_team);
+    const int64_t items = f.pair_on ? f.n_work : f.n_orb;
+    int grid = (int)std::min<int64_t>(std::min<int64_t>((int64_t)c->cus * occ, c->grid), items);
+    const int64_t per_team = (items + grid - 1) / grid;
+    f.orb_per_team = f.work_per_team = per_team;
+    f.grid = (int)((items + per_team - 1) / per_team);
     TRY(fold_build(c));
     if (!(f.max_dev <= FOLD_MAX_DEV)) {
         f.reason = GH_FOLD_DEVIATION;
@@ -357,10 +591,14 @@ static int launch_fold(gh_ctx *c, SweepArgs &a)
     SweepArgs b = a;  // (the kernel loads every per-cell input unconditionally)
     for (const double **v : {&b.x_in, &b.p_in, &b.low, &b.high, &b.greg, &b.pn_in})
         if (!*v) *v = f.zeros;
-    hipLaunchKernelGGL(fold_kernel_for(f.ept2), dim3(f.grid), dim3(1024), f.lds, c->stream, b, fold_args(c));
+    if (f.pair_on)
+        hipLaunchKernelGGL(fold_pair_kernel_for(f.pair_rows), dim3(f.grid), dim3(512), f.lds, c->stream, b, fold_args(c),
+                           fold_pair_args(c));
+    else
+        hipLaunchKernelGGL(fold_kernel_for(f.ept2), dim3(f.grid), dim3(1024), f.lds, c->stream, b, fold_args(c));
     if (timed) {
         HIPCHK(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-        c->ev_bytes[c->ev_used / 2] = fold_store_bytes(c);
+        c->ev_bytes[c->ev_used / 2] = fold_sweep_bytes(c);  // (what this launch reads)
         c->ev_used += 2;
     }
     if (c->prof) c->prof_launches += 1;

@@ -267,14 +267,25 @@ class Engine(object):
     FOLD_REASONS = ("on", "undecided", "switched off", "not gz prisms", "observations not mirror-symmetric",
                     "cells not mirror-symmetric", "fixed point", "small", "path", "no memory", "deviation")
 
+    #: reasons of fold_info's pair keys (GH_FOLD_PAIR_* of include/gravhmc.h)
+    FOLD_PAIR_REASONS = ("on", "undecided", "switched off", "no fold", "observations not square", "cells not square",
+                         "rows")
+
     def fold_info(self):
         """The stored kernel folded over the grid's two mirrors (csrc/fold.hip.h): on (the single-chain sweeps
         read it), reason (FOLD_REASONS), bytes of the folded store, largest deviation of an entry from its orbit's
-        mean relative to the orbit's largest entry, milliseconds of its build."""
+        mean relative to the orbit's largest entry, milliseconds of its build.  The diagonal reflection on top of
+        them: pair_on (a sweep reads one block per pair of orbits), pair_reason (FOLD_PAIR_REASONS), pairs and
+        single_orbits (the sweep's work items), bytes_per_sweep (what a sweep reads of the store)."""
         on, rs, sb, md, bm = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         self._chk(self._lib.gh_fold_info(self._h, C.byref(on), C.byref(rs), C.byref(sb), C.byref(md), C.byref(bm)))
+        pon, prs, npr, nsg, bps = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.gh_fold_pair_info(self._h, C.byref(pon), C.byref(prs), C.byref(npr), C.byref(nsg),
+                                              C.byref(bps)))
         return {"on": bool(on.value), "reason": self.FOLD_REASONS[rs.value], "store_bytes": sb.value,
-                "max_dev": md.value, "build_ms": bm.value}
+                "max_dev": md.value, "build_ms": bm.value, "pair_on": bool(pon.value),
+                "pair_reason": self.FOLD_PAIR_REASONS[prs.value], "pairs": npr.value, "single_orbits": nsg.value,
+                "bytes_per_sweep": bps.value}
 
     def matrix_free_stats(self):
         """Entries / GLQ leaves evaluated and launches of the fused matrix-free pass since

@@ -44,7 +44,8 @@
  *   arithmetic of an entry (within the path's stated 1e-10, ~1e-14 measured): GRAVHMC_MF_EXACT -- the
  *     DEFAULT of gh_set_matrix_free_exact only; that call overrides it; GRAVHMC_FOLD=0 / GRAVHMC_FOLD_MIN_MB (the
  *     sampler's sweeps of a mirror-symmetric gz prism grid on the dense store / the size from which they fold,
- *     gh_fold_info; ~1e-11 measured);
+ *     gh_fold_info; ~1e-11 measured); GRAVHMC_FOLD_PAIR=0 (the folded sweep reads every block instead of one per
+ *     pair of orbits under the diagonal reflection, gh_fold_pair_info);
  *   diagnostics that BREAK the results (timing only): GRAVHMC_LW_BREAK (phases of lonsymw_sweep_kernel off),
  *     GRAVHMC_BT_BREAK; GRAVHMC_LW_LDS_PAD (fewer workgroups per CU, results intact);
  *   tuning without any effect on results: GRAVHMC_PF, _NT, _TW, _TW8, _WG_PER_CU, _MIN_COLS,
@@ -758,6 +759,35 @@ int gh_fold_info(const gh_ctx *ctx, int *on, int *reason, int64_t *store_bytes, 
  * images of each orbit's first cell), both ordered by their first entry, are written when found. */
 int gh_fold_detect(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
                    int *obs_img, int *cell_orbit);
+
+/* The diagonal reflection on top of the two mirrors.  Where the cells are square columns and the observations the
+ * same grid along x and y, the geometry is also symmetric under tau: (x, y) -> (cx + (y - cy), cy + (x - cx)), gz is
+ * symmetric under that swap, and the block of a cell orbit o holds the entries of its partner orbit tau o, row for
+ * row.  The folded store keeps its size and layout (both blocks of a pair hold the mean over all eight images); the
+ * sampler's sweeps read one block per pair and the blocks of the orbits that are their own partners (the cell
+ * columns on a diagonal): about half the store.  GRAVHMC_FOLD_PAIR=0 switches it off (the mirror fold then runs
+ * alone).  pair reason: one of GH_FOLD_PAIR_*. */
+enum {
+    GH_FOLD_PAIR_ON = 0,
+    GH_FOLD_PAIR_UNDECIDED = 1,     /* no sampler sweep since the store changed */
+    GH_FOLD_PAIR_SWITCHED_OFF = 2,  /* GRAVHMC_FOLD_PAIR=0 */
+    GH_FOLD_PAIR_NO_FOLD = 3,       /* the mirrors were not found (gh_fold_info tells why) */
+    GH_FOLD_PAIR_OBS = 4,           /* not square: an observation without its image under tau */
+    GH_FOLD_PAIR_CELLS = 5,         /* not square: a cell without its image under tau */
+    GH_FOLD_PAIR_ROWS = 6           /* r and r o tau of the folded rows do not fit the LDS of a CU (N > 10176) */
+};
+/* on: the sweeps read one block per pair; pairs and single_orbits: the work items of a sweep; bytes_per_sweep: what
+ * a sweep reads of the folded store (work items x block bytes; the whole store where the pairing is off, 0 where
+ * the fold is). */
+int gh_fold_pair_info(const gh_ctx *ctx, int *on, int *reason, int64_t *pairs, int64_t *single_orbits,
+                      int64_t *bytes_per_sweep);
+/* gh_fold_detect and then tau, without a device.  Returns gh_fold_detect's result; *pair_reason is GH_FOLD_PAIR_ON,
+ * _NO_FOLD, _OBS or _CELLS.  When the pairing is found: obs_tau (N ints) and cell_tau (M ints), the involution on
+ * the caller's indices; work (M/4 rows of two ints, *n_work of them written): the leading orbit (a row of
+ * gh_fold_detect's cell_orbit) and its partner orbit, or -1 for an orbit that is its own partner; a pair is led by
+ * its smaller orbit index and listed once, rows ordered by leading orbit. */
+int gh_fold_detect_pair(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
+                        int *obs_tau, int *cell_tau, int *work, int64_t *n_work, int *pair_reason);
 
 /* ---- measurement ----------------------------------------------------------------------- */
 
