@@ -144,3 +144,86 @@ def bootstrap(K, dobs, boundary, initialModel, samples=3, beta=0.01, maxk=5, wav
         idx = np.random.choice(np.arange(N), size=N, replace=True, p=None)
         models[s], dms[s], mms[s], rfs[s] = run(Aw[idx, :], dobs[idx])
     return models, dms, mms, rfs
+
+
+class CountsRun(object):
+    """What bootstrap_counts returns: per replicate the unweighted model (B, M), the misfit rows (B, maxk - 1) and
+    the regularisation factors (B, maxk) with zeros past n_entries / n_alpha, and the trace of the branches taken:
+    trace[b] = {"margin": {k: value}, "seen": [data at the stop test of k = 1, 2, ...], "clamped": [(n_lo, n_hi) per
+    iteration], "on_bounds": (cells of the final model on rhomin, on rhomax)}."""
+
+    def __init__(self, B, M, maxk, dtype):
+        self.models = np.zeros((B, M), dtype=dtype)
+        self.dmis = np.zeros((B, maxk - 1), dtype=dtype)
+        self.mmis = np.zeros((B, maxk - 1), dtype=dtype)
+        self.alpha = np.zeros((B, maxk), dtype=dtype)
+        self.n_entries = np.zeros(B, dtype=np.int32)
+        self.n_alpha = np.zeros(B, dtype=np.int32)
+        self.trace = []
+
+    def results(self):
+        return self.models, self.dmis, self.mmis, self.alpha
+
+
+def bootstrap_counts(Aw, wm, counts, dobs, mw0, boundary, beta2, q, maxk, dtype=np.float64):
+    """The recurrence of bootstrap()'s `run` with draw counts in place of the resampled rows, every operation in
+    `dtype`: data = sum c (Aw mw - d)^2, data_g = 2 Aw^T (c o (Aw mw - d)), the step's denominator sum c (Aw Iw)^2,
+    `q` the factor of the alpha rule.  Aw, wm: the weighted kernel and its weights (oracle.col_weight); counts:
+    (B, N); mw0: the weighted start model.  (A value of data() the loop takes twice at one model is taken once.)"""
+    T = np.dtype(dtype).type
+    A = np.asarray(Aw, dtype=T)
+    At = np.ascontiguousarray(A.T)
+    wm, d, mw0 = np.asarray(wm, dtype=T), np.asarray(dobs, dtype=T), np.asarray(mw0, dtype=T)
+    counts = np.atleast_2d(np.asarray(counts, dtype=T))
+    lo, hi, b2, q = T(boundary[0]), T(boundary[1]), T(beta2), T(q)
+    N, M = A.shape
+    wm2 = wm * wm
+    model = lambda mw: np.sum(wm2 * mw * mw / (mw * mw + b2))
+    model_g = lambda mw: T(2) * wm2 * (mw * b2) / (mw * mw + b2) ** 2
+    out = CountsRun(counts.shape[0], M, maxk, T)
+    for b, c in enumerate(counts):
+        residual = lambda mw: A @ mw - d
+        data = lambda r: np.sum(c * r * r)
+        mw = mw0
+        r = residual(mw)
+        d_cur = data(r)
+        dm, mm, rf = [], [], []
+        tr = {"margin": {}, "seen": [], "clamped": []}
+        for k in range(maxk):
+            if k == 0:
+                alpha = T(0)
+            elif k == 1:
+                alpha = d_new / model(mw_new)
+            else:
+                tr["margin"][k] = float(((d_cur - d_new) - T(0.01) * d_cur) / d_cur)
+                if d_cur - d_new < T(0.01) * d_cur:
+                    alpha = q * alpha
+            rf.append(alpha)
+            if k > 0:
+                I_old, Iw_old = I, Iw
+                mw, r, d_cur = mw_new, r_new, d_new
+            I = T(2) * (At @ (c * r)) + alpha * model_g(mw)
+            Iw = I if k == 0 else I + ((I @ I) / (I_old @ I_old)) * Iw_old
+            F = A @ Iw
+            kstep = (Iw @ I) / (np.sum(c * F * F) + alpha * (Iw @ Iw))
+            m = (mw - kstep * Iw) / wm
+            below, above = m < lo, m > hi
+            tr["clamped"].append((int(below.sum()), int(above.sum())))
+            m[below] = lo
+            m[above] = hi
+            mw_new = wm * m
+            r_new = residual(mw_new)
+            d_new = data(r_new)
+            if k > 0:
+                tr["seen"].append(float(d_new))
+                if d_new < T(0.1):
+                    break
+                dm.append(d_new / T(N))
+                mm.append(model(mw_new) / T(M))
+        m = mw_new / wm
+        tr["on_bounds"] = (int((m <= lo).sum()), int((m >= hi).sum()))
+        out.models[b] = m
+        out.dmis[b, :len(dm)], out.mmis[b, :len(mm)], out.alpha[b, :len(rf)] = dm, mm, rf
+        out.n_entries[b], out.n_alpha[b] = len(dm), len(rf)
+        out.trace.append(tr)
+    return out

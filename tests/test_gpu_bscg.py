@@ -2,8 +2,11 @@
 up to 16 replicates of the conjugate-gradient inversion in lock-step on one read of G per product, against the
 reference's own run, the CPU port of the oracle and the sequential path of the same object.
 
-Tolerance: relmax < 1e-7 throughout -- the bound tests/test_gpu_parity.py::test_bootstrap_matches_reference holds the
-sequential path to on the same golden run (fp64 sums in another order, through a recurrence with a clamp)."""
+Tolerance: the two sizes against the reference's run and the oracle port to TOL_BSCG = 1e-10, the bound of
+tests/test_gpu_bscg_oracle.py (measured on the MI355X: 2.6e-13 at 42 x 120, 2.0e-13 at 600 x 6000); the batch against
+the sequential path of the same object to relmax < 1e-7 -- the bound tests/test_gpu_parity.py::
+test_bootstrap_matches_reference holds that path to (its single-observation replicates cancel in Iw = I + mu Iw_old:
+float64 and longdouble runs of such a replicate differ by 5e-10, tests/bscg_oracle_cases.py)."""
 import numpy as np
 import pytest
 
@@ -13,6 +16,7 @@ from helpers import c1_inputs, relmax
 pytestmark = pytest.mark.gpu
 
 NAMES = ("models", "dmis", "mmis", "alpha")
+TOL_BSCG = 1e-10
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +53,7 @@ def test_batch_matches_the_reference_run_in_ragged_groups(small, capsys, batch):
         err = relmax(v, b[name])
         print("batch=%d %s: relmax %.3e" % (batch, name, err))
         assert v.shape == b[name].shape
-        assert err < 1e-7, name
+        assert err < TOL_BSCG, name
     # the clamp is where the recurrence is non-linear: it must have acted (lower bound 0: wm * 0 / wm is exactly 0)
     on_bound = int((res[0] == 0.0).sum() + (np.abs(res[0] - 1.0) <= 4e-16).sum())
     print("batch=%d: %d model entries on a bound" % (batch, on_bound))
@@ -79,8 +83,8 @@ def test_several_row_and_column_blocks_against_the_oracle_port(G, capsys):
     for name, r, s, v in zip(NAMES, ref, seq, bat):
         es, eb = relmax(s, r), relmax(v, r)
         print("%s: sequential %.3e, batch %.3e against the oracle port" % (name, es, eb))
-        assert es < 1e-7, "sequential " + name
-        assert eb < 1e-7, "batch " + name
+        assert es < TOL_BSCG, "sequential " + name
+        assert eb < TOL_BSCG, "batch " + name
     st = bs._engine.bscg_stats()
     assert st == {"forward_sweeps": 9, "adjoint_sweeps": 4, "lock_steps": 4}
     bs._engine.close()
