@@ -17,6 +17,12 @@ GH_OK, GH_ERR_ARG, GH_ERR_HIP, GH_ERR_NOMEM, GH_ERR_OVERFLOW, GH_ERR_UNSUPPORTED
 CELL_PRISM, CELL_TESSEROID, CELL_PRISM_TF, CELL_PRISM_COMP, CELL_TESSEROID_COMP, CELL_PRISM_JOINT = 0, 1, 2, 3, 4, 5
 CELL_PRISM_MULTI = 6
 CELL_PRISM_MVI = 7
+CELL_PRISM_MVI_DATA = 8
+#: the magnetic data components of prisms (GH_BCOMP_*, gh_set_cells_mvi_data / gh_b_result)
+BCOMP_TF, BCOMP_BX, BCOMP_BY, BCOMP_BZ = range(4)
+BCOMPONENTS = {"tf": BCOMP_TF, "bx": BCOMP_BX, "by": BCOMP_BY, "bz": BCOMP_BZ}
+#: data components a CELL_PRISM_MVI_DATA context stacks at most (GH_BCOMP_MAX)
+BCOMP_MAX = 4
 #: components a CELL_PRISM_MULTI context stacks at most (GH_MULTI_MAX)
 MULTI_MAX = 11
 #: the gravity fields of prisms and tesseroids (GH_COMP_*, gh_set_cells_prism / gh_set_cells_tess)
@@ -42,6 +48,8 @@ PROTOTYPES = {
     "gh_set_cells_tf": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
     "gh_set_cells_joint": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
     "gh_set_cells_mvi": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
+    "gh_set_cells_mvi_data": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), _dp]),
+    "gh_b_result": (C.c_int, [_ctx, C.c_int, _dp, _dp]),
     "gh_set_amplitude": (C.c_int, [_ctx, C.c_double, C.c_double, C.c_double]),
     "gh_amplitude_eval": (C.c_int, [_ctx, _dp, C.POINTER(C.c_double), _dp, _dp]),
     "gh_amplitude_last": (C.c_int, [_ctx, C.POINTER(C.c_double)]),

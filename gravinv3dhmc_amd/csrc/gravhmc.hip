@@ -46,6 +46,9 @@ static_assert(COMP_POTENTIAL == GH_COMP_POTENTIAL && COMP_GEOID == GH_COMP_GEOID
                   COMP_GZZ == GH_COMP_GZZ,
               "the kernels' component numbers are the C ABI's GH_COMP_*");
 static_assert(MULTI_MAX == GH_MULTI_MAX, "the kernels' row-block table holds the C ABI's GH_MULTI_MAX components");
+static_assert(BCOMP_MAX == GH_BCOMP_MAX && BCOMP_MAX <= MULTI_MAX && BCOMP_TF == GH_BCOMP_TF && BCOMP_BX == GH_BCOMP_BX &&
+                  BCOMP_BY == GH_BCOMP_BY && BCOMP_BZ == GH_BCOMP_BZ,
+              "the kernels' data components are the C ABI's GH_BCOMP_*");
 
 #include "host_ctx.h"
 #include "host_sweep.h"
@@ -188,6 +191,8 @@ int gh_set_obs(gh_ctx *c, const double *a, const double *b, const double *cc)
 static int set_cells(gh_ctx *c, const double *bounds6, int kind, int comp, double ratio, const double *dir = nullptr)
 {
     if (c->joint) return fail(c, GH_ERR_UNSUPPORTED, "a joint gravity-magnetic context takes its cells from gh_set_cells_joint");
+    if (c->mc.n > 0 && c->mvi)
+        return fail(c, GH_ERR_UNSUPPORTED, "a vector-data magnetization context takes its cells from gh_set_cells_mvi_data");
     if (c->mc.n > 0) return fail(c, GH_ERR_UNSUPPORTED, "a multi-component context takes its cells from gh_set_cells_multi");
     if (c->mvi) return fail(c, GH_ERR_UNSUPPORTED, "a magnetization-vector context takes its cells from gh_set_cells_mvi");
     HIPCHK(c, hipSetDevice(c->device));
@@ -305,8 +310,69 @@ int gh_set_cells_mvi(gh_ctx *c, const double *bounds6, double fx, double fy, dou
     return GH_OK;
 }
 
+int gh_set_cells_mvi_data(gh_ctx *c, const double *bounds6, double fx, double fy, double fz, int ncomp, const int *comps,
+                          const double *weights)
+{
+    if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: null pointer");
+    if (ncomp < 1 || ncomp > GH_BCOMP_MAX)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: %d data components: the vector-data magnetization store takes 1 "
+                                   "to %d", ncomp, GH_BCOMP_MAX);
+    for (int b = 0; b < ncomp; ++b) {
+        if (comps[b] < GH_BCOMP_TF || comps[b] > GH_BCOMP_BZ)
+            return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: component %d is not one of GH_BCOMP_TF (0) .. GH_BCOMP_BZ (3)",
+                        comps[b]);
+        for (int a = 0; a < b; ++a)
+            if (comps[a] == comps[b])
+                return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: component %d is listed twice", comps[b]);
+        if (!(weights[b] > 0.0) || !std::isfinite(weights[b]))
+            return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: the data weights must be finite and > 0");
+    }
+    if (c->M % 3 != 0 || c->M < 3)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: M = %lld is not three components of the same prisms",
+                    (long long)c->M);
+    if (c->N % ncomp != 0)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: N = %lld is not %d blocks of the same observation points",
+                    (long long)c->N, ncomp);
+    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(fz))
+        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: the field direction must be finite");
+    if (c->joint || c->mvi || c->mc.n > 0 || c->have_obs || c->have_cells || c->have_G || c->slab)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: call it first on a fresh context (before gh_set_obs)");
+    if (c->mf || c->ls)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi_data: the vector-data magnetization store is dense only (no "
+                                           "matrix-free mode, no shift-invariant store)");
+    if (c->sh.kind != 0)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi_data: the vector-data magnetization store is not sharded");
+    if (c->N > 16384)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi_data: %d components x %lld observations = %lld rows: the "
+                                           "vector-data magnetization store takes at most 16384 (it runs on the fused "
+                                           "sweep: no row panels, no team sweep)", ncomp, (long long)(c->N / ncomp),
+                    (long long)c->N);
+    // the total field alone, unweighted: one block with one mean -- the magnetization-vector store itself
+    if (ncomp == 1 && comps[0] == GH_BCOMP_TF && weights[0] == 1.0) return gh_set_cells_mvi(c, bounds6, fx, fy, fz);
+    HIPCHK(c, hipSetDevice(c->device));
+    const double dir[3] = {fx, fy, fz};
+    // (bounds: M/3 cells)
+    TRY(dalloc(c, &c->bounds, (size_t)(c->M / 3) * 6));
+    TRY(h2d(c, c->bounds, bounds6, (size_t)(c->M / 3) * 6));
+    std::copy(dir, dir + 3, c->tf_dir);
+    TRY(dalloc(c, &c->tf_dir_d, 3));
+    TRY(h2d(c, c->tf_dir_d, c->tf_dir, 3));
+    // columns: the magnetization-vector store's; rows: the multi-component store's blocks
+    c->mvi = true;
+    c->mc.n = ncomp;
+    for (int b = 0; b < ncomp; ++b) {
+        c->mc.comp[b] = comps[b];
+        c->mc.w[b] = weights[b];
+    }
+    c->cell_kind = GH_CELL_PRISM_MVI_DATA;
+    c->comp = GH_COMP_GZ;
+    c->have_cells = true;
+    return GH_OK;
+}
+
 static const char *const MVI_ONLY = "the amplitude term couples the three blocks of the magnetization-vector store (a "
-                                    "GH_CELL_PRISM_MVI context, gh_set_cells_mvi)";
+                                    "GH_CELL_PRISM_MVI or GH_CELL_PRISM_MVI_DATA context, gh_set_cells_mvi, "
+                                    "gh_set_cells_mvi_data)";
 
 // amp.sw = 1 / (Wm scale), 0 where Wm is 0: from the weights the store has NOW (gh_weight builds it again)
 static int amplitude_weights(gh_ctx *c, double scale)
@@ -413,7 +479,8 @@ int gh_multi_info(gh_ctx *c, int *ncomp, int *comps, double *weights, double *pr
 {
     if (!c) return GH_ERR_ARG;
     if (c->mc.n == 0)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_multi_info: not a multi-component context (gh_set_cells_multi)");
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_multi_info: not a context of row blocks (gh_set_cells_multi, "
+                                           "gh_set_cells_mvi_data with more than the unweighted total field)");
     if (ncomp) *ncomp = c->mc.n;
     for (int b = 0; b < c->mc.n; ++b) {
         if (comps) comps[b] = c->mc.comp[b];
@@ -566,6 +633,9 @@ static int dense_single_chain_refuse(gh_ctx *c, const char *who)
     if (c && c->joint)
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the joint gravity-magnetic kernel (dense, single chain)",
                     who);
+    if (c && c->mc.n > 0 && c->mvi)
+        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the vector-data magnetization store (dense, single chain)",
+                    who);
     if (c && c->mc.n > 0)
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the multi-component store (dense, single chain)", who);
     if (c && c->mvi)
@@ -576,15 +646,16 @@ static int dense_single_chain_refuse(gh_ctx *c, const char *who)
 // The result passes' scaffolding: upload n_in doubles, enqueue launch(device input, device result of N doubles)
 // on the context's stream, download the result.
 static int run_result(gh_ctx *c, const char *who, const double *in, size_t n_in, double *result,
-                      const std::function<void(const double *, double *)> &launch)
+                      const std::function<void(const double *, double *)> &launch, int64_t n_out = -1)
 {
+    if (n_out < 0) n_out = c->N;  // (a store of row blocks: its observation points, not its rows)
     HIPCHK(c, hipSetDevice(c->device));
     double *din = nullptr, *dres = nullptr;
     HIPCHK(c, hipMalloc((void **)&din, sizeof(double) * std::max<size_t>(n_in, 1)));
-    if (hipMalloc((void **)&dres, sizeof(double) * (size_t)std::max<int64_t>(c->N, 1)) != hipSuccess) {
+    if (hipMalloc((void **)&dres, sizeof(double) * (size_t)std::max<int64_t>(n_out, 1)) != hipSuccess) {
         (void)hipGetLastError();
         hipFree(din);
-        return fail(c, GH_ERR_NOMEM, "%s: device allocation of %lld doubles failed", who, (long long)c->N);
+        return fail(c, GH_ERR_NOMEM, "%s: device allocation of %lld doubles failed", who, (long long)n_out);
     }
     hipError_t e = hipMemcpyAsync(din, in, sizeof(double) * n_in, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
@@ -592,7 +663,7 @@ static int run_result(gh_ctx *c, const char *who, const double *in, size_t n_in,
         e = hipGetLastError();
     }
     if (e == hipSuccess)
-        e = hipMemcpyAsync(result, dres, sizeof(double) * (size_t)c->N, hipMemcpyDeviceToHost, c->stream);
+        e = hipMemcpyAsync(result, dres, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     hipFree(din);
     hipFree(dres);
@@ -616,6 +687,30 @@ int gh_tf_result(gh_ctx *c, const double *mag3, double *result)
             c->obs[0], c->obs[1], c->obs[2], c->bounds, dmag, c->N, cells, c->tf_dir[0], c->tf_dir[1], c->tf_dir[2],
             dres);
     });
+}
+
+int gh_b_result(gh_ctx *c, int component, const double *mag3, double *result)
+{
+    if (!c || !mag3 || !result) return fail(c, GH_ERR_ARG, "gh_b_result: null pointer");
+    TRY(need(c, c->have_obs && c->have_cells, "gh_b_result: call gh_set_cells_mvi_data (or gh_set_cells_mvi) and gh_set_obs "
+                                              "first"));
+    if (!c->mvi)
+        return fail(c, GH_ERR_ARG, "gh_b_result: the cells are not a magnetization-vector model (gh_set_cells_mvi, "
+                                   "gh_set_cells_mvi_data)");
+    if (component < GH_BCOMP_BX || component > GH_BCOMP_BZ)
+        return fail(c, GH_ERR_ARG, "gh_b_result: component %d is not GH_BCOMP_BX (1), GH_BCOMP_BY (2) or GH_BCOMP_BZ (3); the "
+                                   "total field's result is gh_tf_result", component);
+    typedef void (*result_fn)(const double *, const double *, const double *, const double *, const double *, int64_t,
+                              int64_t, double *);
+    static const result_fn fns[] = {prism_b_result_kernel<BCOMP_BX>, prism_b_result_kernel<BCOMP_BY>,
+                                    prism_b_result_kernel<BCOMP_BZ>};
+    const result_fn fn = fns[component - GH_BCOMP_BX];
+    const int64_t cells = c->M / 3, n = c->mc.n > 0 ? c->N / c->mc.n : c->N;
+    return run_result(c, "gh_b_result", mag3, 3 * (size_t)cells, result, [c, cells, n, fn](const double *dmag, double *dres) {
+        hipLaunchKernelGGL(fn, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double *)c->obs[0],
+                           (const double *)c->obs[1], (const double *)c->obs[2], (const double *)c->bounds, dmag, n, cells,
+                           dres);
+    }, n);
 }
 
 int gh_set_cells_prism(gh_ctx *c, const double *bounds6, int component)
@@ -874,6 +969,19 @@ int gh_build_G(gh_ctx *c)
         prism_mvi_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(
             c->obs[0], c->obs[1], c->obs[2], c->bounds, c->N, m, c->ld,
             make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), c->G);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else if (c->cell_kind == GH_CELL_PRISM_MVI_DATA) {
+        // every (data block, axis block) in one launch (m = M/3 cells, Nb points, each corner evaluated once); the
+        // threads behind a column's Nb points zero the padding rows below the stack
+        const int64_t m = c->M / 3, Nb = c->N / c->mc.n, Lr = Nb + (c->ld - c->N);
+        BComps bc{};
+        bc.n = c->mc.n;
+        for (int b = 0; b < bc.n; ++b) bc.comp[b] = c->mc.comp[b];
+        const int64_t blocks = std::min<int64_t>((Lr * m + 255) / 256, 1 << 22);
+        prism_mvi_data_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(
+            c->obs[0], c->obs[1], c->obs[2], c->bounds, Nb, m, c->ld,
+            make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), bc, c->G);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
     } else if (c->cell_kind == GH_CELL_PRISM || c->cell_kind == GH_CELL_PRISM_TF || c->cell_kind == GH_CELL_PRISM_COMP) {

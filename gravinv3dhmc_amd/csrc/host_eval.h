@@ -459,7 +459,11 @@ static int ensure_work(gh_ctx *c)
         // slab rows' sums per row block and the blocks' means)
         TRY(dalloc(c, &c->mc.bsum, (size_t)c->mc.n * (size_t)std::max(c->grid, 128)));
         TRY(dalloc(c, &c->mc.bmean, (size_t)c->mc.n));
-        for (int i = 0; i < 4; ++i) TRY(dalloc(c, &c->st[i].part, (size_t)c->n_dpart + (size_t)((c->M + 255) / 256)));
+        // (vector-data magnetization store: R's blocks are counted per property -- up to two more than ceil(M / 256) --
+        // and the amplitude term's partials follow them, one per 256 cells)
+        for (int i = 0; i < 4; ++i)
+            TRY(dalloc(c, &c->st[i].part, (size_t)c->n_dpart + (size_t)((c->M + 255) / 256) +
+                                              (c->mvi ? 3 + (size_t)((c->M / 3 + 255) / 256) : 0)));
     } else if (c->ld >= 2048 && ((c->TW > 1 && c->n_panels == 1 && !c->mf) || lonsym_on(c)) && env_int("GRAVHMC_EPILOGUE1", 1) != 0) {
         TRY(dalloc(c, &c->dsum, (size_t)std::max(std::max(c->grid, 128), lonsym_on(c) ? lonsym_classes(c) : 0)));
         // (magnetization-vector store: up to three more partials of R, its blocks being counted per property, and

@@ -1661,6 +1661,134 @@ prism_mvi_kernel(const double *__restrict__ xp, const double *__restrict__ yp, c
     }
 }
 
+// ---- vector magnetic data: bx, by, bz of prisms (GH_CELL_PRISM_MVI_DATA)
+
+// The data components: the values of GH_BCOMP_* (include/gravhmc.h; gravhmc.hip checks that they agree)
+enum { BCOMP_TF = 0, BCOMP_BX, BCOMP_BY, BCOMP_BZ };
+constexpr int BCOMP_MAX = 4;  // row blocks at most: every data component once
+struct BComps {
+    int n;
+    int comp[BCOMP_MAX];
+};
+
+// Vector-data magnetization store (GH_CELL_PRISM_MVI_DATA): columns as prism_mvi_kernel's, [A_x | A_y | A_z] of m
+// cells each, rows in bc.n blocks of Nb observations, block b the data component bc.comp[b].  One thread per
+// (obs, cell) pair evaluates the six second derivatives v1..v6 = xx, xy, xz, yy, yz, zz of each corner ONCE and
+// writes the pair's entry of every (data block, axis block).  The entry of component bx and axis a is what
+// _prism.bx accumulates for that prism with (mx, my, mz) = e_a (_prism.pyx:116-142): sum of (+-)(v1 mx + v2 my +
+// v3 mz) = the corner sum of v1, v2 or v3 alone (v * 1 + v' * 0 + v'' * 0 is v: every v is finite); by takes
+// (v2, v4, v5), bz (v3, v5, v6).  So six sums S1..S6 serve the nine (component, axis) entries, and bx's column of
+// axis y IS by's column of axis x.  A tf block is f . (column a of V) in _prism.tf's order fx bx + fy by + fz bz
+// with sums of its own: bit for bit prism_mvi_kernel's entries.  All scaled once by CM * T2NT.
+// Threads walk the Nb rows of a block, then the ld - n Nb padding rows below the stack, which they zero.
+__global__ void __launch_bounds__(256)
+prism_mvi_data_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
+                      const double *__restrict__ bounds6, int64_t Nb, int64_t m, int64_t ld, double3 dir, BComps bc,
+                      double *__restrict__ A)
+{
+#pragma clang fp contract(off)
+    const double fx = dir.x, fy = dir.y, fz = dir.z;
+    const int64_t Lr = Nb + (ld - bc.n * Nb);
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < Lr * m; idx += (int64_t)gridDim.x * 256) {
+        const int64_t c = idx / Lr, l = idx - c * Lr;
+        if (l >= Nb) {
+            const int64_t row = bc.n * Nb + (l - Nb);
+            A[c * ld + row] = 0.0;
+            A[(m + c) * ld + row] = 0.0;
+            A[(2 * m + c) * ld + row] = 0.0;
+            continue;
+        }
+        const double px = xp[l], py = yp[l], pz = zp[l];
+        const double *b = bounds6 + 6 * c;
+        const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
+        double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0, s6 = 0.0;
+        double ax = 0.0, ay = 0.0, az = 0.0;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const double dz = Z[k] - pz;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const double dy = Y[j] - py;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const double dx = X[i] - px;
+                    const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
+                    const double r = sqrt(dx * dx + dy * dy + dz * dz);
+                    const double v1 = -safe_atan2_d(dz * dy, dx * r);
+                    const double v2 = safe_log_d(dz + r);
+                    const double v3 = safe_log_d(dy + r);
+                    const double v4 = -safe_atan2_d(dz * dx, dy * r);
+                    const double v5 = safe_log_d(dx + r);
+                    const double v6 = -safe_atan2_d(dx * dy, dz * r);
+                    s1 += sign * v1;
+                    s2 += sign * v2;
+                    s3 += sign * v3;
+                    s4 += sign * v4;
+                    s5 += sign * v5;
+                    s6 += sign * v6;
+                    ax += sign * (fx * v1 + fy * v2 + fz * v3);
+                    ay += sign * (fx * v2 + fy * v4 + fz * v5);
+                    az += sign * (fx * v3 + fy * v5 + fz * v6);
+                }
+            }
+        }
+        // (coalesced: consecutive threads, consecutive rows of one column, in every block)
+#pragma unroll
+        for (int q = 0; q < BCOMP_MAX; ++q) {
+            if (q < bc.n) {
+                const int comp = bc.comp[q];
+                const double ex = comp == BCOMP_TF ? ax : comp == BCOMP_BX ? s1 : comp == BCOMP_BY ? s2 : s3;
+                const double ey = comp == BCOMP_TF ? ay : comp == BCOMP_BX ? s2 : comp == BCOMP_BY ? s4 : s5;
+                const double ez = comp == BCOMP_TF ? az : comp == BCOMP_BX ? s3 : comp == BCOMP_BY ? s5 : s6;
+                const int64_t row = q * Nb + l;
+                A[c * ld + row] = ex * TF_SCALE;
+                A[(m + c) * ld + row] = ey * TF_SCALE;
+                A[(2 * m + c) * ld + row] = ez * TF_SCALE;
+            }
+        }
+    }
+}
+
+// prism._bx / _by / _bz's `res` (prism.py:735-870): one thread per observation, the cells in mesh order, ONE sum per
+// observation over every corner of every cell of (-1)^(i+j+k) (row B of V) . m_c with the cell's magnetization m_c =
+// mag3[3c .. 3c+2], scaled once at the end -- the reference's accumulation order.  Only the three derivatives of
+// the component's row are evaluated, as _prism.bx / by / bz do.
+template <int B>
+__global__ void __launch_bounds__(256)
+prism_b_result_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
+                      const double *__restrict__ bounds6, const double *__restrict__ mag3, int64_t N, int64_t M,
+                      double *__restrict__ res)
+{
+#pragma clang fp contract(off)
+    const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= N) return;
+    const double px = xp[l], py = yp[l], pz = zp[l];
+    double acc = 0.0;
+    for (int64_t c = 0; c < M; ++c) {
+        const double mx = mag3[3 * c], my = mag3[3 * c + 1], mz = mag3[3 * c + 2];
+        acc = prism_corners(acc, px, py, pz, bounds6 + 6 * c, [&](double dx, double dy, double dz) {
+            const double r = sqrt(dx * dx + dy * dy + dz * dz);
+            if constexpr (B == BCOMP_BX) {
+                const double v1 = -safe_atan2_d(dz * dy, dx * r);
+                const double v2 = safe_log_d(dz + r);
+                const double v3 = safe_log_d(dy + r);
+                return v1 * mx + v2 * my + v3 * mz;
+            } else if constexpr (B == BCOMP_BY) {
+                const double v2 = safe_log_d(dz + r);
+                const double v4 = -safe_atan2_d(dz * dx, dy * r);
+                const double v5 = safe_log_d(dx + r);
+                return v2 * mx + v4 * my + v5 * mz;
+            } else {
+                const double v3 = safe_log_d(dy + r);
+                const double v5 = safe_log_d(dx + r);
+                const double v6 = -safe_atan2_d(dx * dy, dz * r);
+                return v3 * mx + v5 * my + v6 * mz;
+            }
+        });
+    }
+    res[l] = acc * TF_SCALE;
+}
+
 // Two-pass population standard deviation of the two unweighted blocks of a joint store (numpy.std, ddof 0):
 // pass 0 sums the entries, pass 1 the squares of their distances to mean[blk].  blockIdx.y = block; every
 // thread keeps a compensated (Kahan) sum over its grid-stride share, the workgroup sums its 256 threads and

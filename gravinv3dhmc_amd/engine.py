@@ -180,6 +180,46 @@ class Engine(object):
         self._chk(self._lib.gh_set_cells_mvi(self._h, ptr(b), fx, fy, fz))
         self.mvi = True
 
+    def set_cells_mvi_data(self, bounds6, direction, components, weights):
+        """The M/3 prisms (bounds (M/3, 6)) of a magnetization-vector model under vector data (gh_set_cells_mvi_data):
+        the data `components` (names of _lib.BCOMPONENTS or BCOMP_* values, distinct) at the same N / len(components)
+        points, stacked in row blocks, block b with the data weight weights[b] > 0; columns as set_cells_mvi.
+        direction = (fx, fy, fz) serves a "tf" block alone (None: zeros).  Call it before set_obs."""
+        b = f64(bounds6)
+        if self.M % 3 != 0 or b.shape != (self.M // 3, 6):
+            raise ValueError("bounds table of a magnetization-vector model must be (M/3, 6)")
+        comps = [_lib.BCOMPONENTS.get(c, -1) if isinstance(c, str) else int(c) for c in components]
+        if any(c not in _lib.BCOMPONENTS.values() for c in comps):
+            raise ValueError("data component must be one of %s" % ", ".join(_lib.BCOMPONENTS))
+        w = f64(weights)
+        if w.shape != (len(comps),):
+            raise ValueError("one data weight per component")
+        if direction is None:
+            if _lib.BCOMP_TF in comps:
+                raise ValueError("a total-field block needs direction = (fx, fy, fz)")
+            direction = (0.0, 0.0, 0.0)
+        if len(direction) != 3:
+            raise ValueError("direction must be (fx, fy, fz)")
+        fx, fy, fz = (float(v) for v in direction)
+        self._chk(self._lib.gh_set_cells_mvi_data(self._h, ptr(b), fx, fy, fz, len(comps),
+                                                  (C.c_int * max(len(comps), 1))(*comps), ptr(w)))
+        self.mvi = True
+        # (the unweighted total field alone is the magnetization-vector store itself: one block, no block table)
+        if not (comps == [_lib.BCOMP_TF] and w[0] == 1.0):
+            self.multi = len(comps)
+
+    def b_result(self, component, mag3):
+        """bx, by or bz (uT; component a name or BCOMP_* value) at the observation points of a magnetization-vector
+        context whose M/3 cells are magnetized with mag3[M/3, 3] (A/m), in the reference's accumulation order
+        (gh_b_result); needs no G."""
+        comp = _lib.BCOMPONENTS.get(component, -1) if isinstance(component, str) else int(component)
+        m = f64(mag3)
+        if not getattr(self, "mvi", False) or m.shape != (self.M // 3, 3):
+            raise ValueError("magnetization must be (M/3, 3) on a magnetization-vector context")
+        out = np.empty(self.N // getattr(self, "multi", 1))
+        self._chk(self._lib.gh_b_result(self._h, comp, ptr(m), ptr(out)))
+        return out
+
     def set_amplitude(self, lam, beta, scale=1.0):
         """Amplitude coupling lam * sum_c s_c / (s_c + beta) of a weighted magnetization-vector context
         (gh_set_amplitude), s_c the squared amplitude of cell c's physical vector over scale.  lam = 0 switches the

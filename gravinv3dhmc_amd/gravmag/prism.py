@@ -7,7 +7,10 @@ Mirror of the reference's `gravmag.prism.gz` (gravmag/prism.py:911-918 -> _dispa
 `potential` (G, SI units per g/cm^3), `geoid` (m), `gx`, `gy` (mGal) and the gradient tensor `gxx`,
 `gxy`, `gxz`, `gyy`, `gyz`, `gzz` (Eotvos).  And of `gravmag.prism.tf` (prism.py:975 ->
 _dispatcher_magnetic :1140-1180 -> _tf :665-733 -> _prism.tf, _prism.pyx:80-113): `(result, kernel2d)`
-in uT for magnetizations in A/m (CM * T2NT, constants.py).  `njobs`/`pool` are accepted and
+in uT for magnetizations in A/m (CM * T2NT, constants.py).  And of its `_bx`, `_by`, `_bz`
+(prism.py:735-870 -> _prism.bx / by / bz, _prism.pyx:114-202): `bx`, `by`, `bz` return the reference's `res` in
+uT and, beside it, the kernel [K_x | K_y | K_z] of unit-axis columns, which the reference does not form.
+`njobs`/`pool` are accepted and
 ignored (the reference uses them for host multiprocessing; the assembly here is one HIP
 launch over all (observation, cell) pairs).
 """
@@ -86,6 +89,57 @@ def tf(xp, yp, zp, prisms, inc, dec, pmag=None, njobs=1, pool=None, return_kerne
     finally:
         eng.close()
     return result, kernel2d
+
+
+def _b_field(component, xp, yp, zp, prisms, pmag, return_kernel, device):
+    """(result, K) of one component of the anomalous induction: the result in the reference's accumulation order
+    (gh_b_result) from the cells' magnetization VECTORS (or pmag for every cell; cells without the property are
+    skipped), K = [K_x | K_y | K_z] (N x 3 M_active, Fortran-ordered; None without return_kernel) from the dense
+    assembly: column a M_active + c is the component of cell c magnetized 1 A/m along axis a."""
+    xp, yp, zp = (np.asarray(a, dtype=np.float64) for a in (xp, yp, zp))
+    if xp.shape != yp.shape or xp.shape != zp.shape:
+        raise ValueError("Input arrays xp, yp, and zp must have same shape!")
+    if pmag is not None and np.shape(pmag) != (3,):
+        raise ValueError("pmag must be a vector (mx, my, mz)")
+    try:
+        bounds, mag3, _ = active_cells_mag(prisms, pmag, None)
+    except TypeError:       # (a scalar intensity: there is no field direction to put it along)
+        raise ValueError("the 'magnetization' of every cell must be a vector (mx, my, mz)")
+    if bounds.shape[0] == 0:
+        raise ValueError("mesh has no cell with a 'magnetization' property (and no pmag given)")
+    if mag3.shape != (bounds.shape[0], 3):
+        raise ValueError("the 'magnetization' of every cell must be a vector (mx, my, mz)")
+    eng = Engine(xp.size, 3 * bounds.shape[0], device=device)
+    try:
+        eng.set_cells_mvi_data(bounds, None, (component,), (1.0,))
+        eng.set_obs(xp.ravel(), yp.ravel(), zp.ravel())
+        result = eng.b_result(component, mag3)
+        kernel = None
+        if return_kernel:
+            eng.build_G()
+            kernel = eng.download_G()
+    finally:
+        eng.close()
+    return result, kernel
+
+
+def bx(xp, yp, zp, prisms, pmag=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """North component of the anomalous magnetic induction of the prism model in uT, and its kernel.
+
+    A cell's 'magnetization' is a vector (mx, my, mz) in A/m; pmag (a vector) overrides it for every cell; cells
+    without the property are skipped.  Returns (result[N], K[N, 3 M_active]) with K = [K_x | K_y | K_z], the
+    component for a unit magnetization of every kept cell along x north, y east and z down."""
+    return _b_field("bx", xp, yp, zp, prisms, pmag, return_kernel, device)
+
+
+def by(xp, yp, zp, prisms, pmag=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """East component of the anomalous magnetic induction in uT and its kernel [K_x | K_y | K_z] (see bx)."""
+    return _b_field("by", xp, yp, zp, prisms, pmag, return_kernel, device)
+
+
+def bz(xp, yp, zp, prisms, pmag=None, njobs=1, pool=None, return_kernel=True, device=0):
+    """Downward component of the anomalous magnetic induction in uT and its kernel [K_x | K_y | K_z] (see bx)."""
+    return _b_field("bz", xp, yp, zp, prisms, pmag, return_kernel, device)
 
 
 def build_engine_component(xp, yp, zp, prisms, component, dens=None, device=0):

@@ -10,16 +10,27 @@ The store is an ordinary dense N x M kernel: the column-norm weights Wm are take
 removes the mean as the magnetic GravMagModule does, Damping and MS act on the M entries as they are, Smoothness and
 TV apply the stencil to each component on its own.  The amplitude term lambda * sum_c s_c / (s_c + beta), s_c =
 |m_c|^2, is the one term that ties the three components of a cell together; it is off by default.
+
+Vector data.  The total field is the projection of B on the regional direction: it cannot by itself fix a rotated
+(remanent) magnetization.  With data=("bx", "by", "bz") -- any distinct choice of "tf", "bx", "by", "bz" -- the rows
+of the store are blocks of those components at the same points (libgravhmc's GH_CELL_PRISM_MVI_DATA), block b in its
+own units times a data weight w_b.  The rows then behave as MultiComponentModule's: Wm are the column norms of Wb A,
+and the data term removes the mean of every block on its own,
+
+    r_b = (d_b - mean d_b) - (dobsw_b - mean dobsw_b),   data_value = sum_b |r_b|^2,   grad = 2 Aw^T r
+
+with d = Aw mw, Aw = Wb A Wm^-1, dobsw = Wb dobs.  The columns, the regularisers and the amplitude term stay as above.
 """
 import time
 
 import numpy as np
 
-from .. import mesher, utils
+from .. import _lib, mesher, utils
 from ..engine import DeviceMatrix, Engine
 from .potential import _diag, _Potential
 
 _STORE = "the magnetization-vector store"
+_VSTORE = "the vector-data magnetization store"
 
 
 class MagVectorModule(_Potential):
@@ -28,6 +39,14 @@ class MagVectorModule(_Potential):
     dobs: the N total-field anomalies (uT) at obsurface = [xobs, yobs, height]; mrange, mspacing, mratio, mseg,
     mdivisionsection, weightfactor, mtopo=(x, y, topography), device and verbose as GravMagModule; mangle =
     (inclination, declination) of the regional field in degrees.
+
+    data: the data components, a tuple drawn from "tf", "bx", "by", "bz" (distinct).  The default ("tf",) with
+    weights=None is the module as it always was.  Otherwise dobs is a sequence of len(data) arrays, or a dict keyed by
+    component, each of the N values at the N points, in uT; mangle is needed only when "tf" is among them.  weights:
+    None (ones), "std" (w_b = std(dobs_0) / std(dobs_b), MultiComponentModule's rule) or one positive number per
+    component.  The module then has components, weights, Wb, dobs (stacked, component-major) and dobsw = Wb dobs;
+    forward(model) returns the component-major stack, each block in its own units; kernel(axis, component) selects a
+    block; block_means() the means of the last evaluation.  Everything else works as on the default module.
 
     amplitude = lambda, amplitude_beta = beta: with lambda > 0 every potential evaluation and every chain adds
     lambda * Phi, Phi = sum_c s_c / (s_c + beta) with s_c = mx_c^2 + my_c^2 + mz_c^2 of the PHYSICAL model in A/m (the
@@ -39,38 +58,84 @@ class MagVectorModule(_Potential):
 
     HMCSample and misfit_and_grad work on it as on GravMagModule; bounds such as [-mmax, mmax] per component go
     through `boundaries`.  Not supported (NotImplementedError): coordinate="spherical", wavelet compression, the
-    matrix-free mode, the shift-invariant store, shards, HMCSampleBatch and more than 16384 observations (the store
-    runs on the fused sweep).  Smoothness and TV need the full mesh (ValueError on a carved one).
+    matrix-free mode, the shift-invariant store, shards, HMCSampleBatch and more than 16384 observations -- stacked
+    rows len(data) x N under vector data -- (the store runs on the fused sweep).  Smoothness and TV need the full mesh (ValueError on a carved one).
     """
     _props = 3  # (mx, my and mz of the same mesh)
 
     def __init__(self, dobs, mrange, mspacing, obsurface, mangle=(90, 0), mratio=1, mseg=False, mdivisionsection=[],
                  weightfactor=0.5, amplitude=0.0, amplitude_beta=0.01, device=0, verbose=True, coordinate="cartesian",
-                 wavelet=False, matrix_free=False, shift_invariant=False, shard=None, **kwargs):
+                 wavelet=False, matrix_free=False, shift_invariant=False, shard=None, data=("tf",), weights=None,
+                 **kwargs):
         self._say = print if verbose else (lambda *a, **k: None)
         unknown = sorted(set(kwargs) - {"mtopo"})
         if unknown:
             raise TypeError("unexpected keyword argument %r" % unknown[0])
+        data = (data,) if isinstance(data, str) else tuple(data)
+        if len(data) == 0:
+            raise ValueError("data is empty: name at least one of %s" % ", ".join(_lib.BCOMPONENTS))
+        for b in data:
+            if b not in _lib.BCOMPONENTS:
+                raise ValueError("data component %r: must be one of %s" % (b, ", ".join(_lib.BCOMPONENTS)))
+        if len(set(data)) != len(data):
+            raise ValueError("data components must be distinct, got %r" % (data,))
+        n = int(np.asarray(obsurface[0]).size)
+        # the default is the module as it always was: one block of the total field, one mean, no block table
+        self._vector = not (data == ("tf",) and weights is None)
+        store = _VSTORE if self._vector else _STORE
+        if self._vector:
+            if isinstance(dobs, dict):
+                if set(dobs) != set(data):
+                    raise ValueError("dobs has the components %r, expected %r" % (sorted(dobs), sorted(data)))
+                dobs = [dobs[b] for b in data]
+            dobs = [np.asarray(d, dtype=np.float64).ravel() for d in dobs]
+            if len(dobs) != len(data):
+                raise ValueError("%d observation vectors for %d data components" % (len(dobs), len(data)))
+            for b, d in zip(data, dobs):
+                if d.size != n:
+                    raise ValueError("dobs of %s has %d values, the observation points are %d" % (b, d.size, n))
+            if weights is None:
+                w = np.ones(len(data))
+            elif isinstance(weights, str):
+                if weights != "std":
+                    raise ValueError("weights must be None, 'std' or one positive number per data component")
+                sd = np.array([np.std(d) for d in dobs])
+                if not np.all(sd > 0):
+                    raise ValueError("weights='std' needs observations that vary in every component")
+                w = sd[0] / sd
+            else:
+                w = np.asarray(weights, dtype=np.float64).ravel()
+                if w.size != len(data) or not np.all(np.isfinite(w)) or not np.all(w > 0):
+                    raise ValueError("weights must be None, 'std' or one positive number per data component")
         if coordinate == "spherical":
             raise NotImplementedError("%s holds prism fields: tesseroids (coordinate='spherical') are not supported"
-                                      % _STORE)
+                                      % store)
         if coordinate != "cartesian":
             raise ValueError("Please choose coordinate from(cartesian, spherical)!")
         if wavelet not in (False, None):
-            raise NotImplementedError("wavelet compression of %s is not supported" % _STORE)
+            raise NotImplementedError("wavelet compression of %s is not supported" % store)
         if matrix_free:
-            raise NotImplementedError("%s is dense: the matrix-free mode is not supported" % _STORE)
+            raise NotImplementedError("%s is dense: the matrix-free mode is not supported" % store)
         if shift_invariant:
-            raise NotImplementedError("%s is dense: the shift-invariant store is not supported" % _STORE)
+            raise NotImplementedError("%s is dense: the shift-invariant store is not supported" % store)
         if shard is not None:
-            raise NotImplementedError("%s is not sharded" % _STORE)
-        dobs = np.asarray(dobs, dtype=np.float64).ravel()
-        n = int(np.asarray(obsurface[0]).size)
-        if dobs.size != n:
-            raise ValueError("dobs has %d values, the observation points are %d" % (dobs.size, n))
-        if n > 16384:
-            raise NotImplementedError("%d observations: %s takes at most 16384 (it runs on the fused sweep)"
-                                      % (n, _STORE))
+            raise NotImplementedError("%s is not sharded" % store)
+        if self._vector:
+            if len(data) * n > 16384:
+                raise NotImplementedError("%d data components x %d observations = %d rows: %s takes at most 16384 (it "
+                                          "runs on the fused sweep)" % (len(data), n, len(data) * n, store))
+            self.weights = w
+            dobs = np.concatenate(dobs)
+        else:
+            dobs = np.asarray(dobs, dtype=np.float64).ravel()
+            if dobs.size != n:
+                raise ValueError("dobs has %d values, the observation points are %d" % (dobs.size, n))
+            if n > 16384:
+                raise NotImplementedError("%d observations: %s takes at most 16384 (it runs on the fused sweep)"
+                                          % (n, store))
+            self.weights = np.ones(1)
+        self.components = data
+        self._n = n
         if not (amplitude >= 0) or not (amplitude_beta > 0):
             raise ValueError("amplitude must be >= 0 and amplitude_beta > 0")
 
@@ -98,11 +163,15 @@ class MagVectorModule(_Potential):
         self._cells = int(bounds.shape[0])
         self._say("Start of calculate kernel")
         start = time.time()
-        eng = Engine(n, 3 * self._cells, device=device)
-        eng.set_cells_mvi(bounds, utils.dircos(self.inc, self.dec))
+        if self._vector:
+            eng = Engine(len(data) * n, 3 * self._cells, device=device)
+            eng.set_cells_mvi_data(bounds, utils.dircos(self.inc, self.dec) if "tf" in data else None, data, w)
+        else:
+            eng = Engine(n, 3 * self._cells, device=device)
+            eng.set_cells_mvi(bounds, utils.dircos(self.inc, self.dec))
         eng.set_obs(self.lonobs, self.latobs, self.heightobs)
         eng.build_G()
-        self._say("kernel.shape", (n, 3 * self._cells))
+        self._say("kernel.shape", (eng.N, 3 * self._cells))
         self._say("End of calculate kernel:%.6f s" % (time.time() - start))
         self._engine = eng
 
@@ -112,7 +181,11 @@ class MagVectorModule(_Potential):
         start = time.time()
         self.sensitivityWeighting()
         self._say("End of weighting kernel: %.6f s" % (time.time() - start))
-        eng.set_data(self.dobs)
+        if self._vector:
+            self.dobsw = self.Wb @ self.dobs
+            eng.set_data(self.dobsw)
+        else:
+            eng.set_data(self.dobs)
         self._amp = None  # (lambda, beta) once the engine holds the term
         self._amp_beta = float(amplitude_beta)
         if amplitude != 0:
@@ -127,6 +200,8 @@ class MagVectorModule(_Potential):
         self.Wm = _diag(wm)
         self.WmInv = _diag(inv)
         self.WmSquare = _diag(wm * wm)
+        if self._vector:
+            self.Wb = _diag(np.repeat(self.weights, self._n))
         self.Aw = DeviceMatrix(self._engine)
 
     def kernelw(self):
@@ -136,22 +211,42 @@ class MagVectorModule(_Potential):
     @property
     def A(self):
         """The unweighted kernel [A_x | A_y | A_z], N x M, from the device copy (Aw Wm; rounding differs)."""
-        return np.asarray(self.Aw) * self.Wm.diagonal()[None, :]
+        A = np.asarray(self.Aw) * self.Wm.diagonal()[None, :]
+        return A / self.Wb.diagonal()[:, None] if self._vector else A
 
-    def kernel(self, axis):
+    def kernel(self, axis, component=None):
         """Block A_axis (N x M/3, uT per A/m along axis 0 / "x" north, 1 / "y" east, 2 / "z" down), from the device
-        copy."""
+        copy.  Under vector data: of the data component `component` alone (N rows), or with component=None of every
+        row block (len(data) N rows), in the components' own units."""
         a = {"x": 0, "y": 1, "z": 2}.get(axis, axis)
         if a not in (0, 1, 2):
             raise ValueError("axis must be 0, 1, 2 or 'x', 'y', 'z', got %r" % (axis,))
+        if component is not None and component not in self.components:
+            raise ValueError("component %r is not one of this module's %r" % (component, self.components))
         m = self._cells
         Aw = np.asarray(self.Aw)[:, a * m:(a + 1) * m]
+        if self._vector:
+            if component is None:
+                Aw = Aw / self.Wb.diagonal()[:, None]
+            else:
+                b, n = self.components.index(component), self._n
+                Aw = Aw[b * n:(b + 1) * n] / self.weights[b]
         return np.asfortranarray(Aw * self.Wm.diagonal()[None, a * m:(a + 1) * m])
 
     def forward(self, model):
-        """Unweighted forward A @ model (uT): model is the property-major M vector in A/m."""
+        """Unweighted forward A @ model (uT): model is the property-major M vector in A/m.  Under vector data the
+        component-major stack, each block in its own units."""
         model = np.asarray(model, dtype=np.float64).ravel()
-        return self._engine.forward(model * self.Wm.diagonal())
+        d = self._engine.forward(model * self.Wm.diagonal())
+        return d / self.Wb.diagonal() if self._vector else d
+
+    def block_means(self):
+        """Under vector data: (means of the last evaluation's weighted prediction Aw mw, means removed from the weighted
+        observations), one per data component."""
+        if not self._vector:
+            raise ValueError("block_means: the module has one block of total-field data (data=('tf',))")
+        info = self._engine.multi_info()
+        return info["pred_mean"], info["obs_mean"]
 
     # ------------------------------------------------------------------ the model as vectors
     def to_vectors(self, model):

@@ -15,7 +15,7 @@ seen in the code it generated, so the build checks THAT code, with the hipcc tha
   (gfx9 counts loads and stores in the same counter, in order).
 
 The same compile also serves `scan_plain_kernels()`: the kernels listed in PLAIN_KERNELS (the magnetization-vector
-store's assembly and amplitude term) must be in the generated code and must not spill, by the compiler's resource
+stores' assemblies and amplitude term) must be in the generated code and must not spill, by the compiler's resource
 report.
 
 `check()` returns the list of findings (empty: clean).  `stamp()` records the verdict next to the
@@ -36,7 +36,7 @@ HEADERS = ("kernels.hip.h", "batch.hip.h", "exchange.hip.h", "resident.hip.h", "
 SYMBOL = "_ZN3ghk17batch_team_kernelENS_12BatchAdjArgsENS_6BtArgsE"
 _VMEM = re.compile(r"(global|buffer|flat|scratch)_(load|store|atomic)")
 #: kernels held to "present and no spills" (every instantiation whose name contains the entry)
-PLAIN_KERNELS = ("prism_mvi_kernel", "amplitude_kernel")
+PLAIN_KERNELS = ("prism_mvi_kernel", "prism_mvi_data_kernel", "amplitude_kernel")
 
 
 def hipcc_version(hipcc):

@@ -85,9 +85,17 @@ typedef enum {
  * GH_CELL_TESSEROID_COMP: tesseroids, one gravity field other than gz (set with gh_set_cells_tess);
  * GH_CELL_PRISM_JOINT: prisms, gz and the total field inverted together (set with gh_set_cells_joint);
  * GH_CELL_PRISM_MULTI: prisms, several gravity fields of one density model inverted together (gh_set_cells_multi);
- * GH_CELL_PRISM_MVI: prisms, the total field of a magnetization VECTOR per cell (gh_set_cells_mvi) */
+ * GH_CELL_PRISM_MVI: prisms, the total field of a magnetization VECTOR per cell (gh_set_cells_mvi);
+ * GH_CELL_PRISM_MVI_DATA: prisms, a magnetization vector per cell under VECTOR data -- row blocks of tf, bx, by, bz
+ * (gh_set_cells_mvi_data) */
 enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2, GH_CELL_PRISM_COMP = 3, GH_CELL_TESSEROID_COMP = 4,
-       GH_CELL_PRISM_JOINT = 5, GH_CELL_PRISM_MULTI = 6, GH_CELL_PRISM_MVI = 7 };
+       GH_CELL_PRISM_JOINT = 5, GH_CELL_PRISM_MULTI = 6, GH_CELL_PRISM_MVI = 7, GH_CELL_PRISM_MVI_DATA = 8 };
+/* The magnetic data components of prisms, for gh_set_cells_mvi_data and gh_b_result: the total-field anomaly along
+ * the regional field, and the north, east and down components of the anomalous induction (gravmag/prism.py:665-870),
+ * all in uT per A/m (CM * T2NT) */
+enum { GH_BCOMP_TF = 0, GH_BCOMP_BX = 1, GH_BCOMP_BY = 2, GH_BCOMP_BZ = 3 };
+/* data components a GH_CELL_PRISM_MVI_DATA context stacks at most: every GH_BCOMP_* once */
+#define GH_BCOMP_MAX 4
 /* components a GH_CELL_PRISM_MULTI context stacks at most: every GH_COMP_* once */
 #define GH_MULTI_MAX 11
 /* The gravity fields of prisms (gravmag/prism.py:875-972), for gh_set_cells_prism, and of tesseroids
@@ -161,6 +169,40 @@ int gh_tf_result(gh_ctx *ctx, const double *mag3, double *result);
  * gh_shard_init*, gh_upload_G and N > 16384 return GH_ERR_UNSUPPORTED naming the magnetization-vector store; the
  * resident chain kernel and the folded store are never chosen (chains run on the fused sweep). */
 int gh_set_cells_mvi(gh_ctx *ctx, const double *bounds6 /* M/3 x 6 */, double fx, double fy, double fz);
+/* Magnetization vector inversion under VECTOR data (GH_CELL_PRISM_MVI_DATA): three-axis magnetometers record
+ * (bx, by, bz), and the total field alone -- the projection of B on the regional direction -- cannot fix a rotated
+ * (remanent) magnetization.  ncomp distinct data components comps[b] (GH_BCOMP_*) of the same M/3 prisms at the same
+ * N / ncomp observation points, stacked in row blocks; the columns are gh_set_cells_mvi's [A_x | A_y | A_z]:
+ *     rows [b N/ncomp, (b + 1) N/ncomp), column a M/3 + c:  component comps[b] at the block's points of prism c
+ *     magnetized 1 A/m along axis a, in uT -- for bx, by, bz what the reference's _prism.bx / by / bz accumulate for
+ *     that one prism with (mx, my, mz) = e_a, times CM*T2NT (_prism.pyx:114-202: bx uses the second derivatives
+ *     (xx, xy, xz), by (xy, yy, yz), bz (xz, yz, zz)); a tf block is bit for bit the gh_set_cells_mvi store.
+ * The context's N is the STACKED length, observation-space vectors are component-major, M = 3 x prisms and model
+ * vectors are property-major.  (fx, fy, fz) is used by a tf block alone (finite in any case).  Call it on a fresh
+ * context, BEFORE gh_set_obs, which then takes the N / ncomp points.  gh_build_G assembles every block in ONE launch
+ * that evaluates the six second derivatives of a corner once.
+ * The store is the union of two the library already has:
+ *   rows as gh_set_cells_multi: gh_weight scales block b by weights[b] > 0 (Wb), takes the column norms Wm of Wb A and
+ *     leaves Aw = Wb A Wm^-1; gh_set_data takes Wb [dobs_0; ...] and removes the mean of every block on its own
+ *     (grav_fix must be null); the data term removes the mean per block on the prediction's side too; gh_multi_info
+ *     reports the blocks (comps as GH_BCOMP_*) and their means;
+ *   columns as gh_set_cells_mvi: Damping and MS act on the M entries, Smoothness and TV take shape3 with nz*ny*nx ==
+ *     M/3 and apply the stencil to each component on its own, gh_set_amplitude couples the three components of a cell.
+ * With comps = {GH_BCOMP_TF} and weights = {1} the call IS gh_set_cells_mvi: the context is a GH_CELL_PRISM_MVI one
+ * and computes exactly what that call's context computes (one block, one mean; gh_multi_info then refuses).
+ * Dense, single chain only, on the fused sweep with the per-block means: matrix-free, the shift-invariant store, the
+ * wavelet compressor, gh_batch_*, gh_shard_init*, gh_upload_G and a stacked N > 16384 return GH_ERR_UNSUPPORTED naming
+ * the vector-data magnetization store; the resident chain kernel and the folded store are never chosen.
+ * Errors: GH_ERR_ARG for ncomp outside 1..GH_BCOMP_MAX, an unknown or repeated component, a weight that is not
+ * finite and > 0, M not a multiple of 3, N not a multiple of ncomp, a context that is not fresh. */
+int gh_set_cells_mvi_data(gh_ctx *ctx, const double *bounds6 /* M/3 x 6 */, double fx, double fy, double fz, int ncomp,
+                          const int *comps, const double *weights);
+/* prism._bx / _by / _bz's `res` on a GH_CELL_PRISM_MVI or GH_CELL_PRISM_MVI_DATA context (needs gh_set_obs and the
+ * cells, not G): component is GH_BCOMP_BX, _BY or _BZ (the total field: gh_tf_result), mag3 the magnetization
+ * (mx, my, mz) in A/m of each of the M/3 prisms, row-major; result (one value per observation POINT: N / ncomp)
+ * in uT, accumulated corner by corner, cell by cell in mesh order into one sum per observation and scaled once, as
+ * the reference does (prism.py:735-870). */
+int gh_b_result(gh_ctx *ctx, int component, const double *mag3 /* M/3 x 3 */, double *result);
 /* Amplitude coupling of a weighted GH_CELL_PRISM_MVI context: the minimum-support functional of the cells'
  * amplitude, the one term that ties the three components of a cell together (compact bodies).  With
  *     u_a[c] = mw[a M/3 + c] winv[a M/3 + c] / scale   (winv = 1 / Wm, 0 where Wm is 0),   s_c = sum_a u_a[c]^2,
@@ -231,7 +273,8 @@ int gh_joint_layout(const gh_ctx *ctx, int *workgroups_per_block, int *epilogue_
  * matrix-free, the shift-invariant store, the wavelet compressor, gh_batch_*, gh_shard_init* and gh_upload_G; the
  * resident chain kernel and the folded store are never chosen. */
 int gh_set_cells_multi(gh_ctx *ctx, const double *bounds6, int ncomp, const int *comps, const double *weights);
-/* The blocks of a GH_CELL_PRISM_MULTI context (every pointer may be null; arrays of GH_MULTI_MAX hold them):
+/* The blocks of a GH_CELL_PRISM_MULTI or GH_CELL_PRISM_MVI_DATA context (comps: GH_COMP_* or GH_BCOMP_* values; every
+ * pointer may be null; arrays of GH_MULTI_MAX hold them):
  * their number, components and weights, the mean of each block of the LAST evaluation's prediction Aw mw
  * (gh_misfit_and_grad, or the chain's last step; zeros before the first), and the mean gh_set_data removed from
  * each block of the weighted observations. */
