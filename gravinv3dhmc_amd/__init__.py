@@ -9,7 +9,8 @@ from . import constants, mesher  # noqa: F401
 from .engine import DeviceMatrix, Engine  # noqa: F401
 from .gravmag import prism, tesseroid  # noqa: F401
 from .inversion import (BootStrap, ConjugateGradient, GravMagModule, HamitonianMC, HMCSample,  # noqa: F401
-                        HMCSampleBatch, JointModule, MagVectorModule, MultiComponentModule)
+                        HMCSampleBatch, JointModule, MagVectorModule, MultiComponentModule,
+                        TesseroidMagVectorModule)
 
 __all__ = ["constants", "mesher", "prism", "tesseroid", "Engine", "DeviceMatrix",
-           "GravMagModule", "JointModule", "MagVectorModule", "MultiComponentModule", "HamitonianMC", "HMCSample", "HMCSampleBatch", "ConjugateGradient", "BootStrap"]
+           "GravMagModule", "JointModule", "MagVectorModule", "MultiComponentModule", "TesseroidMagVectorModule", "HamitonianMC", "HMCSample", "HMCSampleBatch", "ConjugateGradient", "BootStrap"]

@@ -18,6 +18,7 @@ CELL_PRISM, CELL_TESSEROID, CELL_PRISM_TF, CELL_PRISM_COMP, CELL_TESSEROID_COMP,
 CELL_PRISM_MULTI = 6
 CELL_PRISM_MVI = 7
 CELL_PRISM_MVI_DATA = 8
+CELL_TESS_MVI_DATA = 9
 #: the magnetic data components of prisms (GH_BCOMP_*, gh_set_cells_mvi_data / gh_b_result)
 BCOMP_TF, BCOMP_BX, BCOMP_BY, BCOMP_BZ = range(4)
 BCOMPONENTS = {"tf": BCOMP_TF, "bx": BCOMP_BX, "by": BCOMP_BY, "bz": BCOMP_BZ}
@@ -50,6 +51,8 @@ PROTOTYPES = {
     "gh_set_cells_mvi": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
     "gh_set_cells_mvi_data": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), _dp]),
     "gh_b_result": (C.c_int, [_ctx, C.c_int, _dp, _dp]),
+    "gh_set_cells_tess_mag": (C.c_int, [_ctx, _dp, C.c_double, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
+    "gh_tess_b_result": (C.c_int, [_ctx, C.c_int, _dp, _dp]),
     "gh_set_amplitude": (C.c_int, [_ctx, C.c_double, C.c_double, C.c_double]),
     "gh_amplitude_eval": (C.c_int, [_ctx, _dp, C.POINTER(C.c_double), _dp, _dp]),
     "gh_amplitude_last": (C.c_int, [_ctx, C.POINTER(C.c_double)]),

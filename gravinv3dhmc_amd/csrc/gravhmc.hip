@@ -16,6 +16,7 @@
 #include "lonsymw.hip.h"
 #include "fold.hip.h"
 #include "poststream.hip.h"
+#include "tessmag.hip.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -191,8 +192,9 @@ int gh_set_obs(gh_ctx *c, const double *a, const double *b, const double *cc)
 static int set_cells(gh_ctx *c, const double *bounds6, int kind, int comp, double ratio, const double *dir = nullptr)
 {
     if (c->joint) return fail(c, GH_ERR_UNSUPPORTED, "a joint gravity-magnetic context takes its cells from gh_set_cells_joint");
-    if (c->mc.n > 0 && c->mvi)
-        return fail(c, GH_ERR_UNSUPPORTED, "a vector-data magnetization context takes its cells from gh_set_cells_mvi_data");
+    if (vector_data_store(c))
+        return fail(c, GH_ERR_UNSUPPORTED, "a vector-data magnetization context takes its cells from %s",
+                    tess_mag_store(c) ? "gh_set_cells_tess_mag" : "gh_set_cells_mvi_data");
     if (c->mc.n > 0) return fail(c, GH_ERR_UNSUPPORTED, "a multi-component context takes its cells from gh_set_cells_multi");
     if (c->mvi) return fail(c, GH_ERR_UNSUPPORTED, "a magnetization-vector context takes its cells from gh_set_cells_mvi");
     HIPCHK(c, hipSetDevice(c->device));
@@ -370,9 +372,84 @@ int gh_set_cells_mvi_data(gh_ctx *c, const double *bounds6, double fx, double fy
     return GH_OK;
 }
 
+int gh_set_cells_tess_mag(gh_ctx *c, const double *bounds6, double ratio, int ncomp, const int *comps,
+                          const double *weights, const double *fdir)
+{
+    if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: null pointer");
+    if (ncomp < 1 || ncomp > GH_BCOMP_MAX)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: %d data components: the tesseroid magnetization store takes 1 "
+                                   "to %d", ncomp, GH_BCOMP_MAX);
+    bool tf = false;
+    for (int b = 0; b < ncomp; ++b) {
+        if (comps[b] < GH_BCOMP_TF || comps[b] > GH_BCOMP_BZ)
+            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: component %d is not one of GH_BCOMP_TF (0) .. GH_BCOMP_BZ (3)",
+                        comps[b]);
+        for (int a = 0; a < b; ++a)
+            if (comps[a] == comps[b])
+                return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: component %d is listed twice", comps[b]);
+        if (!(weights[b] > 0.0) || !std::isfinite(weights[b]))
+            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: the data weights must be finite and > 0");
+        tf = tf || comps[b] == GH_BCOMP_TF;
+    }
+    if (c->M % 3 != 0 || c->M < 3)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: M = %lld is not three components of the same tesseroids",
+                    (long long)c->M);
+    if (c->N % ncomp != 0)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: N = %lld is not %d blocks of the same observation points",
+                    (long long)c->N, ncomp);
+    if (!(ratio > 0)) return fail(c, GH_ERR_ARG, "Invalid ratio %g. Must be > 0.", ratio);
+    if (tf && !fdir)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: a total-field block needs fdir, one unit vector per observation "
+                                   "point");
+    const int64_t m = c->M / 3, Nb = c->N / ncomp;
+    if (fdir)
+        for (int64_t i = 0; i < 3 * Nb; ++i)
+            if (!std::isfinite(fdir[i]))
+                return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: the field directions must be finite");
+    // w <= e, s <= n, top >= bottom: the reference's assertion (tesseroid.py:137-138)
+    for (int64_t j = 0; j < m; ++j) {
+        const double *b = bounds6 + 6 * j;
+        if (!(b[0] <= b[1] && b[2] <= b[3] && b[4] >= b[5]))
+            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: invalid tesseroid dimensions (cell %lld: %g %g %g %g %g %g)",
+                        (long long)j, b[0], b[1], b[2], b[3], b[4], b[5]);
+    }
+    if (c->joint || c->mvi || c->mc.n > 0 || c->have_obs || c->have_cells || c->have_G || c->slab)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: call it first on a fresh context (before gh_set_obs)");
+    if (c->mf || c->ls)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_mag: the tesseroid magnetization store is dense only (no "
+                                           "matrix-free mode, no shift-invariant store)");
+    if (c->sh.kind != 0)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_mag: the tesseroid magnetization store is not sharded");
+    if (c->N > 16384)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_mag: %d components x %lld observations = %lld rows: the "
+                                           "tesseroid magnetization store takes at most 16384 (it runs on the fused "
+                                           "sweep: no row panels, no team sweep)", ncomp, (long long)Nb, (long long)c->N);
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(dalloc(c, &c->bounds, (size_t)m * 6));
+    TRY(h2d(c, c->bounds, bounds6, (size_t)m * 6));
+    if (fdir) {
+        TRY(dalloc(c, &c->tmag_fdir, (size_t)Nb * 3));
+        TRY(h2d(c, c->tmag_fdir, fdir, (size_t)Nb * 3));
+    }
+    // columns: the magnetization-vector store's; rows: the multi-component store's blocks (a single block too: the
+    // store has no other form)
+    c->mvi = true;
+    c->mc.n = ncomp;
+    for (int b = 0; b < ncomp; ++b) {
+        c->mc.comp[b] = comps[b];
+        c->mc.w[b] = weights[b];
+    }
+    c->cell_kind = GH_CELL_TESS_MVI_DATA;
+    c->comp = GH_COMP_GZ;
+    c->ratio = ratio;
+    c->have_cells = true;
+    return GH_OK;
+}
+
+
 static const char *const MVI_ONLY = "the amplitude term couples the three blocks of the magnetization-vector store (a "
-                                    "GH_CELL_PRISM_MVI or GH_CELL_PRISM_MVI_DATA context, gh_set_cells_mvi, "
-                                    "gh_set_cells_mvi_data)";
+                                    "GH_CELL_PRISM_MVI, GH_CELL_PRISM_MVI_DATA or GH_CELL_TESS_MVI_DATA context, "
+                                    "gh_set_cells_mvi, gh_set_cells_mvi_data, gh_set_cells_tess_mag)";
 
 // amp.sw = 1 / (Wm scale), 0 where Wm is 0: from the weights the store has NOW (gh_weight builds it again)
 static int amplitude_weights(gh_ctx *c, double scale)
@@ -633,9 +710,8 @@ static int dense_single_chain_refuse(gh_ctx *c, const char *who)
     if (c && c->joint)
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the joint gravity-magnetic kernel (dense, single chain)",
                     who);
-    if (c && c->mc.n > 0 && c->mvi)
-        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the vector-data magnetization store (dense, single chain)",
-                    who);
+    if (c && vector_data_store(c))
+        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on %s (dense, single chain)", who, vector_data_store_name(c));
     if (c && c->mc.n > 0)
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the multi-component store (dense, single chain)", who);
     if (c && c->mvi)
@@ -697,6 +773,9 @@ int gh_b_result(gh_ctx *c, int component, const double *mag3, double *result)
     if (!c->mvi)
         return fail(c, GH_ERR_ARG, "gh_b_result: the cells are not a magnetization-vector model (gh_set_cells_mvi, "
                                    "gh_set_cells_mvi_data)");
+    if (tess_mag_store(c))
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_b_result: the prisms' result pass does not run on the tesseroid "
+                                           "magnetization store: gh_tess_b_result");
     if (component < GH_BCOMP_BX || component > GH_BCOMP_BZ)
         return fail(c, GH_ERR_ARG, "gh_b_result: component %d is not GH_BCOMP_BX (1), GH_BCOMP_BY (2) or GH_BCOMP_BZ (3); the "
                                    "total field's result is gh_tf_result", component);
@@ -711,6 +790,77 @@ int gh_b_result(gh_ctx *c, int component, const double *mag3, double *result)
                            (const double *)c->obs[1], (const double *)c->obs[2], (const double *)c->bounds, dmag, n, cells,
                            dres);
     }, n);
+}
+
+// One pass of the tesseroid magnetization kernels over all (observation point, cell) pairs: the converted
+// observations (tess_convert_kernel with sin / cos of the longitude), the cells' frames (tess_mag_cellframe_kernel),
+// then `launch`; warn_cells, leaves and GH_ERR_OVERFLOW as tess_comp_assemble reports them.
+static int tess_mag_pass(gh_ctx *c, const char *who, const std::function<void(const TessMagObs &, const double *, int *, TessStats *)> &launch)
+{
+    const int64_t m = c->M / 3, Nb = c->N / c->mc.n;
+    double *buf = nullptr;
+    int *err_cell = nullptr;
+    TessStats *stats = nullptr;
+    auto release = [&]() {
+        hipFree(buf);
+        hipFree(err_cell);
+        hipFree(stats);
+    };
+    if (hipMalloc((void **)&buf, sizeof(double) * (size_t)(6 * Nb + TESS_MAG_FRAME * m)) != hipSuccess ||
+        hipMalloc((void **)&err_cell, sizeof(int) * (size_t)m) != hipSuccess ||
+        hipMalloc((void **)&stats, sizeof(TessStats)) != hipSuccess) {
+        (void)hipGetLastError();
+        release();
+        return fail(c, GH_ERR_NOMEM, "%s: device allocation of the tesseroid pass's buffers failed", who);
+    }
+    double *frame = buf + 6 * Nb;
+    const TessMagObs o{buf, buf + Nb, buf + 2 * Nb, buf + 3 * Nb, buf + 4 * Nb, buf + 5 * Nb};
+    std::vector<int> herr((size_t)m);
+    TessStats hs{};
+    hipError_t e = hipMemsetAsync(err_cell, 0, sizeof(int) * (size_t)m, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(stats, 0, sizeof(TessStats), c->stream);
+    if (e == hipSuccess) {
+        tess_convert_kernel<<<dim3((unsigned)((Nb + 255) / 256)), dim3(256), 0, c->stream>>>(
+            c->obs[0], c->obs[1], c->obs[2], Nb, buf, buf + Nb, buf + 2 * Nb, buf + 3 * Nb, buf + 4 * Nb, buf + 5 * Nb);
+        tess_mag_cellframe_kernel<<<dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream>>>(c->bounds, m, frame);
+        launch(o, frame, err_cell, stats);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(herr.data(), err_cell, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&hs, stats, sizeof hs, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    release();
+    HIPCHK(c, e);
+    c->warn_cells = 0;
+    for (int v : herr)
+        if (v != 0) c->warn_cells += 1;
+    c->leaves = (int64_t)hs.leaves;
+    if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
+    return GH_OK;
+}
+
+int gh_tess_b_result(gh_ctx *c, int component, const double *mag3, double *result)
+{
+    if (!c || !mag3 || !result) return fail(c, GH_ERR_ARG, "gh_tess_b_result: null pointer");
+    TRY(need(c, c->have_obs && c->have_cells, "gh_tess_b_result: call gh_set_cells_tess_mag and gh_set_obs first"));
+    if (!tess_mag_store(c))
+        return fail(c, GH_ERR_ARG, "gh_tess_b_result: the cells are not a tesseroid magnetization model "
+                                   "(gh_set_cells_tess_mag)");
+    if (component < GH_BCOMP_TF || component > GH_BCOMP_BZ)
+        return fail(c, GH_ERR_ARG, "gh_tess_b_result: component %d is not one of GH_BCOMP_TF (0) .. GH_BCOMP_BZ (3)",
+                    component);
+    if (component == GH_BCOMP_TF && !c->tmag_fdir)
+        return fail(c, GH_ERR_ARG, "gh_tess_b_result: the total field needs the directions gh_set_cells_tess_mag takes "
+                                   "as fdir");
+    const int64_t m = c->M / 3, Nb = c->N / c->mc.n;
+    int rc = GH_OK;
+    const int rr = run_result(c, "gh_tess_b_result", mag3, 3 * (size_t)m, result, [&](const double *dmag, double *dres) {
+        rc = tess_mag_pass(c, "gh_tess_b_result", [&](const TessMagObs &o, const double *frame, int *err_cell, TessStats *stats) {
+            tess_mag_result_kernel<<<dim3((unsigned)Nb), dim3(256), 0, c->stream>>>(
+                o, c->bounds, frame, c->tmag_fdir, dmag, Nb, m, c->ratio, component, dres, err_cell, stats);
+        });
+    }, Nb);
+    return rc != GH_OK ? rc : rr;
 }
 
 int gh_set_cells_prism(gh_ctx *c, const double *bounds6, int component)
@@ -984,6 +1134,17 @@ int gh_build_G(gh_ctx *c)
             make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), bc, c->G);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else if (tess_mag_store(c)) {
+        // every (data block, axis block) in one launch: one traversal of the subdivision per (point, cell) pair
+        const int64_t m = c->M / 3, Nb = c->N / c->mc.n, Lr = Nb + (c->ld - c->N);
+        BComps bc{};
+        bc.n = c->mc.n;
+        for (int b = 0; b < bc.n; ++b) bc.comp[b] = c->mc.comp[b];
+        TRY(tess_mag_pass(c, "gh_build_G", [&](const TessMagObs &o, const double *frame, int *err_cell, TessStats *stats) {
+            const int64_t blocks = std::min<int64_t>((Lr * m + 63) / 64, 1 << 24);
+            tess_mag_kernel<<<dim3((unsigned)blocks), dim3(64), 0, c->stream>>>(
+                o, c->bounds, frame, c->tmag_fdir, Nb, m, c->ld, c->ratio, bc, c->G, err_cell, stats);
+        }));
     } else if (c->cell_kind == GH_CELL_PRISM || c->cell_kind == GH_CELL_PRISM_TF || c->cell_kind == GH_CELL_PRISM_COMP) {
         TRY(prism_assemble(c, c->cell_kind == GH_CELL_PRISM_TF ? PRISM_TF : c->comp, c->N, c->ld, c->G));
         HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -64,6 +64,7 @@ struct gh_ctx {
     // GH_CELL_PRISM_MVI: A = [A_x | A_y | A_z] of the same M / 3 prisms at the same N points, an ordinary dense
     // N x M store whose model vectors are property-major (mx of every cell, then my, then mz)
     bool mvi = false;
+    double *tmag_fdir = nullptr;  // GH_CELL_TESS_MVI_DATA: the total field's unit vectors, 3 per observation point
     // ... and its amplitude coupling (gh_set_amplitude): lambda > 0 switches it on.  (Phi of the chain's state and
     // of the last evaluation are kept with the cross-gradient term's, cg.phi_cur / cg.phi_last: a context has
     // at most one of the two couplings.)
@@ -430,6 +431,16 @@ struct gh_ctx {
     std::vector<int64_t> ev_bytes;  // bytes of G the timed launch of event pair i read
     int64_t prof_bytes_last = 0;
 };
+
+// A magnetization vector per cell under row blocks of magnetic data: GH_CELL_PRISM_MVI_DATA and its tesseroid form
+// GH_CELL_TESS_MVI_DATA, which differ in the assembly alone (rows as the multi-component store, columns as the
+// magnetization-vector store)
+static inline bool vector_data_store(const gh_ctx *c) { return c->mvi && c->mc.n > 0; }
+static inline bool tess_mag_store(const gh_ctx *c) { return c->cell_kind == GH_CELL_TESS_MVI_DATA; }
+static inline const char *vector_data_store_name(const gh_ctx *c)
+{
+    return tess_mag_store(c) ? "the tesseroid magnetization store" : "the vector-data magnetization store";
+}
 
 static int fail(gh_ctx *c, int code, const char *fmt, ...)
 {

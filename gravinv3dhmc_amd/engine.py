@@ -220,6 +220,48 @@ class Engine(object):
         self._chk(self._lib.gh_b_result(self._h, comp, ptr(m), ptr(out)))
         return out
 
+    def set_cells_tess_mag(self, bounds6, ratio, components, weights, fdir=None):
+        """The M/3 tesseroids (bounds (M/3, 6): w, e, s, n, top, bottom) of a magnetization-vector model under magnetic
+        data (gh_set_cells_tess_mag): rows as set_cells_mvi_data, columns [K_N | K_E | K_D] for a unit magnetization
+        along north, east and down at each cell's centre.  fdir (N / len(components), 3): the unit vectors of the total
+        field at the observation points, needed by a "tf" block (or tess_b_result("tf")) alone.  Call it before
+        set_obs."""
+        b = f64(bounds6)
+        if self.M % 3 != 0 or b.shape != (self.M // 3, 6):
+            raise ValueError("bounds table of a magnetization-vector model must be (M/3, 6)")
+        comps = [_lib.BCOMPONENTS.get(c, -1) if isinstance(c, str) else int(c) for c in components]
+        if any(c not in _lib.BCOMPONENTS.values() for c in comps):
+            raise ValueError("data component must be one of %s" % ", ".join(_lib.BCOMPONENTS))
+        w = f64(weights)
+        if w.shape != (len(comps),):
+            raise ValueError("one data weight per component")
+        if fdir is None:
+            if _lib.BCOMP_TF in comps:
+                raise ValueError("a total-field block needs fdir, one unit vector per observation point")
+            fp = None
+        else:
+            fdir = f64(fdir)
+            if len(comps) == 0 or fdir.shape != (self.N // len(comps), 3):
+                raise ValueError("fdir must be (N / components, 3)")
+            fp = ptr(fdir)
+        self._chk(self._lib.gh_set_cells_tess_mag(self._h, ptr(b), float(ratio), len(comps),
+                                                  (C.c_int * max(len(comps), 1))(*comps), ptr(w), fp))
+        self.mvi = True
+        self.multi = len(comps)
+        self.tess_mag = True
+
+    def tess_b_result(self, component, mag3):
+        """tf, bx, by or bz (uT; component a name or BCOMP_* value) at the observation points of a tesseroid
+        magnetization context whose M/3 cells carry mag3[M/3, 3] = (m_N, m_E, m_D) in A/m, without a store
+        (gh_tess_b_result); kernel_stats() then reports this pass."""
+        comp = _lib.BCOMPONENTS.get(component, -1) if isinstance(component, str) else int(component)
+        m = f64(mag3)
+        if not getattr(self, "tess_mag", False) or m.shape != (self.M // 3, 3):
+            raise ValueError("magnetization must be (M/3, 3) on a tesseroid magnetization context")
+        out = np.empty(self.N // self.multi)
+        self._chk(self._lib.gh_tess_b_result(self._h, comp, ptr(m), ptr(out)))
+        return out
+
     def set_amplitude(self, lam, beta, scale=1.0):
         """Amplitude coupling lam * sum_c s_c / (s_c + beta) of a weighted magnetization-vector context
         (gh_set_amplitude), s_c the squared amplitude of cell c's physical vector over scale.  lam = 0 switches the

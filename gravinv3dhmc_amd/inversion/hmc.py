@@ -378,6 +378,9 @@ def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
     if getattr(model._engine, "joint", False):
         raise NotImplementedError("HMCSampleBatch does not run the joint gravity-magnetic kernel (JointModule): "
                                   "sample its chains one at a time with HMCSample")
+    if getattr(model._engine, "tess_mag", False):
+        raise NotImplementedError("HMCSampleBatch does not run the tesseroid magnetization store "
+                                  "(TesseroidMagVectorModule): sample its chains one at a time with HMCSample")
     if getattr(model._engine, "multi", 0) and getattr(model._engine, "mvi", False):
         raise NotImplementedError("HMCSampleBatch does not run the vector-data magnetization store (MagVectorModule with "
                                   "data=): sample its chains one at a time with HMCSample")

@@ -31,6 +31,7 @@ from .potential import _diag, _Potential
 
 _STORE = "the magnetization-vector store"
 _VSTORE = "the vector-data magnetization store"
+_TSTORE = "the tesseroid magnetization store"
 
 
 class MagVectorModule(_Potential):
@@ -62,6 +63,7 @@ class MagVectorModule(_Potential):
     rows len(data) x N under vector data -- (the store runs on the fused sweep).  Smoothness and TV need the full mesh (ValueError on a carved one).
     """
     _props = 3  # (mx, my and mz of the same mesh)
+    _spherical = False  # (TesseroidMagVectorModule: tesseroids, always the store of row blocks)
 
     def __init__(self, dobs, mrange, mspacing, obsurface, mangle=(90, 0), mratio=1, mseg=False, mdivisionsection=[],
                  weightfactor=0.5, amplitude=0.0, amplitude_beta=0.01, device=0, verbose=True, coordinate="cartesian",
@@ -81,8 +83,8 @@ class MagVectorModule(_Potential):
             raise ValueError("data components must be distinct, got %r" % (data,))
         n = int(np.asarray(obsurface[0]).size)
         # the default is the module as it always was: one block of the total field, one mean, no block table
-        self._vector = not (data == ("tf",) and weights is None)
-        store = _VSTORE if self._vector else _STORE
+        self._vector = self._spherical or not (data == ("tf",) and weights is None)
+        store = _TSTORE if self._spherical else _VSTORE if self._vector else _STORE
         if self._vector:
             if isinstance(dobs, dict):
                 if set(dobs) != set(data):
@@ -107,10 +109,10 @@ class MagVectorModule(_Potential):
                 w = np.asarray(weights, dtype=np.float64).ravel()
                 if w.size != len(data) or not np.all(np.isfinite(w)) or not np.all(w > 0):
                     raise ValueError("weights must be None, 'std' or one positive number per data component")
-        if coordinate == "spherical":
+        if coordinate == "spherical" and not self._spherical:
             raise NotImplementedError("%s holds prism fields: tesseroids (coordinate='spherical') are not supported"
                                       % store)
-        if coordinate != "cartesian":
+        if coordinate != ("spherical" if self._spherical else "cartesian"):
             raise ValueError("Please choose coordinate from(cartesian, spherical)!")
         if wavelet not in (False, None):
             raise NotImplementedError("wavelet compression of %s is not supported" % store)
@@ -149,9 +151,8 @@ class MagVectorModule(_Potential):
         self.wavelet = False
         self.device = device
 
-        self._say("Calculating magnetic field (magnetization vector) in cartesian coordinate.")
-        mesh = (mesher.PrismMeshSegment(mrange, mspacing, mdivisionsection) if mseg
-                else mesher.PrismMesh(mrange, mspacing, mratio))
+        self._say("Calculating magnetic field (magnetization vector) in %s coordinate." % coordinate)
+        mesh = self._make_mesh()
         if "mtopo" in kwargs:
             value = kwargs["mtopo"]
             self.topocarve = True
@@ -165,12 +166,12 @@ class MagVectorModule(_Potential):
         start = time.time()
         if self._vector:
             eng = Engine(len(data) * n, 3 * self._cells, device=device)
-            eng.set_cells_mvi_data(bounds, utils.dircos(self.inc, self.dec) if "tf" in data else None, data, w)
+            self._set_cells(eng, bounds, data, w)
         else:
             eng = Engine(n, 3 * self._cells, device=device)
             eng.set_cells_mvi(bounds, utils.dircos(self.inc, self.dec))
         eng.set_obs(self.lonobs, self.latobs, self.heightobs)
-        eng.build_G()
+        self._build(eng)
         self._say("kernel.shape", (eng.N, 3 * self._cells))
         self._say("End of calculate kernel:%.6f s" % (time.time() - start))
         self._engine = eng
@@ -190,6 +191,17 @@ class MagVectorModule(_Potential):
         self._amp_beta = float(amplitude_beta)
         if amplitude != 0:
             self.set_amplitude(amplitude, amplitude_beta)
+
+    # ------------------------------------------------------------------ the mesh and the assembly (the geometry's part)
+    def _make_mesh(self):
+        return (mesher.PrismMeshSegment(self.mrange, self.mspacing, self.mdivisionsection) if self.mseg
+                else mesher.PrismMesh(self.mrange, self.mspacing, self.mratio))
+
+    def _set_cells(self, eng, bounds, data, w):
+        eng.set_cells_mvi_data(bounds, utils.dircos(self.inc, self.dec) if "tf" in data else None, data, w)
+
+    def _build(self, eng):
+        eng.build_G()
 
     # ------------------------------------------------------------------ weighting
     def sensitivityWeighting(self):
@@ -306,3 +318,56 @@ class MagVectorModule(_Potential):
     def last_amplitude(self):
         """Phi of the last misfit_and_grad, or of the state the chain is in; 0 while the coupling is off."""
         return self._engine.amplitude_last()
+
+
+class TesseroidMagVectorModule(MagVectorModule):
+    """The magnetization vector of every tesseroid under magnetic data, on one MI355X: MagVectorModule(data=...) on a
+    spherical mesh (libgravhmc's GH_CELL_TESS_MVI_DATA), for satellite and global surveys.
+
+    obsurface = (lon, lat, height) in degrees and metres; mrange = (west, east, south, north, top, bottom), mspacing =
+    (dr, dlat, dlon), mratio, mseg, mdivisionsection as the spherical GravMagModule (TesseroidMesh /
+    TesseroidMeshSegment); mtopo carves the mesh.  Every cell has the unknowns (m_N, m_E, m_D) in A/m in the
+    north-east-down frame at its centre; model vectors are property-major.  data: distinct components of "tf", "bx",
+    "by", "bz" -- north, east and down at each observation -- with dobs a sequence (or dict) of len(data) arrays;
+    weights None, "std" or numbers; mangle = (inclination, declination) in degrees of the regional field AT THE
+    OBSERVATIONS, scalars or one value per observation point, needed by a "tf" block alone.  ratio: the
+    subdivision's distance-size ratio (None: RATIO_GG = 8).
+
+    HMCSample, misfit_and_grad, forward, kernel(axis, component) with axis 0 / 1 / 2 ("x" north, "y" east, "z" down AT
+    THE CELL), block_means(), Amplitude / amplitude / direction, to_vectors / from_vectors work as on MagVectorModule:
+    the rows are row blocks with a data weight and a mean each, always (a single tf block too).  Not supported
+    (NotImplementedError naming the tesseroid magnetization store): wavelet compression, the matrix-free mode, the
+    shift-invariant store, shards, HMCSampleBatch and more than 16384 stacked rows."""
+    _spherical = True
+
+    def __init__(self, dobs, mrange, mspacing, obsurface, data=("bx", "by", "bz"), weights=None, mangle=(90, 0),
+                 amplitude=0.0, amplitude_beta=0.01, mratio=1, mseg=False, mdivisionsection=[], weightfactor=0.5,
+                 device=0, verbose=True, wavelet=False, matrix_free=False, shift_invariant=False, shard=None,
+                 ratio=None, **kwargs):
+        from ..gravmag import tesseroid
+        self._ratio = tesseroid.RATIO_GG if ratio is None else ratio
+        if not (self._ratio > 0):
+            raise ValueError("Invalid ratio {}. Must be > 0.".format(ratio))
+        data = (data,) if isinstance(data, str) else tuple(data)
+        self._fdir = None
+        if "tf" in data:
+            self._fdir = tesseroid._field_directions(mangle[0], mangle[1], int(np.asarray(obsurface[0]).size))
+        super().__init__(dobs, mrange, mspacing, obsurface, mangle=mangle, mratio=mratio, mseg=mseg,
+                         mdivisionsection=mdivisionsection, weightfactor=weightfactor, amplitude=amplitude,
+                         amplitude_beta=amplitude_beta, device=device, verbose=verbose, coordinate="spherical",
+                         wavelet=wavelet, matrix_free=matrix_free, shift_invariant=shift_invariant, shard=shard,
+                         data=data, weights=weights, **kwargs)
+
+    def _make_mesh(self):
+        return (mesher.TesseroidMeshSegment(self.mrange, self.mspacing, self.mdivisionsection) if self.mseg
+                else mesher.TesseroidMesh(self.mrange, self.mspacing, self.mratio))
+
+    def _set_cells(self, eng, bounds, data, w):
+        eng.set_cells_tess_mag(bounds, self._ratio, data, w, self._fdir)
+
+    def _build(self, eng):
+        eng.build_G()
+        if eng.kernel_stats()["warn_cells"] > 0:
+            import warnings
+            from ..gravmag.tesseroid import _WARN_DIVIDE
+            warnings.warn(_WARN_DIVIDE, RuntimeWarning)

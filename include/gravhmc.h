@@ -87,9 +87,12 @@ typedef enum {
  * GH_CELL_PRISM_MULTI: prisms, several gravity fields of one density model inverted together (gh_set_cells_multi);
  * GH_CELL_PRISM_MVI: prisms, the total field of a magnetization VECTOR per cell (gh_set_cells_mvi);
  * GH_CELL_PRISM_MVI_DATA: prisms, a magnetization vector per cell under VECTOR data -- row blocks of tf, bx, by, bz
- * (gh_set_cells_mvi_data) */
+ * (gh_set_cells_mvi_data);
+ * GH_CELL_TESS_MVI_DATA: tesseroids, a magnetization vector per cell (north, east, down at the cell's centre) under
+ * row blocks of tf, bx, by, bz in the observations' local frames (gh_set_cells_tess_mag) */
 enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2, GH_CELL_PRISM_COMP = 3, GH_CELL_TESSEROID_COMP = 4,
        GH_CELL_PRISM_JOINT = 5, GH_CELL_PRISM_MULTI = 6, GH_CELL_PRISM_MVI = 7, GH_CELL_PRISM_MVI_DATA = 8 };
+enum { GH_CELL_TESS_MVI_DATA = 9 };
 /* The magnetic data components of prisms, for gh_set_cells_mvi_data and gh_b_result: the total-field anomaly along
  * the regional field, and the north, east and down components of the anomalous induction (gravmag/prism.py:665-870),
  * all in uT per A/m (CM * T2NT) */
@@ -203,6 +206,42 @@ int gh_set_cells_mvi_data(gh_ctx *ctx, const double *bounds6 /* M/3 x 6 */, doub
  * in uT, accumulated corner by corner, cell by cell in mesh order into one sum per observation and scaled once, as
  * the reference does (prism.py:735-870). */
 int gh_b_result(gh_ctx *ctx, int component, const double *mag3 /* M/3 x 3 */, double *result);
+/* The magnetic fields of TESSEROIDS (GH_CELL_TESS_MVI_DATA): the spherical form of gh_set_cells_mvi_data.  Frames: at
+ * longitude lam and latitude phi the ECEF unit vectors are n = (-sin phi cos lam, -sin phi sin lam, cos phi) (north),
+ * e = (-sin lam, cos lam, 0) (east), u = (cos phi cos lam, cos phi sin lam, sin phi) (up).  Cell c carries the
+ * magnetization m_c = (m_N, m_E, m_D) in A/m in the north-east-down frame at its CENTRE (the midpoints of its lon / lat
+ * bounds), uniform over the cell in the Cartesian sense (sub-tesseroids of the subdivision keep the vector and the
+ * frame).  With V_ab(o, c) the unscaled second-derivative sums of the gradient tensor (gh_set_cells_tess with
+ * GH_COMP_GXX .. GH_COMP_GZZ, before their scale; observation frame x north, y east, z up; the same subdivision rule,
+ * stack and error codes at `ratio`) and Q(o, c) = [n_o e_o u_o]^T [n_c e_c -u_c],
+ *     (B_x, B_y, B_zup) = CM T2NT V(o, c) Q(o, c) m_c,    bx = B_x (north), by = B_y (east), bz = -B_zup (down)
+ * in uT, at the observation; tf = f_o . (bx, by, bz) with the unit vector f_o = fdir[3 o ..] given PER OBSERVATION
+ * point (a global survey has no single regional direction).  The store is [K_N | K_E | K_D]:
+ *     rows [b N/ncomp, (b + 1) N/ncomp), column a M/3 + c:  component comps[b] at the block's points of tesseroid c
+ *     magnetized 1 A/m along its axis a (north, east, down).
+ * bounds6: M/3 x 6 (w, e, s, n in degrees, top, bottom in m; w <= e, s <= n, top >= bottom, else GH_ERR_ARG); ratio > 0
+ * (the reference's RATIO_GG = 8 for second derivatives); fdir: N/ncomp x 3, needed only with a GH_BCOMP_TF block, else
+ * it may be NULL.  Call it on a fresh context, BEFORE gh_set_obs, which then takes the N / ncomp points (lon, lat in
+ * degrees, height in m).  gh_build_G assembles every block in ONE launch that walks the adaptive subdivision once per
+ * (point, cell) pair and accumulates the six sums at every leaf; gh_kernel_stats reports its warn_cells and leaves,
+ * a full stack is GH_ERR_OVERFLOW.
+ * In everything but the assembly the context is a GH_CELL_PRISM_MVI_DATA one, always with its block table (a single
+ * unweighted tf block too): gh_weight with block weights, gh_set_data with per-block means, forward / adjoint,
+ * gh_misfit_and_grad, gh_leapfrog and gh_chain_* on the fused sweep, gh_set_amplitude, gh_multi_info, Smoothness / TV
+ * per component on shape3 with product M/3, the posterior window and stream.
+ * Dense, single chain only: matrix-free, the shift-invariant store, the wavelet compressor, gh_batch_*,
+ * gh_shard_init*, gh_upload_G and a stacked N > 16384 return GH_ERR_UNSUPPORTED naming the tesseroid magnetization
+ * store; the resident chain kernel and the folded store are never chosen.
+ * Errors: GH_ERR_ARG for ncomp outside 1..GH_BCOMP_MAX, an unknown or repeated component, a weight that is not
+ * finite and > 0, M not a multiple of 3, N not a multiple of ncomp, a tf block without fdir, a context that is not
+ * fresh. */
+int gh_set_cells_tess_mag(gh_ctx *ctx, const double *bounds6 /* M/3 x 6 */, double ratio, int ncomp, const int *comps,
+                          const double *weights, const double *fdir /* N/ncomp x 3, or NULL */);
+/* The field of a GH_CELL_TESS_MVI_DATA context without a store (needs gh_set_obs and the cells, not G): component is a
+ * GH_BCOMP_* value (GH_BCOMP_TF needs the context's fdir), mag3 the vector (m_N, m_E, m_D) in A/m of each of the M/3
+ * tesseroids, row-major; result (one value per observation POINT: N / ncomp) in uT.  One workgroup per point sums the
+ * cells' fields in a fixed order and scales once.  gh_kernel_stats then reports this pass's warn_cells and leaves. */
+int gh_tess_b_result(gh_ctx *ctx, int component, const double *mag3 /* M/3 x 3 */, double *result);
 /* Amplitude coupling of a weighted GH_CELL_PRISM_MVI context: the minimum-support functional of the cells'
  * amplitude, the one term that ties the three components of a cell together (compact bodies).  With
  *     u_a[c] = mw[a M/3 + c] winv[a M/3 + c] / scale   (winv = 1 / Wm, 0 where Wm is 0),   s_c = sum_a u_a[c]^2,
