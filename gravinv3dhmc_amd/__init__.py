@@ -10,7 +10,7 @@ from .engine import DeviceMatrix, Engine  # noqa: F401
 from .gravmag import prism, tesseroid  # noqa: F401
 from .inversion import (BootStrap, ConjugateGradient, GravMagModule, HamitonianMC, HMCSample,  # noqa: F401
                         HMCSampleBatch, JointModule, MagVectorModule, MultiComponentModule,
-                        TesseroidMagVectorModule)
+                        TesseroidMagVectorModule, TesseroidMultiComponentModule)
 
 __all__ = ["constants", "mesher", "prism", "tesseroid", "Engine", "DeviceMatrix",
-           "GravMagModule", "JointModule", "MagVectorModule", "MultiComponentModule", "TesseroidMagVectorModule", "HamitonianMC", "HMCSample", "HMCSampleBatch", "ConjugateGradient", "BootStrap"]
+           "GravMagModule", "JointModule", "MagVectorModule", "MultiComponentModule", "TesseroidMagVectorModule", "TesseroidMultiComponentModule", "HamitonianMC", "HMCSample", "HMCSampleBatch", "ConjugateGradient", "BootStrap"]

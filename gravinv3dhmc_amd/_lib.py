@@ -19,6 +19,7 @@ CELL_PRISM_MULTI = 6
 CELL_PRISM_MVI = 7
 CELL_PRISM_MVI_DATA = 8
 CELL_TESS_MVI_DATA = 9
+CELL_TESSEROID_MULTI = 10
 #: the magnetic data components of prisms (GH_BCOMP_*, gh_set_cells_mvi_data / gh_b_result)
 BCOMP_TF, BCOMP_BX, BCOMP_BY, BCOMP_BZ = range(4)
 BCOMPONENTS = {"tf": BCOMP_TF, "bx": BCOMP_BX, "by": BCOMP_BY, "bz": BCOMP_BZ}
@@ -57,6 +58,7 @@ PROTOTYPES = {
     "gh_amplitude_eval": (C.c_int, [_ctx, _dp, C.POINTER(C.c_double), _dp, _dp]),
     "gh_amplitude_last": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
     "gh_set_cells_multi": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp]),
+    "gh_set_cells_tess_multi": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
     "gh_multi_info": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp, _dp]),
     "gh_joint_std": (C.c_int, [_ctx, _dp]),
     "gh_joint_layout": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

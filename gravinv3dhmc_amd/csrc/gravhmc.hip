@@ -195,6 +195,8 @@ static int set_cells(gh_ctx *c, const double *bounds6, int kind, int comp, doubl
     if (vector_data_store(c))
         return fail(c, GH_ERR_UNSUPPORTED, "a vector-data magnetization context takes its cells from %s",
                     tess_mag_store(c) ? "gh_set_cells_tess_mag" : "gh_set_cells_mvi_data");
+    if (tess_multi_store(c))
+        return fail(c, GH_ERR_UNSUPPORTED, "a tesseroid multi-component context takes its cells from gh_set_cells_tess_multi");
     if (c->mc.n > 0) return fail(c, GH_ERR_UNSUPPORTED, "a multi-component context takes its cells from gh_set_cells_multi");
     if (c->mvi) return fail(c, GH_ERR_UNSUPPORTED, "a magnetization-vector context takes its cells from gh_set_cells_mvi");
     HIPCHK(c, hipSetDevice(c->device));
@@ -552,12 +554,67 @@ int gh_set_cells_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *c
     return GH_OK;
 }
 
+int gh_set_cells_tess_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *ratios,
+                            const double *weights)
+{
+    if (!c || !bounds6 || !comps || !ratios || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: null pointer");
+    if (ncomp < 1 || ncomp > GH_MULTI_MAX)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: %d components: the tesseroid multi-component store takes 1 to %d",
+                    ncomp, GH_MULTI_MAX);
+    for (int b = 0; b < ncomp; ++b) {
+        if (comps[b] < GH_COMP_POTENTIAL || comps[b] > GH_COMP_GZZ)
+            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: component %d is not one of GH_COMP_POTENTIAL (0) .. GH_COMP_GZZ "
+                                       "(10)", comps[b]);
+        for (int a = 0; a < b; ++a)
+            if (comps[a] == comps[b])
+                return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: component %d is listed twice", comps[b]);
+        if (!(weights[b] > 0.0) || !std::isfinite(weights[b]))
+            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: the data weights must be finite and > 0");
+        if (!(ratios[b] > 0)) return fail(c, GH_ERR_ARG, "Invalid ratio %g. Must be > 0.", ratios[b]);
+    }
+    if (c->N % ncomp != 0)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: N = %lld is not %d blocks of the same observation points",
+                    (long long)c->N, ncomp);
+    // w <= e, s <= n, top >= bottom: the reference's assertion (tesseroid.py:137-138)
+    for (int64_t j = 0; j < c->M; ++j) {
+        const double *b = bounds6 + 6 * j;
+        if (!(b[0] <= b[1] && b[2] <= b[3] && b[4] >= b[5]))
+            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: invalid tesseroid dimensions (cell %lld: %g %g %g %g %g %g)",
+                        (long long)j, b[0], b[1], b[2], b[3], b[4], b[5]);
+    }
+    if (c->joint || c->mvi || c->mc.n > 0 || c->have_obs || c->have_cells || c->have_G || c->slab)
+        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: call it first on a fresh context (before gh_set_obs)");
+    // (the shift-invariant store may have been asked for already: it is the one form besides the dense store)
+    if (c->mf && !c->ls)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_multi: the tesseroid multi-component store has no matrix-free "
+                                           "mode (dense, or the shift-invariant store)");
+    if (c->sh.kind != 0)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_multi: the tesseroid multi-component store is not sharded");
+    // gz alone, unweighted: one block with one mean -- the tesseroid store itself (kind 1), on either form
+    if (ncomp == 1 && comps[0] == GH_COMP_GZ && weights[0] == 1.0) return gh_set_cells(c, bounds6, GH_CELL_TESSEROID, ratios[0]);
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
+    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
+    c->mc.n = ncomp;
+    for (int b = 0; b < ncomp; ++b) {
+        c->mc.comp[b] = comps[b];
+        c->mc.ratio[b] = ratios[b];
+        c->mc.w[b] = weights[b];
+    }
+    c->cell_kind = GH_CELL_TESSEROID_MULTI;
+    c->comp = comps[0];
+    c->ratio = ratios[0];
+    c->have_cells = true;
+    return GH_OK;
+}
+
 int gh_multi_info(gh_ctx *c, int *ncomp, int *comps, double *weights, double *pred_mean, double *obs_mean)
 {
     if (!c) return GH_ERR_ARG;
     if (c->mc.n == 0)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_multi_info: not a context of row blocks (gh_set_cells_multi, "
-                                           "gh_set_cells_mvi_data with more than the unweighted total field)");
+                                           "gh_set_cells_tess_multi, gh_set_cells_mvi_data with more than the unweighted "
+                                           "total field)");
     if (ncomp) *ncomp = c->mc.n;
     for (int b = 0; b < c->mc.n; ++b) {
         if (comps) comps[b] = c->mc.comp[b];
@@ -703,10 +760,14 @@ static int d2h_obsvec(gh_ctx *c, double *dst, const double *src)
     return GH_OK;
 }
 
-// The stores that are dense and run one chain -- the joint gravity-magnetic store, the multi-component store and the
-// magnetization-vector store -- refuse `who`, each naming itself.
+// The stores that are dense and run one chain -- the joint gravity-magnetic store, the multi-component stores and the
+// magnetization-vector store -- refuse `who`, each naming itself.  (The tesseroid multi-component store also runs on
+// the shift-invariant table: still one chain, no other form.)
 static int dense_single_chain_refuse(gh_ctx *c, const char *who)
 {
+    if (c && tess_multi_store(c))
+        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the tesseroid multi-component store (dense or "
+                                           "shift-invariant, single chain)", who);
     if (c && c->joint)
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the joint gravity-magnetic kernel (dense, single chain)",
                     who);
@@ -926,7 +987,8 @@ int gh_set_matrix_free(gh_ctx *c, int enable)
 int gh_set_shift_invariant(gh_ctx *c, int enable)
 {
     if (!c) return GH_ERR_ARG;
-    if (enable) TRY(dense_single_chain_refuse(c, "gh_set_shift_invariant"));
+    // (the tesseroid multi-component store is the one store of row blocks that has the table)
+    if (enable && !(c && tess_multi_store(c))) TRY(dense_single_chain_refuse(c, "gh_set_shift_invariant"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_shift_invariant: call before gh_build_G");
     // (the store is a flavour of the matrix-free mode -- G is never stored -- so enabling it sets c->mf;
     // disabling it puts c->mf back to what gh_set_matrix_free last asked for)
@@ -985,13 +1047,14 @@ int gh_set_matrix_free_exact(gh_ctx *c, int exact)
     return GH_OK;
 }
 
-// tess_comp_kernel of the context's component over all (observation, cell) pairs: G (ld x M) when G is given,
-// else the statistics alone; warn_cells, leaves, and GH_ERR_OVERFLOW.  conv: the converted observations (lon
-// rad, sin lat, cos lat, radius; N each).
-static int tess_comp_assemble(gh_ctx *c, const double *conv, double *G)
+// tess_comp_kernel of one field at one ratio over all (observation, cell) pairs: `rows` rows of every column of the
+// store from G on (the N observations' entries, then zeros) when G is given, else the statistics alone; warn_cells
+// and leaves are added to the context's counts (gh_build_G zeroes them), GH_ERR_OVERFLOW.  conv: the converted
+// observations (lon rad, sin lat, cos lat, radius; N each).
+static int tess_comp_assemble(gh_ctx *c, const double *conv, double *G, int comp, double ratio, int64_t N, int64_t rows)
 {
     typedef void (*tc_fn)(const double *, const double *, const double *, const double *, const double *, int64_t,
-                          int64_t, int64_t, double, int, double *, int *, TessStats *);
+                          int64_t, int64_t, int64_t, double, int, double *, int *, TessStats *);
     // (indexed by GH_COMP_*: one instantiation per leaf, the geoid runs the potential's)
     static const tc_fn fns[] = {tess_comp_kernel<GH_COMP_POTENTIAL>, tess_comp_kernel<GH_COMP_POTENTIAL>,
                                 tess_comp_kernel<GH_COMP_GX>,        tess_comp_kernel<GH_COMP_GY>,
@@ -1007,15 +1070,14 @@ static int tess_comp_assemble(gh_ctx *c, const double *conv, double *G)
         hipFree(err_cell);
         return fail(c, GH_ERR_NOMEM, "gh_build_G: device allocation of the tesseroid statistics failed");
     }
-    const int64_t N = c->N;
     std::vector<int> herr((size_t)c->M);
     TessStats hs{};
     hipError_t e = hipMemsetAsync(err_cell, 0, sizeof(int) * (size_t)c->M, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(stats, 0, sizeof(TessStats), c->stream);
     if (e == hipSuccess) {
-        const int64_t blocks = std::min<int64_t>((c->ld * c->M + 63) / 64, 1 << 24);
-        hipLaunchKernelGGL(fns[c->comp], dim3((unsigned)blocks), dim3(64), 0, c->stream, conv, conv + N, conv + 2 * N,
-                           conv + 3 * N, (const double *)c->bounds, N, c->M, c->ld, c->ratio, c->comp, G, err_cell,
+        const int64_t blocks = std::min<int64_t>((rows * c->M + 63) / 64, 1 << 24);
+        hipLaunchKernelGGL(fns[comp], dim3((unsigned)blocks), dim3(64), 0, c->stream, conv, conv + N, conv + 2 * N,
+                           conv + 3 * N, (const double *)c->bounds, N, c->M, rows, c->ld, ratio, comp, G, err_cell,
                            stats);
         e = hipGetLastError();
     }
@@ -1028,7 +1090,7 @@ static int tess_comp_assemble(gh_ctx *c, const double *conv, double *G)
     HIPCHK(c, e);
     for (int v : herr)
         if (v != 0) c->warn_cells += 1;
-    c->leaves = (int64_t)hs.leaves;
+    c->leaves += (int64_t)hs.leaves;
     if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
     return GH_OK;
 }
@@ -1063,6 +1125,9 @@ int gh_build_G(gh_ctx *c)
     c->leaves = 0;
     if (c->mf) {
         if (c->slab) return fail(c, GH_ERR_ARG, "gh_build_G: a matrix-free context is built once");
+        if (tess_multi_store(c) && !c->ls)
+            return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: the tesseroid multi-component store has no matrix-free mode "
+                                               "(dense, or the shift-invariant store)");
         c->mf_fused = c->ld <= 16384 && env_int("GRAVHMC_MF_FUSED", 1) != 0;
         // (tesseroid components: the two-pass form, with the entry evaluated inside each pass -- no fused KIND;
         // the near-field table and the cell-constant fast leaf are gz's)
@@ -1089,7 +1154,7 @@ int gh_build_G(gh_ctx *c)
         if (c->ls) TRY(lonsym_build(c));
         // (tesseroid components: the error codes, leaves and overflow of the subdivision, as the dense build
         // reports them, from one pass that stores nothing)
-        if (c->cell_kind == GH_CELL_TESSEROID_COMP) TRY(tess_comp_assemble(c, c->tconv, nullptr));
+        if (c->cell_kind == GH_CELL_TESSEROID_COMP) TRY(tess_comp_assemble(c, c->tconv, nullptr, c->comp, c->ratio, c->N, c->ld));
         TRY(configure_mf(c));
         TRY(dalloc(c, &c->mf_stats, 1));
         c->have_G = true;
@@ -1098,6 +1163,12 @@ int gh_build_G(gh_ctx *c)
         c->bt.ready = false;
         return GH_OK;
     }
+    if (tess_multi_store(c) && c->N > 16384)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %d components x %lld observations = %lld rows: the dense form of "
+                                           "the tesseroid multi-component store takes at most 16384 (it runs on the fused "
+                                           "sweep: no row panels, no team sweep); the shift-invariant store has no such "
+                                           "limit (gh_set_shift_invariant)", c->mc.n, (long long)(c->N / c->mc.n),
+                    (long long)c->N);
     if (!c->dense_ok)
         return fail(c, GH_ERR_UNSUPPORTED,
                     "N = %lld: more than 16384 observations per device: shard the observations or use "
@@ -1161,7 +1232,21 @@ int gh_build_G(gh_ctx *c)
         const int64_t N = c->N;
         tess_convert_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream>>>(
             c->obs[0], c->obs[1], c->obs[2], N, conv, conv + N, conv + 2 * N, conv + 3 * N);
-        const int rc = tess_comp_assemble(c, conv, c->G);
+        const int rc = tess_comp_assemble(c, conv, c->G, c->comp, c->ratio, c->N, c->ld);
+        hipFree(conv);
+        TRY(rc);
+    } else if (tess_multi_store(c)) {
+        // the field's assembly once per block into its row block of the one store, at the block's ratio; the last
+        // block's launch also zeroes the padding rows below it; error cells and leaves summed over the blocks
+        const int64_t Nb = c->N / c->mc.n;
+        double *conv = nullptr;
+        HIPCHK(c, hipMalloc((void **)&conv, sizeof(double) * 4 * (size_t)Nb));
+        tess_convert_kernel<<<dim3((unsigned)((Nb + 255) / 256)), dim3(256), 0, c->stream>>>(
+            c->obs[0], c->obs[1], c->obs[2], Nb, conv, conv + Nb, conv + 2 * Nb, conv + 3 * Nb);
+        int rc = GH_OK;
+        for (int b = 0; b < c->mc.n && rc == GH_OK; ++b)
+            rc = tess_comp_assemble(c, conv, c->G + b * Nb, c->mc.comp[b], c->mc.ratio[b], Nb,
+                                    b + 1 < c->mc.n ? Nb : c->ld - b * Nb);
         hipFree(conv);
         TRY(rc);
     } else {
@@ -1280,7 +1365,8 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
             rb.w[b] = c->mc.w[b];
             unit = unit && rb.w[b] == 1.0;
         }
-        if (!unit) {
+        // (the shift-invariant table took the weights when it was built: there is no G)
+        if (!unit && !c->mf) {
             const unsigned blocks = (unsigned)std::min<int64_t>((c->ld * c->M + 255) / 256, 1 << 20);
             scale_rowblocks_kernel<<<dim3(blocks), dim3(256), 0, c->stream>>>(c->G, c->ld, c->M, rb);
             HIPCHK(c, hipGetLastError());
@@ -1385,7 +1471,9 @@ int gh_set_data(gh_ctx *c, const double *dobs, const double *grav_fix)
     };
     if (c->mc.n > 0) {
         // Wb dobs in row blocks: every component loses its own mean
-        if (grav_fix) return fail(c, GH_ERR_ARG, "gh_set_data: the multi-component store takes no grav_fix");
+        if (grav_fix)
+            return fail(c, GH_ERR_ARG, "gh_set_data: %s takes no grav_fix",
+                        tess_multi_store(c) ? "the tesseroid multi-component store" : "the multi-component store");
         const size_t Nb = N / (size_t)c->mc.n;
         for (int b = 0; b < c->mc.n; ++b) {
             double *tb = t.data() + (size_t)b * Nb;

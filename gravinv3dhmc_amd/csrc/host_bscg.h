@@ -8,7 +8,9 @@ static const char *const BSCG_WHO = "the bootstrap batch (gh_bscg_run)";
 static int bscg_refuse(gh_ctx *c, int B, int maxk)
 {
     const char *what = nullptr;
-    if (c->ls)
+    if (tess_multi_store(c))
+        what = "the tesseroid multi-component store";
+    else if (c->ls)
         what = "a shift-invariant store";
     else if (c->mf)
         what = "a matrix-free context";

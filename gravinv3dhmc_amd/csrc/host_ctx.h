@@ -57,6 +57,7 @@ struct gh_ctx {
         int n = 0;  // 0: not a multi-component context
         int comp[GH_MULTI_MAX] = {};
         double w[GH_MULTI_MAX] = {};
+        double ratio[GH_MULTI_MAX] = {};     // GH_CELL_TESSEROID_MULTI: the distance-size ratio of each block's field
         double obs_mean[GH_MULTI_MAX] = {};  // the mean gh_set_data removed from each block of Wb dobs
         double *bsum = nullptr;              // n x (slab rows): sums of the slab rows per block (slab_block_sums_kernel)
         double *bmean = nullptr;             // n: the blocks' means of the last evaluation's prediction
@@ -437,6 +438,9 @@ struct gh_ctx {
 // magnetization-vector store)
 static inline bool vector_data_store(const gh_ctx *c) { return c->mvi && c->mc.n > 0; }
 static inline bool tess_mag_store(const gh_ctx *c) { return c->cell_kind == GH_CELL_TESS_MVI_DATA; }
+// The tesseroid multi-component store (GH_CELL_TESSEROID_MULTI): the multi-component store's row blocks, assembled by
+// the tesseroid field kernels; dense, or the shift-invariant table with the block as one more coordinate of the class
+static inline bool tess_multi_store(const gh_ctx *c) { return c->cell_kind == GH_CELL_TESSEROID_MULTI && c->mc.n > 0; }
 static inline const char *vector_data_store_name(const gh_ctx *c)
 {
     return tess_mag_store(c) ? "the tesseroid magnetization store" : "the vector-data magnetization store";

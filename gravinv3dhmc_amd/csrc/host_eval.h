@@ -340,8 +340,14 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
             fa.bmean = c->mc.bmean;
             fa.dsum = c->mc.bsum;
             fa.n_dsum = fa.n_rows_slab;
-            slab_block_sums_kernel<<<dim3((unsigned)fa.n_rows_slab), dim3(256), 0, c->stream>>>(c->slab, c->ld, fa.Nb, fa.nblk,
-                                                                                                c->mc.bsum);
+            if (lonsym_one_row(c)) {
+                // (the shift-invariant table: the pass delivered the sum of every class, block after block -- the
+                // classes of block b are its n_dsum partials, summed in index order)
+                fa.n_dsum = lonsym_classes(c) / c->mc.n;
+            } else {
+                slab_block_sums_kernel<<<dim3((unsigned)fa.n_rows_slab), dim3(256), 0, c->stream>>>(c->slab, c->ld, fa.Nb, fa.nblk,
+                                                                                                    c->mc.bsum);
+            }
             reduce_finish_kernel<true><<<dim3((unsigned)(c->n_dpart + c->n_regpart)), dim3(256), 0, c->stream>>>(fa);
         } else {
             reduce_finish_kernel<false><<<dim3((unsigned)(c->n_dpart + c->n_regpart)), dim3(256), 0, c->stream>>>(fa);
@@ -457,7 +463,9 @@ static int ensure_work(gh_ctx *c)
     } else if (c->mc.n > 0) {
         // (the multi-component store's epilogue always runs as reduce_finish_kernel<BLOCKS>: its partials, the
         // slab rows' sums per row block and the blocks' means)
-        TRY(dalloc(c, &c->mc.bsum, (size_t)c->mc.n * (size_t)std::max(c->grid, 128)));
+        // (on the shift-invariant table: the classes' sums, which are the blocks' partials there)
+        TRY(dalloc(c, &c->mc.bsum, std::max((size_t)c->mc.n * (size_t)std::max(c->grid, 128),
+                                            lonsym_on(c) ? (size_t)lonsym_classes(c) : (size_t)0)));
         TRY(dalloc(c, &c->mc.bmean, (size_t)c->mc.n));
         // (vector-data magnetization store: R's blocks are counted per property -- up to two more than ceil(M / 256) --
         // and the amplitude term's partials follow them, one per 256 cells)

@@ -22,6 +22,10 @@ struct LonSymHost {
     bool wmirror = false;
     int witems = 0;
     int *item_c = nullptr, *item_c2 = nullptr, *amir = nullptr;
+    // the tesseroid multi-component store: classes are (component block, latitude, height); asgn: the sign a class's
+    // entries take under the north-south mirror (-1 for gx, gxy, gxz)
+    bool multi = false;
+    double *asgn = nullptr;
     int nfp = 0, wbreak = 0;               // pitch of a row of T^ / R^ / D^ in the streamed form (complex entries)
     int wgrid = 0, wparts = 0, wrows = 0;  // workgroups of the sweep; parts of the forward product, cell rows per part
     ghk::d2 *Xhat = nullptr;
@@ -64,8 +68,10 @@ static lonsym_fn_t lonsym_fn(int items, int W, int T)
 }
 
 typedef void (*lonsymw_fn_t)(LonWideGeom, SweepArgs, const double *);
-static lonsymw_fn_t lonsymw_sweep_fn(int nf)
+static lonsymw_fn_t lonsymw_sweep_fn(int nf, bool sgn = false)
 {
+    if (sgn)
+        return nf <= LW_THREADS ? lonsymw_sweep_kernel<1, true> : nf <= 2 * LW_THREADS ? lonsymw_sweep_kernel<2, true> : lonsymw_sweep_kernel<3, true>;
     return nf <= LW_THREADS ? lonsymw_sweep_kernel<1> : nf <= 2 * LW_THREADS ? lonsymw_sweep_kernel<2> : lonsymw_sweep_kernel<3>;
 }
 
@@ -113,8 +119,13 @@ static int lonsym_build(gh_ctx *c)
     if (c->cell_kind == GH_CELL_TESSEROID_COMP)
         return no("tesseroid gravity components other than gz (GH_CELL_TESSEROID_COMP) are not supported: the "
                   "north-south mirror of the table carries no sign; store the kernel or use the matrix-free mode");
-    if (c->cell_kind != GH_CELL_TESSEROID) return no("tesseroid cells only");
-    const int64_t M = c->M, N = c->N;
+    // The tesseroid multi-component store: the component block is one more coordinate of the class.  The geometry
+    // test runs on the N / nb observation points; the stacked observation b P + i then gets the class b na + a_of[i]
+    // and the longitude slot of i.
+    h.multi = tess_multi_store(c);
+    if (c->cell_kind != GH_CELL_TESSEROID && !h.multi) return no("tesseroid cells only");
+    const int nb = h.multi ? c->mc.n : 1;
+    const int64_t M = c->M, N = c->N / nb;
     std::vector<double> b((size_t)M * 6), lon((size_t)N), lat((size_t)N), hh((size_t)N);
     HIPCHK(c, hipMemcpyAsync(b.data(), c->bounds, sizeof(double) * b.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(lon.data(), c->obs[0], sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, c->stream));
@@ -159,7 +170,26 @@ static int lonsym_build(gh_ctx *c)
         }
         a_of[(size_t)i] = it->second;
     }
-    const int64_t na = (int64_t)cl_lat.size(), nc = M / n;
+    // (the blocks' classes: block b's follow block b - 1's, the same latitudes and heights again)
+    const int64_t na1 = (int64_t)cl_lat.size();
+    if (nb > 1) {
+        a_of.resize((size_t)(N * nb));
+        m_of.resize((size_t)(N * nb));
+        cl_lat.resize((size_t)(na1 * nb));
+        cl_h.resize((size_t)(na1 * nb));
+        for (int bb = 1; bb < nb; ++bb) {
+            for (int64_t i = 0; i < N; ++i) {
+                a_of[(size_t)(bb * N + i)] = (int)(bb * na1) + a_of[(size_t)i];
+                m_of[(size_t)(bb * N + i)] = m_of[(size_t)i];
+            }
+            for (int64_t a = 0; a < na1; ++a) {
+                cl_lat[(size_t)(bb * na1 + a)] = cl_lat[(size_t)a];
+                cl_h[(size_t)(bb * na1 + a)] = cl_h[(size_t)a];
+            }
+        }
+    }
+    const int64_t Ns = N * nb;  // the stacked observations
+    const int64_t na = na1 * nb, nc = M / n;
     h.n = (int)n;
     h.na = (int)na;
     h.nc = (int)nc;
@@ -182,7 +212,14 @@ static int lonsym_build(gh_ctx *c)
     else if (h.lds > 160 * 1024 - 512) direct_why = "a cell row's table and the residual grid do not fit the LDS";
     else if (na * n > (int64_t)8 * LS_THREADS) direct_why = "a cell row's table has more than 8192 entries";
     h.direct_ok = direct_why == nullptr;
-    const bool wide_can = n <= LW_NMAX && n >= 2 && env_int("GRAVHMC_LONSYM_WIDE", 1) != 0;
+    // (the multi-component store runs on the streamed harmonic form alone, whatever the switches say: the signed
+    // mirror and the classes per block are written once, there)
+    if (h.multi) {
+        h.direct_ok = false;
+        if (n > LW_NMAX) return no("the tesseroid multi-component store runs on the streamed harmonic form: more than 1024 longitudes per cell row");
+        if (n < 2) return no("the tesseroid multi-component store runs on the streamed harmonic form: fewer than 2 longitudes per cell row");
+    }
+    const bool wide_can = n <= LW_NMAX && n >= 2 && (h.multi || env_int("GRAVHMC_LONSYM_WIDE", 1) != 0);
     if (!h.direct_ok && !wide_can) return no(direct_why);
     if ((int64_t)na * n > 0x7fffffffLL / 4) return no("more than 2^29 (class, longitude) slots");
     // the table: every class at every shift against the cells of longitude index 0 (reference engine)
@@ -222,8 +259,21 @@ static int lonsym_build(gh_ctx *c)
     tess_convert_kernel<<<dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, c->stream>>>(
         d_so, d_so + Np, d_so + 2 * Np, Np, conv, conv + Np, conv + 2 * Np, conv + 3 * Np);
     const int64_t total = h.ldT * nc;
-    tess_comp_kernel<COMP_GZ><<<dim3((unsigned)std::min<int64_t>((total + 63) / 64, 1 << 24)), dim3(64), 0, c->stream>>>(
-        conv, conv + Np, conv + 2 * Np, conv + 3 * Np, d_sb, Np, nc, h.ldT, c->ratio, COMP_GZ, h.T, err_cell, stats);
+    if (h.multi) {
+        // every class by its own field at its own ratio, times its block's data weight: ONE launch
+        TessBlocks tb{};
+        tb.n = nb;
+        for (int bb = 0; bb < nb; ++bb) {
+            tb.comp[bb] = c->mc.comp[bb];
+            tb.ratio[bb] = c->mc.ratio[bb];
+            tb.w[bb] = c->mc.w[bb];
+        }
+        tess_multi_table_kernel<<<dim3((unsigned)std::min<int64_t>((total + 63) / 64, 1 << 24)), dim3(64), 0, c->stream>>>(
+            conv, conv + Np, conv + 2 * Np, conv + 3 * Np, d_sb, Np, nc, h.ldT, na1 * n, tb, h.T, err_cell, stats);
+    } else {
+        tess_comp_kernel<COMP_GZ><<<dim3((unsigned)std::min<int64_t>((total + 63) / 64, 1 << 24)), dim3(64), 0, c->stream>>>(
+            conv, conv + Np, conv + 2 * Np, conv + 3 * Np, d_sb, Np, nc, h.ldT, h.ldT, c->ratio, COMP_GZ, h.T, err_cell, stats);
+    }
     HIPCHK(c, hipGetLastError());
     TessStats hs;
     std::vector<int> herr((size_t)nc);
@@ -238,10 +288,10 @@ static int lonsym_build(gh_ctx *c)
     c->leaves = (int64_t)hs.leaves;
     // slots (a, m) -> observations, ascending: the first one per slot, and the further ones of the few
     // slots that hold several (duplicated longitudes); LDS offset of every observation's slot
-    std::vector<int> sfirst((size_t)Np, -1), xslot, xptr(1, 0), xobs, ldsof((size_t)N);
+    std::vector<int> sfirst((size_t)Np, -1), xslot, xptr(1, 0), xobs, ldsof((size_t)Ns);
     {
         std::vector<std::vector<int>> more((size_t)Np);
-        for (int64_t i = 0; i < N; ++i) {
+        for (int64_t i = 0; i < Ns; ++i) {
             const size_t sl = (size_t)(a_of[(size_t)i] * n + m_of[(size_t)i]);
             if (sfirst[sl] < 0)
                 sfirst[sl] = (int)i;
@@ -261,7 +311,7 @@ static int lonsym_build(gh_ctx *c)
     for (size_t x = 0; x < xslot.size(); ++x) slotx[(size_t)xslot[x]] = (int)x;
     if (xslot.empty()) xslot.push_back(0);
     if (xobs.empty()) xobs.push_back(0);
-    for (int64_t i = 0; i < N; ++i) ldsof[(size_t)i] = a_of[(size_t)i] * h.SW + m_of[(size_t)i];
+    for (int64_t i = 0; i < Ns; ++i) ldsof[(size_t)i] = a_of[(size_t)i] * h.SW + m_of[(size_t)i];
     auto up = [&](int **dst, const std::vector<int> &src) -> int {
         TRY(dalloc(c, dst, src.size(), false));
         HIPCHK(c, hipMemcpyAsync(*dst, src.data(), sizeof(int) * src.size(), hipMemcpyHostToDevice, c->stream));
@@ -291,7 +341,7 @@ static int lonsym_build(gh_ctx *c)
     h.rw = std::min(rp, 4);
     h.hlds = lonsymh_lds_doubles((int)n, h.nf, (int)na, h.rw) * sizeof(double);
     const int force_wide = env_int("GRAVHMC_LONSYM_WIDE", 1) == 2;  // (2: the streamed form also where the register form applies)
-    if (!force_wide && env_int("GRAVHMC_LONSYM_HARMONIC", 1) != 0 && h.nf <= 64 && na <= 4 * LH_AK && n <= 1024 && h.hlds <= 160 * 1024 - 512 &&
+    if (!h.multi && !force_wide && env_int("GRAVHMC_LONSYM_HARMONIC", 1) != 0 && h.nf <= 64 && na <= 4 * LH_AK && n <= 1024 && h.hlds <= 160 * 1024 - 512 &&
         allow_dynamic_lds(reinterpret_cast<const void *>(lonsymh_fn(h.rw)), h.hlds) == hipSuccess) {
         h.hgrid = (int)((nc + rp - 1) / rp);
         TRY(dalloc(c, &h.tw, (size_t)n, false));
@@ -318,7 +368,7 @@ static int lonsym_build(gh_ctx *c)
     // The streamed harmonic form (lonsymw.hip.h) where the register form does not apply: no limit on the classes,
     // n <= 1024.  GRAVHMC_LONSYM_WIDE=0: off (the direct correlations, or a refusal), 2: also where the register form applies.
     h.wide = false;
-    if (!h.harm && wide_can && (env_int("GRAVHMC_LONSYM_HARMONIC", 1) != 0 || force_wide || !h.direct_ok)) {
+    if (!h.harm && wide_can && (h.multi || env_int("GRAVHMC_LONSYM_HARMONIC", 1) != 0 || force_wide || !h.direct_ok)) {
         // (rows of T^ start on 128-byte lines: a wave's 1 KB request then touches 8 of them, not 9)
         h.nfp = (h.nf + 7) / 8 * 8;
         // North-south mirror: a grid symmetric about the equator (cell rows and observation classes come in mirrored pairs)
@@ -330,7 +380,8 @@ static int lonsym_build(gh_ctx *c)
             auto near = [](double x, double y) { return std::fabs(x - y) <= 1e-9 * std::max(1.0, std::max(std::fabs(x), std::fabs(y))); };
             bool ok = true;
             for (int64_t a = 0; a < na && ok; ++a) {
-                for (int64_t b2 = 0; b2 < na; ++b2)
+                // (the partner of class (block, lat, h) is (block, -lat, h))
+                for (int64_t b2 = a / na1 * na1; b2 < (a / na1 + 1) * na1; ++b2)
                     if (near(cl_lat[(size_t)b2], -cl_lat[(size_t)a]) && near(cl_h[(size_t)b2], cl_h[(size_t)a])) {
                         amirv[(size_t)a] = (int)b2;
                         break;
@@ -365,7 +416,7 @@ static int lonsym_build(gh_ctx *c)
         const int64_t ni = h.witems;
         // (GRAVHMC_LW_LDS_PAD: extra LDS per workgroup in KB -- a diagnostic that lowers the workgroups per CU)
         h.wlds = lonsymw_lds_doubles((int)n, h.nf) * sizeof(double) + (size_t)env_int("GRAVHMC_LW_LDS_PAD", 0) * 1024;
-        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(lonsymw_sweep_fn(h.nf)), h.wlds));
+        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(lonsymw_sweep_fn(h.nf, h.multi)), h.wlds));
         h.wgrid = (int)std::min<int64_t>(ni, (int64_t)c->cus * 8);
         // parts of the forward product: ~8 waves per SIMD over the chip, at least 8 rows of T^ per part
         const int64_t waves_row = ((int64_t)na * h.nfp + 63) / 64;
@@ -385,6 +436,17 @@ static int lonsym_build(gh_ctx *c)
             TRY(up(&h.item_c, itc));
             TRY(up(&h.item_c2, itc2));
             TRY(up(&h.amir, amirv));
+            if (h.multi) {
+                // gx, gxy, gxz: odd in the observation's north axis, which the mirror flips
+                std::vector<double> sg((size_t)na);
+                for (int64_t a = 0; a < na; ++a) {
+                    const int comp = c->mc.comp[a / na1];
+                    sg[(size_t)a] = (comp == GH_COMP_GX || comp == GH_COMP_GXY || comp == GH_COMP_GXZ) ? -1.0 : 1.0;
+                }
+                TRY(dalloc(c, &h.asgn, sg.size(), false));
+                HIPCHK(c, hipMemcpyAsync(h.asgn, sg.data(), sizeof(double) * sg.size(), hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));  // (sg leaves scope)
+            }
         }
         lonsymh_twiddle_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>((int)n, h.tw);
         lonsymh_table_kernel<<<dim3((unsigned)(ni * na)), dim3(64), 0, c->stream>>>(h.T, h.ldT, (int)n, h.nf, (int)na, h.tw, h.That, h.nfp,
@@ -413,6 +475,7 @@ static LonWideGeom lonsymw_geom(const gh_ctx *c)
     g.item_c = h.wmirror ? h.item_c : nullptr;
     g.item_c2 = h.wmirror ? h.item_c2 : nullptr;
     g.amir = h.wmirror ? h.amir : nullptr;
+    g.asgn = h.wmirror && h.multi ? h.asgn : nullptr;
     g.parts = h.wparts;
     g.rows_per_part = h.wrows;
     g.That = h.That;
@@ -491,7 +554,7 @@ static int launch_lonsym(gh_ctx *c, SweepArgs &a)
         // transforms behind the row-parallel pass
         const LonWideGeom g = lonsymw_geom(c);
         if (a.mode & SW_ADJ) lonsymw_rhat_kernel<<<dim3((unsigned)h.na), dim3(LW_THREADS), 0, c->stream>>>(g, a.r);
-        hipLaunchKernelGGL(lonsymw_sweep_fn(h.nf), dim3((unsigned)h.wgrid), dim3(LW_THREADS), h.wlds, c->stream, g, a,
+        hipLaunchKernelGGL(lonsymw_sweep_fn(h.nf, h.multi), dim3((unsigned)h.wgrid), dim3(LW_THREADS), h.wlds, c->stream, g, a,
                            c->weighted ? c->wm : nullptr);
         if (a.mode & SW_FWD) {
             const int64_t tot = (int64_t)h.na * h.nfp;
@@ -503,7 +566,10 @@ static int launch_lonsym(gh_ctx *c, SweepArgs &a)
             case 4: lonsymw_forward_kernel<4, false><<<fgrid, dim3(LW_THREADS), 0, c->stream>>>(g); break;
             default: lonsymw_forward_kernel<8, false><<<fgrid, dim3(LW_THREADS), 0, c->stream>>>(g); break;
             }
-            lonsymw_post_kernel<<<dim3((unsigned)h.na), dim3(LW_THREADS), 0, c->stream>>>(g, c->ld, a.slab, a.dsum);
+            if (h.multi)
+                lonsymw_post_kernel<true><<<dim3((unsigned)h.na), dim3(LW_THREADS), 0, c->stream>>>(g, c->ld, a.slab, a.dsum);
+            else
+                lonsymw_post_kernel<false><<<dim3((unsigned)h.na), dim3(LW_THREADS), 0, c->stream>>>(g, c->ld, a.slab, a.dsum);
         }
         return GH_OK;
     }

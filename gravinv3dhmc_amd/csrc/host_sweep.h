@@ -578,6 +578,8 @@ static int launch_sweep(gh_ctx *c, SweepArgs &a)
             a.dsum = c->dsum;  // (the shift-invariant pass delivers the sums of its slab rows as well)
             c->dsum_live = true;
         }
+        // (tesseroid multi-component store: the classes' sums are the row blocks' partials, host_eval.h)
+        if (lonsym_one_row(c) && (a.mode & SW_FWD) && c->mc.n > 0) a.dsum = c->mc.bsum;
         if (lonsym_one_row(c) && (a.mode & SW_FWD)) {
             // (harmonic form: ONE finished slab row; the sums come per class of observations)
             c->slab_live = 1;

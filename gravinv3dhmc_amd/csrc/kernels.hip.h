@@ -1974,6 +1974,7 @@ __device__ __forceinline__ double tess_comp_leaf_rt(int comp, double lon, double
     case COMP_GEOID: return tess_comp_leaf<COMP_POTENTIAL>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
     case COMP_GX: return tess_comp_leaf<COMP_GX>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
     case COMP_GY: return tess_comp_leaf<COMP_GY>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
+    case COMP_GZ: return tess_comp_leaf<COMP_GZ>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
     case COMP_GXX: return tess_comp_leaf<COMP_GXX>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
     case COMP_GXY: return tess_comp_leaf<COMP_GXY>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
     case COMP_GXZ: return tess_comp_leaf<COMP_GXZ>(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
@@ -2088,7 +2089,8 @@ __device__ double tess_comp_entry(int comp, double lon, double sinlat, double co
     return acc;
 }
 
-// Dense assembly of one field, one thread per (obs, cell) pair, obs fastest, zero padding rows to ld; the error
+// Dense assembly of one field, one thread per (obs, cell) pair, obs fastest, into `rows` rows of every column of a
+// store of leading dimension ld (from G on): the first N of them the observations' entries, the rest zero; the error
 // codes summed per cell into err_cell, the leaf count and the overflow flag into stats.  One instantiation
 // per leaf: the leaf fixes the scale, except the potential's, which serves the geoid too (`comp` picks its
 // scale).  G == nullptr: the statistics only (the matrix-free build, which stores no entry).
@@ -2096,8 +2098,50 @@ template <int LEAF>
 __global__ void __launch_bounds__(64)
 tess_comp_kernel(const double *__restrict__ lon_r, const double *__restrict__ sinlat_a,
                  const double *__restrict__ coslat_a, const double *__restrict__ radius_a,
-                 const double *__restrict__ bounds6, int64_t N, int64_t M, int64_t ld, double ratio, int comp,
+                 const double *__restrict__ bounds6, int64_t N, int64_t M, int64_t rows, int64_t ld, double ratio, int comp,
                  double *__restrict__ G, int *__restrict__ err_cell, TessStats *stats)
+{
+    unsigned long long nleaf = 0;
+    bool overflow = false;
+    for (int64_t idx = (int64_t)blockIdx.x * 64 + threadIdx.x; idx < rows * M;
+         idx += (int64_t)gridDim.x * 64) {
+        const int64_t c = idx / rows, l = idx - c * rows;
+        if (l >= N) {
+            if (G) G[c * ld + l] = 0.0;
+            continue;
+        }
+        int error_code = 0;
+        const double v = tess_comp_entry<LEAF>(comp, lon_r[l], sinlat_a[l], coslat_a[l], radius_a[l], bounds6 + 6 * c,
+                                               ratio, error_code, nleaf, overflow);
+        if (G) G[c * ld + l] = tess_comp_scale(LEAF == COMP_POTENTIAL ? comp : LEAF, v);
+        if (error_code != 0) atomicAdd(&err_cell[c], error_code);
+    }
+    if (overflow) atomicExch(&stats->overflow, 1);
+    // one atomic per wave for the leaf count
+    unsigned long long tot = nleaf;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) tot += __shfl_xor(tot, off, WAVE);
+    if ((threadIdx.x & 63) == 0) atomicAdd(&stats->leaves, tot);
+}
+
+// The row blocks of the tesseroid multi-component store (GH_CELL_TESSEROID_MULTI): field, ratio and data weight
+struct TessBlocks {
+    int n;
+    int comp[MULTI_MAX];
+    double ratio[MULTI_MAX];
+    double w[MULTI_MAX];
+};
+
+// The shift-invariant table of the tesseroid multi-component store: rows (class, shift) of every cell row of
+// longitude index 0, tess_comp_kernel's layout (ld rows per column, zero behind the first N).  The class is (block,
+// latitude, height): row l belongs to block l / rows_per_block, and its entry is that block's field at that block's
+// ratio, scaled as gh_set_cells_tess scales it, times the block's data weight.  The leaf is chosen at run time
+// (tess_comp_entry<-1>: the same leaf functions in the same order as the dense store's instantiations).
+__global__ void __launch_bounds__(64)
+tess_multi_table_kernel(const double *__restrict__ lon_r, const double *__restrict__ sinlat_a,
+                        const double *__restrict__ coslat_a, const double *__restrict__ radius_a,
+                        const double *__restrict__ bounds6, int64_t N, int64_t M, int64_t ld, int64_t rows_per_block,
+                        TessBlocks tb, double *__restrict__ T, int *__restrict__ err_cell, TessStats *stats)
 {
     unsigned long long nleaf = 0;
     bool overflow = false;
@@ -2105,17 +2149,18 @@ tess_comp_kernel(const double *__restrict__ lon_r, const double *__restrict__ si
          idx += (int64_t)gridDim.x * 64) {
         const int64_t c = idx / ld, l = idx - c * ld;
         if (l >= N) {
-            if (G) G[idx] = 0.0;
+            T[idx] = 0.0;
             continue;
         }
+        const int b = (int)(l / rows_per_block);
+        const int comp = tb.comp[b];
         int error_code = 0;
-        const double v = tess_comp_entry<LEAF>(comp, lon_r[l], sinlat_a[l], coslat_a[l], radius_a[l], bounds6 + 6 * c,
-                                               ratio, error_code, nleaf, overflow);
-        if (G) G[idx] = tess_comp_scale(LEAF == COMP_POTENTIAL ? comp : LEAF, v);
+        const double v = tess_comp_entry<-1>(comp, lon_r[l], sinlat_a[l], coslat_a[l], radius_a[l], bounds6 + 6 * c,
+                                             tb.ratio[b], error_code, nleaf, overflow);
+        T[idx] = tess_comp_scale(comp, v) * tb.w[b];
         if (error_code != 0) atomicAdd(&err_cell[c], error_code);
     }
     if (overflow) atomicExch(&stats->overflow, 1);
-    // one atomic per wave for the leaf count
     unsigned long long tot = nleaf;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) tot += __shfl_xor(tot, off, WAVE);

@@ -16,6 +16,10 @@
 // on the 1-degree grid = 0.24 ms at 8 TB/s, where the dense kernel of that grid (65 341 x 648 000 doubles = 339 GB) fits no
 // GPU.  On a grid symmetric about the equator ONE row of T^ stands for a north-south mirrored pair of cell rows (the
 // struct's item_* fields): half the table, every entry read serves both rows.  No inter-workgroup waits: four plain launches per step.  Sums in a fixed order: reproducible bit for bit.
+// The tesseroid multi-component store (gh_set_cells_tess_multi) runs here too: its classes are (component block, latitude,
+// height), so nothing changes but the mirror -- gx, gxy and gxz change sign under it (SGN instantiations, LonWideGeom::asgn).
+// Nothing assumes T[d] = T[n - d]: T^ is the full complex transform of all n shifts, so fields odd in the longitude
+// difference (gy, gxy, gyz) need nothing special.
 // Reference arithmetic: gravmag/_tesseroid_numba.py:207-222 (cos(lon - lon')), gravmag/tesseroid.py:189-232,
 // inversion/potential.py:698,708, inversion/hmc.py:114-152; geometry family example/global/SetPMTS.txt.
 #pragma once
@@ -41,6 +45,10 @@ struct LonWideGeom {
     // (the second one lands on the mirrored class).  item_c == nullptr: no mirror, item p = cell row p.
     int nitems, planes;
     const int *item_c, *item_c2, *amir;
+    // Signed mirror (the tesseroid multi-component store, whose classes are (component block, latitude, height)): the
+    // entry of the mirrored pair is asgn[a] K, -1 for the classes of gx, gxy and gxz -- the observation's north axis
+    // flips under the mirror -- and +1 for every other field's.  Read by the SGN instantiations only; nullptr otherwise.
+    const double *asgn;
 };
 
 constexpr int LW_THREADS = 256;
@@ -142,7 +150,8 @@ __global__ void __launch_bounds__(LW_THREADS) lonsymw_rhat_kernel(LonWideGeom g,
 // NP = pairs of longitudes per thread (nf <= NP * 256): the update's operands of a thread's pairs wait in registers
 // while the row's slab of T^ streams -- with NP = 3 for every grid the kernel took 189 registers (two waves per SIMD);
 // NP = 1 (n <= 510): 127, four waves per SIMD = four workgroups per CU.
-template <int NP>
+// SGN: the mirrored class's R^ takes the class's sign (LonWideGeom::asgn); without it the code is what it was.
+template <int NP, bool SGN>
 __device__ __forceinline__ void lonsymw_sweep_body(const LonWideGeom &g, const SweepArgs &a, const double *__restrict__ wm)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -228,6 +237,11 @@ __device__ __forceinline__ void lonsymw_sweep_body(const LonWideGeom &g, const S
                                 t[u] = __builtin_nontemporal_load(&Tg[(int64_t)ac * nfp + fc]);
                                 rr[u] = g.Rhat[(int64_t)ac * nfp + fc];
                                 r2[u] = g.Rhat[(int64_t)g.amir[ac] * nfp + fc];
+                                if (SGN) {
+                                    const double sg = g.asgn[ac];
+                                    r2[u].x *= sg;
+                                    r2[u].y *= sg;
+                                }
                             }
 #pragma unroll
                             for (int u = 0; u < 4; ++u) {
@@ -238,8 +252,13 @@ __device__ __forceinline__ void lonsymw_sweep_body(const LonWideGeom &g, const S
                             }
                         }
                         for (; aa < na; aa += 4) {
-                            const d2 t = __builtin_nontemporal_load(&Tg[(int64_t)aa * nfp + fc]), rr = g.Rhat[(int64_t)aa * nfp + fc],
-                                     r2 = g.Rhat[(int64_t)g.amir[aa] * nfp + fc];
+                            const d2 t = __builtin_nontemporal_load(&Tg[(int64_t)aa * nfp + fc]), rr = g.Rhat[(int64_t)aa * nfp + fc];
+                            d2 r2 = g.Rhat[(int64_t)g.amir[aa] * nfp + fc];
+                            if (SGN) {
+                                const double sg = g.asgn[aa];
+                                r2.x *= sg;
+                                r2.y *= sg;
+                            }
                             acc.x += t.x * rr.x + t.y * rr.y;
                             acc.y += t.x * rr.y - t.y * rr.x;
                             acc2.x += t.x * r2.x + t.y * r2.y;
@@ -344,10 +363,10 @@ __device__ __forceinline__ void lonsymw_sweep_body(const LonWideGeom &g, const S
     }
 }
 
-template <int NP>
+template <int NP, bool SGN = false>
 __global__ void __launch_bounds__(LW_THREADS) lonsymw_sweep_kernel(LonWideGeom g, SweepArgs a, const double *__restrict__ wm)
 {
-    lonsymw_sweep_body<NP>(g, a, wm);
+    lonsymw_sweep_body<NP, SGN>(g, a, wm);
 }
 
 // D^ partial of the items [part * rows_per_part, ...): thread e = a * nfp + f (one complex of a row of T^); an entry of a
@@ -403,7 +422,8 @@ __global__ void __launch_bounds__(LW_THREADS) lonsymw_forward_kernel(LonWideGeom
 }
 
 // block = class a: sum of the parts, inverse transform, scatter to the class's observations (slab row 0), the
-// class's sum of predicted data (dsum[a])
+// class's sum of predicted data (dsum[a]).  SGN: the second plane of D^ partials takes the class's sign.
+template <bool SGN = false>
 __global__ void __launch_bounds__(LW_THREADS) lonsymw_post_kernel(LonWideGeom g, int64_t ld, double *__restrict__ out,
                                                                   double *__restrict__ dsum)
 {
@@ -425,10 +445,11 @@ __global__ void __launch_bounds__(LW_THREADS) lonsymw_post_kernel(LonWideGeom g,
         if (g.planes > 1) {
             // what the mirrored cell rows contribute to this class was accumulated at the mirrored class's entries
             const d2 *src2 = g.Dpart + tot + (int64_t)g.amir[a] * g.nfp + f;
+            const double sg = SGN ? g.asgn[a] : 1.0;
             for (int p = 0; p < g.parts; ++p) {
                 const d2 v = src2[(int64_t)p * g.planes * tot];
-                s.x += v.x;
-                s.y += v.y;
+                s.x += SGN ? sg * v.x : v.x;
+                s.y += SGN ? sg * v.y : v.y;
             }
         }
         const double wf = (f == 0 || (2 * f == n)) ? 1.0 : 2.0;

@@ -167,6 +167,27 @@ class Engine(object):
                                                ptr(w)))
         self.multi = len(comps)
 
+    def set_cells_tess_multi(self, bounds6, components, ratios, weights):
+        """The M tesseroids (w, e, s, n, top, bottom) of a multi-component model (gh_set_cells_tess_multi): rows as
+        set_cells_multi, block c the tesseroid field components[c] assembled at the distance-size ratio ratios[c] > 0,
+        with the data weight weights[c] > 0.  Dense, or -- set_shift_invariant(True) before build_G -- on the
+        shift-invariant table.  Call it before set_obs.  (The unweighted gz alone is the CELL_TESSEROID context.)"""
+        b = f64(bounds6)
+        if b.shape != (self.M, 6):
+            raise ValueError("bounds table must be (M, 6)")
+        comps = [_lib.COMPONENTS.get(c, -1) if isinstance(c, str) else int(c) for c in components]
+        if any(c not in _lib.COMPONENTS.values() for c in comps):
+            raise ValueError("component must be one of %s" % ", ".join(_lib.COMPONENTS))
+        w, r = f64(weights), f64(ratios)
+        if w.shape != (len(comps),) or r.shape != (len(comps),):
+            raise ValueError("one data weight and one ratio per component")
+        self._chk(self._lib.gh_set_cells_tess_multi(self._h, ptr(b), len(comps), (C.c_int * max(len(comps), 1))(*comps),
+                                                    ptr(r), ptr(w)))
+        self.tess_multi = True
+        # (the unweighted gz alone is the tesseroid store itself: one block, no block table)
+        if not (comps == [_lib.COMP_GZ] and w[0] == 1.0):
+            self.multi = len(comps)
+
     def set_cells_mvi(self, bounds6, direction):
         """The M/3 prisms (bounds (M/3, 6)) of a magnetization-vector model (gh_set_cells_mvi): three unknowns
         (mx, my, mz) per prism, model vectors property-major, the total field along direction = (fx, fy, fz);

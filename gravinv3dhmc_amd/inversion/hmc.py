@@ -381,6 +381,9 @@ def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
     if getattr(model._engine, "tess_mag", False):
         raise NotImplementedError("HMCSampleBatch does not run the tesseroid magnetization store "
                                   "(TesseroidMagVectorModule): sample its chains one at a time with HMCSample")
+    if getattr(model._engine, "tess_multi", False):
+        raise NotImplementedError("HMCSampleBatch does not run the tesseroid multi-component store "
+                                  "(TesseroidMultiComponentModule): sample its chains one at a time with HMCSample")
     if getattr(model._engine, "multi", 0) and getattr(model._engine, "mvi", False):
         raise NotImplementedError("HMCSampleBatch does not run the vector-data magnetization store (MagVectorModule with "
                                   "data=): sample its chains one at a time with HMCSample")

@@ -46,6 +46,8 @@ class MultiComponentModule(_Potential):
     chosen for gz prisms alone: this store is never folded (Engine.fold_info() tells).
     """
     _props = 1
+    _spherical = False   # (TesseroidMultiComponentModule: tesseroids, and the shift-invariant store)
+    _store = _STORE
 
     def __init__(self, dobs, mrange, mspacing, obsurface, components=("gz",), weights="std", mratio=1, mseg=False,
                  mdivisionsection=[], weightfactor=0.5, coordinate="cartesian", wavelet=False, device=0, verbose=True,
@@ -84,22 +86,25 @@ class MultiComponentModule(_Potential):
         unknown = sorted(set(kwargs) - {"mtopo"})
         if unknown:
             raise TypeError("unexpected keyword argument %r" % unknown[0])
-        if coordinate == "spherical":
+        _STORE = self._store
+        if coordinate == "spherical" and not self._spherical:
             raise NotImplementedError("%s holds prism fields: tesseroids (coordinate='spherical') are not supported"
                                       % _STORE)
-        if coordinate != "cartesian":
+        if coordinate != ("spherical" if self._spherical else "cartesian"):
             raise ValueError("Please choose coordinate from(cartesian, spherical)!")
         if wavelet not in (False, None):
             raise NotImplementedError("wavelet compression of %s is not supported" % _STORE)
         if matrix_free:
             raise NotImplementedError("%s is dense: the matrix-free mode is not supported" % _STORE)
-        if shift_invariant:
+        if shift_invariant and not self._spherical:
             raise NotImplementedError("%s is dense: the shift-invariant store is not supported" % _STORE)
         if shard is not None:
             raise NotImplementedError("%s is not sharded" % _STORE)
-        if len(components) * n > 16384:
+        if len(components) * n > 16384 and not shift_invariant:
             raise NotImplementedError("%d components x %d observations = %d rows: %s takes at most 16384 (it runs on "
-                                      "the fused sweep)" % (len(components), n, len(components) * n, _STORE))
+                                      "the fused sweep)%s" % (len(components), n, len(components) * n, _STORE,
+                                                               "; shift_invariant=True has no such limit"
+                                                               if self._spherical else ""))
 
         self.components = components
         self.weights = w
@@ -111,9 +116,9 @@ class MultiComponentModule(_Potential):
         self.wavelet = False
         self.device = device
 
-        self._say("Calculating gravity field ({}) in cartesian coordinate.".format(", ".join(components)))
-        mesh = (mesher.PrismMeshSegment(mrange, mspacing, mdivisionsection) if mseg
-                else mesher.PrismMesh(mrange, mspacing, mratio))
+        self.shift_invariant = bool(shift_invariant)
+        self._say("Calculating gravity field ({}) in {} coordinate.".format(", ".join(components), coordinate))
+        mesh = self._make_mesh()
         if "mtopo" in kwargs:
             value = kwargs["mtopo"]
             self.topocarve = True
@@ -125,9 +130,9 @@ class MultiComponentModule(_Potential):
         self._say("Start of calculate kernel")
         start = time.time()
         eng = Engine(len(components) * n, bounds.shape[0], device=device)
-        eng.set_cells_multi(bounds, components, w)
+        self._set_cells(eng, bounds, components, w)
         eng.set_obs(self.lonobs, self.latobs, self.heightobs)
-        eng.build_G()
+        self._build(eng)
         self._say("kernel.shape", (len(components) * n, bounds.shape[0]))
         self._say("End of calculate kernel:%.6f s" % (time.time() - start))
         self._engine = eng
@@ -142,6 +147,17 @@ class MultiComponentModule(_Potential):
         self.dobs = np.concatenate(dobs)
         self.dobsw = self.Wb @ self.dobs
         eng.set_data(self.dobsw)
+
+    # ------------------------------------------------------------------ the store (the spherical module's differ)
+    def _make_mesh(self):
+        return (mesher.PrismMeshSegment(self.mrange, self.mspacing, self.mdivisionsection) if self.mseg
+                else mesher.PrismMesh(self.mrange, self.mspacing, self.mratio))
+
+    def _set_cells(self, eng, bounds, components, w):
+        eng.set_cells_multi(bounds, components, w)
+
+    def _build(self, eng):
+        eng.build_G()
 
     # ------------------------------------------------------------------ weighting
     def sensitivityWeighting(self):
@@ -184,3 +200,105 @@ class MultiComponentModule(_Potential):
         one per component."""
         info = self._engine.multi_info()
         return info["pred_mean"], info["obs_mean"]
+
+
+_TESS_STORE = "the tesseroid multi-component store"
+
+
+def _default_ratio(component):
+    """The reference's distance-size ratio of a tesseroid field (gravmag/tesseroid.py)."""
+    from ..gravmag import tesseroid
+    if component in ("potential", "geoid"):
+        return tesseroid.RATIO_V
+    if component in ("gx", "gy", "gz"):
+        return tesseroid.RATIO_G
+    return tesseroid.RATIO_GG
+
+
+class TesseroidMultiComponentModule(MultiComponentModule):
+    """C gravity components of one tesseroid density model, inverted together on one MI355X: MultiComponentModule on a
+    spherical mesh (libgravhmc's GH_CELL_TESSEROID_MULTI), for satellite gradiometry -- gzz, gxx, gyy, gxz ... measured
+    together at orbit height.
+
+    obsurface = (lon, lat, height) in degrees and metres; mrange = (west, east, south, north, top, bottom), mspacing =
+    (dr, dlat, dlon), mratio, mseg, mdivisionsection as the spherical GravMagModule (TesseroidMesh /
+    TesseroidMeshSegment); mtopo carves the mesh.  components: distinct names of the tesseroid gravity fields
+    (gravmag.tesseroid.potential ... gzz), gz included, in the observations' local north-east-down frames; dobs,
+    weights ("std" or numbers), Wb, dobsw, block_means(), forward(model), kernel(component), HMCSample and
+    misfit_and_grad as MultiComponentModule.
+
+    ratio: the distance-size ratio of the adaptive subdivision.  None takes the reference's per field (RATIO_V = 1 for
+    potential / geoid, RATIO_G = 1.6 for gx / gy / gz, RATIO_GG = 8 for the tensor); a number applies to all
+    components; a sequence gives one per component.  The attribute ratios holds them.
+
+    shift_invariant=True keeps the shift-invariant table instead of the stacked kernel (regular global grids: every
+    cell row a full circle of longitudes, observations on the cells' longitude spacing): the component block is one
+    more coordinate of the observation class, G is never stored and the 16384-row limit does not apply; on a grid
+    symmetric about the equator the table is halved by the signed north-south mirror.  NotImplementedError with the
+    store's reason if the geometry lacks the structure.  On the table Aw, A and kernel(component) do not exist
+    (NotImplementedError).
+
+    With components=("gz",) and weight 1 the dense form is GravMagModule(coordinate="spherical"): one block with one
+    mean, and block_means() raises ValueError.  Not supported (NotImplementedError naming the tesseroid
+    multi-component store): wavelet compression, the matrix-free mode, shards, HMCSampleBatch, and more than 16384
+    stacked rows without shift_invariant=True."""
+    _spherical = True
+    _store = _TESS_STORE
+
+    def __init__(self, dobs, mrange, mspacing, obsurface, components=("gzz",), weights="std", ratio=None,
+                 shift_invariant=False, mratio=1, mseg=False, mdivisionsection=[], weightfactor=0.5, device=0,
+                 verbose=True, wavelet=False, matrix_free=False, shard=None, **kwargs):
+        comps = (components,) if isinstance(components, str) else tuple(components)
+        if ratio is None:
+            ratios = [_default_ratio(c) for c in comps]
+        elif np.ndim(ratio) == 0:
+            ratios = [float(ratio)] * len(comps)
+        else:
+            ratios = [float(r) for r in ratio]
+            if len(ratios) != len(comps):
+                raise ValueError("%d ratios for %d components" % (len(ratios), len(comps)))
+        for r in ratios:
+            if not (r > 0):
+                raise ValueError("Invalid ratio {}. Must be > 0.".format(r))
+        self.ratios = np.asarray(ratios, dtype=np.float64)
+        super().__init__(dobs, mrange, mspacing, obsurface, components=comps, weights=weights, mratio=mratio, mseg=mseg,
+                         mdivisionsection=mdivisionsection, weightfactor=weightfactor, coordinate="spherical",
+                         wavelet=wavelet, device=device, verbose=verbose, shard=shard, matrix_free=matrix_free,
+                         shift_invariant=shift_invariant, **kwargs)
+
+    def _make_mesh(self):
+        return (mesher.TesseroidMeshSegment(self.mrange, self.mspacing, self.mdivisionsection) if self.mseg
+                else mesher.TesseroidMesh(self.mrange, self.mspacing, self.mratio))
+
+    def _set_cells(self, eng, bounds, components, w):
+        if self.shift_invariant:
+            eng.set_shift_invariant(True)
+        eng.set_cells_tess_multi(bounds, components, self.ratios, w)
+
+    def _build(self, eng):
+        eng.build_G()   # (NotImplementedError with the store's reason where the table does not apply)
+        if eng.kernel_stats()["warn_cells"] > 0:
+            import warnings
+            from ..gravmag.tesseroid import _WARN_DIVIDE
+            warnings.warn(_WARN_DIVIDE, RuntimeWarning)
+
+    def _no_table(self, what):
+        if self.shift_invariant:
+            raise NotImplementedError("%s: %s keeps the shift-invariant table, the kernel is never stored" %
+                                      (what, _TESS_STORE))
+
+    @property
+    def A(self):
+        self._no_table("A")
+        return super().A
+
+    def kernel(self, component):
+        if component not in self.components:
+            raise ValueError("component %r is not one of this module's %r" % (component, self.components))
+        self._no_table("kernel(%r)" % (component,))
+        return super().kernel(component)
+
+    def block_means(self):
+        if getattr(self._engine, "multi", 1) == 1 and self.components == ("gz",) and self.weights[0] == 1.0:
+            raise ValueError("block_means: the module has one block of unweighted gz (GravMagModule's store)")
+        return super().block_means()

@@ -89,10 +89,12 @@ typedef enum {
  * GH_CELL_PRISM_MVI_DATA: prisms, a magnetization vector per cell under VECTOR data -- row blocks of tf, bx, by, bz
  * (gh_set_cells_mvi_data);
  * GH_CELL_TESS_MVI_DATA: tesseroids, a magnetization vector per cell (north, east, down at the cell's centre) under
- * row blocks of tf, bx, by, bz in the observations' local frames (gh_set_cells_tess_mag) */
+ * row blocks of tf, bx, by, bz in the observations' local frames (gh_set_cells_tess_mag);
+ * GH_CELL_TESSEROID_MULTI: tesseroids, several gravity fields of one density model inverted together, on the dense
+ * store or on the shift-invariant table (gh_set_cells_tess_multi) */
 enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2, GH_CELL_PRISM_COMP = 3, GH_CELL_TESSEROID_COMP = 4,
        GH_CELL_PRISM_JOINT = 5, GH_CELL_PRISM_MULTI = 6, GH_CELL_PRISM_MVI = 7, GH_CELL_PRISM_MVI_DATA = 8 };
-enum { GH_CELL_TESS_MVI_DATA = 9 };
+enum { GH_CELL_TESS_MVI_DATA = 9, GH_CELL_TESSEROID_MULTI = 10 };
 /* The magnetic data components of prisms, for gh_set_cells_mvi_data and gh_b_result: the total-field anomaly along
  * the regional field, and the north, east and down components of the anomalous induction (gravmag/prism.py:665-870),
  * all in uT per A/m (CM * T2NT) */
@@ -312,7 +314,43 @@ int gh_joint_layout(const gh_ctx *ctx, int *workgroups_per_block, int *epilogue_
  * matrix-free, the shift-invariant store, the wavelet compressor, gh_batch_*, gh_shard_init* and gh_upload_G; the
  * resident chain kernel and the folded store are never chosen. */
 int gh_set_cells_multi(gh_ctx *ctx, const double *bounds6, int ncomp, const int *comps, const double *weights);
-/* The blocks of a GH_CELL_PRISM_MULTI or GH_CELL_PRISM_MVI_DATA context (comps: GH_COMP_* or GH_BCOMP_* values; every
+/* Several gravity fields of ONE density model of TESSEROIDS inverted together (GH_CELL_TESSEROID_MULTI): the spherical
+ * form of gh_set_cells_multi -- satellite gradiometry, gzz, gxx, gyy, gxz ... measured together at orbit height.
+ * ncomp distinct components comps[b] (GH_COMP_*, gz included) of the same M tesseroids (w,e,s,n,top,bottom) at the same
+ * N / ncomp observation points, component b assembled at the distance-size ratio ratios[b] > 0 and weighted by
+ * weights[b] > 0.  The contract is gh_set_cells_multi's: the context's N is the stacked length, observation-space
+ * vectors are component-major; call it on a fresh context, BEFORE gh_set_obs, which then takes the N / ncomp points.
+ * Errors: those of gh_set_cells_multi and of gh_set_cells_tess (GH_ERR_ARG for a ratio <= 0 or a cell without w <= e,
+ * s <= n, top >= bottom).
+ * The dense store (the default; any geometry):
+ *   gh_build_G   runs the field's assembly kernel once per block into the one store: rows [b N/ncomp, (b + 1) N/ncomp)
+ *                are bit for bit the rows of a gh_set_cells_tess(comps[b], ratios[b]) context (GH_COMP_GZ: the bits
+ *                of kind 1).  The error cells and leaves gh_kernel_stats reports are summed over the blocks;
+ *                GH_ERR_OVERFLOW as for one component.
+ *   gh_weight, gh_set_data, the data term with one mean per block on both sides, gh_multi_info, the fused sweep and
+ *                the limit of 16384 stacked rows: as gh_set_cells_multi.
+ * The shift-invariant store (gh_set_shift_invariant(ctx, 1) before gh_build_G, before or after this call; no row limit,
+ * G never stored) on the geometry that store asks for:
+ *   the component block is one more coordinate of the observation class: a class is (block, latitude, height), the
+ *   stacked observation b N/ncomp + i has the class of point i in block b and i's longitude slot.  One launch fills the
+ *   table for all (cell row, class, shift), every entry by its class's field at its class's ratio, scaled as
+ *   gh_set_cells_tess scales it and times weights[b]; it agrees with the dense store to 1e-10 of a block's largest
+ *   entry.  Only the streamed harmonic form serves this kind, one launch per phase, whatever the environment switches
+ *   say (gh_shift_invariant_harmonic: 2); more than 1024 or fewer than 2 longitudes per cell row are refused.  On a
+ *   grid symmetric about the equator a row of the transformed table stands for a mirrored pair of cell rows, and the
+ *   entry of the partner is the sign of the class times the entry: -1 for gx, gxy, gxz (the observation's north axis
+ *   flips), +1 for the potential, geoid, gy, gz, gxx, gyy, gyz, gzz (GRAVHMC_LW_MIRROR=0: no pairing).  The means are
+ *   removed per block, from the classes' sums in index order; gh_weight gives the dense store's Wm (column norms of
+ *   Wb A) from the table; gh_multi_info as on the dense store.
+ * With comps = {GH_COMP_GZ} and weights = {1} the call IS gh_set_cells(kind 1, ratios[0]): the context is a
+ * GH_CELL_TESSEROID one and computes exactly what that call's context computes (one block, one mean; gh_multi_info then
+ * refuses), on the dense store and on the table.
+ * Refused with GH_ERR_UNSUPPORTED, each naming the tesseroid multi-component store: matrix-free without the table,
+ * the wavelet compressor, gh_batch_*, gh_bscg_run, gh_shard_init*, gh_upload_G; grav_fix must be null; the resident
+ * chain kernel, the folded store and the persistent harmonic pass are never chosen. */
+int gh_set_cells_tess_multi(gh_ctx *ctx, const double *bounds6, int ncomp, const int *comps, const double *ratios,
+                            const double *weights);
+/* The blocks of a GH_CELL_PRISM_MULTI, GH_CELL_TESSEROID_MULTI or GH_CELL_PRISM_MVI_DATA context (comps: GH_COMP_* or GH_BCOMP_* values; every
  * pointer may be null; arrays of GH_MULTI_MAX hold them):
  * their number, components and weights, the mean of each block of the LAST evaluation's prediction Aw mw
  * (gh_misfit_and_grad, or the chain's last step; zeros before the first), and the mean gh_set_data removed from
