@@ -53,6 +53,7 @@ PROTOTYPES = {
     "gh_set_cells_mvi_data": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), _dp]),
     "gh_b_result": (C.c_int, [_ctx, C.c_int, _dp, _dp]),
     "gh_set_cells_tess_mag": (C.c_int, [_ctx, _dp, C.c_double, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
+    "gh_set_cells_tess_mag_table": (C.c_int, [_ctx, _dp, C.c_double, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
     "gh_tess_b_result": (C.c_int, [_ctx, C.c_int, _dp, _dp]),
     "gh_set_amplitude": (C.c_int, [_ctx, C.c_double, C.c_double, C.c_double]),
     "gh_amplitude_eval": (C.c_int, [_ctx, _dp, C.POINTER(C.c_double), _dp, _dp]),

@@ -374,8 +374,10 @@ int gh_set_cells_mvi_data(gh_ctx *c, const double *bounds6, double fx, double fy
     return GH_OK;
 }
 
-int gh_set_cells_tess_mag(gh_ctx *c, const double *bounds6, double ratio, int ncomp, const int *comps,
-                          const double *weights, const double *fdir)
+// gh_set_cells_tess_mag, and with `table` gh_set_cells_tess_mag_table: the same context, asked onto the shift-invariant
+// table in the same call (no limit on the stacked rows)
+static int set_cells_tess_mag(gh_ctx *c, const double *bounds6, double ratio, int ncomp, const int *comps,
+                              const double *weights, const double *fdir, bool table)
 {
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: null pointer");
     if (ncomp < 1 || ncomp > GH_BCOMP_MAX)
@@ -417,15 +419,19 @@ int gh_set_cells_tess_mag(gh_ctx *c, const double *bounds6, double ratio, int nc
     }
     if (c->joint || c->mvi || c->mc.n > 0 || c->have_obs || c->have_cells || c->have_G || c->slab)
         return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: call it first on a fresh context (before gh_set_obs)");
+    // (a context of unknown kind cannot be asked onto the table: the table comes after this call, or with it)
     if (c->mf || c->ls)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_mag: the tesseroid magnetization store is dense only (no "
-                                           "matrix-free mode, no shift-invariant store)");
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_mag: the tesseroid magnetization store has no matrix-free "
+                                           "mode, and takes the shift-invariant table after this call "
+                                           "(gh_set_shift_invariant) or with it (gh_set_cells_tess_mag_table)");
     if (c->sh.kind != 0)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_mag: the tesseroid magnetization store is not sharded");
-    if (c->N > 16384)
+    if (c->N > 16384 && !table)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_mag: %d components x %lld observations = %lld rows: the "
-                                           "tesseroid magnetization store takes at most 16384 (it runs on the fused "
-                                           "sweep: no row panels, no team sweep)", ncomp, (long long)Nb, (long long)c->N);
+                                           "dense form of the tesseroid magnetization store takes at most 16384 (it runs "
+                                           "on the fused sweep: no row panels, no team sweep); the shift-invariant table "
+                                           "has no such limit (gh_set_cells_tess_mag_table)", ncomp, (long long)Nb,
+                    (long long)c->N);
     HIPCHK(c, hipSetDevice(c->device));
     TRY(dalloc(c, &c->bounds, (size_t)m * 6));
     TRY(h2d(c, c->bounds, bounds6, (size_t)m * 6));
@@ -445,7 +451,19 @@ int gh_set_cells_tess_mag(gh_ctx *c, const double *bounds6, double ratio, int nc
     c->comp = GH_COMP_GZ;
     c->ratio = ratio;
     c->have_cells = true;
-    return GH_OK;
+    return table ? gh_set_shift_invariant(c, 1) : GH_OK;
+}
+
+int gh_set_cells_tess_mag(gh_ctx *c, const double *bounds6, double ratio, int ncomp, const int *comps,
+                          const double *weights, const double *fdir)
+{
+    return set_cells_tess_mag(c, bounds6, ratio, ncomp, comps, weights, fdir, false);
+}
+
+int gh_set_cells_tess_mag_table(gh_ctx *c, const double *bounds6, double ratio, int ncomp, const int *comps,
+                                const double *weights, const double *fdir)
+{
+    return set_cells_tess_mag(c, bounds6, ratio, ncomp, comps, weights, fdir, true);
 }
 
 
@@ -771,6 +789,9 @@ static int dense_single_chain_refuse(gh_ctx *c, const char *who)
     if (c && c->joint)
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the joint gravity-magnetic kernel (dense, single chain)",
                     who);
+    if (c && tess_mag_store(c))
+        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the tesseroid magnetization store (dense or "
+                                           "shift-invariant, single chain)", who);
     if (c && vector_data_store(c))
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on %s (dense, single chain)", who, vector_data_store_name(c));
     if (c && c->mc.n > 0)
@@ -987,8 +1008,11 @@ int gh_set_matrix_free(gh_ctx *c, int enable)
 int gh_set_shift_invariant(gh_ctx *c, int enable)
 {
     if (!c) return GH_ERR_ARG;
-    // (the tesseroid multi-component store is the one store of row blocks that has the table)
-    if (enable && !(c && tess_multi_store(c))) TRY(dense_single_chain_refuse(c, "gh_set_shift_invariant"));
+    // (the tesseroid multi-component store and the tesseroid magnetization store are the stores of row blocks that
+    // have the table; the prism forms of the vector stores keep refusing)
+    // (a magnetization store that has been built is the dense store: it refuses as it always did)
+    if (enable && !(c && (tess_multi_store(c) || (tess_mag_store(c) && !c->have_G && !c->slab))))
+        TRY(dense_single_chain_refuse(c, "gh_set_shift_invariant"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_shift_invariant: call before gh_build_G");
     // (the store is a flavour of the matrix-free mode -- G is never stored -- so enabling it sets c->mf;
     // disabling it puts c->mf back to what gh_set_matrix_free last asked for)
@@ -1128,6 +1152,9 @@ int gh_build_G(gh_ctx *c)
         if (tess_multi_store(c) && !c->ls)
             return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: the tesseroid multi-component store has no matrix-free mode "
                                                "(dense, or the shift-invariant store)");
+        if (tess_mag_store(c) && !c->ls)
+            return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: the tesseroid magnetization store has no matrix-free mode "
+                                               "(dense, or the shift-invariant store)");
         c->mf_fused = c->ld <= 16384 && env_int("GRAVHMC_MF_FUSED", 1) != 0;
         // (tesseroid components: the two-pass form, with the entry evaluated inside each pass -- no fused KIND;
         // the near-field table and the cell-constant fast leaf are gz's)
@@ -1169,6 +1196,11 @@ int gh_build_G(gh_ctx *c)
                                            "sweep: no row panels, no team sweep); the shift-invariant store has no such "
                                            "limit (gh_set_shift_invariant)", c->mc.n, (long long)(c->N / c->mc.n),
                     (long long)c->N);
+    if (tess_mag_store(c) && c->N > 16384)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %d components x %lld observations = %lld rows: the dense form of "
+                                           "the tesseroid magnetization store takes at most 16384; the shift-invariant "
+                                           "table has no such limit (gh_set_cells_tess_mag_table)", c->mc.n,
+                    (long long)(c->N / c->mc.n), (long long)c->N);
     if (!c->dense_ok)
         return fail(c, GH_ERR_UNSUPPORTED,
                     "N = %lld: more than 16384 observations per device: shard the observations or use "

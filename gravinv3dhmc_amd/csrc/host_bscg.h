@@ -11,7 +11,7 @@ static int bscg_refuse(gh_ctx *c, int B, int maxk)
     if (tess_multi_store(c))
         what = "the tesseroid multi-component store";
     else if (c->ls)
-        what = "a shift-invariant store";
+        what = tess_mag_store(c) ? "the tesseroid magnetization store on the shift-invariant table" : "a shift-invariant store";
     else if (c->mf)
         what = "a matrix-free context";
     else if (c->sh.kind != 0)

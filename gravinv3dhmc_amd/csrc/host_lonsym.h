@@ -26,6 +26,10 @@ struct LonSymHost {
     // entries take under the north-south mirror (-1 for gx, gxy, gxz)
     bool multi = false;
     double *asgn = nullptr;
+    // the tesseroid magnetization store: the classes as above (data block, latitude, height), and the three axis blocks of
+    // the columns as a coordinate of the cell row (row a nc1 + r); rsgn: the sign an item's mirrored row takes (-1: axis N)
+    bool mag = false;
+    double *rsgn = nullptr;
     int nfp = 0, wbreak = 0;               // pitch of a row of T^ / R^ / D^ in the streamed form (complex entries)
     int wgrid = 0, wparts = 0, wrows = 0;  // workgroups of the sweep; parts of the forward product, cell rows per part
     ghk::d2 *Xhat = nullptr;
@@ -68,8 +72,10 @@ static lonsym_fn_t lonsym_fn(int items, int W, int T)
 }
 
 typedef void (*lonsymw_fn_t)(LonWideGeom, SweepArgs, const double *);
-static lonsymw_fn_t lonsymw_sweep_fn(int nf, bool sgn = false)
+static lonsymw_fn_t lonsymw_sweep_fn(int nf, bool sgn = false, bool rsgn = false)
 {
+    if (rsgn)
+        return nf <= LW_THREADS ? lonsymw_sweep_kernel<1, true, true> : nf <= 2 * LW_THREADS ? lonsymw_sweep_kernel<2, true, true> : lonsymw_sweep_kernel<3, true, true>;
     if (sgn)
         return nf <= LW_THREADS ? lonsymw_sweep_kernel<1, true> : nf <= 2 * LW_THREADS ? lonsymw_sweep_kernel<2, true> : lonsymw_sweep_kernel<3, true>;
     return nf <= LW_THREADS ? lonsymw_sweep_kernel<1> : nf <= 2 * LW_THREADS ? lonsymw_sweep_kernel<2> : lonsymw_sweep_kernel<3>;
@@ -110,9 +116,11 @@ static int lonsym_build(gh_ctx *c)
 {
     LonSymHost &h = *c->ls;
     h.on = false;
+    // (the tesseroid magnetization store names itself in front of the reason)
+    h.mag = tess_mag_store(c);
     auto no = [&](const char *why) {
         h.why = why;
-        return fail(c, GH_ERR_UNSUPPORTED, "shift-invariant store: %s", why);
+        return fail(c, GH_ERR_UNSUPPORTED, h.mag ? "shift-invariant store: the tesseroid magnetization store: %s" : "shift-invariant store: %s", why);
     };
     // (a table of a component other than gz would need the sign of the north-south mirror: gx, gxy and gxz
     // change sign under it)
@@ -122,10 +130,14 @@ static int lonsym_build(gh_ctx *c)
     // The tesseroid multi-component store: the component block is one more coordinate of the class.  The geometry
     // test runs on the N / nb observation points; the stacked observation b P + i then gets the class b na + a_of[i]
     // and the longitude slot of i.
-    h.multi = tess_multi_store(c);
+    // The tesseroid magnetization store: its data blocks likewise; the three axis blocks of its columns are a
+    // coordinate of the cell row.  The geometry test runs on the M / 3 cells; column a m + r n + k is then cell row
+    // a nc1 + r, longitude k, of a table of 3 nc1 rows.  (The prism forms of the vector stores never get here:
+    // gh_set_shift_invariant refuses them.)
+    h.multi = tess_multi_store(c) || h.mag;
     if (c->cell_kind != GH_CELL_TESSEROID && !h.multi) return no("tesseroid cells only");
-    const int nb = h.multi ? c->mc.n : 1;
-    const int64_t M = c->M, N = c->N / nb;
+    const int nb = h.multi ? c->mc.n : 1, nax = h.mag ? 3 : 1;
+    const int64_t M = c->M / nax, N = c->N / nb;
     std::vector<double> b((size_t)M * 6), lon((size_t)N), lat((size_t)N), hh((size_t)N);
     HIPCHK(c, hipMemcpyAsync(b.data(), c->bounds, sizeof(double) * b.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(lon.data(), c->obs[0], sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, c->stream));
@@ -189,7 +201,7 @@ static int lonsym_build(gh_ctx *c)
         }
     }
     const int64_t Ns = N * nb;  // the stacked observations
-    const int64_t na = na1 * nb, nc = M / n;
+    const int64_t na = na1 * nb, nc1 = M / n, nc = nax * nc1;  // (nc1: rows of cells, nc: rows of the table)
     h.n = (int)n;
     h.na = (int)na;
     h.nc = (int)nc;
@@ -216,37 +228,71 @@ static int lonsym_build(gh_ctx *c)
     // mirror and the classes per block are written once, there)
     if (h.multi) {
         h.direct_ok = false;
-        if (n > LW_NMAX) return no("the tesseroid multi-component store runs on the streamed harmonic form: more than 1024 longitudes per cell row");
-        if (n < 2) return no("the tesseroid multi-component store runs on the streamed harmonic form: fewer than 2 longitudes per cell row");
+        if (n > LW_NMAX)
+            return no(h.mag ? "it runs on the streamed harmonic form: more than 1024 longitudes per cell row"
+                            : "the tesseroid multi-component store runs on the streamed harmonic form: more than 1024 longitudes per cell row");
+        if (n < 2)
+            return no(h.mag ? "it runs on the streamed harmonic form: fewer than 2 longitudes per cell row"
+                            : "the tesseroid multi-component store runs on the streamed harmonic form: fewer than 2 longitudes per cell row");
     }
     const bool wide_can = n <= LW_NMAX && n >= 2 && (h.multi || env_int("GRAVHMC_LONSYM_WIDE", 1) != 0);
     if (!h.direct_ok && !wide_can) return no(direct_why);
     if ((int64_t)na * n > 0x7fffffffLL / 4) return no("more than 2^29 (class, longitude) slots");
+    // The magnetization store's total field projects on the direction at the observation: a class has ONE table, so
+    // the direction must be the same, bit for bit, at all its points.  sfd: the direction of every synthetic point
+    // (class, shift) of one data block.
+    bool mag_tf = false;
+    for (int bb = 0; bb < nb && h.mag; ++bb) mag_tf = mag_tf || c->mc.comp[bb] == GH_BCOMP_TF;
+    std::vector<double> sfd;
+    if (mag_tf) {
+        std::vector<double> fd((size_t)N * 3), cf((size_t)na1 * 3);
+        std::vector<char> seen((size_t)na1, 0);
+        HIPCHK(c, hipMemcpyAsync(fd.data(), c->tmag_fdir, sizeof(double) * fd.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int64_t i = 0; i < N; ++i) {
+            const size_t a = (size_t)a_of[(size_t)i];
+            if (!seen[a]) {
+                seen[a] = 1;
+                memcpy(&cf[a * 3], &fd[(size_t)i * 3], 3 * sizeof(double));
+            } else if (memcmp(&cf[a * 3], &fd[(size_t)i * 3], 3 * sizeof(double)) != 0) {
+                return no("the total field's direction varies within a class of observations (same latitude and height)");
+            }
+        }
+        sfd.resize((size_t)(na1 * n) * 3);
+        for (int64_t a = 0; a < na1; ++a)
+            for (int64_t d = 0; d < n; ++d) memcpy(&sfd[(size_t)(a * n + d) * 3], &cf[(size_t)a * 3], 3 * sizeof(double));
+    }
     // the table: every class at every shift against the cells of longitude index 0 (reference engine)
     const int64_t Np = na * n;
     h.ldT = (Np + 15) / 16 * 16;
-    std::vector<double> so((size_t)Np * 3), sb((size_t)nc * 6);
+    std::vector<double> so((size_t)Np * 3), sb((size_t)nc1 * 6);
     for (int64_t a = 0; a < na; ++a)
         for (int64_t d = 0; d < n; ++d) {
             so[(size_t)(a * n + d)] = lon_ref + (double)d * dlon;
             so[(size_t)(Np + a * n + d)] = cl_lat[(size_t)a];
             so[(size_t)(2 * Np + a * n + d)] = cl_h[(size_t)a];
         }
-    for (int64_t cc = 0; cc < nc; ++cc) memcpy(&sb[(size_t)cc * 6], &b[(size_t)(cc * n) * 6], 6 * sizeof(double));
+    for (int64_t cc = 0; cc < nc1; ++cc) memcpy(&sb[(size_t)cc * 6], &b[(size_t)(cc * n) * 6], 6 * sizeof(double));
     double *d_so = nullptr, *d_sb = nullptr, *conv = nullptr;
     int *err_cell = nullptr;
     TessStats *stats = nullptr;
     TRY(dalloc(c, &h.T, (size_t)h.ldT * (size_t)nc, false));
-    // (five temporaries of the build: released on every way out of this block)
+    // (the temporaries of the build: released on every way out of this block; the magnetization store's cell frames
+    // and class directions are the last two)
     struct Tmp {
-        void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        void *p[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         ~Tmp() { for (void *q : p) if (q) (void)hipFree(q); }
     } tmp;
     HIPCHK(c, hipMalloc(&tmp.p[0], sizeof(double) * so.size()));
     HIPCHK(c, hipMalloc(&tmp.p[1], sizeof(double) * sb.size()));
-    HIPCHK(c, hipMalloc(&tmp.p[2], sizeof(double) * 4 * (size_t)Np));
+    HIPCHK(c, hipMalloc(&tmp.p[2], sizeof(double) * (h.mag ? 6 : 4) * (size_t)Np));
     HIPCHK(c, hipMalloc(&tmp.p[3], sizeof(int) * (size_t)nc));
     HIPCHK(c, hipMalloc(&tmp.p[4], sizeof(TessStats)));
+    if (h.mag) HIPCHK(c, hipMalloc(&tmp.p[5], sizeof(double) * TESS_MAG_FRAME * (size_t)nc1));
+    if (mag_tf) {
+        HIPCHK(c, hipMalloc(&tmp.p[6], sizeof(double) * sfd.size()));
+        HIPCHK(c, hipMemcpyAsync(tmp.p[6], sfd.data(), sizeof(double) * sfd.size(), hipMemcpyHostToDevice, c->stream));
+    }
     d_so = static_cast<double *>(tmp.p[0]);
     d_sb = static_cast<double *>(tmp.p[1]);
     conv = static_cast<double *>(tmp.p[2]);
@@ -256,10 +302,34 @@ static int lonsym_build(gh_ctx *c)
     HIPCHK(c, hipMemcpyAsync(d_sb, sb.data(), sizeof(double) * sb.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(err_cell, 0, sizeof(int) * (size_t)nc, c->stream));
     HIPCHK(c, hipMemsetAsync(stats, 0, sizeof(TessStats), c->stream));
-    tess_convert_kernel<<<dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, c->stream>>>(
-        d_so, d_so + Np, d_so + 2 * Np, Np, conv, conv + Np, conv + 2 * Np, conv + 3 * Np);
+    if (h.mag)
+        tess_convert_kernel<<<dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, c->stream>>>(
+            d_so, d_so + Np, d_so + 2 * Np, Np, conv, conv + Np, conv + 2 * Np, conv + 3 * Np, conv + 4 * Np, conv + 5 * Np);
+    else
+        tess_convert_kernel<<<dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, c->stream>>>(
+            d_so, d_so + Np, d_so + 2 * Np, Np, conv, conv + Np, conv + 2 * Np, conv + 3 * Np);
     const int64_t total = h.ldT * nc;
-    if (h.multi) {
+    if (h.mag) {
+        // ONE launch of the dense store's body over the na1 n synthetic points (class, shift) of a data block -- the
+        // first na1 n of the Np converted points -- and the nc1 cells of longitude index 0: one traversal of the
+        // subdivision per (point, cell), the entry of every (data block, axis block) from it, times the block's
+        // data weight.  The store's layout with ld = ldT is the table's; the threads behind a column's points zero
+        // the ldT - Np padding rows.
+        const int64_t Np1 = na1 * n, Lr = Np1 + (h.ldT - Np);
+        BComps bc{};
+        BWeights bw{};
+        bc.n = nb;
+        for (int bb = 0; bb < nb; ++bb) {
+            bc.comp[bb] = c->mc.comp[bb];
+            bw.w[bb] = c->mc.w[bb];
+        }
+        double *frame = static_cast<double *>(tmp.p[5]);
+        tess_mag_cellframe_kernel<<<dim3((unsigned)((nc1 + 255) / 256)), dim3(256), 0, c->stream>>>(d_sb, nc1, frame);
+        const TessMagObs o{conv, conv + Np, conv + 2 * Np, conv + 3 * Np, conv + 4 * Np, conv + 5 * Np};
+        tess_mag_table_kernel<<<dim3((unsigned)std::min<int64_t>((Lr * nc1 + 63) / 64, 1 << 24)), dim3(64), 0, c->stream>>>(
+            o, d_sb, frame, mag_tf ? static_cast<const double *>(tmp.p[6]) : nullptr, Np1, nc1, h.ldT, c->ratio, bc, bw, h.T,
+            err_cell, stats);
+    } else if (h.multi) {
         // every class by its own field at its own ratio, times its block's data weight: ONE launch
         TessBlocks tb{};
         tb.n = nb;
@@ -283,6 +353,7 @@ static int lonsym_build(gh_ctx *c)
     if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
     // a cell of longitude index 0 that could not be divided further stands for its whole row of n cells:
     // the count gh_kernel_stats reports is the dense build's (the reference's warning, potential.py:134)
+    // (magnetization store: the nc1 cells' codes, once per cell whatever the axis; the rest of herr is zero)
     for (int v : herr)
         if (v != 0) c->warn_cells += n;
     c->leaves = (int64_t)hs.leaves;
@@ -376,7 +447,9 @@ static int lonsym_build(gh_ctx *c)
         // -- half the table, half the bytes per step.  GRAVHMC_LW_MIRROR=0: off.
         std::vector<int> itc, itc2, amirv((size_t)na, -1);
         h.wmirror = false;
-        if (env_int("GRAVHMC_LW_MIRROR", 1) != 0) {
+        // (the magnetization store's total field projects on a direction that the mirror does not simply flip: with
+        // "tf" among the data there is no pairing)
+        if (env_int("GRAVHMC_LW_MIRROR", 1) != 0 && !mag_tf) {
             auto near = [](double x, double y) { return std::fabs(x - y) <= 1e-9 * std::max(1.0, std::max(std::fabs(x), std::fabs(y))); };
             bool ok = true;
             for (int64_t a = 0; a < na && ok; ++a) {
@@ -389,10 +462,11 @@ static int lonsym_build(gh_ctx *c)
                 ok = amirv[(size_t)a] >= 0;
             }
             for (int64_t a = 0; a < na && ok; ++a) ok = amirv[(size_t)amirv[(size_t)a]] == (int)a;
-            std::vector<int> rmir((size_t)nc, -1);
-            for (int64_t cc = 0; cc < nc && ok; ++cc) {
+            // (rows of cells; the table row a nc1 + r of the magnetization store pairs with a nc1 + rmir[r])
+            std::vector<int> rmir((size_t)nc1, -1);
+            for (int64_t cc = 0; cc < nc1 && ok; ++cc) {
                 const double *q = &sb[(size_t)cc * 6];
-                for (int64_t c2 = 0; c2 < nc; ++c2) {
+                for (int64_t c2 = 0; c2 < nc1; ++c2) {
                     const double *r2 = &sb[(size_t)c2 * 6];
                     if (near(r2[2], -q[3]) && near(r2[3], -q[2]) && near(r2[4], q[4]) && near(r2[5], q[5])) {
                         rmir[(size_t)cc] = (int)c2;
@@ -401,10 +475,10 @@ static int lonsym_build(gh_ctx *c)
                 }
                 ok = rmir[(size_t)cc] >= 0;
             }
-            for (int64_t cc = 0; cc < nc && ok; ++cc) ok = rmir[(size_t)rmir[(size_t)cc]] == (int)cc;
+            for (int64_t cc = 0; cc < nc1 && ok; ++cc) ok = rmir[(size_t)rmir[(size_t)cc]] == (int)cc;
             if (ok) {
                 for (int64_t cc = 0; cc < nc; ++cc) {
-                    const int m2 = rmir[(size_t)cc];
+                    const int m2 = (int)(cc / nc1 * nc1) + rmir[(size_t)(cc % nc1)];
                     if (m2 < cc) continue;  // (listed with its partner)
                     itc.push_back((int)cc);
                     itc2.push_back(m2 == cc ? -1 : m2);
@@ -416,7 +490,7 @@ static int lonsym_build(gh_ctx *c)
         const int64_t ni = h.witems;
         // (GRAVHMC_LW_LDS_PAD: extra LDS per workgroup in KB -- a diagnostic that lowers the workgroups per CU)
         h.wlds = lonsymw_lds_doubles((int)n, h.nf) * sizeof(double) + (size_t)env_int("GRAVHMC_LW_LDS_PAD", 0) * 1024;
-        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(lonsymw_sweep_fn(h.nf, h.multi)), h.wlds));
+        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(lonsymw_sweep_fn(h.nf, h.multi, h.mag)), h.wlds));
         h.wgrid = (int)std::min<int64_t>(ni, (int64_t)c->cus * 8);
         // parts of the forward product: ~8 waves per SIMD over the chip, at least 8 rows of T^ per part
         const int64_t waves_row = ((int64_t)na * h.nfp + 63) / 64;
@@ -439,13 +513,23 @@ static int lonsym_build(gh_ctx *c)
             if (h.multi) {
                 // gx, gxy, gxz: odd in the observation's north axis, which the mirror flips
                 std::vector<double> sg((size_t)na);
+                // (magnetization store: bx, along the same axis; by and bz keep their sign)
                 for (int64_t a = 0; a < na; ++a) {
                     const int comp = c->mc.comp[a / na1];
-                    sg[(size_t)a] = (comp == GH_COMP_GX || comp == GH_COMP_GXY || comp == GH_COMP_GXZ) ? -1.0 : 1.0;
+                    sg[(size_t)a] = h.mag ? (comp == GH_BCOMP_BX ? -1.0 : 1.0)
+                                          : (comp == GH_COMP_GX || comp == GH_COMP_GXY || comp == GH_COMP_GXZ) ? -1.0 : 1.0;
                 }
                 TRY(dalloc(c, &h.asgn, sg.size(), false));
                 HIPCHK(c, hipMemcpyAsync(h.asgn, sg.data(), sizeof(double) * sg.size(), hipMemcpyHostToDevice, c->stream));
                 HIPCHK(c, hipStreamSynchronize(c->stream));  // (sg leaves scope)
+            }
+            if (h.mag) {
+                // the cell's north axis flips too: the items of the axis block N (table rows below nc1) take -1
+                std::vector<double> rs(itc.size());
+                for (size_t p = 0; p < itc.size(); ++p) rs[p] = itc[p] < nc1 ? -1.0 : 1.0;
+                TRY(dalloc(c, &h.rsgn, rs.size(), false));
+                HIPCHK(c, hipMemcpyAsync(h.rsgn, rs.data(), sizeof(double) * rs.size(), hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));  // (rs leaves scope)
             }
         }
         lonsymh_twiddle_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>((int)n, h.tw);
@@ -476,6 +560,7 @@ static LonWideGeom lonsymw_geom(const gh_ctx *c)
     g.item_c2 = h.wmirror ? h.item_c2 : nullptr;
     g.amir = h.wmirror ? h.amir : nullptr;
     g.asgn = h.wmirror && h.multi ? h.asgn : nullptr;
+    g.rsgn = h.wmirror && h.mag ? h.rsgn : nullptr;
     g.parts = h.wparts;
     g.rows_per_part = h.wrows;
     g.That = h.That;
@@ -554,12 +639,15 @@ static int launch_lonsym(gh_ctx *c, SweepArgs &a)
         // transforms behind the row-parallel pass
         const LonWideGeom g = lonsymw_geom(c);
         if (a.mode & SW_ADJ) lonsymw_rhat_kernel<<<dim3((unsigned)h.na), dim3(LW_THREADS), 0, c->stream>>>(g, a.r);
-        hipLaunchKernelGGL(lonsymw_sweep_fn(h.nf, h.multi), dim3((unsigned)h.wgrid), dim3(LW_THREADS), h.wlds, c->stream, g, a,
+        hipLaunchKernelGGL(lonsymw_sweep_fn(h.nf, h.multi, h.mag), dim3((unsigned)h.wgrid), dim3(LW_THREADS), h.wlds, c->stream, g, a,
                            c->weighted ? c->wm : nullptr);
         if (a.mode & SW_FWD) {
             const int64_t tot = (int64_t)h.na * h.nfp;
             const dim3 fgrid((unsigned)((tot + LW_THREADS - 1) / LW_THREADS), (unsigned)h.wparts);
-            switch (h.wfwd) {  // (GRAVHMC_LW_FWD: rows in flight per thread / non-temporal loads; tuning, same results)
+            // (GRAVHMC_LW_FWD: rows in flight per thread / non-temporal loads; tuning, same results.  The magnetization
+            // store: the mirrored row's X^ takes the item's row sign, in the default variant alone)
+            switch (h.mag ? -1 : h.wfwd) {
+            case -1: lonsymw_forward_kernel<8, false, true><<<fgrid, dim3(LW_THREADS), 0, c->stream>>>(g); break;
             case 1: lonsymw_forward_kernel<8, true><<<fgrid, dim3(LW_THREADS), 0, c->stream>>>(g); break;
             case 2: lonsymw_forward_kernel<16, false><<<fgrid, dim3(LW_THREADS), 0, c->stream>>>(g); break;
             case 3: lonsymw_forward_kernel<16, true><<<fgrid, dim3(LW_THREADS), 0, c->stream>>>(g); break;

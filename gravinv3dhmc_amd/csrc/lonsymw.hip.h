@@ -20,6 +20,10 @@
 // height), so nothing changes but the mirror -- gx, gxy and gxz change sign under it (SGN instantiations, LonWideGeom::asgn).
 // Nothing assumes T[d] = T[n - d]: T^ is the full complex transform of all n shifts, so fields odd in the longitude
 // difference (gy, gxy, gyz) need nothing special.
+// The tesseroid magnetization store (gh_set_cells_tess_mag) runs here as well: its data blocks are a coordinate of the class
+// as above, and the three axis blocks of its columns (m_N, m_E, m_D of every cell) are a coordinate of the CELL ROW -- row
+// a nc1 + r, so j = c n + k addresses the property-major model as it is.  Under the mirror the cell's north axis flips as
+// the observation's does: the entry of the mirrored pair is asgn[class] rsgn[item] K (RSGN instantiations, LonWideGeom::rsgn).
 // Reference arithmetic: gravmag/_tesseroid_numba.py:207-222 (cos(lon - lon')), gravmag/tesseroid.py:189-232,
 // inversion/potential.py:698,708, inversion/hmc.py:114-152; geometry family example/global/SetPMTS.txt.
 #pragma once
@@ -49,6 +53,10 @@ struct LonWideGeom {
     // entry of the mirrored pair is asgn[a] K, -1 for the classes of gx, gxy and gxz -- the observation's north axis
     // flips under the mirror -- and +1 for every other field's.  Read by the SGN instantiations only; nullptr otherwise.
     const double *asgn;
+    // Row sign of the mirror (the tesseroid magnetization store): rsgn[p] = -1 for the items of the axis block N -- the
+    // cell's north axis flips under the mirror --, +1 for those of E and D; the mirrored row of item p takes it on top of
+    // the class's sign.  Read by the RSGN instantiations only, and only for items that have a partner; nullptr otherwise.
+    const double *rsgn;
 };
 
 constexpr int LW_THREADS = 256;
@@ -151,7 +159,8 @@ __global__ void __launch_bounds__(LW_THREADS) lonsymw_rhat_kernel(LonWideGeom g,
 // while the row's slab of T^ streams -- with NP = 3 for every grid the kernel took 189 registers (two waves per SIMD);
 // NP = 1 (n <= 510): 127, four waves per SIMD = four workgroups per CU.
 // SGN: the mirrored class's R^ takes the class's sign (LonWideGeom::asgn); without it the code is what it was.
-template <int NP, bool SGN>
+// RSGN: the mirrored row's sum takes the item's row sign (LonWideGeom::rsgn) once, behind the loop over the classes.
+template <int NP, bool SGN, bool RSGN>
 __device__ __forceinline__ void lonsymw_sweep_body(const LonWideGeom &g, const SweepArgs &a, const double *__restrict__ wm)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -266,6 +275,11 @@ __device__ __forceinline__ void lonsymw_sweep_body(const LonWideGeom &g, const S
                         }
                     }
                 }
+                if (RSGN && c2 >= 0) {
+                    const double rs = g.rsgn[p];
+                    acc2.x *= rs;
+                    acc2.y *= rs;
+                }
                 if (fv) {
                     Gp[wv * nf + f] = acc;
                     Gp[(4 + wv) * nf + f] = acc2;
@@ -363,16 +377,17 @@ __device__ __forceinline__ void lonsymw_sweep_body(const LonWideGeom &g, const S
     }
 }
 
-template <int NP, bool SGN = false>
+template <int NP, bool SGN = false, bool RSGN = false>
 __global__ void __launch_bounds__(LW_THREADS) lonsymw_sweep_kernel(LonWideGeom g, SweepArgs a, const double *__restrict__ wm)
 {
-    lonsymw_sweep_body<NP, SGN>(g, a, wm);
+    lonsymw_sweep_body<NP, SGN, RSGN>(g, a, wm);
 }
 
 // D^ partial of the items [part * rows_per_part, ...): thread e = a * nfp + f (one complex of a row of T^); an entry of a
 // mirrored pair of cell rows feeds two accumulators (plane 0: class a from the row itself, plane 1: the mirrored class from
-// the mirrored row).  UN rows in flight per thread; NT: non-temporal loads of T^.
-template <int UN, bool NT>
+// the mirrored row).  UN rows in flight per thread; NT: non-temporal loads of T^.  RSGN: X^ of the mirrored row takes the
+// item's row sign (LonWideGeom::rsgn).
+template <int UN, bool NT, bool RSGN = false>
 __global__ void __launch_bounds__(LW_THREADS) lonsymw_forward_kernel(LonWideGeom g)
 {
     const int nf = g.nf;
@@ -396,6 +411,11 @@ __global__ void __launch_bounds__(LW_THREADS) lonsymw_forward_kernel(LonWideGeom
             const int c1 = mir ? g.item_c[p + u] : p + u, c2 = mir ? g.item_c2[p + u] : -1;
             x[u] = g.Xhat[(int64_t)c1 * nf + f];
             x2[u] = c2 >= 0 ? g.Xhat[(int64_t)c2 * nf + f] : d2{0.0, 0.0};
+            if (RSGN && c2 >= 0) {
+                const double rs = g.rsgn[p + u];
+                x2[u].x *= rs;
+                x2[u].y *= rs;
+            }
         }
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
@@ -409,7 +429,12 @@ __global__ void __launch_bounds__(LW_THREADS) lonsymw_forward_kernel(LonWideGeom
         const d2 t = g.That[(int64_t)p * tot + ec];
         const int c1 = mir ? g.item_c[p] : p, c2 = mir ? g.item_c2[p] : -1;
         const d2 x = g.Xhat[(int64_t)c1 * nf + f];
-        const d2 x2 = c2 >= 0 ? g.Xhat[(int64_t)c2 * nf + f] : d2{0.0, 0.0};
+        d2 x2 = c2 >= 0 ? g.Xhat[(int64_t)c2 * nf + f] : d2{0.0, 0.0};
+        if (RSGN && c2 >= 0) {
+            const double rs = g.rsgn[p];
+            x2.x *= rs;
+            x2.y *= rs;
+        }
         acc.x += t.x * x.x - t.y * x.y;
         acc.y += t.x * x.y + t.y * x.x;
         acc2.x += t.x * x2.x - t.y * x2.y;

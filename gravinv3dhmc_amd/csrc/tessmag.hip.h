@@ -215,16 +215,23 @@ __device__ __forceinline__ void tess_mag_report(unsigned long long nleaf, bool o
     if ((threadIdx.x & 63) == 0) atomicAdd(&stats->leaves, tot);
 }
 
-// Dense assembly of the tesseroid magnetization store: columns [K_N | K_E | K_D] of m cells each, rows in bc.n
+// The data weights of the row blocks, for the shift-invariant table (which takes them when it is filled)
+struct BWeights {
+    double w[BCOMP_MAX];
+};
+
+// Assembly of the tesseroid magnetization store: columns [K_N | K_E | K_D] of m cells each, rows in bc.n
 // blocks of Nb observations (block b the data component bc.comp[b]), column-major with ld, as a
 // GH_CELL_PRISM_MVI_DATA store.  One thread per (obs, cell) pair, obs fastest, laid out as tess_comp_kernel: one
 // traversal, then the pair's entry of every (data block, axis block).  A tf block is fdir[3 l ..] . (bx, by, bz),
 // the direction taken at the observation.  Threads walk the Nb rows of a block, then the ld - n Nb padding rows
 // below the stack, which they zero.  Error codes per cell into err_cell, leaves and overflow into stats.
-__global__ void __launch_bounds__(64)
-tess_mag_kernel(TessMagObs o, const double *__restrict__ bounds6, const double *__restrict__ frame,
-                const double *__restrict__ fdir, int64_t Nb, int64_t m, int64_t ld, double ratio, BComps bc,
-                double *__restrict__ A, int *__restrict__ err_cell, TessStats *stats)
+// WEIGHTED: every entry of block b times bw.w[b] (the table); without it the dense store's code, bit for bit.
+template <bool WEIGHTED>
+__device__ __forceinline__ void
+tess_mag_body(const TessMagObs &o, const double *__restrict__ bounds6, const double *__restrict__ frame,
+              const double *__restrict__ fdir, int64_t Nb, int64_t m, int64_t ld, double ratio, const BComps &bc,
+              const BWeights &bw, double *__restrict__ A, int *__restrict__ err_cell, TessStats *stats)
 {
 #pragma clang fp contract(off)
     unsigned long long nleaf = 0;
@@ -263,12 +270,35 @@ tess_mag_kernel(TessMagObs o, const double *__restrict__ bounds6, const double *
                 if (q < bc.n) {
                     const int comp = bc.comp[q];
                     const double v = comp == BCOMP_TF ? tf : comp == BCOMP_BX ? bx : comp == BCOMP_BY ? by : bz;
-                    A[(a * m + c) * ld + q * Nb + l] = v * TF_SCALE;
+                    A[(a * m + c) * ld + q * Nb + l] = WEIGHTED ? (v * TF_SCALE) * bw.w[q] : v * TF_SCALE;
                 }
             }
         }
     }
     tess_mag_report(nleaf, overflow, stats);
+}
+
+// Dense assembly (gh_build_G of a GH_CELL_TESS_MVI_DATA context without the table)
+__global__ void __launch_bounds__(64)
+tess_mag_kernel(TessMagObs o, const double *__restrict__ bounds6, const double *__restrict__ frame,
+                const double *__restrict__ fdir, int64_t Nb, int64_t m, int64_t ld, double ratio, BComps bc,
+                double *__restrict__ A, int *__restrict__ err_cell, TessStats *stats)
+{
+    tess_mag_body<false>(o, bounds6, frame, fdir, Nb, m, ld, ratio, bc, BWeights{}, A, err_cell, stats);
+}
+
+// The shift-invariant table of the store (host_lonsym.h), ONE launch: the same body over synthetic points and the
+// cells of longitude index 0.  With Nb = na1 n points (class, shift) -- class = (latitude, height) --, m = nc1 cell
+// rows and ld = ldT the store's layout IS the table's,
+//     T[(a nc1 + row) ldT + (b na1 + cls) n + d]:
+// the axis block a is a coordinate of the table's row, the data block b one of the observation class.  fdir holds
+// the direction of every synthetic point's class; every entry takes its block's data weight.
+__global__ void __launch_bounds__(64)
+tess_mag_table_kernel(TessMagObs o, const double *__restrict__ bounds6, const double *__restrict__ frame,
+                      const double *__restrict__ fdir, int64_t Nb, int64_t m, int64_t ld, double ratio, BComps bc,
+                      BWeights bw, double *__restrict__ T, int *__restrict__ err_cell, TessStats *stats)
+{
+    tess_mag_body<true>(o, bounds6, frame, fdir, Nb, m, ld, ratio, bc, bw, T, err_cell, stats);
 }
 
 // The field without a store: one workgroup per observation; thread t takes the cells t, t + 256, ... in mesh

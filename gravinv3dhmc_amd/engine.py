@@ -241,12 +241,14 @@ class Engine(object):
         self._chk(self._lib.gh_b_result(self._h, comp, ptr(m), ptr(out)))
         return out
 
-    def set_cells_tess_mag(self, bounds6, ratio, components, weights, fdir=None):
+    def set_cells_tess_mag(self, bounds6, ratio, components, weights, fdir=None, shift_invariant=False):
         """The M/3 tesseroids (bounds (M/3, 6): w, e, s, n, top, bottom) of a magnetization-vector model under magnetic
         data (gh_set_cells_tess_mag): rows as set_cells_mvi_data, columns [K_N | K_E | K_D] for a unit magnetization
         along north, east and down at each cell's centre.  fdir (N / len(components), 3): the unit vectors of the total
-        field at the observation points, needed by a "tf" block (or tess_b_result("tf")) alone.  Call it before
-        set_obs."""
+        field at the observation points, needed by a "tf" block (or tess_b_result("tf")) alone.  Dense, or -- with
+        shift_invariant=True (gh_set_cells_tess_mag_table: no 16384-row limit), or set_shift_invariant(True) AFTER this
+        call and before build_G -- on the shift-invariant table: the axis block is then a coordinate of the table's
+        cell row, the data block one of the observation class.  Call it before set_obs."""
         b = f64(bounds6)
         if self.M % 3 != 0 or b.shape != (self.M // 3, 6):
             raise ValueError("bounds table of a magnetization-vector model must be (M/3, 6)")
@@ -265,8 +267,10 @@ class Engine(object):
             if len(comps) == 0 or fdir.shape != (self.N // len(comps), 3):
                 raise ValueError("fdir must be (N / components, 3)")
             fp = ptr(fdir)
-        self._chk(self._lib.gh_set_cells_tess_mag(self._h, ptr(b), float(ratio), len(comps),
-                                                  (C.c_int * max(len(comps), 1))(*comps), ptr(w), fp))
+        fn = self._lib.gh_set_cells_tess_mag_table if shift_invariant else self._lib.gh_set_cells_tess_mag
+        self._chk(fn(self._h, ptr(b), float(ratio), len(comps), (C.c_int * max(len(comps), 1))(*comps), ptr(w), fp))
+        if shift_invariant:
+            self._shift_invariant = True
         self.mvi = True
         self.multi = len(comps)
         self.tess_mag = True

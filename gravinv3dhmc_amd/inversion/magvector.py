@@ -34,6 +34,20 @@ _VSTORE = "the vector-data magnetization store"
 _TSTORE = "the tesseroid magnetization store"
 
 
+def mirror_signs(data):
+    """The signs the entries of the tesseroid magnetization store take under the reflection through the equatorial
+    plane, (class_signs, axis_signs): K[(b, mirrored point), (a, mirrored cell)] = class_signs[b] axis_signs[a]
+    K[(b, point), (a, cell)].  Local north flips at both ends, east and down do not: class_signs has -1 for "bx" and
+    +1 for "by" and "bz", one per component of data; axis_signs is (-1, +1, +1) for the cell's (N, E, D).  The total
+    field projects on a direction of its own at the observation and is no pure sign: its entry is None, and the
+    shift-invariant table is built without the north-south mirror when "tf" is among the data."""
+    data = (data,) if isinstance(data, str) else tuple(data)
+    for b in data:
+        if b not in _lib.BCOMPONENTS:
+            raise ValueError("data component %r: must be one of %s" % (b, ", ".join(_lib.BCOMPONENTS)))
+    return tuple(None if b == "tf" else -1.0 if b == "bx" else 1.0 for b in data), (-1.0, 1.0, 1.0)
+
+
 class MagVectorModule(_Potential):
     """The magnetization vector of every prism under total-field data, on one MI355X.
 
@@ -64,6 +78,7 @@ class MagVectorModule(_Potential):
     """
     _props = 3  # (mx, my and mz of the same mesh)
     _spherical = False  # (TesseroidMagVectorModule: tesseroids, always the store of row blocks)
+    _has_table = False  # (TesseroidMagVectorModule: shift_invariant=True keeps the shift-invariant table)
 
     def __init__(self, dobs, mrange, mspacing, obsurface, mangle=(90, 0), mratio=1, mseg=False, mdivisionsection=[],
                  weightfactor=0.5, amplitude=0.0, amplitude_beta=0.01, device=0, verbose=True, coordinate="cartesian",
@@ -118,12 +133,13 @@ class MagVectorModule(_Potential):
             raise NotImplementedError("wavelet compression of %s is not supported" % store)
         if matrix_free:
             raise NotImplementedError("%s is dense: the matrix-free mode is not supported" % store)
-        if shift_invariant:
+        if shift_invariant and not self._has_table:
             raise NotImplementedError("%s is dense: the shift-invariant store is not supported" % store)
+        self.shift_invariant = bool(shift_invariant)
         if shard is not None:
             raise NotImplementedError("%s is not sharded" % store)
         if self._vector:
-            if len(data) * n > 16384:
+            if len(data) * n > 16384 and not self.shift_invariant:
                 raise NotImplementedError("%d data components x %d observations = %d rows: %s takes at most 16384 (it "
                                           "runs on the fused sweep)" % (len(data), n, len(data) * n, store))
             self.weights = w
@@ -335,10 +351,23 @@ class TesseroidMagVectorModule(MagVectorModule):
 
     HMCSample, misfit_and_grad, forward, kernel(axis, component) with axis 0 / 1 / 2 ("x" north, "y" east, "z" down AT
     THE CELL), block_means(), Amplitude / amplitude / direction, to_vectors / from_vectors work as on MagVectorModule:
-    the rows are row blocks with a data weight and a mean each, always (a single tf block too).  Not supported
-    (NotImplementedError naming the tesseroid magnetization store): wavelet compression, the matrix-free mode, the
-    shift-invariant store, shards, HMCSampleBatch and more than 16384 stacked rows."""
+    the rows are row blocks with a data weight and a mean each, always (a single tf block too).
+
+    shift_invariant=True keeps the shift-invariant table instead of the kernel (regular global grids: every cell row
+    a full circle of longitudes, observations on the cells' longitude spacing): the data block is one more coordinate
+    of the observation class, the axis block (N, E, D) one of the cell row; nothing is stored per (observation,
+    cell) and the 16384-row limit does not apply.  On a grid symmetric about the equator the table is halved by the
+    north-south mirror, whose entries take the signs of mirror_signs(data).  With "tf" among the data the table is
+    built WITHOUT that mirror (the total field is no pure sign under it), and inc, dec must be equal, bit for bit,
+    over every class of observations (same latitude and height; scalars always are).  HMCSample (posterior_stream
+    too), misfit_and_grad, forward, block_means, Amplitude / amplitude / direction, to_vectors / from_vectors work on
+    the table; Aw, A and kernel(axis, component) do not exist there (NotImplementedError).  NotImplementedError with
+    the store's reason if the geometry lacks the structure.
+
+    Not supported (NotImplementedError naming the tesseroid magnetization store): wavelet compression, the
+    matrix-free mode, shards, HMCSampleBatch, and more than 16384 stacked rows without shift_invariant=True."""
     _spherical = True
+    _has_table = True
 
     def __init__(self, dobs, mrange, mspacing, obsurface, data=("bx", "by", "bz"), weights=None, mangle=(90, 0),
                  amplitude=0.0, amplitude_beta=0.01, mratio=1, mseg=False, mdivisionsection=[], weightfactor=0.5,
@@ -349,9 +378,15 @@ class TesseroidMagVectorModule(MagVectorModule):
         if not (self._ratio > 0):
             raise ValueError("Invalid ratio {}. Must be > 0.".format(ratio))
         data = (data,) if isinstance(data, str) else tuple(data)
+        if shift_invariant and abs((mrange[1] - mrange[0]) - 360.0) > 1e-9 * 360.0:
+            # (decided on the host, before any device work: a regional mesh has no table; the library tests the rest)
+            raise NotImplementedError("shift-invariant store: %s: a row of cells does not cover the full circle of "
+                                      "longitudes" % _TSTORE)
         self._fdir = None
         if "tf" in data:
             self._fdir = tesseroid._field_directions(mangle[0], mangle[1], int(np.asarray(obsurface[0]).size))
+            if shift_invariant:
+                self._fdir = self._class_directions(self._fdir, mangle, obsurface)
         super().__init__(dobs, mrange, mspacing, obsurface, mangle=mangle, mratio=mratio, mseg=mseg,
                          mdivisionsection=mdivisionsection, weightfactor=weightfactor, amplitude=amplitude,
                          amplitude_beta=amplitude_beta, device=device, verbose=verbose, coordinate="spherical",
@@ -362,12 +397,48 @@ class TesseroidMagVectorModule(MagVectorModule):
         return (mesher.TesseroidMeshSegment(self.mrange, self.mspacing, self.mdivisionsection) if self.mseg
                 else mesher.TesseroidMesh(self.mrange, self.mspacing, self.mratio))
 
+    @staticmethod
+    def _class_directions(fdir, mangle, obsurface):
+        """The table has one set of entries per class of observations (same latitude and height): inc and dec must
+        be equal, bit for bit, over every class.  Returns fdir with every point taking its class's first direction
+        (the same bits for the same angles, however the vector was evaluated)."""
+        n = fdir.shape[0]
+        lat, h = (np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel()) for a in obsurface[1:3])
+        if lat.size != n or h.size != n:
+            return fdir                    # (the constructor reports the shapes)
+        key = np.stack([lat.view(np.int64), h.view(np.int64)], axis=1)
+        _, first, cls = np.unique(key, axis=0, return_index=True, return_inverse=True)
+        cls = cls.ravel()
+        for ang in mangle[:2]:
+            ang = np.asarray(ang, dtype=np.float64)
+            if ang.ndim == 0:
+                continue
+            bits = np.ascontiguousarray(ang.ravel()).view(np.int64)
+            if not np.array_equal(bits, bits[first][cls]):
+                raise NotImplementedError("shift-invariant store: %s: the total field's direction varies within a "
+                                          "class of observations (same latitude and height)" % _TSTORE)
+        return np.ascontiguousarray(fdir[first][cls])
+
     def _set_cells(self, eng, bounds, data, w):
-        eng.set_cells_tess_mag(bounds, self._ratio, data, w, self._fdir)
+        eng.set_cells_tess_mag(bounds, self._ratio, data, w, self._fdir, shift_invariant=self.shift_invariant)
 
     def _build(self, eng):
-        eng.build_G()
+        eng.build_G()   # (NotImplementedError with the store's reason where the table does not apply)
         if eng.kernel_stats()["warn_cells"] > 0:
             import warnings
             from ..gravmag.tesseroid import _WARN_DIVIDE
             warnings.warn(_WARN_DIVIDE, RuntimeWarning)
+
+    def _no_table(self, what):
+        if self.shift_invariant:
+            raise NotImplementedError("%s: %s keeps the shift-invariant table, the kernel is never stored" %
+                                      (what, _TSTORE))
+
+    @property
+    def A(self):
+        self._no_table("A")
+        return super().A
+
+    def kernel(self, axis, component=None):
+        self._no_table("kernel(%r, %r)" % (axis, component))
+        return super().kernel(axis, component)

@@ -89,7 +89,8 @@ typedef enum {
  * GH_CELL_PRISM_MVI_DATA: prisms, a magnetization vector per cell under VECTOR data -- row blocks of tf, bx, by, bz
  * (gh_set_cells_mvi_data);
  * GH_CELL_TESS_MVI_DATA: tesseroids, a magnetization vector per cell (north, east, down at the cell's centre) under
- * row blocks of tf, bx, by, bz in the observations' local frames (gh_set_cells_tess_mag);
+ * row blocks of tf, bx, by, bz in the observations' local frames, on the dense store (gh_set_cells_tess_mag) or on the
+ * shift-invariant table (gh_set_cells_tess_mag_table);
  * GH_CELL_TESSEROID_MULTI: tesseroids, several gravity fields of one density model inverted together, on the dense
  * store or on the shift-invariant table (gh_set_cells_tess_multi) */
 enum { GH_CELL_PRISM = 0, GH_CELL_TESSEROID = 1, GH_CELL_PRISM_TF = 2, GH_CELL_PRISM_COMP = 3, GH_CELL_TESSEROID_COMP = 4,
@@ -231,14 +232,47 @@ int gh_b_result(gh_ctx *ctx, int component, const double *mag3 /* M/3 x 3 */, do
  * unweighted tf block too): gh_weight with block weights, gh_set_data with per-block means, forward / adjoint,
  * gh_misfit_and_grad, gh_leapfrog and gh_chain_* on the fused sweep, gh_set_amplitude, gh_multi_info, Smoothness / TV
  * per component on shape3 with product M/3, the posterior window and stream.
- * Dense, single chain only: matrix-free, the shift-invariant store, the wavelet compressor, gh_batch_*,
- * gh_shard_init*, gh_upload_G and a stacked N > 16384 return GH_ERR_UNSUPPORTED naming the tesseroid magnetization
- * store; the resident chain kernel and the folded store are never chosen.
+ * Single chain only, dense or on the shift-invariant table (below): matrix-free without the table, the wavelet
+ * compressor, gh_batch_*, gh_shard_init*, gh_upload_G and, on the dense form, a stacked N > 16384 return
+ * GH_ERR_UNSUPPORTED naming the tesseroid magnetization store; the resident chain kernel and the folded store are never
+ * chosen.  A context already asked onto the table (gh_set_shift_invariant BEFORE this call) is refused: its kind is not
+ * known yet; ask after this call, or use gh_set_cells_tess_mag_table.
  * Errors: GH_ERR_ARG for ncomp outside 1..GH_BCOMP_MAX, an unknown or repeated component, a weight that is not
  * finite and > 0, M not a multiple of 3, N not a multiple of ncomp, a tf block without fdir, a context that is not
  * fresh. */
 int gh_set_cells_tess_mag(gh_ctx *ctx, const double *bounds6 /* M/3 x 6 */, double ratio, int ncomp, const int *comps,
                           const double *weights, const double *fdir /* N/ncomp x 3, or NULL */);
+/* The same context on the SHIFT-INVARIANT TABLE: gh_set_cells_tess_mag followed by gh_set_shift_invariant(ctx, 1), in
+ * one call and without the limit on the stacked rows (G is never stored).  gh_set_shift_invariant(ctx, 1) between
+ * gh_set_cells_tess_mag and gh_build_G does the same for N <= 16384.  On the geometry that store asks for -- the M/3
+ * cells in rows of n cells that cover the full circle of longitudes, observation longitudes on the cells' spacing --
+ *   the data block is one more coordinate of the observation class, as on a GH_CELL_TESSEROID_MULTI context: a class is
+ *   (block b, latitude, height), na = ncomp na1 classes;
+ *   the axis block is a coordinate of the table's cell row: column a M/3 + r n + k of the property-major model is cell
+ *   row a nc1 + r (nc1 = M / 3 / n), longitude k, of a table of nc = 3 nc1 rows, so j = c n + k addresses the model as
+ *   it is;  T[(a nc1 + r) ldT + (b na1 + cls) n + d] is the entry of shift d.  Both frames turn with a common shift of the
+ *   longitudes, so every (component, axis) pair depends on lon_i - lon_j alone.
+ *   gh_build_G fills the table in ONE launch of the dense assembly's body over the na1 n synthetic points and the nc1
+ *   cells of longitude index 0 -- one traversal of the subdivision per (point, cell), every entry times weights[b] --
+ *   and agrees with the dense store to 1e-10 of a block's largest entry; warn_cells (n per cell of longitude index 0,
+ *   once per cell whatever the axis), leaves and GH_ERR_OVERFLOW as the table of gz reports them.
+ *   Only the streamed harmonic form serves this kind (gh_shift_invariant_harmonic: 2; n < 2 or n > 1024 refused), with
+ *   the same four plain launches per step.  On a grid symmetric about the equator a row of the transformed table stands
+ *   for a mirrored pair of cell rows; local north flips at both ends of the reflection, east and down do not, so the
+ *   entry of the partner is s_b s_a K with s_b = -1 for GH_BCOMP_BX and s_a = -1 for the axis N, +1 otherwise: a sign
+ *   per class times a sign per table row (GRAVHMC_LW_MIRROR=0: no pairing).  With a GH_BCOMP_TF block the table is
+ *   built WITHOUT the mirror (the projection on f_o is no pure sign under it), and fdir must be equal, bit for bit,
+ *   over every class of observations (same latitude and height), else GH_ERR_UNSUPPORTED ("the total field's direction
+ *   varies within a class of observations").
+ *   gh_weight gives the dense store's Wm (column norms of Wb A over all M columns) from the table; the means are
+ *   removed per block, from the classes' sums in index order; gh_multi_info, gh_set_amplitude and the regularisers
+ *   (per property, with Phi's slot in chains) are the dense store's, evaluated by the same launches.
+ * Refused with GH_ERR_UNSUPPORTED and the reason, each naming the tesseroid magnetization store: a geometry without the
+ * structure (carved or irregular cells, observation longitudes off the spacing), the wavelet compressor, gh_batch_*,
+ * gh_bscg_run, gh_shard_init*, gh_upload_G, gh_set_matrix_free.  The prism forms (GH_CELL_PRISM_MVI,
+ * GH_CELL_PRISM_MVI_DATA) have no table. */
+int gh_set_cells_tess_mag_table(gh_ctx *ctx, const double *bounds6 /* M/3 x 6 */, double ratio, int ncomp,
+                                const int *comps, const double *weights, const double *fdir /* N/ncomp x 3, or NULL */);
 /* The field of a GH_CELL_TESS_MVI_DATA context without a store (needs gh_set_obs and the cells, not G): component is a
  * GH_BCOMP_* value (GH_BCOMP_TF needs the context's fdir), mag3 the vector (m_N, m_E, m_D) in A/m of each of the M/3
  * tesseroids, row-major; result (one value per observation POINT: N / ncomp) in uT.  One workgroup per point sums the
