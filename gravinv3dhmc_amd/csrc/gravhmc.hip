@@ -52,6 +52,7 @@ static_assert(BCOMP_MAX == GH_BCOMP_MAX && BCOMP_MAX <= MULTI_MAX && BCOMP_TF ==
               "the kernels' data components are the C ABI's GH_BCOMP_*");
 
 #include "host_ctx.h"
+#include "host_cells.h"
 #include "host_sweep.h"
 #include "host_fold.h"
 #include "host_lonsym.h"
@@ -170,7 +171,7 @@ int gh_set_obs(gh_ctx *c, const double *a, const double *b, const double *cc)
     HIPCHK(c, hipSetDevice(c->device));
     const double *src[3] = {a, b, cc};
     // (joint store: both blocks share the N/2 points; multi-component store: all blocks share the N/n points)
-    const int64_t n = c->joint ? c->N / 2 : c->mc.n > 0 ? c->N / c->mc.n : c->N;
+    const int64_t n = store_points(c);
     for (int i = 0; i < 3; ++i) {
         TRY(dalloc(c, &c->obs[i], (size_t)n));
         TRY(h2d(c, c->obs[i], src[i], (size_t)n));
@@ -191,22 +192,8 @@ int gh_set_obs(gh_ctx *c, const double *a, const double *b, const double *cc)
 // the tesseroids' ratio and, for the total field, its direction.
 static int set_cells(gh_ctx *c, const double *bounds6, int kind, int comp, double ratio, const double *dir = nullptr)
 {
-    if (c->joint) return fail(c, GH_ERR_UNSUPPORTED, "a joint gravity-magnetic context takes its cells from gh_set_cells_joint");
-    if (vector_data_store(c))
-        return fail(c, GH_ERR_UNSUPPORTED, "a vector-data magnetization context takes its cells from %s",
-                    tess_mag_store(c) ? "gh_set_cells_tess_mag" : "gh_set_cells_mvi_data");
-    if (tess_multi_store(c))
-        return fail(c, GH_ERR_UNSUPPORTED, "a tesseroid multi-component context takes its cells from gh_set_cells_tess_multi");
-    if (c->mc.n > 0) return fail(c, GH_ERR_UNSUPPORTED, "a multi-component context takes its cells from gh_set_cells_multi");
-    if (c->mvi) return fail(c, GH_ERR_UNSUPPORTED, "a magnetization-vector context takes its cells from gh_set_cells_mvi");
-    HIPCHK(c, hipSetDevice(c->device));
-    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
-    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
-    if (dir) {
-        std::copy(dir, dir + 3, c->tf_dir);
-        TRY(dalloc(c, &c->tf_dir_d, 3));
-        TRY(h2d(c, c->tf_dir_d, c->tf_dir, 3));
-    }
+    TRY(refuse_plain_cells(c));
+    TRY(upload_cells(c, bounds6, c->M, dir));
     c->cell_kind = kind;
     c->comp = comp;
     c->ratio = ratio;
@@ -232,28 +219,23 @@ int gh_set_cells(gh_ctx *c, const double *bounds6, int kind, double ratio)
 int gh_set_cells_tf(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
 {
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_tf: null pointer");
-    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(fz))
-        return fail(c, GH_ERR_ARG, "gh_set_cells_tf: the field direction must be finite");
     const double dir[3] = {fx, fy, fz};
+    TRY(check_direction(c, "gh_set_cells_tf", dir));
     return set_cells(c, bounds6, GH_CELL_PRISM_TF, GH_COMP_GZ, c->ratio, dir);
 }
 
 int gh_set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
 {
-    if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_joint: null pointer");
+    const CellStore &s = CELL_STORES[GH_CELL_PRISM_JOINT];
+    if (!c || !bounds6) return fail(c, GH_ERR_ARG, "%s: null pointer", s.entry);
     if (c->N % 2 != 0 || c->M % 2 != 0)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_joint: N and M must be even (the stacked gz + tf lengths)");
-    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(fz))
-        return fail(c, GH_ERR_ARG, "gh_set_cells_joint: the field direction must be finite");
-    if (c->have_obs || c->have_cells || c->have_G || c->slab)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_joint: call it first on a fresh context (before gh_set_obs)");
-    if (c->mf || c->ls)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_joint: the joint kernel is dense only (no matrix-free mode, "
-                                           "no shift-invariant store)");
-    if (c->sh.kind != 0) return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_joint: the joint kernel is not sharded");
+        return fail(c, GH_ERR_ARG, "%s: N and M must be even (the stacked gz + tf lengths)", s.entry);
+    const double dir[3] = {fx, fy, fz};
+    TRY(check_direction(c, s.entry, dir));
+    TRY(check_context(c, s, "the joint kernel"));
     if (c->N / 2 > 16384)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_joint: N/2 = %lld observations: the joint kernel takes at "
-                                           "most 16384 (no row panels or team sweep)", (long long)(c->N / 2));
+        return fail(c, GH_ERR_UNSUPPORTED, "%s: N/2 = %lld observations: the joint kernel takes at most 16384 (no row "
+                                           "panels or team sweep)", s.entry, (long long)(c->N / 2));
     HIPCHK(c, hipSetDevice(c->device));
     // the store has N/2 rows: its ld and the sweep's partition (each block on its own) follow from that
     const int64_t ld0 = c->ld;
@@ -269,203 +251,105 @@ int gh_set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double fy, d
         (void)configure_sweep(c);
         return rc;
     }
-    const double dir[3] = {fx, fy, fz};
     // (bounds: M/2 cells; the kind's data lives with the first half of the context's M)
-    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
-    TRY(h2d(c, c->bounds, bounds6, (size_t)(c->M / 2) * 6));
-    std::copy(dir, dir + 3, c->tf_dir);
-    TRY(dalloc(c, &c->tf_dir_d, 3));
-    TRY(h2d(c, c->tf_dir_d, c->tf_dir, 3));
+    TRY(upload_cells(c, bounds6, c->M / 2, dir, c->M));
     c->cell_kind = GH_CELL_PRISM_JOINT;
     c->comp = GH_COMP_GZ;
     c->have_cells = true;
     return GH_OK;
 }
 
+// What the entry points of the stores of blocks below are called with (null where an entry point has no such argument)
+struct BlockCells {
+    const double *bounds6, *dir;  // dir: (fx, fy, fz) of the prisms' total field
+    int ncomp;
+    const int *comps;
+    const double *weights, *ratios;  // ratios: one per block (the tesseroid multi-component store)
+    double ratio;                    // ... or one for the store (the tesseroid magnetization store)
+    const double *fdir;
+    bool on_table;  // gh_set_cells_tess_mag_table: onto the shift-invariant table in the same call (no limit on the rows)
+};
+
+// The stores of blocks but the joint one, each in the order of its own checks: the component list, the column and row
+// blocks, the ratio and the directions, the cells' bounds, the context, the rows; then the uploads and the block table.
+static int set_block_cells(gh_ctx *c, int kind, const BlockCells &a)
+{
+    const CellStore &s = CELL_STORES[kind];
+    const bool blocks = s.comps != COMPS_NONE;
+    if (blocks) TRY(check_components(c, s, a.ncomp, a.comps, a.weights, a.ratios));
+    if (s.cols == 3 && (c->M % 3 != 0 || c->M < 3))
+        return fail(c, GH_ERR_ARG, "%s: M = %lld is not three components of the same %s", s.entry, (long long)c->M,
+                    s.tess ? "tesseroids" : "prisms");
+    if (blocks && c->N % a.ncomp != 0)
+        return fail(c, GH_ERR_ARG, "%s: N = %lld is not %d blocks of the same observation points", s.entry, (long long)c->N,
+                    a.ncomp);
+    const int64_t m = c->M / s.cols, Nb = blocks ? c->N / a.ncomp : c->N;
+    if (kind == GH_CELL_TESS_MVI_DATA) {
+        if (!(a.ratio > 0)) return fail(c, GH_ERR_ARG, "Invalid ratio %g. Must be > 0.", a.ratio);
+        if (!a.fdir && std::find(a.comps, a.comps + a.ncomp, (int)GH_BCOMP_TF) != a.comps + a.ncomp)
+            return fail(c, GH_ERR_ARG, "%s: a total-field block needs fdir, one unit vector per observation point", s.entry);
+        for (int64_t i = 0; a.fdir && i < 3 * Nb; ++i)
+            if (!std::isfinite(a.fdir[i])) return fail(c, GH_ERR_ARG, "%s: the field directions must be finite", s.entry);
+    }
+    if (a.dir) TRY(check_direction(c, s.entry, a.dir));
+    if (s.tess) TRY(check_tess_bounds(c, s.entry, a.bounds6, m));
+    TRY(check_context(c, s, s.name));
+    if (s.row_limit && !a.on_table) TRY(check_row_limit(c, s, blocks ? a.ncomp : 0));
+    // one unweighted block of the field a store of one block holds is that store itself: one block with one mean
+    if (kind == GH_CELL_PRISM_MVI_DATA && a.ncomp == 1 && a.comps[0] == GH_BCOMP_TF && a.weights[0] == 1.0)
+        return gh_set_cells_mvi(c, a.bounds6, a.dir[0], a.dir[1], a.dir[2]);
+    if (kind == GH_CELL_TESSEROID_MULTI && a.ncomp == 1 && a.comps[0] == GH_COMP_GZ && a.weights[0] == 1.0)
+        return gh_set_cells(c, a.bounds6, GH_CELL_TESSEROID, a.ratios[0]);  // (kind 1, on either form)
+    TRY(upload_cells(c, a.bounds6, m, a.dir));
+    if (a.fdir) {
+        TRY(dalloc(c, &c->tmag_fdir, (size_t)Nb * 3));
+        TRY(h2d(c, c->tmag_fdir, a.fdir, (size_t)Nb * 3));
+    }
+    // columns: the magnetization-vector store's; rows: the multi-component store's blocks (the tesseroid magnetization
+    // store with a single block too: it has no other form)
+    c->mvi = s.cols == 3;
+    c->mc.n = blocks ? a.ncomp : 0;
+    for (int b = 0; b < c->mc.n; ++b) {
+        c->mc.comp[b] = a.comps[b];
+        c->mc.w[b] = a.weights[b];
+        if (a.ratios) c->mc.ratio[b] = a.ratios[b];
+    }
+    c->cell_kind = kind;
+    c->comp = s.comps == COMPS_GRAV ? a.comps[0] : GH_COMP_GZ;
+    if (s.tess) c->ratio = a.ratios ? a.ratios[0] : a.ratio;
+    c->have_cells = true;
+    return a.on_table ? gh_set_shift_invariant(c, 1) : GH_OK;
+}
+
 int gh_set_cells_mvi(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
 {
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_mvi: null pointer");
-    if (c->M % 3 != 0 || c->M < 3)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi: M = %lld is not three components of the same prisms", (long long)c->M);
-    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(fz))
-        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi: the field direction must be finite");
-    if (c->joint || c->mc.n > 0 || c->have_obs || c->have_cells || c->have_G || c->slab)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi: call it first on a fresh context (before gh_set_obs)");
-    if (c->mf || c->ls)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi: the magnetization-vector store is dense only (no matrix-free "
-                                           "mode, no shift-invariant store)");
-    if (c->sh.kind != 0) return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi: the magnetization-vector store is not sharded");
-    if (c->N > 16384)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi: N = %lld observations: the magnetization-vector store takes at "
-                                           "most 16384 (it runs on the fused sweep: no row panels, no team sweep)",
-                    (long long)c->N);
-    HIPCHK(c, hipSetDevice(c->device));
     const double dir[3] = {fx, fy, fz};
-    // (bounds: M/3 cells)
-    TRY(dalloc(c, &c->bounds, (size_t)(c->M / 3) * 6));
-    TRY(h2d(c, c->bounds, bounds6, (size_t)(c->M / 3) * 6));
-    std::copy(dir, dir + 3, c->tf_dir);
-    TRY(dalloc(c, &c->tf_dir_d, 3));
-    TRY(h2d(c, c->tf_dir_d, c->tf_dir, 3));
-    c->mvi = true;
-    c->cell_kind = GH_CELL_PRISM_MVI;
-    c->comp = GH_COMP_GZ;
-    c->have_cells = true;
-    return GH_OK;
+    return set_block_cells(c, GH_CELL_PRISM_MVI, {bounds6, dir, 0, nullptr, nullptr, nullptr, 0.0, nullptr, false});
 }
 
 int gh_set_cells_mvi_data(gh_ctx *c, const double *bounds6, double fx, double fy, double fz, int ncomp, const int *comps,
                           const double *weights)
 {
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: null pointer");
-    if (ncomp < 1 || ncomp > GH_BCOMP_MAX)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: %d data components: the vector-data magnetization store takes 1 "
-                                   "to %d", ncomp, GH_BCOMP_MAX);
-    for (int b = 0; b < ncomp; ++b) {
-        if (comps[b] < GH_BCOMP_TF || comps[b] > GH_BCOMP_BZ)
-            return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: component %d is not one of GH_BCOMP_TF (0) .. GH_BCOMP_BZ (3)",
-                        comps[b]);
-        for (int a = 0; a < b; ++a)
-            if (comps[a] == comps[b])
-                return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: component %d is listed twice", comps[b]);
-        if (!(weights[b] > 0.0) || !std::isfinite(weights[b]))
-            return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: the data weights must be finite and > 0");
-    }
-    if (c->M % 3 != 0 || c->M < 3)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: M = %lld is not three components of the same prisms",
-                    (long long)c->M);
-    if (c->N % ncomp != 0)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: N = %lld is not %d blocks of the same observation points",
-                    (long long)c->N, ncomp);
-    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(fz))
-        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: the field direction must be finite");
-    if (c->joint || c->mvi || c->mc.n > 0 || c->have_obs || c->have_cells || c->have_G || c->slab)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: call it first on a fresh context (before gh_set_obs)");
-    if (c->mf || c->ls)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi_data: the vector-data magnetization store is dense only (no "
-                                           "matrix-free mode, no shift-invariant store)");
-    if (c->sh.kind != 0)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi_data: the vector-data magnetization store is not sharded");
-    if (c->N > 16384)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_mvi_data: %d components x %lld observations = %lld rows: the "
-                                           "vector-data magnetization store takes at most 16384 (it runs on the fused "
-                                           "sweep: no row panels, no team sweep)", ncomp, (long long)(c->N / ncomp),
-                    (long long)c->N);
-    // the total field alone, unweighted: one block with one mean -- the magnetization-vector store itself
-    if (ncomp == 1 && comps[0] == GH_BCOMP_TF && weights[0] == 1.0) return gh_set_cells_mvi(c, bounds6, fx, fy, fz);
-    HIPCHK(c, hipSetDevice(c->device));
     const double dir[3] = {fx, fy, fz};
-    // (bounds: M/3 cells)
-    TRY(dalloc(c, &c->bounds, (size_t)(c->M / 3) * 6));
-    TRY(h2d(c, c->bounds, bounds6, (size_t)(c->M / 3) * 6));
-    std::copy(dir, dir + 3, c->tf_dir);
-    TRY(dalloc(c, &c->tf_dir_d, 3));
-    TRY(h2d(c, c->tf_dir_d, c->tf_dir, 3));
-    // columns: the magnetization-vector store's; rows: the multi-component store's blocks
-    c->mvi = true;
-    c->mc.n = ncomp;
-    for (int b = 0; b < ncomp; ++b) {
-        c->mc.comp[b] = comps[b];
-        c->mc.w[b] = weights[b];
-    }
-    c->cell_kind = GH_CELL_PRISM_MVI_DATA;
-    c->comp = GH_COMP_GZ;
-    c->have_cells = true;
-    return GH_OK;
-}
-
-// gh_set_cells_tess_mag, and with `table` gh_set_cells_tess_mag_table: the same context, asked onto the shift-invariant
-// table in the same call (no limit on the stacked rows)
-static int set_cells_tess_mag(gh_ctx *c, const double *bounds6, double ratio, int ncomp, const int *comps,
-                              const double *weights, const double *fdir, bool table)
-{
-    if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: null pointer");
-    if (ncomp < 1 || ncomp > GH_BCOMP_MAX)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: %d data components: the tesseroid magnetization store takes 1 "
-                                   "to %d", ncomp, GH_BCOMP_MAX);
-    bool tf = false;
-    for (int b = 0; b < ncomp; ++b) {
-        if (comps[b] < GH_BCOMP_TF || comps[b] > GH_BCOMP_BZ)
-            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: component %d is not one of GH_BCOMP_TF (0) .. GH_BCOMP_BZ (3)",
-                        comps[b]);
-        for (int a = 0; a < b; ++a)
-            if (comps[a] == comps[b])
-                return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: component %d is listed twice", comps[b]);
-        if (!(weights[b] > 0.0) || !std::isfinite(weights[b]))
-            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: the data weights must be finite and > 0");
-        tf = tf || comps[b] == GH_BCOMP_TF;
-    }
-    if (c->M % 3 != 0 || c->M < 3)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: M = %lld is not three components of the same tesseroids",
-                    (long long)c->M);
-    if (c->N % ncomp != 0)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: N = %lld is not %d blocks of the same observation points",
-                    (long long)c->N, ncomp);
-    if (!(ratio > 0)) return fail(c, GH_ERR_ARG, "Invalid ratio %g. Must be > 0.", ratio);
-    if (tf && !fdir)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: a total-field block needs fdir, one unit vector per observation "
-                                   "point");
-    const int64_t m = c->M / 3, Nb = c->N / ncomp;
-    if (fdir)
-        for (int64_t i = 0; i < 3 * Nb; ++i)
-            if (!std::isfinite(fdir[i]))
-                return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: the field directions must be finite");
-    // w <= e, s <= n, top >= bottom: the reference's assertion (tesseroid.py:137-138)
-    for (int64_t j = 0; j < m; ++j) {
-        const double *b = bounds6 + 6 * j;
-        if (!(b[0] <= b[1] && b[2] <= b[3] && b[4] >= b[5]))
-            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: invalid tesseroid dimensions (cell %lld: %g %g %g %g %g %g)",
-                        (long long)j, b[0], b[1], b[2], b[3], b[4], b[5]);
-    }
-    if (c->joint || c->mvi || c->mc.n > 0 || c->have_obs || c->have_cells || c->have_G || c->slab)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: call it first on a fresh context (before gh_set_obs)");
-    // (a context of unknown kind cannot be asked onto the table: the table comes after this call, or with it)
-    if (c->mf || c->ls)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_mag: the tesseroid magnetization store has no matrix-free "
-                                           "mode, and takes the shift-invariant table after this call "
-                                           "(gh_set_shift_invariant) or with it (gh_set_cells_tess_mag_table)");
-    if (c->sh.kind != 0)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_mag: the tesseroid magnetization store is not sharded");
-    if (c->N > 16384 && !table)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_mag: %d components x %lld observations = %lld rows: the "
-                                           "dense form of the tesseroid magnetization store takes at most 16384 (it runs "
-                                           "on the fused sweep: no row panels, no team sweep); the shift-invariant table "
-                                           "has no such limit (gh_set_cells_tess_mag_table)", ncomp, (long long)Nb,
-                    (long long)c->N);
-    HIPCHK(c, hipSetDevice(c->device));
-    TRY(dalloc(c, &c->bounds, (size_t)m * 6));
-    TRY(h2d(c, c->bounds, bounds6, (size_t)m * 6));
-    if (fdir) {
-        TRY(dalloc(c, &c->tmag_fdir, (size_t)Nb * 3));
-        TRY(h2d(c, c->tmag_fdir, fdir, (size_t)Nb * 3));
-    }
-    // columns: the magnetization-vector store's; rows: the multi-component store's blocks (a single block too: the
-    // store has no other form)
-    c->mvi = true;
-    c->mc.n = ncomp;
-    for (int b = 0; b < ncomp; ++b) {
-        c->mc.comp[b] = comps[b];
-        c->mc.w[b] = weights[b];
-    }
-    c->cell_kind = GH_CELL_TESS_MVI_DATA;
-    c->comp = GH_COMP_GZ;
-    c->ratio = ratio;
-    c->have_cells = true;
-    return table ? gh_set_shift_invariant(c, 1) : GH_OK;
+    return set_block_cells(c, GH_CELL_PRISM_MVI_DATA, {bounds6, dir, ncomp, comps, weights, nullptr, 0.0, nullptr, false});
 }
 
 int gh_set_cells_tess_mag(gh_ctx *c, const double *bounds6, double ratio, int ncomp, const int *comps,
                           const double *weights, const double *fdir)
 {
-    return set_cells_tess_mag(c, bounds6, ratio, ncomp, comps, weights, fdir, false);
+    if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: null pointer");
+    return set_block_cells(c, GH_CELL_TESS_MVI_DATA, {bounds6, nullptr, ncomp, comps, weights, nullptr, ratio, fdir, false});
 }
 
+// (the same context as gh_set_cells_tess_mag makes, and that call's name in the refusals)
 int gh_set_cells_tess_mag_table(gh_ctx *c, const double *bounds6, double ratio, int ncomp, const int *comps,
                                 const double *weights, const double *fdir)
 {
-    return set_cells_tess_mag(c, bounds6, ratio, ncomp, comps, weights, fdir, true);
+    if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: null pointer");
+    return set_block_cells(c, GH_CELL_TESS_MVI_DATA, {bounds6, nullptr, ncomp, comps, weights, nullptr, ratio, fdir, true});
 }
-
 
 static const char *const MVI_ONLY = "the amplitude term couples the three blocks of the magnetization-vector store (a "
                                     "GH_CELL_PRISM_MVI, GH_CELL_PRISM_MVI_DATA or GH_CELL_TESS_MVI_DATA context, "
@@ -508,7 +392,7 @@ int gh_amplitude_eval(gh_ctx *c, const double *mw, double *value, double *grad, 
     TRY(need(c, c->amp.set, "gh_amplitude_eval: call gh_set_amplitude first (lambda = 0 leaves the coupling off)"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(ensure_work(c));
-    const int64_t m = c->M / 3;
+    const int64_t m = store_cells(c);
     if (amp) TRY(dalloc(c, &c->amp.abuf, (size_t)m));
     TRY(h2d(c, c->xb[3], mw, (size_t)c->M));
     launch_amplitude(c, c->xb[3], 1.0, grad ? c->tmpM : nullptr, false, amp ? c->amp.abuf : nullptr, c->amppart);
@@ -532,98 +416,14 @@ int gh_amplitude_last(const gh_ctx *c, double *phi)
 int gh_set_cells_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *weights)
 {
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_multi: null pointer");
-    if (ncomp < 1 || ncomp > GH_MULTI_MAX)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_multi: %d components: the multi-component store takes 1 to %d", ncomp,
-                    GH_MULTI_MAX);
-    for (int b = 0; b < ncomp; ++b) {
-        if (comps[b] < GH_COMP_POTENTIAL || comps[b] > GH_COMP_GZZ)
-            return fail(c, GH_ERR_ARG, "gh_set_cells_multi: component %d is not one of GH_COMP_POTENTIAL (0) .. GH_COMP_GZZ (10)",
-                        comps[b]);
-        for (int a = 0; a < b; ++a)
-            if (comps[a] == comps[b])
-                return fail(c, GH_ERR_ARG, "gh_set_cells_multi: component %d is listed twice", comps[b]);
-        if (!(weights[b] > 0.0) || !std::isfinite(weights[b]))
-            return fail(c, GH_ERR_ARG, "gh_set_cells_multi: the data weights must be finite and > 0");
-    }
-    if (c->N % ncomp != 0)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_multi: N = %lld is not %d blocks of the same observation points",
-                    (long long)c->N, ncomp);
-    if (c->joint || c->mvi || c->have_obs || c->have_cells || c->have_G || c->slab)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_multi: call it first on a fresh context (before gh_set_obs)");
-    if (c->mf || c->ls)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_multi: the multi-component store is dense only (no matrix-free "
-                                           "mode, no shift-invariant store)");
-    if (c->sh.kind != 0) return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_multi: the multi-component store is not sharded");
-    if (c->N > 16384)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_multi: %d components x %lld observations = %lld rows: the "
-                                           "multi-component store takes at most 16384 (it runs on the fused sweep: no row "
-                                           "panels, no team sweep)", ncomp, (long long)(c->N / ncomp), (long long)c->N);
-    HIPCHK(c, hipSetDevice(c->device));
-    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
-    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
-    c->mc.n = ncomp;
-    for (int b = 0; b < ncomp; ++b) {
-        c->mc.comp[b] = comps[b];
-        c->mc.w[b] = weights[b];
-    }
-    c->cell_kind = GH_CELL_PRISM_MULTI;
-    c->comp = comps[0];
-    c->have_cells = true;
-    return GH_OK;
+    return set_block_cells(c, GH_CELL_PRISM_MULTI, {bounds6, nullptr, ncomp, comps, weights, nullptr, 0.0, nullptr, false});
 }
 
 int gh_set_cells_tess_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *ratios,
                             const double *weights)
 {
     if (!c || !bounds6 || !comps || !ratios || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: null pointer");
-    if (ncomp < 1 || ncomp > GH_MULTI_MAX)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: %d components: the tesseroid multi-component store takes 1 to %d",
-                    ncomp, GH_MULTI_MAX);
-    for (int b = 0; b < ncomp; ++b) {
-        if (comps[b] < GH_COMP_POTENTIAL || comps[b] > GH_COMP_GZZ)
-            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: component %d is not one of GH_COMP_POTENTIAL (0) .. GH_COMP_GZZ "
-                                       "(10)", comps[b]);
-        for (int a = 0; a < b; ++a)
-            if (comps[a] == comps[b])
-                return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: component %d is listed twice", comps[b]);
-        if (!(weights[b] > 0.0) || !std::isfinite(weights[b]))
-            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: the data weights must be finite and > 0");
-        if (!(ratios[b] > 0)) return fail(c, GH_ERR_ARG, "Invalid ratio %g. Must be > 0.", ratios[b]);
-    }
-    if (c->N % ncomp != 0)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: N = %lld is not %d blocks of the same observation points",
-                    (long long)c->N, ncomp);
-    // w <= e, s <= n, top >= bottom: the reference's assertion (tesseroid.py:137-138)
-    for (int64_t j = 0; j < c->M; ++j) {
-        const double *b = bounds6 + 6 * j;
-        if (!(b[0] <= b[1] && b[2] <= b[3] && b[4] >= b[5]))
-            return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: invalid tesseroid dimensions (cell %lld: %g %g %g %g %g %g)",
-                        (long long)j, b[0], b[1], b[2], b[3], b[4], b[5]);
-    }
-    if (c->joint || c->mvi || c->mc.n > 0 || c->have_obs || c->have_cells || c->have_G || c->slab)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: call it first on a fresh context (before gh_set_obs)");
-    // (the shift-invariant store may have been asked for already: it is the one form besides the dense store)
-    if (c->mf && !c->ls)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_multi: the tesseroid multi-component store has no matrix-free "
-                                           "mode (dense, or the shift-invariant store)");
-    if (c->sh.kind != 0)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cells_tess_multi: the tesseroid multi-component store is not sharded");
-    // gz alone, unweighted: one block with one mean -- the tesseroid store itself (kind 1), on either form
-    if (ncomp == 1 && comps[0] == GH_COMP_GZ && weights[0] == 1.0) return gh_set_cells(c, bounds6, GH_CELL_TESSEROID, ratios[0]);
-    HIPCHK(c, hipSetDevice(c->device));
-    TRY(dalloc(c, &c->bounds, (size_t)c->M * 6));
-    TRY(h2d(c, c->bounds, bounds6, (size_t)c->M * 6));
-    c->mc.n = ncomp;
-    for (int b = 0; b < ncomp; ++b) {
-        c->mc.comp[b] = comps[b];
-        c->mc.ratio[b] = ratios[b];
-        c->mc.w[b] = weights[b];
-    }
-    c->cell_kind = GH_CELL_TESSEROID_MULTI;
-    c->comp = comps[0];
-    c->ratio = ratios[0];
-    c->have_cells = true;
-    return GH_OK;
+    return set_block_cells(c, GH_CELL_TESSEROID_MULTI, {bounds6, nullptr, ncomp, comps, weights, ratios, 0.0, nullptr, false});
 }
 
 int gh_multi_info(gh_ctx *c, int *ncomp, int *comps, double *weights, double *pred_mean, double *obs_mean)
@@ -673,7 +473,7 @@ int gh_set_cross_gradient(gh_ctx *c, double lambda, const double scale2[2], cons
                                            "joint store (a GH_CELL_PRISM_JOINT context, gh_set_cells_joint)");
     if (!scale2 || !shape3 || !hz) return fail(c, GH_ERR_ARG, "gh_set_cross_gradient: null pointer");
     TRY(need(c, c->weighted, "gh_set_cross_gradient: call gh_weight first (the term acts on mw / Wm)"));
-    const int64_t m = c->M / 2;
+    const int64_t m = store_cells(c);
     if (shape3[0] < 2 || shape3[1] < 2 || shape3[2] < 2)
         return fail(c, GH_ERR_ARG, "gh_set_cross_gradient: every extent of the mesh must be at least 2, got (%d,%d,%d)",
                     shape3[0], shape3[1], shape3[2]);
@@ -720,7 +520,7 @@ int gh_cross_gradient_eval(gh_ctx *c, const double *mw, double *value, double *g
     TRY(need(c, c->cg.set, "gh_cross_gradient_eval: call gh_set_cross_gradient first (lambda = 0 leaves the coupling off)"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(ensure_work(c));
-    const int64_t m = c->M / 2;
+    const int64_t m = store_cells(c);
     if (t) TRY(dalloc(c, &c->cg.tbuf, 3 * (size_t)m));
     TRY(h2d(c, c->xb[3], mw, (size_t)c->M));
     launch_cross_gradient(c, c->xb[3], 1.0, grad ? c->tmpM : nullptr, false, t ? c->cg.tbuf : nullptr, c->regpart);
@@ -761,7 +561,7 @@ int gh_sweep_layout(const gh_ctx *c, int *tw, int *ept2, int *pf, int *nt, int *
 static int h2d_obsvec(gh_ctx *c, double *dst, const double *src)
 {
     if (!c->joint) return h2d(c, dst, src, (size_t)c->N);
-    const size_t n = (size_t)(c->N / 2);
+    const size_t n = (size_t)store_points(c);
     HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)c->ld * sizeof(double), src, n * sizeof(double), n * sizeof(double), 2,
                                hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -771,33 +571,10 @@ static int h2d_obsvec(gh_ctx *c, double *dst, const double *src)
 static int d2h_obsvec(gh_ctx *c, double *dst, const double *src)
 {
     if (!c->joint) return d2h(c, dst, src, (size_t)c->N);
-    const size_t n = (size_t)(c->N / 2);
+    const size_t n = (size_t)store_points(c);
     HIPCHK(c, hipMemcpy2DAsync(dst, n * sizeof(double), src, (size_t)c->ld * sizeof(double), n * sizeof(double), 2,
                                hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return GH_OK;
-}
-
-// The stores that are dense and run one chain -- the joint gravity-magnetic store, the multi-component stores and the
-// magnetization-vector store -- refuse `who`, each naming itself.  (The tesseroid multi-component store also runs on
-// the shift-invariant table: still one chain, no other form.)
-static int dense_single_chain_refuse(gh_ctx *c, const char *who)
-{
-    if (c && tess_multi_store(c))
-        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the tesseroid multi-component store (dense or "
-                                           "shift-invariant, single chain)", who);
-    if (c && c->joint)
-        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the joint gravity-magnetic kernel (dense, single chain)",
-                    who);
-    if (c && tess_mag_store(c))
-        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the tesseroid magnetization store (dense or "
-                                           "shift-invariant, single chain)", who);
-    if (c && vector_data_store(c))
-        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on %s (dense, single chain)", who, vector_data_store_name(c));
-    if (c && c->mc.n > 0)
-        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the multi-component store (dense, single chain)", who);
-    if (c && c->mvi)
-        return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on the magnetization-vector store (dense, single chain)", who);
     return GH_OK;
 }
 
@@ -839,7 +616,7 @@ int gh_tf_result(gh_ctx *c, const double *mag3, double *result)
     if (c->sh.kind != 0)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_tf_result: the magnetic field's result runs on an unsharded context");
     // (magnetization-vector store: M / 3 prisms)
-    const int64_t cells = c->mvi ? c->M / 3 : c->M;
+    const int64_t cells = store_cells(c);
     return run_result(c, "gh_tf_result", mag3, 3 * (size_t)cells, result, [c, cells](const double *dmag, double *dres) {
         prism_tf_result_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(
             c->obs[0], c->obs[1], c->obs[2], c->bounds, dmag, c->N, cells, c->tf_dir[0], c->tf_dir[1], c->tf_dir[2],
@@ -866,59 +643,12 @@ int gh_b_result(gh_ctx *c, int component, const double *mag3, double *result)
     static const result_fn fns[] = {prism_b_result_kernel<BCOMP_BX>, prism_b_result_kernel<BCOMP_BY>,
                                     prism_b_result_kernel<BCOMP_BZ>};
     const result_fn fn = fns[component - GH_BCOMP_BX];
-    const int64_t cells = c->M / 3, n = c->mc.n > 0 ? c->N / c->mc.n : c->N;
+    const int64_t cells = store_cells(c), n = store_points(c);
     return run_result(c, "gh_b_result", mag3, 3 * (size_t)cells, result, [c, cells, n, fn](const double *dmag, double *dres) {
         hipLaunchKernelGGL(fn, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double *)c->obs[0],
                            (const double *)c->obs[1], (const double *)c->obs[2], (const double *)c->bounds, dmag, n, cells,
                            dres);
     }, n);
-}
-
-// One pass of the tesseroid magnetization kernels over all (observation point, cell) pairs: the converted
-// observations (tess_convert_kernel with sin / cos of the longitude), the cells' frames (tess_mag_cellframe_kernel),
-// then `launch`; warn_cells, leaves and GH_ERR_OVERFLOW as tess_comp_assemble reports them.
-static int tess_mag_pass(gh_ctx *c, const char *who, const std::function<void(const TessMagObs &, const double *, int *, TessStats *)> &launch)
-{
-    const int64_t m = c->M / 3, Nb = c->N / c->mc.n;
-    double *buf = nullptr;
-    int *err_cell = nullptr;
-    TessStats *stats = nullptr;
-    auto release = [&]() {
-        hipFree(buf);
-        hipFree(err_cell);
-        hipFree(stats);
-    };
-    if (hipMalloc((void **)&buf, sizeof(double) * (size_t)(6 * Nb + TESS_MAG_FRAME * m)) != hipSuccess ||
-        hipMalloc((void **)&err_cell, sizeof(int) * (size_t)m) != hipSuccess ||
-        hipMalloc((void **)&stats, sizeof(TessStats)) != hipSuccess) {
-        (void)hipGetLastError();
-        release();
-        return fail(c, GH_ERR_NOMEM, "%s: device allocation of the tesseroid pass's buffers failed", who);
-    }
-    double *frame = buf + 6 * Nb;
-    const TessMagObs o{buf, buf + Nb, buf + 2 * Nb, buf + 3 * Nb, buf + 4 * Nb, buf + 5 * Nb};
-    std::vector<int> herr((size_t)m);
-    TessStats hs{};
-    hipError_t e = hipMemsetAsync(err_cell, 0, sizeof(int) * (size_t)m, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(stats, 0, sizeof(TessStats), c->stream);
-    if (e == hipSuccess) {
-        tess_convert_kernel<<<dim3((unsigned)((Nb + 255) / 256)), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], Nb, buf, buf + Nb, buf + 2 * Nb, buf + 3 * Nb, buf + 4 * Nb, buf + 5 * Nb);
-        tess_mag_cellframe_kernel<<<dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream>>>(c->bounds, m, frame);
-        launch(o, frame, err_cell, stats);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(herr.data(), err_cell, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&hs, stats, sizeof hs, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    release();
-    HIPCHK(c, e);
-    c->warn_cells = 0;
-    for (int v : herr)
-        if (v != 0) c->warn_cells += 1;
-    c->leaves = (int64_t)hs.leaves;
-    if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
-    return GH_OK;
 }
 
 int gh_tess_b_result(gh_ctx *c, int component, const double *mag3, double *result)
@@ -934,7 +664,7 @@ int gh_tess_b_result(gh_ctx *c, int component, const double *mag3, double *resul
     if (component == GH_BCOMP_TF && !c->tmag_fdir)
         return fail(c, GH_ERR_ARG, "gh_tess_b_result: the total field needs the directions gh_set_cells_tess_mag takes "
                                    "as fdir");
-    const int64_t m = c->M / 3, Nb = c->N / c->mc.n;
+    const int64_t m = store_cells(c), Nb = store_points(c);
     int rc = GH_OK;
     const int rr = run_result(c, "gh_tess_b_result", mag3, 3 * (size_t)m, result, [&](const double *dmag, double *dres) {
         rc = tess_mag_pass(c, "gh_tess_b_result", [&](const TessMagObs &o, const double *frame, int *err_cell, TessStats *stats) {
@@ -948,9 +678,7 @@ int gh_tess_b_result(gh_ctx *c, int component, const double *mag3, double *resul
 int gh_set_cells_prism(gh_ctx *c, const double *bounds6, int component)
 {
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_prism: null pointer");
-    if (component < GH_COMP_POTENTIAL || component > GH_COMP_GZZ)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_prism: component %d is not one of GH_COMP_POTENTIAL (0) .. GH_COMP_GZZ (10)",
-                    component);
+    TRY(check_component(c, "gh_set_cells_prism", COMPS_GRAV, component));
     // gz is the prism kind of gh_set_cells: the same context, the same kernels, the same bits
     if (component == GH_COMP_GZ) return gh_set_cells(c, bounds6, GH_CELL_PRISM, 1.6);
     return set_cells(c, bounds6, GH_CELL_PRISM_COMP, component, c->ratio);
@@ -959,16 +687,8 @@ int gh_set_cells_prism(gh_ctx *c, const double *bounds6, int component)
 int gh_set_cells_tess(gh_ctx *c, const double *bounds6, int component, double ratio)
 {
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_tess: null pointer");
-    if (component < GH_COMP_POTENTIAL || component > GH_COMP_GZZ)
-        return fail(c, GH_ERR_ARG, "gh_set_cells_tess: component %d is not one of GH_COMP_POTENTIAL (0) .. GH_COMP_GZZ (10)",
-                    component);
-    // w <= e, s <= n, top >= bottom: the reference's assertion (tesseroid.py:137-138)
-    for (int64_t j = 0; j < c->M; ++j) {
-        const double *b = bounds6 + 6 * j;
-        if (!(b[0] <= b[1] && b[2] <= b[3] && b[4] >= b[5]))
-            return fail(c, GH_ERR_ARG, "gh_set_cells_tess: invalid tesseroid dimensions (cell %lld: %g %g %g %g %g %g)",
-                        (long long)j, b[0], b[1], b[2], b[3], b[4], b[5]);
-    }
+    TRY(check_component(c, "gh_set_cells_tess", COMPS_GRAV, component));
+    TRY(check_tess_bounds(c, "gh_set_cells_tess", bounds6, c->M));
     // gz is the tesseroid kind of gh_set_cells: the same context, the same kernels, the same bits
     if (component == GH_COMP_GZ) return gh_set_cells(c, bounds6, GH_CELL_TESSEROID, ratio);
     if (!(ratio > 0)) return fail(c, GH_ERR_ARG, "Invalid ratio %g. Must be > 0.", ratio);
@@ -1071,75 +791,6 @@ int gh_set_matrix_free_exact(gh_ctx *c, int exact)
     return GH_OK;
 }
 
-// tess_comp_kernel of one field at one ratio over all (observation, cell) pairs: `rows` rows of every column of the
-// store from G on (the N observations' entries, then zeros) when G is given, else the statistics alone; warn_cells
-// and leaves are added to the context's counts (gh_build_G zeroes them), GH_ERR_OVERFLOW.  conv: the converted
-// observations (lon rad, sin lat, cos lat, radius; N each).
-static int tess_comp_assemble(gh_ctx *c, const double *conv, double *G, int comp, double ratio, int64_t N, int64_t rows)
-{
-    typedef void (*tc_fn)(const double *, const double *, const double *, const double *, const double *, int64_t,
-                          int64_t, int64_t, int64_t, double, int, double *, int *, TessStats *);
-    // (indexed by GH_COMP_*: one instantiation per leaf, the geoid runs the potential's)
-    static const tc_fn fns[] = {tess_comp_kernel<GH_COMP_POTENTIAL>, tess_comp_kernel<GH_COMP_POTENTIAL>,
-                                tess_comp_kernel<GH_COMP_GX>,        tess_comp_kernel<GH_COMP_GY>,
-                                tess_comp_kernel<GH_COMP_GZ>,        tess_comp_kernel<GH_COMP_GXX>,
-                                tess_comp_kernel<GH_COMP_GXY>,       tess_comp_kernel<GH_COMP_GXZ>,
-                                tess_comp_kernel<GH_COMP_GYY>,       tess_comp_kernel<GH_COMP_GYZ>,
-                                tess_comp_kernel<GH_COMP_GZZ>};
-    int *err_cell = nullptr;
-    TessStats *stats = nullptr;
-    HIPCHK(c, hipMalloc((void **)&err_cell, sizeof(int) * (size_t)std::max<int64_t>(c->M, 1)));
-    if (hipMalloc((void **)&stats, sizeof(TessStats)) != hipSuccess) {
-        (void)hipGetLastError();
-        hipFree(err_cell);
-        return fail(c, GH_ERR_NOMEM, "gh_build_G: device allocation of the tesseroid statistics failed");
-    }
-    std::vector<int> herr((size_t)c->M);
-    TessStats hs{};
-    hipError_t e = hipMemsetAsync(err_cell, 0, sizeof(int) * (size_t)c->M, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(stats, 0, sizeof(TessStats), c->stream);
-    if (e == hipSuccess) {
-        const int64_t blocks = std::min<int64_t>((rows * c->M + 63) / 64, 1 << 24);
-        hipLaunchKernelGGL(fns[comp], dim3((unsigned)blocks), dim3(64), 0, c->stream, conv, conv + N, conv + 2 * N,
-                           conv + 3 * N, (const double *)c->bounds, N, c->M, rows, c->ld, ratio, comp, G, err_cell,
-                           stats);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(herr.data(), err_cell, sizeof(int) * (size_t)c->M, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&hs, stats, sizeof hs, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(err_cell);
-    hipFree(stats);
-    HIPCHK(c, e);
-    for (int v : herr)
-        if (v != 0) c->warn_cells += 1;
-    c->leaves += (int64_t)hs.leaves;
-    if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
-    return GH_OK;
-}
-
-// prism_kernel of one field (GH_COMP_*, or PRISM_TF) into `rows` rows of every column of the dense store, from G on:
-// the first N of them the observations' entries, the rest zero.
-static int prism_assemble(gh_ctx *c, int field, int64_t N, int64_t rows, double *G)
-{
-    typedef void (*prism_fn)(const double *, const double *, const double *, const double *, int64_t, int64_t,
-                             int64_t, double3, double *, int64_t);
-    // (indexed by GH_COMP_*, then the total field)
-    static const prism_fn fns[] = {prism_kernel<GH_COMP_POTENTIAL>, prism_kernel<GH_COMP_GEOID>,
-                                   prism_kernel<GH_COMP_GX>,        prism_kernel<GH_COMP_GY>,
-                                   prism_kernel<GH_COMP_GZ>,        prism_kernel<GH_COMP_GXX>,
-                                   prism_kernel<GH_COMP_GXY>,       prism_kernel<GH_COMP_GXZ>,
-                                   prism_kernel<GH_COMP_GYY>,       prism_kernel<GH_COMP_GYZ>,
-                                   prism_kernel<GH_COMP_GZZ>,       prism_kernel<PRISM_TF>};
-    const int64_t blocks = std::min<int64_t>((rows * c->M + 255) / 256, 1 << 22);
-    hipLaunchKernelGGL(fns[field], dim3((unsigned)blocks), dim3(256), 0, c->stream, c->obs[0], c->obs[1], c->obs[2],
-                       (const double *)c->bounds, N, c->M, rows, make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), G,
-                       c->ld);
-    HIPCHK(c, hipGetLastError());
-    return GH_OK;
-}
-
 int gh_build_G(gh_ctx *c)
 {
     if (!c) return GH_ERR_ARG;
@@ -1149,12 +800,10 @@ int gh_build_G(gh_ctx *c)
     c->leaves = 0;
     if (c->mf) {
         if (c->slab) return fail(c, GH_ERR_ARG, "gh_build_G: a matrix-free context is built once");
-        if (tess_multi_store(c) && !c->ls)
-            return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: the tesseroid multi-component store has no matrix-free mode "
-                                               "(dense, or the shift-invariant store)");
-        if (tess_mag_store(c) && !c->ls)
-            return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: the tesseroid magnetization store has no matrix-free mode "
-                                               "(dense, or the shift-invariant store)");
+        // (a store of blocks: only the tesseroid forms get here, by way of the table)
+        if (store_name(c) && !c->ls)
+            return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s has no matrix-free mode (dense, or the shift-invariant store)",
+                        store_name(c));
         c->mf_fused = c->ld <= 16384 && env_int("GRAVHMC_MF_FUSED", 1) != 0;
         // (tesseroid components: the two-pass form, with the entry evaluated inside each pass -- no fused KIND;
         // the near-field table and the cell-constant fast leaf are gz's)
@@ -1194,96 +843,18 @@ int gh_build_G(gh_ctx *c)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %d components x %lld observations = %lld rows: the dense form of "
                                            "the tesseroid multi-component store takes at most 16384 (it runs on the fused "
                                            "sweep: no row panels, no team sweep); the shift-invariant store has no such "
-                                           "limit (gh_set_shift_invariant)", c->mc.n, (long long)(c->N / c->mc.n),
+                                           "limit (gh_set_shift_invariant)", c->mc.n, (long long)store_points(c),
                     (long long)c->N);
     if (tess_mag_store(c) && c->N > 16384)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %d components x %lld observations = %lld rows: the dense form of "
                                            "the tesseroid magnetization store takes at most 16384; the shift-invariant "
                                            "table has no such limit (gh_set_cells_tess_mag_table)", c->mc.n,
-                    (long long)(c->N / c->mc.n), (long long)c->N);
+                    (long long)store_points(c), (long long)c->N);
     if (!c->dense_ok)
         return fail(c, GH_ERR_UNSUPPORTED,
                     "N = %lld: more than 16384 observations per device: shard the observations or use "
                     "the matrix-free mode (gh_set_matrix_free)", (long long)c->N);
-    TRY(dalloc(c, &c->G, (size_t)c->ld * (size_t)c->M, false));
-    if (c->cell_kind == GH_CELL_PRISM_JOINT) {
-        // both blocks of H = [A_gz | A_tf] in one launch (ld rows of N/2 observations, m = M/2 cells each)
-        const int64_t m = c->M / 2;
-        const int64_t blocks = std::min<int64_t>((c->ld * m + 255) / 256, 1 << 22);
-        prism_joint_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], c->bounds, c->N / 2, m, c->ld,
-            make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), c->G);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else if (c->cell_kind == GH_CELL_PRISM_MVI) {
-        // the three blocks of A = [A_x | A_y | A_z] in one launch (m = M/3 cells, each corner evaluated once)
-        const int64_t m = c->M / 3;
-        const int64_t blocks = std::min<int64_t>((c->ld * m + 255) / 256, 1 << 22);
-        prism_mvi_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], c->bounds, c->N, m, c->ld,
-            make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), c->G);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else if (c->cell_kind == GH_CELL_PRISM_MVI_DATA) {
-        // every (data block, axis block) in one launch (m = M/3 cells, Nb points, each corner evaluated once); the
-        // threads behind a column's Nb points zero the padding rows below the stack
-        const int64_t m = c->M / 3, Nb = c->N / c->mc.n, Lr = Nb + (c->ld - c->N);
-        BComps bc{};
-        bc.n = c->mc.n;
-        for (int b = 0; b < bc.n; ++b) bc.comp[b] = c->mc.comp[b];
-        const int64_t blocks = std::min<int64_t>((Lr * m + 255) / 256, 1 << 22);
-        prism_mvi_data_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], c->bounds, Nb, m, c->ld,
-            make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]), bc, c->G);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else if (tess_mag_store(c)) {
-        // every (data block, axis block) in one launch: one traversal of the subdivision per (point, cell) pair
-        const int64_t m = c->M / 3, Nb = c->N / c->mc.n, Lr = Nb + (c->ld - c->N);
-        BComps bc{};
-        bc.n = c->mc.n;
-        for (int b = 0; b < bc.n; ++b) bc.comp[b] = c->mc.comp[b];
-        TRY(tess_mag_pass(c, "gh_build_G", [&](const TessMagObs &o, const double *frame, int *err_cell, TessStats *stats) {
-            const int64_t blocks = std::min<int64_t>((Lr * m + 63) / 64, 1 << 24);
-            tess_mag_kernel<<<dim3((unsigned)blocks), dim3(64), 0, c->stream>>>(
-                o, c->bounds, frame, c->tmag_fdir, Nb, m, c->ld, c->ratio, bc, c->G, err_cell, stats);
-        }));
-    } else if (c->cell_kind == GH_CELL_PRISM || c->cell_kind == GH_CELL_PRISM_TF || c->cell_kind == GH_CELL_PRISM_COMP) {
-        TRY(prism_assemble(c, c->cell_kind == GH_CELL_PRISM_TF ? PRISM_TF : c->comp, c->N, c->ld, c->G));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else if (c->cell_kind == GH_CELL_PRISM_MULTI) {
-        // one launch per component into its row block of the one store; the last block's launch also zeroes the
-        // padding rows below it
-        const int64_t Nb = c->N / c->mc.n;
-        for (int b = 0; b < c->mc.n; ++b)
-            TRY(prism_assemble(c, c->mc.comp[b], Nb, b + 1 < c->mc.n ? Nb : c->ld - b * Nb, c->G + b * Nb));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else if (c->cell_kind == GH_CELL_TESSEROID || c->cell_kind == GH_CELL_TESSEROID_COMP) {
-        double *conv = nullptr;
-        HIPCHK(c, hipMalloc((void **)&conv, sizeof(double) * 4 * (size_t)c->N));
-        const int64_t N = c->N;
-        tess_convert_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], N, conv, conv + N, conv + 2 * N, conv + 3 * N);
-        const int rc = tess_comp_assemble(c, conv, c->G, c->comp, c->ratio, c->N, c->ld);
-        hipFree(conv);
-        TRY(rc);
-    } else if (tess_multi_store(c)) {
-        // the field's assembly once per block into its row block of the one store, at the block's ratio; the last
-        // block's launch also zeroes the padding rows below it; error cells and leaves summed over the blocks
-        const int64_t Nb = c->N / c->mc.n;
-        double *conv = nullptr;
-        HIPCHK(c, hipMalloc((void **)&conv, sizeof(double) * 4 * (size_t)Nb));
-        tess_convert_kernel<<<dim3((unsigned)((Nb + 255) / 256)), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], Nb, conv, conv + Nb, conv + 2 * Nb, conv + 3 * Nb);
-        int rc = GH_OK;
-        for (int b = 0; b < c->mc.n && rc == GH_OK; ++b)
-            rc = tess_comp_assemble(c, conv, c->G + b * Nb, c->mc.comp[b], c->mc.ratio[b], Nb,
-                                    b + 1 < c->mc.n ? Nb : c->ld - b * Nb);
-        hipFree(conv);
-        TRY(rc);
-    } else {
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: unknown cell kind %d", c->cell_kind);
-    }
+    TRY(build_dense(c));
     c->have_G = true;
     c->weighted = false;
     c->G_gen += 1;
@@ -1366,7 +937,7 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
         if (weightfactor != 0.5)
             return fail(c, GH_ERR_ARG, "gh_weight: the joint kernel is weighted by the column 2-norms (weightfactor 0.5)");
         // population std of each unweighted block, two passes (weightKDM, potential.py:1050-1051)
-        const int64_t m = c->M / 2, n = c->N / 2;
+        const int64_t m = store_cells(c), n = store_points(c);
         const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((c->ld * m + 255) / 256, (int64_t)c->cus * 8));
         double *part = nullptr, *mean = nullptr;
         TRY(dalloc(c, &part, 2 * (size_t)gx));
@@ -1391,7 +962,7 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
         // Wb first: the column norms are those of Wb A, or the component with the largest unit would decide them
         RowBlocks rb{};
         rb.n = c->mc.n;
-        rb.Nb = c->N / c->mc.n;
+        rb.Nb = store_points(c);
         bool unit = true;
         for (int b = 0; b < rb.n; ++b) {
             rb.w[b] = c->mc.w[b];
@@ -1436,7 +1007,7 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
     HIPCHK(c, hipGetLastError());
     if (c->joint) {
         // Wb: the tf block times s = std_gz / std_tf, folded into the stored kernel (Aw = Wb A Wm^-1)
-        const int64_t m = c->M / 2;
+        const int64_t m = store_cells(c);
         const double sb = c->joint_std[0] / c->joint_std[1];
         scale_cols_kernel<<<dim3((unsigned)std::min<int64_t>((c->ld * m + 255) / 256, 1 << 20)), dim3(256), 0, c->stream>>>(
             c->G, c->ld, m, m, sb);
@@ -1504,9 +1075,8 @@ int gh_set_data(gh_ctx *c, const double *dobs, const double *grav_fix)
     if (c->mc.n > 0) {
         // Wb dobs in row blocks: every component loses its own mean
         if (grav_fix)
-            return fail(c, GH_ERR_ARG, "gh_set_data: %s takes no grav_fix",
-                        tess_multi_store(c) ? "the tesseroid multi-component store" : "the multi-component store");
-        const size_t Nb = N / (size_t)c->mc.n;
+            return fail(c, GH_ERR_ARG, "gh_set_data: %s takes no grav_fix", store_of(c).rows_name);
+        const size_t Nb = (size_t)store_points(c);
         for (int b = 0; b < c->mc.n; ++b) {
             double *tb = t.data() + (size_t)b * Nb;
             const double mb = PW::sum(tb, Nb) / (double)Nb;

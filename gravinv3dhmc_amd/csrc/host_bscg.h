@@ -7,21 +7,17 @@ static const char *const BSCG_WHO = "the bootstrap batch (gh_bscg_run)";
 // Which contexts the bootstrap batch runs on: one GPU's dense, weighted store of one field.
 static int bscg_refuse(gh_ctx *c, int B, int maxk)
 {
-    const char *what = nullptr;
-    if (tess_multi_store(c))
-        what = "the tesseroid multi-component store";
+    // (a store of blocks names itself: each is dense and unsharded, but for the tesseroid forms on the table)
+    const char *what = c->ls && tess_mag_store(c) ? "the tesseroid magnetization store on the shift-invariant table"
+                                                  : store_of(c).rows_name;
+    if (what)
+        ;
     else if (c->ls)
-        what = tess_mag_store(c) ? "the tesseroid magnetization store on the shift-invariant table" : "a shift-invariant store";
+        what = "a shift-invariant store";
     else if (c->mf)
         what = "a matrix-free context";
     else if (c->sh.kind != 0)
         what = "a sharded context";
-    else if (c->joint)
-        what = "the joint gravity-magnetic store";
-    else if (c->mc.n > 0)
-        what = "the multi-component store";
-    else if (c->mvi)
-        what = "the magnetization-vector store";
     else if (c->fd.valid && c->fd.gen == c->G_gen)
         what = "a context whose sweeps read the folded store";
     else if (c->wv.on)

@@ -433,19 +433,6 @@ struct gh_ctx {
     int64_t prof_bytes_last = 0;
 };
 
-// A magnetization vector per cell under row blocks of magnetic data: GH_CELL_PRISM_MVI_DATA and its tesseroid form
-// GH_CELL_TESS_MVI_DATA, which differ in the assembly alone (rows as the multi-component store, columns as the
-// magnetization-vector store)
-static inline bool vector_data_store(const gh_ctx *c) { return c->mvi && c->mc.n > 0; }
-static inline bool tess_mag_store(const gh_ctx *c) { return c->cell_kind == GH_CELL_TESS_MVI_DATA; }
-// The tesseroid multi-component store (GH_CELL_TESSEROID_MULTI): the multi-component store's row blocks, assembled by
-// the tesseroid field kernels; dense, or the shift-invariant table with the block as one more coordinate of the class
-static inline bool tess_multi_store(const gh_ctx *c) { return c->cell_kind == GH_CELL_TESSEROID_MULTI && c->mc.n > 0; }
-static inline const char *vector_data_store_name(const gh_ctx *c)
-{
-    return tess_mag_store(c) ? "the tesseroid magnetization store" : "the vector-data magnetization store";
-}
-
 static int fail(gh_ctx *c, int code, const char *fmt, ...)
 {
     char buf[512];

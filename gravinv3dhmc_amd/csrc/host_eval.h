@@ -13,7 +13,7 @@ static void reduce_slab(gh_ctx *c, const double *gfix, double *d_out)
         const int half = c->grid / 2;
         for (int h = 0; h < 2; ++h)
             reduce_slab_kernel<<<dim3(c->n_dpart, 1), dim3(32, 8), 0, c->stream>>>(
-                c->slab + (int64_t)h * half * c->ld, half, c->ld, c->N / 2, nullptr, d_out + h * c->ld, c->dpart);
+                c->slab + (int64_t)h * half * c->ld, half, c->ld, store_points(c), nullptr, d_out + h * c->ld, c->dpart);
         return;
     }
     (void)lonsym_post_now(c);  // (harmonic shift-invariant store: the sweep left D^ partials, not a slab row)
@@ -51,7 +51,7 @@ static void launch_cross_gradient(gh_ctx *c, const double *x, double lambda, dou
 {
     const gh_ctx::CrossGrad &cg = c->cg;
     CrossGradArgs a{};
-    a.m = c->M / 2;
+    a.m = store_cells(c);
     a.nz = cg.shape[0];
     a.ny = cg.shape[1];
     a.nx = cg.shape[2];
@@ -82,7 +82,7 @@ static bool cross_gradient_on(const gh_ctx *c)
 static void launch_amplitude(gh_ctx *c, const double *x, double lambda, double *g, bool add, double *amp, double *part)
 {
     AmpArgs a{};
-    a.m = c->M / 3;
+    a.m = store_cells(c);
     a.lambda = lambda;
     a.beta = c->amp.beta;
     a.scale = c->amp.scale;
@@ -118,7 +118,7 @@ static int reg_props(const gh_ctx *c)
 static int finalize_joint(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
 {
     const int half = c->grid / 2;
-    const int64_t m = c->M / 2, ld = c->ld;
+    const int64_t m = store_cells(c), ld = c->ld;
     const int nrb = (int)((m + 255) / 256);  // regulariser blocks per property
     const bool two_stage = joint_two_stage(c);
     if (two_stage && !c->slab2) return fail(c, GH_ERR_ARG, "joint epilogue: no slab2 (ensure_work not run)");
@@ -153,7 +153,7 @@ static int finalize_joint(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
         fa.n_dpart = c->n_dpart;
         fa.n_regpart = n_reg;
         fa.ld = ld;
-        fa.N = c->N / 2;
+        fa.N = store_points(c);
         fa.dsum = nullptr;
         fa.n_dsum = 0;
         fa.gfix_sum = 0.0;
@@ -194,7 +194,7 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
     ra.regpart = c->regpart;
     if (c->mvi) {
         // (three properties of one mesh: the regulariser block by block on each, RegArgs::nprop)
-        ra.M = c->M / 3;
+        ra.M = store_cells(c);
         ra.nprop = 3;
         ra.nrb = (int)((ra.M + 255) / 256);
     }
@@ -336,7 +336,7 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
         if (c->mc.n > 0) {
             // one mean per component: r_b = (d_b - mean d_b) - (dobs_b - mean dobs_b) in every row block
             fa.nblk = c->mc.n;
-            fa.Nb = c->N / c->mc.n;
+            fa.Nb = store_points(c);
             fa.bmean = c->mc.bmean;
             fa.dsum = c->mc.bsum;
             fa.n_dsum = fa.n_rows_slab;
@@ -373,7 +373,7 @@ static int finalize(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
     if (amp_on) {
         launch_amplitude(c, x, c->amp.lambda, greg_out, true, nullptr, c->amppart);
         fa.cpart = c->amppart;
-        fa.n_cpart = (int)((c->M / 3 + 255) / 256);
+        fa.n_cpart = (int)((store_cells(c) + 255) / 256);
         fa.lambda = c->amp.lambda;
         fa.phi = o.phi;
     }
@@ -400,7 +400,7 @@ static int scal_ready(gh_ctx *c, const gh_ctx::StateSet &o)
     if (!o.pending) return GH_OK;
     // (joint store: |r|^2 partials of both blocks, then R partials of both blocks)
     const int nd = c->joint ? 2 * c->n_dpart : c->n_dpart;
-    const int nr = c->joint ? 2 * (int)((c->M / 2 + 255) / 256) : c->n_regpart;
+    const int nr = c->joint ? 2 * (int)((store_cells(c) + 255) / 256) : c->n_regpart;
     if (cross_gradient_on(c))
         scal_cg_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(o.part, nd, nr, nr / 2, c->alpha, c->cg.lambda, o.scal, o.phi);
     else if (amplitude_on(c))
@@ -457,7 +457,7 @@ static int ensure_work(gh_ctx *c)
         // on -- Phi of the cross-gradient term, one per 256 cells of a property)
         TRY(dalloc(c, &c->cg.phi_all, 4));
         for (int i = 0; i < 4; ++i) {
-            TRY(dalloc(c, &c->st[i].part, 2 * (size_t)c->n_dpart + 3 * (size_t)((c->M / 2 + 255) / 256)));
+            TRY(dalloc(c, &c->st[i].part, 2 * (size_t)c->n_dpart + 3 * (size_t)((store_cells(c) + 255) / 256)));
             c->st[i].phi = c->cg.phi_all + i;
         }
     } else if (c->mc.n > 0) {
@@ -471,20 +471,20 @@ static int ensure_work(gh_ctx *c)
         // and the amplitude term's partials follow them, one per 256 cells)
         for (int i = 0; i < 4; ++i)
             TRY(dalloc(c, &c->st[i].part, (size_t)c->n_dpart + (size_t)((c->M + 255) / 256) +
-                                              (c->mvi ? 3 + (size_t)((c->M / 3 + 255) / 256) : 0)));
+                                              (c->mvi ? 3 + (size_t)((store_cells(c) + 255) / 256) : 0)));
     } else if (c->ld >= 2048 && ((c->TW > 1 && c->n_panels == 1 && !c->mf) || lonsym_on(c)) && env_int("GRAVHMC_EPILOGUE1", 1) != 0) {
         TRY(dalloc(c, &c->dsum, (size_t)std::max(std::max(c->grid, 128), lonsym_on(c) ? lonsym_classes(c) : 0)));
         // (magnetization-vector store: up to three more partials of R, its blocks being counted per property, and
         // behind them those of the amplitude term, one per 256 cells)
         for (int i = 0; i < 4; ++i)
             TRY(dalloc(c, &c->st[i].part, (size_t)c->n_dpart + (size_t)((c->M + 255) / 256) +
-                                              (c->mvi ? 3 + (size_t)((c->M / 3 + 255) / 256) : 0)));
+                                              (c->mvi ? 3 + (size_t)((store_cells(c) + 255) / 256) : 0)));
     }
     if (c->mvi) {
         // Phi of the amplitude term per state set, and its partials where the epilogue keeps none (finish_kernel)
         TRY(dalloc(c, &c->cg.phi_all, 4));
         for (int i = 0; i < 4; ++i) c->st[i].phi = c->cg.phi_all + i;
-        TRY(dalloc(c, &c->amppart, (size_t)((c->M / 3 + 255) / 256)));
+        TRY(dalloc(c, &c->amppart, (size_t)((store_cells(c) + 255) / 256)));
     }
     // (joint and magnetization-vector stores: the regulariser runs per property, ceil(m / 256) blocks each)
     c->n_regpart = reg_props(c) * (int)((c->M / reg_props(c) + 255) / 256);

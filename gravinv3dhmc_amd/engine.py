@@ -1,10 +1,17 @@
 """numpy-facing wrapper of one libgravhmc context (one problem resident on one MI355X)."""
+import collections
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 from ._lib import check, f64, ptr
+
+
+#: What an engine's context holds, as the library's table of cell stores has it (csrc/host_cells.h): the kind that was
+#: asked for (a CELL_* value; None before the cells), the column blocks (M = cols x cells), the row blocks that share
+#: the observation points (N = rows x points) and whether the library keeps a block table for them (multi_info).
+Store = collections.namedtuple("Store", "kind cols rows table")
 
 
 class DeviceMatrix(object):
@@ -22,7 +29,7 @@ class DeviceMatrix(object):
 
     def to_numpy(self):
         eng = self._engine
-        if getattr(eng, "joint", False):
+        if eng.joint:
             # the joint store holds H = [Aw_gz | Aw_tf] (N/2 rows): the stacked layout, zero blocks included
             H = eng.download_G()
             n, m = eng.N // 2, eng.M // 2
@@ -54,6 +61,31 @@ class Engine(object):
         self._h = h
         self._reg_key = None
         self._chain_valid = False
+        self._store = Store(None, 1, 1, False)
+
+    # -- the store (read by the inversion modules) -----------------------------------
+    def _set_store(self, kind, cols=1, rows=1, table=False):
+        self._store = Store(kind, cols, rows, table)
+
+    joint = property(lambda self: self._store.kind == _lib.CELL_PRISM_JOINT)
+    mvi = property(lambda self: self._store.cols == 3)
+    tess_mag = property(lambda self: self._store.kind == _lib.CELL_TESS_MVI_DATA)
+    tess_multi = property(lambda self: self._store.kind == _lib.CELL_TESSEROID_MULTI)
+    #: the length of the block table; 0 without one
+    multi = property(lambda self: self._store.rows if self._store.table else 0)
+
+    @staticmethod
+    def _blocks(names, components, weights, ratios=None):
+        """The row blocks of a store as the library takes them: (values, C array of them, weights, ratios) of the
+        components, names of `names` (_lib.COMPONENTS or _lib.BCOMPONENTS) or their values."""
+        comps = [names.get(c, -1) if isinstance(c, str) else int(c) for c in components]
+        if any(c not in names.values() for c in comps):
+            raise ValueError("%scomponent must be one of %s"
+                             % ("data " if names is _lib.BCOMPONENTS else "", ", ".join(names)))
+        w, r = f64(weights), None if ratios is None else f64(ratios)
+        if w.shape != (len(comps),) or (r is not None and r.shape != (len(comps),)):
+            raise ValueError("one data weight%s per component" % ("" if r is None else " and one ratio"))
+        return comps, (C.c_int * max(len(comps), 1))(*comps), w, r
 
     # -- lifetime -----------------------------------------------------------------
     def close(self):
@@ -98,7 +130,7 @@ class Engine(object):
         a, b, c = f64(a), f64(b), f64(c)
         # (joint gravity-magnetic context: both blocks share the N/2 observation points)
         # (multi-component context: all blocks share the N / ncomp points)
-        n = self.N // 2 if getattr(self, "joint", False) else self.N // getattr(self, "multi", 1)
+        n = self.N // self._store.rows
         if not (a.shape == b.shape == c.shape == (n,)):
             raise ValueError("Input arrays xp, yp, and zp must have same length!")
         self._chk(self._lib.gh_set_obs(self._h, ptr(a), ptr(b), ptr(c)))
@@ -119,7 +151,7 @@ class Engine(object):
                 raise ValueError("the joint kernel's total field needs direction = (fx, fy, fz)")
             fx, fy, fz = (float(v) for v in direction)
             self._chk(self._lib.gh_set_cells_joint(self._h, ptr(b), fx, fy, fz))
-            self.joint = True
+            self._set_store(_lib.CELL_PRISM_JOINT, cols=2, rows=2)
             return
         if b.shape != (self.M, 6):
             raise ValueError("bounds table must be (M, 6)")
@@ -157,15 +189,9 @@ class Engine(object):
         b = f64(bounds6)
         if b.shape != (self.M, 6):
             raise ValueError("bounds table must be (M, 6)")
-        comps = [_lib.COMPONENTS.get(c, -1) if isinstance(c, str) else int(c) for c in components]
-        if any(c not in _lib.COMPONENTS.values() for c in comps):
-            raise ValueError("component must be one of %s" % ", ".join(_lib.COMPONENTS))
-        w = f64(weights)
-        if w.shape != (len(comps),):
-            raise ValueError("one data weight per component")
-        self._chk(self._lib.gh_set_cells_multi(self._h, ptr(b), len(comps), (C.c_int * max(len(comps), 1))(*comps),
-                                               ptr(w)))
-        self.multi = len(comps)
+        comps, carr, w, _ = self._blocks(_lib.COMPONENTS, components, weights)
+        self._chk(self._lib.gh_set_cells_multi(self._h, ptr(b), len(comps), carr, ptr(w)))
+        self._set_store(_lib.CELL_PRISM_MULTI, rows=len(comps), table=True)
 
     def set_cells_tess_multi(self, bounds6, components, ratios, weights):
         """The M tesseroids (w, e, s, n, top, bottom) of a multi-component model (gh_set_cells_tess_multi): rows as
@@ -175,18 +201,10 @@ class Engine(object):
         b = f64(bounds6)
         if b.shape != (self.M, 6):
             raise ValueError("bounds table must be (M, 6)")
-        comps = [_lib.COMPONENTS.get(c, -1) if isinstance(c, str) else int(c) for c in components]
-        if any(c not in _lib.COMPONENTS.values() for c in comps):
-            raise ValueError("component must be one of %s" % ", ".join(_lib.COMPONENTS))
-        w, r = f64(weights), f64(ratios)
-        if w.shape != (len(comps),) or r.shape != (len(comps),):
-            raise ValueError("one data weight and one ratio per component")
-        self._chk(self._lib.gh_set_cells_tess_multi(self._h, ptr(b), len(comps), (C.c_int * max(len(comps), 1))(*comps),
-                                                    ptr(r), ptr(w)))
-        self.tess_multi = True
+        comps, carr, w, r = self._blocks(_lib.COMPONENTS, components, weights, ratios)
+        self._chk(self._lib.gh_set_cells_tess_multi(self._h, ptr(b), len(comps), carr, ptr(r), ptr(w)))
         # (the unweighted gz alone is the tesseroid store itself: one block, no block table)
-        if not (comps == [_lib.COMP_GZ] and w[0] == 1.0):
-            self.multi = len(comps)
+        self._set_store(_lib.CELL_TESSEROID_MULTI, rows=len(comps), table=not (comps == [_lib.COMP_GZ] and w[0] == 1.0))
 
     def set_cells_mvi(self, bounds6, direction):
         """The M/3 prisms (bounds (M/3, 6)) of a magnetization-vector model (gh_set_cells_mvi): three unknowns
@@ -199,7 +217,7 @@ class Engine(object):
             raise ValueError("the magnetization-vector kernel's total field needs direction = (fx, fy, fz)")
         fx, fy, fz = (float(v) for v in direction)
         self._chk(self._lib.gh_set_cells_mvi(self._h, ptr(b), fx, fy, fz))
-        self.mvi = True
+        self._set_store(_lib.CELL_PRISM_MVI, cols=3)
 
     def set_cells_mvi_data(self, bounds6, direction, components, weights):
         """The M/3 prisms (bounds (M/3, 6)) of a magnetization-vector model under vector data (gh_set_cells_mvi_data):
@@ -209,12 +227,7 @@ class Engine(object):
         b = f64(bounds6)
         if self.M % 3 != 0 or b.shape != (self.M // 3, 6):
             raise ValueError("bounds table of a magnetization-vector model must be (M/3, 6)")
-        comps = [_lib.BCOMPONENTS.get(c, -1) if isinstance(c, str) else int(c) for c in components]
-        if any(c not in _lib.BCOMPONENTS.values() for c in comps):
-            raise ValueError("data component must be one of %s" % ", ".join(_lib.BCOMPONENTS))
-        w = f64(weights)
-        if w.shape != (len(comps),):
-            raise ValueError("one data weight per component")
+        comps, carr, w, _ = self._blocks(_lib.BCOMPONENTS, components, weights)
         if direction is None:
             if _lib.BCOMP_TF in comps:
                 raise ValueError("a total-field block needs direction = (fx, fy, fz)")
@@ -222,12 +235,12 @@ class Engine(object):
         if len(direction) != 3:
             raise ValueError("direction must be (fx, fy, fz)")
         fx, fy, fz = (float(v) for v in direction)
-        self._chk(self._lib.gh_set_cells_mvi_data(self._h, ptr(b), fx, fy, fz, len(comps),
-                                                  (C.c_int * max(len(comps), 1))(*comps), ptr(w)))
-        self.mvi = True
+        self._chk(self._lib.gh_set_cells_mvi_data(self._h, ptr(b), fx, fy, fz, len(comps), carr, ptr(w)))
         # (the unweighted total field alone is the magnetization-vector store itself: one block, no block table)
-        if not (comps == [_lib.BCOMP_TF] and w[0] == 1.0):
-            self.multi = len(comps)
+        if comps == [_lib.BCOMP_TF] and w[0] == 1.0:
+            self._set_store(_lib.CELL_PRISM_MVI, cols=3)
+        else:
+            self._set_store(_lib.CELL_PRISM_MVI_DATA, cols=3, rows=len(comps), table=True)
 
     def b_result(self, component, mag3):
         """bx, by or bz (uT; component a name or BCOMP_* value) at the observation points of a magnetization-vector
@@ -235,9 +248,9 @@ class Engine(object):
         (gh_b_result); needs no G."""
         comp = _lib.BCOMPONENTS.get(component, -1) if isinstance(component, str) else int(component)
         m = f64(mag3)
-        if not getattr(self, "mvi", False) or m.shape != (self.M // 3, 3):
+        if not self.mvi or m.shape != (self.M // 3, 3):
             raise ValueError("magnetization must be (M/3, 3) on a magnetization-vector context")
-        out = np.empty(self.N // getattr(self, "multi", 1))
+        out = np.empty(self.N // self._store.rows)
         self._chk(self._lib.gh_b_result(self._h, comp, ptr(m), ptr(out)))
         return out
 
@@ -252,12 +265,7 @@ class Engine(object):
         b = f64(bounds6)
         if self.M % 3 != 0 or b.shape != (self.M // 3, 6):
             raise ValueError("bounds table of a magnetization-vector model must be (M/3, 6)")
-        comps = [_lib.BCOMPONENTS.get(c, -1) if isinstance(c, str) else int(c) for c in components]
-        if any(c not in _lib.BCOMPONENTS.values() for c in comps):
-            raise ValueError("data component must be one of %s" % ", ".join(_lib.BCOMPONENTS))
-        w = f64(weights)
-        if w.shape != (len(comps),):
-            raise ValueError("one data weight per component")
+        comps, carr, w, _ = self._blocks(_lib.BCOMPONENTS, components, weights)
         if fdir is None:
             if _lib.BCOMP_TF in comps:
                 raise ValueError("a total-field block needs fdir, one unit vector per observation point")
@@ -268,12 +276,10 @@ class Engine(object):
                 raise ValueError("fdir must be (N / components, 3)")
             fp = ptr(fdir)
         fn = self._lib.gh_set_cells_tess_mag_table if shift_invariant else self._lib.gh_set_cells_tess_mag
-        self._chk(fn(self._h, ptr(b), float(ratio), len(comps), (C.c_int * max(len(comps), 1))(*comps), ptr(w), fp))
+        self._chk(fn(self._h, ptr(b), float(ratio), len(comps), carr, ptr(w), fp))
         if shift_invariant:
             self._shift_invariant = True
-        self.mvi = True
-        self.multi = len(comps)
-        self.tess_mag = True
+        self._set_store(_lib.CELL_TESS_MVI_DATA, cols=3, rows=len(comps), table=True)
 
     def tess_b_result(self, component, mag3):
         """tf, bx, by or bz (uT; component a name or BCOMP_* value) at the observation points of a tesseroid
@@ -281,9 +287,9 @@ class Engine(object):
         (gh_tess_b_result); kernel_stats() then reports this pass."""
         comp = _lib.BCOMPONENTS.get(component, -1) if isinstance(component, str) else int(component)
         m = f64(mag3)
-        if not getattr(self, "tess_mag", False) or m.shape != (self.M // 3, 3):
+        if not self.tess_mag or m.shape != (self.M // 3, 3):
             raise ValueError("magnetization must be (M/3, 3) on a tesseroid magnetization context")
-        out = np.empty(self.N // self.multi)
+        out = np.empty(self.N // self._store.rows)
         self._chk(self._lib.gh_tess_b_result(self._h, comp, ptr(m), ptr(out)))
         return out
 
@@ -325,7 +331,7 @@ class Engine(object):
         """Total-field anomaly (uT) of the CELL_PRISM_TF or CELL_PRISM_MVI cells magnetized with mag3[M, 3] (A/m), in the
         reference's accumulation order (gh_tf_result); needs no G."""
         m = f64(mag3)
-        cells = self.M // 3 if getattr(self, "mvi", False) else self.M   # (magnetization-vector context: M/3 prisms)
+        cells = self.M // 3 if self.mvi else self.M   # (magnetization-vector context: M/3 prisms)
         if m.shape != (cells, 3):
             raise ValueError("magnetization must be (%s, 3)" % ("M/3" if cells != self.M else "M"))
         out = np.empty(self.N)
@@ -423,7 +429,7 @@ class Engine(object):
 
     def download_G(self):
         """The stored kernel, N x M, Fortran-ordered; a joint context's store H = [Aw_gz | Aw_tf] is N/2 x M."""
-        rows = self.N // 2 if getattr(self, "joint", False) else self.N
+        rows = self.N // 2 if self.joint else self.N
         A = np.empty((self.M, rows))
         self._chk(self._lib.gh_download_G(self._h, ptr(A), rows))
         return A.T  # rows x M, Fortran-ordered view

@@ -299,6 +299,6 @@ class TesseroidMultiComponentModule(MultiComponentModule):
         return super().kernel(component)
 
     def block_means(self):
-        if getattr(self._engine, "multi", 1) == 1 and self.components == ("gz",) and self.weights[0] == 1.0:
+        if not self._engine._store.table:
             raise ValueError("block_means: the module has one block of unweighted gz (GravMagModule's store)")
         return super().block_means()
