@@ -178,6 +178,52 @@ static int dense_single_chain_refuse(gh_ctx *c, const char *who)
     return GH_OK;
 }
 
+// ------------------------------------------------------------------------- what a tesseroid pass reports
+
+// The two device buffers a pass of the tesseroid engine reports into -- the error codes summed per cell, the leaf count
+// with the overflow flag -- from their allocation to their release on every way out.  open() allocates and zeroes them
+// on the context's stream; the caller launches its kernels with err_cell and stats; harvest() waits for them.
+struct TessHarvest {
+    int *err_cell = nullptr;
+    TessStats *stats = nullptr;
+    int64_t cells = 0;
+    TessHarvest() = default;
+    TessHarvest(const TessHarvest &) = delete;
+    TessHarvest &operator=(const TessHarvest &) = delete;
+    ~TessHarvest()
+    {
+        (void)hipFree(err_cell);
+        (void)hipFree(stats);
+    }
+    int open(gh_ctx *c, const char *who, int64_t n_cells)
+    {
+        cells = n_cells;
+        if (hipMalloc((void **)&err_cell, sizeof(int) * (size_t)std::max<int64_t>(cells, 1)) != hipSuccess ||
+            hipMalloc((void **)&stats, sizeof(TessStats)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, GH_ERR_NOMEM, "%s: device allocation of the tesseroid pass's buffers failed", who);
+        }
+        HIPCHK(c, hipMemsetAsync(err_cell, 0, sizeof(int) * (size_t)cells, c->stream));
+        HIPCHK(c, hipMemsetAsync(stats, 0, sizeof(TessStats), c->stream));
+        return GH_OK;
+    }
+    // After the launch: the cells with a non-zero code and the leaves of the pass; GH_ERR_OVERFLOW when a stack was full
+    // (the counts are then the pass's all the same; any other error leaves them as they are).
+    int harvest(gh_ctx *c, int64_t &flagged, int64_t &leaves)
+    {
+        HIPCHK(c, hipGetLastError());
+        std::vector<int> herr((size_t)cells);
+        TessStats hs{};
+        HIPCHK(c, hipMemcpyAsync(herr.data(), err_cell, sizeof(int) * (size_t)cells, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&hs, stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        flagged = (int64_t)std::count_if(herr.begin(), herr.end(), [](int v) { return v != 0; });
+        leaves = (int64_t)hs.leaves;
+        if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
+        return GH_OK;
+    }
+};
+
 // ------------------------------------------------------------------------- the assembly of the dense store
 
 // tess_comp_kernel of one field at one ratio over all (observation, cell) pairs: `rows` rows of every column of the
@@ -195,37 +241,16 @@ static int tess_comp_assemble(gh_ctx *c, const double *conv, double *G, int comp
                                 tess_comp_kernel<GH_COMP_GXY>,       tess_comp_kernel<GH_COMP_GXZ>,
                                 tess_comp_kernel<GH_COMP_GYY>,       tess_comp_kernel<GH_COMP_GYZ>,
                                 tess_comp_kernel<GH_COMP_GZZ>};
-    int *err_cell = nullptr;
-    TessStats *stats = nullptr;
-    HIPCHK(c, hipMalloc((void **)&err_cell, sizeof(int) * (size_t)std::max<int64_t>(c->M, 1)));
-    if (hipMalloc((void **)&stats, sizeof(TessStats)) != hipSuccess) {
-        (void)hipGetLastError();
-        hipFree(err_cell);
-        return fail(c, GH_ERR_NOMEM, "gh_build_G: device allocation of the tesseroid statistics failed");
-    }
-    std::vector<int> herr((size_t)c->M);
-    TessStats hs{};
-    hipError_t e = hipMemsetAsync(err_cell, 0, sizeof(int) * (size_t)c->M, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(stats, 0, sizeof(TessStats), c->stream);
-    if (e == hipSuccess) {
-        const int64_t blocks = std::min<int64_t>((rows * c->M + 63) / 64, 1 << 24);
-        hipLaunchKernelGGL(fns[comp], dim3((unsigned)blocks), dim3(64), 0, c->stream, conv, conv + N, conv + 2 * N,
-                           conv + 3 * N, (const double *)c->bounds, N, c->M, rows, c->ld, ratio, comp, G, err_cell,
-                           stats);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(herr.data(), err_cell, sizeof(int) * (size_t)c->M, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&hs, stats, sizeof hs, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(err_cell);
-    hipFree(stats);
-    HIPCHK(c, e);
-    for (int v : herr)
-        if (v != 0) c->warn_cells += 1;
-    c->leaves += (int64_t)hs.leaves;
-    if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
-    return GH_OK;
+    TessHarvest h;
+    TRY(h.open(c, "gh_build_G", c->M));
+    const int64_t blocks = std::min<int64_t>((rows * c->M + 63) / 64, 1 << 24);
+    hipLaunchKernelGGL(fns[comp], dim3((unsigned)blocks), dim3(64), 0, c->stream, conv, conv + N, conv + 2 * N, conv + 3 * N,
+                       (const double *)c->bounds, N, c->M, rows, c->ld, ratio, comp, G, h.err_cell, h.stats);
+    int64_t flagged = 0, leaves = 0;
+    const int rc = h.harvest(c, flagged, leaves);
+    c->warn_cells += flagged;
+    c->leaves += leaves;
+    return rc;
 }
 
 // prism_kernel of one field (GH_COMP_*, or PRISM_TF) into `rows` rows of every column of the dense store, from G on:
@@ -255,45 +280,20 @@ static int prism_assemble(gh_ctx *c, int field, int64_t N, int64_t rows, double 
 static int tess_mag_pass(gh_ctx *c, const char *who, const std::function<void(const TessMagObs &, const double *, int *, TessStats *)> &launch)
 {
     const int64_t m = store_cells(c), Nb = store_points(c);
-    double *buf = nullptr;
-    int *err_cell = nullptr;
-    TessStats *stats = nullptr;
-    auto release = [&]() {
-        hipFree(buf);
-        hipFree(err_cell);
-        hipFree(stats);
-    };
-    if (hipMalloc((void **)&buf, sizeof(double) * (size_t)(6 * Nb + TESS_MAG_FRAME * m)) != hipSuccess ||
-        hipMalloc((void **)&err_cell, sizeof(int) * (size_t)m) != hipSuccess ||
-        hipMalloc((void **)&stats, sizeof(TessStats)) != hipSuccess) {
-        (void)hipGetLastError();
-        release();
-        return fail(c, GH_ERR_NOMEM, "%s: device allocation of the tesseroid pass's buffers failed", who);
-    }
-    double *frame = buf + 6 * Nb;
-    const TessMagObs o{buf, buf + Nb, buf + 2 * Nb, buf + 3 * Nb, buf + 4 * Nb, buf + 5 * Nb};
-    std::vector<int> herr((size_t)m);
-    TessStats hs{};
-    hipError_t e = hipMemsetAsync(err_cell, 0, sizeof(int) * (size_t)m, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(stats, 0, sizeof(TessStats), c->stream);
-    if (e == hipSuccess) {
-        tess_convert_kernel<<<dim3((unsigned)((Nb + 255) / 256)), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], Nb, buf, buf + Nb, buf + 2 * Nb, buf + 3 * Nb, buf + 4 * Nb, buf + 5 * Nb);
-        tess_mag_cellframe_kernel<<<dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream>>>(c->bounds, m, frame);
-        launch(o, frame, err_cell, stats);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(herr.data(), err_cell, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&hs, stats, sizeof hs, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    release();
-    HIPCHK(c, e);
-    c->warn_cells = 0;
-    for (int v : herr)
-        if (v != 0) c->warn_cells += 1;
-    c->leaves = (int64_t)hs.leaves;
-    if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
-    return GH_OK;
+    struct Buf {
+        double *p = nullptr;
+        ~Buf() { (void)hipFree(p); }
+    } buf;
+    HIPCHK(c, hipMalloc((void **)&buf.p, sizeof(double) * (size_t)(6 * Nb + TESS_MAG_FRAME * m)));
+    TessHarvest h;
+    TRY(h.open(c, who, m));
+    double *o6 = buf.p, *frame = buf.p + 6 * Nb;
+    const TessMagObs o{o6, o6 + Nb, o6 + 2 * Nb, o6 + 3 * Nb, o6 + 4 * Nb, o6 + 5 * Nb};
+    tess_convert_kernel<<<dim3((unsigned)((Nb + 255) / 256)), dim3(256), 0, c->stream>>>(
+        c->obs[0], c->obs[1], c->obs[2], Nb, o6, o6 + Nb, o6 + 2 * Nb, o6 + 3 * Nb, o6 + 4 * Nb, o6 + 5 * Nb);
+    tess_mag_cellframe_kernel<<<dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream>>>(c->bounds, m, frame);
+    launch(o, frame, h.err_cell, h.stats);
+    return h.harvest(c, c->warn_cells, c->leaves);
 }
 
 // the data components of a store of magnetic data, as its assembly kernels take them

@@ -274,34 +274,28 @@ static int lonsym_build(gh_ctx *c)
         }
     for (int64_t cc = 0; cc < nc1; ++cc) memcpy(&sb[(size_t)cc * 6], &b[(size_t)(cc * n) * 6], 6 * sizeof(double));
     double *d_so = nullptr, *d_sb = nullptr, *conv = nullptr;
-    int *err_cell = nullptr;
-    TessStats *stats = nullptr;
     TRY(dalloc(c, &h.T, (size_t)h.ldT * (size_t)nc, false));
     // (the temporaries of the build: released on every way out of this block; the magnetization store's cell frames
     // and class directions are the last two)
     struct Tmp {
-        void *p[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
         ~Tmp() { for (void *q : p) if (q) (void)hipFree(q); }
     } tmp;
     HIPCHK(c, hipMalloc(&tmp.p[0], sizeof(double) * so.size()));
     HIPCHK(c, hipMalloc(&tmp.p[1], sizeof(double) * sb.size()));
     HIPCHK(c, hipMalloc(&tmp.p[2], sizeof(double) * (h.mag ? 6 : 4) * (size_t)Np));
-    HIPCHK(c, hipMalloc(&tmp.p[3], sizeof(int) * (size_t)nc));
-    HIPCHK(c, hipMalloc(&tmp.p[4], sizeof(TessStats)));
-    if (h.mag) HIPCHK(c, hipMalloc(&tmp.p[5], sizeof(double) * TESS_MAG_FRAME * (size_t)nc1));
+    if (h.mag) HIPCHK(c, hipMalloc(&tmp.p[3], sizeof(double) * TESS_MAG_FRAME * (size_t)nc1));
     if (mag_tf) {
-        HIPCHK(c, hipMalloc(&tmp.p[6], sizeof(double) * sfd.size()));
-        HIPCHK(c, hipMemcpyAsync(tmp.p[6], sfd.data(), sizeof(double) * sfd.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMalloc(&tmp.p[4], sizeof(double) * sfd.size()));
+        HIPCHK(c, hipMemcpyAsync(tmp.p[4], sfd.data(), sizeof(double) * sfd.size(), hipMemcpyHostToDevice, c->stream));
     }
+    TessHarvest pass;
+    TRY(pass.open(c, "gh_build_G", nc));
     d_so = static_cast<double *>(tmp.p[0]);
     d_sb = static_cast<double *>(tmp.p[1]);
     conv = static_cast<double *>(tmp.p[2]);
-    err_cell = static_cast<int *>(tmp.p[3]);
-    stats = static_cast<TessStats *>(tmp.p[4]);
     HIPCHK(c, hipMemcpyAsync(d_so, so.data(), sizeof(double) * so.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_sb, sb.data(), sizeof(double) * sb.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(err_cell, 0, sizeof(int) * (size_t)nc, c->stream));
-    HIPCHK(c, hipMemsetAsync(stats, 0, sizeof(TessStats), c->stream));
     if (h.mag)
         tess_convert_kernel<<<dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, c->stream>>>(
             d_so, d_so + Np, d_so + 2 * Np, Np, conv, conv + Np, conv + 2 * Np, conv + 3 * Np, conv + 4 * Np, conv + 5 * Np);
@@ -323,12 +317,12 @@ static int lonsym_build(gh_ctx *c)
             bc.comp[bb] = c->mc.comp[bb];
             bw.w[bb] = c->mc.w[bb];
         }
-        double *frame = static_cast<double *>(tmp.p[5]);
+        double *frame = static_cast<double *>(tmp.p[3]);
         tess_mag_cellframe_kernel<<<dim3((unsigned)((nc1 + 255) / 256)), dim3(256), 0, c->stream>>>(d_sb, nc1, frame);
         const TessMagObs o{conv, conv + Np, conv + 2 * Np, conv + 3 * Np, conv + 4 * Np, conv + 5 * Np};
         tess_mag_table_kernel<<<dim3((unsigned)std::min<int64_t>((Lr * nc1 + 63) / 64, 1 << 24)), dim3(64), 0, c->stream>>>(
-            o, d_sb, frame, mag_tf ? static_cast<const double *>(tmp.p[6]) : nullptr, Np1, nc1, h.ldT, c->ratio, bc, bw, h.T,
-            err_cell, stats);
+            o, d_sb, frame, mag_tf ? static_cast<const double *>(tmp.p[4]) : nullptr, Np1, nc1, h.ldT, c->ratio, bc, bw, h.T,
+            pass.err_cell, pass.stats);
     } else if (h.multi) {
         // every class by its own field at its own ratio, times its block's data weight: ONE launch
         TessBlocks tb{};
@@ -339,24 +333,19 @@ static int lonsym_build(gh_ctx *c)
             tb.w[bb] = c->mc.w[bb];
         }
         tess_multi_table_kernel<<<dim3((unsigned)std::min<int64_t>((total + 63) / 64, 1 << 24)), dim3(64), 0, c->stream>>>(
-            conv, conv + Np, conv + 2 * Np, conv + 3 * Np, d_sb, Np, nc, h.ldT, na1 * n, tb, h.T, err_cell, stats);
+            conv, conv + Np, conv + 2 * Np, conv + 3 * Np, d_sb, Np, nc, h.ldT, na1 * n, tb, h.T, pass.err_cell, pass.stats);
     } else {
         tess_comp_kernel<COMP_GZ><<<dim3((unsigned)std::min<int64_t>((total + 63) / 64, 1 << 24)), dim3(64), 0, c->stream>>>(
-            conv, conv + Np, conv + 2 * Np, conv + 3 * Np, d_sb, Np, nc, h.ldT, h.ldT, c->ratio, COMP_GZ, h.T, err_cell, stats);
+            conv, conv + Np, conv + 2 * Np, conv + 3 * Np, d_sb, Np, nc, h.ldT, h.ldT, c->ratio, COMP_GZ, h.T, pass.err_cell,
+            pass.stats);
     }
-    HIPCHK(c, hipGetLastError());
-    TessStats hs;
-    std::vector<int> herr((size_t)nc);
-    HIPCHK(c, hipMemcpyAsync(&hs, stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(herr.data(), err_cell, sizeof(int) * (size_t)nc, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (hs.overflow) return fail(c, GH_ERR_OVERFLOW, "tesseroid stack overflow (> %d entries)", TESS_STACK);
     // a cell of longitude index 0 that could not be divided further stands for its whole row of n cells:
     // the count gh_kernel_stats reports is the dense build's (the reference's warning, potential.py:134)
-    // (magnetization store: the nc1 cells' codes, once per cell whatever the axis; the rest of herr is zero)
-    for (int v : herr)
-        if (v != 0) c->warn_cells += n;
-    c->leaves = (int64_t)hs.leaves;
+    // (magnetization store: the nc1 cells' codes, once per cell whatever the axis; the other cells' are zero)
+    int64_t flagged = 0, leaves = 0;
+    TRY(pass.harvest(c, flagged, leaves));
+    c->warn_cells += n * flagged;
+    c->leaves = leaves;
     // slots (a, m) -> observations, ascending: the first one per slot, and the further ones of the few
     // slots that hold several (duplicated longitudes); LDS offset of every observation's slot
     std::vector<int> sfirst((size_t)Np, -1), xslot, xptr(1, 0), xobs, ldsof((size_t)Ns);

@@ -1323,10 +1323,34 @@ __device__ __forceinline__ double safe_log_d(double x)
     return log(x);
 }
 
-// The 8-corner sum of every prism field (_prism.pyx's loops): acc plus, over the corners of the prism b
-// (k: z2, z1; then j: y2, y1; then i: x2, x1), (-1)^(i+j+k) corner(dx, dy, dz) with (dx, dy, dz) = corner -
-// observation, into the one accumulator in this order.  The result forms fold the density or the
-// magnetization into corner(): multiplying by the sign +-1 is exact, so where it happens changes no bit.
+// The 8 corners of the prism b in the order every prism field sums them (_prism.pyx's loops: k: z2, z1; then j: y2,
+// y1; then i: x2, x1): f(sign, dx, dy, dz) with sign = (-1)^(i+j+k) and (dx, dy, dz) = corner - observation.
+template <class F>
+__device__ __forceinline__ void prism_each_corner(double px, double py, double pz, const double *b, F f)
+{
+#pragma clang fp contract(off)
+    const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double dz = Z[k] - pz;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const double dy = Y[j] - py;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const double dx = X[i] - px;
+                f(((i + j + k) & 1) ? -1.0 : 1.0, dx, dy, dz);
+            }
+        }
+    }
+}
+
+// The 8-corner sum of a prism field: acc plus sign * corner(dx, dy, dz) over prism_each_corner's corners, into the one
+// accumulator in that order.  The result forms fold the density or the magnetization into corner(): multiplying
+// by the sign +-1 is exact, so where it happens changes no bit.  (The loop is written out: on prism_each_corner the
+// compile of the whole library -- not that of the build's code check, whose code stays the same -- gives the 1024-thread
+// matrix-free kernels of potential / geoid / gx / gy, which spill as they are, 8 more bytes of scratch per lane
+// (mf_fused_kernel<1024, 4 / 16, 7>); this form keeps every gravity kernel's code as it was.)
 template <class F>
 __device__ __forceinline__ double prism_corners(double acc, double px, double py, double pz, const double *b,
                                                 F corner)
@@ -1350,27 +1374,40 @@ __device__ __forceinline__ double prism_corners(double acc, double px, double py
     return acc;
 }
 
+// The six second derivatives of 1/r at one corner (_prism.pyx:52-78: kernelxx, xy, xz, yy, yz, zz), behind the one
+// distance: the magnetic fields of prisms are sums of these and of nothing else.  A caller that reads three of them
+// pays for three.
+struct PrismV {
+    double v1, v2, v3, v4, v5, v6;
+};
+__device__ __forceinline__ PrismV prism_v6(double dx, double dy, double dz)
+{
+#pragma clang fp contract(off)
+    const double r = sqrt(dx * dx + dy * dy + dz * dz);
+    PrismV v;
+    v.v1 = -safe_atan2_d(dz * dy, dx * r);
+    v.v2 = safe_log_d(dz + r);
+    v.v3 = safe_log_d(dy + r);
+    v.v4 = -safe_atan2_d(dz * dx, dy * r);
+    v.v5 = safe_log_d(dx + r);
+    v.v6 = -safe_atan2_d(dx * dy, dz * r);
+    return v;
+}
+
 // CM * T2NT of the reference (constants.py:37,41): 10**-7 * 10**6 rounds to 0.09999999999999999; entries in
 // uT per A/m of magnetization along the field (T2NT is 10**6 there, not the 10**9 of an nT scale)
 #define TF_SCALE (1e-7 * 1e6)
 
-// f.(V m) at one corner, V the six second derivatives of 1/r there (_prism.pyx:52-78: kernelxx, xy, xz, yy,
-// yz, zz), in the reference's order -- b = V m first, then f.b (_prism.pyx:80-113, prism.py:665-733), not the
-// shorter quadratic form, which rounds differently.
+// f.(V m) at one corner, V = prism_v6 there, in the reference's order -- b = V m first, then f.b
+// (_prism.pyx:80-113, prism.py:665-733), not the shorter quadratic form, which rounds differently.
 __device__ __forceinline__ double prism_tf_corner(double dx, double dy, double dz, double mx, double my, double mz,
                                                   double fx, double fy, double fz)
 {
 #pragma clang fp contract(off)
-    const double r = sqrt(dx * dx + dy * dy + dz * dz);
-    const double v1 = -safe_atan2_d(dz * dy, dx * r);
-    const double v2 = safe_log_d(dz + r);
-    const double v3 = safe_log_d(dy + r);
-    const double v4 = -safe_atan2_d(dz * dx, dy * r);
-    const double v5 = safe_log_d(dx + r);
-    const double v6 = -safe_atan2_d(dx * dy, dz * r);
-    const double bx = v1 * mx + v2 * my + v3 * mz;
-    const double by = v2 * mx + v4 * my + v5 * mz;
-    const double bz = v3 * mx + v5 * my + v6 * mz;
+    const PrismV v = prism_v6(dx, dy, dz);
+    const double bx = v.v1 * mx + v.v2 * my + v.v3 * mz;
+    const double by = v.v2 * mx + v.v4 * my + v.v5 * mz;
+    const double bz = v.v3 * mx + v.v5 * my + v.v6 * mz;
     return fx * bx + fy * by + fz * bz;
 }
 
@@ -1557,9 +1594,10 @@ __global__ void __launch_bounds__(256) scale_rowblocks_kernel(double *__restrict
 // Joint gravity-magnetic store (GH_CELL_PRISM_JOINT): one thread per (obs, cell) pair writes both blocks of
 // H = [A_gz | A_tf], the gz entry to column c and the tf entry to column m + c.  One corner loop serves both
 // fields: the distance r, log(dx + r), log(dy + r) and atan2(dx dy, dz r) of a corner are the same function
-// of the same operands in gz's and tf's corner (prism_comp_corner<COMP_GZ>, prism_tf_corner), so computing
-// them once changes no bit; each field keeps its own accumulator, in prism_corners' order, and its own
-// scale.  Every entry equals prism_kernel<COMP_GZ> / prism_kernel<PRISM_TF>'s bit for bit.
+// of the same operands in gz's and tf's corner (prism_comp_corner<COMP_GZ>, prism_tf_corner), so gz's corner reads
+// them from prism_v6 -- v3, v5 and -v6, the negation exact -- and no bit changes; each field keeps its own
+// accumulator, in prism_corners' order, and its own scale.  Every entry equals prism_kernel<COMP_GZ> /
+// prism_kernel<PRISM_TF>'s bit for bit.
 __global__ void __launch_bounds__(256)
 prism_joint_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
                    const double *__restrict__ bounds6, int64_t N, int64_t m, int64_t ld, double3 dir,
@@ -1572,35 +1610,16 @@ prism_joint_kernel(const double *__restrict__ xp, const double *__restrict__ yp,
         const int64_t c = idx / ld, l = idx - c * ld;
         double vg = 0.0, vt = 0.0;
         if (l < N) {
-            const double px = xp[l], py = yp[l], pz = zp[l];
-            const double *b = bounds6 + 6 * c;
-            const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
             double ag = 0.0, at = 0.0;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const double dz = Z[k] - pz;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const double dy = Y[j] - py;
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        const double dx = X[i] - px;
-                        const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
-                        const double r = sqrt(dx * dx + dy * dy + dz * dz);
-                        const double lyr = safe_log_d(dy + r), lxr = safe_log_d(dx + r);
-                        const double azz = safe_atan2_d(dx * dy, dz * r);
-                        ag += sign * -(dx * lyr + dy * lxr - dz * azz);
-                        const double v1 = -safe_atan2_d(dz * dy, dx * r);
-                        const double v2 = safe_log_d(dz + r);
-                        const double v4 = -safe_atan2_d(dz * dx, dy * r);
-                        const double v6 = -azz;
-                        const double bx = v1 * fx + v2 * fy + lyr * fz;
-                        const double by = v2 * fx + v4 * fy + lxr * fz;
-                        const double bz = lyr * fx + lxr * fy + v6 * fz;
-                        at += sign * (fx * bx + fy * by + fz * bz);
-                    }
-                }
-            }
+            prism_each_corner(xp[l], yp[l], zp[l], bounds6 + 6 * c, [&](double sign, double dx, double dy, double dz) {
+#pragma clang fp contract(off)
+                const PrismV v = prism_v6(dx, dy, dz);
+                ag += sign * -(dx * v.v3 + dy * v.v5 - dz * -v.v6);
+                const double bx = v.v1 * fx + v.v2 * fy + v.v3 * fz;
+                const double by = v.v2 * fx + v.v4 * fy + v.v5 * fz;
+                const double bz = v.v3 * fx + v.v5 * fy + v.v6 * fz;
+                at += sign * (fx * bx + fy * by + fz * bz);
+            });
             vg = ag * prism_comp_scale<COMP_GZ>();
             vt = at * TF_SCALE;
         }
@@ -1627,32 +1646,13 @@ prism_mvi_kernel(const double *__restrict__ xp, const double *__restrict__ yp, c
         const int64_t c = idx / ld, l = idx - c * ld;
         double ax = 0.0, ay = 0.0, az = 0.0;
         if (l < N) {
-            const double px = xp[l], py = yp[l], pz = zp[l];
-            const double *b = bounds6 + 6 * c;
-            const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const double dz = Z[k] - pz;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const double dy = Y[j] - py;
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        const double dx = X[i] - px;
-                        const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
-                        const double r = sqrt(dx * dx + dy * dy + dz * dz);
-                        const double v1 = -safe_atan2_d(dz * dy, dx * r);
-                        const double v2 = safe_log_d(dz + r);
-                        const double v3 = safe_log_d(dy + r);
-                        const double v4 = -safe_atan2_d(dz * dx, dy * r);
-                        const double v5 = safe_log_d(dx + r);
-                        const double v6 = -safe_atan2_d(dx * dy, dz * r);
-                        ax += sign * (fx * v1 + fy * v2 + fz * v3);
-                        ay += sign * (fx * v2 + fy * v4 + fz * v5);
-                        az += sign * (fx * v3 + fy * v5 + fz * v6);
-                    }
-                }
-            }
+            prism_each_corner(xp[l], yp[l], zp[l], bounds6 + 6 * c, [&](double sign, double dx, double dy, double dz) {
+#pragma clang fp contract(off)
+                const PrismV v = prism_v6(dx, dy, dz);
+                ax += sign * (fx * v.v1 + fy * v.v2 + fz * v.v3);
+                ay += sign * (fx * v.v2 + fy * v.v4 + fz * v.v5);
+                az += sign * (fx * v.v3 + fy * v.v5 + fz * v.v6);
+            });
         }
         // (coalesced: consecutive threads, consecutive rows of one column, in each of the three blocks)
         A[c * ld + l] = ax * TF_SCALE;
@@ -1698,40 +1698,21 @@ prism_mvi_data_kernel(const double *__restrict__ xp, const double *__restrict__ 
             A[(2 * m + c) * ld + row] = 0.0;
             continue;
         }
-        const double px = xp[l], py = yp[l], pz = zp[l];
-        const double *b = bounds6 + 6 * c;
-        const double X[2] = {b[1], b[0]}, Y[2] = {b[3], b[2]}, Z[2] = {b[5], b[4]};
         double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0, s6 = 0.0;
         double ax = 0.0, ay = 0.0, az = 0.0;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const double dz = Z[k] - pz;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const double dy = Y[j] - py;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const double dx = X[i] - px;
-                    const double sign = ((i + j + k) & 1) ? -1.0 : 1.0;
-                    const double r = sqrt(dx * dx + dy * dy + dz * dz);
-                    const double v1 = -safe_atan2_d(dz * dy, dx * r);
-                    const double v2 = safe_log_d(dz + r);
-                    const double v3 = safe_log_d(dy + r);
-                    const double v4 = -safe_atan2_d(dz * dx, dy * r);
-                    const double v5 = safe_log_d(dx + r);
-                    const double v6 = -safe_atan2_d(dx * dy, dz * r);
-                    s1 += sign * v1;
-                    s2 += sign * v2;
-                    s3 += sign * v3;
-                    s4 += sign * v4;
-                    s5 += sign * v5;
-                    s6 += sign * v6;
-                    ax += sign * (fx * v1 + fy * v2 + fz * v3);
-                    ay += sign * (fx * v2 + fy * v4 + fz * v5);
-                    az += sign * (fx * v3 + fy * v5 + fz * v6);
-                }
-            }
-        }
+        prism_each_corner(xp[l], yp[l], zp[l], bounds6 + 6 * c, [&](double sign, double dx, double dy, double dz) {
+#pragma clang fp contract(off)
+            const PrismV v = prism_v6(dx, dy, dz);
+            s1 += sign * v.v1;
+            s2 += sign * v.v2;
+            s3 += sign * v.v3;
+            s4 += sign * v.v4;
+            s5 += sign * v.v5;
+            s6 += sign * v.v6;
+            ax += sign * (fx * v.v1 + fy * v.v2 + fz * v.v3);
+            ay += sign * (fx * v.v2 + fy * v.v4 + fz * v.v5);
+            az += sign * (fx * v.v3 + fy * v.v5 + fz * v.v6);
+        });
         // (coalesced: consecutive threads, consecutive rows of one column, in every block)
 #pragma unroll
         for (int q = 0; q < BCOMP_MAX; ++q) {
@@ -1752,7 +1733,7 @@ prism_mvi_data_kernel(const double *__restrict__ xp, const double *__restrict__ 
 // prism._bx / _by / _bz's `res` (prism.py:735-870): one thread per observation, the cells in mesh order, ONE sum per
 // observation over every corner of every cell of (-1)^(i+j+k) (row B of V) . m_c with the cell's magnetization m_c =
 // mag3[3c .. 3c+2], scaled once at the end -- the reference's accumulation order.  Only the three derivatives of
-// the component's row are evaluated, as _prism.bx / by / bz do.
+// the component's row are read, so only they are evaluated, as _prism.bx / by / bz do.
 template <int B>
 __global__ void __launch_bounds__(256)
 prism_b_result_kernel(const double *__restrict__ xp, const double *__restrict__ yp, const double *__restrict__ zp,
@@ -1767,23 +1748,14 @@ prism_b_result_kernel(const double *__restrict__ xp, const double *__restrict__ 
     for (int64_t c = 0; c < M; ++c) {
         const double mx = mag3[3 * c], my = mag3[3 * c + 1], mz = mag3[3 * c + 2];
         acc = prism_corners(acc, px, py, pz, bounds6 + 6 * c, [&](double dx, double dy, double dz) {
-            const double r = sqrt(dx * dx + dy * dy + dz * dz);
-            if constexpr (B == BCOMP_BX) {
-                const double v1 = -safe_atan2_d(dz * dy, dx * r);
-                const double v2 = safe_log_d(dz + r);
-                const double v3 = safe_log_d(dy + r);
-                return v1 * mx + v2 * my + v3 * mz;
-            } else if constexpr (B == BCOMP_BY) {
-                const double v2 = safe_log_d(dz + r);
-                const double v4 = -safe_atan2_d(dz * dx, dy * r);
-                const double v5 = safe_log_d(dx + r);
-                return v2 * mx + v4 * my + v5 * mz;
-            } else {
-                const double v3 = safe_log_d(dy + r);
-                const double v5 = safe_log_d(dx + r);
-                const double v6 = -safe_atan2_d(dx * dy, dz * r);
-                return v3 * mx + v5 * my + v6 * mz;
-            }
+#pragma clang fp contract(off)
+            const PrismV v = prism_v6(dx, dy, dz);
+            if constexpr (B == BCOMP_BX)
+                return v.v1 * mx + v.v2 * my + v.v3 * mz;
+            else if constexpr (B == BCOMP_BY)
+                return v.v2 * mx + v.v4 * my + v.v5 * mz;
+            else
+                return v.v3 * mx + v.v5 * my + v.v6 * mz;
         });
     }
     res[l] = acc * TF_SCALE;
@@ -2001,15 +1973,16 @@ __device__ __forceinline__ double tess_comp_scale(int comp, double acc)
     }
 }
 
-// One (observation, tesseroid) entry of a field, unscaled: the reference's adaptive 2x2x2 Gauss-Legendre
-// engine (_tesseroid_numba.py:32-71, 75-157, 207-222: distance_size, divisions, split) with a private
-// 100-entry LIFO stack of sub-tesseroids and the field's leaf.  error_code accumulates the engine's error
-// codes (non-zero => the reference warns), nleaf counts GLQ leaves, overflow flags a full stack.  LEAF < 0:
-// the leaf of `comp`, chosen at run time.
-template <int LEAF>
-__device__ double tess_comp_entry(int comp, double lon, double sinlat, double coslat, double radius,
-                                  const double *bounds, double ratio, int &error_code, unsigned long long &nleaf,
-                                  bool &overflow)
+// The reference's adaptive subdivision of one (observation, tesseroid) pair (_tesseroid_numba.py:32-71, 75-157:
+// distance_size, divisions, split, scale_nodes) with a private 100-entry LIFO stack of sub-tesseroids -- written
+// here ONCE, for every field of tesseroids.  A sub-tesseroid that is not split is a leaf: leaf(lonc, sinlatc, coslatc,
+// rc, scale) gets its 2x2x2 Gauss-Legendre nodes and its weight and adds what the field sums.  error_code
+// accumulates the engine's error codes (non-zero => the reference warns), nleaf counts the leaves, overflow flags
+// a full stack.
+template <class Leaf>
+__device__ __forceinline__ void tess_traverse(double lon, double sinlat, double coslat, double radius,
+                                              const double *bounds, double ratio, int &error_code,
+                                              unsigned long long &nleaf, bool &overflow, Leaf leaf)
 {
 #pragma clang fp contract(off)
     const double MEAN_R = 6378137.0;
@@ -2019,7 +1992,6 @@ __device__ double tess_comp_entry(int comp, double lon, double sinlat, double co
 #pragma unroll
     for (int q = 0; q < 6; ++q) stack[0][q] = bounds[q];
     int stktop = 0;
-    double acc = 0.0;
     while (stktop >= 0) {
         const double w = stack[stktop][0], e = stack[stktop][1], s = stack[stktop][2],
                      n = stack[stktop][3], top = stack[stktop][4], bottom = stack[stktop][5];
@@ -2078,15 +2050,43 @@ __device__ double tess_comp_entry(int comp, double lon, double sinlat, double co
                 coslatc[i] = cos(latc);
                 rc[i] = (0.5 * dr * node[i] + 0.5 * (top + bottom) + MEAN_R);
             }
-            const double scale = dlon * dlat * dr * 0.125;
-            const double k = LEAF >= 0 ? tess_comp_leaf<(LEAF >= 0 ? LEAF : 0)>(lon, sinlat, coslat, radius, lonc,
-                                                                                 sinlatc, coslatc, rc)
-                                       : tess_comp_leaf_rt(comp, lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc);
-            acc += scale * k;
+            leaf(lonc, sinlatc, coslatc, rc, dlon * dlat * dr * 0.125);
             nleaf += 1;
         }
     }
+}
+
+// One (observation, tesseroid) entry of a field, unscaled: tess_traverse with the field's GLQ leaf
+// (_tesseroid_numba.py:207-222), every leaf times its weight into one sum.  LEAF < 0: the leaf of `comp`, chosen at
+// run time.
+template <int LEAF>
+__device__ double tess_comp_entry(int comp, double lon, double sinlat, double coslat, double radius,
+                                  const double *bounds, double ratio, int &error_code, unsigned long long &nleaf,
+                                  bool &overflow)
+{
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    tess_traverse(lon, sinlat, coslat, radius, bounds, ratio, error_code, nleaf, overflow,
+                  [&](const double (&lonc)[2], const double (&sinlatc)[2], const double (&coslatc)[2],
+                      const double (&rc)[2], double scale) {
+#pragma clang fp contract(off)
+                      const double k = LEAF >= 0 ? tess_comp_leaf<(LEAF >= 0 ? LEAF : 0)>(lon, sinlat, coslat, radius, lonc,
+                                                                                           sinlatc, coslatc, rc)
+                                                 : tess_comp_leaf_rt(comp, lon, sinlat, coslat, radius, lonc, sinlatc,
+                                                                     coslatc, rc);
+                      acc += scale * k;
+                  });
     return acc;
+}
+
+// What a tesseroid pass reports besides its entries: the overflow flag, and one atomic per wave for the leaf count
+__device__ __forceinline__ void tess_report(unsigned long long nleaf, bool overflow, TessStats *stats)
+{
+    if (overflow) atomicExch(&stats->overflow, 1);
+    unsigned long long tot = nleaf;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) tot += __shfl_xor(tot, off, WAVE);
+    if ((threadIdx.x & 63) == 0) atomicAdd(&stats->leaves, tot);
 }
 
 // Dense assembly of one field, one thread per (obs, cell) pair, obs fastest, into `rows` rows of every column of a
@@ -2116,12 +2116,7 @@ tess_comp_kernel(const double *__restrict__ lon_r, const double *__restrict__ si
         if (G) G[c * ld + l] = tess_comp_scale(LEAF == COMP_POTENTIAL ? comp : LEAF, v);
         if (error_code != 0) atomicAdd(&err_cell[c], error_code);
     }
-    if (overflow) atomicExch(&stats->overflow, 1);
-    // one atomic per wave for the leaf count
-    unsigned long long tot = nleaf;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) tot += __shfl_xor(tot, off, WAVE);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&stats->leaves, tot);
+    tess_report(nleaf, overflow, stats);
 }
 
 // The row blocks of the tesseroid multi-component store (GH_CELL_TESSEROID_MULTI): field, ratio and data weight
@@ -2160,11 +2155,7 @@ tess_multi_table_kernel(const double *__restrict__ lon_r, const double *__restri
         T[idx] = tess_comp_scale(comp, v) * tb.w[b];
         if (error_code != 0) atomicAdd(&err_cell[c], error_code);
     }
-    if (overflow) atomicExch(&stats->overflow, 1);
-    unsigned long long tot = nleaf;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) tot += __shfl_xor(tot, off, WAVE);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&stats->leaves, tot);
+    tess_report(nleaf, overflow, stats);
 }
 
 // ------------------------------------------------------------- wavelet-compressed forward

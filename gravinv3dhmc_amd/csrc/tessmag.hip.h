@@ -10,7 +10,8 @@
 // midpoints of its lon / lat bounds; sub-tesseroids of the subdivision keep the parent's vector and frame): m_c is
 // given north-east-DOWN at the cell, the outputs are bx = B_x (north), by = B_y (east), bz = -B_zup (down) at the
 // observation.  ONE traversal of the subdivision per (observation, cell) pair serves all six sums: the distance /
-// size test, the stack and the nodes do not depend on the field, only the leaf's last expression does.
+// size test, the stack and the nodes do not depend on the field, only the leaf's last expression does -- so the
+// traversal is the gravity fields' own (tess_traverse), called with a leaf of six sums.
 #pragma once
 #include "kernels.hip.h"
 
@@ -83,90 +84,24 @@ __device__ __forceinline__ void tess_mag_leaf(double lon, double sinlat, double 
     }
 }
 
-// One (observation, tesseroid) pair: tess_comp_entry's traversal -- the same distance / size test, divisions,
-// split, private 100-entry LIFO stack, error codes, leaf count and overflow flag -- with all six sums accumulated
-// at every leaf, acc[q] += scale * V_leaf[q] as tess_comp_entry does for its one field.
+// One (observation, tesseroid) pair: tess_traverse (kernels.hip.h), the one traversal of every tesseroid field, with
+// all six sums accumulated at every leaf, acc[q] += scale * V_leaf[q] as tess_comp_entry does for its one field.
 __device__ void tess_mag_entry(double lon, double sinlat, double coslat, double radius, const double *bounds,
                                double ratio, int &error_code, unsigned long long &nleaf, bool &overflow,
                                double (&acc)[6])
 {
 #pragma clang fp contract(off)
-    const double MEAN_R = 6378137.0;
-    const double d2r = 3.14159265358979323846 / 180;
-    const double node[2] = {-0.577350269189625731058868041146, 0.577350269189625731058868041146};
-    double stack[TESS_STACK][6];
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
-        stack[0][q] = bounds[q];
-        acc[q] = 0.0;
-    }
-    int stktop = 0;
-    while (stktop >= 0) {
-        const double w = stack[stktop][0], e = stack[stktop][1], s = stack[stktop][2],
-                     n = stack[stktop][3], top = stack[stktop][4], bottom = stack[stktop][5];
-        stktop -= 1;
-        // distance_size
-        const double rt = 0.5 * (top + bottom) + MEAN_R;
-        const double lont = d2r * 0.5 * (w + e);
-        const double latt = d2r * 0.5 * (s + n);
-        const double sinlatt = sin(latt), coslatt = cos(latt);
-        const double cospsi0 = sinlat * sinlatt + coslat * coslatt * cos(lon - lont);
-        const double distance = sqrt(radius * radius + rt * rt - 2 * radius * rt * cospsi0);
-        const double rtop = top + MEAN_R;
-        const double Llon = rtop * acos(sinlatt * sinlatt + (coslatt * coslatt) * cos(d2r * (e - w)));
-        const double Llat =
-            rtop * acos(sin(d2r * n) * sin(d2r * s) + cos(d2r * n) * cos(d2r * s));
-        const double Lr = top - bottom;
-        // divisions
-        int nlon = 1, nlat = 1, nr = 1, err = 0;
-        if (distance <= ratio * Llon) {
-            if (Llon <= 0.1) err = -1; else nlon = 2;
-        }
-        if (distance <= ratio * Llat) {
-            if (Llat <= 0.1) err = -1; else nlat = 2;
-        }
-        if (distance <= ratio * Lr) {
-            if (Lr <= 1e3) err = -1; else nr = 2;
-        }
-        error_code += err;
-        const int new_cells = nlon * nlat * nr;
-        if (new_cells > 1) {
-            if (new_cells + (stktop + 1) > TESS_STACK) {
-                overflow = true;
-                break;
-            }
-            const double dlon = (e - w) / nlon, dlat = (n - s) / nlat, dr = (top - bottom) / nr;
-            for (int i = 0; i < nlon; ++i)
-                for (int j = 0; j < nlat; ++j)
-                    for (int k = 0; k < nr; ++k) {
-                        stktop += 1;
-                        stack[stktop][0] = w + i * dlon;
-                        stack[stktop][1] = w + (i + 1) * dlon;
-                        stack[stktop][2] = s + j * dlat;
-                        stack[stktop][3] = s + (j + 1) * dlat;
-                        stack[stktop][4] = bottom + (k + 1) * dr;
-                        stack[stktop][5] = bottom + k * dr;
-                    }
-        } else {
-            // scale_nodes
-            double lonc[2], sinlatc[2], coslatc[2], rc[2];
-            const double dlon = d2r * (e - w), dlat = d2r * (n - s), dr = top - bottom;
+    for (int q = 0; q < 6; ++q) acc[q] = 0.0;
+    tess_traverse(lon, sinlat, coslat, radius, bounds, ratio, error_code, nleaf, overflow,
+                  [&](const double (&lonc)[2], const double (&sinlatc)[2], const double (&coslatc)[2],
+                      const double (&rc)[2], double scale) {
+#pragma clang fp contract(off)
+                      double V[6];
+                      tess_mag_leaf(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc, V);
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                lonc[i] = 0.5 * dlon * node[i] + d2r * 0.5 * (e + w);
-                const double latc = 0.5 * dlat * node[i] + d2r * 0.5 * (n + s);
-                sinlatc[i] = sin(latc);
-                coslatc[i] = cos(latc);
-                rc[i] = (0.5 * dr * node[i] + 0.5 * (top + bottom) + MEAN_R);
-            }
-            const double scale = dlon * dlat * dr * 0.125;
-            double V[6];
-            tess_mag_leaf(lon, sinlat, coslat, radius, lonc, sinlatc, coslatc, rc, V);
-#pragma unroll
-            for (int q = 0; q < 6; ++q) acc[q] += scale * V[q];
-            nleaf += 1;
-        }
-    }
+                      for (int q = 0; q < 6; ++q) acc[q] += scale * V[q];
+                  });
 }
 
 // The observations as the kernels read them: tess_convert_kernel's six outputs, n values each
@@ -203,16 +138,6 @@ __device__ __forceinline__ void tess_mag_obs_frame(const TessMagObs &o, int64_t 
     uo[0] = cp * cl;
     uo[1] = cp * sl;
     uo[2] = sp;
-}
-
-// One wave's leaf count in one atomic, the overflow flag
-__device__ __forceinline__ void tess_mag_report(unsigned long long nleaf, bool overflow, TessStats *stats)
-{
-    if (overflow) atomicExch(&stats->overflow, 1);
-    unsigned long long tot = nleaf;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) tot += __shfl_xor(tot, off, WAVE);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&stats->leaves, tot);
 }
 
 // The data weights of the row blocks, for the shift-invariant table (which takes them when it is filled)
@@ -275,7 +200,7 @@ tess_mag_body(const TessMagObs &o, const double *__restrict__ bounds6, const dou
             }
         }
     }
-    tess_mag_report(nleaf, overflow, stats);
+    tess_report(nleaf, overflow, stats);
 }
 
 // Dense assembly (gh_build_G of a GH_CELL_TESS_MVI_DATA context without the table)
@@ -342,7 +267,7 @@ tess_mag_result_kernel(TessMagObs o, const double *__restrict__ bounds6, const d
         if (comp == BCOMP_TF) v = fdir[3 * l] * bx + fdir[3 * l + 1] * by + fdir[3 * l + 2] * bz;
         res[l] = v * TF_SCALE;
     }
-    tess_mag_report(nleaf, overflow, stats);
+    tess_report(nleaf, overflow, stats);
 }
 
 }  // namespace ghk
