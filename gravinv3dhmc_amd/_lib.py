@@ -169,6 +169,11 @@ PROTOTYPES = {
                                       C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(C.c_int)]),
     "gh_profile_read": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(_i64),
                                   C.POINTER(_i64)]),
+    "gh_set_translation_invariant": (C.c_int, [_ctx, C.c_int]),
+    "gh_translation_invariant_info": (C.c_int, [_ctx] + [C.POINTER(C.c_int)] * 6 + [C.POINTER(_i64), C.POINTER(C.c_double),
+                                                                                   C.POINTER(C.c_double)]),
+    "gh_translation_invariant_table": (C.c_int, [_ctx, _dp]),
+    "gh_lattice_detect": (C.c_int, [_i64, _dp, _dp, _dp, _i64, _dp] + [C.POINTER(C.c_int)] * 5),
 }
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _dp, _i64)

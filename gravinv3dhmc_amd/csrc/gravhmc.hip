@@ -15,6 +15,7 @@
 #include "lonres.hip.h"
 #include "lonsymw.hip.h"
 #include "fold.hip.h"
+#include "lattice.hip.h"
 #include "poststream.hip.h"
 #include "tessmag.hip.h"
 
@@ -55,6 +56,7 @@ static_assert(BCOMP_MAX == GH_BCOMP_MAX && BCOMP_MAX <= MULTI_MAX && BCOMP_TF ==
 #include "host_cells.h"
 #include "host_sweep.h"
 #include "host_fold.h"
+#include "host_lattice.h"
 #include "host_lonsym.h"
 #include "host_comm.h"
 #include "host_wavelet.h"
@@ -140,6 +142,7 @@ void gh_destroy(gh_ctx *c)
     if (c->rs.ev1) hipEventDestroy(c->rs.ev1);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c->ls;
+    delete c->lat;
     delete c;
 }
 
@@ -717,6 +720,11 @@ int gh_set_matrix_free(gh_ctx *c, int enable)
     if (!c) return GH_ERR_ARG;
     if (enable) TRY(dense_single_chain_refuse(c, "gh_set_matrix_free"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_matrix_free: call before gh_build_G");
+    if (c->lat) {
+        if (enable) return fail(c, GH_ERR_ARG, "gh_set_matrix_free: %s is switched on: one form at a time", LATTICE_NAME);
+        c->lat->mf_before = false;  // (the store keeps c->mf)
+        return GH_OK;
+    }
     if (c->ls) {
         c->mf_before_ls = enable != 0;  // (takes effect when the shift-invariant store is switched off)
         return GH_OK;
@@ -734,6 +742,7 @@ int gh_set_shift_invariant(gh_ctx *c, int enable)
     if (enable && !(c && (tess_multi_store(c) || (tess_mag_store(c) && !c->have_G && !c->slab))))
         TRY(dense_single_chain_refuse(c, "gh_set_shift_invariant"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_shift_invariant: call before gh_build_G");
+    if (enable && c->lat) return fail(c, GH_ERR_ARG, "gh_set_shift_invariant: %s is switched on: one form at a time", LATTICE_NAME);
     // (the store is a flavour of the matrix-free mode -- G is never stored -- so enabling it sets c->mf;
     // disabling it puts c->mf back to what gh_set_matrix_free last asked for)
     if (c->ls) c->mf = c->mf_before_ls;
@@ -745,6 +754,78 @@ int gh_set_shift_invariant(gh_ctx *c, int enable)
         c->mf = true;
     }
     return GH_OK;
+}
+
+int gh_set_translation_invariant(gh_ctx *c, int enable)
+{
+    if (!c) return GH_ERR_ARG;
+    if (enable) TRY(dense_single_chain_refuse(c, "gh_set_translation_invariant"));
+    if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: call before gh_build_G");
+    if (enable && c->ls)
+        return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: the shift-invariant store is switched on: one form at a time");
+    if (enable && !c->lat && c->mf)
+        return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: the matrix-free mode is switched on: one form at a time");
+    if (enable && c->have_cells && c->cell_kind != GH_CELL_PRISM && c->cell_kind != GH_CELL_PRISM_COMP &&
+        c->cell_kind != GH_CELL_PRISM_TF)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_translation_invariant: %s holds prisms (tesseroid grids: gh_set_shift_invariant)",
+                    LATTICE_NAME);
+    if (enable && c->sh.kind != 0)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_translation_invariant: not supported on a sharded context (one GPU holds the table)");
+    // (like the longitude table a flavour of the matrix-free mode: enabling it sets c->mf, disabling it puts c->mf back)
+    if (c->lat) c->mf = c->lat->mf_before;
+    delete c->lat;
+    c->lat = nullptr;
+    if (enable) {
+        c->lat = new LatticeHost();
+        c->lat->mf_before = c->mf;
+        c->mf = true;
+    }
+    return GH_OK;
+}
+
+int gh_translation_invariant_info(const gh_ctx *c, int *on, int *nx, int *ny, int *nz, int *px, int *qy, int64_t *table_bytes,
+                                  double *max_dev, double *build_ms)
+{
+    if (!c) return GH_ERR_ARG;
+    const bool o = lattice_on(c);
+    const ghk::LatGeom g = o ? c->lat->g : ghk::LatGeom{};
+    if (on) *on = o ? 1 : 0;
+    if (nx) *nx = g.nx;
+    if (ny) *ny = g.ny;
+    if (nz) *nz = g.nz;
+    if (px) *px = g.px;
+    if (qy) *qy = g.qy;
+    if (table_bytes) *table_bytes = (int64_t)g.nz * g.U * g.V * (int64_t)sizeof(double);
+    if (max_dev) *max_dev = o ? c->lat->max_dev : 0.0;
+    if (build_ms) *build_ms = o ? c->lat->build_ms : 0.0;
+    return GH_OK;
+}
+
+int gh_translation_invariant_table(gh_ctx *c, double *out)
+{
+    if (!c || !out) return fail(c, GH_ERR_ARG, "gh_translation_invariant_table: null pointer");
+    TRY(need(c, lattice_on(c), "gh_translation_invariant_table: no table resident (gh_set_translation_invariant, gh_build_G)"));
+    HIPCHK(c, hipSetDevice(c->device));
+    const ghk::LatGeom &g = c->lat->g;
+    return d2h(c, out, c->lat->T, (size_t)g.nz * (size_t)g.U * (size_t)g.V);
+}
+
+int gh_lattice_detect(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6, int *dims5,
+                      int *lat_of_cell, int *cell_of_lat, int *lat_of_obs, int *obs_of_lat)
+{
+    if (N < 0 || M < 0 || !x || !y || !z || !bounds6 || !dims5 || !lat_of_cell || !cell_of_lat || !lat_of_obs || !obs_of_lat)
+        return GH_ERR_ARG;
+    std::vector<int> loc, col, loo, ool;
+    int dims[5] = {0, 0, 0, 0, 0};
+    const int rc = lattice_detect_host(N, x, y, z, M, bounds6, dims, loc, col, loo, ool);
+    if (rc == GH_LATTICE_ON) {
+        std::copy(dims, dims + 5, dims5);
+        std::copy(loc.begin(), loc.end(), lat_of_cell);
+        std::copy(col.begin(), col.end(), cell_of_lat);
+        std::copy(loo.begin(), loo.end(), lat_of_obs);
+        std::copy(ool.begin(), ool.end(), obs_of_lat);
+    }
+    return rc;
 }
 
 int gh_shift_invariant_resident_stats(gh_ctx *c, int *workgroups, int64_t *launches, int64_t *evaluations, int64_t *trajectories,
@@ -801,10 +882,20 @@ int gh_build_G(gh_ctx *c)
     if (c->mf) {
         if (c->slab) return fail(c, GH_ERR_ARG, "gh_build_G: a matrix-free context is built once");
         // (a store of blocks: only the tesseroid forms get here, by way of the table)
+        if (c->lat) {
+            TRY(dense_single_chain_refuse(c, "gh_build_G on the translation-invariant store"));
+            if (c->cell_kind != GH_CELL_PRISM && c->cell_kind != GH_CELL_PRISM_COMP && c->cell_kind != GH_CELL_PRISM_TF)
+                return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s holds prisms (tesseroid grids: gh_set_shift_invariant)",
+                            LATTICE_NAME);
+            if (c->sh.kind != 0)
+                return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s is not supported on a sharded context (one GPU holds the table)",
+                            LATTICE_NAME);
+        }
         if (store_name(c) && !c->ls)
             return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s has no matrix-free mode (dense, or the shift-invariant store)",
                         store_name(c));
         c->mf_fused = c->ld <= 16384 && env_int("GRAVHMC_MF_FUSED", 1) != 0;
+        if (c->lat) c->mf_fused = false;  // (the table's own two passes, whatever N)
         // (tesseroid components: the two-pass form, with the entry evaluated inside each pass -- no fused KIND;
         // the near-field table and the cell-constant fast leaf are gz's)
         if (c->cell_kind == GH_CELL_TESSEROID_COMP) c->mf_fused = false;
@@ -828,6 +919,7 @@ int gh_build_G(gh_ctx *c)
             }
         }
         if (c->ls) TRY(lonsym_build(c));
+        if (c->lat) TRY(lattice_build(c));
         // (tesseroid components: the error codes, leaves and overflow of the subdivision, as the dense build
         // reports them, from one pass that stores nothing)
         if (c->cell_kind == GH_CELL_TESSEROID_COMP) TRY(tess_comp_assemble(c, c->tconv, nullptr, c->comp, c->ratio, c->N, c->ld));
@@ -875,6 +967,7 @@ int gh_upload_G(gh_ctx *c, const double *A, int64_t ld, int fortran_order)
 {
     if (!c || !A) return fail(c, GH_ERR_ARG, "gh_upload_G: null pointer");
     TRY(dense_single_chain_refuse(c, "gh_upload_G"));
+    TRY(lattice_refuse(c, "gh_upload_G", "its entries come from the cells and observations"));
     if (ld < (fortran_order ? c->N : c->M)) return fail(c, GH_ERR_ARG, "gh_upload_G: ld too small");
     if (c->mf) return fail(c, GH_ERR_ARG, "gh_upload_G: context is matrix-free");
     if (!c->dense_ok) return fail(c, GH_ERR_UNSUPPORTED, "N = %lld: more than 16384 observations per device", (long long)c->N);
@@ -978,6 +1071,8 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
     if (lonsym_on(c)) {
         lonsym_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
             lonsym_geom(c), c->ls->a_of, c->ls->m_of, weightfactor, c->wm);
+    } else if (lattice_on(c)) {
+        lat_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(c->lat->g, weightfactor, c->wm);
     } else if (c->mf) {
         hipLaunchKernelGGL(mf_pick(c, mf_colnorm_kernel<MF_E_GEN>, mf_colnorm_kernel<MF_E_TF>, mf_colnorm_kernel<MF_E_COMP>,
                                    mf_colnorm_kernel<MF_E_TESS>),
@@ -1312,6 +1407,7 @@ int gh_compress_wavelet(gh_ctx *c, int dims, const int shape3[3], double thr, in
 {
     if (!c) return GH_ERR_ARG;
     TRY(dense_single_chain_refuse(c, "gh_compress_wavelet"));
+    TRY(lattice_refuse(c, "gh_compress_wavelet", "the wavelet rows need the stored kernel"));
     TRY(need(c, c->have_G && c->weighted, "gh_compress_wavelet: needs the weighted kernel (gh_weight) first"));
     if (dims != 1 && dims != 3) return fail(c, GH_ERR_ARG, "gh_compress_wavelet: dims must be 1 or 3");
     if (levels < 1 || levels > 4) return fail(c, GH_ERR_ARG, "gh_compress_wavelet: levels must be 1..4");
@@ -1759,6 +1855,7 @@ int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const 
 {
     if (!c || !x0s || !low || !high) return fail(c, GH_ERR_ARG, "gh_batch_init: null pointer");
     TRY(dense_single_chain_refuse(c, "gh_batch_init"));
+    TRY(lattice_refuse(c, "gh_batch_init", "single chain"));
     if (C < 1 || C > CB) return fail(c, GH_ERR_ARG, "gh_batch_init: 1..16 chains per batch");
     TRY(need(c, c->have_G && c->have_data && c->have_reg,
              "gh_batch_init: needs the kernel (gh_build_G / gh_upload_G), gh_set_data and gh_set_reg"));
@@ -1820,6 +1917,7 @@ int gh_batch_trajectory(gh_ctx *c, const double *p0s, double dt, const int *L, c
 {
     if (!c || !p0s || !L || !us || !accepted || !out5s) return fail(c, GH_ERR_ARG, "gh_batch_trajectory: null pointer");
     TRY(dense_single_chain_refuse(c, "gh_batch_trajectory"));
+    TRY(lattice_refuse(c, "gh_batch_trajectory", "single chain"));
     gh_ctx::Batch &b = c->bt;
     TRY(need(c, b.ready, "gh_batch_trajectory: call gh_batch_init first"));
     for (int k = 0; k < b.C; ++k)
@@ -1861,6 +1959,7 @@ int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const
     if (!c || T < 0 || (T > 0 && (!L || !p0s || !us)) || !accepted || !out5s || ((n_started == nullptr) != (n_done == nullptr)))
         return fail(c, GH_ERR_ARG, "gh_batch_run: bad arguments");
     TRY(dense_single_chain_refuse(c, "gh_batch_run"));
+    TRY(lattice_refuse(c, "gh_batch_run", "single chain"));
     if (T == 0 && !n_done) return fail(c, GH_ERR_ARG, "gh_batch_run: T = 0 (drain) needs n_started / n_done");
     gh_ctx::Batch &b = c->bt;
     TRY(need(c, b.ready, "gh_batch_run: call gh_batch_init first"));
@@ -2184,6 +2283,7 @@ int gh_shard_init(gh_ctx *c, const void *id128, int rank, int world, int64_t M_g
     if (!c || !id128) return fail(c, GH_ERR_ARG, "gh_shard_init: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init: already initialised");
     TRY(dense_single_chain_refuse(c, "gh_shard_init"));
+    TRY(lattice_refuse(c, "gh_shard_init", "one GPU holds the table"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_common_init(c, rank, world, M_global, m0));
     std::string err;
@@ -2204,6 +2304,7 @@ int gh_shard_init_callback(gh_ctx *c, gh_allreduce_fn fn, void *user, int rank, 
     if (!c || !fn) return fail(c, GH_ERR_ARG, "gh_shard_init_callback: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init: already initialised");
     TRY(dense_single_chain_refuse(c, "gh_shard_init"));
+    TRY(lattice_refuse(c, "gh_shard_init", "one GPU holds the table"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_common_init(c, rank, world, M_global, m0));
     c->sh.cb = fn;
@@ -2217,6 +2318,7 @@ int gh_shard_init_rows(gh_ctx *c, const void *id128, int rank, int world, int64_
     if (!c || !id128) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: already initialised");
     TRY(dense_single_chain_refuse(c, "gh_shard_init_rows"));
+    TRY(lattice_refuse(c, "gh_shard_init_rows", "one GPU holds the table"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_rows_init(c, rank, world, N_global, n0));
     std::string err;
@@ -2237,6 +2339,7 @@ int gh_shard_init_rows_callback(gh_ctx *c, gh_allreduce_fn fn, void *user, int r
     if (!c || !fn) return fail(c, GH_ERR_ARG, "gh_shard_init_rows_callback: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: already initialised");
     TRY(dense_single_chain_refuse(c, "gh_shard_init_rows"));
+    TRY(lattice_refuse(c, "gh_shard_init_rows", "one GPU holds the table"));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(shard_rows_init(c, rank, world, N_global, n0));
     c->sh.cb = fn;

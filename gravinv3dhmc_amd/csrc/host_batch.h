@@ -128,7 +128,7 @@ static bool mft_plan(gh_ctx *c)
     gh_ctx::MfTeam &t = c->mft;
     if (t.state != 0) return t.state > 0;
     t.state = -1;
-    if (!c->mf || !c->mf_fused || lonsym_on(c) || c->sh.kind != 0) return false;
+    if (!c->mf || !c->mf_fused || lonsym_on(c) || lattice_on(c) || c->sh.kind != 0) return false;
     if (c->cell_kind != GH_CELL_TESSEROID || mfb_kind(c) < 2) return false;  // (the fast / reference-order leaf with the near-field list)
     if (env_int("GRAVHMC_MF_TEAM", 1) == 0) return false;
     const int64_t ntiles = (c->M + 15) / 16;

@@ -14,6 +14,8 @@ static int bscg_refuse(gh_ctx *c, int B, int maxk)
         ;
     else if (c->ls)
         what = "a shift-invariant store";
+    else if (c->lat)
+        what = LATTICE_NAME;
     else if (c->mf)
         what = "a matrix-free context";
     else if (c->sh.kind != 0)

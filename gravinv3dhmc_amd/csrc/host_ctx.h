@@ -5,6 +5,7 @@
 static thread_local std::string g_create_error;
 
 struct LonSymHost;  // host_lonsym.h
+struct LatticeHost; // host_lattice.h
 
 struct DevBuf {
     void *p = nullptr;
@@ -112,6 +113,9 @@ struct gh_ctx {
     // shift-invariant store of a regular spherical grid (lonsym.hip.h): a table instead of G or of
     // per-step evaluations; a flavour of the matrix-free mode (gh_set_shift_invariant)
     LonSymHost *ls = nullptr;
+    // translation-invariant store of a regular prism grid under gridded data (lattice.hip.h): the Cartesian
+    // counterpart, also a flavour of the matrix-free mode (gh_set_translation_invariant)
+    LatticeHost *lat = nullptr;
 
     // chains of a batch on the shift-invariant store: light contexts of their own (stream, chain state, work
     // buffers) that share this context's tables and problem vectors; run concurrently, one host thread each

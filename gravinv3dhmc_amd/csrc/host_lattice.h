@@ -1,0 +1,307 @@
+// libgravhmc host side: the translation-invariant store of a regular prism grid under gridded data
+// (lattice.hip.h).  Detection of the structure (context-free), the build of the table, the partition of the two
+// passes, their launches.  Included once by gravhmc.hip, after host_fold.h.
+#pragma once
+
+// ------------------------------------------------------------------------------------ detection (host)
+
+// Cells: the full product of nx contiguous x-intervals of one width, ny contiguous y-intervals of one width and nz
+// layers (z1, z2 bit for bit), in any order.  Observations: one height (bit for bit), a full px x qy rectangle of
+// the lattice of the cells' spacings, in any order.  Coordinates within the fold's tolerance, a few ulps of their
+// magnitude.  GH_LATTICE_ON, dims = {nx, ny, nz, px, qy} and the four maps, or the reason.
+static int lattice_detect_host(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *b6,
+                               int dims[5], std::vector<int> &lat_of_cell, std::vector<int> &cell_of_lat,
+                               std::vector<int> &lat_of_obs, std::vector<int> &obs_of_lat)
+{
+    using namespace fold_detail;
+    if (N < 1 || M < 1 || N > INT_MAX || M > INT_MAX) return N < 1 ? GH_LATTICE_RECT : GH_LATTICE_CELLS;
+    double mag = 0.0;
+    for (int64_t j = 0; j < M; ++j)
+        for (int e = 0; e < 4; ++e) mag = std::max(mag, std::fabs(b6[6 * j + e]));
+    for (int64_t i = 0; i < N; ++i) mag = std::max(mag, std::max(std::fabs(x[i]), std::fabs(y[i])));
+    if (!std::isfinite(mag)) return GH_LATTICE_CELLS;
+    const double tol = 8.0 * DBL_EPSILON * mag;
+
+    // cells: the edges of an axis are nx + 1 clusters at e_0 + t h
+    Axis ax, ay;
+    {
+        std::vector<double> vx, vy;
+        vx.reserve(2 * (size_t)M);
+        vy.reserve(2 * (size_t)M);
+        for (int64_t j = 0; j < M; ++j) {
+            vx.push_back(b6[6 * j]);
+            vx.push_back(b6[6 * j + 1]);
+            vy.push_back(b6[6 * j + 2]);
+            vy.push_back(b6[6 * j + 3]);
+        }
+        ax.build(std::move(vx), tol);
+        ay.build(std::move(vy), tol);
+    }
+    auto spacing = [&](const Axis &a, double &e0, double &h) {
+        const size_t n = a.lo.size();
+        if (n < 2) return false;
+        e0 = 0.5 * (a.lo[0] + a.hi[0]);
+        h = (0.5 * (a.lo[n - 1] + a.hi[n - 1]) - e0) / (double)(n - 1);
+        if (!(h > 0.0)) return false;
+        for (size_t t = 0; t < n; ++t)
+            if (a.hi[t] - a.lo[t] > 2.0 * tol || std::fabs(0.5 * (a.lo[t] + a.hi[t]) - (e0 + (double)t * h)) > tol) return false;
+        return true;
+    };
+    double ex0 = 0.0, ey0 = 0.0, hx = 0.0, hy = 0.0;
+    if (!spacing(ax, ex0, hx) || !spacing(ay, ey0, hy)) return GH_LATTICE_CELLS;
+    const int64_t nx = (int64_t)ax.lo.size() - 1, ny = (int64_t)ay.lo.size() - 1;
+    // layers: distinct (z1, z2), ordered by their values
+    std::vector<std::pair<double, double>> layers;
+    layers.reserve((size_t)M);
+    for (int64_t j = 0; j < M; ++j) layers.push_back({b6[6 * j + 4], b6[6 * j + 5]});
+    std::sort(layers.begin(), layers.end());
+    layers.erase(std::unique(layers.begin(), layers.end(),
+                             [](const std::pair<double, double> &p, const std::pair<double, double> &q) {
+                                 return bits(p.first) == bits(q.first) && bits(p.second) == bits(q.second);
+                             }),
+                 layers.end());
+    const int64_t nz = (int64_t)layers.size();
+    lat_of_cell.assign(3 * (size_t)M, -1);
+    {
+        Index idx;
+        idx.v.reserve((size_t)M);
+        for (int64_t j = 0; j < M; ++j) {
+            const double *b = b6 + 6 * j;
+            const int a0 = ax.find(b[0]), a1 = ax.find(b[1]), b0 = ay.find(b[2]), b1 = ay.find(b[3]);
+            if (a0 < 0 || b0 < 0 || a1 != a0 + 1 || b1 != b0 + 1) return GH_LATTICE_CELLS;  // not one interval of the axis
+            const int k = (int)(std::lower_bound(layers.begin(), layers.end(), std::make_pair(b[4], b[5])) - layers.begin());
+            if (k >= nz || bits(layers[(size_t)k].first) != bits(b[4]) || bits(layers[(size_t)k].second) != bits(b[5]))
+                return GH_LATTICE_CELLS;  // (NaN, or -0.0 beside 0.0)
+            lat_of_cell[3 * (size_t)j] = k;
+            lat_of_cell[3 * (size_t)j + 1] = a0;
+            lat_of_cell[3 * (size_t)j + 2] = b0;
+            idx.v.push_back({Key{k, a0, b0, 0, 0, 0}, (int)j});
+        }
+        if (!idx.build()) return GH_LATTICE_DUPLICATE;
+    }
+    if ((double)nx * (double)ny * (double)nz != (double)M) return GH_LATTICE_CELLS;  // distinct, in range, too few
+    cell_of_lat.assign((size_t)M, -1);
+    for (int64_t j = 0; j < M; ++j)
+        cell_of_lat[((size_t)lat_of_cell[3 * (size_t)j] * (size_t)nx + (size_t)lat_of_cell[3 * (size_t)j + 1]) * (size_t)ny +
+                    (size_t)lat_of_cell[3 * (size_t)j + 2]] = (int)j;
+
+    // observations
+    for (int64_t i = 1; i < N; ++i)
+        if (bits(z[i]) != bits(z[0])) return GH_LATTICE_HEIGHTS;
+    Axis ox, oy;
+    ox.build(std::vector<double>(x, x + N), tol);
+    oy.build(std::vector<double>(y, y + N), tol);
+    // the clusters of an axis sit at c_0 + m h with the CELLS' h (SPACING), m = 0, 1, 2, ... without a gap (RECT).
+    // (h comes from the cells' extent and carries tol / n of error per step: m steps are allowed tol (1 + m / n))
+    auto on_lattice = [&](const Axis &a, double h, int64_t n) {
+        const double c0 = 0.5 * (a.lo[0] + a.hi[0]);
+        bool gap = false;
+        for (size_t t = 0; t < a.lo.size(); ++t) {
+            const double ct = 0.5 * (a.lo[t] + a.hi[t]);
+            const double m = std::nearbyint((ct - c0) / h);
+            if (a.hi[t] - a.lo[t] > 2.0 * tol || std::fabs(ct - (c0 + m * h)) > tol * (1.0 + m / (double)n)) return GH_LATTICE_SPACING;
+            gap = gap || m != (double)t;
+        }
+        return gap ? GH_LATTICE_RECT : GH_LATTICE_ON;
+    };
+    const int rx = on_lattice(ox, hx, nx), ry = on_lattice(oy, hy, ny);
+    if (rx == GH_LATTICE_SPACING || ry == GH_LATTICE_SPACING) return GH_LATTICE_SPACING;
+    const int64_t px = (int64_t)ox.lo.size(), qy = (int64_t)oy.lo.size();
+    lat_of_obs.assign(2 * (size_t)N, -1);
+    {
+        Index idx;
+        idx.v.reserve((size_t)N);
+        for (int64_t i = 0; i < N; ++i) {
+            const int p = ox.find(x[i]), q = oy.find(y[i]);
+            if (p < 0 || q < 0) return GH_LATTICE_SPACING;
+            lat_of_obs[2 * (size_t)i] = p;
+            lat_of_obs[2 * (size_t)i + 1] = q;
+            idx.v.push_back({Key{p, q, 0, 0, 0, 0}, (int)i});
+        }
+        if (!idx.build()) return GH_LATTICE_DUPLICATE;
+    }
+    if (rx != GH_LATTICE_ON || ry != GH_LATTICE_ON || (double)px * (double)qy != (double)N) return GH_LATTICE_RECT;
+    obs_of_lat.assign((size_t)N, -1);
+    for (int64_t i = 0; i < N; ++i)
+        obs_of_lat[(size_t)lat_of_obs[2 * (size_t)i] * (size_t)qy + (size_t)lat_of_obs[2 * (size_t)i + 1]] = (int)i;
+    dims[0] = (int)nx;
+    dims[1] = (int)ny;
+    dims[2] = (int)nz;
+    dims[3] = (int)px;
+    dims[4] = (int)qy;
+    return GH_LATTICE_ON;
+}
+
+static const char *lattice_reason_text(int reason)
+{
+    switch (reason) {
+    case GH_LATTICE_CELLS:
+        return "the cells are not the full product of equal x-intervals, equal y-intervals and layers (a carved or "
+               "irregular mesh)";
+    case GH_LATTICE_HEIGHTS: return "the observations are at several heights";
+    case GH_LATTICE_SPACING:
+        return "the observations are not on the cells' spacing (n points from one end of the mesh to the other are "
+               "L / (n - 1) apart, the cells L / n)";
+    case GH_LATTICE_RECT: return "the observations are not a full rectangle of the lattice";
+    case GH_LATTICE_DUPLICATE: return "two observations or two cells coincide";
+    case GH_LATTICE_DEVIATION: return "entries of one offset differ beyond the sanity bound";
+    case GH_LATTICE_LDS: return "a row of the lattice is too long for the pass's LDS tile";
+    }
+    return "";
+}
+
+// ----------------------------------------------------------------------------------- store and launches
+
+static const char *const LATTICE_NAME = "the translation-invariant store";
+
+struct LatticeHost {
+    bool on = false;  // the table is built
+    bool mf_before = false;  // what gh_set_matrix_free asked for before the store took c->mf
+    ghk::LatGeom g = {};
+    ghk::LatPlan adj = {}, fwd = {};
+    size_t lds_adj = 0, lds_fwd = 0;
+    int gx_adj = 0, gx_fwd = 0, chunks = 0;
+    double *T = nullptr;
+    int *cell_of = nullptr, *obs_of = nullptr;
+    double max_dev = 0.0, build_ms = 0.0;
+};
+
+static bool lattice_on(const gh_ctx *c) { return c->lat && c->lat->on; }
+
+// What does not run on the store names it
+static int lattice_refuse(gh_ctx *c, const char *who, const char *why)
+{
+    if (c && c->lat) return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on %s (%s)", who, LATTICE_NAME, why);
+    return GH_OK;
+}
+
+// The partition of a pass with NRo output rows of NFo outputs and input rows of NFip (padded) inputs
+static ghk::LatPlan lat_plan(int NRo, int NFo, int NFip)
+{
+    ghk::LatPlan p{};
+    const int nob = (NFo + ghk::LAT_R - 1) / ghk::LAT_R;
+    p.nobt = std::min(64, nob);
+    p.TR = std::max(1, std::min(64 / p.nobt, NRo));
+    p.FT = (nob + p.nobt - 1) / p.nobt;
+    p.WL = NFip + ghk::LAT_R * p.nobt;
+    p.lpc = 1;
+    return p;
+}
+
+static size_t lat_lds_bytes(const ghk::LatPlan &p, int NFip)
+{
+    return ((size_t)(p.TR + ghk::LAT_G - 1) * (size_t)p.WL + (size_t)ghk::LAT_G * (size_t)NFip +
+            (size_t)ghk::LAT_G * 64 * ghk::LAT_R) * sizeof(double);
+}
+
+typedef void (*lat_fill_fn)(MfGeom, ghk::LatGeom, double *, double *);
+
+// gh_build_G of a context with the store switched on: detect, fill, check
+static int lattice_build(gh_ctx *c)
+{
+    LatticeHost &h = *c->lat;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<double> ox((size_t)c->N), oy((size_t)c->N), oz((size_t)c->N), b6((size_t)c->M * 6);
+    TRY(d2h(c, ox.data(), c->obs[0], ox.size()));
+    TRY(d2h(c, oy.data(), c->obs[1], oy.size()));
+    TRY(d2h(c, oz.data(), c->obs[2], oz.size()));
+    TRY(d2h(c, b6.data(), c->bounds, b6.size()));
+    int dims[5] = {0, 0, 0, 0, 0};
+    std::vector<int> loc, col, loo, ool;
+    const int reason = lattice_detect_host(c->N, ox.data(), oy.data(), oz.data(), c->M, b6.data(), dims, loc, col, loo, ool);
+    if (reason != GH_LATTICE_ON)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s needs a regular prism grid under gridded data: %s", LATTICE_NAME,
+                    lattice_reason_text(reason));
+    ghk::LatGeom &g = h.g;
+    g.nx = dims[0];
+    g.ny = dims[1];
+    g.nz = dims[2];
+    g.px = dims[3];
+    g.qy = dims[4];
+    g.U = g.nx + g.px - 1;
+    g.V = g.ny + g.qy - 1;
+    g.nyp = (g.ny + 7) / 8 * 8;
+    g.qyp = (g.qy + 7) / 8 * 8;
+    const size_t nT = (size_t)g.nz * (size_t)g.U * (size_t)g.V;
+    if (nT > (size_t)INT_MAX * 4)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s: a table of %zu entries is beyond the fill kernel's grid", LATTICE_NAME, nT);
+    // the passes' partition and their LDS
+    h.adj = lat_plan(g.nx, g.ny, g.qyp);
+    h.fwd = lat_plan(g.px, g.qy, g.nyp);
+    h.lds_adj = lat_lds_bytes(h.adj, g.qyp);
+    h.lds_fwd = lat_lds_bytes(h.fwd, g.nyp);
+    if (h.lds_adj > 160 * 1024 || h.lds_fwd > 160 * 1024)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s: %s (%d cells, %d observations along y: %zu bytes)", LATTICE_NAME,
+                    lattice_reason_text(GH_LATTICE_LDS), g.ny, g.qy, std::max(h.lds_adj, h.lds_fwd));
+    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<false>), h.lds_adj));
+    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<true>), h.lds_fwd));
+    h.gx_adj = (g.nx + h.adj.TR - 1) / h.adj.TR * h.adj.FT;
+    h.gx_fwd = (g.px + h.fwd.TR - 1) / h.fwd.TR * h.fwd.FT;
+    {
+        // forward: chunks of layers, one slab row each -- about four workgroups per CU, no more rows than layers
+        const int want = std::max(1, std::min(g.nz, (4 * c->cus + h.gx_fwd - 1) / h.gx_fwd));
+        h.fwd.lpc = (g.nz + want - 1) / want;
+        h.chunks = (g.nz + h.fwd.lpc - 1) / h.fwd.lpc;
+    }
+    TRY(dalloc(c, &h.T, nT, false));
+    TRY(dalloc(c, &h.cell_of, (size_t)c->M, false));
+    TRY(dalloc(c, &h.obs_of, (size_t)c->N, false));
+    TRY(dalloc(c, &g.rl, (size_t)g.px * (size_t)g.qyp));          // (zeroed: the padding stays zero)
+    TRY(dalloc(c, &g.xl, (size_t)c->M / (size_t)g.ny * (size_t)g.nyp));
+    HIPCHK(c, hipMemcpyAsync(h.cell_of, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h.obs_of, ool.data(), sizeof(int) * ool.size(), hipMemcpyHostToDevice, c->stream));
+    g.T = h.T;
+    g.cell_of = h.cell_of;
+    g.obs_of = h.obs_of;
+    // fill: the entry of the first and of the last pair of every offset
+    double *T2 = nullptr;
+    HIPCHK(c, hipMalloc((void **)&T2, nT * sizeof(double)));
+    hipLaunchKernelGGL(mf_pick<lat_fill_fn>(c, ghk::lat_fill_kernel<MF_E_GEN>, ghk::lat_fill_kernel<MF_E_TF>,
+                                            ghk::lat_fill_kernel<MF_E_COMP>, ghk::lat_fill_kernel<MF_E_GEN>),
+                       dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, c->stream, mf_geom(c), g, h.T, T2);
+    std::vector<double> t1(nT), t2(nT);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(t1.data(), h.T, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t2.data(), T2, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (col / ool must outlive their copies as well)
+    (void)hipFree(T2);
+    if (e != hipSuccess) return fail(c, GH_ERR_HIP, "gh_build_G: %s: fill of the table: %s", LATTICE_NAME, hipGetErrorString(e));
+    double tmax = 0.0, dmax = 0.0;
+    for (size_t i = 0; i < nT; ++i) {
+        tmax = std::max(tmax, std::fabs(t1[i]));
+        dmax = std::max(dmax, std::fabs(t2[i] - t1[i]));
+    }
+    h.max_dev = tmax > 0.0 ? dmax / tmax : (dmax > 0.0 ? HUGE_VAL : 0.0);
+    h.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (!(h.max_dev <= FOLD_MAX_DEV))
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s: %s (%.3g of the largest entry)", LATTICE_NAME,
+                    lattice_reason_text(GH_LATTICE_DEVIATION), h.max_dev);
+    h.on = true;
+    return GH_OK;
+}
+
+// configure_mf of the store: slab rows = chunks of layers, |p|^2 partials = the adjoint's workgroups
+static void lattice_configure(gh_ctx *c)
+{
+    const LatticeHost &h = *c->lat;
+    c->grid = h.chunks;
+    c->n_teams = h.gx_adj * h.g.nz;
+}
+
+static int launch_lattice(gh_ctx *c, SweepArgs &a, const double *wm)
+{
+    const LatticeHost &h = *c->lat;
+    const ghk::LatGeom &g = h.g;
+    if (a.mode & SW_ADJ) {
+        ghk::lat_gather_r_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(g, a.r);
+        hipLaunchKernelGGL(ghk::lat_pass_kernel<false>, dim3((unsigned)h.gx_adj, (unsigned)g.nz), dim3(ghk::LAT_THREADS),
+                           h.lds_adj, c->stream, g, h.adj, a, wm, c->ld);
+    }
+    if (a.mode & SW_FWD) {
+        const double *x = (a.mode & SW_UPD) ? a.x_out : a.x_in;
+        ghk::lat_gather_x_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(g, x, wm);
+        hipLaunchKernelGGL(ghk::lat_pass_kernel<true>, dim3((unsigned)h.gx_fwd, (unsigned)h.chunks), dim3(ghk::LAT_THREADS),
+                           h.lds_fwd, c->stream, g, h.fwd, a, wm, c->ld);
+    }
+    return GH_OK;
+}

@@ -317,6 +317,9 @@ static int lonsym_grid(const gh_ctx *c);
 static int64_t lonsym_table_bytes(const gh_ctx *c);
 static int fold_use(gh_ctx *c, bool *use);  // host_fold.h
 static int launch_fold(gh_ctx *c, SweepArgs &a);
+static bool lattice_on(const gh_ctx *c);  // host_lattice.h
+static void lattice_configure(gh_ctx *c);
+static int launch_lattice(gh_ctx *c, SweepArgs &a, const double *wm);
 
 // Partition of the matrix-free passes.  N <= 16384: the fused pass (one workgroup per column at a
 // time, columns dealt round-robin); else the two-pass form (one wave per cell for the adjoint,
@@ -326,6 +329,10 @@ static int configure_mf(gh_ctx *c)
     if (lonsym_on(c)) {
         c->grid = lonsym_grid(c);  // one workgroup per cell row at a time, rows dealt round-robin
         c->n_teams = c->grid;
+        return GH_OK;
+    }
+    if (lattice_on(c)) {
+        lattice_configure(c);  // slab rows: chunks of layers; |p|^2 partials: the adjoint's workgroups
         return GH_OK;
     }
     if (c->mf_fused) {
@@ -376,6 +383,8 @@ static int launch_mf(gh_ctx *c, SweepArgs &a)
     if (timed) HIPCHK(c, hipEventRecord(c->ev[c->ev_used], c->stream));
     if (lonsym_on(c)) {
         TRY(launch_lonsym(c, a));
+    } else if (lattice_on(c)) {
+        TRY(launch_lattice(c, a, wm));
     } else if ((a.mode & SW_ADJ) && (a.mode & (SW_UPD | SW_PFIN)) && c->chain_teams_ok && mft_plan(c)) {
         // a leapfrog step of the chain: teams of workgroups (the trajectory code looks at the abort word)
         TRY(mft_launch(c, a));

@@ -376,6 +376,34 @@ class Engine(object):
         return {"on": bool(on.value), "form": {0: None, 1: "registers", 2: "streamed"}[on.value], "n_freq": nf.value,
                 "table_bytes": tb.value, "workgroups": wg.value}
 
+    def set_translation_invariant(self, on=True):
+        """Regular prism grids under gridded data (cells a full product of equal x- and y-intervals and layers,
+        observations a full rectangle of the lattice of the cells' spacings at one height): keep the table
+        T[k][p - a + nx - 1][q - b + ny - 1] instead of G (gh_set_translation_invariant, csrc/lattice.hip.h);
+        build_G raises NotImplementedError with the reason if the geometry lacks the structure."""
+        self._chk(self._lib.gh_set_translation_invariant(self._h, 1 if on else 0))
+        self._translation_invariant = bool(on)
+
+    def translation_invariant_info(self):
+        """on, the lattice's extents nx, ny, nz (cells) and px, qy (observations), table_bytes, and of the build:
+        max_dev (the entries of the first and the last pair of an offset, as a fraction of the largest entry) and
+        build_ms."""
+        i = [C.c_int(0) for _ in range(6)]
+        tb, md, bm = C.c_int64(0), C.c_double(0), C.c_double(0)
+        self._chk(self._lib.gh_translation_invariant_info(self._h, *[C.byref(v) for v in i], C.byref(tb), C.byref(md),
+                                                          C.byref(bm)))
+        return {"on": bool(i[0].value), "nx": i[1].value, "ny": i[2].value, "nz": i[3].value, "px": i[4].value,
+                "qy": i[5].value, "table_bytes": tb.value, "max_dev": md.value, "build_ms": bm.value}
+
+    def translation_invariant_table(self):
+        """The table as it lies on the device: (nz, nx + px - 1, ny + qy - 1)."""
+        t = self.translation_invariant_info()
+        if not t["on"]:
+            raise ValueError("no table resident (set_translation_invariant, build_G)")
+        T = np.empty((t["nz"], t["nx"] + t["px"] - 1, t["ny"] + t["qy"] - 1))
+        self._chk(self._lib.gh_translation_invariant_table(self._h, ptr(T)))
+        return T
+
     #: reasons of fold_info (GH_FOLD_* of include/gravhmc.h)
     FOLD_REASONS = ("on", "undecided", "switched off", "not gz prisms", "observations not mirror-symmetric",
                     "cells not mirror-symmetric", "fixed point", "small", "path", "no memory", "deviation")

@@ -393,6 +393,10 @@ def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
     if getattr(model._engine, "mvi", False):
         raise NotImplementedError("HMCSampleBatch does not run the magnetization-vector store (MagVectorModule): "
                                   "sample its chains one at a time with HMCSample")
+    if getattr(model._engine, "_translation_invariant", False):
+        raise NotImplementedError("HMCSampleBatch does not run the translation-invariant store "
+                                  "(translation_invariant=True; single chain): sample its chains one at a time with "
+                                  "HMCSample")
     eng = model._engine
     _, WmInv, Wm = model.kernelw()
     low, high = Wm @ boundaries[:, 0], Wm @ boundaries[:, 1]

@@ -135,6 +135,14 @@ class GravMagModule(_Potential):
       observations on the same spacing (example/global/main_global.py:25-28): keep the table
       K[i, (c, k)] = T[c][class_i][(m_i - k) mod n] (35 MB for the global example) instead of G
       (4.25 GB); NotImplementedError from the constructor if the geometry lacks the structure.
+    * translation_invariant: cartesian models whose mesh is regular (no mratio growth, mseg or mtopo) with the
+      observations a full rectangle of the lattice of the cells' horizontal spacings at one height (gridded data
+      above cell centres, cell corners or anywhere else): keep the table T[layer][dx][dy] (15.8 MB for 100 x 100 x 50
+      cells under 100 x 100 points) instead of G (40 GB); works with component= and field="magnetic", behaves as
+      matrix_free=True wherever the stored kernel would be needed, has no limit on N.  NotImplementedError from the
+      constructor with the reason if the geometry lacks the structure (utils.regular puts n points L / (n - 1)
+      apart, the cells are L / n wide), and with wavelet, shard, matrix_free, shift_invariant, mtopo and
+      HMCSampleBatch.
     """
 
     def __init__(self, dobs, mrange, mspacing, obsurface, fixed=False, grav_fix=[],
@@ -142,7 +150,7 @@ class GravMagModule(_Potential):
                  coordinate="cartesian", njobs=1, field="gravity",
                  mangle=(90, 0), wavelet=False, device=0, verbose=True, shard=None,
                  shard_backend="rccl", matrix_free=False, shard_planes=False, shift_invariant=False, shard_axis="cells",
-                 component="gz", **kwargs):
+                 component="gz", translation_invariant=False, **kwargs):
         self.dobs = dobs
         self.fixed = fixed
         self.grav_fix = grav_fix
@@ -186,6 +194,17 @@ class GravMagModule(_Potential):
         else:
             self._say("Calculating {} field in {} coordinate.".format(field, coordinate))
         spherical = coordinate == "spherical"
+        if translation_invariant:
+            store = "the translation-invariant store (translation_invariant=True)"
+            if spherical:
+                raise NotImplementedError(store + " is for cartesian (prism) models; spherical grids: shift_invariant")
+            for on, why in ((wavelet, "wavelet: the compressor's rows need the stored kernel"),
+                            (shard is not None and getattr(shard, "world", 1) > 1, "shard: one GPU holds the table"),
+                            (matrix_free, "matrix_free: one form at a time (the store already never stores G)"),
+                            (shift_invariant, "shift_invariant: that table is for spherical grids"),
+                            (bool(kwargs), "mtopo: a carved mesh is not a full regular product of cells")):
+                if on:
+                    raise NotImplementedError(store + " does not combine with " + why)
         if spherical:
             mesh = (mesher.TesseroidMeshSegment(mrange, mspacing, mdivisionsection) if mseg
                     else mesher.TesseroidMesh(mrange, mspacing, mratio))
@@ -228,7 +247,10 @@ class GravMagModule(_Potential):
             if not spherical:
                 raise NotImplementedError("the shift-invariant store is for spherical (tesseroid) models")
             eng.set_shift_invariant(True)
-        self.matrix_free = bool(matrix_free or shift_invariant)
+        if translation_invariant:
+            eng.set_translation_invariant(True)
+        self.matrix_free = bool(matrix_free or shift_invariant or translation_invariant)
+        self.translation_invariant = bool(translation_invariant)
         eng.set_obs(self.lonobs, self.latobs, self.heightobs)
         if spherical:
             self._say("Number of effective tesseroids", bounds.shape[0])
@@ -264,6 +286,10 @@ class GravMagModule(_Potential):
             # threshold 1e-3, CSR -- built and applied on the device
             self._say("Using {} wavelet to compress kernel.".format(wavelet))
             eng.compress_wavelet(3 if wavelet == '3D' else 1, self.mshape, 0.001, 2)
+
+    def translation_invariant_info(self):
+        """The engine's translation_invariant_info(): on, nx, ny, nz, px, qy, table_bytes, max_dev, build_ms."""
+        return self._engine.translation_invariant_info()
 
     @property
     def Awcp(self):

@@ -943,6 +943,46 @@ int gh_fold_pair_info(const gh_ctx *ctx, int *on, int *reason, int64_t *pairs, i
 int gh_fold_detect_pair(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
                         int *obs_tau, int *cell_tau, int *work, int64_t *n_work, int *pair_reason);
 
+/* ---- the translation-invariant store of regular prism grids under gridded data ----------- */
+
+/* Where the cells are the full product of nx equal x-intervals, ny equal y-intervals and nz layers and the
+ * observations a full px x qy rectangle of the lattice of the cells' spacings at one height (above cell centres,
+ * cell corners or anywhere else), every prism field of a pair depends on the layer and the lattice offset alone:
+ * K[(p, q), (k, a, b)] = T[k][p - a + nx - 1][q - b + ny - 1], nz (nx + px - 1) (ny + qy - 1) doubles instead of
+ * N M (csrc/lattice.hip.h).  gh_set_translation_invariant(ctx, 1) before gh_build_G asks for that table instead of
+ * G: a flavour of the matrix-free mode (G is never stored; gh_download_G, the folded store, the resident kernels
+ * do not apply), with no limit on N.  It holds GH_CELL_PRISM, GH_CELL_PRISM_COMP and GH_CELL_PRISM_TF; tesseroids,
+ * the stores of blocks, the wavelet compression, shards, the batches of chains, gh_bscg_run and gh_upload_G are
+ * refused (GH_ERR_UNSUPPORTED), a combination with gh_set_matrix_free or gh_set_shift_invariant too (GH_ERR_ARG).
+ * gh_build_G detects the structure (GH_ERR_UNSUPPORTED with the reason where it is absent), evaluates every table
+ * entry with the dense assembly's entry function on the pair with the smallest (p, q) of its offset -- the entry
+ * equals the dense store's entry of that pair bit for bit -- and compares it with the entry of the pair with the
+ * largest (p, q): max_dev, as a fraction of the largest entry, refused above 1e-7.  Sums run in an order fixed by
+ * indices: results are reproducible bit for bit and agree with the dense store's to ~1e-12. */
+int gh_set_translation_invariant(gh_ctx *ctx, int enable);
+/* on: the table is built; the lattice's extents; table_bytes; max_dev and build_ms of the build. */
+int gh_translation_invariant_info(const gh_ctx *ctx, int *on, int *nx, int *ny, int *nz, int *px, int *qy,
+                                  int64_t *table_bytes, double *max_dev, double *build_ms);
+/* The table T[nz][nx + px - 1][ny + qy - 1] (row-major) as it lies on the device. */
+int gh_translation_invariant_table(gh_ctx *ctx, double *out);
+enum {
+    GH_LATTICE_ON = 0,
+    GH_LATTICE_CELLS = 1,      /* the cells are not a full product of equal x-intervals, equal y-intervals and layers */
+    GH_LATTICE_HEIGHTS = 2,    /* observations at several heights */
+    GH_LATTICE_SPACING = 3,    /* observations not on the cells' spacing (linspace over the mesh's extent: L / (n - 1)) */
+    GH_LATTICE_RECT = 4,       /* observations on the lattice, but not a full rectangle of it */
+    GH_LATTICE_DUPLICATE = 5,  /* two observations or two cells coincide */
+    GH_LATTICE_DEVIATION = 6,  /* (gh_build_G) entries of one offset differ beyond the sanity bound */
+    GH_LATTICE_LDS = 7         /* (gh_build_G) a lattice row too long for the pass's LDS tile */
+};
+/* The structure gh_build_G looks for, without a device: N observations (x, y, z), M cells (bounds6 as in
+ * gh_set_cells), both in any order; coordinates within 8 ulps of their magnitude, heights and layers bit for bit.
+ * Returns one of GH_LATTICE_* (GH_LATTICE_ON: found) or GH_ERR_ARG.  When found: dims5 = {nx, ny, nz, px, qy};
+ * lat_of_cell (3 M ints: (k, a, b) of each cell; layers ordered by (z1, z2)) and its inverse cell_of_lat (M ints,
+ * [k][a][b]); lat_of_obs (2 N ints: (p, q)) and its inverse obs_of_lat (N ints, [p][q]). */
+int gh_lattice_detect(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
+                      int *dims5, int *lat_of_cell, int *cell_of_lat, int *lat_of_obs, int *obs_of_lat);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 
 /* HIP-event timing of the G sweeps (the dominant kernel) on the context's stream.
