@@ -352,6 +352,20 @@ def HMCSample(model, nsamples, ndraws, delta, Lrange,
     return chain
 
 
+#: the stores HMCSampleBatch does not run, in the order they are asked for: (the attributes of the module's engine
+#: that tell the store, the store and its module).  A store of row blocks of magnetization vectors answers both
+#: `multi` and `mvi`: it comes before either.
+_NO_BATCH = (
+    (("joint",), "the joint gravity-magnetic kernel (JointModule)"),
+    (("tess_mag",), "the tesseroid magnetization store (TesseroidMagVectorModule)"),
+    (("tess_multi",), "the tesseroid multi-component store (TesseroidMultiComponentModule)"),
+    (("multi", "mvi"), "the vector-data magnetization store (MagVectorModule with data=)"),
+    (("multi",), "the multi-component store (MultiComponentModule)"),
+    (("mvi",), "the magnetization-vector store (MagVectorModule)"),
+    (("_translation_invariant",), "the translation-invariant store (translation_invariant=True; single chain)"),
+)
+
+
 def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
                    initial_model, aprior_model, boundaries, constraint, log_factor, dobs,
                    adaptiveRegul, RegulRate, RegulFactor, regularization, beta,
@@ -375,28 +389,10 @@ def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
     (Engine.posterior_stream_read, posterior.summarize_stream)."""
     if constraint != 'mandatory':
         raise ValueError("HMCSampleBatch supports the 'mandatory' boundary constraint only")
-    if getattr(model._engine, "joint", False):
-        raise NotImplementedError("HMCSampleBatch does not run the joint gravity-magnetic kernel (JointModule): "
-                                  "sample its chains one at a time with HMCSample")
-    if getattr(model._engine, "tess_mag", False):
-        raise NotImplementedError("HMCSampleBatch does not run the tesseroid magnetization store "
-                                  "(TesseroidMagVectorModule): sample its chains one at a time with HMCSample")
-    if getattr(model._engine, "tess_multi", False):
-        raise NotImplementedError("HMCSampleBatch does not run the tesseroid multi-component store "
-                                  "(TesseroidMultiComponentModule): sample its chains one at a time with HMCSample")
-    if getattr(model._engine, "multi", 0) and getattr(model._engine, "mvi", False):
-        raise NotImplementedError("HMCSampleBatch does not run the vector-data magnetization store (MagVectorModule with "
-                                  "data=): sample its chains one at a time with HMCSample")
-    if getattr(model._engine, "multi", 0):
-        raise NotImplementedError("HMCSampleBatch does not run the multi-component store (MultiComponentModule): "
-                                  "sample its chains one at a time with HMCSample")
-    if getattr(model._engine, "mvi", False):
-        raise NotImplementedError("HMCSampleBatch does not run the magnetization-vector store (MagVectorModule): "
-                                  "sample its chains one at a time with HMCSample")
-    if getattr(model._engine, "_translation_invariant", False):
-        raise NotImplementedError("HMCSampleBatch does not run the translation-invariant store "
-                                  "(translation_invariant=True; single chain): sample its chains one at a time with "
-                                  "HMCSample")
+    for attrs, name in _NO_BATCH:
+        if all(getattr(model._engine, a, False) for a in attrs):
+            raise NotImplementedError("HMCSampleBatch does not run %s: sample its chains one at a time with HMCSample"
+                                      % name)
     eng = model._engine
     _, WmInv, Wm = model.kernelw()
     low, high = Wm @ boundaries[:, 0], Wm @ boundaries[:, 1]

@@ -9,14 +9,12 @@ plus, on request, the cross-gradient term lambda |grad rho x grad kappa|^2 that 
 The device keeps H = [Aw_gz | Aw_tf] (N rows, 2M columns): the zero blocks are never stored or read
 (libgravhmc's GH_CELL_PRISM_JOINT).  `Aw` is a device handle whose array is the reference's 2N x 2M layout.
 """
-import time
-
 import numpy as np
 from scipy.sparse import block_diag, coo_matrix
 
-from .. import _lib, mesher, utils
-from ..engine import DeviceMatrix, Engine
-from .potential import _diag, _Potential
+from .. import _lib, utils
+from ..engine import Engine
+from .potential import _diag, _mesh, _Potential
 
 
 def fd3d(shape):
@@ -97,15 +95,12 @@ class JointModule(_Potential):
         self.lonobs, self.latobs, self.heightobs = obsurface[0], obsurface[1], obsurface[2]
         self.inc, self.dec = mangle[0], mangle[1]
         self.njobs = njobs
-        self.topocarve = False
         self.wavelet = wavelet
         self.device = device
 
         self._say("Joint inversion in {} coordinate.".format(coordinate))
-        mesh = mesher.PrismMesh(mrange, mspacing, mratio)
-        for _key, value in kwargs.items():  # mtopo=(x, y, topography)  (potential.py:899-903)
-            self.topocarve = True
-            self.mask = mesh.carvetopo(value[0], value[1], value[2])
+        mesh = _mesh(False, mrange, mspacing, mratio)
+        self._carve(mesh, kwargs.values())  # (any keyword is the topography, as in the reference)
         meshrho, meshmag = mesh.copy(), mesh.copy()
         meshrho.addprop('density', np.zeros(mesh.size))
         meshmag.addprop('magnetization', utils.ang2vec(np.zeros(mesh.size), self.inc, self.dec))
@@ -138,20 +133,14 @@ class JointModule(_Potential):
     def weightKDM(self):
         """Wm (column 2-norms of A), Wb (std_gz / std_tf on the tf rows), Aw = Wb A Wm^-1 and dobsw = Wb dobs
         (potential.py:1003-1065), on the device."""
-        wm = self._engine.weight(0.5)
+        self._weight(0.5, zero_safe=True)
         std_gz, std_tf = self._engine.joint_std()
         self.std_gz, self.std_tf = std_gz, std_tf
         n = self.dobs_gz.size
         wb = np.append(np.ones(n), np.ones(n) * (std_gz / std_tf))
-        with np.errstate(divide='ignore'):
-            inv = np.where(wm == 0, 0.0, 1.0 / wm)
-        self.Wm = _diag(wm)
-        self.WmInv = _diag(inv)
-        self.WmSquare = _diag(wm * wm)
         self.Wb = _diag(wb)
         self.dobs = np.append(self.dobs_gz, self.dobs_tf)
         self.dobsw = self.Wb @ self.dobs
-        self.Aw = DeviceMatrix(self._engine)
 
     @property
     def A(self):
@@ -169,10 +158,6 @@ class JointModule(_Potential):
     def kernel_tf(self):
         n, m = self.dobs_gz.size, self.Wm.shape[0] // 2
         return np.ascontiguousarray(self.A[n:, m:])
-
-    def kernelw(self):
-        """(Aw, WmInv, Wm) as the sampler expects (potential.py:1561-1566); Aw is a device handle."""
-        return self.Aw, self.WmInv, self.Wm
 
     def forward(self, model):
         """Unweighted forward A @ model (potential.py:1067-1073): 2N values, gz first."""

@@ -21,13 +21,11 @@ and the data term removes the mean of every block on its own,
 
 with d = Aw mw, Aw = Wb A Wm^-1, dobsw = Wb dobs.  The columns, the regularisers and the amplitude term stay as above.
 """
-import time
-
 import numpy as np
 
-from .. import _lib, mesher, utils
-from ..engine import DeviceMatrix, Engine
-from .potential import _diag, _Potential
+from .. import _lib, utils
+from ..engine import Engine
+from .potential import _BlockStore
 
 _STORE = "the magnetization-vector store"
 _VSTORE = "the vector-data magnetization store"
@@ -48,7 +46,7 @@ def mirror_signs(data):
     return tuple(None if b == "tf" else -1.0 if b == "bx" else 1.0 for b in data), (-1.0, 1.0, 1.0)
 
 
-class MagVectorModule(_Potential):
+class MagVectorModule(_BlockStore):
     """The magnetization vector of every prism under total-field data, on one MI355X.
 
     dobs: the N total-field anomalies (uT) at obsurface = [xobs, yobs, height]; mrange, mspacing, mratio, mseg,
@@ -76,169 +74,53 @@ class MagVectorModule(_Potential):
     matrix-free mode, the shift-invariant store, shards, HMCSampleBatch and more than 16384 observations -- stacked
     rows len(data) x N under vector data -- (the store runs on the fused sweep).  Smoothness and TV need the full mesh (ValueError on a carved one).
     """
-    _props = 3  # (mx, my and mz of the same mesh)
-    _spherical = False  # (TesseroidMagVectorModule: tesseroids, always the store of row blocks)
-    _has_table = False  # (TesseroidMagVectorModule: shift_invariant=True keeps the shift-invariant table)
+    _props, _prop = 3, 'magnetization'  # (mx, my and mz of the same mesh)
+    _names, _arg, _word, _none_weight = _lib.BCOMPONENTS, "data", "data component", True
+    _store = property(lambda self: _VSTORE if self._vector else _STORE)
 
     def __init__(self, dobs, mrange, mspacing, obsurface, mangle=(90, 0), mratio=1, mseg=False, mdivisionsection=[],
                  weightfactor=0.5, amplitude=0.0, amplitude_beta=0.01, device=0, verbose=True, coordinate="cartesian",
                  wavelet=False, matrix_free=False, shift_invariant=False, shard=None, data=("tf",), weights=None,
                  **kwargs):
         self._say = print if verbose else (lambda *a, **k: None)
-        unknown = sorted(set(kwargs) - {"mtopo"})
-        if unknown:
-            raise TypeError("unexpected keyword argument %r" % unknown[0])
-        data = (data,) if isinstance(data, str) else tuple(data)
-        if len(data) == 0:
-            raise ValueError("data is empty: name at least one of %s" % ", ".join(_lib.BCOMPONENTS))
-        for b in data:
-            if b not in _lib.BCOMPONENTS:
-                raise ValueError("data component %r: must be one of %s" % (b, ", ".join(_lib.BCOMPONENTS)))
-        if len(set(data)) != len(data):
-            raise ValueError("data components must be distinct, got %r" % (data,))
+        self._only_mtopo(kwargs)
+        data = self._block_names(data)
         n = int(np.asarray(obsurface[0]).size)
         # the default is the module as it always was: one block of the total field, one mean, no block table
         self._vector = self._spherical or not (data == ("tf",) and weights is None)
-        store = _TSTORE if self._spherical else _VSTORE if self._vector else _STORE
         if self._vector:
-            if isinstance(dobs, dict):
-                if set(dobs) != set(data):
-                    raise ValueError("dobs has the components %r, expected %r" % (sorted(dobs), sorted(data)))
-                dobs = [dobs[b] for b in data]
-            dobs = [np.asarray(d, dtype=np.float64).ravel() for d in dobs]
-            if len(dobs) != len(data):
-                raise ValueError("%d observation vectors for %d data components" % (len(dobs), len(data)))
-            for b, d in zip(data, dobs):
-                if d.size != n:
-                    raise ValueError("dobs of %s has %d values, the observation points are %d" % (b, d.size, n))
-            if weights is None:
-                w = np.ones(len(data))
-            elif isinstance(weights, str):
-                if weights != "std":
-                    raise ValueError("weights must be None, 'std' or one positive number per data component")
-                sd = np.array([np.std(d) for d in dobs])
-                if not np.all(sd > 0):
-                    raise ValueError("weights='std' needs observations that vary in every component")
-                w = sd[0] / sd
-            else:
-                w = np.asarray(weights, dtype=np.float64).ravel()
-                if w.size != len(data) or not np.all(np.isfinite(w)) or not np.all(w > 0):
-                    raise ValueError("weights must be None, 'std' or one positive number per data component")
-        if coordinate == "spherical" and not self._spherical:
-            raise NotImplementedError("%s holds prism fields: tesseroids (coordinate='spherical') are not supported"
-                                      % store)
-        if coordinate != ("spherical" if self._spherical else "cartesian"):
-            raise ValueError("Please choose coordinate from(cartesian, spherical)!")
-        if wavelet not in (False, None):
-            raise NotImplementedError("wavelet compression of %s is not supported" % store)
-        if matrix_free:
-            raise NotImplementedError("%s is dense: the matrix-free mode is not supported" % store)
-        if shift_invariant and not self._has_table:
-            raise NotImplementedError("%s is dense: the shift-invariant store is not supported" % store)
-        self.shift_invariant = bool(shift_invariant)
-        if shard is not None:
-            raise NotImplementedError("%s is not sharded" % store)
-        if self._vector:
-            if len(data) * n > 16384 and not self.shift_invariant:
-                raise NotImplementedError("%d data components x %d observations = %d rows: %s takes at most 16384 (it "
-                                          "runs on the fused sweep)" % (len(data), n, len(data) * n, store))
-            self.weights = w
-            dobs = np.concatenate(dobs)
-        else:
-            dobs = np.asarray(dobs, dtype=np.float64).ravel()
-            if dobs.size != n:
-                raise ValueError("dobs has %d values, the observation points are %d" % (dobs.size, n))
+            dobs, w = self._block_data(data, dobs, weights, n)
+        self._refuse(coordinate, wavelet, matrix_free, shift_invariant, shard, len(data) if self._vector else 0, n)
+        if not self._vector:
+            dobs, w = [np.asarray(dobs, dtype=np.float64).ravel()], np.ones(1)
+            if dobs[0].size != n:
+                raise ValueError("dobs has %d values, the observation points are %d" % (dobs[0].size, n))
             if n > 16384:
                 raise NotImplementedError("%d observations: %s takes at most 16384 (it runs on the fused sweep)"
-                                          % (n, store))
-            self.weights = np.ones(1)
-        self.components = data
-        self._n = n
+                                          % (n, self._store))
         if not (amplitude >= 0) or not (amplitude_beta > 0):
             raise ValueError("amplitude must be >= 0 and amplitude_beta > 0")
-
-        self.dobs = dobs
-        self.mrange, self.mspacing, self.mratio = mrange, mspacing, mratio
-        self.mseg, self.mdivisionsection = mseg, mdivisionsection
-        self.weightfactor = weightfactor
-        self.lonobs, self.latobs, self.heightobs = obsurface[0], obsurface[1], obsurface[2]
         self.inc, self.dec = mangle[0], mangle[1]
-        self.topocarve = False
-        self.wavelet = False
-        self.device = device
-
-        self._say("Calculating magnetic field (magnetization vector) in %s coordinate." % coordinate)
-        mesh = self._make_mesh()
-        if "mtopo" in kwargs:
-            value = kwargs["mtopo"]
-            self.topocarve = True
-            self.mask = mesh.carvetopo(value[0], value[1], value[2])
-        mesh.addprop('magnetization', np.zeros((mesh.size, 3)))
-        self.mesh = mesh
-
-        bounds = mesh.cell_bounds(active_only=True)
-        self._cells = int(bounds.shape[0])
-        self._say("Start of calculate kernel")
-        start = time.time()
-        if self._vector:
-            eng = Engine(len(data) * n, 3 * self._cells, device=device)
-            self._set_cells(eng, bounds, data, w)
-        else:
-            eng = Engine(n, 3 * self._cells, device=device)
-            eng.set_cells_mvi(bounds, utils.dircos(self.inc, self.dec))
-        eng.set_obs(self.lonobs, self.latobs, self.heightobs)
-        self._build(eng)
-        self._say("kernel.shape", (eng.N, 3 * self._cells))
-        self._say("End of calculate kernel:%.6f s" % (time.time() - start))
-        self._engine = eng
-
-        self.mshape = mesh.shape
-        self.mxs, self.mys, self.mzs = mesh.get_xs(), mesh.get_ys(), mesh.get_zs()
-        self._say("Start to weight kernel")
-        start = time.time()
-        self.sensitivityWeighting()
-        self._say("End of weighting kernel: %.6f s" % (time.time() - start))
-        if self._vector:
-            self.dobsw = self.Wb @ self.dobs
-            eng.set_data(self.dobsw)
-        else:
-            eng.set_data(self.dobs)
+        title = "Calculating magnetic field (magnetization vector) in %s coordinate." % coordinate
+        self._assemble(Engine, title, data, dobs, w, n, mrange, mspacing, obsurface, mratio, mseg, mdivisionsection,
+                       weightfactor, shift_invariant, device, kwargs.values())
+        self._cells = self._engine.M // 3
         self._amp = None  # (lambda, beta) once the engine holds the term
         self._amp_beta = float(amplitude_beta)
         if amplitude != 0:
             self.set_amplitude(amplitude, amplitude_beta)
 
-    # ------------------------------------------------------------------ the mesh and the assembly (the geometry's part)
-    def _make_mesh(self):
-        return (mesher.PrismMeshSegment(self.mrange, self.mspacing, self.mdivisionsection) if self.mseg
-                else mesher.PrismMesh(self.mrange, self.mspacing, self.mratio))
-
-    def _set_cells(self, eng, bounds, data, w):
-        eng.set_cells_mvi_data(bounds, utils.dircos(self.inc, self.dec) if "tf" in data else None, data, w)
-
-    def _build(self, eng):
-        eng.build_G()
-
-    # ------------------------------------------------------------------ weighting
-    def sensitivityWeighting(self):
-        """Column-norm weighting Wm over all M columns and Aw = A Wm^-1, on the device."""
-        wm = self._engine.weight(self.weightfactor)
-        with np.errstate(divide='ignore'):
-            inv = 1.0 / wm
-        self.Wm = _diag(wm)
-        self.WmInv = _diag(inv)
-        self.WmSquare = _diag(wm * wm)
+    def _set_cells(self, eng, bounds):
+        direction = utils.dircos(self.inc, self.dec) if "tf" in self.components else None
         if self._vector:
-            self.Wb = _diag(np.repeat(self.weights, self._n))
-        self.Aw = DeviceMatrix(self._engine)
-
-    def kernelw(self):
-        """(Aw, WmInv, Wm) as the sampler expects; Aw is a device handle."""
-        return self.Aw, self.WmInv, self.Wm
+            eng.set_cells_mvi_data(bounds, direction, self.components, self.weights)
+        else:
+            eng.set_cells_mvi(bounds, direction)
 
     @property
     def A(self):
         """The unweighted kernel [A_x | A_y | A_z], N x M, from the device copy (Aw Wm; rounding differs)."""
+        self._no_table("A")
         A = np.asarray(self.Aw) * self.Wm.diagonal()[None, :]
         return A / self.Wb.diagonal()[:, None] if self._vector else A
 
@@ -246,6 +128,7 @@ class MagVectorModule(_Potential):
         """Block A_axis (N x M/3, uT per A/m along axis 0 / "x" north, 1 / "y" east, 2 / "z" down), from the device
         copy.  Under vector data: of the data component `component` alone (N rows), or with component=None of every
         row block (len(data) N rows), in the components' own units."""
+        self._no_table("kernel(%r, %r)" % (axis, component))
         a = {"x": 0, "y": 1, "z": 2}.get(axis, axis)
         if a not in (0, 1, 2):
             raise ValueError("axis must be 0, 1, 2 or 'x', 'y', 'z', got %r" % (axis,))
@@ -261,20 +144,12 @@ class MagVectorModule(_Potential):
                 Aw = Aw[b * n:(b + 1) * n] / self.weights[b]
         return np.asfortranarray(Aw * self.Wm.diagonal()[None, a * m:(a + 1) * m])
 
-    def forward(self, model):
-        """Unweighted forward A @ model (uT): model is the property-major M vector in A/m.  Under vector data the
-        component-major stack, each block in its own units."""
-        model = np.asarray(model, dtype=np.float64).ravel()
-        d = self._engine.forward(model * self.Wm.diagonal())
-        return d / self.Wb.diagonal() if self._vector else d
-
     def block_means(self):
         """Under vector data: (means of the last evaluation's weighted prediction Aw mw, means removed from the weighted
         observations), one per data component."""
         if not self._vector:
             raise ValueError("block_means: the module has one block of total-field data (data=('tf',))")
-        info = self._engine.multi_info()
-        return info["pred_mean"], info["obs_mean"]
+        return super().block_means()
 
     # ------------------------------------------------------------------ the model as vectors
     def to_vectors(self, model):
@@ -366,8 +241,8 @@ class TesseroidMagVectorModule(MagVectorModule):
 
     Not supported (NotImplementedError naming the tesseroid magnetization store): wavelet compression, the
     matrix-free mode, shards, HMCSampleBatch, and more than 16384 stacked rows without shift_invariant=True."""
-    _spherical = True
-    _has_table = True
+    _spherical = _has_table = True
+    _store = _TSTORE
 
     def __init__(self, dobs, mrange, mspacing, obsurface, data=("bx", "by", "bz"), weights=None, mangle=(90, 0),
                  amplitude=0.0, amplitude_beta=0.01, mratio=1, mseg=False, mdivisionsection=[], weightfactor=0.5,
@@ -393,10 +268,6 @@ class TesseroidMagVectorModule(MagVectorModule):
                          wavelet=wavelet, matrix_free=matrix_free, shift_invariant=shift_invariant, shard=shard,
                          data=data, weights=weights, **kwargs)
 
-    def _make_mesh(self):
-        return (mesher.TesseroidMeshSegment(self.mrange, self.mspacing, self.mdivisionsection) if self.mseg
-                else mesher.TesseroidMesh(self.mrange, self.mspacing, self.mratio))
-
     @staticmethod
     def _class_directions(fdir, mangle, obsurface):
         """The table has one set of entries per class of observations (same latitude and height): inc and dec must
@@ -419,26 +290,6 @@ class TesseroidMagVectorModule(MagVectorModule):
                                           "class of observations (same latitude and height)" % _TSTORE)
         return np.ascontiguousarray(fdir[first][cls])
 
-    def _set_cells(self, eng, bounds, data, w):
-        eng.set_cells_tess_mag(bounds, self._ratio, data, w, self._fdir, shift_invariant=self.shift_invariant)
-
-    def _build(self, eng):
-        eng.build_G()   # (NotImplementedError with the store's reason where the table does not apply)
-        if eng.kernel_stats()["warn_cells"] > 0:
-            import warnings
-            from ..gravmag.tesseroid import _WARN_DIVIDE
-            warnings.warn(_WARN_DIVIDE, RuntimeWarning)
-
-    def _no_table(self, what):
-        if self.shift_invariant:
-            raise NotImplementedError("%s: %s keeps the shift-invariant table, the kernel is never stored" %
-                                      (what, _TSTORE))
-
-    @property
-    def A(self):
-        self._no_table("A")
-        return super().A
-
-    def kernel(self, axis, component=None):
-        self._no_table("kernel(%r, %r)" % (axis, component))
-        return super().kernel(axis, component)
+    def _set_cells(self, eng, bounds):
+        eng.set_cells_tess_mag(bounds, self._ratio, self.components, self.weights, self._fdir,
+                               shift_invariant=self.shift_invariant)

@@ -35,11 +35,53 @@ def _diag(values):
     return coo_matrix((values, (row, row))).tocsr()
 
 
+def _mesh(spherical, mrange, mspacing, mratio=1, mseg=False, mdivisionsection=()):
+    """The mesh of a module: tesseroids or prisms, dz growing by mratio or, with mseg, piecewise constant."""
+    if spherical:
+        return (mesher.TesseroidMeshSegment(mrange, mspacing, mdivisionsection) if mseg
+                else mesher.TesseroidMesh(mrange, mspacing, mratio))
+    return (mesher.PrismMeshSegment(mrange, mspacing, mdivisionsection) if mseg
+            else mesher.PrismMesh(mrange, mspacing, mratio))
+
+
 class _Potential(object):
-    """The potential methods GravMagModule and JointModule share: the model transform, the regulariser sent to the
-    engine, misfit_and_grad and the reference's wrappers.  `_props`: properties that share the mesh `mshape`
-    (the stencil regularisers act on each of them on its own)."""
+    """What every inversion module shares: the steps of its constructor that do not depend on the store (the mtopo
+    carve, the assembly with the tesseroid divide warning, the column weighting, kernelw), the model transform, the
+    regulariser sent to the engine, misfit_and_grad and the reference's wrappers.  `_props`: properties that share the
+    mesh `mshape` (the stencil regularisers act on each of them on its own)."""
     _props = 1
+
+    def _carve(self, mesh, topos):
+        """mtopo=(x, y, topography): mask the cells above the surface (potential.py:92-96, 899-903)."""
+        self.topocarve = False
+        for value in topos:
+            self.topocarve = True
+            self.mask = mesh.carvetopo(value[0], value[1], value[2])
+
+    @staticmethod
+    def _build(eng, spherical):
+        """build_G (NotImplementedError with the store's reason where a table does not apply), and the reference's
+        warning for tesseroids that could not be divided further."""
+        eng.build_G()
+        if spherical and eng.kernel_stats()["warn_cells"] > 0:
+            import warnings
+            from ..gravmag.tesseroid import _WARN_DIVIDE
+            warnings.warn(_WARN_DIVIDE, RuntimeWarning)
+
+    def _weight(self, weightfactor, zero_safe=False):
+        """Column-norm weighting Wm and Aw = A Wm^-1 (potential.py:232-264), on the device.  WmInv of an empty column
+        is infinite; zero_safe: 0 there (JointModule)."""
+        wm = self._engine.weight(weightfactor)
+        with np.errstate(divide='ignore'):
+            inv = np.where(wm == 0, 0.0, 1.0 / wm) if zero_safe else 1.0 / wm
+        self.Wm = _diag(wm)
+        self.WmInv = _diag(inv)
+        self.WmSquare = _diag(wm * wm)
+        self.Aw = DeviceMatrix(self._engine)
+
+    def kernelw(self):
+        """(Aw, WmInv, Wm) as the sampler expects (potential.py:584-589, 1561-1566); Aw is a device handle."""
+        return self.Aw, self.WmInv, self.Wm
 
     def _to_mw(self, x, low, high, constraint, log_fator):
         if constraint == 'logarithmic':
@@ -165,7 +207,6 @@ class GravMagModule(_Potential):
         self.heightobs = obsurface[2]
         self.inc, self.dec = mangle[0], mangle[1]
         self.njobs = njobs
-        self.topocarve = False
         self.wavelet = wavelet
         self.device = device
         self._say = print if verbose else (lambda *a, **k: None)
@@ -205,15 +246,8 @@ class GravMagModule(_Potential):
                             (bool(kwargs), "mtopo: a carved mesh is not a full regular product of cells")):
                 if on:
                     raise NotImplementedError(store + " does not combine with " + why)
-        if spherical:
-            mesh = (mesher.TesseroidMeshSegment(mrange, mspacing, mdivisionsection) if mseg
-                    else mesher.TesseroidMesh(mrange, mspacing, mratio))
-        else:
-            mesh = (mesher.PrismMeshSegment(mrange, mspacing, mdivisionsection) if mseg
-                    else mesher.PrismMesh(mrange, mspacing, mratio))
-        for _key, value in kwargs.items():  # mtopo=(x, y, topography)  (potential.py:92-96)
-            self.topocarve = True
-            self.mask = mesh.carvetopo(value[0], value[1], value[2])
+        mesh = _mesh(spherical, mrange, mspacing, mratio, mseg, mdivisionsection)
+        self._carve(mesh, kwargs.values())  # (any keyword is the topography, as in the reference)
         if magnetic:
             # (potential.py:139: zero magnetization along the field; the reference's magnetic branch always
             # builds PrismMesh and ignores mseg (potential.py:131) -- mseg is honoured here as for gravity)
@@ -261,11 +295,7 @@ class GravMagModule(_Potential):
             eng.set_cells(bounds, _lib.CELL_PRISM_COMP, component=component)
         else:
             eng.set_cells(bounds, _lib.CELL_PRISM)
-        eng.build_G()
-        if spherical and eng.kernel_stats()["warn_cells"] > 0:
-            import warnings
-            from ..gravmag.tesseroid import _WARN_DIVIDE
-            warnings.warn(_WARN_DIVIDE, RuntimeWarning)
+        self._build(eng, spherical)
         if magnetic:
             self._say("End of calculate kernel:", time.time() - start)   # (potential.py:149)
         else:
@@ -301,14 +331,154 @@ class GravMagModule(_Potential):
     # ------------------------------------------------------------------ weighting
     def sensitivityWeighting(self):
         """Column-norm weighting Wm and Aw = A Wm^-1 (potential.py:232-264), on the device."""
-        wm = self._engine.weight(self.weightfactor)
-        with np.errstate(divide='ignore'):
-            inv = 1.0 / wm
-        self.Wm = _diag(wm)
-        self.WmInv = _diag(inv)
-        self.WmSquare = _diag(wm * wm)
-        self.Aw = DeviceMatrix(self._engine)
+        self._weight(self.weightfactor)
 
-    def kernelw(self):
-        """(Aw, WmInv, Wm) as the sampler expects (potential.py:584-589); Aw is a device handle."""
-        return self.Aw, self.WmInv, self.Wm
+
+class _BlockStore(_Potential):
+    """The modules whose store stacks row blocks -- data components of the same cells at the same points, block b in
+    its own units times a data weight w_b, with a mean of its own (MultiComponentModule, MagVectorModule and their
+    tesseroid forms) -- share the parser of their data, the ladder of their refusals, their construction and what is
+    formed from Wb.  A class states `_names` (the table of its components' names), `_arg` and `_word` (what its texts
+    call the argument and one component), `_none_weight` (weights=None means ones), `_store` (the store's name in the
+    refusals), `_spherical` and `_has_table` (tesseroids; shift_invariant=True keeps the shift-invariant table), `_prop`
+    and `_props` (the mesh property, and its unknowns per cell), and `_set_cells(eng, bounds)`, the engine call."""
+    _spherical = False
+    _has_table = False
+    _rows_hint = ""     # (what the refusal of more than 16384 rows adds)
+    _vector = True      # (False on MagVectorModule's default form alone: one block of the total field, no Wb)
+
+    # ------------------------------------------------------------------ the arguments
+    def _block_names(self, names):
+        names = (names,) if isinstance(names, str) else tuple(names)
+        if len(names) == 0:
+            raise ValueError("%s is empty: name at least one of %s" % (self._arg, ", ".join(self._names)))
+        for c in names:
+            if c not in self._names:
+                raise ValueError("%s %r: must be one of %s" % (self._word, c, ", ".join(self._names)))
+        if len(set(names)) != len(names):
+            raise ValueError("%ss must be distinct, got %r" % (self._word, names))
+        return names
+
+    def _block_data(self, names, dobs, weights, n):
+        """(the blocks' observation vectors, their data weights) from a sequence or dict dobs of n values per block and
+        weights "std", numbers or (with `_none_weight`) None."""
+        if isinstance(dobs, dict):
+            if set(dobs) != set(names):
+                raise ValueError("dobs has the components %r, expected %r" % (sorted(dobs), sorted(names)))
+            dobs = [dobs[c] for c in names]
+        dobs = [np.asarray(d, dtype=np.float64).ravel() for d in dobs]
+        if len(dobs) != len(names):
+            raise ValueError("%d observation vectors for %d %ss" % (len(dobs), len(names), self._word))
+        for c, d in zip(names, dobs):
+            if d.size != n:
+                raise ValueError("dobs of %s has %d values, the observation points are %d" % (c, d.size, n))
+        bad = "weights must be %s'std' or one positive number per %s" % ("None, " if self._none_weight else "", self._word)
+        if weights is None and self._none_weight:
+            w = np.ones(len(names))
+        elif isinstance(weights, str):
+            if weights != "std":
+                raise ValueError(bad)
+            sd = np.array([np.std(d) for d in dobs])
+            if not np.all(sd > 0):
+                raise ValueError("weights='std' needs observations that vary in every component")
+            w = sd[0] / sd
+        else:
+            w = np.asarray(weights, dtype=np.float64).ravel()
+            if w.size != len(names) or not np.all(np.isfinite(w)) or not np.all(w > 0):
+                raise ValueError(bad)
+        return dobs, w
+
+    @staticmethod
+    def _only_mtopo(kwargs):
+        unknown = sorted(set(kwargs) - {"mtopo"})
+        if unknown:
+            raise TypeError("unexpected keyword argument %r" % unknown[0])
+
+    def _refuse(self, coordinate, wavelet, matrix_free, shift_invariant, shard, blocks=0, n=0):
+        """What the store does not do, decided before any device work; blocks x n: its stacked rows."""
+        store = self._store
+        if coordinate == "spherical" and not self._spherical:
+            raise NotImplementedError("%s holds prism fields: tesseroids (coordinate='spherical') are not supported"
+                                      % store)
+        if coordinate != ("spherical" if self._spherical else "cartesian"):
+            raise ValueError("Please choose coordinate from(cartesian, spherical)!")
+        if wavelet not in (False, None):
+            raise NotImplementedError("wavelet compression of %s is not supported" % store)
+        if matrix_free:
+            raise NotImplementedError("%s is dense: the matrix-free mode is not supported" % store)
+        if shift_invariant and not self._has_table:
+            raise NotImplementedError("%s is dense: the shift-invariant store is not supported" % store)
+        if shard is not None:
+            raise NotImplementedError("%s is not sharded" % store)
+        if blocks * n > 16384 and not shift_invariant:
+            raise NotImplementedError("%d %ss x %d observations = %d rows: %s takes at most 16384 (it runs on the fused "
+                                      "sweep)%s" % (blocks, self._word, n, blocks * n, store, self._rows_hint))
+
+    # ------------------------------------------------------------------ the construction
+    def _assemble(self, engine, title, names, dobs, w, n, mrange, mspacing, obsurface, mratio, mseg, mdivisionsection,
+                  weightfactor, shift_invariant, device, topos):
+        """Mesh, assembly, weighting and data of the blocks `names` with the observation vectors dobs and the data
+        weights w at the n points of obsurface, with the lines the constructors print.  engine: Engine, by the name
+        the class's own file has for it (the host suites replace that name to see where device work starts)."""
+        self.components, self.weights, self._n = names, w, n
+        self.mrange, self.mspacing, self.mratio = mrange, mspacing, mratio
+        self.mseg, self.mdivisionsection = mseg, mdivisionsection
+        self.weightfactor = weightfactor
+        self.lonobs, self.latobs, self.heightobs = obsurface[0], obsurface[1], obsurface[2]
+        self.wavelet = False
+        self.device = device
+        self.shift_invariant = bool(shift_invariant)
+
+        self._say(title)
+        mesh = _mesh(self._spherical, mrange, mspacing, mratio, mseg, mdivisionsection)
+        self._carve(mesh, topos)
+        mesh.addprop(self._prop, np.zeros(mesh.size if self._props == 1 else (mesh.size, self._props)))
+        self.mesh = mesh
+
+        bounds = mesh.cell_bounds(active_only=True)
+        self._say("Start of calculate kernel")
+        start = time.time()
+        eng = engine(len(dobs) * n, self._props * bounds.shape[0], device=device)
+        self._set_cells(eng, bounds)
+        eng.set_obs(self.lonobs, self.latobs, self.heightobs)
+        self._build(eng, self._spherical)
+        self._say("kernel.shape", (eng.N, eng.M))
+        self._say("End of calculate kernel:%.6f s" % (time.time() - start))
+        self._engine = eng
+
+        self.mshape = mesh.shape
+        self.mxs, self.mys, self.mzs = mesh.get_xs(), mesh.get_ys(), mesh.get_zs()
+        self._say("Start to weight kernel")
+        start = time.time()
+        self.sensitivityWeighting()
+        self._say("End of weighting kernel: %.6f s" % (time.time() - start))
+        self.dobs = np.concatenate(dobs)
+        if self._vector:
+            self.dobsw = self.Wb @ self.dobs
+        eng.set_data(self.dobsw if self._vector else self.dobs)
+
+    def sensitivityWeighting(self):
+        """Wb (w_b on block b), Wm (column norms of Wb A to the power 2 weightfactor, over all M columns) and
+        Aw = Wb A Wm^-1, on the device."""
+        self._weight(self.weightfactor)
+        if self._vector:
+            self.Wb = _diag(np.repeat(self.weights, self._n))
+
+    # ------------------------------------------------------------------ what is formed from the store
+    def _no_table(self, what):
+        if self.shift_invariant:
+            raise NotImplementedError("%s: %s keeps the shift-invariant table, the kernel is never stored" %
+                                      (what, self._store))
+
+    def forward(self, model):
+        """Unweighted forward A @ model of the physical model (M entries, property-major): the predicted values,
+        component-major, each block in its own units."""
+        model = np.asarray(model, dtype=np.float64).ravel()
+        d = self._engine.forward(model * self.Wm.diagonal())
+        return d / self.Wb.diagonal() if self._vector else d
+
+    def block_means(self):
+        """(means of the last evaluation's weighted prediction Aw mw, means removed from the weighted observations),
+        one per block."""
+        info = self._engine.multi_info()
+        return info["pred_mean"], info["obs_mean"]
