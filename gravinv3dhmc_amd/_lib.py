@@ -59,6 +59,7 @@ PROTOTYPES = {
     "gh_amplitude_eval": (C.c_int, [_ctx, _dp, C.POINTER(C.c_double), _dp, _dp]),
     "gh_amplitude_last": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
     "gh_set_cells_multi": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp]),
+    "gh_set_cells_multi_table": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp]),
     "gh_set_cells_tess_multi": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
     "gh_multi_info": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp, _dp]),
     "gh_joint_std": (C.c_int, [_ctx, _dp]),

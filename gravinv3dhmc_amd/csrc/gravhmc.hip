@@ -270,7 +270,9 @@ struct BlockCells {
     const double *weights, *ratios;  // ratios: one per block (the tesseroid multi-component store)
     double ratio;                    // ... or one for the store (the tesseroid magnetization store)
     const double *fdir;
-    bool on_table;  // gh_set_cells_tess_mag_table: onto the shift-invariant table in the same call (no limit on the rows)
+    // gh_set_cells_tess_mag_table, gh_set_cells_multi_table: onto the store's table -- the shift-invariant one of the
+    // tesseroids, the translation-invariant one of the prisms -- in the same call (no limit on the rows)
+    bool on_table;
 };
 
 // The stores of blocks but the joint one, each in the order of its own checks: the component list, the column and row
@@ -321,7 +323,8 @@ static int set_block_cells(gh_ctx *c, int kind, const BlockCells &a)
     c->comp = s.comps == COMPS_GRAV ? a.comps[0] : GH_COMP_GZ;
     if (s.tess) c->ratio = a.ratios ? a.ratios[0] : a.ratio;
     c->have_cells = true;
-    return a.on_table ? gh_set_shift_invariant(c, 1) : GH_OK;
+    if (a.on_table && !s.tess) lattice_switch_on(c, true);
+    return a.on_table && s.tess ? gh_set_shift_invariant(c, 1) : GH_OK;
 }
 
 int gh_set_cells_mvi(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
@@ -420,6 +423,14 @@ int gh_set_cells_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *c
 {
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_multi: null pointer");
     return set_block_cells(c, GH_CELL_PRISM_MULTI, {bounds6, nullptr, ncomp, comps, weights, nullptr, 0.0, nullptr, false});
+}
+
+// (the same context as gh_set_cells_multi makes, and that call's name in the refusals; the geometry is looked at by
+// gh_build_G)
+int gh_set_cells_multi_table(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *weights)
+{
+    if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_multi: null pointer");
+    return set_block_cells(c, GH_CELL_PRISM_MULTI, {bounds6, nullptr, ncomp, comps, weights, nullptr, 0.0, nullptr, true});
 }
 
 int gh_set_cells_tess_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *ratios,
@@ -761,6 +772,10 @@ int gh_set_translation_invariant(gh_ctx *c, int enable)
     if (!c) return GH_ERR_ARG;
     if (enable) TRY(dense_single_chain_refuse(c, "gh_set_translation_invariant"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: call before gh_build_G");
+    if (lattice_multi(c))
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_set_translation_invariant: %s was set onto %s with its cells "
+                                           "(gh_set_cells_multi_table): the table is this context's form", store_name(c),
+                    LATTICE_NAME);
     if (enable && c->ls)
         return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: the shift-invariant store is switched on: one form at a time");
     if (enable && !c->lat && c->mf)
@@ -775,11 +790,7 @@ int gh_set_translation_invariant(gh_ctx *c, int enable)
     if (c->lat) c->mf = c->lat->mf_before;
     delete c->lat;
     c->lat = nullptr;
-    if (enable) {
-        c->lat = new LatticeHost();
-        c->lat->mf_before = c->mf;
-        c->mf = true;
-    }
+    if (enable) lattice_switch_on(c, false);
     return GH_OK;
 }
 
@@ -795,7 +806,7 @@ int gh_translation_invariant_info(const gh_ctx *c, int *on, int *nx, int *ny, in
     if (nz) *nz = g.nz;
     if (px) *px = g.px;
     if (qy) *qy = g.qy;
-    if (table_bytes) *table_bytes = (int64_t)g.nz * g.U * g.V * (int64_t)sizeof(double);
+    if (table_bytes) *table_bytes = (int64_t)(o ? c->lat->nb : 1) * g.nz * g.U * g.V * (int64_t)sizeof(double);
     if (max_dev) *max_dev = o ? c->lat->max_dev : 0.0;
     if (build_ms) *build_ms = o ? c->lat->build_ms : 0.0;
     return GH_OK;
@@ -807,7 +818,7 @@ int gh_translation_invariant_table(gh_ctx *c, double *out)
     TRY(need(c, lattice_on(c), "gh_translation_invariant_table: no table resident (gh_set_translation_invariant, gh_build_G)"));
     HIPCHK(c, hipSetDevice(c->device));
     const ghk::LatGeom &g = c->lat->g;
-    return d2h(c, out, c->lat->T, (size_t)g.nz * (size_t)g.U * (size_t)g.V);
+    return d2h(c, out, c->lat->T, (size_t)c->lat->nb * (size_t)g.nz * (size_t)g.U * (size_t)g.V);  // (block-major)
 }
 
 int gh_lattice_detect(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6, int *dims5,
@@ -881,17 +892,18 @@ int gh_build_G(gh_ctx *c)
     c->leaves = 0;
     if (c->mf) {
         if (c->slab) return fail(c, GH_ERR_ARG, "gh_build_G: a matrix-free context is built once");
-        // (a store of blocks: only the tesseroid forms get here, by way of the table)
+        // (a store of blocks: the tesseroid forms and the prisms' multi-component store get here, by way of their tables)
         if (c->lat) {
-            TRY(dense_single_chain_refuse(c, "gh_build_G on the translation-invariant store"));
-            if (c->cell_kind != GH_CELL_PRISM && c->cell_kind != GH_CELL_PRISM_COMP && c->cell_kind != GH_CELL_PRISM_TF)
+            if (!c->lat->multi) TRY(dense_single_chain_refuse(c, "gh_build_G on the translation-invariant store"));
+            if (c->cell_kind != GH_CELL_PRISM && c->cell_kind != GH_CELL_PRISM_COMP && c->cell_kind != GH_CELL_PRISM_TF &&
+                !c->lat->multi)
                 return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s holds prisms (tesseroid grids: gh_set_shift_invariant)",
                             LATTICE_NAME);
             if (c->sh.kind != 0)
                 return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s is not supported on a sharded context (one GPU holds the table)",
                             LATTICE_NAME);
         }
-        if (store_name(c) && !c->ls)
+        if (store_name(c) && !c->ls && !lattice_multi(c))
             return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s has no matrix-free mode (dense, or the shift-invariant store)",
                         store_name(c));
         c->mf_fused = c->ld <= 16384 && env_int("GRAVHMC_MF_FUSED", 1) != 0;
@@ -1061,7 +1073,8 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
             rb.w[b] = c->mc.w[b];
             unit = unit && rb.w[b] == 1.0;
         }
-        // (the shift-invariant table took the weights when it was built: there is no G)
+        // (the shift-invariant table took the weights when it was built, the translation-invariant table's passes take
+        // them from here on: there is no G)
         if (!unit && !c->mf) {
             const unsigned blocks = (unsigned)std::min<int64_t>((c->ld * c->M + 255) / 256, 1 << 20);
             scale_rowblocks_kernel<<<dim3(blocks), dim3(256), 0, c->stream>>>(c->G, c->ld, c->M, rb);
@@ -1072,7 +1085,15 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
         lonsym_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
             lonsym_geom(c), c->ls->a_of, c->ls->m_of, weightfactor, c->wm);
     } else if (lattice_on(c)) {
-        lat_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(c->lat->g, weightfactor, c->wm);
+        if (c->lat->multi) {
+            // (the column norms of Wb A: the weights, which the passes apply once the context is weighted)
+            ghk::LatBlocks bl = lattice_blocks(c);
+            for (int b = 0; b < bl.n; ++b) bl.w[b] = c->mc.w[b];
+            lat_colnorm_blocks_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(c->lat->g, bl, weightfactor,
+                                                                                                       c->wm);
+        } else {
+            lat_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(c->lat->g, weightfactor, c->wm);
+        }
     } else if (c->mf) {
         hipLaunchKernelGGL(mf_pick(c, mf_colnorm_kernel<MF_E_GEN>, mf_colnorm_kernel<MF_E_TF>, mf_colnorm_kernel<MF_E_COMP>,
                                    mf_colnorm_kernel<MF_E_TESS>),

@@ -169,12 +169,16 @@ static int refuse_plain_cells(gh_ctx *c)
 
 // The stores that are dense and run one chain -- the joint gravity-magnetic store, the multi-component stores and the
 // magnetization-vector stores -- refuse `who`, each naming itself.  (The tesseroid forms also run on the
-// shift-invariant table: still one chain, no other form.)
+// shift-invariant table, the prisms' multi-component store on the translation-invariant one: still one chain, no
+// other form.)
+static bool lattice_multi(const gh_ctx *c);  // host_lattice.h: the multi-component store set onto its table
 static int dense_single_chain_refuse(gh_ctx *c, const char *who)
 {
     if (c && store_name(c))
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on %s (%s, single chain)", who, store_name(c),
-                    store_of(c).table != TABLE_NO ? "dense or shift-invariant" : "dense");
+                    store_of(c).table != TABLE_NO ? "dense or shift-invariant"
+                    : lattice_multi(c)            ? "dense or on the translation-invariant table"
+                                                  : "dense");
     return GH_OK;
 }
 

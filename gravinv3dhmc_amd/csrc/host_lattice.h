@@ -164,9 +164,35 @@ struct LatticeHost {
     double *T = nullptr;
     int *cell_of = nullptr, *obs_of = nullptr;
     double max_dev = 0.0, build_ms = 0.0;
+    // the multi-component store on the table (gh_set_cells_multi_table): nb row blocks, one table each; else 1
+    bool multi = false;
+    int nb = 1;
 };
 
 static bool lattice_on(const gh_ctx *c) { return c->lat && c->lat->on; }
+// the multi-component store asked onto the table: gh_set_cells_multi_table is the one call that does
+static bool lattice_multi(const gh_ctx *c) { return c->lat && c->lat->multi; }
+
+// What gh_set_translation_invariant(1) does to a context that may take the table (its own checks passed), and what
+// gh_set_cells_multi_table does once the store's blocks are set
+static void lattice_switch_on(gh_ctx *c, bool multi)
+{
+    c->lat = new LatticeHost();
+    c->lat->mf_before = c->mf;
+    c->lat->multi = multi;
+    c->mf = true;
+}
+
+// The row blocks as the kernels take them; the data weights hold from gh_weight on, as on the dense store (whose
+// rows gh_weight scales)
+static ghk::LatBlocks lattice_blocks(const gh_ctx *c)
+{
+    ghk::LatBlocks bl{};
+    bl.n = c->lat->nb;
+    bl.Nb = store_points(c);
+    for (int b = 0; b < bl.n; ++b) bl.w[b] = (c->lat->multi && c->weighted) ? c->mc.w[b] : 1.0;
+    return bl;
+}
 
 // What does not run on the store names it
 static int lattice_refuse(gh_ctx *c, const char *who, const char *why)
@@ -195,20 +221,24 @@ static size_t lat_lds_bytes(const ghk::LatPlan &p, int NFip)
 }
 
 typedef void (*lat_fill_fn)(MfGeom, ghk::LatGeom, double *, double *);
+typedef void (*lat_pass_fn)(ghk::LatGeom, ghk::LatPlan, SweepArgs, const double *, int64_t, ghk::LatBlocks);
 
 // gh_build_G of a context with the store switched on: detect, fill, check
 static int lattice_build(gh_ctx *c)
 {
     LatticeHost &h = *c->lat;
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<double> ox((size_t)c->N), oy((size_t)c->N), oz((size_t)c->N), b6((size_t)c->M * 6);
+    // (row blocks: the blocks share the N / nb points)
+    const int64_t Np = store_points(c);
+    h.nb = h.multi ? c->mc.n : 1;
+    std::vector<double> ox((size_t)Np), oy((size_t)Np), oz((size_t)Np), b6((size_t)c->M * 6);
     TRY(d2h(c, ox.data(), c->obs[0], ox.size()));
     TRY(d2h(c, oy.data(), c->obs[1], oy.size()));
     TRY(d2h(c, oz.data(), c->obs[2], oz.size()));
     TRY(d2h(c, b6.data(), c->bounds, b6.size()));
     int dims[5] = {0, 0, 0, 0, 0};
     std::vector<int> loc, col, loo, ool;
-    const int reason = lattice_detect_host(c->N, ox.data(), oy.data(), oz.data(), c->M, b6.data(), dims, loc, col, loo, ool);
+    const int reason = lattice_detect_host(Np, ox.data(), oy.data(), oz.data(), c->M, b6.data(), dims, loc, col, loo, ool);
     if (reason != GH_LATTICE_ON)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s needs a regular prism grid under gridded data: %s", LATTICE_NAME,
                     lattice_reason_text(reason));
@@ -222,7 +252,7 @@ static int lattice_build(gh_ctx *c)
     g.V = g.ny + g.qy - 1;
     g.nyp = (g.ny + 7) / 8 * 8;
     g.qyp = (g.qy + 7) / 8 * 8;
-    const size_t nT = (size_t)g.nz * (size_t)g.U * (size_t)g.V;
+    const size_t nT = (size_t)g.nz * (size_t)g.U * (size_t)g.V;  // (of one block)
     if (nT > (size_t)INT_MAX * 4)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s: a table of %zu entries is beyond the fill kernel's grid", LATTICE_NAME, nT);
     // the passes' partition and their LDS
@@ -233,45 +263,70 @@ static int lattice_build(gh_ctx *c)
     if (h.lds_adj > 160 * 1024 || h.lds_fwd > 160 * 1024)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s: %s (%d cells, %d observations along y: %zu bytes)", LATTICE_NAME,
                     lattice_reason_text(GH_LATTICE_LDS), g.ny, g.qy, std::max(h.lds_adj, h.lds_fwd));
-    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<false>), h.lds_adj));
-    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<true>), h.lds_fwd));
+    if (h.multi) {
+        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<false, true>), h.lds_adj));
+        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<true, true>), h.lds_fwd));
+    } else {
+        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<false, false>), h.lds_adj));
+        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<true, false>), h.lds_fwd));
+    }
     h.gx_adj = (g.nx + h.adj.TR - 1) / h.adj.TR * h.adj.FT;
     h.gx_fwd = (g.px + h.fwd.TR - 1) / h.fwd.TR * h.fwd.FT;
     {
         // forward: chunks of layers, one slab row each -- about four workgroups per CU, no more rows than layers
-        const int want = std::max(1, std::min(g.nz, (4 * c->cus + h.gx_fwd - 1) / h.gx_fwd));
+        // (row blocks: nb gx_fwd workgroups per chunk)
+        const int per = h.nb * h.gx_fwd;
+        const int want = std::max(1, std::min(g.nz, (4 * c->cus + per - 1) / per));
         h.fwd.lpc = (g.nz + want - 1) / want;
         h.chunks = (g.nz + h.fwd.lpc - 1) / h.fwd.lpc;
     }
-    TRY(dalloc(c, &h.T, nT, false));
+    TRY(dalloc(c, &h.T, (size_t)h.nb * nT, false));
     TRY(dalloc(c, &h.cell_of, (size_t)c->M, false));
-    TRY(dalloc(c, &h.obs_of, (size_t)c->N, false));
-    TRY(dalloc(c, &g.rl, (size_t)g.px * (size_t)g.qyp));          // (zeroed: the padding stays zero)
+    TRY(dalloc(c, &h.obs_of, (size_t)Np, false));
+    TRY(dalloc(c, &g.rl, (size_t)h.nb * (size_t)g.px * (size_t)g.qyp));  // (zeroed: the padding stays zero)
     TRY(dalloc(c, &g.xl, (size_t)c->M / (size_t)g.ny * (size_t)g.nyp));
     HIPCHK(c, hipMemcpyAsync(h.cell_of, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(h.obs_of, ool.data(), sizeof(int) * ool.size(), hipMemcpyHostToDevice, c->stream));
     g.T = h.T;
     g.cell_of = h.cell_of;
     g.obs_of = h.obs_of;
-    // fill: the entry of the first and of the last pair of every offset
+    // fill: the entry of the first and of the last pair of every offset.  (Row blocks: block after block, each with the
+    // entry function of a gh_set_cells_prism context of its component at the Np points; the deviation is a fraction of
+    // the block's own largest entry, and the largest over the blocks is kept.)
     double *T2 = nullptr;
     HIPCHK(c, hipMalloc((void **)&T2, nT * sizeof(double)));
-    hipLaunchKernelGGL(mf_pick<lat_fill_fn>(c, ghk::lat_fill_kernel<MF_E_GEN>, ghk::lat_fill_kernel<MF_E_TF>,
-                                            ghk::lat_fill_kernel<MF_E_COMP>, ghk::lat_fill_kernel<MF_E_GEN>),
-                       dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, c->stream, mf_geom(c), g, h.T, T2);
     std::vector<double> t1(nT), t2(nT);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(t1.data(), h.T, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(t2.data(), T2, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (col / ool must outlive their copies as well)
-    (void)hipFree(T2);
-    if (e != hipSuccess) return fail(c, GH_ERR_HIP, "gh_build_G: %s: fill of the table: %s", LATTICE_NAME, hipGetErrorString(e));
-    double tmax = 0.0, dmax = 0.0;
-    for (size_t i = 0; i < nT; ++i) {
-        tmax = std::max(tmax, std::fabs(t1[i]));
-        dmax = std::max(dmax, std::fabs(t2[i] - t1[i]));
+    h.max_dev = 0.0;
+    for (int b = 0; b < h.nb; ++b) {
+        MfGeom mg = mf_geom(c);
+        lat_fill_fn fill = mf_pick<lat_fill_fn>(c, ghk::lat_fill_kernel<MF_E_GEN>, ghk::lat_fill_kernel<MF_E_TF>,
+                                                ghk::lat_fill_kernel<MF_E_COMP>, ghk::lat_fill_kernel<MF_E_GEN>);
+        if (h.multi) {
+            // (gz is the GH_CELL_PRISM context's entry, as gh_set_cells_prism makes it: not among the run-time components)
+            const bool gz = c->mc.comp[b] == GH_COMP_GZ;
+            mg.kind = gz ? GH_CELL_PRISM : GH_CELL_PRISM_COMP;
+            mg.comp = c->mc.comp[b];
+            mg.N = Np;
+            fill = gz ? ghk::lat_fill_kernel<MF_E_GEN> : ghk::lat_fill_kernel<MF_E_COMP>;
+        }
+        double *Tb = h.T + (size_t)b * nT;
+        hipLaunchKernelGGL(fill, dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, c->stream, mg, g, Tb, T2);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(t1.data(), Tb, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(t2.data(), T2, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (col / ool must outlive their copies as well)
+        if (e != hipSuccess) {
+            (void)hipFree(T2);
+            return fail(c, GH_ERR_HIP, "gh_build_G: %s: fill of the table: %s", LATTICE_NAME, hipGetErrorString(e));
+        }
+        double tmax = 0.0, dmax = 0.0;
+        for (size_t i = 0; i < nT; ++i) {
+            tmax = std::max(tmax, std::fabs(t1[i]));
+            dmax = std::max(dmax, std::fabs(t2[i] - t1[i]));
+        }
+        h.max_dev = std::max(h.max_dev, tmax > 0.0 ? dmax / tmax : (dmax > 0.0 ? HUGE_VAL : 0.0));
     }
-    h.max_dev = tmax > 0.0 ? dmax / tmax : (dmax > 0.0 ? HUGE_VAL : 0.0);
+    (void)hipFree(T2);
     h.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (!(h.max_dev <= FOLD_MAX_DEV))
         return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s: %s (%.3g of the largest entry)", LATTICE_NAME,
@@ -292,16 +347,24 @@ static int launch_lattice(gh_ctx *c, SweepArgs &a, const double *wm)
 {
     const LatticeHost &h = *c->lat;
     const ghk::LatGeom &g = h.g;
+    // (row blocks: the same grid for the adjoint, whose blocks run inside the kernel; the block as the forward's
+    // third grid coordinate, under one gather of x)
+    const ghk::LatBlocks bl = lattice_blocks(c);
+    const lat_pass_fn adj_one = ghk::lat_pass_kernel<false, false>, adj_blocks = ghk::lat_pass_kernel<false, true>;
+    const lat_pass_fn fwd_one = ghk::lat_pass_kernel<true, false>, fwd_blocks = ghk::lat_pass_kernel<true, true>;
     if (a.mode & SW_ADJ) {
-        ghk::lat_gather_r_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(g, a.r);
-        hipLaunchKernelGGL(ghk::lat_pass_kernel<false>, dim3((unsigned)h.gx_adj, (unsigned)g.nz), dim3(ghk::LAT_THREADS),
-                           h.lds_adj, c->stream, g, h.adj, a, wm, c->ld);
+        if (h.multi)
+            ghk::lat_gather_r_blocks_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(g, bl, a.r);
+        else
+            ghk::lat_gather_r_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(g, a.r);
+        hipLaunchKernelGGL(h.multi ? adj_blocks : adj_one, dim3((unsigned)h.gx_adj, (unsigned)g.nz), dim3(ghk::LAT_THREADS),
+                           h.lds_adj, c->stream, g, h.adj, a, wm, c->ld, bl);
     }
     if (a.mode & SW_FWD) {
         const double *x = (a.mode & SW_UPD) ? a.x_out : a.x_in;
         ghk::lat_gather_x_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(g, x, wm);
-        hipLaunchKernelGGL(ghk::lat_pass_kernel<true>, dim3((unsigned)h.gx_fwd, (unsigned)h.chunks), dim3(ghk::LAT_THREADS),
-                           h.lds_fwd, c->stream, g, h.fwd, a, wm, c->ld);
+        hipLaunchKernelGGL(h.multi ? fwd_blocks : fwd_one, dim3((unsigned)h.gx_fwd, (unsigned)h.chunks, (unsigned)h.nb),
+                           dim3(ghk::LAT_THREADS), h.lds_fwd, c->stream, g, h.fwd, a, wm, c->ld, bl);
     }
     return GH_OK;
 }

@@ -14,7 +14,7 @@
 // Both products are correlations along the fast lattice axis, per (layer, cell row a, observation row p):
 //     adjoint   g[k,a,b] = sum_p sum_q T[k][p-a+nx-1][q-b+ny-1] r[p,q]
 //     forward   d[p,q]   = sum_k sum_a sum_b T[k][p-a+nx-1][q-b+ny-1] xs[k,a,b]        xs = x / wm
-// and lat_pass_kernel<FWD> is ONE kernel for both: "output rows" (a | p) of NFo outputs (b | q), "input rows"
+// and lat_pass_kernel<FWD, MB> is ONE kernel for both: "output rows" (a | p) of NFo outputs (b | q), "input rows"
 // (p | a) of NFi inputs (q | b); the forward reads the table row backwards, which turns it into the adjoint's
 // form  out[o] = sum_i row[i - o + const] in[i].  Plain launches, no waits between workgroups.
 //
@@ -43,6 +43,13 @@
 // Every sum runs in an order fixed by indices alone (inputs ascending inside a row, input rows of a wave
 // ascending, layers ascending, waves 0..3): results are reproducible bit for bit.  The update arithmetic behind
 // the adjoint is mf_adjoint_kernel's, expression for expression.
+//
+// Row blocks (the multi-component store on the table, gh_set_cells_multi_table): nb components of the same cells at the
+// same points are nb tables T[b][k][u][v], block-major, each the unweighted table of its field; the data weights w_b
+// are not in them.  rl is [b][p][.] = w_b r of block b, the forward multiplies a finished output sum by w_b.  The
+// adjoint (MB) runs the steps of four input rows block after block into the SAME accumulators -- a step never mixes
+// two blocks, the rows past px of a block's last step are zeros -- then the one cell update; the forward takes the
+// block as blockIdx.z and shares xl.  The LDS tile is the single block's.  Order of the sums: block, input row, input.
 #pragma once
 
 namespace ghk {
@@ -55,11 +62,18 @@ struct LatGeom {
     int nx, ny, nz, px, qy;
     int U, V;             // nx + px - 1, ny + qy - 1
     int nyp, qyp;         // ny, qy rounded up to 8
-    const double *T;      // [nz][U][V]
+    const double *T;      // [nz][U][V] (row blocks: [nb][nz][U][V])
     const int *cell_of;   // [nz][nx][ny]: the caller's cell
     const int *obs_of;    // [px][qy]: the caller's observation
-    double *rl;           // [px][qyp]: r in lattice order (zero beyond qy)
+    double *rl;           // [px][qyp]: r in lattice order (zero beyond qy); row blocks: [nb][px][qyp], w_b r
     double *xl;           // [nz][nx][nyp]: x / wm in lattice order (zero beyond ny)
+};
+
+// The row blocks of the multi-component store on the table: n blocks of Nb observations, block b times w[b]
+struct LatBlocks {
+    int n;
+    int64_t Nb;
+    double w[MULTI_MAX];
 };
 
 // partition of one pass (host_lattice.h: lat_plan)
@@ -119,6 +133,37 @@ __global__ void __launch_bounds__(256) lat_gather_r_kernel(LatGeom l, const doub
     l.rl[(int64_t)p * l.qyp + q] = r[l.obs_of[e]];
 }
 
+// Row blocks: wm_j = (sum_b w_b^2 sum over the window of T_b^2)^wf, blocks ascending, each block's sum as above
+__global__ void __launch_bounds__(256) lat_colnorm_blocks_kernel(LatGeom l, LatBlocks bl, double wf, double *wm)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)l.nz * l.nx * l.ny) return;
+    const int b = (int)(e % l.ny), a = (int)((e / l.ny) % l.nx), k = (int)(e / ((int64_t)l.ny * l.nx));
+    double st = 0.0;
+    for (int blk = 0; blk < bl.n; ++blk) {
+        const double *Tk = l.T + ((int64_t)blk * l.nz + k) * l.U * l.V;
+        double s = 0.0;
+        for (int p = 0; p < l.px; ++p) {
+            const double *row = Tk + (int64_t)(p - a + l.nx - 1) * l.V + (l.ny - 1 - b);
+            for (int q = 0; q < l.qy; ++q) s += row[q] * row[q];
+        }
+        st += (bl.w[blk] * bl.w[blk]) * s;
+    }
+    wm[l.cell_of[e]] = (wf == 0.5) ? sqrt(st) : pow(st, wf);
+}
+
+// Row blocks: rl[b][p][q] = w_b r[b Nb + obs_of[p, q]]
+__global__ void __launch_bounds__(256) lat_gather_r_blocks_kernel(LatGeom l, LatBlocks bl, const double *r)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t PQ = (int64_t)l.px * l.qy;
+    if (e >= PQ * bl.n) return;
+    const int b = (int)(e / PQ);
+    const int64_t o = e - b * PQ;
+    const int p = (int)(o / l.qy), q = (int)(o - (int64_t)p * l.qy);
+    l.rl[((int64_t)b * l.px + p) * l.qyp + q] = bl.w[b] * r[b * bl.Nb + l.obs_of[o]];
+}
+
 // x / wm (the caller's order; wm: or nullptr, the unweighted kernel) -> xl, as mf_forward_kernel scales x
 __global__ void __launch_bounds__(256) lat_gather_x_kernel(LatGeom l, const double *x, const double *wm)
 {
@@ -135,9 +180,11 @@ __global__ void __launch_bounds__(256) lat_gather_x_kernel(LatGeom l, const doub
 // product; else blockIdx.y = layer, and the cells' update follows the dots (a.mode: SW_ADJ with SW_UPD / SW_PFIN /
 // SW_SPEC / SW_GOUT as in mf_adjoint_kernel; pp_part[blockIdx.y * gridDim.x + blockIdx.x]).  blockIdx.x =
 // (tile of output rows) * pl.FT + tile of the fast axis.  Dynamic LDS: (pl.TR + 3) pl.WL + 4 NFi8 + 2048 doubles.
-template <bool FWD>
+// MB: row blocks (bl).  FWD: blockIdx.z = block, outputs to slab[chunk][b Nb + obs] times w_b; else the steps of four
+// input rows run block after block over rl[b] with T[b], before the one update.  !MB: bl is not read.
+template <bool FWD, bool MB>
 __global__ void __launch_bounds__(LAT_THREADS) lat_pass_kernel(LatGeom g, LatPlan pl, SweepArgs a, const double *wm,
-                                                               int64_t ld)
+                                                               int64_t ld, LatBlocks bl)
 {
     extern __shared__ __attribute__((aligned(16))) double lat_lds[];
     __shared__ double ppred[LAT_G];
@@ -161,49 +208,54 @@ __global__ void __launch_bounds__(LAT_THREADS) lat_pass_kernel(LatGeom g, LatPla
 #pragma unroll
     for (int rr = 0; rr < LAT_R; ++rr) acc[rr] = 0.0;
 
+    // (the adjoint's blocks in turn, the forward's one block)
+    const int b0 = (MB && FWD) ? (int)blockIdx.z : 0;
+    const int b1 = (MB && !FWD) ? bl.n : b0 + 1;
     for (int k = k0; k < k1; ++k) {
-        const double *Tk = g.T + (int64_t)k * g.U * g.V;
-        const double *inl = FWD ? g.xl + (int64_t)k * g.nx * g.nyp : g.rl;
-        for (int ir0 = 0; ir0 < NRi; ir0 += LAT_G) {
-            __syncthreads();  // (the previous step's reads of tabs / ins)
-            // table rows u_lo .. u_lo + TRW - 1; staged index wl <-> v (the forward reads the row backwards)
-            const int u_lo = FWD ? row0 - (ir0 + LAT_G - 1) + g.nx - 1 : ir0 - row0 - TR + g.nx;
-            for (int e = tid; e < TRW * WL; e += LAT_THREADS) {
-                const int ur = e / WL, wl = e - ur * WL;
-                const int u = u_lo + ur;
-                const int v = FWD ? ot0 - wl + tnp + g.ny - 2 : wl - tnp - ot0 + g.ny;
-                const double val = (u >= 0 && u < g.U && v >= 0 && v < g.V) ? Tk[(int64_t)u * g.V + v] : 0.0;
-                tabs[ur * WL + ((wl >> 1) & 3) * nb2 + 2 * (wl >> 3) + (wl & 1)] = val;
-            }
-            for (int e = tid; e < LAT_G * NFip; e += LAT_THREADS) {
-                const int gi = e / NFip, i = e - gi * NFip;
-                ins[e] = (ir0 + gi < NRi) ? inl[(int64_t)(ir0 + gi) * NFip + i] : 0.0;
-            }
-            __syncthreads();
-            if (act) {
-                const int ur = FWD ? orow - w + LAT_G - 1 : w - orow + TR - 1;
-                const double *trow = tabs + ur * WL;
-                const double *in = ins + w * NFip;
-                for (int i0 = 0; i0 < NFip; i0 += LAT_R) {
-                    // the window: staged values 8 B0 .. 8 B0 + 15 (tw[t] pairs with input s and output rr = s + 7 - t)
-                    const int B0 = (i0 >> 3) - ob + nobt - 1;
-                    double tw[2 * LAT_R], iv[LAT_R];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const d2 lo = *reinterpret_cast<const d2 *>(trow + t * nb2 + 2 * B0);
-                        const d2 hi = *reinterpret_cast<const d2 *>(trow + t * nb2 + 2 * B0 + 2);
-                        tw[2 * t] = lo.x;
-                        tw[2 * t + 1] = lo.y;
-                        tw[8 + 2 * t] = hi.x;
-                        tw[8 + 2 * t + 1] = hi.y;
-                        const d2 vi = *reinterpret_cast<const d2 *>(in + i0 + 2 * t);
-                        iv[2 * t] = vi.x;
-                        iv[2 * t + 1] = vi.y;
+        for (int blk = b0; blk < b1; ++blk) {
+            const double *Tk = g.T + ((int64_t)blk * g.nz + k) * g.U * g.V;
+            const double *inl = FWD ? g.xl + (int64_t)k * g.nx * g.nyp : g.rl + (int64_t)blk * g.px * g.qyp;
+            for (int ir0 = 0; ir0 < NRi; ir0 += LAT_G) {
+                __syncthreads();  // (the previous step's reads of tabs / ins)
+                // table rows u_lo .. u_lo + TRW - 1; staged index wl <-> v (the forward reads the row backwards)
+                const int u_lo = FWD ? row0 - (ir0 + LAT_G - 1) + g.nx - 1 : ir0 - row0 - TR + g.nx;
+                for (int e = tid; e < TRW * WL; e += LAT_THREADS) {
+                    const int ur = e / WL, wl = e - ur * WL;
+                    const int u = u_lo + ur;
+                    const int v = FWD ? ot0 - wl + tnp + g.ny - 2 : wl - tnp - ot0 + g.ny;
+                    const double val = (u >= 0 && u < g.U && v >= 0 && v < g.V) ? Tk[(int64_t)u * g.V + v] : 0.0;
+                    tabs[ur * WL + ((wl >> 1) & 3) * nb2 + 2 * (wl >> 3) + (wl & 1)] = val;
+                }
+                for (int e = tid; e < LAT_G * NFip; e += LAT_THREADS) {
+                    const int gi = e / NFip, i = e - gi * NFip;
+                    ins[e] = (ir0 + gi < NRi) ? inl[(int64_t)(ir0 + gi) * NFip + i] : 0.0;
+                }
+                __syncthreads();
+                if (act) {
+                    const int ur = FWD ? orow - w + LAT_G - 1 : w - orow + TR - 1;
+                    const double *trow = tabs + ur * WL;
+                    const double *in = ins + w * NFip;
+                    for (int i0 = 0; i0 < NFip; i0 += LAT_R) {
+                        // the window: staged values 8 B0 .. 8 B0 + 15 (tw[t] pairs with input s and output rr = s + 7 - t)
+                        const int B0 = (i0 >> 3) - ob + nobt - 1;
+                        double tw[2 * LAT_R], iv[LAT_R];
+    #pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            const d2 lo = *reinterpret_cast<const d2 *>(trow + t * nb2 + 2 * B0);
+                            const d2 hi = *reinterpret_cast<const d2 *>(trow + t * nb2 + 2 * B0 + 2);
+                            tw[2 * t] = lo.x;
+                            tw[2 * t + 1] = lo.y;
+                            tw[8 + 2 * t] = hi.x;
+                            tw[8 + 2 * t + 1] = hi.y;
+                            const d2 vi = *reinterpret_cast<const d2 *>(in + i0 + 2 * t);
+                            iv[2 * t] = vi.x;
+                            iv[2 * t + 1] = vi.y;
+                        }
+    #pragma unroll
+                        for (int s = 0; s < LAT_R; ++s)
+    #pragma unroll
+                            for (int rr = 0; rr < LAT_R; ++rr) acc[rr] += tw[s - rr + LAT_R - 1] * iv[s];
                     }
-#pragma unroll
-                    for (int s = 0; s < LAT_R; ++s)
-#pragma unroll
-                        for (int rr = 0; rr < LAT_R; ++rr) acc[rr] += tw[s - rr + LAT_R - 1] * iv[s];
                 }
             }
         }
@@ -224,7 +276,10 @@ __global__ void __launch_bounds__(LAT_THREADS) lat_pass_kernel(LatGeom g, LatPla
         double s = ((red[slot * LAT_R + rr] + red[(64 + slot) * LAT_R + rr]) + red[(128 + slot) * LAT_R + rr]) +
                    red[(192 + slot) * LAT_R + rr];
         if (FWD) {
-            a.slab[(int64_t)blockIdx.y * ld + g.obs_of[(int64_t)orow_abs * g.qy + o]] = s;
+            if (MB)
+                a.slab[(int64_t)blockIdx.y * ld + b0 * bl.Nb + g.obs_of[(int64_t)orow_abs * g.qy + o]] = s * bl.w[b0];
+            else
+                a.slab[(int64_t)blockIdx.y * ld + g.obs_of[(int64_t)orow_abs * g.qy + o]] = s;
         } else {
             // (mf_adjoint_kernel's arithmetic per cell)
             const int64_t j = g.cell_of[((int64_t)k0 * g.nx + orow_abs) * g.ny + o];

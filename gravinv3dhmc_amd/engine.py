@@ -182,15 +182,21 @@ class Engine(object):
             return
         self._chk(self._lib.gh_set_cells(self._h, ptr(b), int(kind), float(ratio)))
 
-    def set_cells_multi(self, bounds6, components, weights):
+    def set_cells_multi(self, bounds6, components, weights, translation_invariant=False):
         """The M prisms of a multi-component model (gh_set_cells_multi): the gravity fields `components` (names of
         _lib.COMPONENTS or COMP_* values, distinct) of the same cells at the same N / len(components) points, stacked
-        in row blocks of one store, block c with the data weight weights[c] > 0; call it before set_obs."""
+        in row blocks of one store, block c with the data weight weights[c] > 0; call it before set_obs.
+        translation_invariant=True (gh_set_cells_multi_table): one translation-invariant table per block instead of
+        the dense store, no 16384-row limit; build_G raises NotImplementedError with the reason if the geometry lacks
+        the structure."""
         b = f64(bounds6)
         if b.shape != (self.M, 6):
             raise ValueError("bounds table must be (M, 6)")
         comps, carr, w, _ = self._blocks(_lib.COMPONENTS, components, weights)
-        self._chk(self._lib.gh_set_cells_multi(self._h, ptr(b), len(comps), carr, ptr(w)))
+        fn = self._lib.gh_set_cells_multi_table if translation_invariant else self._lib.gh_set_cells_multi
+        self._chk(fn(self._h, ptr(b), len(comps), carr, ptr(w)))
+        if translation_invariant:
+            self._translation_invariant = True
         self._set_store(_lib.CELL_PRISM_MULTI, rows=len(comps), table=True)
 
     def set_cells_tess_multi(self, bounds6, components, ratios, weights):
@@ -396,11 +402,13 @@ class Engine(object):
                 "qy": i[5].value, "table_bytes": tb.value, "max_dev": md.value, "build_ms": bm.value}
 
     def translation_invariant_table(self):
-        """The table as it lies on the device: (nz, nx + px - 1, ny + qy - 1)."""
+        """The table as it lies on the device: (nz, nx + px - 1, ny + qy - 1); on a multi-component context
+        (set_cells_multi(..., translation_invariant=True)) the C blocks' tables, (C, nz, nx + px - 1, ny + qy - 1)."""
         t = self.translation_invariant_info()
         if not t["on"]:
             raise ValueError("no table resident (set_translation_invariant, build_G)")
-        T = np.empty((t["nz"], t["nx"] + t["px"] - 1, t["ny"] + t["qy"] - 1))
+        shape = (t["nz"], t["nx"] + t["px"] - 1, t["ny"] + t["qy"] - 1)
+        T = np.empty(((self._store.rows,) + shape) if self._store.kind == _lib.CELL_PRISM_MULTI else shape)
         self._chk(self._lib.gh_translation_invariant_table(self._h, ptr(T)))
         return T
 

@@ -38,8 +38,20 @@ class MultiComponentModule(_BlockStore):
 
     HMCSample and misfit_and_grad work on it as on GravMagModule.  Not supported (NotImplementedError): tesseroids
     (coordinate="spherical"), wavelet compression, the matrix-free mode, the shift-invariant store, shards,
-    HMCSampleBatch, and more than 16384 stacked rows C N (the store runs on the fused sweep).  The folded store is
-    chosen for gz prisms alone: this store is never folded (Engine.fold_info() tells).
+    HMCSampleBatch, and more than 16384 stacked rows C N (the store runs on the fused sweep) without
+    translation_invariant=True.  The folded store is chosen for gz prisms alone: this store is never folded
+    (Engine.fold_info() tells).
+
+    translation_invariant=True keeps one translation-invariant table per component instead of the stacked kernel
+    (regular meshes -- no mratio growth, mseg or mtopo -- under gridded data: the observations a full rectangle of the
+    lattice of the cells' horizontal spacings at one height, GravMagModule's translation_invariant): the component
+    block is one more coordinate of the table, T[c][layer][dx][dy], G is never stored and the 16384-row limit does
+    not apply (the full tensor over 100 x 100 x 50 cells under 100 x 100 stations: 95 MB).  HMCSample (with
+    posterior_stream too), misfit_and_grad, forward(model), block_means(), Wb, dobsw, Wm and
+    translation_invariant_info() work on it; Aw, A and kernel(component) do not exist (NotImplementedError).
+    NotImplementedError with the detection's reason if the geometry lacks the structure, and -- naming the
+    multi-component store and the translation-invariant table -- with mtopo, wavelet, matrix_free, shift_invariant,
+    shard and coordinate="spherical".
     """
     _props, _prop = 1, 'density'
     _names, _arg, _word, _none_weight = _lib.COMPONENTS, "components", "component", False
@@ -47,19 +59,93 @@ class MultiComponentModule(_BlockStore):
 
     def __init__(self, dobs, mrange, mspacing, obsurface, components=("gz",), weights="std", mratio=1, mseg=False,
                  mdivisionsection=[], weightfactor=0.5, coordinate="cartesian", wavelet=False, device=0, verbose=True,
-                 shard=None, matrix_free=False, shift_invariant=False, **kwargs):
+                 shard=None, matrix_free=False, shift_invariant=False, translation_invariant=False, **kwargs):
         self._say = print if verbose else (lambda *a, **k: None)
         components = self._block_names(components)
         n = int(np.asarray(obsurface[0]).size)
         dobs, w = self._block_data(components, dobs, weights, n)
         self._only_mtopo(kwargs)
-        self._refuse(coordinate, wavelet, matrix_free, shift_invariant, shard, len(components), n)
+        if translation_invariant:
+            self.translation_invariant = True
+            self._refuse_on_table(coordinate, wavelet, matrix_free, shift_invariant, shard, kwargs)
+        else:
+            if len(components) * n > 16384 and not self._spherical and coordinate == "cartesian":
+                self._rows_hint = self._table_hint(mrange, mspacing, mratio, mseg, mdivisionsection, obsurface, kwargs)
+            self._refuse(coordinate, wavelet, matrix_free, shift_invariant, shard, len(components), n)
         title = "Calculating gravity field ({}) in {} coordinate.".format(", ".join(components), coordinate)
         self._assemble(Engine, title, components, dobs, w, n, mrange, mspacing, obsurface, mratio, mseg,
                        mdivisionsection, weightfactor, shift_invariant, device, kwargs.values())
+        if translation_invariant:
+            self._Aw = self.__dict__.pop("Aw")   # (the sampler's handle; the attribute Aw raises, below)
+
+    translation_invariant = False
+
+    @staticmethod
+    def _table_hint(mrange, mspacing, mratio, mseg, mdivisionsection, obsurface, kwargs):
+        """What the refusal of more than 16384 rows adds: the way to the translation-invariant table, where the geometry
+        has its structure (the library's detection, on the host) -- and nothing where it has not."""
+        import ctypes as C
+        if kwargs:     # (mtopo: a carved mesh)
+            return ""
+        try:
+            from .potential import _mesh
+            b6 = np.ascontiguousarray(_mesh(False, mrange, mspacing, mratio, mseg, mdivisionsection).cell_bounds(),
+                                      dtype=np.float64)
+            x, y, z = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in obsurface[:3])
+            lib = _lib.load()
+        except (OSError, ValueError, TypeError, IndexError):
+            return ""
+        n, m = x.size, b6.shape[0]
+        if y.size != n or z.size != n:
+            return ""
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        dims = np.zeros(5, dtype=np.int32)
+        maps = [np.zeros(k, dtype=np.int32) for k in (3 * m, m, 2 * n, n)]
+        rc = lib.gh_lattice_detect(n, x.ctypes.data_as(dp), y.ctypes.data_as(dp), z.ctypes.data_as(dp), m,
+                                   b6.ctypes.data_as(dp), dims.ctypes.data_as(ip), *[a.ctypes.data_as(ip) for a in maps])
+        return "; translation_invariant=True has no such limit" if rc == 0 else ""
+
+    def _refuse_on_table(self, coordinate, wavelet, matrix_free, shift_invariant, shard, kwargs):
+        """What the store does not do on the translation-invariant table, decided before any device work (the rows are
+        not limited there)."""
+        store = "%s on the translation-invariant table (translation_invariant=True)" % self._store
+        if coordinate == "spherical":
+            raise NotImplementedError("%s holds prism fields: tesseroids (coordinate='spherical') are not supported"
+                                      % store)
+        if coordinate != "cartesian":
+            raise ValueError("Please choose coordinate from(cartesian, spherical)!")
+        for on, why in ((wavelet not in (False, None), "wavelet: the compressor's rows need the stored kernel"),
+                        (matrix_free, "matrix_free: one form at a time (the table already never stores G)"),
+                        (shift_invariant, "shift_invariant: that table is for spherical grids"),
+                        (shard is not None, "shard: one GPU holds the table"),
+                        (bool(kwargs), "mtopo: a carved mesh is not a full regular product of cells")):
+            if on:
+                raise NotImplementedError(store + " does not combine with " + why)
 
     def _set_cells(self, eng, bounds):
-        eng.set_cells_multi(bounds, self.components, self.weights)
+        eng.set_cells_multi(bounds, self.components, self.weights, translation_invariant=self.translation_invariant)
+
+    def translation_invariant_info(self):
+        """The engine's translation_invariant_info(): on, nx, ny, nz, px, qy, table_bytes (all components), max_dev
+        (the largest of the components'), build_ms."""
+        return self._engine.translation_invariant_info()
+
+    def _no_table(self, what):
+        if self.translation_invariant:
+            raise NotImplementedError("%s: %s keeps the translation-invariant table, the kernel is never stored" %
+                                      (what, self._store))
+        super()._no_table(what)
+
+    def __getattr__(self, name):
+        # (reached for an attribute that does not exist: Aw on the translation-invariant table, where no store is behind
+        # the device handle the constructor leaves)
+        if name == "Aw" and self.__dict__.get("translation_invariant"):
+            self._no_table("Aw")
+        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
+
+    def kernelw(self):
+        """(Aw, WmInv, Wm) as the sampler expects; Aw is a device handle (on the table: of the tables)."""
+        return (self._Aw if self.translation_invariant else self.Aw), self.WmInv, self.Wm
 
     @property
     def A(self):

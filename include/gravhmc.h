@@ -10,7 +10,8 @@
  * the gradient tensor gxx ... gzz (`_prism.pyx:36-68, 206-509`, gh_set_cells_prism).  Tesseroids carry
  * the same ten other gravity fields (`_tesseroid_numba.py:161-341`, gh_set_cells_tess).  Several prism
  * gravity fields of one density model can share one store and be inverted together (gh_set_cells_multi; an
- * extension, the reference inverts one field at a time).  Every entry
+ * extension, the reference inverts one field at a time), on a regular grid under gridded data without a limit on the
+ * rows (gh_set_cells_multi_table: one translation-invariant table per field).  Every entry
  * point below names the reference interface it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer of the reference would add.
  *
@@ -348,6 +349,21 @@ int gh_joint_layout(const gh_ctx *ctx, int *workgroups_per_block, int *epilogue_
  * matrix-free, the shift-invariant store, the wavelet compressor, gh_batch_*, gh_shard_init* and gh_upload_G; the
  * resident chain kernel and the folded store are never chosen. */
 int gh_set_cells_multi(gh_ctx *ctx, const double *bounds6, int ncomp, const int *comps, const double *weights);
+/* gh_set_cells_multi and the request for the translation-invariant table (below) in one call: the same checks but the
+ * limit of 16384 stacked rows, which the table does not have.  gh_build_G then looks for the structure on the
+ * N / ncomp points (GH_ERR_UNSUPPORTED with the reason where it is absent) and keeps ncomp tables
+ * T[b][k][u][v], block-major, each entry the unweighted entry of the dense multi-component store bit for bit, each
+ * block with a max_dev of its own (the largest is reported and checked).  The data weights are not in the tables:
+ * from gh_weight on the adjoint reads w_b r and the forward multiplies its finished sums by w_b; the column norms are
+ * (sum_b w_b^2 sum T_b^2)^weightfactor.  One launch per pass: the adjoint runs the blocks in turn into the same
+ * accumulators before the one cell update (order of the sums: block, input row, input), the forward takes the block as
+ * a grid coordinate under one gather of x.  gh_multi_info, gh_set_data and the per-block means of the data term are
+ * those of gh_set_cells_multi.  This call is the only way onto the table: gh_set_cells_multi with
+ * gh_set_translation_invariant, in either order, stays refused, and gh_set_translation_invariant on such a context is
+ * refused too.  gh_compress_wavelet, gh_batch_*, gh_bscg_run, gh_shard_init*, gh_upload_G, gh_set_matrix_free,
+ * gh_set_shift_invariant and a grav_fix return an error naming the store; gh_download_G has no kernel to return.  With
+ * ncomp = 1 and weights[0] = 1 the context computes what a gh_set_cells_prism context on the table computes. */
+int gh_set_cells_multi_table(gh_ctx *ctx, const double *bounds6, int ncomp, const int *comps, const double *weights);
 /* Several gravity fields of ONE density model of TESSEROIDS inverted together (GH_CELL_TESSEROID_MULTI): the spherical
  * form of gh_set_cells_multi -- satellite gradiometry, gzz, gxx, gyy, gxz ... measured together at orbit height.
  * ncomp distinct components comps[b] (GH_COMP_*, gz included) of the same M tesseroids (w,e,s,n,top,bottom) at the same
@@ -951,8 +967,9 @@ int gh_fold_detect_pair(int64_t N, const double *x, const double *y, const doubl
  * K[(p, q), (k, a, b)] = T[k][p - a + nx - 1][q - b + ny - 1], nz (nx + px - 1) (ny + qy - 1) doubles instead of
  * N M (csrc/lattice.hip.h).  gh_set_translation_invariant(ctx, 1) before gh_build_G asks for that table instead of
  * G: a flavour of the matrix-free mode (G is never stored; gh_download_G, the folded store, the resident kernels
- * do not apply), with no limit on N.  It holds GH_CELL_PRISM, GH_CELL_PRISM_COMP and GH_CELL_PRISM_TF; tesseroids,
- * the stores of blocks, the wavelet compression, shards, the batches of chains, gh_bscg_run and gh_upload_G are
+ * do not apply), with no limit on N.  It holds GH_CELL_PRISM, GH_CELL_PRISM_COMP and GH_CELL_PRISM_TF, and
+ * GH_CELL_PRISM_MULTI by way of gh_set_cells_multi_table (one table per row block); tesseroids,
+ * the other stores of blocks, the wavelet compression, shards, the batches of chains, gh_bscg_run and gh_upload_G are
  * refused (GH_ERR_UNSUPPORTED), a combination with gh_set_matrix_free or gh_set_shift_invariant too (GH_ERR_ARG).
  * gh_build_G detects the structure (GH_ERR_UNSUPPORTED with the reason where it is absent), evaluates every table
  * entry with the dense assembly's entry function on the pair with the smallest (p, q) of its offset -- the entry
@@ -960,10 +977,12 @@ int gh_fold_detect_pair(int64_t N, const double *x, const double *y, const doubl
  * largest (p, q): max_dev, as a fraction of the largest entry, refused above 1e-7.  Sums run in an order fixed by
  * indices: results are reproducible bit for bit and agree with the dense store's to ~1e-12. */
 int gh_set_translation_invariant(gh_ctx *ctx, int enable);
-/* on: the table is built; the lattice's extents; table_bytes; max_dev and build_ms of the build. */
+/* on: the table is built; the lattice's extents; table_bytes (all row blocks); max_dev (the largest of the blocks)
+ * and build_ms of the build. */
 int gh_translation_invariant_info(const gh_ctx *ctx, int *on, int *nx, int *ny, int *nz, int *px, int *qy,
                                   int64_t *table_bytes, double *max_dev, double *build_ms);
-/* The table T[nz][nx + px - 1][ny + qy - 1] (row-major) as it lies on the device. */
+/* The table T[nz][nx + px - 1][ny + qy - 1] (row-major) as it lies on the device; a gh_set_cells_multi_table
+ * context: its ncomp tables, block-major. */
 int gh_translation_invariant_table(gh_ctx *ctx, double *out);
 enum {
     GH_LATTICE_ON = 0,
