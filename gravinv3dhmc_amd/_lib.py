@@ -168,6 +168,8 @@ PROTOTYPES = {
                                     C.POINTER(_i64)]),
     "gh_fold_detect_pair": (C.c_int, [_i64, _dp, _dp, _dp, _i64, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(C.c_int)]),
+    "gh_fold_pair_rows": (C.c_int, [_i64, _dp, _dp, _dp, _i64, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(C.c_int)]),
     "gh_profile_read": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(_i64),
                                   C.POINTER(_i64)]),
     "gh_set_translation_invariant": (C.c_int, [_ctx, C.c_int]),

@@ -388,11 +388,47 @@ __global__ void __launch_bounds__(1024) fold_sweep_kernel(SweepArgs a, FoldArgs 
 struct FoldPairArgs {
     const int *wtab;         // n_work x 16: [0, 4) cells s_h j_o of the leading orbit, [4, 8) tau s_h j_o (~ of the
                              // entry four to the left where the orbit has no partner), [8] the orbit, then padding
-    const int *obs_img_tau;  // nF x 4: tau obs_img
+    const int *ptab;         // fold_pair_cols(ROWS) x 512 x 4: the observation behind every value of r in LDS and behind
+                             // every forward sum of thread t (-1: none), in the row order of fold_pair_rows_kernel
     int64_t n_work, work_per_team;
 };
 constexpr int FOLD_PAIR_W = 16;
 constexpr int FOLD_PSLOT = 64;  // doubles: 8 waves x 8 dots
+
+// The rows of a block folded over tau as well.  With tau f = s_(c_f) f' (row_tau[f] = 4 f' + c_f) and
+// tau s_g = s_swap(g) tau, the partner terms of row f read r at, and add into d at, the four observations of row f'
+// (and those of f' the four of f): a thread that holds both rows needs r at eight observations and eight forward
+// sums for the two.  Thread t of 512 owns the rows k 512 + t of a block, k < ROWS, in slots:
+//     pair slot s < NP = (ROWS - 1) / 2     rows 2 s (row f as stored) and 2 s + 1 (row f' as the representative
+//                                           tau f of its orbit: its sub-columns k ^ c_f)
+//     lone slot NP <= s < NS = ROWS - NP    row NP + s alone: r at s_g tau f from LDS and its own four tau sums
+// Column 2 s of ptab holds the observations s_g f of the slot's first row, column 2 s + 1 the observations s_g tau f
+// (those of the second row where there is one).  With A the first row, B the second, As = (A0, A2, A1, A3), ra / rb
+// the two columns of r, x the orbit's cells, y = x o tau, ys = (y0, y2, y1, y3) and t(S, w)[q] = sum_k S[k] w[k ^ q]:
+//     dot[h]     += t(A, ra)[h] + t(B, rb)[h]            dotT[swap h] += t(As, rb)[h] + t(Bs, ra)[h]
+//     d[s_g f]   += t(A, x)[g] + t(Bs, ys)[g]            d[s_g tau f] += t(B, x)[g] + t(As, ys)[g]
+// 16 FMA per double read as before; a lone slot is a pair slot without B.
+constexpr int fold_pair_slots(int rows) { return (rows - 1) / 2; }
+constexpr int fold_pair_cols(int rows) { return 2 * (rows - fold_pair_slots(rows)); }
+
+// The store in the paired sweep's row order, block by block in place (one workgroup per block, the block in LDS):
+// row n becomes row code[n] >> 2 of fold_build_kernel's order with its sub-columns k ^ (code[n] & 3), or zeros
+// (code[n] < 0).  Within a group of w = min(512, ldF - 512 k) rows k 512 + t the first halves (sub-columns 0, 1) of all
+// rows come first, then the second halves: the 64 lanes of a wave read 1 KiB in one piece with either of a row's two
+// 16-byte loads (a row's 32 bytes side by side made every load touch twice the lines it used).
+__global__ void __launch_bounds__(512) fold_pair_rows_kernel(FoldArgs f, const int *code, double *S)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int n = 4 * f.ldF;
+    double *blk = S + (int64_t)blockIdx.x * n;
+    for (int e = threadIdx.x; e < n; e += blockDim.x) smem[e] = blk[e];
+    __syncthreads();
+    for (int e = threadIdx.x; e < n; e += blockDim.x) {
+        const int cd = code[e >> 2];
+        const int k = e >> 11, t = (e >> 2) & 511, w = min(512, f.ldF - 512 * k);
+        blk[2048 * k + 2 * (((e >> 1) & 1) * w + t) + (e & 1)] = cd >= 0 ? smem[(cd & ~3) | ((e ^ cd) & 3)] : 0.0;
+    }
+}
 
 // Both blocks of a pair (or the two halves of a block that is its own partner) become the mean of what
 // fold_build_kernel left in them: S[o][f][k] and S[o'][f'][swap(k) ^ c_o ^ c_f] (row_tau[f] = 4 f' + c_f with
@@ -450,27 +486,27 @@ __global__ void __launch_bounds__(256) fold_pair_mean_kernel(FoldArgs f, const i
 
 template <int ROWS>
 struct FoldPairCol {
-    d2 v[ROWS][2];  // S[o][f][0..1], S[o][f][2..3] of the thread's rows f = k 512 + t
+    d2 v[ROWS][2];  // sub-columns 0..1 and 2..3 of the thread's rows k 512 + t (the order of fold_pair_rows_kernel)
     int j;          // lane 32 s + 8 h + q: cell h of the orbit (s = 0) or of its partner (s = 1)
     int jn, on;     // the same of the work item this buffer takes next, and that item's orbit
     bool live;      // the cell exists (partner lanes of an orbit without a partner: false)
     double cv;      // per-cell inputs as in FoldCol
 };
 
-// The paired form of fold_sweep_kernel: 8 waves per workgroup, a whole folded row (4 k) of ROWS rows per thread,
-// one block in flight ahead with its cells' inputs, no scalar load in the loop (the work item's orbit comes with
-// the cell indices, two blocks ahead, through a vector load).  LDS: r at the four images of each fundamental
-// observation and r o tau in the same order (4 nF doubles each, no padding: at C2 the two and the slots fill 157 of
-// the 160 KiB), 2 x FOLD_PSLOT ping-pong slots of the eight dots.  The eight cells' updates run side by side in
-// lanes 8 h (the orbit) and 32 + 8 h (its partner) with the arithmetic of fold_sweep_kernel per cell.
+// The paired form of fold_sweep_kernel: 8 waves per workgroup, a whole folded row (4 k) of ROWS rows per thread in
+// the slots above, two blocks in flight ahead with their cells' inputs, no scalar load in the loop (the work item's
+// orbit comes with the cell indices, three blocks ahead, through a vector load).  LDS: r behind every entry of ptab
+// (fold_pair_cols(ROWS) x 512 x 4 doubles: 96 KiB at five rows), 2 x FOLD_PSLOT ping-pong slots of the eight dots.
+// The eight cells' updates run side by side in lanes 8 h (the orbit) and 32 + 8 h (its partner) with the arithmetic
+// of fold_sweep_kernel per cell.
 template <int ROWS>
 __global__ void __launch_bounds__(512) fold_pair_sweep_kernel(SweepArgs a, FoldArgs f, FoldPairArgs p)
 {
     constexpr int TT = 512, NW = 8;
+    constexpr int NP = fold_pair_slots(ROWS), NS = ROWS - NP, NC = fold_pair_cols(ROWS);
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    double *rF = smem;
-    double *rT = smem + 4 * f.nF;
-    double *scratch = smem + 8 * f.nF;
+    double *rL = smem;
+    double *scratch = smem + NC * TT * 4;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -478,9 +514,9 @@ __global__ void __launch_bounds__(512) fold_pair_sweep_kernel(SweepArgs a, FoldA
     const int mode = a.mode;
 
     if (mode & SW_ADJ) {
-        for (int e = tid; e < 4 * f.nF; e += TT) {
-            rF[e] = a.r[f.obs_img[e]];
-            rT[e] = a.r[p.obs_img_tau[e]];
+        for (int e = tid; e < NC * TT * 4; e += TT) {
+            const int i = p.ptab[e];
+            rL[e] = i >= 0 ? a.r[i] : 0.0;
         }
     }
     __syncthreads();
@@ -490,18 +526,21 @@ __global__ void __launch_bounds__(512) fold_pair_sweep_kernel(SweepArgs a, FoldA
     if (wend > p.n_work) wend = p.n_work;
     const int cnt = wb < wend ? (int)(wend - wb) : 0;
 
-    d2 acc[ROWS][2], accT[ROWS][2];  // [k][0] = observations s_0 f, s_1 f, [k][1] = s_2 f, s_3 f (accT: their tau images)
+    // [s][c][0] = the forward sums at the observations s_0, s_1 of column 2 s + c of ptab, [s][c][1] = at s_2, s_3
+    d2 acc[NS][2][2];
 #pragma unroll
-    for (int k = 0; k < ROWS; ++k) acc[k][0] = acc[k][1] = accT[k][0] = accT[k][1] = d2{0.0, 0.0};
+    for (int s = 0; s < NS; ++s) acc[s][0][0] = acc[s][0][1] = acc[s][1][0] = acc[s][1][1] = d2{0.0, 0.0};
     double pp = 0.0;
 
-    // (only the last of a thread's rows can lie past nF: (ROWS - 1) 512 <= ldF - 16 < nF.  It re-reads the last row
-    // of the block and of r and takes no part in the sums)
+    // (only the last of a thread's rows, the first row of the last slot, can lie past the block: (ROWS - 1) 512 < ldF.
+    // It re-reads the block's last row and takes no part in the adjoint's sums; its forward sums have no observation
+    // in ptab)
     const int row_last = (ROWS - 1) * TT + tid;
-    const bool last_in = row_last < f.nF;
-    unsigned voff = (unsigned)tid * 32u;
-    unsigned coff_last = (unsigned)(row_last < f.ldF ? row_last : f.ldF - 1) * 32u;
-    const int lrow_last = last_in ? row_last : f.nF - 1;
+    const bool last_in = row_last < f.ldF;
+    // (a group of rows holds the first halves of its rows, then the second halves: fold_pair_rows_kernel)
+    const int w_last = f.ldF - (ROWS - 1) * TT;
+    unsigned voff = (unsigned)tid * 16u;
+    unsigned coff_last = (unsigned)(last_in ? tid : w_last - 1) * 16u;
 
     const int hl = (lane >> 3) & 3, ql = lane & 7, sl = lane >> 5;
     const double *in_base = ql == FOLD_IN_P      ? a.p_in
@@ -514,27 +553,33 @@ __global__ void __launch_bounds__(512) fold_pair_sweep_kernel(SweepArgs a, FoldA
     const int lastc = cnt - 1;
     auto item = [&](int i) -> int64_t { return wb + (i < lastc ? i : lastc); };
     auto load_col = [&](FoldPairCol<ROWS> &c, int64_t w_after) {
-        const int jn = p.wtab[FOLD_PAIR_W * w_after + (lane >> 3)];
-        const int on = p.wtab[FOLD_PAIR_W * w_after + 8];
+        // (this item's cell and orbit, requested three blocks ago, leave their registers before the next item's are
+        // requested into them: otherwise the compiler keeps two sets and copies one to the other at the loop's back
+        // edge, behind a wait for the requests just made)
+        asm volatile("" : "+v"(c.jn), "+v"(c.on)::"memory");
         const int64_t o = __builtin_amdgcn_readfirstlane(c.on);
+        c.live = c.jn >= 0;
+        c.j = c.live ? c.jn : ~c.jn;
+        asm volatile("" : "+v"(c.j));
+        c.jn = p.wtab[FOLD_PAIR_W * w_after + (lane >> 3)];
+        c.on = p.wtab[FOLD_PAIR_W * w_after + 8];
         const unsigned long long col = (unsigned long long)(f.S + o * (int64_t)(4 * f.ldF));
 #pragma unroll
         for (int k = 0; k < ROWS - 1; ++k) {
-            unsigned long long colk = col + (unsigned long long)k * TT * 32u;
+            unsigned long long colk = col + (unsigned long long)k * TT * 32u, colh = colk + TT * 16u;
             asm volatile("" : "+s"(colk));
+            asm volatile("" : "+s"(colh));
             asm volatile("" : "+v"(voff));
             c.v[k][0] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(colk + voff));
-            c.v[k][1] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(colk + voff) + 1);
+            c.v[k][1] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(colh + voff));
         }
+        unsigned long long coll = col + (unsigned long long)(ROWS - 1) * TT * 32u, collh = coll + (unsigned)w_last * 16u;
+        asm volatile("" : "+s"(coll));
+        asm volatile("" : "+s"(collh));
         asm volatile("" : "+v"(coff_last));
-        c.v[ROWS - 1][0] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(col + coff_last));
-        c.v[ROWS - 1][1] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(col + coff_last) + 1);
-        asm volatile("" : "+v"(c.jn)::"memory");
-        c.live = c.jn >= 0;
-        c.j = c.live ? c.jn : ~c.jn;
+        c.v[ROWS - 1][0] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(coll + coff_last));
+        c.v[ROWS - 1][1] = __builtin_nontemporal_load(reinterpret_cast<gconst_d2ptr>(collh + coff_last));
         c.cv = in_base[c.j];
-        c.jn = jn;
-        c.on = on;
     };
 
     // t[q] += sum_k S[f][k] w[k ^ q] of one row: (wa, wb) = w[0..1], w[2..3]
@@ -561,21 +606,29 @@ __global__ void __launch_bounds__(512) fold_pair_sweep_kernel(SweepArgs a, FoldA
         double xl = cur.cv;
         const double pl = dpp_from_up<FOLD_IN_P>(cur.cv);
         if (mode & SW_ADJ) {
-            const d2 *r2 = reinterpret_cast<const d2 *>(rF), *t2 = reinterpret_cast<const d2 *>(rT);
-            d2 ua = d2{0.0, 0.0}, ub = ua, uta = ua, utb = ua;
+            const d2 *r2 = reinterpret_cast<const d2 *>(rL) + 2 * tid;
+            d2 ua = d2{0.0, 0.0}, ub = ua, wa = ua, wb = ua;  // (ua, ub): dot[0..3], (wa, wb): dotT[swap 0..3]
 #pragma unroll
-            for (int k = 0; k < ROWS; ++k) {
+            for (int s = 0; s < NS; ++s) {
+                const int k = s < NP ? 2 * s : NP + s;
                 if (k < ROWS - 1 || last_in) {
-                    const int row = k < ROWS - 1 ? k * TT + tid : lrow_last;
-                    row_fma(cur.v[k][0], cur.v[k][1], r2[2 * row], r2[2 * row + 1], ua, ub);
-                    row_fma(cur.v[k][0], cur.v[k][1], t2[2 * row], t2[2 * row + 1], uta, utb);
+                    const d2 ra0 = r2[4 * s * TT], ra1 = r2[4 * s * TT + 1];
+                    const d2 rb0 = r2[(4 * s + 2) * TT], rb1 = r2[(4 * s + 2) * TT + 1];
+                    const d2 a0 = cur.v[k][0], a1 = cur.v[k][1];
+                    row_fma(a0, a1, ra0, ra1, ua, ub);
+                    row_fma(d2{a0.x, a1.x}, d2{a0.y, a1.y}, rb0, rb1, wa, wb);
+                    if (s < NP) {
+                        const d2 b0 = cur.v[k + 1][0], b1 = cur.v[k + 1][1];
+                        row_fma(b0, b1, rb0, rb1, ua, ub);
+                        row_fma(d2{b0.x, b1.x}, d2{b0.y, b1.y}, ra0, ra1, wa, wb);
+                    }
                 }
             }
             // the eight dots reduced together: lane pairs leave the orbit's four in even lanes and the partner's in odd
             // ones, pairs of pairs dots 2 b, 2 b + 1 of them in the lanes with (l >> 1) & 1 = b, row_shr 4, 8 sum the
             // quads of a row of 16 into its lanes 12 .. 15, two exchanges the four rows.  Fixed order throughout.
             const bool odd = (lane & 1) != 0, hi2 = (lane & 2) != 0;
-            const double u[4] = {ua.x, ua.y, ub.x, ub.y}, ut[4] = {uta.x, uta.y, utb.x, utb.y};
+            const double u[4] = {ua.x, ua.y, ub.x, ub.y}, ut[4] = {wa.x, wb.x, wa.y, wb.y};
             double b[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) b[q] = (odd ? ut[q] : u[q]) + dpp_mov<0xb1>(odd ? u[q] : ut[q]);
@@ -647,10 +700,18 @@ __global__ void __launch_bounds__(512) fold_pair_sweep_kernel(SweepArgs a, FoldA
             const double xz = cur.live ? xl : 0.0;
             const d2 xa = d2{readlane_d(xz, 0), readlane_d(xz, 8)}, xb = d2{readlane_d(xz, 16), readlane_d(xz, 24)};
             const d2 ya = d2{readlane_d(xz, 32), readlane_d(xz, 40)}, yb = d2{readlane_d(xz, 48), readlane_d(xz, 56)};
+            const d2 ysa = d2{ya.x, yb.x}, ysb = d2{ya.y, yb.y};
 #pragma unroll
-            for (int k = 0; k < ROWS; ++k) {
-                row_fma(cur.v[k][0], cur.v[k][1], xa, xb, acc[k][0], acc[k][1]);
-                row_fma(cur.v[k][0], cur.v[k][1], ya, yb, accT[k][0], accT[k][1]);
+            for (int s = 0; s < NS; ++s) {
+                const int k = s < NP ? 2 * s : NP + s;
+                const d2 a0 = cur.v[k][0], a1 = cur.v[k][1];
+                row_fma(a0, a1, xa, xb, acc[s][0][0], acc[s][0][1]);
+                row_fma(d2{a0.x, a1.x}, d2{a0.y, a1.y}, ysa, ysb, acc[s][1][0], acc[s][1][1]);
+                if (s < NP) {
+                    const d2 b0 = cur.v[k + 1][0], b1 = cur.v[k + 1][1];
+                    row_fma(b0, b1, xa, xb, acc[s][1][0], acc[s][1][1]);
+                    row_fma(d2{b0.x, b1.x}, d2{b0.y, b1.y}, ysa, ysb, acc[s][0][0], acc[s][0][1]);
+                }
             }
         }
 #pragma unroll
@@ -661,21 +722,30 @@ __global__ void __launch_bounds__(512) fold_pair_sweep_kernel(SweepArgs a, FoldA
     };
 
     if (cnt > 0) {
-        FoldPairCol<ROWS> b0, b1;
+        // (a buffer takes every third item and requests the cells and the orbit of its own next one: past the end
+        // the requests repeat the last item and nothing uses them)
+        FoldPairCol<ROWS> b0, b1, b2;
         b0.jn = p.wtab[FOLD_PAIR_W * item(0) + (lane >> 3)];
         b0.on = p.wtab[FOLD_PAIR_W * item(0) + 8];
         b1.jn = p.wtab[FOLD_PAIR_W * item(1) + (lane >> 3)];
         b1.on = p.wtab[FOLD_PAIR_W * item(1) + 8];
-        load_col(b0, item(2));
+        b2.jn = p.wtab[FOLD_PAIR_W * item(2) + (lane >> 3)];
+        b2.on = p.wtab[FOLD_PAIR_W * item(2) + 8];
+        load_col(b0, item(3));
+        load_col(b1, item(4));
+        // (no way out of the loop between its three blocks: the compiler routes such an exit through a block with an
+        // edge back to the loop's head, and then waits there as if a request made one block ago had been made three ago)
         int i = 0;
-        for (;;) {
-            load_col(b1, item(i + 3));
+        for (; i + 2 < cnt; i += 3) {
+            load_col(b2, item(i + 5));
             process(b0, i);
-            if (++i >= cnt) break;
-            load_col(b0, item(i + 3));
-            process(b1, i);
-            if (++i >= cnt) break;
+            load_col(b0, item(i + 6));
+            process(b1, i + 1);
+            load_col(b1, item(i + 7));
+            process(b2, i + 2);
         }
+        if (i < cnt) process(b0, i);
+        if (i + 1 < cnt) process(b1, i + 1);
     }
 
     if ((mode & SW_PFIN) && tid == 0) {
@@ -684,40 +754,43 @@ __global__ void __launch_bounds__(512) fold_pair_sweep_kernel(SweepArgs a, FoldA
     }
 
     if (mode & SW_FWD) {
-        // the orbit's sums go to their observations, then, behind a barrier, the partner's are added at the tau images
-        // (another thread's observations of the same slab row); the row's sum in the same order
+        // every stored row is the first row of a slot or the second of a pair slot: their sums go to their observations
+        // (each observation once), then, behind a barrier, the tau sums of the lone slots are added at theirs (another
+        // thread's observations of the same slab row); the row's sum in the same order
         double *out = a.slab + (int64_t)blockIdx.x * a.ld;
+        const int4 *pt = reinterpret_cast<const int4 *>(p.ptab) + tid;
         double ds = 0.0;
 #pragma unroll
-        for (int k = 0; k < ROWS; ++k) {
-            const int i = k * TT + tid;
-            if (i < f.nF) {
-                const int4 oi = reinterpret_cast<const int4 *>(f.obs_img)[i];
-                out[oi.x] = acc[k][0].x;
-                out[oi.y] = acc[k][0].y;
-                out[oi.z] = acc[k][1].x;
-                out[oi.w] = acc[k][1].y;
-                ds += acc[k][0].x;
-                ds += acc[k][0].y;
-                ds += acc[k][1].x;
-                ds += acc[k][1].y;
+        for (int c = 0; c < NC; ++c) {
+            if ((c & 1) && (c >> 1) >= NP) continue;
+            const int4 oi = pt[c * TT];
+            if (oi.x >= 0) {
+                const d2 s01 = acc[c >> 1][c & 1][0], s23 = acc[c >> 1][c & 1][1];
+                out[oi.x] = s01.x;
+                out[oi.y] = s01.y;
+                out[oi.z] = s23.x;
+                out[oi.w] = s23.y;
+                ds += s01.x;
+                ds += s01.y;
+                ds += s23.x;
+                ds += s23.y;
             }
         }
         for (int64_t e = f.N + tid; e < a.ld; e += TT) out[e] = 0.0;
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < ROWS; ++k) {
-            const int i = k * TT + tid;
-            if (i < f.nF) {
-                const int4 oi = reinterpret_cast<const int4 *>(p.obs_img_tau)[i];
-                out[oi.x] += accT[k][0].x;
-                out[oi.y] += accT[k][0].y;
-                out[oi.z] += accT[k][1].x;
-                out[oi.w] += accT[k][1].y;
-                ds += accT[k][0].x;
-                ds += accT[k][0].y;
-                ds += accT[k][1].x;
-                ds += accT[k][1].y;
+        for (int s = NP; s < NS; ++s) {
+            const int4 oi = pt[(2 * s + 1) * TT];
+            if (oi.x >= 0) {
+                const d2 s01 = acc[s][1][0], s23 = acc[s][1][1];
+                out[oi.x] += s01.x;
+                out[oi.y] += s01.y;
+                out[oi.z] += s23.x;
+                out[oi.w] += s23.y;
+                ds += s01.x;
+                ds += s01.y;
+                ds += s23.x;
+                ds += s23.y;
             }
         }
         if (a.dsum) {

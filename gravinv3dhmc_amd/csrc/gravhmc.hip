@@ -2558,6 +2558,34 @@ int gh_fold_detect_pair(int64_t N, const double *x, const double *y, const doubl
     return rc;
 }
 
+int gh_fold_pair_rows(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
+                      int *rows, int *pair_slots, int *code, int *ptab, int64_t *counts, int *pair_reason)
+{
+    if (N < 0 || M < 0 || !x || !y || !z || !bounds6 || !rows || !pair_slots || !code || !ptab || !counts || !pair_reason)
+        return GH_ERR_ARG;
+    std::vector<int> oi, co, ot, ct, rt, qt, wk;
+    *rows = *pair_slots = 0;
+    *pair_reason = GH_FOLD_PAIR_NO_FOLD;
+    const int rc = fold_detect_host(N, x, y, z, M, bounds6, oi, co);
+    if (rc != GH_FOLD_ON) return rc;
+    *pair_reason = fold_pair_detect_host(N, x, y, z, M, bounds6, oi, co, ot, ct, rt, qt, wk);
+    if (*pair_reason != GH_FOLD_PAIR_ON) return rc;
+    const int nF = (int)(N / 4), ldF = (nF + 15) / 16 * 16;
+    fold_detail::PairRows pr;
+    if (ldF > 512 * FOLD_PAIR_MAX_ROWS || !fold_detail::pair_rows_plan(nF, ldF, oi, rt, pr)) {
+        *pair_reason = GH_FOLD_PAIR_ROWS;
+        return rc;
+    }
+    *rows = pr.rows;
+    *pair_slots = pr.pair_slots;
+    std::copy(pr.code.begin(), pr.code.end(), code);
+    std::copy(pr.ptab.begin(), pr.ptab.end(), ptab);
+    counts[0] = pr.pairs_in_slots;
+    counts[1] = pr.pairs_split;
+    counts[2] = pr.self_rows;
+    return rc;
+}
+
 int gh_fold_detect(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
                    int *obs_img, int *cell_orbit)
 {

@@ -393,7 +393,9 @@ struct gh_ctx {
         int pair_reason = GH_FOLD_PAIR_UNDECIDED;
         int64_t n_work = 0, n_pairs = 0, work_per_team = 0;
         int pair_rows = 0;
-        int *wtab_d = nullptr, *obs_img_tau_d = nullptr, *row_tau_d = nullptr, *orb_tau_d = nullptr;
+        bool pair_rows_ok = false;  // the folded rows fit the paired sweep's slots (fold_detail::pair_rows_plan)
+        int *wtab_d = nullptr, *row_tau_d = nullptr, *orb_tau_d = nullptr;
+        int *ptab_d = nullptr, *row_code_d = nullptr;  // the paired sweep's row order: its table and the store's pass
     } fd;
 
     // page-locked host memory handed to the caller (gh_pinned_alloc): momentum rows drawn into it go to the device

@@ -301,6 +301,80 @@ static int fold_pair_detect_host(int64_t N, const double *x, const double *y, co
     return GH_FOLD_PAIR_ON;
 }
 
+namespace fold_detail {
+
+// The paired sweep's row order (fold.hip.h: thread t of 512 owns the rows k 512 + t, k < rows = ceil(ldF / 512), in
+// pair_slots = (rows - 1) / 2 pair slots and rows - 2 pair_slots lone slots).  rho: f -> row_tau[f] >> 2 is an
+// involution on the folded rows.  Pairs {f < rho f} by f fill the pair slots, slot by slot, thread by thread; the
+// pairs beyond them are split into two lone rows in neighbouring lanes, then the rows with rho f = f follow, through
+// the lone rows in the store's order.
+//     code[n], n < ldF     4 f + c: row n of the new order is row f of the mirror table with its sub-columns k ^ c
+//                          (the second row of a pair slot: rho f as the representative tau f of its orbit), -1: zeros
+//     ptab                 fold_pair_cols(rows) x 512 x 4: column 2 s the observations s_g f of the first row of slot
+//                          s, column 2 s + 1 the observations s_g tau f; -1 where the thread has no row there
+// false: the rows do not fit this plan (rows with rho f = f beyond the lone rows left: no grid has them).
+struct PairRows {
+    int rows = 0, pair_slots = 0, cols = 0;
+    int64_t pairs_in_slots = 0, pairs_split = 0, self_rows = 0;
+    std::vector<int> code, ptab;
+};
+
+inline bool pair_rows_plan(int nF, int ldF, const std::vector<int> &obs_img, const std::vector<int> &row_tau, PairRows &pr)
+{
+    constexpr int TT = 512;
+    pr.rows = (ldF + TT - 1) / TT;
+    pr.pair_slots = ghk::fold_pair_slots(pr.rows);
+    pr.cols = ghk::fold_pair_cols(pr.rows);
+    pr.pairs_in_slots = pr.pairs_split = pr.self_rows = 0;
+    pr.code.assign((size_t)ldF, -1);
+    pr.ptab.assign((size_t)pr.cols * TT * 4, -1);
+    // slot s of thread t takes row f at store row k 512 + t (its partner row behind it when both)
+    auto place = [&](int s, int t, int k, int f, bool both) {
+        const int rt = row_tau[(size_t)f], f2 = rt >> 2, cf = rt & 3;
+        int *pa = pr.ptab.data() + ((size_t)(2 * s) * TT + (size_t)t) * 4, *pb = pa + (size_t)TT * 4;
+        for (int g = 0; g < 4; ++g) {
+            pa[g] = obs_img[4 * (size_t)f + g];
+            pb[g] = obs_img[4 * (size_t)f2 + (g ^ cf)];
+        }
+        pr.code[(size_t)k * TT + t] = 4 * f;
+        if (both) pr.code[(size_t)(k + 1) * TT + t] = 4 * f2 + cf;
+    };
+    const int64_t cap = (int64_t)pr.pair_slots * TT;
+    // lone rows in the store's order: n = (2 pair_slots + l) 512 + t < ldF
+    int64_t lone = 0;
+    auto place_lone = [&](int f) -> bool {
+        const int64_t n = 2 * cap + lone;
+        if (n >= ldF) return false;
+        const int l = (int)(lone / TT), t = (int)(lone % TT);
+        place(pr.pair_slots + l, t, 2 * pr.pair_slots + l, f, false);
+        ++lone;
+        return true;
+    };
+    int64_t np = 0;
+    for (int f = 0; f < nF; ++f) {
+        const int f2 = row_tau[(size_t)f] >> 2;
+        if (f2 <= f) continue;
+        if (np < cap) {
+            place((int)(np / TT), (int)(np % TT), 2 * (int)(np / TT), f, true);
+            ++pr.pairs_in_slots;
+        } else {
+            if (!place_lone(f) || !place_lone(f2)) return false;
+            ++pr.pairs_split;
+        }
+        ++np;
+    }
+    for (int f = 0; f < nF; ++f) {
+        if ((row_tau[(size_t)f] >> 2) != f) continue;
+        if (!place_lone(f)) return false;
+        ++pr.self_rows;
+    }
+    return true;
+}
+
+}  // namespace fold_detail
+
+constexpr int FOLD_PAIR_MAX_ROWS = 5;  // rows per thread of fold_pair_sweep_kernel: registers without spills
+
 // the diagonal reflection of a geometry whose mirrors were found: the tables of the paired sweep on the device
 static int fold_pair_tables(gh_ctx *c, const double *ox, const double *oy, const double *oz, const double *b6)
 {
@@ -314,7 +388,7 @@ static int fold_pair_tables(gh_ctx *c, const double *ox, const double *oy, const
     if (!f.pair_detected) return GH_OK;
     f.pair_reason = GH_FOLD_PAIR_UNDECIDED;
     f.n_work = (int64_t)(work.size() / 2);
-    std::vector<int> wtab((size_t)f.n_work * ghk::FOLD_PAIR_W, 0), oit((size_t)c->N);
+    std::vector<int> wtab((size_t)f.n_work * ghk::FOLD_PAIR_W, 0);
     for (int64_t w = 0; w < f.n_work; ++w) {
         const int o = work[2 * (size_t)w], o2 = work[2 * (size_t)w + 1];
         int *t = wtab.data() + w * ghk::FOLD_PAIR_W;
@@ -325,7 +399,13 @@ static int fold_pair_tables(gh_ctx *c, const double *ox, const double *oy, const
         t[8] = o;
         f.n_pairs += o2 >= 0;
     }
-    for (size_t e = 0; e < oit.size(); ++e) oit[e] = obs_tau[(size_t)f.obs_img[e]];
+    // the sweep's row order (more than five rows per thread: the sweep is refused anyway)
+    fold_detail::PairRows pr;
+    f.pair_rows_ok = f.ldF <= 512 * FOLD_PAIR_MAX_ROWS && fold_detail::pair_rows_plan(f.nF, f.ldF, f.obs_img, row_tau, pr);
+    if (!f.pair_rows_ok) {
+        pr.code.assign((size_t)f.ldF, -1);
+        pr.ptab.assign(4, -1);
+    }
     // (sized for any geometry of the context's N and M: a later build reuses them)
     auto up = [&](int **d, const std::vector<int> &h, size_t cap) -> int {
         TRY(dalloc(c, d, cap, false));
@@ -333,7 +413,8 @@ static int fold_pair_tables(gh_ctx *c, const double *ox, const double *oy, const
         return GH_OK;
     };
     TRY(up(&f.wtab_d, wtab, (size_t)f.n_orb * ghk::FOLD_PAIR_W));
-    TRY(up(&f.obs_img_tau_d, oit, (size_t)c->N));
+    TRY(up(&f.ptab_d, pr.ptab, (size_t)ghk::fold_pair_cols(FOLD_PAIR_MAX_ROWS) * 512 * 4));
+    TRY(up(&f.row_code_d, pr.code, (size_t)f.ldF));
     TRY(up(&f.row_tau_d, row_tau, (size_t)f.nF));
     TRY(up(&f.orb_tau_d, orb_tau, (size_t)f.n_orb));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -406,11 +487,19 @@ static fold_pair_fn fold_pair_kernel_for(int rows)
     return nullptr;
 }
 
-constexpr size_t FOLD_PAIR_MAX_LDS = 160u << 10;  // the CU's LDS: r, r o tau and the slots of one workgroup
+constexpr size_t FOLD_PAIR_MAX_LDS = 160u << 10;  // the CU's LDS
 
-static size_t fold_pair_lds(const gh_ctx *c)
+// what decides whether the paired sweep takes a geometry: two unpadded copies of r and the slots (the sweep itself
+// needs less since it folds the rows over tau too; the limit stays where it was)
+static size_t fold_pair_lds_limit(const gh_ctx *c)
 {
     return ((size_t)8 * c->fd.nF + 2 * FOLD_PSLOT) * sizeof(double);
+}
+
+// r behind every entry of the row table, and the slots
+static size_t fold_pair_lds(const gh_ctx *c)
+{
+    return ((size_t)ghk::fold_pair_cols(c->fd.pair_rows) * 512 * 4 + 2 * FOLD_PSLOT) * sizeof(double);
 }
 
 static int64_t fold_store_bytes(const gh_ctx *c)
@@ -439,7 +528,7 @@ static FoldPairArgs fold_pair_args(const gh_ctx *c)
     const gh_ctx::Fold &f = c->fd;
     FoldPairArgs p{};
     p.wtab = f.wtab_d;
-    p.obs_img_tau = f.obs_img_tau_d;
+    p.ptab = f.ptab_d;
     p.n_work = f.n_work;
     p.work_per_team = f.work_per_team;
     return p;
@@ -480,6 +569,12 @@ static int fold_build(gh_ctx *c)
         double d8 = 0.0;
         memcpy(&d8, &bits, sizeof bits);
         f.max_dev += d8;
+        // the blocks in the paired sweep's row order
+        const size_t blk = (size_t)4 * f.ldF * sizeof(double);
+        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(fold_pair_rows_kernel), blk));
+        fold_pair_rows_kernel<<<dim3((unsigned)f.n_orb), dim3(512), blk, c->stream>>>(fold_args(c), f.row_code_d, f.S);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     f.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return GH_OK;
@@ -533,7 +628,7 @@ static int fold_use(gh_ctx *c, bool *use)
         // (the reason of the detection stays)
     } else if (env_int("GRAVHMC_FOLD_PAIR", 1) == 0) {
         f.pair_reason = GH_FOLD_PAIR_SWITCHED_OFF;
-    } else if (fold_pair_lds(c) > FOLD_PAIR_MAX_LDS || f.pair_rows > FOLD_MAX_EPT2) {
+    } else if (fold_pair_lds_limit(c) > FOLD_PAIR_MAX_LDS || f.pair_rows > FOLD_PAIR_MAX_ROWS || !f.pair_rows_ok) {
         f.pair_reason = GH_FOLD_PAIR_ROWS;
     } else if (allow_dynamic_lds(reinterpret_cast<const void *>(fold_pair_kernel_for(f.pair_rows)), fold_pair_lds(c)) !=
                hipSuccess) {

@@ -944,7 +944,8 @@ enum {
     GH_FOLD_PAIR_NO_FOLD = 3,       /* the mirrors were not found (gh_fold_info tells why) */
     GH_FOLD_PAIR_OBS = 4,           /* not square: an observation without its image under tau */
     GH_FOLD_PAIR_CELLS = 5,         /* not square: a cell without its image under tau */
-    GH_FOLD_PAIR_ROWS = 6           /* r and r o tau of the folded rows do not fit the LDS of a CU (N > 10176) */
+    GH_FOLD_PAIR_ROWS = 6           /* more folded rows than the paired sweep takes (N > 10176), or rows that do not
+                                       fit its slots (gh_fold_pair_rows) */
 };
 /* on: the sweeps read one block per pair; pairs and single_orbits: the work items of a sweep; bytes_per_sweep: what
  * a sweep reads of the folded store (work items x block bytes; the whole store where the pairing is off, 0 where
@@ -958,6 +959,22 @@ int gh_fold_pair_info(const gh_ctx *ctx, int *on, int *reason, int64_t *pairs, i
  * its smaller orbit index and listed once, rows ordered by leading orbit. */
 int gh_fold_detect_pair(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
                         int *obs_tau, int *cell_tau, int *work, int64_t *n_work, int *pair_reason);
+/* The row order of the paired sweep, without a device: the folded rows (gh_fold_detect's obs_img, nF = N / 4 of them,
+ * ldF = nF rounded up to 16) folded over tau as well.  tau takes the orbit of row f to that of a row rho f; thread t
+ * of 512 owns the rows k 512 + t of a block, k < *rows = ceil(ldF / 512): *pair_slots = (*rows - 1) / 2 pair slots
+ * (rows 2 s and 2 s + 1: f < rho f and rho f, pairs by f, slot by slot) and the other rows alone (first the pairs the
+ * slots do not hold, their two rows in neighbouring lanes, then the rows with rho f = f).  code (ldF ints): row n of
+ * that order is row code[n] >> 2 of obs_img with its four sub-columns k ^ (code[n] & 3), -1: a row of zeros.  ptab
+ * (2 (*rows - *pair_slots) x 512 x 4 ints, at most 12288): for slot s of thread t column 2 s holds the observations
+ * s_g f of its first row, column 2 s + 1 the observations s_g tau f (those of the second row of a pair slot as the
+ * store holds it), -1 where the thread has no row.  counts: pairs in slots, pairs split, rows with rho f = f.
+ * (Where the paired sweep is on, every block of the folded store is rewritten in that order once, after the means:
+ * within a group of w = min(512, ldF - 512 k) rows the sub-columns 0, 1 of all rows, then their sub-columns 2, 3, so
+ * that a wave's loads are contiguous.  Size and block stride of the store do not change.)
+ * Returns gh_fold_detect's result; *pair_reason as gh_fold_detect_pair, or GH_FOLD_PAIR_ROWS for more than 2560 folded
+ * rows or rows that do not fit the slots. */
+int gh_fold_pair_rows(int64_t N, const double *x, const double *y, const double *z, int64_t M, const double *bounds6,
+                      int *rows, int *pair_slots, int *code, int *ptab, int64_t *counts, int *pair_reason);
 
 /* ---- the translation-invariant store of regular prism grids under gridded data ----------- */
 
