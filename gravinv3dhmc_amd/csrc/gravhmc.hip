@@ -1739,6 +1739,36 @@ int gh_chain_resident_stats(gh_ctx *c, int64_t *launches, int64_t *evaluations)
     return GH_OK;
 }
 
+int gh_chain_resident_plan(gh_ctx *c, int chains, int32_t out[16])
+{
+    if (!c || !out) return fail(c, GH_ERR_ARG, "gh_chain_resident_plan: null pointer");
+    if (chains < 1 || chains > RES_MAX_CHAINS) return fail(c, GH_ERR_ARG, "gh_chain_resident_plan: 1..16 chains");
+    TRY(need(c, c->have_G && c->have_data && c->have_reg,
+             "gh_chain_resident_plan: needs the kernel (gh_build_G / gh_upload_G), gh_set_data and gh_set_reg"));
+    HIPCHK(c, hipSetDevice(c->device));
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    gh_ctx::Resident &r = c->rs;
+    if (!resident_plan(c)) return GH_OK;
+    out[0] = resident_usable(c) ? 1 : 0;
+    out[1] = r.cpw;
+    out[2] = r.nwg;
+    out[3] = r.rc;
+    out[4] = r.ct;
+    out[5] = r.split ? 1 : 0;
+    out[6] = r.stream ? 1 : 0;
+    out[7] = r.lds_cols;
+    out[8] = (int32_t)(resident_lds_doubles(c->ld, r.cpw, chains, r.lds_cols, r.split) * sizeof(double));
+    out[9] = r.lds_max;
+    int ks = 0, nt = 0;
+    size_t lds = 0;
+    out[10] = resbatch_shape(c, chains, &ks, &nt, &lds) ? 1 : 0;
+    out[11] = ks;
+    out[12] = nt;
+    out[13] = (int32_t)lds;
+    out[14] = 1;
+    return GH_OK;
+}
+
 int gh_posterior_window(gh_ctx *c, int K)
 {
     if (!c || K < 1) return fail(c, GH_ERR_ARG, "gh_posterior_window: K must be >= 1");

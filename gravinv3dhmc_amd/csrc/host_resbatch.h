@@ -26,27 +26,43 @@ static resbatch_fn_t resbatch_for(int ks, int nt, bool greg)
 
 // Can the batch of C chains run in lock-step?  The problem must fit the resident chain kernel with every
 // column of a workgroup in LDS (no split / stream mode), at most 32 columns per workgroup and 640 rows.
+// The decision alone (nothing allocated, nothing of the context's lock-step state touched): instantiation and LDS
+// request for C chains.
+static bool resbatch_shape(gh_ctx *c, int C, int *ks, int *nt, size_t *lds)
+{
+    gh_ctx::Resident &r = c->rs;
+    *ks = *nt = 0;
+    *lds = 0;
+    if (env_int("GRAVHMC_RESIDENT_BATCH", 1) == 0 || C < 2 || C > 16) return false;
+    if (!resident_usable(c) || r.split || r.stream || r.cpw > 32 || c->ld > 640 || c->ld % 16 != 0) return false;
+    *ks = (int)((c->ld + 159) / 160) * 5;
+    *nt = (r.cpw + 15) / 16;
+    *lds = resbatch_lds_doubles(c->ld, r.cpw, c->have_fix, c->wv.on) * sizeof(double);
+    if (*lds > (size_t)r.lds_max) return false;
+    resbatch_fn_t f = resbatch_for(*ks, *nt, c->wv.on);
+    if (!f) return false;
+    int per_cu = 0;
+    if (allow_dynamic_lds(reinterpret_cast<const void *>(f), *lds) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(f), RB_THREADS, *lds) != hipSuccess ||
+        per_cu < 1 || (int64_t)per_cu * c->cus < r.nwg) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return true;
+}
+
 static bool resbatch_plan(gh_ctx *c, int C)
 {
     gh_ctx::Resident &r = c->rs;
     gh_ctx::Resident::LockStep &b = r.ls;
     b.on = false;
-    if (env_int("GRAVHMC_RESIDENT_BATCH", 1) == 0 || C < 2 || C > 16) return false;
-    if (!resident_usable(c) || r.split || r.stream || r.cpw > 32 || c->ld > 640 || c->ld % 16 != 0) return false;
-    b.ks = (int)((c->ld + 159) / 160) * 5;
-    b.nt = (r.cpw + 15) / 16;
+    int ks = 0, nt = 0;
+    size_t lds_bytes = 0;
+    if (!resbatch_shape(c, C, &ks, &nt, &lds_bytes)) return false;
+    b.ks = ks;
+    b.nt = nt;
     b.C = C;
-    b.lds = resbatch_lds_doubles(c->ld, r.cpw, c->have_fix, c->wv.on) * sizeof(double);
-    if (b.lds > (size_t)r.lds_max) return false;
-    resbatch_fn_t f = resbatch_for(b.ks, b.nt, c->wv.on);
-    if (!f) return false;
-    int per_cu = 0;
-    if (allow_dynamic_lds(reinterpret_cast<const void *>(f), b.lds) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(f), RB_THREADS, b.lds) != hipSuccess ||
-        per_cu < 1 || (int64_t)per_cu * c->cus < r.nwg) {
-        (void)hipGetLastError();
-        return false;
-    }
+    b.lds = lds_bytes;
     const size_t M = (size_t)c->M, ldx = (size_t)c->ld + RB_XROWS;
     if (dalloc(c, &b.slabd, (size_t)(r.nwg + 8) * ldx * 16) != GH_OK || dalloc(c, &b.flagg, (size_t)r.nwg + 8) != GH_OK ||
         dalloc(c, &b.xslabg, 2 * (size_t)RES_CLUSTERS * ldx * 16) != GH_OK ||

@@ -330,6 +330,9 @@ __global__ void __launch_bounds__(RB_THREADS) resident_batch_kernel(ResBatchArgs
             xs = a.xs_io[(int64_t)ct * M + jg];
             ps = a.ps_io[(int64_t)ct * M + jg];
             p0k = a.pst_io[(int64_t)ct * M + jg];
+            // (restarted after a rejected speculation in the last lock-step of the launch before: its first evaluation
+            // is still to come, and the trajectory's p'p before travels with it)
+            if (s_done == 0) sh_pp0 = p0k * p0k;
         }
     }
     RegArgs ra{};

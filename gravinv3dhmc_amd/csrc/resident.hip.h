@@ -563,8 +563,12 @@ __global__ void __launch_bounds__(RES_THREADS) resident_chain_kernel(ResArgs a)
         d2 dinv = d2{0.0, 0.0};
         {
             double dx = 0.0, dy = 0.0;
-            bool hx = !(tid < ld2), hy = hx;
-            u64 *in = a.dclg + ((int64_t)cg * ld + i0) * 2;
+            // (a stencil thread past the rows of d waits for row 0 instead: with more than 64 ceil(ld / 128) stencil
+            // threads -- many cells per workgroup, few rows -- a wave none of whose lanes polls would request its
+            // neighbours' models below before d, and with it the neighbours' model stores, has arrived)
+            const bool sw = stencil && tid >= ld2 && c6 < nc;
+            bool hx = !(tid < ld2 || sw), hy = !(tid < ld2);
+            u64 *in = a.dclg + ((int64_t)cg * ld + (sw ? 0 : i0)) * 2;
             const bool got = res_poll(a.abort_w, [&]() -> bool {
                 if (!hx) hx = ld_gran(in, tag, dx);
                 if (!hy) hy = ld_gran(in + 2, tag, dy);

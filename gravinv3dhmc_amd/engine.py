@@ -647,6 +647,19 @@ class Engine(object):
                 "team_members": q.value, "team_launches": tl.value, "team_timeouts": to.value,
                 "team_late_parts": late.value}
 
+    def resident_info(self, chains=1):
+        """What the resident kernels would do with this problem (gh_chain_resident_plan; read-only): the partition
+        of csrc/resident.hip.h, its LDS request for `chains` chains, and whether `chains` chains would run in
+        lock-step (csrc/resbatch.hip.h).  Needs the kernel, set_data and set_reg."""
+        out = (C.c_int32 * 16)()
+        self._chk(self._lib.gh_chain_resident_plan(self._h, int(chains), out))
+        names = ("usable", "cpw", "nwg", "rc", "ct", "split", "stream", "lds_cols", "lds_bytes", "lds_max", "lockstep",
+                 "ks", "nt", "lockstep_lds_bytes", "planned")
+        d = dict(zip(names, (int(v) for v in out)))
+        for k in ("usable", "split", "stream", "lockstep", "planned"):
+            d[k] = bool(d[k])
+        return d
+
     def _prepare_batch(self, blk, look, want_x):
         """Arguments of one gh_chain_run call over a block (Ls, p0s[K, M], us) of trajectories,
         marshalled on the calling thread (the 4 MB per momentum of C2 are copied here, not between

@@ -655,6 +655,14 @@ int gh_chain_stats(gh_ctx *ctx, int64_t *spec_hits, int64_t *spec_misses);
  * contract and results to rounding (the summation order over the cells differs); environment
  * GRAVHMC_RESIDENT=0 switches it off.  launches / evaluations: how much ran there so far. */
 int gh_chain_resident_stats(gh_ctx *ctx, int64_t *launches, int64_t *evaluations);
+/* What the resident kernels would do with this context (read-only; needs the kernel, gh_set_data and
+ * gh_set_reg).  out: [0] usable with the regulariser set now, [1] columns per workgroup, [2] workgroups,
+ * [3] double2 chunks of a column per lane (rc), [4] register-held columns per wave (ct), [5] split (one copy
+ * between registers and LDS), [6] stream (columns beyond [7] read from memory in every pass), [7] columns of a
+ * workgroup in LDS, [8] LDS bytes a launch with `chains` chains asks for, [9] LDS bytes a workgroup may
+ * have, [10] `chains` chains would run in lock-step (csrc/resbatch.hip.h), [11] its k-steps per wave, [12] its
+ * column tiles, [13] its LDS bytes, [14] 1 where the plan exists (all zero otherwise), [15] 0. */
+int gh_chain_resident_plan(gh_ctx *ctx, int chains, int32_t out[16]);
 /* More observations than one workgroup holds of a column (N > 16384, stored G): the fused leapfrog
  * step runs on teams of `members` workgroups that share each column (csrc/teamsweep.hip.h), still
  * ONE read of G per step; adjoint-only / forward-only sweeps and the steps after a team timed out
