@@ -52,6 +52,7 @@ static_assert(BCOMP_MAX == GH_BCOMP_MAX && BCOMP_MAX <= MULTI_MAX && BCOMP_TF ==
                   BCOMP_BY == GH_BCOMP_BY && BCOMP_BZ == GH_BCOMP_BZ,
               "the kernels' data components are the C ABI's GH_BCOMP_*");
 
+#include "host_rows.h"
 #include "host_ctx.h"
 #include "host_cells.h"
 #include "host_sweep.h"
@@ -125,14 +126,14 @@ void gh_destroy(gh_ctx *c)
     }
     if (c->sh.hbuf) hipHostFree(c->sh.hbuf);
     if (c->bt.h) hipHostFree(c->bt.h);
-    if (c->rs.ls.h_stage) hipHostFree(c->rs.ls.h_stage);
-    if (c->rs.ls.h_xstage) hipHostFree(c->rs.ls.h_xstage);
+    traj_lists_free(c->rs.lists);
+    traj_lists_free(c->rs.ls.lists);
     if (c->ls) {
-        if (c->ls->res.h_stage) hipHostFree(c->ls->res.h_stage);
+        traj_lists_free(c->ls->res.lists);
         if (c->ls->res.ev0) hipEventDestroy(c->ls->res.ev0);
         if (c->ls->res.ev1) hipEventDestroy(c->ls->res.ev1);
     }
-    for (gh_ctx::Pinned &pm : c->pinned) hipHostFree(pm.base);
+    for (PinnedBlock &pm : c->pinned) hipHostFree(pm.base);
     for (void *p : c->allocs) hipFree(p);
     if (c->h_scal) hipHostFree(c->h_scal);
     for (hipEvent_t ev : c->ev) hipEventDestroy(ev);
@@ -1637,8 +1638,6 @@ int gh_chain_trajectory(gh_ctx *c, const double *p0, double dt, int L, double u,
     return chain_trajectory_impl(c, p0, dt, L, u, nullptr, accepted, out5);
 }
 
-static int posterior_ring_store(gh_ctx *c);
-
 int gh_chain_run(gh_ctx *c, int K, const int *L, const double *p0s, const double *us, double dt,
                  const double *p0_lookahead, int64_t stop_at_accepts, int64_t record_from, int *accepted,
                  double *out5s, double *x_out, int *n_run)
@@ -1650,45 +1649,34 @@ int gh_chain_run(gh_ctx *c, int K, const int *L, const double *p0s, const double
     *n_run = 0;
     // already there (a caller that submits batches ahead of looking at the results)
     if (stop_at_accepts > 0 && c->accept_count >= stop_at_accepts) return GH_OK;
-    if (lonres_usable(c)) {
-        // the shift-invariant store in the harmonic domain: the whole batch in one persistent launch (lonres.hip.h)
+    // one persistent launch for the whole batch, where the problem has one and the steps fit its granule tags (32-bit)
+    const bool lonres = lonres_usable(c);
+    bool fits = false;
+    if (lonres || resident_usable(c)) {
         int64_t steps = 0;
         for (int k = 0; k < K; ++k) {
             if (L[k] < 1) return fail(c, GH_ERR_ARG, "gh_chain_run: L must be >= 1");
             steps += L[k];
         }
-        if (steps < ((int64_t)1 << 28)) {
-            const int rc = chain_run_lonres(c, c, K, L, p0s, nullptr, us, dt, stop_at_accepts, record_from, accepted, out5s, x_out, n_run);
-            if (rc != GH_RESIDENT_ABORTED) return rc;
-            *n_run = 0;
-        }
+        fits = steps < ((int64_t)1 << 28);
     }
-    if (resident_usable(c)) {
-        int64_t steps = 0;
-        bool ok = true;
-        for (int k = 0; k < K; ++k) {
-            if (L[k] < 1) return fail(c, GH_ERR_ARG, "gh_chain_run: L must be >= 1");
-            steps += L[k];
-        }
-        ok = steps < ((int64_t)1 << 28);  // granule tags are 32-bit
-        if (ok) {
-            const int rc = chain_run_resident(c, K, L, p0s, us, dt, stop_at_accepts, record_from, accepted,
-                                              out5s, x_out, n_run);
-            if (rc != GH_RESIDENT_ABORTED) return rc;
-            *n_run = 0;
-        }
+    if (lonres && fits) {
+        // the shift-invariant store in the harmonic domain (lonres.hip.h)
+        const int rc = chain_run_lonres(c, c, K, L, p0s, nullptr, us, dt, stop_at_accepts, record_from, accepted, out5s, x_out, n_run);
+        if (rc != GH_RESIDENT_ABORTED) return rc;
+        *n_run = 0;
+    }
+    if (fits && resident_usable(c)) {
+        const int rc = chain_run_resident(c, K, L, p0s, us, dt, stop_at_accepts, record_from, accepted, out5s, x_out, n_run);
+        if (rc != GH_RESIDENT_ABORTED) return rc;
+        *n_run = 0;
     }
     for (int k = 0; k < K; ++k) {
         const double *nxt = (k + 1 < K) ? p0s + (size_t)(k + 1) * M : p0_lookahead;
         TRY(chain_trajectory_impl(c, p0s + (size_t)k * M, dt, L[k], us[k], nxt, &accepted[k], out5s + 5 * k));
         *n_run = k + 1;
         if (accepted[k]) {
-            c->accept_count += 1;
-            if (c->ring && c->accept_count > record_from) TRY(posterior_ring_store(c));
-            TRY(post_feed_single(c, c, c->xb[c->xcur]));
-            if (x_out)
-                HIPCHK(c, hipMemcpyAsync(x_out + (size_t)k * M, c->xb[c->xcur], M * sizeof(double),
-                                         hipMemcpyDeviceToHost, c->stream));
+            TRY(chain_accept_row(c, c, c->xb[c->xcur], record_from, x_out ? x_out + (size_t)k * M : nullptr));
             if (stop_at_accepts > 0 && c->accept_count >= stop_at_accepts) break;
         }
     }
@@ -1783,29 +1771,15 @@ int gh_posterior_window(gh_ctx *c, int K)
     return GH_OK;
 }
 
-// the chain's current state into the ring's next slot
-static int posterior_ring_store(gh_ctx *c)
-{
-    HIPCHK(c, hipSetDevice(c->device));
-    ring_store_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
-        c->xb[c->xcur], c->weighted ? c->wm : nullptr, c->M, c->ring + (size_t)c->ring_next * (size_t)c->M);
-    HIPCHK(c, hipGetLastError());
-    c->ring_next = (c->ring_next + 1) % c->ring_K;
-    c->ring_count += 1;
-    return GH_OK;
-}
-
 int gh_posterior_add(gh_ctx *c)
 {
     if (!c) return GH_ERR_ARG;
     TRY(need(c, c->chain_ready && (c->ring || c->ps.on),
              "gh_posterior_add: needs gh_chain_init and gh_posterior_window"));
-    if (c->ring) TRY(posterior_ring_store(c));
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->ring) TRY(ring_store_row(c, c, c->xb[c->xcur]));
     // (an explicit call: the caller decides what is recorded, the stream's window does not apply)
-    if (c->ps.on) {
-        HIPCHK(c, hipSetDevice(c->device));
-        TRY(post_feed_row(c, c->ps.slot, c->xb[c->xcur], c->weighted, c->stream));
-    }
+    if (c->ps.on) TRY(post_feed_row(c, c->ps.slot, c->xb[c->xcur], c->weighted, c->stream));
     return GH_OK;
 }
 
@@ -2082,7 +2056,7 @@ int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const
                 accepted[dst] = acc[k];
                 memcpy(out5s + (size_t)dst * 5, o5.data() + (size_t)k * 5, 5 * sizeof(double));
                 if (x_out && acc[k])
-                    HIPCHK(c, hipMemcpyAsync(x_out + (size_t)dst * M, c->rs.xacc + (size_t)k * M, M * sizeof(double),
+                    HIPCHK(c, hipMemcpyAsync(x_out + (size_t)dst * M, c->rs.lists.xacc + (size_t)k * M, M * sizeof(double),
                                              hipMemcpyDeviceToHost, c->stream));
             }
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2197,8 +2171,26 @@ int gh_pinned_free(gh_ctx *c, void *host)
 int gh_batch_staging_stats(gh_ctx *c, int64_t *rows_direct, int64_t *rows_staged)
 {
     if (!c) return GH_ERR_ARG;
-    if (rows_direct) *rows_direct = c->rs.ls.rows_direct;
-    if (rows_staged) *rows_staged = c->rs.ls.rows_staged;
+    if (rows_direct) *rows_direct = c->rs.ls.lists.rows_direct;
+    if (rows_staged) *rows_staged = c->rs.ls.lists.rows_staged;
+    return GH_OK;
+}
+
+// Diagnostic only, without a device or a context: how traj_upload would send K rows of M doubles at the addresses
+// rows[k], given pinned blocks [bases[b], bases[b] + bytes[b]).  Nothing is read through any of the pointers.
+// direct[k]: the row goes from where it lies; run_end[i], i < *n_runs: the row one past copy run i (K entries of room).
+int gh_debug_row_copy_plan(int K, const double *const *rows, int64_t M, int n_blocks, const char *const *bases,
+                           const int64_t *bytes, char *direct, int *run_end, int *n_runs, int *n_staged)
+{
+    if (K < 1 || !rows || M < 1 || n_blocks < 0 || (n_blocks && (!bases || !bytes)) || !direct || !run_end || !n_runs || !n_staged)
+        return GH_ERR_ARG;
+    std::vector<PinnedBlock> blocks;
+    for (int b = 0; b < n_blocks; ++b) blocks.push_back({const_cast<char *>(bases[b]), (size_t)bytes[b]});
+    const RowCopyPlan p = row_copy_plan(rows, K, (size_t)M, blocks.data(), blocks.size());
+    std::copy(p.direct.begin(), p.direct.end(), direct);
+    std::copy(p.run_end.begin(), p.run_end.end(), run_end);
+    *n_runs = (int)p.run_end.size();
+    *n_staged = p.n_staged;
     return GH_OK;
 }
 

@@ -694,7 +694,7 @@ static BatchAdjArgs batch_sweep_args(gh_ctx *c, const BatchSet &in, const double
 }
 
 // Small problem: the chains take turns inside the resident chain kernel (host_resident.h), K trajectories in
-// list order; results in list order, the accepted models in c->rs.xacc if want_x.  GH_RESIDENT_ABORTED: the
+// list order; results in list order, the accepted models in c->rs.lists.xacc if want_x.  GH_RESIDENT_ABORTED: the
 // kernel gave up (its workgroups were not all resident) and the chains carry on as an MFMA batch from their
 // states -- unless trajectories a lock-step launch had in flight were in front of the list (replayed).
 static int batch_resident_turns(gh_ctx *c, int K, const int *chain_of, const int *L, const double *p0s, const double *us,
@@ -719,7 +719,7 @@ static int batch_resident_turns(gh_ctx *c, int K, const int *chain_of, const int
     const int rc = resident_launch(c, q, accepted, out5s, h_run);
     if (rc == GH_OK) r.b_state = true;
     for (int k = 0; rc == GH_OK && k < h_run[0]; ++k)
-        if (accepted[k]) TRY(post_feed_batch_row(c, chain_of[k], r.xacc + (size_t)k * (size_t)c->M, c->stream));
+        if (accepted[k]) TRY(post_feed_batch_row(c, chain_of[k], r.lists.xacc + (size_t)k * (size_t)c->M, c->stream));
     if (rc != GH_RESIDENT_ABORTED) return rc;
     if (replayed) return fail(c, GH_ERR_HIP, "gh_batch_run: the resident kernels timed out with trajectories in flight");
     std::vector<double> xs((size_t)C * (size_t)c->M);

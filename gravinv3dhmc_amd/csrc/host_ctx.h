@@ -25,6 +25,19 @@ struct ExchangeGuard {
     int aborts = 0;                        // launches that gave up
 };
 
+// The trajectory lists of a persistent chain launch on the device (element k: trajectory k) and the pinned host
+// staging on their way in and out.  Each of the three launches embeds one (traj_lists_* and traj_upload below).
+struct TrajLists {
+    int cap = 0;  // list elements the device lists hold
+    int *L = nullptr, *accepted = nullptr, *chain = nullptr;
+    double *p0s = nullptr, *us = nullptr, *out5s = nullptr, *xacc = nullptr;
+    double *h_stage = nullptr;   // pinned staging of the momentum rows
+    size_t h_stage_n = 0;
+    double *h_xstage = nullptr;  // pinned staging of the accepted models on their way out (the lock-step launch)
+    size_t h_xstage_n = 0;
+    int64_t rows_direct = 0, rows_staged = 0;  // rows sent straight from the caller's pinned memory / gathered first
+};
+
 // One state set of the MFMA batch (chain-interleaved): models, alpha * grad R, synthetic data, residuals.
 struct BatchSet { double *X, *GREG, *D, *Rt; };
 
@@ -332,13 +345,12 @@ struct gh_ctx {
         ghk::u64 *slabg = nullptr, *xslabg = nullptr, *dclg = nullptr, *scalg = nullptr, *xscalg = nullptr, *xccg = nullptr;
         double *xpub = nullptr;
         ExchangeGuard xg;  // after three give-ups the context stays on the sweep path
-        int Kcap = 0;
-        int *L = nullptr, *accepted = nullptr, *n_run = nullptr, *chain = nullptr;
+        TrajLists lists;
+        int *n_run = nullptr;
         int lds_max = 0;
         // several chains sharing the resident G (gh_batch_* on small problems)
         double *bx = nullptr, *bg = nullptr, *bu = nullptr;  // C x M models, C x M gradients, 3 C potentials
         bool b_on = false, b_state = false;
-        double *p0s = nullptr, *us = nullptr, *out5s = nullptr, *xacc = nullptr;
         int64_t launches = 0, evals = 0;
         long long *dbg = nullptr;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -351,16 +363,9 @@ struct gh_ctx {
             double *slabd = nullptr;
             ghk::u64 *xccg = nullptr, *flagg = nullptr;
             double *xpub = nullptr, *xs = nullptr, *ps = nullptr, *pst = nullptr, *cst = nullptr;
-            double *p0s = nullptr, *us = nullptr, *out5s = nullptr, *xacc = nullptr;
-            int *L = nullptr, *accepted = nullptr, *n_io = nullptr;
-            double *h_stage = nullptr;       // pinned staging of the momentum rows
-            size_t h_stage_n = 0;
-            double *h_xstage = nullptr;      // pinned staging of the accepted models on their way out
-            size_t h_xstage_n = 0;
-            const double **p0tab = nullptr;  // device: where each list element's momentum row lies (chain-major)
-            int64_t rows_direct = 0, rows_staged = 0;  // rows sent straight from the caller's pinned memory / gathered first
-            int cap = 0;                 // list elements the device lists hold
-            ExchangeGuard xg;            // off at the first give-up
+            int *n_io = nullptr;
+            TrajLists lists;             // chain-major
+            ExchangeGuard xg;           // off at the first give-up
             bool active[16] = {};        // chain has a trajectory in flight (carry-over mode)
             int64_t launches = 0, lock_steps = 0, lost = 0, chain_steps = 0;
             long long *dbg = nullptr;
@@ -400,11 +405,7 @@ struct gh_ctx {
 
     // page-locked host memory handed to the caller (gh_pinned_alloc): momentum rows drawn into it go to the device
     // without a gather on the host
-    struct Pinned {
-        char *base;
-        size_t bytes;
-    };
-    std::vector<Pinned> pinned;
+    std::vector<PinnedBlock> pinned;
 
     // ring of the last K accepted samples (posterior statistics without text I/O)
     double *ring = nullptr, *ring_mean = nullptr, *ring_sd = nullptr;
@@ -518,6 +519,95 @@ static bool xg_give_up(ExchangeGuard &g, int strikes)
 {
     g.dirty = true;
     return ++g.aborts >= strikes;
+}
+
+// Room for n list elements on the device.  Grown rarely (the host batches a fixed number of trajectories per
+// call); the old blocks stay in the context's allocation list until gh_destroy.
+static int traj_lists_reserve(gh_ctx *c, TrajLists &tl, int n)
+{
+    if (n <= tl.cap && tl.L) return GH_OK;
+    const size_t cap = (size_t)std::max(n, 32), M = (size_t)c->M;
+    tl.L = tl.accepted = tl.chain = nullptr;
+    tl.p0s = tl.us = tl.out5s = tl.xacc = nullptr;
+    TRY(dalloc(c, &tl.L, cap));
+    TRY(dalloc(c, &tl.chain, cap));
+    TRY(dalloc(c, &tl.accepted, cap));
+    TRY(dalloc(c, &tl.p0s, cap * M, false));
+    TRY(dalloc(c, &tl.us, cap));
+    TRY(dalloc(c, &tl.out5s, cap * 5));
+    TRY(dalloc(c, &tl.xacc, cap * M, false));
+    tl.cap = (int)cap;
+    return GH_OK;
+}
+
+// Pinned staging for `rows` momentum rows.
+static int traj_lists_stage(gh_ctx *c, TrajLists &tl, int rows)
+{
+    const size_t M = (size_t)c->M;
+    if ((size_t)rows * M <= tl.h_stage_n) return GH_OK;
+    if (tl.h_stage) HIPCHK(c, hipHostFree(tl.h_stage));
+    tl.h_stage = nullptr;
+    tl.h_stage_n = (size_t)std::max(rows, 32) * M;
+    HIPCHK(c, hipHostMalloc((void **)&tl.h_stage, tl.h_stage_n * sizeof(double)));
+    return GH_OK;
+}
+
+static void traj_lists_free(TrajLists &tl)
+{
+    if (tl.h_stage) hipHostFree(tl.h_stage);
+    if (tl.h_xstage) hipHostFree(tl.h_xstage);
+    tl.h_stage = tl.h_xstage = nullptr;
+    tl.h_stage_n = tl.h_xstage_n = 0;
+}
+
+// The K momentum rows (p0flat: adjacent; otherwise p0rows[k]: where each lies), variates and lengths of a launch
+// into tl's device lists, on the context's stream.  Rows inside a block of gh_pinned_alloc go straight from where
+// they lie, adjacent ones in one copy (a sampler drawing into a ring of such rows: one or two copies per chain);
+// the others are gathered into ONE pinned staging buffer first (a few host threads: 6 MB at C1 with 16 chains x 8
+// trajectories) -- 128 separate copies of pageable rows cost more than the kernel they feed.
+static int traj_upload(gh_ctx *c, TrajLists &tl, int K, const double *p0flat, const double *const *p0rows, const double *us,
+                       const int *L)
+{
+    const size_t M = (size_t)c->M;
+    TRY(traj_lists_stage(c, tl, K));
+    if (K <= 0) return GH_OK;
+    std::vector<const double *> src((size_t)K);
+    for (int k = 0; k < K; ++k) src[(size_t)k] = p0flat ? p0flat + (size_t)k * M : p0rows[(size_t)k];
+    const RowCopyPlan plan = row_copy_plan(src.data(), K, M, c->pinned.data(), c->pinned.size());
+    tl.rows_direct += K - plan.n_staged;
+    tl.rows_staged += plan.n_staged;
+    if (plan.n_staged > 0)
+        rows_gather(tl.h_stage, src.data(), plan.direct.data(), K, M,
+                    (size_t)plan.n_staged * M * sizeof(double) >= ((size_t)1 << 20) ? std::min(4, K) : 1);
+    int k0 = 0;
+    for (int k1 : plan.run_end) {
+        const double *from = plan.direct[(size_t)k0] ? src[(size_t)k0] : tl.h_stage + (size_t)k0 * M;
+        HIPCHK(c, hipMemcpyAsync(tl.p0s + (size_t)k0 * M, from, (size_t)(k1 - k0) * M * sizeof(double), hipMemcpyHostToDevice,
+                                 c->stream));
+        k0 = k1;
+    }
+    HIPCHK(c, hipMemcpyAsync(tl.us, us, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tl.L, L, (size_t)K * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    return GH_OK;
+}
+
+// While profiling is on: an event in front of and one behind a persistent launch, and the launch's time and
+// evaluations into the context's totals once it is known to have finished without giving up (the caller's
+// synchronisation point lies in between).
+static int prof_launch_mark(gh_ctx *c, hipEvent_t ev)
+{
+    if (c->prof) HIPCHK(c, hipEventRecord(ev, c->stream));
+    return GH_OK;
+}
+
+static int prof_launch_end(gh_ctx *c, hipEvent_t ev0, hipEvent_t ev1, int64_t evals)
+{
+    if (!c->prof) return GH_OK;
+    float t = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&t, ev0, ev1));
+    c->prof_ms_acc += t;
+    c->prof_res_evals += evals;
+    return GH_OK;
 }
 
 // The Metropolis test of a finished trajectory (hmc.py:158-177).  pp0 / pp1: |p|^2 at its start / end; scal: the

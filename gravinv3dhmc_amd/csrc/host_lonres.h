@@ -98,66 +98,12 @@ static int chain_run_lonres(gh_ctx *c, gh_ctx *st, int K, const int *L, const do
         HIPCHK(c, hipEventCreate(&r.ev1));
     }
     const bool want_x = x_out != nullptr || st->ring != nullptr || c->ps.on;
-    if (K > r.Kcap) {
-        const int cap = std::max(K, 32);
-        r.L = r.accepted = nullptr;
-        r.p0s = r.us = r.out5s = r.xacc = nullptr;
-        TRY(dalloc(c, &r.L, (size_t)cap));
-        TRY(dalloc(c, &r.accepted, (size_t)cap));
-        TRY(dalloc(c, &r.p0s, (size_t)cap * M, false));
-        TRY(dalloc(c, &r.us, (size_t)cap));
-        TRY(dalloc(c, &r.out5s, (size_t)cap * 5));
-        TRY(dalloc(c, &r.xacc, (size_t)cap * M, false));
-        r.Kcap = cap;
-    }
+    TrajLists &tl = r.lists;
+    TRY(traj_lists_reserve(c, tl, K));
     int64_t steps = 1;
     for (int k = 0; k < K; ++k) steps += L[k];
     TRY(xg_prepare(c, r.xg, true, (uint64_t)steps + 2, (uint64_t)K + 2));
-    // the momenta: one pinned staging buffer, one copy (the caller's array is pageable)
-    if ((size_t)K * M > r.h_stage_n) {
-        if (r.h_stage) HIPCHK(c, hipHostFree(r.h_stage));
-        r.h_stage = nullptr;
-        r.h_stage_n = (size_t)std::max(K, 32) * M;
-        HIPCHK(c, hipHostMalloc((void **)&r.h_stage, r.h_stage_n * sizeof(double)));
-    }
-    {
-        // rows inside a block of gh_pinned_alloc go straight from where they lie, adjacent ones in one copy; the others
-        // are gathered into the pinned staging buffer first (host_resbatch.h)
-        std::vector<const double *> src((size_t)K);
-        std::vector<char> direct((size_t)K, 0);
-        int n_staged = 0;
-        for (int k = 0; k < K; ++k) {
-            src[(size_t)k] = p0rows ? p0rows[(size_t)k] : p0s + (size_t)k * M;
-            const char *lo = (const char *)src[(size_t)k], *hi = lo + M * sizeof(double);
-            for (const gh_ctx::Pinned &pm : c->pinned)
-                if (lo >= pm.base && hi <= pm.base + pm.bytes) {
-                    direct[(size_t)k] = 1;
-                    break;
-                }
-            n_staged += direct[(size_t)k] ? 0 : 1;
-        }
-        if (n_staged > 0) {
-            auto part = [&](int k0, int k1) {
-                for (int k = k0; k < k1; ++k)
-                    if (!direct[(size_t)k]) memcpy(r.h_stage + (size_t)k * M, src[(size_t)k], M * sizeof(double));
-            };
-            const int nthr = (size_t)n_staged * M * sizeof(double) >= ((size_t)1 << 20) ? std::min(4, K) : 1;
-            std::vector<std::thread> pool;
-            for (int i = 1; i < nthr; ++i) pool.emplace_back(part, (int)((int64_t)K * i / nthr), (int)((int64_t)K * (i + 1) / nthr));
-            part(0, K / nthr);
-            for (std::thread &th : pool) th.join();
-        }
-        for (int k0 = 0; k0 < K;) {
-            int k1 = k0 + 1;
-            const double *from = direct[(size_t)k0] ? src[(size_t)k0] : r.h_stage + (size_t)k0 * M;
-            while (k1 < K && direct[(size_t)k1] == direct[(size_t)k0] && (direct[(size_t)k0] ? src[(size_t)k1] == src[(size_t)k1 - 1] + M : true))
-                ++k1;
-            HIPCHK(c, hipMemcpyAsync(r.p0s + (size_t)k0 * M, from, (size_t)(k1 - k0) * M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            k0 = k1;
-        }
-        HIPCHK(c, hipMemcpyAsync(r.us, us, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(r.L, L, (size_t)K * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    }
+    TRY(traj_upload(c, tl, K, p0rows ? nullptr : p0s, p0rows, us, L));
     LonResArgs a{};
     a.g = lonsymh_geom(c);
     a.g.dbg = nullptr;
@@ -185,15 +131,15 @@ static int chain_run_lonres(gh_ctx *c, gh_ctx *st, int K, const int *L, const do
     a.Mhat = r.mhat;
     a.x_cur = st->xb[st->xcur];
     a.K = K;
-    a.L = r.L;
-    a.p0s = r.p0s;
-    a.us = r.us;
+    a.L = tl.L;
+    a.p0s = tl.p0s;
+    a.us = tl.us;
     a.dt = dt;
     a.stop_at_accepts = stop_at_accepts;
     a.accept_count0 = st->accept_count;
-    a.accepted = r.accepted;
-    a.out5s = r.out5s;
-    a.xacc = want_x ? r.xacc : nullptr;
+    a.accepted = tl.accepted;
+    a.out5s = tl.out5s;
+    a.xacc = want_x ? tl.xacc : nullptr;
     a.n_run = r.n_run;
     a.ucur = r.ucur;
     a.slab = r.slab;
@@ -211,18 +157,18 @@ static int chain_run_lonres(gh_ctx *c, gh_ctx *st, int K, const int *L, const do
     a.dbg = r.dbg;
     lonres_fn_t f = lonres_fn(h.rw);
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(f), r.lds));
-    if (c->prof) HIPCHK(c, hipEventRecord(r.ev0, c->stream));
+    TRY(prof_launch_mark(c, r.ev0));
     // (a plain launch: the grid was checked against the occupancy query in lonres_plan; every wait inside is bounded)
     hipLaunchKernelGGL(f, dim3((unsigned)nwg), dim3(LR_THREADS), r.lds, c->stream, a);
     HIPCHK(c, hipGetLastError());
-    if (c->prof) HIPCHK(c, hipEventRecord(r.ev1, c->stream));
+    TRY(prof_launch_mark(c, r.ev1));
     int h_run[4] = {0, 0, 0, 0};
     double h_u[4] = {0, 0, 0, 0};
     TRY(xg_read(c, r.xg));
     HIPCHK(c, hipMemcpyAsync(h_run, r.n_run, sizeof h_run, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_u, r.ucur, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(accepted, r.accepted, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out5s, r.out5s, (size_t)K * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(accepted, tl.accepted, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out5s, tl.out5s, (size_t)K * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     r.xg.ltag += 1u;
     if (r.xg.seen[0] != 0u) {
@@ -237,26 +183,10 @@ static int chain_run_lonres(gh_ctx *c, gh_ctx *st, int K, const int *L, const do
     r.launches += 1;
     r.evals += h_run[1];
     r.trajectories += h_run[0];
-    if (c->prof) {
-        float t = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&t, r.ev0, r.ev1));
-        c->prof_ms_acc += t;
-        c->prof_res_evals += h_run[1];
-    }
+    TRY(prof_launch_end(c, r.ev0, r.ev1, h_run[1]));
     *n_run = h_run[0];
-    for (int k = 0; k < h_run[0]; ++k) {
-        if (!accepted[k]) continue;
-        st->accept_count += 1;
-        if (st->ring && st->accept_count > record_from) {
-            ring_store_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
-                r.xacc + (size_t)k * M, c->weighted ? c->wm : nullptr, c->M, st->ring + (size_t)st->ring_next * M);
-            st->ring_next = (st->ring_next + 1) % st->ring_K;
-            st->ring_count += 1;
-        }
-        TRY(post_feed_single(c, st, r.xacc + (size_t)k * M));
-        if (x_out)
-            HIPCHK(c, hipMemcpyAsync(x_out + (size_t)k * M, r.xacc + (size_t)k * M, M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    }
+    for (int k = 0; k < h_run[0]; ++k)
+        if (accepted[k]) TRY(chain_accept_row(c, st, tl.xacc + (size_t)k * M, record_from, x_out ? x_out + (size_t)k * M : nullptr));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // (d, r and the scalars of the current sample are behind x now: chain_state_fresh brings them up to date for
     // whoever reads them next)

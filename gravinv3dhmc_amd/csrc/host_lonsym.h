@@ -50,11 +50,9 @@ struct LonSymHost {
         ghk::u64 *flagg = nullptr, *xccg = nullptr;
         ghk::u32x4 *xslabg = nullptr, *clsg = nullptr, *scalg = nullptr, *ppg = nullptr;
         ExchangeGuard xg;  // off for good after three give-ups
-        int Kcap = 0;
-        int *L = nullptr, *accepted = nullptr, *n_run = nullptr;
-        double *p0s = nullptr, *us = nullptr, *out5s = nullptr, *xacc = nullptr, *ucur = nullptr, *xpub = nullptr;
-        double *h_stage = nullptr;
-        size_t h_stage_n = 0;
+        TrajLists lists;
+        int *n_run = nullptr;
+        double *ucur = nullptr, *xpub = nullptr;
         int64_t launches = 0, evals = 0, trajectories = 0;
         long long *dbg = nullptr;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;

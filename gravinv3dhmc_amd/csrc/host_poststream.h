@@ -54,6 +54,28 @@ static int post_feed_single(gh_ctx *c, gh_ctx *st, const double *x_dev)
     return GH_OK;
 }
 
+// The contiguous device row x_dev into the next slot of st's ring of accepted samples.
+static int ring_store_row(gh_ctx *c, gh_ctx *st, const double *x_dev)
+{
+    ring_store_kernel<<<post_grid(c), dim3(256), 0, c->stream>>>(x_dev, c->weighted ? c->wm : nullptr, c->M,
+                                                                st->ring + (size_t)st->ring_next * (size_t)c->M);
+    HIPCHK(c, hipGetLastError());
+    st->ring_next = (st->ring_next + 1) % st->ring_K;
+    st->ring_count += 1;
+    return GH_OK;
+}
+
+// The chain whose state `st` holds accepted the state in x_dev: counted, into the ring once record_from states
+// were accepted, to the streaming posterior, and to the caller's row x_out (or nullptr) -- on c's stream.
+static int chain_accept_row(gh_ctx *c, gh_ctx *st, const double *x_dev, int64_t record_from, double *x_out)
+{
+    st->accept_count += 1;
+    if (st->ring && st->accept_count > record_from) TRY(ring_store_row(c, st, x_dev));
+    TRY(post_feed_single(c, st, x_dev));
+    if (x_out) HIPCHK(c, hipMemcpyAsync(x_out, x_dev, (size_t)c->M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return GH_OK;
+}
+
 // A chain of a batch accepted the state in the contiguous device row x_dev.
 static int post_feed_batch_row(gh_ctx *c, int chain, const double *x_dev, hipStream_t s)
 {

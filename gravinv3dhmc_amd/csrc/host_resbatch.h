@@ -116,78 +116,14 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
     const int C = b.C, Tout = carry ? T + 1 : T;
     HIPCHK(c, hipSetDevice(c->device));
     const int K = C * T, Kout = C * std::max(Tout, 1);
-    if (std::max(K, Kout) > b.cap) {
-        const int cap = std::max(std::max(K, Kout), 32);
-        b.L = b.accepted = nullptr;
-        b.p0s = b.us = b.out5s = b.xacc = nullptr;
-        TRY(dalloc(c, &b.L, (size_t)cap));
-        TRY(dalloc(c, &b.accepted, (size_t)cap));
-        TRY(dalloc(c, &b.p0s, (size_t)cap * M, false));
-        TRY(dalloc(c, &b.us, (size_t)cap));
-        TRY(dalloc(c, &b.out5s, (size_t)cap * 5));
-        TRY(dalloc(c, &b.xacc, (size_t)cap * M, false));
-        b.cap = cap;
-    }
+    TrajLists &tl = b.lists;
+    TRY(traj_lists_reserve(c, tl, std::max(K, Kout)));
     int64_t steps = 0;
     for (int k = 0; k < K; ++k) steps += L[k] + 1;
     steps += 64 * 17;  // (what is in flight; generous)
     TRY(xg_prepare(c, b.xg, true, (uint64_t)steps + 2));
-    // Momenta: device rows chain-major (ch * T + t), like the lists.  Rows inside a block of gh_pinned_alloc go
-    // straight from where they lie, adjacent ones in one copy (a sampler drawing into a ring of such rows: one
-    // or two copies per chain); the others are gathered into ONE pinned staging buffer first (a few host threads:
-    // 6 MB at C1 with 16 chains x 8 trajectories) -- 128 separate copies of pageable rows cost more than the
-    // kernel they feed.
-    if ((size_t)K * M > b.h_stage_n) {
-        if (b.h_stage) HIPCHK(c, hipHostFree(b.h_stage));
-        b.h_stage = nullptr;
-        b.h_stage_n = (size_t)std::max(K, 32) * M;
-        HIPCHK(c, hipHostMalloc((void **)&b.h_stage, b.h_stage_n * sizeof(double)));
-    }
-    if (K > 0) {
-        std::vector<const double *> src((size_t)K);
-        std::vector<char> direct((size_t)K, 0);
-        int n_staged = 0;
-        for (int k = 0; k < K; ++k) {
-            src[(size_t)k] = p0flat ? p0flat + (size_t)k * M : p0rows[(size_t)k];
-            const char *lo = (const char *)src[(size_t)k], *hi = lo + M * sizeof(double);
-            for (const gh_ctx::Pinned &pm : c->pinned)
-                if (lo >= pm.base && hi <= pm.base + pm.bytes) {
-                    direct[(size_t)k] = 1;
-                    break;
-                }
-            n_staged += direct[(size_t)k] ? 0 : 1;
-        }
-        b.rows_direct += K - n_staged;
-        b.rows_staged += n_staged;
-        if (n_staged > 0) {
-            auto stage_rows = [&](int k0, int k1) {
-                for (int k = k0; k < k1; ++k)
-                    if (!direct[(size_t)k]) memcpy(b.h_stage + (size_t)k * M, src[(size_t)k], M * sizeof(double));
-            };
-            const int nthr = (size_t)n_staged * M * sizeof(double) >= ((size_t)1 << 20) ? std::min(4, K) : 1;
-            if (nthr > 1) {
-                std::vector<std::thread> pool;
-                for (int i = 1; i < nthr; ++i) pool.emplace_back(stage_rows, (int)((int64_t)K * i / nthr), (int)((int64_t)K * (i + 1) / nthr));
-                stage_rows(0, K / nthr);
-                for (std::thread &th : pool) th.join();
-            } else {
-                stage_rows(0, K);
-            }
-        }
-        // one copy per run of rows that are adjacent at their source
-        for (int k0 = 0; k0 < K;) {
-            int k1 = k0 + 1;
-            const double *from = direct[(size_t)k0] ? src[(size_t)k0] : b.h_stage + (size_t)k0 * M;
-            while (k1 < K && direct[(size_t)k1] == direct[(size_t)k0] &&
-                   (direct[(size_t)k0] ? src[(size_t)k1] == src[(size_t)k1 - 1] + M : true))
-                ++k1;
-            HIPCHK(c, hipMemcpyAsync(b.p0s + (size_t)k0 * M, from, (size_t)(k1 - k0) * M * sizeof(double), hipMemcpyHostToDevice,
-                                     c->stream));
-            k0 = k1;
-        }
-        HIPCHK(c, hipMemcpyAsync(b.us, us, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(b.L, L, (size_t)K * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    }
+    // device rows chain-major (ch * T + t), like the lists
+    TRY(traj_upload(c, tl, K, p0flat, p0rows, us, L));
     ResBatchArgs a{};
     a.G = c->G;
     a.Gl = c->wv.on ? c->wv.F : c->G;
@@ -212,9 +148,9 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
     a.wm2 = c->wm2;
     a.C = C;
     a.T = T;
-    a.L = b.L;
-    a.p0s = b.p0s;
-    a.us = b.us;
+    a.L = tl.L;
+    a.p0s = tl.p0s;
+    a.us = tl.us;
     a.dt = dt;
     a.stop_any = carry ? 1 : 0;
     a.x_cur = r.bx;
@@ -225,9 +161,9 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
     a.pst_io = b.pst;
     a.cst_io = b.cst;
     a.Tout = std::max(Tout, 1);
-    a.accepted = b.accepted;
-    a.out5s = b.out5s;
-    a.xacc = (x_out || c->ps.on) ? b.xacc : nullptr;
+    a.accepted = tl.accepted;
+    a.out5s = tl.out5s;
+    a.xacc = (x_out || c->ps.on) ? tl.xacc : nullptr;
     a.n_io = b.n_io;
     a.slabd = b.slabd;
     a.flagg = b.flagg;
@@ -244,11 +180,11 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
     b.lds = resbatch_lds_doubles(c->ld, r.cpw, c->have_fix, c->wv.on) * sizeof(double);
     if (b.lds > (size_t)r.lds_max) return fail(c, GH_ERR_UNSUPPORTED, "resident batch kernel: the problem no longer fits the LDS");
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(f), b.lds));
-    if (c->prof) HIPCHK(c, hipEventRecord(r.ev0, c->stream));
+    TRY(prof_launch_mark(c, r.ev0));
     // (a plain launch: the grid was checked against the occupancy query in resbatch_plan; every wait inside is bounded)
     hipLaunchKernelGGL(f, dim3(r.nwg), dim3(RB_THREADS), b.lds, c->stream, a);
     HIPCHK(c, hipGetLastError());
-    if (c->prof) HIPCHK(c, hipEventRecord(r.ev1, c->stream));
+    TRY(prof_launch_mark(c, r.ev1));
     int h_n[128];
     TRY(xg_read(c, b.xg));
     HIPCHK(c, hipMemcpyAsync(h_n, b.n_io, sizeof h_n, hipMemcpyDeviceToHost, c->stream));
@@ -267,8 +203,8 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
     // results
     std::vector<int> acc((size_t)Kout);
     std::vector<double> o5((size_t)Kout * 5);
-    HIPCHK(c, hipMemcpyAsync(acc.data(), b.accepted, (size_t)Kout * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(o5.data(), b.out5s, (size_t)Kout * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(acc.data(), tl.accepted, (size_t)Kout * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(o5.data(), tl.out5s, (size_t)Kout * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // accepted models: one copy per chain (its done slots are adjacent) into pinned staging, rows picked from there --
     // a copy per accepted row into the caller's pageable array costs ~15 us each, hundreds per call
@@ -280,21 +216,21 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
                         a.Tout, h_n[ch], T);
         // (the streaming posterior reads the accepted models where the kernel left them, in each chain's order)
         for (int i = 0; i < nd; ++i)
-            if (acc[(size_t)ch * a.Tout + i]) TRY(post_feed_batch_row(c, ch, b.xacc + ((size_t)ch * a.Tout + i) * M, c->stream));
+            if (acc[(size_t)ch * a.Tout + i]) TRY(post_feed_batch_row(c, ch, tl.xacc + ((size_t)ch * a.Tout + i) * M, c->stream));
         if (!x_out) continue;
         int last = -1;
         for (int i = 0; i < nd; ++i)
             if (acc[(size_t)ch * a.Tout + i]) last = i;
         if (last < 0) continue;
-        if (!want_rows && (size_t)Kout * M > b.h_xstage_n) {
-            if (b.h_xstage) HIPCHK(c, hipHostFree(b.h_xstage));
-            b.h_xstage = nullptr;
-            b.h_xstage_n = (size_t)std::max(Kout, 32) * M;
-            HIPCHK(c, hipHostMalloc((void **)&b.h_xstage, b.h_xstage_n * sizeof(double)));
+        if (!want_rows && (size_t)Kout * M > tl.h_xstage_n) {
+            if (tl.h_xstage) HIPCHK(c, hipHostFree(tl.h_xstage));
+            tl.h_xstage = nullptr;
+            tl.h_xstage_n = (size_t)std::max(Kout, 32) * M;
+            HIPCHK(c, hipHostMalloc((void **)&tl.h_xstage, tl.h_xstage_n * sizeof(double)));
         }
         want_rows = true;
         const size_t s0 = (size_t)ch * a.Tout;
-        HIPCHK(c, hipMemcpyAsync(b.h_xstage + s0 * M, b.xacc + s0 * M, (size_t)(last + 1) * M * sizeof(double), hipMemcpyDeviceToHost,
+        HIPCHK(c, hipMemcpyAsync(tl.h_xstage + s0 * M, tl.xacc + s0 * M, (size_t)(last + 1) * M * sizeof(double), hipMemcpyDeviceToHost,
                                  c->stream));
     }
     if (want_rows) HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -304,7 +240,7 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
             const size_t slot = (size_t)ch * a.Tout + i;
             accepted[slot] = acc[slot];
             memcpy(out5s + slot * 5, o5.data() + slot * 5, 5 * sizeof(double));
-            if (x_out && acc[slot]) memcpy(x_out + slot * M, b.h_xstage + slot * M, M * sizeof(double));
+            if (x_out && acc[slot]) memcpy(x_out + slot * M, tl.h_xstage + slot * M, M * sizeof(double));
         }
         if (n_started) n_started[ch] = h_n[ch];
         if (n_done) n_done[ch] = nd;
@@ -312,13 +248,7 @@ static int resbatch_launch(gh_ctx *c, int T, const int *L, const double *const *
         b.lost += h_n[48 + ch];
         b.chain_steps += h_n[80 + ch];
     }
-    if (c->prof) {
-        float t = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&t, r.ev0, r.ev1));
-        c->prof_ms_acc += t;
-        c->prof_res_evals += lock_steps;
-    }
-    return GH_OK;
+    return prof_launch_end(c, r.ev0, r.ev1, lock_steps);
 }
 
 // The kernel gave up: the trajectories in flight start again from their chains' current samples (their own

@@ -185,32 +185,19 @@ static int resident_launch(gh_ctx *c, const ResLaunch &q, int *accepted, double 
             HIPCHK(c, hipEventCreate(&r.ev1));
         }
     }
-    if (K > r.Kcap || !r.L) {
-        // grown rarely (the host batches a fixed number of trajectories per call); the old blocks
-        // stay in the context's allocation list until gh_destroy
-        const int cap = std::max(K, 32);
-        r.L = r.accepted = r.chain = nullptr;
-        r.p0s = r.us = r.out5s = r.xacc = nullptr;
-        TRY(dalloc(c, &r.L, (size_t)cap));
-        TRY(dalloc(c, &r.chain, (size_t)cap));
-        TRY(dalloc(c, &r.accepted, (size_t)cap));
-        TRY(dalloc(c, &r.p0s, (size_t)cap * M, false));
-        TRY(dalloc(c, &r.us, (size_t)cap));
-        TRY(dalloc(c, &r.out5s, (size_t)cap * 5));
-        TRY(dalloc(c, &r.xacc, (size_t)cap * M, false));
-        r.Kcap = cap;
-    }
+    TrajLists &tl = r.lists;
+    TRY(traj_lists_reserve(c, tl, K));
     int64_t steps = 0;
     for (int k = 0; k < K; ++k) steps += q.L[k];
     TRY(xg_prepare(c, r.xg, true, (uint64_t)steps + (uint64_t)q.C + 2, (uint64_t)K + (uint64_t)q.C + 2));
     // (K = 0: only the potential and gradient at the chains' current samples are evaluated)
     if (K > 0) {
-        HIPCHK(c, hipMemcpyAsync(r.p0s, q.p0s, (size_t)K * M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(r.us, q.us, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(r.L, q.L, (size_t)K * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(tl.p0s, q.p0s, (size_t)K * M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(tl.us, q.us, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(tl.L, q.L, (size_t)K * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
     if (q.chain_of && K > 0)
-        HIPCHK(c, hipMemcpyAsync(r.chain, q.chain_of, (size_t)K * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(tl.chain, q.chain_of, (size_t)K * sizeof(int), hipMemcpyHostToDevice, c->stream));
     ResArgs a{};
     a.G = c->G;
     a.Gl = c->wv.on ? c->wv.F : c->G;
@@ -238,21 +225,21 @@ static int resident_launch(gh_ctx *c, const ResLaunch &q, int *accepted, double 
     a.mwapr = c->mwapr;
     a.wm2 = c->wm2;
     a.C = q.C;
-    a.chain = q.chain_of ? r.chain : nullptr;
+    a.chain = q.chain_of ? tl.chain : nullptr;
     a.x_cur = q.x_dev;
     a.gcur_io = q.gcur_dev;
     a.ucur_io = q.ucur_dev;
     a.have_state = q.have_state;
     a.K = K;
-    a.L = r.L;
-    a.p0s = r.p0s;
-    a.us = r.us;
+    a.L = tl.L;
+    a.p0s = tl.p0s;
+    a.us = tl.us;
     a.dt = q.dt;
     a.stop_at_accepts = q.stop_at_accepts;
     a.accept_count0 = q.accept_count0;
-    a.accepted = r.accepted;
-    a.out5s = r.out5s;
-    a.xacc = q.want_x ? r.xacc : nullptr;
+    a.accepted = tl.accepted;
+    a.out5s = tl.out5s;
+    a.xacc = q.want_x ? tl.xacc : nullptr;
     a.n_run = r.n_run;
     a.slabg = r.slabg;
     a.xslabg = r.xslabg;
@@ -265,18 +252,18 @@ static int resident_launch(gh_ctx *c, const ResLaunch &q, int *accepted, double 
     a.tagE0 = r.xg.tagE;
     a.abort_w = r.xg.abort_w;
     a.dbg = r.dbg;
-    if (c->prof) HIPCHK(c, hipEventRecord(r.ev0, c->stream));
+    TRY(prof_launch_mark(c, r.ev0));
     // A plain launch: the grid was checked against the occupancy query in resident_plan (one
     // workgroup per CU by its LDS request), which is all hipLaunchCooperativeKernel would add;
     // residency itself is the same for both, and every wait inside the kernel is bounded.
     hipLaunchKernelGGL(resident_for(r.rc, r.ct), dim3(r.nwg), dim3(RES_THREADS), lds, c->stream, a);
     HIPCHK(c, hipGetLastError());
-    if (c->prof) HIPCHK(c, hipEventRecord(r.ev1, c->stream));
+    TRY(prof_launch_mark(c, r.ev1));
     TRY(xg_read(c, r.xg));
     HIPCHK(c, hipMemcpyAsync(h_run, r.n_run, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (K > 0) {
-        HIPCHK(c, hipMemcpyAsync(accepted, r.accepted, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out5s, r.out5s, (size_t)K * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(accepted, tl.accepted, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out5s, tl.out5s, (size_t)K * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (r.xg.seen[0] != 0u) {
@@ -296,13 +283,7 @@ static int resident_launch(gh_ctx *c, const ResLaunch &q, int *accepted, double 
     r.xg.tagE += (unsigned)h_run[2];
     r.launches += 1;
     r.evals += h_run[1];
-    if (c->prof) {
-        float t = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&t, r.ev0, r.ev1));
-        c->prof_ms_acc += t;
-        c->prof_res_evals += h_run[1];
-    }
-    return GH_OK;
+    return prof_launch_end(c, r.ev0, r.ev1, h_run[1]);
 }
 
 // K trajectories of the context's chain in one launch (same contract as gh_chain_run)
@@ -310,7 +291,6 @@ static int chain_run_resident(gh_ctx *c, int K, const int *L, const double *p0s,
                               int64_t stop_at_accepts, int64_t record_from, int *accepted, double *out5s,
                               double *x_out, int *n_run)
 {
-    gh_ctx::Resident &r = c->rs;
     const size_t M = (size_t)c->M;
     ResLaunch q;
     q.K = K;
@@ -325,21 +305,9 @@ static int chain_run_resident(gh_ctx *c, int K, const int *L, const double *p0s,
     int h_run[4] = {0, 0, 0, 0};
     TRY(resident_launch(c, q, accepted, out5s, h_run));
     *n_run = h_run[0];
-    for (int k = 0; k < h_run[0]; ++k) {
-        if (!accepted[k]) continue;
-        c->accept_count += 1;
-        if (c->ring && c->accept_count > record_from) {
-            ring_store_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
-                r.xacc + (size_t)k * M, c->weighted ? c->wm : nullptr, c->M,
-                c->ring + (size_t)c->ring_next * M);
-            c->ring_next = (c->ring_next + 1) % c->ring_K;
-            c->ring_count += 1;
-        }
-        TRY(post_feed_single(c, c, r.xacc + (size_t)k * M));
-        if (x_out)
-            HIPCHK(c, hipMemcpyAsync(x_out + (size_t)k * M, r.xacc + (size_t)k * M, M * sizeof(double),
-                                     hipMemcpyDeviceToHost, c->stream));
-    }
+    for (int k = 0; k < h_run[0]; ++k)
+        if (accepted[k])
+            TRY(chain_accept_row(c, c, c->rs.lists.xacc + (size_t)k * M, record_from, x_out ? x_out + (size_t)k * M : nullptr));
     // the per-launch state (d, r, scalars of the current sample) is behind x now: whoever reads it
     // next brings it up to date (chain_state_fresh) -- not every batch, 150 us of launches and a
     // round trip each

@@ -557,6 +557,68 @@ def test_shift_invariant_persistent_pass_gives_up_cleanly(G, orc, monkeypatch):
     t.close()
 
 
+def test_shift_invariant_persistent_pass_momentum_rows_in_pinned_memory(G):
+    """The chains of a batch on the harmonic store take turns in the persistent launch, and each launch's momentum rows
+    go through the same upload as the lock-step batch's (traj_upload, csrc/host_ctx.h): rows of a page-locked ring
+    from where they lie (the ring's wrap-around splits a run), rows anywhere else gathered first, a list mixing both
+    still the same list.  Same draws (RandomState(seed + chain)) three ways: identical decisions, potentials and
+    samples, bit for bit."""
+    from gravinv3dhmc_amd.inversion.rng import LegacyDraws
+    rng = np.random.default_rng(29)
+    mesh, lon, lat, h = _global_model(G, 10.0, 15.0, -1000000, 30000.0)
+    N, M = lon.size, mesh.size
+    C, T = 2, 6
+    outs = []
+    dobs = None
+    for mode in ("arrays", "ring", "mixed"):
+        t = G.Engine(N, M)
+        t.set_shift_invariant(True)
+        t.set_obs(lon, lat, h)
+        t.set_cells(mesh.cell_bounds(), 1, 1.6)
+        t.build_G()
+        wm = t.weight(0.5)
+        t.set_data(np.zeros(N))
+        t.set_reg("Damping", 0.05, 0.01, mesh.shape, 0.001 * wm)
+        if dobs is None:
+            d = t.forward(wm * rng.uniform(0.0, 0.4, M))
+            dobs = d + 0.02 * np.abs(d).max() * rng.normal(size=N)
+        t.set_data(dobs)
+        t.batch_init(np.stack([(0.1 + 0.05 * k) * wm for k in range(C)]), 0.0 * wm, 0.8 * wm)
+        draws = [LegacyDraws(M, (1, 5), 0.001, seed=70 + k) for k in range(C)]
+        if mode != "arrays":
+            for d in draws:
+                d.use_ring(t, T + 2)
+                d.take_ring(4)                       # (moves the head: the next 6 rows wrap around the ring's end)
+        else:
+            for d in draws:
+                d.take_block(4)
+        p0s, Ls, us = [], [], []
+        for d in draws:
+            if mode == "arrays":
+                Lk, pk, uk = d.take_block(T)
+                rows = [pk[i] for i in range(T)]
+            else:
+                got = d.take_ring(T)
+                Lk, uk = [g[0] for g in got], [g[2] for g in got]
+                rows = [g[1] for g in got]
+                if mode == "mixed":                  # every other row from ordinary memory, as arrays
+                    rows = [d.ring_row(g[3]).copy() if i % 2 else d.ring_row(g[3]) for i, g in enumerate(got)]
+            p0s.append(rows)
+            Ls.append(list(Lk))
+            us.append(list(uk))
+        acc, out5, xs = t.batch_run(p0s, 0.005, Ls, us, want_x=True)
+        st = t.shift_invariant_resident_stats()
+        assert st["launches"] == C and st["timeouts"] == 0, st  # (one persistent launch per chain)
+        outs.append((acc, out5, np.where(acc[:, :, None], xs, 0.0), np.stack([t.batch_get_x(k) for k in range(C)])))
+        for d in draws:
+            d.release()
+        t.close()
+    assert outs[0][0].any()
+    for o in outs[1:]:
+        for a, b in zip(outs[0], o):
+            assert np.array_equal(a, b)
+
+
 def test_one_degree_global_grid_on_the_streamed_harmonic_store(G, orc):
     """A 1-degree global grid (example/global/SetPMTS.txt's geometry family at 1 degree: 360 x 180 x 10 = 648 000 cells,
     361 x 181 = 65 341 observations; refused by every form of the store until round 4): the dense kernel would be 339 GB,

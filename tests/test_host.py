@@ -382,3 +382,48 @@ def test_bench_one_degree_workload_geometry():
         "x3_global_one_degree_shift_invariant": {"value": 2163.4, "roofline": {"frac": 0.5531}},
         "x3_global_one_degree_shift_invariant_8_chains": {"value": 2476.5, "roofline": {"frac": None}}}})
     assert cv["g1deg_si"] == [2163.4, 0.5531] and cv["g1deg_si8"] == [2476.5, None]
+
+
+_ROW = 8 * 8                                  # M = 8 doubles
+_B, _B2, _OUT = 0x10000000, 0x20000000, 0x50000000
+_BLOCK = (_B, 5 * _ROW)                       # a pinned block of 5 rows
+
+
+def _row_copy_plan(lib_path, rows, blocks, M=8):
+    """gh_debug_row_copy_plan on made-up addresses (nothing is read through them): the direct flag per row, the copy
+    runs as [k0, k1) pairs and the number of staged rows."""
+    lib = ctypes.CDLL(lib_path)
+    K, nb = len(rows), len(blocks)
+    direct = (ctypes.c_char * K)()
+    run_end = (ctypes.c_int * K)()
+    n_runs, n_staged = ctypes.c_int(-1), ctypes.c_int(-1)
+    rc = lib.gh_debug_row_copy_plan(
+        ctypes.c_int(K), (ctypes.c_void_p * K)(*rows), ctypes.c_int64(M), ctypes.c_int(nb),
+        (ctypes.c_void_p * max(nb, 1))(*[b for b, _ in blocks]), (ctypes.c_int64 * max(nb, 1))(*[n for _, n in blocks]),
+        direct, run_end, ctypes.byref(n_runs), ctypes.byref(n_staged))
+    assert rc == 0
+    ends = [0] + list(run_end[:n_runs.value])
+    return [ord(f) for f in direct], list(zip(ends[:-1], ends[1:])), n_staged.value
+
+
+@pytest.mark.parametrize("rows, blocks, direct, runs", [
+    ([_OUT], [_BLOCK], [0], [(0, 1)]),
+    ([_B + _ROW], [_BLOCK], [1], [(0, 1)]),
+    ([_B + k * _ROW for k in range(4)], [_BLOCK], [1, 1, 1, 1], [(0, 4)]),
+    ([_B + k * _ROW for k in (3, 4, 0, 1)], [_BLOCK], [1, 1, 1, 1], [(0, 2), (2, 4)]),
+    ([_B + k * _ROW for k in (0, 2, 4)], [_BLOCK], [1, 1, 1], [(0, 1), (1, 2), (2, 3)]),
+    ([_B, _OUT, _B + _ROW, _OUT + _ROW], [_BLOCK], [1, 0, 1, 0], [(0, 1), (1, 2), (2, 3), (3, 4)]),
+    ([_B, _OUT, _OUT + 1000 * _ROW, _B + _ROW], [_BLOCK], [1, 0, 0, 1], [(0, 1), (1, 3), (3, 4)]),
+    ([_B + 4 * _ROW + 8], [_BLOCK], [0], [(0, 1)]),
+    ([_B - 8], [_BLOCK], [0], [(0, 1)]),
+    ([_B + 4 * _ROW, _B2], [_BLOCK, (_B2, _ROW)], [1, 1], [(0, 1), (1, 2)]),
+], ids=["one_row_outside", "one_row_inside", "four_adjacent", "ring_wraps", "direct_not_adjacent", "alternating",
+        "staged_pair_between_direct", "last_double_past_the_end", "one_double_before_base", "two_blocks"])
+def test_momentum_row_copy_plan(built_lib, rows, blocks, direct, runs):
+    """Which momentum rows the persistent launches send from where they lie and how the copies are cut into runs
+    (csrc/host_rows.h): a row is direct iff all of it lies inside one pinned block; staged neighbours share a copy,
+    direct ones only where they are adjacent at their source (host code: no GPU call)."""
+    got_direct, got_runs, n_staged = _row_copy_plan(built_lib, rows, blocks)
+    assert got_direct == direct
+    assert (sum(got_direct), n_staged) == (sum(direct), len(rows) - sum(direct))
+    assert got_runs == runs
