@@ -876,6 +876,55 @@ int gh_shift_invariant_harmonic(const gh_ctx *c, int *on, int *n_freq, int64_t *
     return GH_OK;
 }
 
+int gh_shift_invariant_plan(gh_ctx *c, int32_t out[32])
+{
+    if (!c || !out) return fail(c, GH_ERR_ARG, "gh_shift_invariant_plan: null pointer");
+    for (int i = 0; i < 32; ++i) out[i] = 0;
+    if (!lonsym_on(c)) return GH_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const LonSymHost &h = *c->ls;
+    out[0] = h.harm ? 1 : h.wide ? 2 : 0;
+    out[1] = h.n;
+    out[2] = h.na;
+    out[3] = h.nc;
+    out[4] = h.nf;
+    // the direct correlations (lonsym.hip.h)
+    out[5] = h.W;
+    out[6] = h.KB;
+    out[7] = h.AG;
+    out[8] = h.thr;
+    out[9] = h.items;
+    out[10] = h.grid;
+    out[11] = (int32_t)h.lds;
+    out[12] = h.direct_ok ? 1 : 0;
+    out[13] = h.direct_code;
+    // the register form (lonsymh.hip.h)
+    out[14] = h.rp;
+    out[15] = h.rw;
+    out[16] = h.harm ? h.hgrid : 0;
+    out[17] = (int32_t)h.hlds;
+    // the streamed form (lonsymw.hip.h)
+    if (h.wide) {
+        out[18] = h.nfp;
+        out[19] = h.nf <= LW_THREADS ? 1 : h.nf <= 2 * LW_THREADS ? 2 : 3;
+        out[20] = h.wmirror ? 1 : 0;
+        out[21] = h.witems;
+        out[22] = h.wgrid;
+        out[23] = h.wrows;
+        out[24] = h.wparts;
+    }
+    out[25] = h.n_xslots;
+    out[26] = h.max_extra;
+    // the persistent launch (lonres.hip.h): planned now where it was not yet, as the first gh_chain_run would
+    const bool planned = lonres_plan(c);
+    out[27] = planned ? 1 : 0;
+    out[28] = planned && lonres_usable(c) ? 1 : 0;
+    out[29] = planned ? h.hgrid : 0;
+    out[30] = planned ? (int32_t)h.res.lds : 0;
+    out[31] = 1;
+    return GH_OK;
+}
+
 int gh_set_matrix_free_exact(gh_ctx *c, int exact)
 {
     if (!c) return GH_ERR_ARG;

@@ -14,6 +14,7 @@ struct LonSymHost {
     // the same store in the longitude-harmonic domain (lonsymh.hip.h): default where it applies
     bool harm = false;
     int nf = 0, hgrid = 0, rw = 1;   // rw: cell rows a workgroup of the pass works on at once
+    int rp = 1;                      // cell rows per workgroup of the pass (beyond 4 the launches loop over groups of rw rows)
     ghk::d2 *That = nullptr, *tw = nullptr, *Rhat = nullptr, *Dpart = nullptr;
     // the harmonic store as streaming passes over T^ (lonsymw.hip.h): grids beyond the register form's limits
     bool wide = false, direct_ok = false;
@@ -60,6 +61,7 @@ struct LonSymHost {
     size_t lds = 0;
     int grid = 0, items = 1, W = 8, thr = 1024;  // items: work items per wave, W: longitudes per work item (instantiation of the kernel)
     std::string why;  // why the geometry does not qualify (gh_last_error text)
+    int direct_code = 0;  // which of the direct form's four limits refuses it (1 .. 4 in the order tested, 0: none)
 };
 
 typedef void (*lonsym_fn_t)(LonSymGeom, SweepArgs, const double *);
@@ -216,11 +218,16 @@ static int lonsym_build(gh_ctx *c)
     h.lds = sizeof(double) * ((size_t)(2 * na + 1) * h.SW + steps + 8 + (size_t)h.AG * h.KB * h.W + 32);
     // (the direct correlations of lonsym.hip.h hold a cell row's table and the residual grid in LDS; grids beyond that
     // run on the streamed harmonic form, lonsymw.hip.h, which only needs the transforms' tables there)
-    const char *direct_why = nullptr;
-    if (n > LS_THREADS) direct_why = "more than 1024 longitudes per cell row";
-    else if (h.AG * h.KB > (h.thr / 64) * (h.W == 16 ? 1 : LS_MAXITEMS)) direct_why = "too many (class, longitude block) work items for one workgroup";
-    else if (h.lds > 160 * 1024 - 512) direct_why = "a cell row's table and the residual grid do not fit the LDS";
-    else if (na * n > (int64_t)8 * LS_THREADS) direct_why = "a cell row's table has more than 8192 entries";
+    static const char *const direct_whys[5] = {nullptr, "more than 1024 longitudes per cell row",
+                                               "too many (class, longitude block) work items for one workgroup",
+                                               "a cell row's table and the residual grid do not fit the LDS",
+                                               "a cell row's table has more than 8192 entries"};
+    h.direct_code = 0;
+    if (n > LS_THREADS) h.direct_code = 1;
+    else if (h.AG * h.KB > (h.thr / 64) * (h.W == 16 ? 1 : LS_MAXITEMS)) h.direct_code = 2;
+    else if (h.lds > 160 * 1024 - 512) h.direct_code = 3;
+    else if (na * n > (int64_t)8 * LS_THREADS) h.direct_code = 4;
+    const char *direct_why = direct_whys[h.direct_code];
     h.direct_ok = direct_why == nullptr;
     // (the multi-component store runs on the streamed harmonic form alone, whatever the switches say: the signed
     // mirror and the classes per block are written once, there)
@@ -394,8 +401,10 @@ static int lonsym_build(gh_ctx *c)
     h.harm = false;
     h.nf = (int)n / 2 + 1;
     // (one workgroup per CU at most -- its T^ rows and accumulators take the CU's registers -- every one with the
-    // same number of cell rows, up to four of them at once)
-    const int rp = (int)((nc + (int64_t)c->cus - 1) / (int64_t)c->cus);
+    // same number of cell rows, up to four of them at once; GRAVHMC_LONSYM_ROWS=r: at least r rows per workgroup --
+    // the layouts of a large grid on a small one, for the tests)
+    const int rp = std::max((int)((nc + (int64_t)c->cus - 1) / (int64_t)c->cus), env_int("GRAVHMC_LONSYM_ROWS", 1));
+    h.rp = rp;
     h.rw = std::min(rp, 4);
     h.hlds = lonsymh_lds_doubles((int)n, h.nf, (int)na, h.rw) * sizeof(double);
     const int force_wide = env_int("GRAVHMC_LONSYM_WIDE", 1) == 2;  // (2: the streamed form also where the register form applies)

@@ -382,6 +382,23 @@ class Engine(object):
         return {"on": bool(on.value), "form": {0: None, 1: "registers", 2: "streamed"}[on.value], "n_freq": nf.value,
                 "table_bytes": tb.value, "workgroups": wg.value}
 
+    def shift_invariant_plan(self):
+        """What build_G decided for the store (gh_shift_invariant_plan; read-only): the form, n / na / nc / nf, the direct
+        form's work items (W, KB, AG, thr, items, grid, lds, direct_ok, direct_refusal 0 .. 4), the register form's rows
+        per workgroup (rp, rw, hgrid, hlds), the streamed form's layout (nfp, pairs, wmirror, witems, wgrid, wrows, wparts;
+        0 where another form runs), the slots (n_xslots, max_extra) and the persistent launch (resident_planned,
+        resident_usable with the regulariser set now, nwg, resident_lds)."""
+        out = (C.c_int32 * 32)()
+        self._chk(self._lib.gh_shift_invariant_plan(self._h, out))
+        names = ("form", "n", "na", "nc", "nf", "W", "KB", "AG", "thr", "items", "grid", "lds", "direct_ok", "direct_refusal",
+                 "rp", "rw", "hgrid", "hlds", "nfp", "pairs", "wmirror", "witems", "wgrid", "wrows", "wparts", "n_xslots",
+                 "max_extra", "resident_planned", "resident_usable", "nwg", "resident_lds", "on")
+        d = dict(zip(names, (int(v) for v in out)))
+        d["form"] = ("direct", "registers", "streamed")[d["form"]] if d["on"] else None
+        for k in ("direct_ok", "wmirror", "resident_planned", "resident_usable", "on"):
+            d[k] = bool(d[k])
+        return d
+
     def set_translation_invariant(self, on=True):
         """Regular prism grids under gridded data (cells a full product of equal x- and y-intervals and layers,
         observations a full rectangle of the lattice of the cells' spacings at one height): keep the table

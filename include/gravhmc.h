@@ -527,6 +527,20 @@ int gh_shift_invariant_info(const gh_ctx *ctx, int *n_lon, int *n_classes, int *
 int gh_shift_invariant_resident_stats(gh_ctx *ctx, int *workgroups, int64_t *launches, int64_t *evaluations,
                                       int64_t *trajectories, int *timeouts);
 int gh_shift_invariant_harmonic(const gh_ctx *ctx, int *on, int *n_freq, int64_t *table_bytes, int *workgroups);
+/* What gh_build_G decided for the store (read-only, all zero while no table is resident; `Engine.shift_invariant_plan`).
+ * out: [0] form (0 direct correlations, 1 registers, 2 streamed), [1] longitudes n, [2] classes, [3] table rows, [4]
+ * frequencies; the direct form: [5] longitudes per work item W, [6] longitude blocks KB, [7] class groups AG, [8] threads,
+ * [9] work items per wave, [10] grid, [11] LDS bytes, [12] it could run, [13] which of its four limits refuses it (1 ..
+ * 4 in the order gh_build_G tests them, 0 none); the register form: [14] cell rows per workgroup rp, [15] rows a
+ * workgroup works on at once rw, [16] grid (0: not this form), [17] LDS bytes; the streamed form (0 where it is not
+ * chosen): [18] pitch of a row of T^, [19] pairs of longitudes per thread (1 .. 3: the instantiation of the sweep),
+ * [20] north-south mirror, [21] rows of T^ kept, [22] grid of the sweep, [23] rows per part of the forward product,
+ * [24] parts; the slots: [25] slots that hold several observations, [26] most observations a slot holds beyond its
+ * first; the persistent launch: [27] planned (the plan is made by this call where gh_chain_run has not made it yet),
+ * [28] usable with the regulariser set now, [29] its grid, [30] its LDS bytes; [31] 1 where the table exists.
+ * GRAVHMC_LONSYM_ROWS=r asks the register form for at least r cell rows per workgroup (the layouts of a large grid on a
+ * small one; read by gh_build_G). */
+int gh_shift_invariant_plan(gh_ctx *ctx, int32_t out[32]);
 /* Work of the matrix-free passes since gh_profile_enable(ctx, 1) (fused form only): entries
  * evaluated, 2x2x2 Gauss-Legendre leaves evaluated (tesseroids; = entries for prisms), launches.
  * Tesseroids: the pairs that need the reference's adaptive subdivision (_tesseroid_numba.py:135-157)
