@@ -178,6 +178,7 @@ PROTOTYPES = {
     "gh_translation_invariant_info": (C.c_int, [_ctx] + [C.POINTER(C.c_int)] * 6 + [C.POINTER(_i64), C.POINTER(C.c_double),
                                                                                    C.POINTER(C.c_double)]),
     "gh_translation_invariant_table": (C.c_int, [_ctx, _dp]),
+    "gh_translation_invariant_batch_plan": (C.c_int, [_ctx, C.POINTER(C.c_int32)]),
     "gh_lattice_detect": (C.c_int, [_i64, _dp, _dp, _dp, _i64, _dp] + [C.POINTER(C.c_int)] * 5),
 }
 

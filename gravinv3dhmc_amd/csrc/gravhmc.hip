@@ -16,6 +16,7 @@
 #include "lonsymw.hip.h"
 #include "fold.hip.h"
 #include "lattice.hip.h"
+#include "latbatch.hip.h"
 #include "poststream.hip.h"
 #include "tessmag.hip.h"
 
@@ -771,6 +772,8 @@ int gh_set_shift_invariant(gh_ctx *c, int enable)
 int gh_set_translation_invariant(gh_ctx *c, int enable)
 {
     if (!c) return GH_ERR_ARG;
+    if (enable < 0 || enable > 2)
+        return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: enable must be 0, 1 or 2 (2: the table that takes chain batches)");
     if (enable) TRY(dense_single_chain_refuse(c, "gh_set_translation_invariant"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: call before gh_build_G");
     if (lattice_multi(c))
@@ -791,7 +794,10 @@ int gh_set_translation_invariant(gh_ctx *c, int enable)
     if (c->lat) c->mf = c->lat->mf_before;
     delete c->lat;
     c->lat = nullptr;
-    if (enable) lattice_switch_on(c, false);
+    if (enable) {
+        lattice_switch_on(c, false);
+        c->lat->chains = enable == 2;
+    }
     return GH_OK;
 }
 
@@ -810,6 +816,35 @@ int gh_translation_invariant_info(const gh_ctx *c, int *on, int *nx, int *ny, in
     if (table_bytes) *table_bytes = (int64_t)(o ? c->lat->nb : 1) * g.nz * g.U * g.V * (int64_t)sizeof(double);
     if (max_dev) *max_dev = o ? c->lat->max_dev : 0.0;
     if (build_ms) *build_ms = o ? c->lat->build_ms : 0.0;
+    return GH_OK;
+}
+
+int gh_translation_invariant_batch_plan(gh_ctx *c, int32_t out[24])
+{
+    if (!c || !out) return fail(c, GH_ERR_ARG, "gh_translation_invariant_batch_plan: null pointer");
+    for (int i = 0; i < 24; ++i) out[i] = 0;
+    if (!lattice_on(c) || !lattice_chains(c)) return GH_OK;
+    LatticeHost &h = *c->lat;
+    const bool fits = latb_plan_make(c);  // (arithmetic alone: the context's last error text stays)
+    const ghk::LatbPlan *pl[2] = {&h.badj, &h.bfwd};
+    out[0] = 1;
+    out[1] = fits ? 1 : 0;
+    out[2] = ghk::LATB_TR;
+    out[3] = ghk::LATB_RW;
+    out[4] = ghk::LATB_NT;
+    out[5] = ghk::LATB_MAX_CHUNKS;
+    out[6] = c->cus;
+    for (int q = 0; q < 2; ++q) {
+        out[7 + 6 * q] = pl[q]->ntiles;
+        out[8 + 6 * q] = pl[q]->FT;
+        out[9 + 6 * q] = pl[q]->WT;
+        out[10 + 6 * q] = pl[q]->WL;
+        out[11 + 6 * q] = q ? h.bgx_fwd : h.bgx_adj;
+        out[12 + 6 * q] = (int32_t)std::min<size_t>(q ? h.blds_fwd : h.blds_adj, (size_t)INT32_MAX);
+    }
+    out[19] = h.bfwd.lpc;
+    out[20] = h.bchunks;
+    out[21] = h.bgx_adj * h.g.nz;
     return GH_OK;
 }
 
@@ -1929,16 +1964,20 @@ int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const 
 {
     if (!c || !x0s || !low || !high) return fail(c, GH_ERR_ARG, "gh_batch_init: null pointer");
     TRY(dense_single_chain_refuse(c, "gh_batch_init"));
-    TRY(lattice_refuse(c, "gh_batch_init", "single chain"));
+    TRY(lattice_batch_refuse(c, "gh_batch_init"));
     if (C < 1 || C > CB) return fail(c, GH_ERR_ARG, "gh_batch_init: 1..16 chains per batch");
     TRY(need(c, c->have_G && c->have_data && c->have_reg,
              "gh_batch_init: needs the kernel (gh_build_G / gh_upload_G), gh_set_data and gh_set_reg"));
     if (c->sh.kind != 0)
         return fail(c, GH_ERR_UNSUPPORTED, "batched chains run on the unsharded kernel only");
-    if (c->mf && c->cell_kind == GH_CELL_PRISM_TF)
+    // (the translation-invariant table serves gz, components and the total field alike: a context that takes batches on
+    // it passes the three refusals below)
+    const bool on_table = lattice_chains(c) && lattice_on(c);
+    if (on_table) TRY(latb_plan(c, "gh_batch_init"));  // (an extent the batch tile cannot hold: refused before anything is made)
+    if (c->mf && !on_table && c->cell_kind == GH_CELL_PRISM_TF)
         return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of the magnetic field (total field, "
                                            "GH_CELL_PRISM_TF) are not supported: store the kernel or run single chains");
-    if (c->mf && c->cell_kind == GH_CELL_PRISM_COMP)
+    if (c->mf && !on_table && c->cell_kind == GH_CELL_PRISM_COMP)
         return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of a prism gravity component other "
                                            "than gz (GH_CELL_PRISM_COMP) are not supported: store the kernel or run "
                                            "single chains");
@@ -1991,7 +2030,7 @@ int gh_batch_trajectory(gh_ctx *c, const double *p0s, double dt, const int *L, c
 {
     if (!c || !p0s || !L || !us || !accepted || !out5s) return fail(c, GH_ERR_ARG, "gh_batch_trajectory: null pointer");
     TRY(dense_single_chain_refuse(c, "gh_batch_trajectory"));
-    TRY(lattice_refuse(c, "gh_batch_trajectory", "single chain"));
+    TRY(lattice_batch_refuse(c, "gh_batch_trajectory"));
     gh_ctx::Batch &b = c->bt;
     TRY(need(c, b.ready, "gh_batch_trajectory: call gh_batch_init first"));
     for (int k = 0; k < b.C; ++k)
@@ -2033,7 +2072,7 @@ int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const
     if (!c || T < 0 || (T > 0 && (!L || !p0s || !us)) || !accepted || !out5s || ((n_started == nullptr) != (n_done == nullptr)))
         return fail(c, GH_ERR_ARG, "gh_batch_run: bad arguments");
     TRY(dense_single_chain_refuse(c, "gh_batch_run"));
-    TRY(lattice_refuse(c, "gh_batch_run", "single chain"));
+    TRY(lattice_batch_refuse(c, "gh_batch_run"));
     if (T == 0 && !n_done) return fail(c, GH_ERR_ARG, "gh_batch_run: T = 0 (drain) needs n_started / n_done");
     gh_ctx::Batch &b = c->bt;
     TRY(need(c, b.ready, "gh_batch_run: call gh_batch_init first"));

@@ -343,6 +343,16 @@ static int batch_time_end(gh_ctx *c, bool timed)
 static int mfb_forward(gh_ctx *c, const double *X)
 {
     gh_ctx::Batch &b = c->bt;
+    if (lattice_on(c)) {
+        // the translation-invariant store: the table's batch passes (latbatch.hip.h), one slab row per chunk of layers
+        bool timed;
+        b.fus_fwd_of = nullptr;
+        TRY(batch_time_begin(c, timed));
+        latb_launch_forward(c, X);
+        TRY(batch_time_end(c, timed));
+        HIPCHK(c, hipGetLastError());
+        return GH_OK;
+    }
     int ranges = b.mfb_ranges;
     if (b.fus_fwd_of == X) {
         // the fused kernel that produced X left its forward partials in the slab already
@@ -383,7 +393,11 @@ static int batch_launch_adjoint(gh_ctx *c, BatchAdjArgs &a, bool fwd_follows)
     gh_ctx::Batch &b = c->bt;
     bool timed;
     b.fus_fwd_of = nullptr;
-    if (c->mf && b.fus_on && fwd_follows) {
+    if (lattice_on(c)) {
+        TRY(batch_time_begin(c, timed));
+        latb_launch_adjoint(c, a);
+        TRY(batch_time_end(c, timed));
+    } else if (c->mf && b.fus_on && fwd_follows) {
         if (b.mfb_near) {
             mfb_near_adjoint_kernel<<<dim3((unsigned)c->M), dim3(256), 0, c->stream>>>(
                 c->mf_near_ptr, c->mf_near_row, b.ndelta, c->M, a.Rt, b.Snear);
@@ -483,7 +497,9 @@ static int batch_alloc(gh_ctx *c)
     TRY(dalloc(c, &b.scal, CB * 4));
     TRY(dalloc(c, &b.stage, M16));
     const int64_t ntiles = (c->M + 15) / 16;
-    if (c->mf) {
+    if (lattice_on(c)) {
+        TRY(latb_alloc(c));
+    } else if (c->mf) {
         TRY(mfb_plan(c));
     } else {
         // forward: 512-row blocks x column blocks, about 4 workgroups per CU in total

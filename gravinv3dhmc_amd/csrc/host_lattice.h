@@ -167,6 +167,14 @@ struct LatticeHost {
     // the multi-component store on the table (gh_set_cells_multi_table): nb row blocks, one table each; else 1
     bool multi = false;
     int nb = 1;
+    // gh_set_translation_invariant(2): the table also takes chain batches (latbatch.hip.h).  Their partition is made
+    // by latb_plan on the built table: bt_state 0 not yet, 1 planned, -1 an extent the batch tile cannot hold
+    bool chains = false;
+    int bt_state = 0;
+    ghk::LatbPlan badj = {}, bfwd = {};
+    size_t blds_adj = 0, blds_fwd = 0;
+    int bgx_adj = 0, bgx_fwd = 0, bchunks = 0;
+    double *xl16 = nullptr, *rl16 = nullptr;
 };
 
 static bool lattice_on(const gh_ctx *c) { return c->lat && c->lat->on; }
@@ -199,6 +207,16 @@ static int lattice_refuse(gh_ctx *c, const char *who, const char *why)
 {
     if (c && c->lat) return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on %s (%s)", who, LATTICE_NAME, why);
     return GH_OK;
+}
+
+// The chain batch runs on the single-block table a context was asked for with gh_set_translation_invariant(2)
+static bool lattice_chains(const gh_ctx *c) { return c && c->lat && c->lat->chains && !c->lat->multi; }
+
+// gh_batch_init / gh_batch_trajectory / gh_batch_run: the store's refusal unless the context takes batches
+static int lattice_batch_refuse(gh_ctx *c, const char *who)
+{
+    if (lattice_chains(c)) return GH_OK;
+    return lattice_refuse(c, who, "single chain");
 }
 
 // The partition of a pass with NRo output rows of NFo outputs and input rows of NFip (padded) inputs
@@ -367,4 +385,103 @@ static int launch_lattice(gh_ctx *c, SweepArgs &a, const double *wm)
                            dim3(ghk::LAT_THREADS), h.lds_fwd, c->stream, g, h.fwd, a, wm, c->ld, bl);
     }
     return GH_OK;
+}
+
+// ------------------------------------------------------------------------ chain batches (latbatch.hip.h)
+
+// The partition of a batch pass with NFo outputs along the fast axis and input rows of NFip (padded) inputs
+static ghk::LatbPlan latb_pass_plan(int NFo, int NFip)
+{
+    ghk::LatbPlan p{};
+    p.ntiles = (NFo + 15) / 16;
+    p.FT = (p.ntiles + ghk::LATB_NT - 1) / ghk::LATB_NT;
+    p.WT = 16 * ((p.ntiles + p.FT - 1) / p.FT);
+    p.WL = NFip + p.WT;
+    p.lpc = 1;
+    return p;
+}
+
+constexpr size_t LATB_LDS_MAX = 160 * 1024;  // LDS of a workgroup on gfx950
+
+static size_t latb_lds_bytes(const ghk::LatbPlan &p, int NFip)
+{
+    return ((size_t)ghk::LATB_TR * (size_t)p.WL + (size_t)ghk::CB * (size_t)NFip) * sizeof(double);
+}
+
+// The partition of the two batch passes on the built table: arithmetic only, made once, nothing else of the context
+// touched.  The kernels have no static LDS, so a pass fits where its tile, 192 NFip + 64 WT bytes, is within the 160 KB
+// of a workgroup.  Returns whether both passes fit.
+static bool latb_plan_make(gh_ctx *c)
+{
+    LatticeHost &h = *c->lat;
+    const ghk::LatGeom &g = h.g;
+    if (h.bt_state == 0) {
+        h.badj = latb_pass_plan(g.ny, g.qyp);
+        h.bfwd = latb_pass_plan(g.qy, g.nyp);
+        h.blds_adj = latb_lds_bytes(h.badj, g.qyp);
+        h.blds_fwd = latb_lds_bytes(h.bfwd, g.nyp);
+        h.bgx_adj = (g.nx + ghk::LATB_TR - 1) / ghk::LATB_TR * h.badj.FT;
+        h.bgx_fwd = (g.px + ghk::LATB_TR - 1) / ghk::LATB_TR * h.bfwd.FT;
+        // forward: chunks of layers, one slab row each -- about four workgroups per CU, no more rows than layers
+        const int want = std::max(1, std::min(std::min(g.nz, ghk::LATB_MAX_CHUNKS), (4 * c->cus + h.bgx_fwd - 1) / h.bgx_fwd));
+        h.bfwd.lpc = (g.nz + want - 1) / want;
+        h.bchunks = (g.nz + h.bfwd.lpc - 1) / h.bfwd.lpc;
+        h.bt_state = (h.blds_adj > LATB_LDS_MAX || h.blds_fwd > LATB_LDS_MAX) ? -1 : 1;
+    }
+    return h.bt_state > 0;
+}
+
+// An extent the batch tile cannot hold: GH_ERR_UNSUPPORTED, whoever asks
+static int latb_plan(gh_ctx *c, const char *who)
+{
+    if (latb_plan_make(c)) return GH_OK;
+    const LatticeHost &h = *c->lat;
+    return fail(c, GH_ERR_UNSUPPORTED, "%s: chain batches on %s: %s (%d cells, %d observations along y: %zu bytes)", who,
+                LATTICE_NAME, "a row of the lattice is too long for the batch pass's LDS tile", h.g.ny, h.g.qy,
+                std::max(h.blds_adj, h.blds_fwd));
+}
+
+// batch_alloc of the store: the plan, the passes' LDS, the two gathered operands and what the schedules size by
+static int latb_alloc(gh_ctx *c)
+{
+    LatticeHost &h = *c->lat;
+    gh_ctx::Batch &b = c->bt;
+    const ghk::LatGeom &g = h.g;
+    TRY(latb_plan(c, "gh_batch_init"));
+    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<false>), h.blds_adj));
+    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<true>), h.blds_fwd));
+    TRY(dalloc(c, &h.xl16, (size_t)g.nz * (size_t)g.nx * (size_t)g.nyp * ghk::CB));  // (zeroed: the padding stays zero)
+    TRY(dalloc(c, &h.rl16, (size_t)g.px * (size_t)g.qyp * ghk::CB));
+    TRY(dalloc(c, &b.iw, (size_t)c->M));
+    b.n_waves = h.bgx_adj * g.nz;  // rows of pp_part: one per workgroup of the adjoint
+    b.n_colblocks = h.bchunks;
+    b.slab_live = h.bchunks;
+    b.cols_per_block = 0;
+    b.fus_on = false;
+    b.mfb_near = false;
+    return GH_OK;
+}
+
+// forward of all chains at X into the slab: gather + pass
+static void latb_launch_forward(gh_ctx *c, const double *X)
+{
+    const LatticeHost &h = *c->lat;
+    const ghk::LatGeom &g = h.g;
+    gh_ctx::Batch &b = c->bt;
+    const int64_t n16 = c->M * ghk::CB;
+    ghk::latb_gather_x_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, X, b.iw, h.xl16);
+    hipLaunchKernelGGL(ghk::latb_pass_kernel<true>, dim3((unsigned)h.bgx_fwd, (unsigned)h.bchunks), dim3(ghk::LATB_THREADS),
+                       h.blds_fwd, c->stream, g, h.bfwd, h.xl16, ghk::BatchAdjArgs{}, b.iw, b.slab, c->ld);
+    b.slab_live = h.bchunks;
+}
+
+// adjoint of all chains + the per-chain update: gather + pass
+static void latb_launch_adjoint(gh_ctx *c, const ghk::BatchAdjArgs &a)
+{
+    const LatticeHost &h = *c->lat;
+    const ghk::LatGeom &g = h.g;
+    const int64_t n16 = c->N * ghk::CB;
+    ghk::latb_gather_r_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, a.Rt, h.rl16);
+    hipLaunchKernelGGL(ghk::latb_pass_kernel<false>, dim3((unsigned)h.bgx_adj, (unsigned)g.nz), dim3(ghk::LATB_THREADS),
+                       h.blds_adj, c->stream, g, h.badj, h.rl16, a, c->bt.iw, (double *)nullptr, c->ld);
 }

@@ -1,0 +1,179 @@
+// Chain batches on the translation-invariant store (lattice.hip.h): 16 chains per read of the table (gfx950).
+//
+// The single-chain passes of the table are FMA-issue and LDS bound: a thread's 64 FMAs of a step take 24 doubles
+// from LDS, and a staged table value serves one chain.  With the chains of a batch as the third dimension the
+// correlation of one (layer, output row, input row)
+//     out[o][c] = sum_i row[i - o + const] in[i][c]                c = chain slot 0 .. 15
+// is a product of a Toeplitz matrix with a 16-column matrix, and v_mfma_f64_16x16x4 does it:
+//     A (16 outputs x 4 inputs)   the Toeplitz block of the staged table row: lane (m, kk) reads row[i0 + kk - o0 - m]
+//                                 -- one double at a per-lane address, 19 distinct consecutive doubles per wave
+//     B (4 inputs x 16 chains)    in[i0 + kk][c]: 64 contiguous doubles per wave
+// 2 LDS doubles per lane for 16 FMAs per lane without any reuse; a wave owns LATB_RW output rows x up to LATB_NT
+// tiles of 16 outputs and reuses B for all of them: 9 LDS doubles per 128 FMAs per lane (the single-chain pass: 48).
+// fp64 MFMA runs at the vector rate on this chip, so the gain is LDS traffic and issue slots: one MFMA
+// instruction per 1024 FMAs, no address arithmetic per chain.
+//
+// Partition (host_lattice.h: latb_plan), as lat_pass_kernel's: per (layer | chunk of layers, tile of LATB_TR output
+// rows, range of tiles of the fast axis), all input rows in turn.  Workgroup = 4 waves, wave w the output rows
+// row0 + 2 w, + 1; no sum over waves.  LDS per input row: the LATB_TR table rows of the (output row, input row)
+// pairs, WL = NFip + WT values each (WT = 16 x the most tiles a workgroup has), and the input row, NFip x 16.
+// Plain launches, no waits between workgroups.  Every sum runs in an order fixed by indices alone (layers, input
+// rows, inputs ascending) and column c of an MFMA result depends on column c of B alone: a chain's result does not
+// depend on what the other slots hold, and results are reproducible bit for bit.
+//
+// The adjoint ends with the batch's per-chain update: mfb_adjoint_kernel's arithmetic per (cell, chain), through
+// mfb_update.  Included after mfbatch.hip.h (rt_offset, mfb_update).
+#pragma once
+
+namespace ghk {
+
+constexpr int LATB_THREADS = 256;
+constexpr int LATB_RW = 2;              // output rows per wave
+constexpr int LATB_TR = 4 * LATB_RW;    // output rows per workgroup
+constexpr int LATB_NT = 4;              // tiles of 16 outputs per wave and output row, at most
+constexpr int LATB_MAX_CHUNKS = 32;     // forward: slab rows at most
+
+struct LatbPlan {
+    int ntiles;  // tiles of 16 outputs along the fast axis
+    int FT;      // workgroups along the fast axis: workgroup ft owns the tiles [ft ntiles / FT, (ft + 1) ntiles / FT)
+    int WT;      // 16 x the most tiles of a workgroup
+    int WL;      // staged values per table row: NFip + WT
+    int lpc;     // forward: layers per chunk (slab row); adjoint: 1
+};
+
+// X[M][16] (the caller's cell order) times iw -> xl16[nz][nx][nyp][16] (zero beyond ny), as mfb_forward_kernel scales X
+__global__ void __launch_bounds__(256) latb_gather_x_kernel(LatGeom l, const double *X, const double *iw, double *xl16)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t e = t >> 4;
+    const int c = (int)(t & 15);
+    if (e >= (int64_t)l.nz * l.nx * l.ny) return;
+    const int64_t row = e / l.ny;
+    const int b = (int)(e - row * l.ny);
+    const int64_t j = l.cell_of[e];
+    xl16[(row * l.nyp + b) * CB + c] = X[j * CB + c] * iw[j];
+}
+
+// Rt (patch-transposed residuals of the batch, the caller's observation order) -> rl16[px][qyp][16] (zero beyond qy)
+__global__ void __launch_bounds__(256) latb_gather_r_kernel(LatGeom l, const double *Rt, double *rl16)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t e = t >> 4;
+    const int c = (int)(t & 15);
+    if (e >= (int64_t)l.px * l.qy) return;
+    const int p = (int)(e / l.qy), q = (int)(e - (int64_t)p * l.qy);
+    rl16[((int64_t)p * l.qyp + q) * CB + c] = Rt[rt_offset(l.obs_of[e], c)];
+}
+
+// One pass over the table for all 16 chain slots.  FWD: in16 = xl16, blockIdx.y = chunk of pl.lpc layers,
+// slab[chunk][obs][16] takes the partial forward product (a: not read); else in16 = rl16, blockIdx.y = layer, and
+// the (cell, chain) pairs' update follows the dots (pp_part[(blockIdx.y * gridDim.x + blockIdx.x)][16]).
+// blockIdx.x = (tile of output rows) * pl.FT + range of tiles of the fast axis.
+// Dynamic LDS: (LATB_TR pl.WL + 16 NFip) doubles = 192 NFip + 64 pl.WT bytes, and no static LDS: what the plan checks
+// against the 160 KB of a workgroup is all the kernel asks for.
+template <bool FWD>
+__global__ void __launch_bounds__(LATB_THREADS)
+latb_pass_kernel(LatGeom g, LatbPlan pl, const double *__restrict__ in16, BatchAdjArgs a, const double *__restrict__ iw,
+                 double *__restrict__ slab, int64_t ld)
+{
+    extern __shared__ __attribute__((aligned(16))) double latb_lds[];  // (the kernel's only LDS: the plan's bytes are all of it)
+    const int NRo = FWD ? g.px : g.nx, NFo = FWD ? g.qy : g.ny;
+    const int NRi = FWD ? g.nx : g.px, NFip = FWD ? g.nyp : g.qyp;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int m = lane & 15, kk = lane >> 4;
+    const int rt = (int)(blockIdx.x / pl.FT), ft = (int)(blockIdx.x % pl.FT);
+    const int row0 = rt * LATB_TR;
+    const int t0 = ft * pl.ntiles / pl.FT, t1 = (ft + 1) * pl.ntiles / pl.FT;
+    const int nt = t1 - t0, ot0 = 16 * t0;
+    const int WT = pl.WT, WL = pl.WL;
+    double *tabs = latb_lds;
+    double *ins = tabs + LATB_TR * WL;
+    const int k0 = FWD ? (int)blockIdx.y * pl.lpc : (int)blockIdx.y;
+    const int k1 = FWD ? min(g.nz, k0 + pl.lpc) : k0 + 1;
+    const int nin = NFip * CB;
+
+    d4 acc[LATB_RW][LATB_NT];
+#pragma unroll
+    for (int r = 0; r < LATB_RW; ++r)
+#pragma unroll
+        for (int t = 0; t < LATB_NT; ++t) acc[r][t] = d4{0.0, 0.0, 0.0, 0.0};
+
+    // the lane's A operand of (output row r, tile t) at step i0: staged value i - o + ot0 + WT - 1 with i = i0 + kk,
+    // o = ot0 + 16 t + m
+    const double *abase = tabs + (w * LATB_RW) * WL + (kk - m + WT - 1);
+    for (int k = k0; k < k1; ++k) {
+        const double *Tk = g.T + (int64_t)k * g.U * g.V;
+        const double *inl = FWD ? in16 + (int64_t)k * g.nx * nin : in16;
+        for (int ir = 0; ir < NRi; ++ir) {
+            __syncthreads();  // (the previous input row's reads of tabs / ins)
+            // (wave w stages the table rows w, w + 4; a lane the values lane, lane + 64, ...)
+            for (int r = w; r < LATB_TR; r += 4) {
+                const int u = FWD ? (row0 + r) - ir + g.nx - 1 : ir - (row0 + r) + g.nx - 1;
+                const bool uok = u >= 0 && u < g.U;
+                const double *Tu = Tk + (int64_t)(uok ? u : 0) * g.V;
+                for (int wl = lane; wl < WL; wl += 64) {
+                    const int d = wl - ot0 - WT + 1;  // i - o
+                    const int v = (FWD ? -d : d) + g.ny - 1;
+                    tabs[r * WL + wl] = (uok && v >= 0 && v < g.V) ? Tu[v] : 0.0;
+                }
+            }
+            const double *inr = inl + (int64_t)ir * nin;
+            for (int e = tid; e < nin; e += LATB_THREADS) ins[e] = inr[e];
+            __syncthreads();
+            for (int i0 = 0; i0 < NFip; i0 += 4) {
+                const double bv = ins[i0 * CB + lane];  // in[i0 + kk][m]
+#pragma unroll
+                for (int r = 0; r < LATB_RW; ++r)
+#pragma unroll
+                    for (int t = 0; t < LATB_NT; ++t)
+                        if (t < nt) acc[r][t] = mfma_f64(abase[r * WL + i0 - 16 * t], bv, acc[r][t]);
+            }
+        }
+    }
+
+    // acc[r][t][q] of lane (m, kk): output row row0 + 2 w + r, output ot0 + 16 t + kk + 4 q, chain m
+    const int c = m;
+    double pp = 0.0;
+#pragma unroll
+    for (int r = 0; r < LATB_RW; ++r) {
+        const int orow = row0 + w * LATB_RW + r;
+#pragma unroll
+        for (int t = 0; t < LATB_NT; ++t) {
+            if (t >= nt || orow >= NRo) continue;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int o = ot0 + 16 * t + kk + 4 * q;
+                if (o >= NFo) continue;
+                if (FWD) {
+                    slab[((int64_t)blockIdx.y * ld + g.obs_of[(int64_t)orow * g.qy + o]) * CB + c] = acc[r][t][q];
+                } else {
+                    // (mfb_adjoint_kernel's arithmetic per cell and chain)
+                    const int64_t jc = g.cell_of[((int64_t)k0 * g.nx + orow) * g.ny + o];
+                    const int64_t idx = jc * CB + c;
+                    double s = acc[r][t][q];
+                    s = s * iw[jc];
+                    (void)mfb_update(a, idx, jc, c, 2.0 * s + (a.GREG ? a.GREG[idx] : 0.0), true, pp);
+                }
+            }
+        }
+    }
+    if (!FWD) {
+        // the 16 lanes-of-a-chain of the workgroup, in wave and lane order, through the tile nobody reads any more
+        // (256 doubles; the smallest tile is 8 x 24 + 16 x 8 = 320)
+        double *ppred = latb_lds;
+        __syncthreads();  // (the other waves' last reads of tabs / ins)
+        ppred[w * 64 + lane] = pp;
+        __syncthreads();
+        if (a.pp_part && tid < CB && (a.phase[tid] == PH_PFIN || a.phase[tid] == PH_PFIN_SPEC)) {
+            double s = 0.0;
+#pragma unroll
+            for (int ww = 0; ww < 4; ++ww)
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) s += ppred[ww * 64 + gq * 16 + tid];
+            a.pp_part[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * CB + tid] = s;
+        }
+    }
+}
+
+}  // namespace ghk

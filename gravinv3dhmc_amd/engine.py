@@ -403,9 +403,29 @@ class Engine(object):
         """Regular prism grids under gridded data (cells a full product of equal x- and y-intervals and layers,
         observations a full rectangle of the lattice of the cells' spacings at one height): keep the table
         T[k][p - a + nx - 1][q - b + ny - 1] instead of G (gh_set_translation_invariant, csrc/lattice.hip.h);
-        build_G raises NotImplementedError with the reason if the geometry lacks the structure."""
-        self._chk(self._lib.gh_set_translation_invariant(self._h, 1 if on else 0))
+        build_G raises NotImplementedError with the reason if the geometry lacks the structure.  on="chains": the same
+        table, which also takes chain batches (batch_init, batch_trajectory, batch_run; csrc/latbatch.hip.h); any other
+        string is a ValueError."""
+        if isinstance(on, str) and on != "chains":
+            raise ValueError("set_translation_invariant: on must be True, False or \"chains\", not %r" % (on,))
+        chains = isinstance(on, str)
+        self._chk(self._lib.gh_set_translation_invariant(self._h, 2 if chains else (1 if on else 0)))
         self._translation_invariant = bool(on)
+        self._translation_invariant_chains = chains
+
+    def translation_invariant_batch_plan(self):
+        """What the batch passes of set_translation_invariant("chains") planned on the built table
+        (gh_translation_invariant_batch_plan; read-only): on, fits (False: batch_init refuses the extent), TR / RW (output
+        rows per workgroup / wave), NT (tiles of 16 outputs per wave at most), max_chunks, cus, and per pass
+        adj_* / fwd_*: ntiles, FT, WT, WL, grid, lds; lpc (layers per forward chunk), chunks (slab rows), pp_rows."""
+        out = (C.c_int32 * 24)()
+        self._chk(self._lib.gh_translation_invariant_batch_plan(self._h, out))
+        names = ("on", "fits", "TR", "RW", "NT", "max_chunks", "cus") + tuple(
+            "%s_%s" % (p, n) for p in ("adj", "fwd") for n in ("ntiles", "FT", "WT", "WL", "grid", "lds")) + (
+            "lpc", "chunks", "pp_rows")
+        d = dict(zip(names, (int(v) for v in out)))
+        d["on"], d["fits"] = bool(d["on"]), bool(d["fits"])
+        return d
 
     def translation_invariant_info(self):
         """on, the lattice's extents nx, ny, nz (cells) and px, qy (observations), table_bytes, and of the build:

@@ -355,6 +355,8 @@ def HMCSample(model, nsamples, ndraws, delta, Lrange,
 #: the stores HMCSampleBatch does not run, in the order they are asked for: (the attributes of the module's engine
 #: that tell the store, the store and its module).  A store of row blocks of magnetization vectors answers both
 #: `multi` and `mvi`: it comes before either.
+#: the row of the translation-invariant table: translation_invariant="chains" is the same store with batches
+_TABLE_ROW = (("_translation_invariant",), "the translation-invariant store (translation_invariant=True; single chain)")
 _NO_BATCH = (
     (("joint",), "the joint gravity-magnetic kernel (JointModule)"),
     (("tess_mag",), "the tesseroid magnetization store (TesseroidMagVectorModule)"),
@@ -362,8 +364,13 @@ _NO_BATCH = (
     (("multi", "mvi"), "the vector-data magnetization store (MagVectorModule with data=)"),
     (("multi",), "the multi-component store (MultiComponentModule)"),
     (("mvi",), "the magnetization-vector store (MagVectorModule)"),
-    (("_translation_invariant",), "the translation-invariant store (translation_invariant=True; single chain)"),
+    _TABLE_ROW,
 )
+
+
+def _table_takes_batches(engine, row):
+    """The one store of _NO_BATCH with a door: the table asked for with set_translation_invariant("chains")"""
+    return row is _TABLE_ROW and bool(getattr(engine, "_translation_invariant_chains", False))
 
 
 def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
@@ -389,7 +396,10 @@ def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,
     (Engine.posterior_stream_read, posterior.summarize_stream)."""
     if constraint != 'mandatory':
         raise ValueError("HMCSampleBatch supports the 'mandatory' boundary constraint only")
-    for attrs, name in _NO_BATCH:
+    for row in _NO_BATCH:
+        attrs, name = row
+        if _table_takes_batches(model._engine, row):
+            continue
         if all(getattr(model._engine, a, False) for a in attrs):
             raise NotImplementedError("HMCSampleBatch does not run %s: sample its chains one at a time with HMCSample"
                                       % name)

@@ -184,7 +184,8 @@ class GravMagModule(_Potential):
       matrix_free=True wherever the stored kernel would be needed, has no limit on N.  NotImplementedError from the
       constructor with the reason if the geometry lacks the structure (utils.regular puts n points L / (n - 1)
       apart, the cells are L / n wide), and with wavelet, shard, matrix_free, shift_invariant, mtopo and
-      HMCSampleBatch.
+      HMCSampleBatch.  translation_invariant="chains" is the same table with HMCSampleBatch: up to 16 chains share
+      every read of it (R-hat from the posterior stream), the other refusals unchanged.
     """
 
     def __init__(self, dobs, mrange, mspacing, obsurface, fixed=False, grav_fix=[],
@@ -282,7 +283,8 @@ class GravMagModule(_Potential):
                 raise NotImplementedError("the shift-invariant store is for spherical (tesseroid) models")
             eng.set_shift_invariant(True)
         if translation_invariant:
-            eng.set_translation_invariant(True)
+            # ("chains": the table that also takes HMCSampleBatch; any other string is the engine's ValueError)
+            eng.set_translation_invariant(translation_invariant if isinstance(translation_invariant, str) else True)
         self.matrix_free = bool(matrix_free or shift_invariant or translation_invariant)
         self.translation_invariant = bool(translation_invariant)
         eng.set_obs(self.lonobs, self.latobs, self.heightobs)

@@ -1014,8 +1014,24 @@ int gh_fold_pair_rows(int64_t N, const double *x, const double *y, const double 
  * entry with the dense assembly's entry function on the pair with the smallest (p, q) of its offset -- the entry
  * equals the dense store's entry of that pair bit for bit -- and compares it with the entry of the pair with the
  * largest (p, q): max_dev, as a fraction of the largest entry, refused above 1e-7.  Sums run in an order fixed by
- * indices: results are reproducible bit for bit and agree with the dense store's to ~1e-12. */
+ * indices: results are reproducible bit for bit and agree with the dense store's to ~1e-12.
+ * gh_set_translation_invariant(ctx, 2) asks for the same table under the same checks and also takes chain batches:
+ * gh_batch_init, gh_batch_trajectory and gh_batch_run then run on it, all 16 chain slots sharing every staged table
+ * value (csrc/latbatch.hip.h), for gz, components and the total field alike; 0 and 1 mean what they always did,
+ * every refusal text included; any other value is GH_ERR_ARG.  An extent along y the batch pass's LDS tile cannot hold
+ * -- the tile is 192 bytes per input of a row padded to 8 plus 64 per output of a workgroup's (at most 64), all the LDS
+ * the kernels use, within the 163 840 bytes of a workgroup: 832 cells under 832 observations are the last equal extents
+ * that fit, 848 the longest side at all -- is refused by gh_batch_init with GH_ERR_UNSUPPORTED; the wavelet forward, shards, gh_bscg_run and
+ * gh_upload_G stay refused, and so do batches on gh_set_cells_multi_table. */
 int gh_set_translation_invariant(gh_ctx *ctx, int enable);
+/* What the batch passes of a gh_set_translation_invariant(ctx, 2) context planned on the built table (arithmetic alone:
+ * the context's last error text is left as it is; all 0
+ * otherwise): out[0] on, [1] fits (0: gh_batch_init refuses the extent), [2] output rows per workgroup, [3] per wave,
+ * [4] tiles of 16 outputs per wave at most, [5] forward chunks at most, [6] compute units; then for the adjoint
+ * ([7]..[12]) and the forward ([13]..[18]): tiles of 16 outputs along y, workgroups along y, outputs per workgroup
+ * along y, staged values per table row, grid x, LDS bytes; [19] layers per forward chunk, [20] forward chunks (slab
+ * rows), [21] rows of the |p|^2 partials (workgroups of the adjoint). */
+int gh_translation_invariant_batch_plan(gh_ctx *ctx, int32_t out[24]);
 /* on: the table is built; the lattice's extents; table_bytes (all row blocks); max_dev (the largest of the blocks)
  * and build_ms of the build. */
 int gh_translation_invariant_info(const gh_ctx *ctx, int *on, int *nx, int *ny, int *nz, int *px, int *qy,
