@@ -20,6 +20,8 @@ CELL_PRISM_MVI = 7
 CELL_PRISM_MVI_DATA = 8
 CELL_TESS_MVI_DATA = 9
 CELL_TESSEROID_MULTI = 10
+#: gh_set_translation_invariant's modes beside 0 / 1 (GH_TABLE_*): the table that takes chain batches, the bootstrap batch
+TABLE_CHAINS, TABLE_REPLICATES = 2, 4
 #: the magnetic data components of prisms (GH_BCOMP_*, gh_set_cells_mvi_data / gh_b_result)
 BCOMP_TF, BCOMP_BX, BCOMP_BY, BCOMP_BZ = range(4)
 BCOMPONENTS = {"tf": BCOMP_TF, "bx": BCOMP_BX, "by": BCOMP_BY, "bz": BCOMP_BZ}

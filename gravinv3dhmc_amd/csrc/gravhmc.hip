@@ -772,8 +772,9 @@ int gh_set_shift_invariant(gh_ctx *c, int enable)
 int gh_set_translation_invariant(gh_ctx *c, int enable)
 {
     if (!c) return GH_ERR_ARG;
-    if (enable < 0 || enable > 2)
-        return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: enable must be 0, 1 or 2 (2: the table that takes chain batches)");
+    if (enable != 0 && enable != 1 && enable != GH_TABLE_CHAINS && enable != GH_TABLE_REPLICATES)
+        return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: enable must be 0, 1, 2 or 4 (2: the table that takes chain "
+                                   "batches; 4: the table that takes the bootstrap batch)");
     if (enable) TRY(dense_single_chain_refuse(c, "gh_set_translation_invariant"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: call before gh_build_G");
     if (lattice_multi(c))
@@ -796,7 +797,8 @@ int gh_set_translation_invariant(gh_ctx *c, int enable)
     c->lat = nullptr;
     if (enable) {
         lattice_switch_on(c, false);
-        c->lat->chains = enable == 2;
+        c->lat->chains = enable == GH_TABLE_CHAINS;
+        c->lat->reps = enable == GH_TABLE_REPLICATES;
     }
     return GH_OK;
 }
@@ -823,7 +825,7 @@ int gh_translation_invariant_batch_plan(gh_ctx *c, int32_t out[24])
 {
     if (!c || !out) return fail(c, GH_ERR_ARG, "gh_translation_invariant_batch_plan: null pointer");
     for (int i = 0; i < 24; ++i) out[i] = 0;
-    if (!lattice_on(c) || !lattice_chains(c)) return GH_OK;
+    if (!lattice_on(c) || !(lattice_chains(c) || lattice_reps(c))) return GH_OK;
     LatticeHost &h = *c->lat;
     const bool fits = latb_plan_make(c);  // (arithmetic alone: the context's last error text stays)
     const ghk::LatbPlan *pl[2] = {&h.badj, &h.bfwd};

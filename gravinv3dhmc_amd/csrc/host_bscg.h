@@ -4,9 +4,11 @@
 
 static const char *const BSCG_WHO = "the bootstrap batch (gh_bscg_run)";
 
-// Which contexts the bootstrap batch runs on: one GPU's dense, weighted store of one field.
+// Which contexts the bootstrap batch runs on: one GPU's dense, weighted store of one field, or the translation-invariant
+// table asked for with gh_set_translation_invariant(4) (lattice_reps: the table's batch passes, latbatch.hip.h).
 static int bscg_refuse(gh_ctx *c, int B, int maxk)
 {
+    const bool table = lattice_reps(c);
     // (a store of blocks names itself: each is dense and unsharded, but for the tesseroid forms on the table)
     const char *what = c->ls && tess_mag_store(c) ? "the tesseroid magnetization store on the shift-invariant table"
                                                   : store_of(c).rows_name;
@@ -14,9 +16,9 @@ static int bscg_refuse(gh_ctx *c, int B, int maxk)
         ;
     else if (c->ls)
         what = "a shift-invariant store";
-    else if (c->lat)
+    else if (c->lat && !table)
         what = LATTICE_NAME;
-    else if (c->mf)
+    else if (c->mf && !table)
         what = "a matrix-free context";
     else if (c->sh.kind != 0)
         what = "a sharded context";
@@ -25,19 +27,30 @@ static int bscg_refuse(gh_ctx *c, int B, int maxk)
     else if (c->wv.on)
         what = "a context with the wavelet-compressed forward (another operator)";
     if (what) return fail(c, GH_ERR_UNSUPPORTED, "%s runs on the dense stored kernel of one GPU, not on %s", BSCG_WHO, what);
-    if (!c->G) return fail(c, GH_ERR_UNSUPPORTED, "%s needs the dense stored kernel (gh_build_G / gh_upload_G)", BSCG_WHO);
+    if (table && !lattice_on(c)) return fail(c, GH_ERR_UNSUPPORTED, "%s needs the table of %s (gh_build_G)", BSCG_WHO, LATTICE_NAME);
+    if (!table && !c->G) return fail(c, GH_ERR_UNSUPPORTED, "%s needs the dense stored kernel (gh_build_G / gh_upload_G)", BSCG_WHO);
     if (!c->weighted)
         return fail(c, GH_ERR_UNSUPPORTED, "%s needs the weighted kernel: call gh_weight first (an unweighted store has no Wm)",
                     BSCG_WHO);
     if (B < 1 || B > CB) return fail(c, GH_ERR_UNSUPPORTED, "%s takes 1..16 replicates per group, got %d", BSCG_WHO, B);
     if (maxk < 2) return fail(c, GH_ERR_UNSUPPORTED, "%s needs maxk >= 2, got %d", BSCG_WHO, maxk);
+    if (table) TRY(latb_plan(c, "gh_bscg_run"));  // (an extent the batch tile cannot hold: refused before anything is made)
     return GH_OK;
 }
 
-// D = Aw.X of all slots: batch_forward_kernel and batch_reduce_kernel as the chain batch launches them
+// D = Aw.X of all slots: batch_forward_kernel and batch_reduce_kernel as the chain batch launches them; on the table
+// the batch forward over it (latb_pass_kernel<LATB_FWD>) and the reduction of its slab rows, one per chunk of layers
 static int bscg_forward(gh_ctx *c, const double *X, double *D)
 {
     gh_ctx::Batch &b = c->bt;
+    if (lattice_on(c)) {
+        latb_launch_forward(c, X);
+        const int64_t n16 = c->ld * CB;
+        batch_reduce_kernel<<<blocks256(n16), dim3(256), 0, c->stream>>>(b.slab, b.slab_live, n16, D);
+        HIPCHK(c, hipGetLastError());
+        c->bs.forward_sweeps += 1;
+        return GH_OK;
+    }
     BatchFwdArgs f;
     f.G = c->G;
     f.ld = c->ld;
@@ -69,7 +82,9 @@ static int bscg_run(gh_ctx *c, int B, const double *counts, const double *dobs, 
     TRY(batch_alloc(c));
     // (the adjoint's operand-ordered copy of G where HBM has room -- a second ld x M doubles that stay until
     // gh_destroy, also on a context whose chain batch runs on teams and would not make it; the same bits without)
-    TRY(batch_relayout(c));
+    // (the table has no G to copy; its passes divide by wm through b.iw, which gh_batch_init fills for the chains)
+    const bool table = lattice_on(c);
+    if (!table) TRY(batch_relayout(c));
     b.ready = false;         // the chain batch's state is overwritten
     b.run = gh_ctx::Batch::Run();
     c->rs.b_on = false;
@@ -98,6 +113,7 @@ static int bscg_run(gh_ctx *c, int B, const double *counts, const double *dobs, 
     HIPCHK(c, hipMemsetAsync(s.res, 0, sizeof(double) * 3 * (size_t)CB * (size_t)maxk, c->stream));
     batch_interleave_kernel<<<blocks256(N * CB), dim3(256), 0, c->stream>>>(s.crow, B, N, Cn);
     bscg_init_kernel<<<blocks256(M * CB), dim3(256), 0, c->stream>>>(s.mw0, c->wm, B, M, X, I, Iw, s.iw, s.st);
+    if (table) mfb_invw_kernel<<<blocks256(M), dim3(256), 0, c->stream>>>(c->wm, M, b.iw);
     HIPCHK(c, hipGetLastError());
 
     BscgResArgs ra;
@@ -129,6 +145,13 @@ static int bscg_run(gh_ctx *c, int B, const double *counts, const double *dobs, 
     aa.I = I;
     aa.nI2_part = b.pp_part;
     aa.n_waves = b.n_waves;
+    LatbCgArgs la;
+    la.X = X;
+    la.wm2 = c->wm2;
+    la.beta2 = beta2;
+    la.st = s.st;
+    la.I = I;
+    la.nI2_part = b.pp_part;
 
     // the initial evaluation: D = Aw.x0, data(x0), the residuals, alpha of iteration 0
     TRY(bscg_forward(c, X, D));
@@ -136,7 +159,11 @@ static int bscg_run(gh_ctx *c, int B, const double *counts, const double *dobs, 
     ra.n_mspart = 0;
     bscg_residual_kernel<<<dim3(CB), dim3(1024), 0, c->stream>>>(ra);
     for (int k = 0; k < maxk; ++k) {
-        bscg_adjoint_kernel<<<dim3((unsigned)(b.n_waves / 4)), dim3(256), 0, c->stream>>>(aa);
+        // (b.n_waves: on the table the adjoint's workgroups, bgx_adj nz, one row of partials each)
+        if (table)
+            latb_launch_cg_adjoint(c, Rt, la);
+        else
+            bscg_adjoint_kernel<<<dim3((unsigned)(b.n_waves / 4)), dim3(256), 0, c->stream>>>(aa);
         s.adjoint_sweeps += 1;
         bscg_mu_kernel<<<dim3(CB), dim3(1024), 0, c->stream>>>(b.pp_part, b.n_waves, k, s.st);
         bscg_direction_kernel<<<dim3((unsigned)s.nblk), dim3(256), 0, c->stream>>>(I, Iw, M, k, s.st, s.dirpart);

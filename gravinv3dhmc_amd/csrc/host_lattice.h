@@ -169,7 +169,8 @@ struct LatticeHost {
     int nb = 1;
     // gh_set_translation_invariant(2): the table also takes chain batches (latbatch.hip.h).  Their partition is made
     // by latb_plan on the built table: bt_state 0 not yet, 1 planned, -1 an extent the batch tile cannot hold
-    bool chains = false;
+    // gh_set_translation_invariant(4): the table also takes the bootstrap batch (gh_bscg_run) on the same plan
+    bool chains = false, reps = false;
     int bt_state = 0;
     ghk::LatbPlan badj = {}, bfwd = {};
     size_t blds_adj = 0, blds_fwd = 0;
@@ -211,6 +212,9 @@ static int lattice_refuse(gh_ctx *c, const char *who, const char *why)
 
 // The chain batch runs on the single-block table a context was asked for with gh_set_translation_invariant(2)
 static bool lattice_chains(const gh_ctx *c) { return c && c->lat && c->lat->chains && !c->lat->multi; }
+
+// The bootstrap batch runs on the single-block table a context was asked for with gh_set_translation_invariant(4)
+static bool lattice_reps(const gh_ctx *c) { return c && c->lat && c->lat->reps && !c->lat->multi; }
 
 // gh_batch_init / gh_batch_trajectory / gh_batch_run: the store's refusal unless the context takes batches
 static int lattice_batch_refuse(gh_ctx *c, const char *who)
@@ -436,8 +440,9 @@ static int latb_plan(gh_ctx *c, const char *who)
 {
     if (latb_plan_make(c)) return GH_OK;
     const LatticeHost &h = *c->lat;
-    return fail(c, GH_ERR_UNSUPPORTED, "%s: chain batches on %s: %s (%d cells, %d observations along y: %zu bytes)", who,
-                LATTICE_NAME, "a row of the lattice is too long for the batch pass's LDS tile", h.g.ny, h.g.qy,
+    return fail(c, GH_ERR_UNSUPPORTED, "%s: %s on %s: %s (%d cells, %d observations along y: %zu bytes)", who,
+                h.reps ? "the bootstrap batch" : "chain batches", LATTICE_NAME,
+                "a row of the lattice is too long for the batch pass's LDS tile", h.g.ny, h.g.qy,
                 std::max(h.blds_adj, h.blds_fwd));
 }
 
@@ -447,9 +452,10 @@ static int latb_alloc(gh_ctx *c)
     LatticeHost &h = *c->lat;
     gh_ctx::Batch &b = c->bt;
     const ghk::LatGeom &g = h.g;
-    TRY(latb_plan(c, "gh_batch_init"));
-    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<false>), h.blds_adj));
-    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<true>), h.blds_fwd));
+    TRY(latb_plan(c, h.reps ? "gh_bscg_run" : "gh_batch_init"));
+    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_ADJ>), h.blds_adj));
+    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_CG>), h.blds_adj));
+    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_FWD>), h.blds_fwd));
     TRY(dalloc(c, &h.xl16, (size_t)g.nz * (size_t)g.nx * (size_t)g.nyp * ghk::CB));  // (zeroed: the padding stays zero)
     TRY(dalloc(c, &h.rl16, (size_t)g.px * (size_t)g.qyp * ghk::CB));
     TRY(dalloc(c, &b.iw, (size_t)c->M));
@@ -470,7 +476,7 @@ static void latb_launch_forward(gh_ctx *c, const double *X)
     gh_ctx::Batch &b = c->bt;
     const int64_t n16 = c->M * ghk::CB;
     ghk::latb_gather_x_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, X, b.iw, h.xl16);
-    hipLaunchKernelGGL(ghk::latb_pass_kernel<true>, dim3((unsigned)h.bgx_fwd, (unsigned)h.bchunks), dim3(ghk::LATB_THREADS),
+    hipLaunchKernelGGL(ghk::latb_pass_kernel<ghk::LATB_FWD>, dim3((unsigned)h.bgx_fwd, (unsigned)h.bchunks), dim3(ghk::LATB_THREADS),
                        h.blds_fwd, c->stream, g, h.bfwd, h.xl16, ghk::BatchAdjArgs{}, b.iw, b.slab, c->ld);
     b.slab_live = h.bchunks;
 }
@@ -482,6 +488,17 @@ static void latb_launch_adjoint(gh_ctx *c, const ghk::BatchAdjArgs &a)
     const ghk::LatGeom &g = h.g;
     const int64_t n16 = c->N * ghk::CB;
     ghk::latb_gather_r_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, a.Rt, h.rl16);
-    hipLaunchKernelGGL(ghk::latb_pass_kernel<false>, dim3((unsigned)h.bgx_adj, (unsigned)g.nz), dim3(ghk::LATB_THREADS),
+    hipLaunchKernelGGL(ghk::latb_pass_kernel<ghk::LATB_ADJ>, dim3((unsigned)h.bgx_adj, (unsigned)g.nz), dim3(ghk::LATB_THREADS),
+                       h.blds_adj, c->stream, g, h.badj, h.rl16, a, c->bt.iw, (double *)nullptr, c->ld);
+}
+
+// adjoint of all replicates + the CG gradient and its |I|^2 partials (bgx_adj nz rows): gather + pass
+static void latb_launch_cg_adjoint(gh_ctx *c, const double *Rt, const ghk::LatbCgArgs &a)
+{
+    const LatticeHost &h = *c->lat;
+    const ghk::LatGeom &g = h.g;
+    const int64_t n16 = c->N * ghk::CB;
+    ghk::latb_gather_r_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, Rt, h.rl16);
+    hipLaunchKernelGGL(ghk::latb_pass_kernel<ghk::LATB_CG>, dim3((unsigned)h.bgx_adj, (unsigned)g.nz), dim3(ghk::LATB_THREADS),
                        h.blds_adj, c->stream, g, h.badj, h.rl16, a, c->bt.iw, (double *)nullptr, c->ld);
 }

@@ -23,6 +23,13 @@
 //
 // The adjoint ends with the batch's per-chain update: mfb_adjoint_kernel's arithmetic per (cell, chain), through
 // mfb_update.  Included after mfbatch.hip.h (rt_offset, mfb_update).
+//
+// A third form serves the bootstrap batch (bscg.hip.h) on a gh_set_translation_invariant replicates table: the same
+// adjoint over the table for 16 replicate slots, ending with bscg_adjoint_kernel's epilogue -- the CG gradient I and
+// the workgroup's partial of |I|^2 per slot -- instead of the leapfrog update.  It is an instantiation of the one
+// kernel: the epilogue's arguments are a type the form selects (LatbEpi), so that the chain forms' signature and
+// statements are what they were and their registers with them (the numbers of the three).  Included after
+// bscg.hip.h (BscgState, bscg_ms_grad).
 #pragma once
 
 namespace ghk {
@@ -40,6 +47,22 @@ struct LatbPlan {
     int WL;      // staged values per table row: NFip + WT
     int lpc;     // forward: layers per chunk (slab row); adjoint: 1
 };
+
+// The CG epilogue's arguments (bscg.hip.h: BscgAdjArgs without the dense operands)
+struct LatbCgArgs {
+    const double *X;       // M x 16
+    const double *wm2;     // M
+    double beta2;
+    const BscgState *st;
+    double *I;             // M x 16
+    double *nI2_part;      // (adjoint workgroups) x 16
+};
+
+// What follows the contraction.  LATB_FWD: the slab; LATB_ADJ: the chain batch's leapfrog update; LATB_CG: the
+// bootstrap batch's gradient
+enum { LATB_ADJ = 0, LATB_FWD = 1, LATB_CG = 2 };
+template <int FORM> struct LatbEpi { typedef BatchAdjArgs type; };
+template <> struct LatbEpi<LATB_CG> { typedef LatbCgArgs type; };
 
 // X[M][16] (the caller's cell order) times iw -> xl16[nz][nx][nyp][16] (zero beyond ny), as mfb_forward_kernel scales X
 __global__ void __launch_bounds__(256) latb_gather_x_kernel(LatGeom l, const double *X, const double *iw, double *xl16)
@@ -71,11 +94,16 @@ __global__ void __launch_bounds__(256) latb_gather_r_kernel(LatGeom l, const dou
 // blockIdx.x = (tile of output rows) * pl.FT + range of tiles of the fast axis.
 // Dynamic LDS: (LATB_TR pl.WL + 16 NFip) doubles = 192 NFip + 64 pl.WT bytes, and no static LDS: what the plan checks
 // against the 160 KB of a workgroup is all the kernel asks for.
-template <bool FWD>
+// FORM = LATB_CG: the adjoint's grid and operands; per (cell jc, slot c) with the correlation s
+//     I[jc][c] = 2 s iw[jc] + alpha_c g_MS(X[jc][c])          where st[c].live, else I keeps what it holds
+// and the workgroup's partial of |I|^2 per slot in row blockIdx.y * gridDim.x + blockIdx.x of a.nI2_part (zero for a
+// slot that is not live), summed as the chain form sums |p|^2: through the tile, waves, then the four lane groups.
+template <int FORM>
 __global__ void __launch_bounds__(LATB_THREADS)
-latb_pass_kernel(LatGeom g, LatbPlan pl, const double *__restrict__ in16, BatchAdjArgs a, const double *__restrict__ iw,
-                 double *__restrict__ slab, int64_t ld)
+latb_pass_kernel(LatGeom g, LatbPlan pl, const double *__restrict__ in16, typename LatbEpi<FORM>::type a,
+                 const double *__restrict__ iw, double *__restrict__ slab, int64_t ld)
 {
+    constexpr bool FWD = FORM == LATB_FWD;
     extern __shared__ __attribute__((aligned(16))) double latb_lds[];  // (the kernel's only LDS: the plan's bytes are all of it)
     const int NRo = FWD ? g.px : g.nx, NFo = FWD ? g.qy : g.ny;
     const int NRi = FWD ? g.nx : g.px, NFip = FWD ? g.nyp : g.qyp;
@@ -135,6 +163,13 @@ latb_pass_kernel(LatGeom g, LatbPlan pl, const double *__restrict__ in16, BatchA
     // acc[r][t][q] of lane (m, kk): output row row0 + 2 w + r, output ot0 + 16 t + kk + 4 q, chain m
     const int c = m;
     double pp = 0.0;
+    // (the CG form: the slot's state, read once)
+    bool live = false;
+    double alpha = 0.0;
+    if constexpr (FORM == LATB_CG) {
+        live = a.st[c].live != 0;
+        alpha = a.st[c].alpha;
+    }
 #pragma unroll
     for (int r = 0; r < LATB_RW; ++r) {
         const int orow = row0 + w * LATB_RW + r;
@@ -145,8 +180,18 @@ latb_pass_kernel(LatGeom g, LatbPlan pl, const double *__restrict__ in16, BatchA
             for (int q = 0; q < 4; ++q) {
                 const int o = ot0 + 16 * t + kk + 4 * q;
                 if (o >= NFo) continue;
-                if (FWD) {
+                if constexpr (FWD) {
                     slab[((int64_t)blockIdx.y * ld + g.obs_of[(int64_t)orow * g.qy + o]) * CB + c] = acc[r][t][q];
+                } else if constexpr (FORM == LATB_CG) {
+                    // (bscg_adjoint_kernel's arithmetic per cell and replicate; a slot that is not live keeps its I)
+                    if (!live) continue;
+                    const int64_t jc = g.cell_of[((int64_t)k0 * g.nx + orow) * g.ny + o];
+                    const int64_t idx = jc * CB + c;
+                    double s = acc[r][t][q];
+                    s = s * iw[jc];
+                    const double gI = 2.0 * s + alpha * bscg_ms_grad(a.X[idx], a.wm2[jc], a.beta2);
+                    a.I[idx] = gI;
+                    pp += gI * gI;
                 } else {
                     // (mfb_adjoint_kernel's arithmetic per cell and chain)
                     const int64_t jc = g.cell_of[((int64_t)k0 * g.nx + orow) * g.ny + o];
@@ -158,20 +203,29 @@ latb_pass_kernel(LatGeom g, LatbPlan pl, const double *__restrict__ in16, BatchA
             }
         }
     }
-    if (!FWD) {
+    if constexpr (!FWD) {
         // the 16 lanes-of-a-chain of the workgroup, in wave and lane order, through the tile nobody reads any more
         // (256 doubles; the smallest tile is 8 x 24 + 16 x 8 = 320)
         double *ppred = latb_lds;
         __syncthreads();  // (the other waves' last reads of tabs / ins)
         ppred[w * 64 + lane] = pp;
         __syncthreads();
-        if (a.pp_part && tid < CB && (a.phase[tid] == PH_PFIN || a.phase[tid] == PH_PFIN_SPEC)) {
+        bool wanted;
+        double *part;
+        if constexpr (FORM == LATB_CG) {
+            wanted = tid < CB;  // (every slot's row is written: bscg_mu_kernel reads the live ones)
+            part = a.nI2_part;
+        } else {
+            wanted = a.pp_part && tid < CB && (a.phase[tid] == PH_PFIN || a.phase[tid] == PH_PFIN_SPEC);
+            part = a.pp_part;
+        }
+        if (wanted) {
             double s = 0.0;
 #pragma unroll
             for (int ww = 0; ww < 4; ++ww)
 #pragma unroll
                 for (int gq = 0; gq < 4; ++gq) s += ppred[ww * 64 + gq * 16 + tid];
-            a.pp_part[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * CB + tid] = s;
+            part[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * CB + tid] = s;
         }
     }
 }

@@ -404,14 +404,17 @@ class Engine(object):
         observations a full rectangle of the lattice of the cells' spacings at one height): keep the table
         T[k][p - a + nx - 1][q - b + ny - 1] instead of G (gh_set_translation_invariant, csrc/lattice.hip.h);
         build_G raises NotImplementedError with the reason if the geometry lacks the structure.  on="chains": the same
-        table, which also takes chain batches (batch_init, batch_trajectory, batch_run; csrc/latbatch.hip.h); any other
-        string is a ValueError."""
-        if isinstance(on, str) and on != "chains":
-            raise ValueError("set_translation_invariant: on must be True, False or \"chains\", not %r" % (on,))
-        chains = isinstance(on, str)
-        self._chk(self._lib.gh_set_translation_invariant(self._h, 2 if chains else (1 if on else 0)))
+        table, which also takes chain batches (batch_init, batch_trajectory, batch_run; csrc/latbatch.hip.h);
+        on="replicates": the same table, which also takes the bootstrap batch (bscg_run) and refuses chain batches; any
+        other string is a ValueError."""
+        if isinstance(on, str) and on not in ("chains", "replicates"):
+            raise ValueError("set_translation_invariant: on must be True, False, \"chains\" or \"replicates\", not %r" % (on,))
+        chains, replicates = on == "chains", on == "replicates"
+        mode = _lib.TABLE_CHAINS if chains else _lib.TABLE_REPLICATES if replicates else (1 if on else 0)
+        self._chk(self._lib.gh_set_translation_invariant(self._h, mode))
         self._translation_invariant = bool(on)
         self._translation_invariant_chains = chains
+        self._translation_invariant_replicates = replicates
 
     def translation_invariant_batch_plan(self):
         """What the batch passes of set_translation_invariant("chains") planned on the built table

@@ -18,14 +18,34 @@ from .. import _lib, mesher
 from ..engine import DeviceMatrix, Engine
 
 
+_TABLE = "the translation-invariant store (translation_invariant=True)"
+
+
+def _table_refuse(wavelet, topography, spherical=False):
+    """What the translation-invariant store does not combine with, before any device work (GravMagModule's refusals)"""
+    if spherical:
+        raise NotImplementedError(_TABLE + " is for cartesian (prism) models")
+    for on, why in ((wavelet in ('1D', '3D'), "wavelet: the compressor's rows need the stored kernel"),
+                    (bool(topography), "a topography: a carved mesh is not a full regular product of cells")):
+        if on:
+            raise NotImplementedError(_TABLE + " does not combine with " + why)
+
+
 def _diag(values):
     row = np.arange(0, values.shape[0])
     return coo_matrix((values, (row, row))).tocsr()
 
 
 class ConjugateGradient(object):
+    """translation_invariant=True: a regular prism mesh under gridded data at one height keeps the translation-invariant
+    table instead of the kernel (Engine.set_translation_invariant; tens of MB where the dense store takes tens of GB);
+    CG runs on the table's single-vector passes, translation_invariant_info() reports the table.  It does not combine
+    with wavelet, a topography or coordinate="spherical" (NotImplementedError); a geometry without the structure is
+    refused by the build with the detection's reason."""
+
     def __init__(self, dobs, mrange, mspacing, obsurface, mratio=1, njobs=1, coordinate="cartesian",
-                 field="gravity", mangle=(90, 0), wavelet=False, device=0, verbose=True, **kwargs):
+                 field="gravity", mangle=(90, 0), wavelet=False, device=0, verbose=True, translation_invariant=False,
+                 **kwargs):
         self.dobs = np.asarray(dobs, dtype=np.float64)
         self.mrange, self.mspacing, self.mratio = mrange, mspacing, mratio
         self.lonobs, self.latobs, self.heightobs = obsurface[0], obsurface[1], obsurface[2]
@@ -40,6 +60,9 @@ class ConjugateGradient(object):
                              "from(gravity, magnetic)!")
         say("Calculating {} field in {} coordinate.".format(field, coordinate))
         spherical = coordinate == "spherical"
+        self.translation_invariant = bool(translation_invariant)
+        if translation_invariant:
+            _table_refuse(wavelet, kwargs, spherical)
         mesh = (mesher.TesseroidMesh if spherical else mesher.PrismMesh)(mrange, mspacing, mratio)
         for _key, value in kwargs.items():
             self.topocarve = True
@@ -50,6 +73,8 @@ class ConjugateGradient(object):
         say("Start of calculate kernel")
         start = time.time()
         eng = Engine(int(np.asarray(self.lonobs).size), bounds.shape[0], device=device)
+        if translation_invariant:
+            eng.set_translation_invariant(True)
         eng.set_obs(self.lonobs, self.latobs, self.heightobs)
         eng.set_cells(bounds, _lib.CELL_TESSEROID if spherical else _lib.CELL_PRISM, 1.6)
         eng.build_G()
@@ -62,6 +87,10 @@ class ConjugateGradient(object):
         if wavelet in ('1D', '3D'):
             say("Using {} wavelet to compress kernel.".format(wavelet))
             eng.compress_wavelet(3 if wavelet == '3D' else 1, self.mshape, 0.001, 2)
+
+    def translation_invariant_info(self):
+        """The engine's translation_invariant_info(): on, nx, ny, nz, px, qy, table_bytes, max_dev, build_ms."""
+        return self._engine.translation_invariant_info()
 
     def newkernel(self):
         """Column-norm weighting (reginv.py:120-149), on the device."""
@@ -195,12 +224,21 @@ class BootStrap(object):
         |Aw_s v - d_s|^2 = sum_r c_r (Aw[r].v - d[r])^2,   Aw_s^T (Aw_s v - d_s) = Aw^T (c * (Aw v - d))
     so the resident kernel is used as it is (no second matrix, no gather), with the count vector
     c applied to the N-vector between the forward and the adjoint sweep.  MS stabiliser of that
-    class: no prior, beta squared (reginv.py:599-629)."""
+    class: no prior, beta squared (reginv.py:599-629).
+
+    translation_invariant=True: a regular prism mesh under gridded data at one height keeps the translation-invariant
+    table instead of the kernel (Engine.set_translation_invariant("replicates")): CG runs on the table's single-vector
+    passes, CG_batch and BSCG(batch=B) on its 16-column passes (csrc/latbatch.hip.h), with neither the stored kernel
+    nor the batch's second copy of it.  It does not combine with wavelet or a topography (NotImplementedError); a
+    geometry without the structure is refused by the build with the detection's reason."""
 
     def __init__(self, mrange, mspacing, obsurface, dobs, boundary, samples=100, beta=0.01, maxk=100,
-                 mratio=1, njobs=1, wavelet=False, device=0, verbose=True, **kwargs):
+                 mratio=1, njobs=1, wavelet=False, device=0, verbose=True, translation_invariant=False, **kwargs):
         if wavelet not in (False, None, '1D', '3D'):
             raise ValueError("wavelet must be False, '1D' or '3D'")
+        self.translation_invariant = bool(translation_invariant)
+        if translation_invariant:
+            _table_refuse(wavelet, kwargs)
         self.mrange, self.mspacing, self.mratio = mrange, mspacing, mratio
         self.lonobs, self.latobs, self.heightobs = obsurface[0], obsurface[1], obsurface[2]
         self.boundary, self.samples, self.njobs = boundary, samples, njobs
@@ -216,6 +254,8 @@ class BootStrap(object):
         bounds = mesh.cell_bounds(active_only=True)
         start = time.time()
         eng = Engine(int(np.asarray(self.lonobs).size), bounds.shape[0], device=device)
+        if translation_invariant:
+            eng.set_translation_invariant("replicates")
         eng.set_obs(self.lonobs, self.latobs, self.heightobs)
         eng.set_cells(bounds, _lib.CELL_PRISM)
         eng.build_G()
@@ -235,6 +275,10 @@ class BootStrap(object):
             # gravmag/compressor1D.py / compressor3D.py on the weighted kernel (reginv.py:546-553)
             say("Using {} wavelet to compress kernel.".format(wavelet))
             eng.compress_wavelet(3 if wavelet == '3D' else 1, self.mshape, 0.001, 2)
+
+    def translation_invariant_info(self):
+        """The engine's translation_invariant_info(): on, nx, ny, nz, px, qy, table_bytes, max_dev, build_ms."""
+        return self._engine.translation_invariant_info()
 
     # terms of one replicate: `counts[r]` = how often observation r was drawn
     def data(self, mw, counts, dobs):

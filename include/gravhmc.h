@@ -748,7 +748,10 @@ int gh_batch_get_x(gh_ctx *ctx, int chain, double *x /* M */);
  * of M, unweighted; dmis / mmis, B rows of maxk - 1 (data(x_new) / N and MS(x_new) / M of iterations 1 ..), of which
  * n_entries[b] are valid; alpha, B rows of maxk, n_alpha[b] valid.
  * Runs on the dense, weighted store of one GPU and uses the chain batch's buffers (a gh_batch_* batch must be
- * initialised again afterwards).  GH_ERR_UNSUPPORTED, naming the bootstrap batch: a matrix-free, shift-invariant,
+ * initialised again afterwards), or on the weighted translation-invariant table of a
+ * gh_set_translation_invariant(ctx, GH_TABLE_REPLICATES) context, where a sweep is a pass over the table and no second
+ * copy of G is made.  GH_ERR_UNSUPPORTED, naming the bootstrap batch: a matrix-free, shift-invariant,
+ * translation-invariant (modes 1 and 2, gh_set_cells_multi_table),
  * folded, sharded, joint, multi-component or magnetization-vector context, one with the wavelet-compressed forward,
  * an unweighted store, B outside 1..16, maxk < 2; the context stays usable. */
 int gh_bscg_run(gh_ctx *ctx, int B, const double *counts /* B x N */, const double *dobs /* N */,
@@ -1008,8 +1011,8 @@ int gh_fold_pair_rows(int64_t N, const double *x, const double *y, const double 
  * G: a flavour of the matrix-free mode (G is never stored; gh_download_G, the folded store, the resident kernels
  * do not apply), with no limit on N.  It holds GH_CELL_PRISM, GH_CELL_PRISM_COMP and GH_CELL_PRISM_TF, and
  * GH_CELL_PRISM_MULTI by way of gh_set_cells_multi_table (one table per row block); tesseroids,
- * the other stores of blocks, the wavelet compression, shards, the batches of chains, gh_bscg_run and gh_upload_G are
- * refused (GH_ERR_UNSUPPORTED), a combination with gh_set_matrix_free or gh_set_shift_invariant too (GH_ERR_ARG).
+ * the other stores of blocks, the wavelet compression, shards, the batches of chains, gh_bscg_run (but in mode
+ * GH_TABLE_REPLICATES, below) and gh_upload_G are refused (GH_ERR_UNSUPPORTED), a combination with gh_set_matrix_free or gh_set_shift_invariant too (GH_ERR_ARG).
  * gh_build_G detects the structure (GH_ERR_UNSUPPORTED with the reason where it is absent), evaluates every table
  * entry with the dense assembly's entry function on the pair with the smallest (p, q) of its offset -- the entry
  * equals the dense store's entry of that pair bit for bit -- and compares it with the entry of the pair with the
@@ -1022,9 +1025,19 @@ int gh_fold_pair_rows(int64_t N, const double *x, const double *y, const double 
  * -- the tile is 192 bytes per input of a row padded to 8 plus 64 per output of a workgroup's (at most 64), all the LDS
  * the kernels use, within the 163 840 bytes of a workgroup: 832 cells under 832 observations are the last equal extents
  * that fit, 848 the longest side at all -- is refused by gh_batch_init with GH_ERR_UNSUPPORTED; the wavelet forward, shards, gh_bscg_run and
- * gh_upload_G stay refused, and so do batches on gh_set_cells_multi_table. */
+ * gh_upload_G stay refused, and so do batches on gh_set_cells_multi_table.
+ * gh_set_translation_invariant(ctx, GH_TABLE_REPLICATES) asks for the same table under the same checks and also takes
+ * gh_bscg_run: the bootstrap batch's lock-step on the table's batch passes -- the 16-column forward as the chain batch
+ * runs it, and the 16-column adjoint ending with the CG gradient and its |I|^2 partials instead of the leapfrog update
+ * (csrc/latbatch.hip.h) -- 2 maxk + 1 forward and maxk adjoint passes over the table per group (gh_bscg_stats), for gz,
+ * components and the total field alike, with the results' bits independent of the slot.  gh_batch_* are refused on it
+ * with the store's single-chain refusal, the wavelet forward, shards and gh_upload_G as in modes 1 and 2; an extent the
+ * batch tile cannot hold is refused by gh_bscg_run (GH_ERR_UNSUPPORTED, the same reason and byte count), and the single
+ * vector passes run on it as in mode 1.  gh_bscg_run stays refused in modes 1 and 2 and on gh_set_cells_multi_table.
+ * The value is 4: 3 was GH_ERR_ARG before this mode existed and stays so, as does every value other than 0, 1, 2, 4. */
+enum { GH_TABLE_OFF = 0, GH_TABLE_SINGLE = 1, GH_TABLE_CHAINS = 2, GH_TABLE_REPLICATES = 4 };
 int gh_set_translation_invariant(gh_ctx *ctx, int enable);
-/* What the batch passes of a gh_set_translation_invariant(ctx, 2) context planned on the built table (arithmetic alone:
+/* What the batch passes of a gh_set_translation_invariant(ctx, 2) or (ctx, GH_TABLE_REPLICATES) context planned on the built table (arithmetic alone:
  * the context's last error text is left as it is; all 0
  * otherwise): out[0] on, [1] fits (0: gh_batch_init refuses the extent), [2] output rows per workgroup, [3] per wave,
  * [4] tiles of 16 outputs per wave at most, [5] forward chunks at most, [6] compute units; then for the adjoint
