@@ -62,6 +62,8 @@ PROTOTYPES = {
     "gh_amplitude_last": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
     "gh_set_cells_multi": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp]),
     "gh_set_cells_multi_table": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp]),
+    "gh_set_cells_multi_table_chains": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp]),
+    "gh_batch_block_means": (C.c_int, [_ctx, _dp]),
     "gh_set_cells_tess_multi": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
     "gh_multi_info": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp, _dp]),
     "gh_joint_std": (C.c_int, [_ctx, _dp]),

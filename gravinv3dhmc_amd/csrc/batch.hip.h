@@ -410,6 +410,76 @@ __global__ void __launch_bounds__(1024) batch_finish_kernel(BatchFinishArgs a)
     }
 }
 
+// The rows are nblk row blocks of Nb observations each (the multi-component store, N = nblk Nb), every one with a mean
+// of its own
+struct BatchFinishBlocksArgs {
+    BatchFinishArgs f;
+    int nblk;
+    int64_t Nb;
+    double *bmean;  // 16 x nblk: the blocks' means of the prediction, per chain
+};
+
+// chain c's mean of the Nb rows from i0 on, summed as batch_finish_kernel sums its N (all threads of the 1024 call it)
+__device__ __forceinline__ double batch_block_mean(const double *D, const double *gfix, int64_t i0, int64_t Nb, int c, double *red)
+{
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < Nb; i += 1024) s += D[(i0 + i) * CB + c] + (gfix ? gfix[i0 + i] : 0.0);
+    return block_allreduce_sum(s, red, 16) / (double)Nb;
+}
+
+// bmean[c][b] of the predictions D (ld x 16), as batch_finish_blocks_kernel forms them: one workgroup per chain
+__global__ void __launch_bounds__(1024) batch_block_means_kernel(const double *D, const double *gfix, int nblk, int64_t Nb,
+                                                                double *bmean)
+{
+    __shared__ double red[16];
+    const int c = blockIdx.x;
+    for (int b = 0; b < nblk; ++b) {
+        const double mean = batch_block_mean(D, gfix, (int64_t)b * Nb, Nb, c, red);
+        if (threadIdx.x == 0) bmean[c * nblk + b] = mean;
+    }
+}
+
+// batch_finish_kernel over row blocks: per chain the mean of every block's Nb rows (blocks ascending, each summed as
+// batch_finish_kernel sums its one), the residual (D - mean_b) - dobs_c of a row with the mean of the block the row
+// lies in -- a 16-row patch of Rt may hold rows of two blocks --, the data misfit over all rows, and scal with block
+// 0's mean.  One block: batch_finish_kernel's arithmetic in its order.
+__global__ void __launch_bounds__(1024) batch_finish_blocks_kernel(BatchFinishBlocksArgs ab)
+{
+    __shared__ double red[16];
+    __shared__ double mean_s[MULTI_MAX];
+    const BatchFinishArgs &a = ab.f;
+    const int c = blockIdx.x;
+    for (int b = 0; b < ab.nblk; ++b) {
+        const double mean = batch_block_mean(a.D, a.gfix, (int64_t)b * ab.Nb, ab.Nb, c, red);
+        if (threadIdx.x == 0) {
+            mean_s[b] = mean;
+            ab.bmean[c * ab.nblk + b] = mean;
+        }
+    }
+    __syncthreads();
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < a.ld; i += 1024) {
+        double ri = 0.0;
+        if (i < a.N) {
+            const double dinv = a.D[i * CB + c] + (a.gfix ? a.gfix[i] : 0.0);
+            ri = (dinv - mean_s[i / ab.Nb]) - a.dobs_c[i];
+            acc += ri * ri;
+        }
+        const int64_t p = i >> 4, q = i & 15;  // row q = 8 h + 2 k + t
+        a.Rt[(((p * 2 + (q >> 3)) * 4 + ((q & 7) >> 1)) * CB + c) * 2 + (q & 1)] = ri;
+    }
+    const double ud = block_allreduce_sum(acc, red, 16);
+    double rs = 0.0;
+    for (int t = threadIdx.x; t < a.n_regpart; t += 1024) rs += a.regpart[(int64_t)t * CB + c];
+    const double R = block_allreduce_sum(rs, red, 16);
+    if (threadIdx.x == 0) {
+        a.scal[c * 4 + 0] = ud;
+        a.scal[c * 4 + 1] = R;
+        a.scal[c * 4 + 2] = ud + a.alpha * R;
+        a.scal[c * 4 + 3] = mean_s[0];
+    }
+}
+
 // per-block, per-chain partial sums of P[j][c]^2 (block = 16 cells x 16 chains, grid-stride)
 __global__ void __launch_bounds__(256)
 batch_sumsq_kernel(const double *P, int64_t M, double *part)

@@ -275,6 +275,7 @@ struct BlockCells {
     // gh_set_cells_tess_mag_table, gh_set_cells_multi_table: onto the store's table -- the shift-invariant one of the
     // tesseroids, the translation-invariant one of the prisms -- in the same call (no limit on the rows)
     bool on_table;
+    bool chains = false;  // gh_set_cells_multi_table_chains: the prisms' table of blocks also takes chain batches
 };
 
 // The stores of blocks but the joint one, each in the order of its own checks: the component list, the column and row
@@ -325,7 +326,10 @@ static int set_block_cells(gh_ctx *c, int kind, const BlockCells &a)
     c->comp = s.comps == COMPS_GRAV ? a.comps[0] : GH_COMP_GZ;
     if (s.tess) c->ratio = a.ratios ? a.ratios[0] : a.ratio;
     c->have_cells = true;
-    if (a.on_table && !s.tess) lattice_switch_on(c, true);
+    if (a.on_table && !s.tess) {
+        lattice_switch_on(c, true);
+        c->lat->chains = a.chains;
+    }
     return a.on_table && s.tess ? gh_set_shift_invariant(c, 1) : GH_OK;
 }
 
@@ -433,6 +437,13 @@ int gh_set_cells_multi_table(gh_ctx *c, const double *bounds6, int ncomp, const 
 {
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_multi: null pointer");
     return set_block_cells(c, GH_CELL_PRISM_MULTI, {bounds6, nullptr, ncomp, comps, weights, nullptr, 0.0, nullptr, true});
+}
+
+// (gh_set_cells_multi_table's context, whose table also takes chain batches: latbatch.hip.h, the forms over row blocks)
+int gh_set_cells_multi_table_chains(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *weights)
+{
+    if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_multi: null pointer");
+    return set_block_cells(c, GH_CELL_PRISM_MULTI, {bounds6, nullptr, ncomp, comps, weights, nullptr, 0.0, nullptr, true, true});
 }
 
 int gh_set_cells_tess_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *ratios,
@@ -847,6 +858,7 @@ int gh_translation_invariant_batch_plan(gh_ctx *c, int32_t out[24])
     out[19] = h.bfwd.lpc;
     out[20] = h.bchunks;
     out[21] = h.bgx_adj * h.g.nz;
+    out[22] = h.multi ? h.nb : 0;  // (the table of blocks: the forward's grid is nb workgroups deep)
     return GH_OK;
 }
 
@@ -1965,7 +1977,7 @@ int gh_posterior_stream_free(gh_ctx *c)
 int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const double *high)
 {
     if (!c || !x0s || !low || !high) return fail(c, GH_ERR_ARG, "gh_batch_init: null pointer");
-    TRY(dense_single_chain_refuse(c, "gh_batch_init"));
+    TRY(dense_single_chain_refuse(c, "gh_batch_init"));  // (passes the table of blocks that takes batches)
     TRY(lattice_batch_refuse(c, "gh_batch_init"));
     if (C < 1 || C > CB) return fail(c, GH_ERR_ARG, "gh_batch_init: 1..16 chains per batch");
     TRY(need(c, c->have_G && c->have_data && c->have_reg,
@@ -1975,6 +1987,8 @@ int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const 
     // (the translation-invariant table serves gz, components and the total field alike: a context that takes batches on
     // it passes the three refusals below)
     const bool on_table = lattice_chains(c) && lattice_on(c);
+    if (lattice_multi_chains(c) && !on_table)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_batch_init: needs the table of %s (gh_build_G)", LATTICE_NAME);
     if (on_table) TRY(latb_plan(c, "gh_batch_init"));  // (an extent the batch tile cannot hold: refused before anything is made)
     if (c->mf && !on_table && c->cell_kind == GH_CELL_PRISM_TF)
         return fail(c, GH_ERR_UNSUPPORTED, "batched chains on a matrix-free kernel of the magnetic field (total field, "
@@ -2006,7 +2020,8 @@ int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const 
     gh_ctx::Resident &r = c->rs;
     r.b_on = false;
     c->bt.run = gh_ctx::Batch::Run();  // anything gh_batch_run left in flight is discarded
-    if (resident_usable(c) &&
+    // (the table of blocks: never the resident kernel, which knows one mean)
+    if (!lattice_multi_chains(c) && resident_usable(c) &&
         resident_lds_doubles(c->ld, r.cpw, C, r.lds_cols, r.split) * sizeof(double) <= (size_t)r.lds_max) {
         // small problem: the chains take turns inside the resident chain kernel (one launch per
         // round of trajectories, G loaded into LDS once for all of them) -- a sweep of a 30 MB G
@@ -2295,6 +2310,25 @@ int gh_batch_get_x(gh_ctx *c, int chain, double *x)
                                                                                            c->tmpM);
     HIPCHK(c, hipGetLastError());
     return d2h(c, x, c->tmpM, (size_t)c->M);
+}
+
+int gh_batch_block_means(gh_ctx *c, double *pred_mean)
+{
+    if (!c || !pred_mean) return fail(c, GH_ERR_ARG, "gh_batch_block_means: null pointer");
+    TRY(need(c, c->bt.ready, "gh_batch_block_means: call gh_batch_init first"));
+    if (!lattice_multi_chains(c) || !c->bt.bmean)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_batch_block_means: not a batch on a table of row blocks "
+                                           "(gh_set_cells_multi_table_chains)");
+    HIPCHK(c, hipSetDevice(c->device));
+    // (from the chains' current predictions, as the evaluation formed them: bt.bmean holds the last evaluation's, which
+    // may be a rejected proposal's)
+    const int nb = c->lat->nb;
+    TRY(dalloc(c, &c->bt.bmean_cur, (size_t)CB * (size_t)nb));
+    double *out = c->bt.bmean_cur;
+    batch_block_means_kernel<<<dim3(CB), dim3(1024), 0, c->stream>>>(c->bt.Dc, c->have_fix ? c->gfix : nullptr, nb,
+                                                                     store_points(c), out);
+    HIPCHK(c, hipGetLastError());
+    return d2h(c, pred_mean, out, (size_t)c->bt.C * (size_t)nb);
 }
 
 int gh_bscg_run(gh_ctx *c, int B, const double *counts, const double *dobs, const double *mw0, double rhomin, double rhomax,

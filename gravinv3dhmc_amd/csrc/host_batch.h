@@ -616,7 +616,17 @@ static int batch_evaluate(gh_ctx *c, const double *X, double *D, double *GREG, d
     fa.alpha = c->alpha;
     fa.Rt = Rt;
     fa.scal = scal ? scal : b.scal;
-    batch_finish_kernel<<<dim3(CB), dim3(1024), 0, c->stream>>>(fa);
+    if (lattice_multi(c)) {
+        // (the table of blocks: one mean per block, the means in a buffer of their own)
+        BatchFinishBlocksArgs fb;
+        fb.f = fa;
+        fb.nblk = c->lat->nb;
+        fb.Nb = store_points(c);
+        fb.bmean = b.bmean;
+        batch_finish_blocks_kernel<<<dim3(CB), dim3(1024), 0, c->stream>>>(fb);
+    } else {
+        batch_finish_kernel<<<dim3(CB), dim3(1024), 0, c->stream>>>(fa);
+    }
     HIPCHK(c, hipGetLastError());
     return GH_OK;
 }

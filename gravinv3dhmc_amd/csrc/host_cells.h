@@ -172,9 +172,12 @@ static int refuse_plain_cells(gh_ctx *c)
 // shift-invariant table, the prisms' multi-component store on the translation-invariant one: still one chain, no
 // other form.)
 static bool lattice_multi(const gh_ctx *c);  // host_lattice.h: the multi-component store set onto its table
+// ... with gh_set_cells_multi_table_chains: the table of blocks that takes chain batches.  Not a single-chain store;
+// what it does not run either, the table's own refusals name (lattice_refuse and its kin)
+static bool lattice_multi_chains(const gh_ctx *c);
 static int dense_single_chain_refuse(gh_ctx *c, const char *who)
 {
-    if (c && store_name(c))
+    if (c && store_name(c) && !lattice_multi_chains(c))
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on %s (%s, single chain)", who, store_name(c),
                     store_of(c).table != TABLE_NO ? "dense or shift-invariant"
                     : lattice_multi(c)            ? "dense or on the translation-invariant table"

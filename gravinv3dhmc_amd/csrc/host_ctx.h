@@ -263,6 +263,9 @@ struct gh_ctx {
         double *Xc = nullptr, *Rtc = nullptr, *GREGc = nullptr, *Dc = nullptr;   // current states
         double *Xw[2] = {nullptr, nullptr}, *Pw[2] = {nullptr, nullptr};
         double *Rtw = nullptr, *GREGw = nullptr, *Dw = nullptr, *scal = nullptr;
+        // the table of blocks: 16 x (row blocks) means of the last evaluation's predictions, per chain; of the current states'
+        // (gh_batch_block_means)
+        double *bmean = nullptr, *bmean_cur = nullptr;
         double *slab = nullptr, *regpart = nullptr, *pp_part = nullptr, *pp0_part = nullptr;
         double *stage = nullptr;  // C x M rows as the host passes them
         double *stage2 = nullptr; // second set of rows (gh_batch_run: next trajectories' momenta sent ahead)

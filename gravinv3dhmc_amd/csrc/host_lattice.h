@@ -170,6 +170,7 @@ struct LatticeHost {
     // gh_set_translation_invariant(2): the table also takes chain batches (latbatch.hip.h).  Their partition is made
     // by latb_plan on the built table: bt_state 0 not yet, 1 planned, -1 an extent the batch tile cannot hold
     // gh_set_translation_invariant(4): the table also takes the bootstrap batch (gh_bscg_run) on the same plan
+    // gh_set_cells_multi_table_chains: the table of blocks (multi) that also takes chain batches -- chains with multi
     bool chains = false, reps = false;
     int bt_state = 0;
     ghk::LatbPlan badj = {}, bfwd = {};
@@ -210,8 +211,11 @@ static int lattice_refuse(gh_ctx *c, const char *who, const char *why)
     return GH_OK;
 }
 
-// The chain batch runs on the single-block table a context was asked for with gh_set_translation_invariant(2)
-static bool lattice_chains(const gh_ctx *c) { return c && c->lat && c->lat->chains && !c->lat->multi; }
+// The chain batch runs on the single-block table a context was asked for with gh_set_translation_invariant(2), and on
+// the table of blocks asked for with gh_set_cells_multi_table_chains (the one call that sets chains on a multi table)
+static bool lattice_chains(const gh_ctx *c) { return c && c->lat && c->lat->chains; }
+// ... the latter
+static bool lattice_multi_chains(const gh_ctx *c) { return lattice_chains(c) && c->lat->multi; }
 
 // The bootstrap batch runs on the single-block table a context was asked for with gh_set_translation_invariant(4)
 static bool lattice_reps(const gh_ctx *c) { return c && c->lat && c->lat->reps && !c->lat->multi; }
@@ -427,7 +431,9 @@ static bool latb_plan_make(gh_ctx *c)
         h.bgx_adj = (g.nx + ghk::LATB_TR - 1) / ghk::LATB_TR * h.badj.FT;
         h.bgx_fwd = (g.px + ghk::LATB_TR - 1) / ghk::LATB_TR * h.bfwd.FT;
         // forward: chunks of layers, one slab row each -- about four workgroups per CU, no more rows than layers
-        const int want = std::max(1, std::min(std::min(g.nz, ghk::LATB_MAX_CHUNKS), (4 * c->cus + h.bgx_fwd - 1) / h.bgx_fwd));
+        // (row blocks: nb bgx_fwd workgroups per chunk)
+        const int per = h.nb * h.bgx_fwd;
+        const int want = std::max(1, std::min(std::min(g.nz, ghk::LATB_MAX_CHUNKS), (4 * c->cus + per - 1) / per));
         h.bfwd.lpc = (g.nz + want - 1) / want;
         h.bchunks = (g.nz + h.bfwd.lpc - 1) / h.bfwd.lpc;
         h.bt_state = (h.blds_adj > LATB_LDS_MAX || h.blds_fwd > LATB_LDS_MAX) ? -1 : 1;
@@ -456,8 +462,13 @@ static int latb_alloc(gh_ctx *c)
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_ADJ>), h.blds_adj));
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_CG>), h.blds_adj));
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_FWD>), h.blds_fwd));
+    if (h.multi) {
+        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_ADJ_MB>), h.blds_adj));
+        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_FWD_MB>), h.blds_fwd));
+        TRY(dalloc(c, &b.bmean, (size_t)ghk::CB * (size_t)h.nb));
+    }
     TRY(dalloc(c, &h.xl16, (size_t)g.nz * (size_t)g.nx * (size_t)g.nyp * ghk::CB));  // (zeroed: the padding stays zero)
-    TRY(dalloc(c, &h.rl16, (size_t)g.px * (size_t)g.qyp * ghk::CB));
+    TRY(dalloc(c, &h.rl16, (size_t)h.nb * (size_t)g.px * (size_t)g.qyp * ghk::CB));  // (row blocks: [b][px][qyp][16])
     TRY(dalloc(c, &b.iw, (size_t)c->M));
     b.n_waves = h.bgx_adj * g.nz;  // rows of pp_part: one per workgroup of the adjoint
     b.n_colblocks = h.bchunks;
@@ -476,8 +487,17 @@ static void latb_launch_forward(gh_ctx *c, const double *X)
     gh_ctx::Batch &b = c->bt;
     const int64_t n16 = c->M * ghk::CB;
     ghk::latb_gather_x_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, X, b.iw, h.xl16);
-    hipLaunchKernelGGL(ghk::latb_pass_kernel<ghk::LATB_FWD>, dim3((unsigned)h.bgx_fwd, (unsigned)h.bchunks), dim3(ghk::LATB_THREADS),
-                       h.blds_fwd, c->stream, g, h.bfwd, h.xl16, ghk::BatchAdjArgs{}, b.iw, b.slab, c->ld);
+    if (h.multi) {
+        // (row blocks: the block as the grid's third coordinate, under the one gather of X)
+        ghk::LatbBlockArgs ba{};
+        ba.bl = lattice_blocks(c);
+        hipLaunchKernelGGL(ghk::latb_pass_kernel<ghk::LATB_FWD_MB>, dim3((unsigned)h.bgx_fwd, (unsigned)h.bchunks, (unsigned)h.nb),
+                           dim3(ghk::LATB_THREADS), h.blds_fwd, c->stream, g, h.bfwd, h.xl16, ba, b.iw, b.slab, c->ld);
+    } else {
+        hipLaunchKernelGGL(ghk::latb_pass_kernel<ghk::LATB_FWD>, dim3((unsigned)h.bgx_fwd, (unsigned)h.bchunks),
+                           dim3(ghk::LATB_THREADS), h.blds_fwd, c->stream, g, h.bfwd, h.xl16, ghk::BatchAdjArgs{}, b.iw, b.slab,
+                           c->ld);
+    }
     b.slab_live = h.bchunks;
 }
 
@@ -487,6 +507,18 @@ static void latb_launch_adjoint(gh_ctx *c, const ghk::BatchAdjArgs &a)
     const LatticeHost &h = *c->lat;
     const ghk::LatGeom &g = h.g;
     const int64_t n16 = c->N * ghk::CB;
+    if (h.multi) {
+        // (row blocks: the single block's grid, the blocks in turn inside the kernel)
+        const ghk::LatBlocks bl = lattice_blocks(c);
+        ghk::latb_gather_r_blocks_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, bl, a.Rt, h.rl16);
+        ghk::LatbBlockArgs ba;
+        ba.a = a;
+        ba.bl = bl;
+        hipLaunchKernelGGL(ghk::latb_pass_kernel<ghk::LATB_ADJ_MB>, dim3((unsigned)h.bgx_adj, (unsigned)g.nz),
+                           dim3(ghk::LATB_THREADS), h.blds_adj, c->stream, g, h.badj, h.rl16, ba, c->bt.iw, (double *)nullptr,
+                           c->ld);
+        return;
+    }
     ghk::latb_gather_r_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, a.Rt, h.rl16);
     hipLaunchKernelGGL(ghk::latb_pass_kernel<ghk::LATB_ADJ>, dim3((unsigned)h.bgx_adj, (unsigned)g.nz), dim3(ghk::LATB_THREADS),
                        h.blds_adj, c->stream, g, h.badj, h.rl16, a, c->bt.iw, (double *)nullptr, c->ld);

@@ -30,6 +30,15 @@
 // kernel: the epilogue's arguments are a type the form selects (LatbEpi), so that the chain forms' signature and
 // statements are what they were and their registers with them (the numbers of the three).  Included after
 // bscg.hip.h (BscgState, bscg_ms_grad).
+//
+// Row blocks (the multi-component store on the table asked for with gh_set_cells_multi_table_chains; lattice.hip.h:
+// LatBlocks, nb tables T[b], block-major): two more instantiations of the one kernel, LATB_FWD_MB and LATB_ADJ_MB, added
+// the way the CG form was -- their arguments (LatbBlockArgs) are again the epilogue's type, and the three forms above
+// keep their signature, statements and registers (DESIGN 4.21, row "chains on blocks": the numbers of the five).  The forward takes the block as
+// blockIdx.z under one gather of X, contracts T[b] and writes slab[chunk][b Nb + obs][16] times w_b; the adjoint, on the
+// single block's grid, runs the input rows of block 0, 1, ... nb - 1 into the SAME accumulators -- rl16[b] (w_b r of
+// block b) against T[b] -- before the one update.  The blocks take turns in the tile: the LDS is the single block's.
+// Order of the sums: blocks, input rows, inputs ascending.
 #pragma once
 
 namespace ghk {
@@ -58,11 +67,23 @@ struct LatbCgArgs {
     double *nI2_part;      // (adjoint workgroups) x 16
 };
 
+// The chain batch's arguments on the table of row blocks (lattice.hip.h: LatBlocks): the leapfrog update's, and the blocks
+struct LatbBlockArgs {
+    BatchAdjArgs a;
+    LatBlocks bl;
+};
+
 // What follows the contraction.  LATB_FWD: the slab; LATB_ADJ: the chain batch's leapfrog update; LATB_CG: the
-// bootstrap batch's gradient
-enum { LATB_ADJ = 0, LATB_FWD = 1, LATB_CG = 2 };
+// bootstrap batch's gradient.  LATB_ADJ_MB, LATB_FWD_MB: the two chain forms over row blocks (below)
+enum { LATB_ADJ = 0, LATB_FWD = 1, LATB_CG = 2, LATB_ADJ_MB = 3, LATB_FWD_MB = 4 };
 template <int FORM> struct LatbEpi { typedef BatchAdjArgs type; };
 template <> struct LatbEpi<LATB_CG> { typedef LatbCgArgs type; };
+template <> struct LatbEpi<LATB_ADJ_MB> { typedef LatbBlockArgs type; };
+template <> struct LatbEpi<LATB_FWD_MB> { typedef LatbBlockArgs type; };
+
+// (the leapfrog update's arguments of a chain form)
+__device__ __forceinline__ const BatchAdjArgs &latb_update_args(const BatchAdjArgs &a) { return a; }
+__device__ __forceinline__ const BatchAdjArgs &latb_update_args(const LatbBlockArgs &a) { return a.a; }
 
 // X[M][16] (the caller's cell order) times iw -> xl16[nz][nx][nyp][16] (zero beyond ny), as mfb_forward_kernel scales X
 __global__ void __launch_bounds__(256) latb_gather_x_kernel(LatGeom l, const double *X, const double *iw, double *xl16)
@@ -88,6 +109,20 @@ __global__ void __launch_bounds__(256) latb_gather_r_kernel(LatGeom l, const dou
     rl16[((int64_t)p * l.qyp + q) * CB + c] = Rt[rt_offset(l.obs_of[e], c)];
 }
 
+// Row blocks: rl16[b][p][q][c] = w_b Rt[b Nb + obs_of[p, q]][c] (zero beyond qy)
+__global__ void __launch_bounds__(256) latb_gather_r_blocks_kernel(LatGeom l, LatBlocks bl, const double *Rt, double *rl16)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t e = t >> 4;
+    const int c = (int)(t & 15);
+    const int64_t PQ = (int64_t)l.px * l.qy;
+    if (e >= PQ * bl.n) return;
+    const int b = (int)(e / PQ);
+    const int64_t pq = e - (int64_t)b * PQ;
+    const int p = (int)(pq / l.qy), q = (int)(pq - (int64_t)p * l.qy);
+    rl16[(((int64_t)b * l.px + p) * l.qyp + q) * CB + c] = bl.w[b] * Rt[rt_offset(b * bl.Nb + l.obs_of[pq], c)];
+}
+
 // One pass over the table for all 16 chain slots.  FWD: in16 = xl16, blockIdx.y = chunk of pl.lpc layers,
 // slab[chunk][obs][16] takes the partial forward product (a: not read); else in16 = rl16, blockIdx.y = layer, and
 // the (cell, chain) pairs' update follows the dots (pp_part[(blockIdx.y * gridDim.x + blockIdx.x)][16]).
@@ -98,12 +133,16 @@ __global__ void __launch_bounds__(256) latb_gather_r_kernel(LatGeom l, const dou
 //     I[jc][c] = 2 s iw[jc] + alpha_c g_MS(X[jc][c])          where st[c].live, else I keeps what it holds
 // and the workgroup's partial of |I|^2 per slot in row blockIdx.y * gridDim.x + blockIdx.x of a.nI2_part (zero for a
 // slot that is not live), summed as the chain form sums |p|^2: through the tile, waves, then the four lane groups.
+// FORM = LATB_FWD_MB / LATB_ADJ_MB: the chain forms over the row blocks a.bl.  Forward: blockIdx.z = block b, T[b], outputs
+// to slab[chunk][b Nb + obs][16] times w_b; adjoint: in16 = rl16[nb][px][qyp][16], the input rows of every block in turn
+// against T[b], then the update (a.a).
 template <int FORM>
 __global__ void __launch_bounds__(LATB_THREADS)
 latb_pass_kernel(LatGeom g, LatbPlan pl, const double *__restrict__ in16, typename LatbEpi<FORM>::type a,
                  const double *__restrict__ iw, double *__restrict__ slab, int64_t ld)
 {
-    constexpr bool FWD = FORM == LATB_FWD;
+    constexpr bool FWD = FORM == LATB_FWD || FORM == LATB_FWD_MB;
+    constexpr bool MB = FORM == LATB_ADJ_MB || FORM == LATB_FWD_MB;
     extern __shared__ __attribute__((aligned(16))) double latb_lds[];  // (the kernel's only LDS: the plan's bytes are all of it)
     const int NRo = FWD ? g.px : g.nx, NFo = FWD ? g.qy : g.ny;
     const int NRi = FWD ? g.nx : g.px, NFip = FWD ? g.nyp : g.qyp;
@@ -127,12 +166,19 @@ latb_pass_kernel(LatGeom g, LatbPlan pl, const double *__restrict__ in16, typena
 #pragma unroll
         for (int t = 0; t < LATB_NT; ++t) acc[r][t] = d4{0.0, 0.0, 0.0, 0.0};
 
+    // (row blocks: the adjoint's blocks in turn, the forward's one block)
+    int b0 = 0, b1 = 1;
+    if constexpr (MB) {
+        b0 = FWD ? (int)blockIdx.z : 0;
+        b1 = FWD ? b0 + 1 : a.bl.n;
+    }
     // the lane's A operand of (output row r, tile t) at step i0: staged value i - o + ot0 + WT - 1 with i = i0 + kk,
     // o = ot0 + 16 t + m
     const double *abase = tabs + (w * LATB_RW) * WL + (kk - m + WT - 1);
-    for (int k = k0; k < k1; ++k) {
-        const double *Tk = g.T + (int64_t)k * g.U * g.V;
-        const double *inl = FWD ? in16 + (int64_t)k * g.nx * nin : in16;
+    for (int k = k0; k < k1; ++k)
+    for (int blk = b0; blk < b1; ++blk) {  // (one block but in the adjoint over row blocks: the loop's bounds are constants)
+        const double *Tk = g.T + (MB ? (int64_t)blk * g.nz + k : (int64_t)k) * g.U * g.V;
+        const double *inl = FWD ? in16 + (int64_t)k * g.nx * nin : MB ? in16 + (int64_t)blk * g.px * nin : in16;
         for (int ir = 0; ir < NRi; ++ir) {
             __syncthreads();  // (the previous input row's reads of tabs / ins)
             // (wave w stages the table rows w, w + 4; a lane the values lane, lane + 64, ...)
@@ -180,7 +226,10 @@ latb_pass_kernel(LatGeom g, LatbPlan pl, const double *__restrict__ in16, typena
             for (int q = 0; q < 4; ++q) {
                 const int o = ot0 + 16 * t + kk + 4 * q;
                 if (o >= NFo) continue;
-                if constexpr (FWD) {
+                if constexpr (FWD && MB) {
+                    slab[((int64_t)blockIdx.y * ld + b0 * a.bl.Nb + g.obs_of[(int64_t)orow * g.qy + o]) * CB + c] =
+                        acc[r][t][q] * a.bl.w[b0];
+                } else if constexpr (FWD) {
                     slab[((int64_t)blockIdx.y * ld + g.obs_of[(int64_t)orow * g.qy + o]) * CB + c] = acc[r][t][q];
                 } else if constexpr (FORM == LATB_CG) {
                     // (bscg_adjoint_kernel's arithmetic per cell and replicate; a slot that is not live keeps its I)
@@ -198,7 +247,8 @@ latb_pass_kernel(LatGeom g, LatbPlan pl, const double *__restrict__ in16, typena
                     const int64_t idx = jc * CB + c;
                     double s = acc[r][t][q];
                     s = s * iw[jc];
-                    (void)mfb_update(a, idx, jc, c, 2.0 * s + (a.GREG ? a.GREG[idx] : 0.0), true, pp);
+                    const BatchAdjArgs &ua = latb_update_args(a);
+                    (void)mfb_update(ua, idx, jc, c, 2.0 * s + (ua.GREG ? ua.GREG[idx] : 0.0), true, pp);
                 }
             }
         }
@@ -216,8 +266,9 @@ latb_pass_kernel(LatGeom g, LatbPlan pl, const double *__restrict__ in16, typena
             wanted = tid < CB;  // (every slot's row is written: bscg_mu_kernel reads the live ones)
             part = a.nI2_part;
         } else {
-            wanted = a.pp_part && tid < CB && (a.phase[tid] == PH_PFIN || a.phase[tid] == PH_PFIN_SPEC);
-            part = a.pp_part;
+            const BatchAdjArgs &ua = latb_update_args(a);
+            wanted = ua.pp_part && tid < CB && (ua.phase[tid] == PH_PFIN || ua.phase[tid] == PH_PFIN_SPEC);
+            part = ua.pp_part;
         }
         if (wanted) {
             double s = 0.0;

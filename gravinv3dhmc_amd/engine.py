@@ -188,15 +188,23 @@ class Engine(object):
         in row blocks of one store, block c with the data weight weights[c] > 0; call it before set_obs.
         translation_invariant=True (gh_set_cells_multi_table): one translation-invariant table per block instead of
         the dense store, no 16384-row limit; build_G raises NotImplementedError with the reason if the geometry lacks
-        the structure."""
+        the structure.  translation_invariant="chains" (gh_set_cells_multi_table_chains): the same tables, which also
+        take chain batches (batch_init, batch_trajectory, batch_run, batch_block_means; csrc/latbatch.hip.h); any other
+        string is a ValueError."""
+        if isinstance(translation_invariant, str) and translation_invariant != "chains":
+            raise ValueError("set_cells_multi: translation_invariant must be True, False or \"chains\", not %r"
+                             % (translation_invariant,))
+        chains = translation_invariant == "chains"
         b = f64(bounds6)
         if b.shape != (self.M, 6):
             raise ValueError("bounds table must be (M, 6)")
         comps, carr, w, _ = self._blocks(_lib.COMPONENTS, components, weights)
-        fn = self._lib.gh_set_cells_multi_table if translation_invariant else self._lib.gh_set_cells_multi
+        fn = self._lib.gh_set_cells_multi_table_chains if chains else \
+            self._lib.gh_set_cells_multi_table if translation_invariant else self._lib.gh_set_cells_multi
         self._chk(fn(self._h, ptr(b), len(comps), carr, ptr(w)))
         if translation_invariant:
             self._translation_invariant = True
+            self._translation_invariant_chains = chains
         self._set_store(_lib.CELL_PRISM_MULTI, rows=len(comps), table=True)
 
     def set_cells_tess_multi(self, bounds6, components, ratios, weights):
@@ -420,7 +428,9 @@ class Engine(object):
         """What the batch passes of set_translation_invariant("chains") planned on the built table
         (gh_translation_invariant_batch_plan; read-only): on, fits (False: batch_init refuses the extent), TR / RW (output
         rows per workgroup / wave), NT (tiles of 16 outputs per wave at most), max_chunks, cus, and per pass
-        adj_* / fwd_*: ntiles, FT, WT, WL, grid, lds; lpc (layers per forward chunk), chunks (slab rows), pp_rows."""
+        adj_* / fwd_*: ntiles, FT, WT, WL, grid, lds; lpc (layers per forward chunk), chunks (slab rows), pp_rows.  On
+        the tables of set_cells_multi(..., translation_invariant="chains") also blocks, the number of row blocks (the
+        forward's grid is that many workgroups deep)."""
         out = (C.c_int32 * 24)()
         self._chk(self._lib.gh_translation_invariant_batch_plan(self._h, out))
         names = ("on", "fits", "TR", "RW", "NT", "max_chunks", "cus") + tuple(
@@ -428,6 +438,8 @@ class Engine(object):
             "lpc", "chunks", "pp_rows")
         d = dict(zip(names, (int(v) for v in out)))
         d["on"], d["fits"] = bool(d["on"]), bool(d["fits"])
+        if out[22]:
+            d["blocks"] = int(out[22])
         return d
 
     def translation_invariant_info(self):
@@ -1030,6 +1042,13 @@ class Engine(object):
         return x
 
     # -- bootstrap replicates of the CG inversion in lock-step -------------------------
+    def batch_block_means(self):
+        """The means of the row blocks of the chains' current weighted predictions, (C, blocks), as the batch's
+        evaluation removes them (gh_batch_block_means): a batch on set_cells_multi(..., translation_invariant="chains")."""
+        out = np.zeros((16, max(self._store.rows, 1)))
+        self._chk(self._lib.gh_batch_block_means(self._h, ptr(out)))
+        return out[:self._batch_C].copy()
+
     def bscg_run(self, counts, dobs, mw0, rhomin, rhomax, beta2, q, maxk):
         """Up to 16 replicates of BootStrap.CG on one read of G per product (csrc/bscg.hip.h).  counts: (B, N) draw
         counts; dobs: N; mw0: the weighted start model.  Returns the unweighted models (B, M), the data and model

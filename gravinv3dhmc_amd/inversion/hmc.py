@@ -17,6 +17,7 @@ import sys
 import numpy as np
 from scipy.sparse import coo_matrix
 
+from .. import _lib
 from ..utils import write_rows_fixed8
 from .rng import LegacyDraws
 
@@ -357,20 +358,29 @@ def HMCSample(model, nsamples, ndraws, delta, Lrange,
 #: `multi` and `mvi`: it comes before either.
 #: the row of the translation-invariant table: translation_invariant="chains" is the same store with batches
 _TABLE_ROW = (("_translation_invariant",), "the translation-invariant store (translation_invariant=True; single chain)")
+#: the row of the prisms' multi-component store: on its tables asked for with translation_invariant="chains" it runs batches
+_MULTI_ROW = (("multi",), "the multi-component store (MultiComponentModule)")
 _NO_BATCH = (
     (("joint",), "the joint gravity-magnetic kernel (JointModule)"),
     (("tess_mag",), "the tesseroid magnetization store (TesseroidMagVectorModule)"),
     (("tess_multi",), "the tesseroid multi-component store (TesseroidMultiComponentModule)"),
     (("multi", "mvi"), "the vector-data magnetization store (MagVectorModule with data=)"),
-    (("multi",), "the multi-component store (MultiComponentModule)"),
+    _MULTI_ROW,
     (("mvi",), "the magnetization-vector store (MagVectorModule)"),
     _TABLE_ROW,
 )
 
 
 def _table_takes_batches(engine, row):
-    """The one store of _NO_BATCH with a door: the table asked for with set_translation_invariant("chains")"""
-    return row is _TABLE_ROW and bool(getattr(engine, "_translation_invariant_chains", False))
+    """The one store of _NO_BATCH with a door: the table asked for with set_translation_invariant("chains"), and -- the
+    multi-component store's own row with it -- the tables of set_cells_multi(..., translation_invariant="chains").  The
+    rows in front of these (the vector-data magnetization store answers `multi` too) have refused by then.  The
+    multi-component row opens for the engine whose store IS the prisms' multi-component store, not for the flag alone."""
+    if not getattr(engine, "_translation_invariant_chains", False):
+        return False
+    if row is _MULTI_ROW:
+        return getattr(getattr(engine, "_store", None), "kind", None) == _lib.CELL_PRISM_MULTI
+    return row is _TABLE_ROW
 
 
 def HMCSampleBatch(model, n_chains, nsamples, ndraws, delta, Lrange,

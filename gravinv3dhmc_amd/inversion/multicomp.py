@@ -52,6 +52,13 @@ class MultiComponentModule(_BlockStore):
     NotImplementedError with the detection's reason if the geometry lacks the structure, and -- naming the
     multi-component store and the translation-invariant table -- with mtopo, wavelet, matrix_free, shift_invariant,
     shard and coordinate="spherical".
+
+    translation_invariant="chains" is translation_invariant=True in all of this -- the same tables, refusals, forward,
+    block_means and translation_invariant_info -- and HMCSampleBatch runs on it as well: up to 16 chains share every
+    staged table value of every component (csrc/latbatch.hip.h, the forms over row blocks), so that one run leaves
+    R-hat across chains behind (posterior_stream=True).  translation_invariant_batch_plan() tells the partition, and
+    whether the extent along y fits the batch tile (832 cells under 832 stations at most; beyond it HMCSampleBatch
+    raises NotImplementedError and HMCSample still runs).  Any other string is a ValueError.
     """
     _props, _prop = 1, 'density'
     _names, _arg, _word, _none_weight = _lib.COMPONENTS, "components", "component", False
@@ -65,8 +72,11 @@ class MultiComponentModule(_BlockStore):
         n = int(np.asarray(obsurface[0]).size)
         dobs, w = self._block_data(components, dobs, weights, n)
         self._only_mtopo(kwargs)
+        if isinstance(translation_invariant, str) and translation_invariant != "chains":
+            raise ValueError("translation_invariant must be True, False or \"chains\", not %r" % (translation_invariant,))
         if translation_invariant:
             self.translation_invariant = True
+            self.translation_invariant_chains = translation_invariant == "chains"
             self._refuse_on_table(coordinate, wavelet, matrix_free, shift_invariant, shard, kwargs)
         else:
             if len(components) * n > 16384 and not self._spherical and coordinate == "cartesian":
@@ -78,7 +88,7 @@ class MultiComponentModule(_BlockStore):
         if translation_invariant:
             self._Aw = self.__dict__.pop("Aw")   # (the sampler's handle; the attribute Aw raises, below)
 
-    translation_invariant = False
+    translation_invariant = translation_invariant_chains = False
 
     @staticmethod
     def _table_hint(mrange, mspacing, mratio, mseg, mdivisionsection, obsurface, kwargs):
@@ -123,12 +133,18 @@ class MultiComponentModule(_BlockStore):
                 raise NotImplementedError(store + " does not combine with " + why)
 
     def _set_cells(self, eng, bounds):
-        eng.set_cells_multi(bounds, self.components, self.weights, translation_invariant=self.translation_invariant)
+        eng.set_cells_multi(bounds, self.components, self.weights,
+                            translation_invariant="chains" if self.translation_invariant_chains else self.translation_invariant)
 
     def translation_invariant_info(self):
         """The engine's translation_invariant_info(): on, nx, ny, nz, px, qy, table_bytes (all components), max_dev
         (the largest of the components'), build_ms."""
         return self._engine.translation_invariant_info()
+
+    def translation_invariant_batch_plan(self):
+        """The engine's translation_invariant_batch_plan(): the partition of the chain batch's two passes on the tables
+        (translation_invariant="chains"; "on" is False otherwise), with "blocks", the number of components."""
+        return self._engine.translation_invariant_batch_plan()
 
     def _no_table(self, what):
         if self.translation_invariant:

@@ -11,7 +11,8 @@
  * the same ten other gravity fields (`_tesseroid_numba.py:161-341`, gh_set_cells_tess).  Several prism
  * gravity fields of one density model can share one store and be inverted together (gh_set_cells_multi; an
  * extension, the reference inverts one field at a time), on a regular grid under gridded data without a limit on the
- * rows (gh_set_cells_multi_table: one translation-invariant table per field).  Every entry
+ * rows (gh_set_cells_multi_table: one translation-invariant table per field; gh_set_cells_multi_table_chains: the
+ * same tables, which also take batches of 16 chains per read, gh_batch_*).  Every entry
  * point below names the reference interface it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer of the reference would add.
  *
@@ -364,6 +365,25 @@ int gh_set_cells_multi(gh_ctx *ctx, const double *bounds6, int ncomp, const int 
  * gh_set_shift_invariant and a grav_fix return an error naming the store; gh_download_G has no kernel to return.  With
  * ncomp = 1 and weights[0] = 1 the context computes what a gh_set_cells_prism context on the table computes. */
 int gh_set_cells_multi_table(gh_ctx *ctx, const double *bounds6, int ncomp, const int *comps, const double *weights);
+/* gh_set_cells_multi_table, and the table of blocks also takes chain batches: the same checks, tables, single-chain
+ * passes (gh_chain_*, gh_misfit_and_grad, gh_forward, gh_adjoint run exactly as on a gh_set_cells_multi_table context)
+ * and refusals, except that gh_batch_init, gh_batch_trajectory and gh_batch_run run on it -- always as the fp64-MFMA
+ * batch, never inside the resident kernels -- on the row-block forms of the table's batch passes (csrc/latbatch.hip.h):
+ * the forward takes the block as a grid coordinate under one gather of X and multiplies its sums by w_b, the adjoint
+ * runs the input rows of block 0, 1, ... into the same MFMA accumulators before the one update per (cell, chain), and
+ * the evaluation removes one mean per block and chain (csrc/batch.hip.h: batch_finish_blocks_kernel).  Order of the
+ * sums: blocks, input rows, inputs ascending; a chain's result does not depend on the other slots.  With ncomp = 1 and
+ * weights[0] = 1 the batch computes, bit for bit, what the batch of a gh_set_translation_invariant(ctx, 2) context of
+ * that field computes.  gh_translation_invariant_batch_plan reports the plan (the forward's chunks are planned for
+ * ncomp workgroups per chunk and tile), gh_batch_block_means the blocks' means.  An extent along y the batch tile
+ * cannot hold is refused by gh_batch_init as in mode 2 (the tile is the single block's: the blocks take turns in it);
+ * gh_compress_wavelet, gh_upload_G, gh_bscg_run, gh_shard_init*, gh_set_matrix_free and gh_set_shift_invariant return an
+ * error naming the translation-invariant store; gh_set_translation_invariant stays refused. */
+int gh_set_cells_multi_table_chains(gh_ctx *ctx, const double *bounds6, int ncomp, const int *comps, const double *weights);
+/* The means of the row blocks of the chains' CURRENT predictions Aw mw, pred_mean[chain * ncomp + b] for the C chains of
+ * the batch, as the batch's evaluation removes them.  A batch on a gh_set_cells_multi_table_chains context only
+ * (GH_ERR_UNSUPPORTED otherwise). */
+int gh_batch_block_means(gh_ctx *ctx, double *pred_mean);
 /* Several gravity fields of ONE density model of TESSEROIDS inverted together (GH_CELL_TESSEROID_MULTI): the spherical
  * form of gh_set_cells_multi -- satellite gradiometry, gzz, gxx, gyy, gxz ... measured together at orbit height.
  * ncomp distinct components comps[b] (GH_COMP_*, gz included) of the same M tesseroids (w,e,s,n,top,bottom) at the same
@@ -1025,7 +1045,8 @@ int gh_fold_pair_rows(int64_t N, const double *x, const double *y, const double 
  * -- the tile is 192 bytes per input of a row padded to 8 plus 64 per output of a workgroup's (at most 64), all the LDS
  * the kernels use, within the 163 840 bytes of a workgroup: 832 cells under 832 observations are the last equal extents
  * that fit, 848 the longest side at all -- is refused by gh_batch_init with GH_ERR_UNSUPPORTED; the wavelet forward, shards, gh_bscg_run and
- * gh_upload_G stay refused, and so do batches on gh_set_cells_multi_table.
+ * gh_upload_G stay refused, and so do batches on gh_set_cells_multi_table (gh_set_cells_multi_table_chains is the
+ * table of blocks that takes them).
  * gh_set_translation_invariant(ctx, GH_TABLE_REPLICATES) asks for the same table under the same checks and also takes
  * gh_bscg_run: the bootstrap batch's lock-step on the table's batch passes -- the 16-column forward as the chain batch
  * runs it, and the 16-column adjoint ending with the CG gradient and its |I|^2 partials instead of the leapfrog update
@@ -1037,13 +1058,14 @@ int gh_fold_pair_rows(int64_t N, const double *x, const double *y, const double 
  * The value is 4: 3 was GH_ERR_ARG before this mode existed and stays so, as does every value other than 0, 1, 2, 4. */
 enum { GH_TABLE_OFF = 0, GH_TABLE_SINGLE = 1, GH_TABLE_CHAINS = 2, GH_TABLE_REPLICATES = 4 };
 int gh_set_translation_invariant(gh_ctx *ctx, int enable);
-/* What the batch passes of a gh_set_translation_invariant(ctx, 2) or (ctx, GH_TABLE_REPLICATES) context planned on the built table (arithmetic alone:
+/* What the batch passes of a gh_set_translation_invariant(ctx, 2), (ctx, GH_TABLE_REPLICATES) or gh_set_cells_multi_table_chains context planned on the built table (arithmetic alone:
  * the context's last error text is left as it is; all 0
  * otherwise): out[0] on, [1] fits (0: gh_batch_init refuses the extent), [2] output rows per workgroup, [3] per wave,
  * [4] tiles of 16 outputs per wave at most, [5] forward chunks at most, [6] compute units; then for the adjoint
  * ([7]..[12]) and the forward ([13]..[18]): tiles of 16 outputs along y, workgroups along y, outputs per workgroup
  * along y, staged values per table row, grid x, LDS bytes; [19] layers per forward chunk, [20] forward chunks (slab
- * rows), [21] rows of the |p|^2 partials (workgroups of the adjoint). */
+ * rows), [21] rows of the |p|^2 partials (workgroups of the adjoint), [22] row blocks of a
+ * gh_set_cells_multi_table_chains context (the forward's grid is that many workgroups deep; 0 on a single-block table). */
 int gh_translation_invariant_batch_plan(gh_ctx *ctx, int32_t out[24]);
 /* on: the table is built; the lattice's extents; table_bytes (all row blocks); max_dev (the largest of the blocks)
  * and build_ms of the build. */
