@@ -126,6 +126,16 @@ PROTOTYPES = {
                                       C.POINTER(_i64)]),
     "gh_chain_run": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_int), _dp, _dp, C.c_double, _dp, _i64, _i64,
                                C.POINTER(C.c_int), _dp, _dp, C.POINTER(C.c_int)]),
+    "gh_chain_feed_usable": (C.c_int, [_ctx, C.POINTER(C.c_int)]),
+    "gh_chain_feed_open": (C.c_int, [_ctx, C.c_void_p, C.POINTER(C.c_int), _i64, C.c_int, C.c_int, _i64, C.c_double, _dp,
+                                     C.c_double, _i64, _i64, C.c_int]),
+    "gh_chain_feed_next": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp,
+                                     C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gh_chain_feed_close": (C.c_int, [_ctx, C.POINTER(_i64), C.POINTER(_i64)]),
+    "gh_chain_feed_stats": (C.c_int, [_ctx, _dp, _dp, _dp, C.POINTER(C.c_int)]),
+    "gh_debug_feed_dry_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), _i64, C.c_int, C.c_int, _i64, C.c_double, _dp,
+                                        _i64, C.c_int, _i64, C.POINTER(C.c_int), _dp, _dp, C.POINTER(C.c_int),
+                                        C.POINTER(_i64), C.POINTER(_i64)]),
     "gh_chain_get_x": (C.c_int, [_ctx, _dp]),
     "gh_chain_get_dsyn": (C.c_int, [_ctx, _dp]),
     "gh_batch_init": (C.c_int, [_ctx, C.c_int, _dp, _dp, _dp]),

@@ -72,11 +72,19 @@ static_assert(BCOMP_MAX == GH_BCOMP_MAX && BCOMP_MAX <= MULTI_MAX && BCOMP_TF ==
 #include "host_bscg.h"
 #include "host_chain.h"
 
+extern "C" int gh_chain_feed_close(gh_ctx *c, int64_t *drawn, int64_t *run);
+static void feed_free(gh_ctx *c);  // host_feed.h
+
 // ------------------------------------------------------------------------- C-ABI
 
 extern "C" {
 
-const char *gh_last_error(const gh_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
+const char *gh_last_error(const gh_ctx *ctx)
+{
+    if (ctx && ctx->feed_open.load(std::memory_order_acquire))
+        return "a chain feeder is open on this context: gh_chain_feed_close first";
+    return ctx ? ctx->err.c_str() : g_create_error.c_str();
+}
 
 int gh_create(gh_ctx **out, int device, int64_t N, int64_t M)
 {
@@ -116,6 +124,8 @@ int gh_create(gh_ctx **out, int device, int64_t N, int64_t M)
 void gh_destroy(gh_ctx *c)
 {
     if (!c) return;
+    gh_chain_feed_close(c, nullptr, nullptr);
+    feed_free(c);
     for (gh_ctx *k : c->kids) gh_destroy(k);
     c->kids.clear();
     hipSetDevice(c->device);
@@ -150,6 +160,7 @@ void gh_destroy(gh_ctx *c)
 
 int gh_device_info(const gh_ctx *c, char *name256, int *cus, int64_t *mem_bytes)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return GH_ERR_HIP;
@@ -164,6 +175,7 @@ int gh_device_info(const gh_ctx *c, char *name256, int *cus, int64_t *mem_bytes)
 
 int gh_synchronize(gh_ctx *c)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -172,6 +184,7 @@ int gh_synchronize(gh_ctx *c)
 
 int gh_set_obs(gh_ctx *c, const double *a, const double *b, const double *cc)
 {
+    GH_FEED_GUARD(c);
     if (!c || !a || !b || !cc) return fail(c, GH_ERR_ARG, "gh_set_obs: null pointer");
     HIPCHK(c, hipSetDevice(c->device));
     const double *src[3] = {a, b, cc};
@@ -211,6 +224,7 @@ static int set_cells(gh_ctx *c, const double *bounds6, int kind, int comp, doubl
 
 int gh_set_cells(gh_ctx *c, const double *bounds6, int kind, double ratio)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells: null pointer");
     if (kind != GH_CELL_PRISM && kind != GH_CELL_TESSEROID)
         return fail(c, GH_ERR_ARG, "gh_set_cells: kind must be 0 (prism) or 1 (tesseroid); the total field, the other "
@@ -223,6 +237,7 @@ int gh_set_cells(gh_ctx *c, const double *bounds6, int kind, double ratio)
 
 int gh_set_cells_tf(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_tf: null pointer");
     const double dir[3] = {fx, fy, fz};
     TRY(check_direction(c, "gh_set_cells_tf", dir));
@@ -231,6 +246,7 @@ int gh_set_cells_tf(gh_ctx *c, const double *bounds6, double fx, double fy, doub
 
 int gh_set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
 {
+    GH_FEED_GUARD(c);
     const CellStore &s = CELL_STORES[GH_CELL_PRISM_JOINT];
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "%s: null pointer", s.entry);
     if (c->N % 2 != 0 || c->M % 2 != 0)
@@ -335,6 +351,7 @@ static int set_block_cells(gh_ctx *c, int kind, const BlockCells &a)
 
 int gh_set_cells_mvi(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_mvi: null pointer");
     const double dir[3] = {fx, fy, fz};
     return set_block_cells(c, GH_CELL_PRISM_MVI, {bounds6, dir, 0, nullptr, nullptr, nullptr, 0.0, nullptr, false});
@@ -343,6 +360,7 @@ int gh_set_cells_mvi(gh_ctx *c, const double *bounds6, double fx, double fy, dou
 int gh_set_cells_mvi_data(gh_ctx *c, const double *bounds6, double fx, double fy, double fz, int ncomp, const int *comps,
                           const double *weights)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: null pointer");
     const double dir[3] = {fx, fy, fz};
     return set_block_cells(c, GH_CELL_PRISM_MVI_DATA, {bounds6, dir, ncomp, comps, weights, nullptr, 0.0, nullptr, false});
@@ -351,6 +369,7 @@ int gh_set_cells_mvi_data(gh_ctx *c, const double *bounds6, double fx, double fy
 int gh_set_cells_tess_mag(gh_ctx *c, const double *bounds6, double ratio, int ncomp, const int *comps,
                           const double *weights, const double *fdir)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: null pointer");
     return set_block_cells(c, GH_CELL_TESS_MVI_DATA, {bounds6, nullptr, ncomp, comps, weights, nullptr, ratio, fdir, false});
 }
@@ -359,6 +378,7 @@ int gh_set_cells_tess_mag(gh_ctx *c, const double *bounds6, double ratio, int nc
 int gh_set_cells_tess_mag_table(gh_ctx *c, const double *bounds6, double ratio, int ncomp, const int *comps,
                                 const double *weights, const double *fdir)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_tess_mag: null pointer");
     return set_block_cells(c, GH_CELL_TESS_MVI_DATA, {bounds6, nullptr, ncomp, comps, weights, nullptr, ratio, fdir, true});
 }
@@ -379,6 +399,7 @@ static int amplitude_weights(gh_ctx *c, double scale)
 
 int gh_set_amplitude(gh_ctx *c, double lambda, double beta, double scale)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (!c->mvi) return fail(c, GH_ERR_UNSUPPORTED, "gh_set_amplitude: %s", MVI_ONLY);
     TRY(need(c, c->weighted, "gh_set_amplitude: call gh_weight first (the term acts on mw / Wm)"));
@@ -398,6 +419,7 @@ int gh_set_amplitude(gh_ctx *c, double lambda, double beta, double scale)
 
 int gh_amplitude_eval(gh_ctx *c, const double *mw, double *value, double *grad, double *amp)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (!c->mvi) return fail(c, GH_ERR_UNSUPPORTED, "gh_amplitude_eval: %s", MVI_ONLY);
     if (!mw || !value) return fail(c, GH_ERR_ARG, "gh_amplitude_eval: null pointer");
@@ -419,6 +441,7 @@ int gh_amplitude_eval(gh_ctx *c, const double *mw, double *value, double *grad, 
 
 int gh_amplitude_last(const gh_ctx *c, double *phi)
 {
+    GH_FEED_GUARD(c);
     if (!c || !phi) return GH_ERR_ARG;
     if (!c->mvi) return GH_ERR_UNSUPPORTED;
     *phi = c->cg.phi_last;
@@ -427,6 +450,7 @@ int gh_amplitude_last(const gh_ctx *c, double *phi)
 
 int gh_set_cells_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *weights)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_multi: null pointer");
     return set_block_cells(c, GH_CELL_PRISM_MULTI, {bounds6, nullptr, ncomp, comps, weights, nullptr, 0.0, nullptr, false});
 }
@@ -435,6 +459,7 @@ int gh_set_cells_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *c
 // gh_build_G)
 int gh_set_cells_multi_table(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *weights)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_multi: null pointer");
     return set_block_cells(c, GH_CELL_PRISM_MULTI, {bounds6, nullptr, ncomp, comps, weights, nullptr, 0.0, nullptr, true});
 }
@@ -442,6 +467,7 @@ int gh_set_cells_multi_table(gh_ctx *c, const double *bounds6, int ncomp, const 
 // (gh_set_cells_multi_table's context, whose table also takes chain batches: latbatch.hip.h, the forms over row blocks)
 int gh_set_cells_multi_table_chains(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *weights)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_multi: null pointer");
     return set_block_cells(c, GH_CELL_PRISM_MULTI, {bounds6, nullptr, ncomp, comps, weights, nullptr, 0.0, nullptr, true, true});
 }
@@ -449,12 +475,14 @@ int gh_set_cells_multi_table_chains(gh_ctx *c, const double *bounds6, int ncomp,
 int gh_set_cells_tess_multi(gh_ctx *c, const double *bounds6, int ncomp, const int *comps, const double *ratios,
                             const double *weights)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6 || !comps || !ratios || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_tess_multi: null pointer");
     return set_block_cells(c, GH_CELL_TESSEROID_MULTI, {bounds6, nullptr, ncomp, comps, weights, ratios, 0.0, nullptr, false});
 }
 
 int gh_multi_info(gh_ctx *c, int *ncomp, int *comps, double *weights, double *pred_mean, double *obs_mean)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (c->mc.n == 0)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_multi_info: not a context of row blocks (gh_set_cells_multi, "
@@ -476,6 +504,7 @@ int gh_multi_info(gh_ctx *c, int *ncomp, int *comps, double *weights, double *pr
 
 int gh_joint_std(const gh_ctx *c, double std2[2])
 {
+    GH_FEED_GUARD(c);
     if (!c || !std2) return GH_ERR_ARG;
     if (!c->joint || !c->weighted) return GH_ERR_ARG;
     std2[0] = c->joint_std[0];
@@ -485,6 +514,7 @@ int gh_joint_std(const gh_ctx *c, double std2[2])
 
 int gh_joint_layout(const gh_ctx *c, int *workgroups_per_block, int *epilogue_stages)
 {
+    GH_FEED_GUARD(c);
     if (!c || !c->joint) return GH_ERR_ARG;
     if (workgroups_per_block) *workgroups_per_block = c->grid / 2;
     if (epilogue_stages) *epilogue_stages = joint_two_stage(c) ? 2 : 1;
@@ -494,6 +524,7 @@ int gh_joint_layout(const gh_ctx *c, int *workgroups_per_block, int *epilogue_st
 int gh_set_cross_gradient(gh_ctx *c, double lambda, const double scale2[2], const int shape3[3], double hx, double hy,
                           const double *hz)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (!c->joint)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_set_cross_gradient: the cross-gradient term couples the two blocks of the "
@@ -539,6 +570,7 @@ int gh_set_cross_gradient(gh_ctx *c, double lambda, const double scale2[2], cons
 
 int gh_cross_gradient_eval(gh_ctx *c, const double *mw, double *value, double *grad, double *t)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (!c->joint)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_cross_gradient_eval: the cross-gradient term couples the two blocks of the "
@@ -562,6 +594,7 @@ int gh_cross_gradient_eval(gh_ctx *c, const double *mw, double *value, double *g
 
 int gh_cross_gradient_last(const gh_ctx *c, double *phi)
 {
+    GH_FEED_GUARD(c);
     if (!c || !phi) return GH_ERR_ARG;
     if (!c->joint) return GH_ERR_UNSUPPORTED;
     *phi = c->cg.phi_last;
@@ -571,6 +604,7 @@ int gh_cross_gradient_last(const gh_ctx *c, double *phi)
 int gh_sweep_layout(const gh_ctx *c, int *tw, int *ept2, int *pf, int *nt, int *n_teams, int64_t *cols_per_team,
                     int *grid, int *n_panels)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (tw) *tw = c->TW;
     if (ept2) *ept2 = c->EPT2;
@@ -635,6 +669,7 @@ static int run_result(gh_ctx *c, const char *who, const double *in, size_t n_in,
 
 int gh_tf_result(gh_ctx *c, const double *mag3, double *result)
 {
+    GH_FEED_GUARD(c);
     if (!c || !mag3 || !result) return fail(c, GH_ERR_ARG, "gh_tf_result: null pointer");
     TRY(need(c, c->have_obs && c->have_cells, "gh_tf_result: call gh_set_obs and gh_set_cells_tf first"));
     if (c->cell_kind != GH_CELL_PRISM_TF && c->cell_kind != GH_CELL_PRISM_MVI)
@@ -653,6 +688,7 @@ int gh_tf_result(gh_ctx *c, const double *mag3, double *result)
 
 int gh_b_result(gh_ctx *c, int component, const double *mag3, double *result)
 {
+    GH_FEED_GUARD(c);
     if (!c || !mag3 || !result) return fail(c, GH_ERR_ARG, "gh_b_result: null pointer");
     TRY(need(c, c->have_obs && c->have_cells, "gh_b_result: call gh_set_cells_mvi_data (or gh_set_cells_mvi) and gh_set_obs "
                                               "first"));
@@ -680,6 +716,7 @@ int gh_b_result(gh_ctx *c, int component, const double *mag3, double *result)
 
 int gh_tess_b_result(gh_ctx *c, int component, const double *mag3, double *result)
 {
+    GH_FEED_GUARD(c);
     if (!c || !mag3 || !result) return fail(c, GH_ERR_ARG, "gh_tess_b_result: null pointer");
     TRY(need(c, c->have_obs && c->have_cells, "gh_tess_b_result: call gh_set_cells_tess_mag and gh_set_obs first"));
     if (!tess_mag_store(c))
@@ -704,6 +741,7 @@ int gh_tess_b_result(gh_ctx *c, int component, const double *mag3, double *resul
 
 int gh_set_cells_prism(gh_ctx *c, const double *bounds6, int component)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_prism: null pointer");
     TRY(check_component(c, "gh_set_cells_prism", COMPS_GRAV, component));
     // gz is the prism kind of gh_set_cells: the same context, the same kernels, the same bits
@@ -713,6 +751,7 @@ int gh_set_cells_prism(gh_ctx *c, const double *bounds6, int component)
 
 int gh_set_cells_tess(gh_ctx *c, const double *bounds6, int component, double ratio)
 {
+    GH_FEED_GUARD(c);
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "gh_set_cells_tess: null pointer");
     TRY(check_component(c, "gh_set_cells_tess", COMPS_GRAV, component));
     TRY(check_tess_bounds(c, "gh_set_cells_tess", bounds6, c->M));
@@ -724,6 +763,7 @@ int gh_set_cells_tess(gh_ctx *c, const double *bounds6, int component, double ra
 
 int gh_prism_result(gh_ctx *c, const double *dens, double *result)
 {
+    GH_FEED_GUARD(c);
     if (!c || !dens || !result) return fail(c, GH_ERR_ARG, "gh_prism_result: null pointer");
     TRY(need(c, c->have_obs && c->have_cells, "gh_prism_result: call gh_set_obs and gh_set_cells_prism first"));
     if (c->cell_kind == GH_CELL_TESSEROID_COMP)
@@ -741,6 +781,7 @@ int gh_prism_result(gh_ctx *c, const double *dens, double *result)
 
 int gh_set_matrix_free(gh_ctx *c, int enable)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (enable) TRY(dense_single_chain_refuse(c, "gh_set_matrix_free"));
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_matrix_free: call before gh_build_G");
@@ -759,6 +800,7 @@ int gh_set_matrix_free(gh_ctx *c, int enable)
 
 int gh_set_shift_invariant(gh_ctx *c, int enable)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     // (the tesseroid multi-component store and the tesseroid magnetization store are the stores of row blocks that
     // have the table; the prism forms of the vector stores keep refusing)
@@ -782,6 +824,7 @@ int gh_set_shift_invariant(gh_ctx *c, int enable)
 
 int gh_set_translation_invariant(gh_ctx *c, int enable)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (enable != 0 && enable != 1 && enable != GH_TABLE_CHAINS && enable != GH_TABLE_REPLICATES)
         return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: enable must be 0, 1, 2 or 4 (2: the table that takes chain "
@@ -817,6 +860,7 @@ int gh_set_translation_invariant(gh_ctx *c, int enable)
 int gh_translation_invariant_info(const gh_ctx *c, int *on, int *nx, int *ny, int *nz, int *px, int *qy, int64_t *table_bytes,
                                   double *max_dev, double *build_ms)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     const bool o = lattice_on(c);
     const ghk::LatGeom g = o ? c->lat->g : ghk::LatGeom{};
@@ -834,6 +878,7 @@ int gh_translation_invariant_info(const gh_ctx *c, int *on, int *nx, int *ny, in
 
 int gh_translation_invariant_batch_plan(gh_ctx *c, int32_t out[24])
 {
+    GH_FEED_GUARD(c);
     if (!c || !out) return fail(c, GH_ERR_ARG, "gh_translation_invariant_batch_plan: null pointer");
     for (int i = 0; i < 24; ++i) out[i] = 0;
     if (!lattice_on(c) || !(lattice_chains(c) || lattice_reps(c))) return GH_OK;
@@ -864,6 +909,7 @@ int gh_translation_invariant_batch_plan(gh_ctx *c, int32_t out[24])
 
 int gh_translation_invariant_table(gh_ctx *c, double *out)
 {
+    GH_FEED_GUARD(c);
     if (!c || !out) return fail(c, GH_ERR_ARG, "gh_translation_invariant_table: null pointer");
     TRY(need(c, lattice_on(c), "gh_translation_invariant_table: no table resident (gh_set_translation_invariant, gh_build_G)"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -892,6 +938,7 @@ int gh_lattice_detect(int64_t N, const double *x, const double *y, const double 
 int gh_shift_invariant_resident_stats(gh_ctx *c, int *workgroups, int64_t *launches, int64_t *evaluations, int64_t *trajectories,
                                       int *timeouts)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     const bool on = lonsym_harmonic(c) && c->ls->res.state > 0;
     if (workgroups) *workgroups = on ? c->ls->hgrid : 0;
@@ -904,6 +951,7 @@ int gh_shift_invariant_resident_stats(gh_ctx *c, int *workgroups, int64_t *launc
 
 int gh_shift_invariant_info(const gh_ctx *c, int *n_lon, int *n_classes, int *n_rows, int64_t *table_bytes)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     const bool on = lonsym_on(c);
     if (n_lon) *n_lon = on ? c->ls->n : 0;
@@ -915,6 +963,7 @@ int gh_shift_invariant_info(const gh_ctx *c, int *n_lon, int *n_classes, int *n_
 
 int gh_shift_invariant_harmonic(const gh_ctx *c, int *on, int *n_freq, int64_t *table_bytes, int *workgroups)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     // on: 1 = the register form (lonsymh.hip.h), 2 = the streamed form for large grids (lonsymw.hip.h)
     const bool h = lonsym_one_row(c);
@@ -927,6 +976,7 @@ int gh_shift_invariant_harmonic(const gh_ctx *c, int *on, int *n_freq, int64_t *
 
 int gh_shift_invariant_plan(gh_ctx *c, int32_t out[32])
 {
+    GH_FEED_GUARD(c);
     if (!c || !out) return fail(c, GH_ERR_ARG, "gh_shift_invariant_plan: null pointer");
     for (int i = 0; i < 32; ++i) out[i] = 0;
     if (!lonsym_on(c)) return GH_OK;
@@ -976,6 +1026,7 @@ int gh_shift_invariant_plan(gh_ctx *c, int32_t out[32])
 
 int gh_set_matrix_free_exact(gh_ctx *c, int exact)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_matrix_free_exact: call before gh_build_G");
     c->mf_exact_req = exact != 0 ? 1 : 0;
@@ -984,6 +1035,7 @@ int gh_set_matrix_free_exact(gh_ctx *c, int exact)
 
 int gh_build_G(gh_ctx *c)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     TRY(need(c, c->have_obs && c->have_cells, "gh_build_G: call gh_set_obs and gh_set_cells first"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -1068,6 +1120,7 @@ int gh_build_G(gh_ctx *c)
 
 int gh_kernel_stats(const gh_ctx *c, int64_t *warn_cells, int64_t *leaves)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (warn_cells) *warn_cells = c->warn_cells;
     if (leaves) *leaves = c->leaves;
@@ -1076,6 +1129,7 @@ int gh_kernel_stats(const gh_ctx *c, int64_t *warn_cells, int64_t *leaves)
 
 int gh_upload_G(gh_ctx *c, const double *A, int64_t ld, int fortran_order)
 {
+    GH_FEED_GUARD(c);
     if (!c || !A) return fail(c, GH_ERR_ARG, "gh_upload_G: null pointer");
     TRY(dense_single_chain_refuse(c, "gh_upload_G"));
     TRY(lattice_refuse(c, "gh_upload_G", "its entries come from the cells and observations"));
@@ -1116,6 +1170,7 @@ int gh_upload_G(gh_ctx *c, const double *A, int64_t ld, int fortran_order)
 
 int gh_download_G(gh_ctx *c, double *A, int64_t ld)
 {
+    GH_FEED_GUARD(c);
     if (!c || !A) return fail(c, GH_ERR_ARG, "gh_download_G: null pointer");
     TRY(need(c, c->have_G && !c->mf, "gh_download_G: no kernel matrix resident"));
     // (joint store: H = [Aw_gz | Aw_tf], N/2 rows -- the zero blocks of the stacked A are not stored)
@@ -1131,6 +1186,7 @@ int gh_download_G(gh_ctx *c, double *A, int64_t ld)
 
 int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     TRY(need(c, c->have_G, "gh_weight: no kernel matrix resident"));
     TRY(need(c, !c->weighted, "gh_weight: kernel is already weighted"));
@@ -1244,6 +1300,7 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
 
 int gh_set_data(gh_ctx *c, const double *dobs, const double *grav_fix)
 {
+    GH_FEED_GUARD(c);
     if (!c || !dobs) return fail(c, GH_ERR_ARG, "gh_set_data: null pointer");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->joint) {
@@ -1326,6 +1383,7 @@ int gh_set_data(gh_ctx *c, const double *dobs, const double *grav_fix)
 
 int gh_set_reg(gh_ctx *c, int kind, double alpha, double beta, const int shape3[3], const double *mwapr)
 {
+    GH_FEED_GUARD(c);
     if (!c || !mwapr) return fail(c, GH_ERR_ARG, "gh_set_reg: null pointer");
     if (kind < 0 || kind > 3)
         return fail(c, GH_ERR_ARG, "Please choose regularization from 'MS','Damping', 'Smoothness', 'TV'.");
@@ -1405,6 +1463,7 @@ int gh_set_reg(gh_ctx *c, int kind, double alpha, double beta, const int shape3[
 
 int gh_forward(gh_ctx *c, const double *mw, double *dpre)
 {
+    GH_FEED_GUARD(c);
     if (!c || !mw || !dpre) return fail(c, GH_ERR_ARG, "gh_forward: null pointer");
     TRY(need(c, c->have_G, "gh_forward: no kernel matrix resident"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -1426,6 +1485,7 @@ int gh_forward(gh_ctx *c, const double *mw, double *dpre)
 
 int gh_adjoint(gh_ctx *c, const double *r, double *g)
 {
+    GH_FEED_GUARD(c);
     if (!c || !r || !g) return fail(c, GH_ERR_ARG, "gh_adjoint: null pointer");
     TRY(need(c, c->have_G, "gh_adjoint: no kernel matrix resident"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -1447,6 +1507,7 @@ int gh_adjoint(gh_ctx *c, const double *r, double *g)
 
 int gh_misfit_and_grad(gh_ctx *c, const double *x, double out3[3], double *grad, double *dpre)
 {
+    GH_FEED_GUARD(c);
     if (!c || !x || !out3 || !grad) return fail(c, GH_ERR_ARG, "gh_misfit_and_grad: null pointer");
     TRY(need(c, c->have_G && c->have_data && c->have_reg,
              "gh_misfit_and_grad: needs a kernel matrix, gh_set_data and gh_set_reg"));
@@ -1478,6 +1539,7 @@ int gh_misfit_and_grad(gh_ctx *c, const double *x, double out3[3], double *grad,
 int gh_reg_eval(gh_ctx *c, int kind, double beta, const int shape3[3], int ms_grad_den_mw, const double *mw,
                 const double *mwapr, double *value, double *grad)
 {
+    GH_FEED_GUARD(c);
     if (!c || !mw || !mwapr || !value) return fail(c, GH_ERR_ARG, "gh_reg_eval: null pointer");
     if (kind < 0 || kind > 3)
         return fail(c, GH_ERR_ARG, "Please choose regularization from 'MS','Damping', 'Smoothness', 'TV'.");
@@ -1525,6 +1587,7 @@ int gh_reg_eval(gh_ctx *c, int kind, double beta, const int shape3[3], int ms_gr
 int gh_compress_wavelet(gh_ctx *c, int dims, const int shape3[3], double thr, int levels,
                         int64_t *nnz_out, int64_t *ncols_out)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     TRY(dense_single_chain_refuse(c, "gh_compress_wavelet"));
     TRY(lattice_refuse(c, "gh_compress_wavelet", "the wavelet rows need the stored kernel"));
@@ -1642,6 +1705,7 @@ int gh_compress_wavelet(gh_ctx *c, int dims, const int shape3[3], double thr, in
 
 int gh_download_csr(gh_ctx *c, int64_t *indptr, int32_t *indices, double *data)
 {
+    GH_FEED_GUARD(c);
     if (!c || !indptr || !indices || !data) return fail(c, GH_ERR_ARG, "gh_download_csr: null pointer");
     TRY(need(c, c->wv.on, "gh_download_csr: call gh_compress_wavelet first"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -1657,6 +1721,7 @@ int gh_download_csr(gh_ctx *c, int64_t *indptr, int32_t *indices, double *data)
 
 int gh_model_coeffs(gh_ctx *c, const double *mw, double *coeff)
 {
+    GH_FEED_GUARD(c);
     if (!c || !mw || !coeff) return fail(c, GH_ERR_ARG, "gh_model_coeffs: null pointer");
     TRY(need(c, c->wv.on, "gh_model_coeffs: call gh_compress_wavelet first"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -1668,6 +1733,7 @@ int gh_model_coeffs(gh_ctx *c, const double *mw, double *coeff)
 
 int gh_forward_wavelet(gh_ctx *c, const double *mw, double *dpre)
 {
+    GH_FEED_GUARD(c);
     if (!c || !mw || !dpre) return fail(c, GH_ERR_ARG, "gh_forward_wavelet: null pointer");
     TRY(need(c, c->wv.on, "gh_forward_wavelet: call gh_compress_wavelet first"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -1678,6 +1744,7 @@ int gh_forward_wavelet(gh_ctx *c, const double *mw, double *dpre)
 
 int gh_chain_init(gh_ctx *c, const double *x0, const double *low, const double *high)
 {
+    GH_FEED_GUARD(c);
     if (!c || !x0 || !low || !high) return fail(c, GH_ERR_ARG, "gh_chain_init: null pointer");
     TRY(need(c, c->have_G && c->have_data && c->have_reg,
              "gh_chain_init: needs a kernel matrix, gh_set_data and gh_set_reg"));
@@ -1710,6 +1777,7 @@ int gh_chain_init(gh_ctx *c, const double *x0, const double *low, const double *
 
 int gh_chain_prefetch_momentum(gh_ctx *c, const double *p0_next)
 {
+    GH_FEED_GUARD(c);
     if (!c || !p0_next) return fail(c, GH_ERR_ARG, "gh_chain_prefetch_momentum: null pointer");
     TRY(need(c, c->chain_ready, "gh_chain_prefetch_momentum: call gh_chain_init first"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -1733,6 +1801,7 @@ int gh_chain_prefetch_momentum(gh_ctx *c, const double *p0_next)
 int gh_chain_trajectory(gh_ctx *c, const double *p0, double dt, int L, double u, int *accepted,
                         double out5[5])
 {
+    GH_FEED_GUARD(c);
     return chain_trajectory_impl(c, p0, dt, L, u, nullptr, accepted, out5);
 }
 
@@ -1740,6 +1809,7 @@ int gh_chain_run(gh_ctx *c, int K, const int *L, const double *p0s, const double
                  const double *p0_lookahead, int64_t stop_at_accepts, int64_t record_from, int *accepted,
                  double *out5s, double *x_out, int *n_run)
 {
+    GH_FEED_GUARD(c);
     if (!c || K < 1 || !L || !p0s || !us || !accepted || !out5s || !n_run)
         return fail(c, GH_ERR_ARG, "gh_chain_run: bad arguments");
     TRY(need(c, c->chain_ready, "gh_chain_run: call gh_chain_init first"));
@@ -1784,6 +1854,7 @@ int gh_chain_run(gh_ctx *c, int K, const int *L, const double *p0s, const double
 
 int gh_chain_get_x(gh_ctx *c, double *x)
 {
+    GH_FEED_GUARD(c);
     if (!c || !x) return fail(c, GH_ERR_ARG, "gh_chain_get_x: null pointer");
     TRY(need(c, c->chain_ready, "gh_chain_get_x: call gh_chain_init first"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -1792,6 +1863,7 @@ int gh_chain_get_x(gh_ctx *c, double *x)
 
 int gh_chain_get_dsyn(gh_ctx *c, double *dsyn)
 {
+    GH_FEED_GUARD(c);
     if (!c || !dsyn) return fail(c, GH_ERR_ARG, "gh_chain_get_dsyn: null pointer");
     TRY(need(c, c->chain_ready, "gh_chain_get_dsyn: call gh_chain_init first"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -1801,6 +1873,7 @@ int gh_chain_get_dsyn(gh_ctx *c, double *dsyn)
 
 int gh_chain_stats(gh_ctx *c, int64_t *spec_hits, int64_t *spec_misses)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (spec_hits) *spec_hits = c->spec_hits;
     if (spec_misses) *spec_misses = c->spec_misses;
@@ -1809,6 +1882,7 @@ int gh_chain_stats(gh_ctx *c, int64_t *spec_hits, int64_t *spec_misses)
 
 int gh_team_sweep_stats(gh_ctx *c, int *members, int64_t *launches, int *timeouts, int64_t *late_parts)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (late_parts) *late_parts = c->tm.late_polls;
     if (members) *members = c->tm.state != 0 ? c->tm.Q : 0;
@@ -1819,6 +1893,7 @@ int gh_team_sweep_stats(gh_ctx *c, int *members, int64_t *launches, int *timeout
 
 int gh_chain_resident_stats(gh_ctx *c, int64_t *launches, int64_t *evaluations)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (launches) *launches = c->rs.launches;
     if (evaluations) *evaluations = c->rs.evals;
@@ -1827,6 +1902,7 @@ int gh_chain_resident_stats(gh_ctx *c, int64_t *launches, int64_t *evaluations)
 
 int gh_chain_resident_plan(gh_ctx *c, int chains, int32_t out[16])
 {
+    GH_FEED_GUARD(c);
     if (!c || !out) return fail(c, GH_ERR_ARG, "gh_chain_resident_plan: null pointer");
     if (chains < 1 || chains > RES_MAX_CHAINS) return fail(c, GH_ERR_ARG, "gh_chain_resident_plan: 1..16 chains");
     TRY(need(c, c->have_G && c->have_data && c->have_reg,
@@ -1857,6 +1933,7 @@ int gh_chain_resident_plan(gh_ctx *c, int chains, int32_t out[16])
 
 int gh_posterior_window(gh_ctx *c, int K)
 {
+    GH_FEED_GUARD(c);
     if (!c || K < 1) return fail(c, GH_ERR_ARG, "gh_posterior_window: K must be >= 1");
     if (c->ring) return fail(c, GH_ERR_ARG, "gh_posterior_window: window already allocated");
     HIPCHK(c, hipSetDevice(c->device));
@@ -1871,6 +1948,7 @@ int gh_posterior_window(gh_ctx *c, int K)
 
 int gh_posterior_add(gh_ctx *c)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     TRY(need(c, c->chain_ready && (c->ring || c->ps.on),
              "gh_posterior_add: needs gh_chain_init and gh_posterior_window"));
@@ -1883,6 +1961,7 @@ int gh_posterior_add(gh_ctx *c)
 
 int gh_posterior_read(gh_ctx *c, int64_t *n_in_window, int64_t *n_total, double *mean, double *sd)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     TRY(need(c, c->ring != nullptr, "gh_posterior_read: call gh_posterior_window first"));
     const int nvalid = (int)std::min<int64_t>(c->ring_count, c->ring_K);
@@ -1901,6 +1980,7 @@ int gh_posterior_read(gh_ctx *c, int64_t *n_in_window, int64_t *n_total, double 
 int gh_posterior_stream(gh_ctx *c, int chains, int bins, int batch_len, int64_t record_from, int64_t record_count,
                         const double *lo, const double *hi)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (!lo || !hi) return fail(c, GH_ERR_ARG, "gh_posterior_stream: null pointer");
     if (c->sh.kind != 0)
@@ -1919,6 +1999,7 @@ int gh_posterior_stream(gh_ctx *c, int chains, int bins, int batch_len, int64_t 
 
 int gh_posterior_stream_slot(gh_ctx *c, int slot)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     TRY(need(c, c->ps.on, "gh_posterior_stream_slot: call gh_posterior_stream first"));
     if (slot < 0 || slot >= c->ps.d.C) return fail(c, GH_ERR_ARG, "gh_posterior_stream_slot: no such chain slot");
@@ -1928,6 +2009,7 @@ int gh_posterior_stream_slot(gh_ctx *c, int slot)
 
 int gh_posterior_stream_add(gh_ctx *c, int slot, const double *m)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (!m) return fail(c, GH_ERR_ARG, "gh_posterior_stream_add: null pointer");
     TRY(need(c, c->ps.on, "gh_posterior_stream_add: call gh_posterior_stream first"));
@@ -1940,6 +2022,7 @@ int gh_posterior_stream_add(gh_ctx *c, int slot, const double *m)
 int gh_posterior_stream_read(gh_ctx *c, int64_t *n_per_chain, double *mean, double *sd, double *rhat, double *ess,
                              double *chain_mean, double *chain_M2)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     TRY(need(c, c->ps.on, "gh_posterior_stream_read: call gh_posterior_stream first"));
     return post_read(c, n_per_chain, mean, sd, rhat, ess, chain_mean, chain_M2);
@@ -1947,6 +2030,7 @@ int gh_posterior_stream_read(gh_ctx *c, int64_t *n_per_chain, double *mean, doub
 
 int gh_posterior_stream_quantiles(gh_ctx *c, int nq, const double *q, double *out)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     TRY(need(c, c->ps.on, "gh_posterior_stream_quantiles: call gh_posterior_stream first"));
     if (nq < 1 || nq > POST_MAX_Q || !q || !out) return fail(c, GH_ERR_ARG, "gh_posterior_stream_quantiles: 1..32 quantiles");
@@ -1957,6 +2041,7 @@ int gh_posterior_stream_quantiles(gh_ctx *c, int nq, const double *q, double *ou
 
 int gh_posterior_stream_hist(gh_ctx *c, uint32_t *out)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (!out) return fail(c, GH_ERR_ARG, "gh_posterior_stream_hist: null pointer");
     TRY(need(c, c->ps.on, "gh_posterior_stream_hist: call gh_posterior_stream first"));
@@ -1969,6 +2054,7 @@ int gh_posterior_stream_hist(gh_ctx *c, uint32_t *out)
 
 int gh_posterior_stream_free(gh_ctx *c)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (!c->ps.on) return GH_OK;
     return post_free(c);
@@ -1976,6 +2062,7 @@ int gh_posterior_stream_free(gh_ctx *c)
 
 int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const double *high)
 {
+    GH_FEED_GUARD(c);
     if (!c || !x0s || !low || !high) return fail(c, GH_ERR_ARG, "gh_batch_init: null pointer");
     TRY(dense_single_chain_refuse(c, "gh_batch_init"));  // (passes the table of blocks that takes batches)
     TRY(lattice_batch_refuse(c, "gh_batch_init"));
@@ -2045,6 +2132,7 @@ int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const 
 int gh_batch_trajectory(gh_ctx *c, const double *p0s, double dt, const int *L, const double *us, int *accepted,
                         double *out5s)
 {
+    GH_FEED_GUARD(c);
     if (!c || !p0s || !L || !us || !accepted || !out5s) return fail(c, GH_ERR_ARG, "gh_batch_trajectory: null pointer");
     TRY(dense_single_chain_refuse(c, "gh_batch_trajectory"));
     TRY(lattice_batch_refuse(c, "gh_batch_trajectory"));
@@ -2086,6 +2174,7 @@ int gh_batch_trajectory(gh_ctx *c, const double *p0s, double dt, const int *L, c
 int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const double *us, double dt,
                  int *accepted, double *out5s, double *x_out, int *n_started, int *n_done)
 {
+    GH_FEED_GUARD(c);
     if (!c || T < 0 || (T > 0 && (!L || !p0s || !us)) || !accepted || !out5s || ((n_started == nullptr) != (n_done == nullptr)))
         return fail(c, GH_ERR_ARG, "gh_batch_run: bad arguments");
     TRY(dense_single_chain_refuse(c, "gh_batch_run"));
@@ -2181,6 +2270,7 @@ int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const
 // (GRAVHMC_LONSYM_TIMING=1), 100 MHz ticks of workgroup 0.
 int gh_debug_lonsym_timing(gh_ctx *c, long long out8[8])
 {
+    GH_FEED_GUARD(c);
     if (!c || !out8) return GH_ERR_ARG;
     for (int i = 0; i < 8; ++i) out8[i] = 0;
     if (!c->ls || !c->ls->dbg) return GH_OK;
@@ -2193,6 +2283,7 @@ int gh_debug_lonsym_timing(gh_ctx *c, long long out8[8])
 // (GRAVHMC_LONSYM_TIMING=1; lonres.hip.h), 100 MHz ticks.
 int gh_debug_lonres_timing(gh_ctx *c, long long out16[16])
 {
+    GH_FEED_GUARD(c);
     if (!c || !out16) return GH_ERR_ARG;
     for (int i = 0; i < 16; ++i) out16[i] = 0;
     if (!c->ls || !c->ls->res.dbg) return GH_OK;
@@ -2205,6 +2296,7 @@ int gh_debug_lonres_timing(gh_ctx *c, long long out16[16])
 // (GRAVHMC_MFB_TIMING=1), 100 MHz ticks of workgroup (0, 0).
 int gh_debug_mfb_timing(gh_ctx *c, long long out8[8])
 {
+    GH_FEED_GUARD(c);
     if (!c || !out8) return GH_ERR_ARG;
     for (int i = 0; i < 8; ++i) out8[i] = 0;
     if (!c->bt.fus_dbg) return GH_OK;
@@ -2215,6 +2307,7 @@ int gh_debug_mfb_timing(gh_ctx *c, long long out8[8])
 
 int gh_batch_fused_stats(gh_ctx *c, int *members, int *ranges, int64_t *launches, int *timeouts)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     const gh_ctx::Batch &b = c->bt;
     if (members) *members = b.fus_on ? b.fus_members : 0;
@@ -2226,6 +2319,7 @@ int gh_batch_fused_stats(gh_ctx *c, int *members, int *ranges, int64_t *launches
 
 int gh_matrix_free_team_stats(gh_ctx *c, int *members, int *ranges, int64_t *launches, int *timeouts)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     const gh_ctx::MfTeam &t = c->mft;
     if (members) *members = t.state == 1 ? t.members : 0;
@@ -2238,6 +2332,7 @@ int gh_matrix_free_team_stats(gh_ctx *c, int *members, int *ranges, int64_t *lau
 int gh_batch_resident_stats(gh_ctx *c, int64_t *launches, int64_t *lock_steps, int64_t *chain_steps, int64_t *lost_steps,
                             int *timeouts)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     const gh_ctx::Resident::LockStep &b = c->rs.ls;
     if (launches) *launches = b.launches;
@@ -2250,6 +2345,7 @@ int gh_batch_resident_stats(gh_ctx *c, int64_t *launches, int64_t *lock_steps, i
 
 int gh_pinned_alloc(gh_ctx *c, size_t bytes, void **host)
 {
+    GH_FEED_GUARD(c);
     if (!c || !host || bytes == 0) return fail(c, GH_ERR_ARG, "gh_pinned_alloc: null pointer or no bytes");
     HIPCHK(c, hipSetDevice(c->device));
     void *p = nullptr;
@@ -2261,6 +2357,7 @@ int gh_pinned_alloc(gh_ctx *c, size_t bytes, void **host)
 
 int gh_pinned_free(gh_ctx *c, void *host)
 {
+    GH_FEED_GUARD(c);
     if (!c || !host) return fail(c, GH_ERR_ARG, "gh_pinned_free: null pointer");
     for (size_t i = 0; i < c->pinned.size(); ++i)
         if (c->pinned[i].base == (char *)host) {
@@ -2275,6 +2372,7 @@ int gh_pinned_free(gh_ctx *c, void *host)
 
 int gh_batch_staging_stats(gh_ctx *c, int64_t *rows_direct, int64_t *rows_staged)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (rows_direct) *rows_direct = c->rs.ls.lists.rows_direct;
     if (rows_staged) *rows_staged = c->rs.ls.lists.rows_staged;
@@ -2301,6 +2399,7 @@ int gh_debug_row_copy_plan(int K, const double *const *rows, int64_t M, int n_bl
 
 int gh_batch_get_x(gh_ctx *c, int chain, double *x)
 {
+    GH_FEED_GUARD(c);
     if (!c || !x) return fail(c, GH_ERR_ARG, "gh_batch_get_x: null pointer");
     TRY(need(c, c->bt.ready && chain >= 0 && chain < c->bt.C, "gh_batch_get_x: no such chain"));
     HIPCHK(c, hipSetDevice(c->device));
@@ -2314,6 +2413,7 @@ int gh_batch_get_x(gh_ctx *c, int chain, double *x)
 
 int gh_batch_block_means(gh_ctx *c, double *pred_mean)
 {
+    GH_FEED_GUARD(c);
     if (!c || !pred_mean) return fail(c, GH_ERR_ARG, "gh_batch_block_means: null pointer");
     TRY(need(c, c->bt.ready, "gh_batch_block_means: call gh_batch_init first"));
     if (!lattice_multi_chains(c) || !c->bt.bmean)
@@ -2335,6 +2435,7 @@ int gh_bscg_run(gh_ctx *c, int B, const double *counts, const double *dobs, cons
                 double beta2, double q, int maxk, double *models, double *dmis, double *mmis, double *alpha, int *n_entries,
                 int *n_alpha)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     TRY(bscg_refuse(c, B, maxk));
     if (!counts || !dobs || !mw0 || !models || !dmis || !mmis || !alpha || !n_entries || !n_alpha)
@@ -2347,6 +2448,7 @@ int gh_bscg_run(gh_ctx *c, int B, const double *counts, const double *dobs, cons
 
 int gh_bscg_stats(const gh_ctx *c, int64_t *forward_sweeps, int64_t *adjoint_sweeps, int64_t *lock_steps)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (forward_sweeps) *forward_sweeps = c->bs.forward_sweeps;
     if (adjoint_sweeps) *adjoint_sweeps = c->bs.adjoint_sweeps;
@@ -2357,6 +2459,7 @@ int gh_bscg_stats(const gh_ctx *c, int64_t *forward_sweeps, int64_t *adjoint_swe
 int gh_leapfrog(gh_ctx *c, double *x_inout, const double *p0, double dt, int L, const double *low,
                 const double *high, double u, int *accepted, double out5[5], double *dsyn)
 {
+    GH_FEED_GUARD(c);
     TRY(gh_chain_init(c, x_inout, low, high));
     TRY(gh_chain_trajectory(c, p0, dt, L, u, accepted, out5));
     TRY(gh_chain_get_x(c, x_inout));
@@ -2367,6 +2470,7 @@ int gh_leapfrog(gh_ctx *c, double *x_inout, const double *p0, double dt, int L, 
 // Diagnostic (not in the public header): time a pure streaming read of the resident G.
 int gh_debug_resident_timing(gh_ctx *c, long long out32[32], int64_t *launches, int64_t *evals)
 {
+    GH_FEED_GUARD(c);
     if (!c || !out32) return GH_ERR_ARG;
     if (launches) *launches = c->rs.launches;
     if (evals) *evals = c->rs.evals;
@@ -2388,6 +2492,7 @@ int gh_debug_stream_read(gh_ctx *c, int blocks, int threads, int nt, int reps, d
 
 int gh_measure_stream_read(gh_ctx *c, int nt, int reps, double *ms_per_pass)
 {
+    GH_FEED_GUARD(c);
     if (!c || !ms_per_pass || reps < 1) return fail(c, GH_ERR_ARG, "gh_measure_stream_read: bad arguments");
     TRY(need(c, c->have_G && !c->mf, "gh_measure_stream_read: needs a stored kernel matrix"));
     // the best of three launch shapes (the rate of a plain read depends on how many wide loads the
@@ -2405,6 +2510,7 @@ int gh_measure_stream_read(gh_ctx *c, int nt, int reps, double *ms_per_pass)
 
 int gh_debug_stream_read(gh_ctx *c, int blocks, int threads, int nt, int reps, double *ms_out)
 {
+    GH_FEED_GUARD(c);
     if (!c || !c->have_G) return GH_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     TRY(ensure_work(c));
@@ -2447,6 +2553,7 @@ int gh_shard_unique_id(void *id128)
 
 int gh_shard_init(gh_ctx *c, const void *id128, int rank, int world, int64_t M_global, int64_t m0)
 {
+    GH_FEED_GUARD(c);
     if (!c || !id128) return fail(c, GH_ERR_ARG, "gh_shard_init: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init: already initialised");
     TRY(dense_single_chain_refuse(c, "gh_shard_init"));
@@ -2468,6 +2575,7 @@ int gh_shard_init(gh_ctx *c, const void *id128, int rank, int world, int64_t M_g
 int gh_shard_init_callback(gh_ctx *c, gh_allreduce_fn fn, void *user, int rank, int world, int64_t M_global,
                            int64_t m0)
 {
+    GH_FEED_GUARD(c);
     if (!c || !fn) return fail(c, GH_ERR_ARG, "gh_shard_init_callback: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init: already initialised");
     TRY(dense_single_chain_refuse(c, "gh_shard_init"));
@@ -2482,6 +2590,7 @@ int gh_shard_init_callback(gh_ctx *c, gh_allreduce_fn fn, void *user, int rank, 
 
 int gh_shard_init_rows(gh_ctx *c, const void *id128, int rank, int world, int64_t N_global, int64_t n0)
 {
+    GH_FEED_GUARD(c);
     if (!c || !id128) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: already initialised");
     TRY(dense_single_chain_refuse(c, "gh_shard_init_rows"));
@@ -2503,6 +2612,7 @@ int gh_shard_init_rows(gh_ctx *c, const void *id128, int rank, int world, int64_
 int gh_shard_init_rows_callback(gh_ctx *c, gh_allreduce_fn fn, void *user, int rank, int world, int64_t N_global,
                                 int64_t n0)
 {
+    GH_FEED_GUARD(c);
     if (!c || !fn) return fail(c, GH_ERR_ARG, "gh_shard_init_rows_callback: null pointer");
     if (c->sh.kind != 0) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: already initialised");
     TRY(dense_single_chain_refuse(c, "gh_shard_init_rows"));
@@ -2517,6 +2627,7 @@ int gh_shard_init_rows_callback(gh_ctx *c, gh_allreduce_fn fn, void *user, int r
 
 int gh_shard_allreduce(gh_ctx *c, double *host_buf, int64_t count)
 {
+    GH_FEED_GUARD(c);
     if (!c || !host_buf) return fail(c, GH_ERR_ARG, "gh_shard_allreduce: null pointer");
     HIPCHK(c, hipSetDevice(c->device));
     return comm_allreduce_host(c, host_buf, count);
@@ -2618,6 +2729,7 @@ int64_t gh_format_row_fixed8(const double *v, int64_t n, char *out, int64_t cap)
 
 int gh_profile_enable(gh_ctx *c, int enable)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (enable && c->ev.empty()) {
@@ -2643,6 +2755,7 @@ int gh_profile_enable(gh_ctx *c, int enable)
 int gh_matrix_free_stats(gh_ctx *c, int64_t *entries, int64_t *leaves, int64_t *launches, int64_t *near_entries,
                          int64_t *near_leaves)
 {
+    GH_FEED_GUARD(c);
     if (c && near_entries) *near_entries = c->mf_near_on ? c->mf_near_n : 0;
     if (c && near_leaves) *near_leaves = c->mf_near_on ? c->mf_near_leaves : 0;
     if (!c) return GH_ERR_ARG;
@@ -2659,6 +2772,7 @@ int gh_matrix_free_stats(gh_ctx *c, int64_t *entries, int64_t *leaves, int64_t *
 
 int gh_fold_info(const gh_ctx *c, int *on, int *reason, int64_t *store_bytes, double *max_dev, double *build_ms)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     const gh_ctx::Fold &f = c->fd;
     const bool live = f.valid && f.gen == c->G_gen;
@@ -2672,6 +2786,7 @@ int gh_fold_info(const gh_ctx *c, int *on, int *reason, int64_t *store_bytes, do
 
 int gh_fold_pair_info(const gh_ctx *c, int *on, int *reason, int64_t *pairs, int64_t *single_orbits, int64_t *bytes_per_sweep)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     const gh_ctx::Fold &f = c->fd;
     const bool live = f.valid && f.gen == c->G_gen;
@@ -2747,6 +2862,7 @@ int gh_fold_detect(int64_t N, const double *x, const double *y, const double *z,
 
 int gh_profile_read(gh_ctx *c, double *sweep_ms, int64_t *sweep_launches, int64_t *bytes_per_sweep)
 {
+    GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2784,3 +2900,5 @@ int gh_profile_read(gh_ctx *c, double *sweep_ms, int64_t *sweep_launches, int64_
 }
 
 }  // extern "C"
+
+#include "host_feed.h"

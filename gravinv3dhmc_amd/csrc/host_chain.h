@@ -23,10 +23,19 @@ static inline int other_of3(int a, int b)
     return 0;
 }
 
-// p0_next (or nullptr): momentum of the NEXT trajectory, valid until this call returns.  Announced
+// The momentum of the NEXT trajectory: a pointer known when the call is made (p, or nullptr: none), or `late`,
+// consulted once, right before the upload on the copy stream -- the trajectory feeder (host_feed.h) draws that row
+// while this trajectory's sweeps are already queued, and blocks there until it is complete (nullptr: the stream ended).
+struct P0Next {
+    const double *p = nullptr;
+    const double *(*late)(void *) = nullptr;
+    void *user = nullptr;
+};
+
+// next: momentum of the NEXT trajectory, valid until this call returns.  Announced
 // this way (gh_chain_run) it is uploaded on a second stream while this trajectory's sweeps run --
 // through the public gh_chain_prefetch_momentum the upload happens before them, with the GPU idle.
-static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, double u, const double *p0_next,
+static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, double u, P0Next next,
                                  int *accepted, double out5[5])
 {
     if (!c || !p0 || !accepted || !out5) return fail(c, GH_ERR_ARG, "gh_chain_trajectory: null pointer");
@@ -94,6 +103,7 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
     double probe[3] = {c->pn_probe[0], c->pn_probe[1], c->pn_probe[2]};
     double pn_pp0 = c->pn_pp0;
     bool pn_deferred = false;
+    const double *p0_next = next.late ? next.late(next.user) : next.p;
     if (p0_next) {
         if (!c->copy_stream) {
             HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
@@ -163,7 +173,7 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
     if (!failed) TRY(mft_failed(c, &failed));  // (matrix-free chain on teams: same contract)
     auto redo = [&]() -> int {
         c->spec_valid = c->pn_valid = false;
-        const int rc = chain_trajectory_impl(c, p0, dt, L, u, p0_next, accepted, out5);
+        const int rc = chain_trajectory_impl(c, p0, dt, L, u, P0Next{p0_next}, accepted, out5);
         team_resume(c);
         return rc;
     };
@@ -218,4 +228,10 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
     *accepted = acc ? 1 : 0;
     c->cg.phi_last = c->cg.phi_cur;  // (Phi of the state the chain is left in, as out5[0..2])
     return GH_OK;
+}
+
+static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, double u, const double *p0_next,
+                                 int *accepted, double out5[5])
+{
+    return chain_trajectory_impl(c, p0, dt, L, u, P0Next{p0_next}, accepted, out5);
 }

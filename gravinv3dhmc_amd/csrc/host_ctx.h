@@ -6,6 +6,7 @@ static thread_local std::string g_create_error;
 
 struct LonSymHost;  // host_lonsym.h
 struct LatticeHost; // host_lattice.h
+struct gh_feed;     // host_feed.h
 
 struct DevBuf {
     void *p = nullptr;
@@ -50,6 +51,10 @@ struct gh_ctx {
     hipEvent_t copy_ev = nullptr;
     std::string err;
     std::vector<void *> allocs;
+    // the trajectory feeder (host_feed.h): while feed_open is set two library threads run the chain on this context,
+    // and every entry point but gh_chain_feed_next / _close / _stats refuses (GH_FEED_GUARD)
+    gh_feed *feed = nullptr;
+    std::atomic<int> feed_open{0};
 
     // geometry / kernel
     double *obs[3] = {nullptr, nullptr, nullptr};
@@ -453,6 +458,13 @@ static int fail(gh_ctx *c, int code, const char *fmt, ...)
     if (c) c->err = buf; else g_create_error = buf;
     return code;
 }
+
+// First statement of an entry point: the context belongs to its open feeder's threads (its error text included, so
+// nothing is written: gh_last_error names the feeder while it is open).
+#define GH_FEED_GUARD(c)                                                                    \
+    do {                                                                                    \
+        if ((c) && (c)->feed_open.load(std::memory_order_acquire)) return GH_ERR_ARG;       \
+    } while (0)
 
 #define HIPCHK(c, call)                                                                     \
     do {                                                                                    \

@@ -249,26 +249,41 @@ int gh_rng_draw_trajectories(gh_rng *r, int K, int Lmin, int Lmax, int64_t M, do
         }
     };
     int nt = r->threads > 0 ? r->threads : env_int("GRAVHMC_RNG_THREADS", 2);
-    const bool piped = nt > 1 && npairs >= 16384;
+    bool piped = nt > 1 && npairs >= 16384;
     std::atomic<size_t> produced{0};
     std::atomic<bool> finished{false};
     std::thread helper;
-    if (piped)
-        helper = std::thread([&]() {
-            size_t lo = 0;
-            for (;;) {
-                const bool fin = finished.load(std::memory_order_acquire);
-                const size_t hi = produced.load(std::memory_order_acquire);
-                if (hi > lo) {
-                    scale(lo, hi);
-                    lo = hi;
-                } else if (fin) {
-                    break;
-                } else {
-                    std::this_thread::yield();
+    // (whatever way this function is left, a helper that runs is told to finish and joined)
+    struct JoinHelper {
+        std::thread &t;
+        std::atomic<bool> &fin;
+        ~JoinHelper()
+        {
+            if (!t.joinable()) return;
+            fin.store(true, std::memory_order_release);
+            t.join();
+        }
+    } join_helper{helper, finished};
+    try {
+        if (piped)
+            helper = std::thread([&]() {
+                size_t lo = 0;
+                for (;;) {
+                    const bool fin = finished.load(std::memory_order_acquire);
+                    const size_t hi = produced.load(std::memory_order_acquire);
+                    if (hi > lo) {
+                        scale(lo, hi);
+                        lo = hi;
+                    } else if (fin) {
+                        break;
+                    } else {
+                        std::this_thread::yield();
+                    }
                 }
-            }
-        });
+            });
+    } catch (const std::system_error &) {
+        piped = false;  // no thread to be had: the scale pass runs here, after the generation
+    }
     for (int k = 0; k < K; ++k) {
         // masked rejection on 32-bit outputs (none drawn when there is one possible value)
         uint32_t v = 0;
@@ -283,9 +298,15 @@ int gh_rng_draw_trajectories(gh_rng *r, int K, int Lmin, int Lmax, int64_t M, do
             size_t np = (end - at + 1) / 2;
             const bool spill = tail && k == K - 1;
             if (spill) np -= 1;
-            rng_disc_points(r, np, p0s + at, r2 + ip);
-            at += 2 * np;
-            ip += np;
+            // (in pieces: the scale pass follows the generation inside ONE momentum too, not only a momentum behind)
+            for (size_t left = np; left > 0;) {
+                const size_t n = std::min(left, (size_t)8192);
+                rng_disc_points(r, n, p0s + at, r2 + ip);
+                at += 2 * n;
+                ip += n;
+                left -= n;
+                if (piped) produced.store(ip, std::memory_order_release);
+            }
             if (spill) {
                 rng_disc_points(r, 1, last, r2 + ip);
                 p0s[at] = last[0];

@@ -775,8 +775,14 @@ class Engine(object):
         overlap=True hands a finished batch to `on_result` while the next one already runs (the
         device never waits for Python's bookkeeping or file output); a stop requested by
         `on_result` -- as opposed to `stop_at_accepts`, which the library itself honours, or the
-        end of `draws` -- then takes effect one batch late."""
+        end of `draws` -- then takes effect one batch late.
+        One chain on the sweep launches, fed from a LegacyDraws with overlap=True and the default batch, runs on the
+        library's trajectory feeder instead (_run_chain_feed): same stream, same results, no Python between two
+        trajectories.  Generators, GRAVHMC_HOST_RNG=numpy, sharded engines, the persistent launches, an explicit
+        `batch`, overlap=False and GRAVHMC_CHAIN_FEED=0 keep the loop below."""
         import threading
+        if batch is None and overlap and type(self) is Engine and self._feed_usable(draws):
+            return self._run_chain_feed(draws, dt, on_result, stop_at_accepts, record_from, want_x)
         if batch is None:
             batch = self.default_batch()
         # The momenta of a batch are drawn / gathered into page-locked blocks of the library (three of them in
@@ -907,6 +913,55 @@ class Engine(object):
         finally:
             jobs.put(None)
             th.join()
+
+    def _feed_usable(self, draws):
+        from .inversion.rng import LegacyDraws
+        if not isinstance(draws, LegacyDraws):
+            return False
+        usable = C.c_int(0)
+        self._chk(self._lib.gh_chain_feed_usable(self._h, C.byref(usable)))
+        return bool(usable.value)
+
+    def _run_chain_feed(self, draws, dt, on_result, stop_at_accepts, record_from, want_x):
+        """run_chain on the library's feeder (gh_chain_feed_*): a drawer and a runner thread of the library take the
+        stream from `draws`' generator and run the chain; this thread only hands the results to `on_result`, in
+        order.  A stop asked for by `on_result` ends the chain after the trajectory in flight."""
+        import sys
+        lib = self._lib
+        K = 4 if (want_x and self.M * 8 >= (1 << 20)) else 16
+        Ls, acc = (C.c_int * K)(), (C.c_int * K)()
+        out5 = np.empty((K, 5))
+        xs = np.empty((K, self.M)) if want_x else None
+        n, fin = C.c_int(0), C.c_int(0)
+        self._chk(lib.gh_chain_feed_open(self._h, *draws.feed_args(), float(dt), int(stop_at_accepts), int(record_from),
+                                         1 if want_x else 0))
+        try:
+            stop = False
+            while not stop and not fin.value:
+                # (a bounded wait: the interpreter sees its signals between two calls)
+                self._chk(lib.gh_chain_feed_next(self._h, K, 200, Ls, acc, ptr(out5), ptr(xs), C.byref(n), C.byref(fin)))
+                for k in range(n.value):
+                    x = xs[k].copy() if (want_x and acc[k]) else None
+                    if on_result(int(Ls[k]), bool(acc[k]), out5[k].copy(), x) is False:
+                        stop = True
+                        break
+        finally:
+            drawn, run = C.c_int64(0), C.c_int64(0)
+            rc = lib.gh_chain_feed_close(self._h, C.byref(drawn), C.byref(run))
+            draws.feed_drew(drawn.value)
+            self._feed_last = {"drawn": drawn.value, "run": run.value}
+            if rc != 0 and sys.exc_info()[0] is None:
+                self._chk(rc)
+
+    def feed_stats(self):
+        """Counters of the trajectory feeder (gh_chain_feed_stats; of the open one, else of the last): seconds the
+        runner waited for a draw, the drawer for a free row, the runner for the result queue; the rows of the ring;
+        trajectories drawn and run by the last feeder."""
+        a, b, c_, rows = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int(0)
+        self._chk(self._lib.gh_chain_feed_stats(self._h, C.byref(a), C.byref(b), C.byref(c_), C.byref(rows)))
+        last = getattr(self, "_feed_last", {"drawn": 0, "run": 0})
+        return {"runner_wait_draw_s": a.value, "drawer_wait_row_s": b.value, "runner_wait_queue_s": c_.value,
+                "rows": rows.value, "drawn": last["drawn"], "run": last["run"]}
 
     def chain_get_x(self):
         x = np.empty(self.M)

@@ -130,6 +130,26 @@ class LegacyDraws(object):
             self._left -= n
         return Ls, p0s, us
 
+    # -- the library's trajectory feeder draws for itself ---------------------------------
+    def feed_args(self):
+        """What gh_chain_feed_open takes after (ctx,): the generator's handle, the lengths still planned (or None),
+        their number, Lmin, Lmax, the trajectories left (-1: unbounded), sigma and the sigma vector (or None).  The
+        arrays are kept alive here."""
+        if self._plan is None:
+            plan, n_plan = None, 0
+            limit = -1 if self._left is None else int(self._left)
+        else:
+            done = len(self._plan) - self._left
+            self._feed_plan = np.ascontiguousarray(self._plan[done:], dtype=np.int32)
+            plan, n_plan, limit = self._feed_plan.ctypes.data_as(C.POINTER(C.c_int)), len(self._feed_plan), -1
+        vec = None if self._sigma_vec is None else self._sigma_vec.ctypes.data_as(C.POINTER(C.c_double))
+        return (self._h, plan, n_plan, self.Lmin, self.Lmax, limit, self._sigma, vec)
+
+    def feed_drew(self, n):
+        """The feeder took n trajectories from the stream (gh_chain_feed_close)."""
+        if self._left is not None:
+            self._left -= int(n)
+
     # -- a ring of page-locked rows -------------------------------------------------------
     def use_ring(self, engine, rows):
         """Draw into a ring of `rows` momentum rows in page-locked memory of the engine's library

@@ -70,6 +70,7 @@ extern "C" {
 #endif
 
 typedef struct gh_ctx gh_ctx;
+typedef struct gh_rng gh_rng; /* the reference's random stream, below */
 
 typedef enum {
     GH_OK = 0,
@@ -681,6 +682,41 @@ int gh_chain_prefetch_momentum(gh_ctx *ctx, const double *p0_next);
 int gh_chain_run(gh_ctx *ctx, int K, const int *L, const double *p0s, const double *us, double dt,
                  const double *p0_lookahead, int64_t stop_at_accepts, int64_t record_from,
                  int *accepted, double *out5s, double *x_out, int *n_run);
+/* The trajectory feeder: gh_chain_run's loop on two library threads, for ONE chain on the launches of the sweep path.
+ * While it is open a DRAWER thread takes the reference's stream from `rng` a trajectory at a time -- L (plan_L[k] where a
+ * plan of n_plan lengths is given, else randint(Lmin, Lmax + 1)), randn(M) * sigma (sigma_vec, or NULL: M factors applied
+ * after a draw with sigma = 1), rand() -- into a ring of page-locked rows, at most rows - 2 trajectories ahead, and a
+ * RUNNER thread runs them as gh_chain_run does: the row after the running one is its look-ahead (the runner waits for
+ * it where the upload is issued, never goes without), accepted states are counted, recorded from `record_from` and,
+ * with want_x, copied to a second page-locked ring.  The stream ends after `limit` trajectories (< 0: unbounded; a plan
+ * bounds it too), the runner after the trajectory that reaches stop_at_accepts (> 0), and gh_chain_feed_close ends both
+ * after the trajectory in flight.  The device sees the stream operations of gh_chain_run; results are bit for bit its.
+ *   usable: 1 for one chain on the sweep launches (dense, folded, team sweep, matrix-free, wavelet, the plain passes of
+ *     the shift-invariant store); 0 where gh_chain_run takes a persistent launch, on a sharded context, and with
+ *     GRAVHMC_CHAIN_FEED=0.
+ *   next: blocks for at least one result or the end (timeout_ms >= 0: at most that long), returns up to max_rows
+ *     (<= 64) in stream order -- L, accepted, out5s[5 i ..], xs[i M ..] (or NULL) for accepted ones -- and finished = 1
+ *     once the runner has ended and everything was returned.  A caller that does not call it throttles the chain.
+ *   close: joins both threads; drawn = trajectories taken from the stream, run = trajectories run.
+ *   stats: seconds the runner waited for a draw, the drawer for a free row, the runner for the result queue (of the
+ *     open feeder, else of the last one), and the rows of the ring (32 MiB / 8 M in 4 .. 64; GRAVHMC_FEED_ROWS, >= 3).
+ * An error of either thread is kept with its text and returned by next / close.  While a feeder is open every other
+ * entry point on the context returns GH_ERR_ARG (gh_last_error names the feeder); gh_destroy closes it first. */
+int gh_chain_feed_usable(gh_ctx *ctx, int *usable);
+int gh_chain_feed_open(gh_ctx *ctx, gh_rng *rng, const int *plan_L, int64_t n_plan, int Lmin, int Lmax, int64_t limit,
+                       double sigma, const double *sigma_vec, double dt, int64_t stop_at_accepts, int64_t record_from,
+                       int want_x);
+int gh_chain_feed_next(gh_ctx *ctx, int max_rows, int timeout_ms, int *L, int *accepted, double *out5s, double *xs,
+                       int *n, int *finished);
+int gh_chain_feed_close(gh_ctx *ctx, int64_t *drawn, int64_t *run);
+int gh_chain_feed_stats(gh_ctx *ctx, double *runner_wait_draw_s, double *drawer_wait_row_s, double *runner_wait_queue_s,
+                        int *rows);
+/* The feeder's drawer and queue with a host stub in place of the runner (no context, no GPU).  Per trajectory k: out_L,
+ * out_u, out_probe[4 k ..] = first, middle, last entry and in-order sum of the momentum, out_look[k] = a look-ahead row
+ * was handed over.  The stream must be bounded by at most max_out trajectories. */
+int gh_debug_feed_dry_run(gh_rng *rng, const int *plan_L, int64_t n_plan, int Lmin, int Lmax, int64_t limit, double sigma,
+                          const double *sigma_vec, int64_t M, int rows, int64_t max_out, int *out_L, double *out_u,
+                          double *out_probe, int *out_look, int64_t *n_out, int64_t *drawn);
 /* How often the speculative first step was used / discarded. */
 int gh_chain_stats(gh_ctx *ctx, int64_t *spec_hits, int64_t *spec_misses);
 /* Small dense problems (N <= 1024, one column block per CU fitting its LDS next to the kernel's
@@ -926,7 +962,7 @@ int64_t gh_format_row_fixed8(const double *v, int64_t n, char *out, int64_t cap)
  * K trajectories per call, written straight into the arrays gh_chain_run takes.  Host only, no
  * context.  gh_rng_create(seed) is np.random.seed(seed); get / set_state exchange the stream with
  * np.random.get_state() / set_state() (key[624], pos, has_gauss, cached_gaussian). */
-typedef struct gh_rng gh_rng;
+/* (typedef struct gh_rng gh_rng; stands at the top, for the feeder's entry points) */
 int gh_rng_create(gh_rng **out, uint32_t seed);
 void gh_rng_destroy(gh_rng *rng);
 int gh_rng_set_state(gh_rng *rng, const uint32_t *key624, int pos, int has_gauss, double cached);
