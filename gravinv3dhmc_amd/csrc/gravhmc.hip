@@ -521,6 +521,17 @@ int gh_joint_layout(const gh_ctx *c, int *workgroups_per_block, int *epilogue_st
     return GH_OK;
 }
 
+// cg.sw = 1 / (Wm scale) per block, 0 where Wm is 0: from the weights the store has NOW (gh_weight builds it again)
+static int cross_gradient_weights(gh_ctx *c, const double scale2[2])
+{
+    const int64_t m = store_cells(c);
+    TRY(dalloc(c, &c->cg.sw, (size_t)c->M));
+    std::vector<double> w((size_t)c->M);
+    TRY(d2h(c, w.data(), c->wm, (size_t)c->M));
+    for (int64_t j = 0; j < c->M; ++j) w[(size_t)j] = w[(size_t)j] == 0.0 ? 0.0 : (1.0 / w[(size_t)j]) / scale2[j / m];
+    return h2d(c, c->cg.sw, w.data(), (size_t)c->M);
+}
+
 int gh_set_cross_gradient(gh_ctx *c, double lambda, const double scale2[2], const int shape3[3], double hx, double hy,
                           const double *hz)
 {
@@ -549,12 +560,9 @@ int gh_set_cross_gradient(gh_ctx *c, double lambda, const double scale2[2], cons
     gh_ctx::CrossGrad &cg = c->cg;
     // (sized for any later shape: a mesh of m cells has fewer than m layers)
     TRY(dalloc(c, &cg.ihz, (size_t)m));
-    TRY(dalloc(c, &cg.sw, (size_t)c->M));
-    std::vector<double> w((size_t)c->M), iz((size_t)shape3[0] - 1);
-    TRY(d2h(c, w.data(), c->wm, (size_t)c->M));
-    for (int64_t j = 0; j < c->M; ++j) w[(size_t)j] = w[(size_t)j] == 0.0 ? 0.0 : (1.0 / w[(size_t)j]) / scale2[j / m];
+    TRY(cross_gradient_weights(c, scale2));
+    std::vector<double> iz((size_t)shape3[0] - 1);
     for (size_t k = 0; k < iz.size(); ++k) iz[k] = 1.0 / hz[k];
-    TRY(h2d(c, cg.sw, w.data(), (size_t)c->M));
     TRY(h2d(c, cg.ihz, iz.data(), iz.size()));
     cg.ihx = 1.0 / hx;
     cg.ihy = 1.0 / hy;
@@ -1033,6 +1041,32 @@ int gh_set_matrix_free_exact(gh_ctx *c, int exact)
     return GH_OK;
 }
 
+// The stored kernel, or the weights folded into it, changed (gh_build_G, gh_upload_G, gh_weight): a new generation.
+// What was derived from the old one goes, or is keyed to the generation and made again where it is next used --
+// the folded store (fd.gen), the MFMA operand-order copy (bt.Gb_gen), the wavelet rows with their dense form (a
+// context is compressed again for its new kernel), the chains' states.  The streaming posterior's 1 / wm follows
+// the weights the context has now.
+static int kernel_changed(gh_ctx *c)
+{
+    c->G_gen += 1;
+    c->chain_ready = false;
+    c->bt.ready = false;
+    gh_ctx::Wavelet &w = c->wv;
+    if (w.on || w.indptr) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        w.on = false;
+        w.F_valid = false;
+        w.nnz = 0;
+        dev_release(c, w.indptr);
+        dev_release(c, w.indices);
+        dev_release(c, w.data);
+        if (!shard_rows(c)) c->rs.state = 0;  // (planned for the dense form: plan the resident chain kernel again)
+        if (c->ls) c->ls->res.state = 0;
+    }
+    if (c->ps.on) TRY(post_weights(c));
+    return GH_OK;
+}
+
 int gh_build_G(gh_ctx *c)
 {
     GH_FEED_GUARD(c);
@@ -1112,9 +1146,7 @@ int gh_build_G(gh_ctx *c)
     TRY(build_dense(c));
     c->have_G = true;
     c->weighted = false;
-    c->G_gen += 1;
-    c->chain_ready = false;
-    c->bt.ready = false;
+    TRY(kernel_changed(c));
     return fold_detect(c);  // (gz prisms on a grid symmetric under both mirrors: host_fold.h)
 }
 
@@ -1160,12 +1192,9 @@ int gh_upload_G(gh_ctx *c, const double *A, int64_t ld, int fortran_order)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_G = true;
     c->weighted = false;
-    c->G_gen += 1;
     c->fd.detected = -1;  // (entries of the caller's: no pairing is assumed)
     c->fd.reason = GH_FOLD_NOT_GZ;
-    c->chain_ready = false;
-    c->bt.ready = false;
-    return GH_OK;
+    return kernel_changed(c);
 }
 
 int gh_download_G(gh_ctx *c, double *A, int64_t ld)
@@ -1289,13 +1318,11 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
     if (wm_out) memcpy(wm_out, w.data(), sizeof(double) * (size_t)c->M);
     for (auto &v : w) v = v * v;  // diag(WmSquare) = ADiag * ADiag (potential.py:253)
     TRY(h2d(c, c->wm2, w.data(), (size_t)c->M));
-    // (an amplitude term set on the store's earlier weights follows the new ones)
+    // (a coupling term set on the store's earlier weights follows the new ones)
     if (c->mvi && c->amp.set) TRY(amplitude_weights(c, c->amp.scale));
+    if (c->joint && c->cg.set) TRY(cross_gradient_weights(c, c->cg.scale));
     c->weighted = true;
-    c->G_gen += 1;
-    c->chain_ready = false;
-    c->bt.ready = false;
-    return GH_OK;
+    return kernel_changed(c);
 }
 
 int gh_set_data(gh_ctx *c, const double *dobs, const double *grav_fix)
@@ -2401,7 +2428,8 @@ int gh_batch_get_x(gh_ctx *c, int chain, double *x)
 {
     GH_FEED_GUARD(c);
     if (!c || !x) return fail(c, GH_ERR_ARG, "gh_batch_get_x: null pointer");
-    TRY(need(c, c->bt.ready && chain >= 0 && chain < c->bt.C, "gh_batch_get_x: no such chain"));
+    TRY(need(c, c->bt.ready, "gh_batch_get_x: call gh_batch_init first"));
+    TRY(need(c, chain >= 0 && chain < c->bt.C, "gh_batch_get_x: no such chain"));
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->kids.empty()) return gh_chain_get_x(c->kids[(size_t)chain], x);
     if (c->rs.b_on) return d2h(c, x, c->rs.bx + (size_t)chain * (size_t)c->M, (size_t)c->M);

@@ -271,8 +271,16 @@ static int mfb_plan(gh_ctx *c)
 static int batch_relayout(gh_ctx *c)
 {
     gh_ctx::Batch &b = c->bt;
-    if (c->mf || b.Gb || !c->G || !env_int("GRAVHMC_BATCH_RELAYOUT", 1)) return GH_OK;
+    if (c->mf || !c->G || !env_int("GRAVHMC_BATCH_RELAYOUT", 1)) return GH_OK;
     const int64_t ntiles = (c->M + 15) / 16;
+    if (b.Gb) {
+        // (the copy of an earlier kernel or of other weights: the same block, ld and M being the context's, filled again)
+        if (b.Gb_gen == c->G_gen) return GH_OK;
+        batch_relayout_kernel<<<dim3(1 << 16), dim3(256), 0, c->stream>>>(c->G, c->ld, c->M, (int)(c->ld / 16), ntiles, b.Gb);
+        HIPCHK(c, hipGetLastError());
+        b.Gb_gen = c->G_gen;
+        return GH_OK;
+    }
     size_t free_b = 0, total_b = 0;
     const size_t need_b = sizeof(double) * (size_t)ntiles * 16 * (size_t)c->ld;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > need_b + ((size_t)2 << 30)) {
@@ -280,6 +288,7 @@ static int batch_relayout(gh_ctx *c)
         if (hipMalloc(&ptr, need_b) == hipSuccess) {
             c->allocs.push_back(ptr);
             b.Gb = static_cast<double *>(ptr);
+            b.Gb_gen = c->G_gen;
             batch_relayout_kernel<<<dim3(1 << 16), dim3(256), 0, c->stream>>>(c->G, c->ld, c->M, (int)(c->ld / 16), ntiles, b.Gb);
             HIPCHK(c, hipGetLastError());
         } else {
@@ -647,6 +656,7 @@ static int batch_init_mfma(gh_ctx *c, int C, const double *x0s)
 {
     TRY(batch_alloc(c));
     gh_ctx::Batch &b = c->bt;
+    if (!b.fus_on) TRY(batch_relayout(c));  // (buffers of an earlier batch: the copy follows the kernel it has now)
     b.C = C;
     if (c->mf) {
         // 1 / wm as the single-chain passes round it (x * (1.0 / w); 1 where w == 0 or not weighted)

@@ -278,6 +278,7 @@ struct gh_ctx {
         // proposal's values survive a speculative first step) and the next trajectories' momenta
         double *GREGw2 = nullptr, *Dw2 = nullptr, *Rtw2 = nullptr, *scal2 = nullptr, *Pn = nullptr, *pn0_part = nullptr;
         double *Gb = nullptr;     // second copy of G in MFMA operand order (adjoint), if HBM allows
+        uint64_t Gb_gen = ~0ull;  // G_gen it was laid out from (batch_relayout fills it again for another)
         // matrix-free batch (mfbatch.hip.h): 1 / wm, the near-field pairs as differences to the staged
         // root leaf (column-major: mf_near_ptr / mf_near_row / ndelta; row-major copy: rptr / rcol / rdelta)
         double *iw = nullptr, *Snear = nullptr, *ndelta = nullptr, *rdelta = nullptr;
@@ -486,6 +487,17 @@ static int dalloc(gh_ctx *c, T **out, size_t count, bool zero = true)
     if (zero) HIPCHK(c, hipMemsetAsync(p, 0, bytes, c->stream));
     *out = static_cast<T *>(p);
     return GH_OK;
+}
+
+// A block of dalloc's given back before gh_destroy (sizes that change with the kernel: the wavelet rows).
+template <typename T>
+static void dev_release(gh_ctx *c, T *&p)
+{
+    if (!p) return;
+    auto it = std::find(c->allocs.begin(), c->allocs.end(), (void *)p);
+    if (it != c->allocs.end()) c->allocs.erase(it);
+    hipFree((void *)p);
+    p = nullptr;
 }
 
 #define TRY(x)                 \

@@ -106,11 +106,7 @@ static int post_feed_batch(gh_ctx *c, const double *Xc, unsigned mask)
 template <typename T>
 static void post_release(gh_ctx *c, T *&p)
 {
-    if (!p) return;
-    auto it = std::find(c->allocs.begin(), c->allocs.end(), (void *)p);
-    if (it != c->allocs.end()) c->allocs.erase(it);
-    hipFree((void *)p);
-    p = nullptr;
+    dev_release(c, p);
 }
 
 static int post_free(gh_ctx *c)
@@ -134,6 +130,20 @@ static int post_free(gh_ctx *c)
     return GH_OK;
 }
 
+// 1 / wm of the weights the context has NOW: at allocation on a weighted context, and again from gh_weight (a stream
+// that is older than the weights gets its row here; one that outlives them follows the new ones).
+static int post_weights(gh_ctx *c)
+{
+    gh_ctx::PostStream &p = c->ps;
+    p.d.iw = nullptr;  // (an unweighted store: the rows hold m itself)
+    if (!c->weighted) return GH_OK;
+    TRY(dalloc(c, &p.iw, (size_t)c->M, false));
+    post_recip_kernel<<<post_grid(c), dim3(256), 0, c->stream>>>(c->wm, c->M, p.iw);
+    HIPCHK(c, hipGetLastError());
+    p.d.iw = p.iw;
+    return GH_OK;
+}
+
 static int post_alloc(gh_ctx *c, int chains, int bins, int batch_len, int64_t record_from, int64_t record_count,
                       const double *lo, const double *hi)
 {
@@ -150,7 +160,6 @@ static int post_alloc(gh_ctx *c, int chains, int bins, int batch_len, int64_t re
     if (rc == GH_OK) rc = dalloc(c, &p.hi, M, false);
     if (rc == GH_OK) rc = dalloc(c, &p.row, M, false);
     if (rc == GH_OK) rc = dalloc(c, &p.out, 4 * M, false);
-    if (rc == GH_OK && c->weighted) rc = dalloc(c, &p.iw, M, false);
     if (rc == GH_OK) rc = h2d(c, p.lo, lo, M);
     if (rc == GH_OK) rc = h2d(c, p.hi, hi, M);
     if (rc != GH_OK) {
@@ -159,13 +168,8 @@ static int post_alloc(gh_ctx *c, int chains, int bins, int batch_len, int64_t re
         c->err = why;
         return rc;
     }
-    if (c->weighted) {
-        post_recip_kernel<<<post_grid(c), dim3(256), 0, c->stream>>>(c->wm, c->M, p.iw);
-        HIPCHK(c, hipGetLastError());
-    }
     p.d.lo = p.lo;
     p.d.hi = p.hi;
-    p.d.iw = p.iw;
     p.d.M = c->M;
     p.d.C = chains;
     p.d.B = bins;
@@ -173,6 +177,13 @@ static int post_alloc(gh_ctx *c, int chains, int bins, int batch_len, int64_t re
     p.from = record_from;
     p.count = record_count;
     p.slot = 0;
+    rc = post_weights(c);
+    if (rc != GH_OK) {
+        const std::string why = c->err;
+        post_free(c);
+        c->err = why;
+        return rc;
+    }
     p.on = true;
     return GH_OK;
 }

@@ -1152,7 +1152,8 @@ class Engine(object):
         """Running statistics of whole runs of up to 16 chains on the device (gh_posterior_stream): per chain slot
         mean / M2 and batch means of `batch_len` samples, one pooled histogram of `bins` bins over [lo, hi] per
         cell (unweighted model bounds: scalars or M-vectors).  Chain slot c records its accepted states number
-        record_from + 1 ... record_from + record_count.  Call it after weight()."""
+        record_from + 1 ... record_from + record_count.  Before or after weight(): the stream follows the weights the engine
+        has when a state is recorded."""
         chains, bins, batch_len = int(chains), int(bins), int(batch_len)
         if not 1 <= chains <= 16:
             raise ValueError("posterior_stream: chains must be 1..16")
