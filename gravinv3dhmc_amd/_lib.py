@@ -136,6 +136,7 @@ PROTOTYPES = {
     "gh_debug_feed_dry_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), _i64, C.c_int, C.c_int, _i64, C.c_double, _dp,
                                         _i64, C.c_int, _i64, C.POINTER(C.c_int), _dp, _dp, C.POINTER(C.c_int),
                                         C.POINTER(_i64), C.POINTER(_i64)]),
+    "gh_debug_work_layout": (C.c_int, [_ctx, C.POINTER(_i64)]),
     "gh_chain_get_x": (C.c_int, [_ctx, _dp]),
     "gh_chain_get_dsyn": (C.c_int, [_ctx, _dp]),
     "gh_batch_init": (C.c_int, [_ctx, C.c_int, _dp, _dp, _dp]),

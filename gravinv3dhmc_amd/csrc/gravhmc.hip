@@ -425,15 +425,14 @@ int gh_amplitude_eval(gh_ctx *c, const double *mw, double *value, double *grad, 
     if (!mw || !value) return fail(c, GH_ERR_ARG, "gh_amplitude_eval: null pointer");
     TRY(need(c, c->amp.set, "gh_amplitude_eval: call gh_set_amplitude first (lambda = 0 leaves the coupling off)"));
     HIPCHK(c, hipSetDevice(c->device));
-    TRY(ensure_work(c));
+    TRY(ensure_work(c, "gh_amplitude_eval"));
     const int64_t m = store_cells(c);
     if (amp) TRY(dalloc(c, &c->amp.abuf, (size_t)m));
     TRY(h2d(c, c->xb[3], mw, (size_t)c->M));
     launch_amplitude(c, c->xb[3], 1.0, grad ? c->tmpM : nullptr, false, amp ? c->amp.abuf : nullptr, c->amppart);
-    sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->amppart, (int)((m + 255) / 256), c->st[3].scal);
+    sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->amppart, (int)c->work.amppart, c->st[3].scal);
     HIPCHK(c, hipGetLastError());
-    TRY(d2h(c, c->h_scal, c->st[3].scal, 1));
-    *value = c->h_scal[0];
+    TRY(read_value(c, c->st[3].scal, value));
     if (grad) TRY(d2h(c, grad, c->tmpM, (size_t)c->M));
     if (amp) TRY(d2h(c, amp, c->amp.abuf, (size_t)m));
     return GH_OK;
@@ -586,15 +585,14 @@ int gh_cross_gradient_eval(gh_ctx *c, const double *mw, double *value, double *g
     if (!mw || !value) return fail(c, GH_ERR_ARG, "gh_cross_gradient_eval: null pointer");
     TRY(need(c, c->cg.set, "gh_cross_gradient_eval: call gh_set_cross_gradient first (lambda = 0 leaves the coupling off)"));
     HIPCHK(c, hipSetDevice(c->device));
-    TRY(ensure_work(c));
+    TRY(ensure_work(c, "gh_cross_gradient_eval"));
     const int64_t m = store_cells(c);
     if (t) TRY(dalloc(c, &c->cg.tbuf, 3 * (size_t)m));
     TRY(h2d(c, c->xb[3], mw, (size_t)c->M));
     launch_cross_gradient(c, c->xb[3], 1.0, grad ? c->tmpM : nullptr, false, t ? c->cg.tbuf : nullptr, c->regpart);
-    sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->regpart, (int)((m + 255) / 256), c->st[3].scal);
+    sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->regpart, c->work.reg_blocks, c->st[3].scal);
     HIPCHK(c, hipGetLastError());
-    TRY(d2h(c, c->h_scal, c->st[3].scal, 1));
-    *value = c->h_scal[0];
+    TRY(read_value(c, c->st[3].scal, value));
     if (grad) TRY(d2h(c, grad, c->tmpM, (size_t)c->M));
     if (t) TRY(d2h(c, t, c->cg.tbuf, 3 * (size_t)m));
     return GH_OK;
@@ -792,7 +790,7 @@ int gh_set_matrix_free(gh_ctx *c, int enable)
     GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     if (enable) TRY(dense_single_chain_refuse(c, "gh_set_matrix_free"));
-    if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_matrix_free: call before gh_build_G");
+    if (c->have_G || c->work_ready) return fail(c, GH_ERR_ARG, "gh_set_matrix_free: call before gh_build_G");
     if (c->lat) {
         if (enable) return fail(c, GH_ERR_ARG, "gh_set_matrix_free: %s is switched on: one form at a time", LATTICE_NAME);
         c->lat->mf_before = false;  // (the store keeps c->mf)
@@ -813,9 +811,9 @@ int gh_set_shift_invariant(gh_ctx *c, int enable)
     // (the tesseroid multi-component store and the tesseroid magnetization store are the stores of row blocks that
     // have the table; the prism forms of the vector stores keep refusing)
     // (a magnetization store that has been built is the dense store: it refuses as it always did)
-    if (enable && !(c && (tess_multi_store(c) || (tess_mag_store(c) && !c->have_G && !c->slab))))
+    if (enable && !(c && (tess_multi_store(c) || (tess_mag_store(c) && !c->have_G && !c->work_ready))))
         TRY(dense_single_chain_refuse(c, "gh_set_shift_invariant"));
-    if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_shift_invariant: call before gh_build_G");
+    if (c->have_G || c->work_ready) return fail(c, GH_ERR_ARG, "gh_set_shift_invariant: call before gh_build_G");
     if (enable && c->lat) return fail(c, GH_ERR_ARG, "gh_set_shift_invariant: %s is switched on: one form at a time", LATTICE_NAME);
     // (the store is a flavour of the matrix-free mode -- G is never stored -- so enabling it sets c->mf;
     // disabling it puts c->mf back to what gh_set_matrix_free last asked for)
@@ -838,7 +836,7 @@ int gh_set_translation_invariant(gh_ctx *c, int enable)
         return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: enable must be 0, 1, 2 or 4 (2: the table that takes chain "
                                    "batches; 4: the table that takes the bootstrap batch)");
     if (enable) TRY(dense_single_chain_refuse(c, "gh_set_translation_invariant"));
-    if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: call before gh_build_G");
+    if (c->have_G || c->work_ready) return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: call before gh_build_G");
     if (lattice_multi(c))
         return fail(c, GH_ERR_UNSUPPORTED, "gh_set_translation_invariant: %s was set onto %s with its cells "
                                            "(gh_set_cells_multi_table): the table is this context's form", store_name(c),
@@ -1036,7 +1034,7 @@ int gh_set_matrix_free_exact(gh_ctx *c, int exact)
 {
     GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
-    if (c->have_G || c->slab) return fail(c, GH_ERR_ARG, "gh_set_matrix_free_exact: call before gh_build_G");
+    if (c->have_G || c->work_ready) return fail(c, GH_ERR_ARG, "gh_set_matrix_free_exact: call before gh_build_G");
     c->mf_exact_req = exact != 0 ? 1 : 0;
     return GH_OK;
 }
@@ -1076,7 +1074,7 @@ int gh_build_G(gh_ctx *c)
     c->warn_cells = 0;
     c->leaves = 0;
     if (c->mf) {
-        if (c->slab) return fail(c, GH_ERR_ARG, "gh_build_G: a matrix-free context is built once");
+        if (c->work_ready) return fail(c, GH_ERR_ARG, "gh_build_G: a matrix-free context is built once");
         // (a store of blocks: the tesseroid forms and the prisms' multi-component store get here, by way of their tables)
         if (c->lat) {
             if (!c->lat->multi) TRY(dense_single_chain_refuse(c, "gh_build_G on the translation-invariant store"));
@@ -1494,7 +1492,7 @@ int gh_forward(gh_ctx *c, const double *mw, double *dpre)
     if (!c || !mw || !dpre) return fail(c, GH_ERR_ARG, "gh_forward: null pointer");
     TRY(need(c, c->have_G, "gh_forward: no kernel matrix resident"));
     HIPCHK(c, hipSetDevice(c->device));
-    TRY(ensure_work(c));
+    TRY(ensure_work(c, "gh_forward"));
     TRY(h2d(c, c->tmpM, mw, (size_t)c->M));
     SweepArgs a{};
     a.mode = SW_FWD;
@@ -1516,7 +1514,7 @@ int gh_adjoint(gh_ctx *c, const double *r, double *g)
     if (!c || !r || !g) return fail(c, GH_ERR_ARG, "gh_adjoint: null pointer");
     TRY(need(c, c->have_G, "gh_adjoint: no kernel matrix resident"));
     HIPCHK(c, hipSetDevice(c->device));
-    TRY(ensure_work(c));
+    TRY(ensure_work(c, "gh_adjoint"));
     HIPCHK(c, hipMemsetAsync(c->tmpN, 0, sizeof(double) * (size_t)c->ld * (c->joint ? 2 : 1), c->stream));
     TRY(h2d_obsvec(c, c->tmpN, r));
     SweepArgs a{};
@@ -1539,7 +1537,7 @@ int gh_misfit_and_grad(gh_ctx *c, const double *x, double out3[3], double *grad,
     TRY(need(c, c->have_G && c->have_data && c->have_reg,
              "gh_misfit_and_grad: needs a kernel matrix, gh_set_data and gh_set_reg"));
     HIPCHK(c, hipSetDevice(c->device));
-    TRY(ensure_work(c));
+    TRY(ensure_work(c, "gh_misfit_and_grad"));
     const gh_ctx::StateSet &o = c->st[3];
     TRY(h2d(c, c->xb[3], x, (size_t)c->M));
     TRY(eval_forward(c, c->xb[3], o));
@@ -1550,16 +1548,17 @@ int gh_misfit_and_grad(gh_ctx *c, const double *x, double out3[3], double *grad,
     a.g_out = c->tmpM;
     TRY(launch_sweep(c, a));
     TRY(scal_ready(c, o));
-    HIPCHK(c, hipMemcpyAsync(c->h_scal, o.scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    double *h = c->h_scal + c->work.h_state(), *h_phi = c->h_scal + c->work.h_phi();
+    HIPCHK(c, hipMemcpyAsync(h, o.scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     const bool cg_on = coupling_on(c);
-    if (cg_on) HIPCHK(c, hipMemcpyAsync(c->h_scal + 8, o.phi, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (cg_on) HIPCHK(c, hipMemcpyAsync(h_phi, o.phi, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     TRY(d2h(c, grad, c->tmpM, (size_t)c->M));
     if (dpre) TRY(d2h_obsvec(c, dpre, o.d));
     TRY(lonsym_epilogue_check(c));
-    c->cg.phi_last = cg_on ? c->h_scal[8] : 0.0;
-    out3[0] = c->h_scal[2];
-    out3[1] = c->h_scal[0];
-    out3[2] = c->h_scal[1];
+    c->cg.phi_last = cg_on ? *h_phi : 0.0;
+    out3[0] = h[2];
+    out3[1] = h[0];
+    out3[2] = h[1];
     return GH_OK;
 }
 
@@ -1578,35 +1577,25 @@ int gh_reg_eval(gh_ctx *c, int kind, double beta, const int shape3[3], int ms_gr
                                                 : "gh_reg_eval: Smoothness/TV need shape nz*ny*nx == M");
     if (kind == GH_REG_MS) TRY(need(c, c->weighted, "gh_reg_eval: MS needs gh_weight first (uses Wm^2)"));
     HIPCHK(c, hipSetDevice(c->device));
-    TRY(ensure_work(c));
+    TRY(ensure_work(c, "gh_reg_eval"));
     double *dx = c->xb[3], *dapr = c->st[3].greg, *dg = c->tmpM;
     TRY(h2d(c, dx, mw, (size_t)c->M));
     TRY(h2d(c, dapr, mwapr, (size_t)c->M));
     // (joint and magnetization-vector stores: one property at a time, in one launch -- fd3djoint: the stencil never
     // crosses into the next block)
-    const int props = reg_props(c);
-    const int64_t m = c->M / props;
-    RegArgs ra{};
+    RegArgs ra = reg_args(c, dx, dg, -1);
     ra.ms_grad_den_mw = ms_grad_den_mw;
     ra.kind = kind;
-    ra.M = m;
     ra.nz = shape3 ? shape3[0] : 1;
     ra.ny = shape3 ? shape3[1] : 1;
-    ra.nx = shape3 ? shape3[2] : (int)m;
+    ra.nx = shape3 ? shape3[2] : (int)ra.M;
     ra.alpha = 1.0;
     ra.beta = beta;
-    ra.x = dx;
     ra.mwapr = dapr;
-    ra.wm2 = c->wm2;
-    ra.greg = dg;
-    ra.regpart = c->regpart;
-    ra.nprop = props;
-    ra.nrb = (int)((m + 255) / 256);
-    reg_kernel<<<dim3(c->n_regpart), dim3(256), 0, c->stream>>>(ra);
-    sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->regpart, c->n_regpart, c->st[3].scal);
+    reg_kernel<<<dim3(c->work.n_regpart), dim3(256), 0, c->stream>>>(ra);
+    sum_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(c->regpart, c->work.n_regpart, c->st[3].scal);
     HIPCHK(c, hipGetLastError());
-    TRY(d2h(c, c->h_scal, c->st[3].scal, 2));
-    *value = c->h_scal[0];
+    TRY(read_value(c, c->st[3].scal, value));
     if (grad) TRY(d2h(c, grad, dg, (size_t)c->M));
     return GH_OK;
 }
@@ -1648,7 +1637,7 @@ int gh_compress_wavelet(gh_ctx *c, int dims, const int shape3[3], double thr, in
     w.thr = thr;
     wavelet_plan(w);
     HIPCHK(c, hipSetDevice(c->device));
-    TRY(ensure_work(c));
+    TRY(ensure_work(c, "gh_compress_wavelet"));
     const int64_t N = c->N, M = c->M, Mp = w.Mp;
     // row chunks: 4 buffers of chunk x Mp doubles, bounded to ~2 GB in total
     int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(512 << 20) / (Mp * 8)));
@@ -1776,7 +1765,7 @@ int gh_chain_init(gh_ctx *c, const double *x0, const double *low, const double *
     TRY(need(c, c->have_G && c->have_data && c->have_reg,
              "gh_chain_init: needs a kernel matrix, gh_set_data and gh_set_reg"));
     HIPCHK(c, hipSetDevice(c->device));
-    TRY(ensure_work(c));
+    TRY(ensure_work(c, "gh_chain_init"));
     c->cur = 0;
     c->xcur = 0;
     c->spec_valid = c->pn_valid = false;
@@ -1787,17 +1776,13 @@ int gh_chain_init(gh_ctx *c, const double *x0, const double *low, const double *
     TRY(h2d(c, c->high, high, (size_t)c->M));
     TRY(eval_forward(c, c->xb[0], c->st[0]));
     TRY(scal_ready(c, c->st[0]));
-    TRY(d2h(c, c->h_scal, c->st[0].scal, 4));
+    double U[3];
+    TRY(read_state_scalars(c, c->st[0], U));
     c->cg.phi_cur = 0.0;
-    if (coupling_on(c)) {
-        TRY(d2h(c, c->h_scal + 8, c->st[0].phi, 1));
-        c->cg.phi_cur = c->h_scal[8];
-    }
+    if (coupling_on(c)) TRY(read_value(c, c->st[0].phi, &c->cg.phi_cur));
     c->cg.phi_last = c->cg.phi_cur;
     TRY(lonsym_epilogue_check(c));
-    c->U_cur[0] = c->h_scal[2];
-    c->U_cur[1] = c->h_scal[0];
-    c->U_cur[2] = c->h_scal[1];
+    std::copy(U, U + 3, c->U_cur);  // (only of an evaluation that stands)
     c->chain_ready = true;
     return GH_OK;
 }
@@ -1810,10 +1795,10 @@ int gh_chain_prefetch_momentum(gh_ctx *c, const double *p0_next)
     HIPCHK(c, hipSetDevice(c->device));
     TRY(h2d(c, c->pn, p0_next, (size_t)c->M));
     // initial kinetic energy of that trajectory, summed exactly like the non-speculative path
-    sumsq_kernel<<<dim3(c->n_pp0), dim3(256), 0, c->stream>>>(c->pn, c->M, c->pp0_part);
+    sumsq_kernel<<<dim3(c->work.pp0), dim3(256), 0, c->stream>>>(c->pn, c->M, c->pp0_part);
     {
-        std::vector<double> part((size_t)c->n_pp0);
-        TRY(d2h(c, part.data(), c->pp0_part, (size_t)c->n_pp0));
+        std::vector<double> part((size_t)c->work.pp0);
+        TRY(d2h(c, part.data(), c->pp0_part, (size_t)c->work.pp0));
         double s = 0.0;
         for (double v : part) s += v;
         c->pn_pp0 = s;
@@ -2128,7 +2113,7 @@ int gh_batch_init(gh_ctx *c, int C, const double *x0s, const double *low, const 
                                                   sizeof(double) <= (size_t)c->rs.lds_max))
         return fail(c, GH_ERR_UNSUPPORTED, "batched chains with the wavelet-compressed forward need a problem "
                                            "small enough for the resident chain kernel");
-    TRY(ensure_work(c));
+    TRY(ensure_work(c, "gh_batch_init"));
     TRY(h2d(c, c->low, low, (size_t)c->M));
     TRY(h2d(c, c->high, high, (size_t)c->M));
     gh_ctx::Resident &r = c->rs;
@@ -2291,6 +2276,22 @@ int gh_batch_run(gh_ctx *c, int T, const int *L, const double *const *p0s, const
     }
     // fp64-MFMA batch, the chains desynchronised (host_batchrun.h)
     return BatchRun{c, T, L, p0s, us, dt, accepted, out5s, x_out, n_done != nullptr}.go(n_started, n_done);
+}
+
+// Diagnostic: the layout the work buffers were allocated by (host_layout.h), so that a
+// test can assert the epilogue form it meant to reach.  out[0..15]: allocated (0 / 1), slab rows, slab2 segments, pp,
+// pp0, dsum, bsum, n_dpart, n_regpart, R blocks per property, form of `part` (WORK_PART_*), size of `part`,
+// offset of R in `part`, offset of the coupling term in `part`, size of h_scal, slab rows the last forward wrote.
+int gh_debug_work_layout(const gh_ctx *c, int64_t *out)
+{
+    GH_FEED_GUARD(c);
+    if (!c || !out) return GH_ERR_ARG;
+    const WorkLayout &w = c->work;
+    const int64_t v[16] = {c->work_ready ? 1 : 0, w.slab_rows, w.slab2_rows, w.pp, w.pp0, w.dsum, w.bsum, w.n_dpart,
+                           w.n_regpart, w.reg_blocks, w.part_form, w.size(), w.reg(0), w.coupling(), (int64_t)w.h_size(),
+                           c->slab_live};
+    std::copy(v, v + 16, out);
+    return GH_OK;
 }
 
 // Diagnostic (not in the public header): accumulated phase times of the shift-invariant pass
@@ -2541,7 +2542,7 @@ int gh_debug_stream_read(gh_ctx *c, int blocks, int threads, int nt, int reps, d
     GH_FEED_GUARD(c);
     if (!c || !c->have_G) return GH_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    TRY(ensure_work(c));
+    TRY(ensure_work(c, "gh_debug_stream_read"));
     hipEvent_t e0, e1;
     HIPCHK(c, hipEventCreate(&e0));
     HIPCHK(c, hipEventCreate(&e1));

@@ -165,6 +165,8 @@ static int mft_launch(gh_ctx *c, SweepArgs &a)
     gh_ctx::Batch &b = c->bt;
     a.ld = c->ld;
     a.M = c->M;
+    // (slab rows: one per range, one more for the near field)
+    if (a.mode & SW_FWD) TRY(slab_live_set(c, "matrix-free team pass", t.ranges + (b.mfb_near ? 1 : 0)));
     TRY(xg_prepare(c, t.xg, false, (uint64_t)t.tpr + 2));
     const double *wm = c->weighted ? c->wm : nullptr;
     if (b.mfb_near)
@@ -183,16 +185,11 @@ static int mft_launch(gh_ctx *c, SweepArgs &a)
     t.xg.tag += (unsigned)t.tpr + 1u;
     t.xg.inflight = true;
     t.launches += 1;
-    if (a.mode & SW_FWD) {
-        int rows = t.ranges;
-        if (b.mfb_near) {
-            const double *x = (a.mode & SW_UPD) ? a.x_out : a.x_in;
-            HIPCHK(c, hipMemsetAsync(a.slab + (size_t)rows * (size_t)c->ld, 0, sizeof(double) * (size_t)c->ld, c->stream));
-            mf1_near_forward_kernel<<<dim3((unsigned)c->N), dim3(64), 0, c->stream>>>(b.rptr, b.rcol, b.rdelta, c->N, x, wm,
-                                                                                     a.slab + (size_t)rows * (size_t)c->ld);
-            rows += 1;
-        }
-        c->slab_live = rows;
+    if ((a.mode & SW_FWD) && b.mfb_near) {
+        const double *x = (a.mode & SW_UPD) ? a.x_out : a.x_in;
+        double *row = a.slab + (size_t)t.ranges * (size_t)c->ld;
+        HIPCHK(c, hipMemsetAsync(row, 0, sizeof(double) * (size_t)c->ld, c->stream));
+        mf1_near_forward_kernel<<<dim3((unsigned)c->N), dim3(64), 0, c->stream>>>(b.rptr, b.rcol, b.rdelta, c->N, x, wm, row);
     }
     HIPCHK(c, hipGetLastError());
     return GH_OK;

@@ -80,7 +80,7 @@ static int bscg_run(gh_ctx *c, int B, const double *counts, const double *dobs, 
     gh_ctx::Batch &b = c->bt;
     gh_ctx::Bscg &s = c->bs;
     const int64_t M = c->M, N = c->N, ld = c->ld;
-    TRY(ensure_work(c));
+    TRY(ensure_work(c, "gh_bscg_run"));
     TRY(batch_alloc(c));
     // (the adjoint's operand-ordered copy of G where HBM has room -- a second ld x M doubles that stay until
     // gh_destroy, also on a context whose chain batch runs on teams and would not make it; the same bits without)

@@ -116,7 +116,7 @@ static int check_context(gh_ctx *c, const CellStore &s, const char *name)
         "(gh_set_cells_tess_mag_table)",
         // (the table may have been asked for already: it is the one form besides the dense store)
         "has no matrix-free mode (dense, or the shift-invariant store)"};
-    if (c->joint || c->mvi || c->mc.n > 0 || c->have_obs || c->have_cells || c->have_G || c->slab)
+    if (c->joint || c->mvi || c->mc.n > 0 || c->have_obs || c->have_cells || c->have_G || c->work_ready)
         return fail(c, GH_ERR_ARG, "%s: call it first on a fresh context (before gh_set_obs)", s.entry);
     if (s.table == TABLE_ANY ? c->mf && !c->ls : c->mf || c->ls)
         return fail(c, GH_ERR_UNSUPPORTED, "%s: %s %s", s.entry, name, forms[s.table]);

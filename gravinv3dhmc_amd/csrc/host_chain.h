@@ -8,10 +8,7 @@ static int chain_state_fresh(gh_ctx *c)
     if (!c->st_stale) return GH_OK;
     TRY(eval_forward(c, c->xb[c->xcur], c->st[c->cur]));
     TRY(scal_ready(c, c->st[c->cur]));
-    TRY(d2h(c, c->h_scal, c->st[c->cur].scal, 4));
-    c->U_cur[0] = c->h_scal[2];
-    c->U_cur[1] = c->h_scal[0];
-    c->U_cur[2] = c->h_scal[1];
+    TRY(read_state_scalars(c, c->st[c->cur], c->U_cur));
     c->st_stale = false;
     return GH_OK;
 }
@@ -50,6 +47,7 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
     } teams_guard{c};
     c->chain_teams_ok = true;
     const size_t M = (size_t)c->M;
+    const WorkLayout &w = c->work;
     const int nt = c->n_teams;
     // Was the first step of this trajectory already taken speculatively by the previous call's
     // last sweep (same momentum, same dt, previous proposal accepted)?
@@ -65,7 +63,7 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
     } else {
         // momentum upload + kinetic energy of p0 (hmc.py:95-104)
         HIPCHK(c, hipMemcpyAsync(c->pb[0], p0, M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        sumsq_kernel<<<dim3(c->n_pp0), dim3(256), 0, c->stream>>>(c->pb[0], c->M, c->pp0_part);
+        sumsq_kernel<<<dim3(c->work.pp0), dim3(256), 0, c->stream>>>(c->pb[0], c->M, c->pp0_part);
         xin = c->xcur;
         pin = 0;
         sin = c->cur;
@@ -114,7 +112,7 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
         HIPCHK(c, hipEventRecord(c->copy_ev, c->copy_stream));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->copy_ev, 0));
         // its initial kinetic energy, summed exactly like gh_chain_prefetch_momentum does
-        sumsq_kernel<<<dim3(c->n_pp0), dim3(256), 0, c->stream>>>(c->pn, c->M, c->pn0_part);
+        sumsq_kernel<<<dim3(c->work.pp0), dim3(256), 0, c->stream>>>(c->pn, c->M, c->pn0_part);
         probe[0] = p0_next[0];
         probe[1] = p0_next[c->M / 2];
         probe[2] = p0_next[c->M - 1];
@@ -145,23 +143,23 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
         TRY(launch_sweep(c, a));
         if (spec) TRY(finalize(c, c->xb[xs], c->st[ss]));
     }
-    double *h = c->h_scal;
+    double *h = c->h_scal, *h_pp = h + w.h_pp(), *h_pp0 = h + w.h_pp0(), *h_pn0 = h + w.h_pn0();
     TRY(scal_ready(c, c->st[sin]));
     if (spec) TRY(scal_ready(c, c->st[ss]));
-    HIPCHK(c, hipMemcpyAsync(h, c->st[sin].scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h + w.h_state(), c->st[sin].scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     const bool cg_on = coupling_on(c);  // (cross-gradient or amplitude term: Phi has a slot per state set)
-    if (cg_on) HIPCHK(c, hipMemcpyAsync(h + 8, c->st[sin].phi, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h + 16, c->pp_part, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost,
+    if (cg_on) HIPCHK(c, hipMemcpyAsync(h + w.h_phi(), c->st[sin].phi, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_pp, c->pp_part, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost,
                              c->stream));
     if (spec) {
-        HIPCHK(c, hipMemcpyAsync(h + 4, c->st[ss].scal, 4 * sizeof(double), hipMemcpyDeviceToHost,
+        HIPCHK(c, hipMemcpyAsync(h + w.h_spec(), c->st[ss].scal, 4 * sizeof(double), hipMemcpyDeviceToHost,
                                  c->stream));
     }
     if (!use_spec)
-        HIPCHK(c, hipMemcpyAsync(h + 16 + 2 * nt, c->pp0_part, (size_t)c->n_pp0 * sizeof(double),
+        HIPCHK(c, hipMemcpyAsync(h_pp0, c->pp0_part, (size_t)w.pp0 * sizeof(double),
                                  hipMemcpyDeviceToHost, c->stream));
     if (pn_deferred)
-        HIPCHK(c, hipMemcpyAsync(h + 16 + 2 * nt + c->n_pp0, c->pn0_part, (size_t)c->n_pp0 * sizeof(double),
+        HIPCHK(c, hipMemcpyAsync(h_pn0, c->pn0_part, (size_t)w.pp0 * sizeof(double),
                                  hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // a team sweep of this trajectory gave up (its workgroups were not all resident): nothing of
@@ -180,15 +178,15 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
     if (failed && c->sh.kind == 0) return redo();
     if (pn_deferred) {
         double s = 0.0;
-        for (int t = 0; t < c->n_pp0; ++t) s += h[16 + 2 * nt + c->n_pp0 + t];
+        for (int t = 0; t < w.pp0; ++t) s += h_pn0[t];
         pn_pp0 = s;
     }
     double pp1 = 0.0, pp0 = 0.0;
-    for (int t = 0; t < nt; ++t) pp1 += h[16 + t];
+    for (int t = 0; t < nt; ++t) pp1 += h_pp[t];
     if (use_spec)
         pp0 = c->spec_pp0;
     else
-        for (int t = 0; t < c->n_pp0; ++t) pp0 += h[16 + 2 * nt + t];
+        for (int t = 0; t < w.pp0; ++t) pp0 += h_pp0[t];
     double pn_pp0_g = pn_pp0;
     if (shard_cols(c)) {
         // kinetic energies are sums over cells: combine the ranks' parts (same bits everywhere)
@@ -205,11 +203,11 @@ static int chain_trajectory_impl(gh_ctx *c, const double *p0, double dt, int L, 
         if (!use_spec) pp0 = v[1];
         pn_pp0_g = v[2];
     }
-    const bool acc = metropolis_step(pp0, pp1, h, u, c->U_cur, out5);
+    const bool acc = metropolis_step(pp0, pp1, h + w.h_state(), u, c->U_cur, out5);
     if (acc) {
         c->xcur = xin;
         c->cur = sin;
-        if (cg_on) c->cg.phi_cur = h[8];
+        if (cg_on) c->cg.phi_cur = h[w.h_phi()];
         if (spec) {
             c->spec_valid = true;
             c->spec_dt = dt;

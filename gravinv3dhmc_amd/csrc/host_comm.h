@@ -115,6 +115,11 @@ static int shard_rows_init(gh_ctx *c, int rank, int world, int64_t N_global, int
     if (n0 < 0 || n0 + c->N > N_global) return fail(c, GH_ERR_ARG, "gh_shard_init_rows: observation range outside the problem");
     if (c->mf) return fail(c, GH_ERR_UNSUPPORTED, "row blocks need the stored kernel");
     if (c->wv.on) return fail(c, GH_ERR_UNSUPPORTED, "gh_shard_init_rows comes before gh_compress_wavelet (every rank compresses its own rows)");
+    // (the partial sums of p'p come from vec_update_kernel: one per 256 cells)
+    const int n_pp = std::max(c->n_teams, (int)((c->M + 255) / 256));
+    if (c->work_ready && n_pp > c->work.pp)
+        return fail(c, GH_ERR_ARG, "gh_shard_init_rows: call before the first evaluation (row blocks keep %d partial sums of p'p, "
+                                   "the work buffers sized at the first evaluation hold %d)", n_pp, c->work.pp);
     c->sh.axis = 1;
     c->sh.rank = rank;
     c->sh.world = world;
@@ -127,8 +132,7 @@ static int shard_rows_init(gh_ctx *c, int rank, int world, int64_t N_global, int
     if (!c->sh.hbuf) HIPCHK(c, hipHostMalloc((void **)&c->sh.hbuf, sizeof(double) * need));
     c->sh.buf_n = need;
     TRY(dalloc(c, &c->sh.rbuf, 8));
-    // (the partial sums of p'p come from vec_update_kernel: one per 256 cells)
-    c->n_teams = std::max(c->n_teams, (int)((c->M + 255) / 256));
+    c->n_teams = n_pp;
     c->chain_ready = false;
     c->bt.ready = false;
     c->rs.state = -1;  // (the resident chain kernel has no exchange between GPUs)

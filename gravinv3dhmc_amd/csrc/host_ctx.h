@@ -2,6 +2,8 @@
 // HBM) and the small helpers every other part uses.  Included once by gravhmc.hip.
 #pragma once
 
+#include "host_layout.h"
+
 static thread_local std::string g_create_error;
 
 struct LonSymHost;  // host_lonsym.h
@@ -204,13 +206,13 @@ struct gh_ctx {
     int spec_set = 0, spec_x = 0, spec_p = 0;
     int64_t spec_hits = 0, spec_misses = 0, accept_count = 0;
     double *slab2 = nullptr;
-    int slab2_rows = 0;
     double *slab = nullptr, *dpart = nullptr, *regpart = nullptr, *pp_part = nullptr,
            *ppn_part = nullptr, *pp0_part = nullptr, *pn0_part = nullptr, *scal_all = nullptr;
     double *tmpM = nullptr, *tmpN = nullptr;
-    int n_dpart = 0, n_regpart = 0, n_pp0 = 0;
-    double *h_scal = nullptr;  // pinned: scalars + partial sums
-    size_t h_scal_n = 0;
+    // the layout ensure_work allocated them by (host_layout.h); work_ready: they exist, sized once, never again
+    WorkLayout work;
+    bool work_ready = false, work_epilogue1 = true;
+    double *h_scal = nullptr;  // pinned: scalars + partial sums, laid out by work.h_*()
     bool chain_ready = false;
     double U_cur[3] = {0, 0, 0};
     bool st_stale = false;  // the resident chain kernel moved x: st[cur] / U_cur are those of an older sample

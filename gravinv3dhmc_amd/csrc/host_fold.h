@@ -648,12 +648,13 @@ static int fold_use(gh_ctx *c, bool *use)
         (void)hipGetLastError();
         occ = 1;
     }
-    // (never more workgroups than the dense sweep's slab rows and pp partials)
     const int64_t items = f.pair_on ? f.n_work : f.n_orb;
     int grid = (int)std::min<int64_t>(std::min<int64_t>((int64_t)c->cus * occ, c->grid), items);
     const int64_t per_team = (items + grid - 1) / grid;
     f.orb_per_team = f.work_per_team = per_team;
     f.grid = (int)((items + per_team - 1) / per_team);
+    // (a slab row, a slab-row sum and a pp partial per workgroup: within the dense sweep's, host_layout.h)
+    TRY(work_claim(c, "fold_use", WorkDemand{f.grid, f.grid, f.grid}));
     TRY(fold_build(c));
     if (!(f.max_dev <= FOLD_MAX_DEV)) {
         f.reason = GH_FOLD_DEVIATION;

@@ -362,11 +362,10 @@ static int lattice_build(gh_ctx *c)
 }
 
 // configure_mf of the store: slab rows = chunks of layers, |p|^2 partials = the adjoint's workgroups
-static void lattice_configure(gh_ctx *c)
+static int lattice_configure(gh_ctx *c)
 {
     const LatticeHost &h = *c->lat;
-    c->grid = h.chunks;
-    c->n_teams = h.gx_adj * h.g.nz;
+    return set_partition(c, "lattice_configure", h.chunks, (int64_t)h.gx_adj * h.g.nz);
 }
 
 static int launch_lattice(gh_ctx *c, SweepArgs &a, const double *wm)

@@ -318,23 +318,55 @@ static int64_t lonsym_table_bytes(const gh_ctx *c);
 static int fold_use(gh_ctx *c, bool *use);  // host_fold.h
 static int launch_fold(gh_ctx *c, SweepArgs &a);
 static bool lattice_on(const gh_ctx *c);  // host_lattice.h
-static void lattice_configure(gh_ctx *c);
+static int lattice_configure(gh_ctx *c);
 static int launch_lattice(gh_ctx *c, SweepArgs &a, const double *wm);
+
+// what the work buffers' sizes depend on, as the context stands (WorkShape's members, in their order)
+static WorkShape work_shape(const gh_ctx *c)
+{
+    return WorkShape{c->M, c->ld, c->N, c->grid, c->n_teams, c->n_panels, c->TW, c->joint, c->mvi, c->mc.n, store_cells(c),
+                     c->mf, lonsym_on(c), lonsym_one_row(c), lonsym_on(c) ? lonsym_classes(c) : 0, shard_rows(c),
+                     c->work_epilogue1};
+}
+
+// A producer states what it is about to write (host_layout.h: WorkDemand).  Before the first evaluation nothing is
+// allocated and ensure_work sizes the buffers for the context as it then stands; afterwards they stay as they are,
+// and a demand they cannot hold is an error here, on the host, before anything is launched.
+static int work_claim(gh_ctx *c, const char *who, const WorkDemand &d)
+{
+    int64_t need_n = 0, have_n = 0;
+    const char *what = c->work_ready ? work_exceeds(c->work, d, &need_n, &have_n) : nullptr;
+    if (!what) return GH_OK;
+    return fail(c, GH_ERR_ARG, "%s: needs %lld %s, the work buffers sized at the first evaluation hold %lld", who,
+                (long long)need_n, what, (long long)have_n);
+}
+
+// the partition of a pass: workgroups that write a slab row each, |p|^2 partials
+static int set_partition(gh_ctx *c, const char *who, int64_t grid, int64_t n_teams)
+{
+    c->grid = (int)grid;
+    c->n_teams = (int)n_teams;
+    return work_claim(c, who, work_demand_of(work_layout(work_shape(c))));
+}
+
+// The forward launch `who` writes `rows` slab rows and, where the epilogue takes sums, `sums` of them (0: one per
+// slab row -- per row and row block on the multi-component store).
+static int slab_live_set(gh_ctx *c, const char *who, int rows, int sums = 0)
+{
+    TRY(work_claim(c, who, WorkDemand{rows, sums > 0 ? sums : (int64_t)std::max(c->mc.n, 1) * rows, 0}));
+    c->slab_live = rows;
+    c->dsum_n = sums;
+    return GH_OK;
+}
 
 // Partition of the matrix-free passes.  N <= 16384: the fused pass (one workgroup per column at a
 // time, columns dealt round-robin); else the two-pass form (one wave per cell for the adjoint,
 // chunks of cells per forward partial).
 static int configure_mf(gh_ctx *c)
 {
-    if (lonsym_on(c)) {
-        c->grid = lonsym_grid(c);  // one workgroup per cell row at a time, rows dealt round-robin
-        c->n_teams = c->grid;
-        return GH_OK;
-    }
-    if (lattice_on(c)) {
-        lattice_configure(c);  // slab rows: chunks of layers; |p|^2 partials: the adjoint's workgroups
-        return GH_OK;
-    }
+    // (one workgroup per cell row at a time, rows dealt round-robin)
+    if (lonsym_on(c)) return set_partition(c, "configure_mf", lonsym_grid(c), lonsym_grid(c));
+    if (lattice_on(c)) return lattice_configure(c);  // slab rows: chunks of layers; |p|^2 partials: the adjoint's workgroups
     if (c->mf_fused) {
         const int64_t ld = c->ld;
         c->mf_T = ld <= 2048 ? 256 : 1024;
@@ -362,15 +394,12 @@ static int configure_mf(gh_ctx *c)
             occ = 1;
         }
         occ = env_int("GRAVHMC_MF_WG_PER_CU", occ);
-        c->grid = (int)std::min<int64_t>(c->M, (int64_t)c->cus * occ);
-        c->n_teams = c->grid;  // one partial of p^2 per workgroup
-        return GH_OK;
+        const int64_t grid = std::min<int64_t>(c->M, (int64_t)c->cus * occ);
+        return set_partition(c, "configure_mf", grid, grid);  // one partial of p^2 per workgroup
     }
-    c->n_teams = (int)((c->M + 3) / 4);
     const int64_t chunks = std::min<int64_t>(c->M, std::max<int64_t>(1, (int64_t)c->cus * 16 / std::max<int64_t>(1, (c->ld + 255) / 256)));
     c->mf_cells_per_chunk = (c->M + chunks - 1) / chunks;
-    c->grid = (int)((c->M + c->mf_cells_per_chunk - 1) / c->mf_cells_per_chunk);
-    return GH_OK;
+    return set_partition(c, "configure_mf", (c->M + c->mf_cells_per_chunk - 1) / c->mf_cells_per_chunk, (c->M + 3) / 4);
 }
 
 // matrix-free counterpart of one sweep: the fused pass, or adjoint/update pass then forward pass
@@ -481,7 +510,7 @@ static bool team_plan(gh_ctx *c)
     t.tpx = std::min(32, c->cus / 8) / t.Q;  // blocks with equal blockIdx % 8 share an XCD: 32 CUs each
     if (t.tpx < 1) return false;
     t.grid = 8 * t.tpx * t.Q;
-    const int n_teams = 8 * t.tpx;
+    const int n_teams = 8 * t.tpx;  // (a slab row each, claimed at the launch)
     t.cols_per_team = (c->M + n_teams - 1) / n_teams;
     t.lds = (size_t)t.panel_rows * (size_t)t.lag * sizeof(double) + lds_small;
     team_fn f = team_kernel_for(t.threads, t.ept2, t.depth, t.lag);
@@ -578,9 +607,12 @@ static void team_resume(gh_ctx *c)
 static int launch_sweep(gh_ctx *c, SweepArgs &a)
 {
     if (a.mode & SW_FWD) {
-        c->slab_live = c->grid;
         c->dsum_live = false;
-        c->dsum_n = 0;
+        // (harmonic and wide shift-invariant forms: ONE finished slab row; the sums come per class of observations)
+        if (c->mf && lonsym_one_row(c))
+            TRY(slab_live_set(c, "shift-invariant pass", 1, lonsym_classes(c)));
+        else
+            TRY(slab_live_set(c, "sweep", c->grid));
     }
     if (c->mf) {
         if (lonsym_on(c) && (a.mode & SW_FWD) && c->dsum) {
@@ -589,52 +621,9 @@ static int launch_sweep(gh_ctx *c, SweepArgs &a)
         }
         // (tesseroid multi-component store: the classes' sums are the row blocks' partials, host_eval.h)
         if (lonsym_one_row(c) && (a.mode & SW_FWD) && c->mc.n > 0) a.dsum = c->mc.bsum;
-        if (lonsym_one_row(c) && (a.mode & SW_FWD)) {
-            // (harmonic form: ONE finished slab row; the sums come per class of observations)
-            c->slab_live = 1;
-            c->dsum_n = lonsym_classes(c);
-        }
         return launch_mf(c, a);
     }
-    if (shard_rows(c)) {
-        // Row blocks: the dot of a column with r spans the ranks.  Adjoint of the local rows (panel by panel)
-        // into the gradient buffer -- alpha grad R added by rank 0 only --, all-reduce of its M doubles,
-        // elementwise update (replicated: every rank holds the whole model), forward of the local rows: TWO
-        // reads of the local shard per leapfrog step.
-        const SweepArgs full = a;
-        auto panel = [&](SweepArgs &s, int p) {
-            s.row0 = (int64_t)p * c->panel_rows;
-            s.rows = c->n_panels == 1 ? c->ld : std::min<int64_t>(c->panel_rows, c->ld - s.row0);
-        };
-        if (full.mode & SW_ADJ) {
-            double *gdst = (full.mode & SW_GOUT) ? full.g_out : c->gbuf;
-            for (int p = 0; p < c->n_panels; ++p) {
-                SweepArgs s = full;
-                s.mode = SW_ADJ | SW_GOUT | (p ? SW_GACC : 0);
-                s.greg = (p == 0 && c->sh.rank == 0) ? full.greg : nullptr;
-                s.g_out = gdst;
-                panel(s, p);
-                TRY(launch_sweep_one(c, s));
-            }
-            TRY(comm_allreduce(c, gdst, c->M));
-            if (full.mode & (SW_UPD | SW_PFIN)) {
-                SweepArgs u = full;
-                vec_update_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(u, gdst, c->M, c->n_teams);
-                HIPCHK(c, hipGetLastError());
-            }
-        }
-        if (full.mode & SW_FWD) {
-            for (int p = 0; p < c->n_panels; ++p) {
-                SweepArgs s = full;
-                s.mode = SW_FWD;
-                s.x_in = (full.mode & SW_UPD) ? full.x_out : full.x_in;
-                panel(s, p);
-                TRY(launch_sweep_one(c, s));
-            }
-        }
-        return GH_OK;
-    }
-    if (c->n_panels == 1) {
+    if (c->n_panels == 1 && !shard_rows(c)) {
         a.row0 = 0;
         a.rows = c->ld;
         if ((a.mode & SW_FWD) && c->TW > 1 && c->dsum) {
@@ -644,7 +633,7 @@ static int launch_sweep(gh_ctx *c, SweepArgs &a)
         bool fold = false;
         TRY(fold_use(c, &fold));  // (builds the folded store at the first sweep after the store changed)
         if (fold) {
-            if (a.mode & SW_FWD) c->slab_live = c->fd.grid;
+            if (a.mode & SW_FWD) TRY(slab_live_set(c, "folded sweep", c->fd.grid));
             return launch_fold(c, a);
         }
         return launch_sweep_one(c, a);
@@ -652,23 +641,30 @@ static int launch_sweep(gh_ctx *c, SweepArgs &a)
     // more rows than one workgroup holds of a column.  The fused step (adjoint + update + forward)
     // runs on teams of workgroups: one read of G.  Adjoint-only and forward-only sweeps read G once
     // in row panels anyway.
-    if ((a.mode & SW_ADJ) && (a.mode & SW_FWD) && !(a.mode & SW_GACC) && team_plan(c) && c->tm.state == 1) {
-        c->slab_live = 8 * c->tm.tpx;
+    if (!shard_rows(c) && (a.mode & SW_ADJ) && (a.mode & SW_FWD) && !(a.mode & SW_GACC) && team_plan(c) && c->tm.state == 1) {
+        TRY(slab_live_set(c, "team sweep", 8 * c->tm.tpx));
         return launch_team(c, a);
     }
-    // row panels: adjoint of every panel into gbuf, elementwise update, forward of every panel
+    // Row panels: adjoint of every panel into gbuf, elementwise update, forward of every panel.  Row blocks over
+    // the ranks run the same way on their local rows (one panel or several): the dot of a column with r spans the
+    // ranks, so the gradient -- alpha grad R added by rank 0 only -- is all-reduced (M doubles) before the update,
+    // which every rank repeats on the whole model: TWO reads of the local shard per leapfrog step.
     const SweepArgs full = a;
+    auto panel = [&](SweepArgs &s, int p) {
+        s.row0 = (int64_t)p * c->panel_rows;
+        s.rows = c->n_panels == 1 ? c->ld : std::min<int64_t>(c->panel_rows, c->ld - s.row0);
+    };
     if (full.mode & SW_ADJ) {
         double *gdst = (full.mode & SW_GOUT) ? full.g_out : c->gbuf;
         for (int p = 0; p < c->n_panels; ++p) {
             SweepArgs s = full;
             s.mode = SW_ADJ | SW_GOUT | (p ? SW_GACC : 0);
-            s.greg = p ? nullptr : full.greg;
+            s.greg = (p == 0 && (!shard_rows(c) || c->sh.rank == 0)) ? full.greg : nullptr;
             s.g_out = gdst;
-            s.row0 = (int64_t)p * c->panel_rows;
-            s.rows = std::min<int64_t>(c->panel_rows, c->ld - s.row0);
+            panel(s, p);
             TRY(launch_sweep_one(c, s));
         }
+        if (shard_rows(c)) TRY(comm_allreduce(c, gdst, c->M));
         if (full.mode & (SW_UPD | SW_PFIN)) {
             SweepArgs u = full;
             vec_update_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(u, gdst, c->M, c->n_teams);
@@ -680,8 +676,7 @@ static int launch_sweep(gh_ctx *c, SweepArgs &a)
             SweepArgs s = full;
             s.mode = SW_FWD;
             s.x_in = (full.mode & SW_UPD) ? full.x_out : full.x_in;
-            s.row0 = (int64_t)p * c->panel_rows;
-            s.rows = std::min<int64_t>(c->panel_rows, c->ld - s.row0);
+            panel(s, p);
             TRY(launch_sweep_one(c, s));
         }
     }

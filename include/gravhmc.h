@@ -717,6 +717,12 @@ int gh_chain_feed_stats(gh_ctx *ctx, double *runner_wait_draw_s, double *drawer_
 int gh_debug_feed_dry_run(gh_rng *rng, const int *plan_L, int64_t n_plan, int Lmin, int Lmax, int64_t limit, double sigma,
                           const double *sigma_vec, int64_t M, int rows, int64_t max_out, int *out_L, double *out_u,
                           double *out_probe, int *out_look, int64_t *n_out, int64_t *drawn);
+/* Diagnostic: the layout the single chain's work buffers were allocated by at the first evaluation.  out[0..15]:
+ * allocated (0 / 1), slab rows, slab2 segments, |p|^2 partials of the final half step, of a fresh momentum, slab-row
+ * sums, sums per row block, |r|^2 partials, R partials, R partials per property, form of the epilogue's partials
+ * (0 none, 1 plain, 2 magnetization-vector, 3 multi-component, 4 joint), their size, offset of R's in them, offset
+ * of the coupling term's, doubles of the pinned read-back buffer, slab rows the last forward launch wrote. */
+int gh_debug_work_layout(const gh_ctx *ctx, int64_t *out);
 /* How often the speculative first step was used / discarded. */
 int gh_chain_stats(gh_ctx *ctx, int64_t *spec_hits, int64_t *spec_misses);
 /* Small dense problems (N <= 1024, one column block per CU fitting its LDS next to the kernel's
