@@ -61,6 +61,7 @@ PROTOTYPES = {
     "gh_amplitude_eval": (C.c_int, [_ctx, _dp, C.POINTER(C.c_double), _dp, _dp]),
     "gh_amplitude_last": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
     "gh_set_cells_multi": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp]),
+    "gh_set_cells_mvi_table": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), _dp]),
     "gh_set_cells_multi_table": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp]),
     "gh_set_cells_multi_table_chains": (C.c_int, [_ctx, _dp, C.c_int, C.POINTER(C.c_int), _dp]),
     "gh_batch_block_means": (C.c_int, [_ctx, _dp]),
@@ -192,6 +193,7 @@ PROTOTYPES = {
     "gh_set_translation_invariant": (C.c_int, [_ctx, C.c_int]),
     "gh_translation_invariant_info": (C.c_int, [_ctx] + [C.POINTER(C.c_int)] * 6 + [C.POINTER(_i64), C.POINTER(C.c_double),
                                                                                    C.POINTER(C.c_double)]),
+    "gh_translation_invariant_axes": (C.c_int, [_ctx] + [C.POINTER(C.c_int)] * 3),
     "gh_translation_invariant_table": (C.c_int, [_ctx, _dp]),
     "gh_translation_invariant_batch_plan": (C.c_int, [_ctx, C.POINTER(C.c_int32)]),
     "gh_lattice_detect": (C.c_int, [_i64, _dp, _dp, _dp, _i64, _dp] + [C.POINTER(C.c_int)] * 5),

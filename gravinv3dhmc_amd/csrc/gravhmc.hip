@@ -16,6 +16,7 @@
 #include "lonsymw.hip.h"
 #include "fold.hip.h"
 #include "lattice.hip.h"
+#include "latmvi.hip.h"
 #include "latbatch.hip.h"
 #include "poststream.hip.h"
 #include "tessmag.hip.h"
@@ -320,7 +321,8 @@ static int set_block_cells(gh_ctx *c, int kind, const BlockCells &a)
     TRY(check_context(c, s, s.name));
     if (s.row_limit && !a.on_table) TRY(check_row_limit(c, s, blocks ? a.ncomp : 0));
     // one unweighted block of the field a store of one block holds is that store itself: one block with one mean
-    if (kind == GH_CELL_PRISM_MVI_DATA && a.ncomp == 1 && a.comps[0] == GH_BCOMP_TF && a.weights[0] == 1.0)
+    // (on the table it stays a store of one block: gh_set_cells_mvi has no door to the table)
+    if (kind == GH_CELL_PRISM_MVI_DATA && a.ncomp == 1 && a.comps[0] == GH_BCOMP_TF && a.weights[0] == 1.0 && !a.on_table)
         return gh_set_cells_mvi(c, a.bounds6, a.dir[0], a.dir[1], a.dir[2]);
     if (kind == GH_CELL_TESSEROID_MULTI && a.ncomp == 1 && a.comps[0] == GH_COMP_GZ && a.weights[0] == 1.0)
         return gh_set_cells(c, a.bounds6, GH_CELL_TESSEROID, a.ratios[0]);  // (kind 1, on either form)
@@ -345,6 +347,7 @@ static int set_block_cells(gh_ctx *c, int kind, const BlockCells &a)
     if (a.on_table && !s.tess) {
         lattice_switch_on(c, true);
         c->lat->chains = a.chains;
+        c->lat->axes = s.cols;  // (magnetization vectors: the axis as one more layer coordinate, latmvi.hip.h)
     }
     return a.on_table && s.tess ? gh_set_shift_invariant(c, 1) : GH_OK;
 }
@@ -364,6 +367,17 @@ int gh_set_cells_mvi_data(gh_ctx *c, const double *bounds6, double fx, double fy
     if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: null pointer");
     const double dir[3] = {fx, fy, fz};
     return set_block_cells(c, GH_CELL_PRISM_MVI_DATA, {bounds6, dir, ncomp, comps, weights, nullptr, 0.0, nullptr, false});
+}
+
+// (the same context as gh_set_cells_mvi_data makes, and that call's name in the refusals; a single unweighted tf block
+// too stays a store of one block here; the geometry is looked at by gh_build_G)
+int gh_set_cells_mvi_table(gh_ctx *c, const double *bounds6, double fx, double fy, double fz, int ncomp, const int *comps,
+                           const double *weights)
+{
+    GH_FEED_GUARD(c);
+    if (!c || !bounds6 || !comps || !weights) return fail(c, GH_ERR_ARG, "gh_set_cells_mvi_data: null pointer");
+    const double dir[3] = {fx, fy, fz};
+    return set_block_cells(c, GH_CELL_PRISM_MVI_DATA, {bounds6, dir, ncomp, comps, weights, nullptr, 0.0, nullptr, true});
 }
 
 int gh_set_cells_tess_mag(gh_ctx *c, const double *bounds6, double ratio, int ncomp, const int *comps,
@@ -678,7 +692,9 @@ int gh_tf_result(gh_ctx *c, const double *mag3, double *result)
     GH_FEED_GUARD(c);
     if (!c || !mag3 || !result) return fail(c, GH_ERR_ARG, "gh_tf_result: null pointer");
     TRY(need(c, c->have_obs && c->have_cells, "gh_tf_result: call gh_set_obs and gh_set_cells_tf first"));
-    if (c->cell_kind != GH_CELL_PRISM_TF && c->cell_kind != GH_CELL_PRISM_MVI)
+    // (on the table the unweighted total field alone is a store of one block: the same cells, the same points)
+    const bool table_tf = lattice_mvi(c) && c->mc.n == 1 && c->mc.comp[0] == GH_BCOMP_TF;
+    if (c->cell_kind != GH_CELL_PRISM_TF && c->cell_kind != GH_CELL_PRISM_MVI && !table_tf)
         return fail(c, GH_ERR_ARG, "gh_tf_result: the cells are not a total-field magnetic model (gh_set_cells_tf, "
                                    "gh_set_cells_mvi)");
     if (c->sh.kind != 0)
@@ -839,8 +855,8 @@ int gh_set_translation_invariant(gh_ctx *c, int enable)
     if (c->have_G || c->work_ready) return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: call before gh_build_G");
     if (lattice_multi(c))
         return fail(c, GH_ERR_UNSUPPORTED, "gh_set_translation_invariant: %s was set onto %s with its cells "
-                                           "(gh_set_cells_multi_table): the table is this context's form", store_name(c),
-                    LATTICE_NAME);
+                                           "(%s): the table is this context's form", store_name(c), LATTICE_NAME,
+                    lattice_mvi(c) ? "gh_set_cells_mvi_table" : "gh_set_cells_multi_table");
     if (enable && c->ls)
         return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: the shift-invariant store is switched on: one form at a time");
     if (enable && !c->lat && c->mf)
@@ -873,12 +889,23 @@ int gh_translation_invariant_info(const gh_ctx *c, int *on, int *nx, int *ny, in
     if (on) *on = o ? 1 : 0;
     if (nx) *nx = g.nx;
     if (ny) *ny = g.ny;
-    if (nz) *nz = g.nz;
+    if (nz) *nz = o ? g.nz / c->lat->axes : 0;  // (the geometry's layers: gh_translation_invariant_axes has the factor)
     if (px) *px = g.px;
     if (qy) *qy = g.qy;
     if (table_bytes) *table_bytes = (int64_t)(o ? c->lat->nb : 1) * g.nz * g.U * g.V * (int64_t)sizeof(double);
     if (max_dev) *max_dev = o ? c->lat->max_dev : 0.0;
     if (build_ms) *build_ms = o ? c->lat->build_ms : 0.0;
+    return GH_OK;
+}
+
+int gh_translation_invariant_axes(const gh_ctx *c, int *axes, int *chunks, int *layers_per_chunk)
+{
+    GH_FEED_GUARD(c);
+    if (!c) return GH_ERR_ARG;
+    const bool o = lattice_on(c);
+    if (axes) *axes = o ? c->lat->axes : 0;
+    if (chunks) *chunks = o ? c->lat->chunks : 0;
+    if (layers_per_chunk) *layers_per_chunk = o ? c->lat->fwd.lpc : 0;
     return GH_OK;
 }
 
@@ -1371,6 +1398,7 @@ int gh_set_data(gh_ctx *c, const double *dobs, const double *grav_fix)
     };
     if (c->mc.n > 0) {
         // Wb dobs in row blocks: every component loses its own mean
+        if (grav_fix) TRY(lattice_mvi_refuse(c, "gh_set_data with a grav_fix", "every data block loses its own mean"));
         if (grav_fix)
             return fail(c, GH_ERR_ARG, "gh_set_data: %s takes no grav_fix", store_of(c).rows_name);
         const size_t Nb = (size_t)store_points(c);

@@ -11,7 +11,8 @@ static int bscg_refuse(gh_ctx *c, int B, int maxk)
     const bool table = lattice_reps(c);
     // (a store of blocks names itself: each is dense and unsharded, but for the tesseroid forms on the table)
     // (the table of blocks that takes chain batches names the table, as the single-block table of chains does)
-    const char *what = lattice_multi_chains(c)    ? LATTICE_NAME
+    const char *what = lattice_mvi(c)             ? LATTICE_MVI_NAME
+                       : lattice_multi_chains(c)  ? LATTICE_NAME
                        : c->ls && tess_mag_store(c) ? "the tesseroid magnetization store on the shift-invariant table"
                                                     : store_of(c).rows_name;
     if (what)

@@ -167,6 +167,9 @@ struct LatticeHost {
     // the multi-component store on the table (gh_set_cells_multi_table): nb row blocks, one table each; else 1
     bool multi = false;
     int nb = 1;
+    // the magnetization-vector store on the table (gh_set_cells_mvi_table; latmvi.hip.h): the axis of a column is one more
+    // layer coordinate, g.nz = axes x the geometry's layers, layer L = ax nz + k; else 1
+    int axes = 1;
     // gh_set_translation_invariant(2): the table also takes chain batches (latbatch.hip.h).  Their partition is made
     // by latb_plan on the built table: bt_state 0 not yet, 1 planned, -1 an extent the batch tile cannot hold
     // gh_set_translation_invariant(4): the table also takes the bootstrap batch (gh_bscg_run) on the same plan
@@ -182,6 +185,16 @@ struct LatticeHost {
 static bool lattice_on(const gh_ctx *c) { return c->lat && c->lat->on; }
 // the multi-component store asked onto the table: gh_set_cells_multi_table is the one call that does
 static bool lattice_multi(const gh_ctx *c) { return c->lat && c->lat->multi; }
+// ... the vector-data magnetization store: gh_set_cells_mvi_table is the one call that does (a table of blocks as well)
+static bool lattice_mvi(const gh_ctx *c) { return c && c->lat && c->lat->axes == 3; }
+static const char *const LATTICE_MVI_NAME = "the vector-data magnetization store on the translation-invariant table";
+
+// What the magnetization-vector store on the table does not run names both
+static int lattice_mvi_refuse(gh_ctx *c, const char *who, const char *why)
+{
+    if (lattice_mvi(c)) return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on %s (%s)", who, LATTICE_MVI_NAME, why);
+    return GH_OK;
+}
 
 // What gh_set_translation_invariant(1) does to a context that may take the table (its own checks passed), and what
 // gh_set_cells_multi_table does once the store's blocks are set
@@ -257,21 +270,28 @@ static int lattice_build(gh_ctx *c)
     // (row blocks: the blocks share the N / nb points)
     const int64_t Np = store_points(c);
     h.nb = h.multi ? c->mc.n : 1;
-    std::vector<double> ox((size_t)Np), oy((size_t)Np), oz((size_t)Np), b6((size_t)c->M * 6);
+    // (magnetization vectors: the M columns are three axes of the same M / 3 cells)
+    const int64_t m = store_cells(c);
+    std::vector<double> ox((size_t)Np), oy((size_t)Np), oz((size_t)Np), b6((size_t)m * 6);
     TRY(d2h(c, ox.data(), c->obs[0], ox.size()));
     TRY(d2h(c, oy.data(), c->obs[1], oy.size()));
     TRY(d2h(c, oz.data(), c->obs[2], oz.size()));
     TRY(d2h(c, b6.data(), c->bounds, b6.size()));
     int dims[5] = {0, 0, 0, 0, 0};
     std::vector<int> loc, col, loo, ool;
-    const int reason = lattice_detect_host(Np, ox.data(), oy.data(), oz.data(), c->M, b6.data(), dims, loc, col, loo, ool);
+    const int reason = lattice_detect_host(Np, ox.data(), oy.data(), oz.data(), m, b6.data(), dims, loc, col, loo, ool);
     if (reason != GH_LATTICE_ON)
         return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s needs a regular prism grid under gridded data: %s", LATTICE_NAME,
                     lattice_reason_text(reason));
     ghk::LatGeom &g = h.g;
     g.nx = dims[0];
     g.ny = dims[1];
-    g.nz = dims[2];
+    const int nzg = dims[2];  // (the geometry's layers)
+    g.nz = h.axes * nzg;
+    // the expanded map: layer ax nz + k holds the columns ax m + cell of the geometry's layer k
+    col.resize((size_t)c->M);
+    for (int ax = 1; ax < h.axes; ++ax)
+        for (int64_t e = 0; e < m; ++e) col[(size_t)(ax * m + e)] = (int)(ax * m) + col[(size_t)e];
     g.px = dims[3];
     g.qy = dims[4];
     g.U = g.nx + g.px - 1;
@@ -320,9 +340,17 @@ static int lattice_build(gh_ctx *c)
     // entry function of a gh_set_cells_prism context of its component at the Np points; the deviation is a fraction of
     // the block's own largest entry, and the largest over the blocks is kept.)
     double *T2 = nullptr;
-    HIPCHK(c, hipMalloc((void **)&T2, nT * sizeof(double)));
+    HIPCHK(c, hipMalloc((void **)&T2, (h.axes == 3 ? (size_t)h.nb : 1) * nT * sizeof(double)));
     std::vector<double> t1(nT), t2(nT);
     h.max_dev = 0.0;
+    if (h.axes == 3) {
+        // magnetization vectors: one launch over the geometric offsets writes every (data block, axis) table, T2 laid
+        // out as T (latmvi.hip.h)
+        const size_t nTg = (size_t)nzg * (size_t)g.U * (size_t)g.V;
+        ghk::lat_fill_mvi_kernel<<<dim3((unsigned)((nTg + 255) / 256)), dim3(256), 0, c->stream>>>(
+            c->obs[0], c->obs[1], c->obs[2], c->bounds, g, nzg, make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]),
+            block_comps(c), h.T, T2);
+    }
     for (int b = 0; b < h.nb; ++b) {
         MfGeom mg = mf_geom(c);
         lat_fill_fn fill = mf_pick<lat_fill_fn>(c, ghk::lat_fill_kernel<MF_E_GEN>, ghk::lat_fill_kernel<MF_E_TF>,
@@ -336,10 +364,12 @@ static int lattice_build(gh_ctx *c)
             fill = gz ? ghk::lat_fill_kernel<MF_E_GEN> : ghk::lat_fill_kernel<MF_E_COMP>;
         }
         double *Tb = h.T + (size_t)b * nT;
-        hipLaunchKernelGGL(fill, dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, c->stream, mg, g, Tb, T2);
+        // (magnetization vectors: the block's three axes, filled above, checked against the block's largest entry)
+        const double *T2b = h.axes == 3 ? T2 + (size_t)b * nT : T2;
+        if (h.axes != 3) hipLaunchKernelGGL(fill, dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, c->stream, mg, g, Tb, T2);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(t1.data(), Tb, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(t2.data(), T2, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(t2.data(), T2b, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (col / ool must outlive their copies as well)
         if (e != hipSuccess) {
             (void)hipFree(T2);

@@ -233,11 +233,15 @@ class Engine(object):
         self._chk(self._lib.gh_set_cells_mvi(self._h, ptr(b), fx, fy, fz))
         self._set_store(_lib.CELL_PRISM_MVI, cols=3)
 
-    def set_cells_mvi_data(self, bounds6, direction, components, weights):
+    def set_cells_mvi_data(self, bounds6, direction, components, weights, translation_invariant=False):
         """The M/3 prisms (bounds (M/3, 6)) of a magnetization-vector model under vector data (gh_set_cells_mvi_data):
         the data `components` (names of _lib.BCOMPONENTS or BCOMP_* values, distinct) at the same N / len(components)
         points, stacked in row blocks, block b with the data weight weights[b] > 0; columns as set_cells_mvi.
-        direction = (fx, fy, fz) serves a "tf" block alone (None: zeros).  Call it before set_obs."""
+        direction = (fx, fy, fz) serves a "tf" block alone (None: zeros).  Call it before set_obs.
+        translation_invariant=True (gh_set_cells_mvi_table): the store on the translation-invariant table, the axis of a
+        column one more layer coordinate (csrc/latmvi.hip.h), no 16384-row limit; build_G raises NotImplementedError
+        with the reason if the geometry lacks the structure.  The unweighted total field alone is then a store of one
+        block as well."""
         b = f64(bounds6)
         if self.M % 3 != 0 or b.shape != (self.M // 3, 6):
             raise ValueError("bounds table of a magnetization-vector model must be (M/3, 6)")
@@ -249,9 +253,12 @@ class Engine(object):
         if len(direction) != 3:
             raise ValueError("direction must be (fx, fy, fz)")
         fx, fy, fz = (float(v) for v in direction)
-        self._chk(self._lib.gh_set_cells_mvi_data(self._h, ptr(b), fx, fy, fz, len(comps), carr, ptr(w)))
+        fn = self._lib.gh_set_cells_mvi_table if translation_invariant else self._lib.gh_set_cells_mvi_data
+        self._chk(fn(self._h, ptr(b), fx, fy, fz, len(comps), carr, ptr(w)))
+        if translation_invariant:
+            self._translation_invariant = True
         # (the unweighted total field alone is the magnetization-vector store itself: one block, no block table)
-        if comps == [_lib.BCOMP_TF] and w[0] == 1.0:
+        if comps == [_lib.BCOMP_TF] and w[0] == 1.0 and not translation_invariant:
             self._set_store(_lib.CELL_PRISM_MVI, cols=3)
         else:
             self._set_store(_lib.CELL_PRISM_MVI_DATA, cols=3, rows=len(comps), table=True)
@@ -445,13 +452,20 @@ class Engine(object):
     def translation_invariant_info(self):
         """on, the lattice's extents nx, ny, nz (cells) and px, qy (observations), table_bytes, and of the build:
         max_dev (the entries of the first and the last pair of an offset, as a fraction of the largest entry) and
-        build_ms."""
+        build_ms.  On a table of magnetization vectors (set_cells_mvi_data(..., translation_invariant=True)) also axes
+        (3: the table has axes x nz layers), chunks and layers_per_chunk (the forward's partition of those layers)."""
         i = [C.c_int(0) for _ in range(6)]
         tb, md, bm = C.c_int64(0), C.c_double(0), C.c_double(0)
         self._chk(self._lib.gh_translation_invariant_info(self._h, *[C.byref(v) for v in i], C.byref(tb), C.byref(md),
                                                           C.byref(bm)))
-        return {"on": bool(i[0].value), "nx": i[1].value, "ny": i[2].value, "nz": i[3].value, "px": i[4].value,
-                "qy": i[5].value, "table_bytes": tb.value, "max_dev": md.value, "build_ms": bm.value}
+        d = {"on": bool(i[0].value), "nx": i[1].value, "ny": i[2].value, "nz": i[3].value, "px": i[4].value,
+             "qy": i[5].value, "table_bytes": tb.value, "max_dev": md.value, "build_ms": bm.value}
+        if self._store.kind == _lib.CELL_PRISM_MVI_DATA and d["on"]:
+            a = [C.c_int(0) for _ in range(3)]
+            self._chk(self._lib.gh_translation_invariant_axes(self._h, *[C.byref(v) for v in a]))
+            if a[0].value == 3:
+                d.update(axes=3, chunks=a[1].value, layers_per_chunk=a[2].value)
+        return d
 
     def translation_invariant_table(self):
         """The table as it lies on the device: (nz, nx + px - 1, ny + qy - 1); on a multi-component context
@@ -460,6 +474,8 @@ class Engine(object):
         if not t["on"]:
             raise ValueError("no table resident (set_translation_invariant, build_G)")
         shape = (t["nz"], t["nx"] + t["px"] - 1, t["ny"] + t["qy"] - 1)
+        if t.get("axes"):     # (magnetization vectors: (C, 3, nz, ., .), the axis a layer coordinate)
+            shape = (self._store.rows, t["axes"]) + shape
         T = np.empty(((self._store.rows,) + shape) if self._store.kind == _lib.CELL_PRISM_MULTI else shape)
         self._chk(self._lib.gh_translation_invariant_table(self._h, ptr(T)))
         return T

@@ -73,6 +73,17 @@ class MagVectorModule(_BlockStore):
     through `boundaries`.  Not supported (NotImplementedError): coordinate="spherical", wavelet compression, the
     matrix-free mode, the shift-invariant store, shards, HMCSampleBatch and more than 16384 observations -- stacked
     rows len(data) x N under vector data -- (the store runs on the fused sweep).  Smoothness and TV need the full mesh (ValueError on a carved one).
+
+    translation_invariant=True keeps the translation-invariant table instead of the kernel (a regular mesh -- no mratio
+    growth, mseg or mtopo -- under observations that are a full rectangle of the lattice of the cells' horizontal
+    spacings at one height, GravMagModule's translation_invariant): the axis of a column is one more layer coordinate
+    of the table, T[component][axis nz + layer][dx][dy], the kernel is never stored and the 16384-row limit does not
+    apply.  HMCSample (posterior_stream too), misfit_and_grad, the four regularisers, set_amplitude / Amplitude /
+    last_amplitude, forward, block_means, Wm, Wb, dobsw, to_vectors / from_vectors / amplitude / direction and
+    translation_invariant_info() work on it; Aw, A and kernel(axis, component) do not exist (NotImplementedError).  It
+    does not combine with mtopo, wavelet, matrix_free, shift_invariant, shard or coordinate="spherical", and
+    translation_invariant="chains" is refused -- batches of magnetization vectors are not built -- (NotImplementedError
+    naming the store and the table); NotImplementedError with the reason if the geometry lacks the structure.
     """
     _props, _prop = 3, 'magnetization'  # (mx, my and mz of the same mesh)
     _names, _arg, _word, _none_weight = _lib.BCOMPONENTS, "data", "data component", True
@@ -81,7 +92,7 @@ class MagVectorModule(_BlockStore):
     def __init__(self, dobs, mrange, mspacing, obsurface, mangle=(90, 0), mratio=1, mseg=False, mdivisionsection=[],
                  weightfactor=0.5, amplitude=0.0, amplitude_beta=0.01, device=0, verbose=True, coordinate="cartesian",
                  wavelet=False, matrix_free=False, shift_invariant=False, shard=None, data=("tf",), weights=None,
-                 **kwargs):
+                 translation_invariant=False, **kwargs):
         self._say = print if verbose else (lambda *a, **k: None)
         self._only_mtopo(kwargs)
         data = self._block_names(data)
@@ -90,12 +101,22 @@ class MagVectorModule(_BlockStore):
         self._vector = self._spherical or not (data == ("tf",) and weights is None)
         if self._vector:
             dobs, w = self._block_data(data, dobs, weights, n)
-        self._refuse(coordinate, wavelet, matrix_free, shift_invariant, shard, len(data) if self._vector else 0, n)
+        if isinstance(translation_invariant, str) and translation_invariant != "chains":
+            raise ValueError("translation_invariant must be True or False, not %r" % (translation_invariant,))
+        if translation_invariant:
+            self.translation_invariant = True
+            self._refuse_on_table(coordinate, wavelet, matrix_free, shift_invariant, shard, kwargs)
+            if translation_invariant == "chains":
+                raise NotImplementedError("%s on the translation-invariant table (translation_invariant=True) runs one "
+                                          "chain: batches of magnetization vectors (translation_invariant=\"chains\") are "
+                                          "not built" % self._store)
+        else:
+            self._refuse(coordinate, wavelet, matrix_free, shift_invariant, shard, len(data) if self._vector else 0, n)
         if not self._vector:
             dobs, w = [np.asarray(dobs, dtype=np.float64).ravel()], np.ones(1)
             if dobs[0].size != n:
                 raise ValueError("dobs has %d values, the observation points are %d" % (dobs[0].size, n))
-            if n > 16384:
+            if n > 16384 and not translation_invariant:
                 raise NotImplementedError("%d observations: %s takes at most 16384 (it runs on the fused sweep)"
                                           % (n, self._store))
         if not (amplitude >= 0) or not (amplitude_beta > 0):
@@ -104,6 +125,8 @@ class MagVectorModule(_BlockStore):
         title = "Calculating magnetic field (magnetization vector) in %s coordinate." % coordinate
         self._assemble(Engine, title, data, dobs, w, n, mrange, mspacing, obsurface, mratio, mseg, mdivisionsection,
                        weightfactor, shift_invariant, device, kwargs.values())
+        if translation_invariant:
+            self._hide_Aw()
         self._cells = self._engine.M // 3
         self._amp = None  # (lambda, beta) once the engine holds the term
         self._amp_beta = float(amplitude_beta)
@@ -112,7 +135,10 @@ class MagVectorModule(_BlockStore):
 
     def _set_cells(self, eng, bounds):
         direction = utils.dircos(self.inc, self.dec) if "tf" in self.components else None
-        if self._vector:
+        if self.translation_invariant:
+            # (the default form too: one block of the total field with one mean, the store the table has a door for)
+            eng.set_cells_mvi_data(bounds, direction, self.components, self.weights, translation_invariant=True)
+        elif self._vector:
             eng.set_cells_mvi_data(bounds, direction, self.components, self.weights)
         else:
             eng.set_cells_mvi(bounds, direction)

@@ -86,9 +86,7 @@ class MultiComponentModule(_BlockStore):
         self._assemble(Engine, title, components, dobs, w, n, mrange, mspacing, obsurface, mratio, mseg,
                        mdivisionsection, weightfactor, shift_invariant, device, kwargs.values())
         if translation_invariant:
-            self._Aw = self.__dict__.pop("Aw")   # (the sampler's handle; the attribute Aw raises, below)
-
-    translation_invariant = translation_invariant_chains = False
+            self._hide_Aw()
 
     @staticmethod
     def _table_hint(mrange, mspacing, mratio, mseg, mdivisionsection, obsurface, kwargs):
@@ -115,53 +113,14 @@ class MultiComponentModule(_BlockStore):
                                    b6.ctypes.data_as(dp), dims.ctypes.data_as(ip), *[a.ctypes.data_as(ip) for a in maps])
         return "; translation_invariant=True has no such limit" if rc == 0 else ""
 
-    def _refuse_on_table(self, coordinate, wavelet, matrix_free, shift_invariant, shard, kwargs):
-        """What the store does not do on the translation-invariant table, decided before any device work (the rows are
-        not limited there)."""
-        store = "%s on the translation-invariant table (translation_invariant=True)" % self._store
-        if coordinate == "spherical":
-            raise NotImplementedError("%s holds prism fields: tesseroids (coordinate='spherical') are not supported"
-                                      % store)
-        if coordinate != "cartesian":
-            raise ValueError("Please choose coordinate from(cartesian, spherical)!")
-        for on, why in ((wavelet not in (False, None), "wavelet: the compressor's rows need the stored kernel"),
-                        (matrix_free, "matrix_free: one form at a time (the table already never stores G)"),
-                        (shift_invariant, "shift_invariant: that table is for spherical grids"),
-                        (shard is not None, "shard: one GPU holds the table"),
-                        (bool(kwargs), "mtopo: a carved mesh is not a full regular product of cells")):
-            if on:
-                raise NotImplementedError(store + " does not combine with " + why)
-
     def _set_cells(self, eng, bounds):
         eng.set_cells_multi(bounds, self.components, self.weights,
                             translation_invariant="chains" if self.translation_invariant_chains else self.translation_invariant)
-
-    def translation_invariant_info(self):
-        """The engine's translation_invariant_info(): on, nx, ny, nz, px, qy, table_bytes (all components), max_dev
-        (the largest of the components'), build_ms."""
-        return self._engine.translation_invariant_info()
 
     def translation_invariant_batch_plan(self):
         """The engine's translation_invariant_batch_plan(): the partition of the chain batch's two passes on the tables
         (translation_invariant="chains"; "on" is False otherwise), with "blocks", the number of components."""
         return self._engine.translation_invariant_batch_plan()
-
-    def _no_table(self, what):
-        if self.translation_invariant:
-            raise NotImplementedError("%s: %s keeps the translation-invariant table, the kernel is never stored" %
-                                      (what, self._store))
-        super()._no_table(what)
-
-    def __getattr__(self, name):
-        # (reached for an attribute that does not exist: Aw on the translation-invariant table, where no store is behind
-        # the device handle the constructor leaves)
-        if name == "Aw" and self.__dict__.get("translation_invariant"):
-            self._no_table("Aw")
-        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
-
-    def kernelw(self):
-        """(Aw, WmInv, Wm) as the sampler expects; Aw is a device handle (on the table: of the tables)."""
-        return (self._Aw if self.translation_invariant else self.Aw), self.WmInv, self.Wm
 
     @property
     def A(self):

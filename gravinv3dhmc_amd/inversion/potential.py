@@ -466,11 +466,55 @@ class _BlockStore(_Potential):
         if self._vector:
             self.Wb = _diag(np.repeat(self.weights, self._n))
 
+    # ------------------------------------------------------------------ on the translation-invariant table
+    translation_invariant = translation_invariant_chains = False
+
+    def _refuse_on_table(self, coordinate, wavelet, matrix_free, shift_invariant, shard, kwargs):
+        """What the store does not do on the translation-invariant table, decided before any device work (the rows are
+        not limited there)."""
+        store = "%s on the translation-invariant table (translation_invariant=True)" % self._store
+        if coordinate == "spherical":
+            raise NotImplementedError("%s holds prism fields: tesseroids (coordinate='spherical') are not supported"
+                                      % store)
+        if coordinate != "cartesian":
+            raise ValueError("Please choose coordinate from(cartesian, spherical)!")
+        for on, why in ((wavelet not in (False, None), "wavelet: the compressor's rows need the stored kernel"),
+                        (matrix_free, "matrix_free: one form at a time (the table already never stores G)"),
+                        (shift_invariant, "shift_invariant: that table is for spherical grids"),
+                        (shard is not None, "shard: one GPU holds the table"),
+                        (bool(kwargs), "mtopo: a carved mesh is not a full regular product of cells")):
+            if on:
+                raise NotImplementedError(store + " does not combine with " + why)
+
+    def translation_invariant_info(self):
+        """The engine's translation_invariant_info(): on, nx, ny, nz, px, qy, table_bytes (all blocks), max_dev (the
+        largest of the blocks'), build_ms; on a table of magnetization vectors also axes, chunks, layers_per_chunk."""
+        return self._engine.translation_invariant_info()
+
+    def _hide_Aw(self):
+        """On the translation-invariant table no store is behind the device handle the constructor leaves: the sampler
+        keeps it (kernelw), the attribute Aw raises."""
+        self._Aw = self.__dict__.pop("Aw")
+
     # ------------------------------------------------------------------ what is formed from the store
     def _no_table(self, what):
+        if self.translation_invariant:
+            raise NotImplementedError("%s: %s keeps the translation-invariant table, the kernel is never stored" %
+                                      (what, self._store))
         if self.shift_invariant:
             raise NotImplementedError("%s: %s keeps the shift-invariant table, the kernel is never stored" %
                                       (what, self._store))
+
+    def __getattr__(self, name):
+        # (reached for an attribute that does not exist: Aw on the translation-invariant table, where no store is behind
+        # the device handle the constructor leaves)
+        if name == "Aw" and self.__dict__.get("translation_invariant"):
+            self._no_table("Aw")
+        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
+
+    def kernelw(self):
+        """(Aw, WmInv, Wm) as the sampler expects; Aw is a device handle (on the table: of the tables)."""
+        return (self._Aw if self.translation_invariant else self.Aw), self.WmInv, self.Wm
 
     def forward(self, model):
         """Unweighted forward A @ model of the physical model (M entries, property-major): the predicted values,

@@ -381,6 +381,22 @@ int gh_set_cells_multi_table(gh_ctx *ctx, const double *bounds6, int ncomp, cons
  * gh_compress_wavelet, gh_upload_G, gh_bscg_run, gh_shard_init*, gh_set_matrix_free and gh_set_shift_invariant return an
  * error naming the translation-invariant store; gh_set_translation_invariant stays refused. */
 int gh_set_cells_multi_table_chains(gh_ctx *ctx, const double *bounds6, int ncomp, const int *comps, const double *weights);
+/* gh_set_cells_mvi_data, and the store is built on the translation-invariant table (csrc/latmvi.hip.h) instead of as
+ * ld x M doubles: the same arguments, checks and context -- columns [A_x | A_y | A_z] of the M / 3 cells, rows in ncomp
+ * blocks of data components, model vectors property-major, the regularisers on three properties, gh_set_amplitude,
+ * gh_amplitude_eval, gh_b_result, gh_tf_result (the unweighted tf block alone), gh_multi_info -- without the 16384-row
+ * limit.  The axis of a column is one more layer coordinate of the table: layer L = ax nz + k of 3 nz, T[b][L][u][v]
+ * the field of data block b of a unit magnetization along ax, every entry the dense store's entry of its pair bit for
+ * bit; the passes of gh_set_cells_multi_table run on it unchanged.  gh_build_G looks for the structure on the M / 3
+ * cells under the N / ncomp points (GH_ERR_UNSUPPORTED with the reason where it is absent).  One unweighted tf block
+ * stays a store of one block with one mean here: it agrees with the gh_set_cells_mvi context to rounding, not bit for
+ * bit.  This call is the only way onto the table: gh_set_cells_mvi and gh_set_cells_mvi_data refuse a context with
+ * the table switched on, gh_set_translation_invariant refuses a magnetization-vector context.  gh_batch_*,
+ * gh_bscg_run, gh_compress_wavelet, gh_shard_init*, gh_upload_G, gh_set_matrix_free, gh_set_shift_invariant and a
+ * grav_fix return GH_ERR_UNSUPPORTED naming the vector-data magnetization store and the translation-invariant table;
+ * gh_download_G has no kernel to return. */
+int gh_set_cells_mvi_table(gh_ctx *ctx, const double *bounds6, double fx, double fy, double fz, int ncomp, const int *comps,
+                           const double *weights);
 /* The means of the row blocks of the chains' CURRENT predictions Aw mw, pred_mean[chain * ncomp + b] for the C chains of
  * the batch, as the batch's evaluation removes them.  A batch on a gh_set_cells_multi_table_chains context only
  * (GH_ERR_UNSUPPORTED otherwise). */
@@ -1113,8 +1129,12 @@ int gh_translation_invariant_batch_plan(gh_ctx *ctx, int32_t out[24]);
  * and build_ms of the build. */
 int gh_translation_invariant_info(const gh_ctx *ctx, int *on, int *nx, int *ny, int *nz, int *px, int *qy,
                                   int64_t *table_bytes, double *max_dev, double *build_ms);
+/* What a table of magnetization vectors adds (gh_set_cells_mvi_table): axes, the layers' factor (3 there, 1 on every
+ * other table: the table has axes x nz layers, nz as gh_translation_invariant_info reports it), and the forward
+ * pass's partition of those layers, chunks of layers_per_chunk.  All 0 while no table is built. */
+int gh_translation_invariant_axes(const gh_ctx *ctx, int *axes, int *chunks, int *layers_per_chunk);
 /* The table T[nz][nx + px - 1][ny + qy - 1] (row-major) as it lies on the device; a gh_set_cells_multi_table
- * context: its ncomp tables, block-major. */
+ * context: its ncomp tables, block-major; a gh_set_cells_mvi_table context: T[ncomp][3][nz][.][.]. */
 int gh_translation_invariant_table(gh_ctx *ctx, double *out);
 enum {
     GH_LATTICE_ON = 0,
