@@ -125,6 +125,7 @@ PROTOTYPES = {
     "gh_chain_resident_plan": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_int32)]),
     "gh_team_sweep_stats": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(C.c_int),
                                       C.POINTER(_i64)]),
+    "gh_team_sweep_plan": (C.c_int, [_ctx, C.POINTER(C.c_int32)]),
     "gh_chain_run": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_int), _dp, _dp, C.c_double, _dp, _i64, _i64,
                                C.POINTER(C.c_int), _dp, _dp, C.POINTER(C.c_int)]),
     "gh_chain_feed_usable": (C.c_int, [_ctx, C.POINTER(C.c_int)]),

@@ -1931,6 +1931,32 @@ int gh_team_sweep_stats(gh_ctx *c, int *members, int64_t *launches, int *timeout
     return GH_OK;
 }
 
+int gh_team_sweep_plan(gh_ctx *c, int32_t out[16])
+{
+    GH_FEED_GUARD(c);
+    if (!c || !out) return fail(c, GH_ERR_ARG, "gh_team_sweep_plan: null pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    TeamShape s;
+    const int why = team_shape_of(c, &s);
+    // (a context whose teams gave up for good stays on row panels: the shape is what they ran on)
+    out[0] = (why == TEAM_OK && c->tm.state != -1) ? 1 : 0;
+    out[1] = why;
+    out[2] = s.Q;
+    out[3] = (int32_t)s.panel_rows;
+    out[4] = (int32_t)s.last_rows;
+    out[5] = s.tpx;
+    out[6] = s.n_teams;
+    out[7] = (int32_t)s.cols_per_team;
+    out[8] = s.grid;
+    out[9] = s.lag;
+    out[10] = (int32_t)s.lds;
+    out[11] = c->n_panels;
+    out[12] = (int32_t)c->panel_rows;
+    out[13] = (int32_t)(c->ld - (int64_t)(c->n_panels - 1) * c->panel_rows);
+    return GH_OK;
+}
+
 int gh_chain_resident_stats(gh_ctx *c, int64_t *launches, int64_t *evaluations)
 {
     GH_FEED_GUARD(c);

@@ -487,46 +487,99 @@ static team_fn team_kernel_for(int threads, int ept2, int depth, int lag)
     return nullptr;
 }
 
+// why a context runs in row panels instead (gh_team_sweep_plan reports it)
+enum {
+    TEAM_OK = 0,
+    TEAM_NO_SWITCH = 1,     // GRAVHMC_TEAM=0
+    TEAM_NO_STORE = 2,      // matrix-free, joint or row-sharded store, or no stored G
+    TEAM_NO_PANELS = 3,     // a single panel: one workgroup holds a column
+    TEAM_NO_MEMBERS = 4,    // more than TS_MAXQ members
+    TEAM_NO_CUS = 5,        // fewer than 8 Q CUs
+    TEAM_NO_TPX = 6,        // no team per XCD slot
+    TEAM_NO_LDS = 7,        // the LDS request is refused
+    TEAM_NO_RESIDENCY = 8,  // the grid's workgroups are not all resident
+};
+
+struct TeamShape {
+    int Q = 0, tpx = 0, grid = 0, n_teams = 0;
+    int threads = 0, ept2 = 0, depth = 0, lag = 0;
+    int64_t panel_rows = 0, last_rows = 0, cols_per_team = 0;
+    size_t lds = 0;
+};
+
+// The arithmetic of the team sweep's plan from (ld, M, cus, lag) and the cap on the teams per XCD slot
+// (GRAVHMC_TEAM_TPX; <= 0: none).  Allocates nothing and asks the device nothing; returns TEAM_OK or the refusal.
+static int team_shape(int64_t ld, int64_t M, int cus, int lag, int tpx_cap, TeamShape *s)
+{
+    *s = TeamShape();
+    // instantiation: threads x double2 per thread x column buffers
+    s->threads = 1024;
+    s->ept2 = 5;
+    s->depth = 3;
+    s->lag = lag == 1 ? 1 : 2;
+    const size_t lds_small = (2 * TS_MAXWAVES + 4) * sizeof(double);
+    int64_t cap = (int64_t)s->threads * s->ept2 * 2;  // rows a member holds of a column
+    // lag 2: the member's part of r and the parked column share the 160 KB of LDS
+    if (s->lag == 2) cap = std::min<int64_t>(cap, (int64_t)((160 * 1024 - lds_small) / (2 * sizeof(double))) / 16 * 16);
+    s->Q = (int)((ld + cap - 1) / cap);
+    if (s->Q < 2) s->Q = 2;
+    if (s->Q > TS_MAXQ) return TEAM_NO_MEMBERS;
+    if (cus < 8 * s->Q) return TEAM_NO_CUS;
+    s->panel_rows = ((ld + s->Q - 1) / s->Q + 15) / 16 * 16;
+    s->last_rows = std::max<int64_t>(0, ld - (s->Q - 1) * s->panel_rows);
+    s->tpx = std::min(32, cus / 8) / s->Q;  // blocks with equal blockIdx % 8 share an XCD: 32 CUs each
+    if (s->tpx < 1) return TEAM_NO_TPX;
+    if (tpx_cap > 0) s->tpx = std::min(s->tpx, tpx_cap);  // (only ever fewer teams)
+    s->grid = 8 * s->tpx * s->Q;
+    s->n_teams = 8 * s->tpx;  // (a slab row each, claimed at the launch)
+    s->cols_per_team = (M + s->n_teams - 1) / s->n_teams;
+    s->lds = (size_t)s->panel_rows * (size_t)s->lag * sizeof(double) + lds_small;
+    return TEAM_OK;
+}
+
+// team_shape for the context as it stands, and what the device says to the shape's LDS request and grid
+static int team_shape_of(const gh_ctx *c, TeamShape *s)
+{
+    *s = TeamShape();
+    if (env_int("GRAVHMC_TEAM", 1) == 0) return TEAM_NO_SWITCH;
+    if (c->mf || c->joint || !c->G || shard_rows(c)) return TEAM_NO_STORE;
+    if (c->n_panels < 2) return TEAM_NO_PANELS;
+    const int why = team_shape(c->ld, c->M, c->cus, env_int("GRAVHMC_TEAM_LAG", 2), env_int("GRAVHMC_TEAM_TPX", 0), s);
+    if (why != TEAM_OK) return why;
+    team_fn f = team_kernel_for(s->threads, s->ept2, s->depth, s->lag);
+    if (allow_dynamic_lds(reinterpret_cast<const void *>(f), s->lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return TEAM_NO_LDS;
+    }
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(f), s->threads,
+                                                     s->lds) != hipSuccess ||
+        per_cu < 1 || (int64_t)per_cu * c->cus < s->grid) {
+        (void)hipGetLastError();
+        return TEAM_NO_RESIDENCY;
+    }
+    return TEAM_OK;
+}
+
 static bool team_plan(gh_ctx *c)
 {
     gh_ctx::Team &t = c->tm;
     if (t.state != 0) return t.state > 0;
     t.state = -1;
-    if (env_int("GRAVHMC_TEAM", 1) == 0) return false;
-    if (c->mf || c->joint || c->n_panels < 2 || !c->G) return false;
-    // instantiation: threads x double2 per thread x column buffers
-    t.threads = 1024;
-    t.ept2 = 5;
-    t.depth = 3;
-    t.lag = env_int("GRAVHMC_TEAM_LAG", 2) == 1 ? 1 : 2;
-    const size_t lds_small = (2 * TS_MAXWAVES + 4) * sizeof(double);
-    int64_t cap = (int64_t)t.threads * t.ept2 * 2;  // rows a member holds of a column
-    // lag 2: the member's part of r and the parked column share the 160 KB of LDS
-    if (t.lag == 2) cap = std::min<int64_t>(cap, (int64_t)((160 * 1024 - lds_small) / (2 * sizeof(double))) / 16 * 16);
-    t.Q = (int)((c->ld + cap - 1) / cap);
-    if (t.Q < 2) t.Q = 2;
-    if (t.Q > TS_MAXQ || c->cus < 8 * t.Q) return false;
-    t.panel_rows = ((c->ld + t.Q - 1) / t.Q + 15) / 16 * 16;
-    t.tpx = std::min(32, c->cus / 8) / t.Q;  // blocks with equal blockIdx % 8 share an XCD: 32 CUs each
-    if (t.tpx < 1) return false;
-    t.grid = 8 * t.tpx * t.Q;
-    const int n_teams = 8 * t.tpx;  // (a slab row each, claimed at the launch)
-    t.cols_per_team = (c->M + n_teams - 1) / n_teams;
-    t.lds = (size_t)t.panel_rows * (size_t)t.lag * sizeof(double) + lds_small;
-    team_fn f = team_kernel_for(t.threads, t.ept2, t.depth, t.lag);
-    if (allow_dynamic_lds(reinterpret_cast<const void *>(f), t.lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(f), t.threads,
-                                                     t.lds) != hipSuccess ||
-        per_cu < 1 || (int64_t)per_cu * c->cus < t.grid) {
-        (void)hipGetLastError();
-        return false;
-    }
-    const size_t ng = (size_t)n_teams * TS_MAXQ * TS_RING * 2;
+    TeamShape s;
+    if (team_shape_of(c, &s) != TEAM_OK) return false;
+    const size_t ng = (size_t)s.n_teams * TS_MAXQ * TS_RING * 2;
     if (dalloc(c, &t.gran, ng) != GH_OK || xg_alloc(c, t.xg, {{t.gran, ng * sizeof(u64)}}) != GH_OK) return false;
+    t.Q = s.Q;
+    t.tpx = s.tpx;
+    t.grid = s.grid;
+    t.threads = s.threads;
+    t.ept2 = s.ept2;
+    t.depth = s.depth;
+    t.lag = s.lag;
+    t.panel_rows = s.panel_rows;
+    t.cols_per_team = s.cols_per_team;
+    t.lds = s.lds;
     t.xg.tag = 0;
     t.state = 1;
     return true;

@@ -715,6 +715,22 @@ class Engine(object):
                 "team_members": q.value, "team_launches": tl.value, "team_timeouts": to.value,
                 "team_late_parts": late.value}
 
+    TEAM_REFUSALS = (None, "switch off", "matrix-free / joint", "single panel", "Q > 8", "too few CUs", "tpx < 1", "LDS",
+                     "residency")
+
+    def team_info(self):
+        """What the team sweep (csrc/teamsweep.hip.h) and the row panels would do with this problem as it stands
+        (gh_team_sweep_plan; read-only, callable before the first sweep): `on`, `refusal` (None or one of
+        TEAM_REFUSALS), the team's figures (0 past the refusal) and the row panels'."""
+        out = (C.c_int32 * 16)()
+        self._chk(self._lib.gh_team_sweep_plan(self._h, out))
+        names = ("on", "refusal", "Q", "panel_rows", "last_rows", "tpx", "n_teams", "cols_per_team", "grid", "lag",
+                 "lds_bytes", "n_panels", "rows_per_panel", "last_panel_rows")
+        d = dict(zip(names, (int(v) for v in out)))
+        d["on"] = bool(d["on"])
+        d["refusal"] = self.TEAM_REFUSALS[d["refusal"]]
+        return d
+
     def resident_info(self, chains=1):
         """What the resident kernels would do with this problem (gh_chain_resident_plan; read-only): the partition
         of csrc/resident.hip.h, its LDS request for `chains` chains, and whether `chains` chains would run in

@@ -763,6 +763,17 @@ int gh_chain_resident_plan(gh_ctx *ctx, int chains, int32_t out[16]);
  * columns for which some member found its team's parts not yet published when it needed them
  * and had to wait (as of the last synchronisation; columns x members x launches is the total). */
 int gh_team_sweep_stats(gh_ctx *ctx, int *members, int64_t *launches, int *timeouts, int64_t *late_parts);
+/* What the team sweep and the row panels would do with this context as it stands (read-only: nothing is
+ * allocated or launched; callable before the first sweep, after the kernel is stored).  out: [0] the fused
+ * step runs on teams, [1] why not: 0 it does, 1 GRAVHMC_TEAM=0, 2 matrix-free, joint or row-sharded store
+ * or no stored kernel, 3 a single row panel (N <= 16384), 4 more than 8 members, 5 fewer than 8 CUs per
+ * member, 6 no team per XCD slot, 7 the LDS request is refused, 8 the grid would not be resident; [2] members
+ * per team Q, [3] rows per member, [4] rows of the last member, [5] teams per XCD slot, [6] teams (8 x [5]),
+ * [7] columns per team, [8] workgroups, [9] columns of lag (GRAVHMC_TEAM_LAG), [10] LDS bytes of a workgroup;
+ * the row panels every other sweep of such a context runs in: [11] panels, [12] rows per panel, [13] rows of
+ * the last panel; [14], [15] 0.  Past the refusal that stopped the plan the team's figures are 0.
+ * GRAVHMC_TEAM_TPX=n (diagnostic) lowers [5] to min(n, planned): fewer, longer column runs per team. */
+int gh_team_sweep_plan(gh_ctx *ctx, int32_t out[16]);
 int gh_chain_get_x(gh_ctx *ctx, double *x /* M */);
 int gh_chain_get_dsyn(gh_ctx *ctx, double *dsyn /* N, dpre of the current state */);
 /* ---- several chains sharing every sweep of G (fp64 MFMA) ---------------------------------- */

@@ -1498,7 +1498,9 @@ def test_row_panels_chain_matches_oracle(G, orc, monkeypatch, capfd):
     GRAVHMC_TEAM=0, and after a team timed out, in row panels (adjoint of all panels, update,
     forward of all panels).  Potential, gradient and trajectories against the CPU oracle on both
     paths; a time-out of the teams (test hook) repeats the trajectory in row panels: same bits as
-    the row-panel run."""
+    the row-panel run.  Bound: max(1e-10, 10 x the oracle's own spread under a reversal of the
+    observation rows) -- 5.1e-16 under MS (all five rejected), 1.0e-14 under TV (all accepted), so
+    1e-10; the state is compared after rejections too, and chain_get_x() at the end."""
     rng = np.random.default_rng(8)
     N, M = 17011, 150
     A = np.asfortranarray(rng.normal(size=(N, M)) * rng.uniform(0.2, 2, size=M))
@@ -1527,13 +1529,31 @@ def test_row_panels_chain_matches_oracle(G, orc, monkeypatch, capfd):
             eng.chain_init(xg, low, high)
             ntr = 2 if path == "team-abort" else 5          # (every aborted launch waits 2 s)
             trajs = [(int(rng.integers(1, 7)), rng.normal(size=M) * 0.02, float(rng.uniform())) for _ in range(5)][:ntr]
+            # the bound: the oracle against itself with the observation rows reversed (every sum over the 17011
+            # observations in another order) on these trajectories, times ten, and no less than 1e-10 -- the
+            # rule of tests/team_oracle_cases.py
+            Pr = orc.Problem(np.asfortranarray(Aw[::-1]), dobs[::-1].copy(), 0.001 * wm, reg, 0.7, 0.01, wm=wm, shape=shape)
+            spread, xa, xb = 0.0, xo, xo
+            for L, p0, u in trajs:
+                xa, acca, oa, _ = P.leapfrog(xa, p0, 0.002, L, low, high, u)
+                xb, accb, ob, _ = Pr.leapfrog(xb, p0, 0.002, L, low, high, u)
+                assert acca == accb
+                spread = max(spread, relmax(ob, oa), relmax(xb, xa))
+            tol = max(1e-10, 10.0 * spread)
+            assert tol <= 1e-9
             res = []
             eng.run_chain(iter(trajs), 0.002, lambda L, acc, o, xs: res.append((acc, o.copy(), xs)), want_x=True)
+            xd, worst = xo, 0.0
             for (L, p0, u), (acc, o, xs) in zip(trajs, res):
                 xo, acco, oo, _ = P.leapfrog(xo, p0, 0.002, L, low, high, u)
-                assert acc == acco and relmax(o, oo) < 1e-9
-                if acc:
-                    assert relmax(xs, xo) < 1e-9
+                assert (xs is not None) == bool(acc)
+                xd = xs if acc else xd          # (after a rejection: the state before)
+                worst = max(worst, relmax(o, oo), relmax(xd, xo))
+                assert acc == acco and relmax(o, oo) <= tol, (path, reg, relmax(o, oo), tol)
+                assert relmax(xd, xo) <= tol, (path, reg, relmax(xd, xo), tol)
+            x_end = eng.chain_get_x()           # the state the chain is left in, after a rejection too
+            assert np.array_equal(x_end, xd) and relmax(x_end, xo) <= tol
+            print("%s, %s: spread %.2e, bound %.2e, worst relmax against the oracle %.2e" % (path, reg, spread, tol, worst))
             runs[path].append(res)
         eng.close()
     err = capfd.readouterr().err
