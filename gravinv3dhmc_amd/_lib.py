@@ -51,6 +51,7 @@ PROTOTYPES = {
     "gh_set_cells": (C.c_int, [_ctx, _dp, C.c_int, C.c_double]),
     "gh_set_cells_tf": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
     "gh_set_cells_joint": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
+    "gh_set_cells_joint_table": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
     "gh_set_cells_mvi": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double]),
     "gh_set_cells_mvi_data": (C.c_int, [_ctx, _dp, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), _dp]),
     "gh_b_result": (C.c_int, [_ctx, C.c_int, _dp, _dp]),

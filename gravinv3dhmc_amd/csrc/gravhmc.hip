@@ -17,6 +17,7 @@
 #include "fold.hip.h"
 #include "lattice.hip.h"
 #include "latmvi.hip.h"
+#include "latjoint.hip.h"
 #include "latbatch.hip.h"
 #include "poststream.hip.h"
 #include "tessmag.hip.h"
@@ -245,9 +246,10 @@ int gh_set_cells_tf(gh_ctx *c, const double *bounds6, double fx, double fy, doub
     return set_cells(c, bounds6, GH_CELL_PRISM_TF, GH_COMP_GZ, c->ratio, dir);
 }
 
-int gh_set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
+// The joint store's cells: dense, or -- on_table -- on the translation-invariant table, where the store has no rows to
+// limit (the same checks and the same context otherwise; the geometry is looked at by gh_build_G)
+static int set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double fy, double fz, bool on_table)
 {
-    GH_FEED_GUARD(c);
     const CellStore &s = CELL_STORES[GH_CELL_PRISM_JOINT];
     if (!c || !bounds6) return fail(c, GH_ERR_ARG, "%s: null pointer", s.entry);
     if (c->N % 2 != 0 || c->M % 2 != 0)
@@ -255,7 +257,7 @@ int gh_set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double fy, d
     const double dir[3] = {fx, fy, fz};
     TRY(check_direction(c, s.entry, dir));
     TRY(check_context(c, s, "the joint kernel"));
-    if (c->N / 2 > 16384)
+    if (c->N / 2 > 16384 && !on_table)
         return fail(c, GH_ERR_UNSUPPORTED, "%s: N/2 = %lld observations: the joint kernel takes at most 16384 (no row "
                                            "panels or team sweep)", s.entry, (long long)(c->N / 2));
     HIPCHK(c, hipSetDevice(c->device));
@@ -278,7 +280,24 @@ int gh_set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double fy, d
     c->cell_kind = GH_CELL_PRISM_JOINT;
     c->comp = GH_COMP_GZ;
     c->have_cells = true;
+    if (on_table) {
+        lattice_switch_on(c, false);
+        c->lat->axes = 2;  // (the property of a column as one more layer coordinate, latjoint.hip.h)
+    }
     return GH_OK;
+}
+
+int gh_set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
+{
+    GH_FEED_GUARD(c);
+    return set_cells_joint(c, bounds6, fx, fy, fz, false);
+}
+
+// (the same context as gh_set_cells_joint makes, and that call's name in the refusals)
+int gh_set_cells_joint_table(gh_ctx *c, const double *bounds6, double fx, double fy, double fz)
+{
+    GH_FEED_GUARD(c);
+    return set_cells_joint(c, bounds6, fx, fy, fz, true);
 }
 
 // What the entry points of the stores of blocks below are called with (null where an entry point has no such argument)
@@ -853,10 +872,12 @@ int gh_set_translation_invariant(gh_ctx *c, int enable)
                                    "batches; 4: the table that takes the bootstrap batch)");
     if (enable) TRY(dense_single_chain_refuse(c, "gh_set_translation_invariant"));
     if (c->have_G || c->work_ready) return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: call before gh_build_G");
-    if (lattice_multi(c))
+    if (lattice_multi(c) || lattice_joint(c))
         return fail(c, GH_ERR_UNSUPPORTED, "gh_set_translation_invariant: %s was set onto %s with its cells "
                                            "(%s): the table is this context's form", store_name(c), LATTICE_NAME,
-                    lattice_mvi(c) ? "gh_set_cells_mvi_table" : "gh_set_cells_multi_table");
+                    lattice_joint(c) ? "gh_set_cells_joint_table"
+                    : lattice_mvi(c) ? "gh_set_cells_mvi_table"
+                                     : "gh_set_cells_multi_table");
     if (enable && c->ls)
         return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: the shift-invariant store is switched on: one form at a time");
     if (enable && !c->lat && c->mf)
@@ -1104,16 +1125,18 @@ int gh_build_G(gh_ctx *c)
         if (c->work_ready) return fail(c, GH_ERR_ARG, "gh_build_G: a matrix-free context is built once");
         // (a store of blocks: the tesseroid forms and the prisms' multi-component store get here, by way of their tables)
         if (c->lat) {
-            if (!c->lat->multi) TRY(dense_single_chain_refuse(c, "gh_build_G on the translation-invariant store"));
+            // (... and the joint store, by way of gh_set_cells_joint_table)
+            const bool own_table = c->lat->multi || lattice_joint(c);
+            if (!own_table) TRY(dense_single_chain_refuse(c, "gh_build_G on the translation-invariant store"));
             if (c->cell_kind != GH_CELL_PRISM && c->cell_kind != GH_CELL_PRISM_COMP && c->cell_kind != GH_CELL_PRISM_TF &&
-                !c->lat->multi)
+                !own_table)
                 return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s holds prisms (tesseroid grids: gh_set_shift_invariant)",
                             LATTICE_NAME);
             if (c->sh.kind != 0)
                 return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s is not supported on a sharded context (one GPU holds the table)",
                             LATTICE_NAME);
         }
-        if (store_name(c) && !c->ls && !lattice_multi(c))
+        if (store_name(c) && !c->ls && !lattice_multi(c) && !lattice_joint(c))
             return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s has no matrix-free mode (dense, or the shift-invariant store)",
                         store_name(c));
         c->mf_fused = c->ld <= 16384 && env_int("GRAVHMC_MF_FUSED", 1) != 0;
@@ -1252,14 +1275,20 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
             return fail(c, GH_ERR_ARG, "gh_weight: the joint kernel is weighted by the column 2-norms (weightfactor 0.5)");
         // population std of each unweighted block, two passes (weightKDM, potential.py:1050-1051)
         const int64_t m = store_cells(c), n = store_points(c);
-        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((c->ld * m + 255) / 256, (int64_t)c->cus * 8));
+        // (on the table: over the entries of one property's table, each weighted by the pairs that have its offset)
+        const bool table = lattice_on(c);
+        const int64_t entries = table ? (int64_t)(c->lat->g.nz / 2) * c->lat->g.U * c->lat->g.V : c->ld * m;
+        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((entries + 255) / 256, (int64_t)c->cus * 8));
         double *part = nullptr, *mean = nullptr;
         TRY(dalloc(c, &part, 2 * (size_t)gx));
         TRY(dalloc(c, &mean, 2));
         std::vector<double> hp(2 * (size_t)gx);
         double mu[2], var[2];
         for (int pass = 0; pass < 2; ++pass) {
-            joint_std_kernel<<<dim3(gx, 2), dim3(256), 0, c->stream>>>(c->G, n, m, c->ld, pass, mean, part);
+            if (table)
+                ghk::lat_joint_std_kernel<<<dim3(gx, 2), dim3(256), 0, c->stream>>>(c->lat->g, pass, mean, part);
+            else
+                joint_std_kernel<<<dim3(gx, 2), dim3(256), 0, c->stream>>>(c->G, n, m, c->ld, pass, mean, part);
             HIPCHK(c, hipGetLastError());
             TRY(d2h(c, hp.data(), part, hp.size()));
             for (int h = 0; h < 2; ++h) {
@@ -1330,8 +1359,9 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
                            c->cols_per_team, c->n_teams_sweep, weightfactor, c->wm);
     }
     HIPCHK(c, hipGetLastError());
-    if (c->joint) {
-        // Wb: the tf block times s = std_gz / std_tf, folded into the stored kernel (Aw = Wb A Wm^-1)
+    if (c->joint && !c->mf) {
+        // Wb: the tf block times s = std_gz / std_tf, folded into the stored kernel (Aw = Wb A Wm^-1); on the table the
+        // passes take s from here on (lattice_blocks)
         const int64_t m = store_cells(c);
         const double sb = c->joint_std[0] / c->joint_std[1];
         scale_cols_kernel<<<dim3((unsigned)std::min<int64_t>((c->ld * m + 255) / 256, 1 << 20)), dim3(256), 0, c->stream>>>(

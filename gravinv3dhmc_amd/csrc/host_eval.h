@@ -13,8 +13,9 @@ static void reduce_slab(gh_ctx *c, const double *gfix, double *d_out)
 {
     const dim3 blocks(c->work.n_dpart, 1), threads(32, 8);
     if (c->joint) {
-        // the joint store: the first half of the slab rows sums to d_gz, the second to d_tf ([gz: ld | tf: ld])
-        const int half = c->grid / 2;
+        // the joint store: the first half of the live slab rows sums to d_gz, the second to d_tf ([gz: ld | tf: ld]) --
+        // the sweep's workgroups, or on the table the forward's chunks of layers
+        const int half = slab_rows_live(c) / 2;
         for (int h = 0; h < 2; ++h)
             reduce_slab_kernel<<<blocks, threads, 0, c->stream>>>(c->slab + (int64_t)h * half * c->ld, half, c->ld,
                                                                   store_points(c), nullptr, d_out + h * c->ld, c->dpart);
@@ -40,7 +41,7 @@ static void reduce_slab(gh_ctx *c, const double *gfix, double *d_out)
 // (scal_cg_kernel) sums them.  Below 2048 rows (few 32-row blocks for many slab rows) reduce_reg_kernel first
 // folds the block's slab rows into slab2 segments, as the single-property path does: more than 64 slab rows per
 // block (slab2 exists whenever the grid has more than 64, host_layout.h).
-static bool joint_two_stage(const gh_ctx *c) { return c->joint && c->ld < 2048 && c->grid / 2 > 64; }
+static bool joint_two_stage(const gh_ctx *c) { return c->joint && c->ld < 2048 && slab_rows_live(c) / 2 > 64; }
 
 // The cross-gradient coupling at x (2m), both blocks in one launch: g (or null) takes lambda dPhi/dmw -- added to
 // what is there (the epilogue: behind the two blocks' regulariser) or stored --, t (or null) the vectors, part the
@@ -148,7 +149,7 @@ static ReduceFinishArgs reduce_finish_args(const gh_ctx *c, const gh_ctx::StateS
 static int finalize_joint(gh_ctx *c, const double *x, const gh_ctx::StateSet &o)
 {
     const WorkLayout &w = c->work;
-    const int half = c->grid / 2;
+    const int half = slab_rows_live(c) / 2;
     const bool two_stage = joint_two_stage(c);
     if (two_stage && !c->slab2) return fail(c, GH_ERR_ARG, "joint epilogue: no slab2 (ensure_work not run)");
     for (int h = 0; h < 2; ++h) {

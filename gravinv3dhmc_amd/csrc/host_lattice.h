@@ -169,6 +169,8 @@ struct LatticeHost {
     int nb = 1;
     // the magnetization-vector store on the table (gh_set_cells_mvi_table; latmvi.hip.h): the axis of a column is one more
     // layer coordinate, g.nz = axes x the geometry's layers, layer L = ax nz + k; else 1
+    // the joint gravity-magnetic store on the table (gh_set_cells_joint_table; latjoint.hip.h): axes = 2, the property of
+    // a column as that layer coordinate, and layer L meets the observation block L / nz alone
     int axes = 1;
     // gh_set_translation_invariant(2): the table also takes chain batches (latbatch.hip.h).  Their partition is made
     // by latb_plan on the built table: bt_state 0 not yet, 1 planned, -1 an extent the batch tile cannot hold
@@ -196,6 +198,10 @@ static int lattice_mvi_refuse(gh_ctx *c, const char *who, const char *why)
     return GH_OK;
 }
 
+// ... the joint gravity-magnetic store: gh_set_cells_joint_table is the one call that does (one table of 2 nz layers)
+static bool lattice_joint(const gh_ctx *c) { return c && c->lat && c->lat->axes == 2; }
+static const char *const LATTICE_JOINT_NAME = "the joint store on the translation-invariant table";
+
 // What gh_set_translation_invariant(1) does to a context that may take the table (its own checks passed), and what
 // gh_set_cells_multi_table does once the store's blocks are set
 static void lattice_switch_on(gh_ctx *c, bool multi)
@@ -211,6 +217,14 @@ static void lattice_switch_on(gh_ctx *c, bool multi)
 static ghk::LatBlocks lattice_blocks(const gh_ctx *c)
 {
     ghk::LatBlocks bl{};
+    if (lattice_joint(c)) {
+        // (the joint store: observation vectors are [gz: ld | tf: ld], and the tf block carries s = std_gz / std_tf)
+        bl.n = 2;
+        bl.Nb = c->ld;
+        bl.w[0] = 1.0;
+        bl.w[1] = c->weighted ? c->joint_std[0] / c->joint_std[1] : 1.0;
+        return bl;
+    }
     bl.n = c->lat->nb;
     bl.Nb = store_points(c);
     for (int b = 0; b < bl.n; ++b) bl.w[b] = (c->lat->multi && c->weighted) ? c->mc.w[b] : 1.0;
@@ -281,8 +295,8 @@ static int lattice_build(gh_ctx *c)
     std::vector<int> loc, col, loo, ool;
     const int reason = lattice_detect_host(Np, ox.data(), oy.data(), oz.data(), m, b6.data(), dims, loc, col, loo, ool);
     if (reason != GH_LATTICE_ON)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s needs a regular prism grid under gridded data: %s", LATTICE_NAME,
-                    lattice_reason_text(reason));
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s needs a regular prism grid under gridded data: %s",
+                    lattice_joint(c) ? LATTICE_JOINT_NAME : LATTICE_NAME, lattice_reason_text(reason));
     ghk::LatGeom &g = h.g;
     g.nx = dims[0];
     g.ny = dims[1];
@@ -312,6 +326,9 @@ static int lattice_build(gh_ctx *c)
     if (h.multi) {
         HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<false, true>), h.lds_adj));
         HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<true, true>), h.lds_fwd));
+    } else if (h.axes == 2) {
+        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<false, false, true>), h.lds_adj));
+        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<true, false, true>), h.lds_fwd));
     } else {
         HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<false, false>), h.lds_adj));
         HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<true, false>), h.lds_fwd));
@@ -325,11 +342,18 @@ static int lattice_build(gh_ctx *c)
         const int want = std::max(1, std::min(g.nz, (4 * c->cus + per - 1) / per));
         h.fwd.lpc = (g.nz + want - 1) / want;
         h.chunks = (g.nz + h.fwd.lpc - 1) / h.fwd.lpc;
+        if (h.axes == 2) {
+            // the joint store: a chunk sums into the slab row of ONE observation block, so the chunks of that many
+            // layers are cut per property -- the same number for each, the first half of the slab rows gz's
+            h.fwd.lpc = std::min(h.fwd.lpc, nzg);
+            h.chunks = 2 * ((nzg + h.fwd.lpc - 1) / h.fwd.lpc);
+        }
     }
     TRY(dalloc(c, &h.T, (size_t)h.nb * nT, false));
     TRY(dalloc(c, &h.cell_of, (size_t)c->M, false));
     TRY(dalloc(c, &h.obs_of, (size_t)Np, false));
-    TRY(dalloc(c, &g.rl, (size_t)h.nb * (size_t)g.px * (size_t)g.qyp));  // (zeroed: the padding stays zero)
+    // (zeroed: the padding stays zero; the joint store: its two observation blocks)
+    TRY(dalloc(c, &g.rl, (size_t)(h.axes == 2 ? 2 : h.nb) * (size_t)g.px * (size_t)g.qyp));
     TRY(dalloc(c, &g.xl, (size_t)c->M / (size_t)g.ny * (size_t)g.nyp));
     HIPCHK(c, hipMemcpyAsync(h.cell_of, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(h.obs_of, ool.data(), sizeof(int) * ool.size(), hipMemcpyHostToDevice, c->stream));
@@ -351,6 +375,32 @@ static int lattice_build(gh_ctx *c)
             c->obs[0], c->obs[1], c->obs[2], c->bounds, g, nzg, make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]),
             block_comps(c), h.T, T2);
     }
+    if (h.axes == 2) {
+        // the joint store: the gz table of a gh_set_cells_prism context on the geometry, then the tf table of a
+        // gh_set_cells_tf context, each by that context's launch over the geometry's nzg layers (the first half of the
+        // expanded map is the geometry's)
+        ghk::LatGeom gg = g;
+        gg.nz = nzg;
+        const size_t nTg = (size_t)nzg * (size_t)g.U * (size_t)g.V;
+        MfGeom mg = mf_geom(c);
+        mg.N = Np;
+        mg.M = m;
+        mg.kind = GH_CELL_PRISM;
+        ghk::lat_fill_kernel<MF_E_GEN><<<dim3((unsigned)((nTg + 255) / 256)), dim3(256), 0, c->stream>>>(mg, gg, h.T, T2);
+        mg.kind = GH_CELL_PRISM_TF;
+        mg.o3 = c->tf_dir_d;
+        ghk::lat_fill_kernel<MF_E_TF><<<dim3((unsigned)((nTg + 255) / 256)), dim3(256), 0, c->stream>>>(mg, gg, h.T + nTg,
+                                                                                                     T2 + nTg);
+    }
+    // (the deviation of a table: as a fraction of its own largest entry)
+    auto table_dev = [](const double *a, const double *b, size_t n) {
+        double tmax = 0.0, dmax = 0.0;
+        for (size_t i = 0; i < n; ++i) {
+            tmax = std::max(tmax, std::fabs(a[i]));
+            dmax = std::max(dmax, std::fabs(b[i] - a[i]));
+        }
+        return tmax > 0.0 ? dmax / tmax : (dmax > 0.0 ? HUGE_VAL : 0.0);
+    };
     for (int b = 0; b < h.nb; ++b) {
         MfGeom mg = mf_geom(c);
         lat_fill_fn fill = mf_pick<lat_fill_fn>(c, ghk::lat_fill_kernel<MF_E_GEN>, ghk::lat_fill_kernel<MF_E_TF>,
@@ -366,7 +416,7 @@ static int lattice_build(gh_ctx *c)
         double *Tb = h.T + (size_t)b * nT;
         // (magnetization vectors: the block's three axes, filled above, checked against the block's largest entry)
         const double *T2b = h.axes == 3 ? T2 + (size_t)b * nT : T2;
-        if (h.axes != 3) hipLaunchKernelGGL(fill, dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, c->stream, mg, g, Tb, T2);
+        if (h.axes == 1) hipLaunchKernelGGL(fill, dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, c->stream, mg, g, Tb, T2);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(t1.data(), Tb, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(t2.data(), T2b, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -375,12 +425,11 @@ static int lattice_build(gh_ctx *c)
             (void)hipFree(T2);
             return fail(c, GH_ERR_HIP, "gh_build_G: %s: fill of the table: %s", LATTICE_NAME, hipGetErrorString(e));
         }
-        double tmax = 0.0, dmax = 0.0;
-        for (size_t i = 0; i < nT; ++i) {
-            tmax = std::max(tmax, std::fabs(t1[i]));
-            dmax = std::max(dmax, std::fabs(t2[i] - t1[i]));
-        }
-        h.max_dev = std::max(h.max_dev, tmax > 0.0 ? dmax / tmax : (dmax > 0.0 ? HUGE_VAL : 0.0));
+        // (the joint store: each property's table against its own largest entry)
+        const int parts = h.axes == 2 ? 2 : 1;
+        for (int q = 0; q < parts; ++q)
+            h.max_dev = std::max(h.max_dev, table_dev(t1.data() + (size_t)q * (nT / parts), t2.data() + (size_t)q * (nT / parts),
+                                                      nT / parts));
     }
     (void)hipFree(T2);
     h.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -407,18 +456,22 @@ static int launch_lattice(gh_ctx *c, SweepArgs &a, const double *wm)
     const ghk::LatBlocks bl = lattice_blocks(c);
     const lat_pass_fn adj_one = ghk::lat_pass_kernel<false, false>, adj_blocks = ghk::lat_pass_kernel<false, true>;
     const lat_pass_fn fwd_one = ghk::lat_pass_kernel<true, false>, fwd_blocks = ghk::lat_pass_kernel<true, true>;
+    // (the joint store: the single table's grids, layer L on the observation block L / nz -- two blocks of r ld apart
+    // under the weights {1, s}, the forward's chunks cut per property)
+    const lat_pass_fn adj_bd = ghk::lat_pass_kernel<false, false, true>, fwd_bd = ghk::lat_pass_kernel<true, false, true>;
+    const bool bd = h.axes == 2;
     if (a.mode & SW_ADJ) {
-        if (h.multi)
+        if (h.multi || bd)
             ghk::lat_gather_r_blocks_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(g, bl, a.r);
         else
             ghk::lat_gather_r_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(g, a.r);
-        hipLaunchKernelGGL(h.multi ? adj_blocks : adj_one, dim3((unsigned)h.gx_adj, (unsigned)g.nz), dim3(ghk::LAT_THREADS),
-                           h.lds_adj, c->stream, g, h.adj, a, wm, c->ld, bl);
+        hipLaunchKernelGGL(bd ? adj_bd : h.multi ? adj_blocks : adj_one, dim3((unsigned)h.gx_adj, (unsigned)g.nz),
+                           dim3(ghk::LAT_THREADS), h.lds_adj, c->stream, g, h.adj, a, wm, c->ld, bl);
     }
     if (a.mode & SW_FWD) {
         const double *x = (a.mode & SW_UPD) ? a.x_out : a.x_in;
         ghk::lat_gather_x_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(g, x, wm);
-        hipLaunchKernelGGL(h.multi ? fwd_blocks : fwd_one, dim3((unsigned)h.gx_fwd, (unsigned)h.chunks, (unsigned)h.nb),
+        hipLaunchKernelGGL(bd ? fwd_bd : h.multi ? fwd_blocks : fwd_one, dim3((unsigned)h.gx_fwd, (unsigned)h.chunks, (unsigned)h.nb),
                            dim3(ghk::LAT_THREADS), h.lds_fwd, c->stream, g, h.fwd, a, wm, c->ld, bl);
     }
     return GH_OK;

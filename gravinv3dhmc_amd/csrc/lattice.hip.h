@@ -50,6 +50,14 @@
 // adjoint (MB) runs the steps of four input rows block after block into the SAME accumulators -- a step never mixes
 // two blocks, the rows past px of a block's last step are zeros -- then the one cell update; the forward takes the
 // block as blockIdx.z and shares xl.  The LDS tile is the single block's.  Order of the sums: block, input row, input.
+//
+// Block-diagonal layers (BD; the joint gravity-magnetic store on the table, gh_set_cells_joint_table; latjoint.hip.h):
+// the table has 2 nz layers, layer L = b nz + k the field b (0 gz, 1 tf) of a unit property b in the geometry's layer
+// k, and layer L meets the observation block L / nz ALONE.  rl is [2][p][.] = w_b r of block b.  The adjoint's workgroup
+// of layer L reads rl[L / nz] where the other forms read rl[0]; the forward's chunks of layers never cross the
+// boundary between the properties: gridDim.y / 2 chunks each, chunk c of property b the layers b nz + c lpc ..., its
+// partial sum times w_b into slab row blockIdx.y -- the first half of the slab rows sums to d of block 0, the second
+// to d of block 1, each row c->ld long (the block's own).  Everything else is the single block's pass.
 #pragma once
 
 namespace ghk {
@@ -182,7 +190,8 @@ __global__ void __launch_bounds__(256) lat_gather_x_kernel(LatGeom l, const doub
 // (tile of output rows) * pl.FT + tile of the fast axis.  Dynamic LDS: (pl.TR + 3) pl.WL + 4 NFi8 + 2048 doubles.
 // MB: row blocks (bl).  FWD: blockIdx.z = block, outputs to slab[chunk][b Nb + obs] times w_b; else the steps of four
 // input rows run block after block over rl[b] with T[b], before the one update.  !MB: bl is not read.
-template <bool FWD, bool MB>
+// BD (with !MB): block-diagonal layers, see the head of the file; bl.w[b] weighs the forward of property b.
+template <bool FWD, bool MB, bool BD = false>
 __global__ void __launch_bounds__(LAT_THREADS) lat_pass_kernel(LatGeom g, LatPlan pl, SweepArgs a, const double *wm,
                                                                int64_t ld, LatBlocks bl)
 {
@@ -201,8 +210,13 @@ __global__ void __launch_bounds__(LAT_THREADS) lat_pass_kernel(LatGeom g, LatPla
     double *red = ins + LAT_G * NFip;
     const int orow = lane / nobt, ob = lane - orow * nobt;
     const bool act = orow < TR;
-    const int k0 = FWD ? (int)blockIdx.y * pl.lpc : (int)blockIdx.y;
-    const int k1 = FWD ? min(g.nz, k0 + pl.lpc) : k0 + 1;
+    static_assert(!(MB && BD), "block-diagonal layers are a form of the single table");
+    // (BD: nzl layers per property; the forward's property and its chunk from blockIdx.y)
+    const int nzl = BD ? g.nz / 2 : g.nz;
+    const int prop = (BD && FWD) ? (int)blockIdx.y / ((int)gridDim.y / 2) : 0;
+    const int kb = (BD && FWD) ? prop * nzl + ((int)blockIdx.y - prop * ((int)gridDim.y / 2)) * pl.lpc : 0;
+    const int k0 = (BD && FWD) ? kb : FWD ? (int)blockIdx.y * pl.lpc : (int)blockIdx.y;
+    const int k1 = (BD && FWD) ? min((prop + 1) * nzl, k0 + pl.lpc) : FWD ? min(g.nz, k0 + pl.lpc) : k0 + 1;
 
     double acc[LAT_R];
 #pragma unroll
@@ -214,7 +228,8 @@ __global__ void __launch_bounds__(LAT_THREADS) lat_pass_kernel(LatGeom g, LatPla
     for (int k = k0; k < k1; ++k) {
         for (int blk = b0; blk < b1; ++blk) {
             const double *Tk = g.T + ((int64_t)blk * g.nz + k) * g.U * g.V;
-            const double *inl = FWD ? g.xl + (int64_t)k * g.nx * g.nyp : g.rl + (int64_t)blk * g.px * g.qyp;
+            const double *inl = FWD ? g.xl + (int64_t)k * g.nx * g.nyp
+                                    : g.rl + (int64_t)(BD ? k / nzl : blk) * g.px * g.qyp;
             for (int ir0 = 0; ir0 < NRi; ir0 += LAT_G) {
                 __syncthreads();  // (the previous step's reads of tabs / ins)
                 // table rows u_lo .. u_lo + TRW - 1; staged index wl <-> v (the forward reads the row backwards)
@@ -278,6 +293,8 @@ __global__ void __launch_bounds__(LAT_THREADS) lat_pass_kernel(LatGeom g, LatPla
         if (FWD) {
             if (MB)
                 a.slab[(int64_t)blockIdx.y * ld + b0 * bl.Nb + g.obs_of[(int64_t)orow_abs * g.qy + o]] = s * bl.w[b0];
+            else if (BD)
+                a.slab[(int64_t)blockIdx.y * ld + g.obs_of[(int64_t)orow_abs * g.qy + o]] = s * bl.w[prop];
             else
                 a.slab[(int64_t)blockIdx.y * ld + g.obs_of[(int64_t)orow_abs * g.qy + o]] = s;
         } else {

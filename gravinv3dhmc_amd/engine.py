@@ -135,22 +135,35 @@ class Engine(object):
             raise ValueError("Input arrays xp, yp, and zp must have same length!")
         self._chk(self._lib.gh_set_obs(self._h, ptr(a), ptr(b), ptr(c)))
 
-    def set_cells(self, bounds6, kind, ratio=1.6, direction=None, component=None):
+    def set_cells(self, bounds6, kind, ratio=1.6, direction=None, component=None, translation_invariant=False):
         """kind CELL_PRISM / CELL_TESSEROID (ratio: the tesseroid distance-size ratio), or CELL_PRISM_TF with
         direction = (fx, fy, fz), the unit vector of the regional field (utils.dircos(inc, dec)).
         component (kind CELL_PRISM or CELL_PRISM_COMP for prisms, CELL_TESSEROID or CELL_TESSEROID_COMP for
         tesseroids): the gravity field, a name of _lib.COMPONENTS or a COMP_* value; "gz" is kind CELL_PRISM /
         CELL_TESSEROID itself (gh_set_cells_prism / gh_set_cells_tess).
         CELL_PRISM_JOINT: the M/2 prisms (bounds (M/2, 6)) of a joint gravity-magnetic model -- gz and the total
-        field along direction, inverted together (gh_set_cells_joint); call it before set_obs."""
+        field along direction, inverted together (gh_set_cells_joint); call it before set_obs.
+        translation_invariant=True, with CELL_PRISM_JOINT alone (gh_set_cells_joint_table): the joint store on the
+        translation-invariant table, the property of a column one more layer coordinate and each layer on its own
+        observation block (csrc/latjoint.hip.h), no 16384-point limit; build_G raises NotImplementedError with the
+        reason if the geometry lacks the structure.  Every other kind takes the table from
+        set_translation_invariant."""
         b = f64(bounds6)
+        if translation_invariant and int(kind) != _lib.CELL_PRISM_JOINT:
+            raise ValueError("set_cells: translation_invariant=True is the joint store's door to the table "
+                             "(CELL_PRISM_JOINT); other kinds: set_translation_invariant")
+        if isinstance(translation_invariant, str):
+            raise ValueError("set_cells: translation_invariant must be True or False, not %r" % (translation_invariant,))
         if int(kind) == _lib.CELL_PRISM_JOINT:
             if b.shape != (self.M // 2, 6):
                 raise ValueError("bounds table of a joint model must be (M/2, 6)")
             if direction is None or len(direction) != 3:
                 raise ValueError("the joint kernel's total field needs direction = (fx, fy, fz)")
             fx, fy, fz = (float(v) for v in direction)
-            self._chk(self._lib.gh_set_cells_joint(self._h, ptr(b), fx, fy, fz))
+            fn = self._lib.gh_set_cells_joint_table if translation_invariant else self._lib.gh_set_cells_joint
+            self._chk(fn(self._h, ptr(b), fx, fy, fz))
+            if translation_invariant:
+                self._translation_invariant = True
             self._set_store(_lib.CELL_PRISM_JOINT, cols=2, rows=2)
             return
         if b.shape != (self.M, 6):
@@ -460,11 +473,13 @@ class Engine(object):
                                                           C.byref(bm)))
         d = {"on": bool(i[0].value), "nx": i[1].value, "ny": i[2].value, "nz": i[3].value, "px": i[4].value,
              "qy": i[5].value, "table_bytes": tb.value, "max_dev": md.value, "build_ms": bm.value}
-        if self._store.kind == _lib.CELL_PRISM_MVI_DATA and d["on"]:
+        if self._store.kind in (_lib.CELL_PRISM_MVI_DATA, _lib.CELL_PRISM_JOINT) and d["on"]:
+            # (the joint store on the table, set_cells(..., CELL_PRISM_JOINT, translation_invariant=True): axes = 2, half
+            # of the chunks each property's)
             a = [C.c_int(0) for _ in range(3)]
             self._chk(self._lib.gh_translation_invariant_axes(self._h, *[C.byref(v) for v in a]))
-            if a[0].value == 3:
-                d.update(axes=3, chunks=a[1].value, layers_per_chunk=a[2].value)
+            if a[0].value == (2 if self.joint else 3):
+                d.update(axes=a[0].value, chunks=a[1].value, layers_per_chunk=a[2].value)
         return d
 
     def translation_invariant_table(self):
@@ -474,7 +489,9 @@ class Engine(object):
         if not t["on"]:
             raise ValueError("no table resident (set_translation_invariant, build_G)")
         shape = (t["nz"], t["nx"] + t["px"] - 1, t["ny"] + t["qy"] - 1)
-        if t.get("axes"):     # (magnetization vectors: (C, 3, nz, ., .), the axis a layer coordinate)
+        if self.joint:        # (the joint store: (2, nz, ., .), gz then tf, the property a layer coordinate)
+            shape = (t["axes"],) + shape
+        elif t.get("axes"):   # (magnetization vectors: (C, 3, nz, ., .), the axis a layer coordinate)
             shape = (self._store.rows, t["axes"]) + shape
         T = np.empty(((self._store.rows,) + shape) if self._store.kind == _lib.CELL_PRISM_MULTI else shape)
         self._chk(self._lib.gh_translation_invariant_table(self._h, ptr(T)))

@@ -361,6 +361,9 @@ _TABLE_ROW = (("_translation_invariant",), "the translation-invariant store (tra
 #: the row of the prisms' multi-component store: on its tables asked for with translation_invariant="chains" it runs batches
 _MULTI_ROW = (("multi",), "the multi-component store (MultiComponentModule)")
 _NO_BATCH = (
+    # (the joint store answers `joint` on either form: on the table it names the table too, and comes first)
+    (("joint", "_translation_invariant"), "the joint store on the translation-invariant table (JointModule with "
+                                          "translation_invariant=True)"),
     (("joint",), "the joint gravity-magnetic kernel (JointModule)"),
     (("tess_mag",), "the tesseroid magnetization store (TesseroidMagVectorModule)"),
     (("tess_multi",), "the tesseroid multi-component store (TesseroidMultiComponentModule)"),

@@ -14,7 +14,9 @@ from scipy.sparse import block_diag, coo_matrix
 
 from .. import _lib, utils
 from ..engine import Engine
-from .potential import _diag, _mesh, _Potential
+from .potential import _diag, _mesh, _OnTable, _Potential
+
+_TSTORE = "the joint store on the translation-invariant table"
 
 
 def fd3d(shape):
@@ -43,7 +45,7 @@ def fd3d(shape):
     return coo_matrix((V, (I, J)), (nderivs, nx * ny * nz)).tocsr()
 
 
-class JointModule(_Potential):
+class JointModule(_OnTable, _Potential):
     """Joint gravity (gz) and total-field magnetic inversion model on one MI355X.
 
     Parameters are the reference's (potential.py:848-851): dobs_gz, dobs_tf (the same N observation points),
@@ -68,12 +70,25 @@ class JointModule(_Potential):
     branches are broken); Smoothness and TV work, with the block-diagonal operator fd3djoint (the reference
     raises AttributeError there: it calls a missing fd3d).  CrossGradient is implemented (the reference's body is
     `pass`) and can be switched into the potential.
+
+    translation_invariant=True (extension) keeps the translation-invariant table instead of the kernel (a regular mesh
+    -- no mratio growth or mtopo -- under observations that are a full rectangle of the lattice of the cells'
+    horizontal spacings at one height, GravMagModule's translation_invariant): one table of 2 nz layers, the gz table
+    then the tf table, each layer meeting its own observation block alone (csrc/latjoint.hip.h) -- two tables of 15.8 MB
+    where 100 x 100 x 50 cells under 100 x 100 stations store two blocks of 40 GB, and no limit of 16384 points.
+    HMCSample (posterior_stream too), misfit_and_grad, forward, the four regularisers, crossgradient= /
+    set_cross_gradient / CrossGradient / last_cross_gradient, std_gz, std_tf, Wb, dobsw, Wm, WmInv, WmSquare and
+    translation_invariant_info() work on it as on the dense module and agree with it to 1e-10 (the bound the suites test); Aw, A, kernel_gz and
+    kernel_tf do not exist (the kernel is never stored), and mtopo=, HMCSampleBatch and translation_invariant="chains"
+    are refused (NotImplementedError naming the joint store on the translation-invariant table), as is a geometry
+    without the structure, with the reason.  The default False is the module as it always was.
     """
     _props = 2  # (density and magnetization of the same mesh)
+    _store = _TSTORE
 
     def __init__(self, dobs_gz, dobs_tf, mrange, mspacing, obsurface, mratio=1, coordinate="cartesian", njobs=1,
                  mangle=(90, 0), wavelet=False, device=0, verbose=True, crossgradient=0.0, cg_scale=(1.0, 1.0),
-                 **kwargs):
+                 translation_invariant=False, **kwargs):
         self._say = print if verbose else (lambda *a, **k: None)
         if coordinate == "spherical":
             # (the reference's spherical branch never defines kernel_tf: potential.py:885-895)
@@ -88,6 +103,16 @@ class JointModule(_Potential):
         if dobs_gz.size != dobs_tf.size or dobs_gz.size != n:
             raise ValueError("dobs_gz (%d), dobs_tf (%d) and the observation points (%d) must have the same length"
                              % (dobs_gz.size, dobs_tf.size, n))
+        if isinstance(translation_invariant, str) and translation_invariant != "chains":
+            raise ValueError("translation_invariant must be True or False, not %r" % (translation_invariant,))
+        if translation_invariant:
+            self.translation_invariant = True   # (the default module keeps the attributes it always had: the class's False)
+        if translation_invariant == "chains":
+            raise NotImplementedError("%s (translation_invariant=True) runs one chain: batches of joint models "
+                                      "(translation_invariant=\"chains\") are not built" % _TSTORE)
+        if translation_invariant and kwargs:
+            raise NotImplementedError("%s (translation_invariant=True) does not combine with mtopo: a carved mesh is "
+                                      "not a full regular product of cells" % _TSTORE)
         self.dobs_gz, self.dobs_tf = dobs_gz, dobs_tf
         self.mrange = mrange
         self.mspacing = mspacing
@@ -109,9 +134,13 @@ class JointModule(_Potential):
         bounds = mesh.cell_bounds(active_only=True)
         m = bounds.shape[0]
         eng = Engine(2 * n, 2 * m, device=device)
-        eng.set_cells(bounds, _lib.CELL_PRISM_JOINT, direction=utils.dircos(self.inc, self.dec))
+        if self.translation_invariant:
+            eng.set_cells(bounds, _lib.CELL_PRISM_JOINT, direction=utils.dircos(self.inc, self.dec),
+                          translation_invariant=True)
+        else:
+            eng.set_cells(bounds, _lib.CELL_PRISM_JOINT, direction=utils.dircos(self.inc, self.dec))
         eng.set_obs(self.lonobs, self.latobs, self.heightobs)
-        eng.build_G()
+        eng.build_G()  # (on the table: NotImplementedError with the detection's reason where the structure is absent)
         self._engine = eng
 
         self.mshape = mesh.shape
@@ -141,21 +170,26 @@ class JointModule(_Potential):
         self.Wb = _diag(wb)
         self.dobs = np.append(self.dobs_gz, self.dobs_tf)
         self.dobsw = self.Wb @ self.dobs
+        if self.translation_invariant:
+            self._hide_Aw()
 
     @property
     def A(self):
         """The unweighted stacked kernel, 2N x 2M, from the device copy (Wb^-1 Aw Wm; rounding differs)."""
+        self._no_table("A")
         A = np.asarray(self.Aw)
         wb = self.Wb.diagonal()
         return (A / wb[:, None]) * self.Wm.diagonal()[None, :]
 
     @property
     def kernel_gz(self):
+        self._no_table("kernel_gz")
         n, m = self.dobs_gz.size, self.Wm.shape[0] // 2
         return np.ascontiguousarray(self.A[:n, :m])
 
     @property
     def kernel_tf(self):
+        self._no_table("kernel_tf")
         n, m = self.dobs_gz.size, self.Wm.shape[0] // 2
         return np.ascontiguousarray(self.A[n:, m:])
 

@@ -336,7 +336,44 @@ class GravMagModule(_Potential):
         self._weight(self.weightfactor)
 
 
-class _BlockStore(_Potential):
+class _OnTable(object):
+    """What the modules whose store also runs on a table instead of the stored kernel share (the stores of row blocks,
+    JointModule): the info, the hidden device handle, and the refusal of what is formed from the kernel.  A class states
+    `_store`, the store's name in the refusals."""
+    translation_invariant = shift_invariant = False
+
+    def translation_invariant_info(self):
+        """The engine's translation_invariant_info(): on, nx, ny, nz, px, qy, table_bytes (all blocks), max_dev (the
+        largest of the blocks'), build_ms; on a table of magnetization vectors also axes, chunks, layers_per_chunk."""
+        return self._engine.translation_invariant_info()
+
+    def _hide_Aw(self):
+        """On the translation-invariant table no store is behind the device handle the constructor leaves: the sampler
+        keeps it (kernelw), the attribute Aw raises."""
+        self._Aw = self.__dict__.pop("Aw")
+
+    # ------------------------------------------------------------------ what is formed from the store
+    def _no_table(self, what):
+        if self.translation_invariant:
+            raise NotImplementedError("%s: %s keeps the translation-invariant table, the kernel is never stored" %
+                                      (what, self._store))
+        if self.shift_invariant:
+            raise NotImplementedError("%s: %s keeps the shift-invariant table, the kernel is never stored" %
+                                      (what, self._store))
+
+    def __getattr__(self, name):
+        # (reached for an attribute that does not exist: Aw on the translation-invariant table, where no store is behind
+        # the device handle the constructor leaves)
+        if name == "Aw" and self.__dict__.get("translation_invariant"):
+            self._no_table("Aw")
+        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
+
+    def kernelw(self):
+        """(Aw, WmInv, Wm) as the sampler expects; Aw is a device handle (on the table: of the tables)."""
+        return (self._Aw if self.translation_invariant else self.Aw), self.WmInv, self.Wm
+
+
+class _BlockStore(_OnTable, _Potential):
     """The modules whose store stacks row blocks -- data components of the same cells at the same points, block b in
     its own units times a data weight w_b, with a mean of its own (MultiComponentModule, MagVectorModule and their
     tesseroid forms) -- share the parser of their data, the ladder of their refusals, their construction and what is
@@ -485,36 +522,6 @@ class _BlockStore(_Potential):
                         (bool(kwargs), "mtopo: a carved mesh is not a full regular product of cells")):
             if on:
                 raise NotImplementedError(store + " does not combine with " + why)
-
-    def translation_invariant_info(self):
-        """The engine's translation_invariant_info(): on, nx, ny, nz, px, qy, table_bytes (all blocks), max_dev (the
-        largest of the blocks'), build_ms; on a table of magnetization vectors also axes, chunks, layers_per_chunk."""
-        return self._engine.translation_invariant_info()
-
-    def _hide_Aw(self):
-        """On the translation-invariant table no store is behind the device handle the constructor leaves: the sampler
-        keeps it (kernelw), the attribute Aw raises."""
-        self._Aw = self.__dict__.pop("Aw")
-
-    # ------------------------------------------------------------------ what is formed from the store
-    def _no_table(self, what):
-        if self.translation_invariant:
-            raise NotImplementedError("%s: %s keeps the translation-invariant table, the kernel is never stored" %
-                                      (what, self._store))
-        if self.shift_invariant:
-            raise NotImplementedError("%s: %s keeps the shift-invariant table, the kernel is never stored" %
-                                      (what, self._store))
-
-    def __getattr__(self, name):
-        # (reached for an attribute that does not exist: Aw on the translation-invariant table, where no store is behind
-        # the device handle the constructor leaves)
-        if name == "Aw" and self.__dict__.get("translation_invariant"):
-            self._no_table("Aw")
-        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
-
-    def kernelw(self):
-        """(Aw, WmInv, Wm) as the sampler expects; Aw is a device handle (on the table: of the tables)."""
-        return (self._Aw if self.translation_invariant else self.Aw), self.WmInv, self.Wm
 
     def forward(self, model):
         """Unweighted forward A @ model of the physical model (M entries, property-major): the predicted values,

@@ -12,7 +12,8 @@
  * gravity fields of one density model can share one store and be inverted together (gh_set_cells_multi; an
  * extension, the reference inverts one field at a time), on a regular grid under gridded data without a limit on the
  * rows (gh_set_cells_multi_table: one translation-invariant table per field; gh_set_cells_multi_table_chains: the
- * same tables, which also take batches of 16 chains per read, gh_batch_*).  Every entry
+ * same tables, which also take batches of 16 chains per read, gh_batch_*).  The joint gravity-magnetic store
+ * (gh_set_cells_joint) runs on that table too, as one table of block-diagonal layers (gh_set_cells_joint_table).  Every entry
  * point below names the reference interface it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer of the reference would add.
  *
@@ -324,6 +325,22 @@ int gh_amplitude_last(const gh_ctx *ctx, double *phi);
  * gh_shard_init*, gh_upload_G and N/2 > 16384 return GH_ERR_UNSUPPORTED; the resident chain kernel is
  * never chosen (chains run on the fused sweep). */
 int gh_set_cells_joint(gh_ctx *ctx, const double *bounds6, double fx, double fy, double fz);
+/* The same store on the translation-invariant table (csrc/latjoint.hip.h; gh_set_translation_invariant below has the
+ * geometry the table needs): the arguments, the checks -- but the limit on N/2, the table has no rows -- and the context
+ * of gh_set_cells_joint, whose name the refusals keep.  gh_build_G then detects the structure on the M/2 cells and N/2
+ * points (GH_ERR_UNSUPPORTED naming the joint store on the translation-invariant table, with the reason, where it is
+ * absent) and fills ONE table of 2 nz layers, T[2][nz][nx + px - 1][ny + qy - 1]: T[0], bit for bit, the table a
+ * gh_set_cells_prism (gz) context builds under gh_set_translation_invariant(ctx, 1) on the geometry, T[1] that of a
+ * gh_set_cells_tf context; max_dev is the larger of the two tables' (each against its own largest entry).  The store
+ * is block-diagonal: layer b nz + k meets the observation block b alone, in both passes (lat_pass_kernel's
+ * block-diagonal form) -- the forward's chunks of layers are cut per property, gh_translation_invariant_axes reports
+ * axes = 2, the chunks (half of them each property's) and the layers per chunk.  gh_weight takes Wm from the tables'
+ * windows and std_gz, std_tf from their entries weighted by the pairs that share an offset, and from then on the passes
+ * multiply the tf block by s = std_gz / std_tf where the dense store has it folded in; gh_set_data, gh_set_reg,
+ * gh_set_cross_gradient, gh_forward, gh_adjoint, gh_misfit_and_grad and the single chain (gh_chain_*, the posterior
+ * stream) work as on the dense store and agree with it to 1e-10, the bound the suites test.  Refused as on the dense store, and gh_download_G
+ * (nothing is stored), gh_set_translation_invariant (the table is this context's form), gh_bscg_run. */
+int gh_set_cells_joint_table(gh_ctx *ctx, const double *bounds6, double fx, double fy, double fz);
 /* std_gz, std_tf of the unweighted blocks of a weighted GH_CELL_PRISM_JOINT context (numpy.std, ddof 0,
  * over the (N/2) (M/2) entries of each block; two passes on the device) */
 int gh_joint_std(const gh_ctx *ctx, double std2[2]);
@@ -1140,12 +1157,14 @@ int gh_translation_invariant_batch_plan(gh_ctx *ctx, int32_t out[24]);
  * and build_ms of the build. */
 int gh_translation_invariant_info(const gh_ctx *ctx, int *on, int *nx, int *ny, int *nz, int *px, int *qy,
                                   int64_t *table_bytes, double *max_dev, double *build_ms);
-/* What a table of magnetization vectors adds (gh_set_cells_mvi_table): axes, the layers' factor (3 there, 1 on every
- * other table: the table has axes x nz layers, nz as gh_translation_invariant_info reports it), and the forward
- * pass's partition of those layers, chunks of layers_per_chunk.  All 0 while no table is built. */
+/* What a table of magnetization vectors adds (gh_set_cells_mvi_table): axes, the layers' factor (3 there, 2 on the
+ * joint store's table, gh_set_cells_joint_table, 1 on every other table: the table has axes x nz layers, nz as
+ * gh_translation_invariant_info reports it), and the forward pass's partition of those layers, chunks of
+ * layers_per_chunk (joint store: chunks / 2 per property, none across the boundary).  All 0 while no table is built. */
 int gh_translation_invariant_axes(const gh_ctx *ctx, int *axes, int *chunks, int *layers_per_chunk);
 /* The table T[nz][nx + px - 1][ny + qy - 1] (row-major) as it lies on the device; a gh_set_cells_multi_table
- * context: its ncomp tables, block-major; a gh_set_cells_mvi_table context: T[ncomp][3][nz][.][.]. */
+ * context: its ncomp tables, block-major; a gh_set_cells_mvi_table context: T[ncomp][3][nz][.][.]; a
+ * gh_set_cells_joint_table context: T[2][nz][.][.], gz then tf. */
 int gh_translation_invariant_table(gh_ctx *ctx, double *out);
 enum {
     GH_LATTICE_ON = 0,
