@@ -38,6 +38,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -280,10 +281,7 @@ static int set_cells_joint(gh_ctx *c, const double *bounds6, double fx, double f
     c->cell_kind = GH_CELL_PRISM_JOINT;
     c->comp = GH_COMP_GZ;
     c->have_cells = true;
-    if (on_table) {
-        lattice_switch_on(c, false);
-        c->lat->axes = 2;  // (the property of a column as one more layer coordinate, latjoint.hip.h)
-    }
+    if (on_table) lattice_switch_on(c, LAT_JOINT, GH_TABLE_SINGLE);
     return GH_OK;
 }
 
@@ -363,11 +361,7 @@ static int set_block_cells(gh_ctx *c, int kind, const BlockCells &a)
     c->comp = s.comps == COMPS_GRAV ? a.comps[0] : GH_COMP_GZ;
     if (s.tess) c->ratio = a.ratios ? a.ratios[0] : a.ratio;
     c->have_cells = true;
-    if (a.on_table && !s.tess) {
-        lattice_switch_on(c, true);
-        c->lat->chains = a.chains;
-        c->lat->axes = s.cols;  // (magnetization vectors: the axis as one more layer coordinate, latmvi.hip.h)
-    }
+    if (a.on_table && !s.tess) lattice_switch_on(c, s.cols == 3 ? LAT_MVI : LAT_MULTI, a.chains ? GH_TABLE_CHAINS : GH_TABLE_SINGLE);
     return a.on_table && s.tess ? gh_set_shift_invariant(c, 1) : GH_OK;
 }
 
@@ -872,12 +866,10 @@ int gh_set_translation_invariant(gh_ctx *c, int enable)
                                    "batches; 4: the table that takes the bootstrap batch)");
     if (enable) TRY(dense_single_chain_refuse(c, "gh_set_translation_invariant"));
     if (c->have_G || c->work_ready) return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: call before gh_build_G");
-    if (lattice_multi(c) || lattice_joint(c))
+    if (lattice_own(c))
         return fail(c, GH_ERR_UNSUPPORTED, "gh_set_translation_invariant: %s was set onto %s with its cells "
                                            "(%s): the table is this context's form", store_name(c), LATTICE_NAME,
-                    lattice_joint(c) ? "gh_set_cells_joint_table"
-                    : lattice_mvi(c) ? "gh_set_cells_mvi_table"
-                                     : "gh_set_cells_multi_table");
+                    lattice_form(c).entry);
     if (enable && c->ls)
         return fail(c, GH_ERR_ARG, "gh_set_translation_invariant: the shift-invariant store is switched on: one form at a time");
     if (enable && !c->lat && c->mf)
@@ -892,11 +884,7 @@ int gh_set_translation_invariant(gh_ctx *c, int enable)
     if (c->lat) c->mf = c->lat->mf_before;
     delete c->lat;
     c->lat = nullptr;
-    if (enable) {
-        lattice_switch_on(c, false);
-        c->lat->chains = enable == GH_TABLE_CHAINS;
-        c->lat->reps = enable == GH_TABLE_REPLICATES;
-    }
+    if (enable) lattice_switch_on(c, LAT_SCALAR, enable);
     return GH_OK;
 }
 
@@ -910,7 +898,7 @@ int gh_translation_invariant_info(const gh_ctx *c, int *on, int *nx, int *ny, in
     if (on) *on = o ? 1 : 0;
     if (nx) *nx = g.nx;
     if (ny) *ny = g.ny;
-    if (nz) *nz = o ? g.nz / c->lat->axes : 0;  // (the geometry's layers: gh_translation_invariant_axes has the factor)
+    if (nz) *nz = o ? g.nz / lattice_form(c).groups : 0;  // (the geometry's layers: gh_translation_invariant_axes has the factor)
     if (px) *px = g.px;
     if (qy) *qy = g.qy;
     if (table_bytes) *table_bytes = (int64_t)(o ? c->lat->nb : 1) * g.nz * g.U * g.V * (int64_t)sizeof(double);
@@ -924,7 +912,7 @@ int gh_translation_invariant_axes(const gh_ctx *c, int *axes, int *chunks, int *
     GH_FEED_GUARD(c);
     if (!c) return GH_ERR_ARG;
     const bool o = lattice_on(c);
-    if (axes) *axes = o ? c->lat->axes : 0;
+    if (axes) *axes = o ? lattice_form(c).groups : 0;
     if (chunks) *chunks = o ? c->lat->chunks : 0;
     if (layers_per_chunk) *layers_per_chunk = o ? c->lat->fwd.lpc : 0;
     return GH_OK;
@@ -957,7 +945,7 @@ int gh_translation_invariant_batch_plan(gh_ctx *c, int32_t out[24])
     out[19] = h.bfwd.lpc;
     out[20] = h.bchunks;
     out[21] = h.bgx_adj * h.g.nz;
-    out[22] = h.multi ? h.nb : 0;  // (the table of blocks: the forward's grid is nb workgroups deep)
+    out[22] = lattice_multi(c) ? h.nb : 0;  // (the table of blocks: the forward's grid is nb workgroups deep)
     return GH_OK;
 }
 
@@ -1126,7 +1114,7 @@ int gh_build_G(gh_ctx *c)
         // (a store of blocks: the tesseroid forms and the prisms' multi-component store get here, by way of their tables)
         if (c->lat) {
             // (... and the joint store, by way of gh_set_cells_joint_table)
-            const bool own_table = c->lat->multi || lattice_joint(c);
+            const bool own_table = lattice_own(c);
             if (!own_table) TRY(dense_single_chain_refuse(c, "gh_build_G on the translation-invariant store"));
             if (c->cell_kind != GH_CELL_PRISM && c->cell_kind != GH_CELL_PRISM_COMP && c->cell_kind != GH_CELL_PRISM_TF &&
                 !own_table)
@@ -1136,7 +1124,7 @@ int gh_build_G(gh_ctx *c)
                 return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s is not supported on a sharded context (one GPU holds the table)",
                             LATTICE_NAME);
         }
-        if (store_name(c) && !c->ls && !lattice_multi(c) && !lattice_joint(c))
+        if (store_name(c) && !c->ls && !lattice_own(c))
             return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s has no matrix-free mode (dense, or the shift-invariant store)",
                         store_name(c));
         c->mf_fused = c->ld <= 16384 && env_int("GRAVHMC_MF_FUSED", 1) != 0;
@@ -1323,15 +1311,8 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
         lonsym_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(
             lonsym_geom(c), c->ls->a_of, c->ls->m_of, weightfactor, c->wm);
     } else if (lattice_on(c)) {
-        if (c->lat->multi) {
-            // (the column norms of Wb A: the weights, which the passes apply once the context is weighted)
-            ghk::LatBlocks bl = lattice_blocks(c);
-            for (int b = 0; b < bl.n; ++b) bl.w[b] = c->mc.w[b];
-            lat_colnorm_blocks_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(c->lat->g, bl, weightfactor,
-                                                                                                       c->wm);
-        } else {
-            lat_colnorm_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(c->lat->g, weightfactor, c->wm);
-        }
+        lat_colnorm_blocks_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(c->lat->g, lattice_tables(c),
+                                                                                                   weightfactor, c->wm);
     } else if (c->mf) {
         hipLaunchKernelGGL(mf_pick(c, mf_colnorm_kernel<MF_E_GEN>, mf_colnorm_kernel<MF_E_TF>, mf_colnorm_kernel<MF_E_COMP>,
                                    mf_colnorm_kernel<MF_E_TESS>),
@@ -1361,7 +1342,7 @@ int gh_weight(gh_ctx *c, double weightfactor, double *wm_out)
     HIPCHK(c, hipGetLastError());
     if (c->joint && !c->mf) {
         // Wb: the tf block times s = std_gz / std_tf, folded into the stored kernel (Aw = Wb A Wm^-1); on the table the
-        // passes take s from here on (lattice_blocks)
+        // passes take s from here on (lattice_r_blocks)
         const int64_t m = store_cells(c);
         const double sb = c->joint_std[0] / c->joint_std[1];
         scale_cols_kernel<<<dim3((unsigned)std::min<int64_t>((c->ld * m + 255) / 256, 1 << 20)), dim3(256), 0, c->stream>>>(
@@ -1428,7 +1409,9 @@ int gh_set_data(gh_ctx *c, const double *dobs, const double *grav_fix)
     };
     if (c->mc.n > 0) {
         // Wb dobs in row blocks: every component loses its own mean
-        if (grav_fix) TRY(lattice_mvi_refuse(c, "gh_set_data with a grav_fix", "every data block loses its own mean"));
+        if (grav_fix && lattice_mvi(c))
+            return fail(c, GH_ERR_UNSUPPORTED, "gh_set_data with a grav_fix: not supported on %s (every data block loses its own mean)",
+                        lattice_form(c).name);
         if (grav_fix)
             return fail(c, GH_ERR_ARG, "gh_set_data: %s takes no grav_fix", store_of(c).rows_name);
         const size_t Nb = (size_t)store_points(c);

@@ -11,11 +11,11 @@ static int bscg_refuse(gh_ctx *c, int B, int maxk)
     const bool table = lattice_reps(c);
     // (a store of blocks names itself: each is dense and unsharded, but for the tesseroid forms on the table)
     // (the table of blocks that takes chain batches names the table, as the single-block table of chains does)
-    const char *what = lattice_mvi(c)             ? LATTICE_MVI_NAME
-                       : lattice_multi_chains(c)  ? LATTICE_NAME
-                       : c->ls && tess_mag_store(c) ? "the tesseroid magnetization store on the shift-invariant table"
-                                                    : store_of(c).rows_name;
-    if (what)
+    const char *what = c->ls && tess_mag_store(c) ? "the tesseroid magnetization store on the shift-invariant table"
+                                                  : store_of(c).rows_name;
+    if (lattice_mvi(c) || lattice_multi_chains(c))
+        what = lattice_form(c).name;
+    else if (what)
         ;
     else if (c->ls)
         what = "a shift-invariant store";

@@ -171,17 +171,16 @@ static int refuse_plain_cells(gh_ctx *c)
 // magnetization-vector stores -- refuse `who`, each naming itself.  (The tesseroid forms also run on the
 // shift-invariant table, the prisms' multi-component store on the translation-invariant one: still one chain, no
 // other form.)
-static bool lattice_multi(const gh_ctx *c);  // host_lattice.h: the multi-component store set onto its table
+static bool lattice_own(const gh_ctx *c);  // host_lattice.h: a store set onto the translation-invariant table with its cells
 // ... with gh_set_cells_multi_table_chains: the table of blocks that takes chain batches.  Not a single-chain store;
 // what it does not run either, the table's own refusals name (lattice_refuse and its kin)
 static bool lattice_multi_chains(const gh_ctx *c);
-static bool lattice_joint(const gh_ctx *c);  // host_lattice.h: the joint store set onto the table (gh_set_cells_joint_table)
 static int dense_single_chain_refuse(gh_ctx *c, const char *who)
 {
     if (c && store_name(c) && !lattice_multi_chains(c))
         return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on %s (%s, single chain)", who, store_name(c),
                     store_of(c).table != TABLE_NO           ? "dense or shift-invariant"
-                    : lattice_multi(c) || lattice_joint(c) ? "dense or on the translation-invariant table"
+                    : lattice_own(c)                        ? "dense or on the translation-invariant table"
                                                             : "dense");
     return GH_OK;
 }

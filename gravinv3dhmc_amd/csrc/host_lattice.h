@@ -1,6 +1,6 @@
 // libgravhmc host side: the translation-invariant store of a regular prism grid under gridded data
-// (lattice.hip.h).  Detection of the structure (context-free), the build of the table, the partition of the two
-// passes, their launches.  Included once by gravhmc.hip, after host_fold.h.
+// (lattice.hip.h).  Detection of the structure (context-free), one table of the forms a store takes on it, the build of
+// the table in its steps, the two passes' launches, the batch passes.  Included once by gravhmc.hip, after host_fold.h.
 #pragma once
 
 // ------------------------------------------------------------------------------------ detection (host)
@@ -150,13 +150,55 @@ static const char *lattice_reason_text(int reason)
     return "";
 }
 
-// ----------------------------------------------------------------------------------- store and launches
+// ------------------------------------------------------------------------------------- the table's forms
 
 static const char *const LATTICE_NAME = "the translation-invariant store";
+
+typedef void (*lat_fill_fn)(MfGeom, ghk::LatGeom, double *, double *);
+typedef void (*lat_pass_fn)(ghk::LatGeom, ghk::LatPlan, SweepArgs, const double *, int64_t, ghk::LatBlocks);
+
+// What a store is on the table: one row per form, and the code below reads the row.  LAT_SCALAR: a prism store of one
+// block (gz, a component, the total field).  LAT_MULTI: the multi-component store, one table per row block (lattice.hip.h,
+// "Row blocks").  LAT_MVI: the vector-data magnetization store, the axis of a column as one more layer coordinate under row
+// blocks of magnetic data (latmvi.hip.h).  LAT_JOINT: the joint gravity-magnetic store, the property of a column as that
+// layer coordinate, a layer on the observation block of its property alone (latjoint.hip.h; "Block-diagonal layers").
+enum { LAT_SCALAR = 0, LAT_MULTI, LAT_MVI, LAT_JOINT };
+constexpr int PER_COMPONENT = 0;  // a count of a row: one per component of the store's block table (c->mc.n)
+
+struct LatForm {
+    const char *name;        // the form as the refusals of what it does not run name it
+    const char *build_name;  // ... and as gh_build_G does on a geometry without the structure
+    const char *entry;       // the entry point that set the form with its cells -- the table is then the context's form and
+                             // stays; null: gh_set_translation_invariant, which may also switch it off again
+    int groups;              // layer groups: LatGeom::nz = groups x the geometry's layers, layer L = group nz + k
+    int rblocks;             // blocks of r (LatGeom::rl), one per field of the data: also the parts of the store whose
+                             // deviation is checked against their own largest entry
+    int tables;              // tables T[b] a layer sums over
+    lat_pass_fn adj, fwd;    // the two passes
+    bool cut;                // the forward's chunks of layers are cut per layer group: a chunk sums into one block of d
+};
+
+static const LatForm LAT_FORMS[] = {
+    {LATTICE_NAME, LATTICE_NAME, nullptr, 1, 1, 1, ghk::lat_pass_kernel<false, false>, ghk::lat_pass_kernel<true, false>, false},
+    {LATTICE_NAME, LATTICE_NAME, "gh_set_cells_multi_table", 1, PER_COMPONENT, PER_COMPONENT,
+     ghk::lat_pass_kernel<false, true>, ghk::lat_pass_kernel<true, true>, false},
+    {"the vector-data magnetization store on the translation-invariant table", LATTICE_NAME, "gh_set_cells_mvi_table", 3,
+     PER_COMPONENT, PER_COMPONENT, ghk::lat_pass_kernel<false, true>, ghk::lat_pass_kernel<true, true>, false},
+    {"the joint store on the translation-invariant table", "the joint store on the translation-invariant table",
+     "gh_set_cells_joint_table", 2, 2, 1, ghk::lat_pass_kernel<false, false, true>, ghk::lat_pass_kernel<true, false, true>, true},
+};
+static_assert(sizeof LAT_FORMS / sizeof LAT_FORMS[0] == LAT_JOINT + 1, "one row per LAT_* form");
+
+// ----------------------------------------------------------------------------------- store and launches
 
 struct LatticeHost {
     bool on = false;  // the table is built
     bool mf_before = false;  // what gh_set_matrix_free asked for before the store took c->mf
+    const LatForm *form = &LAT_FORMS[LAT_SCALAR];
+    // What the table runs: GH_TABLE_SINGLE the single chain; GH_TABLE_CHAINS chain batches too (latbatch.hip.h; on the table
+    // of blocks: gh_set_cells_multi_table_chains); GH_TABLE_REPLICATES the bootstrap batch too (gh_bscg_run)
+    int runs = GH_TABLE_SINGLE;
+    int nr = 1, nb = 1;  // the form's blocks of r and tables, counted (lattice_geometry)
     ghk::LatGeom g = {};
     ghk::LatPlan adj = {}, fwd = {};
     size_t lds_adj = 0, lds_fwd = 0;
@@ -164,19 +206,8 @@ struct LatticeHost {
     double *T = nullptr;
     int *cell_of = nullptr, *obs_of = nullptr;
     double max_dev = 0.0, build_ms = 0.0;
-    // the multi-component store on the table (gh_set_cells_multi_table): nb row blocks, one table each; else 1
-    bool multi = false;
-    int nb = 1;
-    // the magnetization-vector store on the table (gh_set_cells_mvi_table; latmvi.hip.h): the axis of a column is one more
-    // layer coordinate, g.nz = axes x the geometry's layers, layer L = ax nz + k; else 1
-    // the joint gravity-magnetic store on the table (gh_set_cells_joint_table; latjoint.hip.h): axes = 2, the property of
-    // a column as that layer coordinate, and layer L meets the observation block L / nz alone
-    int axes = 1;
-    // gh_set_translation_invariant(2): the table also takes chain batches (latbatch.hip.h).  Their partition is made
-    // by latb_plan on the built table: bt_state 0 not yet, 1 planned, -1 an extent the batch tile cannot hold
-    // gh_set_translation_invariant(4): the table also takes the bootstrap batch (gh_bscg_run) on the same plan
-    // gh_set_cells_multi_table_chains: the table of blocks (multi) that also takes chain batches -- chains with multi
-    bool chains = false, reps = false;
+    // The partition of the batch passes (chain batches and the bootstrap batch share it) is made by latb_plan on the
+    // built table: bt_state 0 not yet, 1 planned, -1 an extent the batch tile cannot hold
     int bt_state = 0;
     ghk::LatbPlan badj = {}, bfwd = {};
     size_t blds_adj = 0, blds_fwd = 0;
@@ -185,49 +216,43 @@ struct LatticeHost {
 };
 
 static bool lattice_on(const gh_ctx *c) { return c->lat && c->lat->on; }
-// the multi-component store asked onto the table: gh_set_cells_multi_table is the one call that does
-static bool lattice_multi(const gh_ctx *c) { return c->lat && c->lat->multi; }
-// ... the vector-data magnetization store: gh_set_cells_mvi_table is the one call that does (a table of blocks as well)
-static bool lattice_mvi(const gh_ctx *c) { return c && c->lat && c->lat->axes == 3; }
-static const char *const LATTICE_MVI_NAME = "the vector-data magnetization store on the translation-invariant table";
+static const LatForm &lattice_form(const gh_ctx *c) { return *c->lat->form; }
+// the store was set onto the table with its cells (LatForm::entry)
+static bool lattice_own(const gh_ctx *c) { return c && c->lat && c->lat->form->entry; }
+// ... as a table of row blocks: the multi-component store, the vector-data magnetization store
+static bool lattice_multi(const gh_ctx *c) { return c && c->lat && c->lat->form->tables == PER_COMPONENT; }
+static bool lattice_mvi(const gh_ctx *c) { return c && c->lat && c->lat->form == &LAT_FORMS[LAT_MVI]; }
 
-// What the magnetization-vector store on the table does not run names both
-static int lattice_mvi_refuse(gh_ctx *c, const char *who, const char *why)
-{
-    if (lattice_mvi(c)) return fail(c, GH_ERR_UNSUPPORTED, "%s: not supported on %s (%s)", who, LATTICE_MVI_NAME, why);
-    return GH_OK;
-}
-
-// ... the joint gravity-magnetic store: gh_set_cells_joint_table is the one call that does (one table of 2 nz layers)
-static bool lattice_joint(const gh_ctx *c) { return c && c->lat && c->lat->axes == 2; }
-static const char *const LATTICE_JOINT_NAME = "the joint store on the translation-invariant table";
-
-// What gh_set_translation_invariant(1) does to a context that may take the table (its own checks passed), and what
-// gh_set_cells_multi_table does once the store's blocks are set
-static void lattice_switch_on(gh_ctx *c, bool multi)
+// What gh_set_translation_invariant does to a context that may take the table (its own checks passed), and what the
+// gh_set_cells_*_table entry points do once the store's blocks are set
+static void lattice_switch_on(gh_ctx *c, int form, int runs)
 {
     c->lat = new LatticeHost();
     c->lat->mf_before = c->mf;
-    c->lat->multi = multi;
+    c->lat->form = &LAT_FORMS[form];
+    c->lat->runs = runs;
     c->mf = true;
 }
 
-// The row blocks as the kernels take them; the data weights hold from gh_weight on, as on the dense store (whose
-// rows gh_weight scales)
-static ghk::LatBlocks lattice_blocks(const gh_ctx *c)
+// The blocks of r as the passes and the gathers of r take them.  The data weights hold from gh_weight on, as on the dense
+// store (whose rows gh_weight scales): the components' w_b; the joint store's {1, s = std_gz / std_tf} on [gz: ld | tf: ld]
+static ghk::LatBlocks lattice_r_blocks(const gh_ctx *c)
 {
     ghk::LatBlocks bl{};
-    if (lattice_joint(c)) {
-        // (the joint store: observation vectors are [gz: ld | tf: ld], and the tf block carries s = std_gz / std_tf)
-        bl.n = 2;
-        bl.Nb = c->ld;
-        bl.w[0] = 1.0;
-        bl.w[1] = c->weighted ? c->joint_std[0] / c->joint_std[1] : 1.0;
-        return bl;
-    }
+    bl.n = c->lat->nr;
+    bl.Nb = c->joint ? c->ld : store_points(c);
+    for (int b = 0; b < bl.n; ++b) bl.w[b] = (c->weighted && c->mc.n > 0) ? c->mc.w[b] : 1.0;
+    if (c->weighted && c->joint) bl.w[1] = c->joint_std[0] / c->joint_std[1];
+    return bl;
+}
+
+// The tables a layer sums over, as gh_weight's column norms take them: those of Wb A, so the components' weights whether
+// or not the context is weighted yet (the joint store's s is not in its column norms, as on the dense store)
+static ghk::LatBlocks lattice_tables(const gh_ctx *c)
+{
+    ghk::LatBlocks bl{};
     bl.n = c->lat->nb;
-    bl.Nb = store_points(c);
-    for (int b = 0; b < bl.n; ++b) bl.w[b] = (c->lat->multi && c->weighted) ? c->mc.w[b] : 1.0;
+    for (int b = 0; b < bl.n; ++b) bl.w[b] = c->mc.n > 0 ? c->mc.w[b] : 1.0;
     return bl;
 }
 
@@ -240,12 +265,12 @@ static int lattice_refuse(gh_ctx *c, const char *who, const char *why)
 
 // The chain batch runs on the single-block table a context was asked for with gh_set_translation_invariant(2), and on
 // the table of blocks asked for with gh_set_cells_multi_table_chains (the one call that sets chains on a multi table)
-static bool lattice_chains(const gh_ctx *c) { return c && c->lat && c->lat->chains; }
+static bool lattice_chains(const gh_ctx *c) { return c && c->lat && c->lat->runs == GH_TABLE_CHAINS; }
 // ... the latter
-static bool lattice_multi_chains(const gh_ctx *c) { return lattice_chains(c) && c->lat->multi; }
+static bool lattice_multi_chains(const gh_ctx *c) { return lattice_chains(c) && lattice_multi(c); }
 
 // The bootstrap batch runs on the single-block table a context was asked for with gh_set_translation_invariant(4)
-static bool lattice_reps(const gh_ctx *c) { return c && c->lat && c->lat->reps && !c->lat->multi; }
+static bool lattice_reps(const gh_ctx *c) { return c && c->lat && c->lat->runs == GH_TABLE_REPLICATES; }
 
 // gh_batch_init / gh_batch_trajectory / gh_batch_run: the store's refusal unless the context takes batches
 static int lattice_batch_refuse(gh_ctx *c, const char *who)
@@ -273,165 +298,197 @@ static size_t lat_lds_bytes(const ghk::LatPlan &p, int NFip)
             (size_t)ghk::LAT_G * 64 * ghk::LAT_R) * sizeof(double);
 }
 
-typedef void (*lat_fill_fn)(MfGeom, ghk::LatGeom, double *, double *);
-typedef void (*lat_pass_fn)(ghk::LatGeom, ghk::LatPlan, SweepArgs, const double *, int64_t, ghk::LatBlocks);
+// ------------------------------------------------------------------------ gh_build_G on the table, in its steps
 
-// gh_build_G of a context with the store switched on: detect, fill, check
-static int lattice_build(gh_ctx *c)
+// What the steps hand on
+struct LatBuild {
+    std::vector<int> col, ool;  // the detection's cell_of_lat, expanded over the layer groups, and its obs_of_lat
+    int nzg = 0;                // the geometry's layers
+    size_t nT = 0;              // entries of one table: g.nz U V
+};
+
+// Detection on the store's points and cells, the dims of the table, the expanded map
+static int lattice_geometry(gh_ctx *c, LatBuild &b)
 {
     LatticeHost &h = *c->lat;
-    const auto t0 = std::chrono::steady_clock::now();
-    // (row blocks: the blocks share the N / nb points)
-    const int64_t Np = store_points(c);
-    h.nb = h.multi ? c->mc.n : 1;
-    // (magnetization vectors: the M columns are three axes of the same M / 3 cells)
-    const int64_t m = store_cells(c);
+    const LatForm &f = *h.form;
+    h.nr = f.rblocks == PER_COMPONENT ? c->mc.n : f.rblocks;
+    h.nb = f.tables == PER_COMPONENT ? c->mc.n : f.tables;
+    // (row blocks: the blocks share the N / nb points; layer groups: the M columns are groups of the same M / groups cells)
+    const int64_t Np = store_points(c), m = store_cells(c);
     std::vector<double> ox((size_t)Np), oy((size_t)Np), oz((size_t)Np), b6((size_t)m * 6);
     TRY(d2h(c, ox.data(), c->obs[0], ox.size()));
     TRY(d2h(c, oy.data(), c->obs[1], oy.size()));
     TRY(d2h(c, oz.data(), c->obs[2], oz.size()));
     TRY(d2h(c, b6.data(), c->bounds, b6.size()));
     int dims[5] = {0, 0, 0, 0, 0};
-    std::vector<int> loc, col, loo, ool;
-    const int reason = lattice_detect_host(Np, ox.data(), oy.data(), oz.data(), m, b6.data(), dims, loc, col, loo, ool);
+    std::vector<int> loc, loo;
+    const int reason = lattice_detect_host(Np, ox.data(), oy.data(), oz.data(), m, b6.data(), dims, loc, b.col, loo, b.ool);
     if (reason != GH_LATTICE_ON)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s needs a regular prism grid under gridded data: %s",
-                    lattice_joint(c) ? LATTICE_JOINT_NAME : LATTICE_NAME, lattice_reason_text(reason));
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s needs a regular prism grid under gridded data: %s", f.build_name,
+                    lattice_reason_text(reason));
     ghk::LatGeom &g = h.g;
     g.nx = dims[0];
     g.ny = dims[1];
-    const int nzg = dims[2];  // (the geometry's layers)
-    g.nz = h.axes * nzg;
-    // the expanded map: layer ax nz + k holds the columns ax m + cell of the geometry's layer k
-    col.resize((size_t)c->M);
-    for (int ax = 1; ax < h.axes; ++ax)
-        for (int64_t e = 0; e < m; ++e) col[(size_t)(ax * m + e)] = (int)(ax * m) + col[(size_t)e];
+    b.nzg = dims[2];
+    g.nz = f.groups * b.nzg;
+    // the expanded map: layer grp nz + k holds the columns grp m + cell of the geometry's layer k
+    b.col.resize((size_t)c->M);
+    for (int grp = 1; grp < f.groups; ++grp)
+        for (int64_t e = 0; e < m; ++e) b.col[(size_t)(grp * m + e)] = (int)(grp * m) + b.col[(size_t)e];
     g.px = dims[3];
     g.qy = dims[4];
     g.U = g.nx + g.px - 1;
     g.V = g.ny + g.qy - 1;
     g.nyp = (g.ny + 7) / 8 * 8;
     g.qyp = (g.qy + 7) / 8 * 8;
-    const size_t nT = (size_t)g.nz * (size_t)g.U * (size_t)g.V;  // (of one block)
-    if (nT > (size_t)INT_MAX * 4)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s: a table of %zu entries is beyond the fill kernel's grid", LATTICE_NAME, nT);
-    // the passes' partition and their LDS
+    b.nT = (size_t)g.nz * (size_t)g.U * (size_t)g.V;
+    if (b.nT > (size_t)INT_MAX * 4)
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s: a table of %zu entries is beyond the fill kernel's grid", LATTICE_NAME, b.nT);
+    return GH_OK;
+}
+
+// The partition of the two passes and their LDS: arithmetic on the dims, the CUs and the form, nothing else touched.
+// Returns whether both tiles are within the 160 KB of a workgroup.
+static bool lattice_partition(LatticeHost &h, int cus)
+{
+    const ghk::LatGeom &g = h.g;
     h.adj = lat_plan(g.nx, g.ny, g.qyp);
     h.fwd = lat_plan(g.px, g.qy, g.nyp);
     h.lds_adj = lat_lds_bytes(h.adj, g.qyp);
     h.lds_fwd = lat_lds_bytes(h.fwd, g.nyp);
-    if (h.lds_adj > 160 * 1024 || h.lds_fwd > 160 * 1024)
-        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s: %s (%d cells, %d observations along y: %zu bytes)", LATTICE_NAME,
-                    lattice_reason_text(GH_LATTICE_LDS), g.ny, g.qy, std::max(h.lds_adj, h.lds_fwd));
-    if (h.multi) {
-        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<false, true>), h.lds_adj));
-        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<true, true>), h.lds_fwd));
-    } else if (h.axes == 2) {
-        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<false, false, true>), h.lds_adj));
-        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<true, false, true>), h.lds_fwd));
-    } else {
-        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<false, false>), h.lds_adj));
-        HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::lat_pass_kernel<true, false>), h.lds_fwd));
-    }
     h.gx_adj = (g.nx + h.adj.TR - 1) / h.adj.TR * h.adj.FT;
     h.gx_fwd = (g.px + h.fwd.TR - 1) / h.fwd.TR * h.fwd.FT;
-    {
-        // forward: chunks of layers, one slab row each -- about four workgroups per CU, no more rows than layers
-        // (row blocks: nb gx_fwd workgroups per chunk)
-        const int per = h.nb * h.gx_fwd;
-        const int want = std::max(1, std::min(g.nz, (4 * c->cus + per - 1) / per));
-        h.fwd.lpc = (g.nz + want - 1) / want;
-        h.chunks = (g.nz + h.fwd.lpc - 1) / h.fwd.lpc;
-        if (h.axes == 2) {
-            // the joint store: a chunk sums into the slab row of ONE observation block, so the chunks of that many
-            // layers are cut per property -- the same number for each, the first half of the slab rows gz's
-            h.fwd.lpc = std::min(h.fwd.lpc, nzg);
-            h.chunks = 2 * ((nzg + h.fwd.lpc - 1) / h.fwd.lpc);
-        }
+    // forward: chunks of layers, one slab row each -- about four workgroups per CU, no more rows than layers
+    // (row blocks: nb gx_fwd workgroups per chunk)
+    const int per = h.nb * h.gx_fwd;
+    const int want = std::max(1, std::min(g.nz, (4 * cus + per - 1) / per));
+    h.fwd.lpc = (g.nz + want - 1) / want;
+    h.chunks = (g.nz + h.fwd.lpc - 1) / h.fwd.lpc;
+    if (h.form->cut) {
+        // a chunk sums into the slab row of ONE observation block, so the chunks of that many layers are cut per layer
+        // group -- the same number for each, the first slab rows the first group's
+        const int nzg = g.nz / h.form->groups;
+        h.fwd.lpc = std::min(h.fwd.lpc, nzg);
+        h.chunks = h.form->groups * ((nzg + h.fwd.lpc - 1) / h.fwd.lpc);
     }
-    TRY(dalloc(c, &h.T, (size_t)h.nb * nT, false));
+    return h.lds_adj <= 160 * 1024 && h.lds_fwd <= 160 * 1024;
+}
+
+// The launches that fill the form's store, in their order on the stream: T the entry of the first pair of every offset,
+// T2, laid out as T, the entry of the last
+static std::vector<std::function<void()>> lattice_fills(gh_ctx *c, const LatBuild &b, double *T2)
+{
+    const LatticeHost &h = *c->lat;
+    const ghk::LatGeom g = h.g;
+    double *const T = h.T;
+    std::vector<std::function<void()>> fills;
+    // lat_fill_kernel<E> with the entry function of the context mg describes, over the layers of lg, at `off` of the store
+    auto table = [&](lat_fill_fn fn, const MfGeom &mg, const ghk::LatGeom &lg, size_t off) {
+        const unsigned blocks = (unsigned)(((size_t)lg.nz * (size_t)lg.U * (size_t)lg.V + 255) / 256);
+        fills.push_back([=] { hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, c->stream, mg, lg, T + off, T2 + off); });
+    };
+    // (the geometry's own layers: the first group of the expanded map)
+    ghk::LatGeom gg = g;
+    gg.nz = b.nzg;
+    const size_t nTg = (size_t)b.nzg * (size_t)g.U * (size_t)g.V;
+    MfGeom mg = mf_geom(c);
+    switch ((int)(h.form - LAT_FORMS)) {
+    case LAT_SCALAR:
+        table(mf_pick<lat_fill_fn>(c, ghk::lat_fill_kernel<MF_E_GEN>, ghk::lat_fill_kernel<MF_E_TF>, ghk::lat_fill_kernel<MF_E_COMP>,
+                                   ghk::lat_fill_kernel<MF_E_GEN>), mg, g, 0);
+        break;
+    case LAT_MULTI:
+        // block after block, each with the entry function of a gh_set_cells_prism context of its component at the points
+        // the blocks share (gz is the GH_CELL_PRISM context's entry, as gh_set_cells_prism makes it: not among the
+        // run-time components)
+        mg.N = store_points(c);
+        for (int blk = 0; blk < h.nb; ++blk) {
+            const bool gz = c->mc.comp[blk] == GH_COMP_GZ;
+            mg.kind = gz ? GH_CELL_PRISM : GH_CELL_PRISM_COMP;
+            mg.comp = c->mc.comp[blk];
+            table(gz ? ghk::lat_fill_kernel<MF_E_GEN> : ghk::lat_fill_kernel<MF_E_COMP>, mg, g, (size_t)blk * b.nT);
+        }
+        break;
+    case LAT_MVI:
+        // one launch over the geometric offsets writes every (data block, axis) table (latmvi.hip.h)
+        fills.push_back([=] {
+            ghk::lat_fill_mvi_kernel<<<dim3((unsigned)((nTg + 255) / 256)), dim3(256), 0, c->stream>>>(
+                c->obs[0], c->obs[1], c->obs[2], c->bounds, g, gg.nz, make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]),
+                block_comps(c), T, T2);
+        });
+        break;
+    case LAT_JOINT:
+        // the gz table of a gh_set_cells_prism context on the geometry, then the tf table of a gh_set_cells_tf context,
+        // each by that context's launch over the geometry's layers
+        mg.N = store_points(c);
+        mg.M = store_cells(c);
+        mg.kind = GH_CELL_PRISM;
+        table(ghk::lat_fill_kernel<MF_E_GEN>, mg, gg, 0);
+        mg.kind = GH_CELL_PRISM_TF;
+        mg.o3 = c->tf_dir_d;
+        table(ghk::lat_fill_kernel<MF_E_TF>, mg, gg, nTg);
+        break;
+    }
+    return fills;
+}
+
+// The store's parts (LatForm::rblocks), T against T2: the deviation of a part as a fraction of its own largest entry,
+// the largest over the parts kept
+static int lattice_deviation(gh_ctx *c, const LatBuild &b, const double *T2)
+{
+    LatticeHost &h = *c->lat;
+    const size_t n = (size_t)h.nb * b.nT / (size_t)h.nr;
+    std::vector<double> t1(n), t2(n);
+    h.max_dev = 0.0;
+    hipError_t e = hipGetLastError();  // (the fills')
+    for (int q = 0; q < h.nr; ++q) {
+        if (e == hipSuccess) e = hipMemcpyAsync(t1.data(), h.T + (size_t)q * n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(t2.data(), T2 + (size_t)q * n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess)
+            return fail(c, GH_ERR_HIP, "gh_build_G: %s: fill of the table: %s", LATTICE_NAME, hipGetErrorString(e));
+        double tmax = 0.0, dmax = 0.0;
+        for (size_t i = 0; i < n; ++i) {
+            tmax = std::max(tmax, std::fabs(t1[i]));
+            dmax = std::max(dmax, std::fabs(t2[i] - t1[i]));
+        }
+        h.max_dev = std::max(h.max_dev, tmax > 0.0 ? dmax / tmax : (dmax > 0.0 ? HUGE_VAL : 0.0));
+    }
+    return GH_OK;
+}
+
+// gh_build_G of a context with the store switched on: detect, partition, allocate, fill, check
+static int lattice_build(gh_ctx *c)
+{
+    LatticeHost &h = *c->lat;
+    ghk::LatGeom &g = h.g;
+    const auto t0 = std::chrono::steady_clock::now();
+    LatBuild b;
+    TRY(lattice_geometry(c, b));
+    if (!lattice_partition(h, c->cus))
+        return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s: %s (%d cells, %d observations along y: %zu bytes)", LATTICE_NAME,
+                    lattice_reason_text(GH_LATTICE_LDS), g.ny, g.qy, std::max(h.lds_adj, h.lds_fwd));
+    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(h.form->adj), h.lds_adj));
+    HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(h.form->fwd), h.lds_fwd));
+    TRY(dalloc(c, &h.T, (size_t)h.nb * b.nT, false));
     TRY(dalloc(c, &h.cell_of, (size_t)c->M, false));
-    TRY(dalloc(c, &h.obs_of, (size_t)Np, false));
-    // (zeroed: the padding stays zero; the joint store: its two observation blocks)
-    TRY(dalloc(c, &g.rl, (size_t)(h.axes == 2 ? 2 : h.nb) * (size_t)g.px * (size_t)g.qyp));
+    TRY(dalloc(c, &h.obs_of, b.ool.size(), false));
+    // (zeroed: the padding stays zero)
+    TRY(dalloc(c, &g.rl, (size_t)h.nr * (size_t)g.px * (size_t)g.qyp));
     TRY(dalloc(c, &g.xl, (size_t)c->M / (size_t)g.ny * (size_t)g.nyp));
-    HIPCHK(c, hipMemcpyAsync(h.cell_of, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h.obs_of, ool.data(), sizeof(int) * ool.size(), hipMemcpyHostToDevice, c->stream));
+    // (b.col / b.ool outlive their copies: lattice_deviation waits for the stream)
+    HIPCHK(c, hipMemcpyAsync(h.cell_of, b.col.data(), sizeof(int) * b.col.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h.obs_of, b.ool.data(), sizeof(int) * b.ool.size(), hipMemcpyHostToDevice, c->stream));
     g.T = h.T;
     g.cell_of = h.cell_of;
     g.obs_of = h.obs_of;
-    // fill: the entry of the first and of the last pair of every offset.  (Row blocks: block after block, each with the
-    // entry function of a gh_set_cells_prism context of its component at the Np points; the deviation is a fraction of
-    // the block's own largest entry, and the largest over the blocks is kept.)
-    double *T2 = nullptr;
-    HIPCHK(c, hipMalloc((void **)&T2, (h.axes == 3 ? (size_t)h.nb : 1) * nT * sizeof(double)));
-    std::vector<double> t1(nT), t2(nT);
-    h.max_dev = 0.0;
-    if (h.axes == 3) {
-        // magnetization vectors: one launch over the geometric offsets writes every (data block, axis) table, T2 laid
-        // out as T (latmvi.hip.h)
-        const size_t nTg = (size_t)nzg * (size_t)g.U * (size_t)g.V;
-        ghk::lat_fill_mvi_kernel<<<dim3((unsigned)((nTg + 255) / 256)), dim3(256), 0, c->stream>>>(
-            c->obs[0], c->obs[1], c->obs[2], c->bounds, g, nzg, make_double3(c->tf_dir[0], c->tf_dir[1], c->tf_dir[2]),
-            block_comps(c), h.T, T2);
-    }
-    if (h.axes == 2) {
-        // the joint store: the gz table of a gh_set_cells_prism context on the geometry, then the tf table of a
-        // gh_set_cells_tf context, each by that context's launch over the geometry's nzg layers (the first half of the
-        // expanded map is the geometry's)
-        ghk::LatGeom gg = g;
-        gg.nz = nzg;
-        const size_t nTg = (size_t)nzg * (size_t)g.U * (size_t)g.V;
-        MfGeom mg = mf_geom(c);
-        mg.N = Np;
-        mg.M = m;
-        mg.kind = GH_CELL_PRISM;
-        ghk::lat_fill_kernel<MF_E_GEN><<<dim3((unsigned)((nTg + 255) / 256)), dim3(256), 0, c->stream>>>(mg, gg, h.T, T2);
-        mg.kind = GH_CELL_PRISM_TF;
-        mg.o3 = c->tf_dir_d;
-        ghk::lat_fill_kernel<MF_E_TF><<<dim3((unsigned)((nTg + 255) / 256)), dim3(256), 0, c->stream>>>(mg, gg, h.T + nTg,
-                                                                                                     T2 + nTg);
-    }
-    // (the deviation of a table: as a fraction of its own largest entry)
-    auto table_dev = [](const double *a, const double *b, size_t n) {
-        double tmax = 0.0, dmax = 0.0;
-        for (size_t i = 0; i < n; ++i) {
-            tmax = std::max(tmax, std::fabs(a[i]));
-            dmax = std::max(dmax, std::fabs(b[i] - a[i]));
-        }
-        return tmax > 0.0 ? dmax / tmax : (dmax > 0.0 ? HUGE_VAL : 0.0);
-    };
-    for (int b = 0; b < h.nb; ++b) {
-        MfGeom mg = mf_geom(c);
-        lat_fill_fn fill = mf_pick<lat_fill_fn>(c, ghk::lat_fill_kernel<MF_E_GEN>, ghk::lat_fill_kernel<MF_E_TF>,
-                                                ghk::lat_fill_kernel<MF_E_COMP>, ghk::lat_fill_kernel<MF_E_GEN>);
-        if (h.multi) {
-            // (gz is the GH_CELL_PRISM context's entry, as gh_set_cells_prism makes it: not among the run-time components)
-            const bool gz = c->mc.comp[b] == GH_COMP_GZ;
-            mg.kind = gz ? GH_CELL_PRISM : GH_CELL_PRISM_COMP;
-            mg.comp = c->mc.comp[b];
-            mg.N = Np;
-            fill = gz ? ghk::lat_fill_kernel<MF_E_GEN> : ghk::lat_fill_kernel<MF_E_COMP>;
-        }
-        double *Tb = h.T + (size_t)b * nT;
-        // (magnetization vectors: the block's three axes, filled above, checked against the block's largest entry)
-        const double *T2b = h.axes == 3 ? T2 + (size_t)b * nT : T2;
-        if (h.axes == 1) hipLaunchKernelGGL(fill, dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, c->stream, mg, g, Tb, T2);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(t1.data(), Tb, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(t2.data(), T2b, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (col / ool must outlive their copies as well)
-        if (e != hipSuccess) {
-            (void)hipFree(T2);
-            return fail(c, GH_ERR_HIP, "gh_build_G: %s: fill of the table: %s", LATTICE_NAME, hipGetErrorString(e));
-        }
-        // (the joint store: each property's table against its own largest entry)
-        const int parts = h.axes == 2 ? 2 : 1;
-        for (int q = 0; q < parts; ++q)
-            h.max_dev = std::max(h.max_dev, table_dev(t1.data() + (size_t)q * (nT / parts), t2.data() + (size_t)q * (nT / parts),
-                                                      nT / parts));
-    }
-    (void)hipFree(T2);
+    // (T2, laid out as T: released on every way out)
+    double *T2p = nullptr;
+    HIPCHK(c, hipMalloc((void **)&T2p, (size_t)h.nb * b.nT * sizeof(double)));
+    const std::unique_ptr<double, hipError_t (*)(void *)> T2(T2p, hipFree);
+    for (const auto &launch : lattice_fills(c, b, T2.get())) launch();
+    TRY(lattice_deviation(c, b, T2.get()));
     h.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (!(h.max_dev <= FOLD_MAX_DEV))
         return fail(c, GH_ERR_UNSUPPORTED, "gh_build_G: %s: %s (%.3g of the largest entry)", LATTICE_NAME,
@@ -447,32 +504,23 @@ static int lattice_configure(gh_ctx *c)
     return set_partition(c, "lattice_configure", h.chunks, (int64_t)h.gx_adj * h.g.nz);
 }
 
+// The form's two passes, each behind its gather.  The adjoint's grid is the single table's -- blocks of r run inside the
+// kernel, or a layer picks its own -- and the forward takes the table as its third grid coordinate under one gather of x
 static int launch_lattice(gh_ctx *c, SweepArgs &a, const double *wm)
 {
     const LatticeHost &h = *c->lat;
     const ghk::LatGeom &g = h.g;
-    // (row blocks: the same grid for the adjoint, whose blocks run inside the kernel; the block as the forward's
-    // third grid coordinate, under one gather of x)
-    const ghk::LatBlocks bl = lattice_blocks(c);
-    const lat_pass_fn adj_one = ghk::lat_pass_kernel<false, false>, adj_blocks = ghk::lat_pass_kernel<false, true>;
-    const lat_pass_fn fwd_one = ghk::lat_pass_kernel<true, false>, fwd_blocks = ghk::lat_pass_kernel<true, true>;
-    // (the joint store: the single table's grids, layer L on the observation block L / nz -- two blocks of r ld apart
-    // under the weights {1, s}, the forward's chunks cut per property)
-    const lat_pass_fn adj_bd = ghk::lat_pass_kernel<false, false, true>, fwd_bd = ghk::lat_pass_kernel<true, false, true>;
-    const bool bd = h.axes == 2;
+    const ghk::LatBlocks bl = lattice_r_blocks(c);
     if (a.mode & SW_ADJ) {
-        if (h.multi || bd)
-            ghk::lat_gather_r_blocks_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(g, bl, a.r);
-        else
-            ghk::lat_gather_r_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(g, a.r);
-        hipLaunchKernelGGL(bd ? adj_bd : h.multi ? adj_blocks : adj_one, dim3((unsigned)h.gx_adj, (unsigned)g.nz),
-                           dim3(ghk::LAT_THREADS), h.lds_adj, c->stream, g, h.adj, a, wm, c->ld, bl);
+        ghk::lat_gather_r_blocks_kernel<<<dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream>>>(g, bl, a.r);
+        hipLaunchKernelGGL(h.form->adj, dim3((unsigned)h.gx_adj, (unsigned)g.nz), dim3(ghk::LAT_THREADS), h.lds_adj, c->stream, g,
+                           h.adj, a, wm, c->ld, bl);
     }
     if (a.mode & SW_FWD) {
         const double *x = (a.mode & SW_UPD) ? a.x_out : a.x_in;
         ghk::lat_gather_x_kernel<<<dim3((unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream>>>(g, x, wm);
-        hipLaunchKernelGGL(bd ? fwd_bd : h.multi ? fwd_blocks : fwd_one, dim3((unsigned)h.gx_fwd, (unsigned)h.chunks, (unsigned)h.nb),
-                           dim3(ghk::LAT_THREADS), h.lds_fwd, c->stream, g, h.fwd, a, wm, c->ld, bl);
+        hipLaunchKernelGGL(h.form->fwd, dim3((unsigned)h.gx_fwd, (unsigned)h.chunks, (unsigned)h.nb), dim3(ghk::LAT_THREADS),
+                           h.lds_fwd, c->stream, g, h.fwd, a, wm, c->ld, bl);
     }
     return GH_OK;
 }
@@ -529,7 +577,7 @@ static int latb_plan(gh_ctx *c, const char *who)
     if (latb_plan_make(c)) return GH_OK;
     const LatticeHost &h = *c->lat;
     return fail(c, GH_ERR_UNSUPPORTED, "%s: %s on %s: %s (%d cells, %d observations along y: %zu bytes)", who,
-                h.reps ? "the bootstrap batch" : "chain batches", LATTICE_NAME,
+                lattice_reps(c) ? "the bootstrap batch" : "chain batches", LATTICE_NAME,
                 "a row of the lattice is too long for the batch pass's LDS tile", h.g.ny, h.g.qy,
                 std::max(h.blds_adj, h.blds_fwd));
 }
@@ -540,11 +588,11 @@ static int latb_alloc(gh_ctx *c)
     LatticeHost &h = *c->lat;
     gh_ctx::Batch &b = c->bt;
     const ghk::LatGeom &g = h.g;
-    TRY(latb_plan(c, h.reps ? "gh_bscg_run" : "gh_batch_init"));
+    TRY(latb_plan(c, lattice_reps(c) ? "gh_bscg_run" : "gh_batch_init"));
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_ADJ>), h.blds_adj));
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_CG>), h.blds_adj));
     HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_FWD>), h.blds_fwd));
-    if (h.multi) {
+    if (lattice_multi(c)) {
         HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_ADJ_MB>), h.blds_adj));
         HIPCHK(c, allow_dynamic_lds(reinterpret_cast<const void *>(ghk::latb_pass_kernel<ghk::LATB_FWD_MB>), h.blds_fwd));
         TRY(dalloc(c, &b.bmean, (size_t)ghk::CB * (size_t)h.nb));
@@ -569,10 +617,10 @@ static void latb_launch_forward(gh_ctx *c, const double *X)
     gh_ctx::Batch &b = c->bt;
     const int64_t n16 = c->M * ghk::CB;
     ghk::latb_gather_x_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, X, b.iw, h.xl16);
-    if (h.multi) {
+    if (lattice_multi(c)) {
         // (row blocks: the block as the grid's third coordinate, under the one gather of X)
         ghk::LatbBlockArgs ba{};
-        ba.bl = lattice_blocks(c);
+        ba.bl = lattice_r_blocks(c);
         hipLaunchKernelGGL(ghk::latb_pass_kernel<ghk::LATB_FWD_MB>, dim3((unsigned)h.bgx_fwd, (unsigned)h.bchunks, (unsigned)h.nb),
                            dim3(ghk::LATB_THREADS), h.blds_fwd, c->stream, g, h.bfwd, h.xl16, ba, b.iw, b.slab, c->ld);
     } else {
@@ -589,10 +637,10 @@ static void latb_launch_adjoint(gh_ctx *c, const ghk::BatchAdjArgs &a)
     const LatticeHost &h = *c->lat;
     const ghk::LatGeom &g = h.g;
     const int64_t n16 = c->N * ghk::CB;
-    if (h.multi) {
+    const ghk::LatBlocks bl = lattice_r_blocks(c);
+    ghk::latb_gather_r_blocks_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, bl, a.Rt, h.rl16);
+    if (lattice_multi(c)) {
         // (row blocks: the single block's grid, the blocks in turn inside the kernel)
-        const ghk::LatBlocks bl = lattice_blocks(c);
-        ghk::latb_gather_r_blocks_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, bl, a.Rt, h.rl16);
         ghk::LatbBlockArgs ba;
         ba.a = a;
         ba.bl = bl;
@@ -601,7 +649,6 @@ static void latb_launch_adjoint(gh_ctx *c, const ghk::BatchAdjArgs &a)
                            c->ld);
         return;
     }
-    ghk::latb_gather_r_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, a.Rt, h.rl16);
     hipLaunchKernelGGL(ghk::latb_pass_kernel<ghk::LATB_ADJ>, dim3((unsigned)h.bgx_adj, (unsigned)g.nz), dim3(ghk::LATB_THREADS),
                        h.blds_adj, c->stream, g, h.badj, h.rl16, a, c->bt.iw, (double *)nullptr, c->ld);
 }
@@ -612,7 +659,7 @@ static void latb_launch_cg_adjoint(gh_ctx *c, const double *Rt, const ghk::LatbC
     const LatticeHost &h = *c->lat;
     const ghk::LatGeom &g = h.g;
     const int64_t n16 = c->N * ghk::CB;
-    ghk::latb_gather_r_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, Rt, h.rl16);
+    ghk::latb_gather_r_blocks_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream>>>(g, lattice_r_blocks(c), Rt, h.rl16);
     hipLaunchKernelGGL(ghk::latb_pass_kernel<ghk::LATB_CG>, dim3((unsigned)h.bgx_adj, (unsigned)g.nz), dim3(ghk::LATB_THREADS),
                        h.blds_adj, c->stream, g, h.badj, h.rl16, a, c->bt.iw, (double *)nullptr, c->ld);
 }

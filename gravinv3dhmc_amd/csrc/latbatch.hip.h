@@ -98,18 +98,8 @@ __global__ void __launch_bounds__(256) latb_gather_x_kernel(LatGeom l, const dou
     xl16[(row * l.nyp + b) * CB + c] = X[j * CB + c] * iw[j];
 }
 
-// Rt (patch-transposed residuals of the batch, the caller's observation order) -> rl16[px][qyp][16] (zero beyond qy)
-__global__ void __launch_bounds__(256) latb_gather_r_kernel(LatGeom l, const double *Rt, double *rl16)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t e = t >> 4;
-    const int c = (int)(t & 15);
-    if (e >= (int64_t)l.px * l.qy) return;
-    const int p = (int)(e / l.qy), q = (int)(e - (int64_t)p * l.qy);
-    rl16[((int64_t)p * l.qyp + q) * CB + c] = Rt[rt_offset(l.obs_of[e], c)];
-}
-
-// Row blocks: rl16[b][p][q][c] = w_b Rt[b Nb + obs_of[p, q]][c] (zero beyond qy)
+// Rt (patch-transposed residuals of the batch, the caller's observation order) -> rl16[b][p][q][c] = w_b Rt[b Nb +
+// obs_of[p, q]][c] (zero beyond qy), the bl.n blocks of r; the single table: one block of weight 1, rl16[px][qyp][16]
 __global__ void __launch_bounds__(256) latb_gather_r_blocks_kernel(LatGeom l, LatBlocks bl, const double *Rt, double *rl16)
 {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;

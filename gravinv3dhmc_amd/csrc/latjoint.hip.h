@@ -10,8 +10,8 @@
 // share their rows: lat_pass_kernel<FWD, false, true> is the pass whose layer L reads and writes the observation
 // block L / nz alone (lattice.hip.h, "Block-diagonal layers").  A 2 x 2 table of row blocks with two zero tables would
 // run twice the passes over twice the memory for the same sums.  The gathers and the column norms run on the 2 nz
-// layers as they are (lat_gather_x_kernel, lat_colnorm_kernel; lat_gather_r_blocks_kernel with the blocks ld apart
-// and the weights {1, s}).
+// layers as they are (lat_gather_x_kernel; lat_colnorm_blocks_kernel with its ONE table of weight 1; lat_gather_r_blocks_kernel
+// with its TWO blocks of r ld apart and the weights {1, s}): host_lattice.h, the LAT_JOINT row.
 //
 // What is new here is the data balance s = std(A_gz) / std(A_tf): the population standard deviations over all n m
 // entries of each unweighted block, which the dense store reads off its columns (joint_std_kernel) and the table has

@@ -77,7 +77,8 @@ struct LatGeom {
     double *xl;           // [nz][nx][nyp]: x / wm in lattice order (zero beyond ny)
 };
 
-// The row blocks of the multi-component store on the table: n blocks of Nb observations, block b times w[b]
+// The n blocks of r, Nb observations apart, block b times w[b] (host_lattice.h: lattice_r_blocks) -- or, for the column
+// norms, the n tables of a layer (lattice_tables).  The scalar table: one of weight 1
 struct LatBlocks {
     int n;
     int64_t Nb;
@@ -117,31 +118,8 @@ __global__ void __launch_bounds__(256) lat_fill_kernel(MfGeom g, LatGeom l, doub
     }
 }
 
-// wm_j = (sum over the cell's px x qy window of T^2)^wf: thread = cell in lattice order
-__global__ void __launch_bounds__(256) lat_colnorm_kernel(LatGeom l, double wf, double *wm)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (int64_t)l.nz * l.nx * l.ny) return;
-    const int b = (int)(e % l.ny), a = (int)((e / l.ny) % l.nx), k = (int)(e / ((int64_t)l.ny * l.nx));
-    const double *Tk = l.T + (int64_t)k * l.U * l.V;
-    double s = 0.0;
-    for (int p = 0; p < l.px; ++p) {
-        const double *row = Tk + (int64_t)(p - a + l.nx - 1) * l.V + (l.ny - 1 - b);
-        for (int q = 0; q < l.qy; ++q) s += row[q] * row[q];
-    }
-    wm[l.cell_of[e]] = (wf == 0.5) ? sqrt(s) : pow(s, wf);
-}
-
-// r (the caller's order) -> rl
-__global__ void __launch_bounds__(256) lat_gather_r_kernel(LatGeom l, const double *r)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (int64_t)l.px * l.qy) return;
-    const int p = (int)(e / l.qy), q = (int)(e - (int64_t)p * l.qy);
-    l.rl[(int64_t)p * l.qyp + q] = r[l.obs_of[e]];
-}
-
-// Row blocks: wm_j = (sum_b w_b^2 sum over the window of T_b^2)^wf, blocks ascending, each block's sum as above
+// wm_j = (sum_b w_b^2 sum over the cell's px x qy window of T_b^2)^wf: thread = cell in lattice order, the bl.n tables of
+// its layer ascending.  One table of weight 1 is the single table's norm bit for bit: 0 + (1 * 1) s == s, fused or not
 __global__ void __launch_bounds__(256) lat_colnorm_blocks_kernel(LatGeom l, LatBlocks bl, double wf, double *wm)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -160,7 +138,7 @@ __global__ void __launch_bounds__(256) lat_colnorm_blocks_kernel(LatGeom l, LatB
     wm[l.cell_of[e]] = (wf == 0.5) ? sqrt(st) : pow(st, wf);
 }
 
-// Row blocks: rl[b][p][q] = w_b r[b Nb + obs_of[p, q]]
+// r (the caller's order) -> rl[b][p][q] = w_b r[b Nb + obs_of[p, q]], the bl.n blocks of r (one block of weight 1: r itself)
 __global__ void __launch_bounds__(256) lat_gather_r_blocks_kernel(LatGeom l, LatBlocks bl, const double *r)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;

@@ -104,7 +104,7 @@ def gather_x(X16, iw, dims, col):
 
 
 def gather_r(Rt, dims, ool):
-    """latb_gather_r_kernel: rl16[px][qyp][16], zero beyond qy"""
+    """latb_gather_r_blocks_kernel with one block of weight 1: rl16[px][qyp][16], zero beyond qy"""
     nx, ny, nz, px, qy = dims
     qyp = (qy + 7) // 8 * 8
     rl = np.zeros((px, qyp, CB))

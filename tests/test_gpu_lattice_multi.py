@@ -10,7 +10,8 @@ data, one table T[b][k][u][v] per component, no limit on the stacked rows.
   3. potential and chain against multicomp_host.MultiProblem, the four regularisers; piped run_chain, stateless
      leapfrog and a second engine bit for bit; the dense multi-component engine to 1e-10;
   4. beyond 16384 stacked rows: the per-block epilogue against single-component dense engines;
-  5. C = 1 with weight 1 against the single-component table engine;
+  5. C = 1 with weight 1 against the single-component table engine; one block of gz at weight 1 against the scalar gz
+     table bit for bit: table, weights, forward, adjoint (the gathers and column norms are written once, for n blocks);
   6. MultiComponentModule(translation_invariant=True) against the dense module, HMCSample with the posterior stream;
   7. the module past the dense form's limit (2 x 100 x 100 rows) against GravMagModule(translation_invariant=True);
   8. refusals.
@@ -313,6 +314,38 @@ def test_one_block_of_weight_one_is_the_single_component_table_engine(G, monkeyp
         outs.append(res)
     for (a1, o1, x1), (a2, o2, x2) in zip(*outs):
         assert bool(a1) == bool(a2) and relmax(o1, o2) <= 1e-12 and relmax(x1, x2) <= 1e-12
+    mc.close()
+    one.close()
+
+
+#: 5 x 7 x 2 under 6 x 9: qy and ny no multiples of 8, N = 54 far below a workgroup; 9 x 11 x 2 under 17 x 19: N = 323
+#: reaches the gather's second workgroup with a ragged tail
+UNIT_BLOCK_SHAPES = {"54 points": dict(cells=(5, 7, 2), obs=(6, 9)), "323 points": dict(cells=(9, 11, 2), obs=(17, 19))}
+
+
+@pytest.mark.parametrize("name", sorted(UNIT_BLOCK_SHAPES))
+def test_single_block_of_unit_weight_is_the_scalar_table(G, name):
+    """One row block of gz at weight 1.0 is the scalar gz table, bit for bit: 1.0 * r == r in the gather of r, and
+    0.0 + (1.0 * 1.0) * s == s in the column norms, contracted to an FMA or not.  The table's gathers and column norms
+    are written once, for n blocks, on this property."""
+    from gravinv3dhmc_amd import _lib
+    from lattice_cases import geometry
+    obs, b6 = geometry(**UNIT_BLOCK_SHAPES[name])
+    n, M = obs.shape[1], b6.shape[0]
+    one = G.Engine(n, M)
+    one.set_translation_invariant(True)
+    one.set_obs(*[np.ascontiguousarray(v) for v in obs])
+    one.set_cells(b6, _lib.CELL_PRISM)
+    one.build_G()
+    mc = multi_engine(G, obs, b6, ("gz",), (1.0,), True)
+    assert one.translation_invariant_info()["on"] and mc.translation_invariant_info()["on"]
+    assert np.array_equal(mc.translation_invariant_table()[0], one.translation_invariant_table())
+    wm = one.weight(0.5)
+    assert np.array_equal(mc.weight(0.5), wm)
+    rng = np.random.default_rng(17)
+    x, r = rng.uniform(-1, 1, M) * wm, rng.normal(size=n)
+    assert np.array_equal(mc.forward(x), one.forward(x))
+    assert np.array_equal(mc.adjoint(r), one.adjoint(r))
     mc.close()
     one.close()
 
